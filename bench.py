@@ -94,7 +94,13 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-stage-leg", action="store_true", help="skip the short pass of the stage leg (pixels -> matches.*) appended to the default line as `stage_leg`")
     ap.add_argument("--no-opt-in", action="store_true", help="skip the extra (untimed-region) pass on the opt-in fast path of the config")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the graphs the last timed step returned as DIR/<name>.npy (see dump_outputs); not with --config stage")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and a.config == "stage":
+        ap.error("--dump-outputs covers the collection configs; the stage leg writes its results as files")
     if a.config == "stage":
         return stage_main(a, cpu_baseline_fn=stage_cpu_baseline)
     cfg = dict(CONFIGS[a.config])
@@ -239,6 +245,7 @@ def main():
         elapsed = float(t.item())
 
     value = job_pairs * a.steps / elapsed
+    dumped = dump_outputs(a.dump_outputs, {"putative": full[0], "F": full[1]}) if (a.dump_outputs and rank == 0) else None
     # one more full pass, measured from the host arrays (never `value`)
     fence()
     t0h = time.perf_counter()
@@ -326,11 +333,59 @@ def main():
                                         "the GUI's default arm); profiles/r03_end_bench_stage.json")
         except Exception as e:                    # the headline stands on its own
             out["stage_leg"] = {"error": str(e)[:300]}
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if rank == 0:
         print(json.dumps(out))
     if world > 1:
         td.barrier()
         td.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6        # the .npy files of a dump in all, headers included
+
+
+def _pair_draw(pairs):
+    """a fixed pseudo-random number in [0, 1) per pair (I, J) (splitmix64 of I * 2^32 + J): a sample drawn with it keeps the same
+    pairs whatever else a graph holds, so that the dumps of two builds stay comparable pair by pair"""
+    with np.errstate(over="ignore"):
+        z = (pairs[:, 0].astype(np.uint64) << np.uint64(32)) | pairs[:, 1].astype(np.uint64)
+        z = z + np.uint64(0x9E3779B97F4A7C15)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z = z ^ (z >> np.uint64(31))
+    return (z >> np.uint64(11)).astype(np.float64) / float(1 << 53)
+
+
+def dump_outputs(out_dir, graphs):
+    """What the last timed step returned, the reassembled graphs {name: api.Graph}, as out_dir/<name>_{pairs,offsets,matches}.npy:
+    pairs (view ids) and matches (feature indices) in float32, where every index below 2^24 is exact; offsets in float64.  Above
+    DUMP_LIMIT_BYTES in all, every graph is cut to the pairs whose _pair_draw falls below one fraction (offsets rebuilt for the
+    sample).  Returns what was written, for the JSON line."""
+    arrays = {n: (g.pairs, g.offsets.astype(np.int64), g.matches) for n, g in graphs.items()}
+    for p, _, m in arrays.values():
+        assert (p.size == 0 or int(p.max()) < 1 << 24) and (m.size == 0 or int(m.max()) < 1 << 24), "index not exact in float32"
+
+    def nbytes(arr):
+        return sum(p.size * 4 + o.size * 8 + m.size * 4 + 3 * 128 for p, o, m in arr.values())      # (128 B: one .npy header)
+    frac, sampled = 1.0, dict(arrays)
+    while nbytes(sampled) > DUMP_LIMIT_BYTES:
+        frac *= 0.9 * DUMP_LIMIT_BYTES / nbytes(sampled)
+        sampled = {}
+        for n, (p, o, m) in arrays.items():
+            keep = np.flatnonzero(_pair_draw(p) < frac)
+            counts = o[keep + 1] - o[keep]
+            rows = np.concatenate([np.arange(o[k], o[k + 1]) for k in keep]) if keep.size else np.zeros(0, np.int64)
+            sampled[n] = (p[keep], np.concatenate([[0], np.cumsum(counts)]), m[rows])
+    os.makedirs(out_dir, exist_ok=True)
+    files = {}
+    for n, (p, o, m) in sampled.items():
+        for what, arr in (("pairs", p.astype(np.float32)), ("offsets", o.astype(np.float64)), ("matches", m.astype(np.float32))):
+            np.save(os.path.join(out_dir, f"{n}_{what}.npy"), arr)
+            files[f"{n}_{what}"] = list(arr.shape)
+    return {"dir": out_dir, "files": files, "bytes": nbytes(sampled), "pairs_fraction": frac,
+            "note": "the graphs the last timed step returned (pairs / matches float32, offsets float64)"
+                    + ("" if frac == 1.0 else f"; a fixed per-pair sample (_pair_draw < {frac:.6g}) to stay within {DUMP_LIMIT_BYTES // 10**6} MB")}
 
 
 def ann_vs_exhaustive(ctx, cfg, kp, mine, hd, ann_value):

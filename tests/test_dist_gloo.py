@@ -43,7 +43,7 @@ def _worker(rank, world, port, tmpdir):
     local = api.Graph.from_csr(mine, offs, matches)
     full = dist.all_gather_graph(local, device="cpu")
     np.savez(os.path.join(tmpdir, f"rank{rank}.npz"), pairs=full.pairs, offsets=full.offsets, matches=full.matches)
-    td.barrier()
+    td.monitored_barrier()                                # (a host-side barrier: td.barrier() would probe for, and open, a GPU)
     td.destroy_process_group()
 
 
@@ -72,7 +72,7 @@ def _worker8(rank, world, port, tmpdir, n_img):
     full, full2 = dist.all_gather_graphs([put, second], device="cpu")
     np.savez(os.path.join(tmpdir, f"rank{rank}.npz"), pairs=full.pairs, offsets=full.offsets, matches=full.matches,
              pairs2=full2.pairs, matches2=full2.matches, mine=np.array([mine.shape[0]]))
-    td.barrier()
+    td.monitored_barrier()                                # (a host-side barrier: td.barrier() would probe for, and open, a GPU)
     td.destroy_process_group()
 
 

@@ -129,10 +129,15 @@ def test_bench_contract_one_and_two_ranks(tmp_path):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--steps", "1", "--warmup", "1", "--feat", "1024", "--no-cpu-baseline"]
-    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--images", "17"] + common,
+    one = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--images", "17", "--dump-outputs", str(tmp_path)] + common,
                          capture_output=True, text=True, timeout=300)
     assert one.returncode == 0, one.stderr[-2000:]
     j1 = json.loads(one.stdout.strip().splitlines()[-1])
+    # --dump-outputs: the graphs of the timed step, whole at this size
+    assert j1["dump_outputs"]["pairs_fraction"] == 1.0
+    for name in ("putative", "F"):
+        p, o, m = (np.load(tmp_path / f"{name}_{w}.npy") for w in ("pairs", "offsets", "matches"))
+        assert p.shape == (j1["detail"][f"{name}_pairs"], 2) and m.shape == (j1["detail"][f"{name}_matches"], 2) and o[-1] == len(m)
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
                 "dtype", "data", "config", "roofline"):
         assert key in j1, key
@@ -183,12 +188,12 @@ def test_bench_c5_two_ranks_reassemble_the_single_rank_graph():
         assert j2["detail"][k] == j1["detail"][k], k
 
 
-@pytest.mark.parametrize("config,images,feat", [("c2", 40, 512), ("c2", 6, 512), ("c5", 20, 1024), ("c5", 6, 1024)])
-def test_bench_eight_ranks_reassemble_the_single_rank_graphs(config, images, feat):
-    """N = 8 -- the size of the driver's scaling run -- before an 8-GPU node shows up: eight torch.distributed ranks share this
-    box's GPU (R3DM_SHARE_GPU=1, graphs through gloo; the RCCL branch differs in the tensors' device only).  40 / 20 images:
-    every rank owns rows of I; 6 images: five rows for eight ranks, three ranks run EMPTY shards through match, filter and the
-    exchange.  The reassembled graphs must be those of the single-rank run, byte for byte (detail.graphs_sha16)."""
+@pytest.mark.parametrize("config,images,feat", [("c2", 40, 512), ("c2", 3, 512), ("c5", 20, 1024), ("c5", 3, 1024)])
+def test_bench_four_ranks_reassemble_the_single_rank_graphs(config, images, feat):
+    """N = 4: four torch.distributed ranks share this box's GPU (R3DM_SHARE_GPU=1, graphs through gloo; the RCCL branch differs in
+    the tensors' device only).  Four is the most ranks that may share one GPU: with the launcher and this test process, six processes
+    hold it open.  40 / 20 images: every rank owns rows of I; 3 images: two rows for four ranks, two ranks run EMPTY shards through
+    match, filter and the exchange.  The reassembled graphs must be those of the single-rank run, byte for byte (detail.graphs_sha16)."""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     common = ["--config", config, "--steps", "1", "--warmup", "0", "--images", str(images), "--feat", str(feat), "--no-cpu-baseline", "--no-opt-in"]
@@ -197,22 +202,22 @@ def test_bench_eight_ranks_reassemble_the_single_rank_graphs(config, images, fea
     j1 = json.loads(one.stdout.strip().splitlines()[-1])
     env = dict(os.environ, R3DM_SHARE_GPU="1", R3DM_DIST_BACKEND="gloo")
     port = 28100 + os.getpid() % 900
-    eight = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8",
-                            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "8"] + common,
-                           capture_output=True, text=True, timeout=600, env=env)
-    assert eight.returncode == 0, eight.stderr[-3000:]
-    j8 = json.loads([l for l in eight.stdout.strip().splitlines() if l.startswith("{")][-1])
+    four = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
+                           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "4"] + common,
+                          capture_output=True, text=True, timeout=600, env=env)
+    assert four.returncode == 0, four.stderr[-3000:]
+    j4 = json.loads([l for l in four.stdout.strip().splitlines() if l.startswith("{")][-1])
     n_pairs = images * (images - 1) // 2
-    assert j8["n_gpus"] == 8 and j8["config"]["pairs"] == n_pairs and j8["scaling"] == "strong"
-    assert j8["detail"]["graphs_sha16"] == j1["detail"]["graphs_sha16"]
+    assert j4["n_gpus"] == 4 and j4["config"]["pairs"] == n_pairs and j4["scaling"] == "strong"
+    assert j4["detail"]["graphs_sha16"] == j1["detail"]["graphs_sha16"]
     for k in ("putative_pairs", "putative_matches", "F_pairs", "F_matches"):
-        assert j8["detail"][k] == j1["detail"][k], k
+        assert j4["detail"][k] == j1["detail"][k], k
     assert j1["detail"]["putative_matches"] > 0
 
 
 @pytest.mark.parametrize("config,extra", [("c3", ["--images", "10", "--feat", "2048"]), ("liop144", ["--images", "10", "--feat", "2048"]),
                                           ("c5", ["--images", "6", "--feat", "4096"]), ("c4", ["--images", "24", "--feat", "1024", "--emulate-world", "8"])])
-def test_bench_config_legs(config, extra):
+def test_bench_config_legs(oracle, config, extra):
     """every BASELINE config has a bench leg with its own roofline and a CPU baseline that doubles as a parity check"""
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -237,8 +242,13 @@ def test_bench_config_legs(config, extra):
         assert set(j["roofline"]["bounds"]) == {"valu_issue", "gathered_bytes_over_hbm"}
     if config == "c4":
         assert "shard 0 of 8" in j["config"]["workload"] and j["config"]["pairs"] < 24 * 23 // 2
-        assert cb["optimised_cpu"]["reference_built_index_mismatches"] == 0 and cb["optimised_cpu"]["reference_built_distance_mismatches"] == 0
-        assert cb["optimised_cpu"]["reference_built_rows_checked"] > 0
+        # the reference-built second opinion runs where oracle/_ref was built from the reference tree; the same comparison at full
+        # size is pinned everywhere by tests/golden/knn2_c2_fullsize.npz (test_golden_fixtures.py)
+        if oracle.ref_lib() is not None:
+            assert cb["optimised_cpu"]["reference_built_index_mismatches"] == 0 and cb["optimised_cpu"]["reference_built_distance_mismatches"] == 0
+            assert cb["optimised_cpu"]["reference_built_rows_checked"] > 0
+        else:
+            assert "optimised_cpu" not in cb
 
 
 def test_graph_exchange_over_rccl_single_rank(tmp_path):
