@@ -219,9 +219,8 @@ int ensure_layouts_image(r3dm_ctx* c, HostImage& h, uint32_t want)
         }
         return R3DM_OK;
     }
-    want &= (kLayRows | kLayBf16 | kLaySplit | kLayCounts);
-    if (want & (kLayCounts | kLaySplit)) want |= kLayRows;
-    if ((want & kLayCounts) && !(h.dtype == R3DM_F32 && h.n && h.dim <= 256)) want &= ~kLayCounts;      // never votes x scale: counts_ok stays false
+    want = with_implied_rows(want & (kLayRows | kLayBf16 | kLaySplit | kLayCounts));
+    if (!counts_eligible(h.dtype, h.n, h.dim)) want &= ~kLayCounts;
     const uint32_t todo = want & ~h.have;
     if (!todo) return R3DM_OK;
     const uint32_t GB = (h.G + 1) / 2;
@@ -281,27 +280,25 @@ int ensure_layouts(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t want, bool
     if (rc != R3DM_OK) return rc;
     // verdict words of count-tile checks launched here: one per slot, in scratch (an entry republished behind the kernel would overwrite its own)
     std::vector<uint32_t> checked;
+    // a mounted index: its layouts belong to the index and are added there, under its lock (searches from other contexts run on the
+    // buffers it already holds).  The lock is taken before anything of the index is read and held to the end of the call: only one
+    // index is ever mounted by a call (r3dm_index_knn2), so no two contexts can take two index locks in opposite orders.
     std::vector<std::unique_lock<std::mutex>> locks;
     for (uint32_t s : slots) {
         HostImage& m = *c->imgs[s];
         HostImage* h = &m;
         if (m.borrowed && m.owner) {
-            // a mounted index: its layouts belong to the index and are added there, under its lock (searches from other contexts run
-            // on the buffers it already holds)
-            uint32_t w = want;
-            if (m.dtype != R3DM_BIN && (w & (kLayCounts | kLaySplit))) w |= kLayRows;
+            std::unique_lock<std::mutex> lk(m.owner->mu);
+            const uint32_t w = with_implied_rows(want);
             if ((w & ~m.owner->img.have) == 0 && (w & ~m.have) == 0) continue;
-            locks.emplace_back(m.owner->mu);
+            locks.push_back(std::move(lk));
             h = &m.owner->img;
         }
         const uint32_t before = h->have;
         rc = ensure_layouts_image(c, *h, want);
         if (rc != R3DM_OK) return rc;
         if ((h->have & ~before) & kLayCounts) checked.push_back(s);
-        if (h != &m) {
-            m.rows = h->rows; m.tiled16 = h->tiled16; m.tiledh = h->tiledh; m.tiledc = h->tiledc; m.tiledp = h->tiledp; m.cscale = h->cscale; m.cquad = h->cquad;
-            m.cperm = h->cperm; m.tiled8 = h->tiled8; m.norms = h->norms; m.have = h->have; m.counts_ok = h->counts_ok;
-        }
+        if (h != &m) m.mount(m.owner);
         if (h->have != before || h != &m) { rc = publish_entry(c, s); if (rc != R3DM_OK) return rc; }
     }
     if (!checked.empty()) {
@@ -376,12 +373,12 @@ static void ring_fill(const UploadRing& r, int s, const ViewSrc& v, bool desc_fr
 // Leaves the stream with: [DMA of the slot] -> staging kernel(s) -> the slot's event.  Nothing is waited for.
 static int stage_enqueue(r3dm_ctx* c, uint32_t slot, const ViewSrc& v, int s, int kind_desc, const void* dev_desc, int kind_xy, const void* dev_xy, bool filled, bool* copy_wait_out)
 {
+    // the table first: growing it reads back the statistics of pending views, and this slot's must still be its old tenant's
+    int rc = table_reserve(c, c->imgs.size());
+    if (rc != R3DM_OK) return rc;
     HostImage& h = *c->imgs[slot];
     UploadRing& r = c->ring;
-    h.view_id = v.view_id; h.n = v.n; h.dim = v.dim; h.dtype = v.dtype; h.width = v.width; h.height = v.height;
-    h.has_xy = (v.xy != nullptr); h.has_dup = false; h.live = true;
-    h.G = 0; h.n_tiles = 0; h.words = 0; h.ann_K = 0; h.hnsw_M = 0; h.mrpt_trees = 0; h.compact_ready = false;
-    h.have = 0; h.stats_valid = false; h.counts_ok = false; h.split_k = 0; h.max_abs = 0.0f; h.not_integer = true; h.has_negative = true;
+    h.new_tenant(v.view_id, v.n, v.dim, v.dtype, v.width, v.height, v.xy != nullptr);
     const uint32_t n = v.n, dim = v.dim;
     const size_t dbytes = desc_bytes_of(v), xy_off = ring_xy_offset(v), xy_bytes = v.xy ? (size_t)n * 8 : 0;
     const bool desc_ring = kind_desc == kSrcPageable && n, xy_ring = v.xy && kind_xy == kSrcPageable && n;
@@ -417,8 +414,6 @@ static int stage_enqueue(r3dm_ctx* c, uint32_t slot, const ViewSrc& v, int s, in
         if (v.xy) xy_src = (const float*)(base + xy_off);
     } else c->n_direct_uploads += 1;
 
-    int rc = table_reserve(c, c->imgs.size());
-    if (rc != R3DM_OK) return rc;
     ImgDev* entry_dev = c->d_imgs.as<ImgDev>() + slot;
     StageViewArgs A{};
     A.n = n; A.dim = dim;
@@ -443,7 +438,7 @@ static int stage_enqueue(r3dm_ctx* c, uint32_t slot, const ViewSrc& v, int s, in
         // (the bf16 tiles of r3dm_set_integer_mfma are never staged here: whether a view is integer-valued is a statistic of the very
         //  kernel this call queues -- the facade switches every exact path on and registers LIOP rows -- so they wait for a first match call
         //  that can use them, 12 us per view)
-        if (c->split_mfma) eager |= kLayRows | ((v.dtype == R3DM_F32 && n && dim <= 256) ? kLayCounts : 0u);
+        if (c->split_mfma) eager |= kLayRows | (counts_eligible(v.dtype, n, dim) ? kLayCounts : 0u);
     }
     if (v.dtype == R3DM_BIN) {
         h.words = (dim + 3) / 4;
@@ -522,15 +517,26 @@ int stage_into_slot(r3dm_ctx* c, uint32_t slot, uint32_t view_id, uint32_t width
     return R3DM_OK;
 }
 
-static uint32_t slot_for_view(r3dm_ctx* c, uint32_t view_id)
+// stage(slot) into the slot of the view's id; a new id gets a new slot at the end of the table (a spare view's buffers when there is one)
+// and exists only once its view is staged: if that fails, the id is withdrawn and the slot goes back to the spares
+template <class F>
+static int stage_view(r3dm_ctx* c, uint32_t view_id, F&& stage)
 {
     auto it = c->slot_of.find(view_id);
-    if (it != c->slot_of.end()) return it->second;
+    if (it != c->slot_of.end()) return stage(it->second);
     const uint32_t slot = (uint32_t)c->imgs.size();
-    if (!c->spare.empty()) { c->imgs.emplace_back(std::move(c->spare.back())); c->spare.pop_back(); }      // buffers of a cleared view
-    else { c->imgs.emplace_back(new HostImage()); c->imgs.back()->use_arena(&c->arena); }
+    if (!c->spare.empty()) { c->imgs.push_back(std::move(c->spare.back())); c->spare.pop_back(); }
+    else { c->imgs.push_back(std::unique_ptr<HostImage>(new HostImage())); c->imgs.back()->use_arena(&c->arena); }
     c->slot_of[view_id] = slot;
-    return slot;
+    const int rc = stage(slot);
+    if (rc != R3DM_OK) {
+        c->pending_stats.erase(std::remove(c->pending_stats.begin(), c->pending_stats.end(), slot), c->pending_stats.end());
+        c->slot_of.erase(view_id);
+        c->imgs.back()->clear();
+        c->spare.push_back(std::move(c->imgs.back()));
+        c->imgs.pop_back();
+    }
+    return rc;
 }
 
 static int r3dm_set_image_impl(r3dm_ctx* c, uint32_t view_id, uint32_t width, uint32_t height,
@@ -541,7 +547,7 @@ static int r3dm_set_image_impl(r3dm_ctx* c, uint32_t view_id, uint32_t width, ui
     int rc = check_view(c, v);
     if (rc != R3DM_OK) return rc;
     R3DM_HIP(c, hipSetDevice(c->device));
-    return stage_into_slot(c, slot_for_view(c, view_id), view_id, width, height, desc, n, dim, dtype, xy);
+    return stage_view(c, view_id, [&](uint32_t slot) { return stage_into_slot(c, slot, view_id, width, height, desc, n, dim, dtype, xy); });
 }
 
 extern "C" int r3dm_set_image(r3dm_ctx* c, uint32_t view_id, uint32_t width, uint32_t height,
@@ -560,17 +566,21 @@ static int r3dm_set_images_impl(r3dm_ctx* c, const r3dm_view_desc* views, uint32
     std::vector<ViewSrc> vs(n_views);
     std::vector<int> kd(n_views), kx(n_views);
     std::vector<const void*> dd(n_views), dx(n_views);
-    std::vector<uint32_t> slots(n_views);
+    std::vector<uint32_t> new_ids;
     for (uint32_t k = 0; k < n_views; ++k) {
         const r3dm_view_desc& w = views[k];
         vs[k] = ViewSrc{w.view_id, w.width, w.height, w.desc, w.n, w.dim, (r3dm_dtype)w.dtype, w.xy};
         int rc = check_view(c, vs[k]);
         if (rc != R3DM_OK) return rc;
         kd[k] = source_kind(w.desc, &dd[k], c->device); kx[k] = source_kind(w.xy, &dx[k], c->device);
+        if (!c->slot_of.count(w.view_id)) new_ids.push_back(w.view_id);
     }
-    for (uint32_t k = 0; k < n_views; ++k) slots[k] = slot_for_view(c, vs[k].view_id);
-    int rc = table_reserve(c, c->imgs.size());
+    std::sort(new_ids.begin(), new_ids.end());
+    new_ids.erase(std::unique(new_ids.begin(), new_ids.end()), new_ids.end());
+    int rc = table_reserve(c, c->imgs.size() + new_ids.size());      // (each view's slot is made just before it is staged)
     if (rc != R3DM_OK) return rc;
+    c->imgs.reserve(c->imgs.size() + new_ids.size());
+    c->slot_of.reserve(c->slot_of.size() + new_ids.size());
     UploadRing& r = c->ring;
     constexpr int S = UploadRing::kSlots;
     // every slot's page-locked buffer sized for the largest view before the helpers start (they only memcpy)
@@ -621,7 +631,7 @@ static int r3dm_set_images_impl(r3dm_ctx* c, const r3dm_view_desc* views, uint32
         if (helpers) { while (state[k].load(std::memory_order_acquire) != 1) std::this_thread::yield(); filled = true; }
         else if (r.busy[s]) { if (hipEventSynchronize(r.ev[s]) != hipSuccess) { c->err = "hipEventSynchronize"; rc = R3DM_ERR_HIP; break; } r.busy[s] = false; }
         bool wc = false;
-        rc = stage_enqueue(c, slots[k], vs[k], s, kd[k], dd[k], kx[k], dx[k], filled, &wc);
+        rc = stage_view(c, vs[k].view_id, [&](uint32_t slot) { return stage_enqueue(c, slot, vs[k], s, kd[k], dd[k], kx[k], dx[k], filled, &wc); });
         if (wc) last_copy_slot = s;
         state[k].store(2, std::memory_order_release);
     }
@@ -698,20 +708,14 @@ extern "C" int r3dm_clear_images(r3dm_ctx* c)
     if (!c) return R3DM_ERR_INVALID;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
-    // the views are forgotten, their device buffers are kept for the next collection (a stage object that lives across runs, or a
-    // bench loop, registers views of the same sizes again and again: six hipMalloc per view were most of the registration time)
-    // Kept: the staging buffers of at most kSpareViews views (a collection larger than that gives the rest back at once).  Never kept:
-    // the per-view INDEX buffers (graph adjacency, compact row copies, HNSW arrays) -- they are rebuilt per collection and nothing
-    // reuses them as they stand, so a context that once held a 1000-view collection does not sit on their gigabytes.
+    // the views are forgotten, their layout buffers are kept for the next collection (a stage object that lives across runs, or a
+    // bench loop, registers views of the same sizes again and again: six hipMalloc per view were most of the registration time) --
+    // those of at most kSpareViews views: a collection larger than that gives the rest back at once (HostImage::clear / release)
     constexpr size_t kSpareViews = 256;
     for (auto& im : c->imgs) {
         if (!im) continue;
-        if (im->borrowed) { im->release(); continue; }
-        if (c->spare.size() >= kSpareViews) { im->release(); continue; }
-        im->ann_adj.release(); im->ann_deg.release(); im->ann_rows16.release(); im->ann_rows8.release();
-        im->hnsw_l0.release(); im->hnsw_up_off.release(); im->hnsw_up.release();
-        im->mrpt_R.release(); im->mrpt_RT.release(); im->mrpt_splits.release(); im->mrpt_leaves.release(); im->mrpt_lf.release();
-        im->live = false; im->has_K = false; im->ann_K = 0; im->hnsw_M = 0; im->mrpt_trees = 0; im->compact_ready = false; im->n = 0; im->counts_ok = false; im->have = 0; im->stats_valid = false;
+        if (im->borrowed || c->spare.size() >= kSpareViews) { im->release(); continue; }
+        im->clear();
         c->spare.push_back(std::move(im));
     }
     c->imgs.clear();

@@ -297,16 +297,8 @@ static int r3dm_match_pairs_hnsw_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uin
         if (rc != R3DM_OK) return rc;
         start = end;
     }
-    start = 0;
-    while (start < small_jobs.size()) {
-        size_t end = start;
-        const HostImage& F = *c->imgs[small_jobs[start].sI];
-        while (end < small_jobs.size() && c->imgs[small_jobs[end].sI]->dtype == F.dtype && c->imgs[small_jobs[end].sI]->dim == F.dim) ++end;
-        std::vector<PairJob> batch(small_jobs.begin() + start, small_jobs.begin() + end);
-        rc = run_match_batch(c, batch, R, &gs, nullptr, nullptr);
-        if (rc != R3DM_OK) return rc;
-        start = end;
-    }
+    rc = run_scanned_pairs(c, small_jobs, R, &gs);
+    if (rc != R3DM_OK) return rc;
     rc = merge_parts_keep_mirror(ga, gs, out);
     c->stats.ms_wall_match = now_ms() - t_call;
     return rc;
@@ -327,63 +319,49 @@ static int hnsw_knn2_common(r3dm_ctx* c, const float* dataset, uint32_t n_datase
     if (!hnsw_dim_ok(dim)) { c->err = "HNSW matching needs descriptors of length 64 / 128 / 144 / 256"; return R3DM_ERR_UNSUPPORTED; }
     if (n_dataset > (1u << 18)) { c->err = "HNSW matching: more than 262,144 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
     R3DM_HIP(c, hipSetDevice(c->device));
-    const uint32_t s0 = (uint32_t)c->imgs.size();
-    c->imgs.emplace_back(new HostImage());
-    c->imgs.emplace_back(new HostImage());
-    int rc = stage_into_slot(c, s0, 0, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s0 + 1, 1, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
-    const r3dm_stats keep = c->stats;
-    if (rc == R3DM_OK) {
-        HostImage& h = *c->imgs[s0];
-        if (ix) {                                              // an index handed over as arrays (e.g. written by hnswlib itself)
-            const uint32_t M = ix->M;
-            bool ok = M >= 2 && M <= 32 && ix->links0 && ix->up_off && ix->enterpoint >= 0 && (uint32_t)ix->enterpoint < n_dataset &&
-                      ix->maxlevel >= 0 && (ix->up_rows == 0 || ix->up_links);
-            for (uint32_t i = 0; ok && i < n_dataset; ++i) {
-                const int32_t* l = ix->links0 + (size_t)i * (1 + 2 * M);
-                ok = l[0] >= 0 && (uint32_t)l[0] <= 2 * M && ix->up_off[i] >= 0 && ix->up_off[i] <= ix->up_off[i + 1] && (uint32_t)ix->up_off[i + 1] <= ix->up_rows;
-                for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
-            }
-            for (uint32_t r = 0; ok && r < ix->up_rows; ++r) {
-                const int32_t* l = ix->up_links + (size_t)r * (1 + M);
-                ok = l[0] >= 0 && (uint32_t)l[0] <= M;
-                for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
-            }
-            // the descent reads layer L of every row it reaches there: the rows linked on a layer must own that layer
-            if (ok && (uint32_t)(ix->up_off[ix->enterpoint + 1] - ix->up_off[ix->enterpoint]) < (uint32_t)ix->maxlevel) ok = false;
-            for (uint32_t i = 0; ok && i < n_dataset; ++i)
-                for (int32_t L = 1; ok && L <= ix->up_off[i + 1] - ix->up_off[i]; ++L) {
-                    const int32_t* l = ix->up_links + ((size_t)ix->up_off[i] + (uint32_t)(L - 1)) * (1 + M);
-                    for (int32_t k = 0; ok && k < l[0]; ++k) ok = ix->up_off[l[1 + k] + 1] - ix->up_off[l[1 + k]] >= L;
-                }
-            if (!ok) { c->err = "r3dm_hnsw_knn2_on_index: malformed index arrays"; rc = R3DM_ERR_INVALID; }
-            if (rc == R3DM_OK) {
-                hipError_t e = h.hnsw_l0.ensure((size_t)n_dataset * (1 + 2 * M) * 4);
-                if (e == hipSuccess) e = h.hnsw_up_off.ensure(((size_t)n_dataset + 1) * 4);
-                if (e == hipSuccess) e = h.hnsw_up.ensure((size_t)std::max(ix->up_rows, 1u) * (1 + M) * 4);
-                if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_l0.p, ix->links0, (size_t)n_dataset * (1 + 2 * M) * 4, hipMemcpyHostToDevice, c->stream);
-                if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_up_off.p, ix->up_off, ((size_t)n_dataset + 1) * 4, hipMemcpyHostToDevice, c->stream);
-                if (e == hipSuccess && ix->up_rows) e = hipMemcpyAsync(h.hnsw_up.p, ix->up_links, (size_t)ix->up_rows * (1 + M) * 4, hipMemcpyHostToDevice, c->stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-                if (e != hipSuccess) { c->err = std::string("r3dm_hnsw_knn2_on_index: ") + hipGetErrorString(e); rc = R3DM_ERR_HIP; }
-                h.hnsw_M = M; h.hnsw_up_rows = ix->up_rows; h.hnsw_enter = ix->enterpoint; h.hnsw_maxlevel = ix->maxlevel;
-            }
-        } else rc = ensure_hnsw_indices(c, {s0}, *hp);
-        if (rc == R3DM_OK) {
-            std::vector<PairJob> jobs{{0, 1, s0, s0 + 1}};
-            rc = run_hnsw_batch(c, jobs, 1.0f, hp->ef, nullptr, out_idx, out_dist);
+    PrivateSlots s(c, 2);
+    int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 1, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
+    if (rc != R3DM_OK) return rc;
+    CallCounters counters(c, {&r3dm_stats::n_ann_dist, &r3dm_stats::n_hnsw_launches, &r3dm_stats::n_hnsw_retries},
+                          {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
+    if (ix) {                                                  // an index handed over as arrays (e.g. written by hnswlib itself)
+        const uint32_t M = ix->M;
+        bool ok = M >= 2 && M <= 32 && ix->links0 && ix->up_off && ix->enterpoint >= 0 && (uint32_t)ix->enterpoint < n_dataset &&
+                  ix->maxlevel >= 0 && (ix->up_rows == 0 || ix->up_links);
+        for (uint32_t i = 0; ok && i < n_dataset; ++i) {
+            const int32_t* l = ix->links0 + (size_t)i * (1 + 2 * M);
+            ok = l[0] >= 0 && (uint32_t)l[0] <= 2 * M && ix->up_off[i] >= 0 && ix->up_off[i] <= ix->up_off[i + 1] && (uint32_t)ix->up_off[i + 1] <= ix->up_rows;
+            for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
         }
+        for (uint32_t r = 0; ok && r < ix->up_rows; ++r) {
+            const int32_t* l = ix->up_links + (size_t)r * (1 + M);
+            ok = l[0] >= 0 && (uint32_t)l[0] <= M;
+            for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
+        }
+        // the descent reads layer L of every row it reaches there: the rows linked on a layer must own that layer
+        if (ok && (uint32_t)(ix->up_off[ix->enterpoint + 1] - ix->up_off[ix->enterpoint]) < (uint32_t)ix->maxlevel) ok = false;
+        for (uint32_t i = 0; ok && i < n_dataset; ++i)
+            for (int32_t L = 1; ok && L <= ix->up_off[i + 1] - ix->up_off[i]; ++L) {
+                const int32_t* l = ix->up_links + ((size_t)ix->up_off[i] + (uint32_t)(L - 1)) * (1 + M);
+                for (int32_t k = 0; ok && k < l[0]; ++k) ok = ix->up_off[l[1 + k] + 1] - ix->up_off[l[1 + k]] >= L;
+            }
+        if (!ok) { c->err = "r3dm_hnsw_knn2_on_index: malformed index arrays"; return R3DM_ERR_INVALID; }
+        HostImage& h = *c->imgs[s[0]];
+        hipError_t e = h.hnsw_l0.ensure((size_t)n_dataset * (1 + 2 * M) * 4);
+        if (e == hipSuccess) e = h.hnsw_up_off.ensure(((size_t)n_dataset + 1) * 4);
+        if (e == hipSuccess) e = h.hnsw_up.ensure((size_t)std::max(ix->up_rows, 1u) * (1 + M) * 4);
+        if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_l0.p, ix->links0, (size_t)n_dataset * (1 + 2 * M) * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_up_off.p, ix->up_off, ((size_t)n_dataset + 1) * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && ix->up_rows) e = hipMemcpyAsync(h.hnsw_up.p, ix->up_links, (size_t)ix->up_rows * (1 + M) * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) { c->err = std::string("r3dm_hnsw_knn2_on_index: ") + hipGetErrorString(e); return R3DM_ERR_HIP; }
+        h.hnsw_M = M; h.hnsw_up_rows = ix->up_rows; h.hnsw_enter = ix->enterpoint; h.hnsw_maxlevel = ix->maxlevel;
+    } else {
+        rc = ensure_hnsw_indices(c, {s[0]}, *hp);
+        if (rc != R3DM_OK) return rc;
     }
-    const uint64_t evals = c->stats.n_ann_dist - keep.n_ann_dist, launches = c->stats.n_hnsw_launches - keep.n_hnsw_launches,
-                   retries = c->stats.n_hnsw_retries - keep.n_hnsw_retries;
-    const double ms_b = c->stats.ms_ann_build - keep.ms_ann_build, ms_s = c->stats.ms_ann_search - keep.ms_ann_search;
-    c->stats = keep;
-    c->stats.n_ann_dist = evals; c->stats.n_hnsw_launches = launches; c->stats.n_hnsw_retries = retries;
-    c->stats.ms_ann_build = ms_b; c->stats.ms_ann_search = ms_s;
-    (void)hipStreamSynchronize(c->stream);
-    c->imgs[s0]->release(); c->imgs[s0 + 1]->release();
-    c->imgs.pop_back(); c->imgs.pop_back();
-    return rc;
+    return run_hnsw_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, hp->ef, nullptr, out_idx, out_dist);
 }
 
 extern "C" int r3dm_hnsw_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,

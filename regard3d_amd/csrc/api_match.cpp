@@ -107,6 +107,59 @@ int merge_parts_keep_mirror(r3dm_graph& ga, r3dm_graph& gs, r3dm_graph** out)
     return rc;
 }
 
+// ---- the path of a batch: which kernels it runs on and which layouts they read, decided from the views' statistics and the switches
+// alone.  Every fast path is bit-exact only under its own condition on the views: those conditions are here and nowhere else.
+enum class BatchPath { kHammingScan, kHammingMfma, kF32Tiles, kIntegerTiles, kSplitPlanes, kCountTiles, kExactScan };
+struct BatchPlan { BatchPath path; uint32_t layouts; };                  // layouts: the kLay* bits the path reads
+struct PathSwitches { bool integer_mfma, split_mfma, hamming_mfma, count_tiles; };
+
+// same test as the kernels' exact_pair (kernels_match_common.hpp): key + ||q||^2 IS the reference distance, bit for bit
+static bool exact_pair(const HostImage& A, const HostImage& B, bool bf16)
+{
+    const float dpad = (float)(A.G * 8), mI = A.max_abs, mJ = B.max_abs;
+    return !A.not_integer && !B.not_integer &&
+           ((A.has_negative || B.has_negative)
+                ? dpad * (mI + mJ) * (mI + mJ) < 16777216.0f
+                : (2.0f * dpad * mI * mJ < 16777216.0f && dpad * mI * mI < 16777216.0f && dpad * mJ * mJ < 16777216.0f)) &&
+           (!bf16 || (mI <= 256.0f && mJ <= 256.0f));
+}
+
+static BatchPlan plan_batch(const std::vector<std::unique_ptr<HostImage>>& imgs, const std::vector<PairJob>& jobs, const PathSwitches& sw)
+{
+    auto all_pairs = [&](auto&& pred) { return std::all_of(jobs.begin(), jobs.end(), [&](const PairJob& j) { return pred(*imgs[j.sI], *imgs[j.sJ]); }); };
+    const HostImage& first = *imgs[jobs[0].sI];
+    if (first.dtype == R3DM_BIN) return sw.hamming_mfma ? BatchPlan{BatchPath::kHammingMfma, kLayBin8} : BatchPlan{BatchPath::kHammingScan, 0u};
+    // descriptor length without a tensor kernel: the exact scan of every query reads the rows
+    if (!has_tensor_kernel(first.G)) return {BatchPath::kExactScan, kLayRows};
+    // integer fast path (r3dm_set_integer_mfma): every view of the batch must hold bf16-exact integers
+    if (sw.integer_mfma && first.G != 18 && all_pairs([](const HostImage& A, const HostImage& B) { return exact_pair(A, B, true); }))
+        return {BatchPath::kIntegerTiles, kLayBf16};
+    // split-f16 nominator (r3dm_set_split_mfma): batches with at least one real-valued view (integer-valued batches are exact
+    // on the f32 tiles already and have their own fast path); every view finite, scales within reach of one another
+    const bool split = sw.split_mfma &&
+        all_pairs([](const HostImage& A, const HostImage& B) {
+            return std::isfinite(A.max_abs) && std::isfinite(B.max_abs) && A.max_abs > 0.0f && B.max_abs > 0.0f &&
+                   std::abs(A.split_k - B.split_k) <= 40 && std::abs(A.split_k + B.split_k) <= 100;
+        }) &&
+        !all_pairs([](const HostImage& A, const HostImage& B) { return !A.not_integer && !B.not_integer; });
+    // ... and its cheaper form for views whose rows are small integers x a row scale (LIOP: one f16 MFMA per 16 dimensions on the
+    // count tiles instead of three on the split planes): every view of the batch must also pass the staging check (ensure_layouts)
+    if (split && sw.count_tiles &&
+        all_pairs([](const HostImage& A, const HostImage& B) { return counts_eligible(A.dtype, A.n, A.dim) && counts_eligible(B.dtype, B.n, B.dim); }))
+        return {BatchPath::kCountTiles, kLayRows | kLayCounts};
+    if (split) return {BatchPath::kSplitPlanes, kLayRows | kLaySplit};
+    // the f32 tiles: a pair of integer-valued views never re-reads a row (exact_pair); any other pair re-scores its nominees from
+    // the row-major rows
+    return {BatchPath::kF32Tiles, all_pairs([](const HostImage& A, const HostImage& B) { return exact_pair(A, B, false); }) ? 0u : kLayRows};
+}
+
+// The one way off the chosen path: a batch planned on the count tiles that cannot run there (a view failed the votes-x-scale check,
+// or the launcher has no count kernel for it) runs on the split planes, which are valid for every such batch.
+static BatchPlan without_count_tiles(BatchPlan p)
+{
+    return p.path == BatchPath::kCountTiles ? BatchPlan{BatchPath::kSplitPlanes, kLayRows | kLaySplit} : p;
+}
+
 // runs the 2-NN + ratio kernels over `jobs` (slot pairs, all of one dtype/dim) and appends the
 // non-empty results to `g` in job order.  knn_idx/knn_dist (host, optional) receive the raw 2-NN.
 int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g,
@@ -118,12 +171,13 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     { const int rcs = sync_view_stats(c); if (rcs != R3DM_OK) return rcs; }      // which path a batch takes depends on its views' statistics
     const HostImage& first = *c->imgs[jobs[0].sI];
     const r3dm_dtype dtype = first.dtype;
-    uint32_t max_nJ = 0, max_tiles = 0;
+    uint32_t max_nI = 0, max_nJ = 0, max_tiles = 0;
     uint64_t n_queries = 0;
     double flops = 0, bytes = 0;
     for (const PairJob& j : jobs) {
         const HostImage& A = *c->imgs[j.sI];
         const HostImage& B = *c->imgs[j.sJ];
+        max_nI = std::max(max_nI, A.n);
         max_nJ = std::max(max_nJ, B.n);
         max_tiles = std::max(max_tiles, B.n_tiles);
         n_queries += B.n;
@@ -141,54 +195,13 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     for (const PairJob& j : jobs) { batch_slots.push_back(j.sI); batch_slots.push_back(j.sJ); }
     std::sort(batch_slots.begin(), batch_slots.end());
     batch_slots.erase(std::unique(batch_slots.begin(), batch_slots.end()), batch_slots.end());
-    // same test as the kernels' exact_pair (kernels_match_common.hpp): key + ||q||^2 IS the reference distance, bit for bit
-    auto exact_pair = [&](const HostImage& A, const HostImage& B, bool bf16) {
-        const float dpad = (float)(first.G * 8), mI = A.max_abs, mJ = B.max_abs;
-        return !A.not_integer && !B.not_integer &&
-               ((A.has_negative || B.has_negative)
-                    ? dpad * (mI + mJ) * (mI + mJ) < 16777216.0f
-                    : (2.0f * dpad * mI * mJ < 16777216.0f && dpad * mI * mI < 16777216.0f && dpad * mJ * mJ < 16777216.0f)) &&
-               (!bf16 || (mI <= 256.0f && mJ <= 256.0f));
-    };
-    // integer fast path (r3dm_set_integer_mfma): every view of the batch must hold bf16-exact integers
-    bool int_mfma = c->integer_mfma && dtype != R3DM_BIN && first.G != 18;
-    if (int_mfma)
-        for (const PairJob& j : jobs)
-            if (!exact_pair(*c->imgs[j.sI], *c->imgs[j.sJ], true)) { int_mfma = false; break; }
-    // split-f16 nominator (r3dm_set_split_mfma): batches with at least one real-valued view (integer-valued batches are exact
-    // on the f32 tiles already and have their own fast path); every view finite, scales within reach of one another
-    bool split = c->split_mfma && !int_mfma && dtype != R3DM_BIN && has_tensor_kernel(first.G);
-    if (split) {
-        bool any_real = false;
-        for (const PairJob& j : jobs) {
-            const HostImage& A = *c->imgs[j.sI];
-            const HostImage& B = *c->imgs[j.sJ];
-            any_real |= A.not_integer || B.not_integer;
-            if (!std::isfinite(A.max_abs) || !std::isfinite(B.max_abs) || !(A.max_abs > 0.0f) || !(B.max_abs > 0.0f) ||
-                std::abs(A.split_k - B.split_k) > 40 || std::abs(A.split_k + B.split_k) > 100) { split = false; break; }
-        }
-        split = split && any_real;
-    }
-    // ... and its cheaper form for views whose rows are small integers x a row scale (LIOP: one f16 MFMA per 16 dimensions on the
-    // count tiles instead of three on the split planes): every view of the batch must pass the staging check
-    bool counts = split && !r3dm_dev_knob("R3DM_NO_COUNT_TILES", 0);          // (developer build: A/B against the split planes)
-    if (counts)
-        for (uint32_t s : batch_slots) { const HostImage& h = *c->imgs[s]; if (!(h.dtype == R3DM_F32 && h.n && h.dim <= 256)) { counts = false; break; } }
+    BatchPlan plan = plan_batch(c->imgs, jobs, PathSwitches{c->integer_mfma, c->split_mfma, c->hamming_mfma,
+                                                            !r3dm_dev_knob("R3DM_NO_COUNT_TILES", 0)});    // (developer build: A/B against the split planes)
     // ---- the layouts this batch reads that its views do not hold yet (staged once per view; kernels_match.hip, kernels_match_16bit.hip)
     {
-        int rcl = R3DM_OK;
-        if (dtype == R3DM_BIN) { if (c->hamming_mfma) rcl = ensure_layouts(c, batch_slots, kLayBin8); }
-        else if (int_mfma) rcl = ensure_layouts(c, batch_slots, kLayBf16);
-        else if (split) {
-            if (counts) { bool all_ok = false; rcl = ensure_layouts(c, batch_slots, kLayRows | kLayCounts, &all_ok); counts = all_ok; }
-            if (rcl == R3DM_OK && !counts) rcl = ensure_layouts(c, batch_slots, kLayRows | kLaySplit);
-        } else if (has_tensor_kernel(first.G)) {
-            // the f32 tiles: a pair of integer-valued views never re-reads a row (exact_pair); any other pair re-scores its nominees from
-            // the row-major rows
-            bool all_exact = true;
-            for (const PairJob& j : jobs) if (!exact_pair(*c->imgs[j.sI], *c->imgs[j.sJ], false)) { all_exact = false; break; }
-            if (!all_exact) rcl = ensure_layouts(c, batch_slots, kLayRows);
-        } else rcl = ensure_layouts(c, batch_slots, kLayRows);             // no tensor kernel: the exact scan of every query reads the rows
+        bool counts_ok = true;
+        int rcl = plan.layouts ? ensure_layouts(c, batch_slots, plan.layouts, plan.path == BatchPath::kCountTiles ? &counts_ok : nullptr) : R3DM_OK;
+        if (rcl == R3DM_OK && !counts_ok) { plan = without_count_tiles(plan); rcl = ensure_layouts(c, batch_slots, plan.layouts); }
         if (rcl != R3DM_OK) return rcl;
     }
     const uint32_t q_stride = std::max<uint32_t>(32, (max_nJ + 31) / 32 * 32);
@@ -222,7 +235,7 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     // split-f16 keys: residue of the two-piece split 3 x 2^-22 ||a|| ||b|| <= 1.5 x 2^-22 (||a||^2 + ||b||^2), f32 accumulation of
     // 3 Dpad products + one C operand per MFMA with a one-sided 2^-23 per addition on partial sums <= 2 (||a||^2 + ||b||^2), plus the
     // reference sum's own (D/2 + 12) 2^-24 -- together below (3 Dpad + 34) 2^-22, + 2 for the count kernel's bias (kernels_match.hip, l2_knn2_split_kernel)
-    if (split) mp.err_scale = (3.0f * (float)(first.G * 8) + 36.0f) * 2.3841858e-07f;      // (+ 2: the count kernel's keys carry ||b||^2 / (2 s_b) and drop it again)
+    if (plan.path == BatchPath::kSplitPlanes || plan.path == BatchPath::kCountTiles) mp.err_scale = (3.0f * (float)(first.G * 8) + 36.0f) * 2.3841858e-07f;      // (+ 2: the count kernel's keys carry ||b||^2 / (2 s_b) and drop it again)
     mp.nn_idx = c->d_nn.as<uint32_t>();
     mp.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
     mp.knn_dist = knn_idx_host ? c->d_knn_dist.as<float>() : nullptr;
@@ -233,36 +246,33 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     const double t_dbg1 = now_ms();
     R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
     uint64_t n_fallback = 0;
-    if (dtype == R3DM_BIN) {
-        if (c->hamming_mfma) {
+    if (plan.path == BatchPath::kHammingMfma || plan.path == BatchPath::kHammingScan) {
+        if (plan.path == BatchPath::kHammingMfma) {
             R3DM_HIP(c, launch_hamming_mfma(c->stream, mp, first.words, max_tiles));
             c->stats.n_hamming_mfma += 1;
         } else R3DM_HIP(c, launch_hamming_knn2(c->stream, mp, first.words, max_nJ));
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
         R3DM_HIP(c, hipStreamSynchronize(c->stream));      // (the finaliser would wait here anyway; keeps the wall breakdown honest)
-    } else if (has_tensor_kernel(first.G)) {
-        bool counts_ran = false;
-        if (counts) {
-            // hipErrorInvalidValue = no count kernel for this launch (descriptor length, or a grid beyond the launcher's bound): the split
-            // tiles, which every such view also holds, serve the batch
+    } else if (plan.path != BatchPath::kExactScan) {
+        if (plan.path == BatchPath::kCountTiles) {
+            // hipErrorInvalidValue = no count kernel for this launch (descriptor length, or a grid beyond the launcher's bound)
             // (the one-list kernel packs a key and its row into 32 bits: views beyond 65,536 rows would leave its keys fewer than seven
             //  mantissa bits and send a growing share of their queries to the exact scan -- they take the two-list kernel, float keys)
-            uint32_t max_nI_rows = 0;
-            for (const PairJob& j : jobs) max_nI_rows = std::max(max_nI_rows, c->imgs[j.sI]->n);
-            const int two_lists = (max_nI_rows > 65536u || r3dm_dev_knob("R3DM_COUNTS_TWO_LISTS", 0)) ? 1 : 0;
+            const int two_lists = (max_nI > 65536u || r3dm_dev_knob("R3DM_COUNTS_TWO_LISTS", 0)) ? 1 : 0;
             const hipError_t ec = launch_l2_knn2_counts(c->stream, mp, first.G, max_tiles, two_lists);
-            if (ec == hipErrorInvalidValue) (void)hipGetLastError();
-            else { R3DM_HIP(c, ec); counts_ran = true; c->stats.n_split_mfma += 1; c->stats.n_counts_mfma += 1; }
+            if (ec == hipErrorInvalidValue) {
+                (void)hipGetLastError();
+                plan = without_count_tiles(plan);
+                const int rcl = ensure_layouts(c, batch_slots, plan.layouts);
+                if (rcl != R3DM_OK) return rcl;
+            } else { R3DM_HIP(c, ec); c->stats.n_split_mfma += 1; c->stats.n_counts_mfma += 1; }
         }
-        if (counts_ran) {
-            // (launched above)
-        } else if (split) {
-            if (counts) { const int rcl = ensure_layouts(c, batch_slots, kLayRows | kLaySplit); if (rcl != R3DM_OK) return rcl; }      // (no count kernel for this launch: the split planes after all)
+        if (plan.path == BatchPath::kSplitPlanes) {
             R3DM_HIP(c, launch_l2_knn2_split(c->stream, mp, first.G, max_tiles));
             c->stats.n_split_mfma += 1;
-        } else {
-            R3DM_HIP(c, launch_l2_knn2(c->stream, mp, first.G, max_tiles, int_mfma));
-            if (int_mfma) c->stats.n_integer_mfma += 1;
+        } else if (plan.path != BatchPath::kCountTiles) {
+            R3DM_HIP(c, launch_l2_knn2(c->stream, mp, first.G, max_tiles, plan.path == BatchPath::kIntegerTiles));
+            if (plan.path == BatchPath::kIntegerTiles) c->stats.n_integer_mfma += 1;
         }
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
         uint32_t fbt[2] = {0, 0};
@@ -277,8 +287,6 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
                 // a pair's uncertified queries are scanned by one workgroup per ~1024 rows of image I (at most 64): few pairs with
                 // long views (24 views of 28 k rows: 276 workgroups of 7.7 ms each) otherwise leave the chip idle behind one round,
                 // and a workgroup walks its rows tile by tile behind two barriers each (4096 rows per workgroup: 3.9 ms on those views)
-                uint32_t max_nI = 0;
-                for (const PairJob& j : jobs) max_nI = std::max(max_nI, c->imgs[j.sI]->n);
                 uint32_t S = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (max_nI + 1023u) / 1024u));
                 while (S > 1 && (uint64_t)P * S > 65535ull * 4) --S;
                 mp.fb_slices = S; mp.fb_part = nullptr; mp.fb_done = nullptr;
@@ -320,6 +328,19 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     c->stats.n_exact_fallback += n_fallback;
     c->stats.algorithmic_flops += flops;
     c->stats.algorithmic_bytes += bytes;
+    return R3DM_OK;
+}
+
+// the pairs of an approximate matcher whose dataset view is too small to index: few and tiny, scanned exhaustively, one batch per
+// (dtype, dim) run
+int run_scanned_pairs(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g)
+{
+    for (size_t start = 0, end = 0; start < jobs.size(); start = end) {
+        const HostImage& F = *c->imgs[jobs[start].sI];
+        for (end = start; end < jobs.size() && c->imgs[jobs[end].sI]->dtype == F.dtype && c->imgs[jobs[end].sI]->dim == F.dim;) ++end;
+        const int rc = run_match_batch(c, std::vector<PairJob>(jobs.begin() + start, jobs.begin() + end), ratio_R, g, nullptr, nullptr);
+        if (rc != R3DM_OK) return rc;
+    }
     return R3DM_OK;
 }
 
@@ -391,30 +412,14 @@ static int r3dm_knn2_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, 
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;      // ArrayMatcherBruteForce: NN > nbRows / nbQuery < 1
     if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
     R3DM_HIP(c, hipSetDevice(c->device));
-    // two private slots at the end of the table (never visible through view ids)
-    const uint32_t s0 = (uint32_t)c->imgs.size();
-    c->imgs.emplace_back(new HostImage());
-    c->imgs.emplace_back(new HostImage());
-    int rc = stage_into_slot(c, s0, 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s0 + 1, 0, 0, 0, query, n_query, dim, dtype, nullptr);
-    if (rc == R3DM_OK) {
-        std::vector<PairJob> jobs{{0, 1, s0, s0 + 1}};
-        const r3dm_stats keep = c->stats;
-        rc = run_match_batch(c, jobs, 1.0f, nullptr, out_idx, out_dist);
-        const uint64_t int_launches = c->stats.n_integer_mfma - keep.n_integer_mfma;
-        const uint64_t split_launches = c->stats.n_split_mfma - keep.n_split_mfma;
-        const uint64_t counts_launches = c->stats.n_counts_mfma - keep.n_counts_mfma;
-        const uint64_t ham_launches = c->stats.n_hamming_mfma - keep.n_hamming_mfma;
-        const uint64_t fb = c->stats.n_exact_fallback - keep.n_exact_fallback;
-        c->stats = keep;
-        c->stats.n_integer_mfma = int_launches;           // which tiles this call ran on (r3dm_set_integer_mfma / r3dm_set_split_mfma)
-        c->stats.n_split_mfma = split_launches; c->stats.n_hamming_mfma = ham_launches; c->stats.n_counts_mfma = counts_launches;
-        c->stats.n_exact_fallback = fb;                   // ... and how many of its queries went through the exact scan
-    }
-    (void)hipStreamSynchronize(c->stream);
-    c->imgs[s0]->release(); c->imgs[s0 + 1]->release();
-    c->imgs.pop_back(); c->imgs.pop_back();
-    return rc;
+    PrivateSlots s(c, 2);
+    int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, dim, dtype, nullptr);
+    if (rc != R3DM_OK) return rc;
+    // which tiles this call ran on (r3dm_set_*_mfma), and how many of its queries went through the exact scan
+    CallCounters counters(c, {&r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma,
+                              &r3dm_stats::n_exact_fallback});
+    return run_match_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, nullptr, out_idx, out_dist);
 }
 
 extern "C" int r3dm_knn2(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
@@ -437,26 +442,21 @@ static int r3dm_index_create_impl(r3dm_ctx* c, const void* dataset, uint32_t n_d
     R3DM_HIP(c, hipSetDevice(c->device));
     auto ix = std::unique_ptr<r3dm_index>(new (std::nothrow) r3dm_index());
     if (!ix) return R3DM_ERR_NOMEM;
-    const uint32_t s0 = (uint32_t)c->imgs.size();
-    c->imgs.emplace_back(new HostImage());
-    int rc = stage_into_slot(c, s0, 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
+    PrivateSlots s(c, 1);
+    int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
     // Build stages what searches will read: the row-major rows beside the tiles (an index is one dataset: memory is not the concern,
     // a search from any context must not have to add to it) and the layouts of the paths that are switched on; a path switched on
     // later adds its layout on first use, under the index's lock
-    if (rc == R3DM_OK) rc = ensure_layouts(c, {s0}, dtype == R3DM_BIN ? (c->hamming_mfma ? kLayBin8 : 0u)
-                                                                     : (kLayRows | (c->integer_mfma ? kLayBf16 : 0u) | (c->split_mfma ? (kLayCounts | kLaySplit) : 0u)));
-    if (rc == R3DM_OK) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { c->err = std::string("r3dm_index_create: ") + hipGetErrorString(e); rc = R3DM_ERR_HIP; }
-    }
-    if (rc == R3DM_OK) {
-        ix->device = c->device;
-        ix->img = *c->imgs[s0];                   // the index takes the buffers over ...
-        *c->imgs[s0] = HostImage();               // ... and the private slot forgets them
-        *out = ix.release();
-    } else c->imgs[s0]->release();
-    c->imgs.pop_back();
-    return rc;
+    if (rc == R3DM_OK) rc = ensure_layouts(c, {s[0]}, dtype == R3DM_BIN ? (c->hamming_mfma ? kLayBin8 : 0u)
+                                                                       : (kLayRows | (c->integer_mfma ? kLayBf16 : 0u) | (c->split_mfma ? (kLayCounts | kLaySplit) : 0u)));
+    if (rc != R3DM_OK) return rc;
+    const hipError_t e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("r3dm_index_create: ") + hipGetErrorString(e); return R3DM_ERR_HIP; }
+    ix->device = c->device;
+    ix->img = *c->imgs[s[0]];                 // the index takes the buffers over ...
+    *c->imgs[s[0]] = HostImage();             // ... and the private slot forgets them
+    *out = ix.release();
+    return R3DM_OK;
 }
 
 extern "C" int r3dm_index_create(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, uint32_t dim, r3dm_dtype dtype, r3dm_index** out)
@@ -479,32 +479,14 @@ static int r3dm_index_knn2_impl(r3dm_ctx* c, const r3dm_index* ix, const void* q
     if (n_query < 1 || ix->img.n < 2) return R3DM_ERR_INVALID;          // ArrayMatcherBruteForce: NN > nbRows / nbQuery < 1
     if (ix->device != c->device) { c->err = "r3dm_index_knn2: the index lives on another device"; return R3DM_ERR_INVALID; }
     R3DM_HIP(c, hipSetDevice(c->device));
-    const uint32_t s0 = (uint32_t)c->imgs.size();
-    c->imgs.emplace_back(new HostImage());
-    c->imgs.emplace_back(new HostImage());
-    {
-        std::lock_guard<std::mutex> lk(const_cast<r3dm_index*>(ix)->mu);
-        *c->imgs[s0] = ix->img;                   // aliases of the index's buffers: mounted for this call only
-    }
-    c->imgs[s0]->borrowed = true;
-    c->imgs[s0]->owner = const_cast<r3dm_index*>(ix);
-    int rc = publish_entry(c, s0);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s0 + 1, 0, 0, 0, query, n_query, ix->img.dim, ix->img.dtype, nullptr);
-    if (rc == R3DM_OK) {
-        std::vector<PairJob> jobs{{0, 1, s0, s0 + 1}};
-        const r3dm_stats keep = c->stats;
-        rc = run_match_batch(c, jobs, 1.0f, nullptr, out_idx, out_dist);
-        const uint64_t int_launches = c->stats.n_integer_mfma - keep.n_integer_mfma;
-        const uint64_t split_launches = c->stats.n_split_mfma - keep.n_split_mfma;
-        const uint64_t counts_launches = c->stats.n_counts_mfma - keep.n_counts_mfma;
-        const uint64_t ham_launches = c->stats.n_hamming_mfma - keep.n_hamming_mfma;
-        c->stats = keep;
-        c->stats.n_integer_mfma = int_launches; c->stats.n_split_mfma = split_launches; c->stats.n_hamming_mfma = ham_launches; c->stats.n_counts_mfma = counts_launches;
-    }
-    (void)hipStreamSynchronize(c->stream);
-    c->imgs[s0]->release(); c->imgs[s0 + 1]->release();
-    c->imgs.pop_back(); c->imgs.pop_back();
-    return rc;
+    PrivateSlots s(c, 2);
+    r3dm_index* mix = const_cast<r3dm_index*>(ix);
+    { std::lock_guard<std::mutex> lk(mix->mu); c->imgs[s[0]]->mount(mix); }      // aliases of the index's buffers, for this call only
+    int rc = publish_entry(c, s[0]);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, ix->img.dim, ix->img.dtype, nullptr);
+    if (rc != R3DM_OK) return rc;
+    CallCounters counters(c, {&r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma});
+    return run_match_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, nullptr, out_idx, out_dist);
 }
 
 extern "C" int r3dm_index_knn2(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, int32_t* out_idx, float* out_dist)
@@ -849,16 +831,8 @@ static int r3dm_match_pairs_kgraph_impl(r3dm_ctx* c, const uint32_t* pairs_ij, u
         if (rc != R3DM_OK) return rc;
         start = end;
     }
-    start = 0;
-    while (start < small_jobs.size()) {                      // few and tiny: one batch per (dtype, dim) run
-        size_t end = start;
-        const HostImage& F = *c->imgs[small_jobs[start].sI];
-        while (end < small_jobs.size() && c->imgs[small_jobs[end].sI]->dtype == F.dtype && c->imgs[small_jobs[end].sI]->dim == F.dim) ++end;
-        std::vector<PairJob> batch(small_jobs.begin() + start, small_jobs.begin() + end);
-        rc = run_match_batch(c, batch, R, &gs, nullptr, nullptr);
-        if (rc != R3DM_OK) return rc;
-        start = end;
-    }
+    rc = run_scanned_pairs(c, small_jobs, R, &gs);
+    if (rc != R3DM_OK) return rc;
     rc = merge_parts_keep_mirror(ga, gs, out);
     c->stats.ms_wall_match = now_ms() - t_call;
     return rc;
@@ -880,29 +854,18 @@ static int r3dm_kgraph_knn2_impl(r3dm_ctx* c, const float* dataset, uint32_t n_d
     if (rc != R3DM_OK) return rc;
     if (dim & 3u) { c->err = "kgraph matching needs dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
     R3DM_HIP(c, hipSetDevice(c->device));
-    const uint32_t s0 = (uint32_t)c->imgs.size();
-    c->imgs.emplace_back(new HostImage());
-    c->imgs.emplace_back(new HostImage());
-    rc = stage_into_slot(c, s0, pair_i, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s0 + 1, pair_j, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
-    const r3dm_stats keep = c->stats;
-    if (rc == R3DM_OK) {
-        std::vector<PairJob> jobs{{pair_i, pair_j, s0, s0 + 1}};
-        if (n_dataset < kAnnMinRows || kp->search_P >= n_dataset) rc = run_match_batch(c, jobs, 1.0f, nullptr, out_idx, out_dist);
-        else {
-            rc = ensure_layouts(c, {s0, s0 + 1}, kLayRows);
-            if (rc == R3DM_OK) rc = ensure_ann_indices(c, {s0}, kp->index_K);
-            if (rc == R3DM_OK) rc = ensure_compact_rows(c, {s0 + 1});
-            if (rc == R3DM_OK) rc = run_ann_batch(c, jobs, 1.0f, *kp, nullptr, out_idx, out_dist);
-        }
-    }
-    const uint64_t r16 = c->stats.n_ann_rows16 - keep.n_ann_rows16, r8 = c->stats.n_ann_rows8 - keep.n_ann_rows8, d8 = c->stats.n_ann_dot8 - keep.n_ann_dot8,
-                   evals = c->stats.n_ann_dist - keep.n_ann_dist;
-    c->stats = keep;
-    c->stats.n_ann_rows16 = r16; c->stats.n_ann_rows8 = r8; c->stats.n_ann_dot8 = d8; c->stats.n_ann_dist = evals;   // like r3dm_knn2: which rows this call gathered, how many evaluations
-    (void)hipStreamSynchronize(c->stream);
-    c->imgs[s0]->release(); c->imgs[s0 + 1]->release();
-    c->imgs.pop_back(); c->imgs.pop_back();
+    PrivateSlots s(c, 2);
+    rc = stage_into_slot(c, s[0], pair_i, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], pair_j, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
+    if (rc != R3DM_OK) return rc;
+    // like r3dm_knn2: which rows this call gathered, how many evaluations
+    CallCounters counters(c, {&r3dm_stats::n_ann_rows16, &r3dm_stats::n_ann_rows8, &r3dm_stats::n_ann_dot8, &r3dm_stats::n_ann_dist});
+    const std::vector<PairJob> jobs{{pair_i, pair_j, s[0], s[1]}};
+    if (n_dataset < kAnnMinRows || kp->search_P >= n_dataset) return run_match_batch(c, jobs, 1.0f, nullptr, out_idx, out_dist);
+    rc = ensure_layouts(c, {s[0], s[1]}, kLayRows);
+    if (rc == R3DM_OK) rc = ensure_ann_indices(c, {s[0]}, kp->index_K);
+    if (rc == R3DM_OK) rc = ensure_compact_rows(c, {s[1]});
+    if (rc == R3DM_OK) rc = run_ann_batch(c, jobs, 1.0f, *kp, nullptr, out_idx, out_dist);
     return rc;
 }
 

@@ -291,16 +291,8 @@ static int r3dm_match_pairs_mrpt_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uin
         if (rc != R3DM_OK) return rc;
         start = end;
     }
-    start = 0;
-    while (start < small_jobs.size()) {
-        size_t end = start;
-        const HostImage& F = *c->imgs[small_jobs[start].sI];
-        while (end < small_jobs.size() && c->imgs[small_jobs[end].sI]->dtype == F.dtype && c->imgs[small_jobs[end].sI]->dim == F.dim) ++end;
-        std::vector<PairJob> batch(small_jobs.begin() + start, small_jobs.begin() + end);
-        rc = run_match_batch(c, batch, dist_ratio * dist_ratio, &gs, nullptr, nullptr);
-        if (rc != R3DM_OK) return rc;
-        start = end;
-    }
+    rc = run_scanned_pairs(c, small_jobs, dist_ratio * dist_ratio, &gs);
+    if (rc != R3DM_OK) return rc;
     rc = merge_parts_keep_mirror(ga, gs, out);
     c->stats.ms_wall_match = now_ms() - t_call;
     return rc;
@@ -325,25 +317,14 @@ extern "C" int r3dm_mrpt_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_data
         if (n_dataset > (1u << 17)) { c->err = "MRPT matching: more than 131,072 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
         if (!mrpt_query_fits_lds(n_dataset, *mp)) { c->err = "r3dm_mrpt_knn2: the vote table of this many rows exceeds a wavefront's LDS with these parameters (such views are scanned: r3dm_knn2)"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, hipSetDevice(c->device));
-        const uint32_t s0 = (uint32_t)c->imgs.size();
-        c->imgs.emplace_back(new HostImage());
-        c->imgs.emplace_back(new HostImage());
-        rc = stage_into_slot(c, s0, 0, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
-        if (rc == R3DM_OK) rc = stage_into_slot(c, s0 + 1, 1, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
-        const r3dm_stats keep = c->stats;
-        if (rc == R3DM_OK) rc = ensure_mrpt_indices(c, {s0}, *mp);
-        if (rc == R3DM_OK) {
-            std::vector<PairJob> jobs{{0, 1, s0, s0 + 1}};
-            rc = run_mrpt_batch(c, jobs, 1.0f, mp->votes, nullptr, out_idx, out_dist);
-        }
-        const uint64_t evals = c->stats.n_ann_dist - keep.n_ann_dist;
-        const double ms_b = c->stats.ms_ann_build - keep.ms_ann_build, ms_s = c->stats.ms_ann_search - keep.ms_ann_search;
-        c->stats = keep;
-        c->stats.n_ann_dist = evals; c->stats.ms_ann_build = ms_b; c->stats.ms_ann_search = ms_s;
-        (void)hipStreamSynchronize(c->stream);
-        c->imgs[s0]->release(); c->imgs[s0 + 1]->release();
-        c->imgs.pop_back(); c->imgs.pop_back();
-        return rc;
+        PrivateSlots s(c, 2);
+        rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
+        if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 1, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
+        if (rc != R3DM_OK) return rc;
+        CallCounters counters(c, {&r3dm_stats::n_ann_dist}, {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
+        rc = ensure_mrpt_indices(c, {s[0]}, *mp);
+        if (rc != R3DM_OK) return rc;
+        return run_mrpt_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, mp->votes, nullptr, out_idx, out_dist);
     });
 }
 

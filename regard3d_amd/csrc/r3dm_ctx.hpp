@@ -12,6 +12,7 @@
 #include <sys/syscall.h>
 #include <unistd.h>
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <thread>
@@ -209,14 +210,17 @@ enum : uint32_t {
     kLayBin8   = 16u,    // one byte per bit in i8 fragment order (r3dm_set_hamming_mfma)
 };
 
-struct HostImage {
+// the count tiles exist only for f32 views of at most 256 dimensions (anything else is never votes x scale: counts_ok stays false)
+inline bool counts_eligible(r3dm_dtype dtype, uint32_t n, uint32_t dim) { return dtype == R3DM_F32 && n && dim <= 256; }
+// the split planes and the count tiles are made from the row-major rows, and the nominees of both are re-scored on them
+inline uint32_t with_implied_rows(uint32_t want) { return (want & (kLaySplit | kLayCounts)) ? want | kLayRows : want; }
+
+// The tenant of a slot: the view staged into it, its statistics, and which layouts and indices reflect it
+struct ViewState {
     uint32_t view_id = 0, n = 0, dim = 0, width = 0, height = 0;
     r3dm_dtype dtype = R3DM_F32;
     uint32_t G = 0, n_tiles = 0, words = 0;
     bool has_xy = false, has_dup = false, live = false;
-    bool borrowed = false;            // the buffers belong to an r3dm_index mounted into this slot for one call: never freed here
-    struct r3dm_index* owner = nullptr;   // ... that index (layouts staged on first use are added to IT, under its lock)
-    DevBuf rows, tiled, tiled16, tiledh, tiledc, tiledp, cscale, cquad, cperm, tiled8, norms, bin, xy, canon;
     uint32_t have = 0;                // kLay* bits: which on-demand layouts reflect the staged view
     // staging statistics: accumulated by the staging kernel in the view's table entry, read back -- for all views staged since the last
     // read -- by sync_view_stats() at the first call that needs them (no per-view synchronisation at registration)
@@ -225,32 +229,53 @@ struct HostImage {
     float max_abs = 0.0f; bool not_integer = true, has_negative = true;
     int32_t split_k = 0;                                                    // scale exponent of the f16 split tiles (a function of max_abs)
     bool counts_ok = false;                                                 // every row is small integers x a row scale: the count tiles are valid
-    bool compact_ready = false;     // ann_rows16 / ann_rows8 reflect the staged rows (reset by staging)
-    DevBuf ann_adj, ann_deg, ann_rows16, ann_rows8;   // graph index (r3dm_match_pairs_kgraph), valid when ann_K != 0; compact row copies only for bf16- / u8-exact views
-    uint32_t ann_K = 0;
-    // HNSW index (r3dm_match_pairs_hnsw), valid when hnsw_M != 0: hnswlib's arrays (kernels_hnsw.hip: HnswView) + the host-side scalars
-    DevBuf hnsw_l0, hnsw_up_off, hnsw_up;
-    uint32_t hnsw_M = 0, hnsw_seed = 0, hnsw_up_rows = 0; int32_t hnsw_enter = -1, hnsw_maxlevel = -1;
-    // MRPT index (r3dm_match_pairs_mrpt), valid when mrpt_trees != 0: kernels_mrpt.hip: MrptView
-    DevBuf mrpt_R, mrpt_RT, mrpt_splits, mrpt_leaves, mrpt_lf;
-    uint32_t mrpt_trees = 0, mrpt_depth = 0; float mrpt_density = 0.0f; uint64_t mrpt_seed = 0;
-    bool has_K = false;               // pinhole intrinsics (r3dm_set_intrinsics), needed by the essential-matrix filter
+    bool compact_ready = false;       // ann_rows16 / ann_rows8 reflect the staged rows
+    uint32_t ann_K = 0;               // graph index (r3dm_match_pairs_kgraph) in ann_adj / ann_deg
+    uint32_t hnsw_M = 0, hnsw_seed = 0, hnsw_up_rows = 0; int32_t hnsw_enter = -1, hnsw_maxlevel = -1;     // HNSW index, valid when hnsw_M != 0
+    uint32_t mrpt_trees = 0, mrpt_depth = 0; float mrpt_density = 0.0f; uint64_t mrpt_seed = 0;          // MRPT index, valid when mrpt_trees != 0
+};
+
+// A slot of a context's view table.  What survives which transition:
+//   ViewState        the tenant: replaced as a whole when a view is staged into the slot (new_tenant) and reset when the collection is
+//                    cleared (clear)
+//   has_K, Kinv      the view's intrinsics (r3dm_set_intrinsics): survive a re-registration of the view, forgotten by clear()
+//   index buffers    ann_*, hnsw_*, mrpt_*: survive a new tenant (a rebuild reuses them), given back by clear() (rebuilt per collection:
+//                    a context that once held a 1000-view collection must not sit on their gigabytes)
+//   layout buffers   rows .. canon: survive both (a cleared view is a spare whose buffers serve the next collection), freed by release()
+//   borrowed, owner  a mounted r3dm_index (mount): the buffers are aliases of the index's, never freed here
+struct HostImage : ViewState {
+    bool borrowed = false;
+    struct r3dm_index* owner = nullptr;   // (layouts staged on first use are added to the index, under its lock)
+    DevBuf rows, tiled, tiled16, tiledh, tiledc, tiledp, cscale, cquad, cperm, tiled8, norms, bin, xy, canon;
+    DevBuf ann_adj, ann_deg, ann_rows16, ann_rows8;   // graph index; compact row copies only for bf16- / u8-exact views
+    DevBuf hnsw_l0, hnsw_up_off, hnsw_up;             // hnswlib's arrays (kernels_hnsw.hip: HnswView)
+    DevBuf mrpt_R, mrpt_RT, mrpt_splits, mrpt_leaves, mrpt_lf;      // kernels_mrpt.hip: MrptView
+    bool has_K = false;               // pinhole intrinsics, needed by the essential-matrix filter
     double Kinv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // the layout buffers of a view registered with a context are blocks of the context's arena (an r3dm_index owns plain allocations:
     // it outlives contexts)
-    void use_arena(DevArena* a)
+    std::array<DevBuf*, 14> layout_bufs() { return {&rows, &tiled, &tiled16, &tiledh, &tiledc, &tiledp, &cscale, &cquad, &cperm, &tiled8, &norms, &bin, &xy, &canon}; }
+    void use_arena(DevArena* a) { for (DevBuf* x : layout_bufs()) x->arena = a; }
+    void new_tenant(uint32_t id, uint32_t n_, uint32_t dim_, r3dm_dtype dtype_, uint32_t width_, uint32_t height_, bool xy)
     {
-        DevBuf* b[] = {&rows, &tiled, &tiled16, &tiledh, &tiledc, &tiledp, &cscale, &cquad, &cperm, &tiled8, &norms, &bin, &xy, &canon};
-        for (DevBuf* x : b) x->arena = a;
+        static_cast<ViewState&>(*this) = ViewState();
+        view_id = id; n = n_; dim = dim_; dtype = dtype_; width = width_; height = height_; has_xy = xy; live = true;
+    }
+    void clear()
+    {
+        DevBuf* b[] = {&ann_adj, &ann_deg, &ann_rows16, &ann_rows8, &hnsw_l0, &hnsw_up_off, &hnsw_up, &mrpt_R, &mrpt_RT, &mrpt_splits, &mrpt_leaves, &mrpt_lf};
+        for (DevBuf* x : b) x->release();
+        static_cast<ViewState&>(*this) = ViewState();
+        has_K = false;
     }
     void release()
     {
-        if (borrowed) { *this = HostImage(); return; }     // drop the aliases, keep the index's memory
-        rows.release(); tiled.release(); tiled16.release(); tiledh.release(); tiledc.release(); tiledp.release(); cscale.release(); cquad.release(); cperm.release(); tiled8.release(); norms.release(); bin.release(); xy.release(); canon.release();
-        ann_adj.release(); ann_deg.release(); ann_rows16.release(); ann_rows8.release(); ann_K = 0; compact_ready = false; live = false; have = 0; stats_valid = false;
-        hnsw_l0.release(); hnsw_up_off.release(); hnsw_up.release(); hnsw_M = 0;
-        mrpt_R.release(); mrpt_RT.release(); mrpt_splits.release(); mrpt_leaves.release(); mrpt_lf.release(); mrpt_trees = 0;
+        if (borrowed) { *this = HostImage(); return; }
+        clear();
+        for (DevBuf* x : layout_bufs()) x->release();
     }
+    // this slot becomes (again) an alias of the index as it stands: the caller holds the index's lock
+    inline void mount(struct r3dm_index* ix);
 };
 
 int graph_dev_append(r3dm_ctx* c, r3dm_graph* g, const std::vector<uint32_t>& pair_ids, const std::vector<uint32_t>& counts, std::vector<GraphSeg>& segs,
@@ -444,12 +469,58 @@ static inline int r3dm_guarded(r3dm_ctx* c, F&& body) noexcept
 
 struct PairJob { uint32_t I, J, sI, sJ; };
 
+// Slots of one call (r3dm_knn2 and its relatives), at the end of the table, never visible through view ids: plain HostImages, not arena
+// blocks or spares.  On every exit -- error returns and exceptions included -- the stream is synchronised, and the slots are released,
+// dropped from pending_stats and popped.
+struct PrivateSlots {
+    r3dm_ctx* c;
+    uint32_t first;
+    PrivateSlots(r3dm_ctx* c_, uint32_t n) : c(c_), first((uint32_t)c_->imgs.size())
+    {
+        try { for (uint32_t k = 0; k < n; ++k) c->imgs.push_back(std::unique_ptr<HostImage>(new HostImage())); }
+        catch (...) { drop(); throw; }
+    }
+    ~PrivateSlots() { drop(); }
+    uint32_t operator[](uint32_t k) const { return first + k; }
+    PrivateSlots(const PrivateSlots&) = delete;
+    void operator=(const PrivateSlots&) = delete;
+private:
+    void drop() noexcept
+    {
+        (void)hipStreamSynchronize(c->stream);
+        std::vector<uint32_t>& p = c->pending_stats;
+        p.erase(std::remove_if(p.begin(), p.end(), [this](uint32_t s) { return s >= first; }), p.end());
+        while (c->imgs.size() > first) { if (c->imgs.back()) c->imgs.back()->release(); c->imgs.pop_back(); }
+    }
+};
+
+// The counters of a call that reports its own work in a few named fields of the context's statistics (r3dm_knn2 and its relatives):
+// on every exit c->stats is back to what it was when this was made, except the named counters, which hold the call's delta.
+struct CallCounters {
+    r3dm_ctx* c;
+    const r3dm_stats before;
+    const std::vector<uint64_t r3dm_stats::*> counts;
+    const std::vector<double r3dm_stats::*> times;
+    CallCounters(r3dm_ctx* c_, std::initializer_list<uint64_t r3dm_stats::*> counts_, std::initializer_list<double r3dm_stats::*> times_ = {})
+        : c(c_), before(c_->stats), counts(counts_), times(times_) {}
+    ~CallCounters()
+    {
+        const r3dm_stats after = c->stats;
+        c->stats = before;
+        for (auto m : counts) c->stats.*m = after.*m - before.*m;
+        for (auto m : times) c->stats.*m = after.*m - before.*m;
+    }
+};
+
+
 // A dataset staged once for many queries (ArrayMatcher::Build): owns its device buffers, belongs to a device, not to a context
 struct r3dm_index {
     int device = 0;
     HostImage img;                              // (statistics included: HostImage::stat_bits)
     std::mutex mu;                              // layouts staged after Build (a flag switched on later) are added under this lock
 };
+
+inline void HostImage::mount(r3dm_index* ix) { *this = ix->img; borrowed = true; owner = ix; }
 
 // shared between the translation units
 // part graphs of the approximate matchers (graph-searched pairs + exhaustively scanned small pairs): see their use
@@ -469,6 +540,7 @@ int ensure_layouts(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t want, bool
 int ensure_layouts_image(r3dm_ctx* c, HostImage& h, uint32_t want);        // (no table entry involved; the caller publishes)
 int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g,
                     int32_t* knn_idx_host, float* knn_dist_host);
+int run_scanned_pairs(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g);
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
                    uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host);
 int ensure_ann_indices(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t K);

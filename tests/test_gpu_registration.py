@@ -213,3 +213,35 @@ def test_an_index_gains_the_layout_of_a_switch_that_comes_on_after_build(oracle)
         ix.close()
     finally:
         c.close(); c2.close()
+
+
+def test_a_failed_call_on_private_slots_leaves_the_collection_alone(oracle):
+    # r3dm_hnsw_knn2_on_index stages its dataset and query into two slots of its own, then refuses malformed index arrays: the slots
+    # must leave the table without a trace -- no pending statistics read back into the views that take those slot numbers next (the
+    # table grows past 256 slots on the way, which reads back every pending view), no device memory, no layouts of the earlier views
+    from test_oracle_hnsw import load_case
+    d0, d1, ix, _, _ = load_case("sift", "fast")
+    bad = dict(ix); bad["links0"] = ix["links0"].copy(); bad["links0"][5, 1] = len(d0)            # a link past the last row
+    n_views = 270
+    sc = synth.make_scene(n_views, 96, "liop", seed=23)
+    first = 6
+    pairs = np.array([(a, b) for a in range(first) for b in range(a + 1, first)] +
+                     [(k, k + 1) for k in range(first - 1, n_views - 1)] + [(k, k + 7) for k in range(0, n_views - 7, 5)], np.uint32)
+    counts, matches = oracle.match_collection(sc.descs, sc.xys, pairs, 0.8, True)
+    c = api.Context(0)
+    try:
+        c.set_images(list(range(first)), sc.descs[:first], sc.xys[:first], 4000, 3000)
+        c.match_pairs(pairs[:first * (first - 1) // 2], 0.8, True)          # real-valued views: the rows are staged
+        layouts = [c.view_info(i)[0] for i in range(first)]
+        assert all(lay == api.LAYOUT_ROWS for lay in layouts)
+        view_bytes = c.memory_info()[0]
+        with pytest.raises(api.R3dmError):
+            c.hnsw_knn2_on_index(d0, bad, oracle.HNSW_PRESETS["fast"][0], d1, 5)
+        assert c.memory_info()[0] == view_bytes
+        for i in range(first, n_views):
+            c.set_image(i, sc.descs[i], sc.xys[i], 4000, 3000)
+        g = c.match_pairs(pairs, 0.8, True)
+        _graph_equal(g, pairs, counts, matches)
+        assert [c.view_info(i)[0] for i in range(first)] == layouts
+    finally:
+        c.close()
