@@ -100,6 +100,10 @@ public:
     void setSplitFastPath(bool on);
     // no reference counterpart: forwards r3dm_set_hamming_mfma (bit-identical results, binary descriptors: A-KAZE MLDB on i8 MFMA tiles, 3.0x)
     void setHammingFastPath(bool on);
+    // bGuided_matching of the three Robust_model_estimation calls (src/R3DComputeMatches.cpp:2113-2114 F, :2169-2170 E, :2215-2218 H;
+    // the reference passes false): forwards r3dm_set_guided_matching to every device context, so the F / E / H match files hold the
+    // guided lists of the accepted pairs.  The default ratios are the reference's own dDistanceRatio arguments (H: geometry only).
+    void setGuidedMatching(bool on, double ratio_F = 0.6, double ratio_E = 0.6, double ratio_H = -1.0);
     // How the approximate arms of the dispatch (0 FLANN, 1-3 KGraph, 5 MRPT, 6-8 HNSW) are served.  kArmsFastest (default): by the
     // EXHAUSTIVE matcher whenever r3dm_exhaustive_is_faster says it is not slower on the registered views -- on LIOP-144 every
     // approximate arm is then exact and >= 2x faster than the graph search (the GUI's default arm 0 included); kArmsAsRequested:
@@ -235,6 +239,7 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_INTEGER_MFMA      4u   /* (implied since round 3) */
 #define R3DM_STAGE_BACKGROUND_NICE  16u   /* background writer threads at nice 10 (R3DComputeMatches::setBackgroundThreadsNice(10)); default: priorities untouched */
 #define R3DM_STAGE_F32_TILES         8u   /* plain f32 MFMA tiles for the exhaustive matcher: R3DComputeMatches::setExactFastPaths(false); same files, slower */
+#define R3DM_STAGE_GUIDED_MATCHING  32u   /* bGuided_matching = true (R3DComputeMatches::setGuidedMatching(true)): the filters' match files hold guided lists */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,

@@ -210,6 +210,49 @@ int r3dm_filter_FEH(r3dm_ctx* ctx, const r3dm_graph* putative, double max_residu
                     uint32_t e_min_count, float e_min_ratio, r3dm_graph** out_F, r3dm_graph** out_E, r3dm_graph** out_H,
                     double* ms_kernels3, double* ms_wall3);
 
+/* ---- guided matching (OpenMVG's bGuided_matching) ----
+ * The reference runs every filter as Robust_model_estimation(functor, putatives, bGuided_matching, dDistanceRatio) with
+ * bGuided_matching = false (src/R3DComputeMatches.cpp:2101,2113-2114 F; :2169-2170 E; :2215-2218 H, which already passes the
+ * geometry-only ratio -1.0).  With true, OpenMVG re-matches every ACCEPTED pair over all features of both views and the result
+ * replaces the pair's inlier list ("Guided matching"):
+ *   - the queries are the features of I, the candidates all features of J; a candidate passes the geometric gate iff err < errTh
+ *     (f64, strict) with errTh = threshold_px^2 and err the filter's own error with positions promoted to double: F
+ *     EpipolarDistanceError(F, x_i, x_j), E the same on F = K_J^-T E K_I^-1 (r3dm_set_intrinsics of both views), H AsymmetricError
+ *     (transfer error in J).  E's threshold_px is ALREADY the squared pixel bound (r3dm_pair_report of the E filter), so its
+ *     effective gate is that value squared once more -- what OpenMVG's Square(m_dPrecision_robust) does with it; reproduced as is;
+ *   - ratio >= 0 (descriptor mode; the reference's F and E default 0.6): among the candidates in ascending j, OpenMVG's
+ *     distanceRatio update on SquaredDescriptorDistance (squared L2 in the reference arithmetic for float / byte rows, the Hamming
+ *     distance for binary rows); a match (i, j_best) iff there were two candidates and (double)best < ratio^2 * (double)second;
+ *   - ratio < 0 (geometry only; the reference's H): the j of smallest error (the first one on ties); for H the matches are then
+ *     de-duplicated by coordinates (IndMatchDecorator: the smallest (i, j) of equal (xI, yI, xJ, yJ) stays);
+ *   - matches are (i in I, j in J), ascending i, at most one per i.  A pair whose guided list is empty does not enter the graph
+ *     (graphs here never hold empty entries; OpenMVG would insert it empty).
+ * r3dm_guided_match is the primitive: it reads only the pair list of `pairs` and takes the caller's models (9 doubles per pair: F, E or
+ * H as the filters return them) and thresholds (one per pair, as r3dm_pair_report.threshold_px reports them).  kind R3DM_GUIDED_*. */
+#define R3DM_GUIDED_F 0
+#define R3DM_GUIDED_E 1
+#define R3DM_GUIDED_H 2
+int r3dm_guided_match(r3dm_ctx* ctx, const r3dm_graph* pairs, int kind, const double* models, const double* threshold_px, double ratio,
+                      r3dm_graph** out);
+/* Context switch (default off: every filter returns what it returns without it, byte for byte).  While on, r3dm_filter_F / _E / _H /
+ * _FEH (and r3dm_multi_filter_* through r3dm_multi_set_guided_matching) return the guided lists of their accepted pairs, one guided
+ * launch per call for all its filters; E's overlap rule (min_count / min_ratio) is applied to the guided list, as Regard3D applies it
+ * after Get_geometric_matches() (src/R3DComputeMatches.cpp:2175-2192).  F_out / E_out / H_out and r3dm_filter_report stay what
+ * AC-RANSAC found (one model per pair of the returned graph).  ratio_*: the dDistanceRatio of each filter; the reference's own
+ * arguments are 0.6, 0.6, -1.0 (R3DComputeMatches::setGuidedMatching). */
+int r3dm_set_guided_matching(r3dm_ctx* ctx, int enable, double ratio_F, double ratio_E, double ratio_H);
+/* The last guided step of the context (r3dm_guided_match, or a filter call with the switch on): HIP-event time of its kernels, wall
+ * time, pairs re-matched (accepted pairs), queries (features of the I views), candidates that passed the geometric gate (candidates
+ * per query = n_candidates / n_queries), matches before the graph's pair rules, and the chunks the descriptor mode ran in.
+ * Memory: the descriptor mode holds the candidate lists of at most 2^28 candidates (1 GiB) at a time -- the queries are processed in
+ * chunks of 256-query blocks below that budget, so a wide threshold costs time, not memory; a single block of 256 queries whose lists
+ * alone exceed it is a chunk of its own (at most 256 x |J| candidates).  Everything else is O(queries of the call). */
+typedef struct {
+    double   ms_kernels, ms_wall;
+    uint64_t n_pairs, n_queries, n_candidates, n_matches, n_desc_chunks;
+} r3dm_guided_stats;
+int r3dm_guided_report(const r3dm_ctx* ctx, r3dm_guided_stats* out);
+
 /* ---- ArrayMatcher-shaped low level call: 2-NN of each query row among the dataset rows ----
  * out_idx / out_dist: 2 entries per query, ascending distance (dist: float squared L2 for F32/U8,
  * Hamming distance converted to float for BIN).  Fails (R3DM_ERR_INVALID) when n_query < 1 or
@@ -495,6 +538,8 @@ int r3dm_multi_filter_H(r3dm_multi* m, const r3dm_graph* putative, double max_re
                         uint64_t seed, r3dm_graph** out, double* H_out);
 int r3dm_multi_filter_E(r3dm_multi* m, const r3dm_graph* putative, double max_residual_px, uint32_t max_iter,
                         uint64_t seed, uint32_t min_count, float min_ratio, r3dm_graph** out, double* E_out);
+/* r3dm_set_guided_matching on every device context: r3dm_multi_filter_* then return guided lists */
+int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H);
 /* The features stage over an image list: R3DFeaturesThread::extractFeaturesAndDescriptors (src/threads/R3DFeaturesThread.cpp:38-121),
  * whose worker pool pulls images off a work list and runs processWorkItem on each.  Here every context of `m` is a worker that pulls
  * BATCHES of same-size images (r3dm_extract_features_batch: up to 8 per detector pass): create

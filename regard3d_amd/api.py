@@ -36,7 +36,10 @@ EXPORTS = [
     "r3dm_comm_unique_id", "r3dm_comm_create", "r3dm_comm_destroy", "r3dm_comm_rank", "r3dm_comm_world", "r3dm_comm_last_error",
     "r3dm_allgather_graphs", "r3dm_graphs_pack", "r3dm_words_free", "r3dm_graphs_unpack_merge",
     "r3dm_set_device_graphs", "r3dm_graph_on_device", "r3dm_comm_last_device_graphs",
+    "r3dm_guided_match", "r3dm_set_guided_matching", "r3dm_guided_report", "r3dm_multi_set_guided_matching",
 ]
+GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
+STAGE_GUIDED_MATCHING = 32
 
 
 class R3dmError(RuntimeError):
@@ -63,6 +66,17 @@ class Stats(C.Structure):
                 ("ms_liop_wall", C.c_double), ("ms_feature_files", C.c_double),
                 ("n_hnsw_launches", C.c_uint64), ("n_hnsw_retries", C.c_uint64), ("n_counts_mfma", C.c_uint64),
                 ("detect_compulsory_bytes", C.c_double), ("n_filter_workgroups", C.c_uint64), ("n_filter_coop_pairs", C.c_uint64)]
+
+
+class GuidedStats(C.Structure):
+    """r3dm_guided_stats: the last guided-matching step of a context"""
+    _fields_ = [("ms_kernels", C.c_double), ("ms_wall", C.c_double), ("n_pairs", C.c_uint64), ("n_queries", C.c_uint64),
+                ("n_candidates", C.c_uint64), ("n_matches", C.c_uint64), ("n_desc_chunks", C.c_uint64)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_}
+        d["candidates_per_query"] = self.n_candidates / self.n_queries if self.n_queries else 0.0
+        return d
 
 
 class FeaturesTotals(C.Structure):
@@ -129,13 +143,16 @@ class Stage:
 
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
-            arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False) -> StageReport:
+            arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
+            guided: bool = False) -> StageReport:
+        """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING)"""
         keep = []
         arr = _stage_views(views, keep)
         rep = StageReport(); err = C.create_string_buffer(1024)
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
-                                    (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0), C.byref(rep), err, 1024)
+                                    (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0), C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -155,7 +172,8 @@ class Stage:
 def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6,
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
-                          split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False) -> StageReport:
+                          split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
+                          guided: bool = False) -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy."""
@@ -167,7 +185,8 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     L.r3dm_compute_matches_stage.argtypes = [C.c_void_p, C.c_int] + _STAGE_ARGS
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
-                                      (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0), C.byref(rep), err, 1024)
+                                      (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0), C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
@@ -280,6 +299,10 @@ def load_library():
     L.r3dm_filter_E.argtypes = [vp, vp, C.c_double, u32, u64, u32, C.c_float, C.POINTER(vp), vp]
     L.r3dm_filter_FEH.argtypes = [vp, vp, C.c_double, u32, u64, C.c_int, u32, C.c_float, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), vp, vp]
     L.r3dm_set_intrinsics.argtypes = [vp, u32, vp]
+    L.r3dm_guided_match.argtypes = [vp, vp, C.c_int, vp, vp, C.c_double, C.POINTER(vp)]
+    L.r3dm_set_guided_matching.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
+    L.r3dm_guided_report.argtypes = [vp, vp]
+    L.r3dm_multi_set_guided_matching.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
     L.r3dm_liop_describe_patches.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.r3dm_extract_liop.argtypes = [vp, vp, u32, u32, vp, u32, C.c_float, vp, vp]
     L.r3dm_knn2.argtypes = [vp, vp, u32, vp, u32, u32, C.c_int, vp, vp]
@@ -818,6 +841,35 @@ class Context:
                                             C.byref(hs["F"]), C.byref(hs["E"]), C.byref(hs["H"]), _ptr(msk), _ptr(msw)), "r3dm_filter_FEH")
         return {k: Graph(hs[k].value) for k in which}, msk, msw
 
+    def set_guided_matching(self, enable: bool = True, ratio_F: float = 0.6, ratio_E: float = 0.6, ratio_H: float = -1.0):
+        """r3dm_set_guided_matching: the filters return the guided lists of their accepted pairs (ratio < 0: geometry only)"""
+        self._check(self._L.r3dm_set_guided_matching(self._h, int(bool(enable)), ratio_F, ratio_E, ratio_H), "r3dm_set_guided_matching")
+
+    def guided_match(self, pairs, kind: str, models, threshold_px, ratio: float) -> Graph:
+        """r3dm_guided_match: guided matching of `pairs` (a Graph -- only its pair list is read -- or an (P, 2) array in (I, J) order)
+        with the caller's models (P x 9: F, E or H) and thresholds (P, as filter_report reports them); ratio < 0: geometry only"""
+        if isinstance(pairs, Graph):
+            g = pairs
+        else:
+            pa = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+            key = pa[:, 0].astype(np.uint64) << np.uint64(32) | pa[:, 1].astype(np.uint64)
+            if pa.shape[0] > 1 and not np.all(key[1:] > key[:-1]):
+                raise ValueError("guided_match: pairs must be distinct and in (I, J) order")
+            g = Graph.from_csr(pa, np.arange(pa.shape[0] + 1, dtype=np.uint64), np.zeros((pa.shape[0], 2), np.uint32))
+        P = g.num_pairs
+        M = np.ascontiguousarray(models, np.float64).reshape(P, 9)
+        T = np.ascontiguousarray(threshold_px, np.float64).reshape(P)
+        h = C.c_void_p()
+        self._check(self._L.r3dm_guided_match(self._h, g._h, GUIDED_KIND[kind], _ptr(M) if P else None, _ptr(T) if P else None, float(ratio),
+                                              C.byref(h)), "r3dm_guided_match")
+        return Graph(h.value)
+
+    def guided_report(self) -> dict:
+        """r3dm_guided_report: the last guided step (times, pairs, queries, candidates, matches, candidates per query)"""
+        s = GuidedStats()
+        self._check(self._L.r3dm_guided_report(self._h, C.byref(s)), "r3dm_guided_report")
+        return s.as_dict()
+
     def knn2(self, dataset: np.ndarray, query: np.ndarray, binary: bool = False):
         dataset = np.ascontiguousarray(dataset); query = np.ascontiguousarray(query)
         dt = F32 if dataset.dtype == np.float32 else (BIN if binary else U8)
@@ -1025,6 +1077,9 @@ class MultiContext:
 
     def set_integer_mfma(self, enable: bool = True):
         self._check(self._L.r3dm_multi_set_integer_mfma(self._h, int(bool(enable))), "r3dm_multi_set_integer_mfma")
+
+    def set_guided_matching(self, enable: bool = True, ratio_F: float = 0.6, ratio_E: float = 0.6, ratio_H: float = -1.0):
+        self._check(self._L.r3dm_multi_set_guided_matching(self._h, int(bool(enable)), ratio_F, ratio_E, ratio_H), "r3dm_multi_set_guided_matching")
 
     def extract_features(self, images, feat_paths, desc_paths, threshold: float = 0.001, bgr: bool = False, batch: int = 0):
         """r3dm_multi_extract_features(_bgr8): the features stage over an image list, one BATCH of same-size images in flight per context.

@@ -29,6 +29,10 @@ struct FilterCallOut {
     double ms_kernels = 0.0, ms_wall = 0.0;
     std::vector<r3dm_pair_report> report;
     r3dm_graph* pending = nullptr;        // the graph under construction between filter_prepare and its collect
+    // guided matching on (r3dm_set_guided_matching): collect leaves the accepted pairs as jobs of the call's one guided launch, and
+    // `finish` builds the graph from their lists (job k of this call is job first + k of the launch)
+    std::vector<GuidedJob> gjobs;
+    std::function<int(const GuidedResult&, size_t first)> finish;
     ~FilterCallOut() { delete pending; }
 };
 #define FHIP(call)                                                                     \
@@ -447,6 +451,55 @@ static int filter_prepare(r3dm_ctx* c, FilterCallOut& o, const r3dm_graph* putat
         }
     }
 
+    if (c->guided_on) {
+        // the pairs AC-RANSAC accepted (> 2.5 x MINIMUM_SAMPLES inliers) are re-matched by guided matching; their lists replace the
+        // inliers once the call's guided launch has run (`finish`); models and report stay AC-RANSAC's
+        const int pub = model_kind == 0 ? R3DM_GUIDED_F : (model_kind == 1 ? R3DM_GUIDED_H : R3DM_GUIDED_E);
+        std::vector<uint32_t> acc;
+        for (uint32_t k = 0; k < NI; ++k) {
+            if ((double)h_cnt[k] <= 2.5 * SS) continue;
+            GuidedJob jb;
+            const int grc = guided_job_make(c, slots[k].x, slots[k].y, pub, h_F.data() + 9 * (size_t)k, o.report[item_pair[k]].threshold_px,
+                                            c->guided_ratio[pub], jb);
+            if (grc != R3DM_OK) { o.err = c->err; return grc; }
+            o.gjobs.push_back(jb);
+            acc.push_back(k);
+        }
+        o.pending = g.release();
+        o.finish = [=, &o](const GuidedResult& R, size_t first) -> int {
+            std::unique_ptr<r3dm_graph> g(o.pending);
+            o.pending = nullptr;
+            const bool mirror = c->device_graphs;
+            if (mirror) { g->dev.valid = true; g->dev.device = c->device; }
+            std::vector<uint32_t> m_ids, m_cnts;
+            std::vector<GraphSeg> m_segs;
+            uint64_t kept = 0;
+            for (size_t a = 0; a < acc.size(); ++a) {
+                const uint32_t k = acc[a], p = item_pair[k];
+                const uint32_t n = R.cnt[first + a];
+                const uint32_t q0 = o.gjobs[a].q0;
+                // Regard3D's overlap rule behind the E filter applies to the guided list (it runs after Get_geometric_matches())
+                if (model_kind == 2 && (n < min_count || (float)n / (float)(putative->offsets[p + 1] - putative->offsets[p]) < min_ratio)) continue;
+                if (n == 0) continue;                          // no empty entries ("Guided matching")
+                g->pairs.push_back(putative->pairs[2 * p]); g->pairs.push_back(putative->pairs[2 * p + 1]);
+                const uint64_t at = g->matches.size();
+                g->matches.insert(g->matches.end(), R.host + q0, R.host + q0 + n);
+                g->offsets.push_back(g->matches.size());
+                if (mirror) {
+                    m_ids.push_back(putative->pairs[2 * p]); m_ids.push_back(putative->pairs[2 * p + 1]); m_cnts.push_back(n);
+                    m_segs.push_back(GraphSeg{q0, 0, at, n, 0});
+                }
+                if (F_out) memcpy(F_out + 9 * kept, h_F.data() + 9 * (size_t)k, 72);
+                ++kept;
+            }
+            if (mirror) (void)graph_dev_append(c, g.get(), m_ids, m_cnts, m_segs, R.dev, nullptr);
+            o.ms_wall = now_ms() - t_call;
+            *out = g.release();
+            return R3DM_OK;
+        };
+        return R3DM_OK;
+    }
+
     uint64_t kept = 0;
     {
         uint64_t total_kept = 0;
@@ -630,6 +683,12 @@ static int filter_one(r3dm_ctx* c, const r3dm_graph* putative, double max_residu
     int rc = filter_prepare(c, o, putative, max_residual_px, max_iter, seed, err_kind, model_kind, out, M_out, min_count, min_ratio, fp, plan, collect);
     if (rc == R3DM_OK) rc = filter_launch(c, o, &fp, &plan, 1, &ms);
     if (rc == R3DM_OK) rc = collect(ms);
+    if (rc == R3DM_OK && c->guided_on) {                  // (also without accepted pairs: the guided report then says so)
+        GuidedResult R;
+        rc = guided_run(c, o.gjobs, R);
+        if (rc == R3DM_OK && o.finish) rc = o.finish(R, 0);
+        if (rc != R3DM_OK) o.err = c->err;
+    }
     if (rc != R3DM_OK && !o.err.empty()) c->err = o.err;
     c->stats.ms_filter_kernels = o.ms_kernels;
     c->stats.ms_wall_filter = o.ms_wall;
@@ -769,6 +828,20 @@ extern "C" int r3dm_filter_FEH(r3dm_ctx* c, const r3dm_graph* putative, double m
             if (ms_kernels3) ms_kernels3[k.slot] = ms[i];
             if (ms_wall3) ms_wall3[k.slot] = k.o.ms_wall;
             if (rc == R3DM_OK && (k.kind == 2 || !(which & 2))) c->report = k.o.report;       // the E call's diagnostics, else the last one's
+        }
+        // guided matching on: ONE launch re-matches the accepted pairs of every kind of the call, then each kind builds its graph
+        if (rc == R3DM_OK && c->guided_on) {
+            std::vector<GuidedJob> all;
+            std::vector<size_t> first(calls.size(), 0);
+            for (size_t i = 0; i < calls.size(); ++i) { first[i] = all.size(); all.insert(all.end(), calls[i]->o.gjobs.begin(), calls[i]->o.gjobs.end()); }
+            GuidedResult R;
+            rc = guided_run(c, all, R);
+            for (size_t i = 0; i < calls.size() && rc == R3DM_OK; ++i) {
+                Call& k = *calls[i];
+                for (size_t a = 0; a < k.o.gjobs.size(); ++a) k.o.gjobs[a].q0 = all[first[i] + a].q0;
+                if (k.o.finish) rc = k.o.finish(R, first[i]);    // (a kind without work items -- E without intrinsics -- has its graph already)
+                if (ms_wall3) ms_wall3[k.slot] = k.o.ms_wall;
+            }
         }
         c->stats.ms_filter_kernels = ms_max;
         if (r3dm_dev_knob("R3DM_FILTER_TIMING", 0))

@@ -201,6 +201,16 @@ extern "C" int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) {
+        const int rc = r3dm_set_guided_matching(c, enable, ratio_F, ratio_E, ratio_H);
+        if (rc != R3DM_OK) return rc;
+    }
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,
                                       float dist_ratio, int squared_metric, r3dm_graph** out)
 {

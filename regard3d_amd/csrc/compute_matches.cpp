@@ -323,6 +323,12 @@ void R3DComputeMatches::setHammingFastPath(bool on)
     if (multi_) for (int k = 0; k < r3dm_multi_num_devices(multi_); ++k) (void)r3dm_set_hamming_mfma(r3dm_multi_ctx(multi_, k), on ? 1 : 0);
 }
 
+void R3DComputeMatches::setGuidedMatching(bool on, double ratio_F, double ratio_E, double ratio_H)
+{
+    if (ctx_) (void)r3dm_set_guided_matching(ctx_, on ? 1 : 0, ratio_F, ratio_E, ratio_H);
+    if (multi_) (void)r3dm_multi_set_guided_matching(multi_, on ? 1 : 0, ratio_F, ratio_E, ratio_H);
+}
+
 void R3DComputeMatches::setRegionsType(r3dm_dtype dtype, uint32_t dim) { dtype_ = dtype; dim_ = dim; }
 
 bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const R3DProjectPaths& paths,
@@ -679,6 +685,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setApproximateArmsPolicy((flags & R3DM_STAGE_ARMS_AS_REQUESTED) ? r3d_amd::R3DComputeMatches::kArmsAsRequested : r3d_amd::R3DComputeMatches::kArmsFastest);
         stage.setBackgroundThreadsNice((flags & R3DM_STAGE_BACKGROUND_NICE) ? 10 : 0);
         stage.setExactFastPaths((flags & R3DM_STAGE_F32_TILES) == 0);      // (R3DM_STAGE_SPLIT_MFMA / _INTEGER_MFMA: implied since round 3)
+        stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         r3d_amd::R3DFParams params;
         params.keypointDetectorList_ = {"Fast-AKAZE"};
         params.threshold_ = threshold;

@@ -353,6 +353,28 @@ struct FilterBufs {
     }
 };
 
+// Guided matching (kernels_guided.hip, api_guided.cpp): the work buffers of a call's one launch, and what it hands back
+struct GuidedBufs {
+    DevBuf jobs, res, q_cnt, q_off, blk_cnt, blk_base, cand, ctr, out, out_cnt;
+    PinBuf pin_out, pin_small, pin_blk;
+    void release()
+    {
+        DevBuf* b[] = {&jobs, &res, &q_cnt, &q_off, &blk_cnt, &blk_base, &cand, &ctr, &out, &out_cnt};
+        for (DevBuf* x : b) x->release();
+        pin_out.release(); pin_small.release(); pin_blk.release();
+    }
+};
+struct GuidedResult {
+    std::vector<uint32_t> cnt;             // matches of every job
+    const r3dm_match* host = nullptr;      // job k's list at host + jobs[k].q0 (page-locked, valid until the next guided call)
+    const r3dm_match* dev = nullptr;       // the same on the device (the source of graph mirrors)
+};
+// one job of a guided launch: pub_kind R3DM_GUIDED_F / _E / _H, M the model as the filter returns it, thr_px as r3dm_pair_report
+// reports it, ratio < 0: geometry only
+int guided_job_make(r3dm_ctx* c, uint32_t sI, uint32_t sJ, int pub_kind, const double* M, double thr_px, double ratio, GuidedJob& out);
+// runs the jobs (q0 / b0 are assigned here), fills c->guided_stats; jobs may be empty
+int guided_run(r3dm_ctx* c, std::vector<GuidedJob>& jobs, GuidedResult& R);
+
 // The way of a view from host memory to HBM (r3dm_set_image / r3dm_set_images): a ring of page-locked slots the caller's pageable rows
 // are copied into by the host (several threads for a batch of views), one asynchronous DMA per view from there into the slot's
 // device buffer, the staging kernel behind it, an event behind that -- a slot is reused when its event has passed; nothing waits
@@ -443,6 +465,11 @@ struct r3dm_ctx {
     int file_writer_rc = 0; std::string file_writer_err;
     double file_writer_ms = 0.0;                             // wall time the writer threads spent (sum since the last wait)
     std::vector<r3dm_pair_report> report;                    // last r3dm_filter_F call, one per putative pair
+    // r3dm_set_guided_matching: the filters re-match their accepted pairs; ratios by R3DM_GUIDED_F / _E / _H (< 0: geometry only)
+    bool guided_on = false;
+    double guided_ratio[3] = {0.6, 0.6, -1.0};
+    GuidedBufs gb;
+    r3dm_guided_stats guided_stats{};                        // last guided step (r3dm_guided_report)
 };
 
 #define R3DM_HIP(ctx, call)                                                            \

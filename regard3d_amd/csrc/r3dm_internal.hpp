@@ -436,6 +436,40 @@ hipError_t launch_liop_extract(hipStream_t st, const float* image, int w, int h,
 struct GraphSeg { uint64_t src, idx, dst; uint32_t cnt, pad; };
 hipError_t launch_graph_gather(hipStream_t st, const r3dm_match* src, const uint32_t* idx, const GraphSeg* segs, uint32_t n_segs, r3dm_match* dst);
 
+// guided matching (kernels_guided.hip; OpenMVG's geometry_aware::GuidedMatching): one job per pair, the queries are the rows of I
+struct GuidedJob {
+    double M[9];               // kind 0: F (for E: K_J^-T E K_I^-1), kind 1: H (x_J ~ H x_I)
+    double errTh;              // a candidate passes iff err < errTh (f64, strict)
+    double R;                  // ratio^2 of the descriptor mode
+    uint32_t sI, sJ;           // slots of the two views
+    uint32_t kind;             // 0 = EpipolarDistanceError, 1 = homography AsymmetricError
+    uint32_t flags;            // kGuidedDesc: descriptor mode (else geometry only); kGuidedDedup: coordinate de-duplication; kGuidedBin: Hamming on bin rows
+    uint32_t q0;               // first query of the job in the call's query numbering
+    uint32_t b0;               // first workgroup of the job
+    uint32_t nI, pad;
+};
+constexpr uint32_t kGuidedDesc = 1u, kGuidedDedup = 2u, kGuidedBin = 4u;
+struct GuidedParams {
+    const ImgDev* imgs;
+    const GuidedJob* jobs;
+    uint32_t n_jobs, n_blocks;
+    uint32_t b_lo;             // the launch covers workgroups [b_lo, b_lo + n_blocks) of the call (chunks of the descriptor passes)
+    uint32_t* res;             // [queries] matched row of J or kNone
+    uint32_t* q_cnt;           // [queries] candidates (gate passed) of a descriptor-mode query
+    unsigned long long* q_off; // [queries] their offset in cand (written by pass 1, relative to the chunk)
+    unsigned long long* blk_cnt;         // [workgroups] candidates of a workgroup's descriptor-mode queries (pass 0)
+    const unsigned long long* blk_base;  // [workgroups] where a workgroup's candidates start in cand, relative to its chunk
+    uint32_t* cand;            // candidate rows of J, ascending per query: the lists of one chunk of workgroups
+    unsigned long long* ctr;   // [0] candidates of every query (all modes)
+    r3dm_match* out;           // [queries]: job k's list at [q0, q0 + out_cnt[k])
+    uint32_t* out_cnt;         // [jobs]
+};
+constexpr uint32_t kGuidedTile = 4096;     // positions of J per LDS stage (32 KiB)
+// pass 0: gate every (i, j), resolve geometry-only queries, count the candidates of descriptor-mode queries; pass 1: write them
+hipError_t launch_guided_sweep(hipStream_t st, const GuidedParams& P, int pass);
+hipError_t launch_guided_desc(hipStream_t st, const GuidedParams& P);
+hipError_t launch_guided_compact(hipStream_t st, const GuidedParams& P);
+
 // geometry tables of the 41 x 41 LIOP patch (api_features.cpp: liop_prepare), all in device memory
 struct LiopTables {
     const int* pix;            // [n_pix] support pixels in scan order, as offsets into the zero-ringed 43 x 43 patch
