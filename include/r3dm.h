@@ -443,6 +443,25 @@ int r3dm_detect_akaze_batch(r3dm_ctx* ctx, uint32_t n_images, const float* const
 int r3dm_detect_akaze_mldb(r3dm_ctx* ctx, const float* image, uint32_t width, uint32_t height, float threshold,
                            float* keypoints_out, unsigned char* descriptors_out, uint32_t cap, uint32_t* n_out);
 
+/* ---- keypoint detection: classic A-KAZE ----
+ * The "AKAZE" arm of Regard3DFeatures::detectKeypoints (src/Regard3DFeatures.cpp:578-589), the GUI's default detector:
+ * cv::AKAZE::create(DESCRIPTOR_MLDB, 0, 3, threshold, 4, 4, DIFF_PM_G2) + detect(), restated as libAKAZE, the classic code of the
+ * reference tree (src/thirdparty/akaze/lib/, AKAZEConfig.h defaults): nonlinear scale space by FED, scale-normalised multiscale
+ * derivatives, determinant-of-Hessian extrema with libAKAZE's sequential kpts_aux rule, the upper-level filter, sub-pixel refinement.
+ * Orientation: libAKAZE's Feature_Detection leaves the angle 0, OpenCV 4's detect() assigns one; this arm computes
+ * Compute_Main_Orientation on the level's multiscale Lx / Ly and returns it in DEGREES in [0, 360) with NO + 90 (Regard3D converts
+ * the Fast arm's angle only).  Parity with OpenCV is UNPINNED (its 4.x extrema search is a reworked parallel form): DESIGN.md section 7.
+ * Arguments and output layout as r3dm_detect_akaze: keypoints_out cap x 4 floats (x, y, size, angle in degrees), responses_out optional,
+ * *n_out may exceed cap, output in the reference's order (kpts_aux slot order). */
+int r3dm_detect_akaze_classic(r3dm_ctx* ctx, const float* image, uint32_t width, uint32_t height, float threshold,
+                              float* keypoints_out, float* responses_out, uint32_t cap, uint32_t* n_out);
+
+/* The same over a batch of n_images same-size images in one pass (arguments as r3dm_detect_akaze_batch); results per image are
+ * bit-identical to r3dm_detect_akaze_classic on that image. */
+int r3dm_detect_akaze_classic_batch(r3dm_ctx* ctx, uint32_t n_images, const float* const* images, uint32_t width, uint32_t height,
+                                    float threshold, float* const* keypoints_out, float* const* responses_out, uint32_t cap,
+                                    uint32_t* n_out);
+
 /* ---- the per-image work item of the features stage ----
  * R3DFeaturesThread::processWorkItem (src/threads/R3DFeaturesThread.cpp:123-210) after cv::imread: 8-bit BGR -> float / 255 ->
  * BGR2GRAY (r3dm_gray_from_bgr8; bgr = height x width x 3 bytes, gray_out = height x width floats, host or device), then

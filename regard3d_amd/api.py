@@ -26,7 +26,7 @@ EXPORTS = [
     "r3dm_graph_merge", "r3dm_save_matches", "r3dm_load_matches", "r3dm_get_stats", "r3dm_filter_report",
     "r3dm_compute_matches_dir", "r3dm_compute_matches_stage", "r3dm_stage_create", "r3dm_stage_run", "r3dm_stage_destroy", "r3dm_liop_describe_patches", "r3dm_extract_liop",
     "r3dm_set_intrinsics", "r3dm_filter_E", "r3dm_ann_params_for_algorithm", "r3dm_detect_akaze", "r3dm_detect_akaze_mldb", "r3dm_gray_from_bgr8", "r3dm_extract_features_to_files", "r3dm_multi_extract_features",
-    "r3dm_detect_akaze_batch", "r3dm_extract_features_batch", "r3dm_multi_extract_features_ex", "r3dm_get_features_totals", "r3dm_kgraph_preset", "r3dm_match_pairs_kgraph", "r3dm_exhaustive_is_faster", "r3dm_kgraph_knn2", "r3dm_kgraph_index", "r3dm_drop_indices",
+    "r3dm_detect_akaze_batch", "r3dm_detect_akaze_classic", "r3dm_detect_akaze_classic_batch", "r3dm_extract_features_batch", "r3dm_multi_extract_features_ex", "r3dm_get_features_totals", "r3dm_kgraph_preset", "r3dm_match_pairs_kgraph", "r3dm_exhaustive_is_faster", "r3dm_kgraph_knn2", "r3dm_kgraph_index", "r3dm_drop_indices",
     "r3dm_filter_FEH", "r3dm_host_threads", "r3dm_set_features_sink", "r3dm_multi_set_features_sink", "r3dm_set_deferred_feature_files", "r3dm_set_background_nice", "r3dm_multi_set_background_nice", "r3dm_features_files_wait", "r3dm_multi_set_deferred_feature_files", "r3dm_multi_features_files_wait", "r3dm_hnsw_preset", "r3dm_match_pairs_hnsw", "r3dm_hnsw_knn2", "r3dm_hnsw_knn2_on_index", "r3dm_hnsw_index",
     "r3dm_mrpt_preset", "r3dm_match_pairs_mrpt", "r3dm_mrpt_knn2", "r3dm_mrpt_index", "r3dm_multi_match_pairs_mrpt",
     "r3dm_set_integer_mfma", "r3dm_set_split_mfma", "r3dm_set_hamming_mfma", "r3dm_index_create", "r3dm_index_knn2", "r3dm_index_destroy",
@@ -314,6 +314,8 @@ def load_library():
     L.r3dm_multi_extract_features_ex.argtypes = [vp, u32, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, u32, C.c_char_p, C.c_size_t]
     L.r3dm_get_features_totals.argtypes = [vp, vp]
     L.r3dm_detect_akaze_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
+    L.r3dm_detect_akaze_classic.argtypes = [vp, vp, u32, u32, C.c_float, vp, vp, u32, C.POINTER(u32)]
+    L.r3dm_detect_akaze_classic_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
     L.r3dm_extract_features_batch.argtypes = [vp, u32, vp, vp, u32, u32, C.c_float, vp, vp, vp]
     L.r3dm_kgraph_preset.argtypes = [C.c_int, vp]
     L.r3dm_ann_params_for_algorithm.argtypes = [C.c_int, vp]
@@ -952,6 +954,32 @@ class Context:
         kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); rp_p = (C.c_void_p * B)(*[r.ctypes.data for r in resp])
         n = np.zeros(B, np.uint32)
         self._check(self._L.r3dm_detect_akaze_batch(self._h, B, ip, w, h, threshold, kp_p, rp_p, cap, _ptr(n)), "r3dm_detect_akaze_batch")
+        return [(kps[b][:min(int(n[b]), cap)].copy(), resp[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
+
+    def detect_akaze_classic(self, image, threshold: float = 0.001, cap: int = 200000):
+        """r3dm_detect_akaze_classic, Regard3D's "AKAZE" arm (libAKAZE): image [h, w] float32 in [0, 1] (numpy or torch, host or device)
+        -> (keypoints [n, 4] (x, y, size, angle in degrees, no + 90), responses [n])"""
+        h, w = int(image.shape[0]), int(image.shape[1])
+        if isinstance(image, np.ndarray):
+            image = np.ascontiguousarray(image, np.float32)
+        kps = np.zeros((cap, 4), np.float32); resp = np.zeros(cap, np.float32)
+        n = C.c_uint32(0)
+        self._check(self._L.r3dm_detect_akaze_classic(self._h, _ptr(image), w, h, threshold, _ptr(kps), _ptr(resp), cap, C.byref(n)),
+                    "r3dm_detect_akaze_classic")
+        k = min(n.value, cap)
+        return kps[:k].copy(), resp[:k].copy()
+
+    def detect_akaze_classic_batch(self, images, threshold: float = 0.001, cap: int = 200000):
+        """r3dm_detect_akaze_classic_batch: B same-size images in one pass -> list of (keypoints [n, 4], responses [n])"""
+        imgs = [im if hasattr(im, "data_ptr") else np.ascontiguousarray(im, np.float32) for im in images]
+        B = len(imgs); h, w = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+        assert all(tuple(im.shape) == (h, w) for im in imgs), "a batch holds images of one size"
+        ip = (C.c_void_p * B)(*[(im.data_ptr() if hasattr(im, "data_ptr") else im.ctypes.data) for im in imgs])
+        kps = [np.zeros((cap, 4), np.float32) for _ in range(B)]; resp = [np.zeros(cap, np.float32) for _ in range(B)]
+        kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); rp_p = (C.c_void_p * B)(*[r.ctypes.data for r in resp])
+        n = np.zeros(B, np.uint32)
+        self._check(self._L.r3dm_detect_akaze_classic_batch(self._h, B, ip, w, h, threshold, kp_p, rp_p, cap, _ptr(n)),
+                    "r3dm_detect_akaze_classic_batch")
         return [(kps[b][:min(int(n[b]), cap)].copy(), resp[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
 
     def extract_features_batch(self, images, feat_paths, desc_paths, threshold: float = 0.001, bgr: bool = False):

@@ -54,6 +54,7 @@ extern "C" void r3dm_destroy(r3dm_ctx* c)
     c->coop_ev = nullptr; c->coop_stream = nullptr;
     for (DevBuf* b : bufs) b->release();
     for (DevBuf& b : c->ak_bufs) b.release();
+    for (DevBuf& b : c->ac_bufs) b.release();
     for (auto& im : c->spare) if (im) im->release();
     c->pin_desc.release(); c->pin_out.release(); c->pin_small.release(); c->tab_host.release(); c->tab_back.release();
     c->ring.release();

@@ -45,6 +45,9 @@ std::vector<AkLevelHost> ak_levels(int w, int h)
     return lv;
 }
 
+}  // namespace
+
+// (ak_taps and ak_area_tab also serve the classic arm: api_akaze_classic.cpp)
 // getGaussianKernel(n, sigma, CV_32F) for gaussian_2D_convolutionV2's kernel size rule (nldiffusion_functions.cpp:39-58)
 AkTaps ak_taps(float sigma)
 {
@@ -119,8 +122,6 @@ void ak_area_tab(int ssize, int dsize, std::vector<AkAreaTab>& tab, std::vector<
     }
     begin[dsize] = (int)tab.size();
 }
-
-}  // namespace
 
 // ------------------------------------------------------------------------------------------------
 // The detector over a BATCH of B same-size images.  One image alone cannot fill the chip below the first octave: its ~550

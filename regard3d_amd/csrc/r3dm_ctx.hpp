@@ -294,6 +294,10 @@ inline bool has_tensor_kernel(uint32_t G) { return G == 8 || G == 16 || G == 18 
 
 inline uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
+// Gaussian taps and INTER_AREA tables of the detectors (api_features.cpp; shared by the classic arm, api_akaze_classic.cpp)
+AkTaps ak_taps(float sigma);
+void ak_area_tab(int ssize, int dsize, std::vector<AkAreaTab>& tab, std::vector<int>& begin);
+
 inline double now_ms()
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -438,6 +442,7 @@ struct r3dm_ctx {
     DevBuf a_jobs, a_scratch, a_ids, d_spill, d_fb2;
     DevBuf m_raw, m_peer;                                   // r3dm_multi_set_image: the one upload of a view / this device's copy of it
     std::vector<DevBuf> ak_bufs;                            // Fast-A-KAZE work buffers of the last image size, ak_B planes each
+    std::vector<DevBuf> ac_bufs;                            // classic A-KAZE work buffers (api_akaze_classic.cpp: grow, never shrink)
     int ak_w = 0, ak_h = 0, ak_B = 0;
     uint32_t ak_cap = 0;                                    // candidate slots per image the detector last needed (grows, never shrinks)
     int ak_n_levels = 0;

@@ -368,6 +368,31 @@ hipError_t ak_list_ranges(hipStream_t st, const AkLevelDev* levels, int n_levels
 hipError_t ak_cross(hipStream_t st, const AkLevelDev* levels, int n_levels, int B, int mode);
 hipError_t ak_refine(hipStream_t st, const AkLevelDev* levels, int n_levels, int B);
 hipError_t ak_compact(hipStream_t st, const AkLevelDev* levels, int n_levels, int B, AkKpRec* recs, uint32_t cap, AkBatchMeta* meta);
+
+// ---- classic A-KAZE detector (kernels_akaze_classic.hip) ----
+constexpr int kAcMaxLevels = 16;                        // 4 octaves x 4 sublevels
+struct AcCand { uint32_t x, y, level; float value; };   // a 3 x 3 maximum of one level, in the reference's scan order
+struct AcSlot { float x, y, size, resp; uint32_t cls, pad; };   // an entry of kpts_aux (x, y in image coordinates)
+struct AcOut { float x, y, size, angle, resp; uint32_t ok, pad0, pad1; };   // a slot after the upper-level filter, refinement, orientation
+struct AcLevelTab {
+    int n_levels;
+    int w[kAcMaxLevels], h[kAcMaxLevels], octave[kAcMaxLevels];
+    float esigma[kAcMaxLevels], ratio[kAcMaxLevels], off[kAcMaxLevels];   // off = .5 (ratio - 1)
+    float smax;                                          // 10 sqrt(2) as the reference forms it
+};
+// the spatial grid of the kpts_aux walk, per image: cells_stride heads (-1 = empty) and ent_stride entries (slot, cell, next)
+struct AcGrid { int* heads; uint32_t* ent_slot; uint32_t* ent_cell; int* ent_next; size_t cells_stride, ent_stride; int img_w, img_h; };
+struct AcPlanes { const float* ldet[kAcMaxLevels]; const float* lx[kAcMaxLevels]; const float* ly[kAcMaxLevels]; };
+hipError_t ac_kcontrast(hipStream_t st, const float* smooth1, int w, int h, int B, uint32_t* small);
+hipError_t ac_fed_step(hipStream_t st, const float* Lt, const float* Lf, float* out, int w, int h, int B, float half_step);
+hipError_t ac_hessian(hipStream_t st, const float* smooth, float* Lx, float* Ly, float* Ldet, int w, int h, int B, int s, float norm, float kc);
+hipError_t ac_extrema(hipStream_t st, const float* ldet, int w, int h, int B, float thr, uint32_t* row_counts, uint32_t rows_stride,
+                      uint32_t row0, AcCand* cand, uint32_t cand_stride, int level, int pass);
+hipError_t ac_scan_rows(hipStream_t st, uint32_t* row_counts, uint32_t rows_stride, uint32_t n_rows, int B, uint32_t* totals);
+hipError_t ac_aux(hipStream_t st, const AcCand* cand, uint32_t cand_stride, const uint32_t* totals, const AcLevelTab& tab, AcSlot* slots,
+                  const AcGrid& grid, uint32_t* n_slots, int B);
+hipError_t ac_finish(hipStream_t st, const AcSlot* slots, uint32_t stride, const uint32_t* n_slots, const AcLevelTab& tab, const AcPlanes& pl,
+                     AcOut* out, uint32_t max_slots, int B);
 constexpr uint32_t kAkSlotBytes = 80;                  // per candidate slot: cand 16 + list 16 + live 16 + out0 16 + out1 8 + valid 4 + dead 2 (+ 2 spare)
 
 // ---- launchers implemented in the .hip files (host side) ----
