@@ -240,6 +240,7 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_BACKGROUND_NICE  16u   /* background writer threads at nice 10 (R3DComputeMatches::setBackgroundThreadsNice(10)); default: priorities untouched */
 #define R3DM_STAGE_F32_TILES         8u   /* plain f32 MFMA tiles for the exhaustive matcher: R3DComputeMatches::setExactFastPaths(false); same files, slower */
 #define R3DM_STAGE_GUIDED_MATCHING  32u   /* bGuided_matching = true (R3DComputeMatches::setGuidedMatching(true)): the filters' match files hold guided lists */
+#define R3DM_STAGE_DETECTOR_AKAZE   64u   /* keypointDetectorList_ = {"AKAZE"}, the GUI's keypointDetectorType 0 (classic A-KAZE); default {"Fast-AKAZE"} */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,

@@ -462,6 +462,19 @@ int r3dm_detect_akaze_classic_batch(r3dm_ctx* ctx, uint32_t n_images, const floa
                                     float threshold, float* const* keypoints_out, float* const* responses_out, uint32_t cap,
                                     uint32_t* n_out);
 
+/* Component-size histogram of the classic arm's parallel kpts_aux walk since r3dm_create: hist[k] (32 entries) counts the connected
+ * components of "same or adjacent level and within size" with 2^k .. 2^(k+1) - 1 candidates. */
+int r3dm_akaze_classic_components(const r3dm_ctx* ctx, uint64_t* hist);
+
+/* The detector arm of the features entries (r3dm_extract_features_to_files, r3dm_extract_features_batch, r3dm_multi_extract_features
+ * and _ex): Regard3D's keypointDetectorList_ of one entry.  R3DM_DETECTOR_FAST_AKAZE (the default) is r3dm_detect_akaze,
+ * R3DM_DETECTOR_AKAZE the classic arm r3dm_detect_akaze_classic (the GUI's default, keypointDetectorType 0).  Both feed LIOP with
+ * kpSizeFactor 8 (getKpSizeFactor, src/Regard3DFeatures.cpp:691-717); the classic arm's angle is written as it detects it (degrees, no
+ * + 90).  Everything after the detector -- files, sink, deferred files, skip rule -- is the same.  Other values: R3DM_ERR_INVALID. */
+#define R3DM_DETECTOR_FAST_AKAZE 0
+#define R3DM_DETECTOR_AKAZE 1
+int r3dm_set_keypoint_detector(r3dm_ctx* ctx, int arm);
+
 /* ---- the per-image work item of the features stage ----
  * R3DFeaturesThread::processWorkItem (src/threads/R3DFeaturesThread.cpp:123-210) after cv::imread: 8-bit BGR -> float / 255 ->
  * BGR2GRAY (r3dm_gray_from_bgr8; bgr = height x width x 3 bytes, gray_out = height x width floats, host or device), then
@@ -559,6 +572,8 @@ int r3dm_multi_filter_E(r3dm_multi* m, const r3dm_graph* putative, double max_re
                         uint64_t seed, uint32_t min_count, float min_ratio, r3dm_graph** out, double* E_out);
 /* r3dm_set_guided_matching on every device context: r3dm_multi_filter_* then return guided lists */
 int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H);
+/* r3dm_set_keypoint_detector on every device context: the arm of r3dm_multi_extract_features and _ex */
+int r3dm_multi_set_keypoint_detector(r3dm_multi* m, int arm);
 /* The features stage over an image list: R3DFeaturesThread::extractFeaturesAndDescriptors (src/threads/R3DFeaturesThread.cpp:38-121),
  * whose worker pool pulls images off a work list and runs processWorkItem on each.  Here every context of `m` is a worker that pulls
  * BATCHES of same-size images (r3dm_extract_features_batch: up to 8 per detector pass): create

@@ -100,7 +100,7 @@ public:
     {
         return {"AKAZE", "Fast-AKAZE", "MSER", "ORB", "BRISK", "GFTT"};
     }
-    static bool isDetectorServed(const std::string& fdname) { return fdname == "Fast-AKAZE"; }
+    static bool isDetectorServed(const std::string& fdname) { return fdname == "Fast-AKAZE" || fdname == "AKAZE"; }
     static std::vector<std::string> getFeatureExtractors() { return {"LIOP"}; }            // src/Regard3DFeatures.cpp:198-204
 
     // src/Regard3DFeatures.cpp:206-222.  Appends to feats / descs (the reference never clears them either).
@@ -134,14 +134,16 @@ public:
         vec_keypoints.clear();
         if (!isDetectorServed(fdname))
             throw std::runtime_error("Regard3DFeatures::detectKeypoints: detector \"" + fdname +
-                                     "\" is not computed by the GPU library (only \"Fast-AKAZE\" is)");
+                                     "\" is not computed by the GPU library (only \"Fast-AKAZE\" and \"AKAZE\" are)");
         SemaLocker locker;                                       // AKAZESemaLocker (:580, :592)
         detail::ContextLease lease(detail::ContextPool::of(device()));
         if (!lease.ctx) throw std::runtime_error("Regard3DFeatures::detectKeypoints: no usable gfx950 device");
+        // "AKAZE": the classic arm (libAKAZE, r3dm_detect_akaze_classic), angle in degrees as it detects it; "Fast-AKAZE": :604-613
+        auto* const detect = fdname == "AKAZE" ? &r3dm_detect_akaze_classic : &r3dm_detect_akaze;
         uint32_t n = 0, cap = 65536;
         for (int attempt = 0; attempt < 2; ++attempt) {
             vec_keypoints.resize(cap);
-            if (r3dm_detect_akaze(lease.ctx, img.data(), (uint32_t)img.Width(), (uint32_t)img.Height(), params.threshold_,
+            if (detect(lease.ctx, img.data(), (uint32_t)img.Width(), (uint32_t)img.Height(), params.threshold_,
                                   reinterpret_cast<float*>(vec_keypoints.data()), nullptr, cap, &n) != R3DM_OK) {
                 vec_keypoints.clear();
                 throw std::runtime_error(std::string("Regard3DFeatures::detectKeypoints: ") + r3dm_last_error(lease.ctx));

@@ -37,9 +37,18 @@ EXPORTS = [
     "r3dm_allgather_graphs", "r3dm_graphs_pack", "r3dm_words_free", "r3dm_graphs_unpack_merge",
     "r3dm_set_device_graphs", "r3dm_graph_on_device", "r3dm_comm_last_device_graphs",
     "r3dm_guided_match", "r3dm_set_guided_matching", "r3dm_guided_report", "r3dm_multi_set_guided_matching",
+    "r3dm_set_keypoint_detector", "r3dm_multi_set_keypoint_detector", "r3dm_akaze_classic_components",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
+STAGE_DETECTOR_AKAZE = 64
+DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
+
+
+def _detector_flag(detector: str) -> int:
+    if detector not in DETECTORS:
+        raise ValueError(f"detector must be one of {sorted(DETECTORS)}, not {detector!r}")
+    return STAGE_DETECTOR_AKAZE if detector == "AKAZE" else 0
 
 
 class R3dmError(RuntimeError):
@@ -144,15 +153,17 @@ class Stage:
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-            guided: bool = False) -> StageReport:
-        """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING)"""
+            guided: bool = False, detector: str = "Fast-AKAZE") -> StageReport:
+        """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
+        (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0)"""
+        dflag = _detector_flag(detector)
         keep = []
         arr = _stage_views(views, keep)
         rep = StageReport(); err = C.create_string_buffer(1024)
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                     (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                    | (STAGE_GUIDED_MATCHING if guided else 0), C.byref(rep), err, 1024)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0) | dflag, C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -173,10 +184,12 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-                          guided: bool = False) -> StageReport:
+                          guided: bool = False, detector: str = "Fast-AKAZE") -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
-    gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy."""
+    gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
+    detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE)."""
+    dflag = _detector_flag(detector)
     L = load_library()
     keep = []
     arr = _stage_views(views, keep)
@@ -186,7 +199,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                       (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                      | (STAGE_GUIDED_MATCHING if guided else 0), C.byref(rep), err, 1024)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0) | dflag, C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
@@ -303,6 +316,9 @@ def load_library():
     L.r3dm_set_guided_matching.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
     L.r3dm_guided_report.argtypes = [vp, vp]
     L.r3dm_multi_set_guided_matching.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
+    L.r3dm_set_keypoint_detector.argtypes = [vp, C.c_int]
+    L.r3dm_multi_set_keypoint_detector.argtypes = [vp, C.c_int]
+    L.r3dm_akaze_classic_components.argtypes = [vp, vp]
     L.r3dm_liop_describe_patches.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.r3dm_extract_liop.argtypes = [vp, vp, u32, u32, vp, u32, C.c_float, vp, vp]
     L.r3dm_knn2.argtypes = [vp, vp, u32, vp, u32, u32, C.c_int, vp, vp]
@@ -847,6 +863,18 @@ class Context:
         """r3dm_set_guided_matching: the filters return the guided lists of their accepted pairs (ratio < 0: geometry only)"""
         self._check(self._L.r3dm_set_guided_matching(self._h, int(bool(enable)), ratio_F, ratio_E, ratio_H), "r3dm_set_guided_matching")
 
+    def set_keypoint_detector(self, detector: str = "Fast-AKAZE"):
+        """r3dm_set_keypoint_detector: the arm of the features entries, "Fast-AKAZE" (default) or "AKAZE" (classic A-KAZE)"""
+        _detector_flag(detector)
+        self._check(self._L.r3dm_set_keypoint_detector(self._h, DETECTORS[detector]), "r3dm_set_keypoint_detector")
+
+    def akaze_classic_components(self) -> np.ndarray:
+        """r3dm_akaze_classic_components: [32] component-size histogram of the classic arm's kpts_aux walk since creation
+        (bin k: components of 2^k .. 2^(k+1) - 1 candidates)"""
+        h = np.zeros(32, np.uint64)
+        self._check(self._L.r3dm_akaze_classic_components(self._h, _ptr(h)), "r3dm_akaze_classic_components")
+        return h
+
     def guided_match(self, pairs, kind: str, models, threshold_px, ratio: float) -> Graph:
         """r3dm_guided_match: guided matching of `pairs` (a Graph -- only its pair list is read -- or an (P, 2) array in (I, J) order)
         with the caller's models (P x 9: F, E or H) and thresholds (P, as filter_report reports them); ratio < 0: geometry only"""
@@ -1108,6 +1136,11 @@ class MultiContext:
 
     def set_guided_matching(self, enable: bool = True, ratio_F: float = 0.6, ratio_E: float = 0.6, ratio_H: float = -1.0):
         self._check(self._L.r3dm_multi_set_guided_matching(self._h, int(bool(enable)), ratio_F, ratio_E, ratio_H), "r3dm_multi_set_guided_matching")
+
+    def set_keypoint_detector(self, detector: str = "Fast-AKAZE"):
+        """r3dm_multi_set_keypoint_detector: the arm of extract_features on every context ("Fast-AKAZE" or "AKAZE")"""
+        _detector_flag(detector)
+        self._check(self._L.r3dm_multi_set_keypoint_detector(self._h, DETECTORS[detector]), "r3dm_multi_set_keypoint_detector")
 
     def extract_features(self, images, feat_paths, desc_paths, threshold: float = 0.001, bgr: bool = False, batch: int = 0):
         """r3dm_multi_extract_features(_bgr8): the features stage over an image list, one BATCH of same-size images in flight per context.

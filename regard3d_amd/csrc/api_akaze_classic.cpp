@@ -79,12 +79,16 @@ std::vector<float> ac_fed_tau(float T)
     return tau;
 }
 
-// the detector over B same-size images; out[b] = the keypoints of image b in the reference's order
-int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
-                    std::vector<std::vector<AcOut>>& out)
+}  // namespace
+
+// the detector over B same-size images; out[b] = the keypoints of image b in the reference's order.  images: B pointers to height x width
+// floats (host or device), or bgrs: B pointers to height x width x 3 bytes, converted on the device by the Fast arm's gray kernel.
+// Leaves the B gray images in ac_bufs[0] (B planes) for the LIOP pass of the features entries.
+int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                    float threshold, std::vector<std::vector<AcOut>>& out)
 {
-    if (!c || B == 0 || !images) return R3DM_ERR_INVALID;
-    for (uint32_t b = 0; b < B; ++b) if (!images[b]) return R3DM_ERR_INVALID;
+    if (!c || B == 0 || (!images && !bgrs)) return R3DM_ERR_INVALID;
+    for (uint32_t b = 0; b < B; ++b) if (!(images ? (const void*)images[b] : (const void*)bgrs[b])) return R3DM_ERR_INVALID;
     if ((uint64_t)width * height > (1ull << 30) || B > 4096) return R3DM_ERR_INVALID;
     out.assign(B, std::vector<AcOut>());
     if (width < 3 || height < 3) return R3DM_OK;                      // no 3 x 3 maximum exists
@@ -100,7 +104,7 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_
     // two evolving images, the smoothed image, the conductivity and a Gaussian scratch; per level Lx, Ly, Ldet (read again by the
     // refinement and the orientation); then the candidate, slot, grid and output arrays
     enum { C_IMG, C_LTA, C_LTB, C_SMOOTH, C_FLOW, C_TMP, C_SMALL, C_ROWS, C_TABS, C_CAND, C_SLOTS, C_NSL, C_OUTS, C_HEADS, C_ESLOT, C_ECELL,
-           C_ENEXT, C_PLANES };
+           C_ENEXT, C_CC, C_UPHEADS, C_UPNEXT, C_PLANES };
     if (c->ac_bufs.size() != (size_t)C_PLANES + 3 * kAcMaxLevels) c->ac_bufs.resize((size_t)C_PLANES + 3 * kAcMaxLevels);
     auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
     DevBuf &img = buf(C_IMG), &ltA = buf(C_LTA), &ltB = buf(C_LTB), &smooth = buf(C_SMOOTH), &flow = buf(C_FLOW), &tmp = buf(C_TMP);
@@ -113,7 +117,14 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_
     auto Lx = [&](int i) { return planes[3 * i].as<float>(); };
     auto Ly = [&](int i) { return planes[3 * i + 1].as<float>(); };
     auto Ldet = [&](int i) { return planes[3 * i + 2].as<float>(); };
-    for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(img.as<float>() + b * n0, images[b], n0 * 4, hipMemcpyDefault, st));
+    if (images) {
+        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(img.as<float>() + b * n0, images[b], n0 * 4, hipMemcpyDefault, st));
+    } else {
+        // 8-bit BGR -> gray as the Fast arm converts it (ak_bgr_to_gray): the bytes are staged in the (not yet used) work image tmp
+        unsigned char* stage = tmp.as<unsigned char>();
+        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(stage + b * n0 * 4, bgrs[b], n0 * 3, hipMemcpyDefault, st));
+        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, ak_bgr_to_gray(st, stage + b * n0 * 4, img.as<float>() + b * n0, n0));
+    }
 
     // INTER_AREA tables of the octave transitions that are not exact halvings
     std::vector<std::array<size_t, 4>> toff(nl, {(size_t)-1, 0, 0, 0});
@@ -221,12 +232,48 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_
         tab.esigma[i] = lv[i].esigma; tab.ratio[i] = lv[i].ratio; tab.off[i] = (float)(.5 * (lv[i].ratio - 1.0));
         pl.ldet[i] = Ldet(i); pl.lx[i] = Lx(i); pl.ly[i] = Ly(i);
     }
-    R3DM_HIP(c, ac_aux(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), iB));
-    R3DM_HIP(c, ac_finish(st, slots.as<AcSlot>(), stride, nsl.as<uint32_t>(), tab, pl, outs.as<AcOut>(), stride, iB));
+    for (int i = 0; i < nl; ++i) tab.row0[i] = row0[i];
+    // R3DM_AC_AUX=0 (developer build): the one-wavefront walk over every candidate and the upper-level filter over every later slot.
+    // R3DM_AC_AUX_BOUND (test hook): a smaller wavefront bound hands more components back to the one-wavefront walk.
+    static const bool parallel = r3dm_dev_knob("R3DM_AC_AUX", 1) != 0;
+    static const uint32_t bound = [] { const int v = r3dm_dev_knob("R3DM_AC_AUX_BOUND", 64); return (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v); }();
+    AcUpGrid ug{};
+    uint32_t* hist = nullptr;
+    if (!parallel) {
+        R3DM_HIP(c, ac_aux(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), iB));
+    } else {
+        // nine per-candidate arrays, then n_big [B], scan totals [B], the histogram [32 B]
+        const size_t per = (size_t)B * stride;
+        R3DM_HIP(c, buf(C_CC).ensure((9 * per + 34 * (size_t)B) * 4));
+        uint32_t* w0 = buf(C_CC).as<uint32_t>();
+        AcCc cc{};
+        uint32_t** arrs[9] = {&cc.par, &cc.csz, &cc.boff, &cc.cur, &cc.memb, &cc.fin, &cc.opn, &cc.big, &cc.bopen};
+        for (int k = 0; k < 9; ++k) *arrs[k] = w0 + (size_t)k * per;
+        cc.n_big = w0 + 9 * per; cc.scratch = cc.n_big + B; hist = cc.hist = cc.scratch + B;
+        cc.rows = rc; cc.rows_stride = rows_stride;
+        R3DM_HIP(c, hipMemsetAsync(hist, 0, (size_t)B * 32 * 4, st));
+        R3DM_HIP(c, ac_aux_parallel(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), cc, bound, iB));
+        // the upper-level filter's buckets: class k >= 1 in cells of side floor(size_{k-1}) + 1 over the image
+        ug.img_w = w; ug.img_h = h;
+        size_t cells = 0;
+        for (int k = 1; k < nl; ++k) {
+            ug.G[k] = (int)(lv[k - 1].esigma * 1.5f) + 1;
+            ug.cell_off[k] = (uint32_t)cells;
+            cells += (size_t)(w / ug.G[k] + 2) * (size_t)(h / ug.G[k] + 2);
+        }
+        ug.cells_stride = std::max<size_t>(cells, 1);
+        R3DM_HIP(c, buf(C_UPHEADS).ensure((size_t)B * ug.cells_stride * 4));
+        R3DM_HIP(c, buf(C_UPNEXT).ensure(per * 4));
+        ug.heads = buf(C_UPHEADS).as<int>(); ug.next = buf(C_UPNEXT).as<int>();
+        R3DM_HIP(c, hipMemsetAsync(ug.heads, 0xFF, (size_t)B * ug.cells_stride * 4, st));
+    }
+    R3DM_HIP(c, ac_finish(st, slots.as<AcSlot>(), stride, nsl.as<uint32_t>(), tab, pl, outs.as<AcOut>(), stride, iB, ug));
     R3DM_HIP(c, hipEventRecord(c->ev1, st));
-    std::vector<uint32_t> ns(B);
+    std::vector<uint32_t> ns(B), hs(hist ? (size_t)B * 32 : 0);
     R3DM_HIP(c, hipMemcpyAsync(ns.data(), nsl.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    if (hist) R3DM_HIP(c, hipMemcpyAsync(hs.data(), hist, hs.size() * 4, hipMemcpyDeviceToHost, st));
     R3DM_HIP(c, hipStreamSynchronize(st));
+    for (size_t k = 0; k < hs.size(); ++k) c->ac_components[k % 32] += hs[k];
     for (uint32_t b = 0; b < B; ++b) {
         std::vector<AcOut> all(ns[b]);
         if (ns[b]) R3DM_HIP(c, hipMemcpyAsync(all.data(), outs.as<AcOut>() + (size_t)b * stride, (size_t)ns[b] * sizeof(AcOut), hipMemcpyDeviceToHost, st));
@@ -238,8 +285,13 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_
     c->stats.n_detect_images = B;
     c->stats.ms_detect_kernels = ms;
     c->stats.ms_detect = now_ms() - t_call;
+    r3dm_features_totals& T = c->feat_totals;
+    T.n_images += B; T.n_passes += 1; T.ms_detect_kernels += ms; T.ms_wall += c->stats.ms_detect;
+    for (uint32_t b = 0; b < B; ++b) T.n_keypoints += out[b].size();
     return R3DM_OK;
 }
+
+namespace {
 
 void ac_write(const std::vector<AcOut>& kp, float* keypoints_out, float* responses_out, uint32_t cap)
 {
@@ -259,7 +311,7 @@ extern "C" int r3dm_detect_akaze_classic(r3dm_ctx* c, const float* image, uint32
         if (!c || !image || !n_out || (cap && !keypoints_out)) return R3DM_ERR_INVALID;
         *n_out = 0;
         std::vector<std::vector<AcOut>> kp;
-        const int rc = ac_detect_batch(c, 1, &image, width, height, threshold, kp);
+        const int rc = ac_detect_batch(c, 1, &image, nullptr, width, height, threshold, kp);
         if (rc != R3DM_OK) return rc;
         ac_write(kp[0], keypoints_out, responses_out, cap);
         *n_out = (uint32_t)kp[0].size();
@@ -274,7 +326,7 @@ extern "C" int r3dm_detect_akaze_classic_batch(r3dm_ctx* c, uint32_t n_images, c
     return r3dm_guarded(c, [&]() -> int {
         if (!c || !images || !n_out || (cap && !keypoints_out)) return R3DM_ERR_INVALID;
         std::vector<std::vector<AcOut>> kp;
-        const int rc = ac_detect_batch(c, n_images, images, width, height, threshold, kp);
+        const int rc = ac_detect_batch(c, n_images, images, nullptr, width, height, threshold, kp);
         if (rc != R3DM_OK) return rc;
         for (uint32_t b = 0; b < n_images; ++b) {
             ac_write(kp[b], cap ? keypoints_out[b] : nullptr, responses_out ? responses_out[b] : nullptr, cap);
@@ -282,4 +334,11 @@ extern "C" int r3dm_detect_akaze_classic_batch(r3dm_ctx* c, uint32_t n_images, c
         }
         return R3DM_OK;
     });
+}
+
+extern "C" int r3dm_akaze_classic_components(const r3dm_ctx* c, uint64_t* hist)
+{
+    if (!c || !hist) return R3DM_ERR_INVALID;
+    for (int k = 0; k < 32; ++k) hist[k] = c->ac_components[k];
+    return R3DM_OK;
 }

@@ -845,7 +845,8 @@ static bool both_files_exist(const char* feat_path, const char* desc_path, uint3
     return true;
 }
 
-// detectAndExtract (src/Regard3DFeatures.cpp:206-222) for keypointDetectorList_ = {"Fast-AKAZE"} over a batch of B same-size
+// detectAndExtract (src/Regard3DFeatures.cpp:206-222) for keypointDetectorList_ = {"Fast-AKAZE"} or {"AKAZE"} (the context's
+// r3dm_set_keypoint_detector) over a batch of B same-size
 // images + KeypointSet::saveToBinFile of each: detector batch -> (host: angle and patch map of every keypoint, 24 bytes each back
 // to the device) -> one LIOP patch-extraction launch and one LIOP launch over the keypoints of ALL images -> descriptors to page-locked
 // host memory -> files.  Every image of the batch is computed (the skip rule is the caller's: it only batches images it wants).
@@ -857,13 +858,16 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
                                        std::vector<std::vector<float>>* kps_out = nullptr, std::vector<std::vector<float>>* desc_out = nullptr)
 {
     if (!c || B == 0) return R3DM_ERR_INVALID;
+    const bool classic = c->detector_arm == R3DM_DETECTOR_AKAZE;
     AkBatchOut bo;
-    int rc = ak_detect_batch(c, B, grays, bgrs, width, height, threshold, bo);
+    std::vector<std::vector<AcOut>> ao;
+    int rc = classic ? ac_detect_batch(c, B, grays, bgrs, width, height, threshold, ao) : ak_detect_batch(c, B, grays, bgrs, width, height, threshold, bo);
     if (rc != R3DM_OK) return rc;
+    auto n_of = [&](uint32_t b) -> size_t { return classic ? ao[b].size() : bo.recs[b].size(); };
     const double t_liop = now_ms();
     size_t n_total = 0;
     std::vector<size_t> first(B + 1, 0);
-    for (uint32_t b = 0; b < B; ++b) { first[b] = n_total; n_total += bo.recs[b].size(); }
+    for (uint32_t b = 0; b < B; ++b) { first[b] = n_total; n_total += n_of(b); }
     first[B] = n_total;
     std::vector<float> kps(4 * n_total), M6(6 * n_total);
     std::vector<uint32_t> img_of(n_total);
@@ -877,19 +881,23 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
         struct Chunk { uint32_t b; long k0, k1; };
         std::vector<Chunk> chunks;
         for (uint32_t b = 0; b < B; ++b) {
-            const long nk = (long)bo.recs[b].size();
+            const long nk = (long)n_of(b);
             for (long k0 = 0; k0 < nk; k0 += 4096) chunks.push_back({b, k0, std::min(nk, k0 + 4096)});
         }
         r3dm_parallel_for((long)chunks.size(), host_team, [&](long ci) {
             const Chunk& ch = chunks[(size_t)ci];
-            const AkKpRec* recs = bo.recs[ch.b].data();
             const size_t f0 = first[ch.b];
             for (long k = ch.k0; k < ch.k1; ++k) {
-                const AkKpRec& r = recs[k];
                 const size_t g = f0 + (size_t)k;
                 float* o = &kps[4 * g];
-                o[0] = r.x; o[1] = r.y; o[2] = r.size; o[3] = ak_angle_deg(ak_theta(r));
-                liop_patch_map(o[0], o[1], o[2], o[3], 8.0f /* getKpSizeFactor("Fast-AKAZE"), :703-704 */, &M6[6 * g]);
+                if (classic) {                                   // (the classic arm's angle is already in degrees: no + 90)
+                    const AcOut& a = ao[ch.b][(size_t)k];
+                    o[0] = a.x; o[1] = a.y; o[2] = a.size; o[3] = a.angle;
+                } else {
+                    const AkKpRec& r = bo.recs[ch.b][(size_t)k];
+                    o[0] = r.x; o[1] = r.y; o[2] = r.size; o[3] = ak_angle_deg(ak_theta(r));
+                }
+                liop_patch_map(o[0], o[1], o[2], o[3], 8.0f /* getKpSizeFactor("AKAZE" / "Fast-AKAZE"), :703-704 */, &M6[6 * g]);
                 img_of[g] = ch.b;
             }
         });
@@ -914,15 +922,16 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
         R3DM_HIP(c, hipMemcpyAsync(c->liop_kern.p, kern, sizeof(kern), hipMemcpyHostToDevice, c->stream));
         R3DM_HIP(c, hipMemsetAsync(c->liop_cnt.p, 0, 64, c->stream));
         R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
-        // the detector has left the B gray images in its image buffer (ak_bufs[0], B planes, read-only for it)
+        // the detector has left the B gray images in its image buffer (ak_bufs[0] / ac_bufs[0], B planes, read-only for it)
+        const float* grays_dev = classic ? c->ac_bufs[0].as<float>() : c->ak_bufs[0].as<float>();
         static const int fused_knob = r3dm_dev_knob("R3DM_LIOP_FUSED", 1);     // developer build: 0 = patches through HBM (two kernels)
         if (!fused_knob) {
             R3DM_HIP(c, c->liop_in.ensure(patch_bytes));
-            R3DM_HIP(c, launch_liop_extract(c->stream, c->ak_bufs[0].as<float>(), (int)width, (int)height, c->liop_M.as<float>(),
+            R3DM_HIP(c, launch_liop_extract(c->stream, grays_dev, (int)width, (int)height, c->liop_M.as<float>(),
                                             c->liop_kern.as<float>(), (uint32_t)n_total, c->liop_in.as<float>(), d_img_of));
             R3DM_HIP(c, launch_liop(c->stream, liop_tables(c), c->liop_in.as<float>(), (uint32_t)n_total, c->liop_out.as<float>(), c->liop_cnt.as<uint32_t>(), c->liop_cnt.as<uint32_t>() + 16));
         } else {
-            R3DM_HIP(c, launch_liop_fused(c->stream, liop_tables(c), c->ak_bufs[0].as<float>(), (int)width, (int)height, c->liop_M.as<float>(), c->liop_kern.as<float>(),
+            R3DM_HIP(c, launch_liop_fused(c->stream, liop_tables(c), grays_dev, (int)width, (int)height, c->liop_M.as<float>(), c->liop_kern.as<float>(),
                                           d_img_of, (uint32_t)n_total, c->liop_out.as<float>(), c->liop_cnt.as<uint32_t>(), c->liop_cnt.as<uint32_t>() + 16));
         }
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
@@ -955,7 +964,7 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
         auto jobs = std::make_shared<std::vector<Job>>(B);
         r3dm_parallel_for((long)B, host_team, [&](long b) {
             if (!feat_paths[b] || !desc_paths[b]) return;
-            const uint32_t n = (uint32_t)bo.recs[b].size();
+            const uint32_t n = (uint32_t)n_of((uint32_t)b);
             try {
                 Job& j = (*jobs)[(size_t)b];
                 if (c->feat_sink) j.xy.resize((size_t)n * 2 + 2);
@@ -973,7 +982,7 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
         if (c->feat_sink) {
             r3dm_parallel_for((long)B, host_team, [&](long b) {
                 if (!feat_paths[b] || !desc_paths[b] || wrc[b] != R3DM_OK) return;
-                const uint32_t n = (uint32_t)bo.recs[b].size();
+                const uint32_t n = (uint32_t)n_of((uint32_t)b);
                 const uint32_t id = c->feat_sink_ids ? c->feat_sink_ids[b] : (uint32_t)b;
                 int src = 1;
                 try { src = c->feat_sink(c->feat_sink_user, id, n, n ? c->liop_out.as<float>() + 144 * first[b] : nullptr, (*jobs)[(size_t)b].xy.data()); } catch (...) {}
@@ -1019,7 +1028,7 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
         // The descriptors of the batch are still in liop_out (this context's stream is idle: the copy above was waited for).
         r3dm_parallel_for((long)B, host_team, [&](long b) {
             if (!feat_paths[b] || !desc_paths[b]) return;
-            const uint32_t n = (uint32_t)bo.recs[b].size();
+            const uint32_t n = (uint32_t)n_of((uint32_t)b);
             try {                                                   // nothing may leave an OpenMP region by exception
                 std::vector<float> xy_written;
                 if (c->feat_sink) xy_written.resize((size_t)n * 2 + 2);
@@ -1038,7 +1047,7 @@ static int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* con
     }
     if (deferred && desc_out && n_total) R3DM_HIP(c, hipEventSynchronize(c->ev_desc));
     for (uint32_t b = 0; b < B; ++b) {
-        const uint32_t n = (uint32_t)bo.recs[b].size();
+        const uint32_t n = (uint32_t)n_of((uint32_t)b);
         if (to_files && feat_paths[b] && desc_paths[b] && wrc[b] != R3DM_OK) { c->err = werr[b].empty() ? "out of host memory" : werr[b]; return wrc[b]; }
         if (n_features) n_features[b] = n;
         if (kps_out) (*kps_out)[b].assign(kps.begin() + 4 * first[b], kps.begin() + 4 * first[b + 1]);
@@ -1105,13 +1114,24 @@ r3dm_ctx* r3dm_multi_ctx(r3dm_multi* m, int k);
 
 namespace {
 
-// batch size for images of w x h on context c: 8 when HBM allows (the work buffers take ~125 bytes per pixel and image),
-// fewer for very large images or a nearly full device
+// batch size for images of w x h on context c: 8 when HBM allows (the Fast arm's work buffers take ~125 bytes per pixel and image,
+// the classic arm's ~64: six level-0 planes, three per level over four octaves, the walk's arrays), fewer for very large images or a
+// nearly full device
 uint32_t ak_batch_for(r3dm_ctx* c, uint32_t w, uint32_t h, uint32_t want)
 {
     size_t free_b = 0, total_b = 0;
     (void)hipSetDevice(c->device);
     if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return 1;
+    if (c->detector_arm == R3DM_DETECTOR_AKAZE) {
+        // (the classic arm's buffers grow and are kept: what it already holds counts as free)
+        const double per_image = (double)w * h * 4.0 * 16.0 + 64e6;
+        size_t held = 0;
+        for (const DevBuf& d : c->ac_bufs) held += d.cap;
+        const double budget = (double)free_b * 0.5 + (double)held;
+        uint32_t b = want;
+        while (b > 1 && b * per_image > budget) --b;
+        return b;
+    }
     const double per_image = (double)w * h * 4.0 * 32.0 + 64e6;
     const double budget = (double)free_b * 0.5 + (c->ak_w == (int)w && c->ak_h == (int)h ? (double)c->ak_B * per_image : 0.0);
     uint32_t b = want;
@@ -1275,4 +1295,20 @@ extern "C" int r3dm_multi_extract_features_ex(r3dm_multi* m, uint32_t n_images, 
                                               char* err, size_t err_cap)
 {
     return multi_extract_impl(m, n_images, grays, bgrs, widths, heights, threshold, feat_paths, desc_paths, n_features, skipped, batch, err, err_cap);
+}
+
+extern "C" int r3dm_set_keypoint_detector(r3dm_ctx* c, int arm)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    if (arm != R3DM_DETECTOR_FAST_AKAZE && arm != R3DM_DETECTOR_AKAZE) { c->err = "r3dm_set_keypoint_detector: unknown arm " + std::to_string(arm); return R3DM_ERR_INVALID; }
+    c->detector_arm = arm;
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_multi_set_keypoint_detector(r3dm_multi* m, int arm)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    if (arm != R3DM_DETECTOR_FAST_AKAZE && arm != R3DM_DETECTOR_AKAZE) return R3DM_ERR_INVALID;
+    for (int k = 0; k < r3dm_multi_num_devices(m); ++k) (void)r3dm_set_keypoint_detector(r3dm_multi_ctx(m, k), arm);
+    return R3DM_OK;
 }

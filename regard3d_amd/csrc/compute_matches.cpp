@@ -227,9 +227,17 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     for (size_t vi = 0; vi < views_.size(); ++vi)
         if (!(file_exists(dir + "/" + views_[vi].basename + ".feat") && file_exists(dir + "/" + views_[vi].basename + ".desc"))) need.push_back(vi);
     if (need.empty()) return true;
-    // the detector list of the GUI: only the default arm runs on the GPU (include/regard3d_features.hpp says so too)
-    for (const std::string& d : params.keypointDetectorList_)
-        if (d != "Fast-AKAZE") { errorMessage_ = "keypoint detector \"" + d + "\" is not served by the GPU path (Fast-AKAZE is)"; return false; }
+    // the detector list of the GUI: one served arm, "Fast-AKAZE" or "AKAZE" (include/regard3d_features.hpp says so too); a list of
+    // more than one entry is refused by name
+    const std::vector<std::string>& dl = params.keypointDetectorList_;
+    for (const std::string& d : dl)
+        if (d != "Fast-AKAZE" && d != "AKAZE") { errorMessage_ = "keypoint detector \"" + d + "\" is not served by the GPU path (Fast-AKAZE and AKAZE are)"; return false; }
+    if (dl.size() != 1) {
+        std::string names;
+        for (const std::string& d : dl) names += (names.empty() ? "\"" : ", \"") + d + "\"";
+        errorMessage_ = "keypoint detector list {" + names + "} is not served by the GPU path (one entry, Fast-AKAZE or AKAZE, is)";
+        return false;
+    }
     if (dtype_ != R3DM_F32 || dim_ != 144) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
     if (!feat_multi_) {
         std::vector<int> ids;
@@ -238,6 +246,7 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
         if (rc != R3DM_OK) { feat_multi_ = nullptr; errorMessage_ = "r3dm_multi_create (features stage) failed (" + std::to_string(rc) + ")"; return false; }
     }
     const int n_ctx = r3dm_multi_num_devices(feat_multi_);
+    (void)r3dm_multi_set_keypoint_detector(feat_multi_, dl[0] == "AKAZE" ? R3DM_DETECTOR_AKAZE : R3DM_DETECTOR_FAST_AKAZE);
     (void)r3dm_multi_set_features_sink(feat_multi_, direct_registration_ ? &R3DComputeMatches::features_sink : nullptr, this);
     // the .feat / .desc of a batch are written behind the sink calls, beside the match phase (computeMatches waits for them before it
     // returns): only when the views are registered straight from the device, else Regions_Provider::load reads those files next
@@ -687,7 +696,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setExactFastPaths((flags & R3DM_STAGE_F32_TILES) == 0);      // (R3DM_STAGE_SPLIT_MFMA / _INTEGER_MFMA: implied since round 3)
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         r3d_amd::R3DFParams params;
-        params.keypointDetectorList_ = {"Fast-AKAZE"};
+        params.keypointDetectorList_ = {(flags & R3DM_STAGE_DETECTOR_AKAZE) ? "AKAZE" : "Fast-AKAZE"};
         params.threshold_ = threshold;
         params.distRatio_ = dist_ratio;
         params.computeFundalmentalMatrix_ = compute_F != 0;

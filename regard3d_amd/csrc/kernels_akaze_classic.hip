@@ -217,17 +217,27 @@ void ac_scan_rows_kernel(uint32_t* __restrict__ row_counts, uint32_t rows_stride
 // stays (an entry is only a pointer; every test reads the slot's current class and position).  At the start of level l the cells of the
 // previous level are cleared through their entries and the slots of class l - 1 are entered.
 __device__ __forceinline__ int ac_cell_of(float v, int G) { return (int)v / G; }
+// kMembers = false: every candidate of the image, straight into the slots (the developer build's R3DM_AC_AUX=0 form).
+// kMembers = true: the hand-back of the parallel walk below -- only the candidates flagged in cc.big (the members of the components
+// larger than the wavefront bound), in scan order.  Components do not interact, so walking their union is walking each of them; the
+// slots are scratch (slots[q].pad = the candidate last written into slot q, cc.bopen[q] = the one that opened it) and the walk leaves
+// cc.fin[opener] = last writer, cc.opn[opener] = 1 for ac_cc_emit_kernel.
+template <bool kMembers>
 __global__ __launch_bounds__(64)
 void ac_aux_kernel(const AcCand* __restrict__ cand, uint32_t cand_stride, const uint32_t* __restrict__ totals, AcLevelTab tab,
-                   AcSlot* __restrict__ slots, AcGrid grid, uint32_t* __restrict__ n_slots)
+                   AcSlot* __restrict__ slots, AcGrid grid, uint32_t* __restrict__ n_slots, AcCc cc)
 {
     const uint32_t b = blockIdx.x, lane = threadIdx.x;
+    if (kMembers && cc.n_big[b] == 0) return;
     const AcCand* cb = cand + (size_t)b * cand_stride;
     AcSlot* sl = slots + (size_t)b * cand_stride;
     int* heads = grid.heads + (size_t)b * grid.cells_stride;
     uint32_t* ent_slot = grid.ent_slot + (size_t)b * grid.ent_stride;
     uint32_t* ent_cell = grid.ent_cell + (size_t)b * grid.ent_stride;
     int* ent_next = grid.ent_next + (size_t)b * grid.ent_stride;
+    const uint32_t* big = kMembers ? cc.big + (size_t)b * cand_stride : nullptr;
+    uint32_t* bopen = kMembers ? cc.bopen + (size_t)b * cand_stride : nullptr;
+    const uint32_t* rows = kMembers ? cc.rows + (size_t)b * cc.rows_stride : nullptr;
     const uint32_t nc = totals[b];
     uint32_t n = 0, ne = 0, c = 0;
     for (int l = 0; l < tab.n_levels; ++l) {
@@ -257,8 +267,9 @@ void ac_aux_kernel(const AcCand* __restrict__ cand, uint32_t cand_stride, const 
         const float s2 = size * size;
         const float r = tab.smax * (float)ss;
         const float off = tab.off[l];
-        for (; c < nc && cb[c].level == (uint32_t)l; ++c) {
-            const AcCand k = cb[c];
+        // one candidate through the rule
+        auto step = [&](uint32_t ci) {
+            const AcCand k = cb[ci];
             const float px = (float)k.x, py = (float)k.y;
             const float sx = px * ratio, sy = py * ratio;
             uint32_t best = 0xFFFFFFFFu;
@@ -280,16 +291,17 @@ void ac_aux_kernel(const AcCand* __restrict__ cand, uint32_t cand_stride, const 
             bool rep = false;
             if (hit >= 0) {
                 if (k.value > sl[hit].resp) rep = true;
-                else continue;                                    // the first hit decides: rejected
+                else return;                                      // the first hit decides: rejected
             }
             const int left = ac_fround(px - r) - 1, right = ac_fround(px + r) + 1;
             const int up = ac_fround(py - r) - 1, down = ac_fround(py + r) + 1;
-            if (left < 0 || right >= tab.w[l] || up < 0 || down >= tab.h[l]) continue;   // descriptor border: out
+            if (left < 0 || right >= tab.w[l] || up < 0 || down >= tab.h[l]) return;   // descriptor border: out
             const uint32_t q = rep ? (uint32_t)hit : n;
             if (lane == 0) {
                 // pt * ratio + .5 * (ratio - 1.0): the double sum of exact values, stored as float
                 const float nx = (float)((double)sx + (double)off), ny = (float)((double)sy + (double)off);
-                sl[q] = AcSlot{nx, ny, size, k.value, (uint32_t)l, 0u};
+                sl[q] = AcSlot{nx, ny, size, k.value, (uint32_t)l, kMembers ? ci : 0u};
+                if (kMembers && !rep) bopen[q] = ci;
                 const uint32_t cell = (uint32_t)(ac_cell_of(ny, G) * gw + ac_cell_of(nx, G));
                 ent_slot[ne] = q; ent_cell[ne] = cell;
                 ent_next[ne] = atomicExch(&heads[cell], (int)ne);
@@ -297,9 +309,241 @@ void ac_aux_kernel(const AcCand* __restrict__ cand, uint32_t cand_stride, const 
             ++ne;
             if (!rep) ++n;
             __syncthreads();                                      // workgroup-scope fence: the slot and its entry are seen by every lane
+        };
+        if (!kMembers) {
+            for (; c < nc && cb[c].level == (uint32_t)l; ++c) step(c);
+        } else {
+            // the level's candidates are [rows[row0[l]], rows[row0[l + 1]]): 64 flags at a time, the flagged ones in order
+            const uint32_t lo = rows[tab.row0[l]], hi = l + 1 < tab.n_levels ? rows[tab.row0[l + 1]] : nc;
+            for (uint32_t c0 = lo; c0 < hi; c0 += 64) {
+                uint64_t bal = __ballot(c0 + lane < hi && big[c0 + lane] != 0u);
+                while (bal) {
+                    const uint32_t k = (uint32_t)__builtin_ctzll(bal);
+                    bal &= bal - 1ull;
+                    step(c0 + k);
+                }
+            }
         }
     }
-    if (lane == 0) n_slots[b] = n;
+    if (!kMembers) {
+        if (lane == 0) n_slots[b] = n;
+    } else {
+        uint32_t* fin = cc.fin + (size_t)b * cand_stride;
+        uint32_t* opn = cc.opn + (size_t)b * cand_stride;
+        for (uint32_t q = lane; q < n; q += 64) { fin[bopen[q]] = sl[q].pad; opn[bopen[q]] = 1u; }
+    }
+}
+
+// ---- The same rule, in parallel: connected components (the argument of the Fast arm's in-level pruning,
+// section 4.8, over two levels).  A level-l candidate p reads only slots of class l - 1 or l whose position lies within size_l of p's
+// scaled position, and a slot always holds the position and class of the last candidate written into it.  So link p to every EARLIER
+// candidate q of level l - 1 or l that passes the rule's own float predicate against q's converted position: every interaction of the
+// serial rule is then an edge (extra edges do no harm).  A candidate that fails the descriptor-border test never changes kpts_aux and
+// is dropped before linking.  A slot never leaves its component and no component reads another's slots, so "first slot in list order"
+// is the first slot of the component in the order its candidates opened them, and a slot's global index is the running count of the
+// openers in scan order -- the order the serial rule appends in.
+//   init      per candidate: parent = itself, or none when the border test fails
+//   link      union-find over the earlier candidates of the rows within reach (the row offsets of ac_scan_rows, both levels)
+//   flatten   root (the component's smallest index) and member count (no path halving here: see the kernel)
+//   classify  a lone candidate opens its slot on the spot; a component of <= bound members gets a bucket (bucket sizes, scanned);
+//             the members of a larger one are flagged for the hand-back (ac_aux_kernel<true>)
+//   gather    members into their buckets (any order; the wavefront sorts them)
+//   small     one wavefront per bucketed component: members sorted into scan order, slots in registers (lane = slot, in opening order)
+//   emit      opener flags scanned (ac_scan_rows) = slot indices; every slot written from its last writer
+// All hand-overs between kernels go through the stream order; inside the small kernel they are cross-lane shuffles.
+__device__ __forceinline__ uint32_t ac_ld(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ uint32_t ac_uf_find(uint32_t* par, uint32_t x)
+{
+    for (;;) {
+        const uint32_t p = ac_ld(par + x);
+        if (p == x) return x;
+        const uint32_t g = ac_ld(par + p);
+        if (g == p) return p;
+        __hip_atomic_store(par + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // path halving: g is an ancestor of x whatever else happens
+        x = g;
+    }
+}
+__device__ __forceinline__ void ac_uf_union(uint32_t* par, uint32_t a, uint32_t b)
+{
+    for (;;) {
+        a = ac_uf_find(par, a); b = ac_uf_find(par, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }                                // the later root goes under the earlier one: no cycle
+        if (atomicCAS(par + a, a, b) == a) return;
+    }
+}
+__device__ __forceinline__ bool ac_is_out(const AcLevelTab& tab, const AcCand& k)
+{
+    const int l = (int)k.level;
+    const float size = tab.esigma[l] * 1.5f, ratio = tab.ratio[l];
+    const float r = tab.smax * (float)ac_fround(size / ratio);
+    const float px = (float)k.x, py = (float)k.y;
+    return ac_fround(px - r) - 1 < 0 || ac_fround(px + r) + 1 >= tab.w[l] || ac_fround(py - r) - 1 < 0 || ac_fround(py + r) + 1 >= tab.h[l];
+}
+__device__ __forceinline__ float ac_conv(float v, float ratio, float off) { return (float)((double)(v * ratio) + (double)off); }
+
+__global__ __launch_bounds__(256)
+void ac_cc_init_kernel(const AcCand* __restrict__ cand, uint32_t stride, const uint32_t* __restrict__ totals, AcLevelTab tab, AcCc cc)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= stride) return;
+    const size_t at = (size_t)b * stride + i;
+    const bool in = i < totals[b] && !ac_is_out(tab, cand[at]);
+    cc.par[at] = in ? i : kNone;
+    cc.csz[at] = 0u; cc.boff[at] = 0u; cc.cur[at] = 0u; cc.opn[at] = 0u; cc.big[at] = 0u; cc.fin[at] = kNone;
+    if (i == 0) cc.n_big[b] = 0u;
+}
+__global__ __launch_bounds__(256)
+void ac_cc_link_kernel(const AcCand* __restrict__ cand, uint32_t stride, const uint32_t* __restrict__ totals, AcLevelTab tab, AcCc cc)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= totals[b]) return;
+    const AcCand* cb = cand + (size_t)b * stride;
+    uint32_t* par = cc.par + (size_t)b * stride;
+    if (par[i] == kNone) return;                              // (fixed since init: unions only move roots)
+    const uint32_t* rows = cc.rows + (size_t)b * cc.rows_stride;
+    const AcCand k = cb[i];
+    const int l = (int)k.level;
+    const float size = tab.esigma[l] * 1.5f, s2 = size * size, ratio = tab.ratio[l];
+    const float sx = (float)k.x * ratio, sy = (float)k.y * ratio;
+    for (int m = l > 0 ? l - 1 : l; m <= l; ++m) {
+        const float rm = tab.ratio[m], om = tab.off[m];
+        // level-m rows and columns whose converted position can lie within size (one spare row / column on each side)
+        const int ylo = max(1, (int)floorf((sy - size - om) / rm) - 1), yhi = min(tab.h[m] - 2, (int)ceilf((sy + size - om) / rm) + 1);
+        const uint32_t xlo = (uint32_t)max(1, (int)floorf((sx - size - om) / rm) - 1);
+        const int xhi = (int)ceilf((sx + size - om) / rm) + 1;
+        for (int y = ylo; y <= yhi; ++y) {
+            uint32_t j = rows[tab.row0[m] + y], je = rows[tab.row0[m] + y + 1];
+            if (m == l && je > i) je = i;                         // only earlier candidates
+            uint32_t a = j, z = je;                               // first column >= xlo
+            while (a < z) { const uint32_t h = (a + z) >> 1; if (cb[h].x < xlo) a = h + 1; else z = h; }
+            for (j = a; j < je && (int)cb[j].x <= xhi; ++j) {
+                if (par[j] == kNone) continue;
+                const float tx = sx - ac_conv((float)cb[j].x, rm, om), ty = sy - ac_conv((float)cb[j].y, rm, om);
+                if (tx * tx + ty * ty <= s2) ac_uf_union(par, i, j);
+            }
+        }
+    }
+}
+__global__ __launch_bounds__(256)
+void ac_cc_flatten_kernel(uint32_t stride, const uint32_t* __restrict__ totals, AcCc cc)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= totals[b]) return;
+    uint32_t* par = cc.par + (size_t)b * stride;
+    if (ac_ld(par + i) == kNone) return;
+    // a walk WITHOUT path halving: a halving find of another lane could otherwise put a mere ancestor back over a root stored here,
+    // and that member would miss its component's bucket.  The only stores now are par[i] = root, so every chain a lane follows stays
+    // one of ancestors.
+    uint32_t r = i;
+    for (uint32_t p = ac_ld(par + r); p != r; p = ac_ld(par + r)) r = p;
+    if (r != i) __hip_atomic_store(par + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    atomicAdd(cc.csz + (size_t)b * stride + r, 1u);
+}
+__global__ __launch_bounds__(256)
+void ac_cc_classify_kernel(uint32_t stride, const uint32_t* __restrict__ totals, AcCc cc, uint32_t bound)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= totals[b]) return;
+    const size_t o = (size_t)b * stride;
+    const uint32_t r = cc.par[o + i];
+    if (r == kNone) return;
+    const uint32_t s = cc.csz[o + r];
+    if (s == 1u) { cc.fin[o + i] = i; cc.opn[o + i] = 1u; }           // a lone candidate opens its slot on the spot
+    else if (s <= bound) { if (r == i) cc.boff[o + i] = s; }
+    else { cc.big[o + i] = 1u; if (r == i) atomicAdd(cc.n_big + b, s); }
+    if (r == i && cc.hist) atomicAdd(cc.hist + 32u * b + (31u - (uint32_t)__builtin_clz(s)), 1u);   // bin k: sizes in [2^k, 2^(k+1))
+}
+__global__ __launch_bounds__(256)
+void ac_cc_gather_kernel(uint32_t stride, const uint32_t* __restrict__ totals, AcCc cc, uint32_t bound)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= totals[b]) return;
+    const size_t o = (size_t)b * stride;
+    const uint32_t r = cc.par[o + i];
+    if (r == kNone) return;
+    const uint32_t s = cc.csz[o + r];
+    if (s < 2u || s > bound) return;
+    cc.memb[o + cc.boff[o + r] + atomicAdd(cc.cur + o + r, 1u)] = i;
+}
+__global__ __launch_bounds__(256)
+void ac_cc_small_kernel(const AcCand* __restrict__ cand, uint32_t stride, const uint32_t* __restrict__ totals, AcLevelTab tab, AcCc cc,
+                        uint32_t bound)
+{
+    const uint32_t b = blockIdx.y, lane = threadIdx.x & 63u, wave = (blockIdx.x * 256u + threadIdx.x) >> 6, n_waves = gridDim.x * 4u;
+    const uint32_t nc = totals[b];
+    const size_t o = (size_t)b * stride;
+    const AcCand* cb = cand + o;
+    for (uint32_t c0 = wave * 64u; c0 < nc; c0 += n_waves * 64u) {
+        const uint32_t i = c0 + lane;
+        const bool root = i < nc && cc.par[o + i] == i;
+        const uint32_t sz = root ? cc.csz[o + i] : 0u;
+        uint64_t todo = __ballot(sz >= 2u && sz <= bound);
+        while (todo) {
+            const int bit = __builtin_ctzll(todo);
+            todo &= todo - 1ull;
+            const uint32_t r = c0 + (uint32_t)bit, n = (uint32_t)__shfl((int)sz, bit);
+            // the members, sorted into scan order (bitonic over the wavefront; the empty lanes sort last)
+            uint32_t mem = lane < n ? cc.memb[o + cc.boff[o + r] + lane] : kNone;
+#pragma unroll
+            for (uint32_t k = 2; k <= 64; k <<= 1)
+#pragma unroll
+                for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+                    const uint32_t other = (uint32_t)__shfl_xor((int)mem, (int)j);
+                    const bool up = (lane & k) == 0, low = (lane & j) == 0;
+                    mem = (low == up) ? (mem < other ? mem : other) : (mem > other ? mem : other);
+                }
+            // lane q = slot q of the component, in opening order
+            float qx = 0.f, qy = 0.f, qr = 0.f; uint32_t qcls = 0u, qwr = 0u, qop = 0u, n_open = 0u;
+            for (uint32_t t = 0; t < n; ++t) {
+                const uint32_t ci = (uint32_t)__shfl((int)mem, (int)t);
+                const AcCand k = cb[ci];
+                const uint32_t l = k.level;
+                const float size = tab.esigma[l] * 1.5f, s2 = size * size, ratio = tab.ratio[l];
+                const float sx = (float)k.x * ratio, sy = (float)k.y * ratio;
+                const float tx = sx - qx, ty = sy - qy;
+                const uint64_t bal = __ballot(lane < n_open && (qcls == l || qcls + 1u == l) && tx * tx + ty * ty <= s2);
+                const float nx = (float)((double)sx + (double)tab.off[l]), ny = (float)((double)sy + (double)tab.off[l]);
+                if (bal) {
+                    const int f = __builtin_ctzll(bal);
+                    if (k.value > __shfl(qr, f) && (int)lane == f) { qx = nx; qy = ny; qr = k.value; qcls = l; qwr = ci; }
+                } else {
+                    if (lane == n_open) { qx = nx; qy = ny; qr = k.value; qcls = l; qwr = ci; qop = ci; }
+                    ++n_open;
+                }
+            }
+            if (lane < n_open) { cc.fin[o + qop] = qwr; cc.opn[o + qop] = 1u; }
+        }
+    }
+}
+// opn holds the slot index of every opener now (exclusive scan); its slot takes the last candidate written into it
+__global__ __launch_bounds__(256)
+void ac_cc_emit_kernel(const AcCand* __restrict__ cand, uint32_t stride, const uint32_t* __restrict__ totals, AcLevelTab tab, AcCc cc,
+                       AcSlot* __restrict__ slots)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= totals[b]) return;
+    const size_t o = (size_t)b * stride;
+    const uint32_t w = cc.fin[o + i];
+    if (w == kNone) return;
+    const AcCand k = cand[o + w];
+    const uint32_t l = k.level;
+    const float ratio = tab.ratio[l];
+    slots[o + cc.opn[o + i]] = AcSlot{ac_conv((float)k.x, ratio, tab.off[l]), ac_conv((float)k.y, ratio, tab.off[l]), tab.esigma[l] * 1.5f, k.value, l, 0u};
+}
+
+// ---- the upper-level filter's buckets: the slots of class k >= 1 in linked cell lists of side G_k = floor(size_{k-1}) + 1 > size_{k-1},
+// so a slot of class k - 1 finds every slot of class k within its size in the 3 x 3 cells around it (the walk's own argument)
+__global__ __launch_bounds__(256)
+void ac_up_insert_kernel(const AcSlot* __restrict__ slots, uint32_t stride, const uint32_t* __restrict__ n_slots, AcUpGrid ug)
+{
+    const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_slots[b]) return;
+    const AcSlot s = slots[(size_t)b * stride + i];
+    if (s.cls == 0u) return;
+    const int G = ug.G[s.cls], gw = ug.img_w / G + 2;
+    int* heads = ug.heads + (size_t)b * ug.cells_stride + ug.cell_off[s.cls];
+    ug.next[(size_t)b * stride + i] = atomicExch(&heads[ac_cell_of(s.y, G) * gw + ac_cell_of(s.x, G)], (int)i);
 }
 
 // ---- upper-level filter (AKAZE.cpp:352-381), one lane per slot: slot i goes if a LATER slot of class + 1 lies within slot i's size
@@ -331,7 +575,7 @@ __device__ __forceinline__ float ac_fast_atan2_deg(float y, float x)
 
 __global__ __launch_bounds__(256)
 void ac_finish_kernel(const AcSlot* __restrict__ slots, uint32_t stride, const uint32_t* __restrict__ n_slots, AcLevelTab tab,
-                      AcPlanes pl, AcOut* __restrict__ out)
+                      AcPlanes pl, AcOut* __restrict__ out, AcUpGrid ug)
 {
     const uint32_t b = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     const uint32_t n = n_slots[b];
@@ -341,11 +585,25 @@ void ac_finish_kernel(const AcSlot* __restrict__ slots, uint32_t stride, const u
     o.ok = 0;
     const AcSlot p = sl[i];
     const float p2 = p.size * p.size;
-    for (uint32_t j = i + 1; j < n; ++j) {
+    auto drops = [&](uint32_t j) {
         const AcSlot q = sl[j];
-        if (q.cls != p.cls + 1) continue;
+        if (q.cls != p.cls + 1) return false;
         const float tx = p.x - q.x, ty = p.y - q.y;
-        if (tx * tx + ty * ty <= p2 && p.resp < q.resp) return;
+        return tx * tx + ty * ty <= p2 && p.resp < q.resp;
+    };
+    if (!ug.heads) {                                                  // (the developer build's R3DM_AC_AUX=0: every later slot)
+        for (uint32_t j = i + 1; j < n; ++j) if (drops(j)) return;
+    } else if ((int)p.cls + 1 < tab.n_levels) {
+        // the later slots of class + 1 in the 3 x 3 cells around the slot (ac_up_insert_kernel)
+        const uint32_t k = p.cls + 1;
+        const int G = ug.G[k], gw = ug.img_w / G + 2, gh = ug.img_h / G + 2;
+        const int* heads = ug.heads + (size_t)b * ug.cells_stride + ug.cell_off[k];
+        const int* next = ug.next + (size_t)b * stride;
+        const int cx = ac_cell_of(p.x, G), cy = ac_cell_of(p.y, G);
+        for (int y = max(cy - 1, 0); y <= min(cy + 1, gh - 1); ++y)
+            for (int x = max(cx - 1, 0); x <= min(cx + 1, gw - 1); ++x)
+                for (int j = heads[y * gw + x]; j >= 0; j = next[j])
+                    if ((uint32_t)j > i && drops((uint32_t)j)) return;
     }
     const int l = (int)p.cls, w = tab.w[l];
     const size_t plane = (size_t)tab.w[l] * tab.h[l] * b;
@@ -458,14 +716,32 @@ hipError_t ac_scan_rows(hipStream_t st, uint32_t* row_counts, uint32_t rows_stri
 hipError_t ac_aux(hipStream_t st, const AcCand* cand, uint32_t cand_stride, const uint32_t* totals, const AcLevelTab& tab, AcSlot* slots,
                   const AcGrid& grid, uint32_t* n_slots, int B)
 {
-    hipLaunchKernelGGL(ac_aux_kernel, dim3((unsigned)B), dim3(64), 0, st, cand, cand_stride, totals, tab, slots, grid, n_slots);
+    hipLaunchKernelGGL(ac_aux_kernel<false>, dim3((unsigned)B), dim3(64), 0, st, cand, cand_stride, totals, tab, slots, grid, n_slots, AcCc{});
+    return hipGetLastError();
+}
+hipError_t ac_aux_parallel(hipStream_t st, const AcCand* cand, uint32_t stride, const uint32_t* totals, const AcLevelTab& tab, AcSlot* slots,
+                           const AcGrid& grid, uint32_t* n_slots, const AcCc& cc, uint32_t bound, int B)
+{
+    const dim3 g((stride + 255) / 256, (unsigned)B);
+    const uint32_t small_blocks = std::min<uint32_t>((stride + 255) / 256, 1024u);
+    hipLaunchKernelGGL(ac_cc_init_kernel, g, dim3(256), 0, st, cand, stride, totals, tab, cc);
+    hipLaunchKernelGGL(ac_cc_link_kernel, g, dim3(256), 0, st, cand, stride, totals, tab, cc);
+    hipLaunchKernelGGL(ac_cc_flatten_kernel, g, dim3(256), 0, st, stride, totals, cc);
+    hipLaunchKernelGGL(ac_cc_classify_kernel, g, dim3(256), 0, st, stride, totals, cc, bound);
+    hipLaunchKernelGGL(ac_scan_rows_kernel, dim3((unsigned)B), dim3(1024), 0, st, cc.boff, stride, stride, cc.scratch);
+    hipLaunchKernelGGL(ac_cc_gather_kernel, g, dim3(256), 0, st, stride, totals, cc, bound);
+    hipLaunchKernelGGL(ac_cc_small_kernel, dim3(small_blocks, (unsigned)B), dim3(256), 0, st, cand, stride, totals, tab, cc, bound);
+    hipLaunchKernelGGL(ac_aux_kernel<true>, dim3((unsigned)B), dim3(64), 0, st, cand, stride, totals, tab, slots, grid, n_slots, cc);
+    hipLaunchKernelGGL(ac_scan_rows_kernel, dim3((unsigned)B), dim3(1024), 0, st, cc.opn, stride, stride, n_slots);
+    hipLaunchKernelGGL(ac_cc_emit_kernel, g, dim3(256), 0, st, cand, stride, totals, tab, cc, slots);
     return hipGetLastError();
 }
 hipError_t ac_finish(hipStream_t st, const AcSlot* slots, uint32_t stride, const uint32_t* n_slots, const AcLevelTab& tab, const AcPlanes& pl,
-                     AcOut* out, uint32_t max_slots, int B)
+                     AcOut* out, uint32_t max_slots, int B, const AcUpGrid& ug)
 {
     if (max_slots == 0) return hipSuccess;
-    hipLaunchKernelGGL(ac_finish_kernel, dim3((max_slots + 255) / 256, (unsigned)B), dim3(256), 0, st, slots, stride, n_slots, tab, pl, out);
+    if (ug.heads) hipLaunchKernelGGL(ac_up_insert_kernel, dim3((max_slots + 255) / 256, (unsigned)B), dim3(256), 0, st, slots, stride, n_slots, ug);
+    hipLaunchKernelGGL(ac_finish_kernel, dim3((max_slots + 255) / 256, (unsigned)B), dim3(256), 0, st, slots, stride, n_slots, tab, pl, out, ug);
     return hipGetLastError();
 }
 

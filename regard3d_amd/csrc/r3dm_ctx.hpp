@@ -378,6 +378,9 @@ struct GuidedResult {
 int guided_job_make(r3dm_ctx* c, uint32_t sI, uint32_t sJ, int pub_kind, const double* M, double thr_px, double ratio, GuidedJob& out);
 // runs the jobs (q0 / b0 are assigned here), fills c->guided_stats; jobs may be empty
 int guided_run(r3dm_ctx* c, std::vector<GuidedJob>& jobs, GuidedResult& R);
+// the classic A-KAZE detector over B same-size images (api_akaze_classic.cpp); gray images or 8-bit BGR, left in ac_bufs[0]
+int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                    float threshold, std::vector<std::vector<AcOut>>& out);
 
 // The way of a view from host memory to HBM (r3dm_set_image / r3dm_set_images): a ring of page-locked slots the caller's pageable rows
 // are copied into by the host (several threads for a batch of views), one asynchronous DMA per view from there into the slot's
@@ -443,6 +446,8 @@ struct r3dm_ctx {
     DevBuf m_raw, m_peer;                                   // r3dm_multi_set_image: the one upload of a view / this device's copy of it
     std::vector<DevBuf> ak_bufs;                            // Fast-A-KAZE work buffers of the last image size, ak_B planes each
     std::vector<DevBuf> ac_bufs;                            // classic A-KAZE work buffers (api_akaze_classic.cpp: grow, never shrink)
+    uint64_t ac_components[32] = {};                        // component-size histogram of the classic arm's kpts_aux walk (r3dm_akaze_classic_components)
+    int detector_arm = R3DM_DETECTOR_FAST_AKAZE;            // r3dm_set_keypoint_detector: the arm of the features entries
     int ak_w = 0, ak_h = 0, ak_B = 0;
     uint32_t ak_cap = 0;                                    // candidate slots per image the detector last needed (grows, never shrinks)
     int ak_n_levels = 0;

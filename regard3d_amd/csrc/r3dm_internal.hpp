@@ -379,7 +379,19 @@ struct AcLevelTab {
     int w[kAcMaxLevels], h[kAcMaxLevels], octave[kAcMaxLevels];
     float esigma[kAcMaxLevels], ratio[kAcMaxLevels], off[kAcMaxLevels];   // off = .5 (ratio - 1)
     float smax;                                          // 10 sqrt(2) as the reference forms it
+    uint32_t row0[kAcMaxLevels];                         // first row of each level in the per-image row-offset array of ac_scan_rows
 };
+// the parallel kpts_aux walk (ac_aux_parallel): per-candidate arrays of B x stride words, as kernels_akaze_classic.hip describes them
+struct AcCc {
+    uint32_t *par, *csz, *boff, *cur, *memb, *fin, *opn, *big, *bopen;
+    uint32_t* n_big;                                     // [B] members of the handed-back components
+    uint32_t* scratch;                                   // [B] (scan totals nobody reads)
+    uint32_t* hist;                                      // [B x 32] component-size histogram (bin k: sizes in [2^k, 2^(k+1))), or null
+    const uint32_t* rows;                                // row offsets of ac_scan_rows, rows_stride per image
+    uint32_t rows_stride;
+};
+// the upper-level filter's buckets: per image cells_stride heads (-1 = empty), class k's cells at cell_off[k], side G[k]; next: stride per image
+struct AcUpGrid { int* heads; int* next; size_t cells_stride; int img_w, img_h; uint32_t cell_off[kAcMaxLevels]; int G[kAcMaxLevels]; };
 // the spatial grid of the kpts_aux walk, per image: cells_stride heads (-1 = empty) and ent_stride entries (slot, cell, next)
 struct AcGrid { int* heads; uint32_t* ent_slot; uint32_t* ent_cell; int* ent_next; size_t cells_stride, ent_stride; int img_w, img_h; };
 struct AcPlanes { const float* ldet[kAcMaxLevels]; const float* lx[kAcMaxLevels]; const float* ly[kAcMaxLevels]; };
@@ -391,8 +403,12 @@ hipError_t ac_extrema(hipStream_t st, const float* ldet, int w, int h, int B, fl
 hipError_t ac_scan_rows(hipStream_t st, uint32_t* row_counts, uint32_t rows_stride, uint32_t n_rows, int B, uint32_t* totals);
 hipError_t ac_aux(hipStream_t st, const AcCand* cand, uint32_t cand_stride, const uint32_t* totals, const AcLevelTab& tab, AcSlot* slots,
                   const AcGrid& grid, uint32_t* n_slots, int B);
+// bound: components of at most this many candidates (<= 64) are walked by one wavefront each, larger ones by ac_aux_kernel<true>
+hipError_t ac_aux_parallel(hipStream_t st, const AcCand* cand, uint32_t stride, const uint32_t* totals, const AcLevelTab& tab, AcSlot* slots,
+                           const AcGrid& grid, uint32_t* n_slots, const AcCc& cc, uint32_t bound, int B);
+// ug.heads == null: the upper-level filter compares every later slot (the developer build's R3DM_AC_AUX=0)
 hipError_t ac_finish(hipStream_t st, const AcSlot* slots, uint32_t stride, const uint32_t* n_slots, const AcLevelTab& tab, const AcPlanes& pl,
-                     AcOut* out, uint32_t max_slots, int B);
+                     AcOut* out, uint32_t max_slots, int B, const AcUpGrid& ug);
 constexpr uint32_t kAkSlotBytes = 80;                  // per candidate slot: cand 16 + list 16 + live 16 + out0 16 + out1 8 + valid 4 + dead 2 (+ 2 spare)
 
 // ---- launchers implemented in the .hip files (host side) ----
