@@ -204,8 +204,8 @@ int r3dm_filter_report(const r3dm_ctx* ctx, r3dm_pair_report* out, uint64_t cap)
  * workgroup per pair on a stream per filter; one filter alone is served the same way (r3dm_filter_F / _E / _H).  Results are those of
  * r3dm_filter_F / _E / _H whatever the split (inlier sets, models, iteration counts: tests/test_gpu_filter_coop.py).  ms_kernels3 /
  * ms_wall3 (optional): HIP-event time of the kernels and wall time of each call in the order F, E, H (they overlap; a filter with
- * long pairs ends when the cooperative kernel does).  r3dm_filter_report afterwards: the E call's, else F's.  r3dm_stats:
- * n_filter_workgroups / n_filter_coop_pairs. */
+ * long pairs ends when the cooperative kernel does).  r3dm_filter_report afterwards: the E call's, else the last requested kind's.
+ * r3dm_stats: n_filter_workgroups / n_filter_coop_pairs. */
 int r3dm_filter_FEH(r3dm_ctx* ctx, const r3dm_graph* putative, double max_residual_px, uint32_t max_iter, uint64_t seed, int which,
                     uint32_t e_min_count, float e_min_ratio, r3dm_graph** out_F, r3dm_graph** out_E, r3dm_graph** out_H,
                     double* ms_kernels3, double* ms_wall3);

@@ -173,23 +173,13 @@ static int r3dm_guided_match_impl(r3dm_ctx* c, const r3dm_graph* pairs, int kind
     if (rc != R3DM_OK) return rc;
     auto g = std::unique_ptr<r3dm_graph>(new r3dm_graph());
     g->offsets.push_back(0);
-    const bool mirror = c->device_graphs;
-    if (mirror) { g->dev.valid = true; g->dev.device = c->device; }
-    std::vector<uint32_t> m_ids, m_cnts;
-    std::vector<GraphSeg> m_segs;
+    GraphBuilder b(c, g.get(), c->device_graphs, R.host, nullptr, R.dev, nullptr);
     for (uint64_t p = 0; p < NP; ++p) {
         const uint32_t n = R.cnt[p];
         if (n == 0) continue;                                  // no empty entries ("Guided matching")
-        g->pairs.push_back(pairs->pairs[2 * p]); g->pairs.push_back(pairs->pairs[2 * p + 1]);
-        const uint64_t at = g->matches.size();
-        g->matches.insert(g->matches.end(), R.host + jobs[p].q0, R.host + jobs[p].q0 + n);
-        g->offsets.push_back(g->matches.size());
-        if (mirror) {
-            m_ids.push_back(pairs->pairs[2 * p]); m_ids.push_back(pairs->pairs[2 * p + 1]); m_cnts.push_back(n);
-            m_segs.push_back(GraphSeg{jobs[p].q0, 0, at, n, 0});
-        }
+        b.add(pairs->pairs[2 * p], pairs->pairs[2 * p + 1], jobs[p].q0, 0, n);
     }
-    if (mirror) (void)graph_dev_append(c, g.get(), m_ids, m_cnts, m_segs, R.dev, nullptr);
+    b.done();
     c->guided_stats.ms_wall = now_ms() - t0;
     *out = g.release();
     return R3DM_OK;

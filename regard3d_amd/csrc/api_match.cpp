@@ -71,20 +71,14 @@ int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_str
         // r3dm_set_device_graphs: the same pairs, in the same order, into the graph's device mirror straight from d_out (no payload byte
         // of the mirror crosses PCIe: ids and counts are 12 bytes per pair of host-side bookkeeping)
         const bool mirror = c->device_graphs && (g->dev.valid || (g->pairs.empty() && g->dev.P == 0));
-        if (mirror && !g->dev.valid) { g->dev.valid = true; g->dev.device = c->device; }
-        std::vector<uint32_t> ids, cnts;
-        std::vector<GraphSeg> segs;
-        uint64_t dst = 0;
+        GraphBuilder b(c, g, mirror, h_m, nullptr, c->d_out.as<r3dm_match>(), nullptr);
         g->matches.reserve(g->matches.size() + (size_t)total);     // (one allocation: a graph of millions of matches otherwise re-grows a dozen times)
         g->pairs.reserve(g->pairs.size() + 2 * (size_t)P); g->offsets.reserve(g->offsets.size() + P);
         for (uint32_t p = 0; p < P; ++p) {
             if (h_cnt[p] == 0) continue;                   // empty vectors never enter the map
-            g->pairs.push_back(jobs[p].I); g->pairs.push_back(jobs[p].J);
-            g->matches.insert(g->matches.end(), h_m + h_off[p], h_m + h_off[p] + h_cnt[p]);
-            g->offsets.push_back(g->matches.size());
-            if (mirror) { ids.push_back(jobs[p].I); ids.push_back(jobs[p].J); cnts.push_back(h_cnt[p]); segs.push_back(GraphSeg{h_off[p], 0, dst, h_cnt[p], 0}); dst += h_cnt[p]; }
+            b.add(jobs[p].I, jobs[p].J, h_off[p], 0, h_cnt[p]);
         }
-        if (mirror) (void)graph_dev_append(c, g, ids, cnts, segs, c->d_out.as<r3dm_match>(), nullptr);
+        b.done();
     }
     return R3DM_OK;
 }

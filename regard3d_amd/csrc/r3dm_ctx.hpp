@@ -278,9 +278,6 @@ struct HostImage : ViewState {
     inline void mount(struct r3dm_index* ix);
 };
 
-int graph_dev_append(r3dm_ctx* c, r3dm_graph* g, const std::vector<uint32_t>& pair_ids, const std::vector<uint32_t>& counts, std::vector<GraphSeg>& segs,
-                     const r3dm_match* src, const uint32_t* idx);      // api_core.cpp
-
 inline uint32_t kernel_G_for(uint32_t dim)
 {
     const uint32_t g = (dim + 7) / 8;
@@ -339,9 +336,6 @@ struct FilterBufs {
     // of different priorities never do.
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // the cooperative kernel of the kind's long pairs (kernels_filter_coop.hip) runs beside the one-workgroup kernel of its short ones
-    hipStream_t stream2 = nullptr;
-    hipEvent_t ev2 = nullptr;
     PinBuf pin_idx;           // page-locked landing zone of the inlier indices
     void release()
     {
@@ -349,9 +343,7 @@ struct FilterBufs {
         if (ev0) (void)hipEventDestroy(ev0);
         if (ev1) (void)hipEventDestroy(ev1);
         if (stream) (void)hipStreamDestroy(stream);
-        if (ev2) (void)hipEventDestroy(ev2);
-        if (stream2) (void)hipStreamDestroy(stream2);
-        ev0 = ev1 = ev2 = nullptr; stream = stream2 = nullptr;
+        ev0 = ev1 = nullptr; stream = nullptr;
         DevBuf* b[] = {&f_pairs, &f_ids, &f_offs, &f_matches, &f_inl_cnt, &f_inl_idx, &f_F, &f_thr, &f_iters, &f_log10, &f_logck, &f_scratch, &f_kinv, &f_spill, &f_soff, &f_order, &f_coop, &f_coop_prof, &f_la};
         for (DevBuf* x : b) x->release();
     }
@@ -480,6 +472,48 @@ struct r3dm_ctx {
     double guided_ratio[3] = {0.6, 0.6, -1.0};
     GuidedBufs gb;
     r3dm_guided_stats guided_stats{};                        // last guided step (r3dm_guided_report)
+};
+
+int graph_dev_append(r3dm_ctx* c, r3dm_graph* g, const std::vector<uint32_t>& pair_ids, const std::vector<uint32_t>& counts, std::vector<GraphSeg>& segs,
+                     const r3dm_match* src, const uint32_t* idx);      // api_core.cpp
+
+// Appends pairs to a result graph (match batches, the filters' inliers and guided lists, r3dm_guided_match): a pair's list is src[at ..
+// at + n), or src[idx[ix_at .. ix_at + n)] when the builder has an index list.  With `mirror` (r3dm_set_device_graphs) the builder also
+// records where every list lies in the device copies of those arrays, and done() gathers them into the graph's device mirror; a failed
+// gather only invalidates the mirror (api_core.cpp).
+struct GraphBuilder {
+    r3dm_ctx* c;
+    r3dm_graph* g;
+    bool mirror;
+    const r3dm_match* src; const uint32_t* idx;               // host arrays the lists are read from
+    const r3dm_match* dev_src; const uint32_t* dev_idx;       // the same arrays on the device
+    std::vector<uint32_t> ids, cnts;
+    std::vector<GraphSeg> segs;
+    uint64_t dst = 0;                                         // matches appended so far (the segments count from the first of them)
+    GraphBuilder(r3dm_ctx* c_, r3dm_graph* g_, bool mirror_, const r3dm_match* src_, const uint32_t* idx_, const r3dm_match* dev_src_,
+                 const uint32_t* dev_idx_)
+        : c(c_), g(g_), mirror(mirror_), src(src_), idx(idx_), dev_src(dev_src_), dev_idx(dev_idx_)
+    {
+        if (mirror && !g->dev.valid) { g->dev.valid = true; g->dev.device = c->device; }
+    }
+    void add(uint32_t I, uint32_t J, uint64_t at, uint64_t ix_at, uint32_t n)
+    {
+        g->pairs.push_back(I); g->pairs.push_back(J);
+        if (idx) {
+            const size_t base = g->matches.size();
+            g->matches.resize(base + n);
+            r3dm_match* d = g->matches.data() + base;
+            const r3dm_match* s = src + at;
+            const uint32_t* ix = idx + ix_at;
+            for (uint32_t q = 0; q < n; ++q) d[q] = s[ix[q]];
+        } else {
+            g->matches.insert(g->matches.end(), src + at, src + at + n);
+        }
+        g->offsets.push_back(g->matches.size());
+        if (mirror) { ids.push_back(I); ids.push_back(J); cnts.push_back(n); segs.push_back(GraphSeg{at, ix_at, dst, n, 0}); }
+        dst += n;
+    }
+    void done() { if (mirror) (void)graph_dev_append(c, g, ids, cnts, segs, dev_src, dev_idx); }
 };
 
 #define R3DM_HIP(ctx, call)                                                            \

@@ -430,14 +430,19 @@ def test_filters_side_by_side_equal_the_single_calls(ctx):
     for i in range(sc.n_images):
         ctx.set_image(i, sc.descs[i], sc.xys[i], 4000, 3000); ctx.set_intrinsics(i, K)
     g = ctx.match_pairs(sc.exhaustive_pairs(), 0.6, True)
-    one = {"F": ctx.filter_F(g), "E": ctx.filter_E(g), "H": ctx.filter_H(g)}
-    for which in ("FEH", "FH", "E", "EH"):
+    one, report = {}, {}
+    for k, fn in (("F", ctx.filter_F), ("E", ctx.filter_E), ("H", ctx.filter_H)):
+        one[k] = fn(g)
+        report[k] = ctx.filter_report()
+    for which in ("FEH", "FH", "E", "EH", "F", "H"):
         for rep in range(2):
             got, msk, msw = ctx.filter_FEH(g, which)
             for k in which:
                 assert np.array_equal(got[k].pairs, one[k].pairs) and np.array_equal(got[k].offsets, one[k].offsets), (which, k)
                 assert np.array_equal(got[k].matches, one[k].matches), (which, k)
             assert all(msk["FEH".index(k)] > 0 for k in which)
+            # r3dm_filter_report afterwards: the E call's, else the last requested kind's
+            assert ctx.filter_report() == report["E" if "E" in which else which[-1]], which
     assert one["F"].num_pairs >= 5
 
 
