@@ -1027,7 +1027,7 @@ void ak_prune_level_kernel(const AkLevelDev* __restrict__ levels, uint32_t live_
 // connected components of "within size of each other" (the very float predicate of the rule), and nothing one component does is seen
 // by another: first slot in list order within the radius = first slot OF THE COMPONENT in the order its candidates opened them.
 //   link     one lane per candidate, union-find over the earlier candidates of the rows within the radius (a wave reads them uniformly)
-//   flatten  root, member count and last member of every component
+//   flatten  root, member count and last member of every component (a walk without path halving: see the kernel)
 //   small    a component of <= 64 candidates by one wavefront with its slots in registers (lane = slot, in opening order); a lone
 //            candidate opens its slot on the spot; larger components are queued
 //   large    a queued component by one wavefront: members gathered in raster order, then the batched rule above with the live set in LDS
@@ -1088,7 +1088,12 @@ void ak_prune_flatten_kernel(const AkLevelDev* __restrict__ levels)
     const uint32_t n = L.counts[0];
     uint32_t* par = reinterpret_cast<uint32_t*>(L.live);
     for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < n; i += gridDim.x * 256u) {
-        const uint32_t r = ak_uf_find(par, i);
+        // a walk WITHOUT path halving (as ac_cc_flatten_kernel): the halving find of another lane could put a mere ancestor back over the
+        // root stored here; that member then fails `par[j] == root` in the small / large kernels -- a dropped candidate, or, in a queued
+        // component, a gather that fills fewer than `sz` member indices and leaves the rest to whatever out1 held before.  The only
+        // stores now are par[i] = root, so every chain a lane follows stays one of ancestors.
+        uint32_t r = i;
+        for (uint32_t p = ak_ld(par + r); p != r; p = ak_ld(par + r)) r = p;
         if (r != i) __hip_atomic_store(par + i, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         atomicAdd(par + n + r, 1u);
         atomicMax(par + 2u * n + r, i);

@@ -1,7 +1,7 @@
 // Host program in the reference's own language driving the two C++ faces of the boundary:
 //   argv[1] = "knn"   : ArrayMatcher_r3dm<float>::Build + SearchNeighbours(NN=2) on a .desc pair,
 //                       writes "q i0 d0 i1 d1" lines (what RegionsMatcherT::MatchDistanceRatio consumes)
-//   argv[1] = "stage" : R3DComputeMatches::computeMatches on a matches directory
+//   argv[1] = "stage" : R3DComputeMatches::computeMatches on a matches directory ("stages": two of them on one stage object)
 // Used by tests/test_gpu_cpp_host.py; also the compile check of include/*.hpp on CPU.
 #include <cstdio>
 #include <cstdlib>
@@ -26,6 +26,39 @@ static bool read_desc(const char* path, int dim, std::vector<float>& out, int& n
     fclose(f);
     n = (int)cnt;
     return ok;
+}
+
+// one R3DComputeMatches::computeMatches stage of a (possibly kept-alive) stage object on a matches directory ("stage" / "stages" modes)
+static int run_stage(r3d_amd::R3DComputeMatches& stage, const char* matches_dir, int dim, char** names, int n_names)
+{
+    std::vector<r3d_amd::View> views;
+    // synthetic views (regard3d_amd/synth.py): 4000 x 3000, f = 1.2 * width, principal point at the centre
+    for (int k = 0; k < n_names; ++k) views.push_back({(uint32_t)k, 4000, 3000, names[k], 4800.0, 2000.0, 1500.0});
+    stage.clearViews();
+    stage.addViews(views);
+    stage.setRegionsType(R3DM_F32, (uint32_t)dim);
+    stage.setProgressCallback([](float p, const char* msg, void*) { fprintf(stderr, "progress %.2f %s\n", p, msg); }, nullptr);
+    r3d_amd::R3DFParams params;
+    r3d_amd::R3DProjectPaths paths;
+    paths.relativeMatchesPath_ = matches_dir;
+    // R3DM_TEST_ALGO selects the dispatch arm (default 9 = GPU brute force; 1..3 = KGraph presets)
+    const char* algo_env = getenv("R3DM_TEST_ALGO");
+    const int algo = algo_env ? atoi(algo_env) : r3d_amd::R3DComputeMatches::kMatchingAlgorithmGPU;
+    if (getenv("R3DM_TEST_F32_TILES")) stage.setExactFastPaths(false);          // default: on
+    // R3DM_TEST_ARMS=requested: approximate arms always on the graph matcher (default: on whichever matcher is faster for the views)
+    const char* arms_env = getenv("R3DM_TEST_ARMS");
+    if (arms_env && !strcmp(arms_env, "requested")) stage.setApproximateArmsPolicy(r3d_amd::R3DComputeMatches::kArmsAsRequested);
+    const bool ok = stage.computeMatches(params, true, paths, 1, algo);
+    if (!ok) { fprintf(stderr, "computeMatches failed: %s\n", stage.errorMessage().c_str()); return 7; }
+    fprintf(stderr, "matcher %s\n", stage.lastMatchWasExhaustive() ? "exhaustive" : (stage.lastMatchWasHnsw() ? "hnsw" : "graph"));
+    printf("%zu %zu\n", stage.getStatistics().putativeMatches_.size(), stage.getStatistics().fundamentalMatches_.size());
+    return 0;
+}
+// R3DM_TEST_DEVICES=N: the device-list constructor with N entries of device 0
+static std::vector<int> stage_devices()
+{
+    const char* ndev_env = getenv("R3DM_TEST_DEVICES");
+    return std::vector<int>((size_t)(ndev_env ? atoi(ndev_env) : 1), 0);
 }
 
 int main(int argc, char** argv)
@@ -131,32 +164,20 @@ int main(int argc, char** argv)
         printf("%d %d %d\n", nthreads, same ? 1 : 0, in_flight);
         return 0;
     }
-    if (!strcmp(argv[1], "stage") && argc >= 5) {
-        // stage <matches_dir> <dim> <basename...>;  R3DM_TEST_DEVICES=N: the device-list constructor with N entries of device 0
-        const char* ndev_env = getenv("R3DM_TEST_DEVICES");
-        const std::vector<int> devices((size_t)(ndev_env ? atoi(ndev_env) : 1), 0);
-        r3d_amd::R3DComputeMatches stage(devices);
-        std::vector<r3d_amd::View> views;
-        // synthetic views (regard3d_amd/synth.py): 4000 x 3000, f = 1.2 * width, principal point at the centre
-        for (int k = 4; k < argc; ++k) views.push_back({(uint32_t)(k - 4), 4000, 3000, argv[k], 4800.0, 2000.0, 1500.0});
-        stage.addViews(views);
-        stage.setRegionsType(R3DM_F32, (uint32_t)atoi(argv[3]));
-        stage.setProgressCallback([](float p, const char* msg, void*) { fprintf(stderr, "progress %.2f %s\n", p, msg); }, nullptr);
-        r3d_amd::R3DFParams params;
-        r3d_amd::R3DProjectPaths paths;
-        paths.relativeMatchesPath_ = argv[2];
-        // R3DM_TEST_ALGO selects the dispatch arm (default 9 = GPU brute force; 1..3 = KGraph presets)
-        const char* algo_env = getenv("R3DM_TEST_ALGO");
-        const int algo = algo_env ? atoi(algo_env) : r3d_amd::R3DComputeMatches::kMatchingAlgorithmGPU;
-        if (getenv("R3DM_TEST_F32_TILES")) stage.setExactFastPaths(false);          // default: on
-        // R3DM_TEST_ARMS=requested: approximate arms always on the graph matcher (default: on whichever matcher is faster for the views)
-        const char* arms_env = getenv("R3DM_TEST_ARMS");
-        if (arms_env && !strcmp(arms_env, "requested")) stage.setApproximateArmsPolicy(r3d_amd::R3DComputeMatches::kArmsAsRequested);
-        const bool ok = stage.computeMatches(params, true, paths, 1, algo);
-        if (!ok) { fprintf(stderr, "computeMatches failed: %s\n", stage.errorMessage().c_str()); return 7; }
-        fprintf(stderr, "matcher %s\n", stage.lastMatchWasExhaustive() ? "exhaustive" : (stage.lastMatchWasHnsw() ? "hnsw" : "graph"));
-        printf("%zu %zu\n", stage.getStatistics().putativeMatches_.size(), stage.getStatistics().fundamentalMatches_.size());
-        return 0;
+    if (!strcmp(argv[1], "stage") && argc >= 5) {        // stage <matches_dir> <dim> <basename...>
+        r3d_amd::R3DComputeMatches stage(stage_devices());
+        return run_stage(stage, argv[2], atoi(argv[3]), argv + 4, argc - 4);
+    }
+    if (!strcmp(argv[1], "stages") && argc >= 7) {
+        // stages <dim> <matches_dir A> <n A> <basename of A...> <matches_dir B> <basename of B...>: two stages, one after the other, on
+        // ONE kept-alive R3DComputeMatches object (clearViews between them): the second stage runs on the contexts, and in the grown
+        // buffers, of the first.  (A new object per stage would create and destroy its own contexts: no history.)
+        const int dim = atoi(argv[2]), nA = atoi(argv[4]);
+        if (nA < 1 || 5 + nA + 2 > argc) return 2;
+        r3d_amd::R3DComputeMatches stage(stage_devices());
+        const int rc = run_stage(stage, argv[3], dim, argv + 5, nA);
+        if (rc) return rc;
+        return run_stage(stage, argv[5 + nA], dim, argv + 6 + nA, argc - 6 - nA);
     }
     return 2;
 }

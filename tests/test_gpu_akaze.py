@@ -4,6 +4,8 @@ compared BIT-EXACTLY.  (The oracle itself is parity-unpinned against the referen
 import numpy as np
 import pytest
 
+import akaze_lattices
+
 pytestmark = pytest.mark.gpu
 
 
@@ -105,6 +107,52 @@ def test_in_level_pruning_in_parallel_equals_the_one_wavefront_form(ctx, tmp_pat
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert np.array_equal(np.load(str(tmp_path / "k.npy")), kps) and np.array_equal(np.load(str(tmp_path / "r.npy")), resp)
+
+
+@pytest.mark.parametrize("thr", akaze_lattices.THRESHOLDS)
+@pytest.mark.parametrize("name", ["tile3", "diag13"])
+def test_lattice_images_with_equal_responses_equal_the_cpu_restatement(ctx, oracle, name, thr):
+    """Exactly periodic images (tests/akaze_lattices.py) at thresholds 1e-20 and 0: more than a thousand candidates per image meet a kept
+    point of EQUAL response inside its radius (counted on the CPU by tests/test_akaze_lattice_ties.py); the in-level rule keeps the
+    earlier one.  detect_akaze, detect_akaze_mldb and detect_akaze_batch, the lattice between two ordinary scenes.  (The CPU replay meets
+    no subnormal determinant above either threshold on these images, so denormal handling is not what these thresholds exercise.)"""
+    img = akaze_lattices.lattice_images()[name]
+    ref = oracle.akaze_detect(img, thr)
+    assert len(ref["kps"]) > 1000
+    kps, resp = ctx.detect_akaze(img, thr)
+    assert len(kps) == len(ref["kps"])
+    assert np.array_equal(resp, ref["responses"]) and np.array_equal(kps, ref["kps"])
+    k2, desc = ctx.detect_akaze_mldb(img, thr)
+    okp, odesc, _ = oracle.akaze_detect_mldb(img, thr)
+    assert np.array_equal(k2, okp) and np.array_equal(desc, odesc)
+    imgs = [_scene(akaze_lattices.H, akaze_lattices.W, 61, n_blobs=12), img, _scene(akaze_lattices.H, akaze_lattices.W, 62, n_blobs=12)]
+    for im, (kb, rb) in zip(imgs, ctx.detect_akaze_batch(imgs, thr)):
+        rf = oracle.akaze_detect(im, thr)
+        assert np.array_equal(kb, rf["kps"]) and np.array_equal(rb, rf["responses"])
+
+
+@pytest.mark.parametrize("env", [{"R3DM_AK_PRUNE": "0"}, {"R3DM_AK_LIVE_CAP": "8"}, {"R3DM_AK_PRUNE": "0", "R3DM_AK_LIVE_CAP": "8"}])
+def test_in_level_pruning_forms_agree_on_lattice_images_with_equal_responses(ctx, tmp_path, env):
+    """the developer-build variants of test_in_level_pruning_in_parallel_equals_the_one_wavefront_form on the two lattice images at both
+    thresholds (one child per variant): the one-wavefront form and the forced hand-back keep the same one of two equal responses"""
+    import os, subprocess, sys
+    imgs = akaze_lattices.lattice_images()
+    combos = [(name, thr) for name in sorted(imgs) for thr in akaze_lattices.THRESHOLDS]
+    prod = [ctx.detect_akaze(imgs[name], thr) for name, thr in combos]
+    assert all(len(k) > 1000 for k, _ in prod)
+    np.savez(str(tmp_path / "imgs.npz"), **imgs)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (f"import sys; sys.path.insert(0, {root!r}); import numpy as np; from regard3d_amd import api; api.use_developer_library(); "
+            f"c = api.Context(0); z = np.load({str(tmp_path / 'imgs.npz')!r}); out = {{}}\n"
+            f"for i, (name, thr) in enumerate({combos!r}):\n"
+            f"    out['k%d' % i], out['r%d' % i] = c.detect_akaze(z[name], thr)\n"
+            f"np.savez({str(tmp_path / 'out.npz')!r}, **out)")
+    r = subprocess.run([sys.executable, "-c", code], env=dict({k: v for k, v in os.environ.items() if not k.startswith("R3DM_")}, **env),
+                       capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    z = np.load(str(tmp_path / "out.npz"))
+    for i, (k, rs) in enumerate(prod):
+        assert np.array_equal(z[f"k{i}"], k) and np.array_equal(z[f"r{i}"], rs), combos[i]
 
 
 @pytest.mark.parametrize("env", [{"R3DM_AK_HEAD": "1"}, {"R3DM_AK_FED_MARCH": "0"}, {"R3DM_AK_FED_MARCH": "0", "R3DM_AK_FED_MULTI": "0"},
