@@ -230,6 +230,10 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     // 3 Dpad products + one C operand per MFMA with a one-sided 2^-23 per addition on partial sums <= 2 (||a||^2 + ||b||^2), plus the
     // reference sum's own (D/2 + 12) 2^-24 -- together below (3 Dpad + 34) 2^-22, + 2 for the count kernel's bias (kernels_match.hip, l2_knn2_split_kernel)
     if (plan.path == BatchPath::kSplitPlanes || plan.path == BatchPath::kCountTiles) mp.err_scale = (3.0f * (float)(first.G * 8) + 36.0f) * 2.3841858e-07f;      // (+ 2: the count kernel's keys carry ||b||^2 / (2 s_b) and drop it again)
+    // (developer build: the slack factor in permille of the derived one -- 0 certifies on the bare inequality.  Only verdicts depend
+    //  on it, no address does; tests/test_gpu_certificate.py shows that its cases notice.  The split planes' absolute part is a
+    //  constant of their kernel and stays.)
+    if (const int permille = r3dm_dev_knob("R3DM_CERT_SLACK_PERMILLE", 1000); permille != 1000) mp.err_scale *= (float)permille * 0.001f;
     mp.nn_idx = c->d_nn.as<uint32_t>();
     mp.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
     mp.knn_dist = knn_idx_host ? c->d_knn_dist.as<float>() : nullptr;

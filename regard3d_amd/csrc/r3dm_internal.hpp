@@ -209,7 +209,7 @@ struct MatchParams {
     uint32_t      xcd_map;        // != 0: all workgroups of a pair on one XCD (blockIdx & 7)
     uint32_t      q_stride;       // entries per pair in nn_idx / knn_* (>= max n_J)
     float         ratio_R;        // ratio^2 (squared metric) or ratio
-    float         err_scale;      // certification slack factor: 8 * Dpad * 2^-24
+    float         err_scale;      // certification slack factor: 4.25 Dpad 2^-24 (f32 tiles), (3 Dpad + 36) 2^-22 (split / count tiles)
     uint32_t*     nn_idx;         // [n_pairs][q_stride] matched I row, kNone, or kFallback
     int32_t*      knn_idx;        // optional [n_pairs][q_stride][2]
     float*        knn_dist;       // optional [n_pairs][q_stride][2]
