@@ -271,6 +271,24 @@ int  r3dm_index_create(r3dm_ctx* ctx, const void* dataset, uint32_t n_dataset, u
 int  r3dm_index_knn2(r3dm_ctx* ctx, const r3dm_index* index, const void* query, uint32_t n_query, int32_t* out_idx, float* out_dist);
 void r3dm_index_destroy(r3dm_index* index);
 
+/* ---- the same two calls for k neighbours, k = 1 .. R3DM_KNN_MAX: ArrayMatcher::SearchNeighbours(query, nbQuery, &idx, &dist, NN)
+ * with any NN, as the reference's plugins serve it (src/utils/matcher_kgraph.h:205-251, matcher_hnsw.h:138-173) ----
+ * out_idx / out_dist: k entries per query at [q * k + j], ascending under (distance, dataset row): equal distances, lowest row
+ * first.  F32 / U8 distances are the reference's f32 sums (4-way unrolled, no FMA), Hamming distances exact integers as float.
+ * R3DM_ERR_INVALID: k < 1, k > R3DM_KNN_MAX, n_query < 1, n_dataset < k (the plugins' "NN > rows" rule), null pointers (a null
+ * context is refused before any GPU is touched).  R3DM_ERR_UNSUPPORTED: the BIN byte-length rule of r3dm_knn2.
+ * k <= 2 with n_dataset >= 2 runs the 2-NN path of r3dm_knn2 (bit-identical to it by construction; k = 1 is its first column).
+ * Everything else -- k >= 3, and k = 1 on a one-row dataset -- runs on k-list kernels of its own: always the f32 tiles (F32 / U8)
+ * or the popcount kernel (BIN).  r3dm_set_integer_mfma / _split_mfma / _hamming_mfma are IGNORED there (those nominators keep
+ * 2-lists), and none of their counters moves.  Lengths without a tensor kernel (> 256 elements) are scanned exactly, as in
+ * r3dm_match_pairs.  r3dm_stats.n_queries and .n_exact_fallback (queries answered by the exact scan) describe the call. */
+#define R3DM_KNN_MAX 8
+int r3dm_knn(r3dm_ctx* ctx, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
+             uint32_t dim, r3dm_dtype dtype, uint32_t k, int32_t* out_idx, float* out_dist);
+/* same mounting, locking and "any context of the index's device" rules as r3dm_index_knn2 */
+int r3dm_index_knn(r3dm_ctx* ctx, const r3dm_index* index, const void* query, uint32_t n_query, uint32_t k,
+                   int32_t* out_idx, float* out_dist);
+
 /* ---- approximate matching: the KGraph plugin path (BASELINE config C5) ----
  * Replaces kgraph_match (src/R3DComputeMatches.cpp:808-902): per first view I an index over its descriptors
  * (ArrayMatcher_kgraph::Build, src/utils/matcher_kgraph.h:138-153), per query row of J a graph search for its 2

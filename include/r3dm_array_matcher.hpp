@@ -19,7 +19,9 @@
 // (/root/reference/src/R3DComputeMatches.cpp:838-842).  Without it (this repository: no OpenMVG in
 // the image) equivalent stand-in types are used so the adapter can be compiled and tested.
 //
-// Only NN <= 2 is served (MatchDistanceRatio asks for exactly 2).
+// Any NN up to R3DM_KNN_MAX (8) is served, as the reference's own plugins do (matcher_kgraph.h:205-251 `sparams.K = NN`,
+// matcher_hnsw.h:138-173 `searchKnn(q, NN)`): NN <= 2 on the 2-NN path (MatchDistanceRatio asks for exactly 2), 3 <= NN <= 8 on the
+// k-list kernels (r3dm_index_knn: second-ratio tests, k-NN voting, localisation against a map).  NN > 8 or NN > nbRows: `false`.
 // Build() stages the dataset ONCE (r3dm_index_create: copy to HBM + MFMA fragment tiles + norms); every SearchNeighbours
 // uploads only its query rows (r3dm_index_knn2) -- the amortisation the plugin contract is built around: the reference
 // builds per first view I and searches once per J (/root/reference/src/R3DComputeMatches.cpp:462-479).
@@ -102,6 +104,7 @@ public:
     bool SearchNeighbours(const Scalar* query, int nbQuery, IndMatches* pvec_indices,
                           std::vector<DistanceType>* pvec_distances, size_t NN) R3DM_OVERRIDE
     {
+        if (NN > 2) return SearchK(query, nbQuery, pvec_indices, pvec_distances, NN);
         if (!index_ || !query || nbQuery < 1 || NN < 1 || NN > 2 || nbRows_ < 2) return false;
         std::vector<int32_t> idx(2 * static_cast<size_t>(nbQuery));
         std::vector<float> dist(2 * static_cast<size_t>(nbQuery));
@@ -124,6 +127,28 @@ public:
     }
 
 private:
+    // 3 <= NN <= R3DM_KNN_MAX: r3dm_index_knn.  The opt-in fast paths keep 2-lists and are not consulted (include/r3dm.h).
+    bool SearchK(const Scalar* query, int nbQuery, IndMatches* pvec_indices, std::vector<DistanceType>* pvec_distances, size_t NN)
+    {
+        if (!index_ || !query || nbQuery < 1 || NN > R3DM_KNN_MAX || NN > static_cast<size_t>(nbRows_)) return false;
+        std::vector<int32_t> idx(NN * static_cast<size_t>(nbQuery));
+        std::vector<float> dist(NN * static_cast<size_t>(nbQuery));
+        {
+            detail::ContextLease lease(pool_);                 // one stream + scratch per concurrent search
+            if (!lease.ctx) return false;
+            if (r3dm_index_knn(lease.ctx, index_, query, static_cast<uint32_t>(nbQuery), static_cast<uint32_t>(NN), idx.data(), dist.data()) != R3DM_OK)
+                return false;
+        }
+        pvec_indices->reserve(pvec_indices->size() + nbQuery * NN);
+        pvec_distances->reserve(pvec_distances->size() + nbQuery * NN);
+        for (int q = 0; q < nbQuery; ++q)
+            for (size_t k = 0; k < NN; ++k) {
+                pvec_indices->emplace_back(static_cast<uint32_t>(q), static_cast<uint32_t>(idx[NN * q + k]));
+                pvec_distances->emplace_back(static_cast<DistanceType>(dist[NN * q + k]));
+            }
+        return true;
+    }
+
     detail::ContextPool& pool_;
     r3dm_index* index_ = nullptr;
     int nbRows_ = 0, dimension_ = 0;

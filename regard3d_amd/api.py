@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libr3dm.so")
 
 F32, U8, BIN = 0, 1, 2
+KNN_MAX = 8                      # R3DM_KNN_MAX (include/r3dm.h)
 LAYOUT_ROWS, LAYOUT_BF16, LAYOUT_SPLIT, LAYOUT_COUNTS, LAYOUT_BIN8 = 1, 2, 4, 8, 16
 NONE = 0xFFFFFFFF
 
@@ -30,6 +31,7 @@ EXPORTS = [
     "r3dm_filter_FEH", "r3dm_host_threads", "r3dm_set_features_sink", "r3dm_multi_set_features_sink", "r3dm_set_deferred_feature_files", "r3dm_set_background_nice", "r3dm_multi_set_background_nice", "r3dm_features_files_wait", "r3dm_multi_set_deferred_feature_files", "r3dm_multi_features_files_wait", "r3dm_hnsw_preset", "r3dm_match_pairs_hnsw", "r3dm_hnsw_knn2", "r3dm_hnsw_knn2_on_index", "r3dm_hnsw_index",
     "r3dm_mrpt_preset", "r3dm_match_pairs_mrpt", "r3dm_mrpt_knn2", "r3dm_mrpt_index", "r3dm_multi_match_pairs_mrpt",
     "r3dm_set_integer_mfma", "r3dm_set_split_mfma", "r3dm_set_hamming_mfma", "r3dm_index_create", "r3dm_index_knn2", "r3dm_index_destroy",
+    "r3dm_knn", "r3dm_index_knn",
     "r3dm_multi_create", "r3dm_multi_destroy", "r3dm_multi_num_devices", "r3dm_multi_ctx", "r3dm_multi_last_error",
     "r3dm_multi_set_image", "r3dm_multi_transfer_counts", "r3dm_multi_set_intrinsics", "r3dm_multi_clear_images", "r3dm_multi_set_integer_mfma",
     "r3dm_multi_match_pairs", "r3dm_multi_match_pairs_kgraph", "r3dm_multi_match_pairs_hnsw", "r3dm_multi_filter_F", "r3dm_multi_filter_H", "r3dm_multi_filter_E", "r3dm_shard_pairs",
@@ -322,6 +324,8 @@ def load_library():
     L.r3dm_liop_describe_patches.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.r3dm_extract_liop.argtypes = [vp, vp, u32, u32, vp, u32, C.c_float, vp, vp]
     L.r3dm_knn2.argtypes = [vp, vp, u32, vp, u32, u32, C.c_int, vp, vp]
+    L.r3dm_knn.argtypes = [vp, vp, u32, vp, u32, u32, C.c_int, u32, vp, vp]
+    L.r3dm_index_knn.argtypes = [vp, vp, vp, u32, u32, vp, vp]
     L.r3dm_detect_akaze.argtypes = [vp, vp, u32, u32, C.c_float, vp, vp, u32, C.POINTER(u32)]
     L.r3dm_detect_akaze_mldb.argtypes = [vp, vp, u32, u32, C.c_float, vp, vp, u32, C.POINTER(u32)]
     L.r3dm_gray_from_bgr8.argtypes = [vp, vp, u32, u32, vp]
@@ -404,6 +408,25 @@ def _ptr(a) -> Optional[int]:
     if isinstance(a, np.ndarray):
         return a.ctypes.data
     return int(a.data_ptr())           # torch tensor
+
+
+def _rows_arg(a):
+    """a contiguous [n, dim] numpy array or torch tensor for the ABI.  The library reads a device tensor on its own stream: work torch
+    has queued on the tensor's current stream must have finished before the call, so that stream is synchronised first."""
+    if isinstance(a, np.ndarray):
+        return np.ascontiguousarray(a)
+    a = a.contiguous()
+    if a.is_cuda:
+        import torch
+        torch.cuda.current_stream(a.device).synchronize()
+    return a
+
+
+def _is_f32(a) -> bool:
+    if isinstance(a, np.ndarray):
+        return a.dtype == np.float32
+    import torch
+    return a.dtype == torch.float32
 
 
 class Graph:
@@ -907,6 +930,25 @@ class Context:
         idx = np.full((max(nq, 1), 2), -1, np.int32); dist = np.zeros((max(nq, 1), 2), np.float32)
         self._check(self._L.r3dm_knn2(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1], dt,
                                       _ptr(idx), _ptr(dist)), "r3dm_knn2")
+        return idx[:nq], dist[:nq]
+
+    def knn(self, dataset, query, k: int, binary: bool = False):
+        """ArrayMatcher::SearchNeighbours(NN = k), k = 1 .. KNN_MAX (r3dm_knn): (idx [nq, k] int32, dist [nq, k] float32), each row
+        ascending under (distance, dataset row).  dataset / query: numpy arrays or torch tensors (host or device memory)."""
+        dataset = _rows_arg(dataset); query = _rows_arg(query)
+        dt = F32 if _is_f32(dataset) else (BIN if binary else U8)
+        nq, k = int(query.shape[0]), int(k)
+        idx = np.full((max(nq, 1), max(k, 1)), -1, np.int32); dist = np.zeros((max(nq, 1), max(k, 1)), np.float32)
+        self._check(self._L.r3dm_knn(self._h, _ptr(dataset), int(dataset.shape[0]), _ptr(query), nq, int(dataset.shape[1]), dt, k,
+                                     _ptr(idx), _ptr(dist)), "r3dm_knn")
+        return idx[:nq], dist[:nq]
+
+    def index_knn(self, index: "Index", query, k: int):
+        """ArrayMatcher::SearchNeighbours(NN = k) against a staged dataset (r3dm_index_knn); any context of the index's device"""
+        query = _rows_arg(query)
+        nq, k = int(query.shape[0]), int(k)
+        idx = np.full((max(nq, 1), max(k, 1)), -1, np.int32); dist = np.zeros((max(nq, 1), max(k, 1)), np.float32)
+        self._check(self._L.r3dm_index_knn(self._h, index._h, _ptr(query), nq, k, _ptr(idx), _ptr(dist)), "r3dm_index_knn")
         return idx[:nq], dist[:nq]
 
     def index_create(self, dataset: np.ndarray, binary: bool = False) -> "Index":

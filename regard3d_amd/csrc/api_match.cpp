@@ -493,6 +493,156 @@ extern "C" int r3dm_index_knn2(r3dm_ctx* c, const r3dm_index* ix, const void* qu
 }
 
 // ------------------------------------------------------------------------------------------------
+// k neighbours, k = 1 .. R3DM_KNN_MAX (kernels_match_knn.hip): ArrayMatcher::SearchNeighbours with any NN
+// (/root/reference/src/utils/matcher_kgraph.h:205-251).  One (dataset, query) pair per call; k <= 2 is served by the 2-NN path above.
+// ------------------------------------------------------------------------------------------------
+// the k-list kernels over the views in slots sI (dataset) and sJ (queries): always the f32 tiles / the popcount kernel, whatever the
+// r3dm_set_*_mfma switches say (their nominators keep 2-lists)
+static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int32_t* out_idx_host, float* out_dist_host)
+{
+    { const int rcs = sync_view_stats(c); if (rcs != R3DM_OK) return rcs; }
+    const r3dm_dtype dtype = c->imgs[sI]->dtype;
+    const uint32_t nI = c->imgs[sI]->n, nq = c->imgs[sJ]->n, G = c->imgs[sI]->G, dim = c->imgs[sI]->dim, words = c->imgs[sI]->words;
+    // the nominees are re-scored on the row-major rows, and the exact scan reads them
+    if (dtype != R3DM_BIN) { const int rcl = ensure_layouts(c, {sI, sJ}, kLayRows); if (rcl != R3DM_OK) return rcl; }
+    const size_t out_bytes = (size_t)nq * k * 4;
+    R3DM_HIP(c, c->d_knn_idx.ensure(out_bytes));
+    R3DM_HIP(c, c->d_knn_dist.ensure(out_bytes));
+    // [fb_cnt | pad][fb_q: n_query]: a query is listed at most once, the list cannot overflow
+    R3DM_HIP(c, c->d_fb.ensure((16 + (size_t)nq) * 4));
+    R3DM_HIP(c, hipMemsetAsync(c->d_fb.p, 0, 64, c->stream));
+
+    KnnParams kp{};
+    kp.imgs = c->d_imgs.as<ImgDev>();
+    kp.sI = sI; kp.sJ = sJ; kp.k = k;
+    kp.err_scale = 4.25f * (float)(G * 8) * 5.9604645e-08f;        // as run_match_batch on the f32 tiles (DESIGN.md "Certification")
+    kp.out_idx = c->d_knn_idx.as<int32_t>();
+    kp.out_dist = c->d_knn_dist.as<float>();
+    kp.fb_cnt = c->d_fb.as<uint32_t>();
+    kp.fb_q = c->d_fb.as<uint32_t>() + 16;
+
+    R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
+    uint64_t n_fallback = 0;
+    if (dtype == R3DM_BIN) {
+        R3DM_HIP(c, launch_hamming_knnk(c->stream, kp, words, nq));
+        R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
+    } else {
+        const hipError_t e = has_tensor_kernel(G) ? launch_l2_knnk(c->stream, kp, G, c->imgs[sI]->n_tiles, c->imgs[sJ]->n_tiles) : hipErrorInvalidValue;
+        if (e == hipErrorInvalidValue) {
+            // descriptor length without a tensor kernel (or a dataset beyond the nominator's reach): exact scan of every query
+            (void)hipGetLastError();
+            R3DM_HIP(c, launch_l2_exact_knn_items(c->stream, kp, nq, 0));
+            R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
+            n_fallback = nq;
+        } else {
+            R3DM_HIP(c, e);
+            R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));      // (the nominator alone, as run_match_batch times its tile kernel)
+            uint32_t cnt = 0;
+            R3DM_HIP(c, c->pin_small.ensure(64));
+            R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, kp.fb_cnt, 4, hipMemcpyDeviceToHost, c->stream));
+            R3DM_HIP(c, hipStreamSynchronize(c->stream));
+            memcpy(&cnt, c->pin_small.p, 4);
+            if (cnt > nq) { c->err = "k-NN: fallback list corrupt"; return R3DM_ERR_HIP; }
+            if (cnt) R3DM_HIP(c, launch_l2_exact_knn_items(c->stream, kp, cnt, 1));
+            n_fallback = cnt;
+        }
+    }
+    R3DM_HIP(c, hipMemcpyAsync(out_idx_host, kp.out_idx, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    R3DM_HIP(c, hipMemcpyAsync(out_dist_host, kp.out_dist, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    R3DM_HIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    c->stats.ms_match_kernels += ms;
+    c->stats.n_match_launches += 1;
+    c->stats.n_pairs += 1;
+    c->stats.n_queries += nq;
+    c->stats.n_exact_fallback += n_fallback;
+    if (dtype == R3DM_BIN) { c->stats.algorithmic_flops += 2.0 * nI * (double)nq * words; c->stats.algorithmic_bytes += ((double)nI + nq) * words * 4 + (double)nq * k * 8; }
+    else { c->stats.algorithmic_flops += 2.0 * nI * (double)nq * dim; c->stats.algorithmic_bytes += ((double)nI + nq) * dim * 4 + (double)nq * k * 8; }
+    return R3DM_OK;
+}
+
+// the counters a k-NN call reports: its queries, how many the exact scan answered -- and the opt-in paths' counters, which hold 0
+// after a call on the k-list kernels; ms_match_kernels holds the HIP-event time of the call's first kernel (tools/knn_perf.py)
+#define R3DM_KNN_COUNTERS {&r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma, \
+                           &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries}
+
+// first column of a 2-NN result
+static void first_column(const std::vector<int32_t>& i2, const std::vector<float>& d2, uint32_t n_query, int32_t* out_idx, float* out_dist)
+{
+    for (uint32_t q = 0; q < n_query; ++q) { out_idx[q] = i2[2 * (size_t)q]; out_dist[q] = d2[2 * (size_t)q]; }
+}
+
+static int r3dm_knn_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
+                         uint32_t dim, r3dm_dtype dtype, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    if (!c || !dataset || !query || !out_idx || !out_dist || dim == 0) return R3DM_ERR_INVALID;
+    if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || n_dataset < k) return R3DM_ERR_INVALID;      // ArrayMatcher plugins: NN > nbRows / nbQuery < 1
+    if (dtype != R3DM_F32 && dtype != R3DM_U8 && dtype != R3DM_BIN) return R3DM_ERR_INVALID;
+    if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
+    if (k <= 2 && n_dataset >= 2) {
+        // the 2-NN path itself: bit-identical to r3dm_knn2 by construction
+        int rc;
+        if (k == 2) rc = r3dm_knn2_impl(c, dataset, n_dataset, query, n_query, dim, dtype, out_idx, out_dist);
+        else {
+            std::vector<int32_t> i2(2 * (size_t)n_query); std::vector<float> d2(2 * (size_t)n_query);
+            rc = r3dm_knn2_impl(c, dataset, n_dataset, query, n_query, dim, dtype, i2.data(), d2.data());
+            if (rc == R3DM_OK) first_column(i2, d2, n_query, out_idx, out_dist);
+        }
+        if (rc == R3DM_OK) c->stats.n_queries = n_query;
+        return rc;
+    }
+    if (n_dataset >= (1u << 22)) { c->err = "more than 4M rows in one dataset"; return R3DM_ERR_UNSUPPORTED; }
+    R3DM_HIP(c, hipSetDevice(c->device));
+    PrivateSlots s(c, 2);
+    int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, dim, dtype, nullptr);
+    if (rc != R3DM_OK) return rc;
+    CallCounters counters(c, R3DM_KNN_COUNTERS, {&r3dm_stats::ms_match_kernels});
+    return run_knn_batch(c, s[0], s[1], k, out_idx, out_dist);
+}
+
+extern "C" int r3dm_knn(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
+                        uint32_t dim, r3dm_dtype dtype, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int { return r3dm_knn_impl(c, dataset, n_dataset, query, n_query, dim, dtype, k, out_idx, out_dist); });
+}
+
+static int r3dm_index_knn_impl(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    if (!c || !ix || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+    if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || ix->img.n < k) return R3DM_ERR_INVALID;
+    if (k <= 2 && ix->img.n >= 2) {
+        int rc;
+        if (k == 2) rc = r3dm_index_knn2_impl(c, ix, query, n_query, out_idx, out_dist);
+        else {
+            std::vector<int32_t> i2(2 * (size_t)n_query); std::vector<float> d2(2 * (size_t)n_query);
+            rc = r3dm_index_knn2_impl(c, ix, query, n_query, i2.data(), d2.data());
+            if (rc == R3DM_OK) first_column(i2, d2, n_query, out_idx, out_dist);
+        }
+        if (rc == R3DM_OK) c->stats.n_queries = n_query;
+        return rc;
+    }
+    if (ix->device != c->device) { c->err = "r3dm_index_knn: the index lives on another device"; return R3DM_ERR_INVALID; }
+    R3DM_HIP(c, hipSetDevice(c->device));
+    PrivateSlots s(c, 2);
+    r3dm_index* mix = const_cast<r3dm_index*>(ix);
+    { std::lock_guard<std::mutex> lk(mix->mu); c->imgs[s[0]]->mount(mix); }      // aliases of the index's buffers, for this call only
+    int rc = publish_entry(c, s[0]);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, ix->img.dim, ix->img.dtype, nullptr);
+    if (rc != R3DM_OK) return rc;
+    CallCounters counters(c, R3DM_KNN_COUNTERS, {&r3dm_stats::ms_match_kernels});
+    return run_knn_batch(c, s[0], s[1], k, out_idx, out_dist);
+}
+
+extern "C" int r3dm_index_knn(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int { return r3dm_index_knn_impl(c, ix, query, n_query, k, out_idx, out_dist); });
+}
+
+// ------------------------------------------------------------------------------------------------
 // approximate matching: graph index + graph search (kernels_ann.hip)
 // ------------------------------------------------------------------------------------------------
 extern "C" int r3dm_kgraph_preset(int preset, r3dm_kgraph_params* out)

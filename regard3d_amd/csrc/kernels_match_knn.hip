@@ -1,0 +1,428 @@
+// kernels_match_knn.hip -- exhaustive k-NN, k = 1 .. R3DM_KNN_MAX (8), of one (dataset, query) pair: what stands behind r3dm_knn /
+// r3dm_index_knn for k >= 3 (ArrayMatcher::SearchNeighbours with any NN, /root/reference/src/utils/matcher_kgraph.h:205-251,
+// matcher_hnsw.h:138-173).  The 2-NN kernels, Top2 and the ratio test are untouched; this unit shares only the header's metric and
+// buffer load with them.
+//   l2_knnk_mfma_kernel<G, PF, KL>     the nominator: the f32 MFMA tile stream of l2_knn2_mfma_kernel with K-lists per lane half
+//   knnk_finish<KL>                    its tail: re-score the nominees in the reference arithmetic, order, certify the k-th
+//   l2_exact_knn_items_kernel<KL>      the exact scan behind it (uncertified queries; lengths without a tensor kernel)
+//   hamming_knnk_kernel<W, KL, QL>     binary rows: xor + popcount with exact (distance, row) K-lists per lane
+// KL is the list depth a kernel is built with: 4 for k <= 4, 8 above; k itself is a run-time value (k <= KL).
+//
+// Arithmetic contract as everywhere (kernels_match_common.hpp): the f32 4-way unrolled sum of squared differences without FMA, equal
+// distances -> lowest dataset row.  This file is compiled with -ffp-contract=off; fused operations are spelled fmaf() / MFMA.
+#include "kernels_match_common.hpp"
+
+namespace r3dm {
+
+__device__ __forceinline__ bool knn_lex_less(float da, uint32_t ia, float db, uint32_t ib)
+{
+    return da < db || (da == db && ia < ib);
+}
+
+// ------------------------------------------------------------------------------------------------
+// K-list of one query column held by one lane HALF (16 of a tile's 32 rows): the KL smallest keys with their rows, ascending, and
+// the (KL + 1)-th smallest key d[KL] -- the smallest key this half did NOT nominate, its bound.  The depth is KL per half, not in
+// total: all k neighbours of a query may sit in rows of one half.
+// ------------------------------------------------------------------------------------------------
+template <int KL>
+struct TopK {
+    float d[KL + 1];
+    uint32_t i[KL];
+};
+
+template <int KL>
+__device__ __forceinline__ void topk_init(TopK<KL>& s)
+{
+#pragma unroll
+    for (int j = 0; j <= KL; ++j) s.d[j] = R3DM_INF;
+#pragma unroll
+    for (int j = 0; j < KL; ++j) s.i[j] = kNone;
+}
+
+// sorted insert, branch-free (v_med3 / v_cndmask): new d[j] = min(d[j], max(d[j - 1], key)).  Runs only behind a wave-wide test.
+template <int KL>
+__device__ __forceinline__ void topk_push(TopK<KL>& s, float key, uint32_t idx)
+{
+    bool c[KL];
+#pragma unroll
+    for (int j = 0; j < KL; ++j) c[j] = key < s.d[j];
+    s.d[KL] = __builtin_amdgcn_fmed3f(s.d[KL - 1], s.d[KL], key);
+#pragma unroll
+    for (int j = KL - 1; j >= 1; --j) {                 // downwards: d[j - 1], i[j - 1] are still the old ones
+        s.d[j] = __builtin_amdgcn_fmed3f(s.d[j - 1], s.d[j], key);
+        const uint32_t t = c[j] ? idx : s.i[j];
+        s.i[j] = c[j - 1] ? s.i[j - 1] : t;
+    }
+    s.d[0] = __builtin_amdgcn_fmed3f(-R3DM_INF, s.d[0], key);
+    s.i[0] = c[0] ? idx : s.i[0];
+}
+
+// One dataset tile (l2_tile_step of kernels_match.hip at NJ = 1, PIPE = 3): the MFMAs of tile t into `cur` while the VALU folds
+// the finished accumulator of tile t - 1 (`prev`) into the K-list.  Test-and-skip: a key changes the list only below the lane's
+// bound d[KL]; one ballot guards a slice of the accumulator, one more each key, and the insert runs only when some lane needs it.
+template <int G, int PF, int KL>
+__device__ __forceinline__ void knnk_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                               uint32_t soffA, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4], const f32x4 (&bq)[G],
+                                               f32x16& cur, const f32x16& prev, TopK<KL>& st, uint32_t prev_rowbase)
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) cur[r] = nrm[r >> 2][r & 3];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const f32x4 a = abuf[g % PF];
+        abuf[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 1024u);
+        if (g == 2) {   // next tile's norms: early, so the wait at the tile boundary finds them landed
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+        }
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc) cur = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bq[g][cc], cur, 0, 0, 0);
+        // this group's share of the previous tile's 16 keys
+        bool any = false;
+#pragma unroll
+        for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r) any |= prev[r] < st.d[KL];
+        if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+#pragma unroll
+            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
+                if (__builtin_amdgcn_ballot_w64(prev[r] < st.d[KL]) != 0ull)
+                    topk_push(st, prev[r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+        }
+        __builtin_amdgcn_sched_barrier(0);                // keep each prefetch / epilogue slice in its own step
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// Finish and certificate of one query column (lanes c and c + 32 hold its two halves' lists).
+//   1. nominees = the union of both lists (up to 2 KL rows); bound = min of the two halves' (KL + 1)-th keys
+//   2. every nominee is re-scored with exact_l2sq on the row-major rows, KL per lane half (on an exact pair -- the integer proof of
+//      l2_finish_queries -- key + ||q||^2 IS that distance and nothing is read again)
+//   3. the nominees are ranked under (distance, row); the first k are e_1 .. e_k
+//   4. certified iff e_k < (bound + ||q||^2) - slack, slack = err_scale (max||a||^2 + ||q||^2), 0 on exact pairs (comparison strict:
+//      a k-th neighbour that TIES an un-nominated row needs its index resolved)
+//   5. otherwise the query is listed for the exact scan.
+// Why a certified answer is the reference's: every un-nominated row has key >= bound (it lost against KL + 1 keys of its own half),
+// so its reference distance is >= bound + ||q||^2 - slack > e_k (|key + ||q||^2 - reference distance| <= slack for every row:
+// DESIGN.md "Certification").  k nominees are at most e_k away, every other row is strictly farther: the true top-k under
+// (distance, row) is a subset of the nominees, and all of those carry their reference distance, so their order -- ties included --
+// is the answer.  This is the split path's "second chance" rule (l2_finish_queries) made the only rule.
+// ------------------------------------------------------------------------------------------------
+template <int KL>
+__device__ __forceinline__ void knnk_finish(const KnnParams& P, const ImgDev* __restrict__ Ip, const ImgDev* __restrict__ Jp,
+                                            const TopK<KL>& st, uint32_t qt, uint32_t h, uint32_t c, float dpad)
+{
+    const uint32_t nJ = Jp->n, dim = Ip->dim, k = P.k;
+    const float maxnorm = __uint_as_float(Ip->max_norm_bits);
+    const float mI = __uint_as_float(Ip->max_abs_bits), mJ = __uint_as_float(Jp->max_abs_bits);
+    const uint32_t fl = Ip->not_integer | Jp->not_integer;              // bit 0: non-integer, bit 1: negative elements
+    const bool exact_pair = (fl & 1u) == 0u &&
+                            ((fl & 2u) ? dpad * (mI + mJ) * (mI + mJ) < 16777216.0f
+                                       : (2.0f * dpad * mI * mJ < 16777216.0f && dpad * mI * mI < 16777216.0f && dpad * mJ * mJ < 16777216.0f));
+    const uint32_t q = qt * 32u + c;
+    const bool valid = q < nJ;
+    const float nb = valid ? Jp->norms[q] : 0.0f;
+    float e[KL];
+#pragma unroll
+    for (int j = 0; j < KL; ++j) {
+        e[j] = R3DM_INF;
+        if (valid && st.i[j] != kNone)
+            e[j] = exact_pair ? st.d[j] + nb : exact_l2sq(Ip->rows + (size_t)st.i[j] * dim, Jp->rows + (size_t)q * dim, dim);
+    }
+    // rank of every own nominee among all 2 KL (rows are distinct: a row belongs to one half; empty entries are (inf, kNone) and
+    // rank behind every row)
+    float pe[KL]; uint32_t pi[KL];
+#pragma unroll
+    for (int j = 0; j < KL; ++j) { pe[j] = __shfl_xor(e[j], 32); pi[j] = __shfl_xor(st.i[j], 32); }
+    uint32_t rank[KL];
+#pragma unroll
+    for (int j = 0; j < KL; ++j) {
+        uint32_t r = 0;
+#pragma unroll
+        for (int m = 0; m < KL; ++m) {
+            if (m != j) r += knn_lex_less(e[m], st.i[m], e[j], st.i[j]) ? 1u : 0u;
+            r += knn_lex_less(pe[m], pi[m], e[j], st.i[j]) ? 1u : 0u;
+        }
+        rank[j] = r;
+    }
+    float mine = R3DM_INF;
+#pragma unroll
+    for (int j = 0; j < KL; ++j) if (rank[j] == k - 1u && st.i[j] != kNone) mine = e[j];
+    const float ek = fminf(mine, __shfl_xor(mine, 32));
+    const float bound = fminf(st.d[KL], __shfl_xor(st.d[KL], 32));
+    const float slack = exact_pair ? 0.0f : P.err_scale * (maxnorm + nb);
+    const bool certified = ek < (bound + nb) - slack;         // (evaluated identically by both lane halves)
+    if (!valid) return;
+    if (certified) {
+#pragma unroll
+        for (int j = 0; j < KL; ++j)
+            if (rank[j] < k && st.i[j] != kNone) {
+                P.out_idx[(size_t)q * k + rank[j]] = (int32_t)st.i[j];
+                P.out_dist[(size_t)q * k + rank[j]] = e[j];
+            }
+    } else if (h == 0) {                                      // lane half 0 lists the query (fb_q holds n_query entries: no overflow)
+        P.fb_q[atomicAdd(P.fb_cnt, 1u)] = q;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The nominator.  One workgroup = 4 waves, each wave one query tile (32 queries, pre-scaled by -2) in registers as the MFMA B
+// fragments; every 32-row dataset tile streams through as the A fragment from the fragment-order image (raw_buffer_load_b128, PF-deep
+// rolling window).  C is initialised to ||a||^2, so the accumulator holds key = ||a||^2 - 2 a.q; lane (h, c) owns query column c and
+// the 16 rows {(r & 3) + 8 (r >> 2) + 4 h} of a tile.  Ping-pong accumulators: the list updates of tile t - 1 issue in the shadow of
+// tile t's MFMAs.  No LDS, no barriers.  One query tile per wave (NJ = 1): the K-list of a query tile costs 2 KL + 1 registers where
+// Top2 costs 5, and the 2-NN kernel at NJ = 2 already sits near 256.
+// ------------------------------------------------------------------------------------------------
+template <int G, int PF, int KL>
+__global__ __launch_bounds__(256, 2)
+void l2_knnk_mfma_kernel(const KnnParams P)
+{
+    static_assert(G % PF == 0, "prefetch window must divide the group count");
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t h = lane >> 5, c = lane & 31u;
+    const ImgDev* __restrict__ Ip = P.imgs + P.sI;
+    const ImgDev* __restrict__ Jp = P.imgs + P.sJ;
+    const uint32_t ntI = Ip->n_tiles, ntJ = Jp->n_tiles;
+    const uint32_t qt = blockIdx.x * 4u + wave;
+    if (qt >= ntJ) return;                            // wave-uniform; no barriers in this kernel
+
+    f32x4 bq[G];
+    {
+        const gf4p src = (gf4p)Jp->tiled + (size_t)qt * (G * 64) + lane;
+#pragma unroll
+        for (int g = 0; g < G; ++g) bq[g] = src[g * 64] * -2.0f;
+    }
+    TopK<KL> st;
+    topk_init(st);
+
+    // dataset stream: float4 index = (t G + g) 64 + lane; norms of tile t, quad qd: float4 index 8 t + 2 qd + h
+    const gf4p abase = (gf4p)Ip->tiled;
+    const gf4p nbase = (gf4p)Ip->norms;
+    f32x4 abuf[PF];
+#pragma unroll
+    for (int s = 0; s < PF; ++s) abuf[s] = abase[s * 64 + lane];
+    f32x4 nrm[4];
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) nrm[qd] = nbase[2 * qd + h];
+    f32x16 accA, accB;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) accB[r] = R3DM_INF;          // "tile -1": keys that never enter a list
+    // descriptors from wave-uniform values only (readfirstlane) so no waterfall loop is emitted
+    const uint64_t pa = (uint64_t)Ip->tiled, pn = (uint64_t)Ip->norms;
+    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
+        0, 0x7FFFFFFF, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pn >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pn)),
+        0, 0x7FFFFFFF, 0x00020000);
+    const uint32_t voffA = lane * 16u, voffN = h * 16u;
+    const uint32_t tileB = (uint32_t)G * 1024u;                // bytes per tile (the launcher keeps n_tiles x tileB below 2^31)
+    const uint32_t hb = 4u * h;
+    uint32_t t = 0;
+    for (; t + 1 < ntI; t += 2) {
+        knnk_tile_step<G, PF, KL>(ra, rn, voffA, voffN, t * tileB + PF * 1024u, (t + 1) * 128u, abuf, nrm, bq, accA, accB, st, (t - 1) * 32u + hb);
+        knnk_tile_step<G, PF, KL>(ra, rn, voffA, voffN, (t + 1) * tileB + PF * 1024u, (t + 2) * 128u, abuf, nrm, bq, accB, accA, st, t * 32u + hb);
+    }
+    if (t < ntI) {
+        knnk_tile_step<G, PF, KL>(ra, rn, voffA, voffN, t * tileB + PF * 1024u, (t + 1) * 128u, abuf, nrm, bq, accA, accB, st, (t - 1) * 32u + hb);
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (__builtin_amdgcn_ballot_w64(accA[r] < st.d[KL]) != 0ull) topk_push(st, accA[r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+    } else {
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+            if (__builtin_amdgcn_ballot_w64(accB[r] < st.d[KL]) != 0ull) topk_push(st, accB[r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+    }
+    knnk_finish<KL>(P, Ip, Jp, st, qt, h, c, (float)(G * 8));
+}
+
+template <int G, int PF>
+static hipError_t launch_knnk_g(hipStream_t st, const KnnParams& P, uint32_t grid)
+{
+    if (P.k <= 4) hipLaunchKernelGGL((l2_knnk_mfma_kernel<G, PF, 4>), dim3(grid), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((l2_knnk_mfma_kernel<G, PF, 8>), dim3(grid), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+// hipErrorInvalidValue: no nominator for this launch (G without a tensor kernel, or a dataset whose tiles pass the 2^31-byte reach
+// of the buffer offsets): the caller runs the exact scan over every query
+hipError_t launch_l2_knnk(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query)
+{
+    if (P.k < 1 || P.k > R3DM_KNN_MAX) return hipErrorInvalidValue;
+    if ((uint64_t)n_tiles_dataset * G * 1024ull + 2ull * kSlackBytes >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    const uint32_t grid = (n_tiles_query + 3u) / 4u;
+    if (grid == 0) return hipSuccess;
+    switch (G) {
+        case 8:  return launch_knnk_g<8, 4>(st, P, grid);
+        case 16: return launch_knnk_g<16, 4>(st, P, grid);
+        case 18: return launch_knnk_g<18, 3>(st, P, grid);
+        case 32: return launch_knnk_g<32, 4>(st, P, grid);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The exact K scan: one workgroup per query, the reference arithmetic over every dataset row.  Thread t keeps the K-list of its rows
+// t, t + 256, ... under (distance, row) -- its rows ascend, so a strict `<` keeps the lowest row of equal distances first -- and an
+// LDS tree merges the 256 sorted lists.  Serves the uncertified queries of the nominator (from_list), descriptor lengths without a
+// tensor kernel, and through exact_l2sq any length that is no multiple of 4, scalar tail included.
+// ------------------------------------------------------------------------------------------------
+template <int KL>
+__global__ __launch_bounds__(256)
+void l2_exact_knn_items_kernel(const KnnParams P, uint32_t count, int from_list)
+{
+    __shared__ float sd[KL * 256];
+    __shared__ uint32_t si[KL * 256];
+    const ImgDev* __restrict__ Ip = P.imgs + P.sI;
+    const ImgDev* __restrict__ Jp = P.imgs + P.sJ;
+    const uint32_t dim = Ip->dim, nI = Ip->n, k = P.k, tid = threadIdx.x;
+    for (uint32_t it = blockIdx.x; it < count; it += gridDim.x) {
+        const uint32_t q = from_list ? P.fb_q[it] : it;
+        if (q >= Jp->n) continue;                                 // block-uniform
+        const float* qv = Jp->rows + (size_t)q * dim;
+        float kd[KL]; uint32_t ki[KL];
+#pragma unroll
+        for (int j = 0; j < KL; ++j) { kd[j] = R3DM_INF; ki[j] = kNone; }
+        for (uint32_t r = tid; r < nI; r += 256) {
+            const float d = exact_l2sq(Ip->rows + (size_t)r * dim, qv, dim);
+            if (d < kd[KL - 1]) {
+                bool c[KL];
+#pragma unroll
+                for (int j = 0; j < KL; ++j) c[j] = d < kd[j];
+#pragma unroll
+                for (int j = KL - 1; j >= 1; --j) {
+                    kd[j] = c[j - 1] ? kd[j - 1] : (c[j] ? d : kd[j]);
+                    ki[j] = c[j - 1] ? ki[j - 1] : (c[j] ? r : ki[j]);
+                }
+                kd[0] = c[0] ? d : kd[0];
+                ki[0] = c[0] ? r : ki[0];
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < KL; ++j) { sd[j * 256 + tid] = kd[j]; si[j * 256 + tid] = ki[j]; }
+        r3dm_syncthreads();
+        for (uint32_t s = 128; s > 0; s >>= 1) {
+            if (tid < s) {
+                // merge the sorted lists of slots tid and tid + s into slot tid (no other thread reads or writes slot tid in this stage)
+                uint32_t pa = 0, pb = 0;
+                float rd[KL]; uint32_t ri[KL];
+#pragma unroll
+                for (int j = 0; j < KL; ++j) {                    // pa + pb = j <= KL - 1: both cursors stay inside their lists
+                    const float a = sd[pa * 256 + tid], b = sd[pb * 256 + tid + s];
+                    const uint32_t x = si[pa * 256 + tid], y = si[pb * 256 + tid + s];
+                    const bool tb = knn_lex_less(b, y, a, x);
+                    rd[j] = tb ? b : a; ri[j] = tb ? y : x;
+                    pa += tb ? 0u : 1u; pb += tb ? 1u : 0u;
+                }
+#pragma unroll
+                for (int j = 0; j < KL; ++j) { sd[j * 256 + tid] = rd[j]; si[j * 256 + tid] = ri[j]; }
+            }
+            r3dm_syncthreads();
+        }
+        if (tid < k) {
+            P.out_idx[(size_t)q * k + tid] = (int32_t)si[tid * 256];
+            P.out_dist[(size_t)q * k + tid] = sd[tid * 256];
+        }
+        r3dm_syncthreads();
+    }
+}
+
+hipError_t launch_l2_exact_knn_items(hipStream_t st, const KnnParams& P, uint32_t count, int from_list)
+{
+    if (count == 0) return hipSuccess;
+    if (P.k < 1 || P.k > R3DM_KNN_MAX) return hipErrorInvalidValue;
+    const uint32_t grid = count < 16384u ? count : 16384u;
+    if (P.k <= 4) hipLaunchKernelGGL((l2_exact_knn_items_kernel<4>), dim3(grid), dim3(256), 0, st, P, count, from_list);
+    else hipLaunchKernelGGL((l2_exact_knn_items_kernel<8>), dim3(grid), dim3(256), 0, st, P, count, from_list);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// Hamming k-NN (binary rows of 29..32 / 61..64 bytes in W = 8 / 16 words): the popcount kernel of hamming_knn2_kernel -- each lane
+// owns QL query rows in registers, the dataset rows arrive wave-uniformly through the scalar cache -- with a K-list per query on packed
+// keys (distance << 22 | row): the unsigned order of the keys IS the (distance, row) order, so the lists are exact and there is
+// neither a bound nor a certificate.  A lane owns whole queries here (no lane halves to merge).
+// ------------------------------------------------------------------------------------------------
+typedef const __attribute__((address_space(4))) uint32_t* knn_cu32p;   // constant address space -> SMEM loads
+
+template <int W, int KL, int QL>
+__global__ __launch_bounds__(256)
+void hamming_knnk_kernel(const KnnParams P)
+{
+    const ImgDev* __restrict__ Ip = P.imgs + P.sI;
+    const ImgDev* __restrict__ Jp = P.imgs + P.sJ;
+    const uint32_t nI = Ip->n, nJ = Jp->n, k = P.k;
+    const uint32_t q0 = (blockIdx.x * 256u + threadIdx.x) * QL;
+    const uint32_t wave_q0 = (blockIdx.x * 256u + (threadIdx.x & ~63u)) * QL;
+    if (wave_q0 >= nJ) return;
+
+    uint32_t qw[QL][W];
+#pragma unroll
+    for (int u = 0; u < QL; ++u) {
+        uint32_t q = q0 + u; if (q >= nJ) q = nJ - 1;
+        const uint32_t* src = Jp->bin + (size_t)q * W;
+#pragma unroll
+        for (int w = 0; w < W; ++w) qw[u][w] = src[w];
+    }
+    uint32_t kl[QL][KL];
+#pragma unroll
+    for (int u = 0; u < QL; ++u)
+#pragma unroll
+        for (int j = 0; j < KL; ++j) kl[u][j] = 0xFFFFFFFFu;
+
+    const knn_cu32p base = (knn_cu32p)(uintptr_t)Ip->bin;
+    for (uint32_t r = 0; r < nI; ++r) {
+        const knn_cu32p row = base + (size_t)r * W;
+        uint32_t a[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) a[w] = row[w];
+#pragma unroll
+        for (int u = 0; u < QL; ++u) {
+            uint32_t d = 0;
+#pragma unroll
+            for (int w = 0; w < W; ++w) d += (uint32_t)__builtin_popcount(qw[u][w] ^ a[w]);
+            const uint32_t key = (d << 22) | r;
+            if (__builtin_amdgcn_ballot_w64(key < kl[u][KL - 1]) != 0ull) {
+#pragma unroll
+                for (int j = KL - 1; j >= 1; --j) {               // min(kl[j], max(kl[j - 1], key))  (v_med3_u32)
+                    const uint32_t hi = kl[u][j - 1] > key ? kl[u][j - 1] : key;
+                    kl[u][j] = kl[u][j] < hi ? kl[u][j] : hi;
+                }
+                kl[u][0] = kl[u][0] < key ? kl[u][0] : key;
+            }
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < QL; ++u) {
+        const uint32_t q = q0 + u;
+        if (q >= nJ) continue;
+#pragma unroll
+        for (int j = 0; j < KL; ++j)
+            if ((uint32_t)j < k) {
+                P.out_idx[(size_t)q * k + j] = (int32_t)(kl[u][j] & 0x3FFFFFu);
+                P.out_dist[(size_t)q * k + j] = (float)(kl[u][j] >> 22);
+            }
+    }
+}
+
+template <int W>
+static hipError_t launch_hamming_knnk_w(hipStream_t st, const KnnParams& P, uint32_t n_query)
+{
+    constexpr int QL = 2;
+    const uint32_t grid = (n_query + 256u * QL - 1u) / (256u * QL);
+    if (grid == 0) return hipSuccess;
+    if (P.k <= 4) hipLaunchKernelGGL((hamming_knnk_kernel<W, 4, QL>), dim3(grid), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL((hamming_knnk_kernel<W, 8, QL>), dim3(grid), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+hipError_t launch_hamming_knnk(hipStream_t st, const KnnParams& P, uint32_t words, uint32_t n_query)
+{
+    if (P.k < 1 || P.k > R3DM_KNN_MAX) return hipErrorInvalidValue;
+    switch (words) {
+        case 8:  return launch_hamming_knnk_w<8>(st, P, n_query);
+        case 16: return launch_hamming_knnk_w<16>(st, P, n_query);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace r3dm

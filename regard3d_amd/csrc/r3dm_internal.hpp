@@ -523,4 +523,21 @@ hipError_t launch_liop(hipStream_t st, const LiopTables& T, const float* patches
 hipError_t launch_liop_fused(hipStream_t st, const LiopTables& T, const float* image, int w, int h, const float* M6, const float* kern,
                              const uint32_t* img_of, uint32_t n, float* desc, uint32_t* n_tie_patches, uint32_t* tie_list);
 
+// ---- exhaustive k-NN of one (dataset, query) pair, k = 1 .. R3DM_KNN_MAX (kernels_match_knn.hip; r3dm_knn / r3dm_index_knn)
+struct KnnParams {
+    const ImgDev* imgs;
+    uint32_t      sI, sJ;         // slots of the dataset and of the query set
+    uint32_t      k;              // neighbours per query, 1 .. R3DM_KNN_MAX
+    float         err_scale;      // certification slack factor of the f32 tiles: 4.25 Dpad 2^-24 (as MatchParams::err_scale)
+    int32_t*      out_idx;        // [n_query][k] dataset rows, ascending under (distance, row)
+    float*        out_dist;       // [n_query][k]
+    uint32_t*     fb_q;           // [n_query] queries the nominator could not certify
+    uint32_t*     fb_cnt;         // [1] how many (zeroed by the host)
+};
+// hipErrorInvalidValue: no nominator for this (G, dataset size); the caller scans every query exactly
+hipError_t launch_l2_knnk(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query);
+// from_list != 0: the `count` queries of fb_q; else queries 0 .. count - 1
+hipError_t launch_l2_exact_knn_items(hipStream_t st, const KnnParams& P, uint32_t count, int from_list);
+hipError_t launch_hamming_knnk(hipStream_t st, const KnnParams& P, uint32_t words, uint32_t n_query);
+
 }  // namespace r3dm
