@@ -278,11 +278,26 @@ void r3dm_index_destroy(r3dm_index* index);
  * R3DM_ERR_INVALID: k < 1, k > R3DM_KNN_MAX, n_query < 1, n_dataset < k (the plugins' "NN > rows" rule), null pointers (a null
  * context is refused before any GPU is touched).  R3DM_ERR_UNSUPPORTED: the BIN byte-length rule of r3dm_knn2.
  * k <= 2 with n_dataset >= 2 runs the 2-NN path of r3dm_knn2 (bit-identical to it by construction; k = 1 is its first column).
- * Everything else -- k >= 3, and k = 1 on a one-row dataset -- runs on k-list kernels of its own: always the f32 tiles (F32 / U8)
- * or the popcount kernel (BIN).  r3dm_set_integer_mfma / _split_mfma / _hamming_mfma are IGNORED there (those nominators keep
- * 2-lists), and none of their counters moves.  Lengths without a tensor kernel (> 256 elements) are scanned exactly, as in
- * r3dm_match_pairs.  r3dm_stats.n_queries and .n_exact_fallback (queries answered by the exact scan) describe the call. */
+ * Everything else -- k >= 3, and k = 1 on a one-row dataset -- runs on k-list kernels of its own: by default the f32 tiles (F32 / U8)
+ * or the popcount kernel (BIN).
+ *   IGNORED there: r3dm_set_integer_mfma / _split_mfma / _hamming_mfma (those nominators keep 2-lists).  None of their counters
+ *     (n_integer_mfma, n_split_mfma, n_hamming_mfma, n_counts_mfma) moves on such a call, whatever any switch says.
+ *   NOT ignored: r3dm_set_knn_narrow_tiles, the k-list kernels' own switch (below).
+ * Lengths without a tensor kernel (> 256 elements) are scanned exactly, as in r3dm_match_pairs.  r3dm_stats.n_queries and
+ * .n_exact_fallback (queries answered by the exact scan) describe the call. */
 #define R3DM_KNN_MAX 8
+/* Opt-in (default off), same results bit for bit: while on, a call that runs on the k-list kernels (k >= 3; k = 1 on a one-row
+ * dataset) picks its nominator from the two views' statistics, under the conditions the 2-NN switches use:
+ *   - both views integer-valued with magnitudes <= 256 and every partial sum below 2^24 (SIFT bins, any unsigned char rows), padded
+ *     length 64, 128 or 256: the bf16 tiles of r3dm_set_integer_mfma with exact k-lists -- nothing is certified or scanned
+ *     (r3dm_stats.n_knn_integer_tiles counts the launch; .n_exact_fallback is 0);
+ *   - otherwise both views finite and non-zero, scales within reach of one another, not both integer-valued: the split-f16 planes of
+ *     r3dm_set_split_mfma (r3dm_stats.n_knn_split_tiles); uncertified queries go to the exact scan as on the f32 tiles;
+ *   - anything else (integer views beyond those bounds, 144-element integer views, lengths without a tensor kernel, BIN rows, a
+ *     dataset whose tiles pass 2 GiB) runs exactly what it runs with the switch off, and neither counter moves.
+ * The layouts are staged on first use; on an r3dm_index that is once per index, under its lock, whichever context asks first.
+ * k <= 2 (the 2-NN path) does not consult this switch. */
+int r3dm_set_knn_narrow_tiles(r3dm_ctx* ctx, int enable);
 int r3dm_knn(r3dm_ctx* ctx, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
              uint32_t dim, r3dm_dtype dtype, uint32_t k, int32_t* out_idx, float* out_dist);
 /* same mounting, locking and "any context of the index's device" rules as r3dm_index_knn2 */
@@ -699,6 +714,9 @@ typedef struct {
                                        * conductivity out, 8 bytes per pixel and FED step); detect_algorithmic_bytes is the as-structured count            */
     uint64_t n_filter_workgroups;  /* workgroups of the last AC-RANSAC call (all its filters): pool workers of the cooperative kernel + one per short pair */
     uint64_t n_filter_coop_pairs;  /* ... (pair, filter) items that ran on the cooperative kernel                                                          */
+    /* r3dm_knn / r3dm_index_knn with r3dm_set_knn_narrow_tiles on */
+    uint64_t n_knn_integer_tiles;  /* launches of the K-list nominator on the bf16 tiles (integer-valued rows: exact lists, nothing certified or scanned)  */
+    uint64_t n_knn_split_tiles;    /* launches of the K-list nominator on the split-f16 planes (real-valued rows)                                          */
 } r3dm_stats;
 int r3dm_get_stats(const r3dm_ctx* ctx, r3dm_stats* out);
 

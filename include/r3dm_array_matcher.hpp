@@ -76,6 +76,8 @@ public:
     void setIntegerFastPath(bool on) { integer_fast_path_ = on; }
     // not part of the ArrayMatcher interface: forwards r3dm_set_split_mfma (same results, real-valued rows)
     void setSplitFastPath(bool on) { split_fast_path_ = on; }
+    // not part of the ArrayMatcher interface: forwards r3dm_set_knn_narrow_tiles (same results; NN >= 3 on the bf16 tiles / split planes)
+    void setKnnNarrowTiles(bool on) { knn_narrow_tiles_ = on; }
     // copies + re-layouts made on this adapter's device by all adapters of the process (test / diagnostics hook)
     uint64_t viewsStaged() const { return pool_.viewsStaged(); }
     int contextsInUse() const { return pool_.created(); }
@@ -127,7 +129,8 @@ public:
     }
 
 private:
-    // 3 <= NN <= R3DM_KNN_MAX: r3dm_index_knn.  The opt-in fast paths keep 2-lists and are not consulted (include/r3dm.h).
+    // 3 <= NN <= R3DM_KNN_MAX: r3dm_index_knn.  The 2-NN fast paths keep 2-lists and are not consulted; setKnnNarrowTiles is this
+    // path's own switch (include/r3dm.h).
     bool SearchK(const Scalar* query, int nbQuery, IndMatches* pvec_indices, std::vector<DistanceType>* pvec_distances, size_t NN)
     {
         if (!index_ || !query || nbQuery < 1 || NN > R3DM_KNN_MAX || NN > static_cast<size_t>(nbRows_)) return false;
@@ -136,6 +139,7 @@ private:
         {
             detail::ContextLease lease(pool_);                 // one stream + scratch per concurrent search
             if (!lease.ctx) return false;
+            (void)r3dm_set_knn_narrow_tiles(lease.ctx, knn_narrow_tiles_ ? 1 : 0);
             if (r3dm_index_knn(lease.ctx, index_, query, static_cast<uint32_t>(nbQuery), static_cast<uint32_t>(NN), idx.data(), dist.data()) != R3DM_OK)
                 return false;
         }
@@ -152,7 +156,7 @@ private:
     detail::ContextPool& pool_;
     r3dm_index* index_ = nullptr;
     int nbRows_ = 0, dimension_ = 0;
-    bool integer_fast_path_ = false, split_fast_path_ = false;
+    bool integer_fast_path_ = false, split_fast_path_ = false, knn_narrow_tiles_ = false;
 };
 
 }  // namespace r3d_amd

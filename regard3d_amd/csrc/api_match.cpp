@@ -496,15 +496,21 @@ extern "C" int r3dm_index_knn2(r3dm_ctx* c, const r3dm_index* ix, const void* qu
 // k neighbours, k = 1 .. R3DM_KNN_MAX (kernels_match_knn.hip): ArrayMatcher::SearchNeighbours with any NN
 // (/root/reference/src/utils/matcher_kgraph.h:205-251).  One (dataset, query) pair per call; k <= 2 is served by the 2-NN path above.
 // ------------------------------------------------------------------------------------------------
-// the k-list kernels over the views in slots sI (dataset) and sJ (queries): always the f32 tiles / the popcount kernel, whatever the
-// r3dm_set_*_mfma switches say (their nominators keep 2-lists)
+// the k-list kernels over the views in slots sI (dataset) and sJ (queries): the f32 tiles / the popcount kernel whatever the
+// r3dm_set_*_mfma switches say (their nominators keep 2-lists).  r3dm_set_knn_narrow_tiles is this path's own switch: while it is on,
+// the pair is planned like a one-job 2-NN batch with the integer and split switches on (plan_batch: the conditions under which the
+// bf16 tiles are exact and the split planes usable are stated there and nowhere else) and runs on the K-list kernel of the tiles the
+// plan names (kernels_match_knn16.hip).  A launcher that has no kernel for the launch leaves the pair on the f32 K-list kernel.
 static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int32_t* out_idx_host, float* out_dist_host)
 {
     { const int rcs = sync_view_stats(c); if (rcs != R3DM_OK) return rcs; }
     const r3dm_dtype dtype = c->imgs[sI]->dtype;
     const uint32_t nI = c->imgs[sI]->n, nq = c->imgs[sJ]->n, G = c->imgs[sI]->G, dim = c->imgs[sI]->dim, words = c->imgs[sI]->words;
-    // the nominees are re-scored on the row-major rows, and the exact scan reads them
-    if (dtype != R3DM_BIN) { const int rcl = ensure_layouts(c, {sI, sJ}, kLayRows); if (rcl != R3DM_OK) return rcl; }
+    const bool narrow = c->knn_narrow_tiles;
+    const BatchPlan plan = plan_batch(c->imgs, {PairJob{0, 1, sI, sJ}}, PathSwitches{narrow, narrow, false, false});
+    // the nominees are re-scored on the row-major rows, and the exact scan reads them (on the integer tiles nothing is re-scored, but
+    // the in-kernel re-check of the exact-pair condition still has the scan behind it)
+    if (dtype != R3DM_BIN) { const int rcl = ensure_layouts(c, {sI, sJ}, kLayRows | plan.layouts); if (rcl != R3DM_OK) return rcl; }
     const size_t out_bytes = (size_t)nq * k * 4;
     R3DM_HIP(c, c->d_knn_idx.ensure(out_bytes));
     R3DM_HIP(c, c->d_knn_dist.ensure(out_bytes));
@@ -527,7 +533,22 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
         R3DM_HIP(c, launch_hamming_knnk(c->stream, kp, words, nq));
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
     } else {
-        const hipError_t e = has_tensor_kernel(G) ? launch_l2_knnk(c->stream, kp, G, c->imgs[sI]->n_tiles, c->imgs[sJ]->n_tiles) : hipErrorInvalidValue;
+        const uint32_t ntI = c->imgs[sI]->n_tiles, ntJ = c->imgs[sJ]->n_tiles;
+        hipError_t e = hipErrorInvalidValue;
+        if (plan.path == BatchPath::kIntegerTiles) {
+            e = launch_l2_knnk_int(c->stream, kp, G, ntI, ntJ);
+            if (e == hipSuccess) c->stats.n_knn_integer_tiles += 1;
+        } else if (plan.path == BatchPath::kSplitPlanes) {
+            KnnParams ks = kp;
+            ks.err_scale = (3.0f * (float)(G * 8) + 36.0f) * 2.3841858e-07f;      // the split formula of run_match_batch
+            e = launch_l2_knnk_split(c->stream, ks, G, ntI, ntJ);
+            if (e == hipSuccess) c->stats.n_knn_split_tiles += 1;
+        }
+        if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+            // no narrow-tile kernel for this launch (or none asked for): the f32 K-list kernel
+            (void)hipGetLastError();
+            e = has_tensor_kernel(G) ? launch_l2_knnk(c->stream, kp, G, ntI, ntJ) : hipErrorInvalidValue;
+        }
         if (e == hipErrorInvalidValue) {
             // descriptor length without a tensor kernel (or a dataset beyond the nominator's reach): exact scan of every query
             (void)hipGetLastError();
@@ -562,10 +583,11 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
     return R3DM_OK;
 }
 
-// the counters a k-NN call reports: its queries, how many the exact scan answered -- and the opt-in paths' counters, which hold 0
-// after a call on the k-list kernels; ms_match_kernels holds the HIP-event time of the call's first kernel (tools/knn_perf.py)
+// the counters a k-NN call reports: its queries, how many the exact scan answered, which narrow tiles its K-list kernel ran on
+// (r3dm_set_knn_narrow_tiles) -- and the 2-NN opt-in paths' counters, which hold 0 after a call on the k-list kernels;
+// ms_match_kernels holds the HIP-event time of the call's first kernel (tools/knn_perf.py)
 #define R3DM_KNN_COUNTERS {&r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma, \
-                           &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries}
+                           &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries, &r3dm_stats::n_knn_integer_tiles, &r3dm_stats::n_knn_split_tiles}
 
 // first column of a 2-NN result
 static void first_column(const std::vector<int32_t>& i2, const std::vector<float>& d2, uint32_t n_query, int32_t* out_idx, float* out_dist)

@@ -3,59 +3,17 @@
 // matcher_hnsw.h:138-173).  The 2-NN kernels, Top2 and the ratio test are untouched; this unit shares only the header's metric and
 // buffer load with them.
 //   l2_knnk_mfma_kernel<G, PF, KL>     the nominator: the f32 MFMA tile stream of l2_knn2_mfma_kernel with K-lists per lane half
-//   knnk_finish<KL>                    its tail: re-score the nominees in the reference arithmetic, order, certify the k-th
+//   (TopK<KL>, knnk_finish<KL>         its lists and its tail -- re-score the nominees in the reference arithmetic, order, certify
+//                                      the k-th -- live in kernels_match_knn_lists.hpp, shared with kernels_match_knn16.hip)
 //   l2_exact_knn_items_kernel<KL>      the exact scan behind it (uncertified queries; lengths without a tensor kernel)
 //   hamming_knnk_kernel<W, KL, QL>     binary rows: xor + popcount with exact (distance, row) K-lists per lane
 // KL is the list depth a kernel is built with: 4 for k <= 4, 8 above; k itself is a run-time value (k <= KL).
 //
 // Arithmetic contract as everywhere (kernels_match_common.hpp): the f32 4-way unrolled sum of squared differences without FMA, equal
 // distances -> lowest dataset row.  This file is compiled with -ffp-contract=off; fused operations are spelled fmaf() / MFMA.
-#include "kernels_match_common.hpp"
+#include "kernels_match_knn_lists.hpp"
 
 namespace r3dm {
-
-__device__ __forceinline__ bool knn_lex_less(float da, uint32_t ia, float db, uint32_t ib)
-{
-    return da < db || (da == db && ia < ib);
-}
-
-// ------------------------------------------------------------------------------------------------
-// K-list of one query column held by one lane HALF (16 of a tile's 32 rows): the KL smallest keys with their rows, ascending, and
-// the (KL + 1)-th smallest key d[KL] -- the smallest key this half did NOT nominate, its bound.  The depth is KL per half, not in
-// total: all k neighbours of a query may sit in rows of one half.
-// ------------------------------------------------------------------------------------------------
-template <int KL>
-struct TopK {
-    float d[KL + 1];
-    uint32_t i[KL];
-};
-
-template <int KL>
-__device__ __forceinline__ void topk_init(TopK<KL>& s)
-{
-#pragma unroll
-    for (int j = 0; j <= KL; ++j) s.d[j] = R3DM_INF;
-#pragma unroll
-    for (int j = 0; j < KL; ++j) s.i[j] = kNone;
-}
-
-// sorted insert, branch-free (v_med3 / v_cndmask): new d[j] = min(d[j], max(d[j - 1], key)).  Runs only behind a wave-wide test.
-template <int KL>
-__device__ __forceinline__ void topk_push(TopK<KL>& s, float key, uint32_t idx)
-{
-    bool c[KL];
-#pragma unroll
-    for (int j = 0; j < KL; ++j) c[j] = key < s.d[j];
-    s.d[KL] = __builtin_amdgcn_fmed3f(s.d[KL - 1], s.d[KL], key);
-#pragma unroll
-    for (int j = KL - 1; j >= 1; --j) {                 // downwards: d[j - 1], i[j - 1] are still the old ones
-        s.d[j] = __builtin_amdgcn_fmed3f(s.d[j - 1], s.d[j], key);
-        const uint32_t t = c[j] ? idx : s.i[j];
-        s.i[j] = c[j - 1] ? s.i[j - 1] : t;
-    }
-    s.d[0] = __builtin_amdgcn_fmed3f(-R3DM_INF, s.d[0], key);
-    s.i[0] = c[0] ? idx : s.i[0];
-}
 
 // One dataset tile (l2_tile_step of kernels_match.hip at NJ = 1, PIPE = 3): the MFMAs of tile t into `cur` while the VALU folds
 // the finished accumulator of tile t - 1 (`prev`) into the K-list.  Test-and-skip: a key changes the list only below the lane's
@@ -88,78 +46,6 @@ __device__ __forceinline__ void knnk_tile_step(__amdgpu_buffer_rsrc_t ra, __amdg
                     topk_push(st, prev[r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
         }
         __builtin_amdgcn_sched_barrier(0);                // keep each prefetch / epilogue slice in its own step
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// Finish and certificate of one query column (lanes c and c + 32 hold its two halves' lists).
-//   1. nominees = the union of both lists (up to 2 KL rows); bound = min of the two halves' (KL + 1)-th keys
-//   2. every nominee is re-scored with exact_l2sq on the row-major rows, KL per lane half (on an exact pair -- the integer proof of
-//      l2_finish_queries -- key + ||q||^2 IS that distance and nothing is read again)
-//   3. the nominees are ranked under (distance, row); the first k are e_1 .. e_k
-//   4. certified iff e_k < (bound + ||q||^2) - slack, slack = err_scale (max||a||^2 + ||q||^2), 0 on exact pairs (comparison strict:
-//      a k-th neighbour that TIES an un-nominated row needs its index resolved)
-//   5. otherwise the query is listed for the exact scan.
-// Why a certified answer is the reference's: every un-nominated row has key >= bound (it lost against KL + 1 keys of its own half),
-// so its reference distance is >= bound + ||q||^2 - slack > e_k (|key + ||q||^2 - reference distance| <= slack for every row:
-// DESIGN.md "Certification").  k nominees are at most e_k away, every other row is strictly farther: the true top-k under
-// (distance, row) is a subset of the nominees, and all of those carry their reference distance, so their order -- ties included --
-// is the answer.  This is the split path's "second chance" rule (l2_finish_queries) made the only rule.
-// ------------------------------------------------------------------------------------------------
-template <int KL>
-__device__ __forceinline__ void knnk_finish(const KnnParams& P, const ImgDev* __restrict__ Ip, const ImgDev* __restrict__ Jp,
-                                            const TopK<KL>& st, uint32_t qt, uint32_t h, uint32_t c, float dpad)
-{
-    const uint32_t nJ = Jp->n, dim = Ip->dim, k = P.k;
-    const float maxnorm = __uint_as_float(Ip->max_norm_bits);
-    const float mI = __uint_as_float(Ip->max_abs_bits), mJ = __uint_as_float(Jp->max_abs_bits);
-    const uint32_t fl = Ip->not_integer | Jp->not_integer;              // bit 0: non-integer, bit 1: negative elements
-    const bool exact_pair = (fl & 1u) == 0u &&
-                            ((fl & 2u) ? dpad * (mI + mJ) * (mI + mJ) < 16777216.0f
-                                       : (2.0f * dpad * mI * mJ < 16777216.0f && dpad * mI * mI < 16777216.0f && dpad * mJ * mJ < 16777216.0f));
-    const uint32_t q = qt * 32u + c;
-    const bool valid = q < nJ;
-    const float nb = valid ? Jp->norms[q] : 0.0f;
-    float e[KL];
-#pragma unroll
-    for (int j = 0; j < KL; ++j) {
-        e[j] = R3DM_INF;
-        if (valid && st.i[j] != kNone)
-            e[j] = exact_pair ? st.d[j] + nb : exact_l2sq(Ip->rows + (size_t)st.i[j] * dim, Jp->rows + (size_t)q * dim, dim);
-    }
-    // rank of every own nominee among all 2 KL (rows are distinct: a row belongs to one half; empty entries are (inf, kNone) and
-    // rank behind every row)
-    float pe[KL]; uint32_t pi[KL];
-#pragma unroll
-    for (int j = 0; j < KL; ++j) { pe[j] = __shfl_xor(e[j], 32); pi[j] = __shfl_xor(st.i[j], 32); }
-    uint32_t rank[KL];
-#pragma unroll
-    for (int j = 0; j < KL; ++j) {
-        uint32_t r = 0;
-#pragma unroll
-        for (int m = 0; m < KL; ++m) {
-            if (m != j) r += knn_lex_less(e[m], st.i[m], e[j], st.i[j]) ? 1u : 0u;
-            r += knn_lex_less(pe[m], pi[m], e[j], st.i[j]) ? 1u : 0u;
-        }
-        rank[j] = r;
-    }
-    float mine = R3DM_INF;
-#pragma unroll
-    for (int j = 0; j < KL; ++j) if (rank[j] == k - 1u && st.i[j] != kNone) mine = e[j];
-    const float ek = fminf(mine, __shfl_xor(mine, 32));
-    const float bound = fminf(st.d[KL], __shfl_xor(st.d[KL], 32));
-    const float slack = exact_pair ? 0.0f : P.err_scale * (maxnorm + nb);
-    const bool certified = ek < (bound + nb) - slack;         // (evaluated identically by both lane halves)
-    if (!valid) return;
-    if (certified) {
-#pragma unroll
-        for (int j = 0; j < KL; ++j)
-            if (rank[j] < k && st.i[j] != kNone) {
-                P.out_idx[(size_t)q * k + rank[j]] = (int32_t)st.i[j];
-                P.out_dist[(size_t)q * k + rank[j]] = e[j];
-            }
-    } else if (h == 0) {                                      // lane half 0 lists the query (fb_q holds n_query entries: no overflow)
-        P.fb_q[atomicAdd(P.fb_cnt, 1u)] = q;
     }
 }
 

@@ -528,7 +528,7 @@ struct KnnParams {
     const ImgDev* imgs;
     uint32_t      sI, sJ;         // slots of the dataset and of the query set
     uint32_t      k;              // neighbours per query, 1 .. R3DM_KNN_MAX
-    float         err_scale;      // certification slack factor of the f32 tiles: 4.25 Dpad 2^-24 (as MatchParams::err_scale)
+    float         err_scale;      // certification slack factor of the launch's tiles: 4.25 Dpad 2^-24 on the f32 tiles, (3 Dpad + 36) 2^-22 on the split planes (as MatchParams::err_scale)
     int32_t*      out_idx;        // [n_query][k] dataset rows, ascending under (distance, row)
     float*        out_dist;       // [n_query][k]
     uint32_t*     fb_q;           // [n_query] queries the nominator could not certify
@@ -539,5 +539,10 @@ hipError_t launch_l2_knnk(hipStream_t st, const KnnParams& P, uint32_t G, uint32
 // from_list != 0: the `count` queries of fb_q; else queries 0 .. count - 1
 hipError_t launch_l2_exact_knn_items(hipStream_t st, const KnnParams& P, uint32_t count, int from_list);
 hipError_t launch_hamming_knnk(hipStream_t st, const KnnParams& P, uint32_t words, uint32_t n_query);
+// the K-list nominators on the 16-bit tiles (kernels_match_knn16.hip; r3dm_set_knn_narrow_tiles).  hipErrorInvalidValue /
+// hipErrorNotSupported: no such kernel for this (G, dataset size) -- the caller keeps the f32 K-list kernel.  P.err_scale of the split
+// launch is the split planes' factor, (3 Dpad + 36) 2^-22
+hipError_t launch_l2_knnk_int(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query);
+hipError_t launch_l2_knnk_split(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query);
 
 }  // namespace r3dm

@@ -1,10 +1,16 @@
 """k-NN kernels against the 2-NN kernel on one pair of 8,192 x 8,192 rows:
-    python tools/knn_perf.py [out.txt]
-Data: D = 128 integer bins (C2-like), D = 128 real-valued, D = 144 LIOP (tests/golden/liop_match_ref.npz), 64-byte binary rows
-(C3-like).  Per data set, in one process and one context: the 2-NN tile kernel (r3dm_match_pairs on the registered pair: the kernel
-r3dm_knn2 runs, timed by the library's HIP events around it) and r3dm_knn at k = 3, 4, 8 (HIP events around its first kernel: the
-nominator / the popcount kernel).  Warm-up calls first, then the median of REPS; the k-kernel's share of the f32 MFMA peak counts the
-padded tile products (2 nI nJ Dpad) against 157.3 TFLOP/s; exact = share of the queries answered by the exact scan."""
+    python tools/knn_perf.py [out.txt] [--dev]
+Data: D = 128 integer bins as f32 rows and as unsigned char rows (C2-like), D = 128 real-valued, D = 144 LIOP
+(tests/golden/liop_match_ref.npz), 64-byte binary rows (C3-like).  Per data set, in one process and one context: the 2-NN tile kernel
+(r3dm_match_pairs on the registered pair: the kernel r3dm_knn2 runs, timed by the library's HIP events around it) and r3dm_knn at
+k = 3, 4, 8 (HIP events around its first kernel: the nominator / the popcount kernel).  Warm-up calls first, then the median of REPS
+with the smallest and largest repetition beside it; the k-kernel's share of the f32 MFMA peak counts the padded tile products
+(2 nI nJ Dpad) against 157.3 TFLOP/s; exact = share of the queries answered by the exact scan.
+
+Narrow tiles (r3dm_set_knn_narrow_tiles): for every L2 data set and k the same call with the switch on, ALTERNATED with the switch-off
+call in the same loop (off, on, off, on ...), so both see the same clocks and cache state.  The ratio is f32 K-list kernel / narrow
+kernel on the medians; "beyond spread" says whether the narrow median lies below the f32 median by more than the f32 line's own
+max - min.  --dev: the developer library, plus the integer kernel at one query tile per wave (R3DM_KNN_INT_NJ1) beside the product's."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -19,7 +25,9 @@ N = 8192
 def datasets():
     rng = np.random.default_rng(8192)
     sc = synth.make_scene(2, N, "sift", seed=3003)
-    yield "D=128 integer-valued (SIFT bins)", np.ascontiguousarray(sc.descs[0]), np.ascontiguousarray(sc.descs[1]), False
+    yield "D=128 integer-valued (SIFT bins), f32 rows", np.ascontiguousarray(sc.descs[0]), np.ascontiguousarray(sc.descs[1]), False
+    yield ("D=128 integer-valued (SIFT bins), u8 rows", np.ascontiguousarray(sc.descs[0]).astype(np.uint8),
+           np.ascontiguousarray(sc.descs[1]).astype(np.uint8), False)
     yield "D=128 real-valued", rng.standard_normal((N, 128)).astype(np.float32), rng.standard_normal((N, 128)).astype(np.float32), False
     z = np.load(os.path.join(ROOT, "tests", "golden", "liop_match_ref.npz"))
     yield ("D=144 LIOP fixture", (z["hist0"].astype(np.float32) / z["norm0"][:, None]).astype(np.float32),
@@ -34,9 +42,26 @@ def median_of(fn):
     return float(np.median([fn() for _ in range(REPS)]))
 
 
+def alternated(fns):
+    """every function WARM times, then REPS rounds of (f0, f1, ...): -> per function (median, min, max)"""
+    for _ in range(WARM):
+        for f in fns:
+            f()
+    t = [[] for _ in fns]
+    for _ in range(REPS):
+        for i, f in enumerate(fns):
+            t[i].append(f())
+    return [(float(np.median(x)), float(min(x)), float(max(x))) for x in t]
+
+
 def main():
+    args = [x for x in sys.argv[1:] if not x.startswith("--")]
+    dev = "--dev" in sys.argv
+    if dev:
+        api.use_developer_library()
     c = api.Context(0)
-    lines = ["data | call | kernel ms (median of %d) | vs 2-NN | share of f32 MFMA peak | exact-scan share" % REPS]
+    lines = ["data | call | kernel ms (median of %d) [min .. max] | vs 2-NN | share of f32 MFMA peak | exact-scan share" % REPS]
+    narrow = ["data | k | tiles | f32 K-list ms [min .. max] | narrow ms [min .. max] | f32 / narrow | beyond the f32 spread | exact-scan share f32 / narrow"]
     for name, a, b, binary in datasets():
         c.clear_images()
         c.set_image(0, a, None, 4000, 3000, binary=binary); c.set_image(1, b, None, 4000, 3000, binary=binary)
@@ -51,15 +76,35 @@ def main():
         share = lambda ms: "-" if binary else "%.1f %%" % (100.0 * 2.0 * a.shape[0] * b.shape[0] * dpad / (ms * 1e-3) / PEAK_F32_MFMA)
         lines.append(f"{name} | 2-NN tile kernel (r3dm_match_pairs) | {t2:.3f} | 1.00 | {share(t2)} | {state['fb']:.4f}")
         for k in (3, 4, 8):
-            def kn():
-                c.knn(a, b, k, binary=binary); s = c.stats(); state["fb"] = s.n_exact_fallback / b.shape[0]; return s.ms_match_kernels
-            tk = median_of(kn)
-            lines.append(f"{name} | r3dm_knn k = {k} | {tk:.3f} | {tk / t2:.2f} | {share(tk)} | {state['fb']:.4f}")
+            def kn(on=False, nj1=False, tag="off"):
+                if dev:
+                    os.environ["R3DM_KNN_INT_NJ1"] = "1" if nj1 else "0"
+                c.set_knn_narrow_tiles(on)
+                try:
+                    c.knn(a, b, k, binary=binary)
+                finally:
+                    c.set_knn_narrow_tiles(False)
+                s = c.stats()
+                state[tag] = (s.n_exact_fallback / b.shape[0], "bf16" if s.n_knn_integer_tiles else "split f16" if s.n_knn_split_tiles else "f32")
+                return s.ms_match_kernels
+            fns = [lambda: kn(False, False, "off")]
+            if not binary:
+                fns.append(lambda: kn(True, False, "on"))
+                if dev and not (np.asarray(a, np.float32) != np.rint(a)).any():      # integer rows: the bf16 kernel's A/B
+                    fns.append(lambda: kn(True, True, "on1"))
+            res = alternated(fns)
+            tk, lo, hi = res[0]
+            lines.append(f"{name} | r3dm_knn k = {k} | {tk:.3f} [{lo:.3f} .. {hi:.3f}] | {tk / t2:.2f} | {share(tk)} | {state['off'][0]:.4f}")
+            for (tn, nlo, nhi), tag in zip(res[1:], ("on", "on1")):
+                tiles = state[tag][1] + (", one query tile per wave" if tag == "on1" else "")
+                beyond = "yes" if tk - tn > hi - lo else "NO"
+                narrow.append(f"{name} | {k} | {tiles} | {tk:.3f} [{lo:.3f} .. {hi:.3f}] | {tn:.3f} [{nlo:.3f} .. {nhi:.3f}] | {tk / tn:.2f} | {beyond} | "
+                              f"{state['off'][0]:.4f} / {state[tag][0]:.4f}")
     c.close()
-    text = "\n".join(lines)
+    text = "\n".join(lines + ["", "narrow tiles (r3dm_set_knn_narrow_tiles), alternated with the f32 K-list kernel in one loop"] + narrow)
     print(text)
-    if len(sys.argv) > 1:
-        with open(sys.argv[1], "w") as f:
+    if args:
+        with open(args[0], "w") as f:
             f.write(text + "\n")
 
 
