@@ -154,6 +154,20 @@ static BatchPlan without_count_tiles(BatchPlan p)
     return p.path == BatchPath::kCountTiles ? BatchPlan{BatchPath::kSplitPlanes, kLayRows | kLaySplit} : p;
 }
 
+// The certification slack factor of a launch: a nominee's key + ||q||^2 differs from its reference distance by at most
+// err_scale (max||a||^2 + ||q||^2) (MatchParams::err_scale, KnnParams::err_scale; G = padded descriptor length / 8).
+// f32 tiles: |MFMA-path distance - reference distance| <= (3.5 D + 14) u (max||a||^2 + ||q||^2),
+// u = 2^-24 (DESIGN.md "Certification"); 4.25 D u covers it for every padded D >= 64
+// split-f16 keys: residue of the two-piece split 3 x 2^-22 ||a|| ||b|| <= 1.5 x 2^-22 (||a||^2 + ||b||^2), f32 accumulation of
+// 3 Dpad products + one C operand per MFMA with a one-sided 2^-23 per addition on partial sums <= 2 (||a||^2 + ||b||^2), plus the
+// reference sum's own (D/2 + 12) 2^-24 -- together below (3 Dpad + 34) 2^-22 (kernels_match_16bit.hip, l2_knn2_split_kernel), + 2 for
+// the count kernel's bias: its keys carry ||b||^2 / (2 s_b) and drop it again
+static float cert_slack_factor(uint32_t G, bool split_or_count_tiles)
+{
+    const float dpad = (float)(G * 8);
+    return split_or_count_tiles ? (3.0f * dpad + 36.0f) * 2.3841858e-07f : 4.25f * dpad * 5.9604645e-08f;
+}
+
 // runs the 2-NN + ratio kernels over `jobs` (slot pairs, all of one dtype/dim) and appends the
 // non-empty results to `g` in job order.  knn_idx/knn_dist (host, optional) receive the raw 2-NN.
 int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g,
@@ -223,13 +237,7 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     mp.pairs = c->d_pairs.as<uint2>();
     mp.n_pairs = P; mp.qb_per_pair = 0; mp.q_stride = q_stride;
     mp.ratio_R = ratio_R;
-    // certification slack factor: |MFMA-path distance - reference distance| <= (3.5 D + 14) u (max||a||^2 + ||q||^2),
-    // u = 2^-24 (DESIGN.md "Certification"); 4.25 D u covers it for every padded D >= 64
-    mp.err_scale = 4.25f * (float)(first.G * 8) * 5.9604645e-08f;
-    // split-f16 keys: residue of the two-piece split 3 x 2^-22 ||a|| ||b|| <= 1.5 x 2^-22 (||a||^2 + ||b||^2), f32 accumulation of
-    // 3 Dpad products + one C operand per MFMA with a one-sided 2^-23 per addition on partial sums <= 2 (||a||^2 + ||b||^2), plus the
-    // reference sum's own (D/2 + 12) 2^-24 -- together below (3 Dpad + 34) 2^-22, + 2 for the count kernel's bias (kernels_match.hip, l2_knn2_split_kernel)
-    if (plan.path == BatchPath::kSplitPlanes || plan.path == BatchPath::kCountTiles) mp.err_scale = (3.0f * (float)(first.G * 8) + 36.0f) * 2.3841858e-07f;      // (+ 2: the count kernel's keys carry ||b||^2 / (2 s_b) and drop it again)
+    mp.err_scale = cert_slack_factor(first.G, plan.path == BatchPath::kSplitPlanes || plan.path == BatchPath::kCountTiles);
     // (developer build: the slack factor in permille of the derived one -- 0 certifies on the bare inequality.  Only verdicts depend
     //  on it, no address does; tests/test_gpu_certificate.py shows that its cases notice.  The split planes' absolute part is a
     //  constant of their kernel and stays.)
@@ -471,6 +479,16 @@ extern "C" void r3dm_index_destroy(r3dm_index* ix)
     delete ix;
 }
 
+// an index search's two private slots: the index mounted into slot_index (aliases of its buffers, for this call only) beside the
+// freshly staged query view in slot_query
+static int mount_index_beside_queries(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t slot_index, uint32_t slot_query)
+{
+    r3dm_index* mix = const_cast<r3dm_index*>(ix);
+    { std::lock_guard<std::mutex> lk(mix->mu); c->imgs[slot_index]->mount(mix); }
+    const int rc = publish_entry(c, slot_index);
+    return rc != R3DM_OK ? rc : stage_into_slot(c, slot_query, 0, 0, 0, query, n_query, ix->img.dim, ix->img.dtype, nullptr);
+}
+
 static int r3dm_index_knn2_impl(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, int32_t* out_idx, float* out_dist)
 {
     if (!c || !ix || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
@@ -478,10 +496,7 @@ static int r3dm_index_knn2_impl(r3dm_ctx* c, const r3dm_index* ix, const void* q
     if (ix->device != c->device) { c->err = "r3dm_index_knn2: the index lives on another device"; return R3DM_ERR_INVALID; }
     R3DM_HIP(c, hipSetDevice(c->device));
     PrivateSlots s(c, 2);
-    r3dm_index* mix = const_cast<r3dm_index*>(ix);
-    { std::lock_guard<std::mutex> lk(mix->mu); c->imgs[s[0]]->mount(mix); }      // aliases of the index's buffers, for this call only
-    int rc = publish_entry(c, s[0]);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, ix->img.dim, ix->img.dtype, nullptr);
+    const int rc = mount_index_beside_queries(c, ix, query, n_query, s[0], s[1]);
     if (rc != R3DM_OK) return rc;
     CallCounters counters(c, {&r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma});
     return run_match_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, nullptr, out_idx, out_dist);
@@ -521,7 +536,7 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
     KnnParams kp{};
     kp.imgs = c->d_imgs.as<ImgDev>();
     kp.sI = sI; kp.sJ = sJ; kp.k = k;
-    kp.err_scale = 4.25f * (float)(G * 8) * 5.9604645e-08f;        // as run_match_batch on the f32 tiles (DESIGN.md "Certification")
+    kp.err_scale = cert_slack_factor(G, false);
     kp.out_idx = c->d_knn_idx.as<int32_t>();
     kp.out_dist = c->d_knn_dist.as<float>();
     kp.fb_cnt = c->d_fb.as<uint32_t>();
@@ -540,7 +555,7 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
             if (e == hipSuccess) c->stats.n_knn_integer_tiles += 1;
         } else if (plan.path == BatchPath::kSplitPlanes) {
             KnnParams ks = kp;
-            ks.err_scale = (3.0f * (float)(G * 8) + 36.0f) * 2.3841858e-07f;      // the split formula of run_match_batch
+            ks.err_scale = cert_slack_factor(G, true);
             e = launch_l2_knnk_split(c->stream, ks, G, ntI, ntJ);
             if (e == hipSuccess) c->stats.n_knn_split_tiles += 1;
         }
@@ -586,13 +601,25 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
 // the counters a k-NN call reports: its queries, how many the exact scan answered, which narrow tiles its K-list kernel ran on
 // (r3dm_set_knn_narrow_tiles) -- and the 2-NN opt-in paths' counters, which hold 0 after a call on the k-list kernels;
 // ms_match_kernels holds the HIP-event time of the call's first kernel (tools/knn_perf.py)
-#define R3DM_KNN_COUNTERS {&r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma, \
-                           &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries, &r3dm_stats::n_knn_integer_tiles, &r3dm_stats::n_knn_split_tiles}
+static constexpr std::initializer_list<uint64_t r3dm_stats::*> kKnnCounters = {
+    &r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma,
+    &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries, &r3dm_stats::n_knn_integer_tiles, &r3dm_stats::n_knn_split_tiles};
 
-// first column of a 2-NN result
-static void first_column(const std::vector<int32_t>& i2, const std::vector<float>& d2, uint32_t n_query, int32_t* out_idx, float* out_dist)
+// k <= 2 is the 2-NN path itself, bit-identical to r3dm_knn2 / r3dm_index_knn2 by construction: knn2(idx, dist) runs that call; k = 1
+// keeps the first column of its result
+template <class Knn2>
+static int knn_by_knn2(r3dm_ctx* c, uint32_t k, uint32_t n_query, int32_t* out_idx, float* out_dist, Knn2&& knn2)
 {
-    for (uint32_t q = 0; q < n_query; ++q) { out_idx[q] = i2[2 * (size_t)q]; out_dist[q] = d2[2 * (size_t)q]; }
+    int rc;
+    if (k == 2) rc = knn2(out_idx, out_dist);
+    else {
+        std::vector<int32_t> i2(2 * (size_t)n_query); std::vector<float> d2(2 * (size_t)n_query);
+        rc = knn2(i2.data(), d2.data());
+        if (rc == R3DM_OK)
+            for (uint32_t q = 0; q < n_query; ++q) { out_idx[q] = i2[2 * (size_t)q]; out_dist[q] = d2[2 * (size_t)q]; }
+    }
+    if (rc == R3DM_OK) c->stats.n_queries = n_query;
+    return rc;
 }
 
 static int r3dm_knn_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
@@ -602,25 +629,16 @@ static int r3dm_knn_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, c
     if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || n_dataset < k) return R3DM_ERR_INVALID;      // ArrayMatcher plugins: NN > nbRows / nbQuery < 1
     if (dtype != R3DM_F32 && dtype != R3DM_U8 && dtype != R3DM_BIN) return R3DM_ERR_INVALID;
     if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
-    if (k <= 2 && n_dataset >= 2) {
-        // the 2-NN path itself: bit-identical to r3dm_knn2 by construction
-        int rc;
-        if (k == 2) rc = r3dm_knn2_impl(c, dataset, n_dataset, query, n_query, dim, dtype, out_idx, out_dist);
-        else {
-            std::vector<int32_t> i2(2 * (size_t)n_query); std::vector<float> d2(2 * (size_t)n_query);
-            rc = r3dm_knn2_impl(c, dataset, n_dataset, query, n_query, dim, dtype, i2.data(), d2.data());
-            if (rc == R3DM_OK) first_column(i2, d2, n_query, out_idx, out_dist);
-        }
-        if (rc == R3DM_OK) c->stats.n_queries = n_query;
-        return rc;
-    }
+    if (k <= 2 && n_dataset >= 2)
+        return knn_by_knn2(c, k, n_query, out_idx, out_dist,
+                           [&](int32_t* idx, float* dist) { return r3dm_knn2_impl(c, dataset, n_dataset, query, n_query, dim, dtype, idx, dist); });
     if (n_dataset >= (1u << 22)) { c->err = "more than 4M rows in one dataset"; return R3DM_ERR_UNSUPPORTED; }
     R3DM_HIP(c, hipSetDevice(c->device));
     PrivateSlots s(c, 2);
     int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
     if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, dim, dtype, nullptr);
     if (rc != R3DM_OK) return rc;
-    CallCounters counters(c, R3DM_KNN_COUNTERS, {&r3dm_stats::ms_match_kernels});
+    CallCounters counters(c, kKnnCounters, {&r3dm_stats::ms_match_kernels});
     return run_knn_batch(c, s[0], s[1], k, out_idx, out_dist);
 }
 
@@ -635,26 +653,15 @@ static int r3dm_index_knn_impl(r3dm_ctx* c, const r3dm_index* ix, const void* qu
 {
     if (!c || !ix || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
     if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || ix->img.n < k) return R3DM_ERR_INVALID;
-    if (k <= 2 && ix->img.n >= 2) {
-        int rc;
-        if (k == 2) rc = r3dm_index_knn2_impl(c, ix, query, n_query, out_idx, out_dist);
-        else {
-            std::vector<int32_t> i2(2 * (size_t)n_query); std::vector<float> d2(2 * (size_t)n_query);
-            rc = r3dm_index_knn2_impl(c, ix, query, n_query, i2.data(), d2.data());
-            if (rc == R3DM_OK) first_column(i2, d2, n_query, out_idx, out_dist);
-        }
-        if (rc == R3DM_OK) c->stats.n_queries = n_query;
-        return rc;
-    }
+    if (k <= 2 && ix->img.n >= 2)
+        return knn_by_knn2(c, k, n_query, out_idx, out_dist,
+                           [&](int32_t* idx, float* dist) { return r3dm_index_knn2_impl(c, ix, query, n_query, idx, dist); });
     if (ix->device != c->device) { c->err = "r3dm_index_knn: the index lives on another device"; return R3DM_ERR_INVALID; }
     R3DM_HIP(c, hipSetDevice(c->device));
     PrivateSlots s(c, 2);
-    r3dm_index* mix = const_cast<r3dm_index*>(ix);
-    { std::lock_guard<std::mutex> lk(mix->mu); c->imgs[s[0]]->mount(mix); }      // aliases of the index's buffers, for this call only
-    int rc = publish_entry(c, s[0]);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, ix->img.dim, ix->img.dtype, nullptr);
+    const int rc = mount_index_beside_queries(c, ix, query, n_query, s[0], s[1]);
     if (rc != R3DM_OK) return rc;
-    CallCounters counters(c, R3DM_KNN_COUNTERS, {&r3dm_stats::ms_match_kernels});
+    CallCounters counters(c, kKnnCounters, {&r3dm_stats::ms_match_kernels});
     return run_knn_batch(c, s[0], s[1], k, out_idx, out_dist);
 }
 

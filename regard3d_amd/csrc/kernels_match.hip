@@ -1,6 +1,8 @@
 // kernels_match.hip -- putative matching on gfx950 (MI355X): staging of a view and the fused squared-L2 2-NN on FP32 MFMA tiles
 // (the headline kernel).  Siblings: kernels_match_16bit.hip (bf16 / f16 nominators), kernels_match_hamming.hip (binary descriptors),
-// kernels_match_exact.hip (exact scans, per-pair finalisation); shared device helpers in kernels_match_common.hpp.
+// kernels_match_exact.hip (exact scans, per-pair finalisation), kernels_match_knn.hip / kernels_match_knn16.hip (k-NN); shared device
+// helpers in kernels_match_common.hpp; the tile steps of every MFMA nominator, their list interface, the buffer descriptor and the
+// launchers' grid in kernels_match_tiles.hpp.
 //
 // What it replaces in the reference (rhiestan/Regard3D, /root/reference):
 //   Matcher_Regions(fDistRatio, BRUTE_FORCE_L2).Match()    src/R3DComputeMatches.cpp:2037-2039,2048
@@ -16,7 +18,7 @@
 // This file is compiled with -ffp-contract=off; fused operations are spelled fmaf()/MFMA.
 
 
-#include "kernels_match_common.hpp"
+#include "kernels_match_tiles.hpp"
 
 namespace r3dm {
 
@@ -259,76 +261,7 @@ hipError_t launch_stage_bf16(hipStream_t st, const float* tiled, uint32_t G, uin
 // The k axis is permuted identically on both operands (lane half h supplies dims 8g+4h+cc at
 // step 4g+cc), which a dot product does not notice.
 // ------------------------------------------------------------------------------------------------
-// One dataset tile: MFMAs of tile t into `cur`, while the VALU folds the finished accumulators of
-// tile t-1 (`prev`) into the running top-2 lists -- software pipelining inside the wave, so the
-// epilogue issues in the shadow of the 64-cycle MFMAs instead of after them.
-template <int G, int NJ, int PF, int PIPE>
-__device__ __forceinline__ void l2_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
-                                             uint32_t soffA, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4],
-                                             const f32x4 (&bq)[NJ][G], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
-                                             Top2 (&st)[NJ], uint32_t prev_rowbase)
-{
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) cur[nj][r] = nrm[r >> 2][r & 3];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const f32x4 a = abuf[g % PF];
-        abuf[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 1024u);
-        if (g == 2) {   // next tile's norms: early, so the wait at the tile boundary finds them landed
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
-        }
-        if constexpr (PIPE == 4) __builtin_amdgcn_s_setprio(1);
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc)
-#pragma unroll
-            for (int nj = 0; nj < NJ; ++nj)
-                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bq[nj][g][cc], cur[nj], 0, 0, 0);
-        if constexpr (PIPE == 4) __builtin_amdgcn_s_setprio(0);
-        // this group's share of the previous tile's 16 accumulator values per query tile
-        if constexpr (PIPE == 9) {
-            // ablation (timing only, results meaningless): keep the accumulators alive, skip the epilogue
-#pragma unroll
-            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
-#pragma unroll
-                for (int nj = 0; nj < NJ; ++nj) asm volatile("" ::"v"(prev[nj][r]));
-        } else if constexpr (PIPE == 3) {
-            // test-and-skip: a value can only change a list if it is below that lane's bound d2; once the
-            // lists have warmed up that is rare, so one wave-wide test guards the whole slice
-            bool any = false;
-#pragma unroll
-            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
-#pragma unroll
-                for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < st[nj].d2;
-            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-#pragma unroll
-                for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
-#pragma unroll
-                    for (int nj = 0; nj < NJ; ++nj)
-                        top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
-            }
-        } else {
-#pragma unroll
-            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
-#pragma unroll
-                for (int nj = 0; nj < NJ; ++nj)
-                    top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
-        }
-        if constexpr (PIPE == 2) {
-            // issue order inside the step: MFMA, 3 VALU, MFMA, 3 VALU, ... so the epilogue slice hides
-            // behind the 64-cycle matrix instructions instead of in front of them
-#pragma unroll
-            for (int i = 0; i < 4 * NJ; ++i) {
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);   // 3 VALU
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);                // keep each prefetch / epilogue slice in its own step
-    }
-}
-
+// One dataset tile is l2_tile_step (kernels_match_tiles.hpp), shared with l2_knnk_mfma_kernel.
 template <int G, int NJ, int PF, int PIPE, int WPS>
 __global__ __launch_bounds__(256, WPS)
 void l2_knn2_mfma_kernel(const MatchParams P)
@@ -340,6 +273,8 @@ void l2_knn2_mfma_kernel(const MatchParams P)
     // workgroup -> (pair, query block).  Workgroups are dealt round-robin to the 8 XCDs, each with its own L2; with
     // xcd_map every workgroup of a pair runs on ONE XCD (pair p on XCD p % 8), so image I and the query tiles are pulled
     // into one L2 instead of eight (pairs are sorted by I: an XCD's consecutive pairs mostly share their dataset image).
+    // (Written out in every 2-NN nominator, like the query load and the drain below: as shared functions they change the
+    // kernels' machine code, DESIGN.md 4.19.  The host side is pair_grid.)
     uint32_t pair, qb;
     if (P.xcd_map) {
         const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
@@ -389,14 +324,7 @@ void l2_knn2_mfma_kernel(const MatchParams P)
             for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) accB[nj][r] = R3DM_INF;          // "tile -1": keys that never win
-            // descriptors from wave-uniform values only (readfirstlane) so no waterfall loop is emitted
-            const uint64_t pa = (uint64_t)Ip->tiled, pn = (uint64_t)Ip->norms;
-            const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
-                0, 0x7FFFFFFF, 0x00020000);
-            const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-                (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pn >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pn)),
-                0, 0x7FFFFFFF, 0x00020000);
+            const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms);
             const uint32_t voffA = lane * 16u, voffN = h * 16u;
             const uint32_t tileB = (uint32_t)G * 1024u;                // bytes per tile
             const uint32_t hb = 4u * h;
@@ -458,14 +386,9 @@ template <int G, int NJ, int PF, int PIPE, int WPS>
 static hipError_t launch_l2_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * NJ;                 // 4 waves x NJ query tiles x 32 queries
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
     static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    P.xcd_map = (uint32_t)xcd_map;
-    const uint64_t grid64 = (uint64_t)(xcd_map ? (P.n_pairs + 7u) / 8u * 8u : P.n_pairs) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
-    const uint32_t grid = (uint32_t)grid64;
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
     hipLaunchKernelGGL((l2_knn2_mfma_kernel<G, NJ, PF, PIPE, WPS>), dim3(grid), dim3(256), 0, st, P);
     return hipGetLastError();
 }

@@ -3,83 +3,21 @@
 //   l2_knn2_split_kernel    real-valued rows as two f16 pieces, three MFMAs per 16 dimensions               (r3dm_set_split_mfma)
 //   l2_knn2_counts2_kernel  rows that are small integers x a row scale (LIOP): one MFMA per 16 dimensions, one list per query
 //   l2_knn2_counts_kernel   the same with one list per lane half (256-dimensional views; developer A/B)
-// with their staging kernels.  What they replace is what kernels_match.hip replaces (/root/reference/src/R3DComputeMatches.cpp:437-489,
+// with their staging kernels.  The tile steps of the first two (int_tile_step, split_tile_step), the buffer descriptor, the bf16 x -2
+// repacking and the launchers' grid are in kernels_match_tiles.hpp, shared with the K-list kernels of kernels_match_knn16.hip; the
+// count-tile steps have no K-list twin and stay here.
+// What they replace is what kernels_match.hip replaces (/root/reference/src/R3DComputeMatches.cpp:437-489,
 // src/Regard3DFeatures.h:44-48): nominees are re-scored in the reference's f32 arithmetic and certified by the shared tail
 // (kernels_match_common.hpp), so the distances that are compared, ratio-tested and returned are the reference's own.
-#include "kernels_match_common.hpp"
+#include "kernels_match_tiles.hpp"
 
 namespace r3dm {
 
 // ------------------------------------------------------------------------------------------------
-// integer fast path (r3dm_set_integer_mfma): the same contraction on v_mfma_f32_32x32x16_bf16.
-// Views whose descriptors are integers of magnitude <= 256 (SIFT bins) are staged a second time as bf16 tiles
-// (ImgDev::tiled16, [tile][16-dim block][lane half][32 rows][8 bf16] -- 16 bytes per lane and step like the f32
-// tiles, half as many steps).  Every value is a bf16, every product and partial sum an integer below 2^24, so the f32
-// accumulators hold exactly the values of the f32 path and of the reference's sum of squared differences
-// (l2_finish_queries re-checks the condition per pair; anything else goes to the exact scan).
-// At 32 cycles per MFMA (16x fewer matrix cycles) the VALU side of l2_tile_step -- 10.7 VALU instructions per MFMA:
-// accumulator init, one compare per key, 8-instruction pushes into (best, runner-up, bound) lists -- would hold the
-// issue port longer than the matrix pipe runs.  Exact keys allow less:
-//   * lists hold (best, runner-up) only.  Keys are exact and every lane sees its rows in increasing index order, so
-//     strict '<' keeps the lexicographic (distance, index) top-2 of the lane's rows, and a lexicographic merge of the
-//     two lane halves IS the exact top-2 -- no certification bound, a third fewer list updates;
-//   * one wave-wide test per FOUR keys of a list (v_min3 + v_min + v_cmp instead of four v_cmp);
-//   * the accumulators start from the norm vector through the MFMA's C operand (8 v_mov_b64 per tile instead of 32 v_mov).
-// Measured (780 pairs of 8192 x 8192 rows): f32 tiles 95.0 ms; this kernel 12.4 ms (12.96 before the per-key tests in the
-// update path) (the f32 kernel's structure on bf16
-// tiles: 14.97 ms; without any epilogue: 11.4 ms).  The shader clock drops from 2.32 GHz (f32 kernel) to 1.84 GHz under
-// the bf16 matrix load (GRBM_GUI_ACTIVE / duration), so 12.4 ms is 56 % of the clocked bf16 peak.  Sharing the dataset
-// tiles of a workgroup through LDS (a quarter of the L1 traffic) measured 16.0 ms against 15.0 ms and was dropped.
+// integer fast path (r3dm_set_integer_mfma): integer-valued rows on v_mfma_f32_32x32x16_bf16, exact keys, (best, runner-up) lists
+// without a bound.  The tile step with its design notes and measurements is int_tile_step (kernels_match_tiles.hpp), shared with
+// l2_knnk_int_kernel.  One workgroup = 4 waves, each wave NJ query tiles in registers; ping-pong accumulators, no LDS, no barriers.
 // ------------------------------------------------------------------------------------------------
-template <int GB, int NJ, int PF, int ABL>
-__device__ __forceinline__ void int_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
-                                              uint32_t soffA, uint32_t soffN, f32x4 (&abuf)[PF], const f32x16& nrm_cur, f32x16& nrm_next,
-                                              const f32x4 (&bq)[NJ][GB], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
-                                              Top2 (&st)[NJ], uint32_t prev_rowbase)
-{
-    constexpr int NG = 4 * NJ;                             // (list, quad) groups of four keys per tile
-#pragma unroll
-    for (int g = 0; g < GB; ++g) {
-        const f32x4 a = abuf[g % PF];
-        if (ABL < 2) abuf[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 1024u);
-        if (ABL < 2 && g == (GB > 2 ? 2 : GB - 1)) {   // next tile's norms, element 4 qd + k = row 8 qd + 4 h + k: the accumulator layout
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) {
-                const f32x4 v = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) nrm_next[4 * qd + k] = v[k];
-            }
-        }
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq[nj][g]),
-                                                              g == 0 ? nrm_cur : cur[nj], 0, 0, 0);
-#pragma unroll
-        for (int gi = (g * NG) / GB; gi < ((g + 1) * NG) / GB; ++gi) {
-            const int nj = gi % NJ, qd = gi / NJ;
-            const float p0 = prev[nj][4 * qd], p1 = prev[nj][4 * qd + 1], p2 = prev[nj][4 * qd + 2], p3 = prev[nj][4 * qd + 3];
-            if constexpr ((ABL & 1) != 0) {
-                asm volatile("" ::"v"(p0), "v"(p1), "v"(p2), "v"(p3));
-            } else {
-                // Step 0 may follow the previous tile's last MFMAs (the writers of p0..p3) closely: its minimum goes through
-                // ordinary fminf so that the compiler's MFMA -> VALU hazard pass sees the read; from step 1 on at least NJ
-                // MFMAs and a sched_barrier lie in between and the two-instruction asm form is safe.
-                const float m = g == 0 ? __builtin_fminf(__builtin_fminf(p0, p1), __builtin_fminf(p2, p3)) : vmin2(vmin3(p0, p1, p2), p3);
-                if (__builtin_amdgcn_ballot_w64(m < st[nj].d1) != 0ull) {
-                    // some lane improves on one of the four keys: usually ONE key does, so test each before its 7-instruction push
-                    // (the 16-step body of D = 256 stays with unconditional pushes: the compiler gives up unrolling the larger one)
-                    const uint32_t rb = prev_rowbase + 8u * (uint32_t)qd;
-                    if (GB > 8 || __builtin_amdgcn_ballot_w64(p0 < st[nj].d1) != 0ull) tope_push(st[nj], p0, rb);
-                    if (GB > 8 || __builtin_amdgcn_ballot_w64(p1 < st[nj].d1) != 0ull) tope_push(st[nj], p1, rb + 1u);
-                    if (GB > 8 || __builtin_amdgcn_ballot_w64(p2 < st[nj].d1) != 0ull) tope_push(st[nj], p2, rb + 2u);
-                    if (GB > 8 || __builtin_amdgcn_ballot_w64(p3 < st[nj].d1) != 0ull) tope_push(st[nj], p3, rb + 3u);
-                }
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
 template <int GB, int NJ, int PF, int WPS, int ABL = 0>
 __global__ __launch_bounds__(256, WPS)
 void l2_knn2_int_kernel(const MatchParams P)
@@ -115,10 +53,7 @@ void l2_knn2_int_kernel(const MatchParams P)
             const u32x4 w = __builtin_bit_cast(u32x4, src[g * 64]);     // -2 x (integer, |x| <= 256) is a bf16 again
             u32x4 o;
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float lo = __uint_as_float(w[k] << 16) * -2.0f, hi = __uint_as_float(w[k] & 0xFFFF0000u) * -2.0f;
-                o[k] = (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xFFFF0000u);
-            }
+            for (int k = 0; k < 4; ++k) o[k] = bf16x2_times_m2(w[k]);
             bq[nj][g] = __builtin_bit_cast(f32x4, o);
         }
     }
@@ -127,13 +62,7 @@ void l2_knn2_int_kernel(const MatchParams P)
     for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);     // d2 stays +inf: these lists carry no bound
 
     if (nI >= 2) {
-        const uint64_t pa = (uint64_t)Ip->tiled16, pn = (uint64_t)Ip->norms;
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
-            0, 0x7FFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pn >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pn)),
-            0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled16), rn = wave_uniform_rsrc(Ip->norms);
         const uint32_t voffA = lane * 16u, voffN = h * 16u;
         constexpr uint32_t tileB = (uint32_t)GB * 1024u;
         const uint32_t hb = 4u * h;
@@ -177,14 +106,10 @@ template <int GB, int NJ, int PF, int WPS, int ABL = 0>
 static hipError_t launch_l2_int(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * NJ;
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
     static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    P.xcd_map = (uint32_t)xcd_map;
-    const uint64_t grid64 = (uint64_t)(xcd_map ? (P.n_pairs + 7u) / 8u * 8u : P.n_pairs) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((l2_knn2_int_kernel<GB, NJ, PF, WPS, ABL>), dim3((uint32_t)grid64), dim3(256), 0, st, P);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
+    hipLaunchKernelGGL((l2_knn2_int_kernel<GB, NJ, PF, WPS, ABL>), dim3(grid), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 
@@ -236,10 +161,6 @@ hipError_t launch_l2_knn2_int(hipStream_t st, const MatchParams& P, uint32_t G, 
 // (written once, read by the same wave only: no barrier in the loop); dataset hi / lo fragments stream through a PF-deep
 // register window like the f32 kernel's.
 // ------------------------------------------------------------------------------------------------
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }    // -126 <= k <= 127
-
 // one workgroup per 32-row tile: the two f16 planes of the view, scaled by 2^split_k (read from the image table: the
 // statistics kernel ahead of this one on the stream produced max|x|)
 __global__ __launch_bounds__(256)
@@ -276,57 +197,7 @@ hipError_t launch_stage_split(hipStream_t st, const float* rows, uint32_t n, uin
     return hipGetLastError();
 }
 
-template <int GB, int NJ, int PF>
-__device__ __forceinline__ void split_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
-                                                uint32_t soffA, uint32_t soffN, f32x4 (&ah)[PF], f32x4 (&al)[PF], f32x4 (&nrm)[4], float cscale,
-                                                const f32x4 (&bqh)[NJ][GB], const f32x4* __restrict__ bl_lds, f32x16 (&cur)[NJ],
-                                                const f32x16 (&prev)[NJ], Top2 (&st)[NJ], uint32_t prev_rowbase)
-{
-#pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const float v = nrm[r >> 2][r & 3] * cscale;       // ||a||^2 in key units (sI sJ); +inf for padding rows
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj) cur[nj][r] = v;
-    }
-#pragma unroll
-    for (int g = 0; g < GB; ++g) {
-        const f16x8 a_hi = __builtin_bit_cast(f16x8, ah[g % PF]);
-        const f16x8 a_lo = __builtin_bit_cast(f16x8, al[g % PF]);
-        ah[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 2048u);
-        al[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 2048u + 1024u);
-        if (g == 1) {
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
-        }
-        f32x4 bl[NJ];
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj) bl[nj] = bl_lds[(nj * GB + g) * 64];
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, __builtin_bit_cast(f16x8, bl[nj]), cur[nj], 0, 0, 0);
-#pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
-        // this block's share of the previous tile's keys: wave-wide test-and-skip, as in l2_tile_step<PIPE 3>
-        bool any = false;
-#pragma unroll
-        for (int r = (g * 16) / GB; r < ((g + 1) * 16) / GB; ++r)
-#pragma unroll
-            for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < st[nj].d2;
-        if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-#pragma unroll
-            for (int r = (g * 16) / GB; r < ((g + 1) * 16) / GB; ++r)
-#pragma unroll
-                for (int nj = 0; nj < NJ; ++nj)
-                    top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
+// one dataset tile: split_tile_step (kernels_match_tiles.hpp), shared with l2_knnk_split_kernel
 template <int GB, int NJ, int PF>
 __global__ __launch_bounds__(256, 2)
 void l2_knn2_split_kernel(const MatchParams P)
@@ -375,13 +246,7 @@ void l2_knn2_split_kernel(const MatchParams P)
     for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
 
     if (nI >= 2) {
-        const uint64_t pa = (uint64_t)Ip->tiledh, pn = (uint64_t)Ip->norms;
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
-            0, 0x7FFFFFFF, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pn >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pn)),
-            0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiledh), rn = wave_uniform_rsrc(Ip->norms);
         const uint32_t voffA = lane * 16u, voffN = h * 16u;
         constexpr uint32_t tileB = (uint32_t)GB * 2048u;
         const uint32_t hb = 4u * h;
@@ -423,16 +288,12 @@ template <int GB, int NJ, int PF>
 static hipError_t launch_l2_split_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * NJ;
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
-    P.xcd_map = 1u;
-    const uint64_t grid64 = (uint64_t)((P.n_pairs + 7u) / 8u * 8u) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
     const size_t lds = (size_t)4 * NJ * GB * 1024;
     hipError_t e = hipFuncSetAttribute((const void*)l2_knn2_split_kernel<GB, NJ, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((l2_knn2_split_kernel<GB, NJ, PF>), dim3((uint32_t)grid64), dim3(256), lds, st, P);
+    hipLaunchKernelGGL((l2_knn2_split_kernel<GB, NJ, PF>), dim3(grid), dim3(256), lds, st, P);
     return hipGetLastError();
 }
 
@@ -870,17 +731,11 @@ void l2_knn2_counts_kernel(const MatchParams P)
     for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
 
     if (nI >= 2) {
-        const uint64_t pa = (uint64_t)Ip->tiledp;         // rows in the order of their scales (stage_counts_order_kernel)
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
-            0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiledp);     // rows in the order of their scales (stage_counts_order_kernel)
         const uint32_t voffA = lane * 16u;
         constexpr uint32_t tileB = (uint32_t)GB * 1024u;
         const uint32_t hb = 4u * h;
-        const uint64_t prw = (uint64_t)Ip->cquad;
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(prw >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)prw)),
-            0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rr = wave_uniform_rsrc(Ip->cquad);
         const uint32_t voffR = lane * 4u;
         f32x4 abuf[PF];
 #pragma unroll
@@ -1136,16 +991,10 @@ void l2_knn2_counts2_kernel(const MatchParams P)
     st.d0 = st.d1 = st.d2 = 0x7FFFFFFF; st.d3 = 0x7F800000;
 
     if (nI >= 2) {
-        const uint64_t pa = (uint64_t)Ip->tiledp;
-        const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
-            0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiledp);
         const uint32_t voffA = lane * 16u;
         constexpr uint32_t tileB = (uint32_t)GB * 1024u;
-        const uint64_t prw = (uint64_t)Ip->cquad;
-        const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(
-            (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(prw >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)prw)),
-            0, 0x7FFFFFFF, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rr = wave_uniform_rsrc(Ip->cquad);
         const uint32_t voffR = lane * 4u;
         // the quad summaries of tile t: sixteen floats behind the row lines; "tile -1" reads the line one past the last tile (+inf, 1)
         const cf32p sums = (cf32p)(uintptr_t)(Ip->cquad + counts_summary_offset(ntI));
@@ -1207,13 +1056,9 @@ template <int GB, int PF>
 static hipError_t launch_l2_counts2_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * 2u;
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
-    P.xcd_map = 1u;
-    const uint64_t grid64 = (uint64_t)((P.n_pairs + 7u) / 8u * 8u) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((l2_knn2_counts2_kernel<GB, PF>), dim3((uint32_t)grid64), dim3(256), 0, st, P);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, 2u, 1u, grid, status)) return status;
+    hipLaunchKernelGGL((l2_knn2_counts2_kernel<GB, PF>), dim3(grid), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 
@@ -1221,13 +1066,9 @@ template <int GB, int NJ, int PF>
 static hipError_t launch_l2_counts_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * NJ;
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
-    P.xcd_map = 1u;
-    const uint64_t grid64 = (uint64_t)((P.n_pairs + 7u) / 8u * 8u) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
-    hipLaunchKernelGGL((l2_knn2_counts_kernel<GB, NJ, PF>), dim3((uint32_t)grid64), dim3(256), 0, st, P);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
+    hipLaunchKernelGGL((l2_knn2_counts_kernel<GB, NJ, PF>), dim3(grid), dim3(256), 0, st, P);
     return hipGetLastError();
 }
 

@@ -1,7 +1,8 @@
 // kernels_match_common.hpp -- device helpers shared by the matching kernels (kernels_match.hip: f32 tiles; kernels_match_16bit.hip:
 // bf16 / f16 nominators; kernels_match_hamming.hip: binary descriptors; kernels_match_exact.hip: exact scans + finalisation):
 // the reference metric, the (best, runner-up, bound) lists, the buffer load of a fragment, and the shared tail of every L2 kernel
-// (merge the lane halves, re-score in the reference arithmetic, certify, ratio test).
+// (merge the lane halves, re-score in the reference arithmetic, certify, ratio test).  On top of it: kernels_match_knn_lists.hpp (the
+// K-lists and their tail) and kernels_match_tiles.hpp (the tile steps of the MFMA nominators, for either kind of list).
 //
 // Arithmetic contract (OpenMVG L2<float>; /root/reference/src/R3DComputeMatches.cpp:437-489): distances are the f32
 // 4-way-unrolled sum of squared differences, NO fused multiply-add; equal distances -> lowest dataset row.  Every translation unit

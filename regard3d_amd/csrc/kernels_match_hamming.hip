@@ -2,7 +2,7 @@
 //   hamming_knn2_kernel       xor + popcount on the integer VALU, dataset rows through the scalar cache (the default)
 //   l2_knn2_int_lds_kernel    bits as 0 / 1 bytes on i8 MFMA tiles shared through LDS (r3dm_set_hamming_mfma): d = |a| + |b| - 2 a.b, exact
 // Replaces OpenMVG's ArrayMatcherBruteForce<uchar, Hamming> behind the call sites of /root/reference/src/R3DComputeMatches.cpp:437-489.
-#include "kernels_match_common.hpp"
+#include "kernels_match_tiles.hpp"
 
 namespace r3dm {
 
@@ -191,10 +191,8 @@ void l2_knn2_int_lds_kernel(const MatchParams P)
             u32x4 o;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if constexpr (OPS == 0) {                  // -2 x (integer, |x| <= 256) is a bf16 again
-                    const float lo = __uint_as_float(w[k] << 16) * -2.0f, hi = __uint_as_float(w[k] & 0xFFFF0000u) * -2.0f;
-                    o[k] = (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xFFFF0000u);
-                } else o[k] = w[k] * 0xFEu;                // bytes 0 / 1 -> 0 / -2 as i8 (no carries between bytes)
+                if constexpr (OPS == 0) o[k] = bf16x2_times_m2(w[k]);
+                else o[k] = w[k] * 0xFEu;                  // bytes 0 / 1 -> 0 / -2 as i8 (no carries between bytes)
             }
             bq[nj][g] = __builtin_bit_cast(f32x4, o);
         }
@@ -344,10 +342,8 @@ void l2_knn2_int_ring_kernel(const MatchParams P)
             u32x4 o;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                if constexpr (OPS == 0) {                  // -2 x (integer, |x| <= 256) is a bf16 again
-                    const float lo = __uint_as_float(w[k] << 16) * -2.0f, hi = __uint_as_float(w[k] & 0xFFFF0000u) * -2.0f;
-                    o[k] = (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xFFFF0000u);
-                } else o[k] = w[k] * 0xFEu;                // bytes 0 / 1 -> 0 / -2 as i8 (no carries between bytes)
+                if constexpr (OPS == 0) o[k] = bf16x2_times_m2(w[k]);
+                else o[k] = w[k] * 0xFEu;                  // bytes 0 / 1 -> 0 / -2 as i8 (no carries between bytes)
             }
             bq[nj][g] = __builtin_bit_cast(f32x4, o);
         }
@@ -471,18 +467,14 @@ template <int GB, int NJ, int PF, int WPS, int ABL = 0, int OPS = 0>
 static hipError_t launch_l2_int_ring(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * NJ;
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
-    P.xcd_map = 1u;
-    const uint64_t grid64 = (uint64_t)((P.n_pairs + 7u) / 8u * 8u) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
     const size_t lds = kRingK * ((size_t)GB * 1024 + 256) + 2 * kRingK * 4;
     {
         const hipError_t e = hipFuncSetAttribute((const void*)l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
-    hipLaunchKernelGGL((l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>), dim3((uint32_t)grid64), dim3(256), lds, st, P);
+    hipLaunchKernelGGL((l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>), dim3(grid), dim3(256), lds, st, P);
     return hipGetLastError();
 }
 
@@ -490,14 +482,10 @@ template <int GB, int NJ, int PF, int WPS, int ABL = 0, int OPS = 0>
 static hipError_t launch_l2_int_lds(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
     MatchParams P = Pin;
-    const uint32_t tiles_per_wg = 4u * NJ;
-    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
-    P.xcd_map = 1u;
-    const uint64_t grid64 = (uint64_t)((P.n_pairs + 7u) / 8u * 8u) * P.qb_per_pair;
-    if (grid64 == 0) return hipSuccess;
-    if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
     const size_t lds = 3 * (size_t)GB * 1024 + 3 * 1024;
-    hipLaunchKernelGGL((l2_knn2_int_lds_kernel<GB, NJ, PF, WPS, ABL, OPS>), dim3((uint32_t)grid64), dim3(256), lds, st, P);
+    hipLaunchKernelGGL((l2_knn2_int_lds_kernel<GB, NJ, PF, WPS, ABL, OPS>), dim3(grid), dim3(256), lds, st, P);
     return hipGetLastError();
 }
 

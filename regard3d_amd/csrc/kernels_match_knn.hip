@@ -1,53 +1,19 @@
 // kernels_match_knn.hip -- exhaustive k-NN, k = 1 .. R3DM_KNN_MAX (8), of one (dataset, query) pair: what stands behind r3dm_knn /
 // r3dm_index_knn for k >= 3 (ArrayMatcher::SearchNeighbours with any NN, /root/reference/src/utils/matcher_kgraph.h:205-251,
-// matcher_hnsw.h:138-173).  The 2-NN kernels, Top2 and the ratio test are untouched; this unit shares only the header's metric and
-// buffer load with them.
-//   l2_knnk_mfma_kernel<G, PF, KL>     the nominator: the f32 MFMA tile stream of l2_knn2_mfma_kernel with K-lists per lane half
+// matcher_hnsw.h:138-173).
+//   l2_knnk_mfma_kernel<G, PF, KL>     the nominator on the f32 tiles, K-lists per lane half.  Its tile step is l2_tile_step<G, 1, PF, 3>
+//                                      (kernels_match_tiles.hpp), the function template l2_knn2_mfma_kernel instantiates with Top2
 //   (TopK<KL>, knnk_finish<KL>         its lists and its tail -- re-score the nominees in the reference arithmetic, order, certify
 //                                      the k-th -- live in kernels_match_knn_lists.hpp, shared with kernels_match_knn16.hip)
 //   l2_exact_knn_items_kernel<KL>      the exact scan behind it (uncertified queries; lengths without a tensor kernel)
 //   hamming_knnk_kernel<W, KL, QL>     binary rows: xor + popcount with exact (distance, row) K-lists per lane
-// KL is the list depth a kernel is built with: 4 for k <= 4, 8 above; k itself is a run-time value (k <= KL).
+// KL is the list depth a kernel is built with: 4 for k <= 4, 8 above (dispatch_kl); k itself is a run-time value (k <= KL).
 //
 // Arithmetic contract as everywhere (kernels_match_common.hpp): the f32 4-way unrolled sum of squared differences without FMA, equal
 // distances -> lowest dataset row.  This file is compiled with -ffp-contract=off; fused operations are spelled fmaf() / MFMA.
-#include "kernels_match_knn_lists.hpp"
+#include "kernels_match_tiles.hpp"
 
 namespace r3dm {
-
-// One dataset tile (l2_tile_step of kernels_match.hip at NJ = 1, PIPE = 3): the MFMAs of tile t into `cur` while the VALU folds
-// the finished accumulator of tile t - 1 (`prev`) into the K-list.  Test-and-skip: a key changes the list only below the lane's
-// bound d[KL]; one ballot guards a slice of the accumulator, one more each key, and the insert runs only when some lane needs it.
-template <int G, int PF, int KL>
-__device__ __forceinline__ void knnk_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
-                                               uint32_t soffA, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4], const f32x4 (&bq)[G],
-                                               f32x16& cur, const f32x16& prev, TopK<KL>& st, uint32_t prev_rowbase)
-{
-#pragma unroll
-    for (int r = 0; r < 16; ++r) cur[r] = nrm[r >> 2][r & 3];
-#pragma unroll
-    for (int g = 0; g < G; ++g) {
-        const f32x4 a = abuf[g % PF];
-        abuf[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 1024u);
-        if (g == 2) {   // next tile's norms: early, so the wait at the tile boundary finds them landed
-#pragma unroll
-            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
-        }
-#pragma unroll
-        for (int cc = 0; cc < 4; ++cc) cur = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bq[g][cc], cur, 0, 0, 0);
-        // this group's share of the previous tile's 16 keys
-        bool any = false;
-#pragma unroll
-        for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r) any |= prev[r] < st.d[KL];
-        if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
-#pragma unroll
-            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
-                if (__builtin_amdgcn_ballot_w64(prev[r] < st.d[KL]) != 0ull)
-                    topk_push(st, prev[r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
-        }
-        __builtin_amdgcn_sched_barrier(0);                // keep each prefetch / epilogue slice in its own step
-    }
-}
 
 // ------------------------------------------------------------------------------------------------
 // The nominator.  One workgroup = 4 waves, each wave one query tile (32 queries, pre-scaled by -2) in registers as the MFMA B
@@ -71,14 +37,14 @@ void l2_knnk_mfma_kernel(const KnnParams P)
     const uint32_t qt = blockIdx.x * 4u + wave;
     if (qt >= ntJ) return;                            // wave-uniform; no barriers in this kernel
 
-    f32x4 bq[G];
+    f32x4 bq[1][G];
     {
         const gf4p src = (gf4p)Jp->tiled + (size_t)qt * (G * 64) + lane;
 #pragma unroll
-        for (int g = 0; g < G; ++g) bq[g] = src[g * 64] * -2.0f;
+        for (int g = 0; g < G; ++g) bq[0][g] = src[g * 64] * -2.0f;
     }
-    TopK<KL> st;
-    topk_init(st);
+    TopK<KL> st[1];
+    topk_init(st[0]);
 
     // dataset stream: float4 index = (t G + g) 64 + lane; norms of tile t, quad qd: float4 index 8 t + 2 qd + h
     const gf4p abase = (gf4p)Ip->tiled;
@@ -89,44 +55,38 @@ void l2_knnk_mfma_kernel(const KnnParams P)
     f32x4 nrm[4];
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) nrm[qd] = nbase[2 * qd + h];
-    f32x16 accA, accB;
+    f32x16 accA[1], accB[1];
 #pragma unroll
-    for (int r = 0; r < 16; ++r) accB[r] = R3DM_INF;          // "tile -1": keys that never enter a list
-    // descriptors from wave-uniform values only (readfirstlane) so no waterfall loop is emitted
-    const uint64_t pa = (uint64_t)Ip->tiled, pn = (uint64_t)Ip->norms;
-    const __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pa >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pa)),
-        0, 0x7FFFFFFF, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rn = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(pn >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)pn)),
-        0, 0x7FFFFFFF, 0x00020000);
+    for (int r = 0; r < 16; ++r) accB[0][r] = R3DM_INF;       // "tile -1": keys that never enter a list
+    const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms);
     const uint32_t voffA = lane * 16u, voffN = h * 16u;
     const uint32_t tileB = (uint32_t)G * 1024u;                // bytes per tile (the launcher keeps n_tiles x tileB below 2^31)
     const uint32_t hb = 4u * h;
     uint32_t t = 0;
     for (; t + 1 < ntI; t += 2) {
-        knnk_tile_step<G, PF, KL>(ra, rn, voffA, voffN, t * tileB + PF * 1024u, (t + 1) * 128u, abuf, nrm, bq, accA, accB, st, (t - 1) * 32u + hb);
-        knnk_tile_step<G, PF, KL>(ra, rn, voffA, voffN, (t + 1) * tileB + PF * 1024u, (t + 2) * 128u, abuf, nrm, bq, accB, accA, st, t * 32u + hb);
+        l2_tile_step<G, 1, PF, 3>(ra, rn, voffA, voffN, t * tileB + PF * 1024u, (t + 1) * 128u, abuf, nrm, bq, accA, accB, st, (t - 1) * 32u + hb);
+        l2_tile_step<G, 1, PF, 3>(ra, rn, voffA, voffN, (t + 1) * tileB + PF * 1024u, (t + 2) * 128u, abuf, nrm, bq, accB, accA, st, t * 32u + hb);
     }
     if (t < ntI) {
-        knnk_tile_step<G, PF, KL>(ra, rn, voffA, voffN, t * tileB + PF * 1024u, (t + 1) * 128u, abuf, nrm, bq, accA, accB, st, (t - 1) * 32u + hb);
+        l2_tile_step<G, 1, PF, 3>(ra, rn, voffA, voffN, t * tileB + PF * 1024u, (t + 1) * 128u, abuf, nrm, bq, accA, accB, st, (t - 1) * 32u + hb);
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            if (__builtin_amdgcn_ballot_w64(accA[r] < st.d[KL]) != 0ull) topk_push(st, accA[r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            if (__builtin_amdgcn_ballot_w64(accA[0][r] < st[0].d[KL]) != 0ull) topk_push(st[0], accA[0][r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
     } else {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
-            if (__builtin_amdgcn_ballot_w64(accB[r] < st.d[KL]) != 0ull) topk_push(st, accB[r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            if (__builtin_amdgcn_ballot_w64(accB[0][r] < st[0].d[KL]) != 0ull) topk_push(st[0], accB[0][r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
     }
-    knnk_finish<KL>(P, Ip, Jp, st, qt, h, c, (float)(G * 8));
+    knnk_finish<KL>(P, Ip, Jp, st[0], qt, h, c, (float)(G * 8));
 }
 
 template <int G, int PF>
 static hipError_t launch_knnk_g(hipStream_t st, const KnnParams& P, uint32_t grid)
 {
-    if (P.k <= 4) hipLaunchKernelGGL((l2_knnk_mfma_kernel<G, PF, 4>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((l2_knnk_mfma_kernel<G, PF, 8>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return dispatch_kl(P.k, [&](auto kl) {
+        hipLaunchKernelGGL((l2_knnk_mfma_kernel<G, PF, decltype(kl)::value>), dim3(grid), dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 // hipErrorInvalidValue: no nominator for this launch (G without a tensor kernel, or a dataset whose tiles pass the 2^31-byte reach
@@ -134,7 +94,7 @@ static hipError_t launch_knnk_g(hipStream_t st, const KnnParams& P, uint32_t gri
 hipError_t launch_l2_knnk(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query)
 {
     if (P.k < 1 || P.k > R3DM_KNN_MAX) return hipErrorInvalidValue;
-    if ((uint64_t)n_tiles_dataset * G * 1024ull + 2ull * kSlackBytes >= 0x7FFFFFFFull) return hipErrorInvalidValue;
+    if (!tiles_within_reach(n_tiles_dataset, G * 1024u)) return hipErrorInvalidValue;
     const uint32_t grid = (n_tiles_query + 3u) / 4u;
     if (grid == 0) return hipSuccess;
     switch (G) {
@@ -217,9 +177,10 @@ hipError_t launch_l2_exact_knn_items(hipStream_t st, const KnnParams& P, uint32_
     if (count == 0) return hipSuccess;
     if (P.k < 1 || P.k > R3DM_KNN_MAX) return hipErrorInvalidValue;
     const uint32_t grid = count < 16384u ? count : 16384u;
-    if (P.k <= 4) hipLaunchKernelGGL((l2_exact_knn_items_kernel<4>), dim3(grid), dim3(256), 0, st, P, count, from_list);
-    else hipLaunchKernelGGL((l2_exact_knn_items_kernel<8>), dim3(grid), dim3(256), 0, st, P, count, from_list);
-    return hipGetLastError();
+    return dispatch_kl(P.k, [&](auto kl) {
+        hipLaunchKernelGGL((l2_exact_knn_items_kernel<decltype(kl)::value>), dim3(grid), dim3(256), 0, st, P, count, from_list);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -296,9 +257,10 @@ static hipError_t launch_hamming_knnk_w(hipStream_t st, const KnnParams& P, uint
     constexpr int QL = 2;
     const uint32_t grid = (n_query + 256u * QL - 1u) / (256u * QL);
     if (grid == 0) return hipSuccess;
-    if (P.k <= 4) hipLaunchKernelGGL((hamming_knnk_kernel<W, 4, QL>), dim3(grid), dim3(256), 0, st, P);
-    else hipLaunchKernelGGL((hamming_knnk_kernel<W, 8, QL>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return dispatch_kl(P.k, [&](auto kl) {
+        hipLaunchKernelGGL((hamming_knnk_kernel<W, decltype(kl)::value, QL>), dim3(grid), dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_hamming_knnk(hipStream_t st, const KnnParams& P, uint32_t words, uint32_t n_query)

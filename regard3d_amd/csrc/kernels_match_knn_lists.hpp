@@ -4,6 +4,7 @@
 //   topk_push_exact                    the same list on exact keys: no bound is kept (kernels_match_knn16.hip, integer tiles)
 //   knn_lex_less                       the project's one order: (distance, dataset row)
 //   knnk_finish<KL, MODE>              merge the two lane halves, re-score, rank, certify the k-th, write or list for the exact scan
+// The tile steps that fold keys into these lists, and into Top2, are in kernels_match_tiles.hpp (which includes this header).
 #pragma once
 #include "kernels_match_common.hpp"
 

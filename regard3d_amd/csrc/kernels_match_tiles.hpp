@@ -1,0 +1,320 @@
+// kernels_match_tiles.hpp -- the tile machinery of the MFMA nominators, written once for the 2-NN kernels (Top2 lists:
+// kernels_match.hip, kernels_match_16bit.hip) and the k-NN kernels (TopK<KL> lists: kernels_match_knn.hip, kernels_match_knn16.hip):
+//   wave_uniform_rsrc                  the buffer descriptor of a wave-uniform base pointer
+//   pow2f, f16x8                       2^k as a float; the f16 MFMA operand type
+//   list_bound / list_push             the interface a tile step folds keys through: lists that keep a bound (Top2::d2, TopK::d[KL])
+//   list_last / list_push_exact        ... and lists of exact keys without one (integer tiles: Top2::d1, TopK::d[KL - 1])
+//   kTestsEachKey, kTestsEachKeyExact  whether a list policy guards every single push with a ballot of its own
+//   l2_tile_step                       one dataset tile on the f32 tiles          (v_mfma_f32_32x32x2_f32)
+//   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
+//   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
+//   bf16x2_times_m2                    -2 x a packed pair of bf16 integers (the query fragments of the integer tiles)
+//   pair_grid                          host: qb_per_pair, xcd_map, the grid of a 2-NN launch and its bound
+//   dispatch_kl, tiles_within_reach    host: k -> list depth of a K-list launch; the 2^31-byte reach of the buffer offsets
+// Every step is templated on the list type and on NJ, the query tiles a wave holds; the K-list kernels that hold one tile keep arrays
+// of one.
+// What is NOT here, on purpose: the ping-pong loop around the steps (two steps, the odd tail, the drain of the last tile), the load of
+// a wave's query fragments and the workgroup -> (pair, query block) decode stay written out in every kernel.  Each of them was tried
+// as a function of this header and changed the machine code of the kernels that called it; a kernel's bytes decide.
+// What holds is what was a function before (the steps) and pure expressions on values (the descriptor, the bf16 repacking).
+//
+// Arithmetic contract as everywhere (kernels_match_common.hpp); every unit that includes this header is compiled with
+// -ffp-contract=off, fused operations are spelled fmaf() / MFMA.
+#pragma once
+#include "kernels_match_knn_lists.hpp"
+
+#include <type_traits>
+
+namespace r3dm {
+
+// descriptor from wave-uniform values only (readfirstlane) so no waterfall loop is emitted; 2^31 - 1 bytes of reach
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wave_uniform_rsrc(const void* p)
+{
+    const uint64_t a = (uint64_t)p;
+    return __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)(a >> 32)) << 32) | (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((uint32_t)a)),
+        0, 0x7FFFFFFF, 0x00020000);
+}
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+__device__ __forceinline__ float pow2f(int k) { return __uint_as_float((uint32_t)(127 + k) << 23); }    // -126 <= k <= 127
+
+// ------------------------------------------------------------------------------------------------
+// What a tile step needs of a list.  Bounded lists (f32 tiles, split planes): a key can change the list only below list_bound -- the
+// smallest key the lane half did NOT nominate.  Exact lists (integer tiles): keys are exact and a lane sees its rows in ascending
+// order, so the list is the lexicographic (key, row) top of its rows and carries no bound; a key enters only below list_last.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ float list_bound(const Top2& s) { return s.d2; }
+template <int KL> __device__ __forceinline__ float list_bound(const TopK<KL>& s) { return s.d[KL]; }
+__device__ __forceinline__ void list_push(Top2& s, float key, uint32_t idx) { top2_push(s, key, idx); }
+template <int KL> __device__ __forceinline__ void list_push(TopK<KL>& s, float key, uint32_t idx) { topk_push(s, key, idx); }
+
+__device__ __forceinline__ float list_last(const Top2& s) { return s.d1; }
+template <int KL> __device__ __forceinline__ float list_last(const TopK<KL>& s) { return s.d[KL - 1]; }
+__device__ __forceinline__ void list_push_exact(Top2& s, float key, uint32_t idx) { tope_push(s, key, idx); }
+template <int KL> __device__ __forceinline__ void list_push_exact(TopK<KL>& s, float key, uint32_t idx) { topk_push_exact(s, key, idx); }
+
+// Does the policy test each key with a ballot of its own before the push?  A K-list insert is 3 KL instructions and always is;
+// Top2's 8-instruction push runs unconditionally behind the slice test -- except on the integer tiles up to 128 dimensions, where
+// usually ONE of four keys improves (the 16-step body of D = 256 stays with unconditional pushes: the compiler gives up unrolling the
+// larger one).  The drain of the last tile, written out in each kernel, tests as the list does on the f32 tiles.
+template <class L> inline constexpr bool kTestsEachKey = true;
+template <> inline constexpr bool kTestsEachKey<Top2> = false;
+template <class L, int GB> inline constexpr bool kTestsEachKeyExact = true;
+template <int GB> inline constexpr bool kTestsEachKeyExact<Top2, GB> = GB <= 8;
+// The minimum of four accumulator values may take the two-instruction asm form (vmin2 / vmin3) from step 1 on: Top2 on the integer
+// tiles, measured; the K-lists keep plain fminf in every step (int_tile_step)
+template <class L> inline constexpr bool kQuadMinAsm = false;
+template <> inline constexpr bool kQuadMinAsm<Top2> = true;
+
+// ------------------------------------------------------------------------------------------------
+// f32 tiles.
+// One dataset tile: MFMAs of tile t into `cur`, while the VALU folds the finished accumulators of
+// tile t-1 (`prev`) into the running lists -- software pipelining inside the wave, so the
+// epilogue issues in the shadow of the 64-cycle MFMAs instead of after them.
+// PIPE (developer A/B, tools/ab_l2.py; the product and every K-list kernel run 3): 1 pipelined epilogue | 2 the same with the issue
+// order pinned | 3 pipelined + wave-wide test-and-skip | 4 = 1 with raised priority around the MFMAs | 9 ablation without epilogue.
+// ------------------------------------------------------------------------------------------------
+template <int G, int NJ, int PF, int PIPE, class L>
+__device__ __forceinline__ void l2_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                             uint32_t soffA, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4],
+                                             const f32x4 (&bq)[NJ][G], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
+                                             L (&st)[NJ], uint32_t prev_rowbase)
+{
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cur[nj][r] = nrm[r >> 2][r & 3];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        const f32x4 a = abuf[g % PF];
+        abuf[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 1024u);
+        if (g == 2) {   // next tile's norms: early, so the wait at the tile boundary finds them landed
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+        }
+        if constexpr (PIPE == 4) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bq[nj][g][cc], cur[nj], 0, 0, 0);
+        if constexpr (PIPE == 4) __builtin_amdgcn_s_setprio(0);
+        // this group's share of the previous tile's 16 accumulator values per query tile
+        if constexpr (PIPE == 9) {
+            // ablation (timing only, results meaningless): keep the accumulators alive, skip the epilogue
+#pragma unroll
+            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj) asm volatile("" ::"v"(prev[nj][r]));
+        } else if constexpr (PIPE == 3) {
+            // test-and-skip: a value can only change a list if it is below that lane's bound; once the
+            // lists have warmed up that is rare, so one wave-wide test guards the whole slice (and, where the policy says so, one
+            // more each key: the insert then runs only when some lane needs it)
+            bool any = false;
+#pragma unroll
+            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < list_bound(st[nj]);
+            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+#pragma unroll
+                for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
+#pragma unroll
+                    for (int nj = 0; nj < NJ; ++nj)
+                        if (!kTestsEachKey<L> || __builtin_amdgcn_ballot_w64(prev[nj][r] < list_bound(st[nj])) != 0ull)
+                            list_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        } else {
+#pragma unroll
+            for (int r = (g * 16) / G; r < ((g + 1) * 16) / G; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+                    list_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+        }
+        if constexpr (PIPE == 2) {
+            // issue order inside the step: MFMA, 3 VALU, MFMA, 3 VALU, ... so the epilogue slice hides
+            // behind the 64-cycle matrix instructions instead of in front of them
+#pragma unroll
+            for (int i = 0; i < 4 * NJ; ++i) {
+                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // 1 MFMA
+                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);   // 3 VALU
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);                // keep each prefetch / epilogue slice in its own step
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// integer fast path (r3dm_set_integer_mfma): the same contraction on v_mfma_f32_32x32x16_bf16.
+// Views whose descriptors are integers of magnitude <= 256 (SIFT bins) are staged a second time as bf16 tiles
+// (ImgDev::tiled16, [tile][16-dim block][lane half][32 rows][8 bf16] -- 16 bytes per lane and step like the f32
+// tiles, half as many steps).  Every value is a bf16, every product and partial sum an integer below 2^24, so the f32
+// accumulators hold exactly the values of the f32 path and of the reference's sum of squared differences
+// (l2_finish_queries re-checks the condition per pair; anything else goes to the exact scan).
+// At 32 cycles per MFMA (16x fewer matrix cycles) the VALU side of l2_tile_step -- 10.7 VALU instructions per MFMA:
+// accumulator init, one compare per key, 8-instruction pushes into (best, runner-up, bound) lists -- would hold the
+// issue port longer than the matrix pipe runs.  Exact keys allow less:
+//   * lists hold (best, runner-up) only.  Keys are exact and every lane sees its rows in increasing index order, so
+//     strict '<' keeps the lexicographic (distance, index) top-2 of the lane's rows, and a lexicographic merge of the
+//     two lane halves IS the exact top-2 -- no certification bound, a third fewer list updates;
+//   * one wave-wide test per FOUR keys of a list (v_min3 + v_min + v_cmp instead of four v_cmp);
+//   * the accumulators start from the norm vector through the MFMA's C operand (8 v_mov_b64 per tile instead of 32 v_mov).
+// Measured (780 pairs of 8192 x 8192 rows): f32 tiles 95.0 ms; this kernel 12.4 ms (12.96 before the per-key tests in the
+// update path) (the f32 kernel's structure on bf16
+// tiles: 14.97 ms; without any epilogue: 11.4 ms).  The shader clock drops from 2.32 GHz (f32 kernel) to 1.84 GHz under
+// the bf16 matrix load (GRBM_GUI_ACTIVE / duration), so 12.4 ms is 56 % of the clocked bf16 peak.  Sharing the dataset
+// tiles of a workgroup through LDS (a quarter of the L1 traffic) measured 16.0 ms against 15.0 ms and was dropped.
+// The K-lists (l2_knnk_int_kernel) fold through the same step: topk_push_exact keeps the lexicographic (key, row) top-KL of a lane
+// half's rows, one wave-wide test per four keys of a list (their minimum against the list's last key), one more per key that is
+// reached, and the insert only when some lane needs it.
+// ABL (developer ablations, timing only): bit 0 = no epilogue, bit 1 = no tile / norm loads.
+// ------------------------------------------------------------------------------------------------
+template <int GB, int NJ, int PF, int ABL, class L>
+__device__ __forceinline__ void int_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                              uint32_t soffA, uint32_t soffN, f32x4 (&abuf)[PF], const f32x16& nrm_cur, f32x16& nrm_next,
+                                              const f32x4 (&bq)[NJ][GB], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
+                                              L (&st)[NJ], uint32_t prev_rowbase)
+{
+    constexpr int NG = 4 * NJ;                             // (list, quad) groups of four keys per tile
+#pragma unroll
+    for (int g = 0; g < GB; ++g) {
+        const f32x4 a = abuf[g % PF];
+        if (ABL < 2) abuf[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 1024u);
+        if (ABL < 2 && g == (GB > 2 ? 2 : GB - 1)) {   // next tile's norms, element 4 qd + k = row 8 qd + 4 h + k: the accumulator layout
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                const f32x4 v = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) nrm_next[4 * qd + k] = v[k];
+            }
+        }
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq[nj][g]),
+                                                              g == 0 ? nrm_cur : cur[nj], 0, 0, 0);
+#pragma unroll
+        for (int gi = (g * NG) / GB; gi < ((g + 1) * NG) / GB; ++gi) {
+            const int nj = gi % NJ, qd = gi / NJ;
+            const float p0 = prev[nj][4 * qd], p1 = prev[nj][4 * qd + 1], p2 = prev[nj][4 * qd + 2], p3 = prev[nj][4 * qd + 3];
+            if constexpr ((ABL & 1) != 0) {
+                asm volatile("" ::"v"(p0), "v"(p1), "v"(p2), "v"(p3));
+            } else {
+                // Step 0 may follow the previous tile's last MFMAs (the writers of p0..p3) closely: its minimum goes through
+                // ordinary fminf so that the compiler's MFMA -> VALU hazard pass sees the read; from step 1 on at least NJ
+                // MFMAs and a sched_barrier lie in between and the two-instruction asm form is safe.  (Measured for Top2 only:
+                // the K-lists take plain fminf in every step.)
+                const float m = (g == 0 || !kQuadMinAsm<L>) ? __builtin_fminf(__builtin_fminf(p0, p1), __builtin_fminf(p2, p3)) : vmin2(vmin3(p0, p1, p2), p3);
+                if (__builtin_amdgcn_ballot_w64(m < list_last(st[nj])) != 0ull) {
+                    // some lane improves on one of the four keys: usually ONE key does, so test each before its push
+                    // (7 instructions for Top2, 3 KL for a K-list) where the policy says so (kTestsEachKeyExact)
+                    constexpr bool each = kTestsEachKeyExact<L, GB>;
+                    const uint32_t rb = prev_rowbase + 8u * (uint32_t)qd;
+                    if (!each || __builtin_amdgcn_ballot_w64(p0 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p0, rb);
+                    if (!each || __builtin_amdgcn_ballot_w64(p1 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p1, rb + 1u);
+                    if (!each || __builtin_amdgcn_ballot_w64(p2 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p2, rb + 2u);
+                    if (!each || __builtin_amdgcn_ballot_w64(p3 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p3, rb + 3u);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// split-f16 planes (the format and its error bound: kernels_match_16bit.hip, above stage_split_kernel).  x 2^split_k = hi + lo,
+// a.q ~ al.qh + ah.ql + ah.qh: three MFMAs per 16 dimensions, keys in units of sI sJ (cscale).  The wave's query hi fragments sit
+// in registers (bqh), their lo fragments in its own LDS slice (bl_lds: written once, read by the same wave only).
+// ------------------------------------------------------------------------------------------------
+template <int GB, int NJ, int PF, class L>
+__device__ __forceinline__ void split_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                uint32_t soffA, uint32_t soffN, f32x4 (&ah)[PF], f32x4 (&al)[PF], f32x4 (&nrm)[4], float cscale,
+                                                const f32x4 (&bqh)[NJ][GB], const f32x4* __restrict__ bl_lds, f32x16 (&cur)[NJ],
+                                                const f32x16 (&prev)[NJ], L (&st)[NJ], uint32_t prev_rowbase)
+{
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const float v = nrm[r >> 2][r & 3] * cscale;       // ||a||^2 in key units (sI sJ); +inf for padding rows
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) cur[nj][r] = v;
+    }
+#pragma unroll
+    for (int g = 0; g < GB; ++g) {
+        const f16x8 a_hi = __builtin_bit_cast(f16x8, ah[g % PF]);
+        const f16x8 a_lo = __builtin_bit_cast(f16x8, al[g % PF]);
+        ah[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 2048u);
+        al[g % PF] = bload16(ra, voffA, soffA + (uint32_t)g * 2048u + 1024u);
+        if (g == 1) {
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+        }
+        f32x4 bl[NJ];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) bl[nj] = bl_lds[(nj * GB + g) * 64];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, __builtin_bit_cast(f16x8, bl[nj]), cur[nj], 0, 0, 0);
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
+        // this block's share of the previous tile's keys: wave-wide test-and-skip, as in l2_tile_step<PIPE 3>
+        bool any = false;
+#pragma unroll
+        for (int r = (g * 16) / GB; r < ((g + 1) * 16) / GB; ++r)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < list_bound(st[nj]);
+        if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+#pragma unroll
+            for (int r = (g * 16) / GB; r < ((g + 1) * 16) / GB; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+                    if (!kTestsEachKey<L> || __builtin_amdgcn_ballot_w64(prev[nj][r] < list_bound(st[nj])) != 0ull)
+                        list_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// -2 x (integer, |x| <= 256) is a bf16 again: both halves of a packed pair
+__device__ __forceinline__ uint32_t bf16x2_times_m2(uint32_t w)
+{
+    const float lo = __uint_as_float(w << 16) * -2.0f, hi = __uint_as_float(w & 0xFFFF0000u) * -2.0f;
+    return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xFFFF0000u);
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grid of a 2-NN launch, the host mirror of the kernels' workgroup -> (pair, query block) decode (l2_knn2_mfma_kernel):
+// 4 waves x nj query tiles x 32 queries per workgroup; with xcd_map the pair count is rounded up to the 8 XCDs.  Fills P.qb_per_pair
+// and P.xcd_map and returns true with the grid to launch; false with `status` = hipSuccess (an empty launch) or hipErrorInvalidValue
+// (a grid beyond 2^32 work-items).
+// ------------------------------------------------------------------------------------------------
+inline bool pair_grid(MatchParams& P, uint32_t max_nj_tiles, uint32_t nj, uint32_t xcd_map, uint32_t& grid, hipError_t& status)
+{
+    const uint32_t tiles_per_wg = 4u * nj;
+    P.qb_per_pair = (max_nj_tiles + tiles_per_wg - 1) / tiles_per_wg;
+    P.xcd_map = xcd_map;
+    const uint64_t grid64 = (uint64_t)(xcd_map ? (P.n_pairs + 7u) / 8u * 8u : P.n_pairs) * P.qb_per_pair;
+    status = grid64 > kMaxBlocksOf256 ? hipErrorInvalidValue : hipSuccess;
+    if (grid64 == 0 || grid64 > kMaxBlocksOf256) return false;
+    grid = (uint32_t)grid64;
+    return true;
+}
+
+// ---- host side of the K-list launchers
+// KL is the list depth a kernel is built with: 4 for k <= 4, 8 above (k <= R3DM_KNN_MAX is the caller's check).  f(KL) launches.
+template <class F>
+inline hipError_t dispatch_kl(uint32_t k, F&& f)
+{
+    return k <= 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 8>{});
+}
+
+// the nominators address a dataset through 32-bit buffer offsets: its tiles and both slacks must end below 2^31 - 1 bytes
+inline bool tiles_within_reach(uint32_t n_tiles, uint32_t tile_bytes)
+{
+    return (uint64_t)n_tiles * tile_bytes + 2ull * kSlackBytes < 0x7FFFFFFFull;
+}
+
+}  // namespace r3dm

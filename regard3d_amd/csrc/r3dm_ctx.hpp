@@ -1,6 +1,7 @@
 // r3dm_ctx.hpp -- host-side state shared by the translation units of libr3dm.so (not part of the public ABI).
 //   api_core.cpp      context, views (staging), match-graph objects, matches.* files
-//   api_match.cpp     exhaustive and graph-based putative matching
+//   api_match.cpp     exhaustive and graph-based putative matching: 2-NN batches (run_match_batch), k-NN (run_knn_batch), one
+//                     certificate slack (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
 //   api_filter.cpp    AC-RANSAC geometric filters (F, E, H)
 //   api_features.cpp  Fast-A-KAZE detection, MLDB / LIOP description, the features work item
 #pragma once

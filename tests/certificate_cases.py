@@ -5,7 +5,7 @@ the nominees in the reference arithmetic and keeps them only if
 
     eb < (bound + ||q||^2) - slack,        slack = err_scale (max||a||^2 + ||q||^2) + slack_abs
 
-(kernels_match_common.hpp, l2_finish_queries; err_scale: api_match.cpp, run_match_batch).  The cases here put views where the key's
+(kernels_match_common.hpp, l2_finish_queries; err_scale: api_match.cpp, cert_slack_factor).  The cases here put views where the key's
 rounding error is of the order of the gap between the runner-up and the third row -- norms much larger than distances -- which is
 where a wrong slack, a wrong max||a||^2 or a wrong bound gives a wrong answer instead of a slow one.
 
