@@ -10,8 +10,6 @@
 #include <cmath>
 #include <random>
 
-extern "C" int r3dm_graph_merge(const r3dm_graph* const* parts, uint32_t n_parts, r3dm_graph** out);
-
 // src/R3DComputeMatches.cpp:533-565: (efConstruction, ef, M) = 112 / 5 / 5, 112 / 10 / 15, 100 / 15 / 19
 extern "C" int r3dm_hnsw_preset(int preset, r3dm_hnsw_params* out)
 {
@@ -154,90 +152,46 @@ static HnswView view_of(const HostImage& h)
 static int run_hnsw_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, uint32_t ef, r3dm_graph* g,
                           int32_t* knn_idx_host, float* knn_dist_host)
 {
-    const uint32_t P = (uint32_t)jobs.size();
-    if (P == 0) return R3DM_OK;
-    {   // queries and index rows are gathered from the row-major rows
-        std::vector<uint32_t> slots;
-        for (const PairJob& j : jobs) { slots.push_back(j.sI); slots.push_back(j.sJ); }
-        const int rcl = ensure_layouts(c, slots, kLayRows);
-        if (rcl != R3DM_OK) return rcl;
-    }
-    uint32_t max_nJ = 0, max_nI = 0;
-    uint64_t n_queries = 0;
-    for (const PairJob& j : jobs) {
-        max_nI = std::max(max_nI, c->imgs[j.sI]->n);
-        max_nJ = std::max(max_nJ, c->imgs[j.sJ]->n);
-        n_queries += c->imgs[j.sJ]->n;
-    }
-    const uint32_t dim = c->imgs[jobs[0].sI]->dim;
-    const uint32_t q_stride = std::max<uint32_t>(32, (max_nJ + 31) / 32 * 32);
-    const uint32_t sort_cap = std::min<uint32_t>(16384, std::max<uint32_t>(8, next_pow2(q_stride)));
-    std::vector<uint2> hp(P);
-    std::vector<HnswSearchJob> sj(P);
     bool rows8 = true;                                        // every index view of the batch holds its byte rows (integers 0 .. 255: SIFT bins)
-    for (uint32_t p = 0; p < P; ++p) {
-        hp[p] = make_uint2(jobs[p].sI, jobs[p].sJ);
-        sj[p].ix = view_of(*c->imgs[jobs[p].sI]);
-        sj[p].query = c->imgs[jobs[p].sJ]->rows.as<float>();
-        sj[p].nq = c->imgs[jobs[p].sJ]->n;
-        sj[p].out_base = p * q_stride;
-        rows8 = rows8 && sj[p].ix.rows8 != nullptr;
-    }
-    R3DM_HIP(c, c->d_pairs.ensure(sizeof(uint2) * P));
-    R3DM_HIP(c, c->h_jobs.ensure(sizeof(HnswSearchJob) * P));
-    R3DM_HIP(c, hipMemcpyAsync(c->d_pairs.p, hp.data(), sizeof(uint2) * P, hipMemcpyHostToDevice, c->stream));
-    R3DM_HIP(c, hipMemcpyAsync(c->h_jobs.p, sj.data(), sizeof(HnswSearchJob) * P, hipMemcpyHostToDevice, c->stream));
-    const uint64_t total_slots = (uint64_t)P * q_stride;
-    R3DM_HIP(c, c->d_nn.ensure((size_t)total_slots * 4));
-    R3DM_HIP(c, c->d_cnt.ensure(64));
-    if (knn_idx_host) {
-        R3DM_HIP(c, c->d_knn_idx.ensure((size_t)total_slots * 8));
-        R3DM_HIP(c, c->d_knn_dist.ensure((size_t)total_slots * 8));
-    }
-    HnswSearchParams sp{};
-    sp.jobs = c->h_jobs.as<HnswSearchJob>(); sp.n_jobs = P;
-    sp.ef = std::max(ef, 2u);                                  // searchKnn: max(ef_, k)
-    sp.ratio_R = ratio_R;
-    sp.rows8 = rows8 ? 1u : 0u;
-    sp.dense_steps = r3dm_dev_knob("R3DM_HNSW_DENSE_STEPS", 0) ? 1u : 0u;                // developer build: the round-3 stepping, for A/B runs
-    sp.queries_per_wave = (uint32_t)r3dm_dev_knob("R3DM_HNSW_QW", 0);                    // developer build: 1 / 2 / 4 / 8 queries per wavefront
-    sp.nn_idx = c->d_nn.as<uint32_t>();
-    sp.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
-    sp.knn_dist = knn_idx_host ? c->d_knn_dist.as<float>() : nullptr;
-    sp.n_comps = reinterpret_cast<unsigned long long*>(c->d_cnt.as<uint32_t>() + 4);
-    sp.n_overflow = c->d_cnt.as<uint32_t>() + 2;
-    R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
-    unsigned long long comps = 0;
-    // the candidate heap of a query lives in LDS; a query that outgrows it (rare) makes the whole launch run again with twice the room
-    for (uint32_t cand_cap = 256;; cand_cap *= 2) {
-        sp.cand_cap = cand_cap;
-        R3DM_HIP(c, hipMemsetAsync(c->d_cnt.p, 0, 64, c->stream));
-        hipError_t e = launch_hnsw_search(c->stream, sp, max_nJ, max_nI, dim);
-        if (e == hipErrorInvalidValue) { c->err = "HNSW search: unsupported descriptor length (64 / 128 / 144 / 256) or the view / candidate heap exceeds the LDS"; return R3DM_ERR_UNSUPPORTED; }
-        R3DM_HIP(c, e);
-        uint32_t over = 0;
-        R3DM_HIP(c, hipMemcpyAsync(&over, sp.n_overflow, 4, hipMemcpyDeviceToHost, c->stream));
-        R3DM_HIP(c, hipMemcpyAsync(&comps, sp.n_comps, 8, hipMemcpyDeviceToHost, c->stream));
-        R3DM_HIP(c, hipStreamSynchronize(c->stream));
-        c->stats.n_hnsw_launches += 1;
-        if (over == 0) break;
-        c->stats.n_hnsw_retries += 1;
-    }
-    R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
-    R3DM_HIP(c, hipStreamSynchronize(c->stream));
-    const double t_post = now_ms();
-    int rc = finalize_batch(c, jobs, q_stride, sort_cap, n_queries, max_nJ, g, knn_idx_host, knn_dist_host);
-    if (rc != R3DM_OK) return rc;
-    c->stats.ms_wall_match_post += now_ms() - t_post;
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    c->stats.ms_ann_search += ms;
-    c->stats.n_ann_dist += comps;
-    c->stats.n_ann_rows8 += rows8 ? 1 : 0;
-    c->stats.n_match_launches += 1;
-    c->stats.n_pairs += P;
-    c->stats.n_queries += n_queries;
-    return R3DM_OK;
+    const int rc = run_ann_batch(c, jobs, g, knn_idx_host, knn_dist_host, [&](const AnnBatch& b) -> int {
+        std::vector<HnswSearchJob> sj(b.P);
+        for (uint32_t p = 0; p < b.P; ++p) {
+            sj[p].ix = view_of(*c->imgs[jobs[p].sI]);
+            sj[p].query = c->imgs[jobs[p].sJ]->rows.as<float>();
+            sj[p].nq = c->imgs[jobs[p].sJ]->n;
+            sj[p].out_base = p * b.q_stride;
+            rows8 = rows8 && sj[p].ix.rows8 != nullptr;
+        }
+        R3DM_HIP(c, c->h_jobs.ensure(sizeof(HnswSearchJob) * b.P));
+        R3DM_HIP(c, hipMemcpyAsync(c->h_jobs.p, sj.data(), sizeof(HnswSearchJob) * b.P, hipMemcpyHostToDevice, c->stream));
+        HnswSearchParams sp{};
+        sp.jobs = c->h_jobs.as<HnswSearchJob>(); sp.n_jobs = b.P;
+        sp.ef = std::max(ef, 2u);                                  // searchKnn: max(ef_, k)
+        sp.ratio_R = ratio_R;
+        sp.rows8 = rows8 ? 1u : 0u;
+        sp.dense_steps = r3dm_dev_knob("R3DM_HNSW_DENSE_STEPS", 0) ? 1u : 0u;                // developer build: the round-3 stepping, for A/B runs
+        sp.queries_per_wave = (uint32_t)r3dm_dev_knob("R3DM_HNSW_QW", 0);                    // developer build: 1 / 2 / 4 / 8 queries per wavefront
+        sp.nn_idx = b.nn_idx; sp.knn_idx = b.knn_idx; sp.knn_dist = b.knn_dist; sp.n_comps = b.n_comps;
+        sp.n_overflow = c->d_cnt.as<uint32_t>() + 2;
+        // the candidate heap of a query lives in LDS; a query that outgrows it (rare) makes the whole launch run again with twice the room
+        // (and zeroed counters)
+        for (uint32_t cand_cap = 256;; cand_cap *= 2) {
+            sp.cand_cap = cand_cap;
+            if (cand_cap > 256) R3DM_HIP(c, hipMemsetAsync(c->d_cnt.p, 0, 64, c->stream));
+            hipError_t e = launch_hnsw_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim);
+            if (e == hipErrorInvalidValue) { c->err = "HNSW search: unsupported descriptor length (64 / 128 / 144 / 256) or the view / candidate heap exceeds the LDS"; return R3DM_ERR_UNSUPPORTED; }
+            R3DM_HIP(c, e);
+            uint32_t over = 0;
+            R3DM_HIP(c, hipMemcpyAsync(&over, sp.n_overflow, 4, hipMemcpyDeviceToHost, c->stream));
+            R3DM_HIP(c, hipStreamSynchronize(c->stream));          // (sj is a host temporary)
+            c->stats.n_hnsw_launches += 1;
+            if (over == 0) break;
+            c->stats.n_hnsw_retries += 1;
+        }
+        return R3DM_OK;
+    });
+    if (rc == R3DM_OK && !jobs.empty()) c->stats.n_ann_rows8 += rows8 ? 1 : 0;
+    return rc;
 }
 
 static int r3dm_match_pairs_hnsw_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
@@ -245,69 +199,67 @@ static int r3dm_match_pairs_hnsw_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uin
 {
     if (!c || !out || (n_pairs && !pairs_ij)) return R3DM_ERR_INVALID;
     *out = nullptr;
-    int rc = check_hnsw_params(c, hp);
-    if (rc != R3DM_OK) return rc;
-    R3DM_HIP(c, hipSetDevice(c->device));
-    c->stats = r3dm_stats{};
-    const double t_call = now_ms();
-    std::vector<PairJob> ann_jobs, small_jobs;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint32_t I = pairs_ij[2 * p], J = pairs_ij[2 * p + 1];
-        auto a = c->slot_of.find(I), b = c->slot_of.find(J);
-        if (a == c->slot_of.end() || b == c->slot_of.end()) { c->err = "pair references an unregistered view"; return R3DM_ERR_INVALID; }
-        const HostImage& A = *c->imgs[a->second];
-        const HostImage& B = *c->imgs[b->second];
-        if (A.n == 0 || B.n == 0 || A.dtype != B.dtype || A.dim != B.dim) continue;
+    const int rcp = check_hnsw_params(c, hp);
+    if (rcp != R3DM_OK) return rcp;
+    const float R = dist_ratio * dist_ratio;
+    AnnArm arm;
+    arm.classify = [&](const HostImage& A, bool& index) -> int {
         if (A.dtype == R3DM_BIN || !hnsw_dim_ok(A.dim)) { c->err = "HNSW matching needs F32/U8 descriptors of length 64 / 128 / 144 / 256"; return R3DM_ERR_UNSUPPORTED; }
         if (A.n > (1u << 18)) { c->err = "HNSW matching: more than 262,144 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
-        // an index over a handful of rows finds all of them anyway: small views are scanned
-        if (A.n < kAnnMinRows) small_jobs.push_back({I, J, a->second, b->second});
-        else ann_jobs.push_back({I, J, a->second, b->second});
-    }
-    auto by_pair = [](const PairJob& x, const PairJob& y) { return x.I != y.I ? x.I < y.I : x.J < y.J; };
-    auto same = [](const PairJob& x, const PairJob& y) { return x.I == y.I && x.J == y.J; };
-    for (auto* v : {&ann_jobs, &small_jobs}) { std::sort(v->begin(), v->end(), by_pair); v->erase(std::unique(v->begin(), v->end(), same), v->end()); }
-    const float R = dist_ratio * dist_ratio;
-
-    r3dm_graph ga, gs;
-    ga.offsets.push_back(0); gs.offsets.push_back(0);
-    // (r3dm_set_device_graphs) the two part graphs are merged on the host: a device mirror survives that only when one part is the whole
-    // result -- then it is built and handed over; with both kinds of pairs present no mirror is built at all (it would be dropped)
-    PartMirrorGuard mirror_guard(c, !ann_jobs.empty() && !small_jobs.empty());
-    if (!ann_jobs.empty()) {
+        index = A.n >= kAnnMinRows;                          // an index over a handful of rows finds all of them anyway: small views are scanned
+        return R3DM_OK;
+    };
+    arm.ensure = [&](const std::vector<PairJob>& jobs) {
         std::vector<uint32_t> slots;
-        for (const PairJob& j : ann_jobs) slots.push_back(j.sI);
-        rc = ensure_hnsw_indices(c, slots, *hp);
-        if (rc != R3DM_OK) return rc;
-    }
-    size_t start = 0;
-    while (start < ann_jobs.size()) {
-        const uint32_t dim = c->imgs[ann_jobs[start].sI]->dim;
-        size_t end = start;
-        uint32_t max_n = 0;
-        while (end < ann_jobs.size() && end - start < 65535) {
-            if (c->imgs[ann_jobs[end].sI]->dim != dim) break;
-            const uint32_t mn = std::max(max_n, c->imgs[ann_jobs[end].sJ]->n);
-            const uint64_t s = (uint64_t)(end - start + 1) * ((mn + 31) / 32 * 32);
-            if (end > start && (s * 4 > (3ull << 30) || s / 4 > kMaxBlocksOf256 - 4096)) break;
-            max_n = mn; ++end;
-        }
-        std::vector<PairJob> batch(ann_jobs.begin() + start, ann_jobs.begin() + end);
-        rc = run_hnsw_batch(c, batch, R, hp->ef, &ga, nullptr, nullptr);
-        if (rc != R3DM_OK) return rc;
-        start = end;
-    }
-    rc = run_scanned_pairs(c, small_jobs, R, &gs);
-    if (rc != R3DM_OK) return rc;
-    rc = merge_parts_keep_mirror(ga, gs, out);
-    c->stats.ms_wall_match = now_ms() - t_call;
-    return rc;
+        for (const PairJob& j : jobs) slots.push_back(j.sI);
+        return ensure_hnsw_indices(c, slots, *hp);
+    };
+    arm.run_batch = [&](const std::vector<PairJob>& batch, r3dm_graph* g) { return run_hnsw_batch(c, batch, R, hp->ef, g, nullptr, nullptr); };
+    arm.one_dim_per_chunk = true;
+    arm.max_chunk_pairs = 65535;
+    return match_collection_ann(c, pairs_ij, n_pairs, R, arm, out);
 }
 
 extern "C" int r3dm_match_pairs_hnsw(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
                                      const r3dm_hnsw_params* hp, r3dm_graph** out)
 {
     return r3dm_guarded(c, [&]() -> int { return r3dm_match_pairs_hnsw_impl(c, pairs_ij, n_pairs, dist_ratio, hp, out); });
+}
+
+// an index handed over as arrays (e.g. written by hnswlib itself) becomes the index of the view in `h`, once its arrays are found sound
+static int adopt_hnsw_arrays(r3dm_ctx* c, HostImage& h, uint32_t n_dataset, const r3dm_hnsw_arrays* ix)
+{
+    const uint32_t M = ix->M;
+    bool ok = M >= 2 && M <= 32 && ix->links0 && ix->up_off && ix->enterpoint >= 0 && (uint32_t)ix->enterpoint < n_dataset &&
+              ix->maxlevel >= 0 && (ix->up_rows == 0 || ix->up_links);
+    for (uint32_t i = 0; ok && i < n_dataset; ++i) {
+        const int32_t* l = ix->links0 + (size_t)i * (1 + 2 * M);
+        ok = l[0] >= 0 && (uint32_t)l[0] <= 2 * M && ix->up_off[i] >= 0 && ix->up_off[i] <= ix->up_off[i + 1] && (uint32_t)ix->up_off[i + 1] <= ix->up_rows;
+        for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
+    }
+    for (uint32_t r = 0; ok && r < ix->up_rows; ++r) {
+        const int32_t* l = ix->up_links + (size_t)r * (1 + M);
+        ok = l[0] >= 0 && (uint32_t)l[0] <= M;
+        for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
+    }
+    // the descent reads layer L of every row it reaches there: the rows linked on a layer must own that layer
+    if (ok && (uint32_t)(ix->up_off[ix->enterpoint + 1] - ix->up_off[ix->enterpoint]) < (uint32_t)ix->maxlevel) ok = false;
+    for (uint32_t i = 0; ok && i < n_dataset; ++i)
+        for (int32_t L = 1; ok && L <= ix->up_off[i + 1] - ix->up_off[i]; ++L) {
+            const int32_t* l = ix->up_links + ((size_t)ix->up_off[i] + (uint32_t)(L - 1)) * (1 + M);
+            for (int32_t k = 0; ok && k < l[0]; ++k) ok = ix->up_off[l[1 + k] + 1] - ix->up_off[l[1 + k]] >= L;
+        }
+    if (!ok) { c->err = "r3dm_hnsw_knn2_on_index: malformed index arrays"; return R3DM_ERR_INVALID; }
+    hipError_t e = h.hnsw_l0.ensure((size_t)n_dataset * (1 + 2 * M) * 4);
+    if (e == hipSuccess) e = h.hnsw_up_off.ensure(((size_t)n_dataset + 1) * 4);
+    if (e == hipSuccess) e = h.hnsw_up.ensure((size_t)std::max(ix->up_rows, 1u) * (1 + M) * 4);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_l0.p, ix->links0, (size_t)n_dataset * (1 + 2 * M) * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_up_off.p, ix->up_off, ((size_t)n_dataset + 1) * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && ix->up_rows) e = hipMemcpyAsync(h.hnsw_up.p, ix->up_links, (size_t)ix->up_rows * (1 + M) * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) { c->err = std::string("r3dm_hnsw_knn2_on_index: ") + hipGetErrorString(e); return R3DM_ERR_HIP; }
+    h.hnsw_M = M; h.hnsw_up_rows = ix->up_rows; h.hnsw_enter = ix->enterpoint; h.hnsw_maxlevel = ix->maxlevel;
+    return R3DM_OK;
 }
 
 // two private slots: dataset (+ index) and query
@@ -318,50 +270,12 @@ static int hnsw_knn2_common(r3dm_ctx* c, const float* dataset, uint32_t n_datase
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;
     if (!hnsw_dim_ok(dim)) { c->err = "HNSW matching needs descriptors of length 64 / 128 / 144 / 256"; return R3DM_ERR_UNSUPPORTED; }
     if (n_dataset > (1u << 18)) { c->err = "HNSW matching: more than 262,144 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
-    R3DM_HIP(c, hipSetDevice(c->device));
-    PrivateSlots s(c, 2);
-    int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 1, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
-    if (rc != R3DM_OK) return rc;
-    CallCounters counters(c, {&r3dm_stats::n_ann_dist, &r3dm_stats::n_hnsw_launches, &r3dm_stats::n_hnsw_retries},
-                          {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
-    if (ix) {                                                  // an index handed over as arrays (e.g. written by hnswlib itself)
-        const uint32_t M = ix->M;
-        bool ok = M >= 2 && M <= 32 && ix->links0 && ix->up_off && ix->enterpoint >= 0 && (uint32_t)ix->enterpoint < n_dataset &&
-                  ix->maxlevel >= 0 && (ix->up_rows == 0 || ix->up_links);
-        for (uint32_t i = 0; ok && i < n_dataset; ++i) {
-            const int32_t* l = ix->links0 + (size_t)i * (1 + 2 * M);
-            ok = l[0] >= 0 && (uint32_t)l[0] <= 2 * M && ix->up_off[i] >= 0 && ix->up_off[i] <= ix->up_off[i + 1] && (uint32_t)ix->up_off[i + 1] <= ix->up_rows;
-            for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
-        }
-        for (uint32_t r = 0; ok && r < ix->up_rows; ++r) {
-            const int32_t* l = ix->up_links + (size_t)r * (1 + M);
-            ok = l[0] >= 0 && (uint32_t)l[0] <= M;
-            for (int32_t k = 0; ok && k < l[0]; ++k) ok = l[1 + k] >= 0 && (uint32_t)l[1 + k] < n_dataset;
-        }
-        // the descent reads layer L of every row it reaches there: the rows linked on a layer must own that layer
-        if (ok && (uint32_t)(ix->up_off[ix->enterpoint + 1] - ix->up_off[ix->enterpoint]) < (uint32_t)ix->maxlevel) ok = false;
-        for (uint32_t i = 0; ok && i < n_dataset; ++i)
-            for (int32_t L = 1; ok && L <= ix->up_off[i + 1] - ix->up_off[i]; ++L) {
-                const int32_t* l = ix->up_links + ((size_t)ix->up_off[i] + (uint32_t)(L - 1)) * (1 + M);
-                for (int32_t k = 0; ok && k < l[0]; ++k) ok = ix->up_off[l[1 + k] + 1] - ix->up_off[l[1 + k]] >= L;
-            }
-        if (!ok) { c->err = "r3dm_hnsw_knn2_on_index: malformed index arrays"; return R3DM_ERR_INVALID; }
-        HostImage& h = *c->imgs[s[0]];
-        hipError_t e = h.hnsw_l0.ensure((size_t)n_dataset * (1 + 2 * M) * 4);
-        if (e == hipSuccess) e = h.hnsw_up_off.ensure(((size_t)n_dataset + 1) * 4);
-        if (e == hipSuccess) e = h.hnsw_up.ensure((size_t)std::max(ix->up_rows, 1u) * (1 + M) * 4);
-        if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_l0.p, ix->links0, (size_t)n_dataset * (1 + 2 * M) * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(h.hnsw_up_off.p, ix->up_off, ((size_t)n_dataset + 1) * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && ix->up_rows) e = hipMemcpyAsync(h.hnsw_up.p, ix->up_links, (size_t)ix->up_rows * (1 + M) * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) { c->err = std::string("r3dm_hnsw_knn2_on_index: ") + hipGetErrorString(e); return R3DM_ERR_HIP; }
-        h.hnsw_M = M; h.hnsw_up_rows = ix->up_rows; h.hnsw_enter = ix->enterpoint; h.hnsw_maxlevel = ix->maxlevel;
-    } else {
-        rc = ensure_hnsw_indices(c, {s[0]}, *hp);
-        if (rc != R3DM_OK) return rc;
-    }
-    return run_hnsw_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, hp->ef, nullptr, out_idx, out_dist);
+    return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, 0, 1,
+                            {&r3dm_stats::n_ann_dist, &r3dm_stats::n_hnsw_launches, &r3dm_stats::n_hnsw_retries},
+                            {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search}, [&](uint32_t sI, uint32_t sJ) -> int {
+        const int rc = ix ? adopt_hnsw_arrays(c, *c->imgs[sI], n_dataset, ix) : ensure_hnsw_indices(c, {sI}, *hp);
+        return rc != R3DM_OK ? rc : run_hnsw_batch(c, {{0, 1, sI, sJ}}, 1.0f, hp->ef, nullptr, out_idx, out_dist);
+    });
 }
 
 extern "C" int r3dm_hnsw_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,

@@ -10,8 +10,6 @@
 
 #include <cmath>
 
-extern "C" int r3dm_graph_merge(const r3dm_graph* const* parts, uint32_t n_parts, r3dm_graph** out);
-
 extern "C" int r3dm_mrpt_preset(r3dm_mrpt_params* out)
 {
     if (!out) return R3DM_ERR_INVALID;
@@ -168,74 +166,29 @@ static MrptView mrpt_view_of(const HostImage& h)
 static int run_mrpt_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio, uint32_t votes, r3dm_graph* g,
                           int32_t* knn_idx_host, float* knn_dist_host)
 {
-    const uint32_t P = (uint32_t)jobs.size();
-    if (P == 0) return R3DM_OK;
-    {   // queries and index rows are gathered from the row-major rows
-        std::vector<uint32_t> slots;
-        for (const PairJob& j : jobs) { slots.push_back(j.sI); slots.push_back(j.sJ); }
-        const int rcl = ensure_layouts(c, slots, kLayRows);
-        if (rcl != R3DM_OK) return rcl;
-    }
-    uint32_t max_nJ = 0, max_nI = 0, max_pool = 0, elected_cap = 0;
-    uint64_t n_queries = 0;
-    for (const PairJob& j : jobs) {
-        const HostImage& I = *c->imgs[j.sI];
-        max_nI = std::max(max_nI, I.n);
-        max_nJ = std::max(max_nJ, c->imgs[j.sJ]->n);
-        n_queries += c->imgs[j.sJ]->n;
-        max_pool = std::max(max_pool, I.mrpt_trees * I.mrpt_depth);
-        elected_cap = std::max<uint32_t>(elected_cap, mrpt_elected_cap(I.n, I.mrpt_trees, I.mrpt_depth, votes));
-    }
-    const uint32_t q_stride = std::max<uint32_t>(32, (max_nJ + 31) / 32 * 32);
-    const uint32_t sort_cap = std::min<uint32_t>(16384, std::max<uint32_t>(8, next_pow2(q_stride)));
-    std::vector<uint2> hp(P);
-    std::vector<MrptQueryJob> sj(P);
-    for (uint32_t p = 0; p < P; ++p) {
-        hp[p] = make_uint2(jobs[p].sI, jobs[p].sJ);
-        sj[p].ix = mrpt_view_of(*c->imgs[jobs[p].sI]);
-        sj[p].query = c->imgs[jobs[p].sJ]->rows.as<float>();
-        sj[p].nq = c->imgs[jobs[p].sJ]->n;
-        sj[p].out_base = p * q_stride;
-    }
-    R3DM_HIP(c, c->d_pairs.ensure(sizeof(uint2) * P));
-    R3DM_HIP(c, c->h_jobs.ensure(sizeof(MrptQueryJob) * P));
-    R3DM_HIP(c, hipMemcpyAsync(c->d_pairs.p, hp.data(), sizeof(uint2) * P, hipMemcpyHostToDevice, c->stream));
-    R3DM_HIP(c, hipMemcpyAsync(c->h_jobs.p, sj.data(), sizeof(MrptQueryJob) * P, hipMemcpyHostToDevice, c->stream));
-    const uint64_t total_slots = (uint64_t)P * q_stride;
-    R3DM_HIP(c, c->d_nn.ensure((size_t)total_slots * 4));
-    R3DM_HIP(c, c->d_cnt.ensure(64));
-    if (knn_idx_host) {
-        R3DM_HIP(c, c->d_knn_idx.ensure((size_t)total_slots * 8));
-        R3DM_HIP(c, c->d_knn_dist.ensure((size_t)total_slots * 8));
-    }
-    MrptQueryParams qp{};
-    qp.jobs = c->h_jobs.as<MrptQueryJob>(); qp.n_jobs = P;
-    qp.votes = votes; qp.elected_cap = elected_cap; qp.ratio = ratio;
-    qp.nn_idx = c->d_nn.as<uint32_t>();
-    qp.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
-    qp.knn_dist = knn_idx_host ? c->d_knn_dist.as<float>() : nullptr;
-    qp.n_comps = reinterpret_cast<unsigned long long*>(c->d_cnt.as<uint32_t>() + 4);
-    R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
-    R3DM_HIP(c, hipMemsetAsync(c->d_cnt.p, 0, 64, c->stream));
-    hipError_t e = launch_mrpt_query(c->stream, qp, max_nJ, max_nI, max_pool);
-    if (e == hipErrorInvalidValue) { c->err = "MRPT query: vote bytes + elected list of the largest index view of the batch exceed the 160 KB of LDS a wavefront can have"; return R3DM_ERR_UNSUPPORTED; }
-    R3DM_HIP(c, e);
-    unsigned long long comps = 0;
-    R3DM_HIP(c, hipMemcpyAsync(&comps, qp.n_comps, 8, hipMemcpyDeviceToHost, c->stream));
-    R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
-    R3DM_HIP(c, hipStreamSynchronize(c->stream));              // hp / sj are host temporaries
-    const double t_post = now_ms();
-    int rc = finalize_batch(c, jobs, q_stride, sort_cap, n_queries, max_nJ, g, knn_idx_host, knn_dist_host);
-    if (rc != R3DM_OK) return rc;
-    c->stats.ms_wall_match_post += now_ms() - t_post;
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    c->stats.ms_ann_search += ms;
-    c->stats.n_ann_dist += comps;
-    c->stats.n_match_launches += 1;
-    c->stats.n_pairs += P;
-    c->stats.n_queries += n_queries;
-    return R3DM_OK;
+    std::vector<MrptQueryJob> sj(jobs.size());               // outlives the frame's synchronisation
+    return run_ann_batch(c, jobs, g, knn_idx_host, knn_dist_host, [&](const AnnBatch& b) -> int {
+        uint32_t max_pool = 0, elected_cap = 0;
+        for (uint32_t p = 0; p < b.P; ++p) {
+            const HostImage& I = *c->imgs[jobs[p].sI];
+            max_pool = std::max(max_pool, I.mrpt_trees * I.mrpt_depth);
+            elected_cap = std::max<uint32_t>(elected_cap, mrpt_elected_cap(I.n, I.mrpt_trees, I.mrpt_depth, votes));
+            sj[p].ix = mrpt_view_of(I);
+            sj[p].query = c->imgs[jobs[p].sJ]->rows.as<float>();
+            sj[p].nq = c->imgs[jobs[p].sJ]->n;
+            sj[p].out_base = p * b.q_stride;
+        }
+        R3DM_HIP(c, c->h_jobs.ensure(sizeof(MrptQueryJob) * b.P));
+        R3DM_HIP(c, hipMemcpyAsync(c->h_jobs.p, sj.data(), sizeof(MrptQueryJob) * b.P, hipMemcpyHostToDevice, c->stream));
+        MrptQueryParams qp{};
+        qp.jobs = c->h_jobs.as<MrptQueryJob>(); qp.n_jobs = b.P;
+        qp.votes = votes; qp.elected_cap = elected_cap; qp.ratio = ratio;
+        qp.nn_idx = b.nn_idx; qp.knn_idx = b.knn_idx; qp.knn_dist = b.knn_dist; qp.n_comps = b.n_comps;
+        const hipError_t e = launch_mrpt_query(c->stream, qp, b.max_nJ, b.max_nI, max_pool);
+        if (e == hipErrorInvalidValue) { c->err = "MRPT query: vote bytes + elected list of the largest index view of the batch exceed the 160 KB of LDS a wavefront can have"; return R3DM_ERR_UNSUPPORTED; }
+        R3DM_HIP(c, e);
+        return R3DM_OK;
+    });
 }
 
 static int r3dm_match_pairs_mrpt_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
@@ -243,59 +196,25 @@ static int r3dm_match_pairs_mrpt_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uin
 {
     if (!c || !out || (n_pairs && !pairs_ij)) return R3DM_ERR_INVALID;
     *out = nullptr;
-    int rc = check_mrpt_params(c, mp);
-    if (rc != R3DM_OK) return rc;
-    R3DM_HIP(c, hipSetDevice(c->device));
-    c->stats = r3dm_stats{};
-    const double t_call = now_ms();
-    std::vector<PairJob> ann_jobs, small_jobs;
-    for (uint64_t p = 0; p < n_pairs; ++p) {
-        const uint32_t I = pairs_ij[2 * p], J = pairs_ij[2 * p + 1];
-        auto a = c->slot_of.find(I), b = c->slot_of.find(J);
-        if (a == c->slot_of.end() || b == c->slot_of.end()) { c->err = "pair references an unregistered view"; return R3DM_ERR_INVALID; }
-        const HostImage& A = *c->imgs[a->second];
-        const HostImage& B = *c->imgs[b->second];
-        if (A.n == 0 || B.n == 0 || A.dtype != B.dtype || A.dim != B.dim) continue;
+    const int rcp = check_mrpt_params(c, mp);
+    if (rcp != R3DM_OK) return rcp;
+    AnnArm arm;
+    arm.classify = [&](const HostImage& A, bool& index) -> int {
         if (A.dtype == R3DM_BIN || !mrpt_dim_ok(A.dim)) { c->err = "MRPT matching needs F32/U8 descriptors of a length that is a multiple of 4, at most 512"; return R3DM_ERR_UNSUPPORTED; }
         if (A.n > (1u << 17)) { c->err = "MRPT matching: more than 131,072 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
-        if (A.n < kAnnMinRows || !mrpt_query_fits_lds(A.n, *mp)) small_jobs.push_back({I, J, a->second, b->second});    // a forest over a handful of rows, or a view whose vote table no wavefront's LDS holds: such views are scanned
-        else ann_jobs.push_back({I, J, a->second, b->second});
-    }
-    auto by_pair = [](const PairJob& x, const PairJob& y) { return x.I != y.I ? x.I < y.I : x.J < y.J; };
-    auto same = [](const PairJob& x, const PairJob& y) { return x.I == y.I && x.J == y.J; };
-    for (auto* v : {&ann_jobs, &small_jobs}) { std::sort(v->begin(), v->end(), by_pair); v->erase(std::unique(v->begin(), v->end(), same), v->end()); }
-
-    r3dm_graph ga, gs;
-    ga.offsets.push_back(0); gs.offsets.push_back(0);
-    // (r3dm_set_device_graphs) the two part graphs are merged on the host: a device mirror survives that only when one part is the whole
-    // result -- then it is built and handed over; with both kinds of pairs present no mirror is built at all (it would be dropped)
-    PartMirrorGuard mirror_guard(c, !ann_jobs.empty() && !small_jobs.empty());
-    if (!ann_jobs.empty()) {
+        // a forest over a handful of rows, or a view whose vote table no wavefront's LDS holds: such views are scanned
+        index = !(A.n < kAnnMinRows || !mrpt_query_fits_lds(A.n, *mp));
+        return R3DM_OK;
+    };
+    arm.ensure = [&](const std::vector<PairJob>& jobs) {
         std::vector<uint32_t> slots;
-        for (const PairJob& j : ann_jobs) slots.push_back(j.sI);
-        rc = ensure_mrpt_indices(c, slots, *mp);
-        if (rc != R3DM_OK) return rc;
-    }
-    size_t start = 0;
-    while (start < ann_jobs.size()) {
-        size_t end = start;
-        uint32_t max_n = 0;
-        while (end < ann_jobs.size() && end - start < 65535) {
-            const uint32_t mn = std::max(max_n, c->imgs[ann_jobs[end].sJ]->n);
-            const uint64_t s = (uint64_t)(end - start + 1) * ((mn + 31) / 32 * 32);
-            if (end > start && (s * 4 > (3ull << 30) || s / 4 > kMaxBlocksOf256 - 4096)) break;
-            max_n = mn; ++end;
-        }
-        std::vector<PairJob> batch(ann_jobs.begin() + start, ann_jobs.begin() + end);
-        rc = run_mrpt_batch(c, batch, dist_ratio, mp->votes, &ga, nullptr, nullptr);
-        if (rc != R3DM_OK) return rc;
-        start = end;
-    }
-    rc = run_scanned_pairs(c, small_jobs, dist_ratio * dist_ratio, &gs);
-    if (rc != R3DM_OK) return rc;
-    rc = merge_parts_keep_mirror(ga, gs, out);
-    c->stats.ms_wall_match = now_ms() - t_call;
-    return rc;
+        for (const PairJob& j : jobs) slots.push_back(j.sI);
+        return ensure_mrpt_indices(c, slots, *mp);
+    };
+    // the query kernel applies the ratio to the square roots it returns; the scanned pairs compare squared distances
+    arm.run_batch = [&](const std::vector<PairJob>& batch, r3dm_graph* g) { return run_mrpt_batch(c, batch, dist_ratio, mp->votes, g, nullptr, nullptr); };
+    arm.max_chunk_pairs = 65535;                             // (no cut on the descriptor length: a job record carries its own)
+    return match_collection_ann(c, pairs_ij, n_pairs, dist_ratio * dist_ratio, arm, out);
 }
 
 extern "C" int r3dm_match_pairs_mrpt(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
@@ -316,15 +235,12 @@ extern "C" int r3dm_mrpt_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_data
         if (n_dataset < kAnnMinRows) { c->err = "r3dm_mrpt_knn2: fewer than 128 rows (such views are scanned: r3dm_knn2)"; return R3DM_ERR_UNSUPPORTED; }
         if (n_dataset > (1u << 17)) { c->err = "MRPT matching: more than 131,072 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
         if (!mrpt_query_fits_lds(n_dataset, *mp)) { c->err = "r3dm_mrpt_knn2: the vote table of this many rows exceeds a wavefront's LDS with these parameters (such views are scanned: r3dm_knn2)"; return R3DM_ERR_UNSUPPORTED; }
-        R3DM_HIP(c, hipSetDevice(c->device));
-        PrivateSlots s(c, 2);
-        rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
-        if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 1, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
-        if (rc != R3DM_OK) return rc;
-        CallCounters counters(c, {&r3dm_stats::n_ann_dist}, {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
-        rc = ensure_mrpt_indices(c, {s[0]}, *mp);
-        if (rc != R3DM_OK) return rc;
-        return run_mrpt_batch(c, {{0, 1, s[0], s[1]}}, 1.0f, mp->votes, nullptr, out_idx, out_dist);
+        return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, 0, 1, {&r3dm_stats::n_ann_dist},
+                                {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search}, [&](uint32_t sI, uint32_t sJ) -> int {
+            const int rci = ensure_mrpt_indices(c, {sI}, *mp);
+            if (rci != R3DM_OK) return rci;
+            return run_mrpt_batch(c, {{0, 1, sI, sJ}}, 1.0f, mp->votes, nullptr, out_idx, out_dist);
+        });
     });
 }
 

@@ -211,8 +211,9 @@ extern "C" int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double 
     return R3DM_OK;
 }
 
-extern "C" int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,
-                                      float dist_ratio, int squared_metric, r3dm_graph** out)
+// the pair list dealt to the devices by rows of I, call(ctx, pairs, n, part) on every device's share, the parts merged by (I, J)
+template <class Call>
+static int multi_match(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs, r3dm_graph** out, Call call)
 {
     if (!m || !out || (n_pairs && !pairs_ij)) return R3DM_ERR_INVALID;
     *out = nullptr;
@@ -224,81 +225,36 @@ extern "C" int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, u
         std::vector<std::vector<uint32_t>> mine(W);
         for (uint64_t p = 0; p < n_pairs; ++p) { mine[owner[p]].push_back(pairs_ij[2 * p]); mine[owner[p]].push_back(pairs_ij[2 * p + 1]); }
         std::vector<r3dm_graph*> parts(W, nullptr);
-        rc = for_each_device(m, [&](uint32_t k, r3dm_ctx* c) {
-            return r3dm_match_pairs(c, mine[k].data(), mine[k].size() / 2, dist_ratio, squared_metric, &parts[k]);
-        });
+        rc = for_each_device(m, [&](uint32_t k, r3dm_ctx* c) { return call(c, mine[k].data(), mine[k].size() / 2, &parts[k]); });
         if (rc == R3DM_OK) rc = r3dm_graph_merge(parts.data(), W, out);
         for (r3dm_graph* g : parts) r3dm_graph_free(g);
         return rc;
     } catch (...) { m->err = "out of host memory"; return R3DM_ERR_NOMEM; }
 }
 
+extern "C" int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,
+                                      float dist_ratio, int squared_metric, r3dm_graph** out)
+{
+    return multi_match(m, pairs_ij, n_pairs, out, [&](r3dm_ctx* c, const uint32_t* p, uint64_t n, r3dm_graph** g) { return r3dm_match_pairs(c, p, n, dist_ratio, squared_metric, g); });
+}
+
+// the approximate matchers: a device builds the index of every image I whose row it owns
 extern "C" int r3dm_multi_match_pairs_kgraph(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
                                              const r3dm_kgraph_params* params, r3dm_graph** out)
 {
-    if (!m || !out || !params || (n_pairs && !pairs_ij)) return R3DM_ERR_INVALID;
-    *out = nullptr;
-    const uint32_t W = (uint32_t)m->ctx.size();
-    try {
-        std::vector<uint32_t> owner(n_pairs);
-        int rc = r3dm_shard_pairs(pairs_ij, n_pairs, W, owner.data());
-        if (rc != R3DM_OK) return rc;
-        std::vector<std::vector<uint32_t>> mine(W);
-        for (uint64_t p = 0; p < n_pairs; ++p) { mine[owner[p]].push_back(pairs_ij[2 * p]); mine[owner[p]].push_back(pairs_ij[2 * p + 1]); }
-        std::vector<r3dm_graph*> parts(W, nullptr);
-        rc = for_each_device(m, [&](uint32_t k, r3dm_ctx* c) {
-            return r3dm_match_pairs_kgraph(c, mine[k].data(), mine[k].size() / 2, dist_ratio, params, &parts[k]);
-        });
-        if (rc == R3DM_OK) rc = r3dm_graph_merge(parts.data(), W, out);
-        for (r3dm_graph* g : parts) r3dm_graph_free(g);
-        return rc;
-    } catch (...) { m->err = "out of host memory"; return R3DM_ERR_NOMEM; }
+    return !params ? R3DM_ERR_INVALID : multi_match(m, pairs_ij, n_pairs, out, [&](r3dm_ctx* c, const uint32_t* p, uint64_t n, r3dm_graph** g) { return r3dm_match_pairs_kgraph(c, p, n, dist_ratio, params, g); });
 }
 
-// the same deal for the HNSW matcher (hnsw_match, matchingAlgorithm 6..8): a device builds the index of every image I whose row it owns
 extern "C" int r3dm_multi_match_pairs_hnsw(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
                                            const r3dm_hnsw_params* params, r3dm_graph** out)
 {
-    if (!m || !out || !params || (n_pairs && !pairs_ij)) return R3DM_ERR_INVALID;
-    *out = nullptr;
-    const uint32_t W = (uint32_t)m->ctx.size();
-    try {
-        std::vector<uint32_t> owner(n_pairs);
-        int rc = r3dm_shard_pairs(pairs_ij, n_pairs, W, owner.data());
-        if (rc != R3DM_OK) return rc;
-        std::vector<std::vector<uint32_t>> mine(W);
-        for (uint64_t p = 0; p < n_pairs; ++p) { mine[owner[p]].push_back(pairs_ij[2 * p]); mine[owner[p]].push_back(pairs_ij[2 * p + 1]); }
-        std::vector<r3dm_graph*> parts(W, nullptr);
-        rc = for_each_device(m, [&](uint32_t k, r3dm_ctx* c) {
-            return r3dm_match_pairs_hnsw(c, mine[k].data(), mine[k].size() / 2, dist_ratio, params, &parts[k]);
-        });
-        if (rc == R3DM_OK) rc = r3dm_graph_merge(parts.data(), W, out);
-        for (r3dm_graph* g : parts) r3dm_graph_free(g);
-        return rc;
-    } catch (...) { m->err = "out of host memory"; return R3DM_ERR_NOMEM; }
+    return !params ? R3DM_ERR_INVALID : multi_match(m, pairs_ij, n_pairs, out, [&](r3dm_ctx* c, const uint32_t* p, uint64_t n, r3dm_graph** g) { return r3dm_match_pairs_hnsw(c, p, n, dist_ratio, params, g); });
 }
 
-// ... and for the MRPT matcher (mrpt_match, matchingAlgorithm 5)
 extern "C" int r3dm_multi_match_pairs_mrpt(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
                                            const r3dm_mrpt_params* params, r3dm_graph** out)
 {
-    if (!m || !out || !params || (n_pairs && !pairs_ij)) return R3DM_ERR_INVALID;
-    *out = nullptr;
-    const uint32_t W = (uint32_t)m->ctx.size();
-    try {
-        std::vector<uint32_t> owner(n_pairs);
-        int rc = r3dm_shard_pairs(pairs_ij, n_pairs, W, owner.data());
-        if (rc != R3DM_OK) return rc;
-        std::vector<std::vector<uint32_t>> mine(W);
-        for (uint64_t p = 0; p < n_pairs; ++p) { mine[owner[p]].push_back(pairs_ij[2 * p]); mine[owner[p]].push_back(pairs_ij[2 * p + 1]); }
-        std::vector<r3dm_graph*> parts(W, nullptr);
-        rc = for_each_device(m, [&](uint32_t k, r3dm_ctx* c) {
-            return r3dm_match_pairs_mrpt(c, mine[k].data(), mine[k].size() / 2, dist_ratio, params, &parts[k]);
-        });
-        if (rc == R3DM_OK) rc = r3dm_graph_merge(parts.data(), W, out);
-        for (r3dm_graph* g : parts) r3dm_graph_free(g);
-        return rc;
-    } catch (...) { m->err = "out of host memory"; return R3DM_ERR_NOMEM; }
+    return !params ? R3DM_ERR_INVALID : multi_match(m, pairs_ij, n_pairs, out, [&](r3dm_ctx* c, const uint32_t* p, uint64_t n, r3dm_graph** g) { return r3dm_match_pairs_mrpt(c, p, n, dist_ratio, params, g); });
 }
 
 // model_kind as in api_filter.cpp: 0 F, 1 H, 2 E.  Putative pairs are dealt longest list first (the AC-RANSAC of a pair

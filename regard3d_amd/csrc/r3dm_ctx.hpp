@@ -1,7 +1,10 @@
 // r3dm_ctx.hpp -- host-side state shared by the translation units of libr3dm.so (not part of the public ABI).
 //   api_core.cpp      context, views (staging), match-graph objects, matches.* files
-//   api_match.cpp     exhaustive and graph-based putative matching: 2-NN batches (run_match_batch), k-NN (run_knn_batch), one
-//                     certificate slack (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
+//   api_match.cpp     exhaustive putative matching: 2-NN batches (run_match_batch), k-NN (run_knn_batch), one certificate slack
+//                     (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
+//   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
+//                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
+//   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules
 //   api_filter.cpp    AC-RANSAC geometric filters (F, E, H)
 //   api_features.cpp  Fast-A-KAZE detection, MLDB / LIOP description, the features work item
 #pragma once
@@ -21,6 +24,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -596,13 +600,6 @@ struct r3dm_index {
 inline void HostImage::mount(r3dm_index* ix) { *this = ix->img; borrowed = true; owner = ix; }
 
 // shared between the translation units
-// part graphs of the approximate matchers (graph-searched pairs + exhaustively scanned small pairs): see their use
-struct PartMirrorGuard {
-    r3dm_ctx* c; bool keep;
-    PartMirrorGuard(r3dm_ctx* c_, bool suppress);
-    ~PartMirrorGuard();
-};
-int merge_parts_keep_mirror(r3dm_graph& ga, r3dm_graph& gs, r3dm_graph** out);
 // (re)writes the table entry of `slot` from its HostImage, statistics included: only for views whose statistics the host holds
 int publish_entry(r3dm_ctx* c, uint32_t slot);
 // the statistics of every view staged since the last call -> HostImage (one read of the table, one synchronisation)
@@ -613,9 +610,50 @@ int ensure_layouts(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t want, bool
 int ensure_layouts_image(r3dm_ctx* c, HostImage& h, uint32_t want);        // (no table entry involved; the caller publishes)
 int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g,
                     int32_t* knn_idx_host, float* knn_dist_host);
-int run_scanned_pairs(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g);
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
                    uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host);
 int ensure_ann_indices(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t K);
 int stage_into_slot(r3dm_ctx* c, uint32_t slot, uint32_t view_id, uint32_t width, uint32_t height,
                     const void* desc, uint32_t n, uint32_t dim, r3dm_dtype dtype, const float* xy);
+
+// ---- the frames of the approximate matchers (api_ann.cpp)
+// first view of a valid pair -> index = searched through the arm's index / scanned exhaustively, or the arm's refusal (c->err set)
+using PairClassifier = std::function<int(const HostImage& A, bool& index)>;
+// pairs_ij -> the jobs of its valid pairs, ordered by (I, J), unique; no classifier: every job is scanned
+int resolve_pairs(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, const PairClassifier& classify,
+                  std::vector<PairJob>& indexed, std::vector<PairJob>& scanned);
+// What a collection call of an arm is made of.  The chunk rules differ on purpose: KGraph and HNSW launch one descriptor length at a
+// time, MRPT's job records carry their own; HNSW and MRPT launch a grid row per pair (65,535 at most), KGraph does not.
+struct AnnArm {
+    PairClassifier classify;
+    std::function<int(const std::vector<PairJob>& indexed)> ensure;                    // layouts + indices of the indexed jobs' views
+    std::function<int(const std::vector<PairJob>& batch, r3dm_graph* g)> run_batch;    // one chunk of them, appended to g
+    bool one_dim_per_chunk = false;
+    size_t max_chunk_pairs = SIZE_MAX;
+};
+// resets c->stats; indexed chunks + scanned pairs (ratio scanned_ratio_R) -> *out, ordered by (I, J)
+int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float scanned_ratio_R, const AnnArm& arm, r3dm_graph** out);
+// What the batch frame hands an arm's launch: the arm uploads its job records, fills its parameter struct and launches on c->stream
+// (the pair table is in c->d_pairs; c->d_cnt is zeroed, n_comps counts the distance evaluations)
+struct AnnBatch {
+    uint32_t P, dim, q_stride, max_nI, max_nJ;
+    uint32_t* nn_idx; int32_t* knn_idx; float* knn_dist; unsigned long long* n_comps;
+};
+int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host,
+                  const std::function<int(const AnnBatch&)>& launch);
+
+// An array entry of an arm (r3dm_kgraph_knn2 and its relatives): two private slots, dataset and query staged as F32 under the view ids
+// (id_i, id_j), the call's counters (CallCounters), then body(slot of the dataset, slot of the queries)
+template <class Body>
+inline int with_staged_pair(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query, uint32_t dim,
+                            uint32_t id_i, uint32_t id_j, std::initializer_list<uint64_t r3dm_stats::*> counts,
+                            std::initializer_list<double r3dm_stats::*> times, Body&& body)
+{
+    R3DM_HIP(c, hipSetDevice(c->device));
+    PrivateSlots s(c, 2);
+    int rc = stage_into_slot(c, s[0], id_i, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], id_j, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
+    if (rc != R3DM_OK) return rc;
+    CallCounters counters(c, counts, times);
+    return body(s[0], s[1]);
+}
