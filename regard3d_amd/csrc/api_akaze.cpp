@@ -1,0 +1,626 @@
+// api_akaze.cpp -- part of the host side of libr3dm.so (see r3dm_ctx.hpp for the file map): keypoint detection.  The frame both detector
+// arms stand in (argument checks, gray-or-BGR upload, INTER_AREA tables, statistics tail, the detect entry over a DetectedBatch, the choice
+// of the arm), then the Fast-A-KAZE arm (kernels_akaze.hip): ak_detect_batch in its phases -- buffers, scale space, detection with regrow,
+// read-back -- and its entries.  The classic arm's launch sequence is api_akaze_classic.cpp; what is shared and what stays per arm:
+// DESIGN.md section 4.21.  There is no CPU fallback in this file: when HIP fails, the call fails.
+#include "r3dm_ctx.hpp"
+
+// ======== the frame of both arms
+// getGaussianKernel(n, sigma, CV_32F) for gaussian_2D_convolutionV2's kernel size rule (nldiffusion_functions.cpp:39-58)
+AkTaps ak_taps(float sigma)
+{
+    AkTaps t{};
+    int k = (int)ceil(2.0f * (1.0f + (sigma - 0.8f) / (0.3f)));
+    if ((k % 2) == 0) k += 1;
+    t.n = k;
+    const double s = sigma;
+    const double scale2X = -0.5 / (s * s);
+    double sum = 0;
+    for (int i = 0; i < k; ++i) {
+        const double x = i - (k - 1) * 0.5;
+        const double v = std::exp(scale2X * x * x);
+        t.k[i] = (float)v;
+        sum += t.k[i];
+    }
+    sum = 1. / sum;
+    for (int i = 0; i < k; ++i) t.k[i] = (float)(t.k[i] * sum);
+    return t;
+}
+
+// fed_is_prime_internal (fed.cpp) of both libraries.  (They form the trial-division bound as sqrt(1.0f + n) and as sqrt(n + 1.0): the
+// same integer for every n the FED cycle lengths can reach)
+bool ak_is_prime(int number)
+{
+    if (number <= 1) return false;
+    if (number == 2 || number == 3 || number == 5 || number == 7) return true;
+    if ((number % 2) == 0 || (number % 3) == 0 || (number % 5) == 0 || (number % 7) == 0) return false;
+    const int upper = (int)sqrt(number + 1.0);
+    for (int divisor = 11; divisor <= upper; divisor += 2) if (number % divisor == 0) return false;
+    return true;
+}
+
+bool detect_args_ok(const r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height)
+{
+    if (!c || B == 0 || (!images && !bgrs)) return false;
+    for (uint32_t b = 0; b < B; ++b) if (!(images ? (const void*)images[b] : (const void*)bgrs[b])) return false;
+    return (uint64_t)width * height <= (1ull << 30) && B <= 4096;
+}
+
+int detect_upload(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, size_t n0, float* gray, unsigned char* stage)
+{
+    hipStream_t st = c->stream;
+    if (images) {
+        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(gray + b * n0, images[b], n0 * 4, hipMemcpyDefault, st));
+    } else {
+        // 8-bit BGR -> float / 255 -> gray
+        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(stage + b * n0 * 4, bgrs[b], n0 * 3, hipMemcpyDefault, st));
+        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, ak_bgr_to_gray(st, stage + b * n0 * 4, gray + b * n0, n0));
+    }
+    return R3DM_OK;
+}
+
+// (its own two buffers, released before it returns: the conversion must not depend on, or disturb, either arm's work images)
+extern "C" int r3dm_gray_from_bgr8(r3dm_ctx* c, const unsigned char* bgr, uint32_t width, uint32_t height, float* gray_out)
+{
+    if (!c || !bgr || !gray_out || !width || !height) return R3DM_ERR_INVALID;
+    R3DM_HIP(c, hipSetDevice(c->device));
+    const size_t n = (size_t)width * height;
+    DevBuf in, out;
+    R3DM_HIP(c, in.ensure(n * 3));
+    R3DM_HIP(c, out.ensure(n * 4));
+    const int rc = detect_upload(c, 1, nullptr, &bgr, n, out.as<float>(), in.as<unsigned char>());
+    if (rc != R3DM_OK) return rc;
+    R3DM_HIP(c, hipMemcpyAsync(gray_out, out.p, n * 4, hipMemcpyDefault, c->stream));
+    R3DM_HIP(c, hipStreamSynchronize(c->stream));
+    in.release(); out.release();
+    return R3DM_OK;
+}
+
+// computeResizeAreaTab (imgproc/resize.cpp) as a CSR over destination cells
+static void ak_area_tab(int ssize, int dsize, std::vector<AkAreaTab>& tab, std::vector<int>& begin)
+{
+    const double scale = (double)ssize / dsize;
+    tab.clear(); begin.assign(dsize + 1, 0);
+    for (int dx = 0; dx < dsize; ++dx) {
+        begin[dx] = (int)tab.size();
+        const double fsx1 = dx * scale, fsx2 = fsx1 + scale;
+        const double cell = std::min(scale, ssize - fsx1);
+        int sx1 = (int)ceil(fsx1), sx2 = (int)floor(fsx2);
+        sx2 = std::min(sx2, ssize - 1);
+        sx1 = std::min(sx1, sx2);
+        if (sx1 - fsx1 > 1e-3) tab.push_back({sx1 - 1, (float)((sx1 - fsx1) / cell)});
+        for (int sx = sx1; sx < sx2; ++sx) tab.push_back({sx, (float)(1.0 / cell)});
+        if (fsx2 - sx2 > 1e-3) tab.push_back({sx2, (float)(std::min(std::min(fsx2 - sx2, 1.), cell) / cell)});
+    }
+    begin[dsize] = (int)tab.size();
+}
+
+int detect_area_tabs(r3dm_ctx* c, DevBuf& buf, const std::vector<AkLevelHost>& lv, std::vector<HalfTabs>& tabs)
+{
+    const int nl = (int)lv.size();
+    tabs.assign(nl, HalfTabs());
+    std::vector<unsigned char> blob;
+    std::vector<std::array<size_t, 4>> offs(nl, {(size_t)-1, 0, 0, 0});                 // x table, y table, x begins, y begins
+    auto put = [&](const void* p, size_t bytes) { const size_t at = (blob.size() + 15) / 16 * 16; blob.resize(at + bytes); memcpy(blob.data() + at, p, bytes); return at; };
+    for (int i = 1; i < nl; ++i) {
+        if (lv[i].octave == lv[i - 1].octave) continue;
+        const int sw = lv[i - 1].w, sh = lv[i - 1].h, lw = lv[i].w, lh = lv[i].h;
+        if (lw * 2 == sw && lh * 2 == sh) continue;
+        std::vector<AkAreaTab> tx, ty; std::vector<int> bx, by;
+        ak_area_tab(sw, lw, tx, bx); ak_area_tab(sh, lh, ty, by);
+        offs[i][0] = put(tx.data(), tx.size() * sizeof(AkAreaTab)); offs[i][1] = put(ty.data(), ty.size() * sizeof(AkAreaTab));
+        offs[i][2] = put(bx.data(), bx.size() * 4); offs[i][3] = put(by.data(), by.size() * 4);
+    }
+    if (blob.empty()) return R3DM_OK;
+    R3DM_HIP(c, buf.ensure(blob.size() + 64));
+    R3DM_HIP(c, hipMemcpyAsync(buf.p, blob.data(), blob.size(), hipMemcpyHostToDevice, c->stream));
+    R3DM_HIP(c, hipStreamSynchronize(c->stream));                 // `blob` leaves scope
+    const unsigned char* base = buf.as<unsigned char>();
+    for (int i = 1; i < nl; ++i)
+        if (offs[i][0] != (size_t)-1) {
+            tabs[i].xt = (const AkAreaTab*)(base + offs[i][0]); tabs[i].yt = (const AkAreaTab*)(base + offs[i][1]);
+            tabs[i].xb = (const int*)(base + offs[i][2]); tabs[i].yb = (const int*)(base + offs[i][3]);
+        }
+    return R3DM_OK;
+}
+
+void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints, double algorithmic_bytes)
+{
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
+    c->stats.n_detect_images = B;
+    c->stats.ms_detect_kernels = ms;
+    c->stats.ms_detect = now_ms() - t_call;
+    r3dm_features_totals& T = c->feat_totals;
+    T.n_images += B; T.n_passes += 1; T.ms_detect_kernels += ms; T.detect_algorithmic_bytes += algorithmic_bytes; T.ms_wall += c->stats.ms_detect;
+    T.n_keypoints += n_keypoints;
+}
+
+int detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                 float threshold, DetectedBatch& out)
+{
+    return (c && c->detector_arm == R3DM_DETECTOR_AKAZE ? ac_detect_batch : ak_detect_batch)(c, B, images, bgrs, width, height, threshold, out);
+}
+
+int detect_entry(r3dm_ctx* c, DetectArm* arm, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
+                 float* const* keypoints_out, float* const* responses_out, uint32_t cap, uint32_t* n_out, DetectedBatch& d)
+{
+    if (!c || !images || !n_out || (cap && !keypoints_out) || (single && (!images[0] || (cap && !keypoints_out[0])))) return R3DM_ERR_INVALID;
+    if (single) *n_out = 0;
+    const int rc = arm(c, B, images, nullptr, width, height, threshold, d);
+    if (rc != R3DM_OK) return rc;
+    for (uint32_t b = 0; b < B; ++b) {
+        const size_t n = d.count(b);
+        for (size_t k = 0; k < n && k < cap; ++k) {
+            d.keypoint(b, k, keypoints_out[b] + 4 * k);
+            if (responses_out && responses_out[b]) responses_out[b][k] = d.response(b, k);
+        }
+        n_out[b] = (uint32_t)n;
+    }
+    return R3DM_OK;
+}
+
+// ======== keypoint detection: Fast-A-KAZE (kernels_akaze.hip)
+namespace {
+
+// AKAZEFeaturesV2::Allocate_Memory_Evolution (src/thirdparty/fast-akaze/AKAZEFeatures.cpp:73-131) with the AKAZE2::create()
+// defaults (AKAZEConfig.h:18-43): 4 octaves x 4 sublevels, soffset 1.6, derivative_factor 1.5, MLDB border 10 sqrt(2) sigma
+std::vector<AkLevelHost> ak_levels(int w, int h)
+{
+    std::vector<AkLevelHost> lv;
+    const int omax = 4, nsub = 4;
+    const float soffset = 1.6f, dfac = 1.5f;
+    const float smax = 10.0f * sqrtf(2.0f);
+    int lh = h, lw = w, power = 1;
+    for (int i = 0; i < omax; ++i) {
+        for (int j = 0; j < nsub; ++j) {
+            AkLevelHost e{};
+            e.w = lw; e.h = lh;
+            e.esigma = soffset * powf(2.f, (float)j / nsub + i);
+            e.sigma_size = (int)(e.esigma * dfac / power + 0.5f);
+            e.border = (int)(smax * e.sigma_size + 0.5f) + 1;
+            e.etime = 0.5f * (e.esigma * e.esigma);
+            e.octave = i; e.sublevel = j; e.ratio = (float)power;
+            if (e.border * 2 + 1 >= lw || e.border * 2 + 1 >= lh) return lv;
+            lv.push_back(e);
+        }
+        power <<= 1; lh >>= 1; lw >>= 1;
+        if (lw < 80 || lh < 40) break;
+    }
+    return lv;
+}
+
+// fed_tau_by_process_timeV2(T, 1, 0.25, reordering) (fed.cpp): float arithmetic, cosf -- the classic arm's ac_fed_tau works in double
+std::vector<float> ak_fed_tau(float T)
+{
+    const float tau_max = 0.25f;
+    const int n = (int)(ceilf(sqrtf(3.0f * T / tau_max + 0.25f) - 0.5f - 1.0e-8f) + 0.5f);
+    std::vector<float> tau;
+    if (n <= 0) return tau;
+    const float scale = 3.0f * T / (tau_max * (float)(n * (n + 1)));
+    std::vector<float> tauh(n);
+    const float cc = 1.0f / (4.0f * n + 2.0f);
+    const float d = scale * tau_max / 2.0f;
+    for (int k = 0; k < n; ++k) { const float hh = cosf((float)3.1415926535897932384626433832795 * (2.0f * k + 1.0f) * cc); tauh[k] = d / (hh * hh); }
+    if (n == 1) return tauh;
+    const int kappa = n / 2;
+    int prime = n + 1;
+    while (!ak_is_prime(prime)) prime++;
+    tau.resize(n);
+    for (int k = 0, l = 0; l < n; ++k, ++l) {
+        int index = 0;
+        while ((index = ((k + 1) * kappa) % prime - 1) >= n) k++;
+        tau[l] = tauh[index];
+    }
+    return tau;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The detector over a BATCH of B same-size images.  One image alone cannot fill the chip below the first octave: its ~550
+// dependent launches are a few microseconds each (profiles/r02_e_akaze_kernel_stats.txt), so a single image waits for launch
+// latency, not for HBM.  The launch sequence depends on the image SIZE only, so the same ~550 launches serve B images
+// (blockIdx.z = image), and nothing in the chain goes to the host: the k-contrast stays on the device, the candidate slots are
+// laid out on the device from a capacity (ak_layout_kernel) instead of counts read back, list lengths are read by grid-stride
+// kernels, and the survivors of all levels are compacted into one 32-byte record per keypoint (ak_compact_kernel).  The host sees
+// the batch twice: the per-image counts, then the records.
+// ------------------------------------------------------------------------------------------------
+
+// c->ak_bufs, each B planes: [0] image, [1..10] level-0 sized work images, then 4 per level (Lt, Lx, Ly, Ldet), then the T_* buffers
+enum { B_IMG = 0, B_SMOOTH, B_LXX, B_LXY, B_LYY, B_TMP, B_TMP2, B_WX, B_WY, B_FLOW, B_LT2, B_SMALL, B_LEVEL0 };
+enum { T_META = 0, T_SLOTS, T_MLDB, T_TABS, T_RECS, T_COUNT = 8 };
+
+// one pass of the arm: what its phases share
+struct AkPass {
+    r3dm_ctx* c; hipStream_t st;
+    uint32_t B; int iB, w, h, nl; size_t n0;
+    const std::vector<AkLevelHost>& lv;
+    float *img = nullptr, *smooth = nullptr, *tmp = nullptr, *tmp2 = nullptr, *flow = nullptr, *lt2 = nullptr;
+    // per image (4096 words apart, kernels_akaze.hip kAkSmallWords): [0] maximum of the gradient modulus (float bits),
+    // [16..) 300-bin histogram, [1024 + o] 1 / k^2 of octave o (ak_kcontrast_kernel)
+    uint32_t* small = nullptr;
+    uint32_t* hmax_bits() const { return small; }
+    uint32_t* hist() const { return small + 16; }
+    float* inv_k2() const { return reinterpret_cast<float*>(small + 1024); }
+    AkTaps taps_off, taps_one;
+    std::vector<HalfTabs> half_tabs;
+    // algorithmic HBM bytes of the launch sequence: every pass reads / writes whole image planes once
+    // Beside it the COMPULSORY count: the planes a perfectly fused level would still move -- a smoothed plane in and out, the determinant
+    // out, the conductivity out, and per FED step the evolving plane in and out (a step needs its neighbours' previous step, so steps do
+    // not fuse across a plane without halo recomputation); the k-contrast statistics ride on the Gaussian.  This is round 2's 8 bytes per
+    // pixel and pass; a roofline fraction on it falls when launches are fused, the as-structured one does not.
+    double planes_px = 0.0, compulsory_px = 0.0;
+    void tally(int lw, int lh, int n_planes, int n_compulsory) { planes_px += (double)lw * lh * n_planes; compulsory_px += (double)lw * lh * n_compulsory; }
+    DevBuf& buf(int k) const { return c->ak_bufs[k]; }
+    DevBuf& tail(int k) const { return c->ak_bufs[B_LEVEL0 + 4 * nl + k]; }
+    float* Lt(int i) const { return buf(B_LEVEL0 + 4 * i).as<float>(); }
+    float* Lx(int i) const { return buf(B_LEVEL0 + 4 * i + 1).as<float>(); }
+    float* Ly(int i) const { return buf(B_LEVEL0 + 4 * i + 2).as<float>(); }
+    float* Ldet(int i) const { return buf(B_LEVEL0 + 4 * i + 3).as<float>(); }
+};
+
+// ---- phase 1: the buffers, keyed on (w, h, B) and released when the key changes
+int ak_buffers(AkPass& p)
+{
+    r3dm_ctx* c = p.c; const int nl = p.nl;
+    if (c->ak_w != p.w || c->ak_h != p.h || c->ak_B < p.iB || c->ak_bufs.size() != (size_t)B_LEVEL0 + 4 * nl + T_COUNT) {
+        for (DevBuf& b : c->ak_bufs) b.release();
+        c->ak_bufs.assign((size_t)B_LEVEL0 + 4 * nl + T_COUNT, DevBuf());
+        c->ak_w = p.w; c->ak_h = p.h; c->ak_B = p.iB;
+    }
+    const size_t PB = (size_t)c->ak_B;                            // planes per buffer (the largest batch of this size so far)
+    for (int k = B_IMG; k <= B_LT2; ++k) if (k != B_LYY && k != B_LXX && k != B_LXY && k != B_WX && k != B_WY) R3DM_HIP(c, p.buf(k).ensure(PB * p.n0 * 4));      // (the second derivatives are folded into the determinant kernel)
+    R3DM_HIP(c, p.buf(B_SMALL).ensure(PB * 4096 * 4));
+    for (int i = 0; i < nl; ++i)
+        for (int q = 0; q < 4; ++q) R3DM_HIP(c, p.buf(B_LEVEL0 + 4 * i + q).ensure(PB * (size_t)p.lv[i].w * p.lv[i].h * 4));
+    p.img = p.buf(B_IMG).as<float>(); p.smooth = p.buf(B_SMOOTH).as<float>();
+    p.tmp = p.buf(B_TMP).as<float>(); p.tmp2 = p.buf(B_TMP2).as<float>();
+    p.flow = p.buf(B_FLOW).as<float>(); p.lt2 = p.buf(B_LT2).as<float>();
+    p.small = p.buf(B_SMALL).as<uint32_t>();
+    return R3DM_OK;
+}
+
+// ---- phase 2: Create_Nonlinear_Scale_Space (:245-369), Compute_Base_Evolution_Level (:199-237): ~550 launches for a 12 Mpx image,
+// none of which needs the host -- the k-contrast (compute_k_percentileV2: maximum, 300-bin histogram, percentile scan) stays
+// on the device.  (Replaying the sequence as a hipGraph was measured SLOWER than issuing it, 15.8 vs 7.5 ms per image:
+// DESIGN.md section 4.8 (c); the capture code is in the history.)
+#define AK_TRY(call) do { if ((e = (call)) != hipSuccess) return e; } while (0)
+
+// level i > 0 from level i - 1: start image, conductivity, the FED cycle
+// (Splitting the launches of the 3 Mpx octave into sub-batches whose planes fit the Infinity Cache was measured: 2.31-2.34 ms
+// per image against 2.36 -- not worth a second launch order; profiles/r03_f_*.)
+hipError_t ak_evolve_level(AkPass& p, int i)
+{
+    hipError_t e; hipStream_t st = p.st;
+    const std::vector<AkLevelHost>& lv = p.lv;
+    const int nb = p.iB, lw = lv[i].w, lh = lv[i].h;
+    const size_t n = (size_t)lw * lh;
+    const std::vector<float> tau = ak_fed_tau(lv[i].etime - lv[i - 1].etime);
+    float* Lti = p.Lt(i);
+    // FED launches of this level.  Product: up to four steps per launch in registers (ak_fed_march_kernel: a wavefront marches a
+    // strip of columns down the rows, every step level three rows deep in registers -- 12 bytes of HBM traffic per pixel and
+    // LAUNCH instead of per step).  The older forms stay for the developer build's A/B runs: one step per launch
+    // (R3DM_AK_FED_MARCH=0 R3DM_AK_FED_MULTI=0), four steps through LDS on the levels of <= 3.2 Mpx (R3DM_AK_FED_MARCH=0).
+    static const int march_knob = r3dm_dev_knob("R3DM_AK_FED_MARCH", 1);      // 0 = never, 1 = every level, > 1 = levels of at least that many pixels
+    // steps per launch: up to 4 on the large levels (a step there is bound by the arithmetic of its cells, more per pass only
+    // widens the halo), up to 6 below 1 Mpx per image, where a launch is mostly its own latency and fewer launches is the gain
+    static const int kmax_knob = r3dm_dev_knob("R3DM_AK_FED_KMAX", 0);
+    const int march_kmax = kmax_knob > 0 ? std::min(6, kmax_knob) : (n < (size_t)1000000 ? 6 : 4);
+    static const int march_waves = std::max(256, r3dm_dev_knob("R3DM_AK_FED_WAVES", 12000));
+    const bool march = march_knob && lw >= 3 && lh >= 3 && (march_knob == 1 || n >= (size_t)march_knob);
+    static const int multi_knob = r3dm_dev_knob("R3DM_AK_FED_MULTI", 1);      // developer build: 0 = never, 1 = the product, > 1 = that many pixels
+    static const int multi_px = multi_knob > 1 ? multi_knob : (multi_knob ? 3200000 : 0);
+    std::vector<int> chunk;                                             // chunk[m] = steps of launch m
+    if (march) {
+        const int q = ((int)tau.size() + march_kmax - 1) / march_kmax;         // launches, steps spread evenly over them
+        for (int m = 0; m < q; ++m) chunk.push_back(((int)tau.size() * (m + 1)) / q - ((int)tau.size() * m) / q);
+    } else {
+        const int per = n <= (size_t)multi_px ? 4 : 1;
+        for (size_t k0 = 0; k0 < tau.size(); k0 += (size_t)per) chunk.push_back((int)std::min<size_t>((size_t)per, tau.size() - k0));
+    }
+    const size_t n_launch = chunk.size();                               // plane passes of the FED part (3 planes each): launches, not steps
+    const float* start = nullptr;
+    if (lv[i].octave > lv[i - 1].octave) {
+        // the FED launches ping-pong between Lt(i) and the work image and must END in Lt(i): the half-sampled start image
+        // goes to whichever of the two the first launch does not write
+        float* half = (n_launch % 2 == 1) ? p.lt2 : Lti;
+        const HalfTabs& ht = p.half_tabs[i];
+        AK_TRY(ak_halfsample(st, p.Lt(i - 1), half, lv[i - 1].w, lv[i - 1].h, nb, ht.xt, ht.xb, ht.yt, ht.yb));
+        start = half;
+    } else {
+        start = p.Lt(i - 1);                                        // same octave: the previous level IS the start image, no copy
+    }
+    if (tau.empty()) {                                              // (never for the reference's time steps) plain copy
+        if (start != Lti) AK_TRY(hipMemcpyAsync(Lti, start, (size_t)nb * n * 4, hipMemcpyDeviceToDevice, st));
+        start = Lti;
+    }
+    // Gaussian -> derivatives -> determinant -> conductivity.  Product: four HBM-bound launches (10 plane moves).  The one-pass form
+    // (ak_level_head_kernel: a marching wavefront with the intermediates in LDS rings, 5 plane moves, bit-identical -- level_head.inc,
+    // tests/cpp/level_head_emul.cpp) is built and MEASURED SLOWER, twice: 1,369 us (stages chained inside an iteration) and 1,573 us
+    // (stages one iteration apart) against 1,083 us for the four launches at 8 x 12 Mpx.  PMC (profiles/r05_pmc_level_head.txt):
+    // 271 scalar + 138 vector + 28 LDS instructions per 48 stored pixels -- the per-row bookkeeping of a marching wavefront
+    // (ring slots, border rows, stage predicates) is paid once per 64 lanes and row, where a thread-per-pixel kernel pays it
+    // once per four rows of loads; at ~620 G wave instructions/s the fused form is instruction-bound above the four launches'
+    // HBM time.  It stays behind the developer knob R3DM_AK_HEAD=1 (tests/test_gpu_akaze.py runs it for bit-identity).
+    static const int head_knob = r3dm_dev_knob("R3DM_AK_HEAD", 0);
+    static const int head_waves = std::max(256, r3dm_dev_knob("R3DM_AK_HEAD_WAVES", 8000));
+    const int s_i = lv[i].sigma_size;
+    const bool head = head_knob && p.taps_one.n == 5 && s_i >= 2 && s_i <= 4 && lw >= 16 && lh >= 16;
+    if (head) {
+        const int vw = 64 - 2 * (2 + 2 * s_i), strips = (lw + vw - 1) / vw;
+        int rows = (int)(((int64_t)lh * strips * nb + head_waves - 1) / head_waves);
+        rows = std::max(32, std::min(256, (rows + 15) / 16 * 16));
+        AK_TRY(ak_level_head(st, start, p.Lx(i), p.Ly(i), p.Ldet(i), p.flow, lw, lh, nb, p.taps_one, s_i, p.inv_k2() + lv[i].octave, rows));
+    } else {
+        AK_TRY(ak_gaussian(st, start, p.tmp, p.smooth, lw, lh, nb, p.taps_one));
+        AK_TRY(ak_scaled_deriv_xy(st, p.smooth, p.Lx(i), p.Ly(i), lw, lh, nb, s_i));
+        AK_TRY(ak_scaled_deriv_det(st, p.Lx(i), p.Ly(i), p.Ldet(i), lw, lh, nb, s_i));
+        AK_TRY(ak_scharr_g2(st, p.smooth, p.flow, lw, lh, nb, p.inv_k2() + lv[i].octave));     // kcontrast * 0.75^octave
+    }
+    // Fast Explicit Diffusion: lt += lstep * 0.5 * tau_j; launch m of M writes Lt(i) when M - m is even, else the work image
+    const float* cur = start;
+    size_t k0 = 0;
+    for (size_t m = 1; m <= n_launch; ++m) {
+        float* o = ((n_launch - m) % 2 == 0) ? Lti : p.lt2;
+        const int kn = chunk[m - 1];
+        if (march) {
+            // rows per band: enough wavefronts to fill the chip (strips x bands x images >= march_waves), at most 128 rows
+            const int vw = 64 - 2 * kn, strips = (lw + vw - 1) / vw;
+            int rows = (int)(((int64_t)lh * strips * nb + march_waves - 1) / march_waves);
+            rows = std::max(16, std::min(128, (rows + 7) / 8 * 8));
+            AK_TRY(ak_fed_march(st, cur, p.flow, o, lw, lh, nb, tau.data() + k0, kn, rows));
+        } else if (kn == 1 && n > (size_t)multi_px) AK_TRY(ak_fed_step(st, cur, p.flow, o, lw, lh, nb, tau[k0]));
+        else AK_TRY(ak_fed_multi(st, cur, p.flow, o, lw, lh, nb, tau.data() + k0, kn));
+        cur = o; k0 += (size_t)kn;
+    }
+    if (lv[i].octave > lv[i - 1].octave) { p.tally(lv[i - 1].w, lv[i - 1].h, 1, 1); p.tally(lw, lh, 1, 1); }
+    p.tally(lw, lh, (head ? 5 : 2 + 6 + 2) + 3 * (int)n_launch, 2 + 1 + 1 + 2 * (int)tau.size());       // Gaussian (fused row + column pass) 2, derivatives + determinant 6, conductivity 2, 3 per FED launch (as structured); compulsory: 2 per FED step, the round-2 count
+    return hipSuccess;
+}
+
+hipError_t ak_scale_space(AkPass& p)
+{
+    hipError_t e; hipStream_t st = p.st;
+    const int w = p.w, h = p.h, iB = p.iB, nl = p.nl;
+    // (the base level's smoothed image IS evolution level 0: written straight into Lt(0), no copy)
+    AK_TRY(ak_gaussian(st, p.img, p.tmp, p.Lt(0), w, h, iB, p.taps_off)); p.tally(w, h, 2, 2);
+    // Compute_Determinant_Hessian_Response_Single (AKAZEFeatures.cpp:389-410), two launches: smooth -> (Lx, Ly);  (Lx, Ly) -> Lxx, Lxy, Lyy on
+    // the spot -> the determinant
+    AK_TRY(ak_scaled_deriv_xy(st, p.Lt(0), p.Lx(0), p.Ly(0), w, h, iB, p.lv[0].sigma_size)); p.tally(w, h, 3 + 3, 1);
+    AK_TRY(ak_scaled_deriv_det(st, p.Lx(0), p.Ly(0), p.Ldet(0), w, h, iB, p.lv[0].sigma_size));
+    AK_TRY(hipMemsetAsync(p.small, 0, (size_t)p.B * 4096 * 4, st));
+    const int nbins = 300;
+    if (nl > 1) {
+        AK_TRY(ak_gaussian(st, p.img, p.tmp, p.flow, w, h, iB, p.taps_one)); p.tally(w, h, 2, 1);
+        // (the Scharr derivative images of the reference exist only inside these two kernels: DESIGN.md section 4.8)
+        AK_TRY(ak_modg_max(st, p.flow, w, h, iB, p.hmax_bits())); p.tally(w, h, 1, 0);
+        AK_TRY(ak_modg_hist(st, p.flow, w, h, iB, p.hmax_bits(), nbins, p.hist())); p.tally(w, h, 1, 0);
+    }
+    AK_TRY(ak_kcontrast(st, p.hmax_bits(), p.hist(), nbins, (uint32_t)((size_t)(w - 2) * (h - 2)), nl > 1 ? 1 : 0, p.inv_k2(), iB));
+    for (int i = 1; i < nl; ++i) AK_TRY(ak_evolve_level(p, i));
+    return hipSuccess;
+}
+#undef AK_TRY
+
+// ---- phase 3: Feature_Detection (:371-382): extrema -> in-level pruning -> cross-level pruning -> refinement + orientation
+struct AkDetection {
+    size_t rows_total = 0, n_lv = 0;
+    std::vector<AkLevelDev> ld;                  // [B][nl], uploaded to d_levels by every attempt
+    AkLevelDev* d_levels = nullptr;
+    AkBatchMeta* d_bmeta = nullptr;
+    AkTileTable tiles;
+    uint32_t n_tiles = 0;
+    int max_rows = 0;
+    uint64_t bound = 0;                          // candidates an image can hold at most
+    uint32_t cap = 0;                            // slots per image of the attempt that fitted
+    std::vector<AkBatchMeta> bm;
+};
+
+// the level table of every image, the extremum masks' places, the tiles of the count pass, the candidate bound
+int ak_level_table(AkPass& p, AkDetection& d)
+{
+    r3dm_ctx* c = p.c; const std::vector<AkLevelHost>& lv = p.lv;
+    const int nl = p.nl; const uint32_t B = p.B;
+    d.ld.assign((size_t)nl * B, AkLevelDev{});
+    size_t rows_img = 0;
+    for (int i = 0; i < nl; ++i) rows_img += (size_t)std::max(0, lv[i].h - 2 * lv[i].border);
+    d.rows_total = rows_img * B; d.n_lv = (size_t)nl * B;
+    // row counts + row offsets, per-level counters (4 words), level table, per-image meta
+    DevBuf& meta = p.tail(T_META);
+    const size_t off_levels = ((d.rows_total * 8 + d.n_lv * 16 + 15) / 16) * 16;
+    const size_t off_bmeta = off_levels + ((d.n_lv * sizeof(AkLevelDev) + 15) / 16) * 16;
+    R3DM_HIP(c, meta.ensure(off_bmeta + (size_t)B * sizeof(AkBatchMeta) + 256));
+    uint32_t* rc = meta.as<uint32_t>();
+    uint32_t* cnt = rc + 2 * d.rows_total;
+    d.d_levels = reinterpret_cast<AkLevelDev*>(meta.as<unsigned char>() + off_levels);
+    d.d_bmeta = reinterpret_cast<AkBatchMeta*>(meta.as<unsigned char>() + off_bmeta);
+    std::vector<size_t> mask_off(nl + 1, 0);                          // in 64-bit words, per level, inside an image's mask area
+    for (int i = 0; i < nl; ++i)
+        mask_off[i + 1] = mask_off[i] + (size_t)std::max(0, lv[i].h - 2 * lv[i].border) * (size_t)std::max(0, (lv[i].w - 2 * lv[i].border + 63) / 64);
+    if (mask_off[nl] * 8 + 8 > p.n0 * 4) { c->err = "detector: extremum masks do not fit the work image"; return R3DM_ERR_HIP; }
+    size_t ro = 0;
+    for (uint32_t b = 0; b < B; ++b)
+        for (int i = 0; i < nl; ++i) {
+            AkLevelDev& L = d.ld[(size_t)b * nl + i];
+            const size_t plane = (size_t)lv[i].w * lv[i].h;
+            L.w = lv[i].w; L.h = lv[i].h; L.border = lv[i].border; L.ratio = lv[i].ratio; L.psize = lv[i].esigma * 1.5f;
+            L.Ldet = p.Ldet(i) + b * plane; L.Lx = p.Lx(i) + b * plane; L.Ly = p.Ly(i) + b * plane; L.Lt = p.Lt(i) + b * plane;
+            L.row_cnt = rc + ro; L.row_off = rc + d.rows_total + ro; L.counts = cnt + 4 * ((size_t)b * nl + i);
+            // extremum bit masks: in the row-pass work image of the Gaussian (idle once the scale space is built), image b's
+            // plane, the levels one after another (1 bit per pixel + at most 8 bytes per row: far below the plane's 4 bytes per pixel)
+            const int rows_i = std::max(0, lv[i].h - 2 * lv[i].border);
+            L.mask_words = (uint32_t)std::max(0, (lv[i].w - 2 * lv[i].border + 63) / 64);
+            L.mask = reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned char*>(p.tmp) + (((size_t)b * p.n0 * 4 + 7) / 8) * 8) + mask_off[i];   // (8-byte aligned also when w h is odd)
+            ro += (size_t)rows_i;
+        }
+    for (int i = 0; i < nl; ++i) d.max_rows = std::max(d.max_rows, lv[i].h - 2 * lv[i].border);
+    // tiles of the extremum count pass: 64 columns x 64 rows of a level's interior (kernels_akaze.hip kAkMaskRows = 16 rows per wave), the levels one after another
+    for (int i = 0; i < 17; ++i) d.tiles.begin[i] = 0xFFFFFFFFu;
+    if (nl > 16) { c->err = "detector: more than 16 evolution levels"; return R3DM_ERR_UNSUPPORTED; }
+    for (int i = 0; i < nl; ++i) {
+        d.tiles.begin[i] = d.n_tiles;
+        const int rows_i = std::max(0, lv[i].h - 2 * lv[i].border), words_i = std::max(0, (lv[i].w - 2 * lv[i].border + 63) / 64);
+        d.n_tiles += (uint32_t)words_i * (uint32_t)((rows_i + 63) / 64);
+    }
+    // slot capacity per image: a strict 3x3 maximum excludes its eight neighbours, so a level holds at most ceil(w/2) ceil(h/2)
+    // candidates; start from min(that bound, 256 k) and grow only if an image reports more (the bound itself never overflows)
+    for (int i = 0; i < nl; ++i) d.bound += (uint64_t)((lv[i].w + 1) / 2) * (uint64_t)((lv[i].h + 1) / 2);
+    return R3DM_OK;
+}
+
+// the detection launches at a slot capacity; an image that reports more candidates than it makes them run again with larger arrays
+int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
+{
+    r3dm_ctx* c = p.c; hipStream_t st = p.st;
+    const int nl = p.nl, iB = p.iB; const uint32_t B = p.B;
+    // (R3DM_AK_CAP, developer build only: a tiny first capacity so that the tests reach the grow-and-repeat path)
+    static const uint32_t cap0 = (uint32_t)std::max(1, r3dm_dev_knob("R3DM_AK_CAP", 1 << 18));
+    uint32_t cap = (uint32_t)std::min<uint64_t>(d.bound, std::max<uint64_t>(c->ak_cap, cap0));
+    d.bm.assign(B, AkBatchMeta{});
+    DevBuf &meta = p.tail(T_META), &slots = p.tail(T_SLOTS), &recs = p.tail(T_RECS);
+    for (int attempt = 0;; ++attempt) {
+        const size_t field = (size_t)B * cap;
+        R3DM_HIP(c, slots.ensure(field * kAkSlotBytes + 256));
+        R3DM_HIP(c, recs.ensure(field * sizeof(AkKpRec) + 256));
+        R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
+        R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
+        R3DM_HIP(c, ak_extrema_mask(st, d.d_levels, nl, iB, d.tiles, d.n_tiles, threshold));   // all levels of all images in one launch
+        R3DM_HIP(c, ak_scan_rows(st, d.d_levels, nl, iB));
+        R3DM_HIP(c, ak_layout(st, d.d_levels, nl, iB, slots.as<unsigned char>(), cap, d.d_bmeta));
+        R3DM_HIP(c, hipMemsetAsync(slots.as<unsigned char>() + field * 76, 0, field * 2, st));   // dead_lower / dead_upper flags
+        R3DM_HIP(c, ak_extrema(st, d.d_levels, nl, iB, d.max_rows, threshold, 1));
+        R3DM_HIP(c, ak_prune_levels(st, d.d_levels, nl, iB));
+        R3DM_HIP(c, ak_list_ranges(st, d.d_levels, nl, iB));
+        R3DM_HIP(c, ak_cross(st, d.d_levels, nl, iB, 0));
+        R3DM_HIP(c, ak_cross(st, d.d_levels, nl, iB, 1));
+        R3DM_HIP(c, ak_refine(st, d.d_levels, nl, iB));
+        R3DM_HIP(c, ak_compact(st, d.d_levels, nl, iB, recs.as<AkKpRec>(), cap, d.d_bmeta));
+        R3DM_HIP(c, hipEventRecord(c->ev1, st));
+        R3DM_HIP(c, hipMemcpyAsync(d.bm.data(), d.d_bmeta, (size_t)B * sizeof(AkBatchMeta), hipMemcpyDeviceToHost, st));
+        R3DM_HIP(c, hipStreamSynchronize(st));                                            // host visit 1 of 2: the counts
+        uint32_t need = 0;
+        for (uint32_t b = 0; b < B; ++b) if (d.bm[b].overflow) need = std::max(need, d.bm[b].need);
+        if (!need) break;
+        if (attempt >= 2 || need > d.bound) { c->err = "detector: candidate count exceeds its own bound"; return R3DM_ERR_HIP; }
+        cap = (uint32_t)std::min<uint64_t>(d.bound, (uint64_t)need + need / 4 + 1024);       // grow and redo the detection phase (the scale space stays)
+        c->feat_totals.n_regrows += 1;
+    }
+    d.cap = cap;
+    c->ak_cap = cap;
+    c->ak_n_levels = nl;
+    c->ak_levels_dev = d.d_levels;
+    return R3DM_OK;
+}
+
+// ---- phase 4: the records of every image
+int ak_read_back(AkPass& p, const AkDetection& d, std::vector<std::vector<AkKpRec>>& out)
+{
+    r3dm_ctx* c = p.c; const AkKpRec* recs = p.tail(T_RECS).as<AkKpRec>();
+    for (uint32_t b = 0; b < p.B; ++b) {
+        out[b].resize(d.bm[b].n_kp);
+        if (d.bm[b].n_kp) R3DM_HIP(c, hipMemcpyAsync(out[b].data(), recs + (size_t)b * d.cap, (size_t)d.bm[b].n_kp * sizeof(AkKpRec), hipMemcpyDeviceToHost, p.st));
+    }
+    R3DM_HIP(c, hipStreamSynchronize(p.st));                                              // host visit 2 of 2: the records
+    return R3DM_OK;
+}
+
+}  // namespace
+
+// Leaves the B gray images in ak_bufs[0] (B planes) for the LIOP patch extraction and the level images for MLDB.
+int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                    float threshold, DetectedBatch& out)
+{
+    if (!detect_args_ok(c, B, images, bgrs, width, height)) return R3DM_ERR_INVALID;
+    out = DetectedBatch();
+    out.fast.assign(B, std::vector<AkKpRec>());
+    if (width < 3 || height < 3) return R3DM_ERR_INVALID;
+    R3DM_HIP(c, hipSetDevice(c->device));
+    const double t_call = now_ms();
+    out.fast_levels = ak_levels((int)width, (int)height);
+    AkPass p{c, c->stream, B, (int)B, (int)width, (int)height, (int)out.fast_levels.size(), (size_t)width * height, out.fast_levels};
+    c->stats.n_detect_images = B; c->stats.ms_detect_kernels = 0.0; c->stats.detect_algorithmic_bytes = 0.0; c->stats.detect_compulsory_bytes = 0.0;
+    if (p.nl == 0) { c->stats.ms_detect = now_ms() - t_call; return R3DM_OK; }     // image too small for a single evolution level
+    int rc = ak_buffers(p);
+    out.grays_dev = p.img;                                  // (BGR: the bytes are staged in the not yet used work image tmp2)
+    if (rc == R3DM_OK) rc = detect_upload(c, B, images, bgrs, p.n0, p.img, reinterpret_cast<unsigned char*>(p.tmp2));
+    p.taps_off = ak_taps(1.6f); p.taps_one = ak_taps(1.0f);
+    if (rc == R3DM_OK) rc = detect_area_tabs(c, p.tail(T_TABS), p.lv, p.half_tabs);
+    if (rc != R3DM_OK) return rc;
+    R3DM_HIP(c, hipEventRecord(c->ev0, p.st));
+    R3DM_HIP(c, ak_scale_space(p));
+    AkDetection d;
+    rc = ak_level_table(p, d);
+    if (rc == R3DM_OK) rc = ak_detect_regrow(p, d, threshold);
+    if (rc == R3DM_OK) rc = ak_read_back(p, d, out.fast);
+    if (rc != R3DM_OK) return rc;
+    c->stats.detect_algorithmic_bytes = p.planes_px * 4.0 * B; c->stats.detect_compulsory_bytes = p.compulsory_px * 4.0 * B;
+    uint64_t n_kp = 0;
+    for (uint32_t b = 0; b < B; ++b) n_kp += d.bm[b].n_kp;
+    detect_finish(c, B, t_call, n_kp, p.planes_px * 4.0 * B);
+    return R3DM_OK;
+}
+
+// Get_MLDB_Full_Descriptor of the first min(count, cap) keypoints of image 0: level coordinates, cos / sin of the raw (radian) angle
+static int ak_mldb_describe(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, unsigned char* mldb_out)
+{
+    const std::vector<AkKpRec>& recs = det.fast[0];
+    const std::vector<AkLevelHost>& lv = det.fast_levels;
+    std::vector<AkMldbItem> items;
+    for (uint32_t k = 0; k < recs.size() && k < cap; ++k) {
+        const AkKpRec& r = recs[k];
+        const float theta = ak_theta(r);
+        items.push_back({r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (float)lv[r.level].sigma_size});
+    }
+    if (items.empty()) return R3DM_OK;
+    // comparison table of MLDB_Binary_Comparisons: per grid, per channel, all value pairs i < j
+    std::vector<unsigned char> pairs;
+    const int bases[3] = {0, 12, 39}, cnts[3] = {4, 9, 16};
+    for (int g = 0; g < 3; ++g)
+        for (int pos = 0; pos < 3; ++pos)
+            for (int i = 0; i < cnts[g]; ++i)
+                for (int j = i + 1; j < cnts[g]; ++j) { pairs.push_back((unsigned char)(bases[g] + 3 * i + pos)); pairs.push_back((unsigned char)(bases[g] + 3 * j + pos)); }
+    hipStream_t st = c->stream;
+    DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_MLDB];
+    const size_t ni = items.size();
+    R3DM_HIP(c, mb.ensure(ni * sizeof(AkMldbItem) + 1024 + ni * 61 + 64));
+    unsigned char* base = mb.as<unsigned char>();
+    R3DM_HIP(c, hipMemcpyAsync(base, items.data(), ni * sizeof(AkMldbItem), hipMemcpyHostToDevice, st));
+    R3DM_HIP(c, hipMemcpyAsync(base + ni * sizeof(AkMldbItem), pairs.data(), pairs.size(), hipMemcpyHostToDevice, st));
+    unsigned char* d_out = base + ni * sizeof(AkMldbItem) + 1024;
+    R3DM_HIP(c, ak_mldb(st, c->ak_levels_dev, (const AkMldbItem*)base, (uint32_t)ni, base + ni * sizeof(AkMldbItem), d_out));
+    R3DM_HIP(c, hipMemcpyAsync(mldb_out, d_out, ni * 61, hipMemcpyDeviceToHost, st));
+    R3DM_HIP(c, hipStreamSynchronize(st));
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_detect_akaze(r3dm_ctx* c, const float* image, uint32_t width, uint32_t height, float threshold,
+                                 float* keypoints_out, float* responses_out, uint32_t cap, uint32_t* n_out)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        DetectedBatch det;
+        return detect_entry(c, ak_detect_batch, true, 1, &image, width, height, threshold, &keypoints_out, &responses_out, cap, n_out, det);
+    });
+}
+
+extern "C" int r3dm_detect_akaze_mldb(r3dm_ctx* c, const float* image, uint32_t width, uint32_t height, float threshold,
+                                      float* keypoints_out, unsigned char* descriptors_out, uint32_t cap, uint32_t* n_out)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!descriptors_out && cap) return R3DM_ERR_INVALID;
+        DetectedBatch det;
+        int rc = detect_entry(c, ak_detect_batch, true, 1, &image, width, height, threshold, &keypoints_out, nullptr, cap, n_out, det);
+        if (rc == R3DM_OK && (rc = ak_mldb_describe(c, det, cap, descriptors_out)) != R3DM_OK) *n_out = 0;
+        return rc;
+    });
+}
+
+// B same-size images in one pass of the detector.  keypoints_out[b]: cap x 4 floats (x, y, size, angle in degrees),
+// responses_out (optional, entries optional): cap floats, n_out[b] = number detected (may exceed cap).
+extern "C" int r3dm_detect_akaze_batch(r3dm_ctx* c, uint32_t n_images, const float* const* images, uint32_t width, uint32_t height,
+                                       float threshold, float* const* keypoints_out, float* const* responses_out, uint32_t cap,
+                                       uint32_t* n_out)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        DetectedBatch det;
+        return detect_entry(c, ak_detect_batch, false, n_images, images, width, height, threshold, keypoints_out, responses_out, cap, n_out, det);
+    });
+}

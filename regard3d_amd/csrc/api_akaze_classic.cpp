@@ -2,32 +2,23 @@
 // (r3dm_detect_akaze_classic / _batch in include/r3dm.h; kernels in kernels_akaze_classic.hip).
 // The arm is libAKAZE with its AKAZEConfig.h defaults (src/thirdparty/akaze/lib/), as Regard3D runs it through
 // cv::AKAZE::create(DESCRIPTOR_MLDB, 0, 3, threshold, 4, 4, DIFF_PM_G2) + detect() (src/Regard3DFeatures.cpp:578-589).
+// The frame it shares with the Fast arm (checks, upload, INTER_AREA tables, statistics tail, the detect entry) is api_akaze.cpp.
 #include "r3dm_ctx.hpp"
 
-#include <array>
-#include <cmath>
-#include <cstring>
-#include <vector>
-
 namespace {
-
-struct AcLevelHost {
-    int w, h, octave, sigma_size;
-    float esigma, etime, ratio;
-};
 
 // Allocate_Memory_Evolution (AKAZE.cpp:51-99).  Differs from the Fast arm's table: the level size is (int)(size / 2^i), an octave
 // i > 0 below 80 x 40 ends the table, and no descriptor border stops it; sigma_size is the multiscale derivative's
 // fRound(esigma * derivative_factor / 2^octave) (:198).
-std::vector<AcLevelHost> ac_levels(int w, int h)
+std::vector<AkLevelHost> ac_levels(int w, int h)
 {
-    std::vector<AcLevelHost> lv;
+    std::vector<AkLevelHost> lv;
     for (int i = 0; i < 4; ++i) {
         const double rfactor = 1.0 / pow(2.0f, i);
         const int lh = (int)(h * rfactor), lw = (int)(w * rfactor);
         if ((lw < 80 || lh < 40) && i != 0) break;
         for (int j = 0; j < 4; ++j) {
-            AcLevelHost e{};
+            AkLevelHost e{};
             e.w = lw; e.h = lh; e.octave = i;
             e.esigma = 1.6f * powf(2.0f, (float)j / 4.0f + (float)i);
             e.etime = (float)(0.5 * (e.esigma * e.esigma));
@@ -37,16 +28,6 @@ std::vector<AcLevelHost> ac_levels(int w, int h)
         }
     }
     return lv;
-}
-
-bool ac_is_prime(int number)
-{
-    if (number <= 1) return false;
-    if (number == 2 || number == 3 || number == 5 || number == 7) return true;
-    if ((number % 2) == 0 || (number % 3) == 0 || (number % 5) == 0 || (number % 7) == 0) return false;
-    const int upper = (int)sqrt(number + 1.0);
-    for (int divisor = 11; divisor <= upper; divisor += 2) if (number % divisor == 0) return false;
-    return true;
 }
 
 // fed_tau_by_process_time(T, 1, 0.25, reordering = true) (fed.cpp).  Differs from fed_tau_by_process_timeV2: n and the scale are formed
@@ -69,7 +50,7 @@ std::vector<float> ac_fed_tau(float T)
     if (n == 1) return tauh;
     const int kappa = n / 2;
     int prime = n + 1;
-    while (!ac_is_prime(prime)) prime++;
+    while (!ak_is_prime(prime)) prime++;
     tau.resize(n);
     for (int k = 0, l = 0; l < n; ++k, ++l) {
         int index = 0;
@@ -81,21 +62,19 @@ std::vector<float> ac_fed_tau(float T)
 
 }  // namespace
 
-// the detector over B same-size images; out[b] = the keypoints of image b in the reference's order.  images: B pointers to height x width
-// floats (host or device), or bgrs: B pointers to height x width x 3 bytes, converted on the device by the Fast arm's gray kernel.
+// the detector over B same-size images; out.classic[b] = the keypoints of image b in the reference's order.
 // Leaves the B gray images in ac_bufs[0] (B planes) for the LIOP pass of the features entries.
 int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
-                    float threshold, std::vector<std::vector<AcOut>>& out)
+                    float threshold, DetectedBatch& out)
 {
-    if (!c || B == 0 || (!images && !bgrs)) return R3DM_ERR_INVALID;
-    for (uint32_t b = 0; b < B; ++b) if (!(images ? (const void*)images[b] : (const void*)bgrs[b])) return R3DM_ERR_INVALID;
-    if ((uint64_t)width * height > (1ull << 30) || B > 4096) return R3DM_ERR_INVALID;
-    out.assign(B, std::vector<AcOut>());
+    if (!detect_args_ok(c, B, images, bgrs, width, height)) return R3DM_ERR_INVALID;
+    out = DetectedBatch();
+    out.classic.assign(B, std::vector<AcOut>());
     if (width < 3 || height < 3) return R3DM_OK;                      // no 3 x 3 maximum exists
     R3DM_HIP(c, hipSetDevice(c->device));
     const double t_call = now_ms();
     const int w = (int)width, h = (int)height, iB = (int)B;
-    const std::vector<AcLevelHost> lv = ac_levels(w, h);
+    const std::vector<AkLevelHost> lv = ac_levels(w, h);
     const int nl = (int)lv.size();
     hipStream_t st = c->stream;
     const size_t n0 = (size_t)w * h;
@@ -117,34 +96,12 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     auto Lx = [&](int i) { return planes[3 * i].as<float>(); };
     auto Ly = [&](int i) { return planes[3 * i + 1].as<float>(); };
     auto Ldet = [&](int i) { return planes[3 * i + 2].as<float>(); };
-    if (images) {
-        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(img.as<float>() + b * n0, images[b], n0 * 4, hipMemcpyDefault, st));
-    } else {
-        // 8-bit BGR -> gray as the Fast arm converts it (ak_bgr_to_gray): the bytes are staged in the (not yet used) work image tmp
-        unsigned char* stage = tmp.as<unsigned char>();
-        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(stage + b * n0 * 4, bgrs[b], n0 * 3, hipMemcpyDefault, st));
-        for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, ak_bgr_to_gray(st, stage + b * n0 * 4, img.as<float>() + b * n0, n0));
-    }
-
-    // INTER_AREA tables of the octave transitions that are not exact halvings
-    std::vector<std::array<size_t, 4>> toff(nl, {(size_t)-1, 0, 0, 0});
-    {
-        std::vector<unsigned char> blob;
-        auto put = [&](const void* p, size_t bytes) { const size_t at = (blob.size() + 15) / 16 * 16; blob.resize(at + bytes); memcpy(blob.data() + at, p, bytes); return at; };
-        for (int i = 1; i < nl; ++i) {
-            if (lv[i].octave == lv[i - 1].octave) continue;
-            const int sw = lv[i - 1].w, sh = lv[i - 1].h;
-            if (lv[i].w * 2 == sw && lv[i].h * 2 == sh) continue;
-            std::vector<AkAreaTab> tx, ty; std::vector<int> bx, by;
-            ak_area_tab(sw, lv[i].w, tx, bx); ak_area_tab(sh, lv[i].h, ty, by);
-            toff[i] = {put(tx.data(), tx.size() * sizeof(AkAreaTab)), put(ty.data(), ty.size() * sizeof(AkAreaTab)), put(bx.data(), bx.size() * 4), put(by.data(), by.size() * 4)};
-        }
-        if (!blob.empty()) {
-            R3DM_HIP(c, tabs.ensure(blob.size() + 64));
-            R3DM_HIP(c, hipMemcpyAsync(tabs.p, blob.data(), blob.size(), hipMemcpyHostToDevice, st));
-            R3DM_HIP(c, hipStreamSynchronize(st));
-        }
-    }
+    out.grays_dev = img.as<float>();
+    // (BGR: the bytes are staged in the not yet used work image tmp)
+    int frc = detect_upload(c, B, images, bgrs, n0, img.as<float>(), tmp.as<unsigned char>());
+    if (frc != R3DM_OK) return frc;
+    std::vector<HalfTabs> half_tabs;
+    if ((frc = detect_area_tabs(c, tabs, lv, half_tabs)) != R3DM_OK) return frc;
     const AkTaps taps_off = ak_taps(1.6f), taps_one = ak_taps(1.0f);
     uint32_t* sm = small.as<uint32_t>();
     const float* inv_k2 = reinterpret_cast<const float*>(sm + 1024);
@@ -170,11 +127,8 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     for (int i = 1; i < nl; ++i) {
         const int lw = lv[i].w, lh = lv[i].h;
         if (lv[i].octave > lv[i - 1].octave) {
-            const unsigned char* base = tabs.as<unsigned char>();
-            const bool tab = toff[i][0] != (size_t)-1;
-            R3DM_HIP(c, ak_halfsample(st, cur, other, lv[i - 1].w, lv[i - 1].h, iB,
-                                      tab ? (const AkAreaTab*)(base + toff[i][0]) : nullptr, tab ? (const int*)(base + toff[i][2]) : nullptr,
-                                      tab ? (const AkAreaTab*)(base + toff[i][1]) : nullptr, tab ? (const int*)(base + toff[i][3]) : nullptr));
+            const HalfTabs& ht = half_tabs[i];
+            R3DM_HIP(c, ak_halfsample(st, cur, other, lv[i - 1].w, lv[i - 1].h, iB, ht.xt, ht.xb, ht.yt, ht.yb));
             std::swap(cur, other);
         }
         // (same octave: the previous level's Lt is this level's start image, copyTo without a copy)
@@ -278,44 +232,20 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
         std::vector<AcOut> all(ns[b]);
         if (ns[b]) R3DM_HIP(c, hipMemcpyAsync(all.data(), outs.as<AcOut>() + (size_t)b * stride, (size_t)ns[b] * sizeof(AcOut), hipMemcpyDeviceToHost, st));
         R3DM_HIP(c, hipStreamSynchronize(st));
-        for (const AcOut& o : all) if (o.ok) out[b].push_back(o);             // the slots that survive, in slot order
+        for (const AcOut& o : all) if (o.ok) out.classic[b].push_back(o);             // the slots that survive, in slot order
     }
-    float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, c->ev0, c->ev1);
-    c->stats.n_detect_images = B;
-    c->stats.ms_detect_kernels = ms;
-    c->stats.ms_detect = now_ms() - t_call;
-    r3dm_features_totals& T = c->feat_totals;
-    T.n_images += B; T.n_passes += 1; T.ms_detect_kernels += ms; T.ms_wall += c->stats.ms_detect;
-    for (uint32_t b = 0; b < B; ++b) T.n_keypoints += out[b].size();
+    uint64_t n_kp = 0;
+    for (uint32_t b = 0; b < B; ++b) n_kp += out.classic[b].size();
+    detect_finish(c, B, t_call, n_kp, 0.0);                              // (this arm tallies no plane moves: the byte statistics stay as they were)
     return R3DM_OK;
 }
-
-namespace {
-
-void ac_write(const std::vector<AcOut>& kp, float* keypoints_out, float* responses_out, uint32_t cap)
-{
-    for (size_t k = 0; k < kp.size() && k < cap; ++k) {
-        float* o = keypoints_out + 4 * k;
-        o[0] = kp[k].x; o[1] = kp[k].y; o[2] = kp[k].size; o[3] = kp[k].angle;
-        if (responses_out) responses_out[k] = kp[k].resp;
-    }
-}
-
-}  // namespace
 
 extern "C" int r3dm_detect_akaze_classic(r3dm_ctx* c, const float* image, uint32_t width, uint32_t height, float threshold,
                                          float* keypoints_out, float* responses_out, uint32_t cap, uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        if (!c || !image || !n_out || (cap && !keypoints_out)) return R3DM_ERR_INVALID;
-        *n_out = 0;
-        std::vector<std::vector<AcOut>> kp;
-        const int rc = ac_detect_batch(c, 1, &image, nullptr, width, height, threshold, kp);
-        if (rc != R3DM_OK) return rc;
-        ac_write(kp[0], keypoints_out, responses_out, cap);
-        *n_out = (uint32_t)kp[0].size();
-        return R3DM_OK;
+        DetectedBatch det;
+        return detect_entry(c, ac_detect_batch, true, 1, &image, width, height, threshold, &keypoints_out, &responses_out, cap, n_out, det);
     });
 }
 
@@ -324,15 +254,8 @@ extern "C" int r3dm_detect_akaze_classic_batch(r3dm_ctx* c, uint32_t n_images, c
                                                uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        if (!c || !images || !n_out || (cap && !keypoints_out)) return R3DM_ERR_INVALID;
-        std::vector<std::vector<AcOut>> kp;
-        const int rc = ac_detect_batch(c, n_images, images, nullptr, width, height, threshold, kp);
-        if (rc != R3DM_OK) return rc;
-        for (uint32_t b = 0; b < n_images; ++b) {
-            ac_write(kp[b], cap ? keypoints_out[b] : nullptr, responses_out ? responses_out[b] : nullptr, cap);
-            n_out[b] = (uint32_t)kp[b].size();
-        }
-        return R3DM_OK;
+        DetectedBatch det;
+        return detect_entry(c, ac_detect_batch, false, n_images, images, width, height, threshold, keypoints_out, responses_out, cap, n_out, det);
     });
 }
 

@@ -6,7 +6,12 @@
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
 //   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules
 //   api_filter.cpp    AC-RANSAC geometric filters (F, E, H)
-//   api_features.cpp  Fast-A-KAZE detection, MLDB / LIOP description, the features work item
+//   api_akaze.cpp     the frame of both detector arms (checks, upload, INTER_AREA tables, statistics tail, DetectedBatch's writer) and the
+//                     Fast-A-KAZE arm: its pass in phases, MLDB, r3dm_detect_akaze / _mldb / _batch, r3dm_gray_from_bgr8
+//   api_akaze_classic.cpp   the classic A-KAZE arm's launch sequence on that frame, r3dm_detect_akaze_classic / _batch
+//   api_liop.cpp      LIOP: the patch geometry, the one pass from keypoints to descriptors (liop_pass), its two entries
+//   api_features.cpp  the features work item: .feat / .desc files, the features batch in phases (detect, keypoints and maps, LIOP pass,
+//                     delivery, outputs), the work list of a multi-context, the setters
 #pragma once
 
 #include "r3dm_internal.hpp"
@@ -296,10 +301,6 @@ inline bool has_tensor_kernel(uint32_t G) { return G == 8 || G == 16 || G == 18 
 
 inline uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 
-// Gaussian taps and INTER_AREA tables of the detectors (api_features.cpp; shared by the classic arm, api_akaze_classic.cpp)
-AkTaps ak_taps(float sigma);
-void ak_area_tab(int ssize, int dsize, std::vector<AkAreaTab>& tab, std::vector<int>& begin);
-
 inline double now_ms()
 {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
@@ -310,7 +311,6 @@ inline bool has_ext(const char* path, const char* ext)
     const size_t lp = strlen(path), le = strlen(ext);
     return lp >= le && strcmp(path + lp - le, ext) == 0;
 }
-
 
 // The same CSR in device memory, kept beside the host vectors when the context was asked to (r3dm_set_device_graphs): what
 // r3dm_allgather_graphs puts on the wire without a host round trip of the payload (api_comm.cpp).  Filled where the data already is
@@ -375,9 +375,79 @@ struct GuidedResult {
 int guided_job_make(r3dm_ctx* c, uint32_t sI, uint32_t sJ, int pub_kind, const double* M, double thr_px, double ratio, GuidedJob& out);
 // runs the jobs (q0 / b0 are assigned here), fills c->guided_stats; jobs may be empty
 int guided_run(r3dm_ctx* c, std::vector<GuidedJob>& jobs, GuidedResult& R);
-// the classic A-KAZE detector over B same-size images (api_akaze_classic.cpp); gray images or 8-bit BGR, left in ac_bufs[0]
-int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
-                    float threshold, std::vector<std::vector<AcOut>>& out);
+// ---- the detectors (api_akaze.cpp: the Fast arm and what both arms share; api_akaze_classic.cpp)
+// one evolution level of either arm's table (the classic arm has no descriptor border and no sublevel: both stay 0)
+struct AkLevelHost {
+    int w, h, octave, sublevel, sigma_size, border;
+    float esigma, etime, ratio;
+};
+
+// angle of a Fast-arm keypoint: getAngleV2(maxX, maxY) (fast-akaze utils.h:11-19: atan2f of the host libm, + 2 pi when negative)
+inline float ak_theta(const AkKpRec& r)
+{
+    float theta = atan2f(r.max_y, r.max_x);
+    if (!(theta >= 0)) theta = theta + (float)(2.0f * 3.1415926535897932384626433832795);
+    return theta;
+}
+// ... and the conversion of detectKeypoints (src/Regard3DFeatures.cpp:604-613): degrees, + 90, wrapped into [0, 360]
+inline float ak_angle_deg(float ang)
+{
+    ang *= 180.0 / 3.1415926535897932384626433832795;
+    ang += 90.0f;
+    while (ang < 0) ang += 360.0f;
+    while (ang > 360.0f) ang -= 360.0f;
+    return ang;
+}
+
+// What a detector pass over B same-size images hands its consumers, whichever arm ran.  The Fast arm keeps its raw records (MLDB reads
+// them and the level table): their angle is host libm atan2f per keypoint, formed when a consumer asks -- the features batch asks from
+// its parallel loop.  (The classic arm's angle comes from the device, in degrees, without the + 90: DESIGN.md section 7.)
+struct DetectedBatch {
+    std::vector<std::vector<AkKpRec>> fast;            // Fast arm: per image, the survivors in the reference's order (level, list)
+    std::vector<AkLevelHost> fast_levels;              //           the evolution levels of this image size
+    std::vector<std::vector<AcOut>> classic;           // classic arm: per image, the slots that survive, in slot order
+    const float* grays_dev = nullptr;                  // the B gray planes the detector left on the device (read-only for it)
+    size_t count(uint32_t b) const { return fast.empty() ? classic[b].size() : fast[b].size(); }
+    void keypoint(uint32_t b, size_t k, float* o) const     // x, y, size, angle in degrees
+    {
+        if (fast.empty()) { const AcOut& a = classic[b][k]; o[0] = a.x; o[1] = a.y; o[2] = a.size; o[3] = a.angle; }
+        else { const AkKpRec& r = fast[b][k]; o[0] = r.x; o[1] = r.y; o[2] = r.size; o[3] = ak_angle_deg(ak_theta(r)); }
+    }
+    float response(uint32_t b, size_t k) const { return fast.empty() ? classic[b][k].resp : fast[b][k].response; }
+};
+// the two arms; gray images (host or device) or 8-bit BGR.  detect_batch: the context's arm (r3dm_set_keypoint_detector)
+using DetectArm = int(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                      float threshold, DetectedBatch& out);
+DetectArm ak_detect_batch, ac_detect_batch, detect_batch;
+// A detect entry: its argument checks, B gray images through `arm`, then keypoints_out[b] / responses_out[b] (entries optional) / n_out[b]:
+// min(count, cap) rows are written, the count itself is reported.  single: one image by value, whose count reads 0 when the arm fails
+int detect_entry(r3dm_ctx* c, DetectArm* arm, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
+                 float* const* keypoints_out, float* const* responses_out, uint32_t cap, uint32_t* n_out, DetectedBatch& d);
+
+// The frame both arms stand in (api_akaze.cpp)
+AkTaps ak_taps(float sigma);
+bool ak_is_prime(int number);
+// what every detect entry refuses: no context, no images, an image above 2^30 pixels, more than 4096 images
+bool detect_args_ok(const r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height);
+// B gray images, or B 8-bit BGR images converted on the device as processWorkItem does (src/threads/R3DFeaturesThread.cpp:163-191), into
+// the B planes of n0 floats at `gray`; the BGR bytes are staged at `stage` (4 n0 bytes apart): a work image of the arm's not yet in use
+int detect_upload(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, size_t n0, float* gray, unsigned char* stage);
+// INTER_AREA tables of the octave transitions whose size is not an exact halving (they depend on the image size only): built, uploaded
+// into `buf` and waited for before the launch sequence, which then never touches the host.  Per level; null where the halving is exact
+struct HalfTabs { const AkAreaTab* xt = nullptr; const int* xb = nullptr; const AkAreaTab* yt = nullptr; const int* yb = nullptr; };
+int detect_area_tabs(r3dm_ctx* c, DevBuf& buf, const std::vector<AkLevelHost>& lv, std::vector<HalfTabs>& tabs);
+// the tail of a pass: kernel time (ev0 .. ev1) and wall time into the statistics, the pass into the totals
+void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints, double algorithmic_bytes);
+
+// ---- LIOP (api_liop.cpp)
+// 2x3 inverse map of one keypoint's patch (x, y, size, angle in degrees)
+void liop_patch_map(float x, float y, float size, float angle_deg, float kp_size_factor, float* m);
+// One LIOP pass over n > 0 keypoints of the image(s) at dev_images (planes of width x height floats; img_of: the plane of every keypoint,
+// null = plane 0), M6 = their patch maps on the host.  Descriptors -> c->liop_out; with want_patches (or the developer build's
+// R3DM_LIOP_FUSED=0) the patches go through HBM -> c->liop_in.  Bracketed by ev0 / ev1, not waited for: the caller copies and synchronises
+int liop_pass(r3dm_ctx* c, const float* dev_images, uint32_t width, uint32_t height, const float* M6, const uint32_t* img_of, uint32_t n,
+              bool want_patches);
+void liop_read_time(r3dm_ctx* c);
 
 // The way of a view from host memory to HBM (r3dm_set_image / r3dm_set_images): a ring of page-locked slots the caller's pageable rows
 // are copied into by the host (several threads for a batch of views), one asynchronous DMA per view from there into the slot's
@@ -531,8 +601,6 @@ struct GraphBuilder {
         }                                                                              \
     } while (0)
 
-
-
 // The C ABI never throws: entry points whose bodies size host containers from caller- or file-provided counts run behind this
 // guard (std::bad_alloc / std::length_error would otherwise cross the extern "C" boundary and terminate the host application).
 template <class F>
@@ -588,7 +656,6 @@ struct CallCounters {
         for (auto m : times) c->stats.*m = after.*m - before.*m;
     }
 };
-
 
 // A dataset staged once for many queries (ArrayMatcher::Build): owns its device buffers, belongs to a device, not to a context
 struct r3dm_index {

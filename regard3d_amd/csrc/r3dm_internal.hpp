@@ -511,7 +511,7 @@ hipError_t launch_guided_sweep(hipStream_t st, const GuidedParams& P, int pass);
 hipError_t launch_guided_desc(hipStream_t st, const GuidedParams& P);
 hipError_t launch_guided_compact(hipStream_t st, const GuidedParams& P);
 
-// geometry tables of the 41 x 41 LIOP patch (api_features.cpp: liop_prepare), all in device memory
+// geometry tables of the 41 x 41 LIOP patch (api_liop.cpp: liop_prepare), all in device memory
 struct LiopTables {
     const int* pix;            // [n_pix] support pixels in scan order, as offsets into the zero-ringed 43 x 43 patch
     const double* samp_w;      // [n_pix][4][2] fractional parts (wx, wy) of the four sample positions
