@@ -448,6 +448,44 @@ int r3dm_mrpt_knn2(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, cons
 int r3dm_mrpt_index(r3dm_ctx* ctx, uint32_t view_id, const r3dm_mrpt_params* params, float* R, float* splits, int32_t* leaves,
                     int32_t* leaf_first, uint32_t* depth_out);
 
+/* ---- k neighbours, k = 1 .. R3DM_KNN_MAX, through the three approximate matchers: ArrayMatcher::SearchNeighbours(.., NN) of
+ * ArrayMatcher_kgraph / _hnsw / _mrpt with any NN (sparams.K = NN, matcher_kgraph.h:205-251; searchKnn(q, NN), matcher_hnsw.h:138-173;
+ * Mrpt::query(q, NN, votes), matcher_mrpt.h:186-251) ----
+ * Each entry takes the arguments of its *_knn2 sibling plus k and follows the sibling's rules for lengths, row counts and small
+ * datasets; out_idx / out_dist hold k entries per query at [q * k + j].  R3DM_ERR_INVALID: k < 1, k > R3DM_KNN_MAX, n_dataset < k
+ * (the plugins' "NN > rows" rule), null pointers.  k = 2 returns the sibling's bits.  The search itself depends on k:
+ *   KGraph  the pool holds k + search_P entries (KGraphImpl::search, kgraph.cpp:418), one per lane of a wavefront: k + search_P > 63
+ *           is R3DM_ERR_INVALID.  Output: the first min(L, k) pool entries, ascending; -1 / +inf behind them.
+ *   HNSW    the beam is max(ef, k) (hnswalg.h:765) -- the "fast" preset (ef 5) searches a wider beam at k = 8.  Output: the beam popped
+ *           down to k, ascending by (distance, row); -1 / +inf for rows the search did not find.
+ *   MRPT    the election is the sibling's; the k nearest elected rows by (distance, row) are kept, the retry with votes - 1 runs when
+ *           fewer than k rows were elected, and a query still short of k is dropped: all k entries -1 / -1.  Distances are square
+ *           roots.  (The reference's autotune mode is not served.)
+ * The r3dm_match_pairs_* ratio rule stays on 2-lists.  The ANN counters of r3dm_stats (n_ann_dist, ms_ann_build, ms_ann_search,
+ * n_hnsw_launches, n_hnsw_retries, ...) describe these calls as they describe the siblings. */
+int r3dm_kgraph_knn(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                    uint32_t dim, const r3dm_kgraph_params* params, uint32_t pair_i, uint32_t pair_j, uint32_t k,
+                    int32_t* out_idx, float* out_dist);
+int r3dm_hnsw_knn(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                  uint32_t dim, const r3dm_hnsw_params* params, uint32_t k, int32_t* out_idx, float* out_dist);
+int r3dm_hnsw_knn_on_index(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, uint32_t dim, const r3dm_hnsw_arrays* index,
+                           const float* query, uint32_t n_query, uint32_t ef, uint32_t k, int32_t* out_idx, float* out_dist);
+int r3dm_mrpt_knn(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                  uint32_t dim, const r3dm_mrpt_params* params, uint32_t k, int32_t* out_idx, float* out_dist);
+/* "Build once, search per query block" for the three matchers: the arm's structure lives on an r3dm_index (F32 / U8 rows).
+ * It is built on FIRST USE, under the index's lock, from that call's build parameters -- KGraph: index_K; HNSW: M, ef_construction,
+ * seed; MRPT: n_trees, depth, density, seed -- and never again: a later call whose build parameters differ is R3DM_ERR_INVALID (nothing
+ * is rebuilt under another context's search).  Search parameters (search_P, search_S, seed; ef; votes) are free per call.  Any context
+ * of the index's device may search, several at a time, as for r3dm_index_knn; an index may hold all three structures.  An index of
+ * fewer than 128 rows (KGraph: or of at most search_P rows) is answered by r3dm_index_knn, exactly, as r3dm_match_pairs_* scans such
+ * views (MRPT too: such an answer holds squared distances and drops no query).  r3dm_stats.ms_ann_build / n_ann_built are 0 for every call but the one that built. */
+int r3dm_index_kgraph_knn(r3dm_ctx* ctx, const r3dm_index* index, const r3dm_kgraph_params* params, const void* query, uint32_t n_query,
+                          uint32_t pair_i, uint32_t pair_j, uint32_t k, int32_t* out_idx, float* out_dist);
+int r3dm_index_hnsw_knn(r3dm_ctx* ctx, const r3dm_index* index, const r3dm_hnsw_params* params, const void* query, uint32_t n_query,
+                        uint32_t k, int32_t* out_idx, float* out_dist);
+int r3dm_index_mrpt_knn(r3dm_ctx* ctx, const r3dm_index* index, const r3dm_mrpt_params* params, const void* query, uint32_t n_query,
+                        uint32_t k, int32_t* out_idx, float* out_dist);
+
 /* ---- keypoint detection: Fast-A-KAZE ----
  * The "Fast-AKAZE" arm of Regard3DFeatures::detectKeypoints (src/Regard3DFeatures.cpp:596-617): cv::AKAZE2::create() with its
  * defaults (src/thirdparty/fast-akaze/AKAZEConfig.h:18-43: 4 octaves x 4 sublevels, PM_G2 diffusivity), setThreshold(threshold),

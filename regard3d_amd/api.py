@@ -30,6 +30,7 @@ EXPORTS = [
     "r3dm_detect_akaze_batch", "r3dm_detect_akaze_classic", "r3dm_detect_akaze_classic_batch", "r3dm_extract_features_batch", "r3dm_multi_extract_features_ex", "r3dm_get_features_totals", "r3dm_kgraph_preset", "r3dm_match_pairs_kgraph", "r3dm_exhaustive_is_faster", "r3dm_kgraph_knn2", "r3dm_kgraph_index", "r3dm_drop_indices",
     "r3dm_filter_FEH", "r3dm_host_threads", "r3dm_set_features_sink", "r3dm_multi_set_features_sink", "r3dm_set_deferred_feature_files", "r3dm_set_background_nice", "r3dm_multi_set_background_nice", "r3dm_features_files_wait", "r3dm_multi_set_deferred_feature_files", "r3dm_multi_features_files_wait", "r3dm_hnsw_preset", "r3dm_match_pairs_hnsw", "r3dm_hnsw_knn2", "r3dm_hnsw_knn2_on_index", "r3dm_hnsw_index",
     "r3dm_mrpt_preset", "r3dm_match_pairs_mrpt", "r3dm_mrpt_knn2", "r3dm_mrpt_index", "r3dm_multi_match_pairs_mrpt",
+    "r3dm_kgraph_knn", "r3dm_hnsw_knn", "r3dm_hnsw_knn_on_index", "r3dm_mrpt_knn", "r3dm_index_kgraph_knn", "r3dm_index_hnsw_knn", "r3dm_index_mrpt_knn",
     "r3dm_set_integer_mfma", "r3dm_set_split_mfma", "r3dm_set_hamming_mfma", "r3dm_index_create", "r3dm_index_knn2", "r3dm_index_destroy",
     "r3dm_knn", "r3dm_index_knn", "r3dm_set_knn_narrow_tiles",
     "r3dm_multi_create", "r3dm_multi_destroy", "r3dm_multi_num_devices", "r3dm_multi_ctx", "r3dm_multi_last_error",
@@ -355,6 +356,13 @@ def load_library():
     L.r3dm_hnsw_knn2_on_index.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, vp, vp]
     L.r3dm_hnsw_index.argtypes = [vp, u32, vp, vp, vp, vp, u32, vp, vp, vp]
     L.r3dm_drop_indices.argtypes = [vp]
+    L.r3dm_kgraph_knn.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, u32, vp, vp]
+    L.r3dm_hnsw_knn.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp, vp]
+    L.r3dm_hnsw_knn_on_index.argtypes = [vp, vp, u32, u32, vp, vp, u32, u32, u32, vp, vp]
+    L.r3dm_mrpt_knn.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, vp, vp]
+    L.r3dm_index_kgraph_knn.argtypes = [vp, vp, vp, vp, u32, u32, u32, u32, vp, vp]
+    L.r3dm_index_hnsw_knn.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
+    L.r3dm_index_mrpt_knn.argtypes = [vp, vp, vp, vp, u32, u32, vp, vp]
     L.r3dm_graph_num_pairs.argtypes = [vp]; L.r3dm_graph_num_pairs.restype = u64
     L.r3dm_graph_num_matches.argtypes = [vp]; L.r3dm_graph_num_matches.restype = u64
     L.r3dm_graph_pairs.argtypes = [vp]; L.r3dm_graph_pairs.restype = vp
@@ -598,11 +606,46 @@ class Comm:
         return [Graph(out[k]) for k in range(len(local))]
 
 
+def _knn_out(nq: int, k: int):
+    return np.full((max(nq, 1), max(k, 1)), -1, np.int32), np.zeros((max(nq, 1), max(k, 1)), np.float32)
+
+
 class Index:
-    """r3dm_index: a dataset staged once for many 2-NN searches"""
+    """r3dm_index: a dataset staged once for many searches.  The approximate matchers' structures (graph, HNSW, forest) are built on it
+    by the first kgraph_knn / hnsw_knn / mrpt_knn call, from that call's build parameters; a later call that names other build
+    parameters raises.  ctx: any Context of the index's device."""
 
     def __init__(self, handle: int):
         self._h = handle
+
+    def kgraph_knn(self, ctx: "Context", query, params: "KGraphParams" = None, pair=(0, 1), k: int = 2):
+        """ArrayMatcher_kgraph::SearchNeighbours(NN = k) (r3dm_index_kgraph_knn): (idx [nq, k] int32, -1 where the pool ran short;
+        dist [nq, k] float32, +inf there)"""
+        query = np.ascontiguousarray(query, np.float32)
+        kp = params if params is not None else KGraphParams.preset(3)
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        ctx._check(ctx._L.r3dm_index_kgraph_knn(ctx._h, self._h, C.addressof(kp), _ptr(query), nq, pair[0], pair[1], k, _ptr(idx), _ptr(dist)),
+                   "r3dm_index_kgraph_knn")
+        return idx[:nq], dist[:nq]
+
+    def hnsw_knn(self, ctx: "Context", query, params: "HnswParams" = None, k: int = 2):
+        """ArrayMatcher_hnsw::SearchNeighbours(NN = k) (r3dm_index_hnsw_knn)"""
+        query = np.ascontiguousarray(query, np.float32)
+        hp = params if params is not None else HnswParams.preset(2)
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        ctx._check(ctx._L.r3dm_index_hnsw_knn(ctx._h, self._h, C.addressof(hp), _ptr(query), nq, k, _ptr(idx), _ptr(dist)), "r3dm_index_hnsw_knn")
+        return idx[:nq], dist[:nq]
+
+    def mrpt_knn(self, ctx: "Context", query, params: "MrptParams" = None, k: int = 2):
+        """ArrayMatcher_mrpt::SearchNeighbours(NN = k) (r3dm_index_mrpt_knn): a dropped query holds -1 / -1 in all k entries; dist = SQUARE ROOTS"""
+        query = np.ascontiguousarray(query, np.float32)
+        mp = params if params is not None else MrptParams.preset()
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        ctx._check(ctx._L.r3dm_index_mrpt_knn(ctx._h, self._h, C.addressof(mp), _ptr(query), nq, k, _ptr(idx), _ptr(dist)), "r3dm_index_mrpt_knn")
+        return idx[:nq], dist[:nq]
 
     def close(self):
         if getattr(self, "_h", None):
@@ -744,6 +787,17 @@ class Context:
                                              C.addressof(kp), pair[0], pair[1], _ptr(idx), _ptr(dist)), "r3dm_kgraph_knn2")
         return idx[:nq], dist[:nq]
 
+    def kgraph_knn(self, dataset, query, params: "KGraphParams" = None, pair=(0, 1), k: int = 2):
+        """ArrayMatcher_kgraph::SearchNeighbours(NN = k), k = 1 .. KNN_MAX (r3dm_kgraph_knn): the pool holds k + search_P entries;
+        (idx [nq, k] int32, -1 where the pool ran short; dist [nq, k] float32, +inf there)"""
+        dataset = np.ascontiguousarray(dataset, np.float32); query = np.ascontiguousarray(query, np.float32)
+        kp = params if params is not None else KGraphParams.preset(3)
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        self._check(self._L.r3dm_kgraph_knn(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
+                                            C.addressof(kp), pair[0], pair[1], k, _ptr(idx), _ptr(dist)), "r3dm_kgraph_knn")
+        return idx[:nq], dist[:nq]
+
     def drop_indices(self):
         """r3dm_drop_indices: the next match_pairs_kgraph rebuilds the graph index of every view it uses"""
         self._check(self._L.r3dm_drop_indices(self._h), "r3dm_drop_indices")
@@ -782,6 +836,17 @@ class Context:
                                            C.addressof(mp), _ptr(idx), _ptr(dist)), "r3dm_mrpt_knn2")
         return idx[:nq], dist[:nq]
 
+    def mrpt_knn(self, dataset, query, params: "MrptParams" = None, k: int = 2):
+        """ArrayMatcher_mrpt::SearchNeighbours(NN = k) (r3dm_mrpt_knn): (idx [nq, k] int32, dist [nq, k] float32 = SQUARE ROOTS); a query
+        with fewer than k elected rows after the retry is dropped: -1 / -1 in all k entries"""
+        dataset = np.ascontiguousarray(dataset, np.float32); query = np.ascontiguousarray(query, np.float32)
+        mp = params if params is not None else MrptParams.preset()
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        self._check(self._L.r3dm_mrpt_knn(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
+                                          C.addressof(mp), k, _ptr(idx), _ptr(dist)), "r3dm_mrpt_knn")
+        return idx[:nq], dist[:nq]
+
     def mrpt_index(self, view_id: int, n_rows: int, dim: int, params: "MrptParams" = None) -> dict:
         """the MRPT index of a registered view as arrays (r3dm_mrpt_index), cut to the view's clamped depth"""
         mp = params if params is not None else MrptParams.preset()
@@ -800,6 +865,28 @@ class Context:
         idx = np.full((max(nq, 1), 2), -1, np.int32); dist = np.zeros((max(nq, 1), 2), np.float32)
         self._check(self._L.r3dm_hnsw_knn2(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
                                            C.addressof(hp), _ptr(idx), _ptr(dist)), "r3dm_hnsw_knn2")
+        return idx[:nq], dist[:nq]
+
+    def hnsw_knn(self, dataset, query, params: "HnswParams" = None, k: int = 2):
+        """ArrayMatcher_hnsw::SearchNeighbours(NN = k) (r3dm_hnsw_knn): searchKnn(row, k) with the beam max(ef, k); (idx [nq, k], dist [nq, k])"""
+        dataset = np.ascontiguousarray(dataset, np.float32); query = np.ascontiguousarray(query, np.float32)
+        hp = params if params is not None else HnswParams.preset(2)
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        self._check(self._L.r3dm_hnsw_knn(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
+                                          C.addressof(hp), k, _ptr(idx), _ptr(dist)), "r3dm_hnsw_knn")
+        return idx[:nq], dist[:nq]
+
+    def hnsw_knn_on_index(self, dataset, index: dict, M: int, query, ef: int, k: int):
+        """searchKnn(row, k) with setEf(ef) on an index given as arrays (r3dm_hnsw_knn_on_index; keys as hnsw_knn2_on_index)"""
+        dataset = np.ascontiguousarray(dataset, np.float32); query = np.ascontiguousarray(query, np.float32)
+        l0 = np.ascontiguousarray(index["links0"], np.int32); uo = np.ascontiguousarray(index["up_off"], np.int32)
+        ul = np.ascontiguousarray(index["up_links"], np.int32).reshape(-1, 1 + M)
+        a = HnswArrays(M, l0.ctypes.data, uo.ctypes.data, ul.ctypes.data if ul.size else None, ul.shape[0], int(index["enterpoint"]), int(index["maxlevel"]))
+        nq, k = int(query.shape[0]), int(k)
+        idx, dist = _knn_out(nq, k)
+        self._check(self._L.r3dm_hnsw_knn_on_index(self._h, _ptr(dataset), dataset.shape[0], dataset.shape[1], C.addressof(a),
+                                                   _ptr(query), nq, ef, k, _ptr(idx), _ptr(dist)), "r3dm_hnsw_knn_on_index")
         return idx[:nq], dist[:nq]
 
     def hnsw_knn2_on_index(self, dataset, index: dict, M: int, query, ef: int):

@@ -115,7 +115,7 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
 // one search batch: sizes, pair table, common buffers, event bracket, comparison count, finalisation, common statistics
 // ------------------------------------------------------------------------------------------------
 int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host,
-                  const std::function<int(const AnnBatch&)>& launch)
+                  const std::function<int(const AnnBatch&)>& launch, uint32_t knn_cols)
 {
     AnnBatch b{};
     b.P = (uint32_t)jobs.size();
@@ -143,8 +143,8 @@ int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, 
     R3DM_HIP(c, c->d_nn.ensure((size_t)total_slots * 4));
     R3DM_HIP(c, c->d_cnt.ensure(64));
     if (knn_idx_host) {
-        R3DM_HIP(c, c->d_knn_idx.ensure((size_t)total_slots * 8));
-        R3DM_HIP(c, c->d_knn_dist.ensure((size_t)total_slots * 8));
+        R3DM_HIP(c, c->d_knn_idx.ensure((size_t)total_slots * knn_cols * 4));
+        R3DM_HIP(c, c->d_knn_dist.ensure((size_t)total_slots * knn_cols * 4));
     }
     b.nn_idx = c->d_nn.as<uint32_t>();
     b.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
@@ -159,7 +159,7 @@ int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, 
     R3DM_HIP(c, hipMemcpyAsync(&comps, b.n_comps, 8, hipMemcpyDeviceToHost, c->stream));
     R3DM_HIP(c, hipStreamSynchronize(c->stream));              // (the pair table and the arm's job records are host temporaries)
     const double t_post = now_ms();
-    rc = finalize_batch(c, jobs, b.q_stride, sort_cap, n_queries, b.max_nJ, g, knn_idx_host, knn_dist_host);
+    rc = finalize_batch(c, jobs, b.q_stride, sort_cap, n_queries, b.max_nJ, g, knn_idx_host, knn_dist_host, knn_cols);
     if (rc != R3DM_OK) return rc;
     c->stats.ms_wall_match_post += now_ms() - t_post;
     float ms = 0.f;
@@ -170,6 +170,39 @@ int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, 
     c->stats.n_pairs += b.P;
     c->stats.n_queries += n_queries;
     return R3DM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// an arm's structure on an r3dm_index: built once, searched from any context of the device
+// ------------------------------------------------------------------------------------------------
+// The build runs on a private slot that holds the index's image (its buffers, not aliases: the arm's ensure_* adds the structure's
+// buffers to it) and hands the image back on every exit.  It holds the index's lock for that long: a context that mounts the index
+// waits; a search that mounted it before runs on, on buffers the build does not touch.
+int with_index_structure(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query,
+                         const std::function<int(const r3dm_index&)>& state, const std::function<int(r3dm_index&, uint32_t slot)>& build,
+                         const std::function<int(uint32_t sI, uint32_t sJ)>& search)
+{
+    if (ix->device != c->device) { c->err = "the index lives on another device"; return R3DM_ERR_INVALID; }
+    R3DM_HIP(c, hipSetDevice(c->device));
+    r3dm_index* mix = const_cast<r3dm_index*>(ix);
+    PrivateSlots s(c, 2);
+    {
+        std::lock_guard<std::mutex> lk(mix->mu);
+        const int st = state(*mix);
+        if (st < 0) return st;
+        if (st == 1) {
+            struct Lend {                                     // the slot IS the index for the build, and gives it back whatever happens
+                r3dm_ctx* c; r3dm_index* ix; HostImage& slot;
+                Lend(r3dm_ctx* c_, r3dm_index* ix_, HostImage& slot_) : c(c_), ix(ix_), slot(slot_) { slot = ix->img; }
+                ~Lend() { (void)hipStreamSynchronize(c->stream); ix->img = slot; slot = HostImage(); }
+            } lend(c, mix, *c->imgs[s[0]]);
+            int rc = publish_entry(c, s[0]);
+            if (rc == R3DM_OK) rc = build(*mix, s[0]);
+            if (rc != R3DM_OK) return rc;
+        }
+    }
+    const int rc = mount_index_beside_queries(c, ix, query, n_query, s[0], s[1]);
+    return rc != R3DM_OK ? rc : search(s[0], s[1]);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -369,8 +402,10 @@ int ensure_ann_indices(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t K)
 }
 
 // graph search + ratio test over `jobs` (all of one dim; every sI holds an index), results appended to g in job order
+// knn_k = 0: the 2-NN search (pool of 2 + P entries, ratio test, optional 2-lists); 1 .. R3DM_KNN_MAX: the k-list search of one pair
+// (pool of knn_k + P entries as KGraphImpl::search sizes it, kgraph.cpp:418; knn_*_host receive knn_k entries per query)
 static int run_kgraph_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, const r3dm_kgraph_params& kp,
-                            r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host)
+                            r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_k = 0)
 {
     std::vector<uint2> hid(jobs.size());                     // the search is seeded by (I, J); outlives the frame's synchronisation
     bool rows16 = true, rows8 = true, dot8 = r3dm_dev_knob("R3DM_ANN_ROWS16", 3) >= 3;   // every indexed view of the batch holds that compact row copy
@@ -381,7 +416,7 @@ static int run_kgraph_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float
         AnnSearchParams sp{};
         sp.imgs = c->d_imgs.as<ImgDev>(); sp.pairs = c->d_pairs.as<uint2>(); sp.pair_ids = c->a_ids.as<uint2>();
         sp.n_pairs = b.P; sp.q_stride = b.q_stride;
-        sp.P = kp.search_P; sp.S = kp.search_S; sp.pool_cap = 2 + kp.search_P; sp.seed = kp.seed; sp.ratio_R = ratio_R;
+        sp.P = kp.search_P; sp.S = kp.search_S; sp.pool_cap = (knn_k ? knn_k : 2u) + kp.search_P; sp.seed = kp.seed; sp.ratio_R = ratio_R;
         sp.nn_idx = b.nn_idx; sp.knn_idx = b.knn_idx; sp.knn_dist = b.knn_dist; sp.n_comps = b.n_comps;
         for (const PairJob& j : jobs) {
             const HostImage& A = *c->imgs[j.sI];
@@ -394,11 +429,11 @@ static int run_kgraph_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float
         // descriptor lengths 132 .. 144 (nine float4 per lane: LIOP-144) have no compact-row instantiation of the search kernel
         // (launch_ann_search): integer-valued views of that length gather the f32 rows
         if ((b.dim / 4 + 3) / 4 == 9) { dot8 = false; rows8 = false; rows16 = false; }
-        const hipError_t e = launch_ann_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim, dot8 ? 3 : rows8 ? 2 : (rows16 ? 1 : 0));
+        const hipError_t e = launch_ann_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim, dot8 ? 3 : rows8 ? 2 : (rows16 ? 1 : 0), knn_k);
         if (e == hipErrorInvalidValue) { c->err = "graph search: unsupported descriptor length / view size / parameters"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, e);
         return R3DM_OK;
-    });
+    }, knn_k ? knn_k : 2u);
     if (rc != R3DM_OK || jobs.empty()) return rc;
     c->stats.n_ann_rows16 += (rows16 && !rows8) ? 1 : 0;
     c->stats.n_ann_rows8 += rows8 ? 1 : 0;
@@ -474,6 +509,73 @@ extern "C" int r3dm_kgraph_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_da
                                 int32_t* out_idx, float* out_dist)
 {
     return r3dm_guarded(c, [&]() -> int { return r3dm_kgraph_knn2_impl(c, dataset, n_dataset, query, n_query, dim, kp, pair_i, pair_j, out_idx, out_dist); });
+}
+
+// ---- k neighbours, k = 1 .. R3DM_KNN_MAX: ArrayMatcher_kgraph::SearchNeighbours with any NN (matcher_kgraph.h:205-251, sparams.K = NN)
+static int check_kgraph_knn(r3dm_ctx* c, const r3dm_kgraph_params* kp, uint32_t k, uint32_t n_dataset, uint32_t n_query)
+{
+    if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || n_dataset < k) return R3DM_ERR_INVALID;     // the plugins' "NN > rows" rule
+    const int rc = check_kgraph_params(c, kp);
+    if (rc != R3DM_OK) return rc;
+    if (k + kp->search_P > 63) { c->err = "kgraph k-NN: the pool holds k + search_P entries, 63 at most"; return R3DM_ERR_INVALID; }
+    return R3DM_OK;
+}
+
+// the search of one staged pair whose dataset slot holds the index
+static int kgraph_knn_search(r3dm_ctx* c, const r3dm_kgraph_params& kp, uint32_t pair_i, uint32_t pair_j, uint32_t sI, uint32_t sJ, uint32_t k,
+                             int32_t* out_idx, float* out_dist)
+{
+    int rc = ensure_layouts(c, {sI, sJ}, kLayRows);
+    if (rc == R3DM_OK) rc = ensure_ann_indices(c, {sI}, kp.index_K);
+    if (rc == R3DM_OK) rc = ensure_compact_rows(c, {sJ});
+    if (rc == R3DM_OK) rc = run_kgraph_batch(c, {{pair_i, pair_j, sI, sJ}}, 1.0f, kp, nullptr, out_idx, out_dist, k);
+    return rc;
+}
+
+extern "C" int r3dm_kgraph_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                               uint32_t dim, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j, uint32_t k,
+                               int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !dataset || !query || !out_idx || !out_dist || dim == 0) return R3DM_ERR_INVALID;
+        int rc = check_kgraph_knn(c, kp, k, n_dataset, n_query);
+        if (rc != R3DM_OK) return rc;
+        if (dim & 3u) { c->err = "kgraph matching needs dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+        return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, pair_i, pair_j,
+                                {&r3dm_stats::n_ann_rows16, &r3dm_stats::n_ann_rows8, &r3dm_stats::n_ann_dot8, &r3dm_stats::n_ann_dist},
+                                {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search}, [&](uint32_t sI, uint32_t sJ) -> int {
+            // as r3dm_kgraph_knn2: a small dataset, or one the start rows would cover, is scanned
+            if (n_dataset < kAnnMinRows || kp->search_P >= n_dataset) return run_exact_knn_pair(c, sI, sJ, k, out_idx, out_dist);
+            return kgraph_knn_search(c, *kp, pair_i, pair_j, sI, sJ, k, out_idx, out_dist);
+        });
+    });
+}
+
+extern "C" int r3dm_index_kgraph_knn(r3dm_ctx* c, const r3dm_index* ix, const r3dm_kgraph_params* kp, const void* query, uint32_t n_query,
+                                     uint32_t pair_i, uint32_t pair_j, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !ix || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+        int rc = check_kgraph_knn(c, kp, k, ix->img.n, n_query);
+        if (rc != R3DM_OK) return rc;
+        // as r3dm_match_pairs_kgraph scans such views: the exhaustive k-NN of the index, exactly
+        if (ix->img.n < kAnnMinRows || kp->search_P >= ix->img.n) return r3dm_index_knn(c, ix, query, n_query, k, out_idx, out_dist);
+        if (ix->img.dtype == R3DM_BIN || (ix->img.dim & 3u)) { c->err = "kgraph matching needs F32/U8 descriptors with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+        CallCounters counters(c, {&r3dm_stats::n_ann_rows16, &r3dm_stats::n_ann_rows8, &r3dm_stats::n_ann_dot8, &r3dm_stats::n_ann_dist, &r3dm_stats::n_ann_built},
+                              {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
+        return with_index_structure(c, ix, query, n_query,
+            [&](const r3dm_index& x) -> int {
+                if (!x.kgraph_built) return 1;
+                if (x.kgraph_p.index_K != kp->index_K) { c->err = "r3dm_index_kgraph_knn: the index holds a graph of another index_K"; return R3DM_ERR_INVALID; }
+                return R3DM_OK;
+            },
+            [&](r3dm_index& x, uint32_t slot) -> int {
+                const int rcb = ensure_ann_indices(c, {slot}, kp->index_K);
+                if (rcb == R3DM_OK) { x.kgraph_built = true; x.kgraph_p = *kp; }
+                return rcb;
+            },
+            [&](uint32_t sI, uint32_t sJ) { return kgraph_knn_search(c, *kp, pair_i, pair_j, sI, sJ, k, out_idx, out_dist); });
+    });
 }
 
 extern "C" int r3dm_drop_indices(r3dm_ctx* c)

@@ -149,8 +149,9 @@ static HnswView view_of(const HostImage& h)
 }
 
 // searchKnn + ratio test over `jobs` (all of one dim; every sI holds an index), results appended to g in job order
+// knn_k = 0: searchKnn(row, 2) and the ratio test; 1 .. R3DM_KNN_MAX: searchKnn(row, knn_k) of one pair (knn_*_host: knn_k entries per query)
 static int run_hnsw_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, uint32_t ef, r3dm_graph* g,
-                          int32_t* knn_idx_host, float* knn_dist_host)
+                          int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_k = 0)
 {
     bool rows8 = true;                                        // every index view of the batch holds its byte rows (integers 0 .. 255: SIFT bins)
     const int rc = run_ann_batch(c, jobs, g, knn_idx_host, knn_dist_host, [&](const AnnBatch& b) -> int {
@@ -166,7 +167,9 @@ static int run_hnsw_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float r
         R3DM_HIP(c, hipMemcpyAsync(c->h_jobs.p, sj.data(), sizeof(HnswSearchJob) * b.P, hipMemcpyHostToDevice, c->stream));
         HnswSearchParams sp{};
         sp.jobs = c->h_jobs.as<HnswSearchJob>(); sp.n_jobs = b.P;
-        sp.ef = std::max(ef, 2u);                                  // searchKnn: max(ef_, k)
+        // searchKnn: max(ef_, k) (hnswalg.h:765).  The ONE beam of the search: the kernel's heap tests, its LDS carve-up, the launcher's
+        // LDS size and every repeat of the launch below read sp.ef
+        sp.ef = std::max(ef, knn_k ? knn_k : 2u);
         sp.ratio_R = ratio_R;
         sp.rows8 = rows8 ? 1u : 0u;
         sp.dense_steps = r3dm_dev_knob("R3DM_HNSW_DENSE_STEPS", 0) ? 1u : 0u;                // developer build: the round-3 stepping, for A/B runs
@@ -178,7 +181,7 @@ static int run_hnsw_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float r
         for (uint32_t cand_cap = 256;; cand_cap *= 2) {
             sp.cand_cap = cand_cap;
             if (cand_cap > 256) R3DM_HIP(c, hipMemsetAsync(c->d_cnt.p, 0, 64, c->stream));
-            hipError_t e = launch_hnsw_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim);
+            hipError_t e = launch_hnsw_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim, knn_k);
             if (e == hipErrorInvalidValue) { c->err = "HNSW search: unsupported descriptor length (64 / 128 / 144 / 256) or the view / candidate heap exceeds the LDS"; return R3DM_ERR_UNSUPPORTED; }
             R3DM_HIP(c, e);
             uint32_t over = 0;
@@ -189,7 +192,7 @@ static int run_hnsw_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float r
             c->stats.n_hnsw_retries += 1;
         }
         return R3DM_OK;
-    });
+    }, knn_k ? knn_k : 2u);
     if (rc == R3DM_OK && !jobs.empty()) c->stats.n_ann_rows8 += rows8 ? 1 : 0;
     return rc;
 }
@@ -262,19 +265,19 @@ static int adopt_hnsw_arrays(r3dm_ctx* c, HostImage& h, uint32_t n_dataset, cons
     return R3DM_OK;
 }
 
-// two private slots: dataset (+ index) and query
+// two private slots: dataset (+ index) and query.  knn_k = 0: the 2-NN entries; else the k-NN entries
 static int hnsw_knn2_common(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query, uint32_t dim,
-                            const r3dm_hnsw_params* hp, const r3dm_hnsw_arrays* ix, int32_t* out_idx, float* out_dist)
+                            const r3dm_hnsw_params* hp, const r3dm_hnsw_arrays* ix, int32_t* out_idx, float* out_dist, uint32_t knn_k = 0)
 {
     if (!c || !dataset || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
-    if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;
+    if (n_query < 1 || n_dataset < 2 || n_dataset < knn_k) return R3DM_ERR_INVALID;
     if (!hnsw_dim_ok(dim)) { c->err = "HNSW matching needs descriptors of length 64 / 128 / 144 / 256"; return R3DM_ERR_UNSUPPORTED; }
     if (n_dataset > (1u << 18)) { c->err = "HNSW matching: more than 262,144 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
     return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, 0, 1,
                             {&r3dm_stats::n_ann_dist, &r3dm_stats::n_hnsw_launches, &r3dm_stats::n_hnsw_retries},
                             {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search}, [&](uint32_t sI, uint32_t sJ) -> int {
         const int rc = ix ? adopt_hnsw_arrays(c, *c->imgs[sI], n_dataset, ix) : ensure_hnsw_indices(c, {sI}, *hp);
-        return rc != R3DM_OK ? rc : run_hnsw_batch(c, {{0, 1, sI, sJ}}, 1.0f, hp->ef, nullptr, out_idx, out_dist);
+        return rc != R3DM_OK ? rc : run_hnsw_batch(c, {{0, 1, sI, sJ}}, 1.0f, hp->ef, nullptr, out_idx, out_dist, knn_k);
     });
 }
 
@@ -300,6 +303,74 @@ extern "C" int r3dm_hnsw_knn2_on_index(r3dm_ctx* c, const float* dataset, uint32
         int rc = check_hnsw_params(c, &hp);
         if (rc != R3DM_OK) return rc;
         return hnsw_knn2_common(c, dataset, n_dataset, query, n_query, dim, &hp, ix, out_idx, out_dist);
+    });
+}
+
+// ---- k neighbours, k = 1 .. R3DM_KNN_MAX: ArrayMatcher_hnsw::SearchNeighbours with any NN (matcher_hnsw.h:138-173, searchKnn(q, NN))
+extern "C" int r3dm_hnsw_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                             uint32_t dim, const r3dm_hnsw_params* hp, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+        if (k < 1 || k > R3DM_KNN_MAX || n_dataset < k) return R3DM_ERR_INVALID;
+        int rc = check_hnsw_params(c, hp);
+        if (rc != R3DM_OK) return rc;
+        if (n_dataset < kAnnMinRows) { c->err = "r3dm_hnsw_knn: fewer than 128 rows (such views are scanned: r3dm_knn)"; return R3DM_ERR_UNSUPPORTED; }
+        return hnsw_knn2_common(c, dataset, n_dataset, query, n_query, dim, hp, nullptr, out_idx, out_dist, k);
+    });
+}
+
+extern "C" int r3dm_hnsw_knn_on_index(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, uint32_t dim, const r3dm_hnsw_arrays* ix,
+                                      const float* query, uint32_t n_query, uint32_t ef, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !ix || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+        if (k < 1 || k > R3DM_KNN_MAX || n_dataset < k) return R3DM_ERR_INVALID;
+        r3dm_hnsw_params hp{};
+        hp.M = ix->M; hp.ef = ef; hp.seed = 0;
+        int rc = check_hnsw_params(c, &hp);
+        if (rc != R3DM_OK) return rc;
+        return hnsw_knn2_common(c, dataset, n_dataset, query, n_query, dim, &hp, ix, out_idx, out_dist, k);
+    });
+}
+
+extern "C" int r3dm_index_hnsw_knn(r3dm_ctx* c, const r3dm_index* ix, const r3dm_hnsw_params* hp, const void* query, uint32_t n_query,
+                                   uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !ix || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+        if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || ix->img.n < k) return R3DM_ERR_INVALID;
+        int rc = check_hnsw_params(c, hp);
+        if (rc != R3DM_OK) return rc;
+        // as r3dm_match_pairs_hnsw scans such views: the exhaustive k-NN of the index, exactly
+        if (ix->img.n < kAnnMinRows) return r3dm_index_knn(c, ix, query, n_query, k, out_idx, out_dist);
+        if (ix->img.dtype == R3DM_BIN || !hnsw_dim_ok(ix->img.dim)) { c->err = "HNSW matching needs F32/U8 descriptors of length 64 / 128 / 144 / 256"; return R3DM_ERR_UNSUPPORTED; }
+        if (ix->img.n > (1u << 18)) { c->err = "HNSW matching: more than 262,144 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
+        CallCounters counters(c, {&r3dm_stats::n_ann_dist, &r3dm_stats::n_hnsw_launches, &r3dm_stats::n_hnsw_retries, &r3dm_stats::n_ann_built},
+                              {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
+        return with_index_structure(c, ix, query, n_query,
+            [&](const r3dm_index& x) -> int {
+                if (!x.hnsw_built) return 1;
+                if (x.hnsw_p.M != hp->M || x.hnsw_p.ef_construction != hp->ef_construction || x.hnsw_p.seed != hp->seed) {
+                    c->err = "r3dm_index_hnsw_knn: the index holds an HNSW graph built from other parameters (M, ef_construction, seed)";
+                    return R3DM_ERR_INVALID;
+                }
+                return R3DM_OK;
+            },
+            [&](r3dm_index& x, uint32_t slot) -> int {
+                // the batch build makes the exact 32-NN graph its layer-0 candidates come from in the view's ann_adj / ann_deg: a graph the
+                // KGraph arm may have built on this index (another index_K, searched right now by another context) is set aside for the
+                // build and put back behind it; the build's own graph is scratch
+                struct SetAside {
+                    r3dm_ctx* c; HostImage& h; const DevBuf adj, deg; const uint32_t K;
+                    SetAside(r3dm_ctx* c_, HostImage& h_) : c(c_), h(h_), adj(h_.ann_adj), deg(h_.ann_deg), K(h_.ann_K) { h.ann_adj = DevBuf(); h.ann_deg = DevBuf(); h.ann_K = 0; }
+                    ~SetAside() { (void)hipStreamSynchronize(c->stream); h.ann_adj.release(); h.ann_deg.release(); h.ann_adj = adj; h.ann_deg = deg; h.ann_K = K; }
+                } aside(c, *c->imgs[slot]);
+                const int rcb = ensure_hnsw_indices(c, {slot}, *hp);
+                if (rcb == R3DM_OK) { x.hnsw_built = true; x.hnsw_p = *hp; }
+                return rcb;
+            },
+            [&](uint32_t sI, uint32_t sJ) { return run_hnsw_batch(c, {{0, 1, sI, sJ}}, 1.0f, hp->ef, nullptr, out_idx, out_dist, k); });
     });
 }
 

@@ -11,7 +11,7 @@
 // compaction + ordering + de-duplication of nn_idx[pair][*] (finalize_pairs_kernel), copy back, append the non-empty
 // pairs to `g` in job order.  Shared by the exhaustive and the graph-search drivers.
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
-                          uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host)
+                          uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols)
 {
     const uint32_t P = (uint32_t)jobs.size();
     // ---- finalisation: compact + order + de-duplicate, per pair
@@ -58,9 +58,9 @@ int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_str
         h_m = static_cast<const r3dm_match*>(c->pin_out.p);
     }
     if (knn_idx_host) {
-        // single-pair use (r3dm_knn2): copy the raw 2-NN of pair 0
-        R3DM_HIP(c, hipMemcpyAsync(knn_idx_host, c->d_knn_idx.p, (size_t)max_nJ * 8, hipMemcpyDeviceToHost, c->stream));
-        R3DM_HIP(c, hipMemcpyAsync(knn_dist_host, c->d_knn_dist.p, (size_t)max_nJ * 8, hipMemcpyDeviceToHost, c->stream));
+        // single-pair use (r3dm_knn2; the k-lists of the approximate arms: knn_cols entries per query): copy the raw lists of pair 0
+        R3DM_HIP(c, hipMemcpyAsync(knn_idx_host, c->d_knn_idx.p, (size_t)max_nJ * knn_cols * 4, hipMemcpyDeviceToHost, c->stream));
+        R3DM_HIP(c, hipMemcpyAsync(knn_dist_host, c->d_knn_dist.p, (size_t)max_nJ * knn_cols * 4, hipMemcpyDeviceToHost, c->stream));
     }
     R3DM_HIP(c, hipStreamSynchronize(c->stream));
 
@@ -436,7 +436,7 @@ extern "C" void r3dm_index_destroy(r3dm_index* ix)
 
 // an index search's two private slots: the index mounted into slot_index (aliases of its buffers, for this call only) beside the
 // freshly staged query view in slot_query
-static int mount_index_beside_queries(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t slot_index, uint32_t slot_query)
+int mount_index_beside_queries(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t slot_index, uint32_t slot_query)
 {
     r3dm_index* mix = const_cast<r3dm_index*>(ix);
     { std::lock_guard<std::mutex> lk(mix->mu); c->imgs[slot_index]->mount(mix); }
@@ -575,6 +575,17 @@ static int knn_by_knn2(r3dm_ctx* c, uint32_t k, uint32_t n_query, int32_t* out_i
     }
     if (rc == R3DM_OK) c->stats.n_queries = n_query;
     return rc;
+}
+
+// the exact k nearest rows of the view in slot sI for every row of the view in slot sJ, by the rule of r3dm_knn: k <= 2 on the 2-NN path
+// (the small views of the approximate arms' k-NN entries are answered here, as their 2-NN siblings answer them with run_match_batch)
+int run_exact_knn_pair(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    const uint32_t n_query = c->imgs[sJ]->n;
+    if (k <= 2 && c->imgs[sI]->n >= 2)
+        return knn_by_knn2(c, k, n_query, out_idx, out_dist,
+                           [&](int32_t* idx, float* dist) { return run_match_batch(c, {{0, 1, sI, sJ}}, 1.0f, nullptr, idx, dist); });
+    return run_knn_batch(c, sI, sJ, k, out_idx, out_dist);
 }
 
 static int r3dm_knn_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,

@@ -163,8 +163,9 @@ static MrptView mrpt_view_of(const HostImage& h)
 }
 
 // Mrpt::query + ratio test over `jobs` (every sI holds an index), results appended to g in job order
+// knn_k = 0: Mrpt::query(row, 2, votes) and the ratio test; 1 .. R3DM_KNN_MAX: Mrpt::query(row, knn_k, votes) of one pair
 static int run_mrpt_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio, uint32_t votes, r3dm_graph* g,
-                          int32_t* knn_idx_host, float* knn_dist_host)
+                          int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_k = 0)
 {
     std::vector<MrptQueryJob> sj(jobs.size());               // outlives the frame's synchronisation
     return run_ann_batch(c, jobs, g, knn_idx_host, knn_dist_host, [&](const AnnBatch& b) -> int {
@@ -184,11 +185,11 @@ static int run_mrpt_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float r
         qp.jobs = c->h_jobs.as<MrptQueryJob>(); qp.n_jobs = b.P;
         qp.votes = votes; qp.elected_cap = elected_cap; qp.ratio = ratio;
         qp.nn_idx = b.nn_idx; qp.knn_idx = b.knn_idx; qp.knn_dist = b.knn_dist; qp.n_comps = b.n_comps;
-        const hipError_t e = launch_mrpt_query(c->stream, qp, b.max_nJ, b.max_nI, max_pool);
+        const hipError_t e = launch_mrpt_query(c->stream, qp, b.max_nJ, b.max_nI, max_pool, knn_k);
         if (e == hipErrorInvalidValue) { c->err = "MRPT query: vote bytes + elected list of the largest index view of the batch exceed the 160 KB of LDS a wavefront can have"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, e);
         return R3DM_OK;
-    });
+    }, knn_k ? knn_k : 2u);
 }
 
 static int r3dm_match_pairs_mrpt_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,
@@ -241,6 +242,67 @@ extern "C" int r3dm_mrpt_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_data
             if (rci != R3DM_OK) return rci;
             return run_mrpt_batch(c, {{0, 1, sI, sJ}}, 1.0f, mp->votes, nullptr, out_idx, out_dist);
         });
+    });
+}
+
+// ---- k neighbours, k = 1 .. R3DM_KNN_MAX: ArrayMatcher_mrpt::SearchNeighbours with any NN (matcher_mrpt.h:186-251)
+// what r3dm_mrpt_knn2 refuses, for a dataset of n rows of length dim
+static int check_mrpt_view(r3dm_ctx* c, const char* who, uint32_t n, uint32_t dim, const r3dm_mrpt_params& mp)
+{
+    if (!mrpt_dim_ok(dim)) { c->err = "MRPT matching needs descriptors of a length that is a multiple of 4, at most 512"; return R3DM_ERR_UNSUPPORTED; }
+    if (n < kAnnMinRows) { c->err = std::string(who) + ": fewer than 128 rows (such views are scanned: r3dm_knn)"; return R3DM_ERR_UNSUPPORTED; }
+    if (n > (1u << 17)) { c->err = "MRPT matching: more than 131,072 rows in one view"; return R3DM_ERR_UNSUPPORTED; }
+    if (!mrpt_query_fits_lds(n, mp)) { c->err = std::string(who) + ": the vote table of this many rows exceeds a wavefront's LDS with these parameters (such views are scanned: r3dm_knn)"; return R3DM_ERR_UNSUPPORTED; }
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_mrpt_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                             uint32_t dim, const r3dm_mrpt_params* mp, uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !dataset || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+        if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || n_dataset < 2 || n_dataset < k) return R3DM_ERR_INVALID;
+        int rc = check_mrpt_params(c, mp);
+        if (rc == R3DM_OK) rc = check_mrpt_view(c, "r3dm_mrpt_knn", n_dataset, dim, *mp);
+        if (rc != R3DM_OK) return rc;
+        return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, 0, 1, {&r3dm_stats::n_ann_dist},
+                                {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search}, [&](uint32_t sI, uint32_t sJ) -> int {
+            const int rci = ensure_mrpt_indices(c, {sI}, *mp);
+            if (rci != R3DM_OK) return rci;
+            return run_mrpt_batch(c, {{0, 1, sI, sJ}}, 1.0f, mp->votes, nullptr, out_idx, out_dist, k);
+        });
+    });
+}
+
+extern "C" int r3dm_index_mrpt_knn(r3dm_ctx* c, const r3dm_index* ix, const r3dm_mrpt_params* mp, const void* query, uint32_t n_query,
+                                   uint32_t k, int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        if (!c || !ix || !query || !out_idx || !out_dist) return R3DM_ERR_INVALID;
+        if (k < 1 || k > R3DM_KNN_MAX || n_query < 1 || ix->img.n < k) return R3DM_ERR_INVALID;
+        int rc = check_mrpt_params(c, mp);
+        if (rc != R3DM_OK) return rc;
+        // as r3dm_match_pairs_mrpt scans such views: the exhaustive k-NN of the index, exactly
+        if (ix->img.n < kAnnMinRows) return r3dm_index_knn(c, ix, query, n_query, k, out_idx, out_dist);
+        if (ix->img.dtype == R3DM_BIN) { c->err = "MRPT matching needs F32/U8 descriptors"; return R3DM_ERR_UNSUPPORTED; }
+        rc = check_mrpt_view(c, "r3dm_index_mrpt_knn", ix->img.n, ix->img.dim, *mp);
+        if (rc != R3DM_OK) return rc;
+        CallCounters counters(c, {&r3dm_stats::n_ann_dist, &r3dm_stats::n_ann_built}, {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
+        return with_index_structure(c, ix, query, n_query,
+            [&](const r3dm_index& x) -> int {
+                if (!x.mrpt_built) return 1;
+                if (x.mrpt_p.n_trees != mp->n_trees || x.mrpt_p.depth != mp->depth || x.mrpt_p.density != mp->density || x.mrpt_p.seed != mp->seed) {
+                    c->err = "r3dm_index_mrpt_knn: the index holds a forest built from other parameters (n_trees, depth, density, seed)";
+                    return R3DM_ERR_INVALID;
+                }
+                return R3DM_OK;
+            },
+            [&](r3dm_index& x, uint32_t slot) -> int {
+                const int rcb = ensure_mrpt_indices(c, {slot}, *mp);
+                if (rcb == R3DM_OK) { x.mrpt_built = true; x.mrpt_p = *mp; }
+                return rcb;
+            },
+            [&](uint32_t sI, uint32_t sJ) { return run_mrpt_batch(c, {{0, 1, sI, sJ}}, 1.0f, mp->votes, nullptr, out_idx, out_dist, k); });
     });
 }
 

@@ -2,6 +2,8 @@
 // (f32 tiles) and kernels_match_knn16.hip (bf16 tiles, split-f16 planes):
 //   TopK<KL>, topk_init, topk_push     the KL smallest keys of a lane half with their rows, and the (KL + 1)-th key as its bound
 //   topk_push_exact                    the same list on exact keys: no bound is kept (kernels_match_knn16.hip, integer tiles)
+//   topk_push_lex, topk_wave_select    the same list for rows in any order, and the k smallest entries of a wavefront's 64 lists
+//                                      (kernels_mrpt.hip: the exact re-rank of the elected rows)
 //   knn_lex_less                       the project's one order: (distance, dataset row)
 //   knnk_finish<KL, MODE>              merge the two lane halves, re-score, rank, certify the k-th, write or list for the exact scan
 // The tile steps that fold keys into these lists, and into Top2, are in kernels_match_tiles.hpp (which includes this header).
@@ -70,6 +72,50 @@ __device__ __forceinline__ void topk_push_exact(TopK<KL>& s, float key, uint32_t
     }
     s.d[0] = __builtin_amdgcn_fmed3f(-R3DM_INF, s.d[0], key);
     s.i[0] = c[0] ? idx : s.i[0];
+}
+
+// The same list for rows that arrive in ANY order (kernels_mrpt.hip: the elected rows of a query, in the order their votes came in):
+// the insert compares (key, row) pairs, so the list is the lexicographic top-KL whatever the order.  No bound is kept either.
+template <int KL>
+__device__ __forceinline__ void topk_push_lex(TopK<KL>& s, float key, uint32_t idx)
+{
+    bool c[KL];
+#pragma unroll
+    for (int j = 0; j < KL; ++j) c[j] = knn_lex_less(key, idx, s.d[j], s.i[j]);
+#pragma unroll
+    for (int j = KL - 1; j >= 1; --j) {                 // downwards: d[j - 1], i[j - 1] are still the old ones
+        const float td = c[j] ? key : s.d[j];
+        const uint32_t ti = c[j] ? idx : s.i[j];
+        s.d[j] = c[j - 1] ? s.d[j - 1] : td;
+        s.i[j] = c[j - 1] ? s.i[j - 1] : ti;
+    }
+    s.d[0] = c[0] ? key : s.d[0];
+    s.i[0] = c[0] ? idx : s.i[0];
+}
+
+// The k smallest entries, under (key, row), of the lists the 64 lanes of a wavefront hold (rows distinct across lanes; lists ascending):
+// k rounds of a wave-wide minimum over the lists' heads, the owner of a round's minimum moves its list up.  emit(j, key, row) runs in
+// every lane with the j-th smallest entry, (+inf, kNone) once the lists are exhausted.  The lists are consumed.
+template <int KL, class Emit>
+__device__ __forceinline__ void topk_wave_select(TopK<KL>& s, uint32_t k, Emit&& emit)
+{
+#pragma unroll
+    for (int j = 0; j < KL; ++j) {
+        if ((uint32_t)j >= k) break;                     // wave-uniform
+        float bd = s.d[0]; uint32_t bi = s.i[0];
+#pragma unroll
+        for (int m = 32; m > 0; m >>= 1) {
+            const float od = __shfl_xor(bd, m); const uint32_t oi = (uint32_t)__shfl_xor((int)bi, m);
+            const bool take = knn_lex_less(od, oi, bd, bi);
+            bd = take ? od : bd; bi = take ? oi : bi;
+        }
+        if (bi != kNone && s.i[0] == bi) {
+#pragma unroll
+            for (int t = 0; t + 1 < KL; ++t) { s.d[t] = s.d[t + 1]; s.i[t] = s.i[t + 1]; }
+            s.d[KL - 1] = R3DM_INF; s.i[KL - 1] = kNone;
+        }
+        emit((uint32_t)j, bd, bi);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -662,6 +662,12 @@ struct r3dm_index {
     int device = 0;
     HostImage img;                              // (statistics included: HostImage::stat_bits)
     std::mutex mu;                              // layouts staged after Build (a flag switched on later) are added under this lock
+    // the approximate arms' structures (img.ann_* / hnsw_* / mrpt_*) are built on first use under the lock too, from the first call's
+    // build parameters, which are kept here: a later call that names others is refused, nothing is ever rebuilt under a search's feet
+    bool kgraph_built = false, hnsw_built = false, mrpt_built = false;
+    r3dm_kgraph_params kgraph_p{};
+    r3dm_hnsw_params hnsw_p{};
+    r3dm_mrpt_params mrpt_p{};
 };
 
 inline void HostImage::mount(r3dm_index* ix) { *this = ix->img; borrowed = true; owner = ix; }
@@ -677,8 +683,12 @@ int ensure_layouts(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t want, bool
 int ensure_layouts_image(r3dm_ctx* c, HostImage& h, uint32_t want);        // (no table entry involved; the caller publishes)
 int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g,
                     int32_t* knn_idx_host, float* knn_dist_host);
+// knn_cols: entries per query in d_knn_idx / d_knn_dist (2: the 2-NN kernels; k: the k-list kernels of the approximate arms)
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
-                   uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host);
+                   uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols = 2);
+int run_exact_knn_pair(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int32_t* out_idx, float* out_dist);
+// an index search's two private slots: the index mounted into slot_index beside the freshly staged query view in slot_query
+int mount_index_beside_queries(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t slot_index, uint32_t slot_query);
 int ensure_ann_indices(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t K);
 int stage_into_slot(r3dm_ctx* c, uint32_t slot, uint32_t view_id, uint32_t width, uint32_t height,
                     const void* desc, uint32_t n, uint32_t dim, r3dm_dtype dtype, const float* xy);
@@ -707,7 +717,16 @@ struct AnnBatch {
     uint32_t* nn_idx; int32_t* knn_idx; float* knn_dist; unsigned long long* n_comps;
 };
 int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host,
-                  const std::function<int(const AnnBatch&)>& launch);
+                  const std::function<int(const AnnBatch&)>& launch, uint32_t knn_cols = 2);
+
+// ---- k-NN through an arm's structure on an r3dm_index (r3dm_index_kgraph_knn / _hnsw_knn / _mrpt_knn)
+// state(image of the index): R3DM_OK = the arm's structure is there and was built from these build parameters, 1 = not built yet,
+// R3DM_ERR_INVALID = built from others (c->err set).  Not built: build(slot) runs ONCE, under the index's lock, on a slot that holds the
+// index's image for that long.  Then the index is mounted beside the staged queries and search(slot of the index, slot of the queries)
+// runs, outside the lock: any context of the device, several at a time.
+int with_index_structure(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query,
+                         const std::function<int(const r3dm_index&)>& state, const std::function<int(r3dm_index&, uint32_t slot)>& build,
+                         const std::function<int(uint32_t sI, uint32_t sJ)>& search);
 
 // An array entry of an arm (r3dm_kgraph_knn2 and its relatives): two private slots, dataset and query staged as F32 under the view ids
 // (id_i, id_j), the call's counters (CallCounters), then body(slot of the dataset, slot of the queries)

@@ -183,7 +183,8 @@ struct MrptQueryParams {
 hipError_t launch_mrpt_project(hipStream_t st, const float* rows, uint32_t n, uint32_t dim, const float* R, uint32_t n_trees, uint32_t depth, float* proj);
 hipError_t launch_mrpt_trees(hipStream_t st, const float* proj, uint32_t n, uint32_t n_trees, uint32_t depth, uint32_t cap, unsigned long long* keys,
                              int32_t* leaves, float* splits);
-hipError_t launch_mrpt_query(hipStream_t st, const MrptQueryParams& P, uint32_t max_nq, uint32_t max_n, uint32_t max_pool);
+// knn_k = 0: the 2-NN kernel (nn_idx, optional 2-lists); 1 .. R3DM_KNN_MAX: the k-list kernel (knn_idx / knn_dist [slot][knn_k], no ratio test)
+hipError_t launch_mrpt_query(hipStream_t st, const MrptQueryParams& P, uint32_t max_nq, uint32_t max_n, uint32_t max_pool, uint32_t knn_k = 0);
 
 struct HnswBuildJob {
     const float*    rows;
@@ -465,8 +466,10 @@ size_t     filter_F_lds_bytes(uint32_t m_cap, int model_kind);
 hipError_t launch_ann_build(hipStream_t st, const AnnBuildParams& P, uint32_t n_jobs, uint32_t max_n, uint32_t dim, bool rows8);
 // rows_mode: 0 = f32 rows, 1 = ImgDev::ann_rows16 (bf16), 2 = ImgDev::ann_rows8 (u8) -- every indexed view of the batch must hold that copy;
 // 3 = u8 rows on both sides (the query views hold ann_rows8 too): distances as integer dot products
-hipError_t launch_ann_search(hipStream_t st, const AnnSearchParams& P, uint32_t max_nJ, uint32_t max_nI, uint32_t dim, int rows_mode);
-hipError_t launch_hnsw_search(hipStream_t st, const HnswSearchParams& P, uint32_t max_nq, uint32_t max_n, uint32_t dim);
+// knn_k = 0: the 2-NN search kernels (nn_idx, optional 2-lists); 1 .. R3DM_KNN_MAX: their k-list instantiations, which write
+// knn_idx / knn_dist [slot][knn_k] and no ratio test (pool_cap = knn_k + P; the caller sets ef = max(ef, knn_k))
+hipError_t launch_ann_search(hipStream_t st, const AnnSearchParams& P, uint32_t max_nJ, uint32_t max_nI, uint32_t dim, int rows_mode, uint32_t knn_k = 0);
+hipError_t launch_hnsw_search(hipStream_t st, const HnswSearchParams& P, uint32_t max_nq, uint32_t max_n, uint32_t dim, uint32_t knn_k = 0);
 hipError_t launch_hnsw_link(hipStream_t st, const HnswBuildParams& P, uint32_t n_jobs, uint32_t max_items, uint32_t dim);
 hipError_t launch_ann_rows16(hipStream_t st, const float* rows, uint16_t* rows16, size_t n_elems);
 hipError_t launch_ann_rows8(hipStream_t st, const float* rows, uint8_t* rows8, size_t n_elems);
