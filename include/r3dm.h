@@ -282,7 +282,7 @@ void r3dm_index_destroy(r3dm_index* index);
  * or the popcount kernel (BIN).
  *   IGNORED there: r3dm_set_integer_mfma / _split_mfma / _hamming_mfma (those nominators keep 2-lists).  None of their counters
  *     (n_integer_mfma, n_split_mfma, n_hamming_mfma, n_counts_mfma) moves on such a call, whatever any switch says.
- *   NOT ignored: r3dm_set_knn_narrow_tiles, the k-list kernels' own switch (below).
+ *   NOT ignored: r3dm_set_knn_narrow_tiles and r3dm_set_knn_hamming_tiles, the k-list kernels' own switches (below).
  * Lengths without a tensor kernel (> 256 elements) are scanned exactly, as in r3dm_match_pairs.  r3dm_stats.n_queries and
  * .n_exact_fallback (queries answered by the exact scan) describe the call. */
 #define R3DM_KNN_MAX 8
@@ -298,6 +298,14 @@ void r3dm_index_destroy(r3dm_index* index);
  * The layouts are staged on first use; on an r3dm_index that is once per index, under its lock, whichever context asks first.
  * k <= 2 (the 2-NN path) does not consult this switch. */
 int r3dm_set_knn_narrow_tiles(r3dm_ctx* ctx, int enable);
+/* Opt-in (default off), same results bit for bit: the switch of BIN rows, which r3dm_set_knn_narrow_tiles leaves alone.  While on, a
+ * call that runs on the k-list kernels (k >= 3; k = 1 on a one-row dataset) with BIN views runs on the i8 MFMA tiles of
+ * r3dm_set_hamming_mfma -- one byte per bit, keys popcount(a) - 2 a.b -- with exact k-lists: the keys are integers, so nothing is
+ * certified or scanned (r3dm_stats.n_knn_hamming_tiles counts the launch; .n_exact_fallback is 0; n_hamming_mfma, the 2-NN kernel's
+ * counter, does not move).  With the switch off such a call runs the popcount k-list kernel, as before.  F32 / U8 views and k <= 2
+ * never consult it.  The byte-per-bit tiles are staged on first use; on an r3dm_index that is once per index, under its lock,
+ * whichever context asks first. */
+int r3dm_set_knn_hamming_tiles(r3dm_ctx* ctx, int enable);
 int r3dm_knn(r3dm_ctx* ctx, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
              uint32_t dim, r3dm_dtype dtype, uint32_t k, int32_t* out_idx, float* out_dist);
 /* same mounting, locking and "any context of the index's device" rules as r3dm_index_knn2 */
@@ -755,6 +763,8 @@ typedef struct {
     /* r3dm_knn / r3dm_index_knn with r3dm_set_knn_narrow_tiles on */
     uint64_t n_knn_integer_tiles;  /* launches of the K-list nominator on the bf16 tiles (integer-valued rows: exact lists, nothing certified or scanned)  */
     uint64_t n_knn_split_tiles;    /* launches of the K-list nominator on the split-f16 planes (real-valued rows)                                          */
+    /* ... with r3dm_set_knn_hamming_tiles on */
+    uint64_t n_knn_hamming_tiles;  /* launches of the K-list nominator on the i8 tiles (BIN rows: exact lists, nothing certified or scanned)               */
 } r3dm_stats;
 int r3dm_get_stats(const r3dm_ctx* ctx, r3dm_stats* out);
 

@@ -32,7 +32,7 @@ EXPORTS = [
     "r3dm_mrpt_preset", "r3dm_match_pairs_mrpt", "r3dm_mrpt_knn2", "r3dm_mrpt_index", "r3dm_multi_match_pairs_mrpt",
     "r3dm_kgraph_knn", "r3dm_hnsw_knn", "r3dm_hnsw_knn_on_index", "r3dm_mrpt_knn", "r3dm_index_kgraph_knn", "r3dm_index_hnsw_knn", "r3dm_index_mrpt_knn",
     "r3dm_set_integer_mfma", "r3dm_set_split_mfma", "r3dm_set_hamming_mfma", "r3dm_index_create", "r3dm_index_knn2", "r3dm_index_destroy",
-    "r3dm_knn", "r3dm_index_knn", "r3dm_set_knn_narrow_tiles",
+    "r3dm_knn", "r3dm_index_knn", "r3dm_set_knn_narrow_tiles", "r3dm_set_knn_hamming_tiles",
     "r3dm_multi_create", "r3dm_multi_destroy", "r3dm_multi_num_devices", "r3dm_multi_ctx", "r3dm_multi_last_error",
     "r3dm_multi_set_image", "r3dm_multi_transfer_counts", "r3dm_multi_set_intrinsics", "r3dm_multi_clear_images", "r3dm_multi_set_integer_mfma",
     "r3dm_multi_match_pairs", "r3dm_multi_match_pairs_kgraph", "r3dm_multi_match_pairs_hnsw", "r3dm_multi_filter_F", "r3dm_multi_filter_H", "r3dm_multi_filter_E", "r3dm_shard_pairs",
@@ -78,7 +78,7 @@ class Stats(C.Structure):
                 ("ms_liop_wall", C.c_double), ("ms_feature_files", C.c_double),
                 ("n_hnsw_launches", C.c_uint64), ("n_hnsw_retries", C.c_uint64), ("n_counts_mfma", C.c_uint64),
                 ("detect_compulsory_bytes", C.c_double), ("n_filter_workgroups", C.c_uint64), ("n_filter_coop_pairs", C.c_uint64),
-                ("n_knn_integer_tiles", C.c_uint64), ("n_knn_split_tiles", C.c_uint64)]
+                ("n_knn_integer_tiles", C.c_uint64), ("n_knn_split_tiles", C.c_uint64), ("n_knn_hamming_tiles", C.c_uint64)]
 
 
 class GuidedStats(C.Structure):
@@ -308,6 +308,7 @@ def load_library():
     L.r3dm_set_split_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
+    L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
     L.r3dm_index_create.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
     L.r3dm_index_knn2.argtypes = [vp, vp, vp, u32, vp, vp]
     L.r3dm_index_destroy.argtypes = [vp]; L.r3dm_index_destroy.restype = None
@@ -948,6 +949,11 @@ class Context:
         """opt-in K-list nominators on the bf16 tiles / split-f16 planes for knn / index_knn with k >= 3 (include/r3dm.h:
         r3dm_set_knn_narrow_tiles); same results, Stats.n_knn_integer_tiles / n_knn_split_tiles tell which tiles a call ran on"""
         self._check(self._L.r3dm_set_knn_narrow_tiles(self._h, int(bool(enable))), "r3dm_set_knn_narrow_tiles")
+
+    def set_knn_hamming_tiles(self, enable: bool = True):
+        """opt-in K-list nominator on the i8 MFMA tiles for knn / index_knn with k >= 3 on binary rows (include/r3dm.h:
+        r3dm_set_knn_hamming_tiles); same results, Stats.n_knn_hamming_tiles counts the launch"""
+        self._check(self._L.r3dm_set_knn_hamming_tiles(self._h, int(bool(enable))), "r3dm_set_knn_hamming_tiles")
 
     def set_split_mfma(self, enable: bool = True):
         """opt-in split-f16 nominator for real-valued descriptors (include/r3dm.h: r3dm_set_split_mfma)"""

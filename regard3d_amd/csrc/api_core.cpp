@@ -758,6 +758,13 @@ extern "C" int r3dm_set_knn_narrow_tiles(r3dm_ctx* c, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_set_knn_hamming_tiles(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->knn_hamming_tiles = (enable != 0);
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_set_hamming_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;

@@ -471,6 +471,8 @@ extern "C" int r3dm_index_knn2(r3dm_ctx* c, const r3dm_index* ix, const void* qu
 // the pair is planned like a one-job 2-NN batch with the integer and split switches on (plan_batch: the conditions under which the
 // bf16 tiles are exact and the split planes usable are stated there and nowhere else) and runs on the K-list kernel of the tiles the
 // plan names (kernels_match_knn16.hip).  A launcher that has no kernel for the launch leaves the pair on the f32 K-list kernel.
+// Binary views have a switch of their own, r3dm_set_knn_hamming_tiles: while it is on, both views are staged as byte-per-bit tiles and
+// the pair runs on the i8 K-list kernel (kernels_match_knn8.hip); a launcher without a kernel leaves it on the popcount K-list kernel.
 static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int32_t* out_idx_host, float* out_dist_host)
 {
     { const int rcs = sync_view_stats(c); if (rcs != R3DM_OK) return rcs; }
@@ -481,6 +483,7 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
     // the nominees are re-scored on the row-major rows, and the exact scan reads them (on the integer tiles nothing is re-scored, but
     // the in-kernel re-check of the exact-pair condition still has the scan behind it)
     if (dtype != R3DM_BIN) { const int rcl = ensure_layouts(c, {sI, sJ}, kLayRows | plan.layouts); if (rcl != R3DM_OK) return rcl; }
+    else if (c->knn_hamming_tiles) { const int rcl = ensure_layouts(c, {sI, sJ}, kLayBin8); if (rcl != R3DM_OK) return rcl; }
     const size_t out_bytes = (size_t)nq * k * 4;
     R3DM_HIP(c, c->d_knn_idx.ensure(out_bytes));
     R3DM_HIP(c, c->d_knn_dist.ensure(out_bytes));
@@ -500,7 +503,17 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
     R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
     uint64_t n_fallback = 0;
     if (dtype == R3DM_BIN) {
-        R3DM_HIP(c, launch_hamming_knnk(c->stream, kp, words, nq));
+        hipError_t e = hipErrorInvalidValue;
+        if (c->knn_hamming_tiles) {
+            e = launch_hamming_knnk_mfma(c->stream, kp, words, c->imgs[sJ]->n_tiles);
+            if (e == hipSuccess) c->stats.n_knn_hamming_tiles += 1;
+        }
+        if (e == hipErrorInvalidValue || e == hipErrorNotSupported) {
+            // no i8-tile kernel for this launch (or none asked for): the popcount K-list kernel
+            (void)hipGetLastError();
+            e = launch_hamming_knnk(c->stream, kp, words, nq);
+        }
+        R3DM_HIP(c, e);
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
     } else {
         const uint32_t ntI = c->imgs[sI]->n_tiles, ntJ = c->imgs[sJ]->n_tiles;
@@ -554,11 +567,12 @@ static int run_knn_batch(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int3
 }
 
 // the counters a k-NN call reports: its queries, how many the exact scan answered, which narrow tiles its K-list kernel ran on
-// (r3dm_set_knn_narrow_tiles) -- and the 2-NN opt-in paths' counters, which hold 0 after a call on the k-list kernels;
+// (r3dm_set_knn_narrow_tiles, r3dm_set_knn_hamming_tiles) -- and the 2-NN opt-in paths' counters, which hold 0 after a call on the k-list kernels;
 // ms_match_kernels holds the HIP-event time of the call's first kernel (tools/knn_perf.py)
 static constexpr std::initializer_list<uint64_t r3dm_stats::*> kKnnCounters = {
     &r3dm_stats::n_integer_mfma, &r3dm_stats::n_split_mfma, &r3dm_stats::n_hamming_mfma, &r3dm_stats::n_counts_mfma,
-    &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries, &r3dm_stats::n_knn_integer_tiles, &r3dm_stats::n_knn_split_tiles};
+    &r3dm_stats::n_exact_fallback, &r3dm_stats::n_queries, &r3dm_stats::n_knn_integer_tiles, &r3dm_stats::n_knn_split_tiles,
+    &r3dm_stats::n_knn_hamming_tiles};
 
 // k <= 2 is the 2-NN path itself, bit-identical to r3dm_knn2 / r3dm_index_knn2 by construction: knn2(idx, dist) runs that call; k = 1
 // keeps the first column of its result

@@ -1,7 +1,8 @@
 // kernels_match_knn_lists.hpp -- the K-lists of the exhaustive k-NN kernels and their shared tail, included by kernels_match_knn.hip
 // (f32 tiles) and kernels_match_knn16.hip (bf16 tiles, split-f16 planes):
 //   TopK<KL>, topk_init, topk_push     the KL smallest keys of a lane half with their rows, and the (KL + 1)-th key as its bound
-//   topk_push_exact                    the same list on exact keys: no bound is kept (kernels_match_knn16.hip, integer tiles)
+//   topk_push_exact                    the same list on exact keys: no bound is kept (kernels_match_knn16.hip, integer tiles;
+//                                      kernels_match_knn8.hip, i8 tiles)
 //   topk_push_lex, topk_wave_select    the same list for rows in any order, and the k smallest entries of a wavefront's 64 lists
 //                                      (kernels_mrpt.hip: the exact re-rank of the elected rows)
 //   knn_lex_less                       the project's one order: (distance, dataset row)

@@ -7,6 +7,7 @@
 //   kTestsEachKey, kTestsEachKeyExact  whether a list policy guards every single push with a ballot of its own
 //   l2_tile_step                       one dataset tile on the f32 tiles          (v_mfma_f32_32x32x2_f32)
 //   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
+//   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
 //   bf16x2_times_m2                    -2 x a packed pair of bf16 integers (the query fragments of the integer tiles)
 //   pair_grid                          host: qb_per_pair, xcd_map, the grid of a 2-NN launch and its bound
@@ -220,6 +221,80 @@ __device__ __forceinline__ void int_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgp
         __builtin_amdgcn_sched_barrier(0);
     }
 }
+
+// ------------------------------------------------------------------------------------------------
+// The integer step on dataset tiles SHARED by the four waves of a workgroup through LDS (l2_knn2_int_lds_kernel and
+// l2_knn2_int_ring_kernel, kernels_match_hamming.hip, with Top2; hamming_knnk_mfma_kernel, kernels_match_knn8.hip, with TopK<KL>):
+// the fragments of tile t come from lds_cur through a PF-deep register window that runs on into lds_nxt, the next tile's norms from
+// nrm_nxt; nothing is loaded from global memory here.  The list side is int_tile_step's.
+// ------------------------------------------------------------------------------------------------
+typedef __attribute__((address_space(3))) void* lds_vp;
+typedef const __attribute__((address_space(1))) void* glb_vp;
+
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef int i32x16 __attribute__((ext_vector_type(16)));
+
+// OPS 0: bf16 operands (16 dims per block, v_mfma_f32_32x32x16_bf16).  OPS 1: i8 operands holding the BITS of binary
+// descriptors as 0 / 1 (32 bits per block, v_mfma_i32_32x32x32_i8): with C = popcount(a) and B = -2 b the accumulator is
+// popcount(a) - 2 a.b = Hamming(a, b) - popcount(b), an exact integer.  The accumulators are biased by 0x3F800000 (the bits of
+// 1.0f) through the C operand: the int32 key k and the float with the bits k + 0x3F800000 order identically (normal positive
+// floats, |k| <= 2048 steps of one ulp), so the float list machinery below runs on them unchanged.
+template <int GB, int NJ, int PF, int ABL, int OPS, class L>
+__device__ __forceinline__ void int_tile_step_lds(const unsigned char* __restrict__ lds_cur, const unsigned char* __restrict__ lds_nxt,
+                                                  const unsigned char* __restrict__ nrm_nxt, f32x4 (&abuf)[PF], const f32x16& nrm_cur,
+                                                  f32x16& nrm_next, const f32x4 (&bq)[NJ][GB], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
+                                                  L (&st)[NJ], uint32_t prev_rowbase)
+{
+    constexpr int NG = 4 * NJ;
+#pragma unroll
+    for (int g = 0; g < GB; ++g) {
+        const f32x4 a = abuf[g % PF];
+        // block g + PF of the tile stream: this tile's, or the first blocks of the next one (landed with this step's barrier)
+        abuf[g % PF] = (g + PF < GB) ? *reinterpret_cast<const f32x4*>(lds_cur + (g + PF) * 1024)
+                                     : *reinterpret_cast<const f32x4*>(lds_nxt + (g + PF - GB) * 1024);
+        if (g == (GB > 2 ? 2 : GB - 1)) {   // next tile's norms, element 4 qd + k = row 8 qd + 4 h + k: the accumulator layout
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) {
+                const f32x4 v = *reinterpret_cast<const f32x4*>(nrm_nxt + qd * 32);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) nrm_next[4 * qd + k] = v[k];
+            }
+        }
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) {
+            if constexpr (OPS == 0)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, bq[nj][g]),
+                                                                  g == 0 ? nrm_cur : cur[nj], 0, 0, 0);
+            else
+                cur[nj] = __builtin_bit_cast(f32x16, __builtin_amdgcn_mfma_i32_32x32x32_i8(
+                              __builtin_bit_cast(i32x4, a), __builtin_bit_cast(i32x4, bq[nj][g]),
+                              __builtin_bit_cast(i32x16, g == 0 ? nrm_cur : cur[nj]), 0, 0, 0));
+        }
+#pragma unroll
+        for (int gi = (g * NG) / GB; gi < ((g + 1) * NG) / GB; ++gi) {
+            const int nj = gi % NJ, qd = gi / NJ;
+            const float p0 = prev[nj][4 * qd], p1 = prev[nj][4 * qd + 1], p2 = prev[nj][4 * qd + 2], p3 = prev[nj][4 * qd + 3];
+            if constexpr (ABL != 0) {
+                asm volatile("" ::"v"(p0), "v"(p1), "v"(p2), "v"(p3));
+            } else {
+                // (the minimum and the per-key tests: as in int_tile_step)
+                const float m = (g == 0 || !kQuadMinAsm<L>) ? __builtin_fminf(__builtin_fminf(p0, p1), __builtin_fminf(p2, p3)) : vmin2(vmin3(p0, p1, p2), p3);
+                if (__builtin_amdgcn_ballot_w64(m < list_last(st[nj])) != 0ull) {
+                    constexpr bool each = kTestsEachKeyExact<L, GB>;
+                    const uint32_t rb = prev_rowbase + 8u * (uint32_t)qd;
+                    if (!each || __builtin_amdgcn_ballot_w64(p0 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p0, rb);
+                    if (!each || __builtin_amdgcn_ballot_w64(p1 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p1, rb + 1u);
+                    if (!each || __builtin_amdgcn_ballot_w64(p2 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p2, rb + 2u);
+                    if (!each || __builtin_amdgcn_ballot_w64(p3 < list_last(st[nj])) != 0ull) list_push_exact(st[nj], p3, rb + 3u);
+                }
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the bias of the i8 tiles' keys (OPS 1): the bits of 1.0f
+constexpr uint32_t kHamBias = 0x3F800000u;
 
 // ------------------------------------------------------------------------------------------------
 // split-f16 planes (the format and its error bound: kernels_match_16bit.hip, above stage_split_kernel).  x 2^split_k = hi + lo,

@@ -526,6 +526,7 @@ struct r3dm_ctx {
     bool split_mfma = false;                                // r3dm_set_split_mfma
     bool hamming_mfma = false;                              // r3dm_set_hamming_mfma
     bool knn_narrow_tiles = false;                          // r3dm_set_knn_narrow_tiles
+    bool knn_hamming_tiles = false;                         // r3dm_set_knn_hamming_tiles
     bool device_graphs = false;                             // r3dm_set_device_graphs: match / filter results keep a device mirror (GraphDev)
     DevBuf g_segs;                                          // segment table of the graph gather kernel (kernels_graph.hip)
     uint32_t liop_npix = 0;

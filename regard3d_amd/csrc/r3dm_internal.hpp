@@ -547,5 +547,8 @@ hipError_t launch_hamming_knnk(hipStream_t st, const KnnParams& P, uint32_t word
 // launch is the split planes' factor, (3 Dpad + 36) 2^-22
 hipError_t launch_l2_knnk_int(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query);
 hipError_t launch_l2_knnk_split(hipStream_t st, const KnnParams& P, uint32_t G, uint32_t n_tiles_dataset, uint32_t n_tiles_query);
+// the K-list nominator of binary rows on the i8 tiles (kernels_match_knn8.hip; r3dm_set_knn_hamming_tiles): both views hold kLayBin8.
+// hipErrorInvalidValue: no such kernel for this launch -- the caller keeps the popcount K-list kernel
+hipError_t launch_hamming_knnk_mfma(hipStream_t st, const KnnParams& P, uint32_t words, uint32_t n_tiles_query);
 
 }  // namespace r3dm

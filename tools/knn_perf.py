@@ -10,7 +10,11 @@ with the smallest and largest repetition beside it; the k-kernel's share of the 
 Narrow tiles (r3dm_set_knn_narrow_tiles): for every L2 data set and k the same call with the switch on, ALTERNATED with the switch-off
 call in the same loop (off, on, off, on ...), so both see the same clocks and cache state.  The ratio is f32 K-list kernel / narrow
 kernel on the medians; "beyond spread" says whether the narrow median lies below the f32 median by more than the f32 line's own
-max - min.  --dev: the developer library, plus the integer kernel at one query tile per wave (R3DM_KNN_INT_NJ1) beside the product's."""
+max - min.  --dev: the developer library, plus the integer kernel at one query tile per wave (R3DM_KNN_INT_NJ1) beside the product's.
+
+i8 tiles (r3dm_set_knn_hamming_tiles): binary rows of 32 and of 61 bytes, 8,192 x 8,192, k = 3, 4, 8, the popcount K-list
+kernel (switch off) alternated with the i8-tile kernel (switch on) in the same way; "beyond spread" is taken against the popcount line's
+max - min.  --hamming-only: these lines alone."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -34,6 +38,34 @@ def datasets():
            (z["hist1"].astype(np.float32) / z["norm1"][:, None]).astype(np.float32), False)
     sk = synth.make_scene(2, N, "akaze", seed=3004)
     yield "binary, 486 bits in 64 bytes (A-KAZE MLDB)", np.ascontiguousarray(sk.descs[0]), np.ascontiguousarray(sk.descs[1]), True
+
+
+def binary_datasets():
+    """random rows; half of the queries are 5 %-flipped copies of dataset rows, so that true neighbours exist as in a matching pair"""
+    for nbytes in (32, 61):
+        rng = np.random.default_rng([8192, nbytes])
+        a = rng.integers(0, 256, (N, nbytes), dtype=np.uint8); b = rng.integers(0, 256, (N, nbytes), dtype=np.uint8)
+        b[:N // 2] = a[rng.permutation(N)[:N // 2]] ^ np.packbits(rng.random((N // 2, nbytes * 8)) < 0.05, axis=1)
+        yield f"binary, {nbytes} bytes ({(nbytes + 3) // 4} words)", a, b
+
+
+def hamming_tiles(c):
+    out = ["data | k | popcount K-list ms [min .. max] | i8 tiles ms [min .. max] | popcount / i8 | beyond the popcount spread"]
+    for name, a, b in binary_datasets():
+        for k in (3, 4, 8):
+            def kn(on):
+                c.set_knn_hamming_tiles(on)
+                try:
+                    c.knn(a, b, k, binary=True)
+                finally:
+                    c.set_knn_hamming_tiles(False)
+                s = c.stats()
+                assert s.n_knn_hamming_tiles == int(on) and s.n_exact_fallback == 0
+                return s.ms_match_kernels
+            (tp, lo, hi), (tn, nlo, nhi) = alternated([lambda: kn(False), lambda: kn(True)])
+            beyond = "yes" if tp - tn > hi - lo else "NO"
+            out.append(f"{name} | {k} | {tp:.3f} [{lo:.3f} .. {hi:.3f}] | {tn:.3f} [{nlo:.3f} .. {nhi:.3f}] | {tp / tn:.2f} | {beyond}")
+    return out
 
 
 def median_of(fn):
@@ -62,7 +94,7 @@ def main():
     c = api.Context(0)
     lines = ["data | call | kernel ms (median of %d) [min .. max] | vs 2-NN | share of f32 MFMA peak | exact-scan share" % REPS]
     narrow = ["data | k | tiles | f32 K-list ms [min .. max] | narrow ms [min .. max] | f32 / narrow | beyond the f32 spread | exact-scan share f32 / narrow"]
-    for name, a, b, binary in datasets():
+    for name, a, b, binary in (() if "--hamming-only" in sys.argv else datasets()):
         c.clear_images()
         c.set_image(0, a, None, 4000, 3000, binary=binary); c.set_image(1, b, None, 4000, 3000, binary=binary)
         pair = np.array([[0, 1]], np.uint32)
@@ -100,8 +132,11 @@ def main():
                 beyond = "yes" if tk - tn > hi - lo else "NO"
                 narrow.append(f"{name} | {k} | {tiles} | {tk:.3f} [{lo:.3f} .. {hi:.3f}] | {tn:.3f} [{nlo:.3f} .. {nhi:.3f}] | {tk / tn:.2f} | {beyond} | "
                               f"{state['off'][0]:.4f} / {state[tag][0]:.4f}")
+    ham = hamming_tiles(c)
     c.close()
-    text = "\n".join(lines + ["", "narrow tiles (r3dm_set_knn_narrow_tiles), alternated with the f32 K-list kernel in one loop"] + narrow)
+    text = "\n".join(["i8 tiles (r3dm_set_knn_hamming_tiles), alternated with the popcount K-list kernel in one loop"] + ham)
+    if "--hamming-only" not in sys.argv:
+        text = "\n".join(lines + ["", "narrow tiles (r3dm_set_knn_narrow_tiles), alternated with the f32 K-list kernel in one loop"] + narrow + ["", text])
     print(text)
     if args:
         with open(args[0], "w") as f:
