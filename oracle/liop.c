@@ -97,12 +97,15 @@ static long floor_d(double x)
     return (x >= 0 || (double)xi == x) ? xi : xi - 1;
 }
 
-static void liop_one(const liop_geom* g, const float* patch, float* desc, float* inten, int* perm)
+/* the unnormalised descriptor (integer votes, held in floats as the reference holds them).  order: the ranking of the support
+ * pixels to use (N scan positions, lowest intensity first), or NULL for the reference's own quick sort.  A given order serves the
+ * tests that ask what ANOTHER order of equal intensities would have produced (tests/liop_cases.py). */
+static void liop_votes(const liop_geom* g, const float* patch, const int* order, float* desc, float* inten, int* perm)
 {
     const int L = g->side, N = g->n_pix;
     memset(desc, 0, sizeof(float) * 24 * LIOP_BINS);
-    for (int i = 0; i < N; ++i) { inten[i] = patch[g->pix[i]]; perm[i] = i; }
-    perm_qsort(inten, perm, 0, N - 1);
+    for (int i = 0; i < N; ++i) { inten[i] = patch[g->pix[i]]; perm[i] = order ? order[i] : i; }
+    if (!order) perm_qsort(inten, perm, 0, N - 1);
     const float thr = (float)(-LIOP_THR) * (inten[perm[N - 1]] - inten[perm[0]]);   /* - threshold * (max - min), float */
     const int area = N / LIOP_BINS;
     int bin_end = area, bin = 0, offset = 0;
@@ -136,6 +139,11 @@ static void liop_one(const liop_geom* g, const float* patch, float* desc, float*
                 weight += (nv[a] > nv[b] + thr || nv[b] > nv[a] + thr);
         desc[index + offset] += weight;
     }
+}
+
+static void liop_one(const liop_geom* g, const float* patch, float* desc, float* inten, int* perm)
+{
+    liop_votes(g, patch, NULL, desc, inten, perm);
     float norm = 0;
     for (int i = 0; i < 24 * LIOP_BINS; ++i) norm += desc[i] * desc[i];
     norm = (float)(sqrt(norm) > 1e-12 ? sqrt(norm) : 1e-12);     /* VL_MAX(sqrt(norm), 1e-12) stored to a float */
@@ -155,6 +163,19 @@ int orc_liop_describe(const float* patches, int n, int side, float* desc)
             liop_one(g, patches + (size_t)p * side * side, desc + (size_t)p * 144, inten, perm);
         free(inten); free(perm);
     }
+    geom_free(g);
+    return 0;
+}
+
+/* votes: n x 144 unnormalised descriptors; order: n x n_pix rankings (see liop_votes) or NULL */
+int orc_liop_votes(const float* patches, int n, int side, const int* order, float* votes)
+{
+    liop_geom* g = geom_new(side);
+    float* inten = (float*)malloc(sizeof(float) * g->n_pix);
+    int* perm = (int*)malloc(sizeof(int) * g->n_pix);
+    for (int p = 0; p < n; ++p)
+        liop_votes(g, patches + (size_t)p * side * side, order ? order + (size_t)p * g->n_pix : NULL, votes + (size_t)p * 144, inten, perm);
+    free(inten); free(perm);
     geom_free(g);
     return 0;
 }

@@ -131,6 +131,28 @@ def liop_describe(patches: np.ndarray) -> np.ndarray:
     return out
 
 
+def liop_geometry(side: int = 41):
+    """(pix [N] int32: offsets x + y * side of the circular support in scan order, sx [N, 4], sy [N, 4]: the neighbour sample positions)"""
+    n = C.c_int(0)
+    lib().orc_liop_geometry(side, C.byref(n), None, None, None)
+    pix = np.zeros(n.value, np.int32); sx = np.zeros((n.value, 4), np.float64); sy = np.zeros((n.value, 4), np.float64)
+    lib().orc_liop_geometry(side, C.byref(n), _p(pix), _p(sx), _p(sy))
+    return pix, sx, sy
+
+
+def liop_votes(patches: np.ndarray, order: np.ndarray | None = None) -> np.ndarray:
+    """the unnormalised descriptors [n, 144] (integer votes as float32).  order [n, N] int32: the ranking of the support pixels to use
+    (scan positions, lowest intensity first) instead of the reference's quick sort"""
+    patches = np.ascontiguousarray(patches, np.float32)
+    n, side = patches.shape[0], patches.shape[1]
+    out = np.zeros((n, 144), np.float32)
+    if order is not None:
+        order = np.ascontiguousarray(order, np.int32)
+        assert order.shape[0] == n
+    lib().orc_liop_votes(_p(patches), n, side, _p(order) if order is not None else None, _p(out))
+    return out
+
+
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
 

@@ -7,13 +7,13 @@
 // bins, radius 6, threshold 5/255 of the patch's intensity range.
 //
 // One wave per 41x41 patch, everything in LDS:
-//   1. the 669 pixels of the circular support are ranked by intensity: bitonic sort of (order-preserving
+//   1. the 673 pixels of the circular support are ranked by intensity: bitonic sort of (order-preserving
 //      float bits << 32 | scan position), 16 keys per lane in registers -- exchanges at distance < 16 are register
 //      compare-exchanges, the others lane exchanges (ds_bpermute); no LDS round trips, no barriers (the LDS network this replaces
 //      took ~120 k of the ~330 k cycles of a patch and its 8 KiB held the kernel at five waves per CU).  The reference sorts with its own quick sort, whose result differs
 //      from any other sort only in the order of EQUAL intensities; patches with ties are therefore re-sorted
-//      by one lane with that exact procedure (middle pivot, Lomuto pass, "<= 0") -- rare, and constant
-//      patches short-cut to the all-zero descriptor they produce;
+//      by one lane with that exact procedure (middle pivot, Lomuto pass, "<= 0") -- rare, and patches constant over
+//      all 41 x 41 pixels short-cut to the all-zero descriptor they produce;
 //   2. each rank gets its ordinal bin, 4 bilinear samples (f64, positions from host tables computed with the
 //      host libm exactly as vl_liopdesc_new does), the permutation index of the sample order and the weight
 //      (#pairs differing by more than the threshold); weights are small integers -> integer LDS histogram;
@@ -28,7 +28,7 @@ namespace r3dm {
 constexpr int kLiopSide = 41;
 constexpr int kLiopPix = kLiopSide * kLiopSide;   // 1681
 constexpr int kLiopSortCap = 1024;
-constexpr int kLiopMaxPix = 676;                   // support pixels the exact re-sort's LDS arrays hold (new_basic(41): 669)
+constexpr int kLiopMaxPix = 676;                   // support pixels the exact re-sort's LDS arrays hold (new_basic(41): 673)
 
 __device__ __forceinline__ uint32_t float_order_bits(float v)
 {
@@ -402,6 +402,7 @@ void liop_kernel(const LiopParams P)
         // (a laundered lane id per patch: nothing that depends on the lane alone -- a few hundred registers of index arithmetic over
         // the phases below -- is worth keeping alive across a whole patch, and the compiler would)
         const uint32_t lane = liop_opaque(lane0);
+        bool whole_const;
         {
             float v[27];
             if (FUSED) {
@@ -413,6 +414,14 @@ void liop_kernel(const LiopParams P)
                 const float* src = P.patches + (size_t)item * kLiopPix + liop_opaque(lane);
 #pragma unroll
                 for (int j = 0; j < 27; ++j) v[j] = (j < 26 || lane < (uint32_t)(kLiopPix - 26 * 64)) ? src[64 * j] : 0.0f;
+            }
+            // one value in all 1681 pixels?  (the support alone does not say: the samples of its outer pixels reach 6 pixels beyond it)
+            {
+                const float first = __shfl(v[0], 0);
+                bool differ = false;
+#pragma unroll
+                for (int j = 0; j < 27; ++j) differ |= (j < 26 || lane < (uint32_t)(kLiopPix - 26 * 64)) && v[j] != first;
+                whole_const = __ballot(differ) == 0ull;
             }
             // ring of zeros: rows 0 and 42, columns 0 and 42 of the 43 x 43 image
             for (uint32_t e = lane; e < 4u * (uint32_t)kLiopPS; e += 64u) {
@@ -459,8 +468,10 @@ void liop_kernel(const LiopParams P)
         const float vmin = liop_from_order_bits((uint32_t)__shfl((int)(uint32_t)(keys[0] >> 32), 0));
         const float vmax = liop_from_order_bits((uint32_t)__shfl((int)hi_last, (int)((N - 1u) >> 4)));
         r3dm_syncthreads();
-        if (vmin == vmax) {
-            // constant support: every weight is 0, the descriptor is 0 / max(0, 1e-12) = 0
+        if (whole_const) {
+            // constant patch: every sample is that constant, every weight 0, the descriptor 0 / max(0, 1e-12) = 0.  A constant SUPPORT is
+            // not enough: thr = 0 then, and samples that reach past the support into other values still vote (the reference's result);
+            // such a patch is all ties and takes the exact sort like any other
             for (uint32_t e = lane; e < 144; e += 64) P.desc[(size_t)item * 144 + e] = 0.0f;
             r3dm_syncthreads();
             continue;
