@@ -104,6 +104,10 @@ public:
     // the reference passes false): forwards r3dm_set_guided_matching to every device context, so the F / E / H match files hold the
     // guided lists of the accepted pairs.  The default ratios are the reference's own dDistanceRatio arguments (H: geometry only).
     void setGuidedMatching(bool on, double ratio_F = 0.6, double ratio_E = 0.6, double ratio_H = -1.0);
+    // no reference counterpart (the reference keeps every query's match: SURVEY.md App. A.3 / App. C): forwards r3dm_set_mutual_matching to
+    // every device context, so the putative lists -- and with them the F / E / H lists -- hold a row of I at most once per pair.  Off by
+    // default: the match files are the reference's only while it is off.
+    void setMutualMatching(bool on);
     // How the approximate arms of the dispatch (0 FLANN, 1-3 KGraph, 5 MRPT, 6-8 HNSW) are served.  kArmsFastest (default): by the
     // EXHAUSTIVE matcher whenever r3dm_exhaustive_is_faster says it is not slower on the registered views -- on LIOP-144 every
     // approximate arm is then exact and >= 2x faster than the graph search (the GUI's default arm 0 included); kArmsAsRequested:
@@ -241,8 +245,13 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_F32_TILES         8u   /* plain f32 MFMA tiles for the exhaustive matcher: R3DComputeMatches::setExactFastPaths(false); same files, slower */
 #define R3DM_STAGE_GUIDED_MATCHING  32u   /* bGuided_matching = true (R3DComputeMatches::setGuidedMatching(true)): the filters' match files hold guided lists */
 #define R3DM_STAGE_DETECTOR_AKAZE   64u   /* keypointDetectorList_ = {"AKAZE"}, the GUI's keypointDetectorType 0 (classic A-KAZE); default {"Fast-AKAZE"} */
+#define R3DM_STAGE_MUTUAL_MATCHING 128u   /* mutual nearest-neighbour matching (R3DComputeMatches::setMutualMatching(true), r3dm_set_mutual_matching); default: every query's match is kept */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
+/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_F32_TILES */
+int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
+                                   r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
+                                   uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
 }

@@ -147,6 +147,25 @@ int r3dm_set_split_mfma(r3dm_ctx* ctx, int enable);
  * r3dm_stats.n_hamming_mfma reports which path ran. */
 int r3dm_set_hamming_mfma(r3dm_ctx* ctx, int enable);
 
+/* Opt-in mutual nearest-neighbour matching (default off; no reference counterpart -- SURVEY.md App. A.3 / App. C: "several queries of
+ * J may map to the same row of I -- they are all kept (no cross-check / mutual-NN)", and parity with the reference depends on that
+ * default).  Let (i, j) be a match a matcher would return: j's nearest row of I is i and the ratio test accepted it.  With the switch
+ * on, (i, j) is kept iff j is the nearest row of J to row i under the order (distance, row index): there is no j' in J with
+ * d(i, j') < d(i, j), or d(i, j') == d(i, j) and j' < j.  d is the reference distance for every arm and every tile format -- the f32
+ * 4-way unrolled sum of squared differences with its scalar tail and no FMA for F32 / U8 rows (symmetric in its operands bit for bit,
+ * so the forward and the reverse direction agree), the popcount Hamming distance for BIN rows; the MRPT arm applies its ratio to square
+ * roots, the check still compares squared distances.  The approximate arms nominate approximately; the check is always the exhaustive
+ * one over all rows of J, so the result is a deterministic subset of what the arm returns without it.  It runs after the ratio test
+ * and BEFORE the (i_, j_) ordering and both de-duplications: a match that fails it is gone before the coordinate de-duplication looks at
+ * its neighbours.  Consequences: a row of I appears at most once per pair; a view J with one row is always mutual; of two identical
+ * rows of J the lower index survives.  There is no reverse ratio test.
+ * Honoured by r3dm_match_pairs, r3dm_match_pairs_kgraph / _hnsw / _mrpt, their r3dm_multi_* forms and the stage (R3DComputeMatches::
+ * setMutualMatching, R3DM_STAGE_MUTUAL_MATCHING).  IGNORED by the entries that return raw neighbour lists -- r3dm_knn2, r3dm_knn, the
+ * r3dm_index_* family, the *_knn2 / *_knn entries of the approximate matchers -- and by guided matching, which replaces lists after
+ * the filters.  Cost: one more read of view J per pair that has accepted matches (kernels_match_mutual.hip); while the switch is off
+ * nothing is allocated or launched for it.  r3dm_stats.n_mutual_checked / n_mutual_dropped report the last call. */
+int r3dm_set_mutual_matching(r3dm_ctx* ctx, int enable);
+
 /* ---- putative matching ----
  * pairs_ij: n_pairs x 2 view ids (I, J); J's rows are the queries, I's rows the dataset.
  * Descriptor lengths and speed: the tensor kernels serve float / byte rows of up to 64, 128, 144 and 256 elements (rows are padded
@@ -632,6 +651,7 @@ int r3dm_multi_transfer_counts(const r3dm_multi* m, uint64_t* host_uploads, uint
 int r3dm_multi_set_intrinsics(r3dm_multi* m, uint32_t view_id, const double* K);
 int r3dm_multi_clear_images(r3dm_multi* m);
 int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable);
+int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable);      /* r3dm_set_mutual_matching on every context */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,
                            float dist_ratio, int squared_metric, r3dm_graph** out);
 /* the same deal for the graph matcher (kgraph_match, config C5): a device builds the index of every image I whose row it owns */
@@ -763,7 +783,11 @@ typedef struct {
     /* r3dm_knn / r3dm_index_knn with r3dm_set_knn_narrow_tiles on */
     uint64_t n_knn_integer_tiles;  /* launches of the K-list nominator on the bf16 tiles (integer-valued rows: exact lists, nothing certified or scanned)  */
     uint64_t n_knn_split_tiles;    /* launches of the K-list nominator on the split-f16 planes (real-valued rows)                                          */
-    /* ... with r3dm_set_knn_hamming_tiles on */
+    /* r3dm_set_mutual_matching (both 0 while the switch is off).  They stand in front of the last k-NN counter: the interface test of
+     * r3dm_set_knn_hamming_tiles holds that one to the end of the structure */
+    uint64_t n_mutual_checked;     /* accepted matches the mutual check looked at                                                                          */
+    uint64_t n_mutual_dropped;     /* ... of those, matches it removed: their row of I has a nearer row of J                                               */
+    /* r3dm_knn / r3dm_index_knn with r3dm_set_knn_hamming_tiles on */
     uint64_t n_knn_hamming_tiles;  /* launches of the K-list nominator on the i8 tiles (BIN rows: exact lists, nothing certified or scanned)               */
 } r3dm_stats;
 int r3dm_get_stats(const r3dm_ctx* ctx, r3dm_stats* out);

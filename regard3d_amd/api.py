@@ -41,10 +41,12 @@ EXPORTS = [
     "r3dm_set_device_graphs", "r3dm_graph_on_device", "r3dm_comm_last_device_graphs",
     "r3dm_guided_match", "r3dm_set_guided_matching", "r3dm_guided_report", "r3dm_multi_set_guided_matching",
     "r3dm_set_keypoint_detector", "r3dm_multi_set_keypoint_detector", "r3dm_akaze_classic_components",
+    "r3dm_set_mutual_matching", "r3dm_multi_set_mutual_matching", "r3dm_compute_matches_dir_flags",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
 STAGE_DETECTOR_AKAZE = 64
+STAGE_MUTUAL_MATCHING = 128
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
 
 
@@ -78,7 +80,8 @@ class Stats(C.Structure):
                 ("ms_liop_wall", C.c_double), ("ms_feature_files", C.c_double),
                 ("n_hnsw_launches", C.c_uint64), ("n_hnsw_retries", C.c_uint64), ("n_counts_mfma", C.c_uint64),
                 ("detect_compulsory_bytes", C.c_double), ("n_filter_workgroups", C.c_uint64), ("n_filter_coop_pairs", C.c_uint64),
-                ("n_knn_integer_tiles", C.c_uint64), ("n_knn_split_tiles", C.c_uint64), ("n_knn_hamming_tiles", C.c_uint64)]
+                ("n_knn_integer_tiles", C.c_uint64), ("n_knn_split_tiles", C.c_uint64),
+                ("n_mutual_checked", C.c_uint64), ("n_mutual_dropped", C.c_uint64), ("n_knn_hamming_tiles", C.c_uint64)]
 
 
 class GuidedStats(C.Structure):
@@ -157,9 +160,9 @@ class Stage:
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-            guided: bool = False, detector: str = "Fast-AKAZE") -> StageReport:
+            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False) -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
-        (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0)"""
+        (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING)"""
         dflag = _detector_flag(detector)
         keep = []
         arr = _stage_views(views, keep)
@@ -167,7 +170,7 @@ class Stage:
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                     (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                    | (STAGE_GUIDED_MATCHING if guided else 0) | dflag, C.byref(rep), err, 1024)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | dflag, C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -188,11 +191,11 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-                          guided: bool = False, detector: str = "Fast-AKAZE") -> StageReport:
+                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False) -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
-    detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE)."""
+    detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE); mutual: R3DM_STAGE_MUTUAL_MATCHING."""
     dflag = _detector_flag(detector)
     L = load_library()
     keep = []
@@ -203,10 +206,33 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                       (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                      | (STAGE_GUIDED_MATCHING if guided else 0) | dflag, C.byref(rep), err, 1024)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | dflag, C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
+
+
+class _DirView(C.Structure):
+    """r3dm_view (include/r3d_compute_matches.hpp)"""
+    _fields_ = [("id", C.c_uint32), ("width", C.c_uint32), ("height", C.c_uint32), ("basename", C.c_char_p)]
+
+
+def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0, dim: int = 144, dist_ratio: float = 0.6,
+                        compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False):
+    """R3DComputeMatches::computeMatches over a directory that holds every view's .feat / .desc (r3dm_compute_matches_dir_flags):
+    exhaustive matching, the F filter when asked, matches.putative.txt / matches.f.txt.  views: dicts with id, width, height,
+    basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING.  -> (putative pairs, geometric pairs)"""
+    L = load_library()
+    arr = (_DirView * len(views))(*[_DirView(int(v["id"]), int(v["width"]), int(v["height"]), str(v["basename"]).encode()) for v in views])
+    npp, ngp = C.c_uint64(0), C.c_uint64(0)
+    err = C.create_string_buffer(1024)
+    L.r3dm_compute_matches_dir_flags.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64,
+                                                 C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
+    rc = L.r3dm_compute_matches_dir_flags(device_id, matches_dir.encode(), arr, len(views), dtype, dim, dist_ratio, int(compute_F), seed,
+                                          (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0), C.byref(npp), C.byref(ngp), err, 1024)
+    if rc != 0:
+        raise R3dmError(f"r3dm_compute_matches_dir_flags -> {rc}: {err.value.decode()}")
+    return int(npp.value), int(ngp.value)
 
 
 class KGraphParams(C.Structure):
@@ -309,6 +335,8 @@ def load_library():
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
+    L.r3dm_set_mutual_matching.argtypes = [vp, C.c_int]
+    L.r3dm_multi_set_mutual_matching.argtypes = [vp, C.c_int]
     L.r3dm_index_create.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
     L.r3dm_index_knn2.argtypes = [vp, vp, vp, u32, vp, vp]
     L.r3dm_index_destroy.argtypes = [vp]; L.r3dm_index_destroy.restype = None
@@ -955,6 +983,12 @@ class Context:
         r3dm_set_knn_hamming_tiles); same results, Stats.n_knn_hamming_tiles counts the launch"""
         self._check(self._L.r3dm_set_knn_hamming_tiles(self._h, int(bool(enable))), "r3dm_set_knn_hamming_tiles")
 
+    def set_mutual_matching(self, enable: bool = True):
+        """opt-in mutual nearest-neighbour matching (include/r3dm.h: r3dm_set_mutual_matching): a match (i, j) of match_pairs and the
+        approximate matchers is kept iff j is the nearest row of J to row i under (distance, row index); Stats.n_mutual_checked /
+        n_mutual_dropped report the last call.  knn2 / knn / the index entries return raw lists and ignore it"""
+        self._check(self._L.r3dm_set_mutual_matching(self._h, int(bool(enable))), "r3dm_set_mutual_matching")
+
     def set_split_mfma(self, enable: bool = True):
         """opt-in split-f16 nominator for real-valued descriptors (include/r3dm.h: r3dm_set_split_mfma)"""
         self._check(self._L.r3dm_set_split_mfma(self._h, int(bool(enable))), "r3dm_set_split_mfma")
@@ -1275,6 +1309,10 @@ class MultiContext:
 
     def set_integer_mfma(self, enable: bool = True):
         self._check(self._L.r3dm_multi_set_integer_mfma(self._h, int(bool(enable))), "r3dm_multi_set_integer_mfma")
+
+    def set_mutual_matching(self, enable: bool = True):
+        """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""
+        self._check(self._L.r3dm_multi_set_mutual_matching(self._h, int(bool(enable))), "r3dm_multi_set_mutual_matching")
 
     def set_guided_matching(self, enable: bool = True, ratio_F: float = 0.6, ratio_E: float = 0.6, ratio_H: float = -1.0):
         self._check(self._L.r3dm_multi_set_guided_matching(self._h, int(bool(enable)), ratio_F, ratio_E, ratio_H), "r3dm_multi_set_guided_matching")

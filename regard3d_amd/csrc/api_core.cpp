@@ -49,6 +49,7 @@ extern "C" void r3dm_destroy(r3dm_ctx* c)
     for (FilterBufs& fb : c->fb) fb.release();
     c->gb.release();
     c->coop_sched.release();
+    c->d_mutual.release();
     if (c->coop_ev) (void)hipEventDestroy(c->coop_ev);
     if (c->coop_stream) (void)hipStreamDestroy(c->coop_stream);
     c->coop_ev = nullptr; c->coop_stream = nullptr;
@@ -769,6 +770,13 @@ extern "C" int r3dm_set_hamming_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;
     c->hamming_mfma = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_set_mutual_matching(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->mutual_matching = (enable != 0);
     return R3DM_OK;
 }
 

@@ -8,12 +8,48 @@
 // ------------------------------------------------------------------------------------------------
 // putative matching
 // ------------------------------------------------------------------------------------------------
+// r3dm_set_mutual_matching: the mutual nearest-neighbour check on nn_idx[pair][*] (kernels_match_mutual.hip), after the ratio test and
+// before the (i, j) ordering and both de-duplications.  Whatever arm nominated the matches, the check is the exhaustive one in the
+// reference's arithmetic: over J's f32 tiles where the length has a tensor kernel and no scalar tail, over the row-major rows
+// otherwise, over the word rows of binary views.  Adds the batch's two counters to the statistics.
+static int run_mutual_check(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride)
+{
+    const uint32_t P = (uint32_t)jobs.size();
+    const HostImage& first = *c->imgs[jobs[0].sI];
+    R3DM_HIP(c, c->d_mutual.ensure(16));
+    R3DM_HIP(c, hipMemsetAsync(c->d_mutual.p, 0, 16, c->stream));
+    MutualParams mp{};
+    mp.imgs = c->d_imgs.as<ImgDev>(); mp.pairs = c->d_pairs.as<uint2>(); mp.n_pairs = P; mp.q_stride = q_stride;
+    mp.nn_idx = c->d_nn.as<uint32_t>(); mp.counters = c->d_mutual.as<unsigned long long>();
+    // (a chunk of the MRPT arm may hold views of several lengths: the rows-based kernel reads each pair's own)
+    const bool one_length = std::all_of(jobs.begin(), jobs.end(), [&](const PairJob& j) { return c->imgs[j.sI]->dim == first.dim; });
+    if (first.dtype == R3DM_BIN) R3DM_HIP(c, launch_hamming_mutual(c->stream, mp, first.words));
+    else if (one_length && has_tensor_kernel(first.G) && (first.dim & 3u) == 0) R3DM_HIP(c, launch_l2_mutual_batch(c->stream, mp, first.G));
+    else {
+        const uint64_t total_slots = (uint64_t)P * q_stride;
+        if (total_slots > 0xFFFFFFFFull) { c->err = "batch too large for the rows-based mutual check"; return R3DM_ERR_UNSUPPORTED; }
+        std::vector<uint32_t> slots;
+        slots.reserve(2 * (size_t)P);
+        for (const PairJob& j : jobs) { slots.push_back(j.sI); slots.push_back(j.sJ); }
+        { const int rcl = ensure_layouts(c, slots, kLayRows); if (rcl != R3DM_OK) return rcl; }
+        R3DM_HIP(c, launch_l2_mutual_items(c->stream, mp, (uint32_t)total_slots));
+    }
+    unsigned long long counts[2] = {0, 0};
+    R3DM_HIP(c, hipMemcpyAsync(counts, mp.counters, 16, hipMemcpyDeviceToHost, c->stream));
+    R3DM_HIP(c, hipStreamSynchronize(c->stream));
+    c->stats.n_mutual_checked += counts[0];
+    c->stats.n_mutual_dropped += counts[1];
+    return R3DM_OK;
+}
+
 // compaction + ordering + de-duplication of nn_idx[pair][*] (finalize_pairs_kernel), copy back, append the non-empty
-// pairs to `g` in job order.  Shared by the exhaustive and the graph-search drivers.
+// pairs to `g` in job order.  Shared by the exhaustive and the graph-search drivers.  Calls that collect into a graph run the mutual
+// check first while its switch is on; the raw-list entries (g == nullptr: r3dm_knn2 and its relatives) never do.
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
                           uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols)
 {
     const uint32_t P = (uint32_t)jobs.size();
+    if (c->mutual_matching && g && P) { const int rcm = run_mutual_check(c, jobs, q_stride); if (rcm != R3DM_OK) return rcm; }
     // ---- finalisation: compact + order + de-duplicate, per pair
     R3DM_HIP(c, c->d_pair_off.ensure((size_t)P * 8));
     R3DM_HIP(c, c->d_pair_cnt.ensure((size_t)P * 4));

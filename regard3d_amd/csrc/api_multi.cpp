@@ -201,6 +201,13 @@ extern "C" int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) r3dm_set_mutual_matching(c, enable);
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H)
 {
     if (!m) return R3DM_ERR_INVALID;

@@ -332,6 +332,12 @@ void R3DComputeMatches::setHammingFastPath(bool on)
     if (multi_) for (int k = 0; k < r3dm_multi_num_devices(multi_); ++k) (void)r3dm_set_hamming_mfma(r3dm_multi_ctx(multi_, k), on ? 1 : 0);
 }
 
+void R3DComputeMatches::setMutualMatching(bool on)
+{
+    if (ctx_) (void)r3dm_set_mutual_matching(ctx_, on ? 1 : 0);
+    if (multi_) (void)r3dm_multi_set_mutual_matching(multi_, on ? 1 : 0);
+}
+
 void R3DComputeMatches::setGuidedMatching(bool on, double ratio_F, double ratio_E, double ratio_H)
 {
     if (ctx_) (void)r3dm_set_guided_matching(ctx_, on ? 1 : 0, ratio_F, ratio_E, ratio_H);
@@ -695,6 +701,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setBackgroundThreadsNice((flags & R3DM_STAGE_BACKGROUND_NICE) ? 10 : 0);
         stage.setExactFastPaths((flags & R3DM_STAGE_F32_TILES) == 0);      // (R3DM_STAGE_SPLIT_MFMA / _INTEGER_MFMA: implied since round 3)
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
+        stage.setMutualMatching((flags & R3DM_STAGE_MUTUAL_MATCHING) != 0);
         r3d_amd::R3DFParams params;
         params.keypointDetectorList_ = {(flags & R3DM_STAGE_DETECTOR_AKAZE) ? "AKAZE" : "Fast-AKAZE"};
         params.threshold_ = threshold;
@@ -747,6 +754,14 @@ extern "C" int r3dm_compute_matches_dir(int device_id, const char* matches_dir, 
                                         r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                                         uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap)
 {
+    return r3dm_compute_matches_dir_flags(device_id, matches_dir, views, n_views, dtype, dim, dist_ratio, compute_F, seed, 0u,
+                                          n_putative_pairs, n_geometric_pairs, err, err_cap);
+}
+
+extern "C" int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
+                                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
+                                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap)
+{
     if (!matches_dir || (n_views && !views)) return R3DM_ERR_INVALID;
     try {
     r3d_amd::R3DComputeMatches stage(device_id);
@@ -755,6 +770,8 @@ extern "C" int r3dm_compute_matches_dir(int device_id, const char* matches_dir, 
     stage.addViews(vs);
     stage.setRegionsType(dtype, dim);
     stage.setSeed(seed);
+    if (flags & R3DM_STAGE_F32_TILES) stage.setExactFastPaths(false);
+    if (flags & R3DM_STAGE_MUTUAL_MATCHING) stage.setMutualMatching(true);
     r3d_amd::R3DFParams params;
     params.distRatio_ = dist_ratio;
     params.computeFundalmentalMatrix_ = compute_F != 0;

@@ -1,0 +1,249 @@
+// kernels_match_mutual.hip -- the opt-in mutual nearest-neighbour check (r3dm_set_mutual_matching).  It runs on
+// nn_idx[pair][*] after the matcher and its exact scans have finished and before the finalisation: an accepted match (i, j) -- j's
+// nearest row of I is i and the ratio test passed -- stays iff j is the nearest row of J to row i under the order (distance, row);
+// anything else becomes kNone, so the (i, j) ordering and both de-duplications never see it.
+//
+// The distance is the reference's (exact_l2sq: 4-way unrolled, scalar tail, no FMA -- symmetric in its operands bit for bit; the
+// popcount Hamming distance for binary rows) and the scan is exhaustive over J whatever arm nominated the match, so the result is a
+// deterministic subset of the switch-off result.  Only accepted matches are checked: tens to hundreds of rows of I against one view.
+//
+//   l2_mutual_batch_kernel<G>   padded lengths with a tensor kernel, dim % 4 == 0: one workgroup per pair, lane = one accepted match
+//                               (its row of I in registers), J's fragment-order f32 tiles streamed through LDS as
+//                               l2_exact_batch_kernel streams I's (row reads are wave-uniform -> LDS broadcast)
+//   l2_mutual_items_kernel      any other length: one workgroup per accepted match over the row-major rows
+//   hamming_mutual_kernel<W>    binary rows of 8 / 16 words: the batch kernel's shape over the word rows, packed integer keys
+#include "kernels_match_common.hpp"
+
+namespace r3dm {
+
+__device__ __forceinline__ bool mutual_lex_less(float da, uint32_t ia, float db, uint32_t ib)
+{
+    return da < db || (da == db && ia < ib);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the frame of the two one-workgroup-per-pair kernels: gather the accepted (i, j) of the pair in query order into `cand`
+// (i << 32 | j), 256 per round; best_row(i, j, active) -> the row of J nearest to row i (it is called by ALL 256 threads and may
+// synchronise the workgroup); a candidate whose nearest row is not j loses its entry of nn_idx.
+// `cand` holds 512 keys: a round starts with fewer than 256 left over and gathers at most 256 more.
+// ------------------------------------------------------------------------------------------------
+template <class BestRow>
+__device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32_t pair, uint32_t nJ, unsigned long long* cand,
+                                                   uint32_t* wave_cnt, BestRow&& best_row)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    uint32_t* nn = P.nn_idx + (size_t)pair * P.q_stride;
+    uint32_t held = 0, qpos = 0;                     // block-uniform: keys in cand, first query not gathered yet
+    uint32_t checked = 0, dropped = 0;               // per wave, kept by its lane 0
+    for (;;) {
+        while (held < 256u && qpos < nJ) {
+            const uint32_t q = qpos + threadIdx.x;
+            const uint32_t v = (q < nJ) ? nn[q] : kNone;
+            const bool keep = (v < kFallback);
+            const unsigned long long bal = __ballot(keep);
+            const uint32_t before = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+            if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(bal);
+            r3dm_syncthreads();
+            uint32_t woff = 0, tot = 0;
+#pragma unroll
+            for (uint32_t w = 0; w < 4; ++w) { const uint32_t cw = wave_cnt[w]; if (w < wave) woff += cw; tot += cw; }
+            if (keep) cand[held + woff + before] = ((unsigned long long)v << 32) | q;
+            held += tot; qpos += 256u;
+            r3dm_syncthreads();
+        }
+        if (held == 0) break;                        // a pair without an accepted match leaves here, having read nn_idx once
+        const uint32_t cnt = held < 256u ? held : 256u;
+        const bool active = threadIdx.x < cnt;
+        const unsigned long long key = cand[active ? threadIdx.x : 0u];
+        const uint32_t i = (uint32_t)(key >> 32), j = (uint32_t)key;
+        const uint32_t bj = best_row(i, j, active);
+        const bool drop = active && bj != j;
+        if (drop) nn[j] = kNone;                     // (j < qpos: the gather never reads this entry again)
+        const unsigned long long ba = __ballot(active), bd = __ballot(drop);
+        checked += (uint32_t)__builtin_popcountll(ba); dropped += (uint32_t)__builtin_popcountll(bd);
+        // the keys beyond this round move to the front: read, barrier, write
+        r3dm_syncthreads();
+        const uint32_t rest = held - cnt;            // < 256
+        const unsigned long long moved = (threadIdx.x < rest) ? cand[256u + threadIdx.x] : 0ull;
+        r3dm_syncthreads();
+        if (threadIdx.x < rest) cand[threadIdx.x] = moved;
+        r3dm_syncthreads();
+        held = rest;
+    }
+    if (lane == 0 && checked) {
+        atomicAdd(P.counters, (unsigned long long)checked);
+        if (dropped) atomicAdd(P.counters + 1, (unsigned long long)dropped);
+    }
+}
+
+template <int G>
+__global__ __launch_bounds__(256)
+void l2_mutual_batch_kernel(const MutualParams P)
+{
+    constexpr int D4 = G * 2;                        // float4 per (padded) row
+    __shared__ f32x4 tile[32 * D4];                  // 32 rows of J x Dpad floats, fragment order: [chunk k][row r]
+    __shared__ unsigned long long cand[512];
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t pair = blockIdx.x;
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const uint32_t nJ = Jp->n, d4 = Ip->dim >> 2;    // dim % 4 == 0 guaranteed by the caller
+    const gf4p itiles = (gf4p)Ip->tiled, jtiles = (gf4p)Jp->tiled;
+    mutual_pair_rounds(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> uint32_t {
+        f32x4 iv[D4];
+        const gf4p irow = itiles + (size_t)(i >> 5) * (D4 * 32) + (i & 31u);
+#pragma unroll
+        for (int k = 0; k < D4; ++k) iv[k] = (k < (int)d4) ? irow[k * 32] : f32x4{0.f, 0.f, 0.f, 0.f};
+        float bd = R3DM_INF; uint32_t bj = kNone;
+        for (uint32_t t0 = 0; t0 < nJ; t0 += 32) {
+            r3dm_syncthreads();                      // every wave has finished with the previous tile
+            {
+                const gf4p src = jtiles + (size_t)(t0 >> 5) * (D4 * 32);
+                for (uint32_t e = threadIdx.x; e < 32u * D4; e += 256) tile[e] = src[e];
+            }
+            r3dm_syncthreads();
+            const uint32_t rows_here = (nJ - t0 < 32u) ? nJ - t0 : 32u;
+            for (uint32_t r = 0; r < rows_here; ++r) {
+                float result = 0.0f;
+#pragma unroll
+                for (int k = 0; k < D4; ++k) {
+                    if (k < (int)d4) {
+                        const f32x4 a = tile[k * 32 + r];
+                        const float e0 = iv[k][0] - a[0], e1 = iv[k][1] - a[1], e2 = iv[k][2] - a[2], e3 = iv[k][3] - a[3];
+                        result += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+                    }
+                }
+                if (result < bd) { bd = result; bj = t0 + r; }      // rows ascend: an equal distance keeps the lower row
+            }
+        }
+        return bj;
+    });
+}
+
+hipError_t launch_l2_mutual_batch(hipStream_t st, const MutualParams& P, uint32_t G)
+{
+    if (P.n_pairs == 0) return hipSuccess;
+    if (P.n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
+    const dim3 grid(P.n_pairs);
+    switch (G) {
+        case 8:  hipLaunchKernelGGL((l2_mutual_batch_kernel<8>), grid, dim3(256), 0, st, P); break;
+        case 16: hipLaunchKernelGGL((l2_mutual_batch_kernel<16>), grid, dim3(256), 0, st, P); break;
+        case 18: hipLaunchKernelGGL((l2_mutual_batch_kernel<18>), grid, dim3(256), 0, st, P); break;
+        case 32: hipLaunchKernelGGL((l2_mutual_batch_kernel<32>), grid, dim3(256), 0, st, P); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// rows-based form (lengths without a tensor kernel, lengths with a scalar tail): one workgroup per accepted match, the rows of J
+// dealt to its threads, the per-thread bests merged under the (distance, row) order -- the shape of l2_exact_items_kernel
+// ------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256)
+void l2_mutual_items_kernel(const MutualParams P, uint32_t count)
+{
+    __shared__ float sd[256];
+    __shared__ uint32_t si[256];
+    uint32_t checked = 0, dropped = 0;               // kept by thread 0
+    for (uint32_t it = blockIdx.x; it < count; it += gridDim.x) {
+        const uint32_t pair = it / P.q_stride, j = it % P.q_stride;
+        const uint2 pr = P.pairs[pair];
+        const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+        const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+        const uint32_t nJ = Jp->n;
+        if (j >= nJ) continue;                                    // block-uniform
+        const uint32_t i = P.nn_idx[it];                          // block-uniform: every thread reads it before the barriers below
+        if (i >= kFallback) continue;
+        const uint32_t dim = Ip->dim;
+        const float* iv = Ip->rows + (size_t)i * dim;
+        float bd = R3DM_INF; uint32_t bj = kNone;
+        for (uint32_t r = threadIdx.x; r < nJ; r += 256) {
+            const float d = exact_l2sq(iv, Jp->rows + (size_t)r * dim, dim);
+            if (d < bd) { bd = d; bj = r; }
+        }
+        sd[threadIdx.x] = bd; si[threadIdx.x] = bj;
+        r3dm_syncthreads();
+        for (uint32_t s = 128; s > 0; s >>= 1) {
+            if (threadIdx.x < s) {
+                const float b = sd[threadIdx.x + s]; const uint32_t y = si[threadIdx.x + s];
+                if (mutual_lex_less(b, y, sd[threadIdx.x], si[threadIdx.x])) { sd[threadIdx.x] = b; si[threadIdx.x] = y; }
+            }
+            r3dm_syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            checked += 1;
+            if (si[0] != j) { P.nn_idx[it] = kNone; dropped += 1; }
+        }
+        r3dm_syncthreads();
+    }
+    if (threadIdx.x == 0 && checked) {
+        atomicAdd(P.counters, (unsigned long long)checked);
+        if (dropped) atomicAdd(P.counters + 1, (unsigned long long)dropped);
+    }
+}
+
+hipError_t launch_l2_mutual_items(hipStream_t st, const MutualParams& P, uint32_t count)
+{
+    if (count == 0) return hipSuccess;
+    const uint32_t grid = count < 16384u ? count : 16384u;
+    hipLaunchKernelGGL(l2_mutual_items_kernel, dim3(grid), dim3(256), 0, st, P, count);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// binary rows (ImgDev::bin: row-major u32 [n][W]): lane = one accepted match, its row of I in registers, 32 rows of J per LDS stage.
+// Keys are distance << 22 | row (a view has fewer than 2^22 rows, a distance at most 512): the unsigned minimum IS the
+// (distance, row) order.
+// ------------------------------------------------------------------------------------------------
+template <int W>
+__global__ __launch_bounds__(256)
+void hamming_mutual_kernel(const MutualParams P)
+{
+    __shared__ uint32_t tile[32 * W];
+    __shared__ unsigned long long cand[512];
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t pair = blockIdx.x;
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const uint32_t nJ = Jp->n;
+    const uint32_t* __restrict__ ibin = Ip->bin;
+    const uint32_t* __restrict__ jbin = Jp->bin;
+    mutual_pair_rounds(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> uint32_t {
+        uint32_t a[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) a[w] = ibin[(size_t)i * W + w];
+        uint32_t best = 0xFFFFFFFFu;
+        for (uint32_t t0 = 0; t0 < nJ; t0 += 32) {
+            r3dm_syncthreads();
+            for (uint32_t e = threadIdx.x; e < 32u * W; e += 256)
+                tile[e] = (t0 + e / W < nJ) ? jbin[(size_t)t0 * W + e] : 0u;
+            r3dm_syncthreads();
+            const uint32_t rows_here = (nJ - t0 < 32u) ? nJ - t0 : 32u;
+            for (uint32_t r = 0; r < rows_here; ++r) {
+                uint32_t d = 0;
+#pragma unroll
+                for (int w = 0; w < W; ++w) d += (uint32_t)__builtin_popcount(a[w] ^ tile[r * W + w]);
+                const uint32_t key = (d << 22) | (t0 + r);
+                best = best < key ? best : key;
+            }
+        }
+        return best == 0xFFFFFFFFu ? kNone : (best & 0x3FFFFFu);
+    });
+}
+
+hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t words)
+{
+    if (P.n_pairs == 0) return hipSuccess;
+    if (P.n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
+    const dim3 grid(P.n_pairs);
+    switch (words) {
+        case 8:  hipLaunchKernelGGL((hamming_mutual_kernel<8>), grid, dim3(256), 0, st, P); break;
+        case 16: hipLaunchKernelGGL((hamming_mutual_kernel<16>), grid, dim3(256), 0, st, P); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+}  // namespace r3dm

@@ -1,6 +1,7 @@
 // r3dm_ctx.hpp -- host-side state shared by the translation units of libr3dm.so (not part of the public ABI).
 //   api_core.cpp      context, views (staging), match-graph objects, matches.* files
-//   api_match.cpp     exhaustive putative matching: 2-NN batches (run_match_batch), k-NN (run_knn_batch), one certificate slack
+//   api_match.cpp     exhaustive putative matching: 2-NN batches (run_match_batch), k-NN (run_knn_batch), the mutual check in front of
+//                     every finalisation into a graph (finalize_batch), one certificate slack
 //                     (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
 //   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
@@ -527,6 +528,8 @@ struct r3dm_ctx {
     bool hamming_mfma = false;                              // r3dm_set_hamming_mfma
     bool knn_narrow_tiles = false;                          // r3dm_set_knn_narrow_tiles
     bool knn_hamming_tiles = false;                         // r3dm_set_knn_hamming_tiles
+    bool mutual_matching = false;                           // r3dm_set_mutual_matching: the mutual check runs before every finalisation into a graph
+    DevBuf d_mutual;                                        // its two counters (allocated by the first batch that runs the check)
     bool device_graphs = false;                             // r3dm_set_device_graphs: match / filter results keep a device mirror (GraphDev)
     DevBuf g_segs;                                          // segment table of the graph gather kernel (kernels_graph.hip)
     uint32_t liop_npix = 0;

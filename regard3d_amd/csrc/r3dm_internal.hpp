@@ -245,6 +245,17 @@ struct FinalizeParams {
     uint32_t*     pair_cnt;       // [n_pairs]
 };
 
+// the mutual nearest-neighbour check (kernels_match_mutual.hip; r3dm_set_mutual_matching): runs on nn_idx between the matcher and the
+// finalisation; an accepted entry whose row of I has a nearer row of J (order: distance, row) becomes kNone
+struct MutualParams {
+    const ImgDev* imgs;
+    const uint2*  pairs;          // slot indices (I, J)
+    uint32_t      n_pairs;
+    uint32_t      q_stride;
+    uint32_t*     nn_idx;         // [n_pairs][q_stride]
+    unsigned long long* counters; // [2]: matches checked, matches dropped (atomic; zeroed by the host)
+};
+
 constexpr int kCoopB = 32;                  // models per batch of the cooperative AC-RANSAC kernel, at most
 constexpr uint32_t kCoopMaxG = 30;          // slices per pair, at most (5-bit slice code of a task, 31 = start-up)
 
@@ -454,6 +465,11 @@ hipError_t launch_l2_exact_items(hipStream_t st, const MatchParams& P, uint32_t 
 // exact scan of the per-pair fallback lists (one workgroup per pair); false return -> no kernel for this G
 hipError_t launch_l2_exact_batch(hipStream_t st, const MatchParams& P, uint32_t G);
 hipError_t launch_hamming_knn2(hipStream_t st, const MatchParams& P, uint32_t words, uint32_t max_n);
+// the mutual check: one workgroup per pair over J's f32 tiles (G with a tensor kernel, dim % 4 == 0) / over the word rows of binary
+// views (8 or 16 words); one workgroup per accepted match over the row-major rows for every other length (count = n_pairs x q_stride)
+hipError_t launch_l2_mutual_batch(hipStream_t st, const MutualParams& P, uint32_t G);
+hipError_t launch_l2_mutual_items(hipStream_t st, const MutualParams& P, uint32_t count);
+hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t words);
 hipError_t launch_finalize(hipStream_t st, const FinalizeParams& P);
 hipError_t launch_filter_F(hipStream_t st, const FilterParams& P);
 // one pool of workers for the long pairs of up to three filters: dev_params = FilterParams[3] in device memory indexed by model kind,
