@@ -108,6 +108,13 @@ public:
     // every device context, so the putative lists -- and with them the F / E / H lists -- hold a row of I at most once per pair.  Off by
     // default: the match files are the reference's only while it is off.
     void setMutualMatching(bool on);
+    // no reference counterpart (the reference matches exhaustivePairs): forwards r3dm_set_preemptive_matching to every
+    // device context, so a pair is matched only if the small match of its views' head_rows largest-scale features finds min_matches
+    // correspondences -- dropped pairs lose real matches.  The scale column of every view's .feat file is registered as its priority
+    // (r3dm_set_view_priority).  The features sink carries no scales, so while this is on every view is registered from its files, which
+    // is what setDirectRegistration(false) does.  128 / 4 are Wu's SIFT-era 100 / 4 rounded to a tile multiple, not tuned for LIOP.  Off by
+    // default: the match files are the reference's only while it is off.
+    void setPreemptiveMatching(bool on, uint32_t head_rows = 128, uint32_t min_matches = 4);
     // How the approximate arms of the dispatch (0 FLANN, 1-3 KGraph, 5 MRPT, 6-8 HNSW) are served.  kArmsFastest (default): by the
     // EXHAUSTIVE matcher whenever r3dm_exhaustive_is_faster says it is not slower on the registered views -- on LIOP-144 every
     // approximate arm is then exact and >= 2x faster than the graph search (the GUI's default arm 0 included); kArmsAsRequested:
@@ -189,6 +196,7 @@ private:
     std::vector<uint32_t> registered_n_;
     const size_t* sink_need_ = nullptr;    // views of the running features chunk
     bool direct_registration_ = true;
+    bool preemptive_on_ = false;
     int background_nice_ = 0;
     static int features_sink(void* self, uint32_t image_index, uint32_t n_features, const float* desc_device, const float* xy_as_written);
     ImageProviderFn provider_ = nullptr;
@@ -246,11 +254,12 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_GUIDED_MATCHING  32u   /* bGuided_matching = true (R3DComputeMatches::setGuidedMatching(true)): the filters' match files hold guided lists */
 #define R3DM_STAGE_DETECTOR_AKAZE   64u   /* keypointDetectorList_ = {"AKAZE"}, the GUI's keypointDetectorType 0 (classic A-KAZE); default {"Fast-AKAZE"} */
 #define R3DM_STAGE_MUTUAL_MATCHING 128u   /* mutual nearest-neighbour matching (R3DComputeMatches::setMutualMatching(true), r3dm_set_mutual_matching); default: every query's match is kept */
+#define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
-/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_F32_TILES */
+/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_F32_TILES */
 int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                                    r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
                                    uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);

@@ -110,6 +110,7 @@ int r3dm_images_wait(r3dm_ctx* ctx);
 #define R3DM_LAYOUT_SPLIT  4u   /* split-f16 planes (r3dm_set_split_mfma) */
 #define R3DM_LAYOUT_COUNTS 8u   /* count tiles + scale order (r3dm_set_split_mfma, votes x scale rows) */
 #define R3DM_LAYOUT_BIN8   16u  /* byte-per-bit tiles (r3dm_set_hamming_mfma) */
+#define R3DM_LAYOUT_HEAD   32u  /* the head rows of preemptive matching (r3dm_set_preemptive_matching, r3dm_preselect_pairs) */
 int r3dm_view_info(r3dm_ctx* ctx, uint32_t view_id, uint32_t* layouts, uint64_t* bytes, uint64_t* ring_uploads, uint64_t* direct_uploads);
 /* device memory the context holds for its registered views (the slabs their layouts are cut from, live and recycled blocks alike),
  * for the upload ring (device slots + position-class tables), and the ring's page-locked host memory; any pointer may be NULL */
@@ -165,6 +166,60 @@ int r3dm_set_hamming_mfma(r3dm_ctx* ctx, int enable);
  * the filters.  Cost: one more read of view J per pair that has accepted matches (kernels_match_mutual.hip); while the switch is off
  * nothing is allocated or launched for it.  r3dm_stats.n_mutual_checked / n_mutual_dropped report the last call. */
 int r3dm_set_mutual_matching(r3dm_ctx* ctx, int enable);
+
+/* Opt-in preemptive matching (default off; no reference counterpart -- the reference matches exhaustivePairs, SURVEY.md section 5, and
+ * parity with it depends on that default): match only the largest-scale features of each view first, and run the full match of a pair
+ * only if that small match finds enough correspondences (Wu, "Towards linear-time incremental structure from motion", 3DV 2013).
+ * DROPPED PAIRS LOSE REAL MATCHES: the gate trades recall of the pair graph for time.
+ *
+ * Priority.  A view may carry one float per row: its feature scale, the third column of its .feat line.  Priorities must be finite
+ * and >= 0; -0.0 is stored as +0.0.  Anything else is R3DM_ERR_INVALID; so is a count different from the view's rows, or an unknown
+ * view.  A priority belongs to the registration: r3dm_set_image(s) on that id and r3dm_clear_images remove it.
+ *
+ * Head of a view for head size h (2 <= h <= 256).  The head is the min(h, n) rows that come first under the order (priority
+ * descending, row index ascending).  The head is kept in ascending row index: a tie between two equally distant head rows therefore
+ * resolves to the lower original row, as everywhere else.  A view without priorities has its first min(h, n) rows as head.
+ *
+ * Count of a pair (I, J).  Compute the 2-NN of every head row of J among the head rows of I, with the reference's distance:
+ * exact_l2sq for F32 / U8 rows (4-way unrolled, scalar tail, no FMA) and popcount Hamming for BIN rows; ties go to the lowest row.
+ * A query counts iff d0 < R * d1 in float.  R is what the calling entry uses: r3dm_match_pairs uses ratio^2 or ratio by its
+ * squared_metric; the KGraph / HNSW / MRPT collection entries use ratio^2 on squared distances.  A head of I with fewer than two rows
+ * gives count 0.  There is no de-duplication and no mutual rule: the count is the number of accepted queries.
+ *
+ * Keep.  A pair is kept iff its count >= t, with t >= 1.  A kept pair is then matched by the entry exactly as it is today, on the
+ * whole views; a dropped pair does not enter the graph.  So the graph with the switch on is the graph with the switch off, restricted
+ * to the kept pairs -- bit for bit, on every arm and tile format.
+ *
+ * Lengths.  F32 / U8 rows of any length up to 256 elements are served, lengths with a scalar tail (37, 61 ...) included: the tail is
+ * summed as exact_l2sq sums it, not zero-padded into a group of four.  BIN rows of 29..32 and 61..64 bytes are served.  Longer L2 rows
+ * are R3DM_ERR_UNSUPPORTED: r3dm_preselect_pairs returns it, and the match entries return it when the switch is on and such a view is
+ * in the call.
+ *
+ * r3dm_set_view_priority: priority = n floats in host memory, NULL removes the view's priority (n is then ignored).
+ * r3dm_preselect_pairs: the primitive, whatever the switch says: counts_out[p] = the count of pair p, in the caller's order (a pair
+ *   with an empty view or views of different types has count 0; an unregistered view is R3DM_ERR_INVALID).
+ * r3dm_set_preemptive_matching: the switch.  While it is on, r3dm_match_pairs and r3dm_match_pairs_kgraph / _hnsw / _mrpt (and their
+ *   r3dm_multi_* forms, each context gating its own shard) gate their resolved pair list before they batch it.  IGNORED by the entries
+ *   that return raw neighbour lists -- r3dm_knn2, r3dm_knn, the r3dm_index_* family, the *_knn2 / *_knn entries -- and by guided matching.
+ *   head_rows outside 2..256 or min_matches of 0 is R3DM_ERR_INVALID (also when enable is 0: the values are stored either way).
+ * Heads are made by the first gate that needs them (host selection, one small gather kernel per view: kernels_match_head.hip) and
+ * cached per view with the h they were made for; a head is remade when h, the priority or the view changes.  r3dm_view_info shows
+ * R3DM_LAYOUT_HEAD and counts its bytes.  While the switch is off and the primitive is not called nothing is allocated or launched.
+ * r3dm_preselect_report: the last match call (the switch on) or r3dm_preselect_pairs call; all zero after a match call with the switch
+ * off.  n_kept of r3dm_preselect_pairs counts against the min_matches last set (default 4). */
+int r3dm_set_view_priority(r3dm_ctx* ctx, uint32_t view_id, const float* priority /* host */, uint32_t n);
+int r3dm_preselect_pairs(r3dm_ctx* ctx, const uint32_t* pairs_ij, uint64_t n_pairs, uint32_t head_rows, float dist_ratio,
+                         int squared_metric, uint32_t* counts_out /* [n_pairs], caller's order */);
+int r3dm_set_preemptive_matching(r3dm_ctx* ctx, int enable, uint32_t head_rows, uint32_t min_matches);
+typedef struct {
+    double ms_kernels;                 /* HIP-event time of the gather and gate kernels */
+    double ms_wall;                    /* host time of the gate: selection, uploads, kernels, the counts' way back */
+    uint64_t n_pairs;                  /* pairs the gate looked at: pairs with an empty view or views of different types are skipped, in both entries */
+    uint64_t n_kept;                   /* ... of those, pairs with count >= min_matches */
+    uint64_t n_heads_built;            /* heads made by this call (the others were cached) */
+    uint64_t n_views_without_priority; /* views of the call whose head is their first rows */
+} r3dm_preselect_stats;
+int r3dm_preselect_report(const r3dm_ctx* ctx, r3dm_preselect_stats* out);
 
 /* ---- putative matching ----
  * pairs_ij: n_pairs x 2 view ids (I, J); J's rows are the queries, I's rows the dataset.
@@ -652,6 +707,8 @@ int r3dm_multi_set_intrinsics(r3dm_multi* m, uint32_t view_id, const double* K);
 int r3dm_multi_clear_images(r3dm_multi* m);
 int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable);
 int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable);      /* r3dm_set_mutual_matching on every context */
+int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
+int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,
                            float dist_ratio, int squared_metric, r3dm_graph** out);
 /* the same deal for the graph matcher (kgraph_match, config C5): a device builds the index of every image I whose row it owns */

@@ -42,11 +42,15 @@ EXPORTS = [
     "r3dm_guided_match", "r3dm_set_guided_matching", "r3dm_guided_report", "r3dm_multi_set_guided_matching",
     "r3dm_set_keypoint_detector", "r3dm_multi_set_keypoint_detector", "r3dm_akaze_classic_components",
     "r3dm_set_mutual_matching", "r3dm_multi_set_mutual_matching", "r3dm_compute_matches_dir_flags",
+    "r3dm_set_view_priority", "r3dm_preselect_pairs", "r3dm_set_preemptive_matching", "r3dm_preselect_report",
+    "r3dm_multi_set_view_priority", "r3dm_multi_set_preemptive_matching",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
 STAGE_DETECTOR_AKAZE = 64
 STAGE_MUTUAL_MATCHING = 128
+STAGE_PREEMPTIVE_MATCHING = 256
+LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
 
 
@@ -82,6 +86,15 @@ class Stats(C.Structure):
                 ("detect_compulsory_bytes", C.c_double), ("n_filter_workgroups", C.c_uint64), ("n_filter_coop_pairs", C.c_uint64),
                 ("n_knn_integer_tiles", C.c_uint64), ("n_knn_split_tiles", C.c_uint64),
                 ("n_mutual_checked", C.c_uint64), ("n_mutual_dropped", C.c_uint64), ("n_knn_hamming_tiles", C.c_uint64)]
+
+
+class PreselectStats(C.Structure):
+    """r3dm_preselect_stats: the gate of the last match call (preemptive matching on) or preselect_pairs call"""
+    _fields_ = [("ms_kernels", C.c_double), ("ms_wall", C.c_double), ("n_pairs", C.c_uint64), ("n_kept", C.c_uint64),
+                ("n_heads_built", C.c_uint64), ("n_views_without_priority", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class GuidedStats(C.Structure):
@@ -160,9 +173,10 @@ class Stage:
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False) -> StageReport:
+            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False) -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
-        (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING)"""
+        (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING); preemptive: preemptive matching at 128 / 4
+        (R3DM_STAGE_PREEMPTIVE_MATCHING)"""
         dflag = _detector_flag(detector)
         keep = []
         arr = _stage_views(views, keep)
@@ -170,7 +184,7 @@ class Stage:
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                     (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | dflag, C.byref(rep), err, 1024)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | dflag, C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -191,11 +205,12 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False) -> StageReport:
+                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False) -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
-    detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE); mutual: R3DM_STAGE_MUTUAL_MATCHING."""
+    detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE); mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive:
+    R3DM_STAGE_PREEMPTIVE_MATCHING (head_rows 128, min_matches 4)."""
     dflag = _detector_flag(detector)
     L = load_library()
     keep = []
@@ -206,7 +221,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                       (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | dflag, C.byref(rep), err, 1024)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | dflag, C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
@@ -218,10 +233,11 @@ class _DirView(C.Structure):
 
 
 def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0, dim: int = 144, dist_ratio: float = 0.6,
-                        compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False):
+                        compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False, preemptive: bool = False):
     """R3DComputeMatches::computeMatches over a directory that holds every view's .feat / .desc (r3dm_compute_matches_dir_flags):
     exhaustive matching, the F filter when asked, matches.putative.txt / matches.f.txt.  views: dicts with id, width, height,
-    basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING.  -> (putative pairs, geometric pairs)"""
+    basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive: R3DM_STAGE_PREEMPTIVE_MATCHING (the .feat scale column is
+    every view's priority).  -> (putative pairs, geometric pairs)"""
     L = load_library()
     arr = (_DirView * len(views))(*[_DirView(int(v["id"]), int(v["width"]), int(v["height"]), str(v["basename"]).encode()) for v in views])
     npp, ngp = C.c_uint64(0), C.c_uint64(0)
@@ -229,7 +245,8 @@ def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0,
     L.r3dm_compute_matches_dir_flags.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64,
                                                  C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     rc = L.r3dm_compute_matches_dir_flags(device_id, matches_dir.encode(), arr, len(views), dtype, dim, dist_ratio, int(compute_F), seed,
-                                          (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0), C.byref(npp), C.byref(ngp), err, 1024)
+                                          (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0),
+                                          C.byref(npp), C.byref(ngp), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_dir_flags -> {rc}: {err.value.decode()}")
     return int(npp.value), int(ngp.value)
@@ -337,6 +354,12 @@ def load_library():
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_mutual_matching.argtypes = [vp, C.c_int]
     L.r3dm_multi_set_mutual_matching.argtypes = [vp, C.c_int]
+    L.r3dm_set_view_priority.argtypes = [vp, u32, vp, u32]
+    L.r3dm_multi_set_view_priority.argtypes = [vp, u32, vp, u32]
+    L.r3dm_preselect_pairs.argtypes = [vp, vp, C.c_uint64, u32, C.c_float, C.c_int, vp]
+    L.r3dm_set_preemptive_matching.argtypes = [vp, C.c_int, u32, u32]
+    L.r3dm_multi_set_preemptive_matching.argtypes = [vp, C.c_int, u32, u32]
+    L.r3dm_preselect_report.argtypes = [vp, vp]
     L.r3dm_index_create.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
     L.r3dm_index_knn2.argtypes = [vp, vp, vp, u32, vp, vp]
     L.r3dm_index_destroy.argtypes = [vp]; L.r3dm_index_destroy.restype = None
@@ -989,6 +1012,31 @@ class Context:
         n_mutual_dropped report the last call.  knn2 / knn / the index entries return raw lists and ignore it"""
         self._check(self._L.r3dm_set_mutual_matching(self._h, int(bool(enable))), "r3dm_set_mutual_matching")
 
+    def set_view_priority(self, view_id: int, priority):
+        """r3dm_set_view_priority: one float per row of the view (its feature scale: finite, >= 0), or None to remove it"""
+        p = None if priority is None else np.ascontiguousarray(priority, np.float32).reshape(-1)
+        self._check(self._L.r3dm_set_view_priority(self._h, view_id, None if p is None else p.ctypes.data, 0 if p is None else p.size), "r3dm_set_view_priority")
+
+    def preselect_pairs(self, pairs, head_rows: int = 128, dist_ratio: float = 0.6, squared_metric: bool = True) -> np.ndarray:
+        """r3dm_preselect_pairs: the count of every pair (its accepted queries when the head_rows largest-priority rows of J are
+        2-NN-matched against those of I), in the caller's order; works whatever set_preemptive_matching says"""
+        pairs = np.ascontiguousarray(pairs, np.uint32).reshape(-1, 2)
+        counts = np.zeros(pairs.shape[0], np.uint32)
+        self._check(self._L.r3dm_preselect_pairs(self._h, _ptr(pairs) if pairs.size else None, pairs.shape[0], head_rows, dist_ratio,
+                                                 int(squared_metric), _ptr(counts) if counts.size else None), "r3dm_preselect_pairs")
+        return counts
+
+    def set_preemptive_matching(self, enable: bool = True, head_rows: int = 128, min_matches: int = 4):
+        """opt-in preemptive matching (include/r3dm.h: r3dm_set_preemptive_matching): match_pairs and the approximate matchers match a
+        pair only if its preselect count reaches min_matches -- dropped pairs lose real matches; knn2 / knn / the index entries ignore it"""
+        self._check(self._L.r3dm_set_preemptive_matching(self._h, int(bool(enable)), head_rows, min_matches), "r3dm_set_preemptive_matching")
+
+    def preselect_report(self) -> dict:
+        """r3dm_preselect_report: the gate of the last call (times, pairs, pairs kept, heads built, views without priority)"""
+        s = PreselectStats()
+        self._check(self._L.r3dm_preselect_report(self._h, C.byref(s)), "r3dm_preselect_report")
+        return s.as_dict()
+
     def set_split_mfma(self, enable: bool = True):
         """opt-in split-f16 nominator for real-valued descriptors (include/r3dm.h: r3dm_set_split_mfma)"""
         self._check(self._L.r3dm_set_split_mfma(self._h, int(bool(enable))), "r3dm_set_split_mfma")
@@ -1313,6 +1361,22 @@ class MultiContext:
     def set_mutual_matching(self, enable: bool = True):
         """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""
         self._check(self._L.r3dm_multi_set_mutual_matching(self._h, int(bool(enable))), "r3dm_multi_set_mutual_matching")
+
+    def set_view_priority(self, view_id: int, priority):
+        """r3dm_multi_set_view_priority: Context.set_view_priority on every context"""
+        p = None if priority is None else np.ascontiguousarray(priority, np.float32).reshape(-1)
+        self._check(self._L.r3dm_multi_set_view_priority(self._h, view_id, None if p is None else p.ctypes.data, 0 if p is None else p.size),
+                    "r3dm_multi_set_view_priority")
+
+    def device_preselect_report(self, k: int) -> dict:
+        """r3dm_preselect_report of context k: the gate of its shard of the last call"""
+        s = PreselectStats()
+        self._check(self._L.r3dm_preselect_report(self._L.r3dm_multi_ctx(self._h, k), C.byref(s)), "r3dm_preselect_report")
+        return s.as_dict()
+
+    def set_preemptive_matching(self, enable: bool = True, head_rows: int = 128, min_matches: int = 4):
+        """r3dm_multi_set_preemptive_matching: Context.set_preemptive_matching on every context; each gates its own shard"""
+        self._check(self._L.r3dm_multi_set_preemptive_matching(self._h, int(bool(enable)), head_rows, min_matches), "r3dm_multi_set_preemptive_matching")
 
     def set_guided_matching(self, enable: bool = True, ratio_F: float = 0.6, ratio_E: float = 0.6, ratio_H: float = -1.0):
         self._check(self._L.r3dm_multi_set_guided_matching(self._h, int(bool(enable)), ratio_F, ratio_E, ratio_H), "r3dm_multi_set_guided_matching")

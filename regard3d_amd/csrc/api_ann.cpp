@@ -76,11 +76,14 @@ static int merge_parts_keep_mirror(r3dm_graph& ga, r3dm_graph& gs, r3dm_graph** 
 
 int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float scanned_ratio_R, const AnnArm& arm, r3dm_graph** out)
 {
+    const float gate_ratio_R = scanned_ratio_R;       // the three arms scan with ratio^2 on squared distances: the gate's R as well
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
     const double t_call = now_ms();
     std::vector<PairJob> indexed, scanned;
     int rc = resolve_pairs(c, pairs_ij, n_pairs, arm.classify, indexed, scanned);
+    if (rc != R3DM_OK) return rc;
+    rc = preselect_gate(c, gate_ratio_R, indexed, scanned);                // r3dm_set_preemptive_matching
     if (rc != R3DM_OK) return rc;
 
     r3dm_graph ga, gs;

@@ -50,6 +50,11 @@ extern "C" void r3dm_destroy(r3dm_ctx* c)
     c->gb.release();
     c->coop_sched.release();
     c->d_mutual.release();
+    for (DevBuf* b : {&c->pre_rows, &c->pre_heads, &c->pre_pairs, &c->pre_counts}) b->release();
+    c->pre_pin.release();
+    if (c->pre_ev0) (void)hipEventDestroy(c->pre_ev0);
+    if (c->pre_ev1) (void)hipEventDestroy(c->pre_ev1);
+    c->pre_ev0 = c->pre_ev1 = nullptr;
     if (c->coop_ev) (void)hipEventDestroy(c->coop_ev);
     if (c->coop_stream) (void)hipStreamDestroy(c->coop_stream);
     c->coop_ev = nullptr; c->coop_stream = nullptr;
@@ -659,7 +664,7 @@ extern "C" int r3dm_view_info(r3dm_ctx* c, uint32_t view_id, uint32_t* layouts, 
     if (it == c->slot_of.end()) { c->err = "unregistered view"; return R3DM_ERR_INVALID; }
     const HostImage& h = *c->imgs[it->second];
     static_assert(kLayRows == R3DM_LAYOUT_ROWS && kLayBf16 == R3DM_LAYOUT_BF16 && kLaySplit == R3DM_LAYOUT_SPLIT && kLayCounts == R3DM_LAYOUT_COUNTS &&
-                  kLayBin8 == R3DM_LAYOUT_BIN8, "public layout bits");
+                  kLayBin8 == R3DM_LAYOUT_BIN8 && kLayHead == R3DM_LAYOUT_HEAD, "public layout bits");
     if (layouts) *layouts = h.have;
     if (bytes) {
         // what the view's live layouts occupy (a recycled buffer may be larger than its present tenant; buffers of layouts the view
@@ -672,6 +677,7 @@ extern "C" int r3dm_view_info(r3dm_ctx* c, uint32_t view_id, uint32_t* layouts, 
         if (h.have & kLaySplit) b += h.tiledh.cap;
         if (h.have & kLayCounts) b += h.tiledc.cap + h.tiledp.cap + h.cscale.cap + h.cquad.cap + h.cperm.cap;
         if (h.have & kLayBin8) b += h.tiled8.cap + h.norms.cap;
+        if (h.have & kLayHead) b += h.head.cap;
         if (h.ann_K) b += h.ann_adj.cap + h.ann_deg.cap;
         if (h.compact_ready) b += h.ann_rows16.cap + h.ann_rows8.cap;
         if (h.hnsw_M) b += h.hnsw_l0.cap + h.hnsw_up_off.cap + h.hnsw_up.cap;

@@ -363,10 +363,11 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     std::vector<PairJob> jobs, none;
     const int rcp = resolve_pairs(c, pairs_ij, n_pairs, nullptr, none, jobs);
     if (rcp != R3DM_OK) return rcp;
+    const float R = squared_metric ? dist_ratio * dist_ratio : dist_ratio;
+    { const int rcg = preselect_gate(c, R, none, jobs); if (rcg != R3DM_OK) return rcg; }      // r3dm_set_preemptive_matching
 
     auto g = std::unique_ptr<r3dm_graph>(new r3dm_graph());
     g->offsets.push_back(0);
-    const float R = squared_metric ? dist_ratio * dist_ratio : dist_ratio;
 
     // batches: same (dtype, dim) and a bounded nn_idx footprint
     size_t start = 0;

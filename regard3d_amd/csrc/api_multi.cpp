@@ -208,6 +208,20 @@ extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    return for_each_device(m, [&](uint32_t, r3dm_ctx* c) { return r3dm_set_view_priority(c, view_id, priority, n); });
+}
+
+extern "C" int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    int rc = R3DM_OK;
+    for (r3dm_ctx* c : m->ctx) { const int r = r3dm_set_preemptive_matching(c, enable, head_rows, min_matches); if (r != R3DM_OK) { rc = r; m->err = c->err; } }
+    return rc;
+}
+
 extern "C" int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H)
 {
     if (!m) return R3DM_ERR_INVALID;

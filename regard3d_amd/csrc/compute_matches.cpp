@@ -2,6 +2,7 @@
 // on top of the C ABI only.  Stage order follows /root/reference/src/R3DComputeMatches.cpp:1996-2129:
 // load regions -> exhaustive pairs -> match -> save matches.putative.txt -> F filter -> save matches.f.txt.
 #include "../../include/r3d_compute_matches.hpp"
+#include "feat_text.hpp"
 
 #include <charconv>
 #include <chrono>
@@ -21,47 +22,7 @@ namespace r3d_amd {
 
 namespace {
 
-// .feat: one "x y scale orientation" text line per feature; .desc: 8-byte count + raw rows
-// (/root/reference/src/keypointSet.hpp:49-67 -> OpenMVG loadFeatsFromFile / loadDescsFromBinFile)
-bool load_feat(const std::string& path, std::vector<float>& xy)
-{
-    // the whole file in one buffer, one from_chars per field (what `stream >> float` does, without the stream): groups of four
-    // numbers until the first group that is not complete, like `while (f >> x >> y >> s >> o)`
-    FILE* f = fopen(path.c_str(), "rb");
-    if (!f) return false;
-    std::vector<char> txt;
-    bool ok = fseek(f, 0, SEEK_END) == 0;
-    const long sz = ok ? ftell(f) : -1;
-    ok = ok && sz >= 0 && fseek(f, 0, SEEK_SET) == 0;
-    if (ok) { txt.resize((size_t)sz + 1); ok = fread(txt.data(), 1, (size_t)sz, f) == (size_t)sz; txt[(size_t)sz] = 0; }
-    fclose(f);
-    if (!ok) return false;
-    xy.clear();
-    // locale-independent, like the classic-locale `stream >> float` of OpenMVG's reader (the host application calls
-    // setlocale(LC_ALL, ""), so strtof would read "12.5" as 12 under a comma-decimal locale): std::from_chars, after the white
-    // space and the optional sign that operator>> accepts; hex / inf / nan tokens are not numbers for operator>> and end the file here too
-    const char* s = txt.data();
-    const char* const end_txt = s + (size_t)sz;
-    for (;;) {
-        float v[4];
-        int k = 0;
-        for (; k < 4; ++k) {
-            while (s < end_txt && (*s == ' ' || *s == '\n' || *s == '\t' || *s == '\r' || *s == '\f' || *s == '\v')) ++s;
-            const char* t = s;
-            bool neg = false;
-            if (t < end_txt && (*t == '+' || *t == '-')) { neg = *t == '-'; ++t; }
-            if (t >= end_txt || !((*t >= '0' && *t <= '9') || *t == '.')) break;
-            const std::from_chars_result r = std::from_chars(t, end_txt, v[k], std::chars_format::general);
-            if (r.ec == std::errc::invalid_argument) break;
-            if (r.ec == std::errc::result_out_of_range) v[k] = 0.0f;     // (never for pixel coordinates) operator>> sets failbit; keep going with 0
-            if (neg) v[k] = -v[k];
-            s = r.ptr;
-        }
-        if (k < 4) break;
-        xy.push_back(v[0]); xy.push_back(v[1]);
-    }
-    return true;
-}
+using r3dm_feat::load_feat;      // feat_text.hpp
 
 // first thing in a background writer thread: its work has a whole phase to hide behind, so under contention for the host's cores it
 // stands back (Linux: a per-thread nice value, inherited by the helpers it starts)
@@ -247,10 +208,12 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     }
     const int n_ctx = r3dm_multi_num_devices(feat_multi_);
     (void)r3dm_multi_set_keypoint_detector(feat_multi_, dl[0] == "AKAZE" ? R3DM_DETECTOR_AKAZE : R3DM_DETECTOR_FAST_AKAZE);
-    (void)r3dm_multi_set_features_sink(feat_multi_, direct_registration_ ? &R3DComputeMatches::features_sink : nullptr, this);
+    // the sink carries no scales: while preemptive matching is on, every view is registered from its files (setPreemptiveMatching)
+    const bool direct = direct_registration_ && !preemptive_on_;
+    (void)r3dm_multi_set_features_sink(feat_multi_, direct ? &R3DComputeMatches::features_sink : nullptr, this);
     // the .feat / .desc of a batch are written behind the sink calls, beside the match phase (computeMatches waits for them before it
     // returns): only when the views are registered straight from the device, else Regions_Provider::load reads those files next
-    (void)r3dm_multi_set_deferred_feature_files(feat_multi_, direct_registration_ ? 1 : 0);
+    (void)r3dm_multi_set_deferred_feature_files(feat_multi_, direct ? 1 : 0);
     (void)r3dm_multi_set_background_nice(feat_multi_, background_nice_);
     r3dm_features_totals before{};
     for (int k = 0; k < n_ctx; ++k) {
@@ -338,6 +301,14 @@ void R3DComputeMatches::setMutualMatching(bool on)
     if (multi_) (void)r3dm_multi_set_mutual_matching(multi_, on ? 1 : 0);
 }
 
+void R3DComputeMatches::setPreemptiveMatching(bool on, uint32_t head_rows, uint32_t min_matches)
+{
+    int rc = R3DM_OK;
+    if (ctx_) rc = r3dm_set_preemptive_matching(ctx_, on ? 1 : 0, head_rows, min_matches);
+    if (multi_) rc = r3dm_multi_set_preemptive_matching(multi_, on ? 1 : 0, head_rows, min_matches);
+    preemptive_on_ = on && rc == R3DM_OK;
+}
+
 void R3DComputeMatches::setGuidedMatching(bool on, double ratio_F, double ratio_E, double ratio_H)
 {
     if (ctx_) (void)r3dm_set_guided_matching(ctx_, on ? 1 : 0, ratio_F, ratio_E, ratio_H);
@@ -373,6 +344,8 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
     auto clear_images = [&]() { return ctx_ ? r3dm_clear_images(ctx_) : r3dm_multi_clear_images(multi_); };
     auto set_image = [&](uint32_t id, uint32_t w, uint32_t h, const void* d, uint32_t n, const float* xy) {
         return ctx_ ? r3dm_set_image(ctx_, id, w, h, d, n, dim_, dtype_, xy) : r3dm_multi_set_image(multi_, id, w, h, d, n, dim_, dtype_, xy); };
+    auto set_priority = [&](uint32_t id, const std::vector<float>& s) {
+        return ctx_ ? r3dm_set_view_priority(ctx_, id, s.data(), (uint32_t)s.size()) : r3dm_multi_set_view_priority(multi_, id, s.data(), (uint32_t)s.size()); };
     auto set_intrinsics = [&](uint32_t id, const double* K) { return ctx_ ? r3dm_set_intrinsics(ctx_, id, K) : r3dm_multi_set_intrinsics(multi_, id, K); };
     auto match = [&](const std::vector<uint32_t>& p, float ratio, int squared, r3dm_graph** out) {
         return ctx_ ? r3dm_match_pairs(ctx_, p.data(), p.size() / 2, ratio, squared, out) : r3dm_multi_match_pairs(multi_, p.data(), p.size() / 2, ratio, squared, out); };
@@ -411,7 +384,7 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
     // ---- Regions_Provider::load + Features_Provider::load (src/R3DComputeMatches.cpp:2040,2094-2095): the views the features stage
     // computed in this call are registered already (features_sink); the files of the others are read here
     // files are read and parsed by all host threads, 64 views at a time; registration (device copies) stays in view order
-    struct Loaded { std::vector<float> xy; std::vector<unsigned char> desc; uint64_t n = 0; bool ok = false; };
+    struct Loaded { std::vector<float> xy, scale; std::vector<unsigned char> desc; uint64_t n = 0; bool ok = false; };
     std::vector<Loaded> chunk;
     std::vector<char> batch_done;
     for (size_t vi = 0; vi < views_.size(); ++vi) {
@@ -424,7 +397,7 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
                 Loaded& L = chunk[(size_t)k];
                 if (registered_[vi + (size_t)k]) { L.ok = true; continue; }
                 // nothing may leave an OpenMP region by exception (std::terminate): a failed allocation is a failed load
-                try { L.ok = load_feat(dir + "/" + u.basename + ".feat", L.xy) && load_desc(dir + "/" + u.basename + ".desc", row_bytes, L.desc, L.n); }
+                try { L.ok = load_feat(dir + "/" + u.basename + ".feat", L.xy, preemptive_on_ ? &L.scale : nullptr) && load_desc(dir + "/" + u.basename + ".desc", row_bytes, L.desc, L.n); }
                 catch (...) { L.ok = false; }
             }
             // one device: the chunk's views go to the matcher in ONE call (r3dm_set_images: helper threads fill the page-locked ring beside
@@ -466,6 +439,8 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
                 const int rc = set_image(v.id_view, v.ui_width, v.ui_height, desc.data(), (uint32_t)n, xy.data());
                 if (rc != R3DM_OK) { errorMessage_ = last_error(); return false; }
             }
+            // the scale column is the view's priority (r3dm_set_view_priority) while preemptive matching is on
+            if (preemptive_on_ && n && set_priority(v.id_view, L.scale) != R3DM_OK) { errorMessage_ = "feature scales of " + v.basename + ": " + last_error(); return false; }
         }
         if (v.focal_px > 0.0) {
             const double K[9] = {v.focal_px, 0.0, v.ppx, 0.0, v.focal_px, v.ppy, 0.0, 0.0, 1.0};      // Pinhole_Intrinsic::K()
@@ -702,6 +677,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setExactFastPaths((flags & R3DM_STAGE_F32_TILES) == 0);      // (R3DM_STAGE_SPLIT_MFMA / _INTEGER_MFMA: implied since round 3)
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         stage.setMutualMatching((flags & R3DM_STAGE_MUTUAL_MATCHING) != 0);
+        stage.setPreemptiveMatching((flags & R3DM_STAGE_PREEMPTIVE_MATCHING) != 0);
         r3d_amd::R3DFParams params;
         params.keypointDetectorList_ = {(flags & R3DM_STAGE_DETECTOR_AKAZE) ? "AKAZE" : "Fast-AKAZE"};
         params.threshold_ = threshold;
@@ -772,6 +748,7 @@ extern "C" int r3dm_compute_matches_dir_flags(int device_id, const char* matches
     stage.setSeed(seed);
     if (flags & R3DM_STAGE_F32_TILES) stage.setExactFastPaths(false);
     if (flags & R3DM_STAGE_MUTUAL_MATCHING) stage.setMutualMatching(true);
+    if (flags & R3DM_STAGE_PREEMPTIVE_MATCHING) stage.setPreemptiveMatching(true);
     r3d_amd::R3DFParams params;
     params.distRatio_ = dist_ratio;
     params.computeFundalmentalMatrix_ = compute_F != 0;

@@ -3,6 +3,7 @@
 //   api_match.cpp     exhaustive putative matching: 2-NN batches (run_match_batch), k-NN (run_knn_batch), the mutual check in front of
 //                     every finalisation into a graph (finalize_batch), one certificate slack
 //                     (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
+//   api_preselect.cpp preemptive matching: view priorities, heads, the gate behind resolve_pairs, r3dm_preselect_pairs
 //   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
 //   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules
@@ -219,6 +220,7 @@ enum : uint32_t {
     kLaySplit  = 4u,     // split-f16 planes (r3dm_set_split_mfma)
     kLayCounts = 8u,     // count tiles + scale order (r3dm_set_split_mfma, rows = integer votes x a row scale); needs kLayRows
     kLayBin8   = 16u,    // one byte per bit in i8 fragment order (r3dm_set_hamming_mfma)
+    kLayHead   = 32u,    // the head rows of preemptive matching, row-major (api_preselect.cpp: ensure_heads, not ensure_layouts)
 };
 
 // the count tiles exist only for f32 views of at most 256 dimensions (anything else is never votes x scale: counts_ok stays false)
@@ -244,6 +246,8 @@ struct ViewState {
     uint32_t ann_K = 0;               // graph index (r3dm_match_pairs_kgraph) in ann_adj / ann_deg
     uint32_t hnsw_M = 0, hnsw_seed = 0, hnsw_up_rows = 0; int32_t hnsw_enter = -1, hnsw_maxlevel = -1;     // HNSW index, valid when hnsw_M != 0
     uint32_t mrpt_trees = 0, mrpt_depth = 0; float mrpt_density = 0.0f; uint64_t mrpt_seed = 0;          // MRPT index, valid when mrpt_trees != 0
+    std::vector<float> priority;      // r3dm_set_view_priority: one per row, or empty
+    uint32_t head_h = 0, head_n = 0;  // kLayHead: the head size the head buffer was made for, and its rows (min(head_h, n))
 };
 
 // A slot of a context's view table.  What survives which transition:
@@ -257,7 +261,7 @@ struct ViewState {
 struct HostImage : ViewState {
     bool borrowed = false;
     struct r3dm_index* owner = nullptr;   // (layouts staged on first use are added to the index, under its lock)
-    DevBuf rows, tiled, tiled16, tiledh, tiledc, tiledp, cscale, cquad, cperm, tiled8, norms, bin, xy, canon;
+    DevBuf rows, tiled, tiled16, tiledh, tiledc, tiledp, cscale, cquad, cperm, tiled8, norms, bin, xy, canon, head;
     DevBuf ann_adj, ann_deg, ann_rows16, ann_rows8;   // graph index; compact row copies only for bf16- / u8-exact views
     DevBuf hnsw_l0, hnsw_up_off, hnsw_up;             // hnswlib's arrays (kernels_hnsw.hip: HnswView)
     DevBuf mrpt_R, mrpt_RT, mrpt_splits, mrpt_leaves, mrpt_lf;      // kernels_mrpt.hip: MrptView
@@ -265,7 +269,7 @@ struct HostImage : ViewState {
     double Kinv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // the layout buffers of a view registered with a context are blocks of the context's arena (an r3dm_index owns plain allocations:
     // it outlives contexts)
-    std::array<DevBuf*, 14> layout_bufs() { return {&rows, &tiled, &tiled16, &tiledh, &tiledc, &tiledp, &cscale, &cquad, &cperm, &tiled8, &norms, &bin, &xy, &canon}; }
+    std::array<DevBuf*, 15> layout_bufs() { return {&rows, &tiled, &tiled16, &tiledh, &tiledc, &tiledp, &cscale, &cquad, &cperm, &tiled8, &norms, &bin, &xy, &canon, &head}; }
     void use_arena(DevArena* a) { for (DevBuf* x : layout_bufs()) x->arena = a; }
     void new_tenant(uint32_t id, uint32_t n_, uint32_t dim_, r3dm_dtype dtype_, uint32_t width_, uint32_t height_, bool xy)
     {
@@ -530,6 +534,14 @@ struct r3dm_ctx {
     bool knn_hamming_tiles = false;                         // r3dm_set_knn_hamming_tiles
     bool mutual_matching = false;                           // r3dm_set_mutual_matching: the mutual check runs before every finalisation into a graph
     DevBuf d_mutual;                                        // its two counters (allocated by the first batch that runs the check)
+    // r3dm_set_preemptive_matching (api_preselect.cpp): the switch, its head size and threshold; the buffers of a gate call (row lists,
+    // head table, pairs, counts), its events and its report -- all made by the first gate
+    bool preemptive_on = false;
+    uint32_t preemptive_h = 128, preemptive_t = 4;
+    DevBuf pre_rows, pre_heads, pre_pairs, pre_counts;
+    PinBuf pre_pin;
+    hipEvent_t pre_ev0 = nullptr, pre_ev1 = nullptr;
+    r3dm_preselect_stats preselect_stats{};
     bool device_graphs = false;                             // r3dm_set_device_graphs: match / filter results keep a device mirror (GraphDev)
     DevBuf g_segs;                                          // segment table of the graph gather kernel (kernels_graph.hip)
     uint32_t liop_npix = 0;
@@ -703,6 +715,9 @@ using PairClassifier = std::function<int(const HostImage& A, bool& index)>;
 // pairs_ij -> the jobs of its valid pairs, ordered by (I, J), unique; no classifier: every job is scanned
 int resolve_pairs(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, const PairClassifier& classify,
                   std::vector<PairJob>& indexed, std::vector<PairJob>& scanned);
+// the gate of preemptive matching (api_preselect.cpp), called by the four collection entries right after resolve_pairs: resets the
+// report; while the switch is on, both lists keep only the pairs whose head count reaches the threshold under ratio R
+int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned);
 // What a collection call of an arm is made of.  The chunk rules differ on purpose: KGraph and HNSW launch one descriptor length at a
 // time, MRPT's job records carry their own; HNSW and MRPT launch a grid row per pair (65,535 at most), KGraph does not.
 struct AnnArm {

@@ -256,6 +256,21 @@ struct MutualParams {
     unsigned long long* counters; // [2]: matches checked, matches dropped (atomic; zeroed by the host)
 };
 
+// the gate of preemptive matching (kernels_match_head.hip; r3dm_set_preemptive_matching, r3dm_preselect_pairs): a view's head is its
+// min(h, n) largest-scale rows in a row-major buffer of its own; the table of a gate call is indexed by slot
+struct HeadDev {
+    const void* rows;             // f32 [n][8 G] (F32 / U8 views) or u32 [n][words] (BIN views)
+    uint32_t    n;                // head rows, <= 256
+    uint32_t    dim;              // floats per row as registered (F32 / U8); unused for BIN
+};
+struct HeadPair { uint32_t sI, sJ, out; };      // slots of the pair, entry of `counts` that receives its count
+struct HeadMatchParams {
+    const HeadDev*  heads;
+    const HeadPair* pairs;        // the launch's pairs (one workgroup each): one length class
+    uint32_t*       counts;
+    float           ratio_R;      // ratio^2 (squared metric) or ratio
+};
+
 constexpr int kCoopB = 32;                  // models per batch of the cooperative AC-RANSAC kernel, at most
 constexpr uint32_t kCoopMaxG = 30;          // slices per pair, at most (5-bit slice code of a task, 31 = start-up)
 
@@ -470,6 +485,10 @@ hipError_t launch_hamming_knn2(hipStream_t st, const MatchParams& P, uint32_t wo
 hipError_t launch_l2_mutual_batch(hipStream_t st, const MutualParams& P, uint32_t G);
 hipError_t launch_l2_mutual_items(hipStream_t st, const MutualParams& P, uint32_t count);
 hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t words);
+// preemptive matching: `hn` listed rows of a view -> its head buffer (per_row: float4 per padded row / words per row); the gate itself,
+// one workgroup per pair (G of 8 / 16 / 18 / 32, or 8 / 16 words)
+hipError_t launch_head_gather(hipStream_t st, const void* src, const uint32_t* rows, uint32_t hn, uint32_t per_row, bool binary, void* out);
+hipError_t launch_head_match(hipStream_t st, const HeadMatchParams& P, uint32_t n_pairs, bool binary, uint32_t G_or_words);
 hipError_t launch_finalize(hipStream_t st, const FinalizeParams& P);
 hipError_t launch_filter_F(hipStream_t st, const FilterParams& P);
 // one pool of workers for the long pairs of up to three filters: dev_params = FilterParams[3] in device memory indexed by model kind,
