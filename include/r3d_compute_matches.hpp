@@ -65,6 +65,14 @@ struct View {
 using MatchList = std::vector<r3dm_match>;          // IndMatches (IndMatch{i_, j_} == r3dm_match{i, j})
 using PairWiseMatches = std::map<std::pair<uint32_t, uint32_t>, MatchList>;
 
+// feature tracks of a PairWiseMatches map (r3dm_build_tracks): track t is observations[offsets[t] .. offsets[t + 1]), sorted by view id;
+// tracks are sorted by their first observation
+struct Tracks {
+    std::vector<uint64_t> offsets;
+    std::vector<r3dm_observation> observations;
+    r3dm_tracks_stats stats;
+};
+
 class R3DComputeMatches {
 public:
     // matchingAlgorithm value of the new dispatch arm next to src/R3DComputeMatches.cpp:2054-2062;
@@ -153,6 +161,13 @@ public:
 
     bool computeMatches(R3DFParams& params, bool svgOutput, const R3DProjectPaths& paths,
                         int cameraModel, int matchingAlgorithm);
+
+    // openMVG::tracks::TracksBuilder::Build(map_Matches) + Filter(min_length) + ExportToSTL on the GPU (r3dm_build_tracks: the
+    // contract is in r3dm.h), as Regard3D's match preview runs it behind "Enable Track Filter" and OpenMVG's SfM engines run it first
+    // thing.  `matches`: getStatistics().fundamentalMatches_, or a map loaded from a matches.*.txt.  `kept` (optional): the map
+    // restricted to the matches whose component is a track (pairs left empty are dropped).  On a device-list facade it runs on the
+    // first device.  false: errorMessage() says why (min_length < 2; feature indices beyond R3DM_TRACKS_MAX_SLOTS slots; a HIP failure).
+    bool buildTracks(const PairWiseMatches& matches, uint32_t min_length, Tracks* out, PairWiseMatches* kept = nullptr);
 
     // wall time of the phases of the last computeMatches call, milliseconds (no reference counterpart: the GUI shows progress only)
     struct PhaseTimes {

@@ -791,6 +791,56 @@ void r3dm_words_free(uint32_t* words);
 int  r3dm_graphs_unpack_merge(const uint32_t* const* rank_words, const uint64_t* rank_n_words, uint32_t world, uint32_t n_graphs,
                               r3dm_graph** merged_out /* [n_graphs] */);
 
+/* ---- feature tracks of a match graph: OpenMVG's TracksBuilder (Build, Filter, ExportToSTL, GetTracksInImages) on the GPU ----
+ * Nodes and edges.  For pair p = (I, J) of g and match (i, j) of that pair the nodes are (I, i) and (J, j), and the match is an edge
+ *   between them.  No special cases: duplicate edges are edges; the same two views listed as (I, J) and as (J, I) contribute alike; a
+ *   pair with I == J contributes like any other (i != j joins two features of one view, i == j is a loop on one node).  View ids are
+ *   arbitrary uint32 values, sparse or huge.
+ * Components and the filter.  Components are the connected components over all nodes that appear in g.  The filter is
+ *   TracksBuilder::Filter(nLengthSupTo): a component that contains two different nodes of one view is CONFLICTING and is removed
+ *   whatever its size; of the rest, a component with fewer than min_length nodes is SHORT and is removed.  min_length >= 2; smaller
+ *   values are R3DM_ERR_INVALID.  What remains are the tracks.
+ * Canonical output.  A track's observations are sorted by view id ascending (one per view).  Tracks are sorted by their first
+ *   observation, (view id, feature) ascending.  Track t is observations[offsets[t] .. offsets[t + 1]).  The output is a pure function
+ *   of g and min_length: it does not depend on the order in which unions land on the device.  (OpenMVG numbers tracks by union-find
+ *   root; the set of tracks is the same, the numbering is this library's.)
+ * Size limit.  With s(v) = 1 + the largest feature index view v has in g, a graph whose sum of s(v) exceeds R3DM_TRACKS_MAX_SLOTS is
+ *   R3DM_ERR_UNSUPPORTED: returned before anything sized by that sum is allocated.  So is a graph of 2^32 - 1 matches or more.
+ * Trivial cases.  An empty graph gives zero tracks (offsets = {0}) and success.
+ * kept_out (may be NULL): the track filter applied to the graph itself -- g restricted to the matches whose component is a track, order
+ *   of pairs and of matches unchanged, pairs left empty dropped.  It gets a device mirror under the rule of every produced graph
+ *   (r3dm_set_device_graphs).
+ * Inputs.  A graph with a device mirror on the context's device is read where it is; any other graph (r3dm_graph_from_csr, loaded,
+ *   merged) is uploaded.  NULL handles are R3DM_ERR_INVALID.  Nothing is allocated or launched for this feature before the first call.
+ * r3dm_tracks_in_pair: GetTracksInImages({a, b}) as Regard3D's match preview uses it -- for every track, in track order, that observes
+ *   both views: (feature in view_a, feature in view_b).  Not only direct matches: transitive ones appear too.  At most cap entries are
+ *   written (out may be NULL when cap is 0); *n_out is the full count.  view_a == view_b is R3DM_ERR_INVALID; an unknown view gives
+ *   zero results.  Host code over the arrays above.
+ * r3dm_tracks_phase_ms: ms_kernels split into the call's four phases, each between two counts the host reads back: [0] the views'
+ *   extents, [1] link + flatten + the selection of the nodes, [2] the sort by root + conflicts + the filter + the selection of the
+ *   observations, [3] observations, offsets, kept matches.
+ * Memory.  The work buffers are the context's and serve its next call; those above 64 MiB each are given back to the device when the
+ *   call returns, so a graph near the slot limit (11 bytes per slot) does not pin gigabytes until r3dm_destroy.
+ * The arrays of an r3dm_tracks live until r3dm_tracks_free. */
+#define R3DM_TRACKS_MAX_SLOTS (1ull << 28)
+typedef struct r3dm_tracks r3dm_tracks;
+typedef struct { uint32_t view, feature; } r3dm_observation;
+typedef struct {
+    uint64_t n_matches, n_nodes, n_components, n_conflicting, n_short, n_tracks, n_observations;
+    uint64_t n_matches_kept;          /* matches of g whose component is a track */
+    uint32_t longest;                 /* observations of the longest track */
+    uint32_t largest_component;       /* nodes of the largest component, removed ones included */
+    double   ms_kernels, ms_wall;     /* HIP-event time of the device work (uploads excluded); the whole call */
+} r3dm_tracks_stats;
+int r3dm_build_tracks(r3dm_ctx* ctx, const r3dm_graph* g, uint32_t min_length, r3dm_tracks** out, r3dm_graph** kept_out /* may be NULL */);
+uint64_t                r3dm_tracks_count(const r3dm_tracks* t);
+const uint64_t*         r3dm_tracks_offsets(const r3dm_tracks* t);       /* n_tracks + 1 */
+const r3dm_observation* r3dm_tracks_observations(const r3dm_tracks* t);
+int  r3dm_tracks_report(const r3dm_tracks* t, r3dm_tracks_stats* out);
+int  r3dm_tracks_phase_ms(const r3dm_tracks* t, double* out4);
+int  r3dm_tracks_in_pair(const r3dm_tracks* t, uint32_t view_a, uint32_t view_b, r3dm_match* out, uint64_t cap, uint64_t* n_out);
+void r3dm_tracks_free(r3dm_tracks* t);
+
 /* ---- files: ".txt" (what Regard3D's consumers read) or ".bin" (cereal portable binary) ---- */
 int r3dm_save_matches(const r3dm_graph* g, const char* path);
 int r3dm_load_matches(const char* path, r3dm_graph** out);

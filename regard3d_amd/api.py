@@ -44,6 +44,8 @@ EXPORTS = [
     "r3dm_set_mutual_matching", "r3dm_multi_set_mutual_matching", "r3dm_compute_matches_dir_flags",
     "r3dm_set_view_priority", "r3dm_preselect_pairs", "r3dm_set_preemptive_matching", "r3dm_preselect_report",
     "r3dm_multi_set_view_priority", "r3dm_multi_set_preemptive_matching",
+    "r3dm_build_tracks", "r3dm_tracks_count", "r3dm_tracks_offsets", "r3dm_tracks_observations", "r3dm_tracks_report", "r3dm_tracks_phase_ms", "r3dm_tracks_in_pair",
+    "r3dm_tracks_free",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
@@ -106,6 +108,16 @@ class GuidedStats(C.Structure):
         d = {k: getattr(self, k) for k, _ in self._fields_}
         d["candidates_per_query"] = self.n_candidates / self.n_queries if self.n_queries else 0.0
         return d
+
+
+class TracksStats(C.Structure):
+    """r3dm_tracks_stats"""
+    _fields_ = [(n, C.c_uint64) for n in ("n_matches", "n_nodes", "n_components", "n_conflicting", "n_short", "n_tracks", "n_observations",
+                                          "n_matches_kept")] + \
+               [("longest", C.c_uint32), ("largest_component", C.c_uint32), ("ms_kernels", C.c_double), ("ms_wall", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class FeaturesTotals(C.Structure):
@@ -459,6 +471,14 @@ def load_library():
     L.r3dm_multi_filter_H.argtypes = [vp, vp, C.c_double, u32, u64, C.POINTER(vp), vp]
     L.r3dm_multi_filter_E.argtypes = [vp, vp, C.c_double, u32, u64, u32, C.c_float, C.POINTER(vp), vp]
     L.r3dm_shard_pairs.argtypes = [vp, u64, u32, vp]
+    L.r3dm_build_tracks.argtypes = [vp, vp, u32, C.POINTER(vp), vp]
+    L.r3dm_tracks_count.argtypes = [vp]; L.r3dm_tracks_count.restype = u64
+    L.r3dm_tracks_offsets.argtypes = [vp]; L.r3dm_tracks_offsets.restype = vp
+    L.r3dm_tracks_observations.argtypes = [vp]; L.r3dm_tracks_observations.restype = vp
+    L.r3dm_tracks_report.argtypes = [vp, C.POINTER(TracksStats)]
+    L.r3dm_tracks_phase_ms.argtypes = [vp, vp]
+    L.r3dm_tracks_in_pair.argtypes = [vp, u32, u32, vp, u64, C.POINTER(u64)]
+    L.r3dm_tracks_free.argtypes = [vp]; L.r3dm_tracks_free.restype = None
     _lib = L
     return L
 
@@ -577,6 +597,78 @@ class Graph:
         if rc != 0:
             raise R3dmError(f"r3dm_graph_merge -> {rc}")
         return Graph(h.value)
+
+
+class Tracks:
+    """Feature tracks of a match graph (r3dm_build_tracks): track t is observations[offsets[t]:offsets[t + 1]], rows (view id, feature)
+    sorted by view id; tracks are sorted by their first observation."""
+
+    def __init__(self, handle: int):
+        self._h = handle
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().r3dm_tracks_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # interpreter shutdown
+            pass
+
+    def _handle(self) -> int:
+        if not getattr(self, "_h", None):
+            raise R3dmError("the Tracks object is closed")
+        return self._h
+
+    def __len__(self) -> int:
+        return int(load_library().r3dm_tracks_count(self._handle()))
+
+    @property
+    def offsets(self) -> np.ndarray:
+        n = len(self) + 1
+        buf = (C.c_char * (8 * n)).from_address(load_library().r3dm_tracks_offsets(self._h))
+        return np.frombuffer(buf, dtype=np.uint64).copy()
+
+    @property
+    def observations(self) -> np.ndarray:
+        n = int(self.offsets[-1])
+        if n == 0:
+            return np.zeros((0, 2), np.uint32)
+        buf = (C.c_char * (8 * n)).from_address(load_library().r3dm_tracks_observations(self._h))
+        return np.frombuffer(buf, dtype=np.uint32).copy().reshape(-1, 2)
+
+    @property
+    def stats(self) -> TracksStats:
+        s = TracksStats()
+        rc = load_library().r3dm_tracks_report(self._handle(), C.byref(s))
+        if rc != 0:
+            raise R3dmError(f"r3dm_tracks_report -> {rc}")
+        return s
+
+    @property
+    def phase_ms(self) -> np.ndarray:
+        """r3dm_tracks_phase_ms: stats.ms_kernels split into [extents, components, sort + filter, outputs]"""
+        out = np.zeros(4, np.float64)
+        rc = load_library().r3dm_tracks_phase_ms(self._handle(), _ptr(out))
+        if rc != 0:
+            raise R3dmError(f"r3dm_tracks_phase_ms -> {rc}")
+        return out
+
+    def in_pair(self, view_a: int, view_b: int) -> np.ndarray:
+        """GetTracksInImages({a, b}): [n, 2] (feature in a, feature in b) of every track that observes both views, in track order"""
+        L = load_library()
+        n = C.c_uint64()
+        rc = L.r3dm_tracks_in_pair(self._handle(), view_a, view_b, None, 0, C.byref(n))
+        if rc != 0:
+            raise R3dmError(f"r3dm_tracks_in_pair({view_a}, {view_b}) -> {rc}")
+        out = np.zeros((n.value, 2), np.uint32)
+        if n.value:
+            rc = L.r3dm_tracks_in_pair(self._h, view_a, view_b, _ptr(out), n.value, C.byref(n))
+            if rc != 0:
+                raise R3dmError(f"r3dm_tracks_in_pair({view_a}, {view_b}) -> {rc}")
+        return out
 
 
 def graphs_pack(graphs: Sequence["Graph"]) -> np.ndarray:
@@ -987,6 +1079,13 @@ class Context:
     def set_device_graphs(self, enable: bool = True):
         """r3dm_set_device_graphs: graphs produced from now on keep a device mirror (sent by Comm.allgather_graphs without a host round trip)"""
         self._check(self._L.r3dm_set_device_graphs(self._h, int(bool(enable))), "r3dm_set_device_graphs")
+
+    def build_tracks(self, graph: Graph, min_length: int = 2, want_graph: bool = False):
+        """r3dm_build_tracks: the tracks of `graph` (TracksBuilder Build + Filter); with want_graph also the graph restricted to the
+        matches whose component is a track"""
+        h = C.c_void_p(); k = C.c_void_p()
+        self._check(self._L.r3dm_build_tracks(self._h, graph._h, min_length, C.byref(h), C.byref(k) if want_graph else None), "r3dm_build_tracks")
+        return (Tracks(h.value), Graph(k.value)) if want_graph else Tracks(h.value)
 
     def set_integer_mfma(self, enable: bool = True):
         """opt-in bf16-exact MFMA path for integer-valued descriptors (include/r3dm.h: r3dm_set_integer_mfma)"""

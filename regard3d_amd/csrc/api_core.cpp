@@ -48,6 +48,7 @@ extern "C" void r3dm_destroy(r3dm_ctx* c)
                       &c->a_jobs, &c->h_aux, &c->h_jobs, &c->a_scratch, &c->a_ids, &c->d_spill, &c->d_fb2, &c->g_segs, &c->d_verdict};
     for (FilterBufs& fb : c->fb) fb.release();
     c->gb.release();
+    c->tb.release();
     c->coop_sched.release();
     c->d_mutual.release();
     for (DevBuf* b : {&c->pre_rows, &c->pre_heads, &c->pre_pairs, &c->pre_counts}) b->release();

@@ -301,6 +301,38 @@ void R3DComputeMatches::setMutualMatching(bool on)
     if (multi_) (void)r3dm_multi_set_mutual_matching(multi_, on ? 1 : 0);
 }
 
+// TracksBuilder::Build(map_Matches) + Filter(min_length) + ExportToSTL (and, with `kept`, the filter applied to the map itself): the
+// map becomes a graph (r3dm_graph_from_csr: map order is graph order), r3dm_build_tracks runs on the first device
+bool R3DComputeMatches::buildTracks(const PairWiseMatches& matches, uint32_t min_length, Tracks* out, PairWiseMatches* kept)
+{
+    r3dm_ctx* c = ctx_ ? ctx_ : (multi_ ? r3dm_multi_ctx(multi_, 0) : nullptr);
+    if (!c) { errorMessage_ = "buildTracks: no GPU context"; return false; }
+    if (!out) { errorMessage_ = "buildTracks: no output"; return false; }
+    std::vector<uint32_t> pairs;
+    std::vector<uint64_t> offsets{0};
+    std::vector<r3dm_match> flat;
+    for (const auto& e : matches) {
+        pairs.push_back(e.first.first); pairs.push_back(e.first.second);
+        flat.insert(flat.end(), e.second.begin(), e.second.end());
+        offsets.push_back(flat.size());
+    }
+    r3dm_graph* g = nullptr;
+    r3dm_tracks* t = nullptr;
+    r3dm_graph* kg = nullptr;
+    int rc = r3dm_graph_from_csr(pairs.data(), pairs.size() / 2, offsets.data(), flat.data(), &g);
+    if (rc != R3DM_OK) { errorMessage_ = "buildTracks: r3dm_graph_from_csr failed (" + std::to_string(rc) + ")"; return false; }
+    rc = r3dm_build_tracks(c, g, min_length, &t, kept ? &kg : nullptr);
+    r3dm_graph_free(g);
+    if (rc != R3DM_OK) { errorMessage_ = std::string("buildTracks: ") + r3dm_last_error(c); return false; }
+    const uint64_t n = r3dm_tracks_count(t);
+    out->offsets.assign(r3dm_tracks_offsets(t), r3dm_tracks_offsets(t) + n + 1);
+    out->observations.assign(r3dm_tracks_observations(t), r3dm_tracks_observations(t) + out->offsets.back());
+    (void)r3dm_tracks_report(t, &out->stats);
+    r3dm_tracks_free(t);
+    if (kept) { graph_to_map(kg, *kept); r3dm_graph_free(kg); }
+    return true;
+}
+
 void R3DComputeMatches::setPreemptiveMatching(bool on, uint32_t head_rows, uint32_t min_matches)
 {
     int rc = R3DM_OK;

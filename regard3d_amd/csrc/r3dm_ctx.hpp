@@ -8,6 +8,7 @@
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
 //   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules
 //   api_filter.cpp    AC-RANSAC geometric filters (F, E, H)
+//   api_tracks.cpp    feature tracks of a match graph (r3dm_build_tracks), the track filter applied to the graph, r3dm_tracks_in_pair
 //   api_akaze.cpp     the frame of both detector arms (checks, upload, INTER_AREA tables, statistics tail, DetectedBatch's writer) and the
 //                     Fast-A-KAZE arm: its pass in phases, MLDB, r3dm_detect_akaze / _mldb / _batch, r3dm_gray_from_bgr8
 //   api_akaze_classic.cpp   the classic A-KAZE arm's launch sequence on that frame, r3dm_detect_akaze_classic / _batch
@@ -370,6 +371,21 @@ struct GuidedBufs {
         pin_out.release(); pin_small.release(); pin_blk.release();
     }
 };
+// Feature tracks (kernels_tracks.hip, api_tracks.cpp): the work buffers of r3dm_build_tracks, made by the first call, grown on demand
+struct TracksBufs {
+    DevBuf matches, offsets, pair_rank, view_ids, base, smax, par, slots, ma, rel, keep, pair_kept, nodes, keys, skey, sval, nodeflag,
+           oslots, obs, hflag, toff, kept_rel, ctr, temp;
+    PinBuf pin;
+    hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // four timed phases
+    void release()
+    {
+        DevBuf* b[] = {&matches, &offsets, &pair_rank, &view_ids, &base, &smax, &par, &slots, &ma, &rel, &keep, &pair_kept, &nodes, &keys, &skey,
+                       &sval, &nodeflag, &oslots, &obs, &hflag, &toff, &kept_rel, &ctr, &temp};
+        for (DevBuf* x : b) x->release();
+        pin.release();
+        for (hipEvent_t& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
+    }
+};
 struct GuidedResult {
     std::vector<uint32_t> cnt;             // matches of every job
     const r3dm_match* host = nullptr;      // job k's list at host + jobs[k].q0 (page-locked, valid until the next guided call)
@@ -564,6 +580,7 @@ struct r3dm_ctx {
     double guided_ratio[3] = {0.6, 0.6, -1.0};
     GuidedBufs gb;
     r3dm_guided_stats guided_stats{};                        // last guided step (r3dm_guided_report)
+    TracksBufs tb;                                           // r3dm_build_tracks: nothing in it until the first call
 };
 
 int graph_dev_append(r3dm_ctx* c, r3dm_graph* g, const std::vector<uint32_t>& pair_ids, const std::vector<uint32_t>& counts, std::vector<GraphSeg>& segs,

@@ -515,6 +515,48 @@ hipError_t launch_liop_extract(hipStream_t st, const float* image, int w, int h,
 struct GraphSeg { uint64_t src, idx, dst; uint32_t cnt, pad; };
 hipError_t launch_graph_gather(hipStream_t st, const r3dm_match* src, const uint32_t* idx, const GraphSeg* segs, uint32_t n_segs, r3dm_match* dst);
 
+// ---- feature tracks (kernels_tracks.hip, api_tracks.cpp; r3dm_build_tracks).  A node (view, feature) is the
+// slot base[rank of the view] + feature; all per-slot arrays hold N = base[V] entries, all per-match arrays M
+struct TrkParams {
+    const r3dm_match* matches;    // [M] the graph's matches, graph order
+    const uint64_t* offsets;      // [P + 1]
+    const uint32_t* pair_rank;    // [2 P] ranks of the two views of every pair
+    uint32_t P, V, N, min_length;
+    uint64_t M;
+    const uint32_t* view_ids;     // [V] ascending
+    const uint32_t* base;         // [V + 1] first slot of every view
+    uint32_t* smax;               // [V] largest feature index (zeroed by the host)
+    uint32_t* par;                // [N] union-find parent; after flatten the root (a component's smallest slot) of every touched slot
+    uint32_t* csz;                // [N] nodes of the component, at its root (zeroed)
+    uint8_t* touched;             // [N] the slot is a node of the graph (zeroed)
+    uint8_t* conf;                // [N] at a root: two nodes of one view (zeroed)
+    uint8_t* surv;                // [N] at a root: the component is a track
+    uint32_t* ma;                 // [M] slot of the match's first node
+    uint32_t* rel;                // [M] position of the match in its pair's list
+    uint8_t* keep;                // [M] the match's component is a track
+    uint32_t* pair_kept;          // [P] such matches of every pair (zeroed)
+    uint32_t* nodes;              // [n_nodes] the touched slots, ascending
+    uint32_t* keys;               // [n_nodes] their roots
+    uint32_t* skey; uint32_t* sval;   // [n_nodes] (root, slot) sorted by root, stable: components in root order, members ascending
+    uint8_t* nodeflag;            // [n_nodes] the sorted node is an observation
+    uint64_t n_nodes, n_obs;
+    uint32_t* oslots;             // [n_obs] slots of the observations in output order
+    r3dm_observation* obs;        // [n_obs]
+    uint8_t* hflag;               // [n_obs] first observation of its track
+    unsigned long long* ctr;      // [8] counters (kernels_tracks.hip: trk_classify_kernel), zeroed
+};
+enum class TrkStep { kExtent, kInit, kLink, kFlatten, kKeys, kMark, kClassify, kEmit, kKeep };
+hipError_t launch_tracks(hipStream_t st, const TrkParams& T, TrkStep step);
+// order-preserving selection and stable radix sort (kernels_tracks.hip).  scratch: tracks_scratch_words(n, sort) words
+size_t tracks_scratch_words(uint64_t n, bool sort);
+// out = the positions i < n with flags[i] != 0, ascending (vals == nullptr), or vals[i] of those positions; *count = how many
+hipError_t tracks_select(hipStream_t st, uint32_t* scratch, const uint8_t* flags, uint64_t n, const uint32_t* vals, uint32_t* out, unsigned long long* count);
+hipError_t tracks_select64(hipStream_t st, uint32_t* scratch, const uint8_t* flags, uint64_t n, uint64_t* out, unsigned long long* count);
+// (keys, vals) sorted by the low `bits` bits of the keys, stable; both pairs of arrays are work space; *in_second: the result is in
+// (keys2, vals2), else in (keys, vals)
+hipError_t tracks_sort_by_root(hipStream_t st, uint32_t* scratch, uint32_t* keys, uint32_t* vals, uint32_t* keys2, uint32_t* vals2, uint64_t n,
+                               uint32_t bits, bool* in_second);
+
 // guided matching (kernels_guided.hip; OpenMVG's geometry_aware::GuidedMatching): one job per pair, the queries are the rows of I
 struct GuidedJob {
     double M[9];               // kind 0: F (for E: K_J^-T E K_I^-1), kind 1: H (x_J ~ H x_I)
