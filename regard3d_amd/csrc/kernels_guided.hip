@@ -258,7 +258,6 @@ __global__ __launch_bounds__(256)
 void guided_compact_kernel(const GuidedParams P)
 {
     __shared__ uint32_t wave_cnt[4];
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     for (uint32_t k = blockIdx.x; k < P.n_jobs; k += gridDim.x) {
         const GuidedJob& G = P.jobs[k];
         const ImgDev* __restrict__ Iv = P.imgs + G.sI;
@@ -279,14 +278,9 @@ void guided_compact_kernel(const GuidedParams P)
                     if (je != kNone && cI[e] == ci && cJ[je] == cj) keep = false;
                 }
             }
-            const unsigned long long bal = __ballot(keep);
-            const uint32_t before = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(bal);
-            r3dm_syncthreads();
-            uint32_t woff = 0, tot = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < 4; ++w) { const uint32_t cw = wave_cnt[w]; if (w < wave) woff += cw; tot += cw; }
-            if (keep) { r3dm_match mt; mt.i = i; mt.j = j; P.out[(size_t)G.q0 + m + woff + before] = mt; }
+            uint32_t tot;
+            const uint32_t rank = wg_compact_rank(keep, wave_cnt, tot);
+            if (keep) { r3dm_match mt; mt.i = i; mt.j = j; P.out[(size_t)G.q0 + m + rank] = mt; }
             m += tot;
             r3dm_syncthreads();
         }

@@ -1,8 +1,14 @@
 // kernels_match_common.hpp -- device helpers shared by the matching kernels (kernels_match.hip: f32 tiles; kernels_match_16bit.hip:
-// bf16 / f16 nominators; kernels_match_hamming.hip: binary descriptors; kernels_match_exact.hip: exact scans + finalisation):
-// the reference metric, the (best, runner-up, bound) lists, the buffer load of a fragment, and the shared tail of every L2 kernel
-// (merge the lane halves, re-score in the reference arithmetic, certify, ratio test).  On top of it: kernels_match_knn_lists.hpp (the
-// K-lists and their tail) and kernels_match_tiles.hpp (the tile steps of the MFMA nominators, for either kind of list).
+// bf16 / f16 nominators; kernels_match_hamming.hip: binary descriptors; kernels_match_exact.hip: exact scans + finalisation;
+// kernels_match_mutual.hip, kernels_match_head.hip, kernels_match_knn.hip, kernels_guided.hip: the other scans of every row):
+// the reference metric, the (best, runner-up, bound) lists, the buffer load of a fragment, the steps of the exact-scan kernels
+//   lex_less, lex_push, top2_lex_merge    the order (distance, row); (best, runner-up) lists kept and merged under it
+//   stage_l2sq<D4>                        exact_l2sq's summation order against a row of a fragment-order LDS stage
+//   ham_key, ham_key_row, ham_key_dist    the packed key distance << 22 | row of binary rows and its 22-bit row limit
+//   wg_compact_rank                       one round of a 256-thread compaction: rank and total through wave_cnt[4], one barrier
+// and the shared tail of every L2 tile kernel (merge the lane halves, re-score in the reference arithmetic, certify, ratio test).
+// On top of it: kernels_match_knn_lists.hpp (the K-lists and their tail) and kernels_match_tiles.hpp (the tile steps of the MFMA
+// nominators, for either kind of list).  The run-time value -> template argument dispatchers of the launchers are in r3dm_internal.hpp.
 //
 // Arithmetic contract (OpenMVG L2<float>; /root/reference/src/R3DComputeMatches.cpp:437-489): distances are the f32
 // 4-way-unrolled sum of squared differences, NO fused multiply-add; equal distances -> lowest dataset row.  Every translation unit
@@ -93,20 +99,94 @@ __device__ __forceinline__ f32x4 bload16(__amdgpu_buffer_rsrc_t rsrc, uint32_t v
     return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0));
 }
 
-// ---- per query: merge the two lane halves, re-score exactly, certify, ratio-test (tail of both L2 kernels).
-// dpad = padded descriptor length, bf16_tiles = the keys come from the integer fast path
+// ------------------------------------------------------------------------------------------------
+// The steps the exact-scan kernels share (the exact 2-NN and k-NN scans, the mutual check, the head gate, guided matching, the
+// finalisation).  Each carries one rule that makes a result bit-identical to the reference; a kernel that needs the rule calls the step.
+// ------------------------------------------------------------------------------------------------
+// THE ORDER: (distance, dataset row), the oracle's tie rule -- equal distances -> lowest row.  An empty entry (+inf, kNone) is last.
+__device__ __forceinline__ bool lex_less(float da, uint32_t ia, float db, uint32_t ib)
+{
+    return da < db || (da == db && ia < ib);
+}
+
+// push into a (best, runner-up) list kept under that order (Top2::d2 is not used)
 __device__ __forceinline__ void lex_push(Top2& s, float key, uint32_t idx)
 {
     const float od0 = s.d0, od1 = s.d1;
     const uint32_t oi0 = s.i0, oi1 = s.i1;
-    const bool c0 = key < od0 || (key == od0 && idx < oi0);
-    const bool c1 = key < od1 || (key == od1 && idx < oi1);
+    const bool c0 = lex_less(key, idx, od0, oi0);
+    const bool c1 = lex_less(key, idx, od1, oi1);
     s.d1 = c0 ? od0 : (c1 ? key : od1);
     s.i1 = c0 ? oi0 : (c1 ? idx : oi1);
     s.d0 = c0 ? key : od0;
     s.i0 = c0 ? idx : oi0;
 }
 
+// THE MERGE of the (best, runner-up) of a second list of rows into a first under the order: what a scan over the union of both row
+// sets would hold.  Both lists are sorted and hold distinct rows (or empty entries).
+__device__ __forceinline__ void top2_lex_merge(Top2& s, float bd0, uint32_t bi0, float bd1, uint32_t bi1)
+{
+    lex_push(s, bd0, bi0);
+    lex_push(s, bd1, bi1);
+}
+
+// THE L2 STEP against an LDS stage in fragment order (ImgDev::tiled: float4 chunk k of row r is stage[k * 32 + r]): the distance
+// between a row held in registers (v: float4 chunks) and row r of the stage, over d4 = dim / 4 chunks.  The callers' launch
+// conditions guarantee dim % 4 == 0: there is no tail here.  One written-out copy of this summation order remains, the only one
+// with the scalar tail: l2_head_match_kernel's loop over its row-major stage (kernels_match_head.hip says why).
+// Equal to exact_l2sq(row, v, dim) bit for bit: every chunk adds ((e0^2 + e1^2) + e2^2) + e3^2 to the running float in ascending k,
+// and -ffp-contract=off keeps the compiler from fusing any of it.  Which operand is subtracted from which does not matter: a - b and
+// b - a are exact negatives of each other in IEEE arithmetic, so their squares are the same float.
+template <int D4>
+__device__ __forceinline__ float stage_l2sq(const f32x4 (&v)[D4], const f32x4* stage, uint32_t r, uint32_t d4)
+{
+    float result = 0.0f;
+#pragma unroll
+    for (int k = 0; k < D4; ++k) {
+        if (k < (int)d4) {
+            const f32x4 a = stage[k * 32 + r];
+            const float e0 = a[0] - v[k][0], e1 = a[1] - v[k][1], e2 = a[2] - v[k][2], e3 = a[3] - v[k][3];
+            result += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
+        }
+    }
+    return result;
+}
+
+// THE PACKED KEY of binary rows: distance << 22 | row.  A view has fewer than 2^22 rows (check_view in api_core.cpp refuses more; so
+// do the index and k-NN entry points in api_match.cpp) and a distance is at most 512 bits, so the key fits 32 bits and the UNSIGNED
+// order of the keys IS the order (distance, row): min / med3 on keys keep exact lists.  0xFFFFFFFF is the empty entry.
+constexpr uint32_t kHamRowBits = 22;
+__device__ __forceinline__ uint32_t ham_key(uint32_t dist, uint32_t row) { return (dist << kHamRowBits) | row; }
+__device__ __forceinline__ uint32_t ham_key_row(uint32_t key) { return key & ((1u << kHamRowBits) - 1u); }
+__device__ __forceinline__ uint32_t ham_key_dist(uint32_t key) { return key >> kHamRowBits; }
+
+// THE COMPACTION ROUND of a 256-thread workgroup (4 waves): every thread brings a `keep` flag; returns the thread's rank among the
+// kept threads of the workgroup (thread order) and their number in `total`, through wave_cnt[4] in LDS.  The round contains ONE
+// barrier, between the waves' counts and their sum.  The caller puts a second barrier between two rounds (after the writes that use
+// the rank): the next round's counts overwrite wave_cnt.  `before_barrier` runs between this wave's count and the barrier: the
+// fence of a caller whose kept elements live in global memory (finalize_body).
+template <class BeforeBarrier>
+__device__ __forceinline__ uint32_t wg_compact_rank(bool keep, uint32_t* wave_cnt, uint32_t& total, BeforeBarrier&& before_barrier)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(keep);
+    const uint32_t before = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(bal);
+    before_barrier();
+    r3dm_syncthreads();
+    uint32_t woff = 0, tot = 0;
+#pragma unroll
+    for (uint32_t w = 0; w < 4; ++w) { const uint32_t cw = wave_cnt[w]; if (w < wave) woff += cw; tot += cw; }
+    total = tot;
+    return woff + before;
+}
+__device__ __forceinline__ uint32_t wg_compact_rank(bool keep, uint32_t* wave_cnt, uint32_t& total)
+{
+    return wg_compact_rank(keep, wave_cnt, total, [] {});
+}
+
+// ---- per query: merge the two lane halves, re-score exactly, certify, ratio-test (tail of both L2 kernels).
+// dpad = padded descriptor length, bf16_tiles = the keys come from the integer fast path
 // LEX: the lists are exact lexicographic (distance, index) top-2 lists without a bound (l2_knn2_int_kernel)
 // SPLIT: the keys come from the split-f16 nominator (l2_knn2_split_kernel) in units of key_inv^-1; a query whose merged
 //        top-2 cannot be certified gets a second chance with all four nominees of its two lane halves before it is sent to

@@ -1,7 +1,8 @@
 // kernels_match_exact.hip -- what stands behind the tile kernels: the exact scans in the reference's arithmetic for the (rare) queries
 // whose top-2 a tile kernel could not certify, and the per-pair finalisation (compaction of the accepted queries, (i_, j_) ordering,
 // coordinate de-duplication -- OpenMVG's IndMatchDecorator as restated in SURVEY.md A.4;
-// /root/reference/src/R3DComputeMatches.cpp:479-487).
+// /root/reference/src/R3DComputeMatches.cpp:479-487).  The order, the merges of (best, runner-up) lists, the distance against an LDS
+// stage and the compaction round are the shared steps of kernels_match_common.hpp.
 #include "kernels_match_common.hpp"
 
 namespace r3dm {
@@ -11,11 +12,6 @@ namespace r3dm {
 // Used for un-certified queries (rare), descriptor lengths without a tensor kernel, and as the
 // independent on-device cross-check of the MFMA path.  One workgroup per item.
 // ------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool lex_less(float da, uint32_t ia, float db, uint32_t ib)
-{
-    return da < db || (da == db && ia < ib);
-}
-
 __global__ __launch_bounds__(256)
 void l2_exact_items_kernel(const MatchParams P, uint32_t count, int scan_all)
 {
@@ -41,19 +37,10 @@ void l2_exact_items_kernel(const MatchParams P, uint32_t count, int scan_all)
         r3dm_syncthreads();
         for (uint32_t s = 128; s > 0; s >>= 1) {
             if (threadIdx.x < s) {
-                // merge two sorted pairs under the (distance, index) order
-                float a0 = sd0[threadIdx.x], a1 = sd1[threadIdx.x]; uint32_t x0 = si0[threadIdx.x], x1 = si1[threadIdx.x];
-                const float b0 = sd0[threadIdx.x + s], b1 = sd1[threadIdx.x + s];
-                const uint32_t y0 = si0[threadIdx.x + s], y1 = si1[threadIdx.x + s];
-                float r0, r1; uint32_t j0, j1;
-                if (lex_less(b0, y0, a0, x0)) {
-                    r0 = b0; j0 = y0;
-                    if (lex_less(b1, y1, a0, x0)) { r1 = b1; j1 = y1; } else { r1 = a0; j1 = x0; }
-                } else {
-                    r0 = a0; j0 = x0;
-                    if (lex_less(b0, y0, a1, x1)) { r1 = b0; j1 = y0; } else { r1 = a1; j1 = x1; }
-                }
-                sd0[threadIdx.x] = r0; sd1[threadIdx.x] = r1; si0[threadIdx.x] = j0; si1[threadIdx.x] = j1;
+                Top2 m;
+                m.d0 = sd0[threadIdx.x]; m.d1 = sd1[threadIdx.x]; m.i0 = si0[threadIdx.x]; m.i1 = si1[threadIdx.x];
+                top2_lex_merge(m, sd0[threadIdx.x + s], si0[threadIdx.x + s], sd1[threadIdx.x + s], si1[threadIdx.x + s]);
+                sd0[threadIdx.x] = m.d0; sd1[threadIdx.x] = m.d1; si0[threadIdx.x] = m.i0; si1[threadIdx.x] = m.i1;
             }
             r3dm_syncthreads();
         }
@@ -124,46 +111,27 @@ void l2_exact_batch_kernel(const MatchParams P)
             for (uint32_t rr = 0; rr < 8; ++rr) {
                 const uint32_t r = wave * 8 + rr;
                 if (r >= rows_here) break;                         // wave-uniform
-                float result = 0.0f;
-#pragma unroll
-                for (int k = 0; k < D4; ++k) {
-                    if (k < (int)d4) {
-                        const f32x4 a = tile[k * 32 + r];
-                        const float e0 = a[0] - qv[k][0], e1 = a[1] - qv[k][1], e2 = a[2] - qv[k][2], e3 = a[3] - qv[k][3];
-                        result += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-                    }
-                }
+                const float result = stage_l2sq<D4>(qv, tile, r, d4);
                 const uint32_t row = t0 + r;
                 if (result < d0) { d1 = d0; i1 = i0; d0 = result; i0 = row; }
                 else if (result < d1) { d1 = result; i1 = row; }
             }
         }
-        // merge the four waves' (best, runner-up) per lane under the (distance, row) order
+        // merge the four waves' (best, runner-up) per lane
         r3dm_syncthreads();
         md0[threadIdx.x] = d0; md1[threadIdx.x] = d1; mi0[threadIdx.x] = i0; mi1[threadIdx.x] = i1;
         r3dm_syncthreads();
         if (wave == 0 && active) {
-            float a0 = md0[lane], a1 = md1[lane]; uint32_t x0 = mi0[lane], x1 = mi1[lane];
-            for (uint32_t w = 1; w < 4; ++w) {
-                const float b0_ = md0[w * 64 + lane], b1_ = md1[w * 64 + lane];
-                const uint32_t y0 = mi0[w * 64 + lane], y1 = mi1[w * 64 + lane];
-                float r0, r1; uint32_t j0, j1;
-                if (lex_less(b0_, y0, a0, x0)) {
-                    r0 = b0_; j0 = y0;
-                    if (lex_less(b1_, y1, a0, x0)) { r1 = b1_; j1 = y1; } else { r1 = a0; j1 = x0; }
-                } else {
-                    r0 = a0; j0 = x0;
-                    if (lex_less(b0_, y0, a1, x1)) { r1 = b0_; j1 = y0; } else { r1 = a1; j1 = x1; }
-                }
-                a0 = r0; a1 = r1; x0 = j0; x1 = j1;
-            }
-            if (S > 1) P.fb_part[((size_t)pair * kFbPerPair + b0 + lane) * S + slice] = make_float4(a0, __uint_as_float(x0), a1, __uint_as_float(x1));
+            Top2 m;
+            m.d0 = md0[lane]; m.d1 = md1[lane]; m.i0 = mi0[lane]; m.i1 = mi1[lane];
+            for (uint32_t w = 1; w < 4; ++w) top2_lex_merge(m, md0[w * 64 + lane], mi0[w * 64 + lane], md1[w * 64 + lane], mi1[w * 64 + lane]);
+            if (S > 1) P.fb_part[((size_t)pair * kFbPerPair + b0 + lane) * S + slice] = make_float4(m.d0, __uint_as_float(m.i0), m.d1, __uint_as_float(m.i1));
             else if (nI < 2) emit_result(P, pair, q, R3DM_INF, kNone, R3DM_INF, kNone);
-            else emit_result(P, pair, q, a0, x0, a1, x1);
+            else emit_result(P, pair, q, m.d0, m.i0, m.d1, m.i1);
         }
     }
     if (S > 1) {
-        // the last slice of the pair to get here merges the S partial (best, runner-up) of every query under the (distance, row) order
+        // the last slice of the pair to get here merges the S partial (best, runner-up) of every query
         __threadfence();
         r3dm_syncthreads();
         if (threadIdx.x == 0) s_ticket = atomicAdd(&P.fb_done[pair], 1u);
@@ -174,23 +142,14 @@ void l2_exact_batch_kernel(const MatchParams P)
             const uint32_t q = P.fb_q[(size_t)pair * kFbPerPair + k];
             const float4* part = P.fb_part + ((size_t)pair * kFbPerPair + k) * S;
             float4 v = part[0];
-            float a0 = v.x, a1 = v.z; uint32_t x0 = __float_as_uint(v.y), x1 = __float_as_uint(v.w);
+            Top2 m;
+            m.d0 = v.x; m.i0 = __float_as_uint(v.y); m.d1 = v.z; m.i1 = __float_as_uint(v.w);
             for (uint32_t w = 1; w < S; ++w) {
                 v = part[w];
-                const float b0_ = v.x, b1_ = v.z;
-                const uint32_t y0 = __float_as_uint(v.y), y1 = __float_as_uint(v.w);
-                float r0, r1; uint32_t j0, j1;
-                if (lex_less(b0_, y0, a0, x0)) {
-                    r0 = b0_; j0 = y0;
-                    if (lex_less(b1_, y1, a0, x0)) { r1 = b1_; j1 = y1; } else { r1 = a0; j1 = x0; }
-                } else {
-                    r0 = a0; j0 = x0;
-                    if (lex_less(b0_, y0, a1, x1)) { r1 = b0_; j1 = y0; } else { r1 = a1; j1 = x1; }
-                }
-                a0 = r0; a1 = r1; x0 = j0; x1 = j1;
+                top2_lex_merge(m, v.x, __float_as_uint(v.y), v.z, __float_as_uint(v.w));
             }
             if (nI < 2) emit_result(P, pair, q, R3DM_INF, kNone, R3DM_INF, kNone);
-            else emit_result(P, pair, q, a0, x0, a1, x1);
+            else emit_result(P, pair, q, m.d0, m.i0, m.d1, m.i1);
         }
     }
 }
@@ -200,14 +159,10 @@ hipError_t launch_l2_exact_batch(hipStream_t st, const MatchParams& P, uint32_t 
     if (P.n_pairs == 0) return hipSuccess;
     if (P.n_pairs > kMaxBlocksOf256 || P.fb_slices < 1 || P.fb_slices > 64 || (uint64_t)P.n_pairs * P.fb_slices > kMaxBlocksOf256) return hipErrorInvalidValue;
     const dim3 grid(P.n_pairs, P.fb_slices);
-    switch (G) {
-        case 8:  hipLaunchKernelGGL((l2_exact_batch_kernel<8>), grid, dim3(256), 0, st, P); break;
-        case 16: hipLaunchKernelGGL((l2_exact_batch_kernel<16>), grid, dim3(256), 0, st, P); break;
-        case 18: hipLaunchKernelGGL((l2_exact_batch_kernel<18>), grid, dim3(256), 0, st, P); break;
-        case 32: hipLaunchKernelGGL((l2_exact_batch_kernel<32>), grid, dim3(256), 0, st, P); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_g(G, [&](auto g) {
+        hipLaunchKernelGGL((l2_exact_batch_kernel<decltype(g)::value>), grid, dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -241,7 +196,6 @@ __device__ __forceinline__ void finalize_body(const FinalizeParams& P, KeyT keys
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
     const uint32_t nJ = Jp->n;
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     const uint32_t* src = P.nn_idx + (size_t)pair * P.q_stride;
 
     uint32_t m = 0;                                  // block-uniform running count
@@ -249,14 +203,9 @@ __device__ __forceinline__ void finalize_body(const FinalizeParams& P, KeyT keys
         const uint32_t q = base + threadIdx.x;
         const uint32_t v = (q < nJ) ? src[q] : kNone;
         const bool keep = (v < kFallback);
-        const unsigned long long bal = __ballot(keep);
-        const uint32_t before = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
-        if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(bal);
-        r3dm_syncthreads();
-        uint32_t woff = 0, tot = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < 4; ++w) { const uint32_t cw = wave_cnt[w]; if (w < wave) woff += cw; tot += cw; }
-        if (keep) keys[m + woff + before] = ((unsigned long long)v << 32) | q;
+        uint32_t tot;
+        const uint32_t rank = wg_compact_rank(keep, wave_cnt, tot);
+        if (keep) keys[m + rank] = ((unsigned long long)v << 32) | q;
         m += tot;
         r3dm_syncthreads();
     }
@@ -307,15 +256,9 @@ __device__ __forceinline__ void finalize_body(const FinalizeParams& P, KeyT keys
                 const uint32_t k = base + threadIdx.x;
                 const bool keep = (k < m) && !drop[k];
                 const unsigned long long kk = (k < m) ? keys[k] : 0ull;
-                const unsigned long long bal = __ballot(keep);
-                const uint32_t before = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
-                if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(bal);
-                if (GLOBAL_BUFFERS) fin_fence();
-                r3dm_syncthreads();
-                uint32_t woff = 0, tot = 0;
-#pragma unroll
-                for (uint32_t q = 0; q < 4; ++q) { const uint32_t cw = wave_cnt[q]; if (q < wave) woff += cw; tot += cw; }
-                if (keep) keys[w + woff + before] = kk;
+                uint32_t tot;
+                const uint32_t rank = wg_compact_rank(keep, wave_cnt, tot, [] { if (GLOBAL_BUFFERS) fin_fence(); });
+                if (keep) keys[w + rank] = kk;
                 w += tot;
                 if (GLOBAL_BUFFERS) fin_fence();
                 r3dm_syncthreads();

@@ -491,7 +491,8 @@ hipError_t launch_l2_int_lds_variant(hipStream_t st, const MatchParams& P, uint3
 // Hamming 2-NN (binary descriptors, e.g. 486-bit A-KAZE MLDB stored in 16 words): integer VALU only.
 // Each lane owns QL query rows in registers; dataset rows arrive wave-uniformly through the scalar
 // cache (s_load), so a row costs W x (v_xor + v_bcnt-accumulate) per query and no LDS/vector memory.
-// The running top-2 is kept on packed keys (distance << 22 | row): unsigned min / med3 then break
+// The running top-2 is kept on packed keys (distance << 22 | row, written out: through ham_key of kernels_match_common.hpp this
+// kernel's machine code changes, and that code is what BASELINE config C3 was measured with): unsigned min / med3 then break
 // ties towards the lowest row, exactly the oracle's rule.
 // ------------------------------------------------------------------------------------------------
 typedef const __attribute__((address_space(4))) uint32_t* cu32p;   // constant address space -> SMEM loads
@@ -566,12 +567,10 @@ hipError_t launch_hamming_knn2(hipStream_t st, const MatchParams& Pin, uint32_t 
     if (grid64 == 0) return hipSuccess;
     if (grid64 > kMaxBlocksOf256) return hipErrorInvalidValue;
     const uint32_t grid = (uint32_t)grid64;
-    switch (words) {
-        case 8:  hipLaunchKernelGGL((hamming_knn2_kernel<8, QL>), dim3(grid), dim3(256), 0, st, P); break;
-        case 16: hipLaunchKernelGGL((hamming_knn2_kernel<16, QL>), dim3(grid), dim3(256), 0, st, P); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_words(words, [&](auto w) {
+        hipLaunchKernelGGL((hamming_knn2_kernel<decltype(w)::value, QL>), dim3(grid), dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace r3dm

@@ -5,7 +5,8 @@
 //
 // The distance is the reference's (exact_l2sq: 4-way unrolled, scalar tail, no FMA; the popcount Hamming distance for binary rows):
 // its summation order decides the count and the count decides which pairs exist, so there is nothing to certify against -- both
-// kernels are VALU work on purpose.
+// kernels are VALU work on purpose.  The L2 loop stays written out against the row-major stage, tail included: through the shared
+// stage_l2sq of kernels_match_common.hpp the gate measured 0.1 - 0.3 % slower on 144-float rows (profiles/scan_steps_perf.txt).
 //
 //   head_gather_l2_kernel       rows out of the fragment-order f32 tiles -> f32 [hn][8 G], row-major (views registered from host
 //                               or device pointers alike: the tiles are what every float / byte view holds)
@@ -180,22 +181,15 @@ hipError_t launch_head_match(hipStream_t st, const HeadMatchParams& P, uint32_t 
     if (n_pairs == 0) return hipSuccess;
     if (n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
     const dim3 grid(n_pairs);
-    if (binary) {
-        switch (G_or_words) {
-            case 8:  hipLaunchKernelGGL((hamming_head_match_kernel<8>), grid, dim3(256), 0, st, P); break;
-            case 16: hipLaunchKernelGGL((hamming_head_match_kernel<16>), grid, dim3(256), 0, st, P); break;
-            default: return hipErrorInvalidValue;
-        }
-    } else {
-        switch (G_or_words) {
-            case 8:  hipLaunchKernelGGL((l2_head_match_kernel<8>), grid, dim3(256), 0, st, P); break;
-            case 16: hipLaunchKernelGGL((l2_head_match_kernel<16>), grid, dim3(256), 0, st, P); break;
-            case 18: hipLaunchKernelGGL((l2_head_match_kernel<18>), grid, dim3(256), 0, st, P); break;
-            case 32: hipLaunchKernelGGL((l2_head_match_kernel<32>), grid, dim3(256), 0, st, P); break;
-            default: return hipErrorInvalidValue;
-        }
-    }
-    return hipGetLastError();
+    if (binary)
+        return dispatch_words(G_or_words, [&](auto w) {
+            hipLaunchKernelGGL((hamming_head_match_kernel<decltype(w)::value>), grid, dim3(256), 0, st, P);
+            return hipGetLastError();
+        });
+    return dispatch_g(G_or_words, [&](auto g) {
+        hipLaunchKernelGGL((l2_head_match_kernel<decltype(g)::value>), grid, dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace r3dm

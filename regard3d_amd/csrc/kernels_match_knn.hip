@@ -155,7 +155,7 @@ void l2_exact_knn_items_kernel(const KnnParams P, uint32_t count, int from_list)
                 for (int j = 0; j < KL; ++j) {                    // pa + pb = j <= KL - 1: both cursors stay inside their lists
                     const float a = sd[pa * 256 + tid], b = sd[pb * 256 + tid + s];
                     const uint32_t x = si[pa * 256 + tid], y = si[pb * 256 + tid + s];
-                    const bool tb = knn_lex_less(b, y, a, x);
+                    const bool tb = lex_less(b, y, a, x);
                     rd[j] = tb ? b : a; ri[j] = tb ? y : x;
                     pa += tb ? 0u : 1u; pb += tb ? 1u : 0u;
                 }
@@ -186,7 +186,7 @@ hipError_t launch_l2_exact_knn_items(hipStream_t st, const KnnParams& P, uint32_
 // ------------------------------------------------------------------------------------------------
 // Hamming k-NN (binary rows of 29..32 / 61..64 bytes in W = 8 / 16 words): the popcount kernel of hamming_knn2_kernel -- each lane
 // owns QL query rows in registers, the dataset rows arrive wave-uniformly through the scalar cache -- with a K-list per query on packed
-// keys (distance << 22 | row): the unsigned order of the keys IS the (distance, row) order, so the lists are exact and there is
+// keys (ham_key): their unsigned order IS the (distance, row) order, so the lists are exact and there is
 // neither a bound nor a certificate.  A lane owns whole queries here (no lane halves to merge).
 // ------------------------------------------------------------------------------------------------
 typedef const __attribute__((address_space(4))) uint32_t* knn_cu32p;   // constant address space -> SMEM loads
@@ -227,7 +227,7 @@ void hamming_knnk_kernel(const KnnParams P)
             uint32_t d = 0;
 #pragma unroll
             for (int w = 0; w < W; ++w) d += (uint32_t)__builtin_popcount(qw[u][w] ^ a[w]);
-            const uint32_t key = (d << 22) | r;
+            const uint32_t key = ham_key(d, r);
             if (__builtin_amdgcn_ballot_w64(key < kl[u][KL - 1]) != 0ull) {
 #pragma unroll
                 for (int j = KL - 1; j >= 1; --j) {               // min(kl[j], max(kl[j - 1], key))  (v_med3_u32)
@@ -245,8 +245,8 @@ void hamming_knnk_kernel(const KnnParams P)
 #pragma unroll
         for (int j = 0; j < KL; ++j)
             if ((uint32_t)j < k) {
-                P.out_idx[(size_t)q * k + j] = (int32_t)(kl[u][j] & 0x3FFFFFu);
-                P.out_dist[(size_t)q * k + j] = (float)(kl[u][j] >> 22);
+                P.out_idx[(size_t)q * k + j] = (int32_t)ham_key_row(kl[u][j]);
+                P.out_dist[(size_t)q * k + j] = (float)ham_key_dist(kl[u][j]);
             }
     }
 }
@@ -266,11 +266,7 @@ static hipError_t launch_hamming_knnk_w(hipStream_t st, const KnnParams& P, uint
 hipError_t launch_hamming_knnk(hipStream_t st, const KnnParams& P, uint32_t words, uint32_t n_query)
 {
     if (P.k < 1 || P.k > R3DM_KNN_MAX) return hipErrorInvalidValue;
-    switch (words) {
-        case 8:  return launch_hamming_knnk_w<8>(st, P, n_query);
-        case 16: return launch_hamming_knnk_w<16>(st, P, n_query);
-        default: return hipErrorInvalidValue;
-    }
+    return dispatch_words(words, [&](auto w) { return launch_hamming_knnk_w<decltype(w)::value>(st, P, n_query); });
 }
 
 }  // namespace r3dm

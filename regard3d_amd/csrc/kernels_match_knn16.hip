@@ -4,8 +4,8 @@
 //                                        per 16 dimensions; K-lists with a bound, the finish of the f32 K-list kernel with the
 //                                        split planes' key scale and slack
 // Where things live: the tile steps (int_tile_step, split_tile_step: one function template each, which l2_knn2_int_kernel and
-// l2_knn2_split_kernel instantiate with Top2), the descriptor and the launchers' k -> KL dispatch in kernels_match_tiles.hpp; TopK<KL>
-// and knnk_finish in kernels_match_knn_lists.hpp; the exact scan behind both kernels is l2_exact_knn_items_kernel (kernels_match_knn.hip).
+// l2_knn2_split_kernel instantiate with Top2) and the descriptor in kernels_match_tiles.hpp, the launchers' k -> KL dispatch in
+// r3dm_internal.hpp; TopK<KL> and knnk_finish in kernels_match_knn_lists.hpp; the exact scan behind both kernels is l2_exact_knn_items_kernel (kernels_match_knn.hip).
 // A kernel body here reads: load the queries, initialise the lists, prologue loads, the ping-pong loop over the shared step, drain, finish.
 // Which pair runs where is decided by the host alone (api_match.cpp: plan_batch); DESIGN.md 4.18.
 //

@@ -5,8 +5,8 @@
 //                                                   workgroup through LDS-DMA; exact keys, exact K-lists, nothing certified or scanned
 // The frame is l2_knn2_int_lds_kernel<..., OPS = 1>'s (kernels_match_hamming.hip): three LDS buffers, one s_waitcnt vmcnt(0) + s_barrier
 // per tile, a look-ahead of two tiles, ping-pong accumulators.  Where things live: the tile step (int_tile_step_lds, the function
-// template that kernel instantiates with Top2) and the launchers' k -> KL dispatch in kernels_match_tiles.hpp; TopK<KL>,
-// topk_push_exact and knn_lex_less in kernels_match_knn_lists.hpp.  The popcount K-list kernel this one is measured against is
+// template that kernel instantiates with Top2) in kernels_match_tiles.hpp; the launchers' k -> KL dispatch in r3dm_internal.hpp;
+// TopK<KL> and topk_push_exact in kernels_match_knn_lists.hpp; lex_less in kernels_match_common.hpp.  The popcount K-list kernel this one is measured against is
 // hamming_knnk_kernel (kernels_match_knn.hip).  DESIGN.md 4.23.
 //
 // Arithmetic: key = popcount(a) - 2 a.q + kHamBias, an exact integer carried as the bits of a normal positive float (the float order
@@ -38,8 +38,8 @@ __device__ __forceinline__ void hamming_knnk_finish(const KnnParams& P, const Im
         uint32_t r = 0;
 #pragma unroll
         for (int m = 0; m < KL; ++m) {
-            if (m != j) r += knn_lex_less(st.d[m], st.i[m], st.d[j], st.i[j]) ? 1u : 0u;
-            r += knn_lex_less(pd[m], pi[m], st.d[j], st.i[j]) ? 1u : 0u;
+            if (m != j) r += lex_less(st.d[m], st.i[m], st.d[j], st.i[j]) ? 1u : 0u;
+            r += lex_less(pd[m], pi[m], st.d[j], st.i[j]) ? 1u : 0u;
         }
         if (r < k) {
             P.out_idx[(size_t)q * k + r] = (int32_t)st.i[j];

@@ -5,18 +5,12 @@
 //                                      kernels_match_knn8.hip, i8 tiles)
 //   topk_push_lex, topk_wave_select    the same list for rows in any order, and the k smallest entries of a wavefront's 64 lists
 //                                      (kernels_mrpt.hip: the exact re-rank of the elected rows)
-//   knn_lex_less                       the project's one order: (distance, dataset row)
 //   knnk_finish<KL, MODE>              merge the two lane halves, re-score, rank, certify the k-th, write or list for the exact scan
 // The tile steps that fold keys into these lists, and into Top2, are in kernels_match_tiles.hpp (which includes this header).
 #pragma once
 #include "kernels_match_common.hpp"
 
 namespace r3dm {
-
-__device__ __forceinline__ bool knn_lex_less(float da, uint32_t ia, float db, uint32_t ib)
-{
-    return da < db || (da == db && ia < ib);
-}
 
 // ------------------------------------------------------------------------------------------------
 // K-list of one query column held by one lane HALF (16 of a tile's 32 rows): the KL smallest keys with their rows, ascending, and
@@ -82,7 +76,7 @@ __device__ __forceinline__ void topk_push_lex(TopK<KL>& s, float key, uint32_t i
 {
     bool c[KL];
 #pragma unroll
-    for (int j = 0; j < KL; ++j) c[j] = knn_lex_less(key, idx, s.d[j], s.i[j]);
+    for (int j = 0; j < KL; ++j) c[j] = lex_less(key, idx, s.d[j], s.i[j]);
 #pragma unroll
     for (int j = KL - 1; j >= 1; --j) {                 // downwards: d[j - 1], i[j - 1] are still the old ones
         const float td = c[j] ? key : s.d[j];
@@ -107,7 +101,7 @@ __device__ __forceinline__ void topk_wave_select(TopK<KL>& s, uint32_t k, Emit&&
 #pragma unroll
         for (int m = 32; m > 0; m >>= 1) {
             const float od = __shfl_xor(bd, m); const uint32_t oi = (uint32_t)__shfl_xor((int)bi, m);
-            const bool take = knn_lex_less(od, oi, bd, bi);
+            const bool take = lex_less(od, oi, bd, bi);
             bd = take ? od : bd; bi = take ? oi : bi;
         }
         if (bi != kNone && s.i[0] == bi) {
@@ -183,8 +177,8 @@ __device__ __forceinline__ void knnk_finish(const KnnParams& P, const ImgDev* __
         uint32_t r = 0;
 #pragma unroll
         for (int m = 0; m < KL; ++m) {
-            if (m != j) r += knn_lex_less(e[m], st.i[m], e[j], st.i[j]) ? 1u : 0u;
-            r += knn_lex_less(pe[m], pi[m], e[j], st.i[j]) ? 1u : 0u;
+            if (m != j) r += lex_less(e[m], st.i[m], e[j], st.i[j]) ? 1u : 0u;
+            r += lex_less(pe[m], pi[m], e[j], st.i[j]) ? 1u : 0u;
         }
         rank[j] = r;
     }

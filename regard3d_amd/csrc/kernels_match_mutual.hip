@@ -3,9 +3,11 @@
 // nearest row of I is i and the ratio test passed -- stays iff j is the nearest row of J to row i under the order (distance, row);
 // anything else becomes kNone, so the (i, j) ordering and both de-duplications never see it.
 //
-// The distance is the reference's (exact_l2sq: 4-way unrolled, scalar tail, no FMA -- symmetric in its operands bit for bit; the
-// popcount Hamming distance for binary rows) and the scan is exhaustive over J whatever arm nominated the match, so the result is a
-// deterministic subset of the switch-off result.  Only accepted matches are checked: tens to hundreds of rows of I against one view.
+// The distance is the reference's (exact_l2sq: 4-way unrolled, scalar tail, no FMA -- symmetric in its operands bit for bit; over
+// the tiles stage_l2sq, the same order for lengths without a tail; the popcount Hamming distance for binary rows) and the scan is
+// exhaustive over J whatever arm nominated the match, so the result is a deterministic subset of the switch-off result.  Only
+// accepted matches are checked: tens to hundreds of rows of I against one view.  The L2 step, the order, the packed key and the
+// gather's compaction round are the shared steps of kernels_match_common.hpp.
 //
 //   l2_mutual_batch_kernel<G>   padded lengths with a tensor kernel, dim % 4 == 0: one workgroup per pair, lane = one accepted match
 //                               (its row of I in registers), J's fragment-order f32 tiles streamed through LDS as
@@ -15,11 +17,6 @@
 #include "kernels_match_common.hpp"
 
 namespace r3dm {
-
-__device__ __forceinline__ bool mutual_lex_less(float da, uint32_t ia, float db, uint32_t ib)
-{
-    return da < db || (da == db && ia < ib);
-}
 
 // ------------------------------------------------------------------------------------------------
 // the frame of the two one-workgroup-per-pair kernels: gather the accepted (i, j) of the pair in query order into `cand`
@@ -31,7 +28,7 @@ template <class BestRow>
 __device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32_t pair, uint32_t nJ, unsigned long long* cand,
                                                    uint32_t* wave_cnt, BestRow&& best_row)
 {
-    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t lane = threadIdx.x & 63u;
     uint32_t* nn = P.nn_idx + (size_t)pair * P.q_stride;
     uint32_t held = 0, qpos = 0;                     // block-uniform: keys in cand, first query not gathered yet
     uint32_t checked = 0, dropped = 0;               // per wave, kept by its lane 0
@@ -40,14 +37,9 @@ __device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32
             const uint32_t q = qpos + threadIdx.x;
             const uint32_t v = (q < nJ) ? nn[q] : kNone;
             const bool keep = (v < kFallback);
-            const unsigned long long bal = __ballot(keep);
-            const uint32_t before = (uint32_t)__builtin_popcountll(bal & ((1ull << lane) - 1ull));
-            if (lane == 0) wave_cnt[wave] = (uint32_t)__builtin_popcountll(bal);
-            r3dm_syncthreads();
-            uint32_t woff = 0, tot = 0;
-#pragma unroll
-            for (uint32_t w = 0; w < 4; ++w) { const uint32_t cw = wave_cnt[w]; if (w < wave) woff += cw; tot += cw; }
-            if (keep) cand[held + woff + before] = ((unsigned long long)v << 32) | q;
+            uint32_t tot;
+            const uint32_t rank = wg_compact_rank(keep, wave_cnt, tot);
+            if (keep) cand[held + rank] = ((unsigned long long)v << 32) | q;
             held += tot; qpos += 256u;
             r3dm_syncthreads();
         }
@@ -105,15 +97,7 @@ void l2_mutual_batch_kernel(const MutualParams P)
             r3dm_syncthreads();
             const uint32_t rows_here = (nJ - t0 < 32u) ? nJ - t0 : 32u;
             for (uint32_t r = 0; r < rows_here; ++r) {
-                float result = 0.0f;
-#pragma unroll
-                for (int k = 0; k < D4; ++k) {
-                    if (k < (int)d4) {
-                        const f32x4 a = tile[k * 32 + r];
-                        const float e0 = iv[k][0] - a[0], e1 = iv[k][1] - a[1], e2 = iv[k][2] - a[2], e3 = iv[k][3] - a[3];
-                        result += e0 * e0 + e1 * e1 + e2 * e2 + e3 * e3;
-                    }
-                }
+                const float result = stage_l2sq<D4>(iv, tile, r, d4);
                 if (result < bd) { bd = result; bj = t0 + r; }      // rows ascend: an equal distance keeps the lower row
             }
         }
@@ -126,14 +110,10 @@ hipError_t launch_l2_mutual_batch(hipStream_t st, const MutualParams& P, uint32_
     if (P.n_pairs == 0) return hipSuccess;
     if (P.n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
     const dim3 grid(P.n_pairs);
-    switch (G) {
-        case 8:  hipLaunchKernelGGL((l2_mutual_batch_kernel<8>), grid, dim3(256), 0, st, P); break;
-        case 16: hipLaunchKernelGGL((l2_mutual_batch_kernel<16>), grid, dim3(256), 0, st, P); break;
-        case 18: hipLaunchKernelGGL((l2_mutual_batch_kernel<18>), grid, dim3(256), 0, st, P); break;
-        case 32: hipLaunchKernelGGL((l2_mutual_batch_kernel<32>), grid, dim3(256), 0, st, P); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_g(G, [&](auto g) {
+        hipLaunchKernelGGL((l2_mutual_batch_kernel<decltype(g)::value>), grid, dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -167,7 +147,7 @@ void l2_mutual_items_kernel(const MutualParams P, uint32_t count)
         for (uint32_t s = 128; s > 0; s >>= 1) {
             if (threadIdx.x < s) {
                 const float b = sd[threadIdx.x + s]; const uint32_t y = si[threadIdx.x + s];
-                if (mutual_lex_less(b, y, sd[threadIdx.x], si[threadIdx.x])) { sd[threadIdx.x] = b; si[threadIdx.x] = y; }
+                if (lex_less(b, y, sd[threadIdx.x], si[threadIdx.x])) { sd[threadIdx.x] = b; si[threadIdx.x] = y; }
             }
             r3dm_syncthreads();
         }
@@ -193,8 +173,7 @@ hipError_t launch_l2_mutual_items(hipStream_t st, const MutualParams& P, uint32_
 
 // ------------------------------------------------------------------------------------------------
 // binary rows (ImgDev::bin: row-major u32 [n][W]): lane = one accepted match, its row of I in registers, 32 rows of J per LDS stage.
-// Keys are distance << 22 | row (a view has fewer than 2^22 rows, a distance at most 512): the unsigned minimum IS the
-// (distance, row) order.
+// The unsigned minimum of the packed keys (ham_key) IS the nearest row under the (distance, row) order.
 // ------------------------------------------------------------------------------------------------
 template <int W>
 __global__ __launch_bounds__(256)
@@ -225,11 +204,11 @@ void hamming_mutual_kernel(const MutualParams P)
                 uint32_t d = 0;
 #pragma unroll
                 for (int w = 0; w < W; ++w) d += (uint32_t)__builtin_popcount(a[w] ^ tile[r * W + w]);
-                const uint32_t key = (d << 22) | (t0 + r);
+                const uint32_t key = ham_key(d, t0 + r);
                 best = best < key ? best : key;
             }
         }
-        return best == 0xFFFFFFFFu ? kNone : (best & 0x3FFFFFu);
+        return best == 0xFFFFFFFFu ? kNone : ham_key_row(best);
     });
 }
 
@@ -238,12 +217,10 @@ hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t
     if (P.n_pairs == 0) return hipSuccess;
     if (P.n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
     const dim3 grid(P.n_pairs);
-    switch (words) {
-        case 8:  hipLaunchKernelGGL((hamming_mutual_kernel<8>), grid, dim3(256), 0, st, P); break;
-        case 16: hipLaunchKernelGGL((hamming_mutual_kernel<16>), grid, dim3(256), 0, st, P); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return dispatch_words(words, [&](auto w) {
+        hipLaunchKernelGGL((hamming_mutual_kernel<decltype(w)::value>), grid, dim3(256), 0, st, P);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace r3dm

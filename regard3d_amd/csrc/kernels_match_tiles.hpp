@@ -11,7 +11,7 @@
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
 //   bf16x2_times_m2                    -2 x a packed pair of bf16 integers (the query fragments of the integer tiles)
 //   pair_grid                          host: qb_per_pair, xcd_map, the grid of a 2-NN launch and its bound
-//   dispatch_kl, tiles_within_reach    host: k -> list depth of a K-list launch; the 2^31-byte reach of the buffer offsets
+//   tiles_within_reach                 host: the 2^31-byte reach of the buffer offsets (dispatch_kl is in r3dm_internal.hpp)
 // Every step is templated on the list type and on NJ, the query tiles a wave holds; the K-list kernels that hold one tile keep arrays
 // of one.
 // What is NOT here, on purpose: the ping-pong loop around the steps (two steps, the odd tail, the drain of the last tile), the load of
@@ -376,14 +376,6 @@ inline bool pair_grid(MatchParams& P, uint32_t max_nj_tiles, uint32_t nj, uint32
     if (grid64 == 0 || grid64 > kMaxBlocksOf256) return false;
     grid = (uint32_t)grid64;
     return true;
-}
-
-// ---- host side of the K-list launchers
-// KL is the list depth a kernel is built with: 4 for k <= 4, 8 above (k <= R3DM_KNN_MAX is the caller's check).  f(KL) launches.
-template <class F>
-inline hipError_t dispatch_kl(uint32_t k, F&& f)
-{
-    return k <= 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 8>{});
 }
 
 // the nominators address a dataset through 32-bit buffer offsets: its tiles and both slacks must end below 2^31 - 1 bytes

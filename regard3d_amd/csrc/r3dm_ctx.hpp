@@ -303,7 +303,6 @@ inline uint32_t kernel_G_for(uint32_t dim)
     if (g <= 32) return 32;
     return g;               // no tensor kernel: exact scan only
 }
-inline bool has_tensor_kernel(uint32_t G) { return G == 8 || G == 16 || G == 18 || G == 32; }
 
 inline uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 

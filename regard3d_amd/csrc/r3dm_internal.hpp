@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/r3dm.h"
 
@@ -437,6 +438,40 @@ hipError_t ac_aux_parallel(hipStream_t st, const AcCand* cand, uint32_t stride, 
 hipError_t ac_finish(hipStream_t st, const AcSlot* slots, uint32_t stride, const uint32_t* n_slots, const AcLevelTab& tab, const AcPlanes& pl,
                      AcOut* out, uint32_t max_slots, int B, const AcUpGrid& ug);
 constexpr uint32_t kAkSlotBytes = 80;                  // per candidate slot: cand 16 + list 16 + live 16 + out0 16 + out1 8 + valid 4 + dead 2 (+ 2 spare)
+
+// ---- run-time value -> template argument of a launch.  f(std::integral_constant<int, V>{}) launches and returns the status; a value
+// without a kernel is hipErrorInvalidValue.  Each list is written here and nowhere else: the kernels that exist are the instantiations
+// these functions make.  (Launchers whose cases carry further per-value template arguments -- prefetch depth, tile variants -- keep
+// their own switch.)
+// G: 8-float groups of a padded row with a tensor kernel, i.e. padded lengths 64 / 128 / 144 / 256
+template <class F>
+inline hipError_t dispatch_g(uint32_t G, F&& f)
+{
+    switch (G) {
+        case 8:  return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        case 18: return f(std::integral_constant<int, 18>{});
+        case 32: return f(std::integral_constant<int, 32>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// words: u32 words of a binary row with a kernel of its own (29 .. 32 / 61 .. 64 bytes)
+template <class F>
+inline hipError_t dispatch_words(uint32_t words, F&& f)
+{
+    switch (words) {
+        case 8:  return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+// KL is the list depth a K-list kernel is built with: 4 for k <= 4, 8 above (k <= R3DM_KNN_MAX is the caller's check)
+template <class F>
+inline hipError_t dispatch_kl(uint32_t k, F&& f)
+{
+    return k <= 4 ? f(std::integral_constant<int, 4>{}) : f(std::integral_constant<int, 8>{});
+}
+inline bool has_tensor_kernel(uint32_t G) { return dispatch_g(G, [](auto) { return hipSuccess; }) == hipSuccess; }
 
 // ---- launchers implemented in the .hip files (host side) ----
 // registration of one float view (kernels_match.hip: stage_view_kernel): raw descriptors -> fragment-order tiles + norms + statistics

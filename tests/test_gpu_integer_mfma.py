@@ -175,7 +175,7 @@ def test_collection_graphs_of_every_descriptor_kind(ictx, oracle):
 
 
 def test_views_beyond_the_lds_sort_budget(ictx, oracle):
-    _parity_module().test_views_beyond_the_lds_sort_budget(ictx, oracle, 20000, 1.0)
+    _parity_module().test_views_beyond_the_lds_sort_budget(ictx, oracle, 20000, 1.0, 0)
 
 
 @pytest.mark.parametrize("env,kind", [({"R3DM_L2_INT_VARIANT": "7"}, "sift"), ({"R3DM_L2_INT_VARIANT": "5"}, "sift"), ({"R3DM_HAMMING_RING": "1"}, "akaze")])

@@ -183,6 +183,18 @@ def test_save_load_roundtrip(ctx, oracle, tmp_path):
         assert np.array_equal(p, g.pairs) and np.array_equal(m, g.matches)
 
 
+def _sliced_scan_case():
+    """dataset 2,100 x 128 and queries 200 x 128 of test_uncertified_queries_take_the_exact_paths: the near-duplicate rows of its
+    first case; dataset rows 1,500 and 2,099 are copies of row 5 and the first eight queries lie closer to row 5 than to any other"""
+    rng = np.random.default_rng(22)
+    base = rng.gamma(0.5, 1.0, 128).astype(np.float32); base /= np.linalg.norm(base)
+    a = (base[None, :] * (1 + 1e-6 * rng.normal(size=(2100, 128)))).astype(np.float32)
+    b = (base[None, :] * (1 + 1e-6 * rng.normal(size=(200, 128)))).astype(np.float32)
+    a[1500] = a[5]; a[2099] = a[5]
+    b[:8] = (a[5][None, :] * (1 + 2e-7 * rng.normal(size=(8, 128)))).astype(np.float32)
+    return a, b
+
+
 def test_uncertified_queries_take_the_exact_paths(ctx, oracle):
     """Near-duplicate real-valued rows: the MFMA nomination cannot be certified, so every query goes
     through the per-pair batched exact scan (first 128) and the overflow rescan (the rest)."""
@@ -200,6 +212,16 @@ def test_uncertified_queries_take_the_exact_paths(ctx, oracle):
     assert ctx.stats().n_exact_fallback > 300
     counts, matches = oracle.match_collection([a, b, a[:100]], None, np.array([[0, 1], [0, 2], [1, 2]], np.uint32), 0.999, True)
     _graph_equal(g, np.array([[0, 1], [0, 2], [1, 2]]), counts, matches)
+    # the slice merge: 2,100 dataset rows are three slices of 22 tiles (704 / 704 / 692 rows, the last tile partial), whose partial
+    # (best, runner-up) the last workgroup of the pair merges; rows 1,500 and 2,099 are bit-copies of row 5, so for the queries that
+    # sit next to row 5 best and runner-up tie exactly across slices 0 and 2 and only the (distance, row) order decides the indices
+    a2, b2 = _sliced_scan_case()
+    idx, dist = ctx.knn2(a2, b2)
+    assert ctx.stats().n_exact_fallback == 200
+    oidx, odist = oracle.knn2(a2, b2)
+    tie = (odist[:, 0] == odist[:, 1]) & (oidx[:, 0] == 5) & (oidx[:, 1] == 1500)
+    assert tie.any()                                                      # (the oracle alone: the case holds what it is built for)
+    assert np.array_equal(dist, odist) and np.array_equal(idx, oidx)
 
 
 def test_integer_descriptors_need_no_rounding_slack(ctx):
@@ -366,19 +388,30 @@ def _two_view_scene(rng, n, dim, frac_match=1.0):
     return A, xyA.astype(np.float32), B[perm], xyB[perm].astype(np.float32)
 
 
-@pytest.mark.parametrize("n,frac", [(20000, 1.0), (18000, 0.3)])
-def test_views_beyond_the_lds_sort_budget(ctx, oracle, n, frac):
+@pytest.mark.parametrize("n,frac,dup", [(20000, 1.0, 0), (18000, 0.3, 0), (20000, 1.0, 40)],
+                         ids=["20000-1.0", "18000-0.3", "20000-1.0-dup40"])
+def test_views_beyond_the_lds_sort_budget(ctx, oracle, n, frac, dup):
     """nFeatures_ defaults to 20000 (src/Regard3DFeatures.cpp:128): more rows than the 16384-key LDS sort of the finalisation
-    kernel -> pairs that keep more than 16384 matches sort in global scratch; more than 8192 putatives -> the filter spills too."""
+    kernel -> pairs that keep more than 16384 matches sort in global scratch; more than 8192 putatives -> the filter spills too.
+    dup: view J ends with a copy of its first `dup` rows at their positions (J alone: the same rows twice in I would tie best and
+    runner-up and fail the ratio test), so J repeats positions and the coordinate de-duplication -- the drop pass and the fenced
+    compaction rounds -- runs on the list in global scratch."""
     rng = np.random.default_rng(n)
     A, xyA, B, xyB = _two_view_scene(rng, n, 16, frac)
+    if dup:
+        B = np.concatenate([B, B[:dup]]); xyB = np.concatenate([xyB, xyB[:dup]])
     ctx.clear_images()
     ctx.set_image(0, A, xyA, 4000, 3000); ctx.set_image(1, B, xyB, 4000, 3000)
     pairs = np.array([[0, 1]], np.uint32)
     g = ctx.match_pairs(pairs, 0.6, True)
     counts, matches = oracle.match_collection([A, B], [xyA, xyB], pairs, 0.6, True)
     assert counts[0] > (16384 if frac == 1.0 else 4000)
+    if dup:                                                               # (the oracle alone: the de-duplication has matches to drop)
+        plain, _ = oracle.match_collection([A, B], None, pairs, 0.6, True)
+        assert plain[0] - counts[0] >= 20
     _graph_equal(g, pairs, counts, matches)
+    if dup:
+        return
     gf, F = ctx.filter_F(g, 4.0, 2048, seed=5489, want_F=True)
     oc, om, oF = oracle.filter_F_collection([xyA, xyB], [4000, 4000], [3000, 3000], pairs, counts, matches, 4.0, 2048, 5489, want_F=True)
     assert oc[0] > 0.9 * counts[0] and gf.num_pairs == 1
