@@ -483,6 +483,38 @@ def load_library():
     return L
 
 
+class DevAcLevel(C.Structure):
+    """r3dm_dev_ac_level (developer build, api_akaze_classic.cpp): one level of a classic A-KAZE level table"""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("octave", C.c_int32), ("esigma", C.c_float), ("ratio", C.c_float)]
+
+
+def bind_dev_akaze_classic_walk(L):
+    """the developer build's walk entries (libr3dm_dev.so only, declared in no header), bound when first asked for"""
+    if getattr(L, "_r3dm_dev_walk_bound", False):
+        return L
+    if not hasattr(L, "r3dm_dev_akaze_classic_walk"):
+        raise R3dmError("r3dm_dev_akaze_classic_walk exists in the developer build only: use_developer_library() before the first load")
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.r3dm_dev_akaze_classic_walk_check.argtypes = [vp, u32, u32, u32, u32, vp, vp, C.c_int, u32]
+    L.r3dm_dev_akaze_classic_walk.argtypes = [vp, vp, u32, u32, u32, u32, vp, vp, C.c_int, u32, vp, vp, vp]
+    L._r3dm_dev_walk_bound = True
+    return L
+
+
+def dev_walk_args(levels, lists):
+    """(level array, n_cand [B] uint32, candidates [sum, 4] uint32 words) of the walk entries.  levels: dicts with w, h, octave,
+    esigma, ratio; lists: per image (level, row, col, value) tuples -- stored as the library's (x = col, y = row, level, value)"""
+    lv = (DevAcLevel * max(len(levels), 1))(*[DevAcLevel(int(e["w"]), int(e["h"]), int(e["octave"]), float(e["esigma"]), float(e["ratio"]))
+                                              for e in levels])
+    n_cand = np.array([len(l) for l in lists], np.uint32)
+    words = np.zeros((int(n_cand.sum()), 4), np.uint32)
+    flat = [c for l in lists for c in l]
+    if flat:
+        words[:, 0] = [c[2] for c in flat]; words[:, 1] = [c[1] for c in flat]; words[:, 2] = [c[0] for c in flat]
+        words[:, 3] = np.array([c[3] for c in flat], np.float32).view(np.uint32)
+    return lv, n_cand, words
+
+
 def _ptr(a) -> Optional[int]:
     """address of a numpy array or torch tensor (host or device) -- the ABI takes plain pointers"""
     if a is None:
@@ -1178,6 +1210,25 @@ class Context:
         h = np.zeros(32, np.uint64)
         self._check(self._L.r3dm_akaze_classic_components(self._h, _ptr(h)), "r3dm_akaze_classic_components")
         return h
+
+    def dev_akaze_classic_walk(self, levels, width: int, height: int, lists, parallel: bool = True, bound: int = 64):
+        """r3dm_dev_akaze_classic_walk (developer build): the classic arm's kpts_aux walk and upper-level filter on the caller's
+        candidate lists, one per image (see dev_walk_args) -> per image a dict: x, y, size, resp [n_slots] float32 and cls [n_slots]
+        uint32 in list order, kept [n_slots] bool (the upper-level filter), hist [32] (component sizes of the parallel form)"""
+        L = bind_dev_akaze_classic_walk(self._L)
+        lv, n_cand, words = dev_walk_args(levels, lists)
+        B = len(lists)
+        n_slots = np.zeros(max(B, 1), np.uint32); out = np.zeros((max(len(words), 1), 6), np.uint32); hist = np.zeros((max(B, 1), 32), np.uint32)
+        self._check(L.r3dm_dev_akaze_classic_walk(self._h, C.addressof(lv), len(levels), width, height, B, _ptr(n_cand), _ptr(words),
+                                                  int(bool(parallel)), bound, _ptr(n_slots), _ptr(out), _ptr(hist)), "r3dm_dev_akaze_classic_walk")
+        res, at = [], 0
+        for b in range(B):
+            o = out[at:at + int(n_slots[b])]
+            f = np.ascontiguousarray(o[:, :4]).view(np.float32)
+            res.append(dict(x=f[:, 0].copy(), y=f[:, 1].copy(), size=f[:, 2].copy(), resp=f[:, 3].copy(), cls=o[:, 4].copy(),
+                            kept=o[:, 5] != 0, hist=hist[b].copy()))
+            at += int(n_cand[b])
+        return res
 
     def guided_match(self, pairs, kind: str, models, threshold_px, ratio: float) -> Graph:
         """r3dm_guided_match: guided matching of `pairs` (a Graph -- only its pair list is read -- or an (P, 2) array in (I, J) order)

@@ -60,6 +60,79 @@ std::vector<float> ac_fed_tau(float T)
     return tau;
 }
 
+// the context's work buffers of this arm (c->ac_bufs), by index; from C_PLANES on: per level Lx, Ly, Ldet
+enum { C_IMG, C_LTA, C_LTB, C_SMOOTH, C_FLOW, C_TMP, C_SMALL, C_ROWS, C_TABS, C_CAND, C_SLOTS, C_NSL, C_OUTS, C_HEADS, C_ESLOT, C_ECELL,
+       C_ENEXT, C_CC, C_UPHEADS, C_UPNEXT, C_PLANES };
+void ac_bufs_init(r3dm_ctx* c)
+{
+    if (c->ac_bufs.size() != (size_t)C_PLANES + 3 * kAcMaxLevels) c->ac_bufs.resize((size_t)C_PLANES + 3 * kAcMaxLevels);
+}
+
+// The kpts_aux walk and what follows it, from the point where the candidates of the B images (C_CAND, `stride` per image, scan order),
+// their row offsets rc (rows_stride per image, tab.row0) and their totals are on the device: the walk in the asked form (parallel: the
+// components form with the wavefront bound `bound`; otherwise one wavefront per image over every candidate, and the upper-level filter
+// over every later slot), the upper-level filter's buckets, then ac_finish over the planes pl.  Queues on the context's stream and
+// returns without waiting: the slots are in C_SLOTS, their counts in C_NSL, the finished slots in C_OUTS, and *hist_out is the
+// per-image component histogram on the device (null in the one-wavefront form).  The detector and the developer build's walk entry
+// (r3dm_dev_akaze_classic_walk below) both go through it.
+int ac_walk(r3dm_ctx* c, uint32_t B, int w, int h, const AcLevelTab& tab, const AcPlanes& pl, uint32_t stride, const uint32_t* rc,
+            uint32_t rows_stride, const uint32_t* totals, bool parallel, uint32_t bound, uint32_t** hist_out)
+{
+    hipStream_t st = c->stream;
+    const int iB = (int)B, nl = tab.n_levels;
+    auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
+    DevBuf &cand = buf(C_CAND), &slots = buf(C_SLOTS), &nsl = buf(C_NSL), &outs = buf(C_OUTS);
+    R3DM_HIP(c, slots.ensure((size_t)B * stride * sizeof(AcSlot)));
+    R3DM_HIP(c, nsl.ensure((size_t)B * 4));
+    R3DM_HIP(c, outs.ensure((size_t)B * stride * sizeof(AcOut)));
+    // the kpts_aux walk's grid: cells of side >= 3 px (level 0: size 2.4) over the image, entries = the slots entered at a level start
+    // (<= stride) + one per accepted point of the level (<= stride)
+    AcGrid grid{};
+    grid.img_w = w; grid.img_h = h;
+    grid.cells_stride = (size_t)(w / 3 + 2) * (size_t)(h / 3 + 2);
+    grid.ent_stride = 2 * (size_t)stride;
+    R3DM_HIP(c, buf(C_HEADS).ensure((size_t)B * grid.cells_stride * 4));
+    R3DM_HIP(c, buf(C_ESLOT).ensure((size_t)B * grid.ent_stride * 4));
+    R3DM_HIP(c, buf(C_ECELL).ensure((size_t)B * grid.ent_stride * 4));
+    R3DM_HIP(c, buf(C_ENEXT).ensure((size_t)B * grid.ent_stride * 4));
+    grid.heads = buf(C_HEADS).as<int>(); grid.ent_slot = buf(C_ESLOT).as<uint32_t>(); grid.ent_cell = buf(C_ECELL).as<uint32_t>();
+    grid.ent_next = buf(C_ENEXT).as<int>();
+    R3DM_HIP(c, hipMemsetAsync(grid.heads, 0xFF, (size_t)B * grid.cells_stride * 4, st));
+    AcUpGrid ug{};
+    uint32_t* hist = nullptr;
+    if (!parallel) {
+        R3DM_HIP(c, ac_aux(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), iB));
+    } else {
+        // nine per-candidate arrays, then n_big [B], scan totals [B], the histogram [32 B]
+        const size_t per = (size_t)B * stride;
+        R3DM_HIP(c, buf(C_CC).ensure((9 * per + 34 * (size_t)B) * 4));
+        uint32_t* w0 = buf(C_CC).as<uint32_t>();
+        AcCc cc{};
+        uint32_t** arrs[9] = {&cc.par, &cc.csz, &cc.boff, &cc.cur, &cc.memb, &cc.fin, &cc.opn, &cc.big, &cc.bopen};
+        for (int k = 0; k < 9; ++k) *arrs[k] = w0 + (size_t)k * per;
+        cc.n_big = w0 + 9 * per; cc.scratch = cc.n_big + B; hist = cc.hist = cc.scratch + B;
+        cc.rows = rc; cc.rows_stride = rows_stride;
+        R3DM_HIP(c, hipMemsetAsync(hist, 0, (size_t)B * 32 * 4, st));
+        R3DM_HIP(c, ac_aux_parallel(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), cc, bound, iB));
+        // the upper-level filter's buckets: class k >= 1 in cells of side floor(size_{k-1}) + 1 over the image
+        ug.img_w = w; ug.img_h = h;
+        size_t cells = 0;
+        for (int k = 1; k < nl; ++k) {
+            ug.G[k] = (int)(tab.esigma[k - 1] * 1.5f) + 1;
+            ug.cell_off[k] = (uint32_t)cells;
+            cells += (size_t)(w / ug.G[k] + 2) * (size_t)(h / ug.G[k] + 2);
+        }
+        ug.cells_stride = std::max<size_t>(cells, 1);
+        R3DM_HIP(c, buf(C_UPHEADS).ensure((size_t)B * ug.cells_stride * 4));
+        R3DM_HIP(c, buf(C_UPNEXT).ensure(per * 4));
+        ug.heads = buf(C_UPHEADS).as<int>(); ug.next = buf(C_UPNEXT).as<int>();
+        R3DM_HIP(c, hipMemsetAsync(ug.heads, 0xFF, (size_t)B * ug.cells_stride * 4, st));
+    }
+    R3DM_HIP(c, ac_finish(st, slots.as<AcSlot>(), stride, nsl.as<uint32_t>(), tab, pl, outs.as<AcOut>(), stride, iB, ug));
+    *hist_out = hist;
+    return R3DM_OK;
+}
+
 }  // namespace
 
 // the detector over B same-size images; out.classic[b] = the keypoints of image b in the reference's order.
@@ -82,9 +155,7 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     // work buffers on the context, kept between calls (they grow, never shrink; released with the context): B planes each of the image,
     // two evolving images, the smoothed image, the conductivity and a Gaussian scratch; per level Lx, Ly, Ldet (read again by the
     // refinement and the orientation); then the candidate, slot, grid and output arrays
-    enum { C_IMG, C_LTA, C_LTB, C_SMOOTH, C_FLOW, C_TMP, C_SMALL, C_ROWS, C_TABS, C_CAND, C_SLOTS, C_NSL, C_OUTS, C_HEADS, C_ESLOT, C_ECELL,
-           C_ENEXT, C_CC, C_UPHEADS, C_UPNEXT, C_PLANES };
-    if (c->ac_bufs.size() != (size_t)C_PLANES + 3 * kAcMaxLevels) c->ac_bufs.resize((size_t)C_PLANES + 3 * kAcMaxLevels);
+    ac_bufs_init(c);
     auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
     DevBuf &img = buf(C_IMG), &ltA = buf(C_LTA), &ltB = buf(C_LTB), &smooth = buf(C_SMOOTH), &flow = buf(C_FLOW), &tmp = buf(C_TMP);
     DevBuf &small = buf(C_SMALL), &rows = buf(C_ROWS), &tabs = buf(C_TABS);
@@ -157,24 +228,8 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     R3DM_HIP(c, hipStreamSynchronize(st));
     uint32_t stride = 1;
     for (uint32_t b = 0; b < B; ++b) stride = std::max(stride, tot[b]);
-    DevBuf &cand = buf(C_CAND), &slots = buf(C_SLOTS), &nsl = buf(C_NSL), &outs = buf(C_OUTS);
+    DevBuf &cand = buf(C_CAND), &nsl = buf(C_NSL), &outs = buf(C_OUTS);
     R3DM_HIP(c, cand.ensure((size_t)B * stride * sizeof(AcCand)));
-    R3DM_HIP(c, slots.ensure((size_t)B * stride * sizeof(AcSlot)));
-    R3DM_HIP(c, nsl.ensure((size_t)B * 4));
-    R3DM_HIP(c, outs.ensure((size_t)B * stride * sizeof(AcOut)));
-    // the kpts_aux walk's grid: cells of side >= 3 px (level 0: size 2.4) over the image, entries = the slots entered at a level start
-    // (<= stride) + one per accepted point of the level (<= stride)
-    AcGrid grid{};
-    grid.img_w = w; grid.img_h = h;
-    grid.cells_stride = (size_t)(w / 3 + 2) * (size_t)(h / 3 + 2);
-    grid.ent_stride = 2 * (size_t)stride;
-    R3DM_HIP(c, buf(C_HEADS).ensure((size_t)B * grid.cells_stride * 4));
-    R3DM_HIP(c, buf(C_ESLOT).ensure((size_t)B * grid.ent_stride * 4));
-    R3DM_HIP(c, buf(C_ECELL).ensure((size_t)B * grid.ent_stride * 4));
-    R3DM_HIP(c, buf(C_ENEXT).ensure((size_t)B * grid.ent_stride * 4));
-    grid.heads = buf(C_HEADS).as<int>(); grid.ent_slot = buf(C_ESLOT).as<uint32_t>(); grid.ent_cell = buf(C_ECELL).as<uint32_t>();
-    grid.ent_next = buf(C_ENEXT).as<int>();
-    R3DM_HIP(c, hipMemsetAsync(grid.heads, 0xFF, (size_t)B * grid.cells_stride * 4, st));
     for (int i = 0; i < nl; ++i)
         R3DM_HIP(c, ac_extrema(st, Ldet(i), lv[i].w, lv[i].h, iB, threshold, rc, rows_stride, row0[i], cand.as<AcCand>(), stride, i, 1));
     AcLevelTab tab{};
@@ -187,41 +242,13 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
         pl.ldet[i] = Ldet(i); pl.lx[i] = Lx(i); pl.ly[i] = Ly(i);
     }
     for (int i = 0; i < nl; ++i) tab.row0[i] = row0[i];
+    // the candidates, their row offsets and totals are on the device: the walk, the upper-level filter, refinement and orientation.
     // R3DM_AC_AUX=0 (developer build): the one-wavefront walk over every candidate and the upper-level filter over every later slot.
     // R3DM_AC_AUX_BOUND (test hook): a smaller wavefront bound hands more components back to the one-wavefront walk.
     static const bool parallel = r3dm_dev_knob("R3DM_AC_AUX", 1) != 0;
     static const uint32_t bound = [] { const int v = r3dm_dev_knob("R3DM_AC_AUX_BOUND", 64); return (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v); }();
-    AcUpGrid ug{};
     uint32_t* hist = nullptr;
-    if (!parallel) {
-        R3DM_HIP(c, ac_aux(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), iB));
-    } else {
-        // nine per-candidate arrays, then n_big [B], scan totals [B], the histogram [32 B]
-        const size_t per = (size_t)B * stride;
-        R3DM_HIP(c, buf(C_CC).ensure((9 * per + 34 * (size_t)B) * 4));
-        uint32_t* w0 = buf(C_CC).as<uint32_t>();
-        AcCc cc{};
-        uint32_t** arrs[9] = {&cc.par, &cc.csz, &cc.boff, &cc.cur, &cc.memb, &cc.fin, &cc.opn, &cc.big, &cc.bopen};
-        for (int k = 0; k < 9; ++k) *arrs[k] = w0 + (size_t)k * per;
-        cc.n_big = w0 + 9 * per; cc.scratch = cc.n_big + B; hist = cc.hist = cc.scratch + B;
-        cc.rows = rc; cc.rows_stride = rows_stride;
-        R3DM_HIP(c, hipMemsetAsync(hist, 0, (size_t)B * 32 * 4, st));
-        R3DM_HIP(c, ac_aux_parallel(st, cand.as<AcCand>(), stride, totals, tab, slots.as<AcSlot>(), grid, nsl.as<uint32_t>(), cc, bound, iB));
-        // the upper-level filter's buckets: class k >= 1 in cells of side floor(size_{k-1}) + 1 over the image
-        ug.img_w = w; ug.img_h = h;
-        size_t cells = 0;
-        for (int k = 1; k < nl; ++k) {
-            ug.G[k] = (int)(lv[k - 1].esigma * 1.5f) + 1;
-            ug.cell_off[k] = (uint32_t)cells;
-            cells += (size_t)(w / ug.G[k] + 2) * (size_t)(h / ug.G[k] + 2);
-        }
-        ug.cells_stride = std::max<size_t>(cells, 1);
-        R3DM_HIP(c, buf(C_UPHEADS).ensure((size_t)B * ug.cells_stride * 4));
-        R3DM_HIP(c, buf(C_UPNEXT).ensure(per * 4));
-        ug.heads = buf(C_UPHEADS).as<int>(); ug.next = buf(C_UPNEXT).as<int>();
-        R3DM_HIP(c, hipMemsetAsync(ug.heads, 0xFF, (size_t)B * ug.cells_stride * 4, st));
-    }
-    R3DM_HIP(c, ac_finish(st, slots.as<AcSlot>(), stride, nsl.as<uint32_t>(), tab, pl, outs.as<AcOut>(), stride, iB, ug));
+    if ((frc = ac_walk(c, B, w, h, tab, pl, stride, rc, rows_stride, totals, parallel, bound, &hist)) != R3DM_OK) return frc;
     R3DM_HIP(c, hipEventRecord(c->ev1, st));
     std::vector<uint32_t> ns(B), hs(hist ? (size_t)B * 32 : 0);
     R3DM_HIP(c, hipMemcpyAsync(ns.data(), nsl.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
@@ -265,3 +292,147 @@ extern "C" int r3dm_akaze_classic_components(const r3dm_ctx* c, uint64_t* hist)
     for (int k = 0; k < 32; ++k) hist[k] = c->ac_components[k];
     return R3DM_OK;
 }
+
+#ifdef R3DM_DEVTOOLS
+// ---- developer build only (libr3dm_dev.so; declared in no header): the walk on a caller's candidate lists, so that the suite can put the
+// cases to the kernels that images cannot reach (equal responses, distances exactly on the boundary, component sizes at the wavefront
+// bound, a slot that moved out of its cell).  The kernels that run are the product's: ac_walk above.
+struct r3dm_dev_ac_level { int32_t w, h, octave; float esigma, ratio; };
+
+// What the kernels would mis-read is refused here, before anything touches a device: R3DM_OK or R3DM_ERR_INVALID.
+//   levels [n_levels <= kAcMaxLevels]: w, h >= 3; octave in 0 .. 6 and ratio = 2^octave (ac_finish_kernel converts with either); the
+//   level fits the image (w ratio <= width, h ratio <= height, so a converted position stays inside the walk's grid); esigma finite;
+//   size = 1.5 esigma with a cell side floor(size) + 1 >= 3, the side the grid's allocation assumes; the orientation's sample step and
+//   the border test's agree (both are fRound(size / ratio), formed in double and in float: the border test then covers every read)
+//   n_cand [B], cand: the B lists one after the other, (x = column, y = row, level, value), each in strict scan order (level, row,
+//   column), rows 1 .. h - 2, columns 1 .. w - 2 of the candidate's level, finite values
+//   parallel: 0 = one wavefront per image and the every-later-slot filter, 1 = the product's parallel form; bound: 1 .. 64
+extern "C" int r3dm_dev_akaze_classic_walk_check(const r3dm_dev_ac_level* levels, uint32_t n_levels, uint32_t width, uint32_t height, uint32_t B,
+                                                 const uint32_t* n_cand, const AcCand* cand, int parallel, uint32_t bound)
+{
+    if (!levels || !n_cand || n_levels < 1 || n_levels > (uint32_t)kAcMaxLevels || B < 1 || B > 1024u) return R3DM_ERR_INVALID;
+    if (width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    if ((parallel != 0 && parallel != 1) || bound < 1 || bound > 64) return R3DM_ERR_INVALID;
+    for (uint32_t l = 0; l < n_levels; ++l) {
+        const r3dm_dev_ac_level& e = levels[l];
+        if (e.w < 3 || e.h < 3 || e.octave < 0 || e.octave > 6) return R3DM_ERR_INVALID;
+        if (!std::isfinite(e.esigma) || !(e.ratio == (float)(1 << e.octave))) return R3DM_ERR_INVALID;
+        if ((double)e.w * e.ratio > (double)width || (double)e.h * e.ratio > (double)height) return R3DM_ERR_INVALID;
+        const float size = e.esigma * 1.5f;
+        if (!(size >= 2.0f) || size > 4096.0f) return R3DM_ERR_INVALID;             // cell side floor(size) + 1 >= 3
+        if ((int)((float)(0.5 * (double)(size * 2.0f) / (double)e.ratio) + 0.5f) != (int)(size / e.ratio + 0.5f)) return R3DM_ERR_INVALID;
+    }
+    uint64_t at = 0;
+    for (uint32_t b = 0; b < B; ++b) {
+        if (n_cand[b] > (1u << 24) || (n_cand[b] && !cand)) return R3DM_ERR_INVALID;
+        for (uint32_t k = 0; k < n_cand[b]; ++k) {
+            const AcCand& p = cand[at + k];
+            if (p.level >= n_levels || !std::isfinite(p.value)) return R3DM_ERR_INVALID;
+            if (p.y < 1 || p.y > (uint32_t)levels[p.level].h - 2 || p.x < 1 || p.x > (uint32_t)levels[p.level].w - 2) return R3DM_ERR_INVALID;
+            if (k) {
+                const AcCand& q = cand[at + k - 1];
+                const bool later = p.level != q.level ? p.level > q.level : p.y != q.y ? p.y > q.y : p.x > q.x;
+                if (!later) return R3DM_ERR_INVALID;
+            }
+        }
+        at += n_cand[b];
+    }
+    return R3DM_OK;
+}
+
+// Runs the lists through ac_walk.  The row offsets that ac_cc_link_kernel and the hand-back read (rows, rows_stride = n_rows + 1,
+// tab.row0) are built from the lists here, on the host.  ac_finish_kernel fuses the upper-level filter with the refinement and the
+// orientation, which read the level planes: it is handed ZEROED planes (one zeroed buffer stands for every plane).  The Hessian
+// determinant around every slot is then 0, so the refinement shifts nothing and erases nothing, the orientation reads zeros inside the
+// plane (a slot passed the border test: reach 10 sqrt 2 steps, the orientation's is 6), and AcOut.ok is the filter's verdict alone.
+// Outputs: n_slots [B]; slots_out: six words per slot at the offsets of the candidate lists (image b's slots start at six times the
+// sum of n_cand before b; n_slots[b] <= n_cand[b]): x, y, size, response as float, then class and the kept flag as uint32; hist
+// [B x 32] (may be null): the parallel form's component-size histogram per image, zeros in the one-wavefront form.
+extern "C" int r3dm_dev_akaze_classic_walk(r3dm_ctx* c, const r3dm_dev_ac_level* levels, uint32_t n_levels, uint32_t width, uint32_t height,
+                                           uint32_t B, const uint32_t* n_cand, const AcCand* cand, int parallel, uint32_t bound,
+                                           uint32_t* n_slots, uint32_t* slots_out, uint32_t* hist_out)
+{
+    const int vrc = r3dm_dev_akaze_classic_walk_check(levels, n_levels, width, height, B, n_cand, cand, parallel, bound);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_classic_walk: a level table, candidate list, form or bound the kernels would mis-read"; return vrc; }
+    if (!c || !n_slots) return R3DM_ERR_INVALID;
+    uint64_t total = 0;
+    for (uint32_t b = 0; b < B; ++b) total += n_cand[b];
+    if (total && !slots_out) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        ac_bufs_init(c);
+        auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
+        const int w = (int)width, h = (int)height, nl = (int)n_levels;
+        AcLevelTab tab{};
+        AcPlanes pl{};
+        tab.n_levels = nl;
+        tab.smax = (float)(10.0 * sqrtf(2.0f));
+        uint32_t n_rows = 0;
+        size_t plane = 0;
+        for (int i = 0; i < nl; ++i) {
+            tab.w[i] = levels[i].w; tab.h[i] = levels[i].h; tab.octave[i] = levels[i].octave;
+            tab.esigma[i] = levels[i].esigma; tab.ratio[i] = levels[i].ratio; tab.off[i] = (float)(.5 * (levels[i].ratio - 1.0));
+            tab.row0[i] = n_rows; n_rows += (uint32_t)levels[i].h;
+            plane = std::max(plane, (size_t)levels[i].w * levels[i].h);
+        }
+        DevBuf& zero = buf(C_TMP);
+        plane = (size_t)B * plane + 4 * (size_t)width + 16;                          // (a spare row or two behind the last plane)
+        R3DM_HIP(c, zero.ensure(plane * 4));
+        R3DM_HIP(c, hipMemsetAsync(zero.p, 0, plane * 4, st));
+        for (int i = 0; i < nl; ++i) pl.ldet[i] = pl.lx[i] = pl.ly[i] = zero.as<float>();
+        // rows[r] = the candidates of the image before row r (levels one after the other), then the totals: what ac_scan_rows leaves
+        const uint32_t rows_stride = n_rows + 1;
+        std::vector<uint32_t> hrows((size_t)B * rows_stride + B, 0u);
+        uint32_t stride = 1;
+        uint64_t at = 0;
+        for (uint32_t b = 0; b < B; ++b) {
+            uint32_t* r = hrows.data() + (size_t)b * rows_stride;
+            for (uint32_t k = 0; k < n_cand[b]; ++k) r[tab.row0[cand[at + k].level] + cand[at + k].y + 1]++;
+            for (uint32_t q = 1; q <= n_rows; ++q) r[q] += r[q - 1];
+            r[n_rows] = 0;                                                           // (ac_scan_rows writes n_rows offsets; the spare word stays 0)
+            hrows[(size_t)B * rows_stride + b] = n_cand[b];
+            stride = std::max(stride, n_cand[b]);
+            at += n_cand[b];
+        }
+        DevBuf &rows = buf(C_ROWS), &cd = buf(C_CAND);
+        R3DM_HIP(c, rows.ensure(hrows.size() * 4));
+        R3DM_HIP(c, cd.ensure((size_t)B * stride * sizeof(AcCand)));
+        uint32_t* rc = rows.as<uint32_t>();
+        const uint32_t* totals = rc + (size_t)B * rows_stride;
+        R3DM_HIP(c, hipMemcpyAsync(rc, hrows.data(), hrows.size() * 4, hipMemcpyHostToDevice, st));
+        at = 0;
+        for (uint32_t b = 0; b < B; ++b) {
+            if (n_cand[b]) R3DM_HIP(c, hipMemcpyAsync(cd.as<AcCand>() + (size_t)b * stride, cand + at, (size_t)n_cand[b] * sizeof(AcCand), hipMemcpyHostToDevice, st));
+            at += n_cand[b];
+        }
+        R3DM_HIP(c, hipStreamSynchronize(st));                                       // (the host arrays have been read)
+        uint32_t* hist = nullptr;
+        const int frc = ac_walk(c, B, w, h, tab, pl, stride, rc, rows_stride, totals, parallel != 0, bound, &hist);
+        if (frc != R3DM_OK) { (void)hipStreamSynchronize(st); return frc; }
+        std::vector<uint32_t> hs((size_t)B * 32, 0u);
+        R3DM_HIP(c, hipMemcpyAsync(n_slots, buf(C_NSL).p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+        if (hist) R3DM_HIP(c, hipMemcpyAsync(hs.data(), hist, hs.size() * 4, hipMemcpyDeviceToHost, st));
+        R3DM_HIP(c, hipStreamSynchronize(st));
+        if (hist_out) std::copy(hs.begin(), hs.end(), hist_out);
+        at = 0;
+        for (uint32_t b = 0; b < B; ++b) {
+            if (n_slots[b] > n_cand[b]) { c->err = "r3dm_dev_akaze_classic_walk: more slots than candidates"; return R3DM_ERR_INVALID; }
+            std::vector<AcSlot> sl(n_slots[b]);
+            std::vector<AcOut> ou(n_slots[b]);
+            if (n_slots[b]) {
+                R3DM_HIP(c, hipMemcpyAsync(sl.data(), buf(C_SLOTS).as<AcSlot>() + (size_t)b * stride, sl.size() * sizeof(AcSlot), hipMemcpyDeviceToHost, st));
+                R3DM_HIP(c, hipMemcpyAsync(ou.data(), buf(C_OUTS).as<AcOut>() + (size_t)b * stride, ou.size() * sizeof(AcOut), hipMemcpyDeviceToHost, st));
+            }
+            R3DM_HIP(c, hipStreamSynchronize(st));
+            for (uint32_t q = 0; q < n_slots[b]; ++q) {
+                uint32_t* o = slots_out + 6 * (at + q);
+                memcpy(o, &sl[q], 16);                                               // x, y, size, response
+                o[4] = sl[q].cls; o[5] = ou[q].ok;
+            }
+            at += n_cand[b];
+        }
+        return R3DM_OK;
+    });
+}
+#endif  // R3DM_DEVTOOLS

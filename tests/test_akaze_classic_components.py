@@ -9,83 +9,9 @@ import numpy as np
 import pytest
 
 import akaze_classic_restatement as R
+from akaze_classic_walk_cases import _is_out, _random_list, _scan_order, _size, by_components, components, serial   # (the generators moved there)
 
 f32 = np.float32
-
-
-def _size(lv):
-    return f32(lv["esigma"] * R.DFAC)
-
-
-def _is_out(lv, row, col):
-    size, ratio = _size(lv), f32(lv["ratio"])
-    r = f32(R.SMAX * f32(R.fround(f32(size / ratio))))
-    px, py = f32(col), f32(row)
-    return (R.fround(f32(px - r)) - 1 < 0 or R.fround(f32(px + r)) + 1 >= lv["w"] or
-            R.fround(f32(py - r)) - 1 < 0 or R.fround(f32(py + r)) + 1 >= lv["h"])
-
-
-def _conv(v, lv):
-    ratio = f32(lv["ratio"])
-    return f32(float(f32(f32(v) * ratio)) + 0.5 * (float(ratio) - 1.0))
-
-
-def serial(levels, cands):
-    """cands: (level, row, col, value) in scan order -> the AuxList of the serial rule"""
-    aux = R.AuxList(max(1, len(cands)))
-    for (i, row, col, v) in cands:
-        lv = levels[i]
-        R.offer(aux, lv, i, row, col, f32(v), lv["h"], lv["w"])
-    return aux
-
-
-def components(levels, cands):
-    """union-find over the edges of the rule; returns the root of every candidate (-1: dropped by the border test)"""
-    n = len(cands)
-    par = np.array([-1 if _is_out(levels[c[0]], c[1], c[2]) else k for k, c in enumerate(cands)])
-
-    def find(x):
-        while par[x] != x:
-            par[x] = par[par[x]]
-            x = par[x]
-        return x
-
-    for p in range(n):
-        if par[p] < 0:
-            continue
-        l, row, col, _ = cands[p]
-        size = _size(levels[l]); ratio = f32(levels[l]["ratio"])
-        sx, sy = f32(f32(col) * ratio), f32(f32(row) * ratio)
-        for q in range(p):
-            m = cands[q][0]
-            if par[q] < 0 or m not in (l - 1, l):
-                continue
-            tx, ty = f32(sx - _conv(cands[q][2], levels[m])), f32(sy - _conv(cands[q][1], levels[m]))
-            if f32(tx * tx + ty * ty) <= f32(size * size):
-                a, b = find(p), find(q)
-                if a != b:
-                    par[max(a, b)] = min(a, b)
-    return np.array([find(k) if par[k] >= 0 else -1 for k in range(n)])
-
-
-def by_components(levels, cands):
-    """each component walked on its own, slots numbered by opener rank -> an AuxList laid out as the serial one"""
-    roots = components(levels, cands)
-    opened = []                                   # (opener index, component aux, slot in it)
-    for r in sorted(set(roots[roots >= 0].tolist())):
-        members = [k for k in range(len(cands)) if roots[k] == r]
-        aux = R.AuxList(len(members))
-        for k in members:
-            i, row, col, v = cands[k]
-            before = aux.n
-            R.offer(aux, levels[i], i, row, col, f32(v), levels[i]["h"], levels[i]["w"])
-            if aux.n > before:
-                opened.append((k, aux, before))
-    out = R.AuxList(max(1, len(cands)))
-    for s, (_, aux, q) in enumerate(sorted(opened, key=lambda t: t[0])):
-        out.put(s, aux.x[q], aux.y[q], aux.size[q], aux.resp[q], aux.cls[q], aux.octave[q])
-    out.n = len(opened)
-    return out, roots
 
 
 def _same(a, b):
@@ -94,23 +20,6 @@ def _same(a, b):
     for f in ("x", "y", "size", "resp", "cls", "octave"):
         assert np.array_equal(getattr(a, f)[:n], getattr(b, f)[:n]), f
     assert np.array_equal(R.upper_filter(a), R.upper_filter(b))
-
-
-def _scan_order(cands):
-    return sorted(cands, key=lambda c: (c[0], c[1], c[2]))
-
-
-def _random_list(rng, levels, n_levels, n_clusters, per_cluster, spread):
-    cands = {}
-    for i in range(n_levels):
-        lv = levels[i]
-        for _ in range(n_clusters):
-            cx, cy = rng.uniform(0.1 * lv["w"], 0.9 * lv["w"]), rng.uniform(0.1 * lv["h"], 0.9 * lv["h"])      # (some near the border: out)
-            for _ in range(per_cluster):
-                col = int(np.clip(round(cx + rng.normal(0, spread)), 1, lv["w"] - 2))
-                row = int(np.clip(round(cy + rng.normal(0, spread)), 1, lv["h"] - 2))
-                cands[(i, row, col)] = float(rng.choice([rng.uniform(0.001, 0.01), 0.005]))    # ties among the responses too
-    return _scan_order([(i, r, c, v) for (i, r, c), v in cands.items()])
 
 
 @pytest.mark.parametrize("seed", range(8))
