@@ -92,7 +92,11 @@ public:
 
     void addViews(const std::vector<View>& views);                 // stands in for addImages + sfm_data.bin
     void clearViews() { views_.clear(); }                            // a kept-alive stage object between two collections
-    void setRegionsType(r3dm_dtype dtype, uint32_t dim);           // default: float x 144 (R3D_AKAZE_LIOP_Regions)
+    // default: float x 144 (R3D_AKAZE_LIOP_Regions).  The regions type also chooses what the features stage computes from pixels:
+    // (R3DM_F32, 144) LIOP, what Regard3D computes; (R3DM_BIN, 61) the MLDB-486 rows of the Fast-AKAZE detector (r3dm_set_descriptor_arm:
+    // no reference counterpart, BASELINE config C3), matched by the binary rules (unsquared ratio, exhaustive matcher, Hamming fast path);
+    // with any other type views must come with their .feat / .desc
+    void setRegionsType(r3dm_dtype dtype, uint32_t dim);
     void setSeed(uint64_t seed) { seed_ = seed; }
     // The exhaustive matcher's exact MFMA fast paths: split-f16 nomination for real-valued descriptors (LIOP-144, what Regard3D matches:
     // 2.9x), bf16 tiles for integer-valued ones (SIFT bins: 7.9x) and i8 tiles for binary ones (A-KAZE MLDB: 3.0x, exact integers).  Both nominate candidates on narrow tiles and then compute the
@@ -176,6 +180,7 @@ public:
         double match_post = 0;                                                      // of `match`: everything behind the nomination kernel (exact scan of uncertified queries, finalisation, copy back)
         double filters_wall = 0;                                                    // F + E + H together: they run side by side on one device (r3dm_filter_FEH), so filter_F / _E / _H overlap
         uint64_t images_extracted = 0;
+        int descriptor_arm = R3DM_DESCRIPTOR_LIOP;                                   // what the features stage of this call describes keypoints with (setRegionsType)
         r3dm_features_totals features_totals{};                                      // summed over the contexts of the features stage
     };
     const PhaseTimes& getPhaseTimes() const { return phases_; }
@@ -245,6 +250,7 @@ typedef struct {
     uint64_t n_putative_pairs, n_putative_matches, n_F_pairs, n_F_matches, n_E_pairs, n_E_matches, n_H_pairs, n_H_matches;
     uint64_t match_was_exhaustive;   /* 1: the exhaustive matcher ran (arm 4 / 9, or an approximate arm routed to it) */
     r3dm_features_totals features;
+    uint64_t descriptor_arm;         /* R3DM_DESCRIPTOR_LIOP or R3DM_DESCRIPTOR_MLDB: the descriptor arm of the features stage of this call */
 } r3dm_stage_report;
 int r3dm_compute_matches_stage(const int* device_ids, int n_devices, const char* matches_dir, const r3dm_view_image* views, uint32_t n_views,
                                float threshold, float dist_ratio, int matching_algorithm, int compute_F, int compute_E, int compute_H,
@@ -269,6 +275,7 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_GUIDED_MATCHING  32u   /* bGuided_matching = true (R3DComputeMatches::setGuidedMatching(true)): the filters' match files hold guided lists */
 #define R3DM_STAGE_DETECTOR_AKAZE   64u   /* keypointDetectorList_ = {"AKAZE"}, the GUI's keypointDetectorType 0 (classic A-KAZE); default {"Fast-AKAZE"} */
 #define R3DM_STAGE_MUTUAL_MATCHING 128u   /* mutual nearest-neighbour matching (R3DComputeMatches::setMutualMatching(true), r3dm_set_mutual_matching); default: every query's match is kept */
+#define R3DM_STAGE_DESCRIPTOR_MLDB 512u   /* setRegionsType(R3DM_BIN, 61): the features stage writes MLDB-486 rows (r3dm_set_descriptor_arm), the matcher runs its binary rules; default LIOP (float x 144) */
 #define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,

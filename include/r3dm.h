@@ -596,6 +596,15 @@ int r3dm_detect_akaze_batch(r3dm_ctx* ctx, uint32_t n_images, const float* const
 int r3dm_detect_akaze_mldb(r3dm_ctx* ctx, const float* image, uint32_t width, uint32_t height, float threshold,
                            float* keypoints_out, unsigned char* descriptors_out, uint32_t cap, uint32_t* n_out);
 
+/* The same over a BATCH of n_images same-size images: one pass of the detector (r3dm_detect_akaze_batch), then ONE MLDB launch over the
+ * keypoints of all images (a keypoint names its evolution level as image x levels + level; the level planes of every image stay on
+ * the device until the launch).  keypoints_out[b]: cap x 4 floats, descriptors_out[b]: cap x 61 bytes; min(count, cap) rows are written
+ * per image, n_out[b] = number detected (may exceed cap).  Results per image are bit-identical to r3dm_detect_akaze_mldb on that
+ * image, for any n_images, images without keypoints included. */
+int r3dm_detect_akaze_mldb_batch(r3dm_ctx* ctx, uint32_t n_images, const float* const* images, uint32_t width, uint32_t height,
+                                 float threshold, float* const* keypoints_out, unsigned char* const* descriptors_out, uint32_t cap,
+                                 uint32_t* n_out);
+
 /* ---- keypoint detection: classic A-KAZE ----
  * The "AKAZE" arm of Regard3DFeatures::detectKeypoints (src/Regard3DFeatures.cpp:578-589), the GUI's default detector:
  * cv::AKAZE::create(DESCRIPTOR_MLDB, 0, 3, threshold, 4, 4, DIFF_PM_G2) + detect(), restated as libAKAZE, the classic code of the
@@ -628,12 +637,25 @@ int r3dm_akaze_classic_components(const r3dm_ctx* ctx, uint64_t* hist);
 #define R3DM_DETECTOR_AKAZE 1
 int r3dm_set_keypoint_detector(r3dm_ctx* ctx, int arm);
 
+/* The descriptor arm of the same features entries.  R3DM_DESCRIPTOR_LIOP (the default) is what Regard3D computes: LIOP, 144 floats per
+ * keypoint.  R3DM_DESCRIPTOR_MLDB is the second descriptor of the vendored Fast-A-KAZE, which Regard3D itself never computes: the full
+ * MLDB-486 of r3dm_detect_akaze_mldb, for BASELINE config C3 (binary rows, Hamming brute force) from photographs.  Under it the .feat
+ * of an image is byte for byte the one the LIOP arm writes (same detector, same angle conversion, same text) and its .desc is the
+ * 8-byte count followed by count x 61 bytes (KeypointSet::saveToBinFile with Descriptor<unsigned char, 61>) -- what the facade reads
+ * under setRegionsType(R3DM_BIN, 61).  Skip rule, sink, deferred files and scheduling are shared.  MLDB needs the Fast arm's level
+ * planes: together with R3DM_DETECTOR_AKAZE a features call returns R3DM_ERR_UNSUPPORTED (r3dm_last_error names the arm), computes
+ * nothing and leaves both switches as they are.  Other values: R3DM_ERR_INVALID. */
+#define R3DM_DESCRIPTOR_LIOP 0
+#define R3DM_DESCRIPTOR_MLDB 1
+int r3dm_set_descriptor_arm(r3dm_ctx* ctx, int arm);
+
 /* ---- the per-image work item of the features stage ----
  * R3DFeaturesThread::processWorkItem (src/threads/R3DFeaturesThread.cpp:123-210) after cv::imread: 8-bit BGR -> float / 255 ->
  * BGR2GRAY (r3dm_gray_from_bgr8; bgr = height x width x 3 bytes, gray_out = height x width floats, host or device), then
  * Regard3DFeatures::detectAndExtract with the "Fast-AKAZE" detector + LIOP and KeypointSet::saveToBinFile
  * (src/keypointSet.hpp:61-67): <feat_path> gets one "x y scale orientation" line per feature (scale = size / 2), <desc_path>
- * an 8-byte count followed by count x 144 floats -- the files r3dm_compute_matches_dir / the facade read back.
+ * an 8-byte count followed by count x 144 floats -- the files r3dm_compute_matches_dir / the facade read back.  (Under
+ * R3DM_DESCRIPTOR_MLDB: count x 61 bytes, r3dm_set_descriptor_arm.)
  * As in the reference (:139-142) the work item does nothing when BOTH files already exist (n_features = rows of the existing .desc).
  * Image decoding (cv::imread) stays with the caller. */
 int r3dm_gray_from_bgr8(r3dm_ctx* ctx, const unsigned char* bgr, uint32_t width, uint32_t height, float* gray_out);
@@ -730,6 +752,8 @@ int r3dm_multi_filter_E(r3dm_multi* m, const r3dm_graph* putative, double max_re
 int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H);
 /* r3dm_set_keypoint_detector on every device context: the arm of r3dm_multi_extract_features and _ex */
 int r3dm_multi_set_keypoint_detector(r3dm_multi* m, int arm);
+/* r3dm_set_descriptor_arm on every device context: what r3dm_multi_extract_features and _ex describe the keypoints with */
+int r3dm_multi_set_descriptor_arm(r3dm_multi* m, int arm);
 /* The features stage over an image list: R3DFeaturesThread::extractFeaturesAndDescriptors (src/threads/R3DFeaturesThread.cpp:38-121),
  * whose worker pool pulls images off a work list and runs processWorkItem on each.  Here every context of `m` is a worker that pulls
  * BATCHES of same-size images (r3dm_extract_features_batch: up to 8 per detector pass): create
@@ -859,7 +883,7 @@ typedef struct {
     double   ms_wall_match;        /* whole r3dm_match_pairs call                                   */
     double   ms_wall_match_post;   /* of which: exact scans + finalisation + copies back + assembly */
     double   ms_wall_filter;       /* whole r3dm_filter_F call                                      */
-    double   ms_liop_kernel;       /* HIP-event time of the last r3dm_liop_describe_patches kernel  */
+    double   ms_liop_kernel;       /* HIP-event time of the last r3dm_liop_describe_patches kernel (a features pass under R3DM_DESCRIPTOR_MLDB: of its MLDB launch) */
     /* r3dm_match_pairs_kgraph */
     double   ms_ann_build;         /* HIP-event time of the index builds triggered by the call      */
     double   ms_ann_search;        /* HIP-event time of the search kernel                           */
@@ -877,7 +901,7 @@ typedef struct {
     /* the last detector pass (r3dm_detect_akaze*, r3dm_extract_features_*) */
     double   ms_detect_kernels;    /* HIP-event time from the first scale-space launch to the keypoint compaction, all images of the pass */
     double   detect_algorithmic_bytes; /* HBM bytes the pass structure implies: every stencil pass reads / writes whole image planes once */
-    double   ms_liop_wall;         /* host + device time of the LIOP half of the last features pass (patch maps, two launches, copy back) */
+    double   ms_liop_wall;         /* host + device time of the LIOP half of the last features pass (patch maps, two launches, copy back); under R3DM_DESCRIPTOR_MLDB: of the MLDB half */
     double   ms_feature_files;     /* time spent writing the .feat / .desc files of the last features pass                              */
     /* r3dm_match_pairs_hnsw (ms_ann_build / ms_ann_search / n_ann_built / n_ann_dist are shared with the KGraph path) */
     uint64_t n_hnsw_launches;      /* launches of the HNSW search kernel                                                                */
@@ -908,7 +932,7 @@ typedef struct {
     uint64_t n_regrows;                /* detection phases repeated because an image had more candidates than slots            */
     double   ms_detect_kernels;        /* HIP-event time, first scale-space launch .. keypoint compaction                      */
     double   detect_algorithmic_bytes; /* HBM bytes the pass structure implies (every stencil pass moves whole planes once)    */
-    double   ms_liop_kernels;          /* HIP-event time of the LIOP patch extraction + descriptor launches                     */
+    double   ms_liop_kernels;          /* HIP-event time of the LIOP patch extraction + descriptor launches (+ the MLDB launches of passes under R3DM_DESCRIPTOR_MLDB) */
     double   ms_wall;                  /* wall time inside the features entry points (detector + LIOP + copies + files)        */
     double   ms_files;                 /* of which: writing .feat / .desc                                                      */
 } r3dm_features_totals;
@@ -921,7 +945,8 @@ int r3dm_host_threads(int want);
 /* A sink for the features entry points (r3dm_extract_features_batch, r3dm_multi_extract_features*): called once per COMPUTED image
  * (not for skipped ones), from a helper thread of the library (several images of a batch may arrive concurrently: the sink must be
  * thread-safe), after the image's two files are written.  desc_device = n_features x 144 floats
- * in DEVICE memory of the computing context (valid until the sink returns); xy_as_written = n_features x 2 floats exactly as a reader
+ * in DEVICE memory of the computing context (valid until the sink returns) -- under R3DM_DESCRIPTOR_MLDB it points at n_features x 61
+ * BYTES there instead (the type of the argument stays; r3dm_set_image(dim 61, R3DM_BIN) takes the pointer as it is); xy_as_written = n_features x 2 floats exactly as a reader
  * of the .feat file parses them (the file holds 6 significant digits).  What Regions_Provider::load would read back from the files
  * (src/R3DComputeMatches.cpp:2040) is thus handed over without the round trip through the file system and the PCIe bus: the facade
  * registers the view with the matcher straight from it (r3dm_set_image accepts device pointers).  image_index = the index in the

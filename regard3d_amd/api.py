@@ -46,20 +46,29 @@ EXPORTS = [
     "r3dm_multi_set_view_priority", "r3dm_multi_set_preemptive_matching",
     "r3dm_build_tracks", "r3dm_tracks_count", "r3dm_tracks_offsets", "r3dm_tracks_observations", "r3dm_tracks_report", "r3dm_tracks_phase_ms", "r3dm_tracks_in_pair",
     "r3dm_tracks_free",
+    "r3dm_detect_akaze_mldb_batch", "r3dm_set_descriptor_arm", "r3dm_multi_set_descriptor_arm",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
 STAGE_DETECTOR_AKAZE = 64
 STAGE_MUTUAL_MATCHING = 128
 STAGE_PREEMPTIVE_MATCHING = 256
+STAGE_DESCRIPTOR_MLDB = 512
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
+DESCRIPTORS = {"LIOP": 0, "MLDB": 1}             # R3DM_DESCRIPTOR_LIOP / R3DM_DESCRIPTOR_MLDB
 
 
 def _detector_flag(detector: str) -> int:
     if detector not in DETECTORS:
         raise ValueError(f"detector must be one of {sorted(DETECTORS)}, not {detector!r}")
     return STAGE_DETECTOR_AKAZE if detector == "AKAZE" else 0
+
+
+def _descriptor_flag(descriptor: str) -> int:
+    if descriptor not in DESCRIPTORS:
+        raise ValueError(f"descriptor must be one of {sorted(DESCRIPTORS)}, not {descriptor!r}")
+    return STAGE_DESCRIPTOR_MLDB if descriptor == "MLDB" else 0
 
 
 class R3dmError(RuntimeError):
@@ -138,7 +147,8 @@ class StageReport(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("ms_features", "ms_load", "ms_match", "ms_filter_F", "ms_filter_E", "ms_filter_H", "ms_files", "ms_total",
                                           "ms_match_kernels", "ms_F_kernels", "ms_E_kernels", "ms_H_kernels", "ms_filters_wall", "ms_match_post")] + \
                [(k, C.c_uint64) for k in ("images_extracted", "n_keypoints", "n_putative_pairs", "n_putative_matches", "n_F_pairs", "n_F_matches",
-                                          "n_E_pairs", "n_E_matches", "n_H_pairs", "n_H_matches", "match_was_exhaustive")] + [("features", FeaturesTotals)]
+                                          "n_E_pairs", "n_E_matches", "n_H_pairs", "n_H_matches", "match_was_exhaustive")] + [("features", FeaturesTotals)] + \
+               [("descriptor_arm", C.c_uint64)]          # DESCRIPTORS value: what the features stage of the call describes keypoints with
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "features"}
@@ -185,11 +195,11 @@ class Stage:
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False) -> StageReport:
+            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP") -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
         (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING); preemptive: preemptive matching at 128 / 4
-        (R3DM_STAGE_PREEMPTIVE_MATCHING)"""
-        dflag = _detector_flag(detector)
+        (R3DM_STAGE_PREEMPTIVE_MATCHING); descriptor: "LIOP" or "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB: binary regions, 61 bytes)"""
+        dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
         keep = []
         arr = _stage_views(views, keep)
         rep = StageReport(); err = C.create_string_buffer(1024)
@@ -217,13 +227,14 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False) -> StageReport:
+                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP") -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
     detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE); mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive:
-    R3DM_STAGE_PREEMPTIVE_MATCHING (head_rows 128, min_matches 4)."""
-    dflag = _detector_flag(detector)
+    R3DM_STAGE_PREEMPTIVE_MATCHING (head_rows 128, min_matches 4); descriptor: "LIOP" (default) or "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB:
+    the features stage writes MLDB-486 rows, the matcher runs its binary rules)."""
+    dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
     L = load_library()
     keep = []
     arr = _stage_views(views, keep)
@@ -387,6 +398,8 @@ def load_library():
     L.r3dm_multi_set_guided_matching.argtypes = [vp, C.c_int, C.c_double, C.c_double, C.c_double]
     L.r3dm_set_keypoint_detector.argtypes = [vp, C.c_int]
     L.r3dm_multi_set_keypoint_detector.argtypes = [vp, C.c_int]
+    L.r3dm_set_descriptor_arm.argtypes = [vp, C.c_int]
+    L.r3dm_multi_set_descriptor_arm.argtypes = [vp, C.c_int]
     L.r3dm_akaze_classic_components.argtypes = [vp, vp]
     L.r3dm_liop_describe_patches.argtypes = [vp, vp, u32, u32, vp, C.POINTER(u32)]
     L.r3dm_extract_liop.argtypes = [vp, vp, u32, u32, vp, u32, C.c_float, vp, vp]
@@ -401,6 +414,7 @@ def load_library():
     L.r3dm_multi_extract_features_ex.argtypes = [vp, u32, vp, vp, vp, vp, C.c_float, vp, vp, vp, vp, u32, C.c_char_p, C.c_size_t]
     L.r3dm_get_features_totals.argtypes = [vp, vp]
     L.r3dm_detect_akaze_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
+    L.r3dm_detect_akaze_mldb_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
     L.r3dm_detect_akaze_classic.argtypes = [vp, vp, u32, u32, C.c_float, vp, vp, u32, C.POINTER(u32)]
     L.r3dm_detect_akaze_classic_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
     L.r3dm_extract_features_batch.argtypes = [vp, u32, vp, vp, u32, u32, C.c_float, vp, vp, vp]
@@ -1204,6 +1218,12 @@ class Context:
         _detector_flag(detector)
         self._check(self._L.r3dm_set_keypoint_detector(self._h, DETECTORS[detector]), "r3dm_set_keypoint_detector")
 
+    def set_descriptor_arm(self, descriptor: str = "LIOP"):
+        """r3dm_set_descriptor_arm: what the features entries describe the keypoints with, "LIOP" (default: .desc rows of 144 floats) or
+        "MLDB" (the Fast-AKAZE detector's MLDB-486: .desc rows of 61 bytes)"""
+        _descriptor_flag(descriptor)
+        self._check(self._L.r3dm_set_descriptor_arm(self._h, DESCRIPTORS[descriptor]), "r3dm_set_descriptor_arm")
+
     def akaze_classic_components(self) -> np.ndarray:
         """r3dm_akaze_classic_components: [32] component-size histogram of the classic arm's kpts_aux walk since creation
         (bin k: components of 2^k .. 2^(k+1) - 1 candidates)"""
@@ -1357,6 +1377,19 @@ class Context:
         n = np.zeros(B, np.uint32)
         self._check(self._L.r3dm_detect_akaze_batch(self._h, B, ip, w, h, threshold, kp_p, rp_p, cap, _ptr(n)), "r3dm_detect_akaze_batch")
         return [(kps[b][:min(int(n[b]), cap)].copy(), resp[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
+
+    def detect_akaze_mldb_batch(self, images, threshold: float = 0.001, cap: int = 200000):
+        """r3dm_detect_akaze_mldb_batch: B same-size images in one pass of the detector and ONE MLDB launch
+        -> list of (keypoints [n, 4], descriptors [n, 61] uint8)"""
+        imgs = [im if hasattr(im, "data_ptr") else np.ascontiguousarray(im, np.float32) for im in images]
+        B = len(imgs); h, w = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+        assert all(tuple(im.shape) == (h, w) for im in imgs), "a batch holds images of one size"
+        ip = (C.c_void_p * B)(*[(im.data_ptr() if hasattr(im, "data_ptr") else im.ctypes.data) for im in imgs])
+        kps = [np.zeros((cap, 4), np.float32) for _ in range(B)]; desc = [np.zeros((cap, 61), np.uint8) for _ in range(B)]
+        kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); dp_p = (C.c_void_p * B)(*[d.ctypes.data for d in desc])
+        n = np.zeros(B, np.uint32)
+        self._check(self._L.r3dm_detect_akaze_mldb_batch(self._h, B, ip, w, h, threshold, kp_p, dp_p, cap, _ptr(n)), "r3dm_detect_akaze_mldb_batch")
+        return [(kps[b][:min(int(n[b]), cap)].copy(), desc[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
 
     def detect_akaze_classic(self, image, threshold: float = 0.001, cap: int = 200000):
         """r3dm_detect_akaze_classic, Regard3D's "AKAZE" arm (libAKAZE): image [h, w] float32 in [0, 1] (numpy or torch, host or device)
@@ -1535,6 +1568,11 @@ class MultiContext:
         """r3dm_multi_set_keypoint_detector: the arm of extract_features on every context ("Fast-AKAZE" or "AKAZE")"""
         _detector_flag(detector)
         self._check(self._L.r3dm_multi_set_keypoint_detector(self._h, DETECTORS[detector]), "r3dm_multi_set_keypoint_detector")
+
+    def set_descriptor_arm(self, descriptor: str = "LIOP"):
+        """r3dm_multi_set_descriptor_arm: what extract_features describes the keypoints with on every context ("LIOP" or "MLDB")"""
+        _descriptor_flag(descriptor)
+        self._check(self._L.r3dm_multi_set_descriptor_arm(self._h, DESCRIPTORS[descriptor]), "r3dm_multi_set_descriptor_arm")
 
     def extract_features(self, images, feat_paths, desc_paths, threshold: float = 0.001, bgr: bool = False, batch: int = 0):
         """r3dm_multi_extract_features(_bgr8): the features stage over an image list, one BATCH of same-size images in flight per context.

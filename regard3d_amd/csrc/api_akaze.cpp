@@ -559,18 +559,40 @@ int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     return R3DM_OK;
 }
 
-// Get_MLDB_Full_Descriptor of the first min(count, cap) keypoints of image 0: level coordinates, cos / sin of the raw (radian) angle
-static int ak_mldb_describe(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, unsigned char* mldb_out)
+// Get_MLDB_Full_Descriptor of the first min(count, cap) keypoints of every image of the pass, in ONE launch: level coordinates, cos / sin of
+// the raw (radian) angle (host libm, as the oracle and the LIOP patch map: device trigonometry is not bit-equal to it).  An item names
+// its level as image * n_levels + level: the level table the detector left on the device (ak_levels_dev) and the Lt / Lx / Ly planes of
+// its work buffers cover the B images of the pass until the next pass.  The rows of image b follow those of image b - 1, 61 bytes
+// apart -- the layout r3dm_set_image(dim 61, R3DM_BIN) reads from a device pointer, so a consumer on the device takes image b's rows
+// where the kernel stored them, at rows_dev + 61 first[b]; nothing is copied.  first (B + 1 entries): row offsets per image.
+// rows_dev stays valid until this context's next detector or MLDB pass.  The launch is bracketed by ev0 / ev1 and waited for.
+// host_team: the threads that share the item loop (three libm calls per keypoint: 229 k keypoints of eight 12 Mpx images on one thread
+// took longer than the detector's kernels), in chunks of 4,096 keypoints over all images as the features batch forms its angles.
+int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev)
 {
-    const std::vector<AkKpRec>& recs = det.fast[0];
+    const uint32_t B = (uint32_t)det.fast.size();
     const std::vector<AkLevelHost>& lv = det.fast_levels;
-    std::vector<AkMldbItem> items;
-    for (uint32_t k = 0; k < recs.size() && k < cap; ++k) {
-        const AkKpRec& r = recs[k];
-        const float theta = ak_theta(r);
-        items.push_back({r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (float)lv[r.level].sigma_size});
-    }
-    if (items.empty()) return R3DM_OK;
+    const uint32_t nl = (uint32_t)lv.size();
+    first.assign((size_t)B + 1, 0);
+    for (uint32_t b = 0; b < B; ++b) first[b + 1] = first[b] + std::min<size_t>(det.fast[b].size(), cap);
+    *rows_dev = nullptr;
+    const size_t ni = first[B];
+    if (ni == 0) return R3DM_OK;
+    if (ni >= (1ull << 31)) { c->err = "MLDB: more than 2^31 keypoints in one pass"; return R3DM_ERR_UNSUPPORTED; }
+    std::vector<AkMldbItem> items(ni);
+    struct Chunk { uint32_t b; size_t k0, k1; };
+    std::vector<Chunk> chunks;
+    for (uint32_t b = 0; b < B; ++b)
+        for (size_t k0 = 0, nk = first[b + 1] - first[b]; k0 < nk; k0 += 4096) chunks.push_back({b, k0, std::min(nk, k0 + 4096)});
+    r3dm_parallel_for((long)chunks.size(), host_team, [&](long ci) {
+        const Chunk& ch = chunks[(size_t)ci];
+        const std::vector<AkKpRec>& recs = det.fast[ch.b];
+        for (size_t k = ch.k0; k < ch.k1; ++k) {
+            const AkKpRec& r = recs[k];
+            const float theta = ak_theta(r);
+            items[first[ch.b] + k] = {ch.b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (float)lv[r.level].sigma_size};
+        }
+    });
     // comparison table of MLDB_Binary_Comparisons: per grid, per channel, all value pairs i < j
     std::vector<unsigned char> pairs;
     const int bases[3] = {0, 12, 39}, cnts[3] = {4, 9, 16};
@@ -580,16 +602,38 @@ static int ak_mldb_describe(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap,
                 for (int j = i + 1; j < cnts[g]; ++j) { pairs.push_back((unsigned char)(bases[g] + 3 * i + pos)); pairs.push_back((unsigned char)(bases[g] + 3 * j + pos)); }
     hipStream_t st = c->stream;
     DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_MLDB];
-    const size_t ni = items.size();
     R3DM_HIP(c, mb.ensure(ni * sizeof(AkMldbItem) + 1024 + ni * 61 + 64));
     unsigned char* base = mb.as<unsigned char>();
     R3DM_HIP(c, hipMemcpyAsync(base, items.data(), ni * sizeof(AkMldbItem), hipMemcpyHostToDevice, st));
     R3DM_HIP(c, hipMemcpyAsync(base + ni * sizeof(AkMldbItem), pairs.data(), pairs.size(), hipMemcpyHostToDevice, st));
     unsigned char* d_out = base + ni * sizeof(AkMldbItem) + 1024;
+    R3DM_HIP(c, hipEventRecord(c->ev0, st));
     R3DM_HIP(c, ak_mldb(st, c->ak_levels_dev, (const AkMldbItem*)base, (uint32_t)ni, base + ni * sizeof(AkMldbItem), d_out));
-    R3DM_HIP(c, hipMemcpyAsync(mldb_out, d_out, ni * 61, hipMemcpyDeviceToHost, st));
-    R3DM_HIP(c, hipStreamSynchronize(st));
+    R3DM_HIP(c, hipEventRecord(c->ev1, st));
+    R3DM_HIP(c, hipStreamSynchronize(st));                                // `items` and `pairs` leave scope
+    *rows_dev = d_out;
     return R3DM_OK;
+}
+
+// the detect entry of the MLDB forms: the keypoints through detect_entry, then min(count, cap) rows per image from the one MLDB pass
+static int ak_mldb_entry(r3dm_ctx* c, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
+                         float* const* keypoints_out, unsigned char* const* descriptors_out, uint32_t cap, uint32_t* n_out)
+{
+    if (cap && !descriptors_out) return R3DM_ERR_INVALID;
+    if (cap && images && B <= 4096) for (uint32_t b = 0; b < B; ++b) if (!descriptors_out[b] || (keypoints_out && !keypoints_out[b])) return R3DM_ERR_INVALID;
+    DetectedBatch det;
+    int rc = detect_entry(c, ak_detect_batch, single, B, images, width, height, threshold, keypoints_out, nullptr, cap, n_out, det);
+    if (rc != R3DM_OK) return rc;
+    std::vector<size_t> first;
+    const unsigned char* rows = nullptr;
+    rc = ak_mldb_pass(c, det, cap, r3dm_host_team(8), first, &rows);
+    for (uint32_t b = 0; rc == R3DM_OK && b < B; ++b) {
+        const size_t nb = first[b + 1] - first[b];
+        if (nb && hipMemcpyAsync(descriptors_out[b], rows + 61 * first[b], nb * 61, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { c->err = "MLDB: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
+    }
+    if (rc == R3DM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "MLDB: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
+    if (rc != R3DM_OK) for (uint32_t b = 0; b < B; ++b) n_out[b] = 0;
+    return rc;
 }
 
 extern "C" int r3dm_detect_akaze(r3dm_ctx* c, const float* image, uint32_t width, uint32_t height, float threshold,
@@ -605,11 +649,18 @@ extern "C" int r3dm_detect_akaze_mldb(r3dm_ctx* c, const float* image, uint32_t 
                                       float* keypoints_out, unsigned char* descriptors_out, uint32_t cap, uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        if (!descriptors_out && cap) return R3DM_ERR_INVALID;
-        DetectedBatch det;
-        int rc = detect_entry(c, ak_detect_batch, true, 1, &image, width, height, threshold, &keypoints_out, nullptr, cap, n_out, det);
-        if (rc == R3DM_OK && (rc = ak_mldb_describe(c, det, cap, descriptors_out)) != R3DM_OK) *n_out = 0;
-        return rc;
+        return ak_mldb_entry(c, true, 1, &image, width, height, threshold, &keypoints_out, &descriptors_out, cap, n_out);
+    });
+}
+
+// B same-size images in one pass of the detector, then one MLDB launch over the keypoints of all of them.  descriptors_out[b]: cap x 61
+// bytes; min(count, cap) rows are written per image, n_out[b] reports the count.
+extern "C" int r3dm_detect_akaze_mldb_batch(r3dm_ctx* c, uint32_t n_images, const float* const* images, uint32_t width, uint32_t height,
+                                            float threshold, float* const* keypoints_out, unsigned char* const* descriptors_out, uint32_t cap,
+                                            uint32_t* n_out)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        return ak_mldb_entry(c, false, n_images, images, width, height, threshold, keypoints_out, descriptors_out, cap, n_out);
     });
 }
 

@@ -1,7 +1,8 @@
 // api_features.cpp -- part of the host side of libr3dm.so (see r3dm_ctx.hpp for the file map): the features work item of
 // src/threads/R3DFeaturesThread.cpp and src/Regard3DFeatures.cpp.  The .feat / .desc files; the features batch in its phases -- detect
-// (api_akaze.cpp, whichever arm) -> keypoints and patch maps (host team) -> one LIOP pass (api_liop.cpp) -> delivery (files + sink, at
-// once or deferred to the context's writer thread) -> outputs and totals; the work list over a multi-context; the setters of all this.
+// (api_akaze.cpp, whichever arm) -> keypoints and patch maps (host team) -> one descriptor pass chosen by the context's descriptor arm:
+// LIOP (api_liop.cpp) or MLDB-486 (api_akaze.cpp) -> delivery (files + sink, at once or deferred to the context's writer thread) ->
+// outputs and totals; the work list over a multi-context; the setters of all this.
 // There is no CPU fallback in this file: when HIP fails, the call fails.
 #include "fmt_g6.hpp"
 #include "r3dm_ctx.hpp"
@@ -36,8 +37,9 @@ static size_t format_feat(std::vector<char>& txt, const float* kps, uint32_t n, 
     return (size_t)(p - txt.data());
 }
 
-// one image on its way to its files: the text of its .feat, its rows (in pin_desc), its two paths, the positions for the sink
-struct FeatJob { std::string feat, desc; std::vector<char> txt; size_t len = 0; const float* rows = nullptr; uint32_t n = 0; std::vector<float> xy; };
+// one image on its way to its files: the text of its .feat, its rows (in pin_desc, row_bytes each: 144 floats of LIOP or 61 bytes of
+// MLDB), its two paths, the positions for the sink
+struct FeatJob { std::string feat, desc; std::vector<char> txt; size_t len = 0; const unsigned char* rows = nullptr; size_t row_bytes = 0; uint32_t n = 0; std::vector<float> xy; };
 
 static int write_feat_desc_files(std::string& err, const FeatJob& j)
 {
@@ -49,7 +51,7 @@ static int write_feat_desc_files(std::string& err, const FeatJob& j)
     f = fopen(j.desc.c_str(), "wb");
     if (!f) { err = "cannot write " + j.desc; return R3DM_ERR_IO; }
     const uint64_t cnt = j.n;
-    ok = fwrite(&cnt, 8, 1, f) == 1 && (j.n == 0 || fwrite(j.rows, 144 * 4, j.n, f) == j.n);
+    ok = fwrite(&cnt, 8, 1, f) == 1 && (j.n == 0 || fwrite(j.rows, j.row_bytes, j.n, f) == j.n);
     ok = (fclose(f) == 0) && ok;
     if (!ok) { err = "cannot write " + j.desc; return R3DM_ERR_IO; }
     return R3DM_OK;
@@ -89,14 +91,25 @@ struct BatchKeypoints {
     size_t total() const { return img_of.size(); }
 };
 
-// phase 2: angle (the Fast arm's: atan2f of the host libm, as the reference) and LIOP patch map of every keypoint; a few host threads
-// share the loop, in chunks of 4,096 keypoints over all images of the batch
-void keypoints_and_maps(const DetectedBatch& det, uint32_t B, int host_team, BatchKeypoints& K)
+// the descriptor rows of a batch where the descriptor pass left them on the device: image b's are at dev + row_bytes first[b]
+struct BatchRows { const unsigned char* dev = nullptr; size_t row_bytes = 0; };
+
+// what the context's two switches cannot do together (r3dm_set_descriptor_arm): refused before anything is computed
+int descriptor_arm_check(r3dm_ctx* c)
+{
+    if (c->descriptor_arm != R3DM_DESCRIPTOR_MLDB || c->detector_arm != R3DM_DETECTOR_AKAZE) return R3DM_OK;
+    c->err = "descriptor arm R3DM_DESCRIPTOR_MLDB is not served with the classic detector R3DM_DETECTOR_AKAZE (MLDB reads the Fast-A-KAZE level planes)";
+    return R3DM_ERR_UNSUPPORTED;
+}
+
+// phase 2: angle (the Fast arm's: atan2f of the host libm, as the reference) and, with want_maps (the LIOP arm), LIOP patch map of every
+// keypoint; a few host threads share the loop, in chunks of 4,096 keypoints over all images of the batch
+void keypoints_and_maps(const DetectedBatch& det, uint32_t B, int host_team, bool want_maps, BatchKeypoints& K)
 {
     K.first.assign(B + 1, 0);
     for (uint32_t b = 0; b < B; ++b) K.first[b + 1] = K.first[b] + det.count(b);
     const size_t n_total = K.first[B];
-    K.kps.resize(4 * n_total); K.M6.resize(6 * n_total); K.img_of.resize(n_total);
+    K.kps.resize(4 * n_total); K.M6.resize(want_maps ? 6 * n_total : 0); K.img_of.resize(n_total);
     struct Chunk { uint32_t b; long k0, k1; };
     std::vector<Chunk> chunks;
     for (uint32_t b = 0; b < B; ++b) {
@@ -109,22 +122,32 @@ void keypoints_and_maps(const DetectedBatch& det, uint32_t B, int host_team, Bat
             const size_t g = K.first[ch.b] + (size_t)k;
             float* o = &K.kps[4 * g];
             det.keypoint(ch.b, (size_t)k, o);
-            liop_patch_map(o[0], o[1], o[2], o[3], 8.0f /* getKpSizeFactor("AKAZE" / "Fast-AKAZE"), :703-704 */, &K.M6[6 * g]);
+            if (want_maps) liop_patch_map(o[0], o[1], o[2], o[3], 8.0f /* getKpSizeFactor("AKAZE" / "Fast-AKAZE"), :703-704 */, &K.M6[6 * g]);
             K.img_of[g] = ch.b;
         }
     });
 }
 
-// phase 3: one LIOP pass over the keypoints of ALL images, on the gray planes the detector left on the device; the descriptors go to
-// page-locked host memory.  Immediately: waited for.  Deferred: they travel behind the kernel, only the writer thread waits (ev_desc)
-int describe_batch(r3dm_ctx* c, const DetectedBatch& det, uint32_t width, uint32_t height, const BatchKeypoints& K, bool deferred)
+// phase 3: one descriptor pass over the keypoints of ALL images -- LIOP on the gray planes, or MLDB on the level planes, that the detector
+// left on the device; the rows stay there for the sink (`rows`) and go to page-locked host memory for the files.  Immediately: waited
+// for.  Deferred: they travel behind the kernel, only the writer thread waits (ev_desc)
+int describe_batch(r3dm_ctx* c, const DetectedBatch& det, uint32_t width, uint32_t height, const BatchKeypoints& K, bool deferred, int host_team, BatchRows& rows)
 {
-    const size_t out_bytes = K.total() * 144 * 4;
+    const bool mldb = c->descriptor_arm == R3DM_DESCRIPTOR_MLDB;
+    rows.row_bytes = mldb ? 61 : 144 * 4;
+    const size_t out_bytes = K.total() * rows.row_bytes;
     { const int wrc_prev = features_files_join(c); if (wrc_prev != R3DM_OK) return wrc_prev; }      // the previous batch's writer still reads pin_desc
     R3DM_HIP(c, c->pin_desc.ensure(out_bytes));
-    const int rc = liop_pass(c, det.grays_dev, width, height, K.M6.data(), K.img_of.data(), (uint32_t)K.total(), false);
-    if (rc != R3DM_OK) return rc;
-    R3DM_HIP(c, hipMemcpyAsync(c->pin_desc.p, c->liop_out.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (mldb) {
+        std::vector<size_t> first;
+        const int rc = ak_mldb_pass(c, det, 0xFFFFFFFFu, host_team, first, &rows.dev);
+        if (rc != R3DM_OK) return rc;
+    } else {
+        const int rc = liop_pass(c, det.grays_dev, width, height, K.M6.data(), K.img_of.data(), (uint32_t)K.total(), false);
+        if (rc != R3DM_OK) return rc;
+        rows.dev = c->liop_out.as<unsigned char>();
+    }
+    R3DM_HIP(c, hipMemcpyAsync(c->pin_desc.p, rows.dev, out_bytes, hipMemcpyDeviceToHost, c->stream));
     if (deferred) {
         if (!c->ev_desc) R3DM_HIP(c, hipEventCreateWithFlags(&c->ev_desc, hipEventDisableTiming));
         R3DM_HIP(c, hipEventRecord(c->ev_desc, c->stream));
@@ -137,13 +160,13 @@ int describe_batch(r3dm_ctx* c, const DetectedBatch& det, uint32_t width, uint32
 
 // phase 4, per image, three steps, each written once: format the text, write the two files, offer the image to the sink.  The two modes
 // differ in when the write runs and on which thread.
-// the sink sees the image under the index its caller knows it by, its rows on the device (the batch's are still in liop_out) and the
-// positions as written; a refusal (a sink that throws included) is the image's error
-void offer_to_sink(r3dm_ctx* c, uint32_t b, const FeatJob& j, size_t first_row, int& rc, std::string& err)
+// the sink sees the image under the index its caller knows it by, its rows on the device (the batch's are still where the descriptor
+// pass left them) and the positions as written; a refusal (a sink that throws included) is the image's error
+void offer_to_sink(r3dm_ctx* c, uint32_t b, const FeatJob& j, const BatchRows& rows, size_t first_row, int& rc, std::string& err)
 {
     const uint32_t id = c->feat_sink_ids ? c->feat_sink_ids[b] : b;
     int src = 1;
-    try { src = c->feat_sink(c->feat_sink_user, id, j.n, j.n ? c->liop_out.as<float>() + 144 * first_row : nullptr, j.xy.data()); } catch (...) {}
+    try { src = c->feat_sink(c->feat_sink_user, id, j.n, j.n ? reinterpret_cast<const float*>(rows.dev + rows.row_bytes * first_row) : nullptr, j.xy.data()); } catch (...) {}
     if (src != 0) { rc = R3DM_ERR_INVALID; err = "the features sink refused image " + std::to_string(id); }
 }
 
@@ -156,14 +179,15 @@ void offer_to_sink(r3dm_ctx* c, uint32_t b, const FeatJob& j, size_t first_row, 
 // kernel is done the images go to the sink; the fwrites -- 16 MB of descriptors per 28 k keypoints, still on their way to pin_desc -- are
 // left to the context's writer thread, which runs beside whatever the caller does next
 int deliver_batch(r3dm_ctx* c, uint32_t B, const char* const* feat_paths, const char* const* desc_paths, const DetectedBatch& det,
-                  const BatchKeypoints& K, bool deferred, int host_team, double t_liop, std::vector<int>& wrc, std::vector<std::string>& werr)
+                  const BatchKeypoints& K, const BatchRows& rows, bool deferred, int host_team, double t_liop, std::vector<int>& wrc,
+                  std::vector<std::string>& werr)
 {
     const size_t n_total = K.total();
-    const float* desc_host = n_total ? c->pin_desc.as<float>() : nullptr;
+    const unsigned char* desc_host = n_total ? c->pin_desc.as<unsigned char>() : nullptr;
     auto wanted = [&](long b) { return feat_paths[b] && desc_paths[b]; };
     auto format = [&](FeatJob& j, long b) {
         j.feat = feat_paths[b]; j.desc = desc_paths[b]; j.n = (uint32_t)det.count((uint32_t)b);
-        j.rows = desc_host ? desc_host + 144 * K.first[b] : nullptr;
+        j.rows = desc_host ? desc_host + rows.row_bytes * K.first[b] : nullptr; j.row_bytes = rows.row_bytes;
         if (c->feat_sink) j.xy.resize((size_t)j.n * 2 + 2);
         j.len = format_feat(j.txt, K.kps.data() + 4 * K.first[b], j.n, c->feat_sink ? j.xy.data() : nullptr);
     };
@@ -174,7 +198,7 @@ int deliver_batch(r3dm_ctx* c, uint32_t B, const char* const* feat_paths, const 
                 FeatJob j;
                 format(j, b);
                 wrc[b] = write_feat_desc_files(werr[b], j);
-                if (wrc[b] == R3DM_OK && c->feat_sink) offer_to_sink(c, (uint32_t)b, j, K.first[b], wrc[b], werr[b]);
+                if (wrc[b] == R3DM_OK && c->feat_sink) offer_to_sink(c, (uint32_t)b, j, rows, K.first[b], wrc[b], werr[b]);
             } catch (...) { wrc[b] = R3DM_ERR_NOMEM; }
         });
         (void)hipSetDevice(c->device);                         // a sink may have worked on another device from this thread
@@ -193,7 +217,7 @@ int deliver_batch(r3dm_ctx* c, uint32_t B, const char* const* feat_paths, const 
     if (c->feat_sink) {
         r3dm_parallel_for((long)B, host_team, [&](long b) {
             if (!wanted(b) || wrc[b] != R3DM_OK) return;
-            try { offer_to_sink(c, (uint32_t)b, (*jobs)[(size_t)b], K.first[b], wrc[b], werr[b]); } catch (...) { wrc[b] = R3DM_ERR_NOMEM; }
+            try { offer_to_sink(c, (uint32_t)b, (*jobs)[(size_t)b], rows, K.first[b], wrc[b], werr[b]); } catch (...) { wrc[b] = R3DM_ERR_NOMEM; }
             std::vector<float>().swap((*jobs)[(size_t)b].xy);
         });
         (void)hipSetDevice(c->device);
@@ -240,8 +264,10 @@ int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* const* gra
                                 const char* const* desc_paths, uint32_t* n_features)
 {
     if (!c || B == 0) return R3DM_ERR_INVALID;
+    int rc = descriptor_arm_check(c);
+    if (rc != R3DM_OK) return rc;
     DetectedBatch det;
-    int rc = detect_batch(c, B, grays, bgrs, width, height, threshold, det);
+    rc = detect_batch(c, B, grays, bgrs, width, height, threshold, det);
     if (rc != R3DM_OK) return rc;
     const double t_liop = now_ms();
     // helper threads of this batch: the cores the process really owns (its cgroup quota), shared with the other batches in flight
@@ -249,14 +275,15 @@ int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* const* gra
     struct InFlight { std::atomic<int>& n; int mine; InFlight(std::atomic<int>& a) : n(a), mine(a.fetch_add(1) + 1) {} ~InFlight() { n.fetch_sub(1); } } in_flight(batches_in_flight);
     const int host_team = r3dm_host_team(8, std::max(2, in_flight.mine));
     BatchKeypoints K;
-    keypoints_and_maps(det, B, host_team, K);
+    keypoints_and_maps(det, B, host_team, c->descriptor_arm == R3DM_DESCRIPTOR_LIOP, K);
     const bool deferred = c->defer_files;
-    if (K.total() && (rc = describe_batch(c, det, width, height, K, deferred)) != R3DM_OK) return rc;
+    BatchRows rows;
+    if (K.total() && (rc = describe_batch(c, det, width, height, K, deferred, host_team, rows)) != R3DM_OK) return rc;
     if (!deferred) c->stats.ms_liop_wall = now_ms() - t_liop;
     const double t_io = now_ms();
     std::vector<int> wrc(B, R3DM_OK);
     std::vector<std::string> werr(B);
-    if ((rc = deliver_batch(c, B, feat_paths, desc_paths, det, K, deferred, host_team, t_liop, wrc, werr)) != R3DM_OK) return rc;
+    if ((rc = deliver_batch(c, B, feat_paths, desc_paths, det, K, rows, deferred, host_team, t_liop, wrc, werr)) != R3DM_OK) return rc;
     for (uint32_t b = 0; b < B; ++b) {
         if (feat_paths[b] && desc_paths[b] && wrc[b] != R3DM_OK) { c->err = werr[b].empty() ? "out of host memory" : werr[b]; return wrc[b]; }
         if (n_features) n_features[b] = (uint32_t)det.count(b);
@@ -276,6 +303,7 @@ extern "C" int r3dm_extract_features_to_files(r3dm_ctx* c, const float* gray, ui
     return r3dm_guarded(c, [&]() -> int {
         if (!c || !gray || !feat_path || !desc_path) return R3DM_ERR_INVALID;
         if (n_features) *n_features = 0;
+        { const int arc = descriptor_arm_check(c); if (arc != R3DM_OK) return arc; }
         // "Test if descriptor and feature was already computed" (src/threads/R3DFeaturesThread.cpp:139-142): when BOTH files exist the
         // work item does nothing -- files left by a run with other parameters are reused, the reference wipes the matches directory
         // instead (src/threads/R3DComputeMatchesThread.cpp:84-86).  n_features then reports the row count of the existing .desc.
@@ -345,6 +373,11 @@ int multi_extract_impl(r3dm_multi* m, uint32_t n_images, const float* const* gra
     const uint32_t concurrency = (uint32_t)r3dm_multi_num_devices(m);
     if (concurrency == 0) return R3DM_ERR_INVALID;
     if (batch == 0) batch = 8;
+    for (uint32_t k = 0; k < concurrency; ++k) {                     // (before the skip rule and the workers: a refused call does nothing)
+        r3dm_ctx* c = r3dm_multi_ctx(m, (int)k);
+        const int arc = descriptor_arm_check(c);
+        if (arc != R3DM_OK) { if (err && err_cap) { strncpy(err, r3dm_last_error(c), err_cap - 1); err[err_cap - 1] = 0; } return arc; }
+    }
     int rc_all = R3DM_OK;
     std::vector<std::thread> th;
     try {
@@ -458,6 +491,14 @@ extern "C" int r3dm_set_keypoint_detector(r3dm_ctx* c, int arm)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_set_descriptor_arm(r3dm_ctx* c, int arm)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB) { c->err = "r3dm_set_descriptor_arm: unknown arm " + std::to_string(arm); return R3DM_ERR_INVALID; }
+    c->descriptor_arm = arm;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_background_nice(r3dm_multi* m, int nice_value)
 {
     return multi_each(m, [&](r3dm_ctx* c) { return r3dm_set_background_nice(c, nice_value); });
@@ -477,6 +518,12 @@ extern "C" int r3dm_multi_set_keypoint_detector(r3dm_multi* m, int arm)
 {
     if (arm != R3DM_DETECTOR_FAST_AKAZE && arm != R3DM_DETECTOR_AKAZE) return R3DM_ERR_INVALID;
     return multi_each(m, [&](r3dm_ctx* c) { return r3dm_set_keypoint_detector(c, arm); });
+}
+
+extern "C" int r3dm_multi_set_descriptor_arm(r3dm_multi* m, int arm)
+{
+    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB) return R3DM_ERR_INVALID;
+    return multi_each(m, [&](r3dm_ctx* c) { return r3dm_set_descriptor_arm(c, arm); });
 }
 
 extern "C" int r3dm_multi_features_files_wait(r3dm_multi* m, char* err, size_t err_cap)

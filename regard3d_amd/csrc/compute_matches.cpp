@@ -199,7 +199,9 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
         errorMessage_ = "keypoint detector list {" + names + "} is not served by the GPU path (one entry, Fast-AKAZE or AKAZE, is)";
         return false;
     }
-    if (dtype_ != R3DM_F32 || dim_ != 144) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
+    // the regions type names the descriptor arm: LIOP (float x 144) or the MLDB-486 rows of the Fast-A-KAZE detector (61 bytes)
+    const bool mldb = dtype_ == R3DM_BIN && dim_ == 61;
+    if (!mldb && (dtype_ != R3DM_F32 || dim_ != 144)) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
     if (!feat_multi_) {
         std::vector<int> ids;
         for (int d : devices_) for (int k = 0; k < std::max(1, feat_conc_); ++k) ids.push_back(d);
@@ -208,6 +210,7 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     }
     const int n_ctx = r3dm_multi_num_devices(feat_multi_);
     (void)r3dm_multi_set_keypoint_detector(feat_multi_, dl[0] == "AKAZE" ? R3DM_DETECTOR_AKAZE : R3DM_DETECTOR_FAST_AKAZE);
+    (void)r3dm_multi_set_descriptor_arm(feat_multi_, mldb ? R3DM_DESCRIPTOR_MLDB : R3DM_DESCRIPTOR_LIOP);      // (MLDB with "AKAZE": refused by name by the features call below)
     // the sink carries no scales: while preemptive matching is on, every view is registered from its files (setPreemptiveMatching)
     const bool direct = direct_registration_ && !preemptive_on_;
     (void)r3dm_multi_set_features_sink(feat_multi_, direct ? &R3DComputeMatches::features_sink : nullptr, this);
@@ -354,6 +357,7 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
 {
     statistics_ = R3DComputeMatchesStatistics();
     phases_ = PhaseTimes();
+    phases_.descriptor_arm = dtype_ == R3DM_BIN && dim_ == 61 ? R3DM_DESCRIPTOR_MLDB : R3DM_DESCRIPTOR_LIOP;
     if (!ctx_ && !multi_) return false;
     const double t_begin = wall_ms();
     // the feature files of this call are complete when it returns, however it returns (r3dm_set_deferred_feature_files)
@@ -710,6 +714,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         stage.setMutualMatching((flags & R3DM_STAGE_MUTUAL_MATCHING) != 0);
         stage.setPreemptiveMatching((flags & R3DM_STAGE_PREEMPTIVE_MATCHING) != 0);
+        if (flags & R3DM_STAGE_DESCRIPTOR_MLDB) stage.setRegionsType(R3DM_BIN, 61); else stage.setRegionsType(R3DM_F32, 144);
         r3d_amd::R3DFParams params;
         params.keypointDetectorList_ = {(flags & R3DM_STAGE_DETECTOR_AKAZE) ? "AKAZE" : "Fast-AKAZE"};
         params.threshold_ = threshold;
@@ -731,6 +736,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
             report->ms_match_kernels = P.match_kernels; report->ms_F_kernels = P.F_kernels; report->ms_E_kernels = P.E_kernels; report->ms_H_kernels = P.H_kernels;
             report->images_extracted = P.images_extracted; report->features = P.features_totals;
             report->match_was_exhaustive = stage.lastMatchWasExhaustive() ? 1 : 0;
+            report->descriptor_arm = (uint64_t)P.descriptor_arm;
             for (int n : S.numberOfKeypoints_) report->n_keypoints += (uint64_t)n;
             auto count = [](const r3d_amd::PairWiseMatches& m, uint64_t& pairs, uint64_t& matches) { pairs = m.size(); matches = 0; for (const auto& kv : m) matches += kv.second.size(); };
             count(S.putativeMatches_, report->n_putative_pairs, report->n_putative_matches);

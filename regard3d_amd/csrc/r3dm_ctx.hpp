@@ -10,7 +10,7 @@
 //   api_filter.cpp    AC-RANSAC geometric filters (F, E, H)
 //   api_tracks.cpp    feature tracks of a match graph (r3dm_build_tracks), the track filter applied to the graph, r3dm_tracks_in_pair
 //   api_akaze.cpp     the frame of both detector arms (checks, upload, INTER_AREA tables, statistics tail, DetectedBatch's writer) and the
-//                     Fast-A-KAZE arm: its pass in phases, MLDB, r3dm_detect_akaze / _mldb / _batch, r3dm_gray_from_bgr8
+//                     Fast-A-KAZE arm: its pass in phases, MLDB, r3dm_detect_akaze / _mldb / _mldb_batch / _batch, r3dm_gray_from_bgr8
 //   api_akaze_classic.cpp   the classic A-KAZE arm's launch sequence on that frame, r3dm_detect_akaze_classic / _batch
 //   api_liop.cpp      LIOP: the patch geometry, the one pass from keypoints to descriptors (liop_pass), its two entries
 //   api_features.cpp  the features work item: .feat / .desc files, the features batch in phases (detect, keypoints and maps, LIOP pass,
@@ -459,6 +459,12 @@ int detect_area_tabs(r3dm_ctx* c, DevBuf& buf, const std::vector<AkLevelHost>& l
 // the tail of a pass: kernel time (ev0 .. ev1) and wall time into the statistics, the pass into the totals
 void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints, double algorithmic_bytes);
 
+// ---- MLDB-486 of a Fast-arm pass (api_akaze.cpp): one launch over the first min(count, cap) keypoints of every image of `det`, which
+// must be the context's last detector pass.  first: B + 1 row offsets; *rows_dev: the rows, 61 bytes each, image b's at + 61 first[b]
+// (null when there is no keypoint), valid until the context's next detector or MLDB pass.  Bracketed by ev0 / ev1 and waited for;
+// host_team threads share the item loop (cos / sin of every keypoint's angle, host libm)
+int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev);
+
 // ---- LIOP (api_liop.cpp)
 // 2x3 inverse map of one keypoint's patch (x, y, size, angle in degrees)
 void liop_patch_map(float x, float y, float size, float angle_deg, float kp_size_factor, float* m);
@@ -535,6 +541,7 @@ struct r3dm_ctx {
     std::vector<DevBuf> ac_bufs;                            // classic A-KAZE work buffers (api_akaze_classic.cpp: grow, never shrink)
     uint64_t ac_components[32] = {};                        // component-size histogram of the classic arm's kpts_aux walk (r3dm_akaze_classic_components)
     int detector_arm = R3DM_DETECTOR_FAST_AKAZE;            // r3dm_set_keypoint_detector: the arm of the features entries
+    int descriptor_arm = R3DM_DESCRIPTOR_LIOP;              // r3dm_set_descriptor_arm: what the features entries describe the keypoints with
     int ak_w = 0, ak_h = 0, ak_B = 0;
     uint32_t ak_cap = 0;                                    // candidate slots per image the detector last needed (grows, never shrinks)
     int ak_n_levels = 0;
