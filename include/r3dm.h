@@ -130,6 +130,19 @@ int r3dm_trim(r3dm_ctx* ctx);
  * which path ran. */
 int r3dm_set_integer_mfma(r3dm_ctx* ctx, int enable);
 
+/* Prefix pruning of the f32 L2 matcher in match mode (default ON; no reference counterpart).  r3dm_match_pairs returns, per query,
+ * its nearest row if d1 < R d2 and nothing else, so a dataset row matters to a query only below R x (the runner-up distance seen so
+ * far).  On 128-dimensional rows with 0 < R <= 0.5 (a ratio up to 0.7 on
+ * squared distances) the f32 kernel therefore tests every 32-row x 64-query tile after 96 of its 128
+ * dimensions -- the squared distance over a prefix of the dimensions is a lower bound of the whole -- and skips the rest of a tile
+ * that no query needs.  A query whose verdict could depend on a skipped row goes to the exact scan, so graphs are bit-identical
+ * with the switch on or off (DESIGN.md, f32 kernel section, states the rule and its proof).  Everything else runs the kernel it ran
+ * before: raw neighbour lists (r3dm_knn2, r3dm_knn, r3dm_index_*), other descriptor lengths, larger R, the opt-in
+ * nominators.  r3dm_get_prefix_pruning_counts returns the tiles tested and the tiles skipped in the last r3dm_match_pairs call
+ * (0 / 0 when the pruning kernel did not run); it costs a view 4 more bytes per row. */
+int r3dm_set_prefix_pruning(r3dm_ctx* ctx, int enable);
+int r3dm_get_prefix_pruning_counts(r3dm_ctx* ctx, uint64_t out[2]);
+
 /* Opt-in split-f16 nominator of the L2 matcher for REAL-valued descriptors (default off; no reference counterpart) -- LIOP-144,
  * normalised SIFT: what Regard3D actually matches (src/Regard3DFeatures.h:44-48).  Their matching is always "nominate on
  * MFMA keys, re-score the nominees with the reference's own summation (L2_Vectorized order, no FMA), certify against a
@@ -729,6 +742,8 @@ int r3dm_multi_set_intrinsics(r3dm_multi* m, uint32_t view_id, const double* K);
 int r3dm_multi_clear_images(r3dm_multi* m);
 int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable);
 int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable);      /* r3dm_set_mutual_matching on every context */
+int r3dm_multi_set_prefix_pruning(r3dm_multi* m, int enable);       /* r3dm_set_prefix_pruning on every context */
+int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2]);      /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,

@@ -47,6 +47,7 @@ EXPORTS = [
     "r3dm_build_tracks", "r3dm_tracks_count", "r3dm_tracks_offsets", "r3dm_tracks_observations", "r3dm_tracks_report", "r3dm_tracks_phase_ms", "r3dm_tracks_in_pair",
     "r3dm_tracks_free",
     "r3dm_detect_akaze_mldb_batch", "r3dm_set_descriptor_arm", "r3dm_multi_set_descriptor_arm",
+    "r3dm_set_prefix_pruning", "r3dm_get_prefix_pruning_counts", "r3dm_multi_set_prefix_pruning", "r3dm_multi_get_prefix_pruning_counts",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
@@ -372,6 +373,10 @@ def load_library():
     L.r3dm_trim.argtypes = [vp]
     L.r3dm_set_integer_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_split_mfma.argtypes = [vp, C.c_int]
+    L.r3dm_set_prefix_pruning.argtypes = [vp, C.c_int]
+    L.r3dm_get_prefix_pruning_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_multi_set_prefix_pruning.argtypes = [vp, C.c_int]
+    L.r3dm_multi_get_prefix_pruning_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
@@ -1151,6 +1156,17 @@ class Context:
         r3dm_set_knn_hamming_tiles); same results, Stats.n_knn_hamming_tiles counts the launch"""
         self._check(self._L.r3dm_set_knn_hamming_tiles(self._h, int(bool(enable))), "r3dm_set_knn_hamming_tiles")
 
+    def set_prefix_pruning(self, enable: bool = True):
+        """prefix pruning of the f32 matcher in match mode, default on (include/r3dm.h: r3dm_set_prefix_pruning); graphs are the same
+        either way"""
+        self._check(self._L.r3dm_set_prefix_pruning(self._h, int(bool(enable))), "r3dm_set_prefix_pruning")
+
+    def prefix_pruning_counts(self):
+        """(tiles tested, tiles pruned) of the last match_pairs call; (0, 0) when the pruning kernel did not run"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.r3dm_get_prefix_pruning_counts(self._h, out), "r3dm_get_prefix_pruning_counts")
+        return int(out[0]), int(out[1])
+
     def set_mutual_matching(self, enable: bool = True):
         """opt-in mutual nearest-neighbour matching (include/r3dm.h: r3dm_set_mutual_matching): a match (i, j) of match_pairs and the
         approximate matchers is kept iff j is the nearest row of J to row i under (distance, row index); Stats.n_mutual_checked /
@@ -1540,6 +1556,16 @@ class MultiContext:
 
     def set_integer_mfma(self, enable: bool = True):
         self._check(self._L.r3dm_multi_set_integer_mfma(self._h, int(bool(enable))), "r3dm_multi_set_integer_mfma")
+
+    def set_prefix_pruning(self, enable: bool = True):
+        """r3dm_multi_set_prefix_pruning: Context.set_prefix_pruning on every context"""
+        self._check(self._L.r3dm_multi_set_prefix_pruning(self._h, int(bool(enable))), "r3dm_multi_set_prefix_pruning")
+
+    def prefix_pruning_counts(self):
+        """(tiles tested, tiles pruned) summed over the contexts' last match calls"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.r3dm_multi_get_prefix_pruning_counts(self._h, out), "r3dm_multi_get_prefix_pruning_counts")
+        return int(out[0]), int(out[1])
 
     def set_mutual_matching(self, enable: bool = True):
         """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""

@@ -457,7 +457,7 @@ static int stage_enqueue(r3dm_ctx* c, uint32_t slot, const ViewSrc& v, int s, in
         h.G = kernel_G_for(dim);
         h.n_tiles = (n + kTileRows - 1) / kTileRows;
         R3DM_HIP(c, h.tiled.ensure((size_t)h.n_tiles * h.G * 1024 + kSlackBytes));
-        R3DM_HIP(c, h.norms.ensure((size_t)h.n_tiles * 32 * 4 + kSlackBytes));
+        R3DM_HIP(c, h.norms.ensure(norms_bytes(h.n_tiles)));                       // the norms and, behind them, the prefix norms
         if (eager & kLayRows) {                                   // written by the staging kernel itself, from the tile it holds in LDS
             R3DM_HIP(c, h.rows.ensure((size_t)std::max<uint32_t>(n, 1) * dim * 4 + 256));
             h.have |= kLayRows;
@@ -476,6 +476,7 @@ static int stage_enqueue(r3dm_ctx* c, uint32_t slot, const ViewSrc& v, int s, in
     } else {
         A.raw = raw; A.raw_is_u8 = v.dtype == R3DM_U8; A.G = h.G; A.n_tiles = h.n_tiles;
         A.tiled = h.tiled.as<float>(); A.norms = h.norms.as<float>(); A.rows = (h.have & kLayRows) ? h.rows.as<float>() : nullptr;
+        A.prefix_dims = 8u * l2_prefix_groups();
         A.img_stats = &entry_dev->max_norm_bits;
         R3DM_HIP(c, launch_stage_view(c->stream, A));
     }
@@ -749,6 +750,20 @@ extern "C" int r3dm_set_integer_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;
     c->integer_mfma = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_set_prefix_pruning(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->prefix_pruning = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_get_prefix_pruning_counts(r3dm_ctx* c, uint64_t out[2])
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    out[0] = c->prune_counts[0]; out[1] = c->prune_counts[1];
     return R3DM_OK;
 }
 

@@ -263,6 +263,9 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     mp.fb_total = c->d_fb.as<uint32_t>();
     mp.fb_cnt = c->d_fb.as<uint32_t>() + 16;
     mp.fb_q = c->d_fb.as<uint32_t>() + 16 + P;
+    // (words 4 .. 7 of the zeroed header: the two 64-bit counters of the pruning kernel)
+    mp.prune = c->prefix_pruning ? 1u : 0u;
+    mp.prune_cnt = reinterpret_cast<unsigned long long*>(c->d_fb.as<uint32_t>() + 4);
 
     const double t_dbg1 = now_ms();
     R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -298,9 +301,10 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
         uint32_t fbt[2] = {0, 0};
         R3DM_HIP(c, c->pin_small.ensure(64));
-        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 8, hipMemcpyDeviceToHost, c->stream));
+        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 32, hipMemcpyDeviceToHost, c->stream));
         R3DM_HIP(c, hipStreamSynchronize(c->stream));
         memcpy(fbt, c->pin_small.p, 8);
+        { uint64_t pc[2]; memcpy(pc, (const unsigned char*)c->pin_small.p + 16, 16); c->prune_counts[0] += pc[0]; c->prune_counts[1] += pc[1]; }
         n_fallback = fbt[0];
         if (fbt[0] > 0) {
             bool rescan = fbt[1] > 0;                      // some pair overflowed its list
@@ -359,6 +363,7 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     *out = nullptr;
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
+    c->prune_counts[0] = c->prune_counts[1] = 0;
     const double t_call = now_ms();
     std::vector<PairJob> jobs, none;
     const int rcp = resolve_pairs(c, pairs_ij, n_pairs, nullptr, none, jobs);
@@ -410,6 +415,7 @@ static int r3dm_knn2_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, 
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;      // ArrayMatcherBruteForce: NN > nbRows / nbQuery < 1
     if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
     R3DM_HIP(c, hipSetDevice(c->device));
+    c->prune_counts[0] = c->prune_counts[1] = 0;            // (a raw 2-NN never prunes: the counters of this call read 0 / 0)
     PrivateSlots s(c, 2);
     int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
     if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, dim, dtype, nullptr);

@@ -201,6 +201,21 @@ extern "C" int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_prefix_pruning(r3dm_multi* m, int enable)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) r3dm_set_prefix_pruning(c, enable);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2])
+{
+    if (!m || !out) return R3DM_ERR_INVALID;
+    out[0] = out[1] = 0;
+    for (r3dm_ctx* c : m->ctx) { out[0] += c->prune_counts[0]; out[1] += c->prune_counts[1]; }
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
 {
     if (!m) return R3DM_ERR_INVALID;

@@ -76,6 +76,8 @@ __device__ __forceinline__ void stage_aux_role(const StageViewArgs& A, uint32_t 
         for (uint32_t e = tid; e < kSlackBytes / 4u; e += nthr) ts[e] = 0.0f;
         float* ns = A.norms + (size_t)A.n_tiles * 32u;
         for (uint32_t e = tid; e < kSlackBytes / 4u; e += nthr) ns[e] = 0.0f;
+        float* ps = A.norms + prefix_norm_offset(A.n_tiles) + (size_t)A.n_tiles * 32u;      // ... and behind the prefix norms
+        for (uint32_t e = tid; e < kSlackBytes / 4u; e += nthr) ps[e] = 0.0f;
     }
 }
 
@@ -136,7 +138,7 @@ void stage_view_kernel(const StageViewArgs A)
     }
     if (threadIdx.x < 32u) {
         const uint32_t row = t * 32u + threadIdx.x;
-        float s = R3DM_INF;
+        float s = R3DM_INF, sp = R3DM_INF;             // sp: the chain below after A.prefix_dims elements (the whole of a shorter row)
         if (row < n) {
             s = 0.0f;
             float mx = 0.0f; bool nonint = false, neg = false;
@@ -149,11 +151,17 @@ void stage_view_kernel(const StageViewArgs A)
             };
             if (lds) {
                 const float* p = sm + threadIdx.x * stride;
-                for (uint32_t k = 0; k < dim; k += 4u) { const f32x4 v = *(const f32x4*)(p + k); take(v[0]); take(v[1]); take(v[2]); take(v[3]); }
+                for (uint32_t k = 0; k < dim; k += 4u) {
+                    if (k == A.prefix_dims) sp = s;
+                    const f32x4 v = *(const f32x4*)(p + k); take(v[0]); take(v[1]); take(v[2]); take(v[3]);
+                }
             } else {
-                for (uint32_t k = 0; k < dim; ++k)
+                for (uint32_t k = 0; k < dim; ++k) {
+                    if (k == A.prefix_dims) sp = s;
                     take(A.raw_is_u8 ? (float)((const uint8_t*)A.raw)[(size_t)row * dim + k] : ((const float*)A.raw)[(size_t)row * dim + k]);
+                }
             }
+            if (dim <= A.prefix_dims) sp = s;
             // img_stats = &ImgDev::max_norm_bits, max_abs_bits, not_integer (non-negative floats order like uints)
             atomicMax(A.img_stats + 0, __float_as_uint(s));
             atomicMax(A.img_stats + 1, __float_as_uint(mx));
@@ -161,6 +169,7 @@ void stage_view_kernel(const StageViewArgs A)
             if (neg) atomicOr(A.img_stats + 2, 2u);
         }
         A.norms[(size_t)t * 32u + threadIdx.x] = s;
+        A.norms[prefix_norm_offset(A.n_tiles) + (size_t)t * 32u + threadIdx.x] = sp;
     }
 }
 
@@ -382,6 +391,195 @@ void l2_knn2_mfma_kernel(const MatchParams P)
     l2_finish_queries<NJ>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false);
 }
 
+// ------------------------------------------------------------------------------------------------
+// The same kernel for match mode (r3dm_match_pairs: P.knn_idx == nullptr), stopping tiles early.  Match mode returns, per query, the
+// best row if d1 < R d2 and nothing else, so a row matters to a lane half only below R x (its runner-up's distance): with R = 0.36
+// about a quarter of a stranger's distance.  A squared distance over the first 8 GP dimensions is a lower bound of the whole one;
+// a tile whose every prefix distance lies above every lane's threshold needs no further dimensions (l2_prune_tile_prefix / _finish,
+// kernels_match_tiles.hpp; the verdict rule and its proof: l2_finish_queries<PRUNE>, kernels_match_common.hpp).
+// Per (lane, query tile), with e0 <= e1 the distances (key + ||q||^2, + slack) of the list's best and runner-up:
+//   T   = fl(R e1) if e0 >= fl(R e1) (no match in sight), else max(fl(R e1), e0 / R) -- above e0 / R a pruned row cannot spoil the
+//         match either, so the verdict rule does not have to send the query to the exact scan -- rounded up;
+//   thr = T - |b_P|^2 + slack, rounded up: a prefix key kp = |a_P|^2 - 2 a_P.b_P above thr means kp + |b_P|^2 - slack > T, and the
+//         reference distance of the row is at least that (slack = 0 for pairs with the exactness proof);
+//   pl  = the smallest thr a tile was pruned under; pl + |b_P|^2 - slack, rounded down, is below the distance of every pruned row.
+// e1 = +inf gives thr = +inf (nothing is above it: the first tile, lists of NaN rows); a lane whose query does not exist (the
+// ragged last query tile) never objects.
+// ------------------------------------------------------------------------------------------------
+template <int G, int GP, int NJ, int PF, int WPS>
+__global__ __launch_bounds__(256, WPS)
+void l2_knn2_prune_kernel(const MatchParams P)
+{
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t h = lane >> 5, c = lane & 31u;
+    // workgroup -> (pair, query block): as in l2_knn2_mfma_kernel
+    uint32_t pair, qb;
+    if (P.xcd_map) {
+        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+        pair = (j / P.qb_per_pair) * 8u + xcd;
+        qb = j % P.qb_per_pair;
+        if (pair >= P.n_pairs) return;
+    } else {
+        pair = blockIdx.x / P.qb_per_pair;
+        qb = blockIdx.x % P.qb_per_pair;
+    }
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const uint32_t nI = Ip->n, ntI = Ip->n_tiles, nJ = Jp->n, ntJ = Jp->n_tiles;
+    const uint32_t qt0 = (qb * 4u + wave) * NJ;
+    if (qt0 >= ntJ) return;                           // wave-uniform; no barriers in this kernel
+
+    // ---- query fragments (B operand), scaled by -2: the prefix groups; a tile that goes on reads the others again (soffQ)
+    f32x4 bq[NJ][GP];
+    uint32_t soffQ[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        uint32_t qt = qt0 + nj; if (qt >= ntJ) qt = ntJ - 1;          // clamp: results discarded below
+        soffQ[nj] = qt * (uint32_t)(G * 1024);
+        const gf4p src = (gf4p)Jp->tiled + (size_t)qt * (G * 64) + lane;
+#pragma unroll
+        for (int g = 0; g < GP; ++g) bq[nj][g] = src[g * 64] * -2.0f;
+    }
+    const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled);
+
+    Top2 st[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
+
+    // ---- the lane's share of the threshold: e = key + nbs, thr = T + off (the header comment).  Both come from the query's two norms
+    // and are needed only where a list has changed and once at the end: they are read again there (the index passes through an
+    // empty asm so that the loads stay where they are needed) instead of living in registers the tile loop has no room for.
+    const bool exact_pair = l2_pair_is_exact(Ip, Jp, (float)(G * 8), false);
+    const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
+    const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
+    const float maxnormI = __uint_as_float(Ip->max_norm_bits);
+    auto lane_terms = [&](int nj, float& nbs, float& off) __attribute__((always_inline)) -> bool {
+        uint32_t q = (qt0 + (uint32_t)nj) * 32u + c;
+        asm volatile("" : "+v"(q));
+        const bool dead = !(q < nJ);                    // (covers a query tile beyond the last one too: its rows lie beyond nJ)
+        const uint32_t qo = dead ? 0u : q * 4u;
+        const float nb = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, 0, 0));
+        const float nbp = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, (int)(prefix_norm_offset(ntJ) * 4u), 0));
+        const float slk = exact_pair ? 0.0f : (P.err_scale + kPruneKeySlack) * (maxnormI + nb);
+        nbs = nb + slk;
+        off = slk - nbp;
+        return dead;
+    };
+    float thr[NJ], pl[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; pl[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned)
+    uint32_t n_tested = 0, n_pruned = 0;              // wave-uniform
+    bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since thr was last refreshed (pl does not hold it yet)
+
+    if (nI >= 2) {
+        // ---- dataset stream (A operand): float4 index = (t*G + g)*64 + lane
+        const gf4p abase = (gf4p)Ip->tiled;
+        const gf4p pbase = (gf4p)(Ip->norms + prefix_norm_offset(ntI));      // tile t, quad qd -> float4 index t*8 + 2*qd + h
+        f32x4 abuf[PF];
+#pragma unroll
+        for (int s = 0; s < PF; ++s) abuf[s] = abase[s * 64 + lane];
+        f32x4 pnrm[4];
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) pnrm[qd] = pbase[2 * qd + h];
+
+        f32x16 accA[NJ], accB[NJ];
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms);
+        const uint32_t voffA = lane * 16u, voffN = h * 16u;
+        const uint32_t tileB = (uint32_t)G * 1024u;                // bytes per tile
+        const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
+        const uint32_t hb = 4u * h;
+        // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes)
+        auto refresh = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) {
+                if (pruned_under_thr) pl[nj] = __builtin_fminf(pl[nj], thr[nj]);
+                float nbs, off;
+                const bool dead = lane_terms(nj, nbs, off);
+                const float e0 = st[nj].d0 + nbs, e1 = st[nj].d1 + nbs;
+                const float re1 = R * e1;
+                float T = e0 < re1 ? __builtin_fmaxf(re1, e0 * invR) : re1;
+                T += __builtin_fabsf(T) * 4.76837158203125e-07f;        // 2^-21: the roundings of e1, R e1, 1 / R and e0 / R
+                const float x = T + off;
+                thr[nj] = dead ? -R3DM_INF : x + __builtin_fabsf(x) * 2.384185791015625e-07f;      // 2^-22: the rounding of x
+            }
+        };
+        // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
+        auto tile = [&](uint32_t t, f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ], bool live) __attribute__((always_inline)) -> bool {
+            l2_prune_tile_prefix<G, GP, NJ, PF>(ra, rn, voffA, voffN, t * tileB, poff + t * 128u, abuf, pnrm, bq, cur, prev, st,
+                                                (t - 1) * 32u + hb, live);
+            if (live) { refresh(); pruned_under_thr = false; }
+            n_tested += 1u;
+            const bool on = l2_prune_tile_finish<G, GP, NJ, PF>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, abuf, rqt, soffQ, cur, thr);
+            if (!on) { n_pruned += 1u; pruned_under_thr = true; }
+            return on;
+        };
+        bool live = false;
+        uint32_t t = 0;
+        for (; t + 1 < ntI; t += 2) {
+            live = tile(t, accA, accB, live);
+            live = tile(t + 1, accB, accA, live);
+        }
+        if (t < ntI) {
+            if (tile(t, accA, accB, live)) {
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) top2_push(st[nj], accA[nj][r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        } else if (live) {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) top2_push(st[nj], accB[nj][r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+        }
+    }
+
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+        if (pruned_under_thr) pl[nj] = __builtin_fminf(pl[nj], thr[nj]);
+    // pl -> a lower bound of the pruned rows' distances: pl + |b_P|^2 - slack, rounded down
+    float pruned_lb[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        float nbs, off;
+        const bool dead = lane_terms(nj, nbs, off);
+        const float x = pl[nj] - off;
+        pruned_lb[nj] = dead ? -R3DM_INF : x - __builtin_fabsf(x) * 2.384185791015625e-07f;
+    }
+    if (lane == 0 && n_tested) {
+        atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
+        if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
+    }
+    l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
+}
+
+template <int G, int GP, int NJ, int PF, int WPS>
+static hipError_t launch_l2_prune_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+{
+    MatchParams P = Pin;
+    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
+    hipLaunchKernelGGL((l2_knn2_prune_kernel<G, GP, NJ, PF, WPS>), dim3(grid), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+// The pruning kernel serves ratio tests that leave it room: near R = 1 a row matters up to the runner-up's distance, no prefix
+// rules a tile out and the test only costs.  tools/prefix_prune_model.py on the synthetic SIFT collection (profiles/
+// prefix_prune_model_c2.txt): 96 % of the tiles stop at R = 0.36 (ratio 0.6), 72 % at R = 0.49 (ratio 0.7), 6 % at R = 0.64.
+constexpr float kPruneMaxR = 0.5f;
+
+uint32_t l2_prefix_groups()
+{
+#ifdef R3DM_DEVTOOLS
+    static const int variant = r3dm_dev_knob("R3DM_L2_VARIANT", 3);
+    if (variant >= 109 && variant <= 112) return (uint32_t)(variant - 100);
+#endif
+    return kPrefixGroups;
+}
+
 template <int G, int NJ, int PF, int PIPE, int WPS>
 static hipError_t launch_l2_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
 {
@@ -419,7 +617,20 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
     }
     if (G == 18 && variant == 0) return launch_l2_t<18, 2, 3, 0, 2>(st, P, max_nj_tiles);
     if (G == 18 && variant == 2) return launch_l2_t<18, 2, 2, 3, 2>(st, P, max_nj_tiles);
+    //   109 .. 112: the pruning kernel with GP = 9 .. 12 prefix groups (registration writes the prefix norms of the same variant)
+    if (G == 16 && P.prune && P.knn_idx == nullptr && P.ratio_R > 0.0f && P.ratio_R <= kPruneMaxR) {
+        switch (variant) {
+            case 109: return launch_l2_prune_t<16, 9, 2, 1, 2>(st, P, max_nj_tiles);
+            case 110: return launch_l2_prune_t<16, 10, 2, 2, 2>(st, P, max_nj_tiles);
+            case 111: return launch_l2_prune_t<16, 11, 2, 1, 2>(st, P, max_nj_tiles);
+            case 112: return launch_l2_prune_t<16, 12, 2, 2, 2>(st, P, max_nj_tiles);
+            default: break;
+        }
+    }
 #endif
+    // match mode on 128-dimensional rows: the kernel that stops tiles early (r3dm_set_prefix_pruning, default on)
+    if (G == 16 && P.prune && P.knn_idx == nullptr && P.ratio_R > 0.0f && P.ratio_R <= kPruneMaxR)
+        return launch_l2_prune_t<16, (int)kPrefixGroups, 2, 2, 2>(st, P, max_nj_tiles);
     switch (G) {
         case 8:  return launch_l2_t<8, 2, 4, 3, 2>(st, P, max_nj_tiles);
         case 16: return launch_l2_t<16, 2, 4, 3, 2>(st, P, max_nj_tiles);

@@ -185,6 +185,22 @@ __device__ __forceinline__ uint32_t wg_compact_rank(bool keep, uint32_t* wave_cn
     return wg_compact_rank(keep, wave_cnt, total, [] {});
 }
 
+// whether the MFMA keys of a pair ARE the reference distances (the proof stands in l2_finish_queries, where it is used): both views
+// integer-valued and every partial sum below 2^24; bf16 tiles also need |x| <= 256
+__device__ __forceinline__ bool l2_pair_is_exact(const ImgDev* __restrict__ Ip, const ImgDev* __restrict__ Jp, float dpad, bool bf16_tiles)
+{
+    const float mI = __uint_as_float(Ip->max_abs_bits), mJ = __uint_as_float(Jp->max_abs_bits);
+    const uint32_t fl = Ip->not_integer | Jp->not_integer;              // bit 0: non-integer, bit 1: negative elements
+    return (fl & 1u) == 0u &&
+           ((fl & 2u) ? dpad * (mI + mJ) * (mI + mJ) < 16777216.0f
+                      : (2.0f * dpad * mI * mJ < 16777216.0f && dpad * mI * mI < 16777216.0f && dpad * mJ * mJ < 16777216.0f)) &&
+           (!bf16_tiles || (mI <= 256.0f && mJ <= 256.0f));      // bf16 tiles hold the values exactly
+}
+
+// extra relative slack of the pruning kernel's keys over err_scale (l2_finish_queries<PRUNE>): 8 x 2^-24, for three roundings each
+// below 2^-24 x 2 (maxnorm + ||q||^2)
+constexpr float kPruneKeySlack = 4.76837158203125e-07f;
+
 // ---- per query: merge the two lane halves, re-score exactly, certify, ratio-test (tail of both L2 kernels).
 // dpad = padded descriptor length, bf16_tiles = the keys come from the integer fast path
 // LEX: the lists are exact lexicographic (distance, index) top-2 lists without a bound (l2_knn2_int_kernel)
@@ -193,11 +209,15 @@ __device__ __forceinline__ uint32_t wg_compact_rank(bool keep, uint32_t* wave_cn
 //        the exact scan
 // lane_key_inv (count tiles, l2_knn2_counts_kernel): the keys of query tile nj are in units of lane_key_inv[nj]^-1, a value per QUERY
 //        (both lane halves of a column hold the same one)
-template <int NJ, bool LEX = false, bool SPLIT = false>
+// PRUNE: the lists come from l2_knn2_prune_kernel, which left whole tiles out of them after a prefix of their dimensions;
+//        pruned_lb[nj] is this lane half's lower bound of the reference distance of every row it left out (+inf: none), and the
+//        keys carry up to three more roundings than l2_tile_step's (prefix norm, suffix norm, their sum)
+template <int NJ, bool LEX = false, bool SPLIT = false, bool PRUNE = false>
 __device__ __forceinline__ void l2_finish_queries(const MatchParams& P, uint32_t pair, const ImgDev* __restrict__ Ip,
                                                   const ImgDev* __restrict__ Jp, const Top2 (&st)[NJ], uint32_t qt0,
                                                   uint32_t h, uint32_t c, float dpad, bool bf16_tiles,
-                                                  float key_inv = 1.0f, float slack_abs = 0.0f, const float* lane_key_inv = nullptr)
+                                                  float key_inv = 1.0f, float slack_abs = 0.0f, const float* lane_key_inv = nullptr,
+                                                  const float* pruned_lb = nullptr)
 {
     const uint32_t nI = Ip->n, nJ = Jp->n, ntJ = Jp->n_tiles;
     const float maxnorm = __uint_as_float(Ip->max_norm_bits);
@@ -209,12 +229,7 @@ __device__ __forceinline__ void l2_finish_queries(const MatchParams& P, uint32_t
     // Non-negative data: ||a||^2 <= D mI^2 and the running ||a||^2 - 2 sum(a q) stays within [-2 D mI mJ, D mI^2]; the distance
     // itself is at most D max(mI, mJ)^2.  With negative elements the partial sums reach D mI^2 + 2 D mI mJ and the distance
     // D (mI + mJ)^2, where the reference's own sum starts to round: one bound on the latter covers both.
-    const float mI = __uint_as_float(Ip->max_abs_bits), mJ = __uint_as_float(Jp->max_abs_bits);
-    const uint32_t fl = Ip->not_integer | Jp->not_integer;              // bit 0: non-integer, bit 1: negative elements
-    const bool exact_pair = !SPLIT && (fl & 1u) == 0u &&
-                            ((fl & 2u) ? dpad * (mI + mJ) * (mI + mJ) < 16777216.0f
-                                       : (2.0f * dpad * mI * mJ < 16777216.0f && dpad * mI * mI < 16777216.0f && dpad * mJ * mJ < 16777216.0f)) &&
-                            (!bf16_tiles || (mI <= 256.0f && mJ <= 256.0f));      // bf16 tiles hold the values exactly
+    const bool exact_pair = !SPLIT && l2_pair_is_exact(Ip, Jp, dpad, bf16_tiles);
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) {
         Top2 s = st[nj];
@@ -259,7 +274,8 @@ __device__ __forceinline__ void l2_finish_queries(const MatchParams& P, uint32_t
         if (eb < ea || (eb == ea && ib < ia)) { const float tf = ea; ea = eb; eb = tf; const uint32_t tu = ia; ia = ib; ib = tu; }
         // certification (evaluated identically by both lane halves of a query)
         const float nb = valid ? Jp->norms[q] : 0.0f;
-        const float slack = exact_pair ? 0.0f : P.err_scale * (maxnorm + nb) + slack_abs;
+        float slack = exact_pair ? 0.0f : P.err_scale * (maxnorm + nb) + slack_abs;
+        if constexpr (PRUNE) { if (!exact_pair) slack += kPruneKeySlack * (maxnorm + nb); }
         const float A3 = bound + nb;                        // distance of the best un-nominated row (exact if exact_pair)
         // certified: every un-nominated row is strictly farther than the runner-up.  With exact
         // arithmetic a runner-up that merely TIES an un-nominated row still fixes the best row (ea < eb)
@@ -267,6 +283,24 @@ __device__ __forceinline__ void l2_finish_queries(const MatchParams& P, uint32_t
         // (r3dm_knn2) needs the tie's index resolved by the exact scan.
         bool certified = (eb < A3 - slack) || (exact_pair && P.knn_idx == nullptr && ea < eb && eb <= A3);
         if (bf16_tiles && !exact_pair) certified = false;      // bf16 keys of a non-exact pair mean nothing: exact scan
+        // PRUNE (match mode only: the launcher sees to P.knn_idx == nullptr and 0 < R < 1).  `certified` so far speaks of the rows the
+        // lists have SEEN: (ea, ia), (eb, ib) are their two nearest.  Every row of a pruned tile was left out because its prefix
+        // distance, a lower bound of its reference distance d (the reference adds non-negative terms in dimension order: its partial
+        // sums only grow), lay strictly above the lane half's threshold T, and T >= fl(R e1) for the runner-up distance e1 the half
+        // held at that moment, rounded up and widened by the slack.  Let t1 <= t2 be the true two smallest distances over ALL rows.
+        //   * t2 <= eb, and t2 <= e1 of either half at any moment (two seen rows lie no farther): fl(R x) is monotone in x, so
+        //     d > T >= fl(R e1) >= fl(R t2) for every pruned row: a pruned row is never a best row that passes the ratio test.
+        //   * not ea < fl(R eb): if the true best is a seen row it is ia, and ea >= fl(R eb) >= fl(R t2); if it is a pruned row, the
+        //     line above.  No match either way: emit_result says so from (ea, eb).
+        //   * ea < fl(R eb) and ea < fl(R PL), PL = the smaller pruned_lb of the two halves: d > PL >= fl(R PL) > ea (R < 1), so
+        //     ia is the true best row; the true runner-up is eb or a pruned row, and ea is below fl(R .) of both.  Emit ia.
+        //   * ea < fl(R eb) but not ea < fl(R PL): a pruned row may be the best row or spoil the ratio.  Exact scan.
+        // An uncertified query keeps its shortcut with PL folded into the lower bound of everything un-nominated.
+        float PL = R3DM_INF;
+        if constexpr (PRUNE) {
+            PL = fminf(pruned_lb[nj], __shfl_xor(pruned_lb[nj], 32));
+            if (certified && ea < P.ratio_R * eb && !(ea < P.ratio_R * PL)) certified = false;
+        }
         // Match mode only needs the VERDICT of the ratio test.  The two re-scored nominees bound the true runner-up distance from
         // above (d2 <= eb: two rows are no farther than eb) and, with the un-nominated rows' lower bound L = bound + ||q||^2 -
         // slack, the true best distance from below (d1 >= min(ea, L)).  If min(ea, L) >= R eb then d1 >= R d2 whatever the exact
@@ -276,6 +310,7 @@ __device__ __forceinline__ void l2_finish_queries(const MatchParams& P, uint32_t
         if (!certified && !exact_pair && !bf16_tiles && P.knn_idx == nullptr && valid && nI >= 2 && ib != kNone) {
             float L = A3 - slack;
             L -= fabsf(L) * 9.5367431640625e-07f;            // 2^-20: the float evaluation of L itself
+            if constexpr (PRUNE) L = fminf(L, PL);
             no_match = fminf(ea, L) >= P.ratio_R * eb;
         }
         if constexpr (SPLIT) {

@@ -6,6 +6,7 @@
 //   list_last / list_push_exact        ... and lists of exact keys without one (integer tiles: Top2::d1, TopK::d[KL - 1])
 //   kTestsEachKey, kTestsEachKeyExact  whether a list policy guards every single push with a ballot of its own
 //   l2_tile_step                       one dataset tile on the f32 tiles          (v_mfma_f32_32x32x2_f32)
+//   l2_prune_tile_prefix / _finish     ... stopped after a prefix of its dimensions when no lane needs the rest (match mode)
 //   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
 //   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
@@ -144,6 +145,116 @@ __device__ __forceinline__ void l2_tile_step(__amdgpu_buffer_rsrc_t ra, __amdgpu
         }
         __builtin_amdgcn_sched_barrier(0);                // keep each prefetch / epilogue slice in its own step
     }
+}
+
+// ------------------------------------------------------------------------------------------------
+// f32 tiles, match mode: the step that stops a tile after GP of its G groups (l2_knn2_prune_kernel; Top2 lists only).
+// The accumulators start from the rows' PREFIX norms (|a_P|^2 over the first 8 GP dimensions, ImgDev::norms' second half), so after
+// GP groups they hold kp = |a_P|^2 - 2 a_P.b_P, and kp + |b_P|^2 = d_P <= d.  One wave-wide test against the lane's threshold
+// `thr` (PruneLane, kernels_match.hip says what it is) decides: no lane objects -> the tile is done (the kernel remembers its rows
+// through pl, the smallest threshold it pruned under); else the suffix norms (norms - prefix norms) are added, groups GP .. G-1 run and the keys are those of
+// l2_tile_step (for integer-valued pairs the same floats: every sum is exact).
+// The epilogue of tile t-1 is spread over the GP prefix groups (prev_live says whether there is one: a pruned tile leaves none).
+// The A window: during the prefix it runs on into the NEXT tile's prefix (GP % PF == 0 keeps a group in slot g % PF), so a pruned
+// tile costs no load latency; a continuing tile fetches its groups GP .. GP+PF-1 at the decision and waits for them once -- the
+// other wave of the SIMD has the matrix pipe meanwhile -- then streams in order into the next tile as l2_tile_step does.
+// Two functions, l2_prune_tile_prefix and l2_prune_tile_finish; the second returns whether `cur` holds the keys of a finished tile
+// (wave-uniform).
+// ------------------------------------------------------------------------------------------------
+template <int G, int GP, int NJ, int PF>
+__device__ __forceinline__ void l2_prune_tile_prefix(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                     uint32_t soffA, uint32_t soffP, f32x4 (&abuf)[PF], f32x4 (&pnrm)[4],
+                                                     const f32x4 (&bq)[NJ][GP], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
+                                                     Top2 (&st)[NJ], uint32_t prev_rowbase, bool prev_live)
+{
+    static_assert(GP > 2 && GP < G && GP % PF == 0 && G % PF == 0, "the window keeps group g in slot g % PF across a pruned tile");
+    // soffA: byte offset of this tile's group 0; soffP: of this tile's prefix norms (soffN in the second half: of its norms)
+    constexpr uint32_t tileB = (uint32_t)G * 1024u;
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cur[nj][r] = pnrm[r >> 2][r & 3];
+#pragma unroll
+    for (int g = 0; g < GP; ++g) {
+        const f32x4 a = abuf[g % PF];
+        abuf[g % PF] = bload16(ra, voffA, soffA + (g + PF < GP ? (uint32_t)(g + PF) * 1024u : tileB + (uint32_t)(g + PF - GP) * 1024u));
+        if (g == 2) {   // next tile's prefix norms
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) pnrm[qd] = bload16(rn, voffN, soffP + 128u + (uint32_t)qd * 32u);
+        }
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bq[nj][g][cc], cur[nj], 0, 0, 0);
+        if (prev_live) {
+            // this group's share of the previous tile's keys: test-and-skip as in l2_tile_step<PIPE 3>
+            bool any = false;
+#pragma unroll
+            for (int r = (g * 16) / GP; r < ((g + 1) * 16) / GP; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < st[nj].d2;
+            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+#pragma unroll
+                for (int r = (g * 16) / GP; r < ((g + 1) * 16) / GP; ++r)
+#pragma unroll
+                    for (int nj = 0; nj < NJ; ++nj)
+                        top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// the second half of the step: the decision on the prefix keys and, for a tile that goes on, its suffix.  Split from the first so
+// that the caller refreshes `thr` between them (the lists are final once the epilogue above has run).
+template <int G, int GP, int NJ, int PF>
+__device__ __forceinline__ bool l2_prune_tile_finish(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                     uint32_t soffA, uint32_t soffN, uint32_t soffP, f32x4 (&abuf)[PF],
+                                                     __amdgpu_buffer_rsrc_t rq, const uint32_t (&soffQ)[NJ], f32x16 (&cur)[NJ],
+                                                     const float (&thr)[NJ])
+{
+    constexpr uint32_t tileB = (uint32_t)G * 1024u;
+    // a lane objects when one of its prefix keys is not above its threshold (written so that a NaN key objects)
+    bool obj = false;
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thr[nj]);
+    if (__builtin_amdgcn_ballot_w64(obj) == 0ull) return false;
+    // the tile goes on.  The wave keeps only the PREFIX of its query fragments in registers (the tile loop has no room for more
+    // beside the thresholds): the suffix fragments come from the query view's tiles again, soffQ[nj] = the byte offset of query tile
+    // nj's group 0, scaled by -2 like the others.  Its groups GP .. GP+PF-1 replace the next tile's first groups in the window (fetched again below, in order)
+#pragma unroll
+    for (int s = 0; s < PF; ++s) abuf[(GP + s) % PF] = bload16(ra, voffA, soffA + (uint32_t)(GP + s) * 1024u);
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const f32x4 nf = bload16(rn, voffN, soffN + (uint32_t)qd * 32u), np = bload16(rn, voffN, soffP + (uint32_t)qd * 32u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // |a|^2 - |a_P|^2; a padding row (both +inf) keeps its +inf key
+            const float sn = np[k] < R3DM_INF ? nf[k] - np[k] : 0.0f;
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) cur[nj][4 * qd + k] += sn;
+        }
+    }
+    f32x4 bqs[NJ][G - GP];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int g = GP; g < G; ++g) bqs[nj][g - GP] = bload16(rq, voffA, soffQ[nj] + (uint32_t)g * 1024u) * -2.0f;
+#pragma unroll
+    for (int g = GP; g < G; ++g) {
+        const f32x4 a = abuf[g % PF];
+        abuf[g % PF] = bload16(ra, voffA, soffA + (g + PF < G ? (uint32_t)(g + PF) * 1024u : tileB + (uint32_t)(g + PF - G) * 1024u));
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bqs[nj][g - GP][cc], cur[nj], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+    return true;
 }
 
 // ------------------------------------------------------------------------------------------------

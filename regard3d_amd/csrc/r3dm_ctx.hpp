@@ -550,6 +550,8 @@ struct r3dm_ctx {
     PinBuf pin_out;                                         // page-locked landing zone of the match lists of a batch (finalize_batch)
     PinBuf pin_desc;                                        // page-locked landing zone of the LIOP descriptors of a batch
     bool integer_mfma = false;                              // r3dm_set_integer_mfma
+    bool prefix_pruning = true;                             // r3dm_set_prefix_pruning: match mode on 128-dimensional rows stops tiles early
+    uint64_t prune_counts[2] = {0, 0};                      // r3dm_get_prefix_pruning_counts: wave tiles tested / pruned in the last match call
     bool split_mfma = false;                                // r3dm_set_split_mfma
     bool hamming_mfma = false;                              // r3dm_set_hamming_mfma
     bool knn_narrow_tiles = false;                          // r3dm_set_knn_narrow_tiles

@@ -26,6 +26,12 @@ namespace r3dm {
 constexpr uint32_t kNone = 0xFFFFFFFFu;       // "no match" / invalid row
 constexpr uint32_t kTileRows = 32;            // rows per MFMA tile (32x32x2 f32)
 constexpr uint32_t kSlackBytes = 32768;
+// l2_knn2_prune_kernel tests a tile after GP = kPrefixGroups of its 16 groups of 8 dimensions (DESIGN.md, f32 kernel section)
+constexpr uint32_t kPrefixGroups = 12;
+__host__ __device__ inline uint32_t prefix_norm_offset(uint32_t n_tiles) { return n_tiles * 32u + kSlackBytes / 4u; }      // in floats
+__host__ __device__ inline size_t norms_bytes(uint32_t n_tiles) { return 2 * ((size_t)n_tiles * 128 + kSlackBytes); }
+// the prefix groups of the build that runs: the product's constant; the developer build's R3DM_L2_VARIANT 109 .. 112 pick 9 .. 12
+uint32_t l2_prefix_groups();
 // A dispatch carries its global size (workgroups x threads per workgroup) as a 32-bit number of work-items: a launch of more
 // than 2^32 - 1 threads is not rejected by the runtime, it WRAPS (found on the first C5-sized graph search: 4560 pairs x 4096
 // workgroups x 256 threads ran only the first 464 pairs).  Launchers refuse such grids; callers batch below the limit.
@@ -35,7 +41,9 @@ constexpr uint64_t kMaxBlocksOf256 = 0xFFFFFFFFull / 256ull;       // zero slack
 //   rows  : row-major f32 [n][dim]            -- exact re-scoring in the reference's summation order
 //   tiled : [n_tiles][G][2][32][4] f32        -- MFMA fragment order: float4 (g, h, r) = row 32t+r,
 //                                                dims 8g+4h .. 8g+4h+3; one 1 KiB line per wave load
-//   norms : f32 [n_tiles*32], ||row||^2, +inf for padding rows
+//   norms : f32 [n_tiles*32], ||row||^2, +inf for padding rows; behind its zeroed slack the PREFIX norms in the same form (the sum
+//           over the first kPrefixDims dimensions, then slack again): prefix_norm_offset floats on.  One buffer and no pointer of its
+//           own, so that the entry keeps the size and the offsets the other kernels' machine code was compiled with.
 //   bin   : row-major u32 [n_pad][words]      -- binary descriptors, zero padded
 struct ImgDev {
     const float*    rows;
@@ -225,6 +233,10 @@ struct MatchParams {
     float4*       fb_part;        // [n_pairs][kFbPerPair][fb_slices] (d0, bits of i0, d1, bits of i1)
     uint32_t*     fb_done;        // [n_pairs]
     uint32_t      fb_slices;      // 1: one workgroup per pair, results emitted directly
+    // prefix pruning of the f32 2-NN tiles in match mode (r3dm_set_prefix_pruning; l2_knn2_prune_kernel).  Behind every older field:
+    // their offsets are what the other kernels' machine code was compiled with.
+    uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel
+    unsigned long long* prune_cnt; // [2]: wave tiles (32 rows x 64 queries) tested, and pruned (atomic; zeroed by the host)
 };
 constexpr uint32_t kFbPerPair = 256;
 constexpr uint32_t kFallback = 0xFFFFFFFEu;
@@ -481,7 +493,8 @@ struct StageViewArgs {
     const void* raw;               // [n][dim] f32 or u8, row-major: device memory, or page-locked host memory read over the link
     int raw_is_u8;
     uint32_t n, dim, G, n_tiles;
-    float* tiled; float* norms;
+    float* tiled; float* norms;        // norms: both halves (ImgDev::norms)
+    uint32_t prefix_dims;              // the prefix norms' dimensions (8 l2_prefix_groups())
     float* rows;                   // optional
     uint32_t* img_stats;           // &ImgDev::max_norm_bits: 3 consecutive words (zeroed by the table entry's upload)
     const float* xy_src; float* xy_dst;         // optional positions (xy_src == xy_dst: already in place)
