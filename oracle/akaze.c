@@ -361,8 +361,14 @@ static const float gauss25[7][7] = {
     { 0.00344629f, 0.00318132f, 0.00250252f, 0.00167749f, 0.00095820f, 0.00046640f, 0.00019346f },
     { 0.00142946f, 0.00131956f, 0.00103800f, 0.00069579f, 0.00039744f, 0.00019346f, 0.00008024f } };
 
-/* Compute_Main_Orientation up to the dominant vector (maxX, maxY); the angle is getAngleV2(maxX, maxY) */
-void orc_akaze_orientation_vec(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, float* out_xy)
+/* Compute_Main_Orientation up to the dominant vector (maxX, maxY); the angle is getAngleV2(maxX, maxY).
+ * variant 0 is the reference.  The others exist for the case proofs of tests/akaze_tail_cases.py, which show that an input separates
+ * the reference from a plausible mistake: 1 = a sample of slice key 42 (an angle of exactly 2 pi) is counted into slice 41 instead of
+ * lying behind every window; 2 = the samples of a slice are summed in ascending instead of the counting sort's descending order.
+ * keys (optional, 109): the slice key of every sample; norms (optional, 42): the squared norm of every window the reference forms,
+ * NaN for a window it passes over. */
+static void orientation_impl(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, float* out_xy, int variant,
+                             int* keys, float* norms)
 {
     static const int id[13] = { 6, 5, 4, 3, 2, 1, 0, 1, 2, 3, 4, 5, 6 };
     float resX[109], resY[109], Ang[109];
@@ -381,19 +387,29 @@ void orc_akaze_orientation_vec(const float* Lx, const float* Ly, int cols, int x
     unsigned char slice[slices + 1], sorted_idx[109];
     {   /* quantized_counting_sort(Ang, 109, ang_step, 2 pi, sorted_idx, slice) */
         const int nkeys = (int)((float)(2.0 * AK_PI) / ang_step);
+        int key[109];
+        for (int i = 0; i < 109; ++i) {
+            key[i] = (int)(Ang[i] / ang_step);
+            if (keys) keys[i] = key[i];
+            if (variant == 1 && key[i] >= slices) key[i] = slices - 1;
+        }
         memset(slice, 0, (size_t)nkeys + 1);
-        for (int i = 0; i < 109; ++i) slice[(int)(Ang[i] / ang_step)]++;
+        for (int i = 0; i < 109; ++i) slice[key[i]]++;
         for (int i = 1; i <= nkeys; ++i) slice[i] += slice[i - 1];
-        for (int i = 0; i < 109; ++i) sorted_idx[--slice[(int)(Ang[i] / ang_step)]] = (unsigned char)i;
+        if (variant == 2) for (int i = 108; i >= 0; --i) sorted_idx[--slice[key[i]]] = (unsigned char)i;
+        else for (int i = 0; i < 109; ++i) sorted_idx[--slice[key[i]]] = (unsigned char)i;
     }
+    if (norms) for (int i = 0; i < slices; ++i) norms[i] = NAN;
     float maxX = 0.0f, maxY = 0.0f;
     for (int i = slice[0]; i < slice[win]; ++i) { maxX += resX[sorted_idx[i]]; maxY += resY[sorted_idx[i]]; }
     float maxNorm = maxX * maxX + maxY * maxY;
+    if (norms) norms[0] = maxNorm;
     for (int sn = 1; sn <= slices - win; ++sn) {
         if (slice[sn] == slice[sn - 1] && slice[sn + win] == slice[sn + win - 1]) continue;
         float sumX = 0.0f, sumY = 0.0f;
         for (int i = slice[sn]; i < slice[sn + win]; ++i) { sumX += resX[sorted_idx[i]]; sumY += resY[sorted_idx[i]]; }
         const float nrm = sumX * sumX + sumY * sumY;
+        if (norms) norms[sn] = nrm;
         if (nrm > maxNorm) { maxNorm = nrm; maxX = sumX; maxY = sumY; }
     }
     for (int sn = slices - win + 1; sn < slices; ++sn) {
@@ -403,9 +419,24 @@ void orc_akaze_orientation_vec(const float* Lx, const float* Ly, int cols, int x
         for (int i = slice[sn]; i < slice[slices]; ++i) { sumX += resX[sorted_idx[i]]; sumY += resY[sorted_idx[i]]; }
         for (int i = slice[0]; i < slice[remain]; ++i) { sumX += resX[sorted_idx[i]]; sumY += resY[sorted_idx[i]]; }
         const float nrm = sumX * sumX + sumY * sumY;
+        if (norms) norms[sn] = nrm;
         if (nrm > maxNorm) { maxNorm = nrm; maxX = sumX; maxY = sumY; }
     }
     out_xy[0] = maxX; out_xy[1] = maxY;
+}
+void orc_akaze_orientation_vec(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, float* out_xy)
+{
+    orientation_impl(Lx, Ly, cols, x0, y0, scale, out_xy, 0, NULL, NULL);
+}
+void orc_akaze_orientation_probe(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, int variant, float* out_xy,
+                                 int* keys, float* norms)
+{
+    orientation_impl(Lx, Ly, cols, x0, y0, scale, out_xy, variant, keys, norms);
+}
+/* the slice key Compute_Main_Orientation gives a sample (resX, resY) */
+int orc_akaze_slice_key(float resY, float resX)
+{
+    return (int)(fast_atan2(resY, resX) / (float)(2.0 * AK_PI / 42));
 }
 
 /* MLDB_Full_Descriptor_InvokerV2::Get_MLDB_Full_Descriptor (AKAZEFeatures.cpp:1877-1909) with MLDB_Fill_Values (:1790-1844) and
@@ -459,6 +490,119 @@ void orc_akaze_mldb(const float* Lt, const float* Lx, const float* Ly, int cols,
     }
     const int remain = dpos % 8;
     if (remain > 0) desc[dpos >> 3] &= (unsigned char)(0xff >> (8 - remain));
+}
+
+/* The detector's tail (AKAZEFeatures.cpp: Find_Scale_Space_Extrema's lower- and upper-level loops, Do_Subpixel_Refinement,
+ * Compute_Main_Orientation, getAngleV2, Get_MLDB_Full_Descriptor; Regard3DFeatures.cpp's angle convention) on given level planes
+ * and per-level kept lists.  planes: per level Ldet, Lx, Ly, Lt; lists[i]: n_list[i] triples (x, y, response) in image coordinates,
+ * every entry of level i with size esigma * 1.5.  Out, per surviving keypoint in order of level, then list position: rec (10 floats:
+ * x, y, size, response, maxX, maxY, theta in radians as getAngleV2 forms it, the Regard3D angle in degrees, cosf and sinf of theta as
+ * the descriptor takes them), level, and (desc
+ * non-NULL) 61 descriptor bytes; only the first cap are written, the return value is the number that survive.  dead (optional, per
+ * level n_list[i] x 2 bytes): [0] the lower-level loop erased the entry, [1] the upper-level loop's condition held for it.  (The
+ * reference erases once: its upper loop passes over an entry the lower loop erased.  Here the condition is recorded for every entry,
+ * which changes no survivor: an entry survives when neither byte is set.) */
+int orc_akaze_tail(int nl, const orc_ak_tail_level* lv, const float* const* planes, const int* n_list, const float* const* lists,
+                   int cap, float* rec, int* level_out, unsigned char* mldb /* cap x 61 or NULL */, unsigned char* const* dead)
+{
+    const float dfac = 1.5f;
+    ak_list* kl = (ak_list*)calloc((size_t)nl, sizeof(ak_list));
+    unsigned char** du = (unsigned char**)calloc((size_t)nl, sizeof(unsigned char*));
+    for (int i = 0; i < nl; ++i) {
+        du[i] = (unsigned char*)calloc((size_t)n_list[i] + 1, 1);
+        for (int j = 0; j < n_list[i]; ++j) {
+            ak_kp p = { lists[i][3 * j], lists[i][3 * j + 1], lv[i].esigma * dfac, lists[i][3 * j + 2], i, 1 };
+            kl_push(&kl[i], p);
+        }
+    }
+    for (int i = 1; i < nl; ++i)                       /* lower scale level */
+        for (int j = 0; j < kl[i].n; ++j) {
+            const ak_kp* pt = &kl[i].v[j];
+            for (int q = 0; q < kl[i - 1].n; ++q) {
+                ak_kp* v = &kl[i - 1].v[q];
+                if (!v->alive) continue;
+                const float dx = pt->x - v->x, dy = pt->y - v->y;
+                if (dx * dx + dy * dy <= pt->size * pt->size && pt->response > v->response) v->alive = 0;
+            }
+        }
+    for (int i = nl - 2; i >= 0; --i)                  /* upper scale level */
+        for (int j = 0; j < kl[i].n; ++j) {
+            const ak_kp* pt = &kl[i].v[j];
+            if (!pt->alive) continue;
+            for (int q = 0; q < kl[i + 1].n; ++q) {
+                ak_kp* v = &kl[i + 1].v[q];
+                if (du[i + 1][q]) continue;
+                const float dx = pt->x - v->x, dy = pt->y - v->y;
+                if (dx * dx + dy * dy <= v->size * v->size && pt->response > v->response) du[i + 1][q] = 1;
+            }
+        }
+
+    if (dead)
+        for (int i = 0; i < nl; ++i)
+            for (int j = 0; j < kl[i].n; ++j) { dead[i][2 * j] = (unsigned char)!kl[i].v[j].alive; dead[i][2 * j + 1] = du[i][j]; }
+    for (int i = 0; i < nl; ++i)
+        for (int j = 0; j < kl[i].n; ++j) if (du[i][j]) kl[i].v[j].alive = 0;
+
+    /* Do_Subpixel_Refinement + Compute_Main_Orientation + the Regard3D angle convention */
+    int n_out = 0;
+    for (int i = 0; i < nl; ++i) {
+        const orc_ak_tail_level* e = &lv[i];
+        const float* ldet = planes[4 * i], *pLx = planes[4 * i + 1], *pLy = planes[4 * i + 2], *pLt = planes[4 * i + 3];
+        const int cols = e->w;
+        const float ratio = e->ratio;
+        for (int j = 0; j < kl[i].n; ++j) {
+            ak_kp kp = kl[i].v[j];
+            if (!kp.alive) continue;
+            const int x = (int)(kp.x / ratio), y = (int)(kp.y / ratio);
+            const float Dx = 0.5f * (ldet[y * cols + x + 1] - ldet[y * cols + x - 1]);
+            const float Dy = 0.5f * (ldet[(y + 1) * cols + x] - ldet[(y - 1) * cols + x]);
+            const float Dxx = ldet[y * cols + x + 1] + ldet[y * cols + x - 1] - 2.0f * ldet[y * cols + x];
+            const float Dyy = ldet[(y + 1) * cols + x] + ldet[(y - 1) * cols + x] - 2.0f * ldet[y * cols + x];
+            const float Dxy = 0.25f * (ldet[(y + 1) * cols + x + 1] + ldet[(y - 1) * cols + x - 1] -
+                                       ldet[(y - 1) * cols + x + 1] - ldet[(y + 1) * cols + x - 1]);
+            /* cv::solve, 2x2, DECOMP_LU: Cramer's rule in double (core/lapack.cpp) */
+            float dx = 0.0f, dy = 0.0f;
+            {
+                const float b0 = -Dx, b1 = -Dy;
+                double d = (double)Dxx * Dyy - (double)Dxy * Dxy;
+                if (d != 0.) {
+                    d = 1. / d;
+                    const double t = (float)(((double)b0 * Dyy - (double)b1 * Dxy) * d);
+                    dy = (float)(((double)b1 * Dxx - (double)b0 * Dxy) * d);
+                    dx = (float)t;
+                }
+            }
+            if (fabsf(dx) > 1.0f || fabsf(dy) > 1.0f) continue;
+            kp.x += dx * ratio; kp.y += dy * ratio;
+            kp.size *= 2.0f;
+            /* Compute_Main_Orientation */
+            const int scale = fround(0.5f * kp.size / ratio);
+            const int x0 = fround(kp.x / ratio), y0 = fround(kp.y / ratio);
+            float mv[2];
+            orc_akaze_orientation_vec(pLx, pLy, cols, x0, y0, scale, mv);
+            float theta = atan2f(mv[1], mv[0]);
+            if (!(theta >= 0)) theta = theta + (float)(2.0f * AK_PI);
+            /* detectKeypoints: radians -> degrees, + 90, wrap */
+            float ang = theta;
+            ang *= 180.0 / AK_PI;
+            ang += 90.0f;
+            while (ang < 0) ang += 360.0f;
+            while (ang > 360.0f) ang -= 360.0f;
+            const float co = cosf(theta), si = sinf(theta);
+            if (n_out < cap && mldb)      /* AKAZE2::detectAndCompute: descriptors from the raw (radian) orientation */
+                orc_akaze_mldb(pLt, pLx, pLy, cols, kp.x / ratio, kp.y / ratio, co, si, (float)e->sigma_size, mldb + 61 * (size_t)n_out);
+            if (n_out < cap) {
+                float* r = rec + 10 * (size_t)n_out;
+                r[0] = kp.x; r[1] = kp.y; r[2] = kp.size; r[3] = kp.response; r[4] = mv[0]; r[5] = mv[1]; r[6] = theta; r[7] = ang;
+                r[8] = co; r[9] = si;
+                if (level_out) level_out[n_out] = i;
+            }
+            ++n_out;
+        }
+    }
+    for (int i = 0; i < nl; ++i) { free(kl[i].v); free(du[i]); }
+    free(kl); free(du);
+    return n_out;
 }
 
 /* Regard3DFeatures::detectKeypoints, "Fast-AKAZE" arm: image = h x w floats in [0, 1].
@@ -573,82 +717,29 @@ static int akaze_detect_impl(const float* image, int w, int h, float dthreshold,
             }
         }
     }
-    for (int i = 1; i < nl; ++i)                       /* lower scale level */
-        for (int j = 0; j < kl[i].n; ++j) {
-            const ak_kp* pt = &kl[i].v[j];
-            for (int q = 0; q < kl[i - 1].n; ++q) {
-                ak_kp* v = &kl[i - 1].v[q];
-                if (!v->alive) continue;
-                const float dx = pt->x - v->x, dy = pt->y - v->y;
-                if (dx * dx + dy * dy <= pt->size * pt->size && pt->response > v->response) v->alive = 0;
-            }
-        }
-    for (int i = nl - 2; i >= 0; --i)                  /* upper scale level */
-        for (int j = 0; j < kl[i].n; ++j) {
-            const ak_kp* pt = &kl[i].v[j];
-            if (!pt->alive) continue;
-            for (int q = 0; q < kl[i + 1].n; ++q) {
-                ak_kp* v = &kl[i + 1].v[q];
-                if (!v->alive) continue;
-                const float dx = pt->x - v->x, dy = pt->y - v->y;
-                if (dx * dx + dy * dy <= v->size * v->size && pt->response > v->response) v->alive = 0;
-            }
-        }
-
-    /* Do_Subpixel_Refinement + Compute_Main_Orientation + the Regard3D angle convention */
     int n_out = 0;
-    for (int i = 0; i < nl; ++i) {
-        const ak_level* e = &lv[i];
-        const float* ldet = e->Ldet;
-        const int cols = e->w;
-        const float ratio = e->ratio;
-        for (int j = 0; j < kl[i].n; ++j) {
-            ak_kp kp = kl[i].v[j];
-            if (!kp.alive) continue;
-            const int x = (int)(kp.x / ratio), y = (int)(kp.y / ratio);
-            const float Dx = 0.5f * (ldet[y * cols + x + 1] - ldet[y * cols + x - 1]);
-            const float Dy = 0.5f * (ldet[(y + 1) * cols + x] - ldet[(y - 1) * cols + x]);
-            const float Dxx = ldet[y * cols + x + 1] + ldet[y * cols + x - 1] - 2.0f * ldet[y * cols + x];
-            const float Dyy = ldet[(y + 1) * cols + x] + ldet[(y - 1) * cols + x] - 2.0f * ldet[y * cols + x];
-            const float Dxy = 0.25f * (ldet[(y + 1) * cols + x + 1] + ldet[(y - 1) * cols + x - 1] -
-                                       ldet[(y - 1) * cols + x + 1] - ldet[(y + 1) * cols + x - 1]);
-            /* cv::solve, 2x2, DECOMP_LU: Cramer's rule in double (core/lapack.cpp) */
-            float dx = 0.0f, dy = 0.0f;
-            {
-                const float b0 = -Dx, b1 = -Dy;
-                double d = (double)Dxx * Dyy - (double)Dxy * Dxy;
-                if (d != 0.) {
-                    d = 1. / d;
-                    const double t = (float)(((double)b0 * Dyy - (double)b1 * Dxy) * d);
-                    dy = (float)(((double)b1 * Dxx - (double)b0 * Dxy) * d);
-                    dx = (float)t;
-                }
-            }
-            if (fabsf(dx) > 1.0f || fabsf(dy) > 1.0f) continue;
-            kp.x += dx * ratio; kp.y += dy * ratio;
-            kp.size *= 2.0f;
-            /* Compute_Main_Orientation */
-            const int scale = fround(0.5f * kp.size / ratio);
-            const int x0 = fround(kp.x / ratio), y0 = fround(kp.y / ratio);
-            float mv[2];
-            orc_akaze_orientation_vec(e->Lx, e->Ly, cols, x0, y0, scale, mv);
-            float theta = atan2f(mv[1], mv[0]);
-            if (!(theta >= 0)) theta = theta + (float)(2.0f * AK_PI);
-            /* detectKeypoints: radians -> degrees, + 90, wrap */
-            float ang = theta;
-            ang *= 180.0 / AK_PI;
-            ang += 90.0f;
-            while (ang < 0) ang += 360.0f;
-            while (ang > 360.0f) ang -= 360.0f;
-            if (n_out < cap && mldb)      /* AKAZE2::detectAndCompute: descriptors from the raw (radian) orientation */
-                orc_akaze_mldb(e->Lt, e->Lx, e->Ly, cols, kp.x / ratio, kp.y / ratio, cosf(theta), sinf(theta), (float)e->sigma_size, mldb + 61 * (size_t)n_out);
-            if (n_out < cap) {
-                kps[4 * n_out] = kp.x; kps[4 * n_out + 1] = kp.y; kps[4 * n_out + 2] = kp.size; kps[4 * n_out + 3] = ang;
-                if (responses) responses[n_out] = kp.response;
-                if (levels) levels[n_out] = i;
-            }
-            ++n_out;
+    {   /* the tail: cross-level filters, refinement, orientation, angle, MLDB */
+        orc_ak_tail_level tl[16];
+        const float* planes[16 * 4];
+        int n_list[16];
+        float* lists[16];
+        for (int i = 0; i < nl; ++i) {
+            tl[i].w = lv[i].w; tl[i].h = lv[i].h; tl[i].sigma_size = lv[i].sigma_size; tl[i].ratio = lv[i].ratio; tl[i].esigma = lv[i].esigma;
+            planes[4 * i] = lv[i].Ldet; planes[4 * i + 1] = lv[i].Lx; planes[4 * i + 2] = lv[i].Ly; planes[4 * i + 3] = lv[i].Lt;
+            n_list[i] = kl[i].n;
+            lists[i] = (float*)malloc(sizeof(float) * 3 * (size_t)(kl[i].n + 1));
+            for (int j = 0; j < kl[i].n; ++j) { lists[i][3 * j] = kl[i].v[j].x; lists[i][3 * j + 1] = kl[i].v[j].y; lists[i][3 * j + 2] = kl[i].v[j].response; }
         }
+        float* rec = (float*)malloc(sizeof(float) * 10 * (size_t)(cap + 1));
+        int* rlev = (int*)malloc(sizeof(int) * (size_t)(cap + 1));
+        n_out = orc_akaze_tail(nl, tl, planes, n_list, (const float* const*)lists, cap, rec, rlev, mldb, NULL);
+        for (int k = 0; k < n_out && k < cap; ++k) {
+            kps[4 * k] = rec[10 * k]; kps[4 * k + 1] = rec[10 * k + 1]; kps[4 * k + 2] = rec[10 * k + 2]; kps[4 * k + 3] = rec[10 * k + 7];
+            if (responses) responses[k] = rec[10 * k + 3];
+            if (levels) levels[k] = rlev[k];
+        }
+        for (int i = 0; i < nl; ++i) free(lists[i]);
+        free(rec); free(rlev);
     }
     for (int i = 0; i < nl; ++i) { free(kl[i].v); free(lv[i].Lt); }
     free(kl); free(wx); free(wy); free(wflow); free(wstep);

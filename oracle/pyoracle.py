@@ -554,6 +554,68 @@ def akaze_detect_mldb(img, threshold=0.001, cap=200000):
     return kps[:n].copy(), desc[:n].copy(), resp[:n].copy()
 
 
+class AkTailLevel(C.Structure):
+    """orc_ak_tail_level"""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("sigma_size", C.c_int), ("ratio", C.c_float), ("esigma", C.c_float)]
+
+
+def akaze_tail(levels, planes, lists, want_desc=True):
+    """orc_akaze_tail: the detector's tail (cross-level filters, refinement, orientation, angle, MLDB) on given planes and lists.
+    levels: dicts with w, h, sigma_size, ratio, esigma; planes[i] = (Ldet, Lx, Ly, Lt) float32 [h, w]; lists[i] = [n_i, 3] float32
+    (x, y, response).  -> dict: n, x, y, size, response, max_x, max_y, theta, angle_deg, cos, sin [n] float32, level [n] int32, desc [n, 61]
+    uint8 (None unless want_desc), dead [per level][n_i, 2] uint8 (erased by the lower loop, the upper loop's condition held)"""
+    nl = len(levels)
+    lv = (AkTailLevel * nl)(*[AkTailLevel(int(e["w"]), int(e["h"]), int(e["sigma_size"]), float(e["ratio"]), float(e["esigma"])) for e in levels])
+    pl = [np.ascontiguousarray(q, np.float32) for lev in planes for q in lev]
+    for i, e in enumerate(levels):
+        assert all(q.shape == (e["h"], e["w"]) for q in pl[4 * i:4 * i + 4])
+    ls = [np.ascontiguousarray(l, np.float32).reshape(-1, 3) for l in lists]
+    n_list = np.array([len(l) for l in ls], np.int32)
+    cap = max(int(n_list.sum()), 1)
+    rec = np.zeros((cap, 10), np.float32); lev_out = np.zeros(cap, np.int32)
+    desc = np.zeros((cap, 61), np.uint8) if want_desc else None
+    dead = [np.zeros((len(l) + 1, 2), np.uint8) for l in ls]
+    pp = (C.c_void_p * (4 * nl))(*[q.ctypes.data for q in pl])
+    lp = (C.c_void_p * nl)(*[l.ctypes.data for l in ls])
+    dp = (C.c_void_p * nl)(*[d.ctypes.data for d in dead])
+    L = lib()
+    L.orc_akaze_tail.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    n = L.orc_akaze_tail(nl, C.addressof(lv), C.addressof(pp), _p(n_list), C.addressof(lp), cap, _p(rec), _p(lev_out),
+                         _p(desc) if want_desc else None, C.addressof(dp))
+    assert 0 <= n <= cap
+    names = ("x", "y", "size", "response", "max_x", "max_y", "theta", "angle_deg", "cos", "sin")
+    out = {k: rec[:n, j].copy() for j, k in enumerate(names)}
+    out.update(n=n, level=lev_out[:n].copy(), desc=desc[:n].copy() if want_desc else None, dead=[d[:-1].copy() for d in dead])
+    return out
+
+
+def akaze_orientation_vec(lx, ly, x0, y0, scale, variant=0, probe=False):
+    """orc_akaze_orientation_vec: Compute_Main_Orientation's dominant vector (maxX, maxY) at level position (x0, y0), sample step scale.
+    probe (or variant != 0): orc_akaze_orientation_probe -> (vec, keys [109], window norms [42], NaN where the reference forms none);
+    variant 1 counts a sample of slice key 42 into slice 41, variant 2 sums the samples of a slice in ascending order"""
+    lx = np.ascontiguousarray(lx, np.float32); ly = np.ascontiguousarray(ly, np.float32)
+    out = np.zeros(2, np.float32)
+    if not probe and variant == 0:
+        lib().orc_akaze_orientation_vec(_p(lx), _p(ly), lx.shape[1], int(x0), int(y0), int(scale), _p(out))
+        return out
+    keys = np.zeros(109, np.int32); norms = np.zeros(42, np.float32)
+    lib().orc_akaze_orientation_probe(_p(lx), _p(ly), lx.shape[1], int(x0), int(y0), int(scale), int(variant), _p(out), _p(keys), _p(norms))
+    return out, keys, norms
+
+
+def akaze_slice_key(res_y, res_x):
+    """the slice key (0 .. 42) Compute_Main_Orientation gives a weighted sample (resX, resY)"""
+    return int(lib().orc_akaze_slice_key(C.c_float(res_y), C.c_float(res_x)))
+
+
+def akaze_mldb(lt, lx, ly, xf, yf, co, si, scale):
+    """orc_akaze_mldb: the 61 MLDB-486 bytes of one keypoint at level position (xf, yf), cos / sin of its angle, scale = sigma_size"""
+    lt = np.ascontiguousarray(lt, np.float32); lx = np.ascontiguousarray(lx, np.float32); ly = np.ascontiguousarray(ly, np.float32)
+    desc = np.zeros(61, np.uint8)
+    lib().orc_akaze_mldb(_p(lt), _p(lx), _p(ly), lt.shape[1], C.c_float(xf), C.c_float(yf), C.c_float(co), C.c_float(si), C.c_float(scale), _p(desc))
+    return desc
+
+
 # ---- HNSW plugin path: the restatement (hnsw.c) and the reference-built library (oracle/_ref) ----
 class HnswIndex:
     """orc_hnsw: built by the restatement (hnswlib's single-thread insertion) or wrapped around exported arrays"""

@@ -202,6 +202,13 @@ int   orc_akaze_fed_tau(float T, float* tau);
 void  orc_akaze_orientation_vec(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, float* out_xy);
 void  orc_akaze_mldb(const float* Lt, const float* Lx, const float* Ly, int cols, float xf, float yf, float co, float si,
                      float scale, unsigned char* desc);
+/* the detector's tail on given planes and lists, and two probes of the orientation for the case proofs (akaze.c) */
+typedef struct { int w, h, sigma_size; float ratio, esigma; } orc_ak_tail_level;
+int   orc_akaze_tail(int nl, const orc_ak_tail_level* lv, const float* const* planes, const int* n_list, const float* const* lists,
+                     int cap, float* rec, int* level_out, unsigned char* mldb, unsigned char* const* dead);
+void  orc_akaze_orientation_probe(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, int variant, float* out_xy,
+                                  int* keys, float* norms);
+int   orc_akaze_slice_key(float resY, float resX);
 int   orc_akaze_detect_mldb(const float* image, int w, int h, float dthreshold, float* kps, unsigned char* desc, int cap, float* responses);
 int   orc_akaze_detect(const float* image, int w, int h, float dthreshold, float* kps, int cap, float* responses, int* levels,
                        int dbg_level, float* dbg_ldet, float* dbg_lt, float* dbg_info);

@@ -534,6 +534,51 @@ def dev_walk_args(levels, lists):
     return lv, n_cand, words
 
 
+class DevAkLevel(C.Structure):
+    """r3dm_dev_ak_level (developer build, api_akaze.cpp): one level of the Fast arm's level table"""
+    _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("border", C.c_int32), ("sigma_size", C.c_int32), ("ratio", C.c_float),
+                ("esigma", C.c_float), ("psize", C.c_float)]
+
+
+def bind_dev_akaze_tail(L):
+    """the developer build's Fast-arm tail entries (libr3dm_dev.so only, declared in no header), bound when first asked for"""
+    if getattr(L, "_r3dm_dev_tail_bound", False):
+        return L
+    if not hasattr(L, "r3dm_dev_akaze_tail"):
+        raise R3dmError("r3dm_dev_akaze_tail exists in the developer build only: use_developer_library() before the first load")
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.r3dm_dev_akaze_tail_levels.argtypes = [u32, u32, vp, vp]
+    L.r3dm_dev_akaze_tail_check.argtypes = [u32, u32, u32, u32, vp, vp, vp, vp]
+    L.r3dm_dev_akaze_tail.argtypes = [vp, u32, u32, u32, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L._r3dm_dev_tail_bound = True
+    return L
+
+
+def dev_akaze_tail_levels(L, width: int, height: int):
+    """r3dm_dev_akaze_tail_levels: the Fast arm's level table of a width x height image, as dicts (w, h, border, sigma_size, ratio,
+    esigma, psize)"""
+    bind_dev_akaze_tail(L)
+    lv = (DevAkLevel * 16)(); n = C.c_uint32(0)
+    rc = L.r3dm_dev_akaze_tail_levels(width, height, C.addressof(lv), C.addressof(n))
+    if rc != 0:
+        raise R3dmError(f"r3dm_dev_akaze_tail_levels -> {rc}")
+    return [{k: getattr(lv[i], k) for k, _ in DevAkLevel._fields_} for i in range(n.value)]
+
+
+def dev_tail_args(images):
+    """the arrays of the tail entries.  images: per image a dict with planes [n_levels] of (Ldet, Lx, Ly, Lt) float32 [h, w] and lists
+    [n_levels] of [n, 3] float32 (x, y, response).  -> (n_levels, plane_dims [n_levels, 2] uint32, plane pointers, n_list [B, n_levels]
+    uint32, lists [sum, 3] float32, keep-alive)"""
+    nl = len(images[0]["planes"])
+    keep = [[[np.ascontiguousarray(q, np.float32) for q in lev] for lev in im["planes"]] for im in images]
+    dims = np.array([[lev[0].shape[1], lev[0].shape[0]] for lev in keep[0]], np.uint32).reshape(nl, 2)
+    ptrs = (C.c_void_p * (len(images) * nl * 4))(*[q.ctypes.data for im in keep for lev in im for q in lev])
+    ls = [np.ascontiguousarray(l, np.float32).reshape(-1, 3) for im in images for l in im["lists"]]
+    n_list = np.array([len(l) for l in ls], np.uint32)
+    lists = np.ascontiguousarray(np.concatenate(ls + [np.zeros((1, 3), np.float32)]))
+    return nl, dims, ptrs, n_list, lists, keep
+
+
 def _ptr(a) -> Optional[int]:
     """address of a numpy array or torch tensor (host or device) -- the ABI takes plain pointers"""
     if a is None:
@@ -1264,6 +1309,36 @@ class Context:
             res.append(dict(x=f[:, 0].copy(), y=f[:, 1].copy(), size=f[:, 2].copy(), resp=f[:, 3].copy(), cls=o[:, 4].copy(),
                             kept=o[:, 5] != 0, hist=hist[b].copy()))
             at += int(n_cand[b])
+        return res
+
+    def dev_akaze_tail(self, width: int, height: int, images):
+        """r3dm_dev_akaze_tail (developer build): the Fast arm's tail -- cross-level filters, refinement, orientation, compaction, the
+        host's angles, MLDB -- on the caller's planes and lists (see dev_tail_args) -> per image a dict: n, the seven record fields
+        (x, y, size, response, max_x, max_y float32; level uint32), theta, cos, sin [n] float32, desc [n, 61] uint8, dead [per level]
+        [n_i, 2] uint8 (dead_lower, dead_upper of every list entry)"""
+        L = bind_dev_akaze_tail(self._L)
+        nl, dims, ptrs, n_list, lists, keep = dev_tail_args(images)
+        B = len(images)
+        total = max(int(n_list.sum()), 1)
+        n_kp = np.zeros(B, np.uint32); recs = np.zeros((total, 8), np.uint32); ang = np.zeros((total, 3), np.float32)
+        desc = np.zeros((total, 61), np.uint8); dead = np.zeros((total, 2), np.uint8)
+        self._check(L.r3dm_dev_akaze_tail(self._h, width, height, B, nl, _ptr(dims), C.addressof(ptrs), _ptr(n_list), _ptr(lists),
+                                          _ptr(n_kp), _ptr(recs), _ptr(ang), _ptr(desc), _ptr(dead)), "r3dm_dev_akaze_tail")
+        del keep
+        res, at = [], 0
+        per = n_list.reshape(B, nl)
+        for b in range(B):
+            n = int(n_kp[b])
+            r = recs[at:at + n]; f = np.ascontiguousarray(r[:, :6]).view(np.float32)
+            out = dict(n=n, level=r[:, 6].copy(), theta=ang[at:at + n, 0].copy(), cos=ang[at:at + n, 1].copy(), sin=ang[at:at + n, 2].copy(),
+                       desc=desc[at:at + n].copy(), dead=[])
+            for j, k in enumerate(("x", "y", "size", "response", "max_x", "max_y")):
+                out[k] = f[:, j].copy()
+            e = at
+            for i in range(nl):
+                out["dead"].append(dead[e:e + int(per[b, i])].copy()); e += int(per[b, i])
+            res.append(out)
+            at += int(per[b].sum())
         return res
 
     def guided_match(self, pairs, kind: str, models, threshold_px, ratio: float) -> Graph:

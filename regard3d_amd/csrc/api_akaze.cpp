@@ -2,7 +2,8 @@
 // arms stand in (argument checks, gray-or-BGR upload, INTER_AREA tables, statistics tail, the detect entry over a DetectedBatch, the choice
 // of the arm), then the Fast-A-KAZE arm (kernels_akaze.hip): ak_detect_batch in its phases -- buffers, scale space, detection with regrow,
 // read-back -- and its entries.  The classic arm's launch sequence is api_akaze_classic.cpp; what is shared and what stays per arm:
-// DESIGN.md section 4.21.  There is no CPU fallback in this file: when HIP fails, the call fails.
+// DESIGN.md section 4.21.  There is no CPU fallback in this file: when HIP fails, the call fails.  At the end, developer build only: the
+// arm's tail on a caller's planes and lists (r3dm_dev_akaze_tail).
 #include "r3dm_ctx.hpp"
 
 // ======== the frame of both arms
@@ -467,6 +468,18 @@ int ak_level_table(AkPass& p, AkDetection& d)
     return R3DM_OK;
 }
 
+// the tail of the detection on the pruned lists (counts[1] entries per level): the row spans of the list chunks, the lower- and the
+// upper-level filter, refinement + orientation, the records.  The detector and the developer build's r3dm_dev_akaze_tail both call it.
+hipError_t ak_tail_launches(hipStream_t st, const AkLevelDev* d_levels, int nl, int iB, AkKpRec* recs, uint32_t cap, AkBatchMeta* d_bmeta)
+{
+    hipError_t e;
+    if ((e = ak_list_ranges(st, d_levels, nl, iB)) != hipSuccess) return e;
+    if ((e = ak_cross(st, d_levels, nl, iB, 0)) != hipSuccess) return e;
+    if ((e = ak_cross(st, d_levels, nl, iB, 1)) != hipSuccess) return e;
+    if ((e = ak_refine(st, d_levels, nl, iB)) != hipSuccess) return e;
+    return ak_compact(st, d_levels, nl, iB, recs, cap, d_bmeta);
+}
+
 // the detection launches at a slot capacity; an image that reports more candidates than it makes them run again with larger arrays
 int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
 {
@@ -489,11 +502,7 @@ int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
         R3DM_HIP(c, hipMemsetAsync(slots.as<unsigned char>() + field * 76, 0, field * 2, st));   // dead_lower / dead_upper flags
         R3DM_HIP(c, ak_extrema(st, d.d_levels, nl, iB, d.max_rows, threshold, 1));
         R3DM_HIP(c, ak_prune_levels(st, d.d_levels, nl, iB));
-        R3DM_HIP(c, ak_list_ranges(st, d.d_levels, nl, iB));
-        R3DM_HIP(c, ak_cross(st, d.d_levels, nl, iB, 0));
-        R3DM_HIP(c, ak_cross(st, d.d_levels, nl, iB, 1));
-        R3DM_HIP(c, ak_refine(st, d.d_levels, nl, iB));
-        R3DM_HIP(c, ak_compact(st, d.d_levels, nl, iB, recs.as<AkKpRec>(), cap, d.d_bmeta));
+        R3DM_HIP(c, ak_tail_launches(st, d.d_levels, nl, iB, recs.as<AkKpRec>(), cap, d.d_bmeta));
         R3DM_HIP(c, hipEventRecord(c->ev1, st));
         R3DM_HIP(c, hipMemcpyAsync(d.bm.data(), d.d_bmeta, (size_t)B * sizeof(AkBatchMeta), hipMemcpyDeviceToHost, st));
         R3DM_HIP(c, hipStreamSynchronize(st));                                            // host visit 1 of 2: the counts
@@ -559,6 +568,26 @@ int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     return R3DM_OK;
 }
 
+// one keypoint of image b as the MLDB kernel takes it: the raw (radian) angle of the host libm, its cos / sin, level coordinates, sigma_size
+static AkMldbItem ak_mldb_item(uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r, float* theta_out)
+{
+    const float theta = ak_theta(r);
+    if (theta_out) *theta_out = theta;
+    return {b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (float)lv[r.level].sigma_size};
+}
+
+// comparison table of MLDB_Binary_Comparisons: per grid, per channel, all value pairs i < j
+static std::vector<unsigned char> ak_mldb_pairs()
+{
+    std::vector<unsigned char> pairs;
+    const int bases[3] = {0, 12, 39}, cnts[3] = {4, 9, 16};
+    for (int g = 0; g < 3; ++g)
+        for (int pos = 0; pos < 3; ++pos)
+            for (int i = 0; i < cnts[g]; ++i)
+                for (int j = i + 1; j < cnts[g]; ++j) { pairs.push_back((unsigned char)(bases[g] + 3 * i + pos)); pairs.push_back((unsigned char)(bases[g] + 3 * j + pos)); }
+    return pairs;
+}
+
 // Get_MLDB_Full_Descriptor of the first min(count, cap) keypoints of every image of the pass, in ONE launch: level coordinates, cos / sin of
 // the raw (radian) angle (host libm, as the oracle and the LIOP patch map: device trigonometry is not bit-equal to it).  An item names
 // its level as image * n_levels + level: the level table the detector left on the device (ak_levels_dev) and the Lt / Lx / Ly planes of
@@ -588,18 +617,10 @@ int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_t
         const Chunk& ch = chunks[(size_t)ci];
         const std::vector<AkKpRec>& recs = det.fast[ch.b];
         for (size_t k = ch.k0; k < ch.k1; ++k) {
-            const AkKpRec& r = recs[k];
-            const float theta = ak_theta(r);
-            items[first[ch.b] + k] = {ch.b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (float)lv[r.level].sigma_size};
+            items[first[ch.b] + k] = ak_mldb_item(ch.b, nl, lv, recs[k], nullptr);
         }
     });
-    // comparison table of MLDB_Binary_Comparisons: per grid, per channel, all value pairs i < j
-    std::vector<unsigned char> pairs;
-    const int bases[3] = {0, 12, 39}, cnts[3] = {4, 9, 16};
-    for (int g = 0; g < 3; ++g)
-        for (int pos = 0; pos < 3; ++pos)
-            for (int i = 0; i < cnts[g]; ++i)
-                for (int j = i + 1; j < cnts[g]; ++j) { pairs.push_back((unsigned char)(bases[g] + 3 * i + pos)); pairs.push_back((unsigned char)(bases[g] + 3 * j + pos)); }
+    const std::vector<unsigned char> pairs = ak_mldb_pairs();
     hipStream_t st = c->stream;
     DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_MLDB];
     R3DM_HIP(c, mb.ensure(ni * sizeof(AkMldbItem) + 1024 + ni * 61 + 64));
@@ -675,3 +696,177 @@ extern "C" int r3dm_detect_akaze_batch(r3dm_ctx* c, uint32_t n_images, const flo
         return detect_entry(c, ak_detect_batch, false, n_images, images, width, height, threshold, keypoints_out, responses_out, cap, n_out, det);
     });
 }
+
+#ifdef R3DM_DEVTOOLS
+// ---- developer build only (libr3dm_dev.so; declared in no header): the Fast arm's tail on a caller's level planes and pruned lists, so
+// that the suite can put to the kernels what images hardly produce (a sample at exactly 360 degrees, windows of equal norm, a singular
+// Hessian, a shift of exactly 1, equal responses across levels, unsorted lists, more than 256 killer chunks, tied MLDB cells, a keypoint
+// on the border at 45 degrees).  What runs is the product's: ak_levels, ak_buffers, ak_level_table, ak_layout,
+// ak_tail_launches, ak_mldb_item / ak_mldb_pairs / ak_mldb_pass above.
+struct r3dm_dev_ak_level { int32_t w, h, border, sigma_size; float ratio, esigma, psize; };
+constexpr uint32_t kAkDevMaxB = 64, kAkDevMaxList = 1u << 20;
+
+// the level table the product forms for a width x height image: n_levels <= 16 entries
+extern "C" int r3dm_dev_akaze_tail_levels(uint32_t width, uint32_t height, r3dm_dev_ak_level* out, uint32_t* n_levels)
+{
+    if (!out || !n_levels || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    if (lv.size() > 16) return R3DM_ERR_UNSUPPORTED;
+    for (size_t i = 0; i < lv.size(); ++i) out[i] = {lv[i].w, lv[i].h, lv[i].border, lv[i].sigma_size, lv[i].ratio, lv[i].esigma, lv[i].esigma * 1.5f};
+    *n_levels = (uint32_t)lv.size();
+    return R3DM_OK;
+}
+
+// What the kernels would mis-read is refused here, before anything touches a device (c may be null): R3DM_OK or R3DM_ERR_INVALID.
+//   n_levels and plane_dims [n_levels][2] (w, h of the planes the caller holds) are the table's of (width, height); 1 <= B <= 64
+//   planes [B][n_levels][4]: Ldet, Lx, Ly, Lt, every value finite (a NaN gradient gives a NaN angle and a garbage slice key into LDS)
+//   n_list [B][n_levels] <= 2^20 each; lists: the (x, y, response) triples of image 0's levels, then image 1's, ...: response finite,
+//   x = column ratio and y = row ratio for integers column in [border, w - border), row in [border, h - border) of the entry's level.
+//   Positions may repeat, lists need no order, entries need not be extrema of Ldet.
+// Why every read of an accepted input stays inside its plane (s = sigma_size, border = fRound(10 sqrt 2 s) + 1 >= 15):
+//   the cross-level filter reads the lists only;
+//   the refinement reads Ldet at column +- 1, row +- 1, and moves the position by at most 1 in level coordinates (a larger shift drops
+//   the entry; ratio is a power of two, so position / ratio is exact and rounds to within column +- 1, row +- 1);
+//   the orientation reads Lx, Ly at the rounded position +- 5 s (i, j in -6 .. 6 with i i + j j < 36, step fRound(size / 2 / ratio) = s):
+//   5 s + 1 < border;
+//   MLDB reads at fRound(position + o) with |o| <= 10 sqrt 2 s (l, k in -10 .. 10, |l cos + k sin| <= 10 (|cos| + |sin|)) and position
+//   >= border - 1 = fRound(10 sqrt 2 s): position - 10 sqrt 2 s > -0.5, which rounds half up (and truncates) to 0 or more; on the far
+//   side position <= dim - border = dim - 1 - fRound(10 sqrt 2 s), so position + 10 sqrt 2 s < dim - 0.5, which rounds to dim - 1 at most.
+extern "C" int r3dm_dev_akaze_tail_check(uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
+                                         const float* const* planes, const uint32_t* n_list, const float* lists)
+{
+    if (!plane_dims || !planes || !n_list || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    if (B < 1 || B > kAkDevMaxB) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    const uint32_t nl = (uint32_t)lv.size();
+    if (nl < 1 || nl > 16 || n_levels != nl) return R3DM_ERR_INVALID;
+    for (uint32_t i = 0; i < nl; ++i) if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
+    size_t at = 0;
+    for (uint32_t b = 0; b < B; ++b)
+        for (uint32_t i = 0; i < nl; ++i) {
+            const AkLevelHost& e = lv[i];
+            const size_t plane = (size_t)e.w * e.h;
+            for (int q = 0; q < 4; ++q) {
+                const float* P = planes[((size_t)b * nl + i) * 4 + q];
+                if (!P) return R3DM_ERR_INVALID;
+                for (size_t k = 0; k < plane; ++k) if (!std::isfinite(P[k])) return R3DM_ERR_INVALID;
+            }
+            const uint32_t n = n_list[(size_t)b * nl + i];
+            if (n > kAkDevMaxList || (n && !lists)) return R3DM_ERR_INVALID;
+            for (uint32_t k = 0; k < n; ++k) {
+                const float* t = lists + 3 * (at + k);
+                if (!std::isfinite(t[0]) || !std::isfinite(t[1]) || !std::isfinite(t[2])) return R3DM_ERR_INVALID;
+                const float col = t[0] / e.ratio, row = t[1] / e.ratio;
+                if (col != floorf(col) || row != floorf(row) || col * e.ratio != t[0] || row * e.ratio != t[1]) return R3DM_ERR_INVALID;
+                if (col < (float)e.border || col >= (float)(e.w - e.border) || row < (float)e.border || row >= (float)(e.h - e.border)) return R3DM_ERR_INVALID;
+            }
+            at += n;
+        }
+    return R3DM_OK;
+}
+
+// Runs the lists through the product's tail.  The list lengths stand in for the candidate counts, so that the product's own layout
+// kernel places the slot arrays; the lists are then copied to where it put them and counts[1] says how long they are -- the state the
+// in-level pruning leaves.  Outputs: n_kp [B]; per image, at the offset of its lists (the sum of the list lengths of the images
+// before it; an image has at most as many keypoints as list entries): recs_out (AkKpRec, 32 bytes), angles_out (theta, cos, sin as
+// ak_mldb_item forms them), desc_out (61 bytes a row, from ak_mldb_pass); dead_out: (dead_lower, dead_upper) of every list entry.
+extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
+                                   const float* const* planes, const uint32_t* n_list, const float* lists,
+                                   uint32_t* n_kp, AkKpRec* recs_out, float* angles_out, unsigned char* desc_out, unsigned char* dead_out)
+{
+    const int vrc = r3dm_dev_akaze_tail_check(width, height, B, n_levels, plane_dims, planes, n_list, lists);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_tail: planes or lists the kernels would mis-read"; return vrc; }
+    if (!c || !n_kp) return R3DM_ERR_INVALID;
+    std::vector<size_t> first_entry((size_t)B + 1, 0);
+    for (uint32_t b = 0; b < B; ++b) {
+        size_t t = 0;
+        for (uint32_t i = 0; i < n_levels; ++i) t += n_list[(size_t)b * n_levels + i];
+        first_entry[b + 1] = first_entry[b] + t;
+    }
+    if (first_entry[B] && (!recs_out || !angles_out || !desc_out || !dead_out)) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        DetectedBatch det;
+        det.fast.assign(B, std::vector<AkKpRec>());
+        det.fast_levels = ak_levels((int)width, (int)height);
+        const std::vector<AkLevelHost>& lv = det.fast_levels;
+        const int nl = (int)lv.size();
+        AkPass p{c, c->stream, B, (int)B, (int)width, (int)height, nl, (size_t)width * height, lv};
+        hipStream_t st = p.st;
+        int rc = ak_buffers(p);
+        if (rc != R3DM_OK) return rc;
+        for (uint32_t b = 0; b < B; ++b)
+            for (int i = 0; i < nl; ++i) {
+                const size_t plane = (size_t)lv[i].w * lv[i].h;
+                const float* const* P = planes + ((size_t)b * nl + i) * 4;
+                R3DM_HIP(c, hipMemcpyAsync(p.Ldet(i) + b * plane, P[0], plane * 4, hipMemcpyHostToDevice, st));
+                R3DM_HIP(c, hipMemcpyAsync(p.Lx(i) + b * plane, P[1], plane * 4, hipMemcpyHostToDevice, st));
+                R3DM_HIP(c, hipMemcpyAsync(p.Ly(i) + b * plane, P[2], plane * 4, hipMemcpyHostToDevice, st));
+                R3DM_HIP(c, hipMemcpyAsync(p.Lt(i) + b * plane, P[3], plane * 4, hipMemcpyHostToDevice, st));
+            }
+        AkDetection d;
+        if ((rc = ak_level_table(p, d)) != R3DM_OK) return rc;
+        uint32_t cap = 1;
+        for (uint32_t b = 0; b < B; ++b) cap = std::max<uint32_t>(cap, (uint32_t)(first_entry[b + 1] - first_entry[b]));
+        DevBuf &meta = p.tail(T_META), &slots = p.tail(T_SLOTS), &recs = p.tail(T_RECS);
+        const size_t field = (size_t)B * cap;
+        R3DM_HIP(c, slots.ensure(field * kAkSlotBytes + 256));
+        R3DM_HIP(c, recs.ensure(field * sizeof(AkKpRec) + 256));
+        R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
+        R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
+        std::vector<uint32_t> cnt(4 * d.n_lv, 0u);                       // counts of level k = image * nl + level: [0] candidates, [1] list entries
+        for (size_t k = 0; k < d.n_lv; ++k) cnt[4 * k] = cnt[4 * k + 1] = n_list[k];
+        R3DM_HIP(c, hipMemcpyAsync(d.ld[0].counts, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st));
+        R3DM_HIP(c, ak_layout(st, d.d_levels, nl, (int)B, slots.as<unsigned char>(), cap, d.d_bmeta));
+        R3DM_HIP(c, hipMemsetAsync(slots.as<unsigned char>() + field * 76, 0, field * 2, st));   // dead_lower / dead_upper flags, as the detector clears them
+        std::vector<AkLevelDev> dl(d.n_lv);
+        R3DM_HIP(c, hipMemcpyAsync(dl.data(), d.d_levels, d.n_lv * sizeof(AkLevelDev), hipMemcpyDeviceToHost, st));
+        R3DM_HIP(c, hipStreamSynchronize(st));
+        std::vector<float> l4(4 * std::max<size_t>(first_entry[B], 1), 0.0f);       // the lists as the kernels read them: (x, y, response, -)
+        for (size_t k = 0; k < first_entry[B]; ++k) { l4[4 * k] = lists[3 * k]; l4[4 * k + 1] = lists[3 * k + 1]; l4[4 * k + 2] = lists[3 * k + 2]; }
+        size_t at = 0;
+        for (size_t k = 0; k < d.n_lv; ++k) {
+            if (n_list[k]) R3DM_HIP(c, hipMemcpyAsync(dl[k].list, l4.data() + 4 * at, (size_t)n_list[k] * 16, hipMemcpyHostToDevice, st));
+            at += n_list[k];
+        }
+        R3DM_HIP(c, ak_tail_launches(st, d.d_levels, nl, (int)B, recs.as<AkKpRec>(), cap, d.d_bmeta));
+        d.bm.assign(B, AkBatchMeta{});
+        R3DM_HIP(c, hipMemcpyAsync(d.bm.data(), d.d_bmeta, (size_t)B * sizeof(AkBatchMeta), hipMemcpyDeviceToHost, st));
+        // (the two flag arrays of a level are n_list[k] bytes each; they go out interleaved per entry)
+        std::vector<unsigned char> fl(2 * std::max<size_t>(first_entry[B], 1), 0);
+        at = 0;
+        for (size_t k = 0; k < d.n_lv; ++k) {
+            if (n_list[k]) {
+                R3DM_HIP(c, hipMemcpyAsync(fl.data() + at, dl[k].dead_lower, n_list[k], hipMemcpyDeviceToHost, st));
+                R3DM_HIP(c, hipMemcpyAsync(fl.data() + first_entry[B] + at, dl[k].dead_upper, n_list[k], hipMemcpyDeviceToHost, st));
+            }
+            at += n_list[k];
+        }
+        R3DM_HIP(c, hipStreamSynchronize(st));
+        for (size_t k = 0; k < first_entry[B]; ++k) { dead_out[2 * k] = fl[k]; dead_out[2 * k + 1] = fl[first_entry[B] + k]; }
+        for (uint32_t b = 0; b < B; ++b) {
+            if (d.bm[b].overflow || d.bm[b].n_kp > first_entry[b + 1] - first_entry[b]) { c->err = "r3dm_dev_akaze_tail: more keypoints than list entries"; return R3DM_ERR_INVALID; }
+            n_kp[b] = d.bm[b].n_kp;
+        }
+        d.cap = cap;
+        if ((rc = ak_read_back(p, d, det.fast)) != R3DM_OK) return rc;
+        c->ak_n_levels = nl;
+        c->ak_levels_dev = d.d_levels;                                   // what the detector leaves for the MLDB pass
+        std::vector<size_t> first;
+        const unsigned char* rows = nullptr;
+        if ((rc = ak_mldb_pass(c, det, 0xFFFFFFFFu, 1, first, &rows)) != R3DM_OK) return rc;
+        for (uint32_t b = 0; b < B; ++b) {
+            const size_t n = det.fast[b].size(), o = first_entry[b];
+            for (size_t k = 0; k < n; ++k) {
+                recs_out[o + k] = det.fast[b][k];
+                float theta = 0.0f;
+                const AkMldbItem it = ak_mldb_item(b, (uint32_t)nl, lv, det.fast[b][k], &theta);
+                angles_out[3 * (o + k)] = theta; angles_out[3 * (o + k) + 1] = it.co; angles_out[3 * (o + k) + 2] = it.si;
+            }
+            if (n) R3DM_HIP(c, hipMemcpyAsync(desc_out + 61 * o, rows + 61 * first[b], n * 61, hipMemcpyDeviceToHost, st));
+        }
+        R3DM_HIP(c, hipStreamSynchronize(st));
+        return R3DM_OK;
+    });
+}
+#endif  // R3DM_DEVTOOLS
