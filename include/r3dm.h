@@ -142,6 +142,13 @@ int r3dm_set_integer_mfma(r3dm_ctx* ctx, int enable);
  * (0 / 0 when the pruning kernel did not run); it costs a view 4 more bytes per row. */
 int r3dm_set_prefix_pruning(r3dm_ctx* ctx, int enable);
 int r3dm_get_prefix_pruning_counts(r3dm_ctx* ctx, uint64_t out[2]);
+/* In front of the prefix test the kernel runs a cheaper one on every tile: the same contraction over 64 PAIR NORMS per row
+ * (sqrt(x[2k]^2 + x[2k+1]^2), rounded up; Cauchy-Schwarz per pair bounds the distance from below), half of a tile's work instead of
+ * three quarters.  A tile is skipped if either test rules it out; one that is not starts over and runs as before.  The pair norms are
+ * scratch of the call (2 bytes per dimension and row of the batch's views, in one buffer of the context), made from the views' f32
+ * tiles by every match call that prunes: a view holds no layout for them (r3dm_view_info reports what it reported).
+ * r3dm_get_pair_filter_counts: the tiles of the last r3dm_match_pairs call that this first test skipped (part of out[1] above). */
+int r3dm_get_pair_filter_counts(r3dm_ctx* ctx, uint64_t* out);
 
 /* Opt-in split-f16 nominator of the L2 matcher for REAL-valued descriptors (default off; no reference counterpart) -- LIOP-144,
  * normalised SIFT: what Regard3D actually matches (src/Regard3DFeatures.h:44-48).  Their matching is always "nominate on
@@ -744,6 +751,7 @@ int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable);
 int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable);      /* r3dm_set_mutual_matching on every context */
 int r3dm_multi_set_prefix_pruning(r3dm_multi* m, int enable);       /* r3dm_set_prefix_pruning on every context */
 int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2]);      /* summed over the contexts' last calls */
+int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,

@@ -48,6 +48,7 @@ EXPORTS = [
     "r3dm_tracks_free",
     "r3dm_detect_akaze_mldb_batch", "r3dm_set_descriptor_arm", "r3dm_multi_set_descriptor_arm",
     "r3dm_set_prefix_pruning", "r3dm_get_prefix_pruning_counts", "r3dm_multi_set_prefix_pruning", "r3dm_multi_get_prefix_pruning_counts",
+    "r3dm_get_pair_filter_counts", "r3dm_multi_get_pair_filter_counts",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
@@ -377,6 +378,8 @@ def load_library():
     L.r3dm_get_prefix_pruning_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_multi_set_prefix_pruning.argtypes = [vp, C.c_int]
     L.r3dm_multi_get_prefix_pruning_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_get_pair_filter_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_multi_get_pair_filter_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
@@ -1212,6 +1215,12 @@ class Context:
         self._check(self._L.r3dm_get_prefix_pruning_counts(self._h, out), "r3dm_get_prefix_pruning_counts")
         return int(out[0]), int(out[1])
 
+    def pair_filter_counts(self):
+        """tiles of the last match_pairs call that the pair-norm filter pruned (part of prefix_pruning_counts()[1])"""
+        out = C.c_uint64(0)
+        self._check(self._L.r3dm_get_pair_filter_counts(self._h, C.byref(out)), "r3dm_get_pair_filter_counts")
+        return int(out.value)
+
     def set_mutual_matching(self, enable: bool = True):
         """opt-in mutual nearest-neighbour matching (include/r3dm.h: r3dm_set_mutual_matching): a match (i, j) of match_pairs and the
         approximate matchers is kept iff j is the nearest row of J to row i under (distance, row index); Stats.n_mutual_checked /
@@ -1641,6 +1650,12 @@ class MultiContext:
         out = (C.c_uint64 * 2)()
         self._check(self._L.r3dm_multi_get_prefix_pruning_counts(self._h, out), "r3dm_multi_get_prefix_pruning_counts")
         return int(out[0]), int(out[1])
+
+    def pair_filter_counts(self):
+        """tiles pruned by the pair-norm filter, summed over the contexts' last match calls"""
+        out = C.c_uint64(0)
+        self._check(self._L.r3dm_multi_get_pair_filter_counts(self._h, C.byref(out)), "r3dm_multi_get_pair_filter_counts")
+        return int(out.value)
 
     def set_mutual_matching(self, enable: bool = True):
         """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""

@@ -42,7 +42,7 @@ extern "C" void r3dm_destroy(r3dm_ctx* c)
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     for (auto& im : c->imgs) if (im) im->release();
-    DevBuf* bufs[] = {&c->d_imgs, &c->d_pairs, &c->d_nn, &c->d_knn_idx, &c->d_knn_dist, &c->d_fb, &c->d_cnt, &c->d_out,
+    DevBuf* bufs[] = {&c->d_imgs, &c->d_pairs, &c->d_pairnorm, &c->d_pairnorm_tiles, &c->d_nn, &c->d_knn_idx, &c->d_knn_dist, &c->d_fb, &c->d_cnt, &c->d_out,
                       &c->d_pair_off, &c->d_pair_cnt, &c->d_raw, &c->m_raw, &c->m_peer,
                       &c->liop_pix, &c->liop_sx, &c->liop_sy, &c->liop_in, &c->liop_out, &c->liop_cnt, &c->liop_img, &c->liop_M, &c->liop_kern,
                       &c->a_jobs, &c->h_aux, &c->h_jobs, &c->a_scratch, &c->a_ids, &c->d_spill, &c->d_fb2, &c->g_segs, &c->d_verdict};
@@ -764,6 +764,13 @@ extern "C" int r3dm_get_prefix_pruning_counts(r3dm_ctx* c, uint64_t out[2])
 {
     if (!c || !out) return R3DM_ERR_INVALID;
     out[0] = c->prune_counts[0]; out[1] = c->prune_counts[1];
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_get_pair_filter_counts(r3dm_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    *out = c->prune_counts[2];
     return R3DM_OK;
 }
 

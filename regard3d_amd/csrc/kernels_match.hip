@@ -258,6 +258,36 @@ hipError_t launch_stage_bf16(hipStream_t st, const float* tiled, uint32_t G, uin
     return hipGetLastError();
 }
 
+// pair-norm tiles of the cascade's filter (l2_knn2_cascade_kernel): [tile][G / 2 groups][2][32][4] f32 in the fragment order of
+// `tiled`, element k of a row = an upper bound of sqrt(x[2k]^2 + x[2k+1]^2).  Dimensions 2k and 2k+1 share a float4 of `tiled`.
+// The bound: x^2 and y^2 are exact in double (24-bit significands), their sum s and its root rd carry one rounding each, so
+// rd >= (1 - 2^-52) |(x, y)| (2^-50 if the root were off by a few ulps); f = (float)rd rounded to nearest is kept only if
+// f >= rd (1 + 2^-40) >= |(x, y)|, else the next float up is taken, which lies above rd by more than that.  So f >= |(x, y)| always
+// and f <= (1 + 2^-22) |(x, y)|.  Zero pairs (padding rows and dimensions) stay 0; a NaN element gives NaN, which objects in the test.
+__global__ __launch_bounds__(256)
+void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* __restrict__ tiledr)
+{
+    const uint32_t t = blockIdx.x, GR = G / 2u;
+    const float* src = tiled + (size_t)t * G * 256u;
+    float* dst = tiledr + (size_t)t * GR * 256u;
+    for (uint32_t e = threadIdx.x; e < GR * 256u; e += 256u) {
+        const uint32_t c = e & 3u, r = (e >> 2) & 31u, h = (e >> 7) & 1u, g = e >> 8;
+        const uint32_t d = 2u * (8u * g + 4u * h + c);               // the pair's first dimension; in the f32 tiles: g = d / 8, half (d / 4) & 1
+        const float* p = src + (d >> 3) * 256u + ((d >> 2) & 1u) * 128u + r * 4u + (d & 3u);
+        const double x = (double)p[0], y = (double)p[1];
+        const double rd = __builtin_sqrt(x * x + y * y);
+        float f = (float)rd;
+        if ((double)f < rd * (1.0 + 0x1p-40)) f = __uint_as_float(__float_as_uint(f) + 1u);      // (f >= 0 and finite here: the next float up)
+        dst[e] = f;
+    }
+}
+hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr)
+{
+    if (n_tiles == 0) return hipSuccess;
+    hipLaunchKernelGGL(stage_pairnorm_kernel, dim3(n_tiles), dim3(256), 0, st, tiled, G, tiledr);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------------------------------------
 // fused squared-L2 2-NN: one workgroup = 4 waves; each wave keeps NJ query tiles (32 queries each,
 // pre-scaled by -2) in registers as MFMA B fragments and streams every 32-row dataset tile of
@@ -566,10 +596,215 @@ static hipError_t launch_l2_prune_t(hipStream_t st, const MatchParams& Pin, uint
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// The cascade: a cheaper proof in front of the prefix test.  The prefix test above runs GP = 12 of a tile's 16 groups before it may
+// stop it; most tiles it stops hold strangers only, and for those HALF the contraction proves as much.  Split the 128 dimensions
+// into 64 pairs; with sa_k >= |(a_2k, a_2k+1)| and sb_k likewise (the pair-norm tiles, stage_pairnorm_kernel), Cauchy-Schwarz per pair gives
+// a.b <= sum_k sa_k sb_k, hence
+//     kf + |b|^2 <= |a - b|^2,   kf = |a|^2 - 2 sum_k sa_k sb_k,
+// for any signs and any data: the same MFMA contraction over reduced rows of 64 floats (8 groups), started from the FULL norms.
+// Per tile (T, thr as above; thrF = T - |b|^2 + slackF, rounded up):
+//   1. l2_pairnorm_tile_filter: 8 groups on the pair-norm tiles.  No lane has a kf that is not above its thrF -> the tile is done.
+//   2. else l2_prune_tile_restart: the tile runs the step above from its group 0 -- prefix norms, 12 groups, the prefix test against
+//      thr, suffix, epilogue -- with all its fragments read again (the wave keeps only the reduced query fragments in registers).
+// A tile is pruned if EITHER bound rules it out, and the keys of every tile that finishes are the floats of the kernel above.
+// slackF (carried by EVERY pair: products of roots are no integers, the exactness proof does not reach kf), in units of
+// u (max|a|^2 + |q|^2), u = 2^-24, against the reference distance d_ref:
+//     128   the stored |a|^2 (the accumulators' start) and the stored |q|^2 (in thrF): fma chains of 128 non-negative terms, each
+//           off by at most 128 u of its own norm
+//      65   the 64 products sa_k sb_k and their sum (non-negative terms: the error is relative to the sum), the nudges of both
+//           factors included: 2 sum_k sa_k sb_k <= (1 + 2^-21) 2 |a| |b| <= (1 + 2^-21) (|a|^2 + |q|^2)
+//      64   64 roundings of accumulators whose values stay within [-|q|^2, |a|^2 + |q|^2] (two products per MFMA, 32 MFMAs)
+//     256   d_ref itself: the reference's sum of 128 non-negative terms is at least (1 - 128 u) |a - b|^2 <= 2 (|a|^2 + |q|^2)
+//   = 513 <= 4.25 x 128 = 544 u = err_scale, the certificate's own factor; kPruneKeySlack (8 u) on top pays the roundings of slackF,
+//     of slackF - |q|^2 and of T.  So slackF = (err_scale + kPruneKeySlack) (max|a|^2 + |q|^2): the certificate's form, for EVERY pair.
+//   The nudge itself costs no slack: it only raises sa, sb, which lowers kf -- the bound gets looser, never wrong.
+// Rows pruned by either test lie strictly above the lane half's T of that moment in reference distance (the filter: kf > thrF >=
+// T - |b|^2 + slackF, and d_ref >= kf + |b|^2 - slackF; the prefix test: kernel above), so plT, the smallest T a lane half pruned
+// under, is the lower bound l2_finish_queries<PRUNE> asks for, whichever test pruned.
+// MODE (developer ablations): 0 the cascade | 1 filter only (step 2 never stops a tile).
+// ------------------------------------------------------------------------------------------------
+template <int G, int GP, int NJ, int PF, int WPS, int MODE>
+__global__ __launch_bounds__(256, WPS)
+void l2_knn2_cascade_kernel(const MatchParams P)
+{
+    constexpr int GR = G / 2;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t h = lane >> 5, c = lane & 31u;
+    // workgroup -> (pair, query block): as in l2_knn2_mfma_kernel
+    uint32_t pair, qb;
+    if (P.xcd_map) {
+        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+        pair = (j / P.qb_per_pair) * 8u + xcd;
+        qb = j % P.qb_per_pair;
+        if (pair >= P.n_pairs) return;
+    } else {
+        pair = blockIdx.x / P.qb_per_pair;
+        qb = blockIdx.x % P.qb_per_pair;
+    }
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const float* const* pairnorm = reinterpret_cast<const float* const*>(P.prune_cnt[3]);      // (MatchParams::prune_cnt says why it lives there)
+    const float* __restrict__ redI = pairnorm[pr.x];
+    const float* __restrict__ redJ = pairnorm[pr.y];
+    const uint32_t nI = Ip->n, ntI = Ip->n_tiles, nJ = Jp->n, ntJ = Jp->n_tiles;
+    const uint32_t qt0 = (qb * 4u + wave) * NJ;
+    if (qt0 >= ntJ) return;                           // wave-uniform; no barriers in this kernel
+
+    // ---- reduced query fragments (B operand of the filter), scaled by -2; a tile that goes on reads the full ones (soffQ)
+    f32x4 bqr[NJ][GR];
+    uint32_t soffQ[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        uint32_t qt = qt0 + nj; if (qt >= ntJ) qt = ntJ - 1;          // clamp: results discarded below
+        soffQ[nj] = qt * (uint32_t)(G * 1024);
+        const gf4p src = (gf4p)redJ + (size_t)qt * (GR * 64) + lane;
+#pragma unroll
+        for (int g = 0; g < GR; ++g) bqr[nj][g] = src[g * 64] * -2.0f;
+    }
+    const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled);
+
+    Top2 st[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
+
+    // ---- the lane's share of the thresholds (read again where a list has changed, as in the kernel above)
+    const bool exact_pair = l2_pair_is_exact(Ip, Jp, (float)(G * 8), false);
+    const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
+    const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
+    const float maxnormI = __uint_as_float(Ip->max_norm_bits);
+    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF) __attribute__((always_inline)) -> bool {
+        uint32_t q = (qt0 + (uint32_t)nj) * 32u + c;
+        asm volatile("" : "+v"(q));
+        const bool dead = !(q < nJ);                    // (covers a query tile beyond the last one too: its rows lie beyond nJ)
+        const uint32_t qo = dead ? 0u : q * 4u;
+        const float nb = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, 0, 0));
+        const float nbp = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, (int)(prefix_norm_offset(ntJ) * 4u), 0));
+        const float slkF = (P.err_scale + kPruneKeySlack) * (maxnormI + nb);
+        const float slk = exact_pair ? 0.0f : slkF;
+        nbs = nb + slk;
+        off = slk - nbp;
+        offF = slkF - nb;
+        return dead;
+    };
+    float thr[NJ], thrF[NJ], Tl[NJ], plT[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned)
+    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0;      // wave-uniform
+    bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
+
+    if (nI >= 2) {
+        // ---- dataset stream of the filter (A operand): the pair-norm tiles, float4 index = (t*GR + g)*64 + lane, and the full norms
+        const gf4p abase = (gf4p)redI;
+        const gf4p nbase = (gf4p)Ip->norms;               // tile t, quad qd -> float4 index t*8 + 2*qd + h
+        f32x4 abuf[PF];
+#pragma unroll
+        for (int s = 0; s < PF; ++s) abuf[s] = abase[s * 64 + lane];
+        f32x4 nrm[4];
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) nrm[qd] = nbase[2 * qd + h];
+
+        f32x16 accA[NJ], accB[NJ];
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms), rr = wave_uniform_rsrc(redI);
+        const uint32_t voffA = lane * 16u, voffN = h * 16u;
+        const uint32_t tileB = (uint32_t)G * 1024u, tileRB = (uint32_t)GR * 1024u;      // bytes per tile, per reduced tile
+        const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
+        const uint32_t hb = 4u * h;
+        // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes)
+        auto refresh = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) {
+                if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
+                float nbs, off, offF;
+                const bool dead = lane_terms(nj, nbs, off, offF);
+                const float e0 = st[nj].d0 + nbs, e1 = st[nj].d1 + nbs;
+                const float re1 = R * e1;
+                float T = e0 < re1 ? __builtin_fmaxf(re1, e0 * invR) : re1;
+                T += __builtin_fabsf(T) * 4.76837158203125e-07f;        // 2^-21: the roundings of e1, R e1, 1 / R and e0 / R
+                Tl[nj] = T;
+                const float x = T + off, xF = T + offF;
+                thr[nj] = dead ? -R3DM_INF : x + __builtin_fabsf(x) * 2.384185791015625e-07f;      // 2^-22: the rounding of x
+                thrF[nj] = dead ? -R3DM_INF : xF + __builtin_fabsf(xF) * 2.384185791015625e-07f;
+            }
+        };
+        // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
+        auto tile = [&](uint32_t t, f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ], bool live) __attribute__((always_inline)) -> bool {
+            l2_pairnorm_tile_filter<GR, NJ, PF>(rr, rn, voffA, voffN, t * tileRB, (t + 1) * 128u, abuf, nrm, bqr, cur, prev, st,
+                                                (t - 1) * 32u + hb, live);
+            if (live) { refresh(); pruned_under_thr = false; }
+            n_tested += 1u;
+            // a lane objects when one of its filter keys is not above its threshold (written so that a NaN key objects)
+            bool obj = false;
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrF[nj]);
+            if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true; return false; }
+            const bool on = l2_prune_tile_restart<G, GP, NJ, MODE == 0>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
+            if (!on) { n_pruned += 1u; pruned_under_thr = true; }
+            return on;
+        };
+        bool live = false;
+        uint32_t t = 0;
+        for (; t + 1 < ntI; t += 2) {
+            live = tile(t, accA, accB, live);
+            live = tile(t + 1, accB, accA, live);
+        }
+        if (t < ntI) {
+            if (tile(t, accA, accB, live)) {
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) top2_push(st[nj], accA[nj][r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        } else if (live) {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) top2_push(st[nj], accB[nj][r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+        }
+    }
+
+    // plT -> the lower bound of the pruned rows' distances (a lane whose query does not exist holds none)
+    float pruned_lb[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
+        const bool dead = !((qt0 + (uint32_t)nj) * 32u + c < nJ);
+        pruned_lb[nj] = dead ? -R3DM_INF : plT[nj];
+    }
+    if (lane == 0 && n_tested) {
+        atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
+        if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
+        if (n_filtered) atomicAdd(P.prune_cnt + 2, (unsigned long long)n_filtered);
+    }
+    l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
+}
+
+template <int G, int GP, int NJ, int PF, int WPS, int MODE>
+static hipError_t launch_l2_cascade_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+{
+    MatchParams P = Pin;
+    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
+    hipLaunchKernelGGL((l2_knn2_cascade_kernel<G, GP, NJ, PF, WPS, MODE>), dim3(grid), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
 // The pruning kernel serves ratio tests that leave it room: near R = 1 a row matters up to the runner-up's distance, no prefix
 // rules a tile out and the test only costs.  tools/prefix_prune_model.py on the synthetic SIFT collection (profiles/
 // prefix_prune_model_c2.txt): 96 % of the tiles stop at R = 0.36 (ratio 0.6), 72 % at R = 0.49 (ratio 0.7), 6 % at R = 0.64.
+// With the pair-norm filter in front the bound stays (tools/prefix_prune_model.py --filter pairnorm, profiles/
+// pairnorm_filter_model_c2.txt): at R = 0.49 the cascade still leaves less work than the plain kernel, at R = 0.64 neither test stops tiles.
 constexpr float kPruneMaxR = 0.5f;
+
+bool l2_prune_serves(uint32_t G, bool prune, bool raw_knn, float ratio_R)
+{
+    return G == 16 && prune && !raw_knn && ratio_R > 0.0f && ratio_R <= kPruneMaxR;
+}
 
 uint32_t l2_prefix_groups()
 {
@@ -617,20 +852,22 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
     }
     if (G == 18 && variant == 0) return launch_l2_t<18, 2, 3, 0, 2>(st, P, max_nj_tiles);
     if (G == 18 && variant == 2) return launch_l2_t<18, 2, 2, 3, 2>(st, P, max_nj_tiles);
-    //   109 .. 112: the pruning kernel with GP = 9 .. 12 prefix groups (registration writes the prefix norms of the same variant)
-    if (G == 16 && P.prune && P.knn_idx == nullptr && P.ratio_R > 0.0f && P.ratio_R <= kPruneMaxR) {
+    //   109 .. 112: the prefix test alone (the cascade without its filter) with GP = 9 .. 12 prefix groups (registration writes the
+    //   prefix norms of the same variant) | 120: the filter alone (no tile stops at the prefix test)
+    if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R)) {
         switch (variant) {
             case 109: return launch_l2_prune_t<16, 9, 2, 1, 2>(st, P, max_nj_tiles);
             case 110: return launch_l2_prune_t<16, 10, 2, 2, 2>(st, P, max_nj_tiles);
             case 111: return launch_l2_prune_t<16, 11, 2, 1, 2>(st, P, max_nj_tiles);
             case 112: return launch_l2_prune_t<16, 12, 2, 2, 2>(st, P, max_nj_tiles);
+            case 120: return launch_l2_cascade_t<16, (int)kPrefixGroups, 2, 2, 2, 1>(st, P, max_nj_tiles);
             default: break;
         }
     }
 #endif
     // match mode on 128-dimensional rows: the kernel that stops tiles early (r3dm_set_prefix_pruning, default on)
-    if (G == 16 && P.prune && P.knn_idx == nullptr && P.ratio_R > 0.0f && P.ratio_R <= kPruneMaxR)
-        return launch_l2_prune_t<16, (int)kPrefixGroups, 2, 2, 2>(st, P, max_nj_tiles);
+    if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R))
+        return launch_l2_cascade_t<16, (int)kPrefixGroups, 2, 2, 2, 0>(st, P, max_nj_tiles);
     switch (G) {
         case 8:  return launch_l2_t<8, 2, 4, 3, 2>(st, P, max_nj_tiles);
         case 16: return launch_l2_t<16, 2, 4, 3, 2>(st, P, max_nj_tiles);

@@ -7,6 +7,7 @@
 //   kTestsEachKey, kTestsEachKeyExact  whether a list policy guards every single push with a ballot of its own
 //   l2_tile_step                       one dataset tile on the f32 tiles          (v_mfma_f32_32x32x2_f32)
 //   l2_prune_tile_prefix / _finish     ... stopped after a prefix of its dimensions when no lane needs the rest (match mode)
+//   l2_pairnorm_tile_filter / l2_prune_tile_restart   ... ruled out on its pair norms first; a tile that is not starts over
 //   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
 //   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
@@ -254,6 +255,131 @@ __device__ __forceinline__ bool l2_prune_tile_finish(__amdgpu_buffer_rsrc_t ra, 
                 cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bqs[nj][g - GP][cc], cur[nj], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// f32 tiles, match mode: the pair-norm filter in front of the prefix test (l2_knn2_cascade_kernel; Top2 lists only).
+// The same contraction over the REDUCED rows (the table behind MatchParams::prune_cnt: GR = G / 2 groups of 8 pair norms per tile,
+// tiles contiguous), accumulators started from the rows' FULL norms: after GR groups they hold kf = |a|^2 - 2 sum_k sa_k sb_k, and
+// kf + |b|^2 <= |a - b|^2 (Cauchy-Schwarz per pair; the proof and the slack: kernels_match.hip above the kernel).  The epilogue of
+// tile t-1 is spread over the GR groups as in l2_prune_tile_prefix; the A window simply runs on (reduced tiles follow one another),
+// so a filtered tile exposes no load latency.  The caller decides on `cur`.
+// ------------------------------------------------------------------------------------------------
+template <int GR, int NJ, int PF>
+__device__ __forceinline__ void l2_pairnorm_tile_filter(__amdgpu_buffer_rsrc_t rr, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                        uint32_t soffR, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4],
+                                                        const f32x4 (&bqr)[NJ][GR], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
+                                                        Top2 (&st)[NJ], uint32_t prev_rowbase, bool prev_live)
+{
+    static_assert(GR > 2 && GR % PF == 0, "the window keeps group g in slot g % PF from tile to tile");
+    // soffR: byte offset of this tile's reduced group 0; soffN: of the NEXT tile's norms
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cur[nj][r] = nrm[r >> 2][r & 3];
+#pragma unroll
+    for (int g = 0; g < GR; ++g) {
+        const f32x4 a = abuf[g % PF];
+        abuf[g % PF] = bload16(rr, voffA, soffR + (uint32_t)(g + PF) * 1024u);
+        if (g == 2) {   // next tile's norms
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+        }
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], bqr[nj][g][cc], cur[nj], 0, 0, 0);
+        if (prev_live) {
+            // this group's share of the previous tile's keys: test-and-skip as in l2_tile_step<PIPE 3>
+            bool any = false;
+#pragma unroll
+            for (int r = (g * 16) / GR; r < ((g + 1) * 16) / GR; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < st[nj].d2;
+            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+#pragma unroll
+                for (int r = (g * 16) / GR; r < ((g + 1) * 16) / GR; ++r)
+#pragma unroll
+                    for (int nj = 0; nj < NJ; ++nj)
+                        top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// A tile the filter let through, from its group 0: the prefix norms, GP groups, the prefix test against `thr`, then the suffix norms
+// and groups GP .. G-1 -- the MFMAs of l2_prune_tile_prefix / _finish in the same order on the same operands, so the keys of a tile
+// that finishes are the same floats.  Nothing of it is in registers when it starts (the wave holds the reduced query fragments
+// only): dataset and query fragments of all G groups stream through a W-deep window of their own, from the dataset's and the query
+// view's tiles; the first W groups' latency is exposed once per such tile -- the other wave of the SIMD has the matrix pipe meanwhile.
+// The filter's window (next reduced tile) and norms stay untouched.  Returns whether `cur` holds the keys of a finished tile
+// (wave-uniform).  TEST_PREFIX = false (developer ablation): the tile always finishes.
+template <int G, int GP, int NJ, bool TEST_PREFIX>
+__device__ __forceinline__ bool l2_prune_tile_restart(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                      uint32_t soffA, uint32_t soffN, uint32_t soffP, __amdgpu_buffer_rsrc_t rq,
+                                                      const uint32_t (&soffQ)[NJ], f32x16 (&cur)[NJ], const float (&thr)[NJ])
+{
+    constexpr int W = 2;
+    static_assert(GP > 2 && GP < G && G % W == 0, "window slots");
+    f32x4 wa[W], wb[NJ][W];
+#pragma unroll
+    for (int s = 0; s < W; ++s) {
+        wa[s] = bload16(ra, voffA, soffA + (uint32_t)s * 1024u);
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) wb[nj][s] = bload16(rq, voffA, soffQ[nj] + (uint32_t)s * 1024u);
+    }
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const f32x4 np = bload16(rn, voffN, soffP + (uint32_t)qd * 32u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) cur[nj][4 * qd + k] = np[k];
+    }
+    auto group = [&](int g) __attribute__((always_inline)) {
+        const f32x4 a = wa[g % W];
+        f32x4 b[NJ];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) b[nj] = wb[nj][g % W] * -2.0f;
+        if (g + W < G) {
+            wa[g % W] = bload16(ra, voffA, soffA + (uint32_t)(g + W) * 1024u);
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) wb[nj][g % W] = bload16(rq, voffA, soffQ[nj] + (uint32_t)(g + W) * 1024u);
+        }
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], b[nj][cc], cur[nj], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    };
+#pragma unroll
+    for (int g = 0; g < GP; ++g) group(g);
+    if constexpr (TEST_PREFIX) {
+        // a lane objects when one of its prefix keys is not above its threshold (written so that a NaN key objects)
+        bool obj = false;
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thr[nj]);
+        if (__builtin_amdgcn_ballot_w64(obj) == 0ull) return false;
+    }
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const f32x4 nf = bload16(rn, voffN, soffN + (uint32_t)qd * 32u), np = bload16(rn, voffN, soffP + (uint32_t)qd * 32u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            // |a|^2 - |a_P|^2; a padding row (both +inf) keeps its +inf key
+            const float sn = np[k] < R3DM_INF ? nf[k] - np[k] : 0.0f;
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) cur[nj][4 * qd + k] += sn;
+        }
+    }
+#pragma unroll
+    for (int g = GP; g < G; ++g) group(g);
     return true;
 }
 

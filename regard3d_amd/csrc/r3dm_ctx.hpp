@@ -524,7 +524,7 @@ struct r3dm_ctx {
     DevBuf d_verdict;                                        // verdict words of count-tile checks launched by ensure_layouts
     uint64_t n_ring_uploads = 0, n_direct_uploads = 0;       // views that went through the ring / were read where the caller had them
     // scratch (grown on demand, reused across calls)
-    DevBuf d_pairs, d_nn, d_knn_idx, d_knn_dist, d_fb, d_cnt, d_out, d_pair_off, d_pair_cnt, d_raw;
+    DevBuf d_pairs, d_pairnorm, d_pairnorm_tiles, d_nn, d_knn_idx, d_knn_dist, d_fb, d_cnt, d_out, d_pair_off, d_pair_cnt, d_raw;
     // geometric filters: one set of work buffers per model kind (0 F, 1 H, 2 E), so that r3dm_filter_FEH can run the three
     // AC-RANSAC kernels of a putative graph side by side (a collection with few, long pairs leaves most CUs idle under one)
     FilterBufs fb[3];
@@ -551,7 +551,7 @@ struct r3dm_ctx {
     PinBuf pin_desc;                                        // page-locked landing zone of the LIOP descriptors of a batch
     bool integer_mfma = false;                              // r3dm_set_integer_mfma
     bool prefix_pruning = true;                             // r3dm_set_prefix_pruning: match mode on 128-dimensional rows stops tiles early
-    uint64_t prune_counts[2] = {0, 0};                      // r3dm_get_prefix_pruning_counts: wave tiles tested / pruned in the last match call
+    uint64_t prune_counts[3] = {0, 0, 0};                   // r3dm_get_prefix_pruning_counts: wave tiles tested / pruned in the last match call; [2] r3dm_get_pair_filter_counts: pruned by the filter
     bool split_mfma = false;                                // r3dm_set_split_mfma
     bool hamming_mfma = false;                              // r3dm_set_hamming_mfma
     bool knn_narrow_tiles = false;                          // r3dm_set_knn_narrow_tiles

@@ -11,7 +11,9 @@ above the kernel; l2_finish_queries<PRUNE> has the proof): per (query, half) wit
   T = R e1 if e0 >= R e1 else max(R e1, e0 / R), rounded up;  a tile is pruned when every prefix distance of every lane lies above its T;
   pl = the smallest T a lane pruned under.  Verdict from the merged lists (ea, eb) and PL = min of both halves' pl:
   not ea < R eb -> no match;  ea < R eb and ea < R PL -> the best seen row;  else the exact scan.
-Distances are exact here (integer-valued rows: float32 sums below 2^24), as the kernel's are for such pairs."""
+Distances are exact here (integer-valued rows: float32 sums below 2^24), as the kernel's are for such pairs.
+   python tools/prefix_prune_model.py --filter pairnorm [--gp 12] ...
+the cascade of l2_knn2_cascade_kernel: the pair-norm filter in front of the prefix test (model_pair_cascade)."""
 import argparse
 import os
 import sys
@@ -99,6 +101,130 @@ def model_pair(a, b, gp, R):
             "matches": int((truth >= 0).sum()), "queries": nJ}
 
 
+U = 2.0 ** -24
+ERR_SCALE = 4.25 * 128 * U            # cert_slack_factor (api_match.cpp) of 128-dimensional rows on the f32 tiles
+KEY_SLACK = 8 * U                     # kPruneKeySlack (kernels_match_common.hpp)
+
+
+def pair_norms(x):
+    """[n, D] float32 -> [n, D / 2] float32, element k >= sqrt(x[2k]^2 + x[2k+1]^2): stage_pairnorm_kernel (kernels_match.hip) --
+    the root in double, rounded to float32, moved one float up unless it lies above the double root by 2^-40 of it already"""
+    x64 = x.astype(np.float64)
+    rd = np.sqrt(x64[:, 0::2] ** 2 + x64[:, 1::2] ** 2)
+    f = rd.astype(np.float32)
+    up = f.astype(np.float64) < rd * (1.0 + 2.0 ** -40)
+    return np.where(up, np.nextafter(f, INF), f).astype(np.float32)
+
+
+def _exact_pair(a, b):
+    """l2_pair_is_exact (kernels_match_common.hpp): integer-valued views whose partial sums stay below 2^24"""
+    if not (np.all(a == np.rint(a)) and np.all(b == np.rint(b))):
+        return False
+    mI, mJ = float(np.abs(a).max(initial=0.0)), float(np.abs(b).max(initial=0.0))
+    d = float(a.shape[1])
+    if (a < 0).any() or (b < 0).any():
+        return d * (mI + mJ) ** 2 < 2.0 ** 24
+    return 2 * d * mI * mJ < 2.0 ** 24 and d * mI * mI < 2.0 ** 24 and d * mJ * mJ < 2.0 ** 24
+
+
+def pairnorm_bound(a, b):
+    """-> (LB [nI, nJ], slack [nJ]) in float64: LB = |a|^2 + |b|^2 - 2 sum_k sa_k sb_k <= |a - b|^2, and the slack the kernel's filter
+    carries for its own float32 evaluation of it, (err_scale + kPruneKeySlack) (max|a|^2 + |b|^2)"""
+    sa, sb = pair_norms(a).astype(np.float64), pair_norms(b).astype(np.float64)
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    na, nb = (a64 * a64).sum(1), (b64 * b64).sum(1)
+    return na[:, None] + nb[None, :] - 2.0 * sa @ sb.T, (ERR_SCALE + KEY_SLACK) * (na.max(initial=0.0) + nb)
+
+
+def model_pair_cascade(a, b, gp, R, filter_only=False):
+    """the cascade of l2_knn2_cascade_kernel: per wave tile the pair-norm filter (8 groups), and behind it, for a tile some lane still
+    needs, the prefix test of model_pair on the tile run again from its group 0.  Distances in float64 (exact for the integer-valued
+    views; the reference for any other, whose prefix test then carries the certificate's slack as the kernel's does).
+    -> model_pair's dict + filtered (tiles the filter pruned), work (MFMA groups run, of 16 a tile)"""
+    R64 = float(np.float32(R))
+    nI, nJ = a.shape[0], b.shape[0]
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    D = ((a64[:, None, :] - b64[None, :, :]) ** 2).sum(2) if nI * nJ <= 1 << 16 else \
+        (a64 * a64).sum(1)[:, None] - 2.0 * a64 @ b64.T + (b64 * b64).sum(1)[None, :]
+    ap, bp = a64[:, :8 * gp], b64[:, :8 * gp]
+    DP = (ap * ap).sum(1)[:, None] - 2.0 * ap @ bp.T + (bp * bp).sum(1)[None, :]
+    LB, slackF = pairnorm_bound(a, b)
+    slackP = np.zeros(nJ) if _exact_pair(a, b) else slackF
+    n_tiles = (nI + 31) // 32
+    n_waves = (nJ + 63) // 64
+    half_of_row = (np.arange(32) >> 2) & 1
+    d0 = np.full((2, nJ), np.inf); d1 = np.full((2, nJ), np.inf)
+    i0 = np.full((2, nJ), -1, np.int64); i1 = np.full((2, nJ), -1, np.int64)
+    pl = np.full((2, nJ), np.inf)
+    wave_of_q = np.arange(nJ) // 64
+    tiles = pruned = filtered = work = 0
+    for t in range(n_tiles):
+        lo, hi = t * 32, min(nI, t * 32 + 32)
+        rows = np.arange(lo, hi)
+        with np.errstate(invalid="ignore"):
+            e0, e1 = d0 + slackP, d1 + slackP                                  # the lists' distances as the kernel sees them (+ slack)
+            re1 = R64 * e1
+            T = np.where(e0 < re1, np.maximum(re1, e0 / R64), re1)
+            T = T + np.abs(T) * 2.0 ** -21
+        objF = np.zeros((2, nJ), bool); objP = np.zeros((2, nJ), bool)
+        for h in (0, 1):
+            m = half_of_row[: hi - lo] == h
+            if m.any():
+                objF[h] = ~((LB[rows[m]] - slackF[None, :]).min(0) > T[h])
+                objP[h] = ~((DP[rows[m]] - slackP[None, :]).min(0) > T[h])
+        wF = np.zeros(n_waves, bool); wP = np.zeros(n_waves, bool)
+        np.logical_or.at(wF, wave_of_q, objF[0] | objF[1])
+        np.logical_or.at(wP, wave_of_q, objP[0] | objP[1])
+        if filter_only:
+            wP[:] = True
+        wave_on = wF & wP
+        tiles += n_waves
+        filtered += int((~wF).sum())
+        pruned += int((~wave_on).sum())
+        work += 8 * n_waves + gp * int((wF & ~wP).sum()) + 16 * int(wave_on.sum())
+        go = wave_on[wave_of_q]
+        pl[:, ~go] = np.minimum(pl[:, ~go], T[:, ~go])
+        if go.any():
+            q = np.flatnonzero(go)
+            for h in (0, 1):
+                m = half_of_row[: hi - lo] == h
+                if m.any():
+                    f0, f1, j0, j1 = d0[h, q], d1[h, q], i0[h, q], i1[h, q]
+                    _push(f0, j0, f1, j1, D[rows[m]][:, q], rows[m])
+                    d0[h, q], d1[h, q], i0[h, q], i1[h, q] = f0, f1, j0, j1
+    cd = np.concatenate([d0, d1]); ci = np.concatenate([i0, i1]).astype(np.float64)
+    ci[ci < 0] = np.inf
+    order = np.lexsort((ci, cd), axis=0)
+    ea = np.take_along_axis(cd, order[:1], 0)[0]; eb = np.take_along_axis(cd, order[1:2], 0)[0]
+    ia = np.take_along_axis(ci, order[:1], 0)[0]
+    PL = pl.min(0)
+    with np.errstate(invalid="ignore"):
+        passes = ea < R64 * eb
+        verdict = np.where(~passes, -1, np.where(ea < R64 * PL, ia, -2)).astype(np.int64)
+    o = np.argsort(D, axis=0, kind="stable")[:2]
+    t1 = np.take_along_axis(D, o[:1], 0)[0]; t2 = np.take_along_axis(D, o[1:2], 0)[0]
+    truth = np.where(t1 < R64 * t2, o[0], -1)
+    decided = verdict != -2
+    return {"tiles": tiles, "pruned": pruned, "filtered": filtered, "work": work, "fallback": int((~decided).sum()),
+            "wrong": int((decided & (verdict != truth)).sum()), "matches": int((truth >= 0).sum()), "queries": nJ}
+
+
+def run_cascade(views, pairs, gp, ratio, squared=True, out=print):
+    R = ratio * ratio if squared else ratio
+    keys = ("tiles", "pruned", "filtered", "work", "fallback", "wrong", "matches", "queries")
+    acc = dict.fromkeys(keys, 0)
+    line = lambda r: (f"filter {r['filtered'] / r['tiles']:.4f}  prefix behind it {(r['pruned'] - r['filtered']) / r['tiles']:.4f}  "
+                      f"MFMA work left {r['work'] / (16 * r['tiles']):.4f}")
+    for (i, j) in pairs:
+        r = model_pair_cascade(views[i], views[j], gp, R)
+        for k in keys:
+            acc[k] += r[k]
+        out(f"pairnorm + GP {gp:2d}  pair ({i},{j})  {line(r)}  matches {r['matches']:5d}  exact scan {r['fallback']:4d}  wrong verdicts {r['wrong']}")
+    out(f"pairnorm + GP {gp:2d}  ALL {len(pairs)} pairs, {acc['queries']} queries, R = {R:.4f}: {line(acc)}  "
+        f"exact scan {acc['fallback']} ({acc['fallback'] / max(acc['queries'], 1):.2e})  wrong verdicts {acc['wrong']}")
+    return acc
+
+
 def run(views, pairs, gps, ratio, squared=True, out=print):
     R = ratio * ratio if squared else ratio
     total = {}
@@ -126,6 +252,8 @@ def main():
     ap.add_argument("--gp", type=int, nargs="+", default=[9, 10, 11, 12])
     ap.add_argument("--ratio", type=float, nargs="+", default=[0.6])
     ap.add_argument("--pairs", type=int, default=0, help="pairs (0, 1 .. n); default: every other view")
+    ap.add_argument("--filter", choices=["none", "pairnorm"], default="none", help="pairnorm: the cascade, the pair-norm filter in front of GP = --gp[-1]")
+    ap.add_argument("--summary", action="store_true", help="with --filter pairnorm: only the ALL line")
     a = ap.parse_args()
     from regard3d_amd import synth
     descs, _, _ = synth.make_scene_torch(a.images, a.feat, seed=a.seed, device="cpu", kind=a.kind)
@@ -133,6 +261,9 @@ def main():
     pairs = [(0, j) for j in range(1, (a.pairs or a.images - 1) + 1)]
     bad = 0
     for ratio in a.ratio:
+        if a.filter == "pairnorm":
+            bad += run_cascade(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print)["wrong"]
+            continue
         tot = run(views, pairs, a.gp, ratio)
         bad += sum(v["wrong"] for v in tot.values())
     sys.exit(1 if bad else 0)
