@@ -42,12 +42,6 @@
 
 #define AK_PI 3.1415926535897932384626433832795
 
-typedef struct {
-    int w, h, octave, sublevel, sigma_size, border;
-    float esigma, etime, ratio;
-    float *Lt, *Lsmooth, *Lx, *Ly, *Lxx, *Lxy, *Lyy, *Ldet;
-} ak_level;
-
 static int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 static int refl101(int p, int len)
 {
@@ -177,8 +171,8 @@ static void pm_g2(const float* Lx, const float* Ly, size_t n, float k, float* ds
     for (size_t i = 0; i < n; ++i) dst[i] = 1.0f / (1.0f + ((Lx[i] * Lx[i] + Ly[i] * Ly[i]) * inv_k2));
 }
 
-/* compute_k_percentileV2 */
-float orc_akaze_kcontrast(const float* Lx, const float* Ly, int w, int h, float perc, int nbins)
+/* compute_k_percentileV2.  hmax_out, hist_out (optional; nbins entries, all 0 when the maximum is 0: the reference forms no histogram then) */
+static float kcontrast_impl(const float* Lx, const float* Ly, int w, int h, float perc, int nbins, float* hmax_out, int* hist_out)
 {
     const size_t total = (size_t)(w - 2) * (h - 2);
     float* modg = (float*)malloc(sizeof(float) * total);
@@ -190,6 +184,8 @@ float orc_akaze_kcontrast(const float* Lx, const float* Ly, int w, int h, float 
         }
     float hmax = 0.0f;
     for (size_t i = 0; i < total; ++i) if (hmax < modg[i]) hmax = modg[i];
+    if (hmax_out) *hmax_out = hmax;
+    if (hist_out) memset(hist_out, 0, sizeof(int) * (size_t)nbins);
     if (hmax == 0.0f) { free(modg); return 0.03f; }
     const float sc = (nbins - 1) / hmax;
     int* hist = (int*)calloc((size_t)nbins, sizeof(int));
@@ -201,8 +197,13 @@ float orc_akaze_kcontrast(const float* Lx, const float* Ly, int w, int h, float 
         if (nelements >= nthreshold) { ret = (float)hmax * k / nbins; break; }
         nelements = nelements + hist[k];
     }
+    if (hist_out) memcpy(hist_out, hist, sizeof(int) * (size_t)nbins);
     free(hist); free(modg);
     return ret;
+}
+float orc_akaze_kcontrast(const float* Lx, const float* Ly, int w, int h, float perc, int nbins)
+{
+    return kcontrast_impl(Lx, Ly, w, h, perc, nbins, NULL, NULL);
 }
 
 /* nld_step_scalarV2 + the update lt += lstep * 0.5 * step */
@@ -605,144 +606,189 @@ int orc_akaze_tail(int nl, const orc_ak_tail_level* lv, const float* const* plan
     return n_out;
 }
 
-/* Regard3DFeatures::detectKeypoints, "Fast-AKAZE" arm: image = h x w floats in [0, 1].
- * keypoints out: (x, y, size, angle_degrees) x cap; responses/levels optional.  Returns the number detected (may exceed cap:
- * only the first cap are written).  dbg_level >= 0: copies that level's Ldet (and Lt) into dbg_ldet / dbg_lt if non-NULL. */
-static int akaze_detect_impl(const float* image, int w, int h, float dthreshold, float* kps, int cap, float* responses, int* levels,
-                             int dbg_level, float* dbg_ldet, float* dbg_lt, float* dbg_info, unsigned char* mldb /* cap x 61 or NULL */)
+/* Allocate_Memory_Evolution with the AKAZE2::create() defaults: the level table of a w x h image (at most 16 entries) -> n_levels */
+int orc_akaze_levels(int w, int h, orc_ak_head_level* lv)
 {
     const int omax = 4, nsub = 4;
     const float soffset = 1.6f, dfac = 1.5f;
     const float smax = 10.0f * sqrtf(2.0f);
-    ak_level lv[16];
     int nl = 0;
-    {   /* Allocate_Memory_Evolution */
-        int lh = h, lw = w, power = 1, stop = 0;
-        for (int i = 0; i < omax && !stop; ++i) {
-            for (int j = 0; j < nsub; ++j) {
-                ak_level e; memset(&e, 0, sizeof(e));
-                e.w = lw; e.h = lh;
-                e.esigma = soffset * powf(2.f, (float)j / nsub + i);
-                e.sigma_size = fround(e.esigma * dfac / power);
-                e.border = fround(smax * e.sigma_size) + 1;
-                e.etime = 0.5f * (e.esigma * e.esigma);
-                e.octave = i; e.sublevel = j; e.ratio = (float)power;
-                if (e.border * 2 + 1 >= lw || e.border * 2 + 1 >= lh) { stop = 1; break; }
-                lv[nl++] = e;
+    int lh = h, lw = w, power = 1;
+    for (int i = 0; i < omax; ++i) {
+        for (int j = 0; j < nsub; ++j) {
+            orc_ak_head_level e; memset(&e, 0, sizeof(e));
+            e.w = lw; e.h = lh;
+            e.esigma = soffset * powf(2.f, (float)j / nsub + i);
+            e.sigma_size = fround(e.esigma * dfac / power);
+            e.border = fround(smax * e.sigma_size) + 1;
+            e.etime = 0.5f * (e.esigma * e.esigma);
+            e.octave = i; e.sublevel = j; e.ratio = (float)power;
+            e.psize = e.esigma * dfac;
+            if (e.border * 2 + 1 >= lw || e.border * 2 + 1 >= lh) return nl;
+            lv[nl++] = e;
+        }
+        power <<= 1; lh >>= 1; lw >>= 1;
+        if (lw < 80 || lh < 40) break;
+    }
+    return nl;
+}
+
+/* Find_Scale_Space_Extrema (threaded variant), the loop of ONE level on a determinant plane: the 3 x 3 maxima above the threshold inside
+ * the border, in raster order; a candidate within psize of a kept point (the first such in list order) replaces it in place when its
+ * response is larger and is dropped otherwise; else it is appended.  list: the first cap kept points (x, y, response) in insertion
+ * order; *n_cand (optional): candidates before the pruning.  Returns the number kept. */
+int orc_akaze_extrema(const float* Ldet, int w, int h, int border, float ratio, float psize, float dthreshold, float* list, int cap,
+                      int* n_cand)
+{
+    ak_list kl = { NULL, 0, 0 };
+    int nc = 0;
+    for (int y = border; y < h - border; ++y) {
+        const float* prev = Ldet + (size_t)(y - 1) * w; const float* curr = prev + w; const float* next = curr + w;
+        for (int x = border; x < w - border; ++x) {
+            const float value = curr[x];
+            if (value <= dthreshold) continue;
+            if (value <= curr[x - 1] || value <= curr[x + 1]) continue;
+            if (value <= prev[x - 1] || value <= prev[x] || value <= prev[x + 1]) continue;
+            if (value <= next[x - 1] || value <= next[x] || value <= next[x + 1]) continue;
+            ++nc;
+            ak_kp p = { (float)(x * ratio), (float)(y * ratio), psize, value, 0, 1 };
+            int found = -1;
+            for (int q = 0; q < kl.n; ++q) {
+                const float dx = p.x - kl.v[q].x, dy = p.y - kl.v[q].y;
+                if (dx * dx + dy * dy <= p.size * p.size) { found = q; break; }
             }
-            if (stop) break;
-            power <<= 1; lh >>= 1; lw >>= 1;
-            if (lw < 80 || lh < 40) break;
+            if (found >= 0) { if (p.response > kl.v[found].response) kl.v[found] = p; continue; }
+            kl_push(&kl, p);
         }
     }
-    if (nl == 0) return 0;
-    for (int i = 0; i < nl; ++i) {
-        const size_t n = (size_t)lv[i].w * lv[i].h;
-        float* blk = (float*)malloc(sizeof(float) * n * 8);
-        lv[i].Lt = blk; lv[i].Lsmooth = blk + n; lv[i].Lx = blk + 2 * n; lv[i].Ly = blk + 3 * n;
-        lv[i].Lxx = blk + 4 * n; lv[i].Lxy = blk + 5 * n; lv[i].Lyy = blk + 6 * n; lv[i].Ldet = blk + 7 * n;
-    }
-    const size_t n0 = (size_t)w * h;
-    float* wx = (float*)malloc(sizeof(float) * n0); float* wy = (float*)malloc(sizeof(float) * n0);
-    float* wflow = (float*)malloc(sizeof(float) * n0); float* wstep = (float*)malloc(sizeof(float) * n0);
+    for (int j = 0; j < kl.n && j < cap; ++j) { list[3 * j] = kl.v[j].x; list[3 * j + 1] = kl.v[j].y; list[3 * j + 2] = kl.v[j].response; }
+    if (n_cand) *n_cand = nc;
+    const int n = kl.n;
+    free(kl.v);
+    return n;
+}
 
-#define AK_HESSIAN(e)                                                                               \
+/* The detector's head: Create_Nonlinear_Scale_Space and, per level, Find_Scale_Space_Extrema's first loop.  lv: the table of
+ * orc_akaze_levels(w, h), nl > 0 entries.  planes [nl][4]: Ldet, Lx, Ly, Lt of every level (w_i x h_i floats each, the caller's).
+ * lists [nl]: list_cap[i] triples each; n_cand, n_list [nl]: candidates before and kept points after the in-level pruning.
+ * kstate [10]: the maximum of the gradient modulus, the base k-contrast, then 1 / (k_o k_o) of octaves 0 .. 7 with k_o = k_{o-1} 0.75
+ * (the factor the conductivity of octave o takes); hist [300]: the histogram (0 when the maximum is 0 or the image has one level). */
+void orc_akaze_head(const float* image, int w, int h, float dthreshold, int nl, const orc_ak_head_level* lv, float* const* planes,
+                    float* const* lists, const int* list_cap, int* n_cand, int* n_list, float* kstate, int* hist)
+{
+    const float soffset = 1.6f;
+    const size_t n0 = (size_t)w * h;
+    float* work = (float*)malloc(sizeof(float) * n0 * 8);
+    float* wx = work, *wy = work + n0, *wflow = work + 2 * n0, *wstep = work + 3 * n0;
+    float* Lsmooth = work + 4 * n0, *Lxx = work + 5 * n0, *Lxy = work + 6 * n0, *Lyy = work + 7 * n0;
+#define AK_LDET(i) planes[4 * (i)]
+#define AK_LX(i) planes[4 * (i) + 1]
+#define AK_LY(i) planes[4 * (i) + 2]
+#define AK_LT(i) planes[4 * (i) + 3]
+#define AK_HESSIAN(i)                                                                               \
     do {                                                                                            \
-        orc_akaze_scaled_deriv((e).Lsmooth, (e).w, (e).h, (e).sigma_size, 1, (e).Lx);               \
-        orc_akaze_scaled_deriv((e).Lx, (e).w, (e).h, (e).sigma_size, 1, (e).Lxx);                   \
-        orc_akaze_scaled_deriv((e).Lx, (e).w, (e).h, (e).sigma_size, 0, (e).Lxy);                   \
-        orc_akaze_scaled_deriv((e).Lsmooth, (e).w, (e).h, (e).sigma_size, 0, (e).Ly);               \
-        orc_akaze_scaled_deriv((e).Ly, (e).w, (e).h, (e).sigma_size, 0, (e).Lyy);                   \
-        const size_t nn = (size_t)(e).w * (e).h;                                                    \
-        for (size_t q = 0; q < nn; ++q) (e).Ldet[q] = (e).Lxx[q] * (e).Lyy[q] - (e).Lxy[q] * (e).Lxy[q]; \
+        orc_akaze_scaled_deriv(Lsmooth, lv[i].w, lv[i].h, lv[i].sigma_size, 1, AK_LX(i));            \
+        orc_akaze_scaled_deriv(AK_LX(i), lv[i].w, lv[i].h, lv[i].sigma_size, 1, Lxx);                \
+        orc_akaze_scaled_deriv(AK_LX(i), lv[i].w, lv[i].h, lv[i].sigma_size, 0, Lxy);                \
+        orc_akaze_scaled_deriv(Lsmooth, lv[i].w, lv[i].h, lv[i].sigma_size, 0, AK_LY(i));            \
+        orc_akaze_scaled_deriv(AK_LY(i), lv[i].w, lv[i].h, lv[i].sigma_size, 0, Lyy);                \
+        const size_t nn = (size_t)lv[i].w * lv[i].h;                                                \
+        for (size_t q = 0; q < nn; ++q) AK_LDET(i)[q] = Lxx[q] * Lyy[q] - Lxy[q] * Lxy[q];          \
     } while (0)
 
     /* Create_Nonlinear_Scale_Space */
-    float kcontrast = 0.03f;
-    orc_akaze_gaussian(image, w, h, soffset, lv[0].Lsmooth);
-    AK_HESSIAN(lv[0]);
+    float kcontrast = 0.03f, hmax = 0.0f;
+    memset(hist, 0, sizeof(int) * 300);
+    orc_akaze_gaussian(image, w, h, soffset, Lsmooth);
+    AK_HESSIAN(0);
+    memcpy(AK_LT(0), Lsmooth, sizeof(float) * n0);
     if (nl > 1) {
         orc_akaze_gaussian(image, w, h, 1.0f, wflow);
         orc_akaze_scharr(wflow, w, h, wx, wy);
-        kcontrast = orc_akaze_kcontrast(wx, wy, w, h, 0.7f, 300);
+        kcontrast = kcontrast_impl(wx, wy, w, h, 0.7f, 300, &hmax, hist);
     }
-    memcpy(lv[0].Lt, lv[0].Lsmooth, sizeof(float) * n0);
+    kstate[0] = hmax; kstate[1] = kcontrast;
+    { float k = kcontrast; for (int o = 0; o < 8; ++o) { kstate[2 + o] = 1.0f / (k * k); k = k * 0.75f; } }
     for (int i = 1; i < nl; ++i) {
-        ak_level* e = &lv[i];
+        const orc_ak_head_level* e = &lv[i];
         const size_t n = (size_t)e->w * e->h;
-        if (e->octave > lv[i - 1].octave) { orc_akaze_halfsample(lv[i - 1].Lt, lv[i - 1].w, lv[i - 1].h, e->Lt); kcontrast = kcontrast * 0.75f; }
-        else memcpy(e->Lt, lv[i - 1].Lt, sizeof(float) * n);
-        orc_akaze_gaussian(e->Lt, e->w, e->h, 1.0f, e->Lsmooth);
-        orc_akaze_scharr(e->Lsmooth, e->w, e->h, wx, wy);
-        AK_HESSIAN(*e);
+        if (e->octave > lv[i - 1].octave) { orc_akaze_halfsample(AK_LT(i - 1), lv[i - 1].w, lv[i - 1].h, AK_LT(i)); kcontrast = kcontrast * 0.75f; }
+        else memcpy(AK_LT(i), AK_LT(i - 1), sizeof(float) * n);
+        orc_akaze_gaussian(AK_LT(i), e->w, e->h, 1.0f, Lsmooth);
+        orc_akaze_scharr(Lsmooth, e->w, e->h, wx, wy);
+        AK_HESSIAN(i);
         pm_g2(wx, wy, n, kcontrast, wflow);
         float tau[256];
         const int nt = orc_akaze_fed_tau(e->etime - lv[i - 1].etime, tau);
         for (int j = 0; j < nt; ++j) {
-            nld_step(e->Lt, wflow, e->w, e->h, wstep);
+            nld_step(AK_LT(i), wflow, e->w, e->h, wstep);
             const float step_size = tau[j];
-            for (size_t q = 0; q < n; ++q) e->Lt[q] += wstep[q] * 0.5f * step_size;
+            for (size_t q = 0; q < n; ++q) AK_LT(i)[q] += wstep[q] * 0.5f * step_size;
         }
     }
-    if (dbg_info) { dbg_info[0] = (float)nl; dbg_info[1] = kcontrast; }
+    /* Find_Scale_Space_Extrema, the first loop of every level */
+    for (int i = 0; i < nl; ++i)
+        n_list[i] = orc_akaze_extrema(AK_LDET(i), lv[i].w, lv[i].h, lv[i].border, lv[i].ratio, lv[i].psize, dthreshold, lists[i], list_cap[i],
+                                      &n_cand[i]);
+#undef AK_HESSIAN
+#undef AK_LDET
+#undef AK_LX
+#undef AK_LY
+#undef AK_LT
+    free(work);
+}
+
+/* Regard3DFeatures::detectKeypoints, "Fast-AKAZE" arm: image = h x w floats in [0, 1].
+ * keypoints out: (x, y, size, angle_degrees) x cap; responses/levels optional.  Returns the number detected (may exceed cap:
+ * only the first cap are written).  dbg_level >= 0: copies that level's Ldet (and Lt) into dbg_ldet / dbg_lt if non-NULL.
+ * The head (scale space, extrema, in-level pruning) is orc_akaze_head, the rest orc_akaze_tail. */
+static int akaze_detect_impl(const float* image, int w, int h, float dthreshold, float* kps, int cap, float* responses, int* levels,
+                             int dbg_level, float* dbg_ldet, float* dbg_lt, float* dbg_info, unsigned char* mldb /* cap x 61 or NULL */)
+{
+    orc_ak_head_level lv[16];
+    const int nl = orc_akaze_levels(w, h, lv);
+    if (nl == 0) return 0;
+    float* planes[16 * 4];
+    float* lists[16];
+    int list_cap[16], n_cand[16], n_list[16], hist[300];
+    float kstate[10];
+    for (int i = 0; i < nl; ++i) {
+        const size_t n = (size_t)lv[i].w * lv[i].h;
+        float* blk = (float*)malloc(sizeof(float) * n * 4);
+        for (int q = 0; q < 4; ++q) planes[4 * i + q] = blk + q * n;
+        list_cap[i] = ((lv[i].w + 1) / 2) * ((lv[i].h + 1) / 2);           /* a strict 3 x 3 maximum excludes its eight neighbours */
+        lists[i] = (float*)malloc(sizeof(float) * 3 * (size_t)(list_cap[i] + 1));
+    }
+    orc_akaze_head(image, w, h, dthreshold, nl, lv, planes, lists, list_cap, n_cand, n_list, kstate, hist);
+    if (dbg_info) {
+        float kcontrast = kstate[1];
+        for (int i = 1; i < nl; ++i) if (lv[i].octave > lv[i - 1].octave) kcontrast = kcontrast * 0.75f;
+        dbg_info[0] = (float)nl; dbg_info[1] = kcontrast;
+    }
     if (dbg_level >= 0 && dbg_level < nl) {
         const size_t n = (size_t)lv[dbg_level].w * lv[dbg_level].h;
-        if (dbg_ldet) memcpy(dbg_ldet, lv[dbg_level].Ldet, sizeof(float) * n);
-        if (dbg_lt) memcpy(dbg_lt, lv[dbg_level].Lt, sizeof(float) * n);
+        if (dbg_ldet) memcpy(dbg_ldet, planes[4 * dbg_level], sizeof(float) * n);
+        if (dbg_lt) memcpy(dbg_lt, planes[4 * dbg_level + 3], sizeof(float) * n);
         if (dbg_info) { dbg_info[2] = (float)lv[dbg_level].w; dbg_info[3] = (float)lv[dbg_level].h; dbg_info[4] = (float)lv[dbg_level].border;
                         dbg_info[5] = (float)lv[dbg_level].sigma_size; dbg_info[6] = lv[dbg_level].esigma; }
-    }
-
-    /* Find_Scale_Space_Extrema (threaded variant) */
-    ak_list* kl = (ak_list*)calloc((size_t)nl, sizeof(ak_list));
-    for (int i = 0; i < nl; ++i) {
-        const ak_level* e = &lv[i];
-        const float psize = e->esigma * dfac;
-        for (int y = e->border; y < e->h - e->border; ++y) {
-            const float* prev = e->Ldet + (size_t)(y - 1) * e->w; const float* curr = prev + e->w; const float* next = curr + e->w;
-            for (int x = e->border; x < e->w - e->border; ++x) {
-                const float value = curr[x];
-                if (value <= dthreshold) continue;
-                if (value <= curr[x - 1] || value <= curr[x + 1]) continue;
-                if (value <= prev[x - 1] || value <= prev[x] || value <= prev[x + 1]) continue;
-                if (value <= next[x - 1] || value <= next[x] || value <= next[x + 1]) continue;
-                ak_kp p = { (float)(x * e->ratio), (float)(y * e->ratio), psize, value, i, 1 };
-                int found = -1;
-                for (int q = 0; q < kl[i].n; ++q) {
-                    const float dx = p.x - kl[i].v[q].x, dy = p.y - kl[i].v[q].y;
-                    if (dx * dx + dy * dy <= p.size * p.size) { found = q; break; }
-                }
-                if (found >= 0) { if (p.response > kl[i].v[found].response) kl[i].v[found] = p; continue; }
-                kl_push(&kl[i], p);
-            }
-        }
     }
     int n_out = 0;
     {   /* the tail: cross-level filters, refinement, orientation, angle, MLDB */
         orc_ak_tail_level tl[16];
-        const float* planes[16 * 4];
-        int n_list[16];
-        float* lists[16];
         for (int i = 0; i < nl; ++i) {
             tl[i].w = lv[i].w; tl[i].h = lv[i].h; tl[i].sigma_size = lv[i].sigma_size; tl[i].ratio = lv[i].ratio; tl[i].esigma = lv[i].esigma;
-            planes[4 * i] = lv[i].Ldet; planes[4 * i + 1] = lv[i].Lx; planes[4 * i + 2] = lv[i].Ly; planes[4 * i + 3] = lv[i].Lt;
-            n_list[i] = kl[i].n;
-            lists[i] = (float*)malloc(sizeof(float) * 3 * (size_t)(kl[i].n + 1));
-            for (int j = 0; j < kl[i].n; ++j) { lists[i][3 * j] = kl[i].v[j].x; lists[i][3 * j + 1] = kl[i].v[j].y; lists[i][3 * j + 2] = kl[i].v[j].response; }
         }
         float* rec = (float*)malloc(sizeof(float) * 10 * (size_t)(cap + 1));
         int* rlev = (int*)malloc(sizeof(int) * (size_t)(cap + 1));
-        n_out = orc_akaze_tail(nl, tl, planes, n_list, (const float* const*)lists, cap, rec, rlev, mldb, NULL);
+        n_out = orc_akaze_tail(nl, tl, (const float* const*)planes, n_list, (const float* const*)lists, cap, rec, rlev, mldb, NULL);
         for (int k = 0; k < n_out && k < cap; ++k) {
             kps[4 * k] = rec[10 * k]; kps[4 * k + 1] = rec[10 * k + 1]; kps[4 * k + 2] = rec[10 * k + 2]; kps[4 * k + 3] = rec[10 * k + 7];
             if (responses) responses[k] = rec[10 * k + 3];
             if (levels) levels[k] = rlev[k];
         }
-        for (int i = 0; i < nl; ++i) free(lists[i]);
         free(rec); free(rlev);
     }
-    for (int i = 0; i < nl; ++i) { free(kl[i].v); free(lv[i].Lt); }
-    free(kl); free(wx); free(wy); free(wflow); free(wstep);
+    for (int i = 0; i < nl; ++i) { free(lists[i]); free(planes[4 * i]); }
     return n_out;
 }
 

@@ -554,6 +554,65 @@ def akaze_detect_mldb(img, threshold=0.001, cap=200000):
     return kps[:n].copy(), desc[:n].copy(), resp[:n].copy()
 
 
+class AkHeadLevel(C.Structure):
+    """orc_ak_head_level"""
+    _fields_ = [("w", C.c_int), ("h", C.c_int), ("octave", C.c_int), ("sublevel", C.c_int), ("sigma_size", C.c_int), ("border", C.c_int),
+                ("ratio", C.c_float), ("esigma", C.c_float), ("etime", C.c_float), ("psize", C.c_float)]
+
+
+def _akaze_level_table(w, h):
+    lv = (AkHeadLevel * 16)()
+    L = lib()
+    L.orc_akaze_levels.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    nl = L.orc_akaze_levels(int(w), int(h), C.addressof(lv))
+    return lv, nl
+
+
+def akaze_levels(w, h):
+    """orc_akaze_levels: the level table of a w x h image, as dicts (w, h, octave, sublevel, sigma_size, border, ratio, esigma, etime, psize)"""
+    lv, nl = _akaze_level_table(w, h)
+    return [{k: getattr(lv[i], k) for k, _ in AkHeadLevel._fields_} for i in range(nl)]
+
+
+def akaze_extrema(ldet, border, ratio, psize, threshold):
+    """orc_akaze_extrema: Find_Scale_Space_Extrema's loop of one level on a determinant plane [h, w] -> (candidates before the pruning,
+    the kept points [n, 3] float32 (x, y, response) in insertion order)"""
+    ldet = np.ascontiguousarray(ldet, np.float32)
+    h, w = ldet.shape
+    assert border >= 1 and w > 2 * border and h > 2 * border
+    cap = ((w + 1) // 2) * ((h + 1) // 2)
+    lst = np.zeros((cap + 1, 3), np.float32); nc = C.c_int(0)
+    L = lib()
+    L.orc_akaze_extrema.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+    n = L.orc_akaze_extrema(_p(ldet), w, h, int(border), float(ratio), float(psize), float(threshold), _p(lst), cap, C.addressof(nc))
+    assert 0 <= n <= nc.value <= cap
+    return nc.value, lst[:n].copy()
+
+
+def akaze_head(img, threshold):
+    """orc_akaze_head: the detector's head on an image [h, w] in [0, 1] -> dict: levels (akaze_levels), planes [n_levels] of (Ldet, Lx, Ly,
+    Lt) float32 [h_i, w_i], n_cand [n_levels], lists [n_levels] of [n_i, 3] float32 (x, y, response) in insertion order, hmax and
+    kcontrast (float32), inv_k2 [8] float32, hist [300] int32.  None when the image has no evolution level."""
+    img = np.ascontiguousarray(img, np.float32)
+    h, w = img.shape
+    lv, nl = _akaze_level_table(w, h)
+    if nl == 0:
+        return None
+    planes = [[np.zeros((lv[i].h, lv[i].w), np.float32) for _ in range(4)] for i in range(nl)]
+    caps = np.array([((lv[i].w + 1) // 2) * ((lv[i].h + 1) // 2) for i in range(nl)], np.int32)
+    lists = [np.zeros((int(c) + 1, 3), np.float32) for c in caps]
+    n_cand = np.zeros(nl, np.int32); n_list = np.zeros(nl, np.int32); kstate = np.zeros(10, np.float32); hist = np.zeros(300, np.int32)
+    pp = (C.c_void_p * (4 * nl))(*[q.ctypes.data for lev in planes for q in lev])
+    lp = (C.c_void_p * nl)(*[l.ctypes.data for l in lists])
+    L = lib()
+    L.orc_akaze_head.restype = None
+    L.orc_akaze_head.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int] + [C.c_void_p] * 8
+    L.orc_akaze_head(_p(img), w, h, float(threshold), nl, C.addressof(lv), C.addressof(pp), C.addressof(lp), _p(caps), _p(n_cand), _p(n_list),
+                     _p(kstate), _p(hist))
+    return dict(levels=akaze_levels(w, h), planes=planes, n_cand=n_cand, lists=[l[:int(n)].copy() for l, n in zip(lists, n_list)],
+                hmax=kstate[0], kcontrast=kstate[1], inv_k2=kstate[2:].copy(), hist=hist)
+
+
 class AkTailLevel(C.Structure):
     """orc_ak_tail_level"""
     _fields_ = [("w", C.c_int), ("h", C.c_int), ("sigma_size", C.c_int), ("ratio", C.c_float), ("esigma", C.c_float)]

@@ -209,6 +209,14 @@ int   orc_akaze_tail(int nl, const orc_ak_tail_level* lv, const float* const* pl
 void  orc_akaze_orientation_probe(const float* Lx, const float* Ly, int cols, int x0, int y0, int scale, int variant, float* out_xy,
                                   int* keys, float* norms);
 int   orc_akaze_slice_key(float resY, float resX);
+/* the detector's head -- scale space, k-contrast state, extrema and in-level pruning of every level -- and the extremum loop of one level
+ * on a caller's determinant plane (akaze.c); the detector itself runs on both */
+typedef struct { int w, h, octave, sublevel, sigma_size, border; float ratio, esigma, etime, psize; } orc_ak_head_level;
+int   orc_akaze_levels(int w, int h, orc_ak_head_level* lv /* 16 */);
+int   orc_akaze_extrema(const float* Ldet, int w, int h, int border, float ratio, float psize, float dthreshold, float* list, int cap,
+                        int* n_cand);
+void  orc_akaze_head(const float* image, int w, int h, float dthreshold, int nl, const orc_ak_head_level* lv, float* const* planes,
+                     float* const* lists, const int* list_cap, int* n_cand, int* n_list, float* kstate /* 10 */, int* hist /* 300 */);
 int   orc_akaze_detect_mldb(const float* image, int w, int h, float dthreshold, float* kps, unsigned char* desc, int cap, float* responses);
 int   orc_akaze_detect(const float* image, int w, int h, float dthreshold, float* kps, int cap, float* responses, int* levels,
                        int dbg_level, float* dbg_ldet, float* dbg_lt, float* dbg_info);

@@ -582,6 +582,85 @@ def dev_tail_args(images):
     return nl, dims, ptrs, n_list, lists, keep
 
 
+class DevAkPlan(C.Structure):
+    """r3dm_dev_ak_plan (developer build, api_akaze.cpp): what the scale space launched for one level"""
+    _fields_ = [("head_form", C.c_int32), ("head_rows", C.c_int32), ("n_launch", C.c_int32), ("n_steps", C.c_int32),
+                ("form", C.c_int32 * 32), ("steps", C.c_int32 * 32), ("rows", C.c_int32 * 32)]
+
+
+def bind_dev_akaze_head(L):
+    """the developer build's Fast-arm head entries (libr3dm_dev.so only, declared in no header), bound when first asked for"""
+    if getattr(L, "_r3dm_dev_head_bound", False):
+        return L
+    if not hasattr(L, "r3dm_dev_akaze_head"):
+        raise R3dmError("r3dm_dev_akaze_head exists in the developer build only: use_developer_library() before the first load")
+    bind_dev_akaze_tail(L)
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.r3dm_dev_akaze_head_bound.argtypes = [u32, u32, vp]
+    L.r3dm_dev_akaze_head_plan.argtypes = [u32, u32, u32, vp]
+    L.r3dm_dev_akaze_head_check.argtypes = [u32, vp, u32, u32]
+    L.r3dm_dev_akaze_head.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, vp, vp, vp]
+    L.r3dm_dev_akaze_extrema_check.argtypes = [u32, u32, u32, u32, vp, vp]
+    L.r3dm_dev_akaze_extrema.argtypes = [vp, u32, u32, u32, u32, vp, vp, C.c_float, vp, vp]
+    L._r3dm_dev_head_bound = True
+    return L
+
+
+def dev_head_bound(L, width: int, height: int) -> int:
+    """r3dm_dev_akaze_head_bound: the candidates an image of this size can hold at most -- the triples per image of the head entries' lists"""
+    bound = C.c_uint64(0)
+    rc = bind_dev_akaze_head(L).r3dm_dev_akaze_head_bound(width, height, C.addressof(bound))
+    if rc != 0:
+        raise R3dmError(f"r3dm_dev_akaze_head_bound -> {rc}")
+    return int(bound.value)
+
+
+def _dev_plan_dicts(plan, nl):
+    return [dict(head_form=plan[i].head_form, head_rows=plan[i].head_rows, n_steps=plan[i].n_steps,
+                 launches=[(plan[i].form[m], plan[i].steps[m], plan[i].rows[m]) for m in range(plan[i].n_launch)]) for i in range(nl)]
+
+
+def dev_head_plan(L, width: int, height: int, B: int = 1):
+    """r3dm_dev_akaze_head_plan (needs no device): the launches the scale space issues per level for B width x height images, under this
+    process's developer knobs -> per level a dict: head_form (the one-pass level head runs), head_rows, n_steps (FED steps), launches
+    [(form: 0 one step, 1 steps through LDS, 2 marching strips; steps; rows per band)]"""
+    bind_dev_akaze_head(L)
+    nl = len(dev_akaze_tail_levels(L, width, height))
+    plan = (DevAkPlan * max(nl, 1))()
+    rc = L.r3dm_dev_akaze_head_plan(width, height, B, C.addressof(plan))
+    if rc != 0:
+        raise R3dmError(f"r3dm_dev_akaze_head_plan -> {rc}")
+    return _dev_plan_dicts(plan, nl)
+
+
+def dev_head_images(images):
+    """the image array of r3dm_dev_akaze_head(_check): (pointers, keep-alive)"""
+    keep = [np.ascontiguousarray(im, np.float32) for im in images]
+    return (C.c_void_p * len(keep))(*[k.ctypes.data for k in keep]), keep
+
+
+def dev_extrema_args(planes):
+    """the arrays of r3dm_dev_akaze_extrema(_check).  planes: per image [n_levels] Ldet float32 [h, w] -> (n_levels, plane_dims
+    [n_levels, 2] uint32, plane pointers, keep-alive)"""
+    nl = len(planes[0])
+    keep = [[np.ascontiguousarray(q, np.float32) for q in im] for im in planes]
+    dims = np.array([[q.shape[1], q.shape[0]] for q in keep[0]], np.uint32).reshape(nl, 2)
+    ptrs = (C.c_void_p * (len(planes) * nl))(*[q.ctypes.data for im in keep for q in im])
+    return nl, dims, ptrs, keep
+
+
+def _dev_head_lists(counts, lists, B, nl, bound):
+    """(n_cand [nl], lists [nl] of [n, 3]) per image from the head entries' counts_out and lists_out"""
+    out = []
+    for b in range(B):
+        at, ls = b * bound, []
+        for i in range(nl):
+            n = int(counts[b, i, 1])
+            ls.append(lists[at:at + n].copy()); at += n
+        out.append((counts[b, :, 0].copy(), ls))
+    return out
+
+
 def _ptr(a) -> Optional[int]:
     """address of a numpy array or torch tensor (host or device) -- the ABI takes plain pointers"""
     if a is None:
@@ -1349,6 +1428,45 @@ class Context:
             res.append(out)
             at += int(per[b].sum())
         return res
+
+    def dev_akaze_head(self, images, threshold: float):
+        """r3dm_dev_akaze_head (developer build): the Fast arm's head -- scale space, extremum pass, in-level pruning, the product's
+        own launches -- on same-size images [h, w] in [0, 1] -> (per image a dict: planes [n_levels] of [Ldet, Lx, Ly, Lt] float32,
+        n_cand [n_levels] uint32, lists [n_levels] of [n, 3] float32 in list order, hmax_bits (uint32), hist [300] uint32, inv_k2 [8]
+        float32; plan: per level a dict head_form, head_rows, n_steps, launches [(form, steps, rows per band)])"""
+        L = bind_dev_akaze_head(self._L)
+        ptrs, keep = dev_head_images(images)
+        B = len(keep)
+        h, w = keep[0].shape
+        lv = dev_akaze_tail_levels(L, w, h)
+        nl = len(lv)
+        bound = dev_head_bound(L, w, h)
+        planes = [[[np.zeros((e["h"], e["w"]), np.float32) for _ in range(4)] for e in lv] for _ in range(B)]
+        pp = (C.c_void_p * max(B * nl * 4, 1))(*[q.ctypes.data for im in planes for lev in im for q in lev])
+        counts = np.zeros((B, max(nl, 1), 2), np.uint32); lists = np.zeros((B * max(bound, 1), 3), np.float32)
+        small = np.zeros((B, 309), np.uint32); plan = (DevAkPlan * max(nl, 1))()
+        self._check(L.r3dm_dev_akaze_head(self._h, B, C.addressof(ptrs), w, h, float(threshold), C.addressof(pp), _ptr(counts), _ptr(lists),
+                                          _ptr(small), C.addressof(plan)), "r3dm_dev_akaze_head")
+        del keep
+        res = []
+        for b, (n_cand, ls) in enumerate(_dev_head_lists(counts, lists, B, nl, bound)):
+            res.append(dict(planes=planes[b], n_cand=n_cand, lists=ls, hmax_bits=small[b, 0].copy(), hist=small[b, 1:301].copy(),
+                            inv_k2=small[b, 301:309].copy().view(np.float32)))
+        return res, _dev_plan_dicts(plan, nl)
+
+    def dev_akaze_extrema(self, width: int, height: int, planes, threshold: float):
+        """r3dm_dev_akaze_extrema (developer build): the Fast arm's extremum pass and in-level pruning on the caller's determinant
+        planes (per image [n_levels] float32 [h_i, w_i], the level table of width x height) -> per image (n_cand [n_levels] uint32,
+        lists [n_levels] of [n, 3] float32 (x, y, response) in list order)"""
+        L = bind_dev_akaze_head(self._L)
+        nl, dims, ptrs, keep = dev_extrema_args(planes)
+        B = len(planes)
+        bound = dev_head_bound(L, width, height)
+        counts = np.zeros((B, max(nl, 1), 2), np.uint32); lists = np.zeros((B * max(bound, 1), 3), np.float32)
+        self._check(L.r3dm_dev_akaze_extrema(self._h, width, height, B, nl, _ptr(dims), C.addressof(ptrs), float(threshold), _ptr(counts),
+                                             _ptr(lists)), "r3dm_dev_akaze_extrema")
+        del keep
+        return _dev_head_lists(counts, lists, B, nl, bound)
 
     def guided_match(self, pairs, kind: str, models, threshold_px, ratio: float) -> Graph:
         """r3dm_guided_match: guided matching of `pairs` (a Graph -- only its pair list is read -- or an (P, 2) array in (I, J) order)

@@ -3,7 +3,8 @@
 // of the arm), then the Fast-A-KAZE arm (kernels_akaze.hip): ak_detect_batch in its phases -- buffers, scale space, detection with regrow,
 // read-back -- and its entries.  The classic arm's launch sequence is api_akaze_classic.cpp; what is shared and what stays per arm:
 // DESIGN.md section 4.21.  There is no CPU fallback in this file: when HIP fails, the call fails.  At the end, developer build only: the
-// arm's tail on a caller's planes and lists (r3dm_dev_akaze_tail).
+// arm's tail on a caller's planes and lists (r3dm_dev_akaze_tail), and its head -- scale space, extrema, in-level pruning -- on a caller's images
+// or determinant planes, every plane and list read back (r3dm_dev_akaze_head, r3dm_dev_akaze_extrema).
 #include "r3dm_ctx.hpp"
 
 // ======== the frame of both arms
@@ -230,6 +231,11 @@ std::vector<float> ak_fed_tau(float T)
 enum { B_IMG = 0, B_SMOOTH, B_LXX, B_LXY, B_LYY, B_TMP, B_TMP2, B_WX, B_WY, B_FLOW, B_LT2, B_SMALL, B_LEVEL0 };
 enum { T_META = 0, T_SLOTS, T_MLDB, T_TABS, T_RECS, T_COUNT = 8 };
 
+// the launches of one level i > 0 (ak_level_plan decides, ak_evolve_level issues): the one-pass level head (with its rows per band) or the
+// four launches, and per FED launch its form, its steps and (marching) its rows per band
+enum { AK_FED_STEP = 0, AK_FED_MULTI = 1, AK_FED_MARCH = 2 };   // ak_fed_step (one step), ak_fed_multi (steps through LDS), ak_fed_march (marching strips)
+struct AkLevelPlan { bool head = false; int head_rows = 0; std::vector<int> form, steps, rows; };
+
 // one pass of the arm: what its phases share
 struct AkPass {
     r3dm_ctx* c; hipStream_t st;
@@ -286,17 +292,12 @@ int ak_buffers(AkPass& p)
 // DESIGN.md section 4.8 (c); the capture code is in the history.)
 #define AK_TRY(call) do { if ((e = (call)) != hipSuccess) return e; } while (0)
 
-// level i > 0 from level i - 1: start image, conductivity, the FED cycle
-// (Splitting the launches of the 3 Mpx octave into sub-batches whose planes fit the Infinity Cache was measured: 2.31-2.34 ms
-// per image against 2.36 -- not worth a second launch order; profiles/r03_f_*.)
-hipError_t ak_evolve_level(AkPass& p, int i)
+// The launch plan of level i > 0 for a batch of nb images: a function of the level table, nb and (developer build) the knobs alone.
+AkLevelPlan ak_level_plan(const std::vector<AkLevelHost>& lv, int i, int nb, int taps_one_n, size_t n_tau)
 {
-    hipError_t e; hipStream_t st = p.st;
-    const std::vector<AkLevelHost>& lv = p.lv;
-    const int nb = p.iB, lw = lv[i].w, lh = lv[i].h;
+    AkLevelPlan pl;
+    const int lw = lv[i].w, lh = lv[i].h;
     const size_t n = (size_t)lw * lh;
-    const std::vector<float> tau = ak_fed_tau(lv[i].etime - lv[i - 1].etime);
-    float* Lti = p.Lt(i);
     // FED launches of this level.  Product: up to four steps per launch in registers (ak_fed_march_kernel: a wavefront marches a
     // strip of columns down the rows, every step level three rows deep in registers -- 12 bytes of HBM traffic per pixel and
     // LAUNCH instead of per step).  The older forms stay for the developer build's A/B runs: one step per launch
@@ -310,15 +311,57 @@ hipError_t ak_evolve_level(AkPass& p, int i)
     const bool march = march_knob && lw >= 3 && lh >= 3 && (march_knob == 1 || n >= (size_t)march_knob);
     static const int multi_knob = r3dm_dev_knob("R3DM_AK_FED_MULTI", 1);      // developer build: 0 = never, 1 = the product, > 1 = that many pixels
     static const int multi_px = multi_knob > 1 ? multi_knob : (multi_knob ? 3200000 : 0);
-    std::vector<int> chunk;                                             // chunk[m] = steps of launch m
     if (march) {
-        const int q = ((int)tau.size() + march_kmax - 1) / march_kmax;         // launches, steps spread evenly over them
-        for (int m = 0; m < q; ++m) chunk.push_back(((int)tau.size() * (m + 1)) / q - ((int)tau.size() * m) / q);
+        const int q = ((int)n_tau + march_kmax - 1) / march_kmax;             // launches, steps spread evenly over them
+        for (int m = 0; m < q; ++m) pl.steps.push_back(((int)n_tau * (m + 1)) / q - ((int)n_tau * m) / q);
     } else {
         const int per = n <= (size_t)multi_px ? 4 : 1;
-        for (size_t k0 = 0; k0 < tau.size(); k0 += (size_t)per) chunk.push_back((int)std::min<size_t>((size_t)per, tau.size() - k0));
+        for (size_t k0 = 0; k0 < n_tau; k0 += (size_t)per) pl.steps.push_back((int)std::min<size_t>((size_t)per, n_tau - k0));
     }
-    const size_t n_launch = chunk.size();                               // plane passes of the FED part (3 planes each): launches, not steps
+    for (const int kn : pl.steps) {
+        if (march) {
+            // rows per band: enough wavefronts to fill the chip (strips x bands x images >= march_waves), at most 128 rows
+            const int vw = 64 - 2 * kn, strips = (lw + vw - 1) / vw;
+            int rows = (int)(((int64_t)lh * strips * nb + march_waves - 1) / march_waves);
+            rows = std::max(16, std::min(128, (rows + 7) / 8 * 8));
+            pl.form.push_back(AK_FED_MARCH); pl.rows.push_back(rows);
+        } else {
+            pl.form.push_back(kn == 1 && n > (size_t)multi_px ? AK_FED_STEP : AK_FED_MULTI); pl.rows.push_back(0);
+        }
+    }
+    // Gaussian -> derivatives -> determinant -> conductivity.  Product: four HBM-bound launches (10 plane moves).  The one-pass form
+    // (ak_level_head_kernel: a marching wavefront with the intermediates in LDS rings, 5 plane moves, bit-identical -- level_head.inc,
+    // tests/cpp/level_head_emul.cpp) is built and MEASURED SLOWER, twice: 1,369 us (stages chained inside an iteration) and 1,573 us
+    // (stages one iteration apart) against 1,083 us for the four launches at 8 x 12 Mpx.  PMC (profiles/r05_pmc_level_head.txt):
+    // 271 scalar + 138 vector + 28 LDS instructions per 48 stored pixels -- the per-row bookkeeping of a marching wavefront
+    // (ring slots, border rows, stage predicates) is paid once per 64 lanes and row, where a thread-per-pixel kernel pays it
+    // once per four rows of loads; at ~620 G wave instructions/s the fused form is instruction-bound above the four launches'
+    // HBM time.  It stays behind the developer knob R3DM_AK_HEAD=1 (tests/test_gpu_akaze.py runs it for bit-identity).
+    static const int head_knob = r3dm_dev_knob("R3DM_AK_HEAD", 0);
+    static const int head_waves = std::max(256, r3dm_dev_knob("R3DM_AK_HEAD_WAVES", 8000));
+    const int s_i = lv[i].sigma_size;
+    pl.head = head_knob && taps_one_n == 5 && s_i >= 2 && s_i <= 4 && lw >= 16 && lh >= 16;
+    if (pl.head) {
+        const int vw = 64 - 2 * (2 + 2 * s_i), strips = (lw + vw - 1) / vw;
+        int rows = (int)(((int64_t)lh * strips * nb + head_waves - 1) / head_waves);
+        pl.head_rows = std::max(32, std::min(256, (rows + 15) / 16 * 16));
+    }
+    return pl;
+}
+
+// level i > 0 from level i - 1: start image, conductivity, the FED cycle
+// (Splitting the launches of the 3 Mpx octave into sub-batches whose planes fit the Infinity Cache was measured: 2.31-2.34 ms
+// per image against 2.36 -- not worth a second launch order; profiles/r03_f_*.)
+hipError_t ak_evolve_level(AkPass& p, int i)
+{
+    hipError_t e; hipStream_t st = p.st;
+    const std::vector<AkLevelHost>& lv = p.lv;
+    const int nb = p.iB, lw = lv[i].w, lh = lv[i].h;
+    const size_t n = (size_t)lw * lh;
+    const std::vector<float> tau = ak_fed_tau(lv[i].etime - lv[i - 1].etime);
+    float* Lti = p.Lt(i);
+    const AkLevelPlan pl = ak_level_plan(lv, i, nb, p.taps_one.n, tau.size());
+    const size_t n_launch = pl.steps.size();                            // plane passes of the FED part (3 planes each): launches, not steps
     const float* start = nullptr;
     if (lv[i].octave > lv[i - 1].octave) {
         // the FED launches ping-pong between Lt(i) and the work image and must END in Lt(i): the half-sampled start image
@@ -334,23 +377,9 @@ hipError_t ak_evolve_level(AkPass& p, int i)
         if (start != Lti) AK_TRY(hipMemcpyAsync(Lti, start, (size_t)nb * n * 4, hipMemcpyDeviceToDevice, st));
         start = Lti;
     }
-    // Gaussian -> derivatives -> determinant -> conductivity.  Product: four HBM-bound launches (10 plane moves).  The one-pass form
-    // (ak_level_head_kernel: a marching wavefront with the intermediates in LDS rings, 5 plane moves, bit-identical -- level_head.inc,
-    // tests/cpp/level_head_emul.cpp) is built and MEASURED SLOWER, twice: 1,369 us (stages chained inside an iteration) and 1,573 us
-    // (stages one iteration apart) against 1,083 us for the four launches at 8 x 12 Mpx.  PMC (profiles/r05_pmc_level_head.txt):
-    // 271 scalar + 138 vector + 28 LDS instructions per 48 stored pixels -- the per-row bookkeeping of a marching wavefront
-    // (ring slots, border rows, stage predicates) is paid once per 64 lanes and row, where a thread-per-pixel kernel pays it
-    // once per four rows of loads; at ~620 G wave instructions/s the fused form is instruction-bound above the four launches'
-    // HBM time.  It stays behind the developer knob R3DM_AK_HEAD=1 (tests/test_gpu_akaze.py runs it for bit-identity).
-    static const int head_knob = r3dm_dev_knob("R3DM_AK_HEAD", 0);
-    static const int head_waves = std::max(256, r3dm_dev_knob("R3DM_AK_HEAD_WAVES", 8000));
     const int s_i = lv[i].sigma_size;
-    const bool head = head_knob && p.taps_one.n == 5 && s_i >= 2 && s_i <= 4 && lw >= 16 && lh >= 16;
-    if (head) {
-        const int vw = 64 - 2 * (2 + 2 * s_i), strips = (lw + vw - 1) / vw;
-        int rows = (int)(((int64_t)lh * strips * nb + head_waves - 1) / head_waves);
-        rows = std::max(32, std::min(256, (rows + 15) / 16 * 16));
-        AK_TRY(ak_level_head(st, start, p.Lx(i), p.Ly(i), p.Ldet(i), p.flow, lw, lh, nb, p.taps_one, s_i, p.inv_k2() + lv[i].octave, rows));
+    if (pl.head) {
+        AK_TRY(ak_level_head(st, start, p.Lx(i), p.Ly(i), p.Ldet(i), p.flow, lw, lh, nb, p.taps_one, s_i, p.inv_k2() + lv[i].octave, pl.head_rows));
     } else {
         AK_TRY(ak_gaussian(st, start, p.tmp, p.smooth, lw, lh, nb, p.taps_one));
         AK_TRY(ak_scaled_deriv_xy(st, p.smooth, p.Lx(i), p.Ly(i), lw, lh, nb, s_i));
@@ -362,19 +391,14 @@ hipError_t ak_evolve_level(AkPass& p, int i)
     size_t k0 = 0;
     for (size_t m = 1; m <= n_launch; ++m) {
         float* o = ((n_launch - m) % 2 == 0) ? Lti : p.lt2;
-        const int kn = chunk[m - 1];
-        if (march) {
-            // rows per band: enough wavefronts to fill the chip (strips x bands x images >= march_waves), at most 128 rows
-            const int vw = 64 - 2 * kn, strips = (lw + vw - 1) / vw;
-            int rows = (int)(((int64_t)lh * strips * nb + march_waves - 1) / march_waves);
-            rows = std::max(16, std::min(128, (rows + 7) / 8 * 8));
-            AK_TRY(ak_fed_march(st, cur, p.flow, o, lw, lh, nb, tau.data() + k0, kn, rows));
-        } else if (kn == 1 && n > (size_t)multi_px) AK_TRY(ak_fed_step(st, cur, p.flow, o, lw, lh, nb, tau[k0]));
+        const int kn = pl.steps[m - 1];
+        if (pl.form[m - 1] == AK_FED_MARCH) AK_TRY(ak_fed_march(st, cur, p.flow, o, lw, lh, nb, tau.data() + k0, kn, pl.rows[m - 1]));
+        else if (pl.form[m - 1] == AK_FED_STEP) AK_TRY(ak_fed_step(st, cur, p.flow, o, lw, lh, nb, tau[k0]));
         else AK_TRY(ak_fed_multi(st, cur, p.flow, o, lw, lh, nb, tau.data() + k0, kn));
         cur = o; k0 += (size_t)kn;
     }
     if (lv[i].octave > lv[i - 1].octave) { p.tally(lv[i - 1].w, lv[i - 1].h, 1, 1); p.tally(lw, lh, 1, 1); }
-    p.tally(lw, lh, (head ? 5 : 2 + 6 + 2) + 3 * (int)n_launch, 2 + 1 + 1 + 2 * (int)tau.size());       // Gaussian (fused row + column pass) 2, derivatives + determinant 6, conductivity 2, 3 per FED launch (as structured); compulsory: 2 per FED step, the round-2 count
+    p.tally(lw, lh, (pl.head ? 5 : 2 + 6 + 2) + 3 * (int)n_launch, 2 + 1 + 1 + 2 * (int)tau.size());       // Gaussian (fused row + column pass) 2, derivatives + determinant 6, conductivity 2, 3 per FED launch (as structured); compulsory: 2 per FED step, the round-2 count
     return hipSuccess;
 }
 
@@ -480,6 +504,23 @@ hipError_t ak_tail_launches(hipStream_t st, const AkLevelDev* d_levels, int nl, 
     return ak_compact(st, d_levels, nl, iB, recs, cap, d_bmeta);
 }
 
+// the head of the detection on the determinant planes of the level table: the extremum bit masks and row counts, their scan, the slot
+// layout at `cap` slots per image, the raster-ordered candidates, the in-level pruning -- it leaves counts[0] candidates and the kept
+// list of counts[1] entries per level.  The caller has zeroed the row counts and counters and uploaded the table.  The detector and the
+// developer build's r3dm_dev_akaze_head / r3dm_dev_akaze_extrema both call it.
+hipError_t ak_head_launches(hipStream_t st, AkLevelDev* d_levels, int nl, int iB, const AkTileTable& tiles, uint32_t n_tiles, int max_rows,
+                            unsigned char* slots, uint32_t cap, AkBatchMeta* d_bmeta, float threshold)
+{
+    hipError_t e;
+    const size_t field = (size_t)iB * cap;
+    if ((e = ak_extrema_mask(st, d_levels, nl, iB, tiles, n_tiles, threshold)) != hipSuccess) return e;   // all levels of all images in one launch
+    if ((e = ak_scan_rows(st, d_levels, nl, iB)) != hipSuccess) return e;
+    if ((e = ak_layout(st, d_levels, nl, iB, slots, cap, d_bmeta)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(slots + field * 76, 0, field * 2, st)) != hipSuccess) return e;               // dead_lower / dead_upper flags
+    if ((e = ak_extrema(st, d_levels, nl, iB, max_rows, threshold, 1)) != hipSuccess) return e;
+    return ak_prune_levels(st, d_levels, nl, iB);
+}
+
 // the detection launches at a slot capacity; an image that reports more candidates than it makes them run again with larger arrays
 int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
 {
@@ -496,12 +537,7 @@ int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
         R3DM_HIP(c, recs.ensure(field * sizeof(AkKpRec) + 256));
         R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
         R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
-        R3DM_HIP(c, ak_extrema_mask(st, d.d_levels, nl, iB, d.tiles, d.n_tiles, threshold));   // all levels of all images in one launch
-        R3DM_HIP(c, ak_scan_rows(st, d.d_levels, nl, iB));
-        R3DM_HIP(c, ak_layout(st, d.d_levels, nl, iB, slots.as<unsigned char>(), cap, d.d_bmeta));
-        R3DM_HIP(c, hipMemsetAsync(slots.as<unsigned char>() + field * 76, 0, field * 2, st));   // dead_lower / dead_upper flags
-        R3DM_HIP(c, ak_extrema(st, d.d_levels, nl, iB, d.max_rows, threshold, 1));
-        R3DM_HIP(c, ak_prune_levels(st, d.d_levels, nl, iB));
+        R3DM_HIP(c, ak_head_launches(st, d.d_levels, nl, iB, d.tiles, d.n_tiles, d.max_rows, slots.as<unsigned char>(), cap, d.d_bmeta, threshold));
         R3DM_HIP(c, ak_tail_launches(st, d.d_levels, nl, iB, recs.as<AkKpRec>(), cap, d.d_bmeta));
         R3DM_HIP(c, hipEventRecord(c->ev1, st));
         R3DM_HIP(c, hipMemcpyAsync(d.bm.data(), d.d_bmeta, (size_t)B * sizeof(AkBatchMeta), hipMemcpyDeviceToHost, st));
@@ -867,6 +903,213 @@ extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height,
         }
         R3DM_HIP(c, hipStreamSynchronize(st));
         return R3DM_OK;
+    });
+}
+
+// ---- developer build only: the Fast arm's HEAD, every plane and list read back, so that the suite can hold each pixel of each level
+// to the oracle -- the border rings no keypoint can lie in, the last level's Lt, the k-contrast's branches, the seams of the extremum
+// pass and of the FED launches, the in-level pruning before the cross-level filters hide it.  What runs is the
+// product's: ak_levels, ak_buffers, detect_upload, detect_area_tabs, ak_scale_space (with the launch forms the developer knobs choose),
+// ak_level_table, ak_head_launches.  The slot capacity is the level table's own bound, so nothing regrows.
+// a level's launch plan as it crosses the ABI (AkLevelPlan): form 0 = one step per launch, 1 = steps through LDS, 2 = marching strips
+struct r3dm_dev_ak_plan { int32_t head_form, head_rows, n_launch, n_steps; int32_t form[32], steps[32], rows[32]; };
+constexpr uint32_t kAkDevHeadMaxB = 8, kAkDevHeadMaxDim = 4096, kAkDevSmallOut = 1 + 300 + 8;
+
+// the candidate bound of an image of the level table (ak_level_table's d.bound): the slots per image both entries below allocate and the
+// triples per image of their lists_out
+static uint64_t ak_dev_bound(const std::vector<AkLevelHost>& lv)
+{
+    uint64_t bound = 0;
+    for (const AkLevelHost& e : lv) bound += (uint64_t)((e.w + 1) / 2) * (uint64_t)((e.h + 1) / 2);
+    return bound;
+}
+
+// The launch plan ak_evolve_level follows for every level of a batch of B width x height images (ak_level_plan, the detector's own
+// decision; level 0 has no launches of this kind), with the developer knobs of this process.  Needs no device.  plan_out [n_levels].
+extern "C" int r3dm_dev_akaze_head_plan(uint32_t width, uint32_t height, uint32_t B, r3dm_dev_ak_plan* plan_out)
+{
+    if (!plan_out || B < 1 || B > kAkDevHeadMaxB || width < 3 || height < 3 || width > kAkDevHeadMaxDim || height > kAkDevHeadMaxDim) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    if (lv.empty() || lv.size() > 16) return R3DM_ERR_INVALID;
+    const int taps_one_n = ak_taps(1.0f).n;
+    for (size_t i = 0; i < lv.size(); ++i) {
+        r3dm_dev_ak_plan o{};
+        if (i > 0) {
+            const size_t n_tau = ak_fed_tau(lv[i].etime - lv[i - 1].etime).size();
+            const AkLevelPlan pl = ak_level_plan(lv, (int)i, (int)B, taps_one_n, n_tau);
+            if (pl.steps.size() > 32) return R3DM_ERR_UNSUPPORTED;
+            o.head_form = pl.head ? 1 : 0; o.head_rows = pl.head_rows; o.n_launch = (int32_t)pl.steps.size(); o.n_steps = (int32_t)n_tau;
+            for (size_t m = 0; m < pl.steps.size(); ++m) { o.form[m] = pl.form[m]; o.steps[m] = pl.steps[m]; o.rows[m] = pl.rows[m]; }
+        }
+        plan_out[i] = o;
+    }
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_dev_akaze_head_bound(uint32_t width, uint32_t height, uint64_t* bound)
+{
+    if (!bound || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    *bound = ak_dev_bound(ak_levels((int)width, (int)height));
+    return R3DM_OK;
+}
+
+// Refused before anything touches a device (R3DM_OK or R3DM_ERR_INVALID): B outside 1 .. 8, a dimension above 4096 (or below 3), an
+// image size without an evolution level, a null image, a value that is not finite or lies outside [0, 1].
+// Every kernel of the scale space addresses by the plane's own (w, h) alone -- clamped or reflected taps, one-sided stencils on the rim,
+// strips and bands cut at the plane's edge -- and for a finite image in [0, 1] every plane stays finite: the gradient modulus is at most
+// 32 sqrt 2 (Scharr weights sum to 32), so a bin index (int)(m 299 / hmax) lies in 0 .. 299.  The extremum pass reads Ldet at interior
+// columns +- 1 and at rows border - 1 .. min(., h - 1) (border >= 1 of a level the table holds); the pruning reads the lists only.
+extern "C" int r3dm_dev_akaze_head_check(uint32_t B, const float* const* images, uint32_t width, uint32_t height)
+{
+    if (!images || B < 1 || B > kAkDevHeadMaxB) return R3DM_ERR_INVALID;
+    if (width < 3 || height < 3 || width > kAkDevHeadMaxDim || height > kAkDevHeadMaxDim) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    if (lv.empty() || lv.size() > 16) return R3DM_ERR_INVALID;
+    const size_t n0 = (size_t)width * height;
+    for (uint32_t b = 0; b < B; ++b) {
+        if (!images[b]) return R3DM_ERR_INVALID;
+        for (size_t k = 0; k < n0; ++k) if (!(images[b][k] >= 0.0f && images[b][k] <= 1.0f)) return R3DM_ERR_INVALID;    // (false for a NaN too)
+    }
+    return R3DM_OK;
+}
+
+// what both entries share once the planes stand on the device: the level table, the head launches at the bound, the read-back of
+// counts_out [B][nl][2] (candidates, kept) and lists_out [B][bound][3] (image b's kept lists, level after level, from b bound on)
+static int ak_dev_head_run(AkPass& p, float threshold, uint32_t* counts_out, float* lists_out)
+{
+    r3dm_ctx* c = p.c; hipStream_t st = p.st;
+    const int nl = p.nl; const uint32_t B = p.B;
+    AkDetection d;
+    int rc = ak_level_table(p, d);
+    if (rc != R3DM_OK) return rc;
+    if (d.bound == 0 || d.bound * B >= (1ull << 31)) { c->err = "developer head entry: more slots than the arrays index"; return R3DM_ERR_UNSUPPORTED; }
+    const uint32_t cap = (uint32_t)d.bound;
+    DevBuf &meta = p.tail(T_META), &slots = p.tail(T_SLOTS);
+    const size_t field = (size_t)B * cap;
+    R3DM_HIP(c, slots.ensure(field * kAkSlotBytes + 256));
+    R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
+    R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
+    R3DM_HIP(c, ak_head_launches(st, d.d_levels, nl, (int)B, d.tiles, d.n_tiles, d.max_rows, slots.as<unsigned char>(), cap, d.d_bmeta, threshold));
+    std::vector<AkLevelDev> dl(d.n_lv);
+    std::vector<uint32_t> cnt(4 * d.n_lv, 0u);
+    d.bm.assign(B, AkBatchMeta{});
+    R3DM_HIP(c, hipMemcpyAsync(dl.data(), d.d_levels, d.n_lv * sizeof(AkLevelDev), hipMemcpyDeviceToHost, st));
+    R3DM_HIP(c, hipMemcpyAsync(cnt.data(), d.ld[0].counts, cnt.size() * 4, hipMemcpyDeviceToHost, st));
+    R3DM_HIP(c, hipMemcpyAsync(d.bm.data(), d.d_bmeta, (size_t)B * sizeof(AkBatchMeta), hipMemcpyDeviceToHost, st));
+    R3DM_HIP(c, hipStreamSynchronize(st));
+    std::vector<float> l4;
+    for (uint32_t b = 0; b < B; ++b) {
+        if (d.bm[b].overflow) { c->err = "developer head entry: candidate count exceeds its own bound"; return R3DM_ERR_HIP; }
+        size_t at = (size_t)b * cap, kept = 0;
+        for (int i = 0; i < nl; ++i) {
+            const size_t k = (size_t)b * nl + i;
+            const uint32_t nc = cnt[4 * k], nk = cnt[4 * k + 1];
+            kept += nk;
+            if (nk > nc || kept > cap) { c->err = "developer head entry: a list longer than its candidates"; return R3DM_ERR_HIP; }
+            counts_out[2 * k] = nc; counts_out[2 * k + 1] = nk;
+            if (!nk) continue;
+            l4.resize(4 * (size_t)nk);
+            R3DM_HIP(c, hipMemcpyAsync(l4.data(), dl[k].list, (size_t)nk * 16, hipMemcpyDeviceToHost, st));
+            R3DM_HIP(c, hipStreamSynchronize(st));
+            for (size_t q = 0; q < nk; ++q) { lists_out[3 * (at + q)] = l4[4 * q]; lists_out[3 * (at + q) + 1] = l4[4 * q + 1]; lists_out[3 * (at + q) + 2] = l4[4 * q + 2]; }
+            at += nk;
+        }
+    }
+    return R3DM_OK;
+}
+
+// planes_out [B][nl][4]: Ldet, Lx, Ly, Lt of every level (the caller's, w_i x h_i floats each); small_out [B][309]: the bits of the
+// gradient modulus' maximum, the 300 bins, the bits of 1 / k^2 of octaves 0 .. 7; plan_out [nl]: what ak_evolve_level launched.
+extern "C" int r3dm_dev_akaze_head(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
+                                   float* const* planes_out, uint32_t* counts_out, float* lists_out, uint32_t* small_out, r3dm_dev_ak_plan* plan_out)
+{
+    const int vrc = r3dm_dev_akaze_head_check(B, images, width, height);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_head: images the entry does not take"; return vrc; }
+    if (!c || !planes_out || !counts_out || !lists_out || !small_out || !plan_out) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+        const int nl = (int)lv.size();
+        for (size_t k = 0; k < (size_t)B * nl * 4; ++k) if (!planes_out[k]) return R3DM_ERR_INVALID;
+        AkPass p{c, c->stream, B, (int)B, (int)width, (int)height, nl, (size_t)width * height, lv};
+        hipStream_t st = p.st;
+        int rc_plan = R3DM_OK;
+        if ((rc_plan = r3dm_dev_akaze_head_plan(width, height, B, plan_out)) != R3DM_OK) return rc_plan;
+        int rc = ak_buffers(p);
+        if (rc == R3DM_OK) rc = detect_upload(c, B, images, nullptr, p.n0, p.img, reinterpret_cast<unsigned char*>(p.tmp2));
+        p.taps_off = ak_taps(1.6f); p.taps_one = ak_taps(1.0f);
+        if (rc == R3DM_OK) rc = detect_area_tabs(c, p.tail(T_TABS), p.lv, p.half_tabs);
+        if (rc != R3DM_OK) return rc;
+        R3DM_HIP(c, ak_scale_space(p));
+        if ((rc = ak_dev_head_run(p, threshold, counts_out, lists_out)) != R3DM_OK) return rc;
+        for (uint32_t b = 0; b < B; ++b) {
+            for (int i = 0; i < nl; ++i) {
+                const size_t plane = (size_t)lv[i].w * lv[i].h;
+                float* const* P = planes_out + ((size_t)b * nl + i) * 4;
+                R3DM_HIP(c, hipMemcpyAsync(P[0], p.Ldet(i) + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+                R3DM_HIP(c, hipMemcpyAsync(P[1], p.Lx(i) + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+                R3DM_HIP(c, hipMemcpyAsync(P[2], p.Ly(i) + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+                R3DM_HIP(c, hipMemcpyAsync(P[3], p.Lt(i) + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+            }
+            uint32_t* S = small_out + (size_t)b * kAkDevSmallOut;
+            const uint32_t* D = p.small + (size_t)b * 4096;
+            R3DM_HIP(c, hipMemcpyAsync(S, D, 4, hipMemcpyDeviceToHost, st));
+            R3DM_HIP(c, hipMemcpyAsync(S + 1, D + 16, 300 * 4, hipMemcpyDeviceToHost, st));
+            R3DM_HIP(c, hipMemcpyAsync(S + 301, D + 1024, 8 * 4, hipMemcpyDeviceToHost, st));
+        }
+        R3DM_HIP(c, hipStreamSynchronize(st));
+        return R3DM_OK;
+    });
+}
+
+// The extremum pass and the in-level pruning on a caller's determinant planes.  Refused (R3DM_OK or R3DM_ERR_INVALID; c may be null):
+// what the tail's check refuses of planes -- n_levels and plane_dims [n_levels][2] other than the table's of (width, height), B outside
+// 1 .. 64, a null plane, a value that is not finite.  ldet [B][n_levels].
+// Why every read of an accepted input stays inside its plane: the extremum pass reads Ldet at columns border - 1 .. w - border (a lane
+// beyond the interior reads column border) and at rows border - 1 .. min(h - border, h - 1), border >= 1; the emit pass reads Ldet at the
+// set bits, interior positions; the pruning reads the candidate and list arrays only, which hold at most the bound's entries.
+extern "C" int r3dm_dev_akaze_extrema_check(uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
+                                            const float* const* ldet)
+{
+    if (!plane_dims || !ldet || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    if (B < 1 || B > kAkDevMaxB) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    const uint32_t nl = (uint32_t)lv.size();
+    if (nl < 1 || nl > 16 || n_levels != nl) return R3DM_ERR_INVALID;
+    for (uint32_t i = 0; i < nl; ++i) if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
+    for (uint32_t b = 0; b < B; ++b)
+        for (uint32_t i = 0; i < nl; ++i) {
+            const float* P = ldet[(size_t)b * nl + i];
+            if (!P) return R3DM_ERR_INVALID;
+            const size_t plane = (size_t)lv[i].w * lv[i].h;
+            for (size_t k = 0; k < plane; ++k) if (!std::isfinite(P[k])) return R3DM_ERR_INVALID;
+        }
+    return R3DM_OK;
+}
+
+// Lx, Ly and Lt of every level are zero; counts_out and lists_out as r3dm_dev_akaze_head's.
+extern "C" int r3dm_dev_akaze_extrema(r3dm_ctx* c, uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
+                                      const float* const* ldet, float threshold, uint32_t* counts_out, float* lists_out)
+{
+    const int vrc = r3dm_dev_akaze_extrema_check(width, height, B, n_levels, plane_dims, ldet);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_extrema: planes the kernels would mis-read"; return vrc; }
+    if (!c || !counts_out || !lists_out) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+        const int nl = (int)lv.size();
+        AkPass p{c, c->stream, B, (int)B, (int)width, (int)height, nl, (size_t)width * height, lv};
+        hipStream_t st = p.st;
+        int rc = ak_buffers(p);
+        if (rc != R3DM_OK) return rc;
+        for (int i = 0; i < nl; ++i) {
+            const size_t plane = (size_t)lv[i].w * lv[i].h;
+            for (uint32_t b = 0; b < B; ++b) R3DM_HIP(c, hipMemcpyAsync(p.Ldet(i) + b * plane, ldet[(size_t)b * nl + i], plane * 4, hipMemcpyHostToDevice, st));
+            R3DM_HIP(c, hipMemsetAsync(p.Lx(i), 0, (size_t)B * plane * 4, st));
+            R3DM_HIP(c, hipMemsetAsync(p.Ly(i), 0, (size_t)B * plane * 4, st));
+            R3DM_HIP(c, hipMemsetAsync(p.Lt(i), 0, (size_t)B * plane * 4, st));
+        }
+        return ak_dev_head_run(p, threshold, counts_out, lists_out);
     });
 }
 #endif  // R3DM_DEVTOOLS
