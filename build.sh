@@ -10,10 +10,9 @@ HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 WHAT=${1:-all}
 SRC="kernels_match.hip kernels_match_16bit.hip kernels_match_hamming.hip kernels_match_exact.hip kernels_match_mutual.hip kernels_match_head.hip kernels_match_knn.hip kernels_match_knn16.hip kernels_match_knn8.hip kernels_filter.hip kernels_filter_e.hip kernels_filter_coop.hip kernels_liop.hip kernels_ann.hip kernels_hnsw.hip kernels_mrpt.hip kernels_akaze.hip kernels_akaze_classic.hip kernels_graph.hip kernels_guided.hip kernels_tracks.hip api_core.cpp api_match.cpp api_preselect.cpp api_ann.cpp api_hnsw.cpp api_mrpt.cpp api_filter.cpp api_guided.cpp api_tracks.cpp api_akaze.cpp api_akaze_classic.cpp api_liop.cpp api_features.cpp api_multi.cpp api_comm.cpp compute_matches.cpp"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -fopenmp -Wall -Wno-unused-result -Iinclude"
-HDRS="regard3d_amd/csrc/*.hpp regard3d_amd/csrc/*.inc include/*.h include/*.hpp"
-# kernels_filter.hip (wg_fence) orders global-memory exchanges INSIDE a workgroup with a workgroup-scope fence: valid only while the
+# filter_device.hpp (wg_fence) orders global-memory exchanges INSIDE a workgroup with a workgroup-scope fence: valid only while the
 # waves of a workgroup share a CU and its L1, i.e. never in threadgroup-split mode
-case " $HIPCC $FLAGS $HIPCC_FLAGS $CXXFLAGS " in *tgsplit*) echo "build.sh: -mtgsplit is not supported (kernels_filter.hip: wg_fence)"; exit 1;; esac
+case " $HIPCC $FLAGS $HIPCC_FLAGS $CXXFLAGS " in *tgsplit*) echo "build.sh: -mtgsplit is not supported (filter_device.hpp: wg_fence)"; exit 1;; esac
 
 build_one() {   # $1 = variant dir, $2 = extra flags, $3 = output, $4 = extra sources
   local dir=build/$1; mkdir -p $dir
@@ -21,15 +20,13 @@ build_one() {   # $1 = variant dir, $2 = extra flags, $3 = output, $4 = extra so
   for f in $SRC; do
     local o=$dir/${f%.*}.o
     objs="$objs $o"
-    local stale=0
-    if [ ! -f $o ]; then stale=1; else
-      for d in regard3d_amd/csrc/$f $HDRS build.sh; do [ $d -nt $o ] && stale=1; done
+    # stale when the source, build.sh or one of the project's files the last compilation read (its -MMD list) is newer than the object
+    local dep=${o%.o}.d stale=0
+    if [ ! -f $o ] || [ ! -f $dep ]; then stale=1; else
+      for d in build.sh $(sed -e 's/^[^ ]*: *//' -e 's/ *\\$//' $dep); do { [ ! -e $d ] || [ $d -nt $o ]; } && stale=1; done
     fi
-    local extra=""
     # (no per-file compiler options: the essential-matrix kernel no longer needs -amdgpu-spill-sgpr-to-vgpr=0)
-    case $f in kernels_filter_e.hip|kernels_filter_coop.hip)
-      [ regard3d_amd/csrc/kernels_filter.hip -nt $o ] && stale=1; [ regard3d_amd/csrc/kernels_filter_coop.hip -nt $o ] && stale=1;; esac
-    if [ $stale = 1 ]; then ( $HIPCC $FLAGS $2 $extra -x hip -c regard3d_amd/csrc/$f -o $o ) & pids="$pids $!"; fi
+    if [ $stale = 1 ]; then ( $HIPCC $FLAGS $2 -MMD -MF $dep -x hip -c regard3d_amd/csrc/$f -o $o ) & pids="$pids $!"; fi
   done
   for f in $4; do
     local o=$dir/$(basename ${f%.*}).o

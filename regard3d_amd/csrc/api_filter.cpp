@@ -250,7 +250,7 @@ int FilterCall::upload(const r3dm_match* dev_matches)
     const FilterPlan& P = plan;
     const uint32_t NI = P.n_items(), max_m = P.max_m, n_coop = (uint32_t)P.coop_items.size();
     const uint64_t n_slice = P.soff[NI];
-    // host tables in the reference's own float arithmetic (glibc log10f), see kernels_filter.hip
+    // host tables in the reference's own float arithmetic (glibc log10f), see acransac_body (filter_acransac.inc)
     std::vector<float> l10(max_m + 2), lck(max_m + 2);
     for (uint32_t k = 0; k <= max_m + 1; ++k) l10[k] = std::log10((float)k);
     for (uint32_t n = 0; n <= max_m + 1; ++n) {
@@ -836,7 +836,7 @@ extern "C" int r3dm_filter_E(r3dm_ctx* c, const r3dm_graph* putative, double max
 // workers (kernels_filter_coop.hip) -- so a collection of few, long pairs (24 photographs: 94 putative pairs of
 // 10-20 k matches) fills the chip instead of a third of it, and a pair is no longer bound by one CU's f64 rate.  Short pairs keep the
 // one-workgroup-per-pair kernels, one launch per kind on streams of three priority classes, beside the cooperative kernel.  What lets
-// kernels overlap at all was taking the agent-scope fences out of their barriers (kernels_filter.hip: wg_fence).  Measured and
+// kernels overlap at all was taking the agent-scope fences out of their barriers (filter_device.hpp: wg_fence).  Measured and
 // dropped in round 3: one merged one-workgroup-per-pair kernel with the three model kinds as branches (hipcc's code for the
 // fundamental-matrix branch faulted, product build only, spilled lists only); the cooperative kernel keeps its phases out of line
 // (noinline) for the same family of reasons.

@@ -1,6 +1,6 @@
 // kernels_filter_coop.hip -- AC-RANSAC of a LONG pair spread over several workgroups (round 4).
 //
-// The one-workgroup-per-pair kernel (kernels_filter.hip) binds a pair to one CU: a pair of 10-20 k putative matches is bound by
+// The one-workgroup-per-pair kernel (filter_acransac.inc) binds a pair to one CU: a pair of 10-20 k putative matches is bound by
 // that CU's f64 rate, and a collection of few, long pairs (what Regard3D produces: tens of photographs) leaves most of the chip
 // idle.  Here a pair with more than a threshold of matches (api_filter.cpp: 4096) is evaluated by G workgroups:
 //
@@ -34,8 +34,7 @@
 // word relaxed with s_sleep between reads.  No agent-scope fence anywhere: the first version fenced (__threadfence, every thread,
 // four times per batch) and polled its queue with acquire loads -- correct, and 15x slower than the work on a collection of 66
 // pairs (every fence a write-back + invalidate that the other 255 workgroups pay for).
-#define R3DM_FILTER_DEVICE_ONLY 1
-#include "kernels_filter.hip"
+#include "filter_device.hpp"
 
 namespace r3dm {
 
@@ -527,7 +526,7 @@ __device__ __forceinline__ void coop_run_task(const FilterParams* params, unsign
 // sort, 150 us per full evaluation on an idle device and 3-4x that with the other 255 workgroups loading the memory system.)
 // The stages `size_from .. size_to` of the network on the block that starts at entry i0 (directions from the GLOBAL index, so blocks
 // sorted one after the other come out alternately ascending / descending, as the merge stages behind them need).  Strides >= the
-// block are not this routine's business.  Same exchange rules as wg_sort_regs (kernels_filter.hip).  The caller has made the
+// block are not this routine's business.  Same exchange rules as wg_sort_regs (filter_device.hpp).  The caller has made the
 // lists visible to the workgroup (wg_sync_t<true>) and finds them visible again on return.
 template <int E>
 __device__ __forceinline__ void coop_sort_block(unsigned long long* __restrict__ keys, uint32_t* __restrict__ sidx,

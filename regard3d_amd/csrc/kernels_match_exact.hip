@@ -176,7 +176,7 @@ hipError_t launch_l2_exact_batch(hipStream_t st, const MatchParams& P, uint32_t 
 // visible to the other waves of the SAME workgroup after a barrier.  They share one CU and its L1, so a workgroup-scope fence and
 // the completion of this wave's own memory operations is all that takes (an agent-scope fence -- what __threadfence() is -- writes
 // the L2 back on this eight-L2 part: ~20 us per sorting stage, 2.5 ms for a pair of 20 k matches; same shortcut and the same two
-// conditions as wg_fence in kernels_filter.hip: gfx9 s_waitcnt encoding, no threadgroup-split mode -- build.sh refuses -mtgsplit)
+// conditions as wg_fence in filter_device.hpp: gfx9 s_waitcnt encoding, no threadgroup-split mode -- build.sh refuses -mtgsplit)
 #if defined(__HIP_DEVICE_COMPILE__)
 #if !defined(__gfx950__) && !defined(__gfx942__)
 #error "fin_fence: the s_waitcnt encoding and the same-CU L1 argument are written for gfx942 / gfx950"

@@ -32,7 +32,7 @@ __device__ __forceinline__ float mr_from_order_bits(uint32_t b)
 {
     return __uint_as_float((b & 0x80000000u) ? (b & 0x7FFFFFFFu) : ~b);
 }
-// global-memory exchange INSIDE a workgroup (same recipe as kernels_filter.hip: wg_fence): the waves of a workgroup share one CU
+// global-memory exchange INSIDE a workgroup (same recipe as filter_device.hpp: wg_fence): the waves of a workgroup share one CU
 // and its L1, a workgroup-scope fence + an explicit wait for outstanding stores and loads is enough (no -mtgsplit: build.sh)
 __device__ __forceinline__ void mr_sync_global()
 {

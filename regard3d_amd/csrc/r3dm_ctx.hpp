@@ -7,7 +7,8 @@
 //   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
 //   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules
-//   api_filter.cpp    AC-RANSAC geometric filters (F, E, H)
+//   api_filter.cpp    AC-RANSAC geometric filters (F, E, H); their kernels: filter_device.hpp (shared device routines), filter_acransac.inc
+//                     (one workgroup per pair; kernels_filter.hip F / H, kernels_filter_e.hip E), kernels_filter_coop.hip (long pairs)
 //   api_tracks.cpp    feature tracks of a match graph (r3dm_build_tracks), the track filter applied to the graph, r3dm_tracks_in_pair
 //   api_akaze.cpp     the frame of both detector arms (checks, upload, INTER_AREA tables, statistics tail, DetectedBatch's writer) and the
 //                     Fast-A-KAZE arm: its pass in phases, MLDB, r3dm_detect_akaze / _mldb / _mldb_batch / _batch, r3dm_gray_from_bgr8

@@ -326,7 +326,7 @@ struct FilterParams {
     uint32_t*     pool_scratch;   // [n_matches]    current sampling pool
     float*        scratch_logc;   // [n_matches + n_items + 1] logcombi(k, m) table of each item
     double*       la_tab;         // [n_items][1024] NFA slope of every residual-histogram bin of the item (the one-workgroup kernel's scout pass)
-    uint32_t      scout;          // != 0: the one-workgroup kernel scouts its models a wavefront each ahead of the walk (kernels_filter.hip)
+    uint32_t      scout;          // != 0: the one-workgroup kernel scouts its models a wavefront each ahead of the walk (filter_acransac.inc)
     // ---- long pairs: the cooperative kernel (kernels_filter_coop.hip).  Items order[0 .. n_short) run on the one-workgroup-per-pair
     // kernel, the n_coop items of coop_items on a pool of workers over a task queue.
     uint32_t      n_short;
@@ -353,7 +353,7 @@ struct FilterParams {
 
 // Workgroup barrier for waves that exchange data through LDS, with an EXPLICIT `s_waitcnt lgkmcnt(0)`.  hipcc (ROCm 7.2) was
 // seen to emit a bare s_barrier -- dropping the wait that __syncthreads' release fence implies -- when the barrier opens a loop
-// header and the pending ds_write sits in the latch block (kernels_filter.hip, chunk loop: other waves then read a stale loop
+// header and the pending ds_write sits in the latch block (filter_acransac.inc, chunk loop: other waves then read a stale loop
 // counter).  The builtin cannot be optimised away and costs nothing when nothing is pending.
 #if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
 __device__ __forceinline__ void r3dm_syncthreads()
@@ -547,6 +547,7 @@ hipError_t launch_head_gather(hipStream_t st, const void* src, const uint32_t* r
 hipError_t launch_head_match(hipStream_t st, const HeadMatchParams& P, uint32_t n_pairs, bool binary, uint32_t G_or_words);
 hipError_t launch_finalize(hipStream_t st, const FinalizeParams& P);
 hipError_t launch_filter_F(hipStream_t st, const FilterParams& P);
+hipError_t launch_filter_E(hipStream_t st, const FilterParams& P, size_t lds);   // the E kernels of launch_filter_F (kernels_filter_e.hip)
 // one pool of workers for the long pairs of up to three filters: dev_params = FilterParams[3] in device memory indexed by model kind,
 // q = the scheduling words, start = kind << 30 | pair in the order pairs are started
 hipError_t launch_filter_coop(hipStream_t st, const FilterParams* dev_params, uint32_t* q, const uint32_t* start, uint32_t n_workers);

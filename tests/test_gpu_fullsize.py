@@ -96,7 +96,7 @@ def test_filter_is_independent_of_batching_and_sharding(ctx):
 
 def test_filters_are_deterministic_when_workgroups_share_a_cu(ctx, oracle):
     """Regression: the homography kernel (two workgroups per CU) returned different pair counts from run to run, up to memory
-    faults, because the barrier at the top of its chunk loop was emitted without the LDS wait (kernels_filter.hip).  Enough
+    faults, because the barrier at the top of its chunk loop was emitted without the LDS wait (filter_acransac.inc).  Enough
     pairs to oversubscribe the CUs, every filter several times in mixed order, identical graphs required; a sample of the H
     results is checked against the CPU restatement."""
     sc = synth.make_scene(110, 4096, "sift", seed=2002)

@@ -537,7 +537,7 @@ def test_filters_on_degenerate_and_tiny_pairs(ctx, oracle):
 @pytest.mark.parametrize("scout", ["0", "3"])
 def test_filters_skip_no_model_that_could_win(ctx, scout):
     """The AC-RANSAC kernels skip the sort of a model whose histogram bound on the NFA stays above the best NFA so far
-    (kernels_filter.hip).  The developer build with R3DM_FILTER_CHECK=1 skips nothing and checks `bound <= NFA` on every model it
+    (filter_acransac.inc).  The developer build with R3DM_FILTER_CHECK=1 skips nothing and checks `bound <= NFA` on every model it
     evaluates (invariant 8 -> error); its inlier sets and models must equal the product's.  R3DM_FILTER_SCOUT=3 beside it: the scout
     pass runs too (reciprocal intervals instead of divisions, the NFA bound from the two ends of every bin's count range less the
     tables' drift) and every model's exact count and NFA are checked against what the scout promised (invariants 9, 10)."""

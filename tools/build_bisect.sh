@@ -1,9 +1,8 @@
 #!/bin/bash
-# Throwaway variants of the AC-RANSAC filter translation units, linked against the current product objects (run build.sh first)
-#   -> regard3d_amd/libr3dm_bisect_<v>.so, loaded with api.use_library():
-#   timing  -DR3DM_E_TIMING: the report's (threshold, NFA) fields carry wave-0 cycles of the solve / evaluation phases
-#           (all three models; tools/filter_phase_split.py)
-# Earlier variants (the E filter's nondeterminism bisect, profiles/r02_d..f): git history.
+# The timing variant of the one-workgroup AC-RANSAC kernels: kernels_filter.hip and kernels_filter_e.hip compiled with
+# -DR3DM_E_TIMING (E_TIME, filter_device.hpp) and linked against the current product objects (run build.sh first)
+#   -> regard3d_amd/libr3dm_bisect_timing.so, loaded with api.use_library(): the report's (threshold, NFA) fields carry wave-0 cycles
+#      of the solve / evaluation phases (all three models; tools/filter_phase_split.py)
 set -e
 cd "$(dirname "$0")/.."
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}

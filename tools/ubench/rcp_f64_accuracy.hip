@@ -1,5 +1,5 @@
 // tools/ubench/rcp_f64_accuracy.hip -- how good is v_rcp_f64 on gfx950, bare and after one Newton step?  The scout pass of the
-// AC-RANSAC kernel (kernels_filter.hip: scout_residual) replaces IEEE divisions by it and carries error intervals; this is the
+// AC-RANSAC kernel (filter_acransac.inc: scout_residual) replaces IEEE divisions by it and carries error intervals; this is the
 // measurement behind their margins.
 //   hipcc --offload-arch=gfx950 -O2 -ffp-contract=off -o /tmp/rcp_acc tools/ubench/rcp_f64_accuracy.hip && /tmp/rcp_acc
 #include <hip/hip_runtime.h>
