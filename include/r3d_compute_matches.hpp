@@ -95,7 +95,8 @@ public:
     // default: float x 144 (R3D_AKAZE_LIOP_Regions).  The regions type also chooses what the features stage computes from pixels:
     // (R3DM_F32, 144) LIOP, what Regard3D computes; (R3DM_BIN, 61) the MLDB-486 rows of the Fast-AKAZE detector (r3dm_set_descriptor_arm:
     // no reference counterpart, BASELINE config C3), matched by the binary rules (unsquared ratio, exhaustive matcher, Hamming fast path);
-    // with any other type views must come with their .feat / .desc
+    // (R3DM_F32, 64) the M-SURF-64 rows of the same detector (R3DM_DESCRIPTOR_MSURF; OpenMVG's AKAZE_FLOAT), matched by the float rules
+    // as LIOP is; with any other type views must come with their .feat / .desc
     void setRegionsType(r3dm_dtype dtype, uint32_t dim);
     void setSeed(uint64_t seed) { seed_ = seed; }
     // The exhaustive matcher's exact MFMA fast paths: split-f16 nomination for real-valued descriptors (LIOP-144, what Regard3D matches:
@@ -250,7 +251,7 @@ typedef struct {
     uint64_t n_putative_pairs, n_putative_matches, n_F_pairs, n_F_matches, n_E_pairs, n_E_matches, n_H_pairs, n_H_matches;
     uint64_t match_was_exhaustive;   /* 1: the exhaustive matcher ran (arm 4 / 9, or an approximate arm routed to it) */
     r3dm_features_totals features;
-    uint64_t descriptor_arm;         /* R3DM_DESCRIPTOR_LIOP or R3DM_DESCRIPTOR_MLDB: the descriptor arm of the features stage of this call */
+    uint64_t descriptor_arm;         /* R3DM_DESCRIPTOR_LIOP, _MLDB or _MSURF: the descriptor arm of the features stage of this call */
 } r3dm_stage_report;
 int r3dm_compute_matches_stage(const int* device_ids, int n_devices, const char* matches_dir, const r3dm_view_image* views, uint32_t n_views,
                                float threshold, float dist_ratio, int matching_algorithm, int compute_F, int compute_E, int compute_H,
@@ -276,6 +277,7 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_DETECTOR_AKAZE   64u   /* keypointDetectorList_ = {"AKAZE"}, the GUI's keypointDetectorType 0 (classic A-KAZE); default {"Fast-AKAZE"} */
 #define R3DM_STAGE_MUTUAL_MATCHING 128u   /* mutual nearest-neighbour matching (R3DComputeMatches::setMutualMatching(true), r3dm_set_mutual_matching); default: every query's match is kept */
 #define R3DM_STAGE_DESCRIPTOR_MLDB 512u   /* setRegionsType(R3DM_BIN, 61): the features stage writes MLDB-486 rows (r3dm_set_descriptor_arm), the matcher runs its binary rules; default LIOP (float x 144) */
+#define R3DM_STAGE_DESCRIPTOR_MSURF 1024u /* setRegionsType(R3DM_F32, 64): the features stage writes M-SURF-64 rows (r3dm_set_descriptor_arm); together with R3DM_STAGE_DESCRIPTOR_MLDB: R3DM_ERR_INVALID */
 #define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,

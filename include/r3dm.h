@@ -625,6 +625,21 @@ int r3dm_detect_akaze_mldb_batch(r3dm_ctx* ctx, uint32_t n_images, const float* 
                                  float threshold, float* const* keypoints_out, unsigned char* const* descriptors_out, uint32_t cap,
                                  uint32_t* n_out);
 
+/* Fast-A-KAZE keypoints with their M-SURF-64 rows, the float descriptor of the vendored Fast-A-KAZE (MSURF_Descriptor_64_InvokerV2,
+ * src/thirdparty/fast-akaze/AKAZEFeatures.cpp:1431-1544; OpenMVG's AKAZE_FLOAT): 64 floats per keypoint, unit length.  Shapes as the
+ * MLDB entries above; descriptors_out (descriptors_out[b]) holds cap x 64 floats.
+ * THE BORDER IS THE DESCRIPTOR'S: as the reference does when it is configured for the KAZE descriptors (:78-84,105,112), the detector
+ * of these entries runs on a level table whose borders are fRound(12 sqrt(2) sigma_size) + 1, not MLDB's 10 sqrt(2): levels are cut
+ * sooner on small images and keypoints near the frame are not found, so the keypoints are NOT those of r3dm_detect_akaze(_mldb) there.
+ * The exponential of the Gaussian weights is the library's own (evaluated in double, within 0.5 + 2^-28 ulp of exp; the reference
+ * calls libm's expf, which a device cannot reproduce bit for bit): rows differ from a CPU run of the reference in the last bits only
+ * (DESIGN.md section 4.8).  A keypoint whose window holds no gradient has length 0 and a row of NaN, as in the reference. */
+int r3dm_detect_akaze_msurf(r3dm_ctx* ctx, const float* image, uint32_t width, uint32_t height, float threshold,
+                            float* keypoints_out, float* descriptors_out, uint32_t cap, uint32_t* n_out);
+int r3dm_detect_akaze_msurf_batch(r3dm_ctx* ctx, uint32_t n_images, const float* const* images, uint32_t width, uint32_t height,
+                                  float threshold, float* const* keypoints_out, float* const* descriptors_out, uint32_t cap,
+                                  uint32_t* n_out);
+
 /* ---- keypoint detection: classic A-KAZE ----
  * The "AKAZE" arm of Regard3DFeatures::detectKeypoints (src/Regard3DFeatures.cpp:578-589), the GUI's default detector:
  * cv::AKAZE::create(DESCRIPTOR_MLDB, 0, 3, threshold, 4, 4, DIFF_PM_G2) + detect(), restated as libAKAZE, the classic code of the
@@ -664,9 +679,16 @@ int r3dm_set_keypoint_detector(r3dm_ctx* ctx, int arm);
  * 8-byte count followed by count x 61 bytes (KeypointSet::saveToBinFile with Descriptor<unsigned char, 61>) -- what the facade reads
  * under setRegionsType(R3DM_BIN, 61).  Skip rule, sink, deferred files and scheduling are shared.  MLDB needs the Fast arm's level
  * planes: together with R3DM_DETECTOR_AKAZE a features call returns R3DM_ERR_UNSUPPORTED (r3dm_last_error names the arm), computes
- * nothing and leaves both switches as they are.  Other values: R3DM_ERR_INVALID. */
+ * nothing and leaves both switches as they are.
+ * R3DM_DESCRIPTOR_MSURF is the M-SURF-64 of r3dm_detect_akaze_msurf: same .feat text format, a .desc of the 8-byte count followed by
+ * count x 64 floats (the LIOP layout with 64 columns: what the facade reads under setRegionsType(R3DM_F32, 64)), the sink's pointer
+ * at n_features x 64 floats.  The detector then runs on the M-SURF level table (wider borders, see r3dm_detect_akaze_msurf), so the
+ * .feat of an image near whose frame keypoints lie differs from the other arms'.  With R3DM_DETECTOR_AKAZE it is refused exactly as
+ * MLDB is.  Its value is 3: 2 stays unassigned and refused (it is the value the suite holds to R3DM_ERR_INVALID).
+ * Other values: R3DM_ERR_INVALID. */
 #define R3DM_DESCRIPTOR_LIOP 0
 #define R3DM_DESCRIPTOR_MLDB 1
+#define R3DM_DESCRIPTOR_MSURF 3
 int r3dm_set_descriptor_arm(r3dm_ctx* ctx, int arm);
 
 /* ---- the per-image work item of the features stage ----
@@ -675,7 +697,7 @@ int r3dm_set_descriptor_arm(r3dm_ctx* ctx, int arm);
  * Regard3DFeatures::detectAndExtract with the "Fast-AKAZE" detector + LIOP and KeypointSet::saveToBinFile
  * (src/keypointSet.hpp:61-67): <feat_path> gets one "x y scale orientation" line per feature (scale = size / 2), <desc_path>
  * an 8-byte count followed by count x 144 floats -- the files r3dm_compute_matches_dir / the facade read back.  (Under
- * R3DM_DESCRIPTOR_MLDB: count x 61 bytes, r3dm_set_descriptor_arm.)
+ * R3DM_DESCRIPTOR_MLDB: count x 61 bytes, under R3DM_DESCRIPTOR_MSURF: count x 64 floats, r3dm_set_descriptor_arm.)
  * As in the reference (:139-142) the work item does nothing when BOTH files already exist (n_features = rows of the existing .desc).
  * Image decoding (cv::imread) stays with the caller. */
 int r3dm_gray_from_bgr8(r3dm_ctx* ctx, const unsigned char* bgr, uint32_t width, uint32_t height, float* gray_out);
@@ -906,7 +928,7 @@ typedef struct {
     double   ms_wall_match;        /* whole r3dm_match_pairs call                                   */
     double   ms_wall_match_post;   /* of which: exact scans + finalisation + copies back + assembly */
     double   ms_wall_filter;       /* whole r3dm_filter_F call                                      */
-    double   ms_liop_kernel;       /* HIP-event time of the last r3dm_liop_describe_patches kernel (a features pass under R3DM_DESCRIPTOR_MLDB: of its MLDB launch) */
+    double   ms_liop_kernel;       /* HIP-event time of the last r3dm_liop_describe_patches kernel (a features pass under R3DM_DESCRIPTOR_MLDB / _MSURF: of its MLDB / M-SURF launch) */
     /* r3dm_match_pairs_kgraph */
     double   ms_ann_build;         /* HIP-event time of the index builds triggered by the call      */
     double   ms_ann_search;        /* HIP-event time of the search kernel                           */
@@ -924,7 +946,7 @@ typedef struct {
     /* the last detector pass (r3dm_detect_akaze*, r3dm_extract_features_*) */
     double   ms_detect_kernels;    /* HIP-event time from the first scale-space launch to the keypoint compaction, all images of the pass */
     double   detect_algorithmic_bytes; /* HBM bytes the pass structure implies: every stencil pass reads / writes whole image planes once */
-    double   ms_liop_wall;         /* host + device time of the LIOP half of the last features pass (patch maps, two launches, copy back); under R3DM_DESCRIPTOR_MLDB: of the MLDB half */
+    double   ms_liop_wall;         /* host + device time of the LIOP half of the last features pass (patch maps, two launches, copy back); under R3DM_DESCRIPTOR_MLDB / _MSURF: of that descriptor's half */
     double   ms_feature_files;     /* time spent writing the .feat / .desc files of the last features pass                              */
     /* r3dm_match_pairs_hnsw (ms_ann_build / ms_ann_search / n_ann_built / n_ann_dist are shared with the KGraph path) */
     uint64_t n_hnsw_launches;      /* launches of the HNSW search kernel                                                                */
@@ -955,7 +977,7 @@ typedef struct {
     uint64_t n_regrows;                /* detection phases repeated because an image had more candidates than slots            */
     double   ms_detect_kernels;        /* HIP-event time, first scale-space launch .. keypoint compaction                      */
     double   detect_algorithmic_bytes; /* HBM bytes the pass structure implies (every stencil pass moves whole planes once)    */
-    double   ms_liop_kernels;          /* HIP-event time of the LIOP patch extraction + descriptor launches (+ the MLDB launches of passes under R3DM_DESCRIPTOR_MLDB) */
+    double   ms_liop_kernels;          /* HIP-event time of the LIOP patch extraction + descriptor launches (+ the MLDB / M-SURF launches of passes under those arms) */
     double   ms_wall;                  /* wall time inside the features entry points (detector + LIOP + copies + files)        */
     double   ms_files;                 /* of which: writing .feat / .desc                                                      */
 } r3dm_features_totals;
@@ -969,7 +991,7 @@ int r3dm_host_threads(int want);
  * (not for skipped ones), from a helper thread of the library (several images of a batch may arrive concurrently: the sink must be
  * thread-safe), after the image's two files are written.  desc_device = n_features x 144 floats
  * in DEVICE memory of the computing context (valid until the sink returns) -- under R3DM_DESCRIPTOR_MLDB it points at n_features x 61
- * BYTES there instead (the type of the argument stays; r3dm_set_image(dim 61, R3DM_BIN) takes the pointer as it is); xy_as_written = n_features x 2 floats exactly as a reader
+ * BYTES there instead (the type of the argument stays; r3dm_set_image(dim 61, R3DM_BIN) takes the pointer as it is), under R3DM_DESCRIPTOR_MSURF at n_features x 64 floats (r3dm_set_image(dim 64, R3DM_F32)); xy_as_written = n_features x 2 floats exactly as a reader
  * of the .feat file parses them (the file holds 6 significant digits).  What Regions_Provider::load would read back from the files
  * (src/R3DComputeMatches.cpp:2040) is thus handed over without the round trip through the file system and the PCIe bus: the facade
  * registers the view with the matcher straight from it (r3dm_set_image accepts device pointers).  image_index = the index in the

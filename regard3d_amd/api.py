@@ -49,6 +49,7 @@ EXPORTS = [
     "r3dm_detect_akaze_mldb_batch", "r3dm_set_descriptor_arm", "r3dm_multi_set_descriptor_arm",
     "r3dm_set_prefix_pruning", "r3dm_get_prefix_pruning_counts", "r3dm_multi_set_prefix_pruning", "r3dm_multi_get_prefix_pruning_counts",
     "r3dm_get_pair_filter_counts", "r3dm_multi_get_pair_filter_counts",
+    "r3dm_detect_akaze_msurf", "r3dm_detect_akaze_msurf_batch",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
@@ -56,9 +57,12 @@ STAGE_DETECTOR_AKAZE = 64
 STAGE_MUTUAL_MATCHING = 128
 STAGE_PREEMPTIVE_MATCHING = 256
 STAGE_DESCRIPTOR_MLDB = 512
+STAGE_DESCRIPTOR_MSURF = 1024
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
 DESCRIPTORS = {"LIOP": 0, "MLDB": 1}             # R3DM_DESCRIPTOR_LIOP / R3DM_DESCRIPTOR_MLDB
+DESCRIPTOR_ARMS = {**DESCRIPTORS, "MSURF": 3}     # every arm r3dm_set_descriptor_arm takes: + R3DM_DESCRIPTOR_MSURF (2 is unassigned)
+_DESCRIPTOR_STAGE_FLAGS = {"LIOP": 0, "MLDB": STAGE_DESCRIPTOR_MLDB, "MSURF": STAGE_DESCRIPTOR_MSURF}
 
 
 def _detector_flag(detector: str) -> int:
@@ -68,9 +72,9 @@ def _detector_flag(detector: str) -> int:
 
 
 def _descriptor_flag(descriptor: str) -> int:
-    if descriptor not in DESCRIPTORS:
-        raise ValueError(f"descriptor must be one of {sorted(DESCRIPTORS)}, not {descriptor!r}")
-    return STAGE_DESCRIPTOR_MLDB if descriptor == "MLDB" else 0
+    if descriptor not in DESCRIPTOR_ARMS:
+        raise ValueError(f"descriptor must be one of {sorted(DESCRIPTOR_ARMS)}, not {descriptor!r}")
+    return _DESCRIPTOR_STAGE_FLAGS[descriptor]
 
 
 class R3dmError(RuntimeError):
@@ -150,7 +154,7 @@ class StageReport(C.Structure):
                                           "ms_match_kernels", "ms_F_kernels", "ms_E_kernels", "ms_H_kernels", "ms_filters_wall", "ms_match_post")] + \
                [(k, C.c_uint64) for k in ("images_extracted", "n_keypoints", "n_putative_pairs", "n_putative_matches", "n_F_pairs", "n_F_matches",
                                           "n_E_pairs", "n_E_matches", "n_H_pairs", "n_H_matches", "match_was_exhaustive")] + [("features", FeaturesTotals)] + \
-               [("descriptor_arm", C.c_uint64)]          # DESCRIPTORS value: what the features stage of the call describes keypoints with
+               [("descriptor_arm", C.c_uint64)]          # DESCRIPTOR_ARMS value: what the features stage of the call describes keypoints with
 
     def as_dict(self):
         d = {k: getattr(self, k) for k, _ in self._fields_ if k != "features"}
@@ -200,7 +204,8 @@ class Stage:
             guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP") -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
         (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING); preemptive: preemptive matching at 128 / 4
-        (R3DM_STAGE_PREEMPTIVE_MATCHING); descriptor: "LIOP" or "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB: binary regions, 61 bytes)"""
+        (R3DM_STAGE_PREEMPTIVE_MATCHING); descriptor: "LIOP", "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB: binary regions, 61 bytes) or "MSURF"
+        (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64, 64 floats)"""
         dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
         keep = []
         arr = _stage_views(views, keep)
@@ -234,8 +239,9 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
     detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE); mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive:
-    R3DM_STAGE_PREEMPTIVE_MATCHING (head_rows 128, min_matches 4); descriptor: "LIOP" (default) or "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB:
-    the features stage writes MLDB-486 rows, the matcher runs its binary rules)."""
+    R3DM_STAGE_PREEMPTIVE_MATCHING (head_rows 128, min_matches 4); descriptor: "LIOP" (default), "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB:
+    the features stage writes MLDB-486 rows, the matcher runs its binary rules) or "MSURF" (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64
+    rows of 64 floats, matched by the float rules as LIOP is)."""
     dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
     L = load_library()
     keep = []
@@ -423,6 +429,8 @@ def load_library():
     L.r3dm_get_features_totals.argtypes = [vp, vp]
     L.r3dm_detect_akaze_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
     L.r3dm_detect_akaze_mldb_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
+    L.r3dm_detect_akaze_msurf.argtypes = [vp, vp, u32, u32, C.c_float, vp, vp, u32, C.POINTER(u32)]
+    L.r3dm_detect_akaze_msurf_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
     L.r3dm_detect_akaze_classic.argtypes = [vp, vp, u32, u32, C.c_float, vp, vp, u32, C.POINTER(u32)]
     L.r3dm_detect_akaze_classic_batch.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, u32, vp]
     L.r3dm_extract_features_batch.argtypes = [vp, u32, vp, vp, u32, u32, C.c_float, vp, vp, vp]
@@ -566,6 +574,53 @@ def dev_akaze_tail_levels(L, width: int, height: int):
     if rc != 0:
         raise R3dmError(f"r3dm_dev_akaze_tail_levels -> {rc}")
     return [{k: getattr(lv[i], k) for k, _ in DevAkLevel._fields_} for i in range(n.value)]
+
+
+MSURF_ITEM = np.dtype([("level", np.uint32), ("xf", np.float32), ("yf", np.float32), ("co", np.float32), ("si", np.float32),
+                       ("scale", np.int32)])          # AkMsurfItem (r3dm_internal.hpp): a keypoint in level coordinates, cos / sin of its angle
+
+
+def bind_dev_akaze_msurf(L):
+    """the developer build's M-SURF-64 kernel entries (libr3dm_dev.so only, declared in no header), bound when first asked for"""
+    if getattr(L, "_r3dm_dev_msurf_bound", False):
+        return L
+    if not hasattr(L, "r3dm_dev_akaze_msurf"):
+        raise R3dmError("r3dm_dev_akaze_msurf exists in the developer build only: use_developer_library() before the first load")
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.r3dm_dev_akaze_msurf_levels.argtypes = [u32, u32, vp, vp]
+    L.r3dm_dev_akaze_msurf_check.argtypes = [u32, u32, u32, vp, vp, u32, vp]
+    L.r3dm_dev_akaze_msurf.argtypes = [vp, u32, u32, u32, vp, vp, u32, vp, vp]
+    L._r3dm_dev_msurf_bound = True
+    return L
+
+
+def dev_akaze_msurf_levels(L, width: int, height: int):
+    """r3dm_dev_akaze_msurf_levels: the level table the M-SURF arm forms for a width x height image (border from 12 sqrt(2)), as
+    dev_akaze_tail_levels gives the MLDB one"""
+    bind_dev_akaze_msurf(L)
+    lv = (DevAkLevel * 16)(); n = C.c_uint32(0)
+    rc = L.r3dm_dev_akaze_msurf_levels(width, height, C.addressof(lv), C.addressof(n))
+    if rc != 0:
+        raise R3dmError(f"r3dm_dev_akaze_msurf_levels -> {rc}")
+    return [{k: getattr(lv[i], k) for k, _ in DevAkLevel._fields_} for i in range(n.value)]
+
+
+def dev_msurf_args(planes, items):
+    """the arrays of the M-SURF entries.  planes: [n_levels] of (Lx, Ly) float32 [h, w]; items: MSURF_ITEM records
+    -> (n_levels, plane_dims, plane pointers, n, items, keep-alive)"""
+    keep = [[np.ascontiguousarray(q, np.float32) for q in lev] for lev in planes]
+    nl = len(keep)
+    dims = np.array([[lev[0].shape[1], lev[0].shape[0]] for lev in keep], np.uint32).reshape(nl, 2)
+    ptrs = (C.c_void_p * max(2 * nl, 1))(*[q.ctypes.data for lev in keep for q in lev])
+    its = np.ascontiguousarray(items, MSURF_ITEM)
+    return nl, dims, ptrs, len(its), its, keep
+
+
+def dev_akaze_msurf_check(L, width: int, height: int, planes, items) -> int:
+    """r3dm_dev_akaze_msurf_check: 0 when the kernel reads these planes and items inside the planes, R3DM_ERR_INVALID else; needs no device"""
+    bind_dev_akaze_msurf(L)
+    nl, dims, ptrs, n, its, keep = dev_msurf_args(planes, items)
+    return L.r3dm_dev_akaze_msurf_check(width, height, nl, _ptr(dims), C.addressof(ptrs), n, its.ctypes.data)
 
 
 def dev_tail_args(images):
@@ -1368,10 +1423,11 @@ class Context:
         self._check(self._L.r3dm_set_keypoint_detector(self._h, DETECTORS[detector]), "r3dm_set_keypoint_detector")
 
     def set_descriptor_arm(self, descriptor: str = "LIOP"):
-        """r3dm_set_descriptor_arm: what the features entries describe the keypoints with, "LIOP" (default: .desc rows of 144 floats) or
-        "MLDB" (the Fast-AKAZE detector's MLDB-486: .desc rows of 61 bytes)"""
+        """r3dm_set_descriptor_arm: what the features entries describe the keypoints with, "LIOP" (default: .desc rows of 144 floats),
+        "MLDB" (the Fast-AKAZE detector's MLDB-486: .desc rows of 61 bytes) or "MSURF" (its M-SURF-64: .desc rows of 64 floats; the
+        detector then runs on the level table with the M-SURF border)"""
         _descriptor_flag(descriptor)
-        self._check(self._L.r3dm_set_descriptor_arm(self._h, DESCRIPTORS[descriptor]), "r3dm_set_descriptor_arm")
+        self._check(self._L.r3dm_set_descriptor_arm(self._h, DESCRIPTOR_ARMS[descriptor]), "r3dm_set_descriptor_arm")
 
     def akaze_classic_components(self) -> np.ndarray:
         """r3dm_akaze_classic_components: [32] component-size histogram of the classic arm's kpts_aux walk since creation
@@ -1428,6 +1484,17 @@ class Context:
             res.append(out)
             at += int(per[b].sum())
         return res
+
+    def dev_akaze_msurf(self, width: int, height: int, planes, items) -> np.ndarray:
+        """r3dm_dev_akaze_msurf (developer build): the product's M-SURF-64 kernel on the caller's Lx / Ly planes (see dev_msurf_args)
+        and items, through r3dm_dev_akaze_msurf_check first -> rows [n, 64] float32"""
+        L = bind_dev_akaze_msurf(self._L)
+        nl, dims, ptrs, n, its, keep = dev_msurf_args(planes, items)
+        rows = np.zeros((n, 64), np.float32)
+        self._check(L.r3dm_dev_akaze_msurf(self._h, width, height, nl, _ptr(dims), C.addressof(ptrs), n, its.ctypes.data, rows.ctypes.data),
+                    "r3dm_dev_akaze_msurf")
+        del keep
+        return rows
 
     def dev_akaze_head(self, images, threshold: float):
         """r3dm_dev_akaze_head (developer build): the Fast arm's head -- scale space, extremum pass, in-level pruning, the product's
@@ -1607,6 +1674,25 @@ class Context:
         kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); dp_p = (C.c_void_p * B)(*[d.ctypes.data for d in desc])
         n = np.zeros(B, np.uint32)
         self._check(self._L.r3dm_detect_akaze_mldb_batch(self._h, B, ip, w, h, threshold, kp_p, dp_p, cap, _ptr(n)), "r3dm_detect_akaze_mldb_batch")
+        return [(kps[b][:min(int(n[b]), cap)].copy(), desc[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
+
+    def detect_akaze_msurf_batch(self, images, threshold: float = 0.001, cap: int = 200000, single: bool = False):
+        """r3dm_detect_akaze_msurf_batch: B same-size images in one pass of the detector (on the level table with the M-SURF border) and
+        ONE M-SURF-64 launch -> list of (keypoints [n, 4], descriptors [n, 64] float32).  single: the one image of the list through
+        r3dm_detect_akaze_msurf instead"""
+        imgs = [im if hasattr(im, "data_ptr") else np.ascontiguousarray(im, np.float32) for im in images]
+        B = len(imgs); h, w = int(imgs[0].shape[0]), int(imgs[0].shape[1])
+        assert all(tuple(im.shape) == (h, w) for im in imgs), "a batch holds images of one size"
+        ip = (C.c_void_p * B)(*[(im.data_ptr() if hasattr(im, "data_ptr") else im.ctypes.data) for im in imgs])
+        kps = [np.zeros((cap, 4), np.float32) for _ in range(B)]; desc = [np.zeros((cap, 64), np.float32) for _ in range(B)]
+        kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); dp_p = (C.c_void_p * B)(*[d.ctypes.data for d in desc])
+        n = np.zeros(B, np.uint32)
+        if single:
+            assert B == 1
+            self._check(self._L.r3dm_detect_akaze_msurf(self._h, ip[0], w, h, threshold, kp_p[0], dp_p[0], cap, n.ctypes.data_as(C.POINTER(C.c_uint32))),
+                        "r3dm_detect_akaze_msurf")
+        else:
+            self._check(self._L.r3dm_detect_akaze_msurf_batch(self._h, B, ip, w, h, threshold, kp_p, dp_p, cap, _ptr(n)), "r3dm_detect_akaze_msurf_batch")
         return [(kps[b][:min(int(n[b]), cap)].copy(), desc[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
 
     def detect_akaze_classic(self, image, threshold: float = 0.001, cap: int = 200000):
@@ -1804,9 +1890,9 @@ class MultiContext:
         self._check(self._L.r3dm_multi_set_keypoint_detector(self._h, DETECTORS[detector]), "r3dm_multi_set_keypoint_detector")
 
     def set_descriptor_arm(self, descriptor: str = "LIOP"):
-        """r3dm_multi_set_descriptor_arm: what extract_features describes the keypoints with on every context ("LIOP" or "MLDB")"""
+        """r3dm_multi_set_descriptor_arm: what extract_features describes the keypoints with on every context ("LIOP", "MLDB" or "MSURF")"""
         _descriptor_flag(descriptor)
-        self._check(self._L.r3dm_multi_set_descriptor_arm(self._h, DESCRIPTORS[descriptor]), "r3dm_multi_set_descriptor_arm")
+        self._check(self._L.r3dm_multi_set_descriptor_arm(self._h, DESCRIPTOR_ARMS[descriptor]), "r3dm_multi_set_descriptor_arm")
 
     def extract_features(self, images, feat_paths, desc_paths, threshold: float = 0.001, bgr: bool = False, batch: int = 0):
         """r3dm_multi_extract_features(_bgr8): the features stage over an image list, one BATCH of same-size images in flight per context.

@@ -141,7 +141,9 @@ void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints,
 int detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
                  float threshold, DetectedBatch& out)
 {
-    return (c && c->detector_arm == R3DM_DETECTOR_AKAZE ? ac_detect_batch : ak_detect_batch)(c, B, images, bgrs, width, height, threshold, out);
+    if (c && c->detector_arm == R3DM_DETECTOR_AKAZE) return ac_detect_batch(c, B, images, bgrs, width, height, threshold, out);
+    // (the Fast arm's level table carries the border of the descriptor that will read its planes)
+    return (c && c->descriptor_arm == R3DM_DESCRIPTOR_MSURF ? ak_detect_batch_msurf : ak_detect_batch)(c, B, images, bgrs, width, height, threshold, out);
 }
 
 int detect_entry(r3dm_ctx* c, DetectArm* arm, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
@@ -166,13 +168,15 @@ int detect_entry(r3dm_ctx* c, DetectArm* arm, bool single, uint32_t B, const flo
 namespace {
 
 // AKAZEFeaturesV2::Allocate_Memory_Evolution (src/thirdparty/fast-akaze/AKAZEFeatures.cpp:73-131) with the AKAZE2::create()
-// defaults (AKAZEConfig.h:18-43): 4 octaves x 4 sublevels, soffset 1.6, derivative_factor 1.5, MLDB border 10 sqrt(2) sigma
-std::vector<AkLevelHost> ak_levels(int w, int h)
+// defaults (AKAZEConfig.h:18-43): 4 octaves x 4 sublevels, soffset 1.6, derivative_factor 1.5.  The border is the DESCRIPTOR's
+// (:78-84): smax = 10 sqrt(2) for MLDB (ak_smax(false): what the detector, LIOP and MLDB arms run on), 12 sqrt(2) for the KAZE
+// descriptors (ak_smax(true): M-SURF-64).  The larger border cuts the table earlier, so the M-SURF table is a prefix of the other
+// with wider borders, and detection under it differs near the frame and on small images.
+std::vector<AkLevelHost> ak_levels(int w, int h, float smax = ak_smax(false))
 {
     std::vector<AkLevelHost> lv;
     const int omax = 4, nsub = 4;
     const float soffset = 1.6f, dfac = 1.5f;
-    const float smax = 10.0f * sqrtf(2.0f);
     int lh = h, lw = w, power = 1;
     for (int i = 0; i < omax; ++i) {
         for (int j = 0; j < nsub; ++j) {
@@ -571,8 +575,8 @@ int ak_read_back(AkPass& p, const AkDetection& d, std::vector<std::vector<AkKpRe
 }  // namespace
 
 // Leaves the B gray images in ak_bufs[0] (B planes) for the LIOP patch extraction and the level images for MLDB.
-int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
-                    float threshold, DetectedBatch& out)
+static int ak_detect_batch_smax(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                                float threshold, float smax, DetectedBatch& out)
 {
     if (!detect_args_ok(c, B, images, bgrs, width, height)) return R3DM_ERR_INVALID;
     out = DetectedBatch();
@@ -580,7 +584,8 @@ int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     if (width < 3 || height < 3) return R3DM_ERR_INVALID;
     R3DM_HIP(c, hipSetDevice(c->device));
     const double t_call = now_ms();
-    out.fast_levels = ak_levels((int)width, (int)height);
+    out.fast_levels = ak_levels((int)width, (int)height, smax);
+    out.fast_smax = smax;
     AkPass p{c, c->stream, B, (int)B, (int)width, (int)height, (int)out.fast_levels.size(), (size_t)width * height, out.fast_levels};
     c->stats.n_detect_images = B; c->stats.ms_detect_kernels = 0.0; c->stats.detect_algorithmic_bytes = 0.0; c->stats.detect_compulsory_bytes = 0.0;
     if (p.nl == 0) { c->stats.ms_detect = now_ms() - t_call; return R3DM_OK; }     // image too small for a single evolution level
@@ -602,6 +607,19 @@ int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     for (uint32_t b = 0; b < B; ++b) n_kp += d.bm[b].n_kp;
     detect_finish(c, B, t_call, n_kp, p.planes_px * 4.0 * B);
     return R3DM_OK;
+}
+
+int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                    float threshold, DetectedBatch& out)
+{
+    return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, ak_smax(false), out);
+}
+
+// the same pass on the level table of the KAZE descriptors (ak_levels): what M-SURF-64 must be computed on
+int ak_detect_batch_msurf(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                          float threshold, DetectedBatch& out)
+{
+    return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, ak_smax(true), out);
 }
 
 // one keypoint of image b as the MLDB kernel takes it: the raw (radian) angle of the host libm, its cos / sin, level coordinates, sigma_size
@@ -672,6 +690,86 @@ int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_t
     return R3DM_OK;
 }
 
+// one keypoint of image b as the M-SURF kernel takes it: as ak_mldb_item, with the reference's int scale (fRound(0.5 size / ratio), which
+// is the level's sigma_size: size = 2 esigma derivative_factor and sigma_size = fRound(esigma derivative_factor / ratio))
+static AkMsurfItem ak_msurf_item(uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r)
+{
+    const float theta = ak_theta(r);
+    return {b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), lv[r.level].sigma_size};
+}
+
+// the launch of the M-SURF kernel over `items` (host memory) on the level table the context's last pass left on the device, which the
+// caller vouches was cut with ak_smax(true): items up, one launch between ev0 / ev1, waited for; *rows_dev: 64 floats a row
+static int ak_msurf_launch(r3dm_ctx* c, const std::vector<AkMsurfItem>& items, const unsigned char** rows_dev)
+{
+    const size_t ni = items.size();
+    hipStream_t st = c->stream;
+    DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_MLDB];
+    const size_t off_rows = (ni * sizeof(AkMsurfItem) + 255) / 256 * 256;
+    R3DM_HIP(c, mb.ensure(off_rows + ni * 256 + 64));
+    unsigned char* base = mb.as<unsigned char>();
+    R3DM_HIP(c, hipMemcpyAsync(base, items.data(), ni * sizeof(AkMsurfItem), hipMemcpyHostToDevice, st));
+    R3DM_HIP(c, hipEventRecord(c->ev0, st));
+    R3DM_HIP(c, ak_msurf(st, c->ak_levels_dev, (const AkMsurfItem*)base, (uint32_t)ni, reinterpret_cast<float*>(base + off_rows)));
+    R3DM_HIP(c, hipEventRecord(c->ev1, st));
+    R3DM_HIP(c, hipStreamSynchronize(st));                                // the caller's `items` may leave scope
+    *rows_dev = base + off_rows;
+    return R3DM_OK;
+}
+
+// Get_MSURF_Descriptor_64 of the first min(count, cap) keypoints of every image of the pass, in ONE launch, as ak_mldb_pass does it for
+// MLDB: same item loop, same buffer, same lifetime of rows_dev; image b's rows are at rows_dev + 256 first[b], the layout
+// r3dm_set_image(dim 64, R3DM_F32) reads from a device pointer.  The kernel reads Lx / Ly up to 12 sqrt(2) sigma_size + 1 from a
+// keypoint: only the level table of ak_detect_batch_msurf keeps that inside the planes, a pass on any other is refused here.
+int ak_msurf_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev)
+{
+    const uint32_t B = (uint32_t)det.fast.size();
+    const std::vector<AkLevelHost>& lv = det.fast_levels;
+    const uint32_t nl = (uint32_t)lv.size();
+    first.assign((size_t)B + 1, 0);
+    for (uint32_t b = 0; b < B; ++b) first[b + 1] = first[b] + std::min<size_t>(det.fast[b].size(), cap);
+    *rows_dev = nullptr;
+    const size_t ni = first[B];
+    if (ni == 0) return R3DM_OK;
+    if (det.fast_smax != ak_smax(true)) { c->err = "M-SURF: the detector pass ran on the MLDB level table, whose borders do not hold the descriptor's reads"; return R3DM_ERR_INVALID; }
+    if (ni >= (1ull << 31)) { c->err = "M-SURF: more than 2^31 keypoints in one pass"; return R3DM_ERR_UNSUPPORTED; }
+    // (the in-plane argument at r3dm_dev_akaze_msurf_check counts on float positions below 2^16 and on sigma_size 2 .. 4)
+    if (lv[0].w > 65536 || lv[0].h > 65536) { c->err = "M-SURF: images of more than 65536 columns or rows are not served"; return R3DM_ERR_UNSUPPORTED; }
+    for (const AkLevelHost& e : lv) if (e.sigma_size < 2 || e.sigma_size > 4) { c->err = "M-SURF: unexpected level table"; return R3DM_ERR_UNSUPPORTED; }
+    std::vector<AkMsurfItem> items(ni);
+    struct Chunk { uint32_t b; size_t k0, k1; };
+    std::vector<Chunk> chunks;
+    for (uint32_t b = 0; b < B; ++b)
+        for (size_t k0 = 0, nk = first[b + 1] - first[b]; k0 < nk; k0 += 4096) chunks.push_back({b, k0, std::min(nk, k0 + 4096)});
+    r3dm_parallel_for((long)chunks.size(), host_team, [&](long ci) {
+        const Chunk& ch = chunks[(size_t)ci];
+        const std::vector<AkKpRec>& recs = det.fast[ch.b];
+        for (size_t k = ch.k0; k < ch.k1; ++k) items[first[ch.b] + k] = ak_msurf_item(ch.b, nl, lv, recs[k]);
+    });
+    return ak_msurf_launch(c, items, rows_dev);
+}
+
+// the detect entry of the M-SURF forms: ak_mldb_entry on the M-SURF level table, rows of 64 floats
+static int ak_msurf_entry(r3dm_ctx* c, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
+                          float* const* keypoints_out, float* const* descriptors_out, uint32_t cap, uint32_t* n_out)
+{
+    if (cap && !descriptors_out) return R3DM_ERR_INVALID;
+    if (cap && images && B <= 4096) for (uint32_t b = 0; b < B; ++b) if (!descriptors_out[b] || (keypoints_out && !keypoints_out[b])) return R3DM_ERR_INVALID;
+    DetectedBatch det;
+    int rc = detect_entry(c, ak_detect_batch_msurf, single, B, images, width, height, threshold, keypoints_out, nullptr, cap, n_out, det);
+    if (rc != R3DM_OK) return rc;
+    std::vector<size_t> first;
+    const unsigned char* rows = nullptr;
+    rc = ak_msurf_pass(c, det, cap, r3dm_host_team(8), first, &rows);
+    for (uint32_t b = 0; rc == R3DM_OK && b < B; ++b) {
+        const size_t nb = first[b + 1] - first[b];
+        if (nb && hipMemcpyAsync(descriptors_out[b], rows + 256 * first[b], nb * 256, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { c->err = "M-SURF: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
+    }
+    if (rc == R3DM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "M-SURF: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
+    if (rc != R3DM_OK) for (uint32_t b = 0; b < B; ++b) n_out[b] = 0;
+    return rc;
+}
+
 // the detect entry of the MLDB forms: the keypoints through detect_entry, then min(count, cap) rows per image from the one MLDB pass
 static int ak_mldb_entry(r3dm_ctx* c, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
                          float* const* keypoints_out, unsigned char* const* descriptors_out, uint32_t cap, uint32_t* n_out)
@@ -718,6 +816,25 @@ extern "C" int r3dm_detect_akaze_mldb_batch(r3dm_ctx* c, uint32_t n_images, cons
 {
     return r3dm_guarded(c, [&]() -> int {
         return ak_mldb_entry(c, false, n_images, images, width, height, threshold, keypoints_out, descriptors_out, cap, n_out);
+    });
+}
+
+// Fast-A-KAZE keypoints with their M-SURF-64 rows: the detector runs on the level table of the KAZE descriptors (ak_levels), so near
+// the frame and on small images the keypoints are not those of r3dm_detect_akaze.  descriptors_out: cap x 64 floats.
+extern "C" int r3dm_detect_akaze_msurf(r3dm_ctx* c, const float* image, uint32_t width, uint32_t height, float threshold,
+                                       float* keypoints_out, float* descriptors_out, uint32_t cap, uint32_t* n_out)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        return ak_msurf_entry(c, true, 1, &image, width, height, threshold, &keypoints_out, &descriptors_out, cap, n_out);
+    });
+}
+
+extern "C" int r3dm_detect_akaze_msurf_batch(r3dm_ctx* c, uint32_t n_images, const float* const* images, uint32_t width, uint32_t height,
+                                             float threshold, float* const* keypoints_out, float* const* descriptors_out, uint32_t cap,
+                                             uint32_t* n_out)
+{
+    return r3dm_guarded(c, [&]() -> int {
+        return ak_msurf_entry(c, false, n_images, images, width, height, threshold, keypoints_out, descriptors_out, cap, n_out);
     });
 }
 
@@ -902,6 +1019,96 @@ extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height,
             if (n) R3DM_HIP(c, hipMemcpyAsync(desc_out + 61 * o, rows + 61 * first[b], n * 61, hipMemcpyDeviceToHost, st));
         }
         R3DM_HIP(c, hipStreamSynchronize(st));
+        return R3DM_OK;
+    });
+}
+
+// ---- developer build only: the M-SURF-64 kernel on a caller's Lx / Ly planes of ONE image size and a caller's items, so that the suite
+// can put keypoints on the border at the reach extremes, samples on .5 boundaries, windows without gradient.
+// What runs is the product's: ak_levels with the M-SURF border, ak_buffers, ak_level_table, ak_msurf_launch.
+// The level table of the KAZE descriptors for a width x height image, as r3dm_dev_akaze_tail_levels gives the other one.
+extern "C" int r3dm_dev_akaze_msurf_levels(uint32_t width, uint32_t height, r3dm_dev_ak_level* out, uint32_t* n_levels)
+{
+    if (!out || !n_levels || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, ak_smax(true));
+    if (lv.size() > 16) return R3DM_ERR_UNSUPPORTED;
+    for (size_t i = 0; i < lv.size(); ++i) out[i] = {lv[i].w, lv[i].h, lv[i].border, lv[i].sigma_size, lv[i].ratio, lv[i].esigma, lv[i].esigma * 1.5f};
+    *n_levels = (uint32_t)lv.size();
+    return R3DM_OK;
+}
+
+// What the kernel would mis-read is refused here, before anything touches a device: R3DM_OK or R3DM_ERR_INVALID.
+//   n_levels and plane_dims [n_levels][2] are the M-SURF table's of (width, height); planes [n_levels][2]: Lx, Ly, every value finite;
+//   n <= 2^20 items: level < n_levels, scale == the level's sigma_size, xf in [border - 1, w - border] and yf in [border - 1, h - border]
+//   of that level (the range the detector's refinement leaves, r3dm_dev_akaze_tail_check), |co^2 + si^2 - 1| <= 1e-6.
+// Why every read of an accepted item stays inside its plane (s = sigma_size, which the table holds as 2, 3 or 4; R = 12 sqrt(2) s;
+// border = fRound(R) + 1 with fRound(R) - R = 0.059, 0.088, 0.118 for these s):
+//   a sample lies at position + (l s co + k s si) resp. + (-l s si + k s co) with k, l in [-12, 11], so |sample - position| <=
+//   12 s (|co| + |si|) <= R (1 + 1e-6), and the float sum position + offset adds half an ulp of the position: <= 0.004 for planes of at
+//   most 65536 columns and rows, which the check and ak_msurf_pass hold to (together: e < 5e-3);
+//   the rows read are y1 = (int)(sample - 0.5 + 0.5) and y2 = (int)(sample + 0.5 + 0.5), columns alike.  position >= border - 1 =
+//   fRound(R) gives sample >= fRound(R) - R - e > 0.05, so y1 >= 0 (and y1 <= y2); position <= dim - border = dim - 1 - fRound(R)
+//   gives sample + 1 <= dim - (fRound(R) - R) + e < dim - 0.05, so y2 <= dim - 1.
+//   On the MLDB table (border from 10 sqrt(2) s) the same keypoints reach 2 sqrt(2) s beyond the plane: ak_msurf_pass refuses it.
+extern "C" int r3dm_dev_akaze_msurf_check(uint32_t width, uint32_t height, uint32_t n_levels, const uint32_t* plane_dims, const float* const* planes,
+                                          uint32_t n, const AkMsurfItem* items)
+{
+    if (!plane_dims || !planes || (n && !items) || n > kAkDevMaxList || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, ak_smax(true));
+    const uint32_t nl = (uint32_t)lv.size();
+    if (nl < 1 || nl > 16 || n_levels != nl) return R3DM_ERR_INVALID;
+    for (uint32_t i = 0; i < nl; ++i) {
+        if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
+        if (lv[i].sigma_size < 2 || lv[i].sigma_size > 4) return R3DM_ERR_INVALID;                  // (the in-plane argument above)
+        const size_t plane = (size_t)lv[i].w * lv[i].h;
+        for (int q = 0; q < 2; ++q) {
+            const float* P = planes[2 * i + q];
+            if (!P) return R3DM_ERR_INVALID;
+            for (size_t k = 0; k < plane; ++k) if (!std::isfinite(P[k])) return R3DM_ERR_INVALID;
+        }
+    }
+    for (uint32_t k = 0; k < n; ++k) {
+        const AkMsurfItem& it = items[k];
+        if (it.level >= nl) return R3DM_ERR_INVALID;
+        const AkLevelHost& e = lv[it.level];
+        if (it.scale != e.sigma_size) return R3DM_ERR_INVALID;
+        if (!std::isfinite(it.xf) || !std::isfinite(it.yf) || !std::isfinite(it.co) || !std::isfinite(it.si)) return R3DM_ERR_INVALID;
+        if (it.xf < (float)(e.border - 1) || it.xf > (float)(e.w - e.border) || it.yf < (float)(e.border - 1) || it.yf > (float)(e.h - e.border)) return R3DM_ERR_INVALID;
+        if (fabs((double)it.co * it.co + (double)it.si * it.si - 1.0) > 1e-6) return R3DM_ERR_INVALID;
+    }
+    return R3DM_OK;
+}
+
+// Runs the items through the product's kernel: rows_out = n x 64 floats.
+extern "C" int r3dm_dev_akaze_msurf(r3dm_ctx* c, uint32_t width, uint32_t height, uint32_t n_levels, const uint32_t* plane_dims, const float* const* planes,
+                                    uint32_t n, const AkMsurfItem* items, float* rows_out)
+{
+    const int vrc = r3dm_dev_akaze_msurf_check(width, height, n_levels, plane_dims, planes, n, items);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_msurf: planes or items the kernel would mis-read"; return vrc; }
+    if (!c || (n && !rows_out)) return R3DM_ERR_INVALID;
+    if (n == 0) return R3DM_OK;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, ak_smax(true));
+        const int nl = (int)lv.size();
+        AkPass p{c, c->stream, 1, 1, (int)width, (int)height, nl, (size_t)width * height, lv};
+        int rc = ak_buffers(p);
+        if (rc != R3DM_OK) return rc;
+        for (int i = 0; i < nl; ++i) {
+            const size_t plane = (size_t)lv[i].w * lv[i].h;
+            R3DM_HIP(c, hipMemcpyAsync(p.Lx(i), planes[2 * i], plane * 4, hipMemcpyHostToDevice, p.st));
+            R3DM_HIP(c, hipMemcpyAsync(p.Ly(i), planes[2 * i + 1], plane * 4, hipMemcpyHostToDevice, p.st));
+        }
+        AkDetection d;
+        if ((rc = ak_level_table(p, d)) != R3DM_OK) return rc;
+        R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, p.st));
+        R3DM_HIP(c, hipStreamSynchronize(p.st));
+        c->ak_n_levels = nl;
+        c->ak_levels_dev = d.d_levels;
+        const std::vector<AkMsurfItem> its(items, items + n);
+        const unsigned char* rows = nullptr;
+        if ((rc = ak_msurf_launch(c, its, &rows)) != R3DM_OK) return rc;
+        R3DM_HIP(c, hipMemcpy(rows_out, rows, (size_t)n * 256, hipMemcpyDeviceToHost));
         return R3DM_OK;
     });
 }

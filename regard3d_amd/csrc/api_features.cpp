@@ -1,7 +1,7 @@
 // api_features.cpp -- part of the host side of libr3dm.so (see r3dm_ctx.hpp for the file map): the features work item of
 // src/threads/R3DFeaturesThread.cpp and src/Regard3DFeatures.cpp.  The .feat / .desc files; the features batch in its phases -- detect
 // (api_akaze.cpp, whichever arm) -> keypoints and patch maps (host team) -> one descriptor pass chosen by the context's descriptor arm:
-// LIOP (api_liop.cpp) or MLDB-486 (api_akaze.cpp) -> delivery (files + sink, at once or deferred to the context's writer thread) ->
+// LIOP (api_liop.cpp), MLDB-486 or M-SURF-64 (api_akaze.cpp) -> delivery (files + sink, at once or deferred to the context's writer thread) ->
 // outputs and totals; the work list over a multi-context; the setters of all this.
 // There is no CPU fallback in this file: when HIP fails, the call fails.
 #include "fmt_g6.hpp"
@@ -37,8 +37,8 @@ static size_t format_feat(std::vector<char>& txt, const float* kps, uint32_t n, 
     return (size_t)(p - txt.data());
 }
 
-// one image on its way to its files: the text of its .feat, its rows (in pin_desc, row_bytes each: 144 floats of LIOP or 61 bytes of
-// MLDB), its two paths, the positions for the sink
+// one image on its way to its files: the text of its .feat, its rows (in pin_desc, row_bytes each: 144 floats of LIOP, 61 bytes of
+// MLDB or 64 floats of M-SURF), its two paths, the positions for the sink
 struct FeatJob { std::string feat, desc; std::vector<char> txt; size_t len = 0; const unsigned char* rows = nullptr; size_t row_bytes = 0; uint32_t n = 0; std::vector<float> xy; };
 
 static int write_feat_desc_files(std::string& err, const FeatJob& j)
@@ -97,8 +97,11 @@ struct BatchRows { const unsigned char* dev = nullptr; size_t row_bytes = 0; };
 // what the context's two switches cannot do together (r3dm_set_descriptor_arm): refused before anything is computed
 int descriptor_arm_check(r3dm_ctx* c)
 {
-    if (c->descriptor_arm != R3DM_DESCRIPTOR_MLDB || c->detector_arm != R3DM_DETECTOR_AKAZE) return R3DM_OK;
-    c->err = "descriptor arm R3DM_DESCRIPTOR_MLDB is not served with the classic detector R3DM_DETECTOR_AKAZE (MLDB reads the Fast-A-KAZE level planes)";
+    if (c->descriptor_arm == R3DM_DESCRIPTOR_LIOP || c->detector_arm != R3DM_DETECTOR_AKAZE) return R3DM_OK;
+    if (c->descriptor_arm == R3DM_DESCRIPTOR_MLDB)
+        c->err = "descriptor arm R3DM_DESCRIPTOR_MLDB is not served with the classic detector R3DM_DETECTOR_AKAZE (MLDB reads the Fast-A-KAZE level planes)";
+    else
+        c->err = "descriptor arm R3DM_DESCRIPTOR_MSURF is not served with the classic detector R3DM_DETECTOR_AKAZE (M-SURF-64 reads the Fast-A-KAZE level planes)";
     return R3DM_ERR_UNSUPPORTED;
 }
 
@@ -128,19 +131,19 @@ void keypoints_and_maps(const DetectedBatch& det, uint32_t B, int host_team, boo
     });
 }
 
-// phase 3: one descriptor pass over the keypoints of ALL images -- LIOP on the gray planes, or MLDB on the level planes, that the detector
-// left on the device; the rows stay there for the sink (`rows`) and go to page-locked host memory for the files.  Immediately: waited
+// phase 3: one descriptor pass over the keypoints of ALL images -- LIOP on the gray planes, or MLDB / M-SURF-64 on the level planes, that
+// the detector left on the device; the rows stay there for the sink (`rows`) and go to page-locked host memory for the files.  Immediately: waited
 // for.  Deferred: they travel behind the kernel, only the writer thread waits (ev_desc)
 int describe_batch(r3dm_ctx* c, const DetectedBatch& det, uint32_t width, uint32_t height, const BatchKeypoints& K, bool deferred, int host_team, BatchRows& rows)
 {
-    const bool mldb = c->descriptor_arm == R3DM_DESCRIPTOR_MLDB;
-    rows.row_bytes = mldb ? 61 : 144 * 4;
+    const bool mldb = c->descriptor_arm == R3DM_DESCRIPTOR_MLDB, msurf = c->descriptor_arm == R3DM_DESCRIPTOR_MSURF;
+    rows.row_bytes = mldb ? 61 : msurf ? 64 * 4 : 144 * 4;
     const size_t out_bytes = K.total() * rows.row_bytes;
     { const int wrc_prev = features_files_join(c); if (wrc_prev != R3DM_OK) return wrc_prev; }      // the previous batch's writer still reads pin_desc
     R3DM_HIP(c, c->pin_desc.ensure(out_bytes));
-    if (mldb) {
+    if (mldb || msurf) {
         std::vector<size_t> first;
-        const int rc = ak_mldb_pass(c, det, 0xFFFFFFFFu, host_team, first, &rows.dev);
+        const int rc = (msurf ? ak_msurf_pass : ak_mldb_pass)(c, det, 0xFFFFFFFFu, host_team, first, &rows.dev);
         if (rc != R3DM_OK) return rc;
     } else {
         const int rc = liop_pass(c, det.grays_dev, width, height, K.M6.data(), K.img_of.data(), (uint32_t)K.total(), false);
@@ -494,7 +497,7 @@ extern "C" int r3dm_set_keypoint_detector(r3dm_ctx* c, int arm)
 extern "C" int r3dm_set_descriptor_arm(r3dm_ctx* c, int arm)
 {
     if (!c) return R3DM_ERR_INVALID;
-    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB) { c->err = "r3dm_set_descriptor_arm: unknown arm " + std::to_string(arm); return R3DM_ERR_INVALID; }
+    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB && arm != R3DM_DESCRIPTOR_MSURF) { c->err = "r3dm_set_descriptor_arm: unknown arm " + std::to_string(arm); return R3DM_ERR_INVALID; }
     c->descriptor_arm = arm;
     return R3DM_OK;
 }
@@ -522,7 +525,7 @@ extern "C" int r3dm_multi_set_keypoint_detector(r3dm_multi* m, int arm)
 
 extern "C" int r3dm_multi_set_descriptor_arm(r3dm_multi* m, int arm)
 {
-    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB) return R3DM_ERR_INVALID;
+    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB && arm != R3DM_DESCRIPTOR_MSURF) return R3DM_ERR_INVALID;
     return multi_each(m, [&](r3dm_ctx* c) { return r3dm_set_descriptor_arm(c, arm); });
 }
 

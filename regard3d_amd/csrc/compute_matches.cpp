@@ -200,8 +200,9 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
         return false;
     }
     // the regions type names the descriptor arm: LIOP (float x 144) or the MLDB-486 rows of the Fast-A-KAZE detector (61 bytes)
-    const bool mldb = dtype_ == R3DM_BIN && dim_ == 61;
-    if (!mldb && (dtype_ != R3DM_F32 || dim_ != 144)) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
+    // or its M-SURF-64 rows (float x 64)
+    const bool mldb = dtype_ == R3DM_BIN && dim_ == 61, msurf = dtype_ == R3DM_F32 && dim_ == 64;
+    if (!mldb && !msurf && (dtype_ != R3DM_F32 || dim_ != 144)) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
     if (!feat_multi_) {
         std::vector<int> ids;
         for (int d : devices_) for (int k = 0; k < std::max(1, feat_conc_); ++k) ids.push_back(d);
@@ -210,7 +211,7 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     }
     const int n_ctx = r3dm_multi_num_devices(feat_multi_);
     (void)r3dm_multi_set_keypoint_detector(feat_multi_, dl[0] == "AKAZE" ? R3DM_DETECTOR_AKAZE : R3DM_DETECTOR_FAST_AKAZE);
-    (void)r3dm_multi_set_descriptor_arm(feat_multi_, mldb ? R3DM_DESCRIPTOR_MLDB : R3DM_DESCRIPTOR_LIOP);      // (MLDB with "AKAZE": refused by name by the features call below)
+    (void)r3dm_multi_set_descriptor_arm(feat_multi_, mldb ? R3DM_DESCRIPTOR_MLDB : msurf ? R3DM_DESCRIPTOR_MSURF : R3DM_DESCRIPTOR_LIOP);      // (MLDB / M-SURF with "AKAZE": refused by name by the features call below)
     // the sink carries no scales: while preemptive matching is on, every view is registered from its files (setPreemptiveMatching)
     const bool direct = direct_registration_ && !preemptive_on_;
     (void)r3dm_multi_set_features_sink(feat_multi_, direct ? &R3DComputeMatches::features_sink : nullptr, this);
@@ -357,7 +358,7 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
 {
     statistics_ = R3DComputeMatchesStatistics();
     phases_ = PhaseTimes();
-    phases_.descriptor_arm = dtype_ == R3DM_BIN && dim_ == 61 ? R3DM_DESCRIPTOR_MLDB : R3DM_DESCRIPTOR_LIOP;
+    phases_.descriptor_arm = dtype_ == R3DM_BIN && dim_ == 61 ? R3DM_DESCRIPTOR_MLDB : dtype_ == R3DM_F32 && dim_ == 64 ? R3DM_DESCRIPTOR_MSURF : R3DM_DESCRIPTOR_LIOP;
     if (!ctx_ && !multi_) return false;
     const double t_begin = wall_ms();
     // the feature files of this call are complete when it returns, however it returns (r3dm_set_deferred_feature_files)
@@ -688,6 +689,14 @@ extern "C" void r3dm_stage_destroy(r3dm_stage* s)
     delete s;
 }
 
+// flags no call can honour together: the two descriptor arms.  Refused by name, before a stage is created or run
+static bool stage_flags_ok(uint32_t flags, char* err, size_t err_cap)
+{
+    if (!(flags & R3DM_STAGE_DESCRIPTOR_MLDB) || !(flags & R3DM_STAGE_DESCRIPTOR_MSURF)) return true;
+    if (err && err_cap) snprintf(err, err_cap, "R3DM_STAGE_DESCRIPTOR_MLDB and R3DM_STAGE_DESCRIPTOR_MSURF name two descriptor arms: one call runs one");
+    return false;
+}
+
 extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3dm_view_image* views, uint32_t n_views,
                               float threshold, float dist_ratio, int matching_algorithm, int compute_F, int compute_E, int compute_H,
                               uint64_t seed, int features_batches_in_flight, int features_images_per_batch, uint32_t flags,
@@ -695,6 +704,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
 {
     if (!sp || !sp->stage || !matches_dir || (n_views && !views)) return R3DM_ERR_INVALID;
     if (err && err_cap) err[0] = 0;
+    if (!stage_flags_ok(flags, err, err_cap)) return R3DM_ERR_INVALID;
     try {
         r3d_amd::R3DComputeMatches& stage = *sp->stage;
         stage.clearViews();
@@ -714,7 +724,9 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         stage.setMutualMatching((flags & R3DM_STAGE_MUTUAL_MATCHING) != 0);
         stage.setPreemptiveMatching((flags & R3DM_STAGE_PREEMPTIVE_MATCHING) != 0);
-        if (flags & R3DM_STAGE_DESCRIPTOR_MLDB) stage.setRegionsType(R3DM_BIN, 61); else stage.setRegionsType(R3DM_F32, 144);
+        if (flags & R3DM_STAGE_DESCRIPTOR_MLDB) stage.setRegionsType(R3DM_BIN, 61);
+        else if (flags & R3DM_STAGE_DESCRIPTOR_MSURF) stage.setRegionsType(R3DM_F32, 64);
+        else stage.setRegionsType(R3DM_F32, 144);
         r3d_amd::R3DFParams params;
         params.keypointDetectorList_ = {(flags & R3DM_STAGE_DETECTOR_AKAZE) ? "AKAZE" : "Fast-AKAZE"};
         params.threshold_ = threshold;
@@ -755,6 +767,7 @@ extern "C" int r3dm_compute_matches_stage(const int* device_ids, int n_devices, 
                                           r3dm_stage_report* report, char* err, size_t err_cap)
 {
     if (err && err_cap) err[0] = 0;
+    if (!stage_flags_ok(flags, err, err_cap)) return R3DM_ERR_INVALID;
     r3dm_stage* s = nullptr;
     int rc = r3dm_stage_create(device_ids, n_devices, &s);
     if (rc != R3DM_OK) { if (err && err_cap) snprintf(err, err_cap, "r3dm_create failed (%d): no gfx950 GPU", rc); return rc; }

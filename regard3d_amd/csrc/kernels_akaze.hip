@@ -12,6 +12,7 @@
 // pruned by one wavefront per level that keeps the reference's sequential "first neighbour in the list" rule, with the
 // live part of the list (rows within one radius of the scan line) held in LDS.
 #include "r3dm_internal.hpp"
+#include "ak_expf.hpp"
 
 namespace r3dm {
 
@@ -1556,6 +1557,80 @@ void ak_mldb_kernel(const AkLevelDev* __restrict__ levels, const AkMldbItem* __r
     }
 }
 
+// ---- M-SURF-64 descriptor (MSURF_Descriptor_64_InvokerV2::Get_MSURF_Descriptor_64, AKAZEFeatures.cpp:1431-1544): one keypoint per
+// wavefront, four per workgroup.  A keypoint has 4 x 4 overlapping subregions of 9 x 9 samples (rows i0 .. i0 + 8 for i0 = -12, -7, -2,
+// 3, columns alike): 1,296 samples, each two bilinear reads (Lx, Ly), a Gaussian weight and a rotation.  Two phases:
+//   1. the samples, in parallel: lane t, t + 64, ... takes sample t = 81 subregion + 9 (k - i0) + (l - j0) and parks its weighted,
+//      rotated responses rrx, rry in LDS.  Consecutive lanes take consecutive samples of ONE subregion, so a load instruction of the
+//      wavefront reads a patch of about 9 x 7 sample spacings -- a few cache lines, each used by many lanes.  (The first form of this
+//      kernel gave a lane a whole subregion: its 64 lanes then read 64 places up to 24 spacings apart per instruction, and the launch
+//      was bound by the cache lines that fetched -- 66 ns per keypoint against 17 here, profiles/msurf_arm_perf.txt.)
+//   2. the sums, in the reference's order: lane (q, subregion) adds the 81 parked values of its subregion k-outer, l-inner as ONE
+//      serial float chain -- q = 0: dx, 1: dy, 2: mdx (of |rrx|), 3: mdy -- so no sum is ever split.  A workgroup barrier separates
+//      the phases (every wavefront of the group reaches it: one beyond n works on keypoint n - 1 and stores nothing).
+// The float arithmetic is the reference's operation by operation (the build has -ffp-contract=off; int products such as l * scale stay
+// int products), the exponential is ak_expf (ak_expf.hpp).  The squared length is summed over the 16 subregions i-outer, j-inner: the
+// four sums of a subregion meet by shuffle, every lane then adds the 16 terms in that order itself.  A window without gradient has
+// length 0 and its row is 0 / 0 = NaN, as in the reference.
+// Reads: Lx, Ly at rows / columns (int)(sample) and (int)(sample + 1) with |sample - position| <= 12 sqrt(2) scale; in-plane for
+// every position in [border - 1, dim - border] of a level table built with the M-SURF border (api_akaze.cpp: ak_levels, the
+// argument is next to r3dm_dev_akaze_msurf_check) -- and ONLY of that table.
+constexpr uint32_t kAkMsurfPerGroup = 4, kAkMsurfSamples = 16 * 81;
+__global__ __launch_bounds__(256)
+void ak_msurf_kernel(const AkLevelDev* __restrict__ levels, const AkMsurfItem* __restrict__ items, uint32_t n, float* __restrict__ out /* [n][64] */)
+{
+    __shared__ float parked[kAkMsurfPerGroup][2][kAkMsurfSamples];
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t kp = blockIdx.x * kAkMsurfPerGroup + wave;
+    const bool live = kp < n;
+    const AkMsurfItem it = items[live ? kp : n - 1];
+    const float* __restrict__ Lx = levels[it.level].Lx;
+    const float* __restrict__ Ly = levels[it.level].Ly;
+    const size_t w = (size_t)levels[it.level].w;
+    const float co = it.co, si = it.si, xf = it.xf, yf = it.yf;
+    const int scale = it.scale;
+    const float sigma = 2.5f * (float)scale;
+    float* prx = parked[wave][0];
+    float* pry = parked[wave][1];
+    for (uint32_t t = lane; t < kAkMsurfSamples; t += 64u) {
+        const uint32_t sub = t / 81u, r = t - 81u * sub, kk = r / 9u;
+        const int i0 = -12 + 5 * (int)(sub >> 2), j0 = -12 + 5 * (int)(sub & 3u);
+        const int k = i0 + (int)kk, l = j0 + (int)(r - 9u * kk);
+        const int ky = i0 + 5, kx = j0 + 5;
+        const float xs = xf + ((float)(-kx * scale) * si + (float)(ky * scale) * co);
+        const float ys = yf + ((float)(kx * scale) * co + (float)(ky * scale) * si);
+        const float sample_y = yf + ((float)(l * scale) * co + (float)(k * scale) * si);
+        const float sample_x = xf + ((float)(-l * scale) * si + (float)(k * scale) * co);
+        const float ex = xs - sample_x, ey = ys - sample_y;
+        const float gauss_s1 = ak_expf(-(ex * ex + ey * ey) / (2.0f * sigma * sigma));
+        const int y1 = (int)(sample_y - 0.5f + 0.5f), x1 = (int)(sample_x - 0.5f + 0.5f);
+        const int y2 = (int)(sample_y + 0.5f + 0.5f), x2 = (int)(sample_x + 0.5f + 0.5f);
+        const float fx = sample_x - (float)x1, fy = sample_y - (float)y1;
+        const size_t p11 = (size_t)y1 * w + x1, p12 = (size_t)y1 * w + x2, p21 = (size_t)y2 * w + x1, p22 = (size_t)y2 * w + x2;
+        const float w11 = (1.0f - fx) * (1.0f - fy), w12 = fx * (1.0f - fy), w21 = (1.0f - fx) * fy, w22 = fx * fy;
+        const float rx = w11 * Lx[p11] + w12 * Lx[p12] + w21 * Lx[p21] + w22 * Lx[p22];
+        const float ry = w11 * Ly[p11] + w12 * Ly[p12] + w21 * Ly[p21] + w22 * Ly[p22];
+        pry[t] = gauss_s1 * (rx * co + ry * si);
+        prx[t] = gauss_s1 * (-rx * si + ry * co);
+    }
+    r3dm_syncthreads();
+    const uint32_t sub = lane & 15u, q = lane >> 4;
+    const float* src = ((q & 1u) ? pry : prx) + 81u * sub;           // (stride 81 words across lanes: no two of 32 share a bank)
+    float sum = 0.0f;
+    if (q < 2u) for (uint32_t t = 0; t < 81u; ++t) sum += src[t];
+    else for (uint32_t t = 0; t < 81u; ++t) sum += fabsf(src[t]);
+    const float dx = __shfl(sum, (int)sub, 64), dy = __shfl(sum, (int)(16u + sub), 64);
+    const float mdx = __shfl(sum, (int)(32u + sub), 64), mdy = __shfl(sum, (int)(48u + sub), 64);
+    const float cx = (float)(sub >> 2) + 0.5f, cy = (float)(sub & 3u) + 0.5f;
+    const float gauss_s2 = ak_expf(-((cx - 2.0f) * (cx - 2.0f) + (cy - 2.0f) * (cy - 2.0f)) / (2.0f * 1.5f * 1.5f));
+    const float term = (dx * dx + dy * dy + mdx * mdx + mdy * mdy) * gauss_s2 * gauss_s2;
+    float len = 0.0f;
+#pragma unroll
+    for (uint32_t s = 0; s < 16u; ++s) len += __shfl(term, (int)s, 64);
+    len = sqrtf(len);
+    if (live) out[(size_t)kp * 64 + 4u * sub + q] = sum * gauss_s2 / len;
+}
+
 // ---- image preparation of R3DFeaturesThread::processWorkItem (src/threads/R3DFeaturesThread.cpp:163-191): 8-bit BGR ->
 // float (convertTo, scale 1/255) -> gray (cvtColor BGR2GRAY on floats: 0.114 B + 0.587 G + 0.299 R)
 __global__ __launch_bounds__(256)
@@ -1581,6 +1656,13 @@ hipError_t ak_mldb(hipStream_t st, const AkLevelDev* levels, const AkMldbItem* i
 {
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(ak_mldb_kernel, dim3((n + 1) / 2), dim3(64), 0, st, levels, items, n, pairs, out);
+    return hipGetLastError();
+}
+
+hipError_t ak_msurf(hipStream_t st, const AkLevelDev* levels, const AkMsurfItem* items, uint32_t n, float* out)
+{
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(ak_msurf_kernel, dim3((n + kAkMsurfPerGroup - 1) / kAkMsurfPerGroup), dim3(256), 0, st, levels, items, n, out);
     return hipGetLastError();
 }
 

@@ -11,7 +11,8 @@
 //                     (one workgroup per pair; kernels_filter.hip F / H, kernels_filter_e.hip E), kernels_filter_coop.hip (long pairs)
 //   api_tracks.cpp    feature tracks of a match graph (r3dm_build_tracks), the track filter applied to the graph, r3dm_tracks_in_pair
 //   api_akaze.cpp     the frame of both detector arms (checks, upload, INTER_AREA tables, statistics tail, DetectedBatch's writer) and the
-//                     Fast-A-KAZE arm: its pass in phases, MLDB, r3dm_detect_akaze / _mldb / _mldb_batch / _batch, r3dm_gray_from_bgr8
+//                     Fast-A-KAZE arm: its pass in phases, MLDB, M-SURF-64, r3dm_detect_akaze / _mldb / _mldb_batch / _msurf / _msurf_batch / _batch,
+//                     r3dm_gray_from_bgr8
 //   api_akaze_classic.cpp   the classic A-KAZE arm's launch sequence on that frame, r3dm_detect_akaze_classic / _batch
 //   api_liop.cpp      LIOP: the patch geometry, the one pass from keypoints to descriptors (liop_pass), its two entries
 //   api_features.cpp  the features work item: .feat / .desc files, the features batch in phases (detect, keypoints and maps, LIOP pass,
@@ -403,6 +404,10 @@ struct AkLevelHost {
     float esigma, etime, ratio;
 };
 
+// border factor of the Fast arm's level table (Allocate_Memory_Evolution, fast-akaze AKAZEFeatures.cpp:78-84,105,112: border =
+// fRound(smax sigma_size) + 1): 10 sqrt(2) under MLDB -- the table of the detector, LIOP and MLDB entries -- and 12 sqrt(2) under the
+// KAZE descriptors, i.e. M-SURF-64, whose samples reach that far
+inline float ak_smax(bool msurf) { return (msurf ? 12.0f : 10.0f) * sqrtf(2.0f); }
 // angle of a Fast-arm keypoint: getAngleV2(maxX, maxY) (fast-akaze utils.h:11-19: atan2f of the host libm, + 2 pi when negative)
 inline float ak_theta(const AkKpRec& r)
 {
@@ -426,6 +431,7 @@ inline float ak_angle_deg(float ang)
 struct DetectedBatch {
     std::vector<std::vector<AkKpRec>> fast;            // Fast arm: per image, the survivors in the reference's order (level, list)
     std::vector<AkLevelHost> fast_levels;              //           the evolution levels of this image size
+    float fast_smax = 0.0f;                            //           ... and the border factor they were cut with (ak_smax)
     std::vector<std::vector<AcOut>> classic;           // classic arm: per image, the slots that survive, in slot order
     const float* grays_dev = nullptr;                  // the B gray planes the detector left on the device (read-only for it)
     size_t count(uint32_t b) const { return fast.empty() ? classic[b].size() : fast[b].size(); }
@@ -439,7 +445,7 @@ struct DetectedBatch {
 // the two arms; gray images (host or device) or 8-bit BGR.  detect_batch: the context's arm (r3dm_set_keypoint_detector)
 using DetectArm = int(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
                       float threshold, DetectedBatch& out);
-DetectArm ak_detect_batch, ac_detect_batch, detect_batch;
+DetectArm ak_detect_batch, ak_detect_batch_msurf, ac_detect_batch, detect_batch;
 // A detect entry: its argument checks, B gray images through `arm`, then keypoints_out[b] / responses_out[b] (entries optional) / n_out[b]:
 // min(count, cap) rows are written, the count itself is reported.  single: one image by value, whose count reads 0 when the arm fails
 int detect_entry(r3dm_ctx* c, DetectArm* arm, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
@@ -465,6 +471,9 @@ void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints,
 // (null when there is no keypoint), valid until the context's next detector or MLDB pass.  Bracketed by ev0 / ev1 and waited for;
 // host_team threads share the item loop (cos / sin of every keypoint's angle, host libm)
 int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev);
+// ---- M-SURF-64 of a Fast-arm pass, the same way: rows of 64 floats, image b's at + 256 first[b] bytes.  `det` must come from
+// ak_detect_batch_msurf: a pass on the other level table is refused (R3DM_ERR_INVALID), its borders do not hold M-SURF's reads in
+int ak_msurf_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev);
 
 // ---- LIOP (api_liop.cpp)
 // 2x3 inverse map of one keypoint's patch (x, y, size, angle in degrees)

@@ -380,6 +380,7 @@ struct AkLevelDev {
     float4* out0; float2* out1; uint32_t* out_valid;     // refined (x, y, size, response), dominant gradient vector, kept?
 };
 struct AkMldbItem { uint32_t level; float xf, yf, co, si, scale; };   // keypoint in level coordinates (level = image * n_levels + level), cos / sin of its angle, sigma_size
+struct AkMsurfItem { uint32_t level; float xf, yf, co, si; int32_t scale; };   // the same for M-SURF-64: scale is the reference's int (fRound(size / 2 / ratio) = sigma_size)
 // per image of a batch, written by the device: candidates the count pass found, whether they exceeded the slot capacity (then the
 // image's lists were not built and the host repeats the detection phase with larger slot arrays), keypoints compacted
 struct AkBatchMeta { uint32_t need, overflow, n_kp, pad; };
@@ -387,6 +388,8 @@ struct AkBatchMeta { uint32_t need, overflow, n_kp, pad; };
 struct AkKpRec { float x, y, size, response, max_x, max_y; uint32_t level, pad; };
 // All launchers: B = images of the batch (same size); image buffers hold B planes back to back; levels = [B][n_levels].
 hipError_t ak_mldb(hipStream_t st, const AkLevelDev* levels, const AkMldbItem* items, uint32_t n, const unsigned char* pairs, unsigned char* out);
+// M-SURF-64 rows (64 floats each, 16-byte aligned) of n keypoints; `levels` must carry the M-SURF border (kAkSmaxMsurf)
+hipError_t ak_msurf(hipStream_t st, const AkLevelDev* levels, const AkMsurfItem* items, uint32_t n, float* out);
 hipError_t ak_bgr_to_gray(hipStream_t st, const unsigned char* bgr, float* gray, size_t n);
 hipError_t ak_gaussian(hipStream_t st, const float* src, float* tmp, float* dst, int w, int h, int B, const AkTaps& kf);
 hipError_t ak_scharr(hipStream_t st, const float* src, float* rd, float* rs, float* Lx, float* Ly, int w, int h, int B);
