@@ -60,9 +60,13 @@ STAGE_DESCRIPTOR_MLDB = 512
 STAGE_DESCRIPTOR_MSURF = 1024
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
-DESCRIPTORS = {"LIOP": 0, "MLDB": 1}             # R3DM_DESCRIPTOR_LIOP / R3DM_DESCRIPTOR_MLDB
-DESCRIPTOR_ARMS = {**DESCRIPTORS, "MSURF": 3}     # every arm r3dm_set_descriptor_arm takes: + R3DM_DESCRIPTOR_MSURF (2 is unassigned)
-_DESCRIPTOR_STAGE_FLAGS = {"LIOP": 0, "MLDB": STAGE_DESCRIPTOR_MLDB, "MSURF": STAGE_DESCRIPTOR_MSURF}
+# the descriptor arms, the rows of csrc/descriptor_arms.hpp (tests/test_descriptor_arms.py holds the two to each other): name, id
+# (R3DM_DESCRIPTOR_*; 2 is unassigned), stage flag, numpy dtype and length of a row
+_ARMS = [("LIOP", 0, 0, np.float32, 144), ("MLDB", 1, STAGE_DESCRIPTOR_MLDB, np.uint8, 61), ("MSURF", 3, STAGE_DESCRIPTOR_MSURF, np.float32, 64)]
+DESCRIPTOR_ARMS = {name: arm_id for name, arm_id, _, _, _ in _ARMS}      # every arm r3dm_set_descriptor_arm takes
+DESCRIPTORS = {name: arm_id for name, arm_id in DESCRIPTOR_ARMS.items() if arm_id < 2}      # (the arms before M-SURF: a name the suite pins)
+_DESCRIPTOR_STAGE_FLAGS = {name: flag for name, _, flag, _, _ in _ARMS}
+_ARM_ROWS = {name: (dtype, dim) for name, _, _, dtype, dim in _ARMS}
 
 
 def _detector_flag(detector: str) -> int:
@@ -1663,37 +1667,35 @@ class Context:
         self._check(self._L.r3dm_detect_akaze_batch(self._h, B, ip, w, h, threshold, kp_p, rp_p, cap, _ptr(n)), "r3dm_detect_akaze_batch")
         return [(kps[b][:min(int(n[b]), cap)].copy(), resp[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
 
-    def detect_akaze_mldb_batch(self, images, threshold: float = 0.001, cap: int = 200000):
-        """r3dm_detect_akaze_mldb_batch: B same-size images in one pass of the detector and ONE MLDB launch
-        -> list of (keypoints [n, 4], descriptors [n, 61] uint8)"""
+    def _detect_describe_batch(self, arm: str, entry: str, images, threshold: float, cap: int, single: bool = False):
+        """a describing detect entry of `arm` over B same-size images -> list of (keypoints [n, 4], descriptors [n, dim]); single: the
+        one image of the list through the entry of one image, `entry` without its _batch"""
+        dtype, dim = _ARM_ROWS[arm]
         imgs = [im if hasattr(im, "data_ptr") else np.ascontiguousarray(im, np.float32) for im in images]
         B = len(imgs); h, w = int(imgs[0].shape[0]), int(imgs[0].shape[1])
         assert all(tuple(im.shape) == (h, w) for im in imgs), "a batch holds images of one size"
         ip = (C.c_void_p * B)(*[(im.data_ptr() if hasattr(im, "data_ptr") else im.ctypes.data) for im in imgs])
-        kps = [np.zeros((cap, 4), np.float32) for _ in range(B)]; desc = [np.zeros((cap, 61), np.uint8) for _ in range(B)]
+        kps = [np.zeros((cap, 4), np.float32) for _ in range(B)]; desc = [np.zeros((cap, dim), dtype) for _ in range(B)]
         kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); dp_p = (C.c_void_p * B)(*[d.ctypes.data for d in desc])
         n = np.zeros(B, np.uint32)
-        self._check(self._L.r3dm_detect_akaze_mldb_batch(self._h, B, ip, w, h, threshold, kp_p, dp_p, cap, _ptr(n)), "r3dm_detect_akaze_mldb_batch")
+        if single:
+            assert B == 1
+            entry = entry[:-len("_batch")]
+            self._check(getattr(self._L, entry)(self._h, ip[0], w, h, threshold, kp_p[0], dp_p[0], cap, n.ctypes.data_as(C.POINTER(C.c_uint32))), entry)
+        else:
+            self._check(getattr(self._L, entry)(self._h, B, ip, w, h, threshold, kp_p, dp_p, cap, _ptr(n)), entry)
         return [(kps[b][:min(int(n[b]), cap)].copy(), desc[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
+
+    def detect_akaze_mldb_batch(self, images, threshold: float = 0.001, cap: int = 200000):
+        """r3dm_detect_akaze_mldb_batch: B same-size images in one pass of the detector and ONE MLDB launch
+        -> list of (keypoints [n, 4], descriptors [n, 61] uint8)"""
+        return self._detect_describe_batch("MLDB", "r3dm_detect_akaze_mldb_batch", images, threshold, cap)
 
     def detect_akaze_msurf_batch(self, images, threshold: float = 0.001, cap: int = 200000, single: bool = False):
         """r3dm_detect_akaze_msurf_batch: B same-size images in one pass of the detector (on the level table with the M-SURF border) and
         ONE M-SURF-64 launch -> list of (keypoints [n, 4], descriptors [n, 64] float32).  single: the one image of the list through
         r3dm_detect_akaze_msurf instead"""
-        imgs = [im if hasattr(im, "data_ptr") else np.ascontiguousarray(im, np.float32) for im in images]
-        B = len(imgs); h, w = int(imgs[0].shape[0]), int(imgs[0].shape[1])
-        assert all(tuple(im.shape) == (h, w) for im in imgs), "a batch holds images of one size"
-        ip = (C.c_void_p * B)(*[(im.data_ptr() if hasattr(im, "data_ptr") else im.ctypes.data) for im in imgs])
-        kps = [np.zeros((cap, 4), np.float32) for _ in range(B)]; desc = [np.zeros((cap, 64), np.float32) for _ in range(B)]
-        kp_p = (C.c_void_p * B)(*[k.ctypes.data for k in kps]); dp_p = (C.c_void_p * B)(*[d.ctypes.data for d in desc])
-        n = np.zeros(B, np.uint32)
-        if single:
-            assert B == 1
-            self._check(self._L.r3dm_detect_akaze_msurf(self._h, ip[0], w, h, threshold, kp_p[0], dp_p[0], cap, n.ctypes.data_as(C.POINTER(C.c_uint32))),
-                        "r3dm_detect_akaze_msurf")
-        else:
-            self._check(self._L.r3dm_detect_akaze_msurf_batch(self._h, B, ip, w, h, threshold, kp_p, dp_p, cap, _ptr(n)), "r3dm_detect_akaze_msurf_batch")
-        return [(kps[b][:min(int(n[b]), cap)].copy(), desc[b][:min(int(n[b]), cap)].copy()) for b in range(B)]
+        return self._detect_describe_batch("MSURF", "r3dm_detect_akaze_msurf_batch", images, threshold, cap, single)
 
     def detect_akaze_classic(self, image, threshold: float = 0.001, cap: int = 200000):
         """r3dm_detect_akaze_classic, Regard3D's "AKAZE" arm (libAKAZE): image [h, w] float32 in [0, 1] (numpy or torch, host or device)

@@ -1,8 +1,8 @@
 // api_akaze.cpp -- part of the host side of libr3dm.so (see r3dm_ctx.hpp for the file map): keypoint detection.  The frame both detector
 // arms stand in (argument checks, gray-or-BGR upload, INTER_AREA tables, statistics tail, the detect entry over a DetectedBatch, the choice
 // of the arm), then the Fast-A-KAZE arm (kernels_akaze.hip): ak_detect_batch in its phases -- buffers, scale space, detection with regrow,
-// read-back -- and its entries.  The classic arm's launch sequence is api_akaze_classic.cpp; what is shared and what stays per arm:
-// DESIGN.md section 4.21.  There is no CPU fallback in this file: when HIP fails, the call fails.  At the end, developer build only: the
+// read-back -- the one pass of the level-plane descriptors (ak_describe_pass: MLDB-486, M-SURF-64) and the entries.  The classic arm's launch
+// sequence is api_akaze_classic.cpp; what is shared and what stays per arm, of the detectors and of the descriptors: DESIGN.md section 4.21.  There is no CPU fallback in this file: when HIP fails, the call fails.  At the end, developer build only: the
 // arm's tail on a caller's planes and lists (r3dm_dev_akaze_tail), and its head -- scale space, extrema, in-level pruning -- on a caller's images
 // or determinant planes, every plane and list read back (r3dm_dev_akaze_head, r3dm_dev_akaze_extrema).
 #include "r3dm_ctx.hpp"
@@ -138,12 +138,16 @@ void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints,
     T.n_keypoints += n_keypoints;
 }
 
+static int ak_detect_batch_smax(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
+                                float threshold, float smax, DetectedBatch& out);
+
 int detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
                  float threshold, DetectedBatch& out)
 {
     if (c && c->detector_arm == R3DM_DETECTOR_AKAZE) return ac_detect_batch(c, B, images, bgrs, width, height, threshold, out);
-    // (the Fast arm's level table carries the border of the descriptor that will read its planes)
-    return (c && c->descriptor_arm == R3DM_DESCRIPTOR_MSURF ? ak_detect_batch_msurf : ak_detect_batch)(c, B, images, bgrs, width, height, threshold, out);
+    // (the Fast arm's level table carries the border of the descriptor that will read its planes; the setter admits the table's ids only)
+    const DescriptorArm& arm = *descriptor_arm_by_id(c ? c->descriptor_arm : R3DM_DESCRIPTOR_LIOP);
+    return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, ak_smax(arm), out);
 }
 
 int detect_entry(r3dm_ctx* c, DetectArm* arm, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
@@ -169,10 +173,11 @@ namespace {
 
 // AKAZEFeaturesV2::Allocate_Memory_Evolution (src/thirdparty/fast-akaze/AKAZEFeatures.cpp:73-131) with the AKAZE2::create()
 // defaults (AKAZEConfig.h:18-43): 4 octaves x 4 sublevels, soffset 1.6, derivative_factor 1.5.  The border is the DESCRIPTOR's
-// (:78-84): smax = 10 sqrt(2) for MLDB (ak_smax(false): what the detector, LIOP and MLDB arms run on), 12 sqrt(2) for the KAZE
-// descriptors (ak_smax(true): M-SURF-64).  The larger border cuts the table earlier, so the M-SURF table is a prefix of the other
-// with wider borders, and detection under it differs near the frame and on small images.
-std::vector<AkLevelHost> ak_levels(int w, int h, float smax = ak_smax(false))
+// (:78-84): smax = 10 sqrt(2) for MLDB (what the detector, LIOP and MLDB arms run on), 12 sqrt(2) for the KAZE descriptors (M-SURF-64):
+// ak_smax of the arm's row in descriptor_arms.hpp.  The larger border cuts the table earlier, so the M-SURF table is a prefix of the
+// other with wider borders, and detection under it differs near the frame and on small images.
+const float kAkSmaxDetector = ak_smax(*descriptor_arm_by_id(R3DM_DESCRIPTOR_LIOP)), kAkSmaxMsurf = ak_smax(*descriptor_arm_by_id(R3DM_DESCRIPTOR_MSURF));
+std::vector<AkLevelHost> ak_levels(int w, int h, float smax = kAkSmaxDetector)
 {
     std::vector<AkLevelHost> lv;
     const int omax = 4, nsub = 4;
@@ -233,7 +238,7 @@ std::vector<float> ak_fed_tau(float T)
 
 // c->ak_bufs, each B planes: [0] image, [1..10] level-0 sized work images, then 4 per level (Lt, Lx, Ly, Ldet), then the T_* buffers
 enum { B_IMG = 0, B_SMOOTH, B_LXX, B_LXY, B_LYY, B_TMP, B_TMP2, B_WX, B_WY, B_FLOW, B_LT2, B_SMALL, B_LEVEL0 };
-enum { T_META = 0, T_SLOTS, T_MLDB, T_TABS, T_RECS, T_COUNT = 8 };
+enum { T_META = 0, T_SLOTS, T_DESC /* items, extra bytes and rows of the level-plane descriptor pass */, T_TABS, T_RECS, T_COUNT = 8 };
 
 // the launches of one level i > 0 (ak_level_plan decides, ak_evolve_level issues): the one-pass level head (with its rows per band) or the
 // four launches, and per FED launch its form, its steps and (marching) its rows per band
@@ -525,6 +530,20 @@ hipError_t ak_head_launches(hipStream_t st, AkLevelDev* d_levels, int nl, int iB
     return ak_prune_levels(st, d_levels, nl, iB);
 }
 
+// the level table of a pass on the device, as every caller of the head or tail launches (and the developer M-SURF entry, cap 0) puts it
+// there: the slot arrays -- with `with_recs` the record array too -- of `cap` slots per image, the row counts and counters cleared, d.ld
+// at d.d_levels, in this order on the stream
+int ak_table_upload(AkPass& p, AkDetection& d, uint32_t cap, bool with_recs)
+{
+    r3dm_ctx* c = p.c;
+    const size_t field = (size_t)p.B * cap;
+    R3DM_HIP(c, p.tail(T_SLOTS).ensure(field * kAkSlotBytes + 256));
+    if (with_recs) R3DM_HIP(c, p.tail(T_RECS).ensure(field * sizeof(AkKpRec) + 256));
+    R3DM_HIP(c, hipMemsetAsync(p.tail(T_META).p, 0, d.rows_total * 8 + d.n_lv * 16, p.st));
+    R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, p.st));
+    return R3DM_OK;
+}
+
 // the detection launches at a slot capacity; an image that reports more candidates than it makes them run again with larger arrays
 int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
 {
@@ -534,13 +553,9 @@ int ak_detect_regrow(AkPass& p, AkDetection& d, float threshold)
     static const uint32_t cap0 = (uint32_t)std::max(1, r3dm_dev_knob("R3DM_AK_CAP", 1 << 18));
     uint32_t cap = (uint32_t)std::min<uint64_t>(d.bound, std::max<uint64_t>(c->ak_cap, cap0));
     d.bm.assign(B, AkBatchMeta{});
-    DevBuf &meta = p.tail(T_META), &slots = p.tail(T_SLOTS), &recs = p.tail(T_RECS);
+    DevBuf &slots = p.tail(T_SLOTS), &recs = p.tail(T_RECS);
     for (int attempt = 0;; ++attempt) {
-        const size_t field = (size_t)B * cap;
-        R3DM_HIP(c, slots.ensure(field * kAkSlotBytes + 256));
-        R3DM_HIP(c, recs.ensure(field * sizeof(AkKpRec) + 256));
-        R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
-        R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
+        { const int urc = ak_table_upload(p, d, cap, true); if (urc != R3DM_OK) return urc; }
         R3DM_HIP(c, ak_head_launches(st, d.d_levels, nl, iB, d.tiles, d.n_tiles, d.max_rows, slots.as<unsigned char>(), cap, d.d_bmeta, threshold));
         R3DM_HIP(c, ak_tail_launches(st, d.d_levels, nl, iB, recs.as<AkKpRec>(), cap, d.d_bmeta));
         R3DM_HIP(c, hipEventRecord(c->ev1, st));
@@ -609,26 +624,25 @@ static int ak_detect_batch_smax(r3dm_ctx* c, uint32_t B, const float* const* ima
     return R3DM_OK;
 }
 
+// the two level tables as detect arms (detect_entry's shape): the detector's own, which LIOP and MLDB read, and that of the KAZE
+// descriptors, which M-SURF-64 must be computed on
 int ak_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
-                    float threshold, DetectedBatch& out)
-{
-    return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, ak_smax(false), out);
-}
-
-// the same pass on the level table of the KAZE descriptors (ak_levels): what M-SURF-64 must be computed on
+                    float threshold, DetectedBatch& out) { return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, kAkSmaxDetector, out); }
 int ak_detect_batch_msurf(r3dm_ctx* c, uint32_t B, const float* const* images, const unsigned char* const* bgrs, uint32_t width, uint32_t height,
-                          float threshold, DetectedBatch& out)
-{
-    return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, ak_smax(true), out);
-}
+                          float threshold, DetectedBatch& out) { return ak_detect_batch_smax(c, B, images, bgrs, width, height, threshold, kAkSmaxMsurf, out); }
 
-// one keypoint of image b as the MLDB kernel takes it: the raw (radian) angle of the host libm, its cos / sin, level coordinates, sigma_size
-static AkMldbItem ak_mldb_item(uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r, float* theta_out)
+// ======== the level-plane descriptors of the Fast arm: MLDB-486 and M-SURF-64 ("The descriptor arms")
+// one keypoint of image b as either kernel takes it: the raw (radian) angle of the host libm, its cos / sin, level coordinates, and the
+// level's sigma_size -- a float for MLDB, for M-SURF the reference's int scale (fRound(0.5 size / ratio), which is the level's sigma_size:
+// size = 2 esigma derivative_factor and sigma_size = fRound(esigma derivative_factor / ratio)).  The two items stay as the kernels declare them.
+template <class Item> static Item ak_item(uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r, float* theta_out = nullptr)
 {
     const float theta = ak_theta(r);
     if (theta_out) *theta_out = theta;
-    return {b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (float)lv[r.level].sigma_size};
+    return {b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), (decltype(Item::scale))lv[r.level].sigma_size};
 }
+constexpr size_t kAkItemBytes = 24;
+static_assert(sizeof(AkMldbItem) == kAkItemBytes && sizeof(AkMsurfItem) == kAkItemBytes, "the level-plane items are 24 bytes each");
 
 // comparison table of MLDB_Binary_Comparisons: per grid, per channel, all value pairs i < j
 static std::vector<unsigned char> ak_mldb_pairs()
@@ -642,87 +656,78 @@ static std::vector<unsigned char> ak_mldb_pairs()
     return pairs;
 }
 
-// Get_MLDB_Full_Descriptor of the first min(count, cap) keypoints of every image of the pass, in ONE launch: level coordinates, cos / sin of
-// the raw (radian) angle (host libm, as the oracle and the LIOP patch map: device trigonometry is not bit-equal to it).  An item names
-// its level as image * n_levels + level: the level table the detector left on the device (ak_levels_dev) and the Lt / Lx / Ly planes of
-// its work buffers cover the B images of the pass until the next pass.  The rows of image b follow those of image b - 1, 61 bytes
-// apart -- the layout r3dm_set_image(dim 61, R3DM_BIN) reads from a device pointer, so a consumer on the device takes image b's rows
-// where the kernel stored them, at rows_dev + 61 first[b]; nothing is copied.  first (B + 1 entries): row offsets per image.
-// rows_dev stays valid until this context's next detector or MLDB pass.  The launch is bracketed by ev0 / ev1 and waited for.
-// host_team: the threads that share the item loop (three libm calls per keypoint: 229 k keypoints of eight 12 Mpx images on one thread
-// took longer than the detector's kernels), in chunks of 4,096 keypoints over all images as the features batch forms its angles.
-int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev)
+// M-SURF's own refusals.  The kernel reads Lx / Ly up to 12 sqrt(2) sigma_size + 1 from a keypoint: only the level table cut with the
+// arm's border keeps that inside the planes, a pass on any other is refused here.
+static int ak_msurf_refuse(r3dm_ctx* c, const DescriptorArm& arm, const DetectedBatch& det)
 {
-    const uint32_t B = (uint32_t)det.fast.size();
     const std::vector<AkLevelHost>& lv = det.fast_levels;
-    const uint32_t nl = (uint32_t)lv.size();
-    first.assign((size_t)B + 1, 0);
-    for (uint32_t b = 0; b < B; ++b) first[b + 1] = first[b] + std::min<size_t>(det.fast[b].size(), cap);
-    *rows_dev = nullptr;
-    const size_t ni = first[B];
-    if (ni == 0) return R3DM_OK;
-    if (ni >= (1ull << 31)) { c->err = "MLDB: more than 2^31 keypoints in one pass"; return R3DM_ERR_UNSUPPORTED; }
-    std::vector<AkMldbItem> items(ni);
-    struct Chunk { uint32_t b; size_t k0, k1; };
-    std::vector<Chunk> chunks;
-    for (uint32_t b = 0; b < B; ++b)
-        for (size_t k0 = 0, nk = first[b + 1] - first[b]; k0 < nk; k0 += 4096) chunks.push_back({b, k0, std::min(nk, k0 + 4096)});
-    r3dm_parallel_for((long)chunks.size(), host_team, [&](long ci) {
-        const Chunk& ch = chunks[(size_t)ci];
-        const std::vector<AkKpRec>& recs = det.fast[ch.b];
-        for (size_t k = ch.k0; k < ch.k1; ++k) {
-            items[first[ch.b] + k] = ak_mldb_item(ch.b, nl, lv, recs[k], nullptr);
-        }
-    });
-    const std::vector<unsigned char> pairs = ak_mldb_pairs();
-    hipStream_t st = c->stream;
-    DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_MLDB];
-    R3DM_HIP(c, mb.ensure(ni * sizeof(AkMldbItem) + 1024 + ni * 61 + 64));
-    unsigned char* base = mb.as<unsigned char>();
-    R3DM_HIP(c, hipMemcpyAsync(base, items.data(), ni * sizeof(AkMldbItem), hipMemcpyHostToDevice, st));
-    R3DM_HIP(c, hipMemcpyAsync(base + ni * sizeof(AkMldbItem), pairs.data(), pairs.size(), hipMemcpyHostToDevice, st));
-    unsigned char* d_out = base + ni * sizeof(AkMldbItem) + 1024;
-    R3DM_HIP(c, hipEventRecord(c->ev0, st));
-    R3DM_HIP(c, ak_mldb(st, c->ak_levels_dev, (const AkMldbItem*)base, (uint32_t)ni, base + ni * sizeof(AkMldbItem), d_out));
-    R3DM_HIP(c, hipEventRecord(c->ev1, st));
-    R3DM_HIP(c, hipStreamSynchronize(st));                                // `items` and `pairs` leave scope
-    *rows_dev = d_out;
+    if (det.fast_smax != ak_smax(arm)) { c->err = "M-SURF: the detector pass ran on the MLDB level table, whose borders do not hold the descriptor's reads"; return R3DM_ERR_INVALID; }
+    // (the in-plane argument at r3dm_dev_akaze_msurf_check counts on float positions below 2^16 and on sigma_size 2 .. 4)
+    if (lv[0].w > 65536 || lv[0].h > 65536) { c->err = "M-SURF: images of more than 65536 columns or rows are not served"; return R3DM_ERR_UNSUPPORTED; }
+    for (const AkLevelHost& e : lv) if (e.sigma_size < 2 || e.sigma_size > 4) { c->err = "M-SURF: unexpected level table"; return R3DM_ERR_UNSUPPORTED; }
     return R3DM_OK;
 }
 
-// one keypoint of image b as the M-SURF kernel takes it: as ak_mldb_item, with the reference's int scale (fRound(0.5 size / ratio), which
-// is the level's sigma_size: size = 2 esigma derivative_factor and sigma_size = fRound(esigma derivative_factor / ratio))
-static AkMsurfItem ak_msurf_item(uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r)
+// what a level-plane arm adds to the one pass below: how an item is formed from a record, the bytes uploaded behind the items (null:
+// none), its launcher, its own refusals (null: none), and the detect arm that cuts its level table
+struct AkDescribeOps {
+    int id; DetectArm* detect;
+    void (*item)(void* at, uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r);
+    std::vector<unsigned char> (*extra)();
+    hipError_t (*launch)(hipStream_t st, const AkLevelDev* levels, const void* items, uint32_t n, const unsigned char* extra, unsigned char* rows);
+    int (*refuse)(r3dm_ctx* c, const DescriptorArm& arm, const DetectedBatch& det);
+};
+template <class Item> static void ak_item_at(void* at, uint32_t b, uint32_t nl, const std::vector<AkLevelHost>& lv, const AkKpRec& r)
+{ const Item it = ak_item<Item>(b, nl, lv, r); memcpy(at, &it, sizeof it); }
+static const AkDescribeOps kAkDescribeOps[] = {
+    {R3DM_DESCRIPTOR_MLDB, ak_detect_batch, ak_item_at<AkMldbItem>, ak_mldb_pairs,
+     [](hipStream_t st, const AkLevelDev* levels, const void* items, uint32_t n, const unsigned char* extra, unsigned char* rows) {
+         return ak_mldb(st, levels, (const AkMldbItem*)items, n, extra, rows); }, nullptr},
+    {R3DM_DESCRIPTOR_MSURF, ak_detect_batch_msurf, ak_item_at<AkMsurfItem>, nullptr,
+     [](hipStream_t st, const AkLevelDev* levels, const void* items, uint32_t n, const unsigned char*, unsigned char* rows) {
+         return ak_msurf(st, levels, (const AkMsurfItem*)items, n, reinterpret_cast<float*>(rows)); }, ak_msurf_refuse},
+};
+static const AkDescribeOps& ak_describe_ops(const DescriptorArm& arm)
 {
-    const float theta = ak_theta(r);
-    return {b * nl + r.level, r.x / lv[r.level].ratio, r.y / lv[r.level].ratio, cosf(theta), sinf(theta), lv[r.level].sigma_size};
+    for (const AkDescribeOps& o : kAkDescribeOps) if (o.id == arm.id) return o;
+    abort();                                                              // (a level-plane arm of the table without a row here)
 }
 
-// the launch of the M-SURF kernel over `items` (host memory) on the level table the context's last pass left on the device, which the
-// caller vouches was cut with ak_smax(true): items up, one launch between ev0 / ev1, waited for; *rows_dev: 64 floats a row
-static int ak_msurf_launch(r3dm_ctx* c, const std::vector<AkMsurfItem>& items, const unsigned char** rows_dev)
+// the launch of the arm's kernel over ni > 0 items (host memory) on the level table the context's last pass left on the device, which the
+// caller vouches was cut for the arm: items and the arm's extra bytes up, one launch between ev0 / ev1, waited for (the caller's items may
+// leave scope); *rows_dev: arm.row_bytes a row, 256-byte aligned (M-SURF's float4 stores need 16).  One buffer holds items, extra bytes, rows.
+static int ak_describe_launch(r3dm_ctx* c, const DescriptorArm& arm, const void* items, size_t ni, const unsigned char** rows_dev)
 {
-    const size_t ni = items.size();
+    const AkDescribeOps& ops = ak_describe_ops(arm);
+    const std::vector<unsigned char> extra = ops.extra ? ops.extra() : std::vector<unsigned char>();
     hipStream_t st = c->stream;
-    DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_MLDB];
-    const size_t off_rows = (ni * sizeof(AkMsurfItem) + 255) / 256 * 256;
-    R3DM_HIP(c, mb.ensure(off_rows + ni * 256 + 64));
+    DevBuf& mb = c->ak_bufs[c->ak_bufs.size() - T_COUNT + T_DESC];
+    const size_t off_extra = ni * kAkItemBytes, off_rows = (off_extra + extra.size() + 255) / 256 * 256;
+    R3DM_HIP(c, mb.ensure(off_rows + ni * arm.row_bytes + 64));
     unsigned char* base = mb.as<unsigned char>();
-    R3DM_HIP(c, hipMemcpyAsync(base, items.data(), ni * sizeof(AkMsurfItem), hipMemcpyHostToDevice, st));
+    R3DM_HIP(c, hipMemcpyAsync(base, items, ni * kAkItemBytes, hipMemcpyHostToDevice, st));
+    if (!extra.empty()) R3DM_HIP(c, hipMemcpyAsync(base + off_extra, extra.data(), extra.size(), hipMemcpyHostToDevice, st));
     R3DM_HIP(c, hipEventRecord(c->ev0, st));
-    R3DM_HIP(c, ak_msurf(st, c->ak_levels_dev, (const AkMsurfItem*)base, (uint32_t)ni, reinterpret_cast<float*>(base + off_rows)));
+    R3DM_HIP(c, ops.launch(st, c->ak_levels_dev, base, (uint32_t)ni, base + off_extra, base + off_rows));
     R3DM_HIP(c, hipEventRecord(c->ev1, st));
-    R3DM_HIP(c, hipStreamSynchronize(st));                                // the caller's `items` may leave scope
+    R3DM_HIP(c, hipStreamSynchronize(st));                                // the items and `extra` may leave scope
     *rows_dev = base + off_rows;
     return R3DM_OK;
 }
 
-// Get_MSURF_Descriptor_64 of the first min(count, cap) keypoints of every image of the pass, in ONE launch, as ak_mldb_pass does it for
-// MLDB: same item loop, same buffer, same lifetime of rows_dev; image b's rows are at rows_dev + 256 first[b], the layout
-// r3dm_set_image(dim 64, R3DM_F32) reads from a device pointer.  The kernel reads Lx / Ly up to 12 sqrt(2) sigma_size + 1 from a
-// keypoint: only the level table of ak_detect_batch_msurf keeps that inside the planes, a pass on any other is refused here.
-int ak_msurf_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev)
+// Get_MLDB_Full_Descriptor / Get_MSURF_Descriptor_64 of the first min(count, cap) keypoints of every image of the pass, in ONE launch:
+// level coordinates, cos / sin of the raw (radian) angle (host libm, as the oracle and the LIOP patch map: device trigonometry is not
+// bit-equal to it).  An item names its level as image * n_levels + level: the level table the detector left on the device (ak_levels_dev)
+// and the Lt / Lx / Ly planes of its work buffers cover the B images of the pass until the next pass.  The rows of image b follow those of
+// image b - 1, arm.row_bytes apart -- the layout r3dm_set_image(arm.dim, arm.dtype) reads from a device pointer, so a consumer on the
+// device takes image b's rows where the kernel stored them, at rows_dev + arm.row_bytes first[b]; nothing is copied.  first (B + 1
+// entries): row offsets per image.  rows_dev stays valid until this context's next detector or descriptor pass.
+// host_team: the threads that share the item loop (three libm calls per keypoint: 229 k keypoints of eight 12 Mpx images on one thread
+// took longer than the detector's kernels), in chunks of 4,096 keypoints over all images as the features batch forms its angles.
+int ak_describe_pass(r3dm_ctx* c, const DescriptorArm& arm, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first,
+                     const unsigned char** rows_dev)
 {
+    const AkDescribeOps& ops = ak_describe_ops(arm);
     const uint32_t B = (uint32_t)det.fast.size();
     const std::vector<AkLevelHost>& lv = det.fast_levels;
     const uint32_t nl = (uint32_t)lv.size();
@@ -731,12 +736,9 @@ int ak_msurf_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_
     *rows_dev = nullptr;
     const size_t ni = first[B];
     if (ni == 0) return R3DM_OK;
-    if (det.fast_smax != ak_smax(true)) { c->err = "M-SURF: the detector pass ran on the MLDB level table, whose borders do not hold the descriptor's reads"; return R3DM_ERR_INVALID; }
-    if (ni >= (1ull << 31)) { c->err = "M-SURF: more than 2^31 keypoints in one pass"; return R3DM_ERR_UNSUPPORTED; }
-    // (the in-plane argument at r3dm_dev_akaze_msurf_check counts on float positions below 2^16 and on sigma_size 2 .. 4)
-    if (lv[0].w > 65536 || lv[0].h > 65536) { c->err = "M-SURF: images of more than 65536 columns or rows are not served"; return R3DM_ERR_UNSUPPORTED; }
-    for (const AkLevelHost& e : lv) if (e.sigma_size < 2 || e.sigma_size > 4) { c->err = "M-SURF: unexpected level table"; return R3DM_ERR_UNSUPPORTED; }
-    std::vector<AkMsurfItem> items(ni);
+    if (ops.refuse) { const int rrc = ops.refuse(c, arm, det); if (rrc != R3DM_OK) return rrc; }
+    if (ni >= (1ull << 31)) { c->err = std::string(arm.tag) + ": more than 2^31 keypoints in one pass"; return R3DM_ERR_UNSUPPORTED; }
+    std::vector<unsigned char> items(ni * kAkItemBytes);
     struct Chunk { uint32_t b; size_t k0, k1; };
     std::vector<Chunk> chunks;
     for (uint32_t b = 0; b < B; ++b)
@@ -744,52 +746,35 @@ int ak_msurf_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_
     r3dm_parallel_for((long)chunks.size(), host_team, [&](long ci) {
         const Chunk& ch = chunks[(size_t)ci];
         const std::vector<AkKpRec>& recs = det.fast[ch.b];
-        for (size_t k = ch.k0; k < ch.k1; ++k) items[first[ch.b] + k] = ak_msurf_item(ch.b, nl, lv, recs[k]);
+        for (size_t k = ch.k0; k < ch.k1; ++k) ops.item(items.data() + (first[ch.b] + k) * kAkItemBytes, ch.b, nl, lv, recs[k]);
     });
-    return ak_msurf_launch(c, items, rows_dev);
+    return ak_describe_launch(c, arm, items.data(), ni, rows_dev);
 }
 
-// the detect entry of the M-SURF forms: ak_mldb_entry on the M-SURF level table, rows of 64 floats
-static int ak_msurf_entry(r3dm_ctx* c, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
-                          float* const* keypoints_out, float* const* descriptors_out, uint32_t cap, uint32_t* n_out)
+// the detect entry of the describing forms: the keypoints through detect_entry on the arm's level table, then min(count, cap) rows per
+// image from the one pass; on failure every count reads 0
+static int ak_describe_entry(r3dm_ctx* c, const DescriptorArm& arm, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height,
+                             float threshold, float* const* keypoints_out, void* const* descriptors_out, uint32_t cap, uint32_t* n_out)
 {
     if (cap && !descriptors_out) return R3DM_ERR_INVALID;
     if (cap && images && B <= 4096) for (uint32_t b = 0; b < B; ++b) if (!descriptors_out[b] || (keypoints_out && !keypoints_out[b])) return R3DM_ERR_INVALID;
     DetectedBatch det;
-    int rc = detect_entry(c, ak_detect_batch_msurf, single, B, images, width, height, threshold, keypoints_out, nullptr, cap, n_out, det);
+    int rc = detect_entry(c, ak_describe_ops(arm).detect, single, B, images, width, height, threshold, keypoints_out, nullptr, cap, n_out, det);
     if (rc != R3DM_OK) return rc;
     std::vector<size_t> first;
     const unsigned char* rows = nullptr;
-    rc = ak_msurf_pass(c, det, cap, r3dm_host_team(8), first, &rows);
+    rc = ak_describe_pass(c, arm, det, cap, r3dm_host_team(8), first, &rows);
+    const auto lost = [&]() { c->err = std::string(arm.tag) + ": the descriptors did not reach the host"; rc = R3DM_ERR_HIP; };
     for (uint32_t b = 0; rc == R3DM_OK && b < B; ++b) {
         const size_t nb = first[b + 1] - first[b];
-        if (nb && hipMemcpyAsync(descriptors_out[b], rows + 256 * first[b], nb * 256, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { c->err = "M-SURF: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
+        if (nb && hipMemcpyAsync(descriptors_out[b], rows + arm.row_bytes * first[b], nb * arm.row_bytes, hipMemcpyDeviceToHost, c->stream) != hipSuccess) lost();
     }
-    if (rc == R3DM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "M-SURF: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
+    if (rc == R3DM_OK && hipStreamSynchronize(c->stream) != hipSuccess) lost();
     if (rc != R3DM_OK) for (uint32_t b = 0; b < B; ++b) n_out[b] = 0;
     return rc;
 }
-
-// the detect entry of the MLDB forms: the keypoints through detect_entry, then min(count, cap) rows per image from the one MLDB pass
-static int ak_mldb_entry(r3dm_ctx* c, bool single, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
-                         float* const* keypoints_out, unsigned char* const* descriptors_out, uint32_t cap, uint32_t* n_out)
-{
-    if (cap && !descriptors_out) return R3DM_ERR_INVALID;
-    if (cap && images && B <= 4096) for (uint32_t b = 0; b < B; ++b) if (!descriptors_out[b] || (keypoints_out && !keypoints_out[b])) return R3DM_ERR_INVALID;
-    DetectedBatch det;
-    int rc = detect_entry(c, ak_detect_batch, single, B, images, width, height, threshold, keypoints_out, nullptr, cap, n_out, det);
-    if (rc != R3DM_OK) return rc;
-    std::vector<size_t> first;
-    const unsigned char* rows = nullptr;
-    rc = ak_mldb_pass(c, det, cap, r3dm_host_team(8), first, &rows);
-    for (uint32_t b = 0; rc == R3DM_OK && b < B; ++b) {
-        const size_t nb = first[b + 1] - first[b];
-        if (nb && hipMemcpyAsync(descriptors_out[b], rows + 61 * first[b], nb * 61, hipMemcpyDeviceToHost, c->stream) != hipSuccess) { c->err = "MLDB: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
-    }
-    if (rc == R3DM_OK && hipStreamSynchronize(c->stream) != hipSuccess) { c->err = "MLDB: the descriptors did not reach the host"; rc = R3DM_ERR_HIP; }
-    if (rc != R3DM_OK) for (uint32_t b = 0; b < B; ++b) n_out[b] = 0;
-    return rc;
-}
+static const DescriptorArm& kArmMldb = *descriptor_arm_by_id(R3DM_DESCRIPTOR_MLDB);
+static const DescriptorArm& kArmMsurf = *descriptor_arm_by_id(R3DM_DESCRIPTOR_MSURF);
 
 extern "C" int r3dm_detect_akaze(r3dm_ctx* c, const float* image, uint32_t width, uint32_t height, float threshold,
                                  float* keypoints_out, float* responses_out, uint32_t cap, uint32_t* n_out)
@@ -804,7 +789,7 @@ extern "C" int r3dm_detect_akaze_mldb(r3dm_ctx* c, const float* image, uint32_t 
                                       float* keypoints_out, unsigned char* descriptors_out, uint32_t cap, uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        return ak_mldb_entry(c, true, 1, &image, width, height, threshold, &keypoints_out, &descriptors_out, cap, n_out);
+        return ak_describe_entry(c, kArmMldb, true, 1, &image, width, height, threshold, &keypoints_out, (void* const*)&descriptors_out, cap, n_out);
     });
 }
 
@@ -815,7 +800,7 @@ extern "C" int r3dm_detect_akaze_mldb_batch(r3dm_ctx* c, uint32_t n_images, cons
                                             uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        return ak_mldb_entry(c, false, n_images, images, width, height, threshold, keypoints_out, descriptors_out, cap, n_out);
+        return ak_describe_entry(c, kArmMldb, false, n_images, images, width, height, threshold, keypoints_out, (void* const*)descriptors_out, cap, n_out);
     });
 }
 
@@ -825,7 +810,7 @@ extern "C" int r3dm_detect_akaze_msurf(r3dm_ctx* c, const float* image, uint32_t
                                        float* keypoints_out, float* descriptors_out, uint32_t cap, uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        return ak_msurf_entry(c, true, 1, &image, width, height, threshold, &keypoints_out, &descriptors_out, cap, n_out);
+        return ak_describe_entry(c, kArmMsurf, true, 1, &image, width, height, threshold, &keypoints_out, (void* const*)&descriptors_out, cap, n_out);
     });
 }
 
@@ -834,7 +819,7 @@ extern "C" int r3dm_detect_akaze_msurf_batch(r3dm_ctx* c, uint32_t n_images, con
                                              uint32_t* n_out)
 {
     return r3dm_guarded(c, [&]() -> int {
-        return ak_msurf_entry(c, false, n_images, images, width, height, threshold, keypoints_out, descriptors_out, cap, n_out);
+        return ak_describe_entry(c, kArmMsurf, false, n_images, images, width, height, threshold, keypoints_out, (void* const*)descriptors_out, cap, n_out);
     });
 }
 
@@ -855,19 +840,41 @@ extern "C" int r3dm_detect_akaze_batch(r3dm_ctx* c, uint32_t n_images, const flo
 // that the suite can put to the kernels what images hardly produce (a sample at exactly 360 degrees, windows of equal norm, a singular
 // Hessian, a shift of exactly 1, equal responses across levels, unsorted lists, more than 256 killer chunks, tied MLDB cells, a keypoint
 // on the border at 45 degrees).  What runs is the product's: ak_levels, ak_buffers, ak_level_table, ak_layout,
-// ak_tail_launches, ak_mldb_item / ak_mldb_pairs / ak_mldb_pass above.
+// ak_table_upload, ak_tail_launches, ak_item / ak_mldb_pairs / ak_describe_pass above.
 struct r3dm_dev_ak_level { int32_t w, h, border, sigma_size; float ratio, esigma, psize; };
 constexpr uint32_t kAkDevMaxB = 64, kAkDevMaxList = 1u << 20;
 
-// the level table the product forms for a width x height image: n_levels <= 16 entries
-extern "C" int r3dm_dev_akaze_tail_levels(uint32_t width, uint32_t height, r3dm_dev_ak_level* out, uint32_t* n_levels)
+// the level table the product forms for a width x height image under a border factor: n_levels <= 16 entries
+static int ak_dev_levels(uint32_t width, uint32_t height, float smax, r3dm_dev_ak_level* out, uint32_t* n_levels)
 {
     if (!out || !n_levels || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
-    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, smax);
     if (lv.size() > 16) return R3DM_ERR_UNSUPPORTED;
     for (size_t i = 0; i < lv.size(); ++i) out[i] = {lv[i].w, lv[i].h, lv[i].border, lv[i].sigma_size, lv[i].ratio, lv[i].esigma, lv[i].esigma * 1.5f};
     *n_levels = (uint32_t)lv.size();
     return R3DM_OK;
+}
+// (the detector's table; r3dm_dev_akaze_msurf_levels below gives that of the KAZE descriptors)
+extern "C" int r3dm_dev_akaze_tail_levels(uint32_t width, uint32_t height, r3dm_dev_ak_level* out, uint32_t* n_levels) { return ak_dev_levels(width, height, kAkSmaxDetector, out, n_levels); }
+
+// what the _check entries below share: (width, height) has a level table under `smax` of 1 .. 16 levels (-> lv), n_levels and plane_dims
+// [n_levels][2] agree with it, and planes [B][n_levels][per] are non-null with every value finite
+static bool ak_dev_planes_ok(uint32_t width, uint32_t height, float smax, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
+                             const float* const* planes, uint32_t per, std::vector<AkLevelHost>& lv)
+{
+    if (!plane_dims || !planes || width < 3 || height < 3 || width > 65536u || height > 65536u) return false;
+    lv = ak_levels((int)width, (int)height, smax);
+    const uint32_t nl = (uint32_t)lv.size();
+    if (nl < 1 || nl > 16 || n_levels != nl) return false;
+    for (uint32_t i = 0; i < nl; ++i) if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return false;
+    for (uint32_t b = 0; b < B; ++b)
+        for (uint32_t i = 0; i < nl; ++i)
+            for (uint32_t q = 0; q < per; ++q) {
+                const float* P = planes[((size_t)b * nl + i) * per + q];
+                if (!P) return false;
+                for (size_t k = 0, plane = (size_t)lv[i].w * lv[i].h; k < plane; ++k) if (!std::isfinite(P[k])) return false;
+            }
+    return true;
 }
 
 // What the kernels would mis-read is refused here, before anything touches a device (c may be null): R3DM_OK or R3DM_ERR_INVALID.
@@ -888,22 +895,13 @@ extern "C" int r3dm_dev_akaze_tail_levels(uint32_t width, uint32_t height, r3dm_
 extern "C" int r3dm_dev_akaze_tail_check(uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
                                          const float* const* planes, const uint32_t* n_list, const float* lists)
 {
-    if (!plane_dims || !planes || !n_list || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
-    if (B < 1 || B > kAkDevMaxB) return R3DM_ERR_INVALID;
-    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
+    std::vector<AkLevelHost> lv;
+    if (!n_list || B < 1 || B > kAkDevMaxB || !ak_dev_planes_ok(width, height, kAkSmaxDetector, B, n_levels, plane_dims, planes, 4, lv)) return R3DM_ERR_INVALID;
     const uint32_t nl = (uint32_t)lv.size();
-    if (nl < 1 || nl > 16 || n_levels != nl) return R3DM_ERR_INVALID;
-    for (uint32_t i = 0; i < nl; ++i) if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
     size_t at = 0;
     for (uint32_t b = 0; b < B; ++b)
         for (uint32_t i = 0; i < nl; ++i) {
             const AkLevelHost& e = lv[i];
-            const size_t plane = (size_t)e.w * e.h;
-            for (int q = 0; q < 4; ++q) {
-                const float* P = planes[((size_t)b * nl + i) * 4 + q];
-                if (!P) return R3DM_ERR_INVALID;
-                for (size_t k = 0; k < plane; ++k) if (!std::isfinite(P[k])) return R3DM_ERR_INVALID;
-            }
             const uint32_t n = n_list[(size_t)b * nl + i];
             if (n > kAkDevMaxList || (n && !lists)) return R3DM_ERR_INVALID;
             for (uint32_t k = 0; k < n; ++k) {
@@ -922,7 +920,7 @@ extern "C" int r3dm_dev_akaze_tail_check(uint32_t width, uint32_t height, uint32
 // kernel places the slot arrays; the lists are then copied to where it put them and counts[1] says how long they are -- the state the
 // in-level pruning leaves.  Outputs: n_kp [B]; per image, at the offset of its lists (the sum of the list lengths of the images
 // before it; an image has at most as many keypoints as list entries): recs_out (AkKpRec, 32 bytes), angles_out (theta, cos, sin as
-// ak_mldb_item forms them), desc_out (61 bytes a row, from ak_mldb_pass); dead_out: (dead_lower, dead_upper) of every list entry.
+// ak_item forms them), desc_out (61 bytes a row, from ak_describe_pass); dead_out: (dead_lower, dead_upper) of every list entry.
 extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
                                    const float* const* planes, const uint32_t* n_list, const float* lists,
                                    uint32_t* n_kp, AkKpRec* recs_out, float* angles_out, unsigned char* desc_out, unsigned char* dead_out)
@@ -961,12 +959,9 @@ extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height,
         if ((rc = ak_level_table(p, d)) != R3DM_OK) return rc;
         uint32_t cap = 1;
         for (uint32_t b = 0; b < B; ++b) cap = std::max<uint32_t>(cap, (uint32_t)(first_entry[b + 1] - first_entry[b]));
-        DevBuf &meta = p.tail(T_META), &slots = p.tail(T_SLOTS), &recs = p.tail(T_RECS);
+        if ((rc = ak_table_upload(p, d, cap, true)) != R3DM_OK) return rc;
+        DevBuf &slots = p.tail(T_SLOTS), &recs = p.tail(T_RECS);
         const size_t field = (size_t)B * cap;
-        R3DM_HIP(c, slots.ensure(field * kAkSlotBytes + 256));
-        R3DM_HIP(c, recs.ensure(field * sizeof(AkKpRec) + 256));
-        R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
-        R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
         std::vector<uint32_t> cnt(4 * d.n_lv, 0u);                       // counts of level k = image * nl + level: [0] candidates, [1] list entries
         for (size_t k = 0; k < d.n_lv; ++k) cnt[4 * k] = cnt[4 * k + 1] = n_list[k];
         R3DM_HIP(c, hipMemcpyAsync(d.ld[0].counts, cnt.data(), cnt.size() * 4, hipMemcpyHostToDevice, st));
@@ -1007,13 +1002,13 @@ extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height,
         c->ak_levels_dev = d.d_levels;                                   // what the detector leaves for the MLDB pass
         std::vector<size_t> first;
         const unsigned char* rows = nullptr;
-        if ((rc = ak_mldb_pass(c, det, 0xFFFFFFFFu, 1, first, &rows)) != R3DM_OK) return rc;
+        if ((rc = ak_describe_pass(c, kArmMldb, det, 0xFFFFFFFFu, 1, first, &rows)) != R3DM_OK) return rc;
         for (uint32_t b = 0; b < B; ++b) {
             const size_t n = det.fast[b].size(), o = first_entry[b];
             for (size_t k = 0; k < n; ++k) {
                 recs_out[o + k] = det.fast[b][k];
                 float theta = 0.0f;
-                const AkMldbItem it = ak_mldb_item(b, (uint32_t)nl, lv, det.fast[b][k], &theta);
+                const AkMldbItem it = ak_item<AkMldbItem>(b, (uint32_t)nl, lv, det.fast[b][k], &theta);
                 angles_out[3 * (o + k)] = theta; angles_out[3 * (o + k) + 1] = it.co; angles_out[3 * (o + k) + 2] = it.si;
             }
             if (n) R3DM_HIP(c, hipMemcpyAsync(desc_out + 61 * o, rows + 61 * first[b], n * 61, hipMemcpyDeviceToHost, st));
@@ -1025,17 +1020,9 @@ extern "C" int r3dm_dev_akaze_tail(r3dm_ctx* c, uint32_t width, uint32_t height,
 
 // ---- developer build only: the M-SURF-64 kernel on a caller's Lx / Ly planes of ONE image size and a caller's items, so that the suite
 // can put keypoints on the border at the reach extremes, samples on .5 boundaries, windows without gradient.
-// What runs is the product's: ak_levels with the M-SURF border, ak_buffers, ak_level_table, ak_msurf_launch.
+// What runs is the product's: ak_levels with the M-SURF border, ak_buffers, ak_level_table, ak_table_upload, ak_describe_launch.
 // The level table of the KAZE descriptors for a width x height image, as r3dm_dev_akaze_tail_levels gives the other one.
-extern "C" int r3dm_dev_akaze_msurf_levels(uint32_t width, uint32_t height, r3dm_dev_ak_level* out, uint32_t* n_levels)
-{
-    if (!out || !n_levels || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
-    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, ak_smax(true));
-    if (lv.size() > 16) return R3DM_ERR_UNSUPPORTED;
-    for (size_t i = 0; i < lv.size(); ++i) out[i] = {lv[i].w, lv[i].h, lv[i].border, lv[i].sigma_size, lv[i].ratio, lv[i].esigma, lv[i].esigma * 1.5f};
-    *n_levels = (uint32_t)lv.size();
-    return R3DM_OK;
-}
+extern "C" int r3dm_dev_akaze_msurf_levels(uint32_t width, uint32_t height, r3dm_dev_ak_level* out, uint32_t* n_levels) { return ak_dev_levels(width, height, kAkSmaxMsurf, out, n_levels); }
 
 // What the kernel would mis-read is refused here, before anything touches a device: R3DM_OK or R3DM_ERR_INVALID.
 //   n_levels and plane_dims [n_levels][2] are the M-SURF table's of (width, height); planes [n_levels][2]: Lx, Ly, every value finite;
@@ -1045,28 +1032,18 @@ extern "C" int r3dm_dev_akaze_msurf_levels(uint32_t width, uint32_t height, r3dm
 // border = fRound(R) + 1 with fRound(R) - R = 0.059, 0.088, 0.118 for these s):
 //   a sample lies at position + (l s co + k s si) resp. + (-l s si + k s co) with k, l in [-12, 11], so |sample - position| <=
 //   12 s (|co| + |si|) <= R (1 + 1e-6), and the float sum position + offset adds half an ulp of the position: <= 0.004 for planes of at
-//   most 65536 columns and rows, which the check and ak_msurf_pass hold to (together: e < 5e-3);
+//   most 65536 columns and rows, which the check and ak_msurf_refuse hold to (together: e < 5e-3);
 //   the rows read are y1 = (int)(sample - 0.5 + 0.5) and y2 = (int)(sample + 0.5 + 0.5), columns alike.  position >= border - 1 =
 //   fRound(R) gives sample >= fRound(R) - R - e > 0.05, so y1 >= 0 (and y1 <= y2); position <= dim - border = dim - 1 - fRound(R)
 //   gives sample + 1 <= dim - (fRound(R) - R) + e < dim - 0.05, so y2 <= dim - 1.
-//   On the MLDB table (border from 10 sqrt(2) s) the same keypoints reach 2 sqrt(2) s beyond the plane: ak_msurf_pass refuses it.
+//   On the MLDB table (border from 10 sqrt(2) s) the same keypoints reach 2 sqrt(2) s beyond the plane: ak_msurf_refuse (ak_describe_pass) refuses it.
 extern "C" int r3dm_dev_akaze_msurf_check(uint32_t width, uint32_t height, uint32_t n_levels, const uint32_t* plane_dims, const float* const* planes,
                                           uint32_t n, const AkMsurfItem* items)
 {
-    if (!plane_dims || !planes || (n && !items) || n > kAkDevMaxList || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
-    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, ak_smax(true));
+    std::vector<AkLevelHost> lv;
+    if ((n && !items) || n > kAkDevMaxList || !ak_dev_planes_ok(width, height, kAkSmaxMsurf, 1, n_levels, plane_dims, planes, 2, lv)) return R3DM_ERR_INVALID;
     const uint32_t nl = (uint32_t)lv.size();
-    if (nl < 1 || nl > 16 || n_levels != nl) return R3DM_ERR_INVALID;
-    for (uint32_t i = 0; i < nl; ++i) {
-        if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
-        if (lv[i].sigma_size < 2 || lv[i].sigma_size > 4) return R3DM_ERR_INVALID;                  // (the in-plane argument above)
-        const size_t plane = (size_t)lv[i].w * lv[i].h;
-        for (int q = 0; q < 2; ++q) {
-            const float* P = planes[2 * i + q];
-            if (!P) return R3DM_ERR_INVALID;
-            for (size_t k = 0; k < plane; ++k) if (!std::isfinite(P[k])) return R3DM_ERR_INVALID;
-        }
-    }
+    for (const AkLevelHost& e : lv) if (e.sigma_size < 2 || e.sigma_size > 4) return R3DM_ERR_INVALID;     // (the in-plane argument above)
     for (uint32_t k = 0; k < n; ++k) {
         const AkMsurfItem& it = items[k];
         if (it.level >= nl) return R3DM_ERR_INVALID;
@@ -1089,7 +1066,7 @@ extern "C" int r3dm_dev_akaze_msurf(r3dm_ctx* c, uint32_t width, uint32_t height
     if (n == 0) return R3DM_OK;
     return r3dm_guarded(c, [&]() -> int {
         R3DM_HIP(c, hipSetDevice(c->device));
-        const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, ak_smax(true));
+        const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height, kAkSmaxMsurf);
         const int nl = (int)lv.size();
         AkPass p{c, c->stream, 1, 1, (int)width, (int)height, nl, (size_t)width * height, lv};
         int rc = ak_buffers(p);
@@ -1100,14 +1077,12 @@ extern "C" int r3dm_dev_akaze_msurf(r3dm_ctx* c, uint32_t width, uint32_t height
             R3DM_HIP(c, hipMemcpyAsync(p.Ly(i), planes[2 * i + 1], plane * 4, hipMemcpyHostToDevice, p.st));
         }
         AkDetection d;
-        if ((rc = ak_level_table(p, d)) != R3DM_OK) return rc;
-        R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, p.st));
+        if ((rc = ak_level_table(p, d)) != R3DM_OK || (rc = ak_table_upload(p, d, 0, false)) != R3DM_OK) return rc;
         R3DM_HIP(c, hipStreamSynchronize(p.st));
         c->ak_n_levels = nl;
         c->ak_levels_dev = d.d_levels;
-        const std::vector<AkMsurfItem> its(items, items + n);
         const unsigned char* rows = nullptr;
-        if ((rc = ak_msurf_launch(c, its, &rows)) != R3DM_OK) return rc;
+        if ((rc = ak_describe_launch(c, kArmMsurf, items, n, &rows)) != R3DM_OK) return rc;
         R3DM_HIP(c, hipMemcpy(rows_out, rows, (size_t)n * 256, hipMemcpyDeviceToHost));
         return R3DM_OK;
     });
@@ -1191,12 +1166,8 @@ static int ak_dev_head_run(AkPass& p, float threshold, uint32_t* counts_out, flo
     if (rc != R3DM_OK) return rc;
     if (d.bound == 0 || d.bound * B >= (1ull << 31)) { c->err = "developer head entry: more slots than the arrays index"; return R3DM_ERR_UNSUPPORTED; }
     const uint32_t cap = (uint32_t)d.bound;
-    DevBuf &meta = p.tail(T_META), &slots = p.tail(T_SLOTS);
-    const size_t field = (size_t)B * cap;
-    R3DM_HIP(c, slots.ensure(field * kAkSlotBytes + 256));
-    R3DM_HIP(c, hipMemsetAsync(meta.p, 0, d.rows_total * 8 + d.n_lv * 16, st));
-    R3DM_HIP(c, hipMemcpyAsync(d.d_levels, d.ld.data(), d.n_lv * sizeof(AkLevelDev), hipMemcpyHostToDevice, st));
-    R3DM_HIP(c, ak_head_launches(st, d.d_levels, nl, (int)B, d.tiles, d.n_tiles, d.max_rows, slots.as<unsigned char>(), cap, d.d_bmeta, threshold));
+    if ((rc = ak_table_upload(p, d, cap, false)) != R3DM_OK) return rc;
+    R3DM_HIP(c, ak_head_launches(st, d.d_levels, nl, (int)B, d.tiles, d.n_tiles, d.max_rows, p.tail(T_SLOTS).as<unsigned char>(), cap, d.d_bmeta, threshold));
     std::vector<AkLevelDev> dl(d.n_lv);
     std::vector<uint32_t> cnt(4 * d.n_lv, 0u);
     d.bm.assign(B, AkBatchMeta{});
@@ -1278,20 +1249,8 @@ extern "C" int r3dm_dev_akaze_head(r3dm_ctx* c, uint32_t B, const float* const* 
 extern "C" int r3dm_dev_akaze_extrema_check(uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
                                             const float* const* ldet)
 {
-    if (!plane_dims || !ldet || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
-    if (B < 1 || B > kAkDevMaxB) return R3DM_ERR_INVALID;
-    const std::vector<AkLevelHost> lv = ak_levels((int)width, (int)height);
-    const uint32_t nl = (uint32_t)lv.size();
-    if (nl < 1 || nl > 16 || n_levels != nl) return R3DM_ERR_INVALID;
-    for (uint32_t i = 0; i < nl; ++i) if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
-    for (uint32_t b = 0; b < B; ++b)
-        for (uint32_t i = 0; i < nl; ++i) {
-            const float* P = ldet[(size_t)b * nl + i];
-            if (!P) return R3DM_ERR_INVALID;
-            const size_t plane = (size_t)lv[i].w * lv[i].h;
-            for (size_t k = 0; k < plane; ++k) if (!std::isfinite(P[k])) return R3DM_ERR_INVALID;
-        }
-    return R3DM_OK;
+    std::vector<AkLevelHost> lv;
+    return B >= 1 && B <= kAkDevMaxB && ak_dev_planes_ok(width, height, kAkSmaxDetector, B, n_levels, plane_dims, ldet, 1, lv) ? R3DM_OK : R3DM_ERR_INVALID;
 }
 
 // Lx, Ly and Lt of every level are zero; counts_out and lists_out as r3dm_dev_akaze_head's.

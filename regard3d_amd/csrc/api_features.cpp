@@ -97,11 +97,9 @@ struct BatchRows { const unsigned char* dev = nullptr; size_t row_bytes = 0; };
 // what the context's two switches cannot do together (r3dm_set_descriptor_arm): refused before anything is computed
 int descriptor_arm_check(r3dm_ctx* c)
 {
-    if (c->descriptor_arm == R3DM_DESCRIPTOR_LIOP || c->detector_arm != R3DM_DETECTOR_AKAZE) return R3DM_OK;
-    if (c->descriptor_arm == R3DM_DESCRIPTOR_MLDB)
-        c->err = "descriptor arm R3DM_DESCRIPTOR_MLDB is not served with the classic detector R3DM_DETECTOR_AKAZE (MLDB reads the Fast-A-KAZE level planes)";
-    else
-        c->err = "descriptor arm R3DM_DESCRIPTOR_MSURF is not served with the classic detector R3DM_DETECTOR_AKAZE (M-SURF-64 reads the Fast-A-KAZE level planes)";
+    const DescriptorArm& arm = *descriptor_arm_by_id(c->descriptor_arm);
+    if (!arm.level_planes || c->detector_arm != R3DM_DETECTOR_AKAZE) return R3DM_OK;
+    c->err = std::string("descriptor arm ") + arm.macro + " is not served with the classic detector R3DM_DETECTOR_AKAZE (" + arm.name + " reads the Fast-A-KAZE level planes)";
     return R3DM_ERR_UNSUPPORTED;
 }
 
@@ -136,14 +134,14 @@ void keypoints_and_maps(const DetectedBatch& det, uint32_t B, int host_team, boo
 // for.  Deferred: they travel behind the kernel, only the writer thread waits (ev_desc)
 int describe_batch(r3dm_ctx* c, const DetectedBatch& det, uint32_t width, uint32_t height, const BatchKeypoints& K, bool deferred, int host_team, BatchRows& rows)
 {
-    const bool mldb = c->descriptor_arm == R3DM_DESCRIPTOR_MLDB, msurf = c->descriptor_arm == R3DM_DESCRIPTOR_MSURF;
-    rows.row_bytes = mldb ? 61 : msurf ? 64 * 4 : 144 * 4;
+    const DescriptorArm& arm = *descriptor_arm_by_id(c->descriptor_arm);
+    rows.row_bytes = arm.row_bytes;
     const size_t out_bytes = K.total() * rows.row_bytes;
     { const int wrc_prev = features_files_join(c); if (wrc_prev != R3DM_OK) return wrc_prev; }      // the previous batch's writer still reads pin_desc
     R3DM_HIP(c, c->pin_desc.ensure(out_bytes));
-    if (mldb || msurf) {
+    if (arm.level_planes) {
         std::vector<size_t> first;
-        const int rc = (msurf ? ak_msurf_pass : ak_mldb_pass)(c, det, 0xFFFFFFFFu, host_team, first, &rows.dev);
+        const int rc = ak_describe_pass(c, arm, det, 0xFFFFFFFFu, host_team, first, &rows.dev);
         if (rc != R3DM_OK) return rc;
     } else {
         const int rc = liop_pass(c, det.grays_dev, width, height, K.M6.data(), K.img_of.data(), (uint32_t)K.total(), false);
@@ -278,7 +276,7 @@ int extract_features_batch_impl(r3dm_ctx* c, uint32_t B, const float* const* gra
     struct InFlight { std::atomic<int>& n; int mine; InFlight(std::atomic<int>& a) : n(a), mine(a.fetch_add(1) + 1) {} ~InFlight() { n.fetch_sub(1); } } in_flight(batches_in_flight);
     const int host_team = r3dm_host_team(8, std::max(2, in_flight.mine));
     BatchKeypoints K;
-    keypoints_and_maps(det, B, host_team, c->descriptor_arm == R3DM_DESCRIPTOR_LIOP, K);
+    keypoints_and_maps(det, B, host_team, !descriptor_arm_by_id(c->descriptor_arm)->level_planes, K);
     const bool deferred = c->defer_files;
     BatchRows rows;
     if (K.total() && (rc = describe_batch(c, det, width, height, K, deferred, host_team, rows)) != R3DM_OK) return rc;
@@ -497,7 +495,7 @@ extern "C" int r3dm_set_keypoint_detector(r3dm_ctx* c, int arm)
 extern "C" int r3dm_set_descriptor_arm(r3dm_ctx* c, int arm)
 {
     if (!c) return R3DM_ERR_INVALID;
-    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB && arm != R3DM_DESCRIPTOR_MSURF) { c->err = "r3dm_set_descriptor_arm: unknown arm " + std::to_string(arm); return R3DM_ERR_INVALID; }
+    if (!descriptor_arm_by_id(arm)) { c->err = "r3dm_set_descriptor_arm: unknown arm " + std::to_string(arm); return R3DM_ERR_INVALID; }
     c->descriptor_arm = arm;
     return R3DM_OK;
 }
@@ -525,7 +523,7 @@ extern "C" int r3dm_multi_set_keypoint_detector(r3dm_multi* m, int arm)
 
 extern "C" int r3dm_multi_set_descriptor_arm(r3dm_multi* m, int arm)
 {
-    if (arm != R3DM_DESCRIPTOR_LIOP && arm != R3DM_DESCRIPTOR_MLDB && arm != R3DM_DESCRIPTOR_MSURF) return R3DM_ERR_INVALID;
+    if (!descriptor_arm_by_id(arm)) return R3DM_ERR_INVALID;
     return multi_each(m, [&](r3dm_ctx* c) { return r3dm_set_descriptor_arm(c, arm); });
 }
 

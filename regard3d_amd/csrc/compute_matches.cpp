@@ -3,6 +3,7 @@
 // load regions -> exhaustive pairs -> match -> save matches.putative.txt -> F filter -> save matches.f.txt.
 #include "../../include/r3d_compute_matches.hpp"
 #include "feat_text.hpp"
+#include "descriptor_arms.hpp"
 
 #include <charconv>
 #include <chrono>
@@ -201,8 +202,8 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     }
     // the regions type names the descriptor arm: LIOP (float x 144) or the MLDB-486 rows of the Fast-A-KAZE detector (61 bytes)
     // or its M-SURF-64 rows (float x 64)
-    const bool mldb = dtype_ == R3DM_BIN && dim_ == 61, msurf = dtype_ == R3DM_F32 && dim_ == 64;
-    if (!mldb && !msurf && (dtype_ != R3DM_F32 || dim_ != 144)) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
+    const DescriptorArm* arm = descriptor_arm_by_type(dtype_, dim_);
+    if (!arm) { errorMessage_ = "the features stage writes LIOP regions (float x 144); setRegionsType disagrees"; return false; }
     if (!feat_multi_) {
         std::vector<int> ids;
         for (int d : devices_) for (int k = 0; k < std::max(1, feat_conc_); ++k) ids.push_back(d);
@@ -211,7 +212,7 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     }
     const int n_ctx = r3dm_multi_num_devices(feat_multi_);
     (void)r3dm_multi_set_keypoint_detector(feat_multi_, dl[0] == "AKAZE" ? R3DM_DETECTOR_AKAZE : R3DM_DETECTOR_FAST_AKAZE);
-    (void)r3dm_multi_set_descriptor_arm(feat_multi_, mldb ? R3DM_DESCRIPTOR_MLDB : msurf ? R3DM_DESCRIPTOR_MSURF : R3DM_DESCRIPTOR_LIOP);      // (MLDB / M-SURF with "AKAZE": refused by name by the features call below)
+    (void)r3dm_multi_set_descriptor_arm(feat_multi_, arm->id);      // (MLDB / M-SURF with "AKAZE": refused by name by the features call below)
     // the sink carries no scales: while preemptive matching is on, every view is registered from its files (setPreemptiveMatching)
     const bool direct = direct_registration_ && !preemptive_on_;
     (void)r3dm_multi_set_features_sink(feat_multi_, direct ? &R3DComputeMatches::features_sink : nullptr, this);
@@ -358,7 +359,7 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
 {
     statistics_ = R3DComputeMatchesStatistics();
     phases_ = PhaseTimes();
-    phases_.descriptor_arm = dtype_ == R3DM_BIN && dim_ == 61 ? R3DM_DESCRIPTOR_MLDB : dtype_ == R3DM_F32 && dim_ == 64 ? R3DM_DESCRIPTOR_MSURF : R3DM_DESCRIPTOR_LIOP;
+    { const DescriptorArm* arm = descriptor_arm_by_type(dtype_, dim_); phases_.descriptor_arm = arm ? arm->id : R3DM_DESCRIPTOR_LIOP; }   // (no arm's type: the features stage refuses it)
     if (!ctx_ && !multi_) return false;
     const double t_begin = wall_ms();
     // the feature files of this call are complete when it returns, however it returns (r3dm_set_deferred_feature_files)
@@ -724,9 +725,8 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         stage.setMutualMatching((flags & R3DM_STAGE_MUTUAL_MATCHING) != 0);
         stage.setPreemptiveMatching((flags & R3DM_STAGE_PREEMPTIVE_MATCHING) != 0);
-        if (flags & R3DM_STAGE_DESCRIPTOR_MLDB) stage.setRegionsType(R3DM_BIN, 61);
-        else if (flags & R3DM_STAGE_DESCRIPTOR_MSURF) stage.setRegionsType(R3DM_F32, 64);
-        else stage.setRegionsType(R3DM_F32, 144);
+        const DescriptorArm& arm = *descriptor_arm_by_id((flags & R3DM_STAGE_DESCRIPTOR_MLDB) ? R3DM_DESCRIPTOR_MLDB : (flags & R3DM_STAGE_DESCRIPTOR_MSURF) ? R3DM_DESCRIPTOR_MSURF : R3DM_DESCRIPTOR_LIOP);
+        stage.setRegionsType(arm.dtype, arm.dim);
         r3d_amd::R3DFParams params;
         params.keypointDetectorList_ = {(flags & R3DM_STAGE_DETECTOR_AKAZE) ? "AKAZE" : "Fast-AKAZE"};
         params.threshold_ = threshold;

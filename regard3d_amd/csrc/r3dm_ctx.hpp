@@ -11,15 +11,18 @@
 //                     (one workgroup per pair; kernels_filter.hip F / H, kernels_filter_e.hip E), kernels_filter_coop.hip (long pairs)
 //   api_tracks.cpp    feature tracks of a match graph (r3dm_build_tracks), the track filter applied to the graph, r3dm_tracks_in_pair
 //   api_akaze.cpp     the frame of both detector arms (checks, upload, INTER_AREA tables, statistics tail, DetectedBatch's writer) and the
-//                     Fast-A-KAZE arm: its pass in phases, MLDB, M-SURF-64, r3dm_detect_akaze / _mldb / _mldb_batch / _msurf / _msurf_batch / _batch,
+//                     Fast-A-KAZE arm: its pass in phases, the one pass of the level-plane descriptors (ak_describe_pass: MLDB, M-SURF-64)
+//                     and their one entry, r3dm_detect_akaze / _mldb / _mldb_batch / _msurf / _msurf_batch / _batch,
 //                     r3dm_gray_from_bgr8
 //   api_akaze_classic.cpp   the classic A-KAZE arm's launch sequence on that frame, r3dm_detect_akaze_classic / _batch
+//   descriptor_arms.hpp     the one table of the descriptor arms (host only): id, names, regions type, row bytes, level table
 //   api_liop.cpp      LIOP: the patch geometry, the one pass from keypoints to descriptors (liop_pass), its two entries
 //   api_features.cpp  the features work item: .feat / .desc files, the features batch in phases (detect, keypoints and maps, LIOP pass,
 //                     delivery, outputs), the work list of a multi-context, the setters
 #pragma once
 
 #include "r3dm_internal.hpp"
+#include "descriptor_arms.hpp"
 
 #include <sched.h>
 #include <sys/resource.h>
@@ -404,10 +407,6 @@ struct AkLevelHost {
     float esigma, etime, ratio;
 };
 
-// border factor of the Fast arm's level table (Allocate_Memory_Evolution, fast-akaze AKAZEFeatures.cpp:78-84,105,112: border =
-// fRound(smax sigma_size) + 1): 10 sqrt(2) under MLDB -- the table of the detector, LIOP and MLDB entries -- and 12 sqrt(2) under the
-// KAZE descriptors, i.e. M-SURF-64, whose samples reach that far
-inline float ak_smax(bool msurf) { return (msurf ? 12.0f : 10.0f) * sqrtf(2.0f); }
 // angle of a Fast-arm keypoint: getAngleV2(maxX, maxY) (fast-akaze utils.h:11-19: atan2f of the host libm, + 2 pi when negative)
 inline float ak_theta(const AkKpRec& r)
 {
@@ -431,7 +430,7 @@ inline float ak_angle_deg(float ang)
 struct DetectedBatch {
     std::vector<std::vector<AkKpRec>> fast;            // Fast arm: per image, the survivors in the reference's order (level, list)
     std::vector<AkLevelHost> fast_levels;              //           the evolution levels of this image size
-    float fast_smax = 0.0f;                            //           ... and the border factor they were cut with (ak_smax)
+    float fast_smax = 0.0f;                            //           ... and the border factor they were cut with (ak_smax, descriptor_arms.hpp)
     std::vector<std::vector<AcOut>> classic;           // classic arm: per image, the slots that survive, in slot order
     const float* grays_dev = nullptr;                  // the B gray planes the detector left on the device (read-only for it)
     size_t count(uint32_t b) const { return fast.empty() ? classic[b].size() : fast[b].size(); }
@@ -466,14 +465,14 @@ int detect_area_tabs(r3dm_ctx* c, DevBuf& buf, const std::vector<AkLevelHost>& l
 // the tail of a pass: kernel time (ev0 .. ev1) and wall time into the statistics, the pass into the totals
 void detect_finish(r3dm_ctx* c, uint32_t B, double t_call, uint64_t n_keypoints, double algorithmic_bytes);
 
-// ---- MLDB-486 of a Fast-arm pass (api_akaze.cpp): one launch over the first min(count, cap) keypoints of every image of `det`, which
-// must be the context's last detector pass.  first: B + 1 row offsets; *rows_dev: the rows, 61 bytes each, image b's at + 61 first[b]
-// (null when there is no keypoint), valid until the context's next detector or MLDB pass.  Bracketed by ev0 / ev1 and waited for;
-// host_team threads share the item loop (cos / sin of every keypoint's angle, host libm)
-int ak_mldb_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev);
-// ---- M-SURF-64 of a Fast-arm pass, the same way: rows of 64 floats, image b's at + 256 first[b] bytes.  `det` must come from
-// ak_detect_batch_msurf: a pass on the other level table is refused (R3DM_ERR_INVALID), its borders do not hold M-SURF's reads in
-int ak_msurf_pass(r3dm_ctx* c, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first, const unsigned char** rows_dev);
+// ---- the level-plane descriptors of a Fast-arm pass, MLDB-486 and M-SURF-64 (api_akaze.cpp): one launch of `arm`'s kernel over the first
+// min(count, cap) keypoints of every image of `det`, which must be the context's last detector pass and, for M-SURF, cut on the arm's own
+// level table (else R3DM_ERR_INVALID: the other table's borders do not hold its reads in).  first: B + 1 row offsets; *rows_dev: the
+// rows, arm.row_bytes each, image b's at + arm.row_bytes first[b] (null when there is no keypoint), valid until the context's next
+// detector or descriptor pass.  Bracketed by ev0 / ev1 and waited for; host_team threads share the item loop (cos / sin of every
+// keypoint's angle, host libm)
+int ak_describe_pass(r3dm_ctx* c, const DescriptorArm& arm, const DetectedBatch& det, uint32_t cap, int host_team, std::vector<size_t>& first,
+                     const unsigned char** rows_dev);
 
 // ---- LIOP (api_liop.cpp)
 // 2x3 inverse map of one keypoint's patch (x, y, size, angle in degrees)

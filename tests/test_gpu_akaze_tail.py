@@ -1,6 +1,6 @@
 """The Fast-A-KAZE tail on the GPU, on planes and lists built for its edges (tests/akaze_tail_cases.py): the
 developer build's r3dm_dev_akaze_tail runs the PRODUCT's code -- ak_tail_launches (list ranges, both cross-level passes, refinement +
-orientation, compaction), the host's angle and item formation and ak_mldb_pass, the functions the detector calls -- on the caller's
+orientation, compaction), the host's angle and item formation and ak_describe_pass, the functions the detector calls -- on the caller's
 planes and lists.  The reference of every case is oracle/akaze.c's orc_akaze_tail alone, and the comparison is bit for bit: the count,
 the seven record fields, theta, cos and sin, the descriptor rows, and the dead_lower / dead_upper flags of every list entry.  Every case
 also rides in a call of B = 3 with an empty image in the middle: the batch equals the single calls image for image.
@@ -101,7 +101,7 @@ def test_batch_equals_the_single_calls(batch, tmp_path_factory):
 
 
 def test_product_detector_still_equals_the_oracle():
-    """the product library, in this process: r3dm_detect_akaze_mldb calls ak_tail_launches and ak_mldb_item, the functions the developer
+    """the product library, in this process: r3dm_detect_akaze_mldb calls ak_tail_launches and ak_item, the functions the developer
     entry shares with it -- keypoints and descriptors of one scene of the MLDB arm's cases against the oracle's detector"""
     import mldb_arm_cases as M
     from regard3d_amd import api

@@ -1,6 +1,6 @@
 """The M-SURF-64 kernel on the GPU, on planes and items built for its edges (tests/msurf_cases.py: kernel_cases):
 the developer build's r3dm_dev_akaze_msurf runs the PRODUCT's kernel (ak_levels with the M-SURF border, ak_buffers, ak_level_table,
-ak_msurf_launch) on the caller's Lx / Ly planes and items, after r3dm_dev_akaze_msurf_check has accepted them.  The reference of every case
+ak_describe_launch) on the caller's Lx / Ly planes and items, after r3dm_dev_akaze_msurf_check has accepted them.  The reference of every case
 is the serial restatement tests/cpp/msurf_restatement.cpp in its ak_expf form, and the comparison is bit for bit, a row of a window
 without gradient as "all NaN".
 
@@ -85,7 +85,7 @@ def test_the_cases_are_the_ones_the_kernel_can_go_wrong_on():
 
 
 def test_product_entry_still_equals_the_reference_chain(ctx):
-    """the product library, in this process: r3dm_detect_akaze_msurf runs ak_msurf_launch and the kernel the developer entry shares with it"""
+    """the product library, in this process: r3dm_detect_akaze_msurf runs ak_describe_launch and the kernel the developer entry shares with it"""
     thr, ims, ref = S.batch_refs((120, 160))
     kps, rows = ctx.detect_akaze_msurf_batch(ims[:1], thr, single=True)[0]
     assert len(kps) >= 15 and kps.tobytes() == ref[0]["kps"].tobytes() and S.same_rows(rows, ref[0]["rows"])

@@ -7,8 +7,8 @@ and the whole stage from pixels (r3dm_stage_run, 3 batches of 8 in flight) on N 
                                   [--parent-lib PATH] [--stage-images 24] [--out FILE]
 Every leg runs in a process of its own (one library per process) and the legs ALTERNATE over --rounds rounds, so that a drift of the
 machine shows as spread inside a leg instead of as a difference between legs.  --parent-lib names a libr3dm.so built from the parent
-commit: its `liop` leg runs between this tree's legs -- the LIOP path must not move beyond the spread, which the summary states (min ..
-max of the rounds' medians).  A leg's figure is the median of --reps calls after one warm-up call, host clock around calls that end in a
+commit: its legs (`mldb` too when that library exports the arm) run between this tree's -- they must not move beyond the spread, which
+the summary states (min .. max of the rounds' medians).  A leg's figure is the median of --reps calls after one warm-up call, host clock around calls that end in a
 stream synchronise, divided by the images of the batch.  One JSON line per leg and round, then a summary line.  The tool does not time
 single kernels: run a leg under `rocprofv3 --kernel-trace --stats` for that split (tools/rocprof_summary.py)."""
 import argparse
@@ -25,6 +25,7 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 THIS_LIB = os.path.join(ROOT, "regard3d_amd", "libr3dm.so")
+from regard3d_amd import api        # (the arm ids: importing the package loads no library, so a leg on --parent-lib still holds that one alone)
 
 
 def _photos(n, h, w):
@@ -45,7 +46,7 @@ def leg_batch(a):
     if L.r3dm_create(0, C.byref(ctx)) != 0:
         raise SystemExit("r3dm_create failed: no gfx950 GPU")
     L.r3dm_last_error.restype = C.c_char_p
-    if a.leg == "mldb" and L.r3dm_set_descriptor_arm(ctx, 1) != 0:
+    if a.leg == "mldb" and L.r3dm_set_descriptor_arm(ctx, api.DESCRIPTOR_ARMS["MLDB"]) != 0:
         raise SystemExit("r3dm_set_descriptor_arm failed")
     ip = (C.c_void_p * B)(*[im.data_ptr() for im in imgs])
     none = (C.c_char_p * B)()
@@ -71,7 +72,6 @@ def leg_batch(a):
 
 
 def leg_stage(a):
-    from regard3d_amd import api
     N, (h, w) = a.stage_images, a.size
     imgs, K = _photos(N, h, w)
     views = [dict(id=k, width=w, height=h, basename=f"img{k:04d}", gray=imgs[k], focal_px=K[0, 0], ppx=K[0, 2], ppy=K[1, 2]) for k in range(N)]
@@ -123,7 +123,11 @@ def main():
             if ln.startswith("{"):
                 print(ln, flush=True); lines.append(json.loads(ln))
 
-    legs = [("detect", THIS_LIB, "this")] + ([("liop", a.parent_lib, "parent")] if a.parent_lib else []) + [("liop", THIS_LIB, "this"), ("mldb", THIS_LIB, "this")]
+    legs = []
+    for leg in ("detect", "liop", "mldb"):
+        if a.parent_lib and (leg != "mldb" or b"r3dm_detect_akaze_mldb_batch" in open(a.parent_lib, "rb").read()):     # (a parent from before the arm lacks it)
+            legs.append((leg, a.parent_lib, "parent"))
+        legs.append((leg, THIS_LIB, "this"))
     for _ in range(a.rounds):
         for leg, lib, tag in legs:
             child(leg, lib, tag)

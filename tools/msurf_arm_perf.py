@@ -9,8 +9,8 @@ operations / s it amounts to) and the matcher's rate on two such views as f32[64
     python tools/msurf_arm_perf.py [--images 8] [--size 3000 4000] [--threshold 0.001] [--reps 5] [--rounds 3] [--parent-lib PATH] [--out FILE]
 Every leg runs in a process of its own (one library per process) and the legs ALTERNATE over --rounds rounds, so that a drift of the
 machine shows as spread inside a leg instead of as a difference between legs.  --parent-lib names a libr3dm.so built from the parent
-commit: its detect / liop / mldb legs run between this tree's -- those three must not move beyond the spread, which the summary states
-(min .. max of the rounds' medians).  A leg's figure is the median of --reps calls after one warm-up call, host clock around calls that
+commit: its detect / liop / mldb legs -- and its msurf leg when that library exports the arm -- run between this tree's; they must not move
+beyond the spread, which the summary states (min .. max of the rounds' medians).  A leg's figure is the median of --reps calls after one warm-up call, host clock around calls that
 end in a stream synchronise, divided by the images of the batch.  One JSON line per leg and round, then a summary line.  The tool does
 not time single kernels beyond the descriptor launch's event time: run `--leg msurf` under `rocprofv3 --kernel-trace --stats` for that
 (tools/rocprof_summary.py)."""
@@ -26,7 +26,8 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 THIS_LIB = os.path.join(ROOT, "regard3d_amd", "libr3dm.so")
-ARM = {"liop": 0, "mldb": 1, "msurf": 3}
+from regard3d_amd import api        # (the arm ids: importing the package loads no library, so a leg on --parent-lib still holds that one alone)
+ARM = {name.lower(): arm_id for name, arm_id in api.DESCRIPTOR_ARMS.items()}
 # per keypoint (kernels_akaze.hip, ak_msurf_kernel): 16 x 81 samples, each 8 gathered floats and one ak_expf; + 16 subregion weights
 SAMPLES = 16 * 81
 GATHER_BYTES = SAMPLES * 8 * 4
@@ -43,7 +44,7 @@ def _photos(n, h, w):
 
 
 def leg_batch(a):
-    """detect / liop / mldb / msurf through the C ABI of the library at a.lib (plain ctypes: the parent's library lacks the new arm)"""
+    """detect / liop / mldb / msurf through the C ABI of the library at a.lib (plain ctypes: api.Context would load this tree's library)"""
     imgs, _ = _photos(a.images, *a.size)
     B, (h, w) = a.images, a.size
     L = C.CDLL(a.lib)
@@ -67,18 +68,23 @@ def leg_batch(a):
             raise SystemExit(f"{a.leg}: rc {rc}: {L.r3dm_last_error(ctx).decode()}")
 
     call()                      # warm-up: work buffers, code objects
-    ms = []
+    ms, kern, parts, st = [], [], [], api.Stats()
     for _ in range(a.reps):
         t = time.perf_counter(); call(); ms.append((time.perf_counter() - t) * 1e3 / B)
+        L.r3dm_get_stats(ctx, C.byref(st)); kern.append(st.ms_liop_kernel)      # the descriptor launch's event time, whichever arm (outside the timed call)
+        parts.append((st.ms_detect, st.ms_liop_wall, st.ms_feature_files))      # the call's host phases: detector, keypoints + descriptor pass + rows to the host, delivery
     L.r3dm_destroy.restype = None
     L.r3dm_destroy(ctx)
     print(json.dumps(dict(leg=a.leg, lib=a.tag, images=B, image=[h, w], threshold=a.threshold, keypoints=int(sum(n)),
-                          ms_per_image=round(statistics.median(ms), 3), ms_per_image_min=round(min(ms), 3), ms_per_image_max=round(max(ms), 3))), flush=True)
+                          ms_per_image=round(statistics.median(ms), 3), ms_per_image_min=round(min(ms), 3), ms_per_image_max=round(max(ms), 3),
+                          ms_descriptor_kernel=None if a.leg == "detect" else round(statistics.median(kern), 3),
+                          ms_detect_wall=round(statistics.median(p[0] for p in parts), 3),
+                          ms_descriptor_wall=None if a.leg == "detect" else round(statistics.median(p[1] for p in parts), 3),
+                          ms_delivery_wall=None if a.leg == "detect" else round(statistics.median(p[2] for p in parts), 3))), flush=True)
 
 
 def leg_split(a):
     """the M-SURF batch's parts from r3dm_stats, and the launch against what it moves and computes"""
-    from regard3d_amd import api
     imgs, _ = _photos(a.images, *a.size)
     ctx = api.Context(0)
     ctx.set_descriptor_arm("MSURF")
@@ -105,7 +111,6 @@ def leg_split(a):
 def leg_match(a):
     """r3dm_match_pairs on two views: the M-SURF rows of two photographs as f32[64], and LIOP f32[144] of the SAME keypoints"""
     import numpy as np
-    from regard3d_amd import api
     imgs, _ = _photos(2, *a.size)
     ctx = api.Context(0)
     res = ctx.detect_akaze_msurf_batch(imgs, a.threshold)
@@ -155,11 +160,10 @@ def main():
                 print(ln, flush=True); lines.append(json.loads(ln))
 
     legs = []
-    for leg in ("detect", "liop", "mldb"):
-        if a.parent_lib:
+    for leg in ("detect", "liop", "mldb", "msurf"):
+        if a.parent_lib and (leg != "msurf" or b"r3dm_detect_akaze_msurf" in open(a.parent_lib, "rb").read()):     # (a parent from before the arm lacks the symbol)
             legs.append((leg, a.parent_lib, "parent"))
         legs.append((leg, THIS_LIB, "this"))
-    legs.append(("msurf", THIS_LIB, "this"))
     for _ in range(a.rounds):
         for leg, lib, tag in legs:
             child(leg, lib, tag)
@@ -169,6 +173,9 @@ def main():
     for leg, _, tag in legs:
         v = [ln["ms_per_image"] for ln in lines if ln["leg"] == leg and ln.get("lib") == tag]
         summary[f"{leg}_{tag}"] = dict(median=round(statistics.median(v), 3), min=min(v), max=max(v), rounds=len(v))
+        k = [ln["ms_descriptor_kernel"] for ln in lines if ln["leg"] == leg and ln.get("lib") == tag and ln.get("ms_descriptor_kernel") is not None]
+        if k:
+            summary[f"{leg}_{tag}"]["descriptor_kernel_ms"] = dict(median=round(statistics.median(k), 3), min=min(k), max=max(k))
     tail = json.dumps(dict(summary=summary, unit="ms per image"))
     print(tail, flush=True)
     if a.out:
