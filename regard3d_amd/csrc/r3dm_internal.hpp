@@ -493,6 +493,21 @@ inline hipError_t dispatch_kl(uint32_t k, F&& f)
 }
 inline bool has_tensor_kernel(uint32_t G) { return dispatch_g(G, [](auto) { return hipSuccess; }) == hipSuccess; }
 
+// ---- launch of a kernel whose dynamic LDS may pass the 64 KiB a kernel gets by default (the KGraph, HNSW and MRPT searches: their
+// visited sets grow with the view).  The limit is raised on the kernel that is launched: one name, so the two cannot differ.
+#if defined(__HIP_DEVICE_COMPILE__) || defined(__HIPCC__)
+template <class... KArgs, class... Args>
+inline hipError_t launch_with_lds(void (*kernel)(KArgs...), dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args)
+{
+    if (lds > 64 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
+    return hipGetLastError();
+}
+#endif
+
 // ---- launchers implemented in the .hip files (host side) ----
 // registration of one float view (kernels_match.hip: stage_view_kernel): raw descriptors -> fragment-order tiles + norms + statistics
 // (+ the row-major f32 copy when `rows` is given), the positions copied / entered into the position-class table by role blocks of the

@@ -7,7 +7,8 @@ What each arm is compared with, rows AND distance bits:
   KGraph  the CPU restatement's orc_kgraph_search(K = k) on the exact index and the start rows of orc_kgraph_seeds
   MRPT    a numpy model of Mrpt::query(q, k, votes) + ArrayMatcher_mrpt's retry in this file, pinned at k = 2 to orc_mrpt_knn2
 The shapes are the smallest at which these kernels can still go wrong (600-row views, 128 rows = the smallest indexed view, query
-counts that leave a workgroup partly empty); every reference is computed once per session.
+counts that leave a workgroup partly empty, and one MRPT view of 12,288 rows: the smallest round size whose query launch needs more
+than 64 KiB of LDS); every reference is computed once per session.
 """
 import ctypes as C
 import functools
@@ -307,6 +308,67 @@ def test_mrpt_equals_the_model(ctx, oracle, votes, k):
     assert np.array_equal(gi, mi)
     assert np.array_equal(_bits(gd), _bits(md))
     assert ((gi == -1).all(axis=1) == (cls == 2)).all() and ((gd == -1.0).all(axis=1) == (cls == 2)).all()
+
+
+# ---- MRPT above 64 KiB of LDS: the branch of the launchers' shared helper (r3dm_internal.hpp: launch_with_lds) that raises the limit
+# of dynamic LDS on the kernel it launches.  The views above have 600 rows (14,976 B per wavefront at 8,192 rows: 59,904 B a workgroup),
+# so nothing else in the suite takes it.  KGraph and HNSW take theirs only above 131,072 and about 107,000 rows of a view, too large for
+# this suite: they are covered by sharing the helper.
+MRPT_BIG_ROWS, MRPT_BIG_QUERIES, MRPT_BIG_VOTES = 12288, 97, 4       # 97 queries: the last workgroup of four wavefronts holds one
+
+
+def mrpt_launch_lds(n, n_trees, depth, votes):
+    """launch_mrpt_query's LDS bytes for one index view of n rows (kernels_mrpt.hip; elected_cap: api_mrpt.cpp, mrpt_elected_cap)"""
+    max_leaf = n // (1 << depth) + 1
+    elected_cap = min(n, n_trees * max_leaf // max(votes - 1 if votes > 1 else 1, 1)) + 64
+    pool_pad = (n_trees * depth + 63) // 64 * 64
+    per_wave = (pool_pad * 4 + 256 * 4 + 8 + elected_cap * 4 + (n + 3) // 4 * 4 + 15) // 16 * 16
+    waves = 4
+    while waves > 1 and per_wave * waves > 150 * 1024:
+        waves >>= 1
+    return per_wave * waves
+
+
+@functools.lru_cache(maxsize=None)
+def _mrpt_big_views():
+    d0, d1 = _views("sift", MRPT_BIG_ROWS, 47)
+    return d0, np.ascontiguousarray(d1[:MRPT_BIG_QUERIES])
+
+
+@functools.lru_cache(maxsize=None)
+def _mrpt_big_index(oracle_mod):
+    d0, _ = _mrpt_big_views()
+    mp = api.MrptParams.preset()
+    assert (mp.n_trees, mp.depth) == (26, 6)
+    return oracle_mod.mrpt_build(d0, mp.n_trees, mp.depth, float(np.float32(1.0 / np.sqrt(np.float64(d0.shape[1])))), mp.seed)
+
+
+@functools.lru_cache(maxsize=None)
+def _mrpt_big_case(oracle_mod, k):
+    d0, d1 = _mrpt_big_views()
+    ix = _mrpt_big_index(oracle_mod)
+    lds = mrpt_launch_lds(len(d0), ix.n_trees, ix.depth, MRPT_BIG_VOTES)          # 21,040 B a wavefront, four of them: 84,160 B
+    assert 64 * 1024 < lds <= 150 * 1024, lds                                     # a change of preset cannot take the case off the branch
+    return mrpt_model(ix.export(), d0, d1, ix.n_trees, ix.depth, MRPT_BIG_VOTES, k)
+
+
+def test_mrpt_model_is_the_restatement_at_k2_above_64k_lds(oracle):
+    """CPU: the numpy model against orc_mrpt_knn2 on the 12,288-row scene -- rows, distance bits, n_elected"""
+    mi, md, mne, cls = _mrpt_big_case(oracle, 2)
+    ei, ed, ene = _mrpt_big_index(oracle).knn2(_mrpt_big_views()[1], MRPT_BIG_VOTES)
+    assert np.array_equal(mi, ei) and np.array_equal(_bits(md), _bits(ed)) and np.array_equal(mne, ene)
+    assert (cls != 2).sum() >= MRPT_BIG_QUERIES // 2, "most queries are answered: the comparison is about rows, not about -1"
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("k", [2, 3], ids=["knn2", "k3"])
+def test_mrpt_above_64k_lds_equals_the_model(ctx, oracle, k):
+    """k = 2 is the 2-NN call (mrpt_knn2: the kernel's 2-NN tail), k = 3 the k-list tail; each raises its own kernel's LDS limit"""
+    d0, d1 = _mrpt_big_views()
+    mi, md, _, _ = _mrpt_big_case(oracle, k)
+    gi, gd = ctx.mrpt_knn2(d0, d1, _mrpt_params(MRPT_BIG_VOTES)) if k == 2 else ctx.mrpt_knn(d0, d1, _mrpt_params(MRPT_BIG_VOTES), k)
+    assert np.array_equal(gi, mi)
+    assert np.array_equal(_bits(gd), _bits(md))
 
 
 # ------------------------------------------------------------------------------------------------------------------ every arm
