@@ -411,7 +411,8 @@ int r3dm_index_knn(r3dm_ctx* ctx, const r3dm_index* index, const void* query, ui
  * (ArrayMatcher_kgraph::Build, src/utils/matcher_kgraph.h:138-153), per query row of J a graph search for its 2
  * nearest rows (SearchNeighbours, :204-251 -> KGraphImpl::search, src/thirdparty/kgraph/kgraph.cpp:411-552), then
  * the same ratio test / de-duplication / pair rules as r3dm_match_pairs.  F32 (and U8) descriptors with
- * dim % 4 == 0 only, squared-L2 metric (kgraph_match constructs its matcher with b_squared_metric = true, :842).
+ * dim % 4 == 0 only, squared-L2 metric (kgraph_match constructs its matcher with b_squared_metric = true, :842); binary views under
+ * the Hamming metric behind r3dm_set_kgraph_hamming (below), refused otherwise.
  * The index is the exact index_K-nearest-neighbour graph completed with reverse edges (DESIGN.md "ANN"); it is
  * built on first use and cached with the view.  Views with fewer than 128 rows are matched exhaustively.
  * Results are deterministic: they depend on (descriptors, parameters, view ids) only. */
@@ -445,7 +446,10 @@ int r3dm_match_pairs_kgraph(r3dm_ctx* ctx, const uint32_t* pairs_ij, uint64_t n_
  * search then gathers f32 rows and runs at 937 pairs/s on 16,384-row views where the exhaustive f32 kernel runs at 2,017 and the
  * split-f16 path at ~5,000, profiles/r02_p_ann_perf_f32rows.txt) of a length the tensor kernels serve (64 / 128 / 144 / 256) and no
  * view has more than 32,768 rows.  0 otherwise (integer-valued byte rows, where the v_dot4 graph search beats the f32 tiles; very
- * large views, where n log n beats n^2).  A host that only wants the arm's RESULT QUALITY (the reference's approximate arms 0-3,
+ * large views, where n log n beats n^2).  Binary views: 1 while no view exceeds 32,768 rows, the largest measured size at which the
+ * faster of the two exhaustive Hamming paths is at least as fast as the Hamming graph matcher's default preset
+ * (profiles/ann_hamming_perf.txt, 16 views: 3,084 against 2,476 pairs/s at 32,768 rows, lines 19 / 20; 816 against 829 at 65,536,
+ * lines 26 / 27).  A host that only wants the arm's RESULT QUALITY (the reference's approximate arms 0-3,
  * 5-8 exist to save CPU time, not to lose matches) can use this to serve them with the exact matcher: the facade's default. */
 int r3dm_exhaustive_is_faster(const r3dm_ctx* ctx);
 /* ArrayMatcher_kgraph-shaped call: index `dataset`, 2 approximate nearest rows of every query row.  pair_i / pair_j
@@ -459,12 +463,46 @@ int r3dm_kgraph_knn2(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, co
  * R3DM_ERR_UNSUPPORTED for a larger view instead of indexing it in quadratic time (the reference's NN-descent builder,
  * src/thirdparty/kgraph/kgraph.cpp:703-999, is not built); the exhaustive matcher has no such bound. */
 #define R3DM_KGRAPH_MAX_ROWS 131072u
-/* the index of a registered view (built if necessary): adj_out = n x 64 rows (0xFFFFFFFF padded), deg_out = n */
+/* the index of a registered view (built if necessary): adj_out = n x 64 rows (0xFFFFFFFF padded), deg_out = n.  Binary views: only
+ * while r3dm_set_kgraph_hamming is on (the Hamming index). */
 int r3dm_kgraph_index(r3dm_ctx* ctx, uint32_t view_id, uint32_t index_K, uint32_t* adj_out, uint32_t* deg_out);
-/* forget the graph indices of all registered views (they are rebuilt on the next r3dm_match_pairs_kgraph); the reference builds
+/* forget the graph indices of all registered views, binary ones included (they are rebuilt on the next r3dm_match_pairs_kgraph); the reference builds
  * the index of image I inside every kgraph_match call (src/R3DComputeMatches.cpp:826-841), so a measurement that wants the same
  * accounting calls this between passes.  The registered descriptors stay. */
 int r3dm_drop_indices(r3dm_ctx* ctx);
+
+/* ---- binary views on the graph matcher: ArrayMatcher_kgraph<unsigned char, Hamming<unsigned char>> (the reference's plugin is generic
+ * in its metric: src/utils/matcher_kgraph.h:33-37,60,90) ----
+ * r3dm_set_kgraph_hamming: per-context switch, default 0.  While it is on, r3dm_match_pairs_kgraph (and its r3dm_multi_ form),
+ * r3dm_kgraph_index, r3dm_index_kgraph_knn (the context passed is the one consulted) and r3dm_drop_indices serve R3DM_BIN views (29..32
+ * or 61..64 bytes per row, the lengths a binary view can be registered with) as they serve float views: the index is the exact
+ * index_K-nearest-neighbour graph under the Hamming distance, completed, ordered by (distance, row) and cut as for float rows; the search
+ * is the same pool expansion with xor + popcount distances.  Both read the view's packed rows; no unpacked copy is made.  A Hamming
+ * distance equals the squared L2 distance of the rows unpacked to 0 / 1 floats, so index and search are bit for bit those of the float
+ * graph matcher on the unpacked rows.  Only the ratio rule differs: binary views take dist_ratio UNSQUARED (RegionsMatcherT's
+ * b_squared_metric = false), in the search, in the exhaustively scanned part (views below 128 rows, search_P >= rows) and in the
+ * preemptive gate alike.  A list that mixes float and binary views is cut into chunks by (type, length); pairs of different types are
+ * skipped as ever.  While the switch is off every entry refuses binary views as before.  r3dm_stats counts the path as it counts the
+ * float one (n_ann_built, n_ann_dist, ms_ann_build, ms_ann_search, n_match_launches, n_pairs; n_ann_rows16 / _rows8 / _dot8 stay 0).
+ * HNSW and MRPT keep refusing binary views: hnswlib's L2Space is hard-wired in matcher_hnsw.h:70, MRPT projects floats. */
+int r3dm_set_kgraph_hamming(r3dm_ctx* ctx, int enable);
+/* what the packed-row kernels did since the context was created: indices built by the Hamming index kernel, launches of the Hamming
+ * search (both tails) */
+typedef struct {
+    uint64_t n_index_builds;
+    uint64_t n_search_launches;
+} r3dm_kgraph_hamming_stats;
+int r3dm_kgraph_hamming_report(const r3dm_ctx* ctx, r3dm_kgraph_hamming_stats* out);
+/* r3dm_kgraph_knn2 / r3dm_kgraph_knn (below) for packed binary rows of n_bytes bytes (29..32 or 61..64), Hamming metric: same pair_i /
+ * pair_j, parameters, outputs and bounds (k + search_P <= 63, R3DM_KGRAPH_MAX_ROWS); distances are the Hamming counts as floats, as
+ * r3dm_knn2 reports them.  A dataset below 128 rows, or with search_P >= n_dataset, goes to the exhaustive Hamming 2-NN / k-list.
+ * Their own opt-in: they need no switch. */
+int r3dm_kgraph_knn2_bits(r3dm_ctx* ctx, const uint8_t* dataset, uint32_t n_dataset, const uint8_t* query, uint32_t n_query,
+                          uint32_t n_bytes, const r3dm_kgraph_params* params, uint32_t pair_i, uint32_t pair_j,
+                          int32_t* out_idx, float* out_dist);
+int r3dm_kgraph_knn_bits(r3dm_ctx* ctx, const uint8_t* dataset, uint32_t n_dataset, const uint8_t* query, uint32_t n_query,
+                         uint32_t n_bytes, const r3dm_kgraph_params* params, uint32_t pair_i, uint32_t pair_j, uint32_t k,
+                         int32_t* out_idx, float* out_dist);
 
 /* ---- approximate matching: the HNSW plugin path (matchingAlgorithm 6 / 7 / 8) ----
  * Replaces hnsw_match (src/R3DComputeMatches.cpp:497-593): per first view I an HNSW index over its descriptors
@@ -581,6 +619,7 @@ int r3dm_mrpt_knn(r3dm_ctx* ctx, const float* dataset, uint32_t n_dataset, const
  * of the index's device may search, several at a time, as for r3dm_index_knn; an index may hold all three structures.  An index of
  * fewer than 128 rows (KGraph: or of at most search_P rows) is answered by r3dm_index_knn, exactly, as r3dm_match_pairs_* scans such
  * views (MRPT too: such an answer holds squared distances and drops no query).  r3dm_stats.ms_ann_build / n_ann_built are 0 for every call but the one that built. */
+/* (a binary index: served by r3dm_index_kgraph_knn while r3dm_set_kgraph_hamming is on in the context passed; queries are packed rows) */
 int r3dm_index_kgraph_knn(r3dm_ctx* ctx, const r3dm_index* index, const r3dm_kgraph_params* params, const void* query, uint32_t n_query,
                           uint32_t pair_i, uint32_t pair_j, uint32_t k, int32_t* out_idx, float* out_dist);
 int r3dm_index_hnsw_knn(r3dm_ctx* ctx, const r3dm_index* index, const r3dm_hnsw_params* params, const void* query, uint32_t n_query,
@@ -771,6 +810,7 @@ int r3dm_multi_set_intrinsics(r3dm_multi* m, uint32_t view_id, const double* K);
 int r3dm_multi_clear_images(r3dm_multi* m);
 int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable);
 int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable);      /* r3dm_set_mutual_matching on every context */
+int r3dm_multi_set_kgraph_hamming(r3dm_multi* m, int enable);       /* r3dm_set_kgraph_hamming on every context */
 int r3dm_multi_set_prefix_pruning(r3dm_multi* m, int enable);       /* r3dm_set_prefix_pruning on every context */
 int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2]);      /* summed over the contexts' last calls */
 int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */

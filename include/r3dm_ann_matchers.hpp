@@ -20,6 +20,13 @@
 // Build parameters are read when Build is called and belong to the index from then on (KGraph: index_K; HNSW: M_, efConstruction_;
 // MRPT: trees, depth); search parameters are read at every search (search_P / search_S / seed; ef_; votes).
 //
+// Binary rows: ArrayMatcher_r3dm_kgraph<unsigned char, Metric> with a Hamming metric -- the tag type r3d_amd::HammingMetric, or
+// openMVG::matching::Hamming<unsigned char> under R3DM_WITH_OPENMVG -- stages its rows as R3DM_BIN (`dimension` bytes per row: 29..32 or
+// 61..64) and searches the Hamming graph index (r3dm_set_kgraph_hamming, switched on in the leased context for the length of the search);
+// distances are the Hamming counts.  The reference's plugin is generic in its metric in the same way (matcher_kgraph.h:33-37,60,90).  With
+// any other metric unsigned char rows are R3DM_U8 under L2, as before.  The HNSW and MRPT plugins serve no Hamming metric: hnswlib's
+// L2Space is hard-wired (matcher_hnsw.h:70), MRPT projects floats.
+//
 // Thread-safety: as r3dm_array_matcher.hpp -- the reference calls SearchNeighbours from many OpenMP threads; a context drives one HIP
 // stream and owns its scratch, so every call leases a context from the process-wide pool of its device and concurrent searches run on
 // different streams.  The FIRST search of an index builds the arm's structure under the index's lock: concurrent first searches wait
@@ -29,13 +36,24 @@
 #pragma once
 
 #include <cstdint>
+#include <type_traits>
 #include <vector>
 
 #include "r3dm.h"
 #include "r3dm_array_matcher.hpp"    // IndMatch / IndMatches / DefaultMetric / R3DM_ARRAY_MATCHER_BASE, the context pool
 
 namespace r3d_amd {
+
+// the Hamming metric of ArrayMatcher_r3dm_kgraph<unsigned char, ...> where OpenMVG's Hamming<unsigned char> is not at hand
+struct HammingMetric { using ElementType = unsigned char; using ResultType = unsigned; };
+
 namespace detail {
+
+template <typename Metric> struct is_hamming_metric : std::false_type {};
+template <> struct is_hamming_metric<HammingMetric> : std::true_type {};
+#ifdef R3DM_WITH_OPENMVG
+template <typename T> struct is_hamming_metric<openMVG::matching::Hamming<T>> : std::true_type {};
+#endif
 
 // what the three classes share: the staged dataset and the emission of an index search's k-lists
 class AnnMatcherCore {
@@ -45,14 +63,15 @@ public:
     AnnMatcherCore(const AnnMatcherCore&) = delete;
     AnnMatcherCore& operator=(const AnnMatcherCore&) = delete;
 
+    // binary: unsigned char rows under a Hamming metric -> R3DM_BIN (dimension = bytes per row)
     template <typename Scalar>
-    bool build(const Scalar* dataset, int nbRows, int dimension)
+    bool build(const Scalar* dataset, int nbRows, int dimension, bool binary = false)
     {
         if (nbRows < 1 || dimension < 1 || !dataset) return false;     // matcher_kgraph.h:126-130
         ContextLease lease(pool_);
         if (!lease.ctx) return false;
         if (index_) { r3dm_index_destroy(index_); index_ = nullptr; }
-        const r3dm_dtype dt = sizeof(Scalar) == 1 ? R3DM_U8 : R3DM_F32;
+        const r3dm_dtype dt = sizeof(Scalar) == 1 ? (binary ? R3DM_BIN : R3DM_U8) : R3DM_F32;
         nbRows_ = nbRows;
         return r3dm_index_create(lease.ctx, dataset, static_cast<uint32_t>(nbRows), static_cast<uint32_t>(dimension), dt, &index_) == R3DM_OK;
     }
@@ -106,7 +125,10 @@ public:
     virtual ~ArrayMatcher_r3dm_kgraph() = default;
     uint64_t viewsStaged() const { return core_.viewsStaged(); }        // not part of the ArrayMatcher interface (test / diagnostics hook)
 
-    bool Build(const Scalar* dataset, int nbRows, int dimension) R3DM_OVERRIDE { return core_.build(dataset, nbRows, dimension); }
+    // unsigned char rows under a Hamming metric are binary rows (R3DM_BIN) on the Hamming graph index
+    static constexpr bool kHamming = sizeof(Scalar) == 1 && detail::is_hamming_metric<Metric>::value;
+
+    bool Build(const Scalar* dataset, int nbRows, int dimension) R3DM_OVERRIDE { return core_.build(dataset, nbRows, dimension, kHamming); }
 
     bool SearchNeighbour(const Scalar* query, int* indice, DistanceType* distance) R3DM_OVERRIDE
     {
@@ -120,7 +142,11 @@ public:
     {
         return core_.neighbours(query, nbQuery, pvec_indices, pvec_distances, NN, false,
                                 [&](r3dm_ctx* c, const r3dm_index* ix, int32_t* idx, float* dist) {
-            return r3dm_index_kgraph_knn(c, ix, &params_, query, static_cast<uint32_t>(nbQuery), pair_i_, pair_j_, static_cast<uint32_t>(NN), idx, dist);
+            // (the lease is exclusive: the pooled context serves binary indices for this search only)
+            if (kHamming) (void)r3dm_set_kgraph_hamming(c, 1);
+            const int rc = r3dm_index_kgraph_knn(c, ix, &params_, query, static_cast<uint32_t>(nbQuery), pair_i_, pair_j_, static_cast<uint32_t>(NN), idx, dist);
+            if (kHamming) (void)r3dm_set_kgraph_hamming(c, 0);
+            return rc;
         });
     }
 

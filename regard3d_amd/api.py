@@ -42,6 +42,7 @@ EXPORTS = [
     "r3dm_guided_match", "r3dm_set_guided_matching", "r3dm_guided_report", "r3dm_multi_set_guided_matching",
     "r3dm_set_keypoint_detector", "r3dm_multi_set_keypoint_detector", "r3dm_akaze_classic_components",
     "r3dm_set_mutual_matching", "r3dm_multi_set_mutual_matching", "r3dm_compute_matches_dir_flags",
+    "r3dm_set_kgraph_hamming", "r3dm_multi_set_kgraph_hamming", "r3dm_kgraph_hamming_report", "r3dm_kgraph_knn2_bits", "r3dm_kgraph_knn_bits",
     "r3dm_set_view_priority", "r3dm_preselect_pairs", "r3dm_set_preemptive_matching", "r3dm_preselect_report",
     "r3dm_multi_set_view_priority", "r3dm_multi_set_preemptive_matching",
     "r3dm_build_tracks", "r3dm_tracks_count", "r3dm_tracks_offsets", "r3dm_tracks_observations", "r3dm_tracks_report", "r3dm_tracks_phase_ms", "r3dm_tracks_in_pair",
@@ -107,6 +108,11 @@ class Stats(C.Structure):
                 ("detect_compulsory_bytes", C.c_double), ("n_filter_workgroups", C.c_uint64), ("n_filter_coop_pairs", C.c_uint64),
                 ("n_knn_integer_tiles", C.c_uint64), ("n_knn_split_tiles", C.c_uint64),
                 ("n_mutual_checked", C.c_uint64), ("n_mutual_dropped", C.c_uint64), ("n_knn_hamming_tiles", C.c_uint64)]
+
+
+class KGraphHammingStats(C.Structure):
+    """r3dm_kgraph_hamming_stats: what the packed-row kernels of the graph matcher did since the context was created"""
+    _fields_ = [("n_index_builds", C.c_uint64), ("n_search_launches", C.c_uint64)]
 
 
 class PreselectStats(C.Structure):
@@ -395,6 +401,11 @@ def load_library():
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_mutual_matching.argtypes = [vp, C.c_int]
     L.r3dm_multi_set_mutual_matching.argtypes = [vp, C.c_int]
+    L.r3dm_set_kgraph_hamming.argtypes = [vp, C.c_int]
+    L.r3dm_multi_set_kgraph_hamming.argtypes = [vp, C.c_int]
+    L.r3dm_kgraph_hamming_report.argtypes = [vp, vp]
+    L.r3dm_kgraph_knn2_bits.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, vp, vp]
+    L.r3dm_kgraph_knn_bits.argtypes = [vp, vp, u32, vp, u32, u32, vp, u32, u32, u32, vp, vp]
     L.r3dm_set_view_priority.argtypes = [vp, u32, vp, u32]
     L.r3dm_multi_set_view_priority.argtypes = [vp, u32, vp, u32]
     L.r3dm_preselect_pairs.argtypes = [vp, vp, C.c_uint64, u32, C.c_float, C.c_int, vp]
@@ -996,13 +1007,14 @@ class Index:
     by the first kgraph_knn / hnsw_knn / mrpt_knn call, from that call's build parameters; a later call that names other build
     parameters raises.  ctx: any Context of the index's device."""
 
-    def __init__(self, handle: int):
+    def __init__(self, handle: int, binary: bool = False):
         self._h = handle
+        self.binary = bool(binary)
 
     def kgraph_knn(self, ctx: "Context", query, params: "KGraphParams" = None, pair=(0, 1), k: int = 2):
         """ArrayMatcher_kgraph::SearchNeighbours(NN = k) (r3dm_index_kgraph_knn): (idx [nq, k] int32, -1 where the pool ran short;
-        dist [nq, k] float32, +inf there)"""
-        query = np.ascontiguousarray(query, np.float32)
+        dist [nq, k] float32, +inf there).  A binary index (ctx.set_kgraph_hamming on) takes packed uint8 rows and reports Hamming counts."""
+        query = np.ascontiguousarray(query, np.uint8) if self.binary else np.ascontiguousarray(query, np.float32)
         kp = params if params is not None else KGraphParams.preset(3)
         nq, k = int(query.shape[0]), int(k)
         idx, dist = _knn_out(nq, k)
@@ -1159,25 +1171,42 @@ class Context:
                                                     C.addressof(kp), C.byref(h)), "r3dm_match_pairs_kgraph")
         return Graph(h.value)
 
-    def kgraph_knn2(self, dataset, query, params: "KGraphParams" = None, pair=(0, 1)):
-        dataset = np.ascontiguousarray(dataset, np.float32); query = np.ascontiguousarray(query, np.float32)
+    def kgraph_knn2(self, dataset, query, params: "KGraphParams" = None, pair=(0, 1), binary: bool = False):
+        """binary: packed uint8 rows under the Hamming metric (r3dm_kgraph_knn2_bits), distances are the counts as float32"""
+        rows_t, entry, name = (np.uint8, self._L.r3dm_kgraph_knn2_bits, "r3dm_kgraph_knn2_bits") if binary else \
+                              (np.float32, self._L.r3dm_kgraph_knn2, "r3dm_kgraph_knn2")
+        dataset = np.ascontiguousarray(dataset, rows_t); query = np.ascontiguousarray(query, rows_t)
         kp = params if params is not None else KGraphParams.preset(3)
         nq = query.shape[0]
         idx = np.full((max(nq, 1), 2), -1, np.int32); dist = np.zeros((max(nq, 1), 2), np.float32)
-        self._check(self._L.r3dm_kgraph_knn2(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
-                                             C.addressof(kp), pair[0], pair[1], _ptr(idx), _ptr(dist)), "r3dm_kgraph_knn2")
+        self._check(entry(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
+                          C.addressof(kp), pair[0], pair[1], _ptr(idx), _ptr(dist)), name)
         return idx[:nq], dist[:nq]
 
-    def kgraph_knn(self, dataset, query, params: "KGraphParams" = None, pair=(0, 1), k: int = 2):
+    def kgraph_knn(self, dataset, query, params: "KGraphParams" = None, pair=(0, 1), k: int = 2, binary: bool = False):
         """ArrayMatcher_kgraph::SearchNeighbours(NN = k), k = 1 .. KNN_MAX (r3dm_kgraph_knn): the pool holds k + search_P entries;
-        (idx [nq, k] int32, -1 where the pool ran short; dist [nq, k] float32, +inf there)"""
-        dataset = np.ascontiguousarray(dataset, np.float32); query = np.ascontiguousarray(query, np.float32)
+        (idx [nq, k] int32, -1 where the pool ran short; dist [nq, k] float32, +inf there).  binary: packed uint8 rows under the
+        Hamming metric (r3dm_kgraph_knn_bits)"""
+        rows_t, entry, name = (np.uint8, self._L.r3dm_kgraph_knn_bits, "r3dm_kgraph_knn_bits") if binary else \
+                              (np.float32, self._L.r3dm_kgraph_knn, "r3dm_kgraph_knn")
+        dataset = np.ascontiguousarray(dataset, rows_t); query = np.ascontiguousarray(query, rows_t)
         kp = params if params is not None else KGraphParams.preset(3)
         nq, k = int(query.shape[0]), int(k)
         idx, dist = _knn_out(nq, k)
-        self._check(self._L.r3dm_kgraph_knn(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
-                                            C.addressof(kp), pair[0], pair[1], k, _ptr(idx), _ptr(dist)), "r3dm_kgraph_knn")
+        self._check(entry(self._h, _ptr(dataset), dataset.shape[0], _ptr(query), nq, dataset.shape[1],
+                          C.addressof(kp), pair[0], pair[1], k, _ptr(idx), _ptr(dist)), name)
         return idx[:nq], dist[:nq]
+
+    def set_kgraph_hamming(self, enable: bool = True):
+        """opt-in (include/r3dm.h: r3dm_set_kgraph_hamming): match_pairs_kgraph, kgraph_index and Index.kgraph_knn serve binary views --
+        Hamming index and search on the packed rows, the ratio unsquared.  Off: they refuse binary views."""
+        self._check(self._L.r3dm_set_kgraph_hamming(self._h, int(bool(enable))), "r3dm_set_kgraph_hamming")
+
+    def kgraph_hamming_report(self) -> dict:
+        """r3dm_kgraph_hamming_report: indices built and searches launched by the packed-row kernels since the context was created"""
+        s = KGraphHammingStats()
+        self._check(self._L.r3dm_kgraph_hamming_report(self._h, C.byref(s)), "r3dm_kgraph_hamming_report")
+        return {"n_index_builds": int(s.n_index_builds), "n_search_launches": int(s.n_search_launches)}
 
     def drop_indices(self):
         """r3dm_drop_indices: the next match_pairs_kgraph rebuilds the graph index of every view it uses"""
@@ -1598,7 +1627,7 @@ class Context:
         dt = F32 if dataset.dtype == np.float32 else (BIN if binary else U8)
         h = C.c_void_p()
         self._check(self._L.r3dm_index_create(self._h, _ptr(dataset), dataset.shape[0], dataset.shape[1], dt, C.byref(h)), "r3dm_index_create")
-        return Index(h.value)
+        return Index(h.value, binary=dt == BIN)
 
     def index_knn2(self, index: "Index", query: np.ndarray):
         """ArrayMatcher::SearchNeighbours(NN = 2) against a staged dataset; any context of the index's device"""
@@ -1866,6 +1895,10 @@ class MultiContext:
     def set_mutual_matching(self, enable: bool = True):
         """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""
         self._check(self._L.r3dm_multi_set_mutual_matching(self._h, int(bool(enable))), "r3dm_multi_set_mutual_matching")
+
+    def set_kgraph_hamming(self, enable: bool = True):
+        """r3dm_multi_set_kgraph_hamming: Context.set_kgraph_hamming on every context"""
+        self._check(self._L.r3dm_multi_set_kgraph_hamming(self._h, int(bool(enable))), "r3dm_multi_set_kgraph_hamming")
 
     def set_view_priority(self, view_id: int, priority):
         """r3dm_multi_set_view_priority: Context.set_view_priority on every context"""

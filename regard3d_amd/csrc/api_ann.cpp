@@ -40,12 +40,13 @@ int resolve_pairs(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, const
 
 // the pairs of an approximate matcher whose dataset view is not indexed: few and tiny, scanned exhaustively, one batch per
 // (dtype, dim) run
-static int run_scanned_pairs(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g)
+static int run_scanned_pairs(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, float bin_ratio_R, r3dm_graph* g)
 {
     for (size_t start = 0, end = 0; start < jobs.size(); start = end) {
         const HostImage& F = *c->imgs[jobs[start].sI];
         for (end = start; end < jobs.size() && c->imgs[jobs[end].sI]->dtype == F.dtype && c->imgs[jobs[end].sI]->dim == F.dim;) ++end;
-        const int rc = run_match_batch(c, std::vector<PairJob>(jobs.begin() + start, jobs.begin() + end), ratio_R, g, nullptr, nullptr);
+        const float R = (F.dtype == R3DM_BIN && bin_ratio_R >= 0.0f) ? bin_ratio_R : ratio_R;
+        const int rc = run_match_batch(c, std::vector<PairJob>(jobs.begin() + start, jobs.begin() + end), R, g, nullptr, nullptr);
         if (rc != R3DM_OK) return rc;
     }
     return R3DM_OK;
@@ -83,7 +84,7 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
     std::vector<PairJob> indexed, scanned;
     int rc = resolve_pairs(c, pairs_ij, n_pairs, arm.classify, indexed, scanned);
     if (rc != R3DM_OK) return rc;
-    rc = preselect_gate(c, gate_ratio_R, indexed, scanned);                // r3dm_set_preemptive_matching
+    rc = preselect_gate(c, gate_ratio_R, indexed, scanned, arm.bin_ratio_R);      // r3dm_set_preemptive_matching
     if (rc != R3DM_OK) return rc;
 
     r3dm_graph ga, gs;
@@ -95,9 +96,10 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
     }
     for (size_t start = 0, end = 0; start < indexed.size(); start = end) {
         const uint32_t dim = c->imgs[indexed[start].sI]->dim;
+        const r3dm_dtype dtype = c->imgs[indexed[start].sI]->dtype;
         uint32_t max_n = 0;
         for (end = start; end < indexed.size() && end - start < arm.max_chunk_pairs; ++end) {
-            if (arm.one_dim_per_chunk && c->imgs[indexed[end].sI]->dim != dim) break;
+            if (arm.one_dim_per_chunk && (c->imgs[indexed[end].sI]->dim != dim || (c->imgs[indexed[end].sI]->dtype == R3DM_BIN) != (dtype == R3DM_BIN))) break;
             const uint32_t mn = std::max(max_n, c->imgs[indexed[end].sJ]->n);
             const uint64_t s = (uint64_t)(end - start + 1) * ((mn + 31) / 32 * 32);
             // <= 3 GiB of nn_idx, and one workgroup per 4 queries: the dispatch must stay below 2^32 work-items (kMaxBlocksOf256)
@@ -107,7 +109,7 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
         rc = arm.run_batch(std::vector<PairJob>(indexed.begin() + start, indexed.begin() + end), &ga);
         if (rc != R3DM_OK) return rc;
     }
-    rc = run_scanned_pairs(c, scanned, scanned_ratio_R, &gs);
+    rc = run_scanned_pairs(c, scanned, scanned_ratio_R, arm.bin_ratio_R, &gs);
     if (rc != R3DM_OK) return rc;
     rc = merge_parts_keep_mirror(ga, gs, out);
     c->stats.ms_wall_match = now_ms() - t_call;
@@ -270,7 +272,11 @@ extern "C" int r3dm_exhaustive_is_faster(const r3dm_ctx* c)
         if (!up || !up->live) continue;
         const HostImage& h = *up;
         any = true;
-        if (h.dtype == R3DM_BIN) return 0;                                   // no graph matcher for Hamming anyway
+        // Binary views: 1 while no view exceeds 32,768 rows, the largest measured size at which the faster exhaustive Hamming path is at
+        // least as fast as the Hamming graph matcher's default preset (profiles/ann_hamming_perf.txt, 16 views, pairs/s: line 19, MFMA
+        // path 3,084, against line 20, graph 2,476; at 65,536 rows lines 26 / 27: 816 against 829 -- where the graph matcher recovers
+        // 0.27 of the exhaustive matches, 0.41 at 32,768 and 0.75 at 8,192: it is the approximate matcher)
+        if (h.dtype == R3DM_BIN) { if (h.n > 32768u) return 0; continue; }
         if (!h.not_integer) return 0;                                        // integer-valued rows: the byte-row graph search is the faster one
         if (!has_tensor_kernel(kernel_G_for(h.dim))) return 0;               // other lengths run the one-workgroup-per-query exact scan
         if (h.n > 32768u) return 0;
@@ -344,9 +350,10 @@ int ensure_ann_indices(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t K)
         size_t end = start, bytes = 0;
         uint32_t max_n = 0;
         const uint32_t dim = c->imgs[todo[start]]->dim;
+        const bool binary = c->imgs[todo[start]]->dtype == R3DM_BIN;       // packed rows under Hamming: the build reads ImgDev::bin
         while (end < todo.size() && end - start < 256) {
             const HostImage& h = *c->imgs[todo[end]];
-            if (h.dim != dim) break;
+            if (h.dim != dim || (h.dtype == R3DM_BIN) != binary) break;
             const size_t need = (size_t)h.n * K * 16 + (size_t)h.n * 12 + 64;
             if (end > start && bytes + need > (4ull << 30)) break;
             bytes += need; max_n = std::max(max_n, h.n); ++end;
@@ -377,7 +384,9 @@ int ensure_ann_indices(r3dm_ctx* c, std::vector<uint32_t> slots, uint32_t K)
         R3DM_HIP(c, hipMemcpyAsync(c->a_jobs.p, jobs.data(), jobs.size() * sizeof(AnnBuildJob), hipMemcpyHostToDevice, c->stream));
         AnnBuildParams bp{};
         bp.imgs = c->d_imgs.as<ImgDev>(); bp.jobs = c->a_jobs.as<AnnBuildJob>(); bp.K = K;
-        hipError_t e = launch_ann_build(c->stream, bp, (uint32_t)jobs.size(), max_n, dim, all_rows8 && dim <= 256 && (dim & 15u) == 0);
+        hipError_t e = launch_ann_build(c->stream, bp, (uint32_t)jobs.size(), max_n, dim, !binary && all_rows8 && dim <= 256 && (dim & 15u) == 0,
+                                        binary ? c->imgs[todo[start]]->words : 0u);
+        if (binary && e == hipSuccess) c->kgraph_hamming_stats.n_index_builds += jobs.size();
         if (e == hipErrorInvalidValue) { c->err = "no graph-index kernel for this descriptor length (dim % 4 != 0 or too long)"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, e);
         static_assert(offsetof(ImgDev, ann_deg) == offsetof(ImgDev, ann_adj) + sizeof(void*) &&
@@ -428,11 +437,14 @@ static int run_kgraph_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float
             rows8 = rows8 && A.compact_ready && A.ann_rows8.p != nullptr;
             dot8 = dot8 && B.compact_ready && B.ann_rows8.p != nullptr;        // ... and every query view its byte copy
         }
+        const bool binary = c->imgs[jobs[0].sI]->dtype == R3DM_BIN;             // (a batch is of one dtype and length)
+        if (binary) { dot8 = false; rows8 = false; rows16 = false; }
         dot8 = dot8 && rows8 && b.dim <= 256 && (b.dim & 15u) == 0;
         // descriptor lengths 132 .. 144 (nine float4 per lane: LIOP-144) have no compact-row instantiation of the search kernel
         // (launch_ann_search): integer-valued views of that length gather the f32 rows
         if ((b.dim / 4 + 3) / 4 == 9) { dot8 = false; rows8 = false; rows16 = false; }
-        const hipError_t e = launch_ann_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim, dot8 ? 3 : rows8 ? 2 : (rows16 ? 1 : 0), knn_k);
+        const hipError_t e = launch_ann_search(c->stream, sp, b.max_nJ, b.max_nI, b.dim, binary ? 4 : dot8 ? 3 : rows8 ? 2 : (rows16 ? 1 : 0), knn_k);
+        if (binary && e == hipSuccess) c->kgraph_hamming_stats.n_search_launches += 1;
         if (e == hipErrorInvalidValue) { c->err = "graph search: unsupported descriptor length / view size / parameters"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, e);
         return R3DM_OK;
@@ -453,8 +465,10 @@ static int r3dm_match_pairs_kgraph_impl(r3dm_ctx* c, const uint32_t* pairs_ij, u
     if (rcp != R3DM_OK) return rcp;
     const float R = dist_ratio * dist_ratio;
     AnnArm arm;
+    // binary views (r3dm_set_kgraph_hamming): the ratio unsquared, in the search, the scanned part and the gate alike
+    if (c->kgraph_hamming) arm.bin_ratio_R = dist_ratio;
     arm.classify = [&](const HostImage& A, bool& index) -> int {
-        if (A.dtype == R3DM_BIN || (A.dim & 3u)) { c->err = "kgraph matching needs F32/U8 descriptors with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+        if (A.dtype == R3DM_BIN ? !c->kgraph_hamming : (A.dim & 3u) != 0) { c->err = "kgraph matching needs F32/U8 descriptors with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
         // KGraphImpl::search scans linearly when P >= n (kgraph.cpp:415-421); here every small index is scanned
         index = !(A.n < kAnnMinRows || kp->search_P >= A.n);
         return R3DM_OK;
@@ -473,7 +487,9 @@ static int r3dm_match_pairs_kgraph_impl(r3dm_ctx* c, const uint32_t* pairs_ij, u
         for (const PairJob& j : jobs) slots.push_back(j.sJ);
         return ensure_compact_rows(c, slots);
     };
-    arm.run_batch = [&](const std::vector<PairJob>& batch, r3dm_graph* g) { return run_kgraph_batch(c, batch, R, *kp, g, nullptr, nullptr); };
+    arm.run_batch = [&](const std::vector<PairJob>& batch, r3dm_graph* g) {
+        return run_kgraph_batch(c, batch, c->imgs[batch[0].sI]->dtype == R3DM_BIN ? dist_ratio : R, *kp, g, nullptr, nullptr);
+    };
     arm.one_dim_per_chunk = true;                            // (no cap on a chunk's pairs: the search has no per-pair grid dimension)
     return match_collection_ann(c, pairs_ij, n_pairs, R, arm, out);
 }
@@ -484,7 +500,19 @@ extern "C" int r3dm_match_pairs_kgraph(r3dm_ctx* c, const uint32_t* pairs_ij, ui
     return r3dm_guarded(c, [&]() -> int { return r3dm_match_pairs_kgraph_impl(c, pairs_ij, n_pairs, dist_ratio, kp, out); });
 }
 
-static int r3dm_kgraph_knn2_impl(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+// the length check of an array entry: float rows in fours; packed rows (the _bits entries) of 8 or 16 words, as every binary view
+static int check_kgraph_row_length(r3dm_ctx* c, r3dm_dtype dtype, uint32_t dim)
+{
+    if (dtype == R3DM_BIN) {
+        if (((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16) return R3DM_OK;
+        c->err = "binary descriptors must be 29..32 or 61..64 bytes";
+        return R3DM_ERR_UNSUPPORTED;
+    }
+    if (dim & 3u) { c->err = "kgraph matching needs dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+    return R3DM_OK;
+}
+
+static int r3dm_kgraph_knn2_impl(r3dm_ctx* c, r3dm_dtype dtype, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
                                 uint32_t dim, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j,
                                 int32_t* out_idx, float* out_dist)
 {
@@ -492,9 +520,10 @@ static int r3dm_kgraph_knn2_impl(r3dm_ctx* c, const float* dataset, uint32_t n_d
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;
     int rc = check_kgraph_params(c, kp);
     if (rc != R3DM_OK) return rc;
-    if (dim & 3u) { c->err = "kgraph matching needs dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+    rc = check_kgraph_row_length(c, dtype, dim);
+    if (rc != R3DM_OK) return rc;
     // like r3dm_knn2: which rows this call gathered, how many evaluations
-    return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, pair_i, pair_j,
+    return with_staged_pair_of(c, dtype, dataset, n_dataset, query, n_query, dim, pair_i, pair_j,
                             {&r3dm_stats::n_ann_rows16, &r3dm_stats::n_ann_rows8, &r3dm_stats::n_ann_dot8, &r3dm_stats::n_ann_dist}, {},
                             [&](uint32_t sI, uint32_t sJ) -> int {
         const std::vector<PairJob> jobs{{pair_i, pair_j, sI, sJ}};
@@ -511,7 +540,14 @@ extern "C" int r3dm_kgraph_knn2(r3dm_ctx* c, const float* dataset, uint32_t n_da
                                 uint32_t dim, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j,
                                 int32_t* out_idx, float* out_dist)
 {
-    return r3dm_guarded(c, [&]() -> int { return r3dm_kgraph_knn2_impl(c, dataset, n_dataset, query, n_query, dim, kp, pair_i, pair_j, out_idx, out_dist); });
+    return r3dm_guarded(c, [&]() -> int { return r3dm_kgraph_knn2_impl(c, R3DM_F32, dataset, n_dataset, query, n_query, dim, kp, pair_i, pair_j, out_idx, out_dist); });
+}
+
+extern "C" int r3dm_kgraph_knn2_bits(r3dm_ctx* c, const uint8_t* dataset, uint32_t n_dataset, const uint8_t* query, uint32_t n_query,
+                                     uint32_t n_bytes, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j,
+                                     int32_t* out_idx, float* out_dist)
+{
+    return r3dm_guarded(c, [&]() -> int { return r3dm_kgraph_knn2_impl(c, R3DM_BIN, dataset, n_dataset, query, n_query, n_bytes, kp, pair_i, pair_j, out_idx, out_dist); });
 }
 
 // ---- k neighbours, k = 1 .. R3DM_KNN_MAX: ArrayMatcher_kgraph::SearchNeighbours with any NN (matcher_kgraph.h:205-251, sparams.K = NN)
@@ -535,7 +571,7 @@ static int kgraph_knn_search(r3dm_ctx* c, const r3dm_kgraph_params& kp, uint32_t
     return rc;
 }
 
-extern "C" int r3dm_kgraph_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+static int r3dm_kgraph_knn_impl(r3dm_ctx* c, r3dm_dtype dtype, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query,
                                uint32_t dim, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j, uint32_t k,
                                int32_t* out_idx, float* out_dist)
 {
@@ -543,8 +579,9 @@ extern "C" int r3dm_kgraph_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dat
         if (!c || !dataset || !query || !out_idx || !out_dist || dim == 0) return R3DM_ERR_INVALID;
         int rc = check_kgraph_knn(c, kp, k, n_dataset, n_query);
         if (rc != R3DM_OK) return rc;
-        if (dim & 3u) { c->err = "kgraph matching needs dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
-        return with_staged_pair(c, dataset, n_dataset, query, n_query, dim, pair_i, pair_j,
+        rc = check_kgraph_row_length(c, dtype, dim);
+        if (rc != R3DM_OK) return rc;
+        return with_staged_pair_of(c, dtype, dataset, n_dataset, query, n_query, dim, pair_i, pair_j,
                                 {&r3dm_stats::n_ann_rows16, &r3dm_stats::n_ann_rows8, &r3dm_stats::n_ann_dot8, &r3dm_stats::n_ann_dist},
                                 {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search}, [&](uint32_t sI, uint32_t sJ) -> int {
             // as r3dm_kgraph_knn2: a small dataset, or one the start rows would cover, is scanned
@@ -552,6 +589,20 @@ extern "C" int r3dm_kgraph_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dat
             return kgraph_knn_search(c, *kp, pair_i, pair_j, sI, sJ, k, out_idx, out_dist);
         });
     });
+}
+
+extern "C" int r3dm_kgraph_knn(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query,
+                               uint32_t dim, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j, uint32_t k,
+                               int32_t* out_idx, float* out_dist)
+{
+    return r3dm_kgraph_knn_impl(c, R3DM_F32, dataset, n_dataset, query, n_query, dim, kp, pair_i, pair_j, k, out_idx, out_dist);
+}
+
+extern "C" int r3dm_kgraph_knn_bits(r3dm_ctx* c, const uint8_t* dataset, uint32_t n_dataset, const uint8_t* query, uint32_t n_query,
+                                    uint32_t n_bytes, const r3dm_kgraph_params* kp, uint32_t pair_i, uint32_t pair_j, uint32_t k,
+                                    int32_t* out_idx, float* out_dist)
+{
+    return r3dm_kgraph_knn_impl(c, R3DM_BIN, dataset, n_dataset, query, n_query, n_bytes, kp, pair_i, pair_j, k, out_idx, out_dist);
 }
 
 extern "C" int r3dm_index_kgraph_knn(r3dm_ctx* c, const r3dm_index* ix, const r3dm_kgraph_params* kp, const void* query, uint32_t n_query,
@@ -563,7 +614,7 @@ extern "C" int r3dm_index_kgraph_knn(r3dm_ctx* c, const r3dm_index* ix, const r3
         if (rc != R3DM_OK) return rc;
         // as r3dm_match_pairs_kgraph scans such views: the exhaustive k-NN of the index, exactly
         if (ix->img.n < kAnnMinRows || kp->search_P >= ix->img.n) return r3dm_index_knn(c, ix, query, n_query, k, out_idx, out_dist);
-        if (ix->img.dtype == R3DM_BIN || (ix->img.dim & 3u)) { c->err = "kgraph matching needs F32/U8 descriptors with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+        if (ix->img.dtype == R3DM_BIN ? !c->kgraph_hamming : (ix->img.dim & 3u) != 0) { c->err = "kgraph matching needs F32/U8 descriptors with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
         CallCounters counters(c, {&r3dm_stats::n_ann_rows16, &r3dm_stats::n_ann_rows8, &r3dm_stats::n_ann_dot8, &r3dm_stats::n_ann_dist, &r3dm_stats::n_ann_built},
                               {&r3dm_stats::ms_ann_build, &r3dm_stats::ms_ann_search});
         return with_index_structure(c, ix, query, n_query,
@@ -595,7 +646,7 @@ extern "C" int r3dm_kgraph_index(r3dm_ctx* c, uint32_t view_id, uint32_t index_K
     if (it == c->slot_of.end()) { c->err = "unregistered view"; return R3DM_ERR_INVALID; }
     if (index_K < 1 || index_K > kAnnMaxK) return R3DM_ERR_INVALID;
     HostImage& h = *c->imgs[it->second];
-    if (h.dtype == R3DM_BIN || (h.dim & 3u) || h.n < 2) { c->err = "kgraph index needs >= 2 F32/U8 rows with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
+    if ((h.dtype == R3DM_BIN ? !c->kgraph_hamming : (h.dim & 3u) != 0) || h.n < 2) { c->err = "kgraph index needs >= 2 F32/U8 rows with dim % 4 == 0"; return R3DM_ERR_UNSUPPORTED; }
     R3DM_HIP(c, hipSetDevice(c->device));
     int rc = ensure_layouts(c, {it->second}, kLayRows);
     if (rc == R3DM_OK) rc = ensure_ann_indices(c, {it->second}, index_K);
@@ -605,3 +656,18 @@ extern "C" int r3dm_kgraph_index(r3dm_ctx* c, uint32_t view_id, uint32_t index_K
     return R3DM_OK;
 }
 
+
+// ---- binary views on the graph matcher (kernels_ann.hip: ann_knn_bits_kernel, the ROWS 4 arm of ann_search_kernel)
+extern "C" int r3dm_set_kgraph_hamming(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->kgraph_hamming = enable != 0;
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_kgraph_hamming_report(const r3dm_ctx* c, r3dm_kgraph_hamming_stats* out)
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    *out = c->kgraph_hamming_stats;
+    return R3DM_OK;
+}

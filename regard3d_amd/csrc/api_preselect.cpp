@@ -83,7 +83,8 @@ int ensure_heads(r3dm_ctx* c, const std::vector<uint32_t>& slots, uint32_t h, ui
 struct GatePair { uint32_t sI, sJ; };
 
 // counts[p] = the head count of pairs[p] (slots of two non-empty views of one type and length) for head size h under ratio R
-int head_counts(r3dm_ctx* c, const std::vector<GatePair>& pairs, uint32_t h, float R, std::vector<uint32_t>& counts)
+// (R_bin >= 0: the R of the binary classes instead)
+int head_counts(r3dm_ctx* c, const std::vector<GatePair>& pairs, uint32_t h, float R, std::vector<uint32_t>& counts, float R_bin = -1.0f)
 {
     counts.assign(pairs.size(), 0u);
     if (pairs.empty()) return R3DM_OK;
@@ -132,6 +133,7 @@ int head_counts(r3dm_ctx* c, const std::vector<GatePair>& pairs, uint32_t h, flo
     P.heads = c->pre_heads.as<HeadDev>(); P.counts = c->pre_counts.as<uint32_t>(); P.ratio_R = R;
     size_t o = 0;
     for (const Class& k : classes) {
+        P.ratio_R = (k.binary && R_bin >= 0.0f) ? R_bin : R;
         // one workgroup per pair: launches stay below kMaxBlocksOf256
         for (size_t s = 0; s < k.pairs.size();) {
             const size_t cnt = std::min<size_t>(k.pairs.size() - s, (size_t)kMaxBlocksOf256 - 8);
@@ -153,7 +155,7 @@ int head_counts(r3dm_ctx* c, const std::vector<GatePair>& pairs, uint32_t h, flo
 
 }  // namespace
 
-int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned)
+int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned, float bin_ratio_R)
 {
     c->preselect_stats = r3dm_preselect_stats{};
     if (!c->preemptive_on) return R3DM_OK;
@@ -162,7 +164,7 @@ int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, st
     pairs.reserve(indexed.size() + scanned.size());
     for (const auto* v : {&indexed, &scanned}) for (const PairJob& j : *v) pairs.push_back(GatePair{j.sI, j.sJ});
     std::vector<uint32_t> counts;
-    const int rc = head_counts(c, pairs, c->preemptive_h, ratio_R, counts);
+    const int rc = head_counts(c, pairs, c->preemptive_h, ratio_R, counts, bin_ratio_R);
     if (rc != R3DM_OK) return rc;
     size_t p = 0;
     for (auto* v : {&indexed, &scanned}) {

@@ -501,6 +501,12 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
     r3dm_graph* putative = nullptr;
     const int squared = dtype_ == R3DM_BIN ? 0 : 1;        // RegionsMatcherT squared flag: true for L2 metrics
     int rc;
+    // binary regions: the graph matcher serves them behind its switch (r3dm_set_kgraph_hamming), which this stage turns on for its own
+    // contexts -- HNSW and MRPT do not serve them, their arm numbers run the graph matcher with the preset r3dm_ann_params_for_algorithm names
+    if (dtype_ == R3DM_BIN && use_kgraph) {
+        const int rcs = ctx_ ? r3dm_set_kgraph_hamming(ctx_, 1) : r3dm_multi_set_kgraph_hamming(multi_, 1);
+        if (rcs != R3DM_OK) { errorMessage_ = last_error(); return false; }
+    }
     // an approximate arm whose job the exhaustive matcher does at least as fast -- and exactly -- is served by it (setApproximateArmsPolicy)
     if (use_kgraph && arms_policy_ == kArmsFastest && r3dm_exhaustive_is_faster(ctx_ ? ctx_ : r3dm_multi_ctx(multi_, 0)) == 1) use_kgraph = false;
     last_exhaustive_ = !use_kgraph;

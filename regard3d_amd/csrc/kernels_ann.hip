@@ -184,6 +184,60 @@ void ann_knn_rows8_kernel(const AnnBuildParams P)
     }
 }
 
+// The same scan for binary views (R3DM_BIN: ImgDev::bin, W zero-padded u32 words per row) under the Hamming metric: xor + popcount per
+// word, the scanned row wave-uniform (scalar loads of the packed words), the thread's own row packed in VGPRs.  The key carries the
+// count as a float -- an integer below 2^24, the squared L2 distance of the rows unpacked to 0 / 1 floats -- so the reverse, merge, cut
+// and degree kernels run on it unchanged.  No unpacked copy of the view exists anywhere.
+template <int W /* u32 words per row: 8 or 16 */>
+__global__ __launch_bounds__(256)
+void ann_knn_bits_kernel(const AnnBuildParams P)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char ann_smem[];
+    const AnnBuildJob job = P.jobs[blockIdx.y];
+    const ImgDev* __restrict__ im = P.imgs + job.slot;
+    const uint32_t n = im->n;
+    const uint32_t row = blockIdx.x * 256 + threadIdx.x;
+    if (blockIdx.x * 256 >= n) return;
+    const uint32_t K = P.K;
+    unsigned long long* list = (unsigned long long*)ann_smem;            // [K][256]
+    const uint32_t my = row < n ? row : n - 1;
+    uint32_t q[W];
+    {
+        const u32x4* src = (const u32x4*)(im->bin + (size_t)my * W);
+#pragma unroll
+        for (int g = 0; g < W / 4; ++g) {
+            const u32x4 v = src[g];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) q[4 * g + k] = v[k];
+        }
+    }
+    for (uint32_t k = 0; k < K; ++k) list[k * 256 + threadIdx.x] = ~0ull;
+    unsigned long long worst = ~0ull;
+    const cu32p base = (cu32p)(uintptr_t)im->bin;
+    for (uint32_t r = 0; r < n; ++r) {
+        const cu32p a = base + (size_t)r * W;
+        uint32_t d = 0;
+#pragma unroll
+        for (int w = 0; w < W; ++w) d += (uint32_t)__builtin_popcount(a[w] ^ q[w]);
+        const unsigned long long key = (r == my) ? ~0ull : key_of((float)d, r);
+        if (key < worst) {
+            uint32_t k = K - 1;
+            while (k > 0) {
+                const unsigned long long up = list[(k - 1) * 256 + threadIdx.x];
+                if (up <= key) break;
+                list[k * 256 + threadIdx.x] = up;
+                --k;
+            }
+            list[k * 256 + threadIdx.x] = key;
+            worst = list[(K - 1) * 256 + threadIdx.x];
+        }
+    }
+    if (row < n) {
+        unsigned long long* out = job.fwd + (size_t)row * K;
+        for (uint32_t k = 0; k < K; ++k) out[k] = list[k * 256 + threadIdx.x];
+    }
+}
+
 // is `id` one of the forward neighbours of `node`?
 __device__ __forceinline__ bool ann_has_forward(const unsigned long long* fwd, uint32_t K, uint32_t node, uint32_t id)
 {
@@ -307,6 +361,9 @@ void ann_merge_kernel(const AnnBuildParams P)
 // an integer below 2^24 (D <= 256), i.e. exact in ANY order, and the distance is ||a||^2 - 2 a.q + ||q||^2 from two v_dot4_u32_u8
 // per four dimensions instead of ~6 f32 instructions per dimension -- the kernel is bound by VALU issue (86 % busy, 41 VALU
 // instructions per evaluation on f32 arithmetic: profiles/r02_r_pmc_ann_search.txt), not by its gathers.
+// ROWS 4: binary views under the Hamming metric (r3dm_set_kgraph_hamming).  Both sides are the packed word rows of ImgDev::bin, NQ words
+// per lane (4: rows of 16 words, one u32x4 per lane; 2: rows of 8 words); the distance is xor + popcount summed over the quad, as a float.
+// It equals the squared L2 distance of the rows unpacked to 0 / 1 floats, so the model of the float search is the model of this one.
 // One kernel template, two tails:
 //   KNN 0   the two best pool entries and the ratio test; `k` is unused (launched with 0)
 //   KNN 1   the same search with a pool of k + P entries (P.pool_cap, as KGraphImpl::search sizes it) and the k-list tail
@@ -338,10 +395,15 @@ void ann_search_kernel(const AnnSearchParams P, const uint32_t k)
     const uint32_t* __restrict__ adj = Ip->ann_adj;
     const uint32_t* __restrict__ deg = Ip->ann_deg;
 
-    f32x4 qv[ROWS == 3 ? 1 : NQ];
-    [[maybe_unused]] uint32_t q8[ROWS == 3 ? NQ : 1];
+    f32x4 qv[(ROWS == 3 || ROWS == 4) ? 1 : NQ];
+    [[maybe_unused]] uint32_t q8[(ROWS == 3 || ROWS == 4) ? NQ : 1];
     [[maybe_unused]] uint32_t qq_part = 0;                  // ||q||^2 (summed over the four lanes of the group below)
-    if constexpr (ROWS == 3) {
+    if constexpr (ROWS == 4) {
+        static_assert(ROWS != 4 || NQ == 2 || NQ == 4, "binary rows are 8 or 16 words: 2 or 4 per lane");
+        const uint32_t* src = Jp->bin + (size_t)q * (4 * NQ) + g_lo;
+        if constexpr (NQ == 4) { const u32x4 w = *(const u32x4*)src; q8[0] = w[0]; q8[1] = w[1]; q8[2] = w[2]; q8[3] = w[3]; }
+        else { const uint2 w = *(const uint2*)src; q8[0] = w.x; q8[1] = w.y; }
+    } else if constexpr (ROWS == 3) {
         static_assert(ROWS != 3 || NQ % 4 == 0, "byte rows are read 16 elements at a time");
         const u32x4* src = (const u32x4*)(Jp->ann_rows8 + (size_t)q * dim) + (g_lo >> 2);
 #pragma unroll
@@ -402,6 +464,23 @@ void ann_search_kernel(const AnnSearchParams P, const uint32_t k)
         // ---- distance of the group's candidate in the reference's summation order
         float r = 0.0f;
         uint32_t cdeg = 0;
+        if constexpr (ROWS == 4) {
+            if (fresh) {
+                const uint32_t* a = Ip->bin + (size_t)cid * (4 * NQ) + g_lo;
+                uint32_t d;
+                if constexpr (NQ == 4) {
+                    const u32x4 w = *(const u32x4*)a;
+                    d = (uint32_t)(__builtin_popcount(w[0] ^ q8[0]) + __builtin_popcount(w[1] ^ q8[1]) + __builtin_popcount(w[2] ^ q8[2]) + __builtin_popcount(w[3] ^ q8[3]));
+                } else {
+                    const uint2 w = *(const uint2*)a;
+                    d = (uint32_t)(__builtin_popcount(w.x ^ q8[0]) + __builtin_popcount(w.y ^ q8[1]));
+                }
+                cdeg = deg[cid];
+                d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0xB1, 0xF, 0xF, true);      // quad_perm [1,0,3,2]
+                d += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)d, 0x4E, 0xF, 0xF, true);      // quad_perm [2,3,0,1]: all four lanes hold the count
+                r = (float)d;
+            }
+        } else
         if constexpr (ROWS == 3) {
             if (fresh) {
                 const u32x4* a8 = (const u32x4*)(rows8 + (size_t)cid * dim) + (g_lo >> 2);
@@ -524,14 +603,21 @@ void ann_search_kernel(const AnnSearchParams P, const uint32_t k)
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-hipError_t launch_ann_build(hipStream_t st, const AnnBuildParams& P, uint32_t n_jobs, uint32_t max_n, uint32_t dim, bool rows8)
+hipError_t launch_ann_build(hipStream_t st, const AnnBuildParams& P, uint32_t n_jobs, uint32_t max_n, uint32_t dim, bool rows8, uint32_t bin_words)
 {
     if (n_jobs == 0 || max_n == 0) return hipSuccess;
     const uint32_t K = P.K;
-    if ((dim & 3u) || K < 1 || K > kAnnMaxK) return hipErrorInvalidValue;
+    if ((!bin_words && (dim & 3u)) || K < 1 || K > kAnnMaxK) return hipErrorInvalidValue;
     const dim3 g256((max_n + 255) / 256, n_jobs);
     const size_t l256 = (size_t)K * 256 * 8;
-    if (rows8 && dim == 128) hipLaunchKernelGGL((ann_knn_rows8_kernel<32>), g256, dim3(256), l256, st, P);
+    if (bin_words) {
+        const hipError_t e = dispatch_words(bin_words, [&](auto w) {
+            hipLaunchKernelGGL((ann_knn_bits_kernel<decltype(w)::value>), g256, dim3(256), l256, st, P);
+            return hipSuccess;
+        });
+        if (e != hipSuccess) return e;
+    }
+    else if (rows8 && dim == 128) hipLaunchKernelGGL((ann_knn_rows8_kernel<32>), g256, dim3(256), l256, st, P);
     else if (rows8 && dim == 64) hipLaunchKernelGGL((ann_knn_rows8_kernel<16>), g256, dim3(256), l256, st, P);
     else if (rows8 && dim == 256) hipLaunchKernelGGL((ann_knn_rows8_kernel<64>), g256, dim3(256), l256, st, P);
     else if (rows8 && dim == 96) hipLaunchKernelGGL((ann_knn_rows8_kernel<24>), g256, dim3(256), l256, st, P);
@@ -596,7 +682,7 @@ static hipError_t launch_ann_search_t(hipStream_t st, const AnnSearchParams& P, 
 hipError_t launch_ann_search(hipStream_t st, const AnnSearchParams& Pin, uint32_t max_nJ, uint32_t max_nI, uint32_t dim, int rows_mode, uint32_t knn_k)
 {
     AnnSearchParams P = Pin;
-    if ((dim & 3u) || P.pool_cap > 63 || P.S < 1 || P.S > 16 || P.P < 2) return hipErrorInvalidValue;
+    if ((rows_mode != 4 && (dim & 3u)) || P.pool_cap > 63 || P.S < 1 || P.S > 16 || P.P < 2) return hipErrorInvalidValue;
     if (knn_k && (knn_k > R3DM_KNN_MAX || P.pool_cap != knn_k + P.P || !P.knn_idx || !P.knn_dist)) return hipErrorInvalidValue;
     P.qb_per_pair = (max_nJ + 3) / 4;
     P.flag_words = (max_nI + 31) / 32;
@@ -607,7 +693,13 @@ hipError_t launch_ann_search(hipStream_t st, const AnnSearchParams& Pin, uint32_
     if (grid > kMaxBlocksOf256) return hipErrorInvalidValue;
     const uint32_t nq = (dim / 4 + 3) / 4;
     const dim3 g((uint32_t)grid);
-    if (rows_mode == 3 && (dim & 15u) == 0 && dim <= 256 && nq != 9) {
+    if (rows_mode == 4) {                                    // binary rows: dim is their bytes
+        const uint32_t words = (dim + 3) / 4;
+        if (words == 16) return launch_ann_search_t<4, 4>(st, P, g, lds, knn_k);
+        else if (words == 8) return launch_ann_search_t<2, 4>(st, P, g, lds, knn_k);
+        else return hipErrorInvalidValue;
+    }
+    else if (rows_mode == 3 && (dim & 15u) == 0 && dim <= 256 && nq != 9) {
         if (nq <= 4) return launch_ann_search_t<4, 3>(st, P, g, lds, knn_k);
         else if (nq <= 8) return launch_ann_search_t<8, 3>(st, P, g, lds, knn_k);
         else if (nq <= 16) return launch_ann_search_t<16, 3>(st, P, g, lds, knn_k);

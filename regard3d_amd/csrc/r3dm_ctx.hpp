@@ -566,6 +566,8 @@ struct r3dm_ctx {
     bool knn_narrow_tiles = false;                          // r3dm_set_knn_narrow_tiles
     bool knn_hamming_tiles = false;                         // r3dm_set_knn_hamming_tiles
     bool mutual_matching = false;                           // r3dm_set_mutual_matching: the mutual check runs before every finalisation into a graph
+    bool kgraph_hamming = false;                            // r3dm_set_kgraph_hamming: the graph matcher serves binary views (Hamming index + search on the packed rows)
+    r3dm_kgraph_hamming_stats kgraph_hamming_stats{};       // r3dm_kgraph_hamming_report: since r3dm_create (never reset)
     DevBuf d_mutual;                                        // its two counters (allocated by the first batch that runs the check)
     // r3dm_set_preemptive_matching (api_preselect.cpp): the switch, its head size and threshold; the buffers of a gate call (row lists,
     // head table, pairs, counts), its events and its report -- all made by the first gate
@@ -751,15 +753,18 @@ int resolve_pairs(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, const
                   std::vector<PairJob>& indexed, std::vector<PairJob>& scanned);
 // the gate of preemptive matching (api_preselect.cpp), called by the four collection entries right after resolve_pairs: resets the
 // report; while the switch is on, both lists keep only the pairs whose head count reaches the threshold under ratio R
-int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned);
+// (bin_ratio_R >= 0: the R of pairs of binary views, where a call's list may mix them with float views under another rule)
+int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned, float bin_ratio_R = -1.0f);
 // What a collection call of an arm is made of.  The chunk rules differ on purpose: KGraph and HNSW launch one descriptor length at a
 // time, MRPT's job records carry their own; HNSW and MRPT launch a grid row per pair (65,535 at most), KGraph does not.
 struct AnnArm {
     PairClassifier classify;
     std::function<int(const std::vector<PairJob>& indexed)> ensure;                    // layouts + indices of the indexed jobs' views
     std::function<int(const std::vector<PairJob>& batch, r3dm_graph* g)> run_batch;    // one chunk of them, appended to g
-    bool one_dim_per_chunk = false;
+    bool one_dim_per_chunk = false;                          // a chunk holds one (dtype, dim)
     size_t max_chunk_pairs = SIZE_MAX;
+    // >= 0: the arm serves binary views, whose scanned pairs and gate take this R (the ratio unsquared: Hamming is no squared metric)
+    float bin_ratio_R = -1.0f;
 };
 // resets c->stats; indexed chunks + scanned pairs (ratio scanned_ratio_R) -> *out, ordered by (I, J)
 int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float scanned_ratio_R, const AnnArm& arm, r3dm_graph** out);
@@ -781,18 +786,26 @@ int with_index_structure(r3dm_ctx* c, const r3dm_index* ix, const void* query, u
                          const std::function<int(const r3dm_index&)>& state, const std::function<int(r3dm_index&, uint32_t slot)>& build,
                          const std::function<int(uint32_t sI, uint32_t sJ)>& search);
 
-// An array entry of an arm (r3dm_kgraph_knn2 and its relatives): two private slots, dataset and query staged as F32 under the view ids
-// (id_i, id_j), the call's counters (CallCounters), then body(slot of the dataset, slot of the queries)
+// An array entry of an arm (r3dm_kgraph_knn2 and its relatives): two private slots, dataset and query staged as `dtype` (F32; R3DM_BIN for
+// the _bits entries, dim = bytes per row) under the view ids (id_i, id_j), the call's counters (CallCounters), then body(slot of the
+// dataset, slot of the queries)
+template <class Body>
+inline int with_staged_pair_of(r3dm_ctx* c, r3dm_dtype dtype, const void* dataset, uint32_t n_dataset, const void* query, uint32_t n_query, uint32_t dim,
+                               uint32_t id_i, uint32_t id_j, std::initializer_list<uint64_t r3dm_stats::*> counts,
+                               std::initializer_list<double r3dm_stats::*> times, Body&& body)
+{
+    R3DM_HIP(c, hipSetDevice(c->device));
+    PrivateSlots s(c, 2);
+    int rc = stage_into_slot(c, s[0], id_i, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
+    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], id_j, 0, 0, query, n_query, dim, dtype, nullptr);
+    if (rc != R3DM_OK) return rc;
+    CallCounters counters(c, counts, times);
+    return body(s[0], s[1]);
+}
 template <class Body>
 inline int with_staged_pair(r3dm_ctx* c, const float* dataset, uint32_t n_dataset, const float* query, uint32_t n_query, uint32_t dim,
                             uint32_t id_i, uint32_t id_j, std::initializer_list<uint64_t r3dm_stats::*> counts,
                             std::initializer_list<double r3dm_stats::*> times, Body&& body)
 {
-    R3DM_HIP(c, hipSetDevice(c->device));
-    PrivateSlots s(c, 2);
-    int rc = stage_into_slot(c, s[0], id_i, 0, 0, dataset, n_dataset, dim, R3DM_F32, nullptr);
-    if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], id_j, 0, 0, query, n_query, dim, R3DM_F32, nullptr);
-    if (rc != R3DM_OK) return rc;
-    CallCounters counters(c, counts, times);
-    return body(s[0], s[1]);
+    return with_staged_pair_of(c, R3DM_F32, dataset, n_dataset, query, n_query, dim, id_i, id_j, counts, times, std::forward<Body>(body));
 }

@@ -573,9 +573,11 @@ size_t     filter_coop_lds_bytes();
 inline size_t filter_coop_model_doubles(int model_kind) { return model_kind == 2 ? 32u * 90u : 64u * 27u; }   // chunk x 9 x MAX_MODELS
 size_t     filter_F_lds_bytes(uint32_t m_cap, int model_kind);
 // rows8: every job carries byte rows -> the all-pairs scan runs on integer dot products (same keys)
-hipError_t launch_ann_build(hipStream_t st, const AnnBuildParams& P, uint32_t n_jobs, uint32_t max_n, uint32_t dim, bool rows8);
+// bin_words != 0: every job is a binary view of that many words per row (8 / 16) -> the Hamming scan of ImgDev::bin (dim unused)
+hipError_t launch_ann_build(hipStream_t st, const AnnBuildParams& P, uint32_t n_jobs, uint32_t max_n, uint32_t dim, bool rows8, uint32_t bin_words = 0);
 // rows_mode: 0 = f32 rows, 1 = ImgDev::ann_rows16 (bf16), 2 = ImgDev::ann_rows8 (u8) -- every indexed view of the batch must hold that copy;
 // 3 = u8 rows on both sides (the query views hold ann_rows8 too): distances as integer dot products
+// 4 = binary views on both sides (ImgDev::bin, 8 / 16 words per row; dim = their bytes): Hamming distances
 // knn_k = 0: the 2-NN search kernels (nn_idx, optional 2-lists); 1 .. R3DM_KNN_MAX: their k-list instantiations, which write
 // knn_idx / knn_dist [slot][knn_k] and no ratio test (pool_cap = knn_k + P; the caller sets ef = max(ef, knn_k))
 hipError_t launch_ann_search(hipStream_t st, const AnnSearchParams& P, uint32_t max_nJ, uint32_t max_nI, uint32_t dim, int rows_mode, uint32_t knn_k = 0);

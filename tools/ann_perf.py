@@ -1,5 +1,8 @@
 """Config C5 probe: graph-based approximate matching vs the exhaustive matcher on the same views
-(throughput, distance evaluations, recall of the exhaustive putative matches).  Not the bench contract."""
+(throughput, distance evaluations, recall of the exhaustive putative matches).  Not the bench contract.
+--kind akaze: binary rows (MLDB-486 shaped) -- the two exhaustive Hamming paths against the Hamming graph matcher (r3dm_set_kgraph_hamming),
+R = 0.8 unsquared as config C3; the methods alternate over --rounds rounds in this one process, each timed call ends in the library's
+own synchronisation, the median per method is the figure (profiles/ann_hamming_perf.txt)."""
 import argparse, json, sys, time, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -17,7 +20,82 @@ ap.add_argument("--hnsw", default="fast,medium,precise", help="HNSW presets to t
 ap.add_argument("--mrpt", type=int, default=1, help="time the MRPT arm (matchingAlgorithm 5) as well")
 ap.add_argument("--S", type=int, default=0, help="override search_S (0 = preset)")
 ap.add_argument("--K", type=int, default=0, help="override index_K (0 = preset)")
+ap.add_argument("--rounds", type=int, default=3, help="--kind akaze: rounds the methods alternate over")
 a = ap.parse_args()
+
+
+def akaze_probe():
+    ratio = 0.8
+    t = time.time(); sc = synth.make_scene(a.images, a.feat, "akaze", seed=2005); print("gen %.1fs" % (time.time() - t), flush=True)
+    descs = [np.ascontiguousarray(d[:, :61]) for d in sc.descs]
+    c = api.Context(0)
+    c.set_kgraph_hamming(True)
+    for i in range(sc.n_images):
+        c.set_image(i, descs[i], sc.xys[i], 4000, 3000, binary=True)
+    pairs = sc.exhaustive_pairs()
+    presets = [x for x in a.presets.split(",") if x]
+    params = {}
+    for name in presets:
+        kp = api.KGraphParams.preset(name)
+        if a.S: kp.search_S = a.S
+        if a.K: kp.index_K = a.K
+        params[name] = kp
+
+    def exhaustive(mfma):
+        c.set_hamming_mfma(mfma)
+        t0 = time.time(); g = c.match_pairs(pairs, ratio, False); dt = time.time() - t0
+        st = c.stats()
+        assert st.n_hamming_mfma == (st.n_match_launches if mfma else 0)
+        return g, dt, st
+
+    def graph(name):
+        t0 = time.time(); g = c.match_pairs_kgraph(pairs, ratio, params[name]); dt = time.time() - t0
+        return g, dt, c.stats()
+
+    # warm-up: every shape of the timed window once; the first graph call of a preset also builds (and times) its indices
+    base, _, _ = exhaustive(False)
+    gm, _, _ = exhaustive(True)
+    assert np.array_equal(gm.matches, base.matches) and np.array_equal(gm.offsets, base.offsets), "the two exhaustive Hamming paths differ"
+    bd, nb = base.as_dict(), base.num_matches
+    build, quality = {}, {}
+    for name in presets:
+        c.drop_indices()
+        g, _, st = graph(name)
+        build[name] = (st.ms_ann_build, st.n_ann_built)
+        d = g.as_dict()
+        hit = sum(len(set(map(tuple, d[k].tolist())) & set(map(tuple, bd[k].tolist()))) for k in d if k in bd)
+        quality[name] = (g.num_matches, hit / max(nb, 1), hit / max(g.num_matches, 1), (g.pairs.tobytes(), g.matches.tobytes()))
+    # the timed rounds: methods alternate; indices of the last preset stay cached only when its K equals the next one's, so every graph
+    # call is preceded by an untimed one that leaves its own indices in place
+    times = {m: [] for m in ["popcount", "mfma"] + presets}
+    kern = {m: [] for m in times}
+    evals = {}
+    for _ in range(a.rounds):
+        _, dt, st = exhaustive(False); times["popcount"].append(dt); kern["popcount"].append(st.ms_match_kernels)
+        _, dt, st = exhaustive(True); times["mfma"].append(dt); kern["mfma"].append(st.ms_match_kernels)
+        for name in presets:
+            graph(name)
+            g, dt, st = graph(name)
+            assert st.n_ann_built == 0 and (g.pairs.tobytes(), g.matches.tobytes()) == quality[name][3], "cached graph call rebuilt or changed"
+            times[name].append(dt); kern[name].append(st.ms_ann_search)
+            evals[name] = st.n_ann_dist / max(st.n_queries, 1)
+    c.set_hamming_mfma(False)
+    med = lambda v: float(np.median(v))
+    for m, label in (("popcount", "exhaustive-hamming-popcount"), ("mfma", "exhaustive-hamming-mfma")):
+        print(json.dumps(dict(method=label, rows=a.feat, views=a.images, pairs=len(pairs), ratio=ratio, s_median=med(times[m]), s_all=times[m],
+                              pairs_per_s=len(pairs) / med(times[m]), ms_kernel=med(kern[m]), matches=nb)), flush=True)
+    for name in presets:
+        kp = params[name]
+        print(json.dumps(dict(method="kgraph-hamming-" + name, rows=a.feat, views=a.images, pairs=len(pairs), ratio=ratio, K=kp.index_K, P=kp.search_P,
+                              S=kp.search_S, s_cached_median=med(times[name]), s_all=times[name], pairs_per_s=len(pairs) / med(times[name]),
+                              ms_build_per_view=build[name][0] / max(build[name][1], 1), ms_search=med(kern[name]), evals_per_query=evals[name],
+                              matches=quality[name][0], match_recall=quality[name][1], match_precision=quality[name][2])), flush=True)
+    c.close()
+
+
+if a.kind == "akaze":
+    akaze_probe()
+    sys.exit(0)
 
 t = time.time(); sc = synth.make_scene(a.images, a.feat, a.kind, seed=2005); print("gen %.1fs" % (time.time() - t), flush=True)
 c = api.Context(0)
