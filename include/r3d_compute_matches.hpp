@@ -128,6 +128,17 @@ public:
     // is what setDirectRegistration(false) does.  128 / 4 are Wu's SIFT-era 100 / 4 rounded to a tile multiple, not tuned for LIOP.  Off by
     // default: the match files are the reference's only while it is off.
     void setPreemptiveMatching(bool on, uint32_t head_rows = 128, uint32_t min_matches = 4);
+    // no reference counterpart (the reference matches exhaustivePairs): instead of all pairs, the stage matches the pairs that
+    // r3dm_propose_pairs proposes (the contract is in r3dm.h).  After the views are registered it samples a vocabulary of n_words rows
+    // from them in view-id order (r3dm_vocab_sample; lowered to half the collection's rows when it has fewer than 2 n_words), proposes
+    // every view's top_k partners on its first device context, and hands that list to the matcher it would have run anyway -- on a device
+    // list through the same r3dm_shard_pairs deal as ever.  The match files are then those of the switch-off run restricted to the
+    // proposed pairs, byte for byte, on every arm; pairs that are not proposed are never matched.  With setPreemptiveMatching on as well,
+    // the gate sees the proposed pairs.  A collection with fewer than 4 rows or 2 views keeps all pairs.  16,384 / 20 are untuned defaults.
+    // Off by default: the match files are the reference's only while it is off.
+    void setPairProposal(bool on, uint32_t n_words = 16384, uint32_t top_k = 20);
+    // pairs the last computeMatches call handed to its matcher (all pairs, or the proposed ones)
+    uint64_t lastPairCount() const { return last_pair_count_; }
     // How the approximate arms of the dispatch (0 FLANN, 1-3 KGraph, 5 MRPT, 6-8 HNSW) are served.  kArmsFastest (default): by the
     // EXHAUSTIVE matcher whenever r3dm_exhaustive_is_faster says it is not slower on the registered views -- on LIOP-144 every
     // approximate arm is then exact and >= 2x faster than the graph search (the GUI's default arm 0 included); kArmsAsRequested:
@@ -218,6 +229,9 @@ private:
     const size_t* sink_need_ = nullptr;    // views of the running features chunk
     bool direct_registration_ = true;
     bool preemptive_on_ = false;
+    bool proposal_on_ = false;
+    uint32_t proposal_words_ = 16384, proposal_top_k_ = 20;
+    uint64_t last_pair_count_ = 0;
     int background_nice_ = 0;
     static int features_sink(void* self, uint32_t image_index, uint32_t n_features, const float* desc_device, const float* xy_as_written);
     ImageProviderFn provider_ = nullptr;
@@ -279,11 +293,12 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_DESCRIPTOR_MLDB 512u   /* setRegionsType(R3DM_BIN, 61): the features stage writes MLDB-486 rows (r3dm_set_descriptor_arm), the matcher runs its binary rules; default LIOP (float x 144) */
 #define R3DM_STAGE_DESCRIPTOR_MSURF 1024u /* setRegionsType(R3DM_F32, 64): the features stage writes M-SURF-64 rows (r3dm_set_descriptor_arm); together with R3DM_STAGE_DESCRIPTOR_MLDB: R3DM_ERR_INVALID */
 #define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
+#define R3DM_STAGE_PAIR_PROPOSAL 2048u /* the matcher gets the pairs r3dm_propose_pairs proposes, not all pairs (R3DComputeMatches::setPairProposal(true)): 16,384 words, lowered to half the collection's rows when it is smaller, top_k 20 -- untuned defaults */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
-/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_F32_TILES */
+/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_F32_TILES */
 int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                                    r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
                                    uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);

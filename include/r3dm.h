@@ -241,6 +241,75 @@ typedef struct {
 } r3dm_preselect_stats;
 int r3dm_preselect_report(const r3dm_ctx* ctx, r3dm_preselect_stats* out);
 
+/* Pair proposal from bag-of-words view signatures (no reference counterpart -- the reference matches exhaustivePairs, SURVEY.md section
+ * 5, and parity with it depends on that: nothing proposes pairs unless a caller asks).  Instead of matching all n (n - 1) / 2 pairs of a
+ * collection, quantise every descriptor to a visual word, describe a view by its word histogram, score every pair of views by histogram
+ * intersection and match only each view's top_k best partners.  PAIRS THAT ARE NOT PROPOSED ARE NEVER MATCHED: retrieval trades recall of
+ * the pair graph for time.  Every quantity below is an integer, so a result depends on (rows, vocabulary, view list, top_k) only.
+ *
+ * Vocabulary.  n_words rows of one type and length, 2 <= n_words <= 65,536: F32 or U8 rows of any length the exhaustive matcher serves,
+ * BIN rows of the byte lengths it serves (29..32, 61..64; others R3DM_ERR_UNSUPPORTED).  It belongs to the device of the context that
+ * made it and may be used with any context of that device.
+ *   r3dm_vocab_sample: a deterministic even sample of registered views -- no RNG, no k-means.  All listed views must be registered, of
+ *     one type and one length, and listed once; otherwise R3DM_ERR_INVALID.  Let T be the total row count of the listed views and their
+ *     rows be concatenated in list order: word t is row floor((2 t + 1) T / (2 n_words)), in 64-bit integer arithmetic, t = 0 ..
+ *     n_words - 1.  T < n_words is R3DM_ERR_INVALID.  The rows are gathered on the device from the views' resident layouts.
+ *   r3dm_vocab_from_rows: the caller's own words, n_words x dim elements in host memory (floats for F32, bytes for U8 / BIN).
+ *   r3dm_vocab_words: copies the words back (n_words x dim elements of the vocabulary's type): tests, callers that save a codebook.
+ *   r3dm_vocab_free: releases the vocabulary and its signatures.  A failed creation leaves *out NULL and nothing behind.
+ *
+ * Word of a row.  Its nearest word under the reference's distance -- exact_l2sq for F32 / U8 rows (4-way unrolled, scalar tail, no FMA),
+ * popcount Hamming for BIN rows -- ties to the lowest word index.  It is the first neighbour the exhaustive matcher returns with the
+ * codebook staged as a private dataset view and the registered view as the query side (as r3dm_knn2 stages its arrays), so whichever
+ * exact tile path the context's switches select (f32, r3dm_set_integer_mfma, r3dm_set_split_mfma, r3dm_set_hamming_mfma) gives the
+ * same words.  r3dm_stats is left as the call found it.
+ *
+ * Signature of a view.  h[w] = the number of the view's rows whose word is w, u32; an empty view has an all-zero signature.  Signatures
+ * live in the vocabulary, keyed by view id and by the view's registration: r3dm_set_image(s) on that id, or r3dm_clear_images, makes a
+ * signature stale, and a stale or missing signature is rebuilt by the next call that needs it.
+ *
+ * Score of a pair.  s(i, j) = sum over w of min(h_i[w], h_j[w]), u32; s <= min(n_i, n_j).  s(i, i) is not used.
+ *
+ * Rank.  For view i the candidates are the other listed views j with n_j > 0; a view with n_i = 0 proposes nothing and is proposed by
+ * nobody.  Candidates are ordered by key(i, j) = floor(s(i, j) * 2^32 / min(n_i, n_j)), computed in u64, descending, then by view id
+ * ascending.  An integer key on purpose: a float division would make the order depend on rounding.
+ *
+ * r3dm_propose_pairs: builds the missing signatures, takes the first min(top_k, candidates) of every listed view's rank and returns the
+ *   union as pairs (min id, max id), unique, sorted by (I, J), in pairs_out (2 ids per pair); *n_pairs_out = their number.  top_k >= 1.
+ *   cap_pairs (the room of pairs_out, in pairs) below n_views * top_k is R3DM_ERR_INVALID: the union never exceeds that.  scores_out may
+ *   be NULL; otherwise [n_views][n_views] u32 in list order, the diagonal 0.  R3DM_ERR_INVALID as well: an unregistered view, an id listed
+ *   twice, a view whose type or length differs from the vocabulary's, n_views of 0.
+ * r3dm_view_signatures: the primitive -- the histograms of the listed views, [n_views][n_words] u32 in list order; same refusals.
+ * r3dm_vocab_report: the last r3dm_propose_pairs or r3dm_view_signatures call on the vocabulary.
+ *
+ * Cost.  Signatures: n_words * 4 bytes per view (rounded up to 16), in the vocabulary; a call's scratch is the matcher's own.  A view's
+ * r3dm_view_info changes only as a match call on it would change it (layouts staged on first use).  While no vocabulary exists nothing is
+ * allocated or launched; r3dm_stats gains no field.  The matchers know nothing of vocabularies: hand the proposed pairs to r3dm_match_pairs
+ * or any other collection entry (r3dm_shard_pairs for a device list), and the graph is that of all pairs restricted to the proposed ones,
+ * bit for bit; with r3dm_set_preemptive_matching on, the gate sees the proposed pairs.  The kernels are in kernels_vocab.hip; the
+ * histogram kernel counts in LDS up to R3DM_VOCAB_HIST_LDS_WORDS words and with global atomics beyond, the score kernel streams the word
+ * axis in chunks of R3DM_VOCAB_WORD_CHUNK -- both only matter to tests that straddle them. */
+#define R3DM_VOCAB_MAX_WORDS 65536u
+#define R3DM_VOCAB_HIST_LDS_WORDS 8192u
+#define R3DM_VOCAB_WORD_CHUNK 32u
+typedef struct r3dm_vocab r3dm_vocab;
+int  r3dm_vocab_sample(r3dm_ctx* ctx, const uint32_t* view_ids, uint32_t n_views, uint32_t n_words, r3dm_vocab** out);
+int  r3dm_vocab_from_rows(r3dm_ctx* ctx, const void* rows /* host */, uint32_t n_words, uint32_t dim, r3dm_dtype dtype, r3dm_vocab** out);
+int  r3dm_vocab_info(const r3dm_vocab* vocab, uint32_t* n_words, uint32_t* dim, int32_t* dtype);      /* any pointer may be NULL */
+int  r3dm_vocab_words(const r3dm_vocab* vocab, void* rows_out /* host */);
+void r3dm_vocab_free(r3dm_vocab* vocab);
+int  r3dm_view_signatures(r3dm_ctx* ctx, r3dm_vocab* vocab, const uint32_t* view_ids, uint32_t n_views, uint32_t* hist_out /* host */);
+int  r3dm_propose_pairs(r3dm_ctx* ctx, r3dm_vocab* vocab, const uint32_t* view_ids, uint32_t n_views, uint32_t top_k,
+                        uint32_t* pairs_out /* host, 2 x cap_pairs */, uint64_t cap_pairs, uint64_t* n_pairs_out, uint32_t* scores_out /* host, or NULL */);
+typedef struct {
+    double   ms_quantise;              /* HIP-event time of staging the codebook and the matcher's batches */
+    double   ms_histogram, ms_score, ms_select;      /* ... of the histogram, score and selection kernels */
+    uint64_t n_rows_quantised;         /* rows sent through the matcher by the call */
+    uint64_t n_signatures_built;       /* signatures the call made (missing or stale) */
+    uint64_t n_signatures_cached;      /* ... and found valid */
+} r3dm_vocab_stats;
+int  r3dm_vocab_report(const r3dm_vocab* vocab, r3dm_vocab_stats* out);
+
 /* ---- putative matching ----
  * pairs_ij: n_pairs x 2 view ids (I, J); J's rows are the queries, I's rows the dataset.
  * Descriptor lengths and speed: the tensor kernels serve float / byte rows of up to 64, 128, 144 and 256 elements (rows are padded

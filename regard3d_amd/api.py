@@ -51,6 +51,8 @@ EXPORTS = [
     "r3dm_set_prefix_pruning", "r3dm_get_prefix_pruning_counts", "r3dm_multi_set_prefix_pruning", "r3dm_multi_get_prefix_pruning_counts",
     "r3dm_get_pair_filter_counts", "r3dm_multi_get_pair_filter_counts",
     "r3dm_detect_akaze_msurf", "r3dm_detect_akaze_msurf_batch",
+    "r3dm_vocab_sample", "r3dm_vocab_from_rows", "r3dm_vocab_info", "r3dm_vocab_words", "r3dm_vocab_free", "r3dm_view_signatures", "r3dm_propose_pairs",
+    "r3dm_vocab_report",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
@@ -59,6 +61,8 @@ STAGE_MUTUAL_MATCHING = 128
 STAGE_PREEMPTIVE_MATCHING = 256
 STAGE_DESCRIPTOR_MLDB = 512
 STAGE_DESCRIPTOR_MSURF = 1024
+STAGE_PAIR_PROPOSAL = 2048                        # R3DM_STAGE_PAIR_PROPOSAL: 16,384 words (half the collection's rows when that is less), top_k 20
+VOCAB_MAX_WORDS, VOCAB_HIST_LDS_WORDS, VOCAB_WORD_CHUNK = 65536, 8192, 32      # R3DM_VOCAB_* (include/r3dm.h)
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
 # the descriptor arms, the rows of csrc/descriptor_arms.hpp (tests/test_descriptor_arms.py holds the two to each other): name, id
@@ -122,6 +126,45 @@ class PreselectStats(C.Structure):
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class VocabStats(C.Structure):
+    """r3dm_vocab_stats: the last propose_pairs / view_signatures call on a vocabulary"""
+    _fields_ = [("ms_quantise", C.c_double), ("ms_histogram", C.c_double), ("ms_score", C.c_double), ("ms_select", C.c_double),
+                ("n_rows_quantised", C.c_uint64), ("n_signatures_built", C.c_uint64), ("n_signatures_cached", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Vocab:
+    """r3dm_vocab (include/r3dm.h, "Pair proposal"): n_words rows of one type and length, and the signatures of the views counted
+    against them.  Made by Context.vocab_sample / vocab_from_rows; close() releases it."""
+
+    def __init__(self, L, handle):
+        self._L, self._h = L, handle
+        nw, dim, dt = C.c_uint32(0), C.c_uint32(0), C.c_int32(0)
+        L.r3dm_vocab_info(handle, C.byref(nw), C.byref(dim), C.byref(dt))
+        self.n_words, self.dim, self.dtype = int(nw.value), int(dim.value), int(dt.value)
+
+    def words(self) -> np.ndarray:
+        """r3dm_vocab_words: the codebook, [n_words, dim] float32 (F32) or uint8 (U8 / BIN)"""
+        out = np.zeros((self.n_words, self.dim), np.float32 if self.dtype == F32 else np.uint8)
+        rc = self._L.r3dm_vocab_words(self._h, out.ctypes.data)
+        if rc != 0:
+            raise R3dmError(f"r3dm_vocab_words -> {rc}")
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.r3dm_vocab_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class GuidedStats(C.Structure):
@@ -211,11 +254,12 @@ class Stage:
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP") -> StageReport:
+            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False) -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
         (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING); preemptive: preemptive matching at 128 / 4
         (R3DM_STAGE_PREEMPTIVE_MATCHING); descriptor: "LIOP", "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB: binary regions, 61 bytes) or "MSURF"
-        (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64, 64 floats)"""
+        (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64, 64 floats); proposal: the matcher gets the pairs r3dm_propose_pairs proposes
+        (R3DM_STAGE_PAIR_PROPOSAL)"""
         dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
         keep = []
         arr = _stage_views(views, keep)
@@ -223,7 +267,7 @@ class Stage:
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                     (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | dflag, C.byref(rep), err, 1024)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | dflag, C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -244,14 +288,16 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP") -> StageReport:
+                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False) -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
     detector: "Fast-AKAZE" (default) or "AKAZE" (R3DM_STAGE_DETECTOR_AKAZE); mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive:
     R3DM_STAGE_PREEMPTIVE_MATCHING (head_rows 128, min_matches 4); descriptor: "LIOP" (default), "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB:
     the features stage writes MLDB-486 rows, the matcher runs its binary rules) or "MSURF" (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64
-    rows of 64 floats, matched by the float rules as LIOP is)."""
+    rows of 64 floats, matched by the float rules as LIOP is); proposal: R3DM_STAGE_PAIR_PROPOSAL (the matcher gets the pairs
+    r3dm_propose_pairs proposes from a vocabulary sampled from the stage's views: 16,384 words, half the collection's rows when that is
+    less, top_k 20)."""
     dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
     L = load_library()
     keep = []
@@ -262,7 +308,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                       (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | dflag, C.byref(rep), err, 1024)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | dflag, C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
@@ -274,11 +320,12 @@ class _DirView(C.Structure):
 
 
 def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0, dim: int = 144, dist_ratio: float = 0.6,
-                        compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False, preemptive: bool = False):
+                        compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False, preemptive: bool = False,
+                        proposal: bool = False):
     """R3DComputeMatches::computeMatches over a directory that holds every view's .feat / .desc (r3dm_compute_matches_dir_flags):
     exhaustive matching, the F filter when asked, matches.putative.txt / matches.f.txt.  views: dicts with id, width, height,
     basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive: R3DM_STAGE_PREEMPTIVE_MATCHING (the .feat scale column is
-    every view's priority).  -> (putative pairs, geometric pairs)"""
+    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL.  -> (putative pairs, geometric pairs)"""
     L = load_library()
     arr = (_DirView * len(views))(*[_DirView(int(v["id"]), int(v["width"]), int(v["height"]), str(v["basename"]).encode()) for v in views])
     npp, ngp = C.c_uint64(0), C.c_uint64(0)
@@ -286,7 +333,8 @@ def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0,
     L.r3dm_compute_matches_dir_flags.argtypes = [C.c_int, C.c_char_p, C.c_void_p, C.c_uint32, C.c_int, C.c_uint32, C.c_float, C.c_int, C.c_uint64,
                                                  C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     rc = L.r3dm_compute_matches_dir_flags(device_id, matches_dir.encode(), arr, len(views), dtype, dim, dist_ratio, int(compute_F), seed,
-                                          (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0),
+                                          (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0)
+                                          | (STAGE_PAIR_PROPOSAL if proposal else 0),
                                           C.byref(npp), C.byref(ngp), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_dir_flags -> {rc}: {err.value.decode()}")
@@ -412,6 +460,14 @@ def load_library():
     L.r3dm_set_preemptive_matching.argtypes = [vp, C.c_int, u32, u32]
     L.r3dm_multi_set_preemptive_matching.argtypes = [vp, C.c_int, u32, u32]
     L.r3dm_preselect_report.argtypes = [vp, vp]
+    L.r3dm_vocab_sample.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
+    L.r3dm_vocab_from_rows.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
+    L.r3dm_vocab_info.argtypes = [vp, vp, vp, vp]
+    L.r3dm_vocab_words.argtypes = [vp, vp]
+    L.r3dm_vocab_free.argtypes = [vp]; L.r3dm_vocab_free.restype = None
+    L.r3dm_view_signatures.argtypes = [vp, vp, vp, u32, vp]
+    L.r3dm_propose_pairs.argtypes = [vp, vp, vp, u32, u32, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
+    L.r3dm_vocab_report.argtypes = [vp, vp]
     L.r3dm_index_create.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
     L.r3dm_index_knn2.argtypes = [vp, vp, vp, u32, vp, vp]
     L.r3dm_index_destroy.argtypes = [vp]; L.r3dm_index_destroy.restype = None
@@ -1417,6 +1473,53 @@ class Context:
         """r3dm_preselect_report: the gate of the last call (times, pairs, pairs kept, heads built, views without priority)"""
         s = PreselectStats()
         self._check(self._L.r3dm_preselect_report(self._h, C.byref(s)), "r3dm_preselect_report")
+        return s.as_dict()
+
+    def vocab_sample(self, view_ids, n_words: int) -> Vocab:
+        """r3dm_vocab_sample: a vocabulary of n_words rows, the deterministic even sample of the listed registered views (one type,
+        one length, each listed once): word t is row floor((2 t + 1) T / (2 n_words)) of their T rows in list order"""
+        ids = np.ascontiguousarray(view_ids, np.uint32).reshape(-1)
+        h = C.c_void_p()
+        self._check(self._L.r3dm_vocab_sample(self._h, _ptr(ids) if ids.size else None, ids.size, n_words, C.byref(h)), "r3dm_vocab_sample")
+        return Vocab(self._L, h.value)
+
+    def vocab_from_rows(self, rows, binary: bool = False) -> Vocab:
+        """r3dm_vocab_from_rows: the caller's own words, [n_words, dim] float32 (F32), uint8 (U8) or uint8 with binary=True (BIN)"""
+        rows = np.asarray(rows)
+        dtype = BIN if binary else (U8 if rows.dtype == np.uint8 else F32)
+        rows = np.ascontiguousarray(rows, np.uint8 if dtype != F32 else np.float32)
+        h = C.c_void_p()
+        self._check(self._L.r3dm_vocab_from_rows(self._h, _ptr(rows) if rows.size else None, rows.shape[0], rows.shape[1] if rows.ndim == 2 else 0, dtype,
+                                                 C.byref(h)), "r3dm_vocab_from_rows")
+        return Vocab(self._L, h.value)
+
+    def view_signatures(self, vocab: Vocab, view_ids) -> np.ndarray:
+        """r3dm_view_signatures: the word histograms of the listed views, [n_views, n_words] uint32 in list order"""
+        ids = np.ascontiguousarray(view_ids, np.uint32).reshape(-1)
+        out = np.zeros((ids.size, vocab.n_words), np.uint32)
+        self._check(self._L.r3dm_view_signatures(self._h, vocab._h, _ptr(ids) if ids.size else None, ids.size, _ptr(out) if out.size else None), "r3dm_view_signatures")
+        return out
+
+    def propose_pairs(self, vocab: Vocab, view_ids, top_k: int, with_scores: bool = False, cap_pairs=None):
+        """r3dm_propose_pairs: every listed view's top_k partners by histogram intersection, as unique pairs (min id, max id) sorted by
+        (I, J): [n_pairs, 2] uint32 -- and, with_scores, the [n_views, n_views] uint32 score matrix in list order (diagonal 0).
+        cap_pairs: the room handed to the library (default n_views * top_k, the least it accepts)"""
+        ids = np.ascontiguousarray(view_ids, np.uint32).reshape(-1)
+        cap = ids.size * max(int(top_k), 0) if cap_pairs is None else int(cap_pairs)
+        pairs = np.zeros((max(cap, 1), 2), np.uint32)
+        scores = np.zeros((ids.size, ids.size), np.uint32) if with_scores else None
+        n = C.c_uint64(0)
+        self._check(self._L.r3dm_propose_pairs(self._h, vocab._h, _ptr(ids) if ids.size else None, ids.size, top_k, _ptr(pairs), cap, C.byref(n),
+                                               _ptr(scores) if with_scores and scores.size else None), "r3dm_propose_pairs")
+        pairs = pairs[:int(n.value)].copy()
+        return (pairs, scores) if with_scores else pairs
+
+    def vocab_report(self, vocab: Vocab) -> dict:
+        """r3dm_vocab_report: rows quantised, signatures built / cached and the HIP-event times of the phases of the last call"""
+        s = VocabStats()
+        rc = self._L.r3dm_vocab_report(vocab._h, C.byref(s))
+        if rc != 0:
+            raise R3dmError(f"r3dm_vocab_report -> {rc}")
         return s.as_dict()
 
     def set_split_mfma(self, enable: bool = True):

@@ -230,7 +230,7 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
         if (rcl == R3DM_OK && !counts_ok) { plan = without_count_tiles(plan); rcl = ensure_layouts(c, batch_slots, plan.layouts); }
         if (rcl != R3DM_OK) return rcl;
     }
-    const uint32_t q_stride = std::max<uint32_t>(32, (max_nJ + 31) / 32 * 32);
+    const uint32_t q_stride = match_q_stride(max_nJ);
     const uint32_t sort_cap = std::min<uint32_t>(16384, std::max<uint32_t>(8, next_pow2(q_stride)));   // LDS budget; larger views may spill
 
     std::vector<uint2> hp(P);

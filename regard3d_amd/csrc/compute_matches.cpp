@@ -346,6 +346,12 @@ void R3DComputeMatches::setPreemptiveMatching(bool on, uint32_t head_rows, uint3
     preemptive_on_ = on && rc == R3DM_OK;
 }
 
+void R3DComputeMatches::setPairProposal(bool on, uint32_t n_words, uint32_t top_k)
+{
+    proposal_on_ = on && n_words >= 2 && n_words <= R3DM_VOCAB_MAX_WORDS && top_k >= 1;
+    proposal_words_ = n_words; proposal_top_k_ = top_k;
+}
+
 void R3DComputeMatches::setGuidedMatching(bool on, double ratio_F, double ratio_E, double ratio_H)
 {
     if (ctx_) (void)r3dm_set_guided_matching(ctx_, on ? 1 : 0, ratio_F, ratio_E, ratio_H);
@@ -493,6 +499,26 @@ bool R3DComputeMatches::computeMatches(R3DFParams& params, bool svgOutput, const
     std::vector<uint32_t> pairs;
     for (size_t a = 0; a < ids.size(); ++a)
         for (size_t b = a + 1; b < ids.size(); ++b) { pairs.push_back(ids[a]); pairs.push_back(ids[b]); }
+    // ---- setPairProposal: the pairs r3dm_propose_pairs proposes instead (no reference counterpart).  The views are replicated on every
+    // device of a list, so the first context holds them all; the matchers below deal whatever list they get
+    if (proposal_on_ && ids.size() >= 2) {
+        uint64_t T = 0;
+        for (int n : statistics_.numberOfKeypoints_) T += (uint64_t)n;
+        const uint32_t n_words = (uint32_t)std::min<uint64_t>(proposal_words_, T / 2);
+        if (n_words >= 2) {
+            r3dm_ctx* pc = ctx_ ? ctx_ : r3dm_multi_ctx(multi_, 0);
+            r3dm_vocab* vocab = nullptr;
+            int rcp = r3dm_vocab_sample(pc, ids.data(), (uint32_t)ids.size(), n_words, &vocab);
+            std::vector<uint32_t> proposed(2 * ids.size() * (size_t)proposal_top_k_);
+            uint64_t n_proposed = 0;
+            if (rcp == R3DM_OK) rcp = r3dm_propose_pairs(pc, vocab, ids.data(), (uint32_t)ids.size(), proposal_top_k_, proposed.data(), proposed.size() / 2, &n_proposed, nullptr);
+            r3dm_vocab_free(vocab);
+            if (rcp != R3DM_OK) { errorMessage_ = std::string("pair proposal: ") + r3dm_last_error(pc); return false; }
+            proposed.resize(2 * (size_t)n_proposed);
+            pairs.swap(proposed);
+        }
+    }
+    last_pair_count_ = pairs.size() / 2;
 
     phases_.load = wall_ms() - t_load;
     if (progress_) progress_(0.7f, "Find putative matches", progress_user_);
@@ -731,6 +757,7 @@ extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3d
         stage.setGuidedMatching((flags & R3DM_STAGE_GUIDED_MATCHING) != 0);
         stage.setMutualMatching((flags & R3DM_STAGE_MUTUAL_MATCHING) != 0);
         stage.setPreemptiveMatching((flags & R3DM_STAGE_PREEMPTIVE_MATCHING) != 0);
+        stage.setPairProposal((flags & R3DM_STAGE_PAIR_PROPOSAL) != 0);
         const DescriptorArm& arm = *descriptor_arm_by_id((flags & R3DM_STAGE_DESCRIPTOR_MLDB) ? R3DM_DESCRIPTOR_MLDB : (flags & R3DM_STAGE_DESCRIPTOR_MSURF) ? R3DM_DESCRIPTOR_MSURF : R3DM_DESCRIPTOR_LIOP);
         stage.setRegionsType(arm.dtype, arm.dim);
         r3d_amd::R3DFParams params;
@@ -806,6 +833,7 @@ extern "C" int r3dm_compute_matches_dir_flags(int device_id, const char* matches
     if (flags & R3DM_STAGE_F32_TILES) stage.setExactFastPaths(false);
     if (flags & R3DM_STAGE_MUTUAL_MATCHING) stage.setMutualMatching(true);
     if (flags & R3DM_STAGE_PREEMPTIVE_MATCHING) stage.setPreemptiveMatching(true);
+    if (flags & R3DM_STAGE_PAIR_PROPOSAL) stage.setPairProposal(true);
     r3d_amd::R3DFParams params;
     params.distRatio_ = dist_ratio;
     params.computeFundalmentalMatrix_ = compute_F != 0;

@@ -4,6 +4,7 @@
 //                     every finalisation into a graph (finalize_batch), one certificate slack
 //                     (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
 //   api_preselect.cpp preemptive matching: view priorities, heads, the gate behind resolve_pairs, r3dm_preselect_pairs
+//   api_vocab.cpp     pair proposal: vocabularies, view signatures through the exhaustive matcher, scores, top-k selection
 //   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
 //   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules
@@ -254,7 +255,10 @@ struct ViewState {
     uint32_t mrpt_trees = 0, mrpt_depth = 0; float mrpt_density = 0.0f; uint64_t mrpt_seed = 0;          // MRPT index, valid when mrpt_trees != 0
     std::vector<float> priority;      // r3dm_set_view_priority: one per row, or empty
     uint32_t head_h = 0, head_n = 0;  // kLayHead: the head size the head buffer was made for, and its rows (min(head_h, n))
+    uint64_t serial = 0;              // this registration's number, unique in the process (new_tenant); 0: no tenant.  Keys what outlives
+                                      // a registration outside the context: the signatures of an r3dm_vocab (api_vocab.cpp)
 };
+inline std::atomic<uint64_t> g_view_serial{0};
 
 // A slot of a context's view table.  What survives which transition:
 //   ViewState        the tenant: replaced as a whole when a view is staged into the slot (new_tenant) and reset when the collection is
@@ -281,6 +285,7 @@ struct HostImage : ViewState {
     {
         static_cast<ViewState&>(*this) = ViewState();
         view_id = id; n = n_; dim = dim_; dtype = dtype_; width = width_; height = height_; has_xy = xy; live = true;
+        serial = g_view_serial.fetch_add(1, std::memory_order_relaxed) + 1;
     }
     void clear()
     {
@@ -308,6 +313,10 @@ inline uint32_t kernel_G_for(uint32_t dim)
     if (g <= 32) return 32;
     return g;               // no tensor kernel: exact scan only
 }
+
+// entries per pair of a match batch's nn_idx / 2-lists, for the longest query view of the batch (run_match_batch; api_vocab.cpp reads
+// the 2-lists of its batches where the matcher left them)
+inline uint32_t match_q_stride(uint32_t max_nJ) { return std::max<uint32_t>(32, (max_nJ + 31) / 32 * 32); }
 
 inline uint32_t next_pow2(uint32_t v) { uint32_t p = 1; while (p < v) p <<= 1; return p; }
 

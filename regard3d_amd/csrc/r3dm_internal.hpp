@@ -289,6 +289,30 @@ struct HeadMatchParams {
     float           ratio_R;      // ratio^2 (squared metric) or ratio
 };
 
+// pair proposal from bag-of-words view signatures (kernels_vocab.hip; r3dm_propose_pairs, r3dm_view_signatures)
+constexpr uint32_t kVocabHistLdsWords = 8192;       // largest vocabulary whose histogram a workgroup privatises in LDS (32 KiB); R3DM_VOCAB_HIST_LDS_WORDS
+constexpr uint32_t kVocabTile = 64;                 // views per side of a score tile
+constexpr uint32_t kVocabChunk = 32;                // words of a score tile's LDS stage; R3DM_VOCAB_WORD_CHUNK
+struct VocabHistJob {
+    const int32_t* idx;           // the view's 2-lists as the matcher leaves them: [n][2], entry 0 = the row's word
+    uint32_t       n;             // rows of the view
+    uint32_t*      hist;          // [n_words], zeroed by the host
+};
+struct VocabScoreParams {
+    const uint32_t* sig;          // signatures, `stride` words apart (a multiple of 4; the words past n_words are zero)
+    const uint32_t* sig_row;      // [n_views]: the signature of every listed view
+    uint32_t        stride, n_views;
+    uint32_t        words_per_z;  // words of a workgroup's slice of the word axis (a multiple of kVocabChunk)
+    uint32_t*       scores;       // [n_views][n_views], zeroed by the host; the diagonal stays 0
+};
+struct VocabSelectParams {
+    const uint32_t* scores;       // [n_views][n_views]
+    const uint32_t* n_rows;       // [n_views]: rows of every listed view
+    const uint32_t* rank;         // [n_views]: place of every listed view in view-id order
+    uint32_t        n_views, top_k;
+    uint32_t*       sel;          // [n_views][top_k]: ranks of the picks in order, kNone behind the last candidate
+};
+
 constexpr int kCoopB = 32;                  // models per batch of the cooperative AC-RANSAC kernel, at most
 constexpr uint32_t kCoopMaxG = 30;          // slices per pair, at most (5-bit slice code of a task, 31 = start-up)
 
@@ -563,6 +587,9 @@ hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t
 // one workgroup per pair (G of 8 / 16 / 18 / 32, or 8 / 16 words)
 hipError_t launch_head_gather(hipStream_t st, const void* src, const uint32_t* rows, uint32_t hn, uint32_t per_row, bool binary, void* out);
 hipError_t launch_head_match(hipStream_t st, const HeadMatchParams& P, uint32_t n_pairs, bool binary, uint32_t G_or_words);
+hipError_t launch_vocab_hist(hipStream_t st, const VocabHistJob* jobs, uint32_t n_jobs, uint32_t max_n, uint32_t n_words);
+hipError_t launch_vocab_intersect(hipStream_t st, const VocabScoreParams& P, uint32_t n_slices);
+hipError_t launch_vocab_select(hipStream_t st, const VocabSelectParams& P);
 hipError_t launch_finalize(hipStream_t st, const FinalizeParams& P);
 hipError_t launch_filter_F(hipStream_t st, const FilterParams& P);
 hipError_t launch_filter_E(hipStream_t st, const FilterParams& P, size_t lds);   // the E kernels of launch_filter_F (kernels_filter_e.hip)
