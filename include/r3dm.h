@@ -149,6 +149,14 @@ int r3dm_get_prefix_pruning_counts(r3dm_ctx* ctx, uint64_t out[2]);
  * tiles by every match call that prunes: a view holds no layout for them (r3dm_view_info reports what it reported).
  * r3dm_get_pair_filter_counts: the tiles of the last r3dm_match_pairs call that this first test skipped (part of out[1] above). */
 int r3dm_get_pair_filter_counts(r3dm_ctx* ctx, uint64_t* out);
+/* In front of that filter, a cheaper one still (default on): the same contraction on the pair norms rounded UP to f16, on the f16
+ * matrix instructions -- a sixteenth of the filter's matrix cycles.  Its threshold carries a margin for the arithmetic of both, so
+ * it skips a tile only if the filter would: the tiles skipped, both counters above and every result are the same with the switch
+ * on or off, on any data (pair norms beyond f16's range just get nothing from it); only the time differs.  Off runs the kernel the
+ * library ran before.  The f16 pair norms are scratch of the call too (half a byte more per dimension and row).
+ * r3dm_get_half_filter_counts: the tiles of the last r3dm_match_pairs call that this level skipped (part of the filter's count). */
+int r3dm_set_half_filter(r3dm_ctx* ctx, int enable);
+int r3dm_get_half_filter_counts(r3dm_ctx* ctx, uint64_t* out);
 
 /* Opt-in split-f16 nominator of the L2 matcher for REAL-valued descriptors (default off; no reference counterpart) -- LIOP-144,
  * normalised SIFT: what Regard3D actually matches (src/Regard3DFeatures.h:44-48).  Their matching is always "nominate on
@@ -883,6 +891,8 @@ int r3dm_multi_set_kgraph_hamming(r3dm_multi* m, int enable);       /* r3dm_set_
 int r3dm_multi_set_prefix_pruning(r3dm_multi* m, int enable);       /* r3dm_set_prefix_pruning on every context */
 int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2]);      /* summed over the contexts' last calls */
 int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
+int r3dm_multi_set_half_filter(r3dm_multi* m, int enable);          /* r3dm_set_half_filter on every context */
+int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,

@@ -774,6 +774,20 @@ extern "C" int r3dm_get_pair_filter_counts(r3dm_ctx* c, uint64_t* out)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_set_half_filter(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->half_filter = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_get_half_filter_counts(r3dm_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    *out = c->half_count;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_set_split_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;

@@ -267,7 +267,8 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     mp.fb_cnt = c->d_fb.as<uint32_t>() + 16;
     mp.fb_q = c->d_fb.as<uint32_t>() + 16 + P;
     // (words 4 .. 11 of the zeroed header: the three 64-bit counters of the pruning kernel and its pair-norm table's address)
-    mp.prune = c->prefix_pruning ? 1u : 0u;
+    const bool halves = prunes && c->half_filter;          // the f16 level in front of the filter (r3dm_set_half_filter)
+    mp.prune = c->prefix_pruning ? (halves ? 3u : 1u) : 0u;
     mp.prune_cnt = reinterpret_cast<unsigned long long*>(c->d_fb.as<uint32_t>() + 4);
     // The pair-norm tiles are scratch of this call, not a layout of a view: made here from the f32 tiles of the batch's views (one
     // small kernel per view: 4 MB read, 2 MB written at 8192 rows) into one buffer of the context, which the next batch overwrites.
@@ -275,23 +276,32 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     std::vector<uint64_t> tr;                              // (lives to the end of the call, like hp: the copies below are asynchronous)
     if (prunes) {
         constexpr size_t kPad = 4096;                      // the filter's window runs two groups (2 KiB) past a view's last tile
+        constexpr size_t kPadH = 8192;                     // the f16 level's window runs four blocks (4 KiB) past a view's last f16 tile
+        // per view: its f32 pair-norm tiles and, with the f16 level, its f16 tiles behind them (a quarter of the f32 tiles' bytes)
+        const size_t nslots = c->imgs.size();
         size_t total = 0;
-        for (uint32_t s : batch_slots) total += (size_t)c->imgs[s]->n_tiles * (first.G / 2) * 1024 + kPad;
+        for (uint32_t s : batch_slots)
+            total += (size_t)c->imgs[s]->n_tiles * (first.G / 2) * 1024 + kPad + (halves ? (size_t)c->imgs[s]->n_tiles * (first.G / 4) * 1024 + kPadH : 0);
         R3DM_HIP(c, c->d_pairnorm_tiles.ensure(total));
-        tr.assign(c->imgs.size() + 1, 0);
+        tr.assign(2 * nslots + 2, 0);                      // [slots: f32 tiles][slots: f16 tiles][the two tables' addresses]
         size_t at = 0;
         for (uint32_t s : batch_slots) {
             const HostImage& h = *c->imgs[s];
             float* dst = reinterpret_cast<float*>(c->d_pairnorm_tiles.as<unsigned char>() + at);
-            R3DM_HIP(c, launch_stage_pairnorm(c->stream, h.tiled.as<float>(), h.G, h.n_tiles, dst));
-            tr[s] = (uint64_t)(uintptr_t)dst;
             at += (size_t)h.n_tiles * (first.G / 2) * 1024 + kPad;
+            uint16_t* dsth = halves ? reinterpret_cast<uint16_t*>(c->d_pairnorm_tiles.as<unsigned char>() + at) : nullptr;
+            if (halves) at += (size_t)h.n_tiles * (first.G / 4) * 1024 + kPadH;
+            R3DM_HIP(c, launch_stage_pairnorm(c->stream, h.tiled.as<float>(), h.G, h.n_tiles, dst, dsth));
+            tr[s] = (uint64_t)(uintptr_t)dst;
+            tr[nslots + s] = (uint64_t)(uintptr_t)dsth;
         }
-        // the table of the tiles by slot, and its address behind the counters (MatchParams::prune_cnt)
-        R3DM_HIP(c, c->d_pairnorm.ensure(8 * tr.size()));
-        tr.back() = (uint64_t)(uintptr_t)c->d_pairnorm.p;
-        R3DM_HIP(c, hipMemcpyAsync(c->d_pairnorm.p, tr.data(), 8 * (tr.size() - 1), hipMemcpyHostToDevice, c->stream));
-        R3DM_HIP(c, hipMemcpyAsync(mp.prune_cnt + 3, &tr.back(), 8, hipMemcpyHostToDevice, c->stream));
+        // the tables of the tiles by slot, and their addresses behind the counters (MatchParams::prune_cnt [3] and [5])
+        R3DM_HIP(c, c->d_pairnorm.ensure(8 * 2 * nslots));
+        tr[2 * nslots] = (uint64_t)(uintptr_t)c->d_pairnorm.p;
+        tr[2 * nslots + 1] = (uint64_t)(uintptr_t)(c->d_pairnorm.as<uint64_t>() + nslots);
+        R3DM_HIP(c, hipMemcpyAsync(c->d_pairnorm.p, tr.data(), 8 * 2 * nslots, hipMemcpyHostToDevice, c->stream));
+        R3DM_HIP(c, hipMemcpyAsync(mp.prune_cnt + 3, &tr[2 * nslots], 8, hipMemcpyHostToDevice, c->stream));
+        if (halves) R3DM_HIP(c, hipMemcpyAsync(mp.prune_cnt + 5, &tr[2 * nslots + 1], 8, hipMemcpyHostToDevice, c->stream));
     }
 
     const double t_dbg1 = now_ms();
@@ -328,10 +338,11 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
         uint32_t fbt[2] = {0, 0};
         R3DM_HIP(c, c->pin_small.ensure(64));
-        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 40, hipMemcpyDeviceToHost, c->stream));
+        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 56, hipMemcpyDeviceToHost, c->stream));
         R3DM_HIP(c, hipStreamSynchronize(c->stream));
         memcpy(fbt, c->pin_small.p, 8);
         { uint64_t pc[3]; memcpy(pc, (const unsigned char*)c->pin_small.p + 16, 24); for (int k = 0; k < 3; ++k) c->prune_counts[k] += pc[k]; }
+        { uint64_t hc; memcpy(&hc, (const unsigned char*)c->pin_small.p + 48, 8); c->half_count += hc; }      // (prune_cnt[4]; [3] is the table's address)
         n_fallback = fbt[0];
         if (fbt[0] > 0) {
             bool rescan = fbt[1] > 0;                      // some pair overflowed its list
@@ -391,6 +402,7 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
     c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;
+    c->half_count = 0;
     const double t_call = now_ms();
     std::vector<PairJob> jobs, none;
     const int rcp = resolve_pairs(c, pairs_ij, n_pairs, nullptr, none, jobs);
@@ -442,6 +454,7 @@ static int r3dm_knn2_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, 
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;      // ArrayMatcherBruteForce: NN > nbRows / nbQuery < 1
     if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
     R3DM_HIP(c, hipSetDevice(c->device));
+    c->half_count = 0;
     c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;            // (a raw 2-NN never prunes: the counters of this call read 0 / 0)
     PrivateSlots s(c, 2);
     int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);

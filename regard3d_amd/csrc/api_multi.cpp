@@ -224,6 +224,21 @@ extern "C" int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_half_filter(r3dm_multi* m, int enable)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) r3dm_set_half_filter(c, enable);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out)
+{
+    if (!m || !out) return R3DM_ERR_INVALID;
+    *out = 0;
+    for (r3dm_ctx* c : m->ctx) *out += c->half_count;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
 {
     if (!m) return R3DM_ERR_INVALID;

@@ -264,12 +264,27 @@ hipError_t launch_stage_bf16(hipStream_t st, const float* tiled, uint32_t G, uin
 // rd >= (1 - 2^-52) |(x, y)| (2^-50 if the root were off by a few ulps); f = (float)rd rounded to nearest is kept only if
 // f >= rd (1 + 2^-40) >= |(x, y)|, else the next float up is taken, which lies above rd by more than that.  So f >= |(x, y)| always
 // and f <= (1 + 2^-22) |(x, y)|.  Zero pairs (padding rows and dimensions) stay 0; a NaN element gives NaN, which objects in the test.
+// tiledrh (may be null): the same pair norms once more as f16, rounded UP again, for the f16 level of l2_knn2_half_kernel:
+// [tile][G / 4 blocks of 16 pair norms][lane half][32 rows][8 f16] -- the fragment order of v_mfma_f32_32x32x16_f16, a quarter of
+// `tiled`'s bytes.  h >= f for every element (pairnorm_to_half), so h >= |(x, y)| as well.
+__device__ __forceinline__ uint16_t pairnorm_to_half(float f)
+{
+    // f is a pair norm: +0, positive, +inf or NaN.  Each case keeps h >= f:
+    if (f != f) return 0x7E00u;                                      // NaN stays NaN: its keys object
+    if (f == 0.0f) return 0u;                                        // zero stays zero (padding rows and dimensions)
+    if (f > 65504.0f) return 0x7C00u;                                // beyond the largest f16: +inf, whose keys are -inf or NaN -- both object
+    if (f < 6.103515625e-05f) return 0x0400u;                        // below 2^-14: 2^-14, the smallest normal (no subnormal is emitted)
+    // a normal f16: drop 13 significand bits, rounding up (the carry may run into the exponent; f <= 65504 keeps it below +inf)
+    return (uint16_t)((__float_as_uint(f) - (112u << 23) + 0x1FFFu) >> 13);
+}
+
 __global__ __launch_bounds__(256)
-void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* __restrict__ tiledr)
+void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* __restrict__ tiledr, uint16_t* __restrict__ tiledrh)
 {
     const uint32_t t = blockIdx.x, GR = G / 2u;
     const float* src = tiled + (size_t)t * G * 256u;
     float* dst = tiledr + (size_t)t * GR * 256u;
+    uint16_t* dsth = tiledrh ? tiledrh + (size_t)t * GR * 256u : nullptr;
     for (uint32_t e = threadIdx.x; e < GR * 256u; e += 256u) {
         const uint32_t c = e & 3u, r = (e >> 2) & 31u, h = (e >> 7) & 1u, g = e >> 8;
         const uint32_t d = 2u * (8u * g + 4u * h + c);               // the pair's first dimension; in the f32 tiles: g = d / 8, half (d / 4) & 1
@@ -279,12 +294,16 @@ void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* _
         float f = (float)rd;
         if ((double)f < rd * (1.0 + 0x1p-40)) f = __uint_as_float(__float_as_uint(f) + 1u);      // (f >= 0 and finite here: the next float up)
         dst[e] = f;
+        if (dsth) {
+            const uint32_t k = 8u * g + 4u * h + c;                  // the pair; in the f16 tiles: block k / 16, lane half (k / 8) & 1
+            dsth[(k >> 4) * 512u + ((k >> 3) & 1u) * 256u + r * 8u + (k & 7u)] = pairnorm_to_half(f);
+        }
     }
 }
-hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr)
+hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr, uint16_t* tiledrh)
 {
     if (n_tiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(stage_pairnorm_kernel, dim3(n_tiles), dim3(256), 0, st, tiled, G, tiledr);
+    hipLaunchKernelGGL(stage_pairnorm_kernel, dim3(n_tiles), dim3(256), 0, st, tiled, G, tiledr, tiledrh);
     return hipGetLastError();
 }
 
@@ -794,6 +813,230 @@ static hipError_t launch_l2_cascade_t(hipStream_t st, const MatchParams& Pin, ui
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// The f16 level: a cheaper filter in front of the filter (r3dm_set_half_filter, default on).  The pair-norm filter is the one
+// contraction of the cascade whose result reaches no caller -- a lower bound, compared against a threshold -- and it stays a lower
+// bound when the pair norms are rounded UP to f16: with ha_k >= sa_k, hb_k >= sb_k (stage_pairnorm_kernel's second table)
+//     kh = |a|^2 - 2 sum_k ha_k hb_k  <=  kf            in exact arithmetic,
+// and v_mfma_f32_32x32x16_f16 contracts 16 pair norms in 32 cycles where v_mfma_f32_32x32x2_f32 takes 64 for two.  Per tile:
+//   1. l2_halfnorm_tile_filter: 4 blocks on the f16 tiles.  No lane has a kh that is not above its thrH -> the tile is done.
+//   2. else l2_pairnorm_tile_stream: the cascade's filter, its 8 groups read again (the wave keeps only the f16 query fragments in
+//      registers); no lane has a kf that is not above its thrF -> the tile is done.
+//   3. else l2_prune_tile_restart, as in the cascade.
+// THE INVARIANT: level 1 prunes a tile only if level 2 would.  Then the pruned tiles, hence the lists, T, plT, the counters of the
+// cascade and every result are the cascade's on any data, and only the work differs.  It holds when thrH >= thrF + margin and the
+// margin covers the evaluation errors of both COMPUTED keys against their exact values on the STORED operands (the stored norm N,
+// the stored f32 pair norms s, the stored f16 pair norms h; h >= s holds exactly, whatever the rows):
+//     kf_c >= kf - eF,  kh_c <= kh + eH,  kh <= kf   =>   kh_c > thrF + eF + eH  implies  kf_c > thrF.
+// In units of u M, u = 2^-24, M = max|a|^2 + |q|^2 (the stored norms, as in slackF), assuming the matrix unit may TRUNCATE: one ulp,
+// 2 u of the value, per product rounding and per addition (the form of the split planes' bound, kernels_match_16bit.hip):
+//   eF   2   the 64 products -2 sa_k sb_k of the f32 MFMAs, one ulp each: 2 u x 2 sum sa_k sb_k <= 2 u (1 + 2^-20) M
+//      128   64 additions into accumulators that stay within [-(1 + 2^-20) M, M]
+//   eH     0 the products -2 ha_k hb_k: 11-bit x 11-bit significands, exact in f32 (h <= 65504 and h = 0 or h >= 2^-14: no overflow,
+//            no underflow); -2 hb is exact in f16 or overflows to -inf, which objects
+//      257   64 additions (16 per MFMA, in any order) of partial sums and accumulators whose magnitude stays below
+//            sum_k (ha_k^2 + hb_k^2) + M <= 2 (1 + 2^-10)^2 (1 + 2^-21) M + 2^-20 <= 2.005 M + 2^-20:  h <= (1 + 2^-10) s + 2^-14
+//            (the round-up and the floor at 2^-14), so h^2 <= 2 (1 + 2^-10)^2 s^2 + 2^-27 over 128 pair norms
+//   = 387 u M + 128 u 2^-19; the kernel takes margin = 400 u M + 2^-35 (kHalfMarginFactor, kHalfMarginAbs: the roundings of the
+//   margin itself included) and thrH = (thrF + margin) rounded up by 2^-22 of it, which pays that sum's rounding.  That is
+//   0.72 of one more slackF (552 u M): tools/prefix_prune_model.py --filter half shows what it costs (0.15 % of c2's tiles).
+// Values outside f16's range cost level 1's work and nothing else: a pair norm above 65,504 is +inf, its keys -inf or NaN, both
+// object and the tile goes to level 2; non-zero values below 2^-14 are held at 2^-14 (the bound gets looser, never wrong).
+// MODE (developer ablations): 0 the three levels | 1 level 1, then straight to the restart (timing only: other tiles are pruned).
+// ------------------------------------------------------------------------------------------------
+constexpr float kHalfMarginFactor = 400.0f * 5.9604644775390625e-08f;       // 400 x 2^-24
+constexpr float kHalfMarginAbs = 2.9103830456733704e-11f;                   // 2^-35
+
+template <int G, int GP, int NJ, int PF, int WPS, int MODE>
+__global__ __launch_bounds__(256, WPS)
+void l2_knn2_half_kernel(const MatchParams P)
+{
+    constexpr int GR = G / 2, GH = G / 4;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t h = lane >> 5, c = lane & 31u;
+    // workgroup -> (pair, query block): as in l2_knn2_mfma_kernel
+    uint32_t pair, qb;
+    if (P.xcd_map) {
+        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+        pair = (j / P.qb_per_pair) * 8u + xcd;
+        qb = j % P.qb_per_pair;
+        if (pair >= P.n_pairs) return;
+    } else {
+        pair = blockIdx.x / P.qb_per_pair;
+        qb = blockIdx.x % P.qb_per_pair;
+    }
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const float* const* pairnorm = reinterpret_cast<const float* const*>(P.prune_cnt[3]);      // (MatchParams::prune_cnt says why they live there)
+    const uint16_t* const* halfnorm = reinterpret_cast<const uint16_t* const*>(P.prune_cnt[5]);
+    const float* __restrict__ redI = pairnorm[pr.x];
+    const float* __restrict__ redJ = pairnorm[pr.y];
+    const uint16_t* __restrict__ hlfI = halfnorm[pr.x];
+    const uint16_t* __restrict__ hlfJ = halfnorm[pr.y];
+    const uint32_t nI = Ip->n, ntI = Ip->n_tiles, nJ = Jp->n, ntJ = Jp->n_tiles;
+    const uint32_t qt0 = (qb * 4u + wave) * NJ;
+    if (qt0 >= ntJ) return;                           // wave-uniform; no barriers in this kernel
+
+    // ---- f16 query fragments (B operand of level 1), scaled by -2 (exact, or -inf); a tile that goes on reads the f32 ones
+    // (soffQR: the reduced groups, soffQ: the full ones)
+    f32x4 bqh[NJ][GH];
+    uint32_t soffQ[NJ], soffQR[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        uint32_t qt = qt0 + nj; if (qt >= ntJ) qt = ntJ - 1;          // clamp: results discarded below
+        soffQ[nj] = qt * (uint32_t)(G * 1024);
+        soffQR[nj] = qt * (uint32_t)(GR * 1024);
+        const gf4p src = (gf4p)hlfJ + (size_t)qt * (GH * 64) + lane;
+#pragma unroll
+        for (int g = 0; g < GH; ++g) bqh[nj][g] = __builtin_bit_cast(f32x4, __builtin_bit_cast(f16x8, src[g * 64]) * (_Float16)-2.0f);
+    }
+    const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled), rqr = wave_uniform_rsrc(redJ);
+
+    Top2 st[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
+
+    // ---- the lane's share of the thresholds (read again where a list has changed, as in the kernels above)
+    const bool exact_pair = l2_pair_is_exact(Ip, Jp, (float)(G * 8), false);
+    const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
+    const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
+    const float maxnormI = __uint_as_float(Ip->max_norm_bits);
+    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF, float& mgn) __attribute__((always_inline)) -> bool {
+        uint32_t q = (qt0 + (uint32_t)nj) * 32u + c;
+        asm volatile("" : "+v"(q));
+        const bool dead = !(q < nJ);                    // (covers a query tile beyond the last one too: its rows lie beyond nJ)
+        const uint32_t qo = dead ? 0u : q * 4u;
+        const float nb = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, 0, 0));
+        const float nbp = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, (int)(prefix_norm_offset(ntJ) * 4u), 0));
+        const float slkF = (P.err_scale + kPruneKeySlack) * (maxnormI + nb);
+        const float slk = exact_pair ? 0.0f : slkF;
+        nbs = nb + slk;
+        off = slk - nbp;
+        offF = slkF - nb;
+        mgn = kHalfMarginFactor * (maxnormI + nb) + kHalfMarginAbs;
+        return dead;
+    };
+    float thr[NJ], thrF[NJ], thrH[NJ], Tl[NJ], plT[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; thrH[nj] = R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned)
+    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0, n_half = 0;      // wave-uniform
+    bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
+
+    if (nI >= 2) {
+        // ---- dataset stream of level 1 (A operand): the f16 tiles, float4 index = (t*GH + g)*64 + lane, and the full norms
+        const gf4p abase = (gf4p)hlfI;
+        const gf4p nbase = (gf4p)Ip->norms;               // tile t, quad qd -> float4 index t*8 + 2*qd + h
+        f32x4 abuf[PF];
+#pragma unroll
+        for (int s = 0; s < PF; ++s) abuf[s] = abase[s * 64 + lane];
+        f32x4 nrm[4];
+#pragma unroll
+        for (int qd = 0; qd < 4; ++qd) nrm[qd] = nbase[2 * qd + h];
+
+        f32x16 accA[NJ], accB[NJ];
+        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms), rr = wave_uniform_rsrc(redI),
+                                     rh = wave_uniform_rsrc(hlfI);
+        const uint32_t voffA = lane * 16u, voffN = h * 16u;
+        const uint32_t tileB = (uint32_t)G * 1024u, tileRB = (uint32_t)GR * 1024u, tileHB = (uint32_t)GH * 1024u;      // bytes per tile, reduced tile, f16 tile
+        const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
+        const uint32_t hb = 4u * h;
+        // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes).  T, thr and thrF are the
+        // cascade's floats; thrH >= thrF + margin (the header comment)
+        auto refresh = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) {
+                if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
+                float nbs, off, offF, mgn;
+                const bool dead = lane_terms(nj, nbs, off, offF, mgn);
+                const float e0 = st[nj].d0 + nbs, e1 = st[nj].d1 + nbs;
+                const float re1 = R * e1;
+                float T = e0 < re1 ? __builtin_fmaxf(re1, e0 * invR) : re1;
+                T += __builtin_fabsf(T) * 4.76837158203125e-07f;        // 2^-21: the roundings of e1, R e1, 1 / R and e0 / R
+                Tl[nj] = T;
+                const float x = T + off, xF = T + offF;
+                thr[nj] = dead ? -R3DM_INF : x + __builtin_fabsf(x) * 2.384185791015625e-07f;      // 2^-22: the rounding of x
+                thrF[nj] = dead ? -R3DM_INF : xF + __builtin_fabsf(xF) * 2.384185791015625e-07f;
+                const float xH = thrF[nj] + mgn;
+                thrH[nj] = dead ? -R3DM_INF : xH + __builtin_fabsf(xH) * 2.384185791015625e-07f;   // 2^-22: the rounding of xH
+            }
+        };
+        // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
+        auto tile = [&](uint32_t t, f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ], bool live) __attribute__((always_inline)) -> bool {
+            l2_halfnorm_tile_filter<GH, NJ, PF>(rh, rn, voffA, voffN, t * tileHB, (t + 1) * 128u, abuf, nrm, bqh, cur, prev, st,
+                                                (t - 1) * 32u + hb, live);
+            if (live) { refresh(); pruned_under_thr = false; }
+            n_tested += 1u;
+            // a lane objects when one of its keys is not above its threshold (written so that a NaN key objects)
+            bool obj = false;
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrH[nj]);
+            if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; n_half += 1u; pruned_under_thr = true; return false; }
+            if constexpr (MODE == 0) {
+                l2_pairnorm_tile_stream<GR, NJ>(rr, rn, voffA, voffN, t * tileRB, t * 128u, rqr, soffQR, cur);
+                obj = false;
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrF[nj]);
+                if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true; return false; }
+            }
+            const bool on = l2_prune_tile_restart<G, GP, NJ, true>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
+            if (!on) { n_pruned += 1u; pruned_under_thr = true; }
+            return on;
+        };
+        bool live = false;
+        uint32_t t = 0;
+        for (; t + 1 < ntI; t += 2) {
+            live = tile(t, accA, accB, live);
+            live = tile(t + 1, accB, accA, live);
+        }
+        if (t < ntI) {
+            if (tile(t, accA, accB, live)) {
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) top2_push(st[nj], accA[nj][r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        } else if (live) {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) top2_push(st[nj], accB[nj][r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
+        }
+    }
+
+    // plT -> the lower bound of the pruned rows' distances (a lane whose query does not exist holds none)
+    float pruned_lb[NJ];
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
+        const bool dead = !((qt0 + (uint32_t)nj) * 32u + c < nJ);
+        pruned_lb[nj] = dead ? -R3DM_INF : plT[nj];
+    }
+    if (lane == 0 && n_tested) {
+        atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
+        if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
+        if (n_filtered) atomicAdd(P.prune_cnt + 2, (unsigned long long)n_filtered);
+        if (n_half) atomicAdd(P.prune_cnt + 4, (unsigned long long)n_half);
+    }
+    l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
+}
+
+template <int G, int GP, int NJ, int PF, int WPS, int MODE>
+static hipError_t launch_l2_half_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+{
+    MatchParams P = Pin;
+    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
+    hipLaunchKernelGGL((l2_knn2_half_kernel<G, GP, NJ, PF, WPS, MODE>), dim3(grid), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
 // The pruning kernel serves ratio tests that leave it room: near R = 1 a row matters up to the runner-up's distance, no prefix
 // rules a tile out and the test only costs.  tools/prefix_prune_model.py on the synthetic SIFT collection (profiles/
 // prefix_prune_model_c2.txt): 96 % of the tiles stop at R = 0.36 (ratio 0.6), 72 % at R = 0.49 (ratio 0.7), 6 % at R = 0.64.
@@ -863,11 +1106,26 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
             case 120: return launch_l2_cascade_t<16, (int)kPrefixGroups, 2, 2, 2, 1>(st, P, max_nj_tiles);
             default: break;
         }
+        //   130: the f16 level, then straight to the restart (no f32 filter; timing only) | 131 / 132: the three levels with a
+        //   window of 1 / 2 blocks instead of 4
+        if ((P.prune & 2u) != 0) {
+            switch (variant) {
+                case 130: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 1>(st, P, max_nj_tiles);
+                case 131: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 1, 2, 0>(st, P, max_nj_tiles);
+                case 132: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 0>(st, P, max_nj_tiles);
+                default: break;
+            }
+        }
     }
 #endif
-    // match mode on 128-dimensional rows: the kernel that stops tiles early (r3dm_set_prefix_pruning, default on)
-    if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R))
+    // match mode on 128-dimensional rows: the kernels that stop tiles early (r3dm_set_prefix_pruning, default on) -- with the f16
+    // level in front (r3dm_set_half_filter, default on: MatchParams::prune bit 1) or the cascade alone.  The f16 level reaches as far
+    // as the cascade does (kPruneMaxR): it prunes what the filter prunes, at a sixteenth of the matrix cycles, and where the filter
+    // stops few tiles it adds 256 cycles to a tile of 4,096 and more (profiles/half_filter_model_c2.txt has R = 0.49).
+    if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R)) {
+        if ((P.prune & 2u) != 0) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
         return launch_l2_cascade_t<16, (int)kPrefixGroups, 2, 2, 2, 0>(st, P, max_nj_tiles);
+    }
     switch (G) {
         case 8:  return launch_l2_t<8, 2, 4, 3, 2>(st, P, max_nj_tiles);
         case 16: return launch_l2_t<16, 2, 4, 3, 2>(st, P, max_nj_tiles);

@@ -8,6 +8,7 @@
 //   l2_tile_step                       one dataset tile on the f32 tiles          (v_mfma_f32_32x32x2_f32)
 //   l2_prune_tile_prefix / _finish     ... stopped after a prefix of its dimensions when no lane needs the rest (match mode)
 //   l2_pairnorm_tile_filter / l2_prune_tile_restart   ... ruled out on its pair norms first; a tile that is not starts over
+//   l2_halfnorm_tile_filter / l2_pairnorm_tile_stream ... ruled out on its pair norms in f16 before that (v_mfma_f32_32x32x16_f16)
 //   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
 //   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
@@ -306,6 +307,104 @@ __device__ __forceinline__ void l2_pairnorm_tile_filter(__amdgpu_buffer_rsrc_t r
                         top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
             }
         }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// f32 tiles, match mode: the f16 level in front of the pair-norm filter (l2_knn2_half_kernel; Top2 lists only).
+// The filter's contraction once more on the pair norms rounded UP to f16 (the second table behind MatchParams::prune_cnt:
+// [tile][4 blocks of 16 pair norms][lane half][32 rows][8 f16], 4 KiB per tile, tiles contiguous): four v_mfma_f32_32x32x16_f16 per
+// query tile instead of 32 v_mfma_f32_32x32x2_f32, accumulators started from the rows' FULL norms, so they end as
+// kh = |a|^2 - 2 sum_k ha_k hb_k <= kf in exact arithmetic (ha >= sa, hb >= sb).  The epilogue of tile t-1 is spread over the four
+// blocks; the A window runs on from tile to tile.  The caller decides on `cur`.
+//   v_mfma_f32_32x32x16_f16: A lane l = A[i = l&31][k = 8 (l>>5) .. + 7], B lane l = B[k = 8 (l>>5) .. + 7][j = l&31], D as the f32 form.
+// ------------------------------------------------------------------------------------------------
+template <int GH, int NJ, int PF>
+__device__ __forceinline__ void l2_halfnorm_tile_filter(__amdgpu_buffer_rsrc_t rh, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                        uint32_t soffH, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4],
+                                                        const f32x4 (&bqh)[NJ][GH], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
+                                                        Top2 (&st)[NJ], uint32_t prev_rowbase, bool prev_live)
+{
+    static_assert(GH % PF == 0, "the window keeps block g in slot g % PF from tile to tile");
+    // soffH: byte offset of this tile's f16 block 0; soffN: of the NEXT tile's norms
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cur[nj][r] = nrm[r >> 2][r & 3];
+#pragma unroll
+    for (int g = 0; g < GH; ++g) {
+        const f16x8 a = __builtin_bit_cast(f16x8, abuf[g % PF]);
+        abuf[g % PF] = bload16(rh, voffA, soffH + (uint32_t)(g + PF) * 1024u);
+        if (g == 0) {   // next tile's norms: as early as the accumulators' start allows
+#pragma unroll
+            for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+        }
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj)
+            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
+        if (prev_live) {
+            // this block's share of the previous tile's keys: test-and-skip as in l2_tile_step<PIPE 3>
+            bool any = false;
+#pragma unroll
+            for (int r = (g * 16) / GH; r < ((g + 1) * 16) / GH; ++r)
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj) any |= prev[nj][r] < st[nj].d2;
+            if (__builtin_amdgcn_ballot_w64(any) != 0ull) {
+#pragma unroll
+                for (int r = (g * 16) / GH; r < ((g + 1) * 16) / GH; ++r)
+#pragma unroll
+                    for (int nj = 0; nj < NJ; ++nj)
+                        top2_push(st[nj], prev[nj][r], prev_rowbase + (uint32_t)((r & 3) + 8 * (r >> 2)));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The pair-norm filter on a tile the f16 level let through: the MFMAs of l2_pairnorm_tile_filter in the same order on the same
+// operands (the keys are the same floats), but nothing of it is in registers when it starts -- the tile's norms, its reduced groups
+// and the query view's reduced groups stream through a W-deep window as in l2_prune_tile_restart below.  The f16 level's window and
+// norms stay untouched.  The caller decides on `cur`.
+template <int GR, int NJ>
+__device__ __forceinline__ void l2_pairnorm_tile_stream(__amdgpu_buffer_rsrc_t rr, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                        uint32_t soffR, uint32_t soffN, __amdgpu_buffer_rsrc_t rqr,
+                                                        const uint32_t (&soffQR)[NJ], f32x16 (&cur)[NJ])
+{
+    constexpr int W = 2;
+    static_assert(GR % W == 0, "window slots");
+    // soffR: byte offset of this tile's reduced group 0; soffN: of THIS tile's norms
+    f32x4 wa[W], wb[NJ][W];
+#pragma unroll
+    for (int s = 0; s < W; ++s) {
+        wa[s] = bload16(rr, voffA, soffR + (uint32_t)s * 1024u);
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) wb[nj][s] = bload16(rqr, voffA, soffQR[nj] + (uint32_t)s * 1024u);
+    }
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) {
+        const f32x4 nf = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) cur[nj][4 * qd + k] = nf[k];
+    }
+#pragma unroll
+    for (int g = 0; g < GR; ++g) {
+        const f32x4 a = wa[g % W];
+        f32x4 b[NJ];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) b[nj] = wb[nj][g % W] * -2.0f;
+        if (g + W < GR) {
+            wa[g % W] = bload16(rr, voffA, soffR + (uint32_t)(g + W) * 1024u);
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) wb[nj][g % W] = bload16(rqr, voffA, soffQR[nj] + (uint32_t)(g + W) * 1024u);
+        }
+#pragma unroll
+        for (int cc = 0; cc < 4; ++cc)
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], b[nj][cc], cur[nj], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
     }
 }

@@ -235,11 +235,13 @@ struct MatchParams {
     uint32_t      fb_slices;      // 1: one workgroup per pair, results emitted directly
     // prefix pruning of the f32 2-NN tiles in match mode (r3dm_set_prefix_pruning; l2_knn2_prune_kernel).  Behind every older field:
     // their offsets are what the other kernels' machine code was compiled with.
-    uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel
+    uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel; bit 1: with the f16 level in front (r3dm_set_half_filter)
     // [0 .. 2]: wave tiles (32 rows x 64 queries) tested, pruned by any test, pruned by the pair-norm filter (atomic; zeroed by the
     // host); [3]: the bits of a `const float* const*`, the pair-norm tiles of the cascade's filter (l2_knn2_cascade_kernel) per slot
     // of `imgs`: [n_tiles][G / 2][2][32][4] f32 in the fragment order of `tiled`, half its bytes (scratch of the call: run_match_batch),
-    // written by the host when the launch may prune.  Behind this pointer and no field of ImgDev or of this struct: their sizes and
+    // written by the host when the launch may prune; [4]: wave tiles pruned by the f16 level (l2_knn2_half_kernel; part of [2]);
+    // [5]: the bits of a `const uint16_t* const*`, the f16 pair-norm tiles per slot: [n_tiles][G / 4][2][32][8] f16, written by the host
+    // when prune bit 1 is set.  Behind this pointer and no field of ImgDev or of this struct: their sizes and
     // offsets are what every other kernel's machine code and kernel arguments were compiled with.
     unsigned long long* prune_cnt;
 };
@@ -552,7 +554,8 @@ hipError_t launch_stage_view(hipStream_t st, const StageViewArgs& A);
 hipError_t launch_stage_positions(hipStream_t st, const StageViewArgs& A);      // the position part alone (binary views)
 hipError_t launch_untile_rows(hipStream_t st, const float* tiled, uint32_t n, uint32_t dim, uint32_t G, uint32_t n_tiles, float* rows);
 hipError_t launch_stage_bf16(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, uint16_t* tiled16);
-hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr);
+// tiledrh: null, or the f16 tiles of the same pair norms (the f16 level of l2_knn2_half_kernel), n_tiles x G x 256 bytes
+hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr, uint16_t* tiledrh);
 // whether launch_l2_knn2 takes the pruning kernel for such a launch (which reads the pair-norm tiles behind MatchParams::prune_cnt: the caller makes them, run_match_batch)
 bool l2_prune_serves(uint32_t G, bool prune, bool raw_knn, float ratio_R);
 hipError_t launch_stage_bin(hipStream_t st, const uint8_t* raw, uint32_t n, uint32_t nbytes,

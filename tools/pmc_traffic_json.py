@@ -8,7 +8,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from regard3d_amd.codeobj import kernel_hash, mangled_needle
 LIB = os.path.join(ROOT, "regard3d_amd", "libr3dm.so")
-KERNELS = "l2_knn2_cascade_kernel|l2_knn2_prune_kernel|l2_knn2_mfma_kernel|l2_knn2_int_kernel|l2_knn2_int_lds_kernel|l2_knn2_split_kernel|l2_knn2_counts2_kernel|l2_knn2_counts_kernel|hamming_knn2_kernel|hamming_knn2_mfma_kernel"
+KERNELS = "l2_knn2_half_kernel|l2_knn2_cascade_kernel|l2_knn2_prune_kernel|l2_knn2_mfma_kernel|l2_knn2_int_kernel|l2_knn2_int_lds_kernel|l2_knn2_split_kernel|l2_knn2_counts2_kernel|l2_knn2_counts_kernel|hamming_knn2_kernel|hamming_knn2_mfma_kernel"
 config = sys.argv[2] if len(sys.argv) > 2 else "c2"
 txt = open(sys.argv[1]).read()
 vals = {}
@@ -27,8 +27,8 @@ out = {"_comment": "HBM-side traffic of ONE launch of the dominant kernel per be
        "16 B/lane streams -> read side doubled; WRITE_SIZE is uncalibrated on gfx950 and tiny here.  bench.py reports an entry only while "
        "code_sha16 equals the fingerprint of that kernel's machine code in the library it runs (regard3d_amd/codeobj.py)."}
 # bench.py's roofline names the headline kernel l2_knn2_mfma_kernel<G, NJ> whichever build of it ran: the pruning build
-# (l2_knn2_cascade_kernel, before it l2_knn2_prune_kernel; match mode on 128-dimensional rows) is entered under that key, with its own name and fingerprint inside
-for pruning in ("l2_knn2_prune_kernel", "l2_knn2_cascade_kernel"):
+# (l2_knn2_half_kernel, before it l2_knn2_cascade_kernel and l2_knn2_prune_kernel; match mode on 128-dimensional rows) is entered under that key, with its own name and fingerprint inside
+for pruning in ("l2_knn2_prune_kernel", "l2_knn2_cascade_kernel", "l2_knn2_half_kernel"):
     if pruning in vals:
         vals["l2_knn2_mfma_kernel"] = vals.pop(pruning)
 for k, v in vals.items():

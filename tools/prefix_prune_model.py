@@ -13,7 +13,10 @@ above the kernel; l2_finish_queries<PRUNE> has the proof): per (query, half) wit
   not ea < R eb -> no match;  ea < R eb and ea < R PL -> the best seen row;  else the exact scan.
 Distances are exact here (integer-valued rows: float32 sums below 2^24), as the kernel's are for such pairs.
    python tools/prefix_prune_model.py --filter pairnorm [--gp 12] ...
-the cascade of l2_knn2_cascade_kernel: the pair-norm filter in front of the prefix test (model_pair_cascade)."""
+the cascade of l2_knn2_cascade_kernel: the pair-norm filter in front of the prefix test (model_pair_cascade).
+   python tools/prefix_prune_model.py --filter half [--gp 12] ...
+the three levels of l2_knn2_half_kernel: the same filter on pair norms rounded up to f16 in front of the cascade (model_pair_levels);
+it must prune no tile the cascade does not prune."""
 import argparse
 import os
 import sys
@@ -209,6 +212,151 @@ def model_pair_cascade(a, b, gp, R, filter_only=False):
             "wrong": int((decided & (verdict != truth)).sum()), "matches": int((truth >= 0).sum()), "queries": nJ}
 
 
+HALF_MARGIN = 400 * U                 # kHalfMarginFactor (kernels_match.hip, above l2_knn2_half_kernel)
+HALF_MARGIN_ABS = 2.0 ** -35          # kHalfMarginAbs
+# matrix cycles of a wave tile (32 rows x 64 queries) per level: 8 v_mfma_f32_32x32x16_f16 of 32 cycles; 64 v_mfma_f32_32x32x2_f32 of
+# 64 cycles per 8 groups
+CYC_HALF, CYC_GROUP = 8 * 32, 8 * 64
+
+
+def pair_norms_half(x):
+    """[n, D] float32 -> [n, D / 2] float64 holding f16 values >= pair_norms(x): pairnorm_to_half (kernels_match.hip) -- rounded up
+    from the float32 pair norm; +inf above 65,504; 2^-14 for a non-zero value below 2^-14 (no subnormal); 0 stays 0, NaN stays NaN"""
+    s = pair_norms(x)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hn = s.astype(np.float16)                                    # to nearest (overflow -> +inf)
+        up = hn.astype(np.float32) < s
+        hn = np.where(up, np.nextafter(hn, np.float16(np.inf)), hn).astype(np.float16)
+    h = hn.astype(np.float64)
+    h = np.where(s > np.float32(65504.0), np.inf, h)
+    h = np.where((s != 0) & (s < np.float32(2.0 ** -14)), 2.0 ** -14, h)
+    return np.where(np.isnan(s), np.nan, h)
+
+
+def halfnorm_bound(a, b):
+    """-> (LBH [nI, nJ], margin [nJ]) in float64: LBH = |a|^2 + |b|^2 - 2 sum_k ha_k hb_k <= pairnorm_bound's LB (ha >= sa, hb >= sb),
+    NaN or -inf where a factor is +inf; and the margin thrH carries above thrF, 400 u (max|a|^2 + |b|^2) + 2^-35"""
+    ha, hb = pair_norms_half(a), pair_norms_half(b)
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    na, nb = (a64 * a64).sum(1), (b64 * b64).sum(1)
+    with np.errstate(invalid="ignore", over="ignore"):
+        # the contraction as the matrix unit sees it: a product 0 x inf is a NaN and poisons its sum
+        dot = (ha[:, None, :] * hb[None, :, :]).sum(2) if a.shape[0] * b.shape[0] <= 1 << 16 else ha @ hb.T
+        return na[:, None] + nb[None, :] - 2.0 * dot, HALF_MARGIN * (na.max(initial=0.0) + nb) + HALF_MARGIN_ABS
+
+
+def model_pair_levels(a, b, gp, R, half=True):
+    """the three levels of l2_knn2_half_kernel: per wave tile the f16 level (thrH = thrF + margin), behind it the pair-norm filter,
+    behind that the tile run again with the prefix test -- model_pair_cascade with one more level in front (half=False: without it,
+    the cascade itself), and with the outcome PER TILE.
+    -> model_pair_cascade's dict + half (tiles level 1 pruned), cycles (matrix cycles), and [n_tiles, n_waves] bool arrays
+    tile_half / tile_filtered / tile_pruned, verdict [nJ] (-1 none, -2 exact scan, else the row)"""
+    R64 = float(np.float32(R))
+    nI, nJ = a.shape[0], b.shape[0]
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        D = ((a64[:, None, :] - b64[None, :, :]) ** 2).sum(2) if nI * nJ <= 1 << 16 else \
+            (a64 * a64).sum(1)[:, None] - 2.0 * a64 @ b64.T + (b64 * b64).sum(1)[None, :]
+        ap, bp = a64[:, :8 * gp], b64[:, :8 * gp]
+        DP = (ap * ap).sum(1)[:, None] - 2.0 * ap @ bp.T + (bp * bp).sum(1)[None, :]
+        LB, slackF = pairnorm_bound(a, b)
+        LBH, margin = halfnorm_bound(a, b)
+    slackP = np.zeros(nJ) if _exact_pair(a, b) else slackF
+    n_tiles = (nI + 31) // 32
+    n_waves = (nJ + 63) // 64
+    half_of_row = (np.arange(32) >> 2) & 1
+    d0 = np.full((2, nJ), np.inf); d1 = np.full((2, nJ), np.inf)
+    i0 = np.full((2, nJ), -1, np.int64); i1 = np.full((2, nJ), -1, np.int64)
+    pl = np.full((2, nJ), np.inf)
+    wave_of_q = np.arange(nJ) // 64
+    tiles = pruned = filtered = halved = work = cycles = 0
+    tile_half = np.zeros((n_tiles, n_waves), bool); tile_filtered = np.zeros((n_tiles, n_waves), bool); tile_pruned = np.zeros((n_tiles, n_waves), bool)
+    for t in range(n_tiles):
+        lo, hi = t * 32, min(nI, t * 32 + 32)
+        rows = np.arange(lo, hi)
+        with np.errstate(invalid="ignore"):
+            e0, e1 = d0 + slackP, d1 + slackP
+            re1 = R64 * e1
+            T = np.where(e0 < re1, np.maximum(re1, e0 / R64), re1)
+            T = T + np.abs(T) * 2.0 ** -21
+        objH = np.zeros((2, nJ), bool); objF = np.zeros((2, nJ), bool); objP = np.zeros((2, nJ), bool)
+        with np.errstate(invalid="ignore"):
+            for h in (0, 1):
+                m = half_of_row[: hi - lo] == h
+                if m.any():
+                    # (a NaN key objects: the comparisons are written as the kernel's)
+                    objH[h] = ~(LBH[rows[m]] - (slackF + margin)[None, :] > T[h][None, :]).all(0)
+                    objF[h] = ~(LB[rows[m]] - slackF[None, :] > T[h][None, :]).all(0)
+                    objP[h] = ~(DP[rows[m]] - slackP[None, :] > T[h][None, :]).all(0)
+        wH = np.zeros(n_waves, bool); wF = np.zeros(n_waves, bool); wP = np.zeros(n_waves, bool)
+        np.logical_or.at(wH, wave_of_q, objH[0] | objH[1])
+        np.logical_or.at(wF, wave_of_q, objF[0] | objF[1])
+        np.logical_or.at(wP, wave_of_q, objP[0] | objP[1])
+        if not half:
+            wH[:] = True
+        wave_on = wH & wF & wP
+        tile_half[t] = ~wH; tile_filtered[t] = ~(wH & wF); tile_pruned[t] = ~wave_on
+        tiles += n_waves
+        halved += int((~wH).sum())
+        filtered += int((~(wH & wF)).sum())
+        pruned += int((~wave_on).sum())
+        n2, n3p, n3 = int(wH.sum()), int((wH & wF & ~wP).sum()), int(wave_on.sum())
+        work += 8 * n2 + gp * n3p + 16 * n3
+        cycles += (CYC_HALF * n_waves if half else 0) + CYC_GROUP * (8 * n2 + gp * n3p + 16 * n3)
+        go = wave_on[wave_of_q]
+        pl[:, ~go] = np.minimum(pl[:, ~go], T[:, ~go])
+        if go.any():
+            q = np.flatnonzero(go)
+            for h in (0, 1):
+                m = half_of_row[: hi - lo] == h
+                if m.any():
+                    f0, f1, j0, j1 = d0[h, q], d1[h, q], i0[h, q], i1[h, q]
+                    with np.errstate(invalid="ignore"):
+                        _push(f0, j0, f1, j1, D[rows[m]][:, q], rows[m])
+                    d0[h, q], d1[h, q], i0[h, q], i1[h, q] = f0, f1, j0, j1
+    cd = np.concatenate([d0, d1]); ci = np.concatenate([i0, i1]).astype(np.float64)
+    ci[ci < 0] = np.inf
+    order = np.lexsort((ci, cd), axis=0)
+    ea = np.take_along_axis(cd, order[:1], 0)[0]; eb = np.take_along_axis(cd, order[1:2], 0)[0]
+    ia = np.take_along_axis(ci, order[:1], 0)[0]
+    PL = pl.min(0)
+    with np.errstate(invalid="ignore"):
+        passes = ea < R64 * eb
+        verdict = np.where(~passes, -1, np.where(ea < R64 * PL, ia, -2)).astype(np.int64)
+        Dt = np.where(np.isnan(D), np.inf, D)                          # (a NaN distance is below nothing: the oracle never takes it)
+        o = np.argsort(Dt, axis=0, kind="stable")[:2]
+        t1 = np.take_along_axis(Dt, o[:1], 0)[0]; t2 = np.take_along_axis(Dt, o[1:2], 0)[0]
+        truth = np.where(t1 < R64 * t2, o[0], -1)
+    decided = verdict != -2
+    return {"tiles": tiles, "pruned": pruned, "filtered": filtered, "half": halved, "work": work, "cycles": cycles,
+            "fallback": int((~decided).sum()), "wrong": int((decided & (verdict != truth)).sum()), "matches": int((truth >= 0).sum()),
+            "queries": nJ, "tile_half": tile_half, "tile_filtered": tile_filtered, "tile_pruned": tile_pruned, "verdict": verdict}
+
+
+def run_levels(views, pairs, gp, ratio, squared=True, out=print):
+    """model_pair_levels with and without the f16 level on every pair: the shares per level, the matrix cycles of both, and whether
+    any tile or verdict differs between them (it must not)"""
+    R = ratio * ratio if squared else ratio
+    keys = ("tiles", "pruned", "filtered", "half", "cycles", "fallback", "wrong", "matches", "queries")
+    acc = dict.fromkeys(keys, 0); acc["cycles_cascade"] = 0; acc["differs"] = 0
+    line = lambda r: (f"level 1 {r['half'] / r['tiles']:.4f}  filter behind it {(r['filtered'] - r['half']) / r['tiles']:.4f}  "
+                      f"prefix behind that {(r['pruned'] - r['filtered']) / r['tiles']:.4f}  "
+                      f"matrix cycles a tile {r['cycles'] / r['tiles']:.0f} (cascade {r['cycles_cascade'] / r['tiles']:.0f}, brute force {16 * CYC_GROUP})")
+    for (i, j) in pairs:
+        r = model_pair_levels(views[i], views[j], gp, R)
+        r0 = model_pair_levels(views[i], views[j], gp, R, half=False)
+        r["cycles_cascade"] = r0["cycles"]
+        r["differs"] = int((r["tile_filtered"] != r0["tile_filtered"]).sum() + (r["tile_pruned"] != r0["tile_pruned"]).sum() + (r["verdict"] != r0["verdict"]).sum())
+        for k in acc:
+            acc[k] += r[k]
+        out(f"half + pairnorm + GP {gp:2d}  pair ({i},{j})  {line(r)}  matches {r['matches']:5d}  exact scan {r['fallback']:4d}  "
+            f"wrong verdicts {r['wrong']}  tiles or verdicts unlike the cascade's {r['differs']}")
+    out(f"half + pairnorm + GP {gp:2d}  ALL {len(pairs)} pairs, {acc['queries']} queries, R = {R:.4f}: {line(acc)}  "
+        f"exact scan {acc['fallback']} ({acc['fallback'] / max(acc['queries'], 1):.2e})  wrong verdicts {acc['wrong']}  "
+        f"tiles or verdicts unlike the cascade's {acc['differs']}")
+    return acc
+
+
 def run_cascade(views, pairs, gp, ratio, squared=True, out=print):
     R = ratio * ratio if squared else ratio
     keys = ("tiles", "pruned", "filtered", "work", "fallback", "wrong", "matches", "queries")
@@ -252,7 +400,8 @@ def main():
     ap.add_argument("--gp", type=int, nargs="+", default=[9, 10, 11, 12])
     ap.add_argument("--ratio", type=float, nargs="+", default=[0.6])
     ap.add_argument("--pairs", type=int, default=0, help="pairs (0, 1 .. n); default: every other view")
-    ap.add_argument("--filter", choices=["none", "pairnorm"], default="none", help="pairnorm: the cascade, the pair-norm filter in front of GP = --gp[-1]")
+    ap.add_argument("--filter", choices=["none", "pairnorm", "half"], default="none",
+                    help="pairnorm: the cascade, the pair-norm filter in front of GP = --gp[-1]; half: the f16 level in front of the cascade")
     ap.add_argument("--summary", action="store_true", help="with --filter pairnorm: only the ALL line")
     a = ap.parse_args()
     from regard3d_amd import synth
@@ -261,6 +410,10 @@ def main():
     pairs = [(0, j) for j in range(1, (a.pairs or a.images - 1) + 1)]
     bad = 0
     for ratio in a.ratio:
+        if a.filter == "half":
+            acc = run_levels(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print)
+            bad += acc["wrong"] + acc["differs"]
+            continue
         if a.filter == "pairnorm":
             bad += run_cascade(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print)["wrong"]
             continue
