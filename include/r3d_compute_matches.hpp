@@ -238,7 +238,15 @@ private:
     ImageReleaseFn provider_release_ = nullptr;
     void* provider_user_ = nullptr;
     PhaseTimes phases_;
+    // the phases of computeMatches, in the reference's order (compute_matches.cpp); false: errorMessage_ says why
+    struct Background;                     // what a call has running on host threads: match-file writers, PairWiseMatches map builders
     bool runFeaturesStage(const R3DFParams& params, const std::string& dir);
+    bool loadViews(const std::string& dir);
+    bool listPairs(std::vector<uint32_t>& pairs);
+    bool matchPutative(float dist_ratio, int matchingAlgorithm, const std::vector<uint32_t>& pairs, r3dm_graph** putative);
+    void startPutativeFiles(r3dm_graph* putative, const R3DProjectPaths& paths, bool svgOutput, Background& bg);
+    bool runFilters(const R3DFParams& params, const R3DProjectPaths& paths, const r3dm_graph* putative, Background& bg);
+    bool finishFiles(Background& bg);
     R3DComputeMatchesStatistics statistics_;
     std::string errorMessage_;
 };

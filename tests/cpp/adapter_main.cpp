@@ -48,6 +48,20 @@ static int run_stage(r3d_amd::R3DComputeMatches& stage, const char* matches_dir,
     // R3DM_TEST_ARMS=requested: approximate arms always on the graph matcher (default: on whichever matcher is faster for the views)
     const char* arms_env = getenv("R3DM_TEST_ARMS");
     if (arms_env && !strcmp(arms_env, "requested")) stage.setApproximateArmsPolicy(r3d_amd::R3DComputeMatches::kArmsAsRequested);
+    // R3DM_TEST_FILTERS: which of the three filters run, a subset of the letters FEH (default: all three)
+    if (const char* filters_env = getenv("R3DM_TEST_FILTERS")) {
+        params.computeFundalmentalMatrix_ = strchr(filters_env, 'F') != nullptr;
+        params.computeEssentialMatrix_ = strchr(filters_env, 'E') != nullptr;
+        params.computeHomographyMatrix_ = strchr(filters_env, 'H') != nullptr;
+    }
+    // R3DM_TEST_NAMED=1: the four match files get the names a project gives them, in <matches_dir>/named (which exists)
+    if (getenv("R3DM_TEST_NAMED")) {
+        const std::string named = std::string(matches_dir) + "/named/";
+        paths.matchesPutitativeFilename_ = named + "project.putative.txt";
+        paths.matchesFFilename_ = named + "project.f.txt";
+        paths.matchesEFilename_ = named + "project.e.txt";
+        paths.matchesHFilename_ = named + "project.h.txt";
+    }
     const bool ok = stage.computeMatches(params, true, paths, 1, algo);
     if (!ok) { fprintf(stderr, "computeMatches failed: %s\n", stage.errorMessage().c_str()); return 7; }
     fprintf(stderr, "matcher %s\n", stage.lastMatchWasExhaustive() ? "exhaustive" : (stage.lastMatchWasHnsw() ? "hnsw" : "graph"));

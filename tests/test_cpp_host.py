@@ -246,6 +246,94 @@ def test_stage_facade_on_a_device_list_writes_the_same_files(host_exe, oracle, t
         assert open(str(tmp_path / f), "rb").read() == blob, f
 
 
+_STAGE_GRAPHS = ("putative", "f", "e", "h")
+_ANNOUNCED = {"F": "progress 0.80 Calculate fundamental matrix", "E": "progress 0.90 Calculate essential matrix",
+              "H": "progress 0.95 Calculate homography matrix"}
+
+
+def _run_filters_stage(sf, **env):
+    """one run of the stage program on the scene of `stage_filters`, every match file of an earlier run deleted first"""
+    d = sf["dir"]
+    for sub, stem in (("", "matches"), ("named", "project")):
+        for g in _STAGE_GRAPHS:
+            for ext in ("txt", "bin"):
+                p = os.path.join(d, sub, f"{stem}.{g}.{ext}")
+                if os.path.exists(p):
+                    os.remove(p)
+    r = subprocess.run([sf["exe"], "stage", d, "144"] + sf["names"], capture_output=True, text=True, env=dict(os.environ, **env))
+    assert r.returncode == 0, r.stderr
+    return r
+
+
+def _stage_files(d, stem="matches"):
+    """the bytes of the match files that exist, by '<graph>.<ext>'"""
+    out = {}
+    for g in _STAGE_GRAPHS:
+        for ext in ("txt", "bin"):
+            p = os.path.join(d, f"{stem}.{g}.{ext}")
+            if os.path.exists(p):
+                out[f"{g}.{ext}"] = open(p, "rb").read()
+    return out
+
+
+@pytest.fixture(scope="module")
+def stage_filters(host_exe, oracle, tmp_path_factory):
+    """a 4-view LIOP scene on which the F and the E filter keep pairs (the seed was chosen with the oracle, and the oracle's counts
+    are asserted here, so no comparison below is one of empty files; H keeps one pair or none), and the files of the reference run:
+    F + E + H on one device"""
+    d = str(tmp_path_factory.mktemp("stage_filters"))
+    os.mkdir(os.path.join(d, "named"))
+    sc = synth.make_scene(4, 600, "liop", seed=42)
+    sf = {"dir": d, "exe": host_exe, "names": _write_views(oracle, d, sc)}
+    pairs = sc.exhaustive_pairs()
+    counts, matches = oracle.match_collection(sc.descs, sc.xys, pairs, 0.6, True)
+    of, _ = oracle.filter_F_collection(sc.xys, sc.widths, sc.heights, pairs, counts, matches, 4.0, 2048, 5489)
+    Ks = np.stack([synth.intrinsics()] * sc.n_images)
+    oe, _ = oracle.filter_E_collection(sc.xys, sc.widths, sc.heights, Ks, pairs, counts, matches, 4.0, 2048, 5489)
+    assert (of > 0).sum() >= 1 and (oe > 0).sum() >= 1
+    r = _run_filters_stage(sf)
+    sf["n_put"], sf["n_f"] = map(int, r.stdout.split())
+    sf["ref"] = _stage_files(d)
+    assert sorted(sf["ref"]) == sorted(f"{g}.{ext}" for g in _STAGE_GRAPHS for ext in ("txt", "bin"))
+    assert sf["n_put"] == int((counts > 0).sum()) and sf["n_f"] == int((of > 0).sum())
+    for g, kept in (("f", of), ("e", oe)):
+        assert np.array_equal(oracle.load_matches(os.path.join(d, f"matches.{g}.bin"))[0], pairs[kept > 0])
+    return sf
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("subset,devices", [(s, n) for n in ("1", "2") for s in ("F", "E", "H", "FE", "FH", "EH")] + [("FEH", "2")])
+def test_stage_facade_runs_the_filters_asked_for(stage_filters, subset, devices):
+    """every proper subset of the F / E / H filters, on one device (two of them: side by side, r3dm_filter_FEH) and on a device list
+    (one dealt call per filter), and all three on the device list: the files of the filters asked for and the putative files are
+    those of the F + E + H run on one device, byte for byte; no other match file is written; a progress line announces each filter
+    that runs, and only those"""
+    sf = stage_filters
+    r = _run_filters_stage(sf, R3DM_TEST_FILTERS=subset, R3DM_TEST_DEVICES=devices)
+    want = {k: v for k, v in sf["ref"].items() if k.startswith("putative") or k[0].upper() in subset}
+    got = _stage_files(sf["dir"])
+    assert sorted(got) == sorted(want)
+    for k in want:
+        assert got[k] == want[k], k
+    prog = [l for l in r.stderr.splitlines() if l.startswith("progress")]
+    assert prog == ["progress 0.70 Find putative matches"] + [_ANNOUNCED[c] for c in subset]
+    assert list(map(int, r.stdout.split())) == [sf["n_put"], sf["n_f"] if "F" in subset else 0]
+
+
+@pytest.mark.gpu
+def test_stage_facade_writes_to_the_named_paths(stage_filters):
+    """R3DProjectPaths::matches*Filename_: the four .txt files and their .bin siblings appear under the names the project gives them,
+    with the bytes of the default-named run, and nothing is written under the default names"""
+    sf = stage_filters
+    r = _run_filters_stage(sf, R3DM_TEST_NAMED="1")
+    assert list(map(int, r.stdout.split())) == [sf["n_put"], sf["n_f"]]
+    assert _stage_files(sf["dir"]) == {}
+    got = _stage_files(os.path.join(sf["dir"], "named"), "project")
+    assert sorted(got) == sorted(sf["ref"])
+    for k in sf["ref"]:
+        assert got[k] == sf["ref"][k], k
+
+
 @pytest.mark.gpu
 def test_features_facade_matches_oracle(host_exe, oracle, tmp_path):
     """Regard3DFeatures::detectAndExtract (include/regard3d_features.hpp) == CPU restatement of detect + LIOP"""
