@@ -621,6 +621,48 @@ def dev_walk_args(levels, lists):
     return lv, n_cand, words
 
 
+def bind_dev_akaze_classic_head(L):
+    """the developer build's classic head entries (libr3dm_dev.so only, declared in no header), bound when first asked for"""
+    if getattr(L, "_r3dm_dev_classic_head_bound", False):
+        return L
+    if not hasattr(L, "r3dm_dev_akaze_classic_head"):
+        raise R3dmError("r3dm_dev_akaze_classic_head exists in the developer build only: use_developer_library() before the first load")
+    vp, u32 = C.c_void_p, C.c_uint32
+    L.r3dm_dev_akaze_classic_levels.argtypes = [u32, u32, vp, vp]
+    L.r3dm_dev_akaze_classic_head_check.argtypes = [u32, vp, u32, u32]
+    L.r3dm_dev_akaze_classic_head.argtypes = [vp, u32, vp, u32, u32, C.c_float, vp, vp, vp, u32, vp, vp]
+    L.r3dm_dev_akaze_classic_extrema_check.argtypes = [u32, u32, u32, u32, vp, vp]
+    L.r3dm_dev_akaze_classic_extrema.argtypes = [vp, u32, u32, u32, u32, vp, vp, C.c_float, vp, u32, vp, vp]
+    L._r3dm_dev_classic_head_bound = True
+    return L
+
+
+def dev_akaze_classic_levels(L, width: int, height: int):
+    """r3dm_dev_akaze_classic_levels (needs no device): the classic arm's level table of an image size, a list of dicts"""
+    bind_dev_akaze_classic_head(L)
+    lv = (DevAcLevel * 16)()
+    n = C.c_uint32(0)
+    rc = L.r3dm_dev_akaze_classic_levels(width, height, C.addressof(lv), C.addressof(n))
+    if rc != 0:
+        raise R3dmError(f"r3dm_dev_akaze_classic_levels -> {rc}")
+    return [dict(w=lv[i].w, h=lv[i].h, octave=lv[i].octave, esigma=lv[i].esigma, ratio=lv[i].ratio) for i in range(n.value)]
+
+
+def dev_classic_bound(levels) -> int:
+    """the candidates an image of this level table can hold at most: strict 3 x 3 maxima lie at least two apart on both axes, inside
+    rows 1 .. h - 2 and columns 1 .. w - 2"""
+    return sum(((e["w"] - 1) // 2) * ((e["h"] - 1) // 2) for e in levels)
+
+
+def _dev_classic_candidates(counts, n, cand, B):
+    """per image (counts [n_levels] uint32, candidates [n, 4]: x, y, level as uint32 words and the value's bits) -> dicts"""
+    out = []
+    for b in range(B):
+        words = cand[b, :int(n[b])].copy()
+        out.append(dict(counts=counts[b].copy(), x=words[:, 0], y=words[:, 1], level=words[:, 2], value=words[:, 3].copy().view(np.float32)))
+    return out
+
+
 class DevAkLevel(C.Structure):
     """r3dm_dev_ak_level (developer build, api_akaze.cpp): one level of the Fast arm's level table"""
     _fields_ = [("w", C.c_int32), ("h", C.c_int32), ("border", C.c_int32), ("sigma_size", C.c_int32), ("ratio", C.c_float),
@@ -1606,6 +1648,45 @@ class Context:
                             kept=o[:, 5] != 0, hist=hist[b].copy()))
             at += int(n_cand[b])
         return res
+
+    def dev_akaze_classic_head(self, images, threshold: float):
+        """r3dm_dev_akaze_classic_head (developer build): the classic arm's head -- k-contrast, scale space, derivatives, determinant,
+        extremum passes, the functions the detector calls -- on same-size images [h, w] in [0, 1] -> per image a dict: hmax_bits
+        (uint32), hist [300] uint32, inv_k2 [8] float32, planes [n_levels] of dicts Lsmooth, Lflow (None at level 0), Lt, Lx, Ly, Ldet
+        float32 [h_i, w_i], counts [n_levels] uint32, and the candidates in scan order: x, y, level uint32 and value float32"""
+        L = bind_dev_akaze_classic_head(self._L)
+        ptrs, keep = dev_head_images(images)
+        B = len(keep)
+        h, w = keep[0].shape
+        lv = dev_akaze_classic_levels(L, w, h)
+        nl, cap = len(lv), max(dev_classic_bound(lv), 1)
+        names = ("Lsmooth", "Lflow", "Lt", "Lx", "Ly", "Ldet")
+        planes = [[[np.zeros((e["h"], e["w"]), np.float32) for _ in names] for e in lv] for _ in range(B)]
+        pp = (C.c_void_p * (B * nl * 6))(*[q.ctypes.data for im in planes for lev in im for q in lev])
+        small = np.zeros((B, 309), np.uint32); counts = np.zeros((B, nl), np.uint32); n = np.zeros(B, np.uint32)
+        cand = np.zeros((B, cap, 4), np.uint32)
+        self._check(L.r3dm_dev_akaze_classic_head(self._h, B, C.addressof(ptrs), w, h, float(threshold), _ptr(small), C.addressof(pp),
+                                                  _ptr(counts), cap, _ptr(n), _ptr(cand)), "r3dm_dev_akaze_classic_head")
+        del keep
+        res = _dev_classic_candidates(counts, n, cand, B)
+        for b, r in enumerate(res):
+            r.update(hmax_bits=small[b, 0].copy(), hist=small[b, 1:301].copy(), inv_k2=small[b, 301:309].copy().view(np.float32),
+                     planes=[{k: (None if i == 0 and k == "Lflow" else q) for k, q in zip(names, lev)} for i, lev in enumerate(planes[b])])
+        return res
+
+    def dev_akaze_classic_extrema(self, width: int, height: int, planes, threshold: float):
+        """r3dm_dev_akaze_classic_extrema (developer build): the classic arm's extremum passes, row scan and totals on the caller's
+        determinant planes (per image [n_levels] float32 [h_i, w_i], the level table of width x height; any value) -> per image a
+        dict: counts [n_levels] uint32 and the candidates in scan order (x, y, level, value)"""
+        L = bind_dev_akaze_classic_head(self._L)
+        nl, dims, ptrs, keep = dev_extrema_args(planes)
+        B = len(planes)
+        cap = max(dev_classic_bound(dev_akaze_classic_levels(L, width, height)), 1)
+        counts = np.zeros((B, max(nl, 1)), np.uint32); n = np.zeros(B, np.uint32); cand = np.zeros((B, cap, 4), np.uint32)
+        self._check(L.r3dm_dev_akaze_classic_extrema(self._h, width, height, B, nl, _ptr(dims), C.addressof(ptrs), float(threshold),
+                                                     _ptr(counts), cap, _ptr(n), _ptr(cand)), "r3dm_dev_akaze_classic_extrema")
+        del keep
+        return _dev_classic_candidates(counts, n, cand, B)
 
     def dev_akaze_tail(self, width: int, height: int, images):
         """r3dm_dev_akaze_tail (developer build): the Fast arm's tail -- cross-level filters, refinement, orientation, compaction, the

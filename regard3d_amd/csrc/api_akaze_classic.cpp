@@ -133,6 +133,114 @@ int ac_walk(r3dm_ctx* c, uint32_t B, int w, int h, const AcLevelTab& tab, const 
     return R3DM_OK;
 }
 
+// The head's work buffers on the context, kept between calls (they grow, never shrink; released with the context): B planes each of the
+// image, two evolving images, the smoothed image, the conductivity and a Gaussian scratch; the per-image scalars; per level Lx, Ly, Ldet
+// (read again by the refinement and the orientation).
+int ac_head_bufs(r3dm_ctx* c, uint32_t B, const std::vector<AkLevelHost>& lv)
+{
+    ac_bufs_init(c);
+    const size_t n0 = (size_t)lv[0].w * lv[0].h;
+    for (int k : {C_IMG, C_LTA, C_LTB, C_SMOOTH, C_FLOW, C_TMP}) R3DM_HIP(c, c->ac_bufs[k].ensure((size_t)B * n0 * 4));
+    R3DM_HIP(c, c->ac_bufs[C_SMALL].ensure((size_t)B * 4096 * 4));
+    for (size_t i = 0; i < lv.size(); ++i)
+        for (int q = 0; q < 3; ++q) R3DM_HIP(c, c->ac_bufs[C_PLANES + 3 * i + q].ensure((size_t)B * lv[i].w * lv[i].h * 4));
+    return R3DM_OK;
+}
+float* ac_plane(r3dm_ctx* c, int level, int q) { return c->ac_bufs[C_PLANES + 3 * level + q].as<float>(); }     // q: 0 Lx, 1 Ly, 2 Ldet
+
+// A tap of ac_scale_space: called when a level's FED steps are queued, with the level's Lsmooth (the image its derivatives are taken
+// from), its conductivity (null at level 0, which has none) and its Lt, B planes each.  The three are work buffers the next level
+// overwrites: a tap copies what it wants on the context's stream.  R3DM_OK, or the code the scale space returns with.
+using AcTap = std::function<int(int level, const float* smooth, const float* flow, const float* lt)>;
+
+// Create_Nonlinear_Scale_Space (AKAZE.cpp:102-170) with Compute_Multiscale_Derivatives + Compute_Determinant_Hessian_Response (:188-248)
+// of every level, for the B images in C_IMG (ac_head_bufs; half_tabs from detect_area_tabs).  Queues on the context's stream and returns
+// without waiting: Lx, Ly and Ldet of every level stand in the level planes, the histogram words in C_SMALL.  The detector passes no tap;
+// the developer build's head entry (r3dm_dev_akaze_classic_head below) reads the planes through one.
+int ac_scale_space(r3dm_ctx* c, uint32_t B, const std::vector<AkLevelHost>& lv, const std::vector<HalfTabs>& half_tabs, const AcTap* tap)
+{
+    hipStream_t st = c->stream;
+    const int iB = (int)B, nl = (int)lv.size(), w = lv[0].w, h = lv[0].h;
+    auto buf = [&](int k) { return c->ac_bufs[k].as<float>(); };
+    float *img = buf(C_IMG), *smooth = buf(C_SMOOTH), *flow = buf(C_FLOW), *tmp = buf(C_TMP);
+    const AkTaps taps_off = ak_taps(1.6f), taps_one = ak_taps(1.0f);
+    uint32_t* sm = c->ac_bufs[C_SMALL].as<uint32_t>();
+    const float* inv_k2 = reinterpret_cast<const float*>(sm + 1024);
+    int trc = R3DM_OK;
+    // Level 0: Lt = Lsmooth = the soffset Gaussian of the image.  The contrast factor is compute_k_percentile of the INPUT image
+    // (sigma 1, Scharr, its own histogram: ac_kcontrast).
+    float* cur = buf(C_LTA);
+    float* other = buf(C_LTB);
+    R3DM_HIP(c, ak_gaussian(st, img, tmp, cur, w, h, iB, taps_off));
+    R3DM_HIP(c, hipMemsetAsync(sm, 0, (size_t)B * 4096 * 4, st));
+    R3DM_HIP(c, ak_gaussian(st, img, tmp, smooth, w, h, iB, taps_one));
+    R3DM_HIP(c, ak_modg_max(st, smooth, w, h, iB, sm));
+    R3DM_HIP(c, ac_kcontrast(st, smooth, w, h, iB, sm));
+    // the derivatives and the determinant of a level: from its Lsmooth, taps of scale s
+    auto hessian = [&](int i, const float* src) -> hipError_t {
+        const int s = lv[i].sigma_size;
+        const float wq = (float)(10.0 / 3.0);
+        const float norm = (float)(1.0 / (2.0 * (double)s * (wq + 2.0)));
+        return ac_hessian(st, src, ac_plane(c, i, 0), ac_plane(c, i, 1), ac_plane(c, i, 2), lv[i].w, lv[i].h, iB, s, norm, wq * norm);
+    };
+    R3DM_HIP(c, hessian(0, cur));
+    if (tap && (trc = (*tap)(0, cur, nullptr, cur)) != R3DM_OK) return trc;
+    for (int i = 1; i < nl; ++i) {
+        const int lw = lv[i].w, lh = lv[i].h;
+        if (lv[i].octave > lv[i - 1].octave) {
+            const HalfTabs& ht = half_tabs[i];
+            R3DM_HIP(c, ak_halfsample(st, cur, other, lv[i - 1].w, lv[i - 1].h, iB, ht.xt, ht.xb, ht.yt, ht.yb));
+            std::swap(cur, other);
+        }
+        // (same octave: the previous level's Lt is this level's start image, copyTo without a copy)
+        R3DM_HIP(c, ak_gaussian(st, cur, tmp, smooth, lw, lh, iB, taps_one));
+        R3DM_HIP(c, hessian(i, smooth));
+        R3DM_HIP(c, ak_scharr_g2(st, smooth, flow, lw, lh, iB, inv_k2 + lv[i].octave));   // pm_g2, 1 / k^2 of the octave
+        for (float tau : ac_fed_tau(lv[i].etime - lv[i - 1].etime)) {
+            R3DM_HIP(c, ac_fed_step(st, cur, flow, other, lw, lh, iB, 0.5f * tau));
+            std::swap(cur, other);
+        }
+        if (tap && (trc = (*tap)(i, smooth, flow, cur)) != R3DM_OK) return trc;
+    }
+    return R3DM_OK;
+}
+
+// Find_Scale_Space_Extrema's candidates (AKAZE.cpp:251-287) of the B images' Ldet planes: per-row counts, their scan, the totals (the
+// one wait of the head: the candidate stride is the largest total), then the candidates in scan order (levels, rows, columns) in C_CAND.
+// The detector and the developer build's head and extrema entries all go through it.
+struct AcExtrema {
+    std::vector<uint32_t> row0, tot;                     // first row of each level among the image's n_rows rows; candidates per image
+    uint32_t n_rows = 0, rows_stride = 0, stride = 1;    // stride: candidates per image in C_CAND
+    uint32_t* rc = nullptr;                              // device: row offsets, rows_stride per image
+    uint32_t* totals = nullptr;                          // device: [B]
+};
+int ac_find_extrema(r3dm_ctx* c, uint32_t B, const std::vector<AkLevelHost>& lv, float threshold, AcExtrema& x)
+{
+    hipStream_t st = c->stream;
+    const int iB = (int)B, nl = (int)lv.size();
+    x.row0.assign(nl, 0u);
+    x.n_rows = 0;
+    for (int i = 0; i < nl; ++i) { x.row0[i] = x.n_rows; x.n_rows += (uint32_t)lv[i].h; }
+    x.rows_stride = x.n_rows + 1;
+    DevBuf &rows = c->ac_bufs[C_ROWS], &cand = c->ac_bufs[C_CAND];
+    R3DM_HIP(c, rows.ensure(((size_t)B * x.rows_stride + B) * 4));
+    x.rc = rows.as<uint32_t>();
+    x.totals = x.rc + (size_t)B * x.rows_stride;
+    R3DM_HIP(c, hipMemsetAsync(x.rc, 0, ((size_t)B * x.rows_stride + B) * 4, st));
+    for (int i = 0; i < nl; ++i)
+        R3DM_HIP(c, ac_extrema(st, ac_plane(c, i, 2), lv[i].w, lv[i].h, iB, threshold, x.rc, x.rows_stride, x.row0[i], nullptr, 0, i, 0));
+    R3DM_HIP(c, ac_scan_rows(st, x.rc, x.rows_stride, x.n_rows, iB, x.totals));
+    x.tot.assign(B, 0u);
+    R3DM_HIP(c, hipMemcpyAsync(x.tot.data(), x.totals, (size_t)B * 4, hipMemcpyDeviceToHost, st));
+    R3DM_HIP(c, hipStreamSynchronize(st));
+    x.stride = 1;
+    for (uint32_t b = 0; b < B; ++b) x.stride = std::max(x.stride, x.tot[b]);
+    R3DM_HIP(c, cand.ensure((size_t)B * x.stride * sizeof(AcCand)));
+    for (int i = 0; i < nl; ++i)
+        R3DM_HIP(c, ac_extrema(st, ac_plane(c, i, 2), lv[i].w, lv[i].h, iB, threshold, x.rc, x.rows_stride, x.row0[i], cand.as<AcCand>(), x.stride, i, 1));
+    return R3DM_OK;
+}
+
 }  // namespace
 
 // the detector over B same-size images; out.classic[b] = the keypoints of image b in the reference's order.
@@ -146,92 +254,26 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     if (width < 3 || height < 3) return R3DM_OK;                      // no 3 x 3 maximum exists
     R3DM_HIP(c, hipSetDevice(c->device));
     const double t_call = now_ms();
-    const int w = (int)width, h = (int)height, iB = (int)B;
+    const int w = (int)width, h = (int)height;
     const std::vector<AkLevelHost> lv = ac_levels(w, h);
     const int nl = (int)lv.size();
     hipStream_t st = c->stream;
     const size_t n0 = (size_t)w * h;
 
-    // work buffers on the context, kept between calls (they grow, never shrink; released with the context): B planes each of the image,
-    // two evolving images, the smoothed image, the conductivity and a Gaussian scratch; per level Lx, Ly, Ldet (read again by the
-    // refinement and the orientation); then the candidate, slot, grid and output arrays
-    ac_bufs_init(c);
-    auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
-    DevBuf &img = buf(C_IMG), &ltA = buf(C_LTA), &ltB = buf(C_LTB), &smooth = buf(C_SMOOTH), &flow = buf(C_FLOW), &tmp = buf(C_TMP);
-    DevBuf &small = buf(C_SMALL), &rows = buf(C_ROWS), &tabs = buf(C_TABS);
-    DevBuf* planes = &c->ac_bufs[C_PLANES];
-    for (DevBuf* b : {&img, &ltA, &ltB, &smooth, &flow, &tmp}) R3DM_HIP(c, b->ensure((size_t)B * n0 * 4));
-    R3DM_HIP(c, small.ensure((size_t)B * 4096 * 4));
-    for (int i = 0; i < nl; ++i)
-        for (int q = 0; q < 3; ++q) R3DM_HIP(c, planes[3 * i + q].ensure((size_t)B * lv[i].w * lv[i].h * 4));
-    auto Lx = [&](int i) { return planes[3 * i].as<float>(); };
-    auto Ly = [&](int i) { return planes[3 * i + 1].as<float>(); };
-    auto Ldet = [&](int i) { return planes[3 * i + 2].as<float>(); };
-    out.grays_dev = img.as<float>();
-    // (BGR: the bytes are staged in the not yet used work image tmp)
-    int frc = detect_upload(c, B, images, bgrs, n0, img.as<float>(), tmp.as<unsigned char>());
+    int frc = ac_head_bufs(c, B, lv);
     if (frc != R3DM_OK) return frc;
+    auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
+    out.grays_dev = buf(C_IMG).as<float>();
+    // (BGR: the bytes are staged in the not yet used work image C_TMP)
+    if ((frc = detect_upload(c, B, images, bgrs, n0, buf(C_IMG).as<float>(), buf(C_TMP).as<unsigned char>())) != R3DM_OK) return frc;
     std::vector<HalfTabs> half_tabs;
-    if ((frc = detect_area_tabs(c, tabs, lv, half_tabs)) != R3DM_OK) return frc;
-    const AkTaps taps_off = ak_taps(1.6f), taps_one = ak_taps(1.0f);
-    uint32_t* sm = small.as<uint32_t>();
-    const float* inv_k2 = reinterpret_cast<const float*>(sm + 1024);
+    if ((frc = detect_area_tabs(c, buf(C_TABS), lv, half_tabs)) != R3DM_OK) return frc;
     R3DM_HIP(c, hipEventRecord(c->ev0, st));
-
-    // Create_Nonlinear_Scale_Space (AKAZE.cpp:102-170).  Level 0: Lt = Lsmooth = the soffset Gaussian of the image.  The contrast factor is
-    // compute_k_percentile of the INPUT image (sigma 1, Scharr, its own histogram: ac_kcontrast).
-    float* cur = ltA.as<float>();
-    float* other = ltB.as<float>();
-    R3DM_HIP(c, ak_gaussian(st, img.as<float>(), tmp.as<float>(), cur, w, h, iB, taps_off));
-    R3DM_HIP(c, hipMemsetAsync(sm, 0, (size_t)B * 4096 * 4, st));
-    R3DM_HIP(c, ak_gaussian(st, img.as<float>(), tmp.as<float>(), smooth.as<float>(), w, h, iB, taps_one));
-    R3DM_HIP(c, ak_modg_max(st, smooth.as<float>(), w, h, iB, sm));
-    R3DM_HIP(c, ac_kcontrast(st, smooth.as<float>(), w, h, iB, sm));
-    // Compute_Multiscale_Derivatives + Compute_Determinant_Hessian_Response (:188-248) of a level: from its Lsmooth, taps of scale s
-    auto hessian = [&](int i, const float* src) -> hipError_t {
-        const int s = lv[i].sigma_size;
-        const float wq = (float)(10.0 / 3.0);
-        const float norm = (float)(1.0 / (2.0 * (double)s * (wq + 2.0)));
-        return ac_hessian(st, src, Lx(i), Ly(i), Ldet(i), lv[i].w, lv[i].h, iB, s, norm, wq * norm);
-    };
-    R3DM_HIP(c, hessian(0, cur));
-    for (int i = 1; i < nl; ++i) {
-        const int lw = lv[i].w, lh = lv[i].h;
-        if (lv[i].octave > lv[i - 1].octave) {
-            const HalfTabs& ht = half_tabs[i];
-            R3DM_HIP(c, ak_halfsample(st, cur, other, lv[i - 1].w, lv[i - 1].h, iB, ht.xt, ht.xb, ht.yt, ht.yb));
-            std::swap(cur, other);
-        }
-        // (same octave: the previous level's Lt is this level's start image, copyTo without a copy)
-        R3DM_HIP(c, ak_gaussian(st, cur, tmp.as<float>(), smooth.as<float>(), lw, lh, iB, taps_one));
-        R3DM_HIP(c, hessian(i, smooth.as<float>()));
-        R3DM_HIP(c, ak_scharr_g2(st, smooth.as<float>(), flow.as<float>(), lw, lh, iB, inv_k2 + lv[i].octave));   // pm_g2, 1 / k^2 of the octave
-        for (float tau : ac_fed_tau(lv[i].etime - lv[i - 1].etime)) {
-            R3DM_HIP(c, ac_fed_step(st, cur, flow.as<float>(), other, lw, lh, iB, 0.5f * tau));
-            std::swap(cur, other);
-        }
-    }
-
-    // Find_Scale_Space_Extrema (:251-386): per-row counts, their scan, the candidates in scan order (levels, rows, columns)
-    std::vector<uint32_t> row0(nl);
-    uint32_t n_rows = 0;
-    for (int i = 0; i < nl; ++i) { row0[i] = n_rows; n_rows += (uint32_t)lv[i].h; }
-    const uint32_t rows_stride = n_rows + 1;
-    R3DM_HIP(c, rows.ensure(((size_t)B * rows_stride + B) * 4));
-    uint32_t* rc = rows.as<uint32_t>();
-    uint32_t* totals = rc + (size_t)B * rows_stride;
-    R3DM_HIP(c, hipMemsetAsync(rc, 0, ((size_t)B * rows_stride + B) * 4, st));
-    for (int i = 0; i < nl; ++i) R3DM_HIP(c, ac_extrema(st, Ldet(i), lv[i].w, lv[i].h, iB, threshold, rc, rows_stride, row0[i], nullptr, 0, i, 0));
-    R3DM_HIP(c, ac_scan_rows(st, rc, rows_stride, n_rows, iB, totals));
-    std::vector<uint32_t> tot(B);
-    R3DM_HIP(c, hipMemcpyAsync(tot.data(), totals, (size_t)B * 4, hipMemcpyDeviceToHost, st));
-    R3DM_HIP(c, hipStreamSynchronize(st));
-    uint32_t stride = 1;
-    for (uint32_t b = 0; b < B; ++b) stride = std::max(stride, tot[b]);
-    DevBuf &cand = buf(C_CAND), &nsl = buf(C_NSL), &outs = buf(C_OUTS);
-    R3DM_HIP(c, cand.ensure((size_t)B * stride * sizeof(AcCand)));
-    for (int i = 0; i < nl; ++i)
-        R3DM_HIP(c, ac_extrema(st, Ldet(i), lv[i].w, lv[i].h, iB, threshold, rc, rows_stride, row0[i], cand.as<AcCand>(), stride, i, 1));
+    if ((frc = ac_scale_space(c, B, lv, half_tabs, nullptr)) != R3DM_OK) return frc;
+    AcExtrema ex;
+    if ((frc = ac_find_extrema(c, B, lv, threshold, ex)) != R3DM_OK) return frc;
+    const uint32_t stride = ex.stride;
+    DevBuf &nsl = buf(C_NSL), &outs = buf(C_OUTS);
     AcLevelTab tab{};
     AcPlanes pl{};
     tab.n_levels = nl;
@@ -239,16 +281,16 @@ int ac_detect_batch(r3dm_ctx* c, uint32_t B, const float* const* images, const u
     for (int i = 0; i < nl; ++i) {
         tab.w[i] = lv[i].w; tab.h[i] = lv[i].h; tab.octave[i] = lv[i].octave;
         tab.esigma[i] = lv[i].esigma; tab.ratio[i] = lv[i].ratio; tab.off[i] = (float)(.5 * (lv[i].ratio - 1.0));
-        pl.ldet[i] = Ldet(i); pl.lx[i] = Lx(i); pl.ly[i] = Ly(i);
+        pl.ldet[i] = ac_plane(c, i, 2); pl.lx[i] = ac_plane(c, i, 0); pl.ly[i] = ac_plane(c, i, 1);
     }
-    for (int i = 0; i < nl; ++i) tab.row0[i] = row0[i];
+    for (int i = 0; i < nl; ++i) tab.row0[i] = ex.row0[i];
     // the candidates, their row offsets and totals are on the device: the walk, the upper-level filter, refinement and orientation.
     // R3DM_AC_AUX=0 (developer build): the one-wavefront walk over every candidate and the upper-level filter over every later slot.
     // R3DM_AC_AUX_BOUND (test hook): a smaller wavefront bound hands more components back to the one-wavefront walk.
     static const bool parallel = r3dm_dev_knob("R3DM_AC_AUX", 1) != 0;
     static const uint32_t bound = [] { const int v = r3dm_dev_knob("R3DM_AC_AUX_BOUND", 64); return (uint32_t)(v < 1 ? 1 : v > 64 ? 64 : v); }();
     uint32_t* hist = nullptr;
-    if ((frc = ac_walk(c, B, w, h, tab, pl, stride, rc, rows_stride, totals, parallel, bound, &hist)) != R3DM_OK) return frc;
+    if ((frc = ac_walk(c, B, w, h, tab, pl, stride, ex.rc, ex.rows_stride, ex.totals, parallel, bound, &hist)) != R3DM_OK) return frc;
     R3DM_HIP(c, hipEventRecord(c->ev1, st));
     std::vector<uint32_t> ns(B), hs(hist ? (size_t)B * 32 : 0);
     R3DM_HIP(c, hipMemcpyAsync(ns.data(), nsl.p, (size_t)B * 4, hipMemcpyDeviceToHost, st));
@@ -433,6 +475,159 @@ extern "C" int r3dm_dev_akaze_classic_walk(r3dm_ctx* c, const r3dm_dev_ac_level*
             at += n_cand[b];
         }
         return R3DM_OK;
+    });
+}
+
+// ---- the head, plane by plane ("The head, plane by plane"): the entries below run ac_scale_space and
+// ac_find_extrema, the functions the detector calls, and read back what the detector only passes on.
+constexpr uint32_t kAcDevSmallOut = 309;             // hmax bits, 300 bins, 1 / k^2 of octaves 0 .. 7
+
+// the level table of an image size (needs no device): levels_out [<= 16], *n_levels_out
+extern "C" int r3dm_dev_akaze_classic_levels(uint32_t width, uint32_t height, r3dm_dev_ac_level* levels_out, uint32_t* n_levels_out)
+{
+    if (!levels_out || !n_levels_out || width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ac_levels((int)width, (int)height);
+    for (size_t i = 0; i < lv.size(); ++i) levels_out[i] = r3dm_dev_ac_level{lv[i].w, lv[i].h, lv[i].octave, lv[i].esigma, lv[i].ratio};
+    *n_levels_out = (uint32_t)lv.size();
+    return R3DM_OK;
+}
+
+// Refused before anything touches a device (R3DM_OK or R3DM_ERR_INVALID): B outside 1 .. 1024, a dimension below 3 (no 3 x 3 maximum
+// exists; the FED step's corner forms read a neighbour on either axis) or above 65536, a null image array or image, a value that is
+// not finite or lies outside [0, 1].  Every kernel of the head addresses by the plane's own (w, h) alone -- clamped or reflected taps,
+// one-sided fluxes on the rim -- and the histogram's bin floor(300 (modg / hmax)) of a finite modulus <= hmax lies in 0 .. 300, folded
+// to 299.
+extern "C" int r3dm_dev_akaze_classic_head_check(uint32_t B, const float* const* images, uint32_t width, uint32_t height)
+{
+    if (!images || B < 1 || B > 1024u) return R3DM_ERR_INVALID;
+    if (width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    const size_t n0 = (size_t)width * height;
+    for (uint32_t b = 0; b < B; ++b) {
+        if (!images[b]) return R3DM_ERR_INVALID;
+        for (size_t k = 0; k < n0; ++k) if (!(images[b][k] >= 0.0f && images[b][k] <= 1.0f)) return R3DM_ERR_INVALID;    // (false for a NaN too)
+    }
+    return R3DM_OK;
+}
+
+// Refused (R3DM_OK or R3DM_ERR_INVALID): B outside 1 .. 1024, an image size below 3 or above 65536, n_levels or plane_dims [n_levels][2]
+// (w, h) other than the table's of (width, height), a null array or plane.  planes [B][n_levels].  Any VALUE is taken, NaN and the
+// infinities included: ac_extrema_kernel only compares them (rows 1 .. h - 2, columns 1 .. w - 2 and their eight neighbours, inside a
+// plane of the table's size).
+extern "C" int r3dm_dev_akaze_classic_extrema_check(uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels, const uint32_t* plane_dims,
+                                                    const float* const* planes)
+{
+    if (!plane_dims || !planes || B < 1 || B > 1024u) return R3DM_ERR_INVALID;
+    if (width < 3 || height < 3 || width > 65536u || height > 65536u) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ac_levels((int)width, (int)height);
+    if (n_levels != lv.size()) return R3DM_ERR_INVALID;
+    for (size_t i = 0; i < lv.size(); ++i)
+        if (plane_dims[2 * i] != (uint32_t)lv[i].w || plane_dims[2 * i + 1] != (uint32_t)lv[i].h) return R3DM_ERR_INVALID;
+    for (size_t k = 0; k < (size_t)B * n_levels; ++k) if (!planes[k]) return R3DM_ERR_INVALID;
+    return R3DM_OK;
+}
+
+// what both entries read back once ac_find_extrema has run: counts_out [B][nl] (from the scanned row offsets: a level's count is the
+// offset of the next level's first row less its own; the last level's ends at the image's total), n_out [B] and cand_out [B][cap]
+// (x, y, level, value bits; image b's candidates from b cap on, in scan order)
+static int ac_dev_read_candidates(r3dm_ctx* c, uint32_t B, int nl, const AcExtrema& ex, uint32_t cap, uint32_t* counts_out, uint32_t* n_out,
+                                  uint32_t* cand_out)
+{
+    hipStream_t st = c->stream;
+    std::vector<uint32_t> hrc((size_t)B * ex.rows_stride);
+    R3DM_HIP(c, hipMemcpyAsync(hrc.data(), ex.rc, hrc.size() * 4, hipMemcpyDeviceToHost, st));
+    for (uint32_t b = 0; b < B; ++b) {
+        if (ex.tot[b] > cap) { c->err = "developer classic head entry: more candidates than the caller's bound"; return R3DM_ERR_INVALID; }
+        if (ex.tot[b]) R3DM_HIP(c, hipMemcpyAsync(cand_out + 4 * (size_t)b * cap, c->ac_bufs[C_CAND].as<AcCand>() + (size_t)b * ex.stride,
+                                                  (size_t)ex.tot[b] * sizeof(AcCand), hipMemcpyDeviceToHost, st));
+    }
+    R3DM_HIP(c, hipStreamSynchronize(st));
+    for (uint32_t b = 0; b < B; ++b) {
+        const uint32_t* r = hrc.data() + (size_t)b * ex.rows_stride;
+        n_out[b] = ex.tot[b];
+        for (int i = 0; i < nl; ++i) counts_out[(size_t)b * nl + i] = (i + 1 < nl ? r[ex.row0[i + 1]] : ex.tot[b]) - r[ex.row0[i]];
+    }
+    return R3DM_OK;
+}
+
+// The classic head on the caller's B same-size images in [0, 1]: the detector's upload, ac_scale_space with a tap, ac_find_extrema.
+//   small_out [B][309]: the bits of the largest gradient modulus, the 300 histogram bins, the bits of 1 / k^2 of octaves 0 .. 7
+//   planes_out [B][n_levels][6]: Lsmooth, Lflow (level 0 has none: left untouched), Lt as the level's FED steps leave it, Lx, Ly, Ldet
+//   (the caller's, w_i x h_i floats each); counts_out, n_out, cand_out: ac_dev_read_candidates, cap candidates per image
+extern "C" int r3dm_dev_akaze_classic_head(r3dm_ctx* c, uint32_t B, const float* const* images, uint32_t width, uint32_t height, float threshold,
+                                           uint32_t* small_out, float* const* planes_out, uint32_t* counts_out, uint32_t cap, uint32_t* n_out,
+                                           uint32_t* cand_out)
+{
+    const int vrc = r3dm_dev_akaze_classic_head_check(B, images, width, height);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_classic_head: images the entry does not take"; return vrc; }
+    if (!c || !small_out || !planes_out || !counts_out || !n_out || !cand_out) return R3DM_ERR_INVALID;
+    const std::vector<AkLevelHost> lv = ac_levels((int)width, (int)height);
+    const int nl = (int)lv.size();
+    for (size_t k = 0; k < (size_t)B * nl * 6; ++k) if (!planes_out[k]) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        int rc = ac_head_bufs(c, B, lv);
+        if (rc != R3DM_OK) return rc;
+        auto buf = [&](int k) -> DevBuf& { return c->ac_bufs[k]; };
+        const size_t n0 = (size_t)width * height;
+        if ((rc = detect_upload(c, B, images, nullptr, n0, buf(C_IMG).as<float>(), buf(C_TMP).as<unsigned char>())) != R3DM_OK) return rc;
+        std::vector<HalfTabs> half_tabs;
+        if ((rc = detect_area_tabs(c, buf(C_TABS), lv, half_tabs)) != R3DM_OK) return rc;
+        const AcTap tap = [&](int i, const float* smooth, const float* flow, const float* lt) -> int {
+            const size_t plane = (size_t)lv[i].w * lv[i].h;
+            for (uint32_t b = 0; b < B; ++b) {
+                float* const* P = planes_out + ((size_t)b * nl + i) * 6;
+                R3DM_HIP(c, hipMemcpyAsync(P[0], smooth + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+                if (flow) R3DM_HIP(c, hipMemcpyAsync(P[1], flow + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+                R3DM_HIP(c, hipMemcpyAsync(P[2], lt + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+            }
+            R3DM_HIP(c, hipStreamSynchronize(st));                                   // (the work buffers are free for the next level)
+            return R3DM_OK;
+        };
+        if ((rc = ac_scale_space(c, B, lv, half_tabs, &tap)) != R3DM_OK) { (void)hipStreamSynchronize(st); return rc; }
+        AcExtrema ex;
+        if ((rc = ac_find_extrema(c, B, lv, threshold, ex)) != R3DM_OK) { (void)hipStreamSynchronize(st); return rc; }
+        for (uint32_t b = 0; b < B; ++b) {
+            for (int i = 0; i < nl; ++i) {
+                const size_t plane = (size_t)lv[i].w * lv[i].h;
+                float* const* P = planes_out + ((size_t)b * nl + i) * 6;
+                for (int q = 0; q < 3; ++q) R3DM_HIP(c, hipMemcpyAsync(P[3 + q], ac_plane(c, i, q) + b * plane, plane * 4, hipMemcpyDeviceToHost, st));
+            }
+            uint32_t* S = small_out + (size_t)b * kAcDevSmallOut;
+            const uint32_t* D = buf(C_SMALL).as<uint32_t>() + (size_t)b * 4096;
+            R3DM_HIP(c, hipMemcpyAsync(S, D, 4, hipMemcpyDeviceToHost, st));
+            R3DM_HIP(c, hipMemcpyAsync(S + 1, D + 16, 300 * 4, hipMemcpyDeviceToHost, st));
+            R3DM_HIP(c, hipMemcpyAsync(S + 301, D + 1024, 8 * 4, hipMemcpyDeviceToHost, st));
+        }
+        return ac_dev_read_candidates(c, B, nl, ex, cap, counts_out, n_out, cand_out);
+    });
+}
+
+// ac_find_extrema on the caller's Ldet planes (planes [B][n_levels], the level table of width x height); the outputs are
+// ac_dev_read_candidates'.
+extern "C" int r3dm_dev_akaze_classic_extrema(r3dm_ctx* c, uint32_t width, uint32_t height, uint32_t B, uint32_t n_levels,
+                                              const uint32_t* plane_dims, const float* const* planes, float threshold, uint32_t* counts_out,
+                                              uint32_t cap, uint32_t* n_out, uint32_t* cand_out)
+{
+    const int vrc = r3dm_dev_akaze_classic_extrema_check(width, height, B, n_levels, plane_dims, planes);
+    if (vrc != R3DM_OK) { if (c) c->err = "r3dm_dev_akaze_classic_extrema: planes the kernels would mis-read"; return vrc; }
+    if (!c || !counts_out || !n_out || !cand_out) return R3DM_ERR_INVALID;
+    return r3dm_guarded(c, [&]() -> int {
+        R3DM_HIP(c, hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        const std::vector<AkLevelHost> lv = ac_levels((int)width, (int)height);
+        const int nl = (int)lv.size();
+        int rc = ac_head_bufs(c, B, lv);
+        if (rc != R3DM_OK) return rc;
+        for (int i = 0; i < nl; ++i) {
+            const size_t plane = (size_t)lv[i].w * lv[i].h;
+            for (uint32_t b = 0; b < B; ++b)
+                R3DM_HIP(c, hipMemcpyAsync(ac_plane(c, i, 2) + b * plane, planes[(size_t)b * nl + i], plane * 4, hipMemcpyHostToDevice, st));
+        }
+        R3DM_HIP(c, hipStreamSynchronize(st));                                       // (the host planes have been read)
+        AcExtrema ex;
+        if ((rc = ac_find_extrema(c, B, lv, threshold, ex)) != R3DM_OK) { (void)hipStreamSynchronize(st); return rc; }
+        return ac_dev_read_candidates(c, B, nl, ex, cap, counts_out, n_out, cand_out);
     });
 }
 #endif  // R3DM_DEVTOOLS

@@ -128,13 +128,10 @@ def fed_tau(T) -> list:
 
 
 # ---------------------------------------------------------------------------------------------------- scale space
-def kcontrast(img: np.ndarray) -> np.float32:
-    """compute_k_percentile(img, 0.7, 1.0, 300, 0, 0) (nldiffusion_functions.cpp:126-199): the INPUT image, sigma 1, Scharr, a
-    FLOAT histogram (a float count stops at 2^24), nbin = floor(nbins * (modg / hmax)), 0.03 if the percentile is not reached"""
-    O = _oracle()
-    lx, ly = O.akaze_scharr(O.akaze_gaussian(img, 1.0))
-    lx, ly = lx[1:-1, 1:-1], ly[1:-1, 1:-1]
-    modg = np.sqrt(lx * lx + ly * ly)
+def modulus_histogram(modg: np.ndarray):
+    """the histogram of compute_k_percentile (nldiffusion_functions.cpp:166-186) over gradient moduli: (hmax, hist [300] float64,
+    the counted points).  A zero modulus is not counted; nbin = floor(nbins * (modg / hmax)) with nbins itself (modg == hmax) folded
+    into the last bin; a FLOAT histogram (a float count stops at 2^24)"""
     hmax = f32(max(f32(0.0), modg.max())) if modg.size else f32(0.0)
     nz = modg[modg != 0.0]
     hist = np.zeros(NBINS, np.float64)
@@ -142,15 +139,29 @@ def kcontrast(img: np.ndarray) -> np.float32:
         nbin = np.floor(f32(NBINS) * (nz / hmax)).astype(np.int64)
         nbin[nbin == NBINS] = NBINS - 1
         hist = np.minimum(np.bincount(nbin, minlength=NBINS).astype(np.float64), 2.0 ** 24)
-    npoints = f32(min(nz.size, 2 ** 24))
+    return hmax, hist, nz.size
+
+
+def kcontrast_parts(img: np.ndarray):
+    """compute_k_percentile(img, 0.7, 1.0, 300, 0, 0) (nldiffusion_functions.cpp:126-199): the INPUT image, sigma 1, Scharr, the
+    histogram above, 0.03 if the percentile is not reached -> (hmax, hist [300] float64, k)"""
+    O = _oracle()
+    lx, ly = O.akaze_scharr(O.akaze_gaussian(img, 1.0))
+    lx, ly = lx[1:-1, 1:-1], ly[1:-1, 1:-1]
+    hmax, hist, n = modulus_histogram(np.sqrt(lx * lx + ly * ly))
+    npoints = f32(min(n, 2 ** 24))
     nthreshold = int(f32(npoints * KPERC))
     nelements, k = 0, 0
     while nelements < nthreshold and k < NBINS:
         nelements = int(f32(f32(nelements) + f32(hist[k])))
         k += 1
     if nelements < nthreshold:
-        return f32(0.03)
-    return f32(hmax * f32(f32(k) / f32(NBINS)))
+        return hmax, hist, f32(0.03)
+    return hmax, hist, f32(hmax * f32(f32(k) / f32(NBINS)))
+
+
+def kcontrast(img: np.ndarray) -> np.float32:
+    return kcontrast_parts(img)[2]
 
 
 def nld_step(L: np.ndarray, c: np.ndarray, stepsize) -> np.ndarray:
@@ -214,7 +225,8 @@ def scaled_deriv(src: np.ndarray, s: int, dx: bool) -> np.ndarray:
 
 def scale_space(img: np.ndarray):
     """Create_Nonlinear_Scale_Space (AKAZE.cpp:102-170) and Compute_Multiscale_Derivatives / Compute_Determinant_Hessian_Response
-    (:188-248): per level a dict with Ldet, Lx, Ly (the scaled derivatives) added to the table entry"""
+    (:188-248): per level a dict with Ldet, Lx, Ly (the scaled derivatives), Lsmooth (what they are taken from), Lflow (the
+    conductivity, None at level 0) and Lt (as the level's FED steps leave it) added to the table entry"""
     O = _oracle()
     img = np.ascontiguousarray(img, np.float32)
     h, w = img.shape
@@ -227,6 +239,7 @@ def _scale_space(O, img, lv):
     k = kcontrast(img)
     Lt = O.akaze_gaussian(img, float(SOFFSET))
     smooth = [Lt]
+    lv[0]["Lt"], lv[0]["Lflow"] = Lt, None                     # (level 0 has no conductivity and no FED step)
     for i in range(1, len(lv)):
         if lv[i]["octave"] > lv[i - 1]["octave"]:
             Lt = O.akaze_halfsample(Lt)
@@ -240,6 +253,7 @@ def _scale_space(O, img, lv):
         for tau in fed_tau(f32(lv[i]["etime"] - lv[i - 1]["etime"])):
             Lt = nld_step(Lt, flow, tau)
         smooth.append(Ls)
+        lv[i]["Lt"], lv[i]["Lflow"] = Lt, flow                  # Lt as the level's FED steps leave it
     for e, Ls in zip(lv, smooth):
         s = e["sigma_size"]
         Lx = scaled_deriv(Ls, s, True)
@@ -248,7 +262,7 @@ def _scale_space(O, img, lv):
         Lyy = scaled_deriv(Ly, s, False)
         Lxy = scaled_deriv(Lx, s, False)
         e["Ldet"] = (Lxx * Lyy - Lxy * Lxy) * f32(s * s * s * s)
-        e["Lx"], e["Ly"] = Lx, Ly
+        e["Lx"], e["Ly"], e["Lsmooth"] = Lx, Ly, Ls
     return lv, k
 
 
