@@ -157,6 +157,11 @@ int r3dm_get_pair_filter_counts(r3dm_ctx* ctx, uint64_t* out);
  * r3dm_get_half_filter_counts: the tiles of the last r3dm_match_pairs call that this level skipped (part of the filter's count). */
 int r3dm_set_half_filter(r3dm_ctx* ctx, int enable);
 int r3dm_get_half_filter_counts(r3dm_ctx* ctx, uint64_t* out);
+/* A tile the f16 level cannot skip goes to the filter -- unless one of its f16 keys lies so far below the filter's threshold that
+ * the filter provably cannot skip the tile either (the f16 rounding loses a bounded amount); then it starts over at once.  No tile
+ * is treated differently by it, only the filter's work on such a tile is saved.  r3dm_get_level2_skip_counts: the tiles of the last
+ * r3dm_match_pairs call that went from the f16 level straight to the restart (0 with the f16 level off). */
+int r3dm_get_level2_skip_counts(r3dm_ctx* ctx, uint64_t* out);
 
 /* Opt-in split-f16 nominator of the L2 matcher for REAL-valued descriptors (default off; no reference counterpart) -- LIOP-144,
  * normalised SIFT: what Regard3D actually matches (src/Regard3DFeatures.h:44-48).  Their matching is always "nominate on
@@ -893,6 +898,7 @@ int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2]);      /
 int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_set_half_filter(r3dm_multi* m, int enable);          /* r3dm_set_half_filter on every context */
 int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
+int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,

@@ -51,6 +51,7 @@ EXPORTS = [
     "r3dm_set_prefix_pruning", "r3dm_get_prefix_pruning_counts", "r3dm_multi_set_prefix_pruning", "r3dm_multi_get_prefix_pruning_counts",
     "r3dm_get_pair_filter_counts", "r3dm_multi_get_pair_filter_counts",
     "r3dm_set_half_filter", "r3dm_get_half_filter_counts", "r3dm_multi_set_half_filter", "r3dm_multi_get_half_filter_counts",
+    "r3dm_get_level2_skip_counts", "r3dm_multi_get_level2_skip_counts",
     "r3dm_detect_akaze_msurf", "r3dm_detect_akaze_msurf_batch",
     "r3dm_vocab_sample", "r3dm_vocab_from_rows", "r3dm_vocab_info", "r3dm_vocab_words", "r3dm_vocab_free", "r3dm_view_signatures", "r3dm_propose_pairs",
     "r3dm_vocab_report",
@@ -449,6 +450,8 @@ def load_library():
     L.r3dm_get_half_filter_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_multi_set_half_filter.argtypes = [vp, C.c_int]
     L.r3dm_multi_get_half_filter_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_get_level2_skip_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_multi_get_level2_skip_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
@@ -1502,6 +1505,13 @@ class Context:
         self._check(self._L.r3dm_get_half_filter_counts(self._h, C.byref(out)), "r3dm_get_half_filter_counts")
         return int(out.value)
 
+    def level2_skip_counts(self):
+        """tiles of the last match_pairs call that went from the f16 level straight to the restart, the filter provably unable to
+        prune them (0 with the f16 level off)"""
+        out = C.c_uint64(0)
+        self._check(self._L.r3dm_get_level2_skip_counts(self._h, C.byref(out)), "r3dm_get_level2_skip_counts")
+        return int(out.value)
+
     def set_mutual_matching(self, enable: bool = True):
         """opt-in mutual nearest-neighbour matching (include/r3dm.h: r3dm_set_mutual_matching): a match (i, j) of match_pairs and the
         approximate matchers is kept iff j is the nearest row of J to row i under (distance, row index); Stats.n_mutual_checked /
@@ -2100,6 +2110,12 @@ class MultiContext:
         """tiles pruned by the f16 level, summed over the contexts' last match calls"""
         out = C.c_uint64(0)
         self._check(self._L.r3dm_multi_get_half_filter_counts(self._h, C.byref(out)), "r3dm_multi_get_half_filter_counts")
+        return int(out.value)
+
+    def level2_skip_counts(self):
+        """tiles that went from the f16 level straight to the restart, summed over the contexts' last match calls"""
+        out = C.c_uint64(0)
+        self._check(self._L.r3dm_multi_get_level2_skip_counts(self._h, C.byref(out)), "r3dm_multi_get_level2_skip_counts")
         return int(out.value)
 
     def set_mutual_matching(self, enable: bool = True):

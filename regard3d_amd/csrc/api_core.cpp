@@ -788,6 +788,13 @@ extern "C" int r3dm_get_half_filter_counts(r3dm_ctx* c, uint64_t* out)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_get_level2_skip_counts(r3dm_ctx* c, uint64_t* out)
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    *out = c->level2_skip_count;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_set_split_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;

@@ -239,10 +239,11 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     R3DM_HIP(c, hipMemcpyAsync(c->d_pairs.p, hp.data(), sizeof(uint2) * P, hipMemcpyHostToDevice, c->stream));
     R3DM_HIP(c, c->d_nn.ensure((size_t)P * q_stride * 4));
     const uint64_t total_slots = (uint64_t)P * q_stride;
-    // per-pair lists of uncertified queries: [fb_total(2 words) | pad][fb_cnt: P][fb_q: P x kFbPerPair]
-    const size_t fb_words = 16 + (size_t)P + (size_t)P * kFbPerPair;
+    // per-pair lists of uncertified queries: [fb_total(2 words) | pad | the pruning kernels' words][fb_cnt: P][fb_q: P x kFbPerPair]
+    constexpr size_t kFbHeader = 24;                       // words: fb_total [0, 2), pad, MatchParams::prune_cnt's seven slots [4, 18), pad
+    const size_t fb_words = kFbHeader + (size_t)P + (size_t)P * kFbPerPair;
     R3DM_HIP(c, c->d_fb.ensure(fb_words * 4));
-    R3DM_HIP(c, hipMemsetAsync(c->d_fb.p, 0, (16 + (size_t)P) * 4, c->stream));
+    R3DM_HIP(c, hipMemsetAsync(c->d_fb.p, 0, (kFbHeader + (size_t)P) * 4, c->stream));
     R3DM_HIP(c, c->d_cnt.ensure(64));
     R3DM_HIP(c, hipMemsetAsync(c->d_cnt.p, 0, 64, c->stream));
     if (knn_idx_host) {
@@ -264,9 +265,9 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     mp.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
     mp.knn_dist = knn_idx_host ? c->d_knn_dist.as<float>() : nullptr;
     mp.fb_total = c->d_fb.as<uint32_t>();
-    mp.fb_cnt = c->d_fb.as<uint32_t>() + 16;
-    mp.fb_q = c->d_fb.as<uint32_t>() + 16 + P;
-    // (words 4 .. 11 of the zeroed header: the three 64-bit counters of the pruning kernel and its pair-norm table's address)
+    mp.fb_cnt = c->d_fb.as<uint32_t>() + kFbHeader;
+    mp.fb_q = c->d_fb.as<uint32_t>() + kFbHeader + P;
+    // (words 4 .. 17 of the zeroed header: the 64-bit counters of the pruning kernels and their tables' addresses)
     const bool halves = prunes && c->half_filter;          // the f16 level in front of the filter (r3dm_set_half_filter)
     mp.prune = c->prefix_pruning ? (halves ? 3u : 1u) : 0u;
     mp.prune_cnt = reinterpret_cast<unsigned long long*>(c->d_fb.as<uint32_t>() + 4);
@@ -337,12 +338,13 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
         }
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
         uint32_t fbt[2] = {0, 0};
-        R3DM_HIP(c, c->pin_small.ensure(64));
-        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 56, hipMemcpyDeviceToHost, c->stream));
+        R3DM_HIP(c, c->pin_small.ensure(72));
+        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 72, hipMemcpyDeviceToHost, c->stream));
         R3DM_HIP(c, hipStreamSynchronize(c->stream));
         memcpy(fbt, c->pin_small.p, 8);
         { uint64_t pc[3]; memcpy(pc, (const unsigned char*)c->pin_small.p + 16, 24); for (int k = 0; k < 3; ++k) c->prune_counts[k] += pc[k]; }
         { uint64_t hc; memcpy(&hc, (const unsigned char*)c->pin_small.p + 48, 8); c->half_count += hc; }      // (prune_cnt[4]; [3] is the table's address)
+        { uint64_t sc; memcpy(&sc, (const unsigned char*)c->pin_small.p + 64, 8); c->level2_skip_count += sc; }      // (prune_cnt[6]; [5] is the f16 table's address)
         n_fallback = fbt[0];
         if (fbt[0] > 0) {
             bool rescan = fbt[1] > 0;                      // some pair overflowed its list
@@ -402,7 +404,7 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
     c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;
-    c->half_count = 0;
+    c->half_count = 0; c->level2_skip_count = 0;
     const double t_call = now_ms();
     std::vector<PairJob> jobs, none;
     const int rcp = resolve_pairs(c, pairs_ij, n_pairs, nullptr, none, jobs);
@@ -454,7 +456,7 @@ static int r3dm_knn2_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, 
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;      // ArrayMatcherBruteForce: NN > nbRows / nbQuery < 1
     if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
     R3DM_HIP(c, hipSetDevice(c->device));
-    c->half_count = 0;
+    c->half_count = 0; c->level2_skip_count = 0;
     c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;            // (a raw 2-NN never prunes: the counters of this call read 0 / 0)
     PrivateSlots s(c, 2);
     int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);

@@ -239,6 +239,14 @@ extern "C" int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out)
+{
+    if (!m || !out) return R3DM_ERR_INVALID;
+    *out = 0;
+    for (r3dm_ctx* c : m->ctx) *out += c->level2_skip_count;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
 {
     if (!m) return R3DM_ERR_INVALID;

@@ -842,10 +842,35 @@ static hipError_t launch_l2_cascade_t(hipStream_t st, const MatchParams& Pin, ui
 //   0.72 of one more slackF (552 u M): tools/prefix_prune_model.py --filter half shows what it costs (0.15 % of c2's tiles).
 // Values outside f16's range cost level 1's work and nothing else: a pair norm above 65,504 is +inf, its keys -inf or NaN, both
 // object and the tile goes to level 2; non-zero values below 2^-14 are held at 2^-14 (the bound gets looser, never wrong).
-// MODE (developer ablations): 0 the three levels | 1 level 1, then straight to the restart (timing only: other tiles are pruned).
+// THE SKIP OF LEVEL 2.  Level 2 leaves a tile alone as soon as ONE lane holds one key kf_c <= thrF, and most tiles that object at
+// level 1 hold an f16 key far below the threshold: the f32 pair norms cannot lift it above.  With a bound L on what they can lift,
+//     kf_c <= kh_c + L   (same row, same query),   so   kh_c <= thrF - L  =>  kf_c <= thrF  =>  level 2 would not prune,
+// and the tile goes from level 1 straight to the restart: the decision is the one level 2 would have taken, its 64 f32 MFMAs and 24 KiB
+// are saved.  L on the STORED operands, M = max|a|^2 + |q|^2 as above, eps = 2^-10, dlt = 2^-14:
+//   the rounding loss   kf - kh = 2 sum_k (ha_k hb_k - sa_k sb_k).  pairnorm_to_half gives h = 0 iff s = 0 and, for every finite h,
+//           h <= (1 + eps) s + dlt (the round-up of a normal; the floor at 2^-14).  A pair with sa_k sb_k = 0 has ha_k hb_k = 0; else
+//           ha hb - sa sb <= ((1 + eps)^2 - 1) sa sb + dlt (1 + eps) (sa + sb) + dlt^2.  Over the 64 pairs, twice:
+//             ((1 + eps)^2 - 1) 2 sum sa sb  <=  (2^-9 + 2^-20) (1 + 2^-16) M:   2 sum sa sb <= sum sa^2 + sum sb^2, s <= (1 + 2^-22) |(x, y)|
+//                 (stage_pairnorm_kernel) and a stored norm is at least (1 - 128 u) of its row's, so sum sa^2 + sum sb^2 <= (1 + 2^-16) M
+//             2 dlt (1 + eps) sum (sa + sb)  <=  2^-13 (1 + 2^-16) M + 2^-8 (1 + eps)^2:   2 d x <= e x^2 + d^2 / e for each of the 128
+//                 values x, with e = 2^-13, d = dlt (1 + eps): 128 d^2 / e = 2^-8 (1 + eps)^2
+//             128 dlt^2 = 2^-21
+//   the evaluation errors, in the direction opposite to the margin's: kf_c <= kf + eF, kh_c >= kh - eH, the same counts:
+//           130 + 257 = 387 u M + 128 u 2^-19
+//   = (2^-9 + 2^-13 + 2^-20 + 2^-24 + 387 u) M + 2^-8 + 2^-16.  The kernel takes L = (2^-9 + 2^-13 + 2^-15) M + 2^-8 + 2^-15
+//   (kSkipLossFactor, kSkipLossAbs): 2^-15 = 512 u leaves 100 u M for the three roundings of L itself, and thrS = thrF - L rounded DOWN by
+//   2^-22 of it, which pays that difference's rounding.  The form is lane-constant, refreshed beside thrH; tools/prefix_prune_model.py
+//   --filter half compares it with the key-dependent form from 2 sum ha hb = N - kh (profiles/level2_skip_model_c2.txt).
+// A key that is -inf or NaN comes from an f16 pair norm of +inf (or a NaN), whose loss no L bounds: only a key above -inf counts (a NaN
+// fails both compares).  thrS is -inf for a dead lane and while thrF = +inf; a NaN thrS (M = +inf) skips nothing.  A tile may still run
+// level 2 when it need not; the skip never fires where level 2 would prune.
+// MODE (developer ablations): 0 the three levels, level 2 skipped where it cannot prune | 1 level 1, then straight to the restart
+// (timing only: other tiles are pruned) | 2 the three levels without the skip.
 // ------------------------------------------------------------------------------------------------
 constexpr float kHalfMarginFactor = 400.0f * 5.9604644775390625e-08f;       // 400 x 2^-24
 constexpr float kHalfMarginAbs = 2.9103830456733704e-11f;                   // 2^-35
+constexpr float kSkipLossFactor = 0.001953125f + 0.0001220703125f + 3.0517578125e-05f;      // 2^-9 + 2^-13 + 2^-15
+constexpr float kSkipLossAbs = 0.00390625f + 3.0517578125e-05f;                               // 2^-8 + 2^-15
 
 template <int G, int GP, int NJ, int PF, int WPS, int MODE>
 __global__ __launch_bounds__(256, WPS)
@@ -903,7 +928,7 @@ void l2_knn2_half_kernel(const MatchParams P)
     const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
     const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
     const float maxnormI = __uint_as_float(Ip->max_norm_bits);
-    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF, float& mgn) __attribute__((always_inline)) -> bool {
+    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF, float& mgn, float& loss) __attribute__((always_inline)) -> bool {
         uint32_t q = (qt0 + (uint32_t)nj) * 32u + c;
         asm volatile("" : "+v"(q));
         const bool dead = !(q < nJ);                    // (covers a query tile beyond the last one too: its rows lie beyond nJ)
@@ -916,12 +941,13 @@ void l2_knn2_half_kernel(const MatchParams P)
         off = slk - nbp;
         offF = slkF - nb;
         mgn = kHalfMarginFactor * (maxnormI + nb) + kHalfMarginAbs;
+        loss = kSkipLossFactor * (maxnormI + nb) + kSkipLossAbs;
         return dead;
     };
-    float thr[NJ], thrF[NJ], thrH[NJ], Tl[NJ], plT[NJ];
+    float thr[NJ], thrF[NJ], thrH[NJ], thrS[NJ], Tl[NJ], plT[NJ];
 #pragma unroll
-    for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; thrH[nj] = R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned)
-    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0, n_half = 0;      // wave-uniform
+    for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; thrH[nj] = R3DM_INF; thrS[nj] = -R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned, and never skips level 2)
+    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0, n_half = 0, n_skip = 0;      // wave-uniform
     bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
 
     if (nI >= 2) {
@@ -941,15 +967,15 @@ void l2_knn2_half_kernel(const MatchParams P)
         const uint32_t voffA = lane * 16u, voffN = h * 16u;
         const uint32_t tileB = (uint32_t)G * 1024u, tileRB = (uint32_t)GR * 1024u, tileHB = (uint32_t)GH * 1024u;      // bytes per tile, reduced tile, f16 tile
         const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
-        const uint32_t hb = 4u * h;
+        uint32_t hb = 4u * h;
         // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes).  T, thr and thrF are the
         // cascade's floats; thrH >= thrF + margin (the header comment)
         auto refresh = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int nj = 0; nj < NJ; ++nj) {
                 if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
-                float nbs, off, offF, mgn;
-                const bool dead = lane_terms(nj, nbs, off, offF, mgn);
+                float nbs, off, offF, mgn, loss;
+                const bool dead = lane_terms(nj, nbs, off, offF, mgn, loss);
                 const float e0 = st[nj].d0 + nbs, e1 = st[nj].d1 + nbs;
                 const float re1 = R * e1;
                 float T = e0 < re1 ? __builtin_fmaxf(re1, e0 * invR) : re1;
@@ -960,6 +986,8 @@ void l2_knn2_half_kernel(const MatchParams P)
                 thrF[nj] = dead ? -R3DM_INF : xF + __builtin_fabsf(xF) * 2.384185791015625e-07f;
                 const float xH = thrF[nj] + mgn;
                 thrH[nj] = dead ? -R3DM_INF : xH + __builtin_fabsf(xH) * 2.384185791015625e-07f;   // 2^-22: the rounding of xH
+                const float xS = thrF[nj] - loss;
+                thrS[nj] = (dead || !(thrF[nj] < R3DM_INF)) ? -R3DM_INF : xS - __builtin_fabsf(xS) * 2.384185791015625e-07f;      // rounded down
             }
         };
         // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
@@ -975,7 +1003,23 @@ void l2_knn2_half_kernel(const MatchParams P)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrH[nj]);
             if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; n_half += 1u; pruned_under_thr = true; return false; }
+            auto restart = [&]() __attribute__((always_inline)) -> bool {
+                const bool on = l2_prune_tile_restart<G, GP, NJ, true>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
+                if (!on) { n_pruned += 1u; pruned_under_thr = true; }
+                return on;
+            };
+            // level 2 cannot prune a tile that holds a finite f16 key at or below thrS (the header comment): such a tile skips it.  Only
+            // the tiles that object get here, so the second pass over the keys is off level 1's path.  The skip has a copy of the restart
+            // to itself: with one copy entered from both sides the register allocator spills 70 registers, with two it spills none
             if constexpr (MODE == 0) {
+                bool far = false;
+#pragma unroll
+                for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) far |= (cur[nj][r] <= thrS[nj]) && (cur[nj][r] > -R3DM_INF);
+                if (__builtin_amdgcn_ballot_w64(far) != 0ull) { n_skip += 1u; return restart(); }
+            }
+            if constexpr (MODE != 1) {
                 l2_pairnorm_tile_stream<GR, NJ>(rr, rn, voffA, voffN, t * tileRB, t * 128u, rqr, soffQR, cur);
                 obj = false;
 #pragma unroll
@@ -984,9 +1028,7 @@ void l2_knn2_half_kernel(const MatchParams P)
                     for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrF[nj]);
                 if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true; return false; }
             }
-            const bool on = l2_prune_tile_restart<G, GP, NJ, true>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
-            if (!on) { n_pruned += 1u; pruned_under_thr = true; }
-            return on;
+            return restart();
         };
         bool live = false;
         uint32_t t = 0;
@@ -994,6 +1036,8 @@ void l2_knn2_half_kernel(const MatchParams P)
             live = tile(t, accA, accB, live);
             live = tile(t + 1, accB, accA, live);
         }
+        // (the lane's half once more, from the lane counter: nothing of it has to live through the loop, whose registers are all taken)
+        hb = 4u * (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 5);
         if (t < ntI) {
             if (tile(t, accA, accB, live)) {
 #pragma unroll
@@ -1010,20 +1054,22 @@ void l2_knn2_half_kernel(const MatchParams P)
     }
 
     // plT -> the lower bound of the pruned rows' distances (a lane whose query does not exist holds none)
+    const uint32_t lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), he = lane_e >> 5, ce = lane_e & 31u;      // (= lane, h, c: as above)
     float pruned_lb[NJ];
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) {
         if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
-        const bool dead = !((qt0 + (uint32_t)nj) * 32u + c < nJ);
+        const bool dead = !((qt0 + (uint32_t)nj) * 32u + ce < nJ);
         pruned_lb[nj] = dead ? -R3DM_INF : plT[nj];
     }
-    if (lane == 0 && n_tested) {
+    if (lane_e == 0 && n_tested) {
         atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
         if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
         if (n_filtered) atomicAdd(P.prune_cnt + 2, (unsigned long long)n_filtered);
         if (n_half) atomicAdd(P.prune_cnt + 4, (unsigned long long)n_half);
+        if (n_skip) atomicAdd(P.prune_cnt + 6, (unsigned long long)n_skip);
     }
-    l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
+    l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, he, ce, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
 }
 
 template <int G, int GP, int NJ, int PF, int WPS, int MODE>
@@ -1107,12 +1153,13 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
             default: break;
         }
         //   130: the f16 level, then straight to the restart (no f32 filter; timing only) | 131 / 132: the three levels with a
-        //   window of 1 / 2 blocks instead of 4
+        //   window of 1 / 2 blocks instead of 4 | 133: the three levels without the skip of level 2 (results and older counters unchanged)
         if ((P.prune & 2u) != 0) {
             switch (variant) {
                 case 130: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 1>(st, P, max_nj_tiles);
                 case 131: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 1, 2, 0>(st, P, max_nj_tiles);
                 case 132: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 0>(st, P, max_nj_tiles);
+                case 133: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 2>(st, P, max_nj_tiles);
                 default: break;
             }
         }

@@ -571,6 +571,7 @@ struct r3dm_ctx {
     bool prefix_pruning = true;                             // r3dm_set_prefix_pruning: match mode on 128-dimensional rows stops tiles early
     bool half_filter = true;                                // r3dm_set_half_filter: the f16 level in front of the pair-norm filter
     uint64_t half_count = 0;                                // r3dm_get_half_filter_counts: wave tiles the f16 level pruned in the last match call (part of prune_counts[2])
+    uint64_t level2_skip_count = 0;                         // r3dm_get_level2_skip_counts: wave tiles the f16 level sent straight to the restart in the last match call (no f32 filter)
     uint64_t prune_counts[3] = {0, 0, 0};                   // r3dm_get_prefix_pruning_counts: wave tiles tested / pruned in the last match call; [2] r3dm_get_pair_filter_counts: pruned by the filter
     bool split_mfma = false;                                // r3dm_set_split_mfma
     bool hamming_mfma = false;                              // r3dm_set_hamming_mfma

@@ -241,7 +241,8 @@ struct MatchParams {
     // of `imgs`: [n_tiles][G / 2][2][32][4] f32 in the fragment order of `tiled`, half its bytes (scratch of the call: run_match_batch),
     // written by the host when the launch may prune; [4]: wave tiles pruned by the f16 level (l2_knn2_half_kernel; part of [2]);
     // [5]: the bits of a `const uint16_t* const*`, the f16 pair-norm tiles per slot: [n_tiles][G / 4][2][32][8] f16, written by the host
-    // when prune bit 1 is set.  Behind this pointer and no field of ImgDev or of this struct: their sizes and
+    // when prune bit 1 is set; [6]: wave tiles the f16 level sent straight to the restart, the filter unable to prune them (part of
+    // neither count above: these tiles go on).  Behind this pointer and no field of ImgDev or of this struct: their sizes and
     // offsets are what every other kernel's machine code and kernel arguments were compiled with.
     unsigned long long* prune_cnt;
 };

@@ -245,12 +245,36 @@ def halfnorm_bound(a, b):
         return na[:, None] + nb[None, :] - 2.0 * dot, HALF_MARGIN * (na.max(initial=0.0) + nb) + HALF_MARGIN_ABS
 
 
-def model_pair_levels(a, b, gp, R, half=True):
+SKIP_LOSS = 2.0 ** -9 + 2.0 ** -13 + 2.0 ** -15       # kSkipLossFactor (kernels_match.hip, above l2_knn2_half_kernel)
+SKIP_LOSS_ABS = 2.0 ** -8 + 2.0 ** -15                # kSkipLossAbs
+
+
+def skip_loss(a, b, LBH, form="lane"):
+    """L with kf_c <= kh_c + L (the derivation above l2_knn2_half_kernel), in float64, broadcastable against LBH [nI, nJ]:
+    "lane": the kernel's, (2^-9 + 2^-13 + 2^-15) (max|a|^2 + |b|^2) + 2^-8 + 2^-15 -- [1, nJ];
+    "key":  the key-dependent form: 2 sum sa sb <= 2 sum ha hb = |a|^2 + |b|^2 - LBH carries the factor (1 + 2^-10)^2 - 1 instead of
+            M; the cross terms of the floor and the evaluation errors stay on M -- [nI, nJ]"""
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    na, nb = (a64 * a64).sum(1), (b64 * b64).sum(1)
+    M = (na.max(initial=0.0) + nb)[None, :]
+    if form == "lane":
+        return SKIP_LOSS * M + SKIP_LOSS_ABS
+    with np.errstate(invalid="ignore"):
+        dot2 = na[:, None] + nb[None, :] - LBH                        # 2 sum ha hb
+        return (2.0 ** -9 + 2.0 ** -20) * dot2 + (2.0 ** -13 + 2.0 ** -15) * M + SKIP_LOSS_ABS
+
+
+def model_pair_levels(a, b, gp, R, half=True, skip=None):
     """the three levels of l2_knn2_half_kernel: per wave tile the f16 level (thrH = thrF + margin), behind it the pair-norm filter,
     behind that the tile run again with the prefix test -- model_pair_cascade with one more level in front (half=False: without it,
     the cascade itself), and with the outcome PER TILE.
     -> model_pair_cascade's dict + half (tiles level 1 pruned), cycles (matrix cycles), and [n_tiles, n_waves] bool arrays
-    tile_half / tile_filtered / tile_pruned, verdict [nJ] (-1 none, -2 exact scan, else the row)"""
+    tile_half / tile_filtered / tile_pruned, verdict [nJ] (-1 none, -2 exact scan, else the row).
+    skip = "lane" / "key" (skip_loss's forms; None: the kernel before the skip): a tile that objects at level 1 and holds a finite f16
+    key at or below thrS = thrF - L goes straight to the restart.  No older output depends on it but `cycles`; it adds skipped (such
+    tiles), unsound (those of them the pair-norm filter would have pruned: must be 0), tile_skip [n_tiles, n_waves] and gap: the
+    smallest distance of any finite key of level 1 or 2 from the threshold it is compared with (thrH, thrF, thrS) -- where that is well
+    above the float32 roundings, the kernel decides every tile as this model does."""
     R64 = float(np.float32(R))
     nI, nJ = a.shape[0], b.shape[0]
     a64, b64 = a.astype(np.float64), b.astype(np.float64)
@@ -261,6 +285,7 @@ def model_pair_levels(a, b, gp, R, half=True):
         DP = (ap * ap).sum(1)[:, None] - 2.0 * ap @ bp.T + (bp * bp).sum(1)[None, :]
         LB, slackF = pairnorm_bound(a, b)
         LBH, margin = halfnorm_bound(a, b)
+        loss = skip_loss(a, b, LBH, skip) if (skip and half) else None
     slackP = np.zeros(nJ) if _exact_pair(a, b) else slackF
     n_tiles = (nI + 31) // 32
     n_waves = (nJ + 63) // 64
@@ -269,7 +294,8 @@ def model_pair_levels(a, b, gp, R, half=True):
     i0 = np.full((2, nJ), -1, np.int64); i1 = np.full((2, nJ), -1, np.int64)
     pl = np.full((2, nJ), np.inf)
     wave_of_q = np.arange(nJ) // 64
-    tiles = pruned = filtered = halved = work = cycles = 0
+    tiles = pruned = filtered = halved = work = cycles = skipped = unsound = 0
+    tile_skip = np.zeros((n_tiles, n_waves), bool); gap = np.inf
     tile_half = np.zeros((n_tiles, n_waves), bool); tile_filtered = np.zeros((n_tiles, n_waves), bool); tile_pruned = np.zeros((n_tiles, n_waves), bool)
     for t in range(n_tiles):
         lo, hi = t * 32, min(nI, t * 32 + 32)
@@ -279,7 +305,7 @@ def model_pair_levels(a, b, gp, R, half=True):
             re1 = R64 * e1
             T = np.where(e0 < re1, np.maximum(re1, e0 / R64), re1)
             T = T + np.abs(T) * 2.0 ** -21
-        objH = np.zeros((2, nJ), bool); objF = np.zeros((2, nJ), bool); objP = np.zeros((2, nJ), bool)
+        objH = np.zeros((2, nJ), bool); objF = np.zeros((2, nJ), bool); objP = np.zeros((2, nJ), bool); far = np.zeros((2, nJ), bool)
         with np.errstate(invalid="ignore"):
             for h in (0, 1):
                 m = half_of_row[: hi - lo] == h
@@ -288,13 +314,24 @@ def model_pair_levels(a, b, gp, R, half=True):
                     objH[h] = ~(LBH[rows[m]] - (slackF + margin)[None, :] > T[h][None, :]).all(0)
                     objF[h] = ~(LB[rows[m]] - slackF[None, :] > T[h][None, :]).all(0)
                     objP[h] = ~(DP[rows[m]] - slackP[None, :] > T[h][None, :]).all(0)
-        wH = np.zeros(n_waves, bool); wF = np.zeros(n_waves, bool); wP = np.zeros(n_waves, bool)
+                    if loss is not None:
+                        # kh_c <= thrS and kh_c > -inf (false for a NaN key); thrS = -inf while the threshold is +inf
+                        Lm = loss[rows[m]] if loss.shape[0] > 1 else loss
+                        far[h] = ((LBH[rows[m]] - slackF[None, :] + Lm <= T[h][None, :]) & (LBH[rows[m]] > -INF) & (T[h][None, :] < INF)).any(0)
+                        for keys in (LBH[rows[m]] - (slackF + margin)[None, :], LB[rows[m]] - slackF[None, :], LBH[rows[m]] - slackF[None, :] + Lm):
+                            g = np.abs(keys - T[h][None, :])
+                            gap = min(gap, float(g[np.isfinite(g)].min(initial=np.inf)))
+        wH = np.zeros(n_waves, bool); wF = np.zeros(n_waves, bool); wP = np.zeros(n_waves, bool); wS = np.zeros(n_waves, bool)
+        np.logical_or.at(wS, wave_of_q, far[0] | far[1])
         np.logical_or.at(wH, wave_of_q, objH[0] | objH[1])
         np.logical_or.at(wF, wave_of_q, objF[0] | objF[1])
         np.logical_or.at(wP, wave_of_q, objP[0] | objP[1])
         if not half:
             wH[:] = True
         wave_on = wH & wF & wP
+        wS &= wH                                                       # (only a tile that objects at level 1 gets as far as the skip)
+        tile_skip[t] = wS
+        skipped += int(wS.sum()); unsound += int((wS & ~wF).sum())
         tile_half[t] = ~wH; tile_filtered[t] = ~(wH & wF); tile_pruned[t] = ~wave_on
         tiles += n_waves
         halved += int((~wH).sum())
@@ -302,7 +339,7 @@ def model_pair_levels(a, b, gp, R, half=True):
         pruned += int((~wave_on).sum())
         n2, n3p, n3 = int(wH.sum()), int((wH & wF & ~wP).sum()), int(wave_on.sum())
         work += 8 * n2 + gp * n3p + 16 * n3
-        cycles += (CYC_HALF * n_waves if half else 0) + CYC_GROUP * (8 * n2 + gp * n3p + 16 * n3)
+        cycles += (CYC_HALF * n_waves if half else 0) + CYC_GROUP * (8 * (n2 - int(wS.sum())) + gp * n3p + 16 * n3)
         go = wave_on[wave_of_q]
         pl[:, ~go] = np.minimum(pl[:, ~go], T[:, ~go])
         if go.any():
@@ -330,27 +367,40 @@ def model_pair_levels(a, b, gp, R, half=True):
     decided = verdict != -2
     return {"tiles": tiles, "pruned": pruned, "filtered": filtered, "half": halved, "work": work, "cycles": cycles,
             "fallback": int((~decided).sum()), "wrong": int((decided & (verdict != truth)).sum()), "matches": int((truth >= 0).sum()),
-            "queries": nJ, "tile_half": tile_half, "tile_filtered": tile_filtered, "tile_pruned": tile_pruned, "verdict": verdict}
+            "queries": nJ, "skipped": skipped, "unsound": unsound, "tile_skip": tile_skip, "gap": gap, "tile_half": tile_half, "tile_filtered": tile_filtered, "tile_pruned": tile_pruned, "verdict": verdict}
 
 
-def run_levels(views, pairs, gp, ratio, squared=True, out=print):
+def run_levels(views, pairs, gp, ratio, squared=True, out=print, skip=None):
     """model_pair_levels with and without the f16 level on every pair: the shares per level, the matrix cycles of both, and whether
-    any tile or verdict differs between them (it must not)"""
+    any tile or verdict differs between them (it must not).  skip = "lane" / "key": with the skip of level 2 in that form of L (a
+    second line per pair: the share of level 1's objecting tiles that skip, the cycles with it, the unsound skips -- must be 0)"""
     R = ratio * ratio if squared else ratio
-    keys = ("tiles", "pruned", "filtered", "half", "cycles", "fallback", "wrong", "matches", "queries")
-    acc = dict.fromkeys(keys, 0); acc["cycles_cascade"] = 0; acc["differs"] = 0
+    keys = ("tiles", "pruned", "filtered", "half", "cycles", "fallback", "wrong", "matches", "queries", "skipped", "unsound")
+    acc = dict.fromkeys(keys, 0); acc["cycles_cascade"] = 0; acc["differs"] = 0; acc["cycles_skip"] = 0
+    sline = lambda r: (f"level 2 skipped on {r['skipped']} of {r['tiles'] - r['half']} objecting tiles ({r['skipped'] / max(r['tiles'] - r['half'], 1):.4f}; "
+                       f"level 2 still runs on {(r['tiles'] - r['half'] - r['skipped']) / r['tiles']:.4f} of all, prunes {(r['filtered'] - r['half']) / r['tiles']:.4f})  "
+                       f"matrix cycles a tile {r['cycles_skip'] / r['tiles']:.0f} (without the skip {r['cycles'] / r['tiles']:.0f})  "
+                       f"tiles where the skip fired and the f32 filter would have pruned {r['unsound']}")
     line = lambda r: (f"level 1 {r['half'] / r['tiles']:.4f}  filter behind it {(r['filtered'] - r['half']) / r['tiles']:.4f}  "
                       f"prefix behind that {(r['pruned'] - r['filtered']) / r['tiles']:.4f}  "
                       f"matrix cycles a tile {r['cycles'] / r['tiles']:.0f} (cascade {r['cycles_cascade'] / r['tiles']:.0f}, brute force {16 * CYC_GROUP})")
     for (i, j) in pairs:
         r = model_pair_levels(views[i], views[j], gp, R)
         r0 = model_pair_levels(views[i], views[j], gp, R, half=False)
-        r["cycles_cascade"] = r0["cycles"]
+        r["cycles_cascade"] = r0["cycles"]; r["cycles_skip"] = r["cycles"]
+        if skip:
+            rs = model_pair_levels(views[i], views[j], gp, R, skip=skip)
+            assert all(np.array_equal(rs[k], r[k]) for k in ("pruned", "filtered", "half", "tile_half", "tile_filtered", "tile_pruned", "verdict"))
+            r["cycles_skip"] = rs["cycles"]; r["skipped"] = rs["skipped"]; r["unsound"] = rs["unsound"]
         r["differs"] = int((r["tile_filtered"] != r0["tile_filtered"]).sum() + (r["tile_pruned"] != r0["tile_pruned"]).sum() + (r["verdict"] != r0["verdict"]).sum())
         for k in acc:
             acc[k] += r[k]
         out(f"half + pairnorm + GP {gp:2d}  pair ({i},{j})  {line(r)}  matches {r['matches']:5d}  exact scan {r['fallback']:4d}  "
             f"wrong verdicts {r['wrong']}  tiles or verdicts unlike the cascade's {r['differs']}")
+        if skip:
+            out(f"skip of level 2 ({skip})  pair ({i},{j})  {sline(r)}")
+    if skip:
+        out(f"skip of level 2 ({skip})  ALL {len(pairs)} pairs, R = {R:.4f}: {sline(acc)}")
     out(f"half + pairnorm + GP {gp:2d}  ALL {len(pairs)} pairs, {acc['queries']} queries, R = {R:.4f}: {line(acc)}  "
         f"exact scan {acc['fallback']} ({acc['fallback'] / max(acc['queries'], 1):.2e})  wrong verdicts {acc['wrong']}  "
         f"tiles or verdicts unlike the cascade's {acc['differs']}")
@@ -402,6 +452,8 @@ def main():
     ap.add_argument("--pairs", type=int, default=0, help="pairs (0, 1 .. n); default: every other view")
     ap.add_argument("--filter", choices=["none", "pairnorm", "half"], default="none",
                     help="pairnorm: the cascade, the pair-norm filter in front of GP = --gp[-1]; half: the f16 level in front of the cascade")
+    ap.add_argument("--skip", choices=["none", "lane", "key"], default="none",
+                    help="with --filter half: the skip of level 2 with L lane-constant (the kernel's) or key-dependent")
     ap.add_argument("--summary", action="store_true", help="with --filter pairnorm: only the ALL line")
     a = ap.parse_args()
     from regard3d_amd import synth
@@ -411,8 +463,9 @@ def main():
     bad = 0
     for ratio in a.ratio:
         if a.filter == "half":
-            acc = run_levels(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print)
-            bad += acc["wrong"] + acc["differs"]
+            acc = run_levels(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print,
+                             skip=None if a.skip == "none" else a.skip)
+            bad += acc["wrong"] + acc["differs"] + acc["unsound"]
             continue
         if a.filter == "pairnorm":
             bad += run_cascade(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print)["wrong"]
