@@ -107,6 +107,14 @@ def candidates(kind, M, xyI, xyJ, errTh):
     return out
 
 
+def candidate_count(kind: str, M, thr_px: float, xyI, xyJ, KI=None, KJ=None) -> int:
+    """the number of (i, j) of one pair with err < errTh, as candidates() decides them: what r3dm_guided_report's n_candidates sums
+    over the pairs of a call, in either mode.  kind, M, thr_px, KI / KJ as guided_pair takes them."""
+    Fm = f_from_e(M, KI, KJ) if kind == "E" else np.ascontiguousarray(M, np.float64).reshape(9)
+    errTh = float(thr_px) * float(thr_px)
+    return sum(len(js) for js, _ in candidates("H" if kind == "H" else "F", Fm, xyI, xyJ, errTh))
+
+
 def descriptor_distance(a: np.ndarray, b: np.ndarray, binary: bool):
     """SquaredDescriptorDistance: the oracle's squared L2 (f32 / u8 rows) or Hamming distance (binary rows)"""
     L = _lib()

@@ -37,6 +37,12 @@ def _restated(kind, sc, pairs, models, thrs, ratio, descs, binary):
     return out_p, out_o, (np.concatenate(out_m) if out_m else np.zeros((0, 2), np.uint32))
 
 
+def _candidate_count(kind, sc, pairs, models, thrs):
+    """what r3dm_guided_report's n_candidates must be: every (i, j) with err < errTh of every pair, in either mode"""
+    return sum(G.candidate_count(kind, M, t, sc.xys[I], sc.xys[J], synth.intrinsics(), synth.intrinsics())
+               for (I, J), M, t in zip(np.asarray(pairs).tolist(), models, thrs))
+
+
 def _accepted(ctx, g, kind):
     """the accepted pairs of one filter, their models and thresholds (r3dm_pair_report of the putative pairs)"""
     f = {"F": ctx.filter_F, "H": ctx.filter_H, "E": ctx.filter_E}[kind]
@@ -63,21 +69,24 @@ def test_guided_match_equals_the_restatement(ctx, desc):
         gf, M, thr = _accepted(ctx, g, kind_f)
         if gf.num_pairs == 0:
             continue
+        n_cand = _candidate_count(kind_f, sc, gf.pairs, M, thr)
         for ratio in ((0.8 if binary else 0.6), -1.0):
             got = ctx.guided_match(gf, kind_f, M, thr, ratio)
             _graph_equal(got, *_restated(kind_f, sc, gf.pairs, M, thr, ratio, descs, binary))
             rep = ctx.guided_report()
             assert rep["n_pairs"] == gf.num_pairs and rep["n_queries"] == sum(sc.xys[int(I)].shape[0] for I, _ in gf.pairs)
-            assert rep["n_candidates"] >= rep["n_matches"] and rep["ms_kernels"] > 0
+            assert rep["n_candidates"] == n_cand and rep["n_matches"] == got.num_matches and rep["ms_kernels"] > 0
             checked += 1
     assert checked >= 4
     # a homography chosen by the caller (a translation by the mean displacement, 8 px), both modes: the primitive takes any model
     d = np.array([np.mean(sc.xys[int(J)][m[:, 1]] - sc.xys[int(I)][m[:, 0]], axis=0) for (I, J), m in g.as_dict().items()])
     Hs = np.array([[1, 0, dx, 0, 1, dy, 0, 0, 1] for dx, dy in d], np.float64)
     thr = np.full(g.num_pairs, 8.0)
+    n_cand = _candidate_count("H", sc, g.pairs, Hs, thr)
     for ratio in ((0.8 if binary else 0.6), -1.0):
         got = ctx.guided_match(g.pairs, "H", Hs, thr, ratio)
         _graph_equal(got, *_restated("H", sc, g.pairs, Hs, thr, ratio, descs, binary))
+        assert ctx.guided_report()["n_candidates"] == n_cand
 
 
 def test_full_size_pair_and_tiled_J(ctx):
@@ -88,9 +97,11 @@ def test_full_size_pair_and_tiled_J(ctx):
         g = ctx.match_pairs(sc.exhaustive_pairs(), 0.6, True)
         gf, M, thr = _accepted(ctx, g, "F")
         assert gf.num_pairs == 1
+        n_cand = _candidate_count("F", sc, gf.pairs, M, thr)
         for ratio in (0.6, -1.0):
             got = ctx.guided_match(gf, "F", M, thr, ratio)
             _graph_equal(got, *_restated("F", sc, gf.pairs, M, thr, ratio, sc.descs, False))
+            assert ctx.guided_report()["n_candidates"] == n_cand
         assert got.num_matches > 0
 
 
