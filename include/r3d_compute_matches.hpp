@@ -121,6 +121,10 @@ public:
     // every device context, so the putative lists -- and with them the F / E / H lists -- hold a row of I at most once per pair.  Off by
     // default: the match files are the reference's only while it is off.
     void setMutualMatching(bool on);
+    // no reference counterpart either: forwards r3dm_set_symmetric_ratio to every device context -- a putative match stays only if the
+    // 2-NN + ratio rule with the two views swapped accepts it too (nearest in both directions, ratio test in both directions).  It
+    // contains the mutual rule; the two switches are independent.  Off by default.
+    void setSymmetricRatio(bool on);
     // no reference counterpart (the reference matches exhaustivePairs): forwards r3dm_set_preemptive_matching to every
     // device context, so a pair is matched only if the small match of its views' head_rows largest-scale features finds min_matches
     // correspondences -- dropped pairs lose real matches.  The scale column of every view's .feat file is registered as its priority
@@ -302,11 +306,12 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_DESCRIPTOR_MSURF 1024u /* setRegionsType(R3DM_F32, 64): the features stage writes M-SURF-64 rows (r3dm_set_descriptor_arm); together with R3DM_STAGE_DESCRIPTOR_MLDB: R3DM_ERR_INVALID */
 #define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
 #define R3DM_STAGE_PAIR_PROPOSAL 2048u /* the matcher gets the pairs r3dm_propose_pairs proposes, not all pairs (R3DComputeMatches::setPairProposal(true)): 16,384 words, lowered to half the collection's rows when it is smaller, top_k 20 -- untuned defaults */
+#define R3DM_STAGE_SYMMETRIC_RATIO 4096u /* symmetric ratio test (R3DComputeMatches::setSymmetricRatio(true), r3dm_set_symmetric_ratio): a match must also pass the 2-NN + ratio rule with the views swapped; default off */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
-/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_F32_TILES */
+/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_SYMMETRIC_RATIO, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_F32_TILES */
 int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                                    r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
                                    uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);

@@ -192,13 +192,45 @@ int r3dm_set_hamming_mfma(r3dm_ctx* ctx, int enable);
  * one over all rows of J, so the result is a deterministic subset of what the arm returns without it.  It runs after the ratio test
  * and BEFORE the (i_, j_) ordering and both de-duplications: a match that fails it is gone before the coordinate de-duplication looks at
  * its neighbours.  Consequences: a row of I appears at most once per pair; a view J with one row is always mutual; of two identical
- * rows of J the lower index survives.  There is no reverse ratio test.
+ * rows of J the lower index survives.  The reverse ratio test is a switch of its own: r3dm_set_symmetric_ratio, below.
  * Honoured by r3dm_match_pairs, r3dm_match_pairs_kgraph / _hnsw / _mrpt, their r3dm_multi_* forms and the stage (R3DComputeMatches::
  * setMutualMatching, R3DM_STAGE_MUTUAL_MATCHING).  IGNORED by the entries that return raw neighbour lists -- r3dm_knn2, r3dm_knn, the
  * r3dm_index_* family, the *_knn2 / *_knn entries of the approximate matchers -- and by guided matching, which replaces lists after
  * the filters.  Cost: one more read of view J per pair that has accepted matches (kernels_match_mutual.hip); while the switch is off
  * nothing is allocated or launched for it.  r3dm_stats.n_mutual_checked / n_mutual_dropped report the last call. */
 int r3dm_set_mutual_matching(r3dm_ctx* ctx, int enable);
+
+/* Opt-in symmetric ratio test ("mutual + ratio", SMNN; default off; no reference counterpart -- SURVEY.md App. A.3 / App. C).  Let
+ * (i, j) be a match a matcher would return: j's nearest row of I is i and the forward ratio test accepted it.  With the switch on,
+ * (i, j) is kept iff the same 2-NN + ratio rule, applied with the two views swapped, accepts it:
+ *   1. Nearest.  j is the nearest row of J to row i under the order (distance, row index) -- the rule of r3dm_set_mutual_matching,
+ *      with the same distance d (the reference's f32 sum for F32 / U8 rows, the popcount distance for BIN rows).
+ *   2. Reverse ratio.  Let d1 = d(i, j) and d2 = the smallest d(i, j') over all rows j' != j of J; which row gives d2 does not matter,
+ *      and a duplicate of row j in J gives d2 = d1.  The match stays iff f(d1) < R * f(d2), evaluated in f32 with one multiply, a
+ *      strict < and no FMA, where R and f are those of the forward test that accepted it: R = dist_ratio * dist_ratio (the f32
+ *      product) and f the identity where the call compares squared distances (squared_metric != 0; the KGraph and HNSW matchers; the
+ *      pairs an approximate matcher scans exhaustively); R = dist_ratio and f the identity otherwise, Hamming distances converted to
+ *      float; R = dist_ratio and f = sqrtf for the pairs the MRPT matcher answers through its index, whose forward test runs on
+ *      square roots.
+ *   3. Fewer than two rows.  A view J with fewer than two rows has no second neighbour: the matcher with the views swapped returns
+ *      nothing (SearchNeighbours fails for NN > rows), so NO match of such a pair survives.  This differs from the mutual rule on
+ *      purpose, under which a view J with one row is always mutual.
+ * Non-finite distances follow from the comparisons: a NaN is never less than anything, so it never becomes a minimum -- a row of I
+ * whose distances are all NaN has no nearest row and its match is dropped as not nearest; a comparison with a NaN on either side of
+ * the ratio test fails.
+ * The two switches are independent: this one alone still applies part 1, and both together give what this one alone gives.  The check
+ * runs where the mutual check runs -- after the forward ratio test, before the (i_, j_) ordering and both de-duplications -- on the
+ * same exhaustive scan of J (kernels_match_mutual.hip keeps the second minimum of it), so the result is a deterministic subset of the
+ * mutual result.  Honoured and ignored by the same entries as r3dm_set_mutual_matching (stage: R3DComputeMatches::setSymmetricRatio,
+ * R3DM_STAGE_SYMMETRIC_RATIO); also ignored by the head match of preemptive matching and the quantisation of pair proposal.  While the
+ * switch is off nothing is allocated or launched for it.  r3dm_stats.n_mutual_checked / n_mutual_dropped keep their meaning
+ * (candidates looked at / dropped because not nearest: what the mutual switch alone would report); the matches the reverse ratio
+ * alone removed are read through r3dm_symmetric_ratio_report. */
+int r3dm_set_symmetric_ratio(r3dm_ctx* ctx, int enable);
+/* The symmetric ratio test's counters of the last call that collected matches (r3dm_match_pairs and the three approximate matchers):
+ * candidates checked, dropped because not nearest, dropped by the reverse ratio (every candidate of a pair whose view J has fewer than
+ * two rows counts here).  Any pointer may be null.  All three are 0 after a call with the switch off. */
+int r3dm_symmetric_ratio_report(const r3dm_ctx* ctx, uint64_t* checked, uint64_t* dropped_not_nearest, uint64_t* dropped_ratio);
 
 /* Opt-in preemptive matching (default off; no reference counterpart -- the reference matches exhaustivePairs, SURVEY.md section 5, and
  * parity with it depends on that default): match only the largest-scale features of each view first, and run the full match of a pair
@@ -892,6 +924,7 @@ int r3dm_multi_set_intrinsics(r3dm_multi* m, uint32_t view_id, const double* K);
 int r3dm_multi_clear_images(r3dm_multi* m);
 int r3dm_multi_set_integer_mfma(r3dm_multi* m, int enable);
 int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable);      /* r3dm_set_mutual_matching on every context */
+int r3dm_multi_set_symmetric_ratio(r3dm_multi* m, int enable);      /* r3dm_set_symmetric_ratio on every context (r3dm_symmetric_ratio_report: per context, through r3dm_multi_ctx) */
 int r3dm_multi_set_kgraph_hamming(r3dm_multi* m, int enable);       /* r3dm_set_kgraph_hamming on every context */
 int r3dm_multi_set_prefix_pruning(r3dm_multi* m, int enable);       /* r3dm_set_prefix_pruning on every context */
 int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[2]);      /* summed over the contexts' last calls */

@@ -42,6 +42,7 @@ EXPORTS = [
     "r3dm_guided_match", "r3dm_set_guided_matching", "r3dm_guided_report", "r3dm_multi_set_guided_matching",
     "r3dm_set_keypoint_detector", "r3dm_multi_set_keypoint_detector", "r3dm_akaze_classic_components",
     "r3dm_set_mutual_matching", "r3dm_multi_set_mutual_matching", "r3dm_compute_matches_dir_flags",
+    "r3dm_set_symmetric_ratio", "r3dm_multi_set_symmetric_ratio", "r3dm_symmetric_ratio_report",
     "r3dm_set_kgraph_hamming", "r3dm_multi_set_kgraph_hamming", "r3dm_kgraph_hamming_report", "r3dm_kgraph_knn2_bits", "r3dm_kgraph_knn_bits",
     "r3dm_set_view_priority", "r3dm_preselect_pairs", "r3dm_set_preemptive_matching", "r3dm_preselect_report",
     "r3dm_multi_set_view_priority", "r3dm_multi_set_preemptive_matching",
@@ -63,6 +64,7 @@ STAGE_MUTUAL_MATCHING = 128
 STAGE_PREEMPTIVE_MATCHING = 256
 STAGE_DESCRIPTOR_MLDB = 512
 STAGE_DESCRIPTOR_MSURF = 1024
+STAGE_SYMMETRIC_RATIO = 4096                      # R3DM_STAGE_SYMMETRIC_RATIO: r3dm_set_symmetric_ratio on every context of the stage
 STAGE_PAIR_PROPOSAL = 2048                        # R3DM_STAGE_PAIR_PROPOSAL: 16,384 words (half the collection's rows when that is less), top_k 20
 VOCAB_MAX_WORDS, VOCAB_HIST_LDS_WORDS, VOCAB_WORD_CHUNK = 65536, 8192, 32      # R3DM_VOCAB_* (include/r3dm.h)
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
@@ -256,12 +258,13 @@ class Stage:
     def run(self, matches_dir: str, views, threshold: float = 0.001, dist_ratio: float = 0.6, matching_algorithm: int = 9, compute_F: bool = True,
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False) -> StageReport:
+            guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False,
+            symmetric_ratio: bool = False) -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
         (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING); preemptive: preemptive matching at 128 / 4
         (R3DM_STAGE_PREEMPTIVE_MATCHING); descriptor: "LIOP", "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB: binary regions, 61 bytes) or "MSURF"
         (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64, 64 floats); proposal: the matcher gets the pairs r3dm_propose_pairs proposes
-        (R3DM_STAGE_PAIR_PROPOSAL)"""
+        (R3DM_STAGE_PAIR_PROPOSAL); symmetric_ratio: the symmetric ratio test (R3DM_STAGE_SYMMETRIC_RATIO)"""
         dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
         keep = []
         arr = _stage_views(views, keep)
@@ -269,7 +272,7 @@ class Stage:
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                     (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | dflag, C.byref(rep), err, 1024)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | dflag, C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -290,7 +293,8 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           matching_algorithm: int = 9, compute_F: bool = True, compute_E: bool = True, compute_H: bool = True,
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
-                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False) -> StageReport:
+                          guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False,
+            symmetric_ratio: bool = False) -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
@@ -299,7 +303,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     the features stage writes MLDB-486 rows, the matcher runs its binary rules) or "MSURF" (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64
     rows of 64 floats, matched by the float rules as LIOP is); proposal: R3DM_STAGE_PAIR_PROPOSAL (the matcher gets the pairs
     r3dm_propose_pairs proposes from a vocabulary sampled from the stage's views: 16,384 words, half the collection's rows when that is
-    less, top_k 20)."""
+    less, top_k 20); symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO (a match must also pass the 2-NN + ratio rule with the views swapped)."""
     dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
     L = load_library()
     keep = []
@@ -310,7 +314,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                       (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | dflag, C.byref(rep), err, 1024)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | dflag, C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
@@ -323,11 +327,11 @@ class _DirView(C.Structure):
 
 def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0, dim: int = 144, dist_ratio: float = 0.6,
                         compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False, preemptive: bool = False,
-                        proposal: bool = False):
+                        proposal: bool = False, symmetric_ratio: bool = False):
     """R3DComputeMatches::computeMatches over a directory that holds every view's .feat / .desc (r3dm_compute_matches_dir_flags):
     exhaustive matching, the F filter when asked, matches.putative.txt / matches.f.txt.  views: dicts with id, width, height,
     basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive: R3DM_STAGE_PREEMPTIVE_MATCHING (the .feat scale column is
-    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL.  -> (putative pairs, geometric pairs)"""
+    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL; symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO.  -> (putative pairs, geometric pairs)"""
     L = load_library()
     arr = (_DirView * len(views))(*[_DirView(int(v["id"]), int(v["width"]), int(v["height"]), str(v["basename"]).encode()) for v in views])
     npp, ngp = C.c_uint64(0), C.c_uint64(0)
@@ -336,7 +340,7 @@ def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0,
                                                  C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     rc = L.r3dm_compute_matches_dir_flags(device_id, matches_dir.encode(), arr, len(views), dtype, dim, dist_ratio, int(compute_F), seed,
                                           (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0)
-                                          | (STAGE_PAIR_PROPOSAL if proposal else 0),
+                                          | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0),
                                           C.byref(npp), C.byref(ngp), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_dir_flags -> {rc}: {err.value.decode()}")
@@ -457,6 +461,9 @@ def load_library():
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_mutual_matching.argtypes = [vp, C.c_int]
     L.r3dm_multi_set_mutual_matching.argtypes = [vp, C.c_int]
+    L.r3dm_set_symmetric_ratio.argtypes = [vp, C.c_int]
+    L.r3dm_multi_set_symmetric_ratio.argtypes = [vp, C.c_int]
+    L.r3dm_symmetric_ratio_report.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
     L.r3dm_set_kgraph_hamming.argtypes = [vp, C.c_int]
     L.r3dm_multi_set_kgraph_hamming.argtypes = [vp, C.c_int]
     L.r3dm_kgraph_hamming_report.argtypes = [vp, vp]
@@ -1518,6 +1525,20 @@ class Context:
         n_mutual_dropped report the last call.  knn2 / knn / the index entries return raw lists and ignore it"""
         self._check(self._L.r3dm_set_mutual_matching(self._h, int(bool(enable))), "r3dm_set_mutual_matching")
 
+    def set_symmetric_ratio(self, enable: bool = True):
+        """opt-in symmetric ratio test (include/r3dm.h: r3dm_set_symmetric_ratio): a match (i, j) of match_pairs and the approximate
+        matchers is kept iff the 2-NN + ratio rule with the views swapped accepts it too -- j is the nearest row of J to row i AND
+        f(d1) < R f(d2) with the forward test's R and f, d2 the smallest distance from row i to another row of J; no match survives
+        a view J of fewer than two rows.  Contains the mutual rule; independent of set_mutual_matching.  Raw-list entries ignore it"""
+        self._check(self._L.r3dm_set_symmetric_ratio(self._h, int(bool(enable))), "r3dm_set_symmetric_ratio")
+
+    def symmetric_ratio_report(self):
+        """r3dm_symmetric_ratio_report of the last collecting call -> (checked, dropped_not_nearest, dropped_ratio); zeros after a call
+        with the switch off"""
+        a, b, c = C.c_uint64(0), C.c_uint64(0), C.c_uint64(0)
+        self._check(self._L.r3dm_symmetric_ratio_report(self._h, C.byref(a), C.byref(b), C.byref(c)), "r3dm_symmetric_ratio_report")
+        return int(a.value), int(b.value), int(c.value)
+
     def set_view_priority(self, view_id: int, priority):
         """r3dm_set_view_priority: one float per row of the view (its feature scale: finite, >= 0), or None to remove it"""
         p = None if priority is None else np.ascontiguousarray(priority, np.float32).reshape(-1)
@@ -2121,6 +2142,10 @@ class MultiContext:
     def set_mutual_matching(self, enable: bool = True):
         """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""
         self._check(self._L.r3dm_multi_set_mutual_matching(self._h, int(bool(enable))), "r3dm_multi_set_mutual_matching")
+
+    def set_symmetric_ratio(self, enable: bool = True):
+        """r3dm_multi_set_symmetric_ratio: Context.set_symmetric_ratio on every context"""
+        self._check(self._L.r3dm_multi_set_symmetric_ratio(self._h, int(bool(enable))), "r3dm_multi_set_symmetric_ratio")
 
     def set_kgraph_hamming(self, enable: bool = True):
         """r3dm_multi_set_kgraph_hamming: Context.set_kgraph_hamming on every context"""

@@ -80,6 +80,7 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
     const float gate_ratio_R = scanned_ratio_R;       // the three arms scan with ratio^2 on squared distances: the gate's R as well
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
+    c->symratio_counts[0] = c->symratio_counts[1] = c->symratio_counts[2] = 0;
     const double t_call = now_ms();
     std::vector<PairJob> indexed, scanned;
     int rc = resolve_pairs(c, pairs_ij, n_pairs, arm.classify, indexed, scanned);
@@ -120,7 +121,7 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
 // one search batch: sizes, pair table, common buffers, event bracket, comparison count, finalisation, common statistics
 // ------------------------------------------------------------------------------------------------
 int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host,
-                  const std::function<int(const AnnBatch&)>& launch, uint32_t knn_cols)
+                  const std::function<int(const AnnBatch&)>& launch, uint32_t knn_cols, ForwardRatio forward)
 {
     AnnBatch b{};
     b.P = (uint32_t)jobs.size();
@@ -164,7 +165,7 @@ int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, 
     R3DM_HIP(c, hipMemcpyAsync(&comps, b.n_comps, 8, hipMemcpyDeviceToHost, c->stream));
     R3DM_HIP(c, hipStreamSynchronize(c->stream));              // (the pair table and the arm's job records are host temporaries)
     const double t_post = now_ms();
-    rc = finalize_batch(c, jobs, b.q_stride, sort_cap, n_queries, b.max_nJ, g, knn_idx_host, knn_dist_host, knn_cols);
+    rc = finalize_batch(c, jobs, b.q_stride, sort_cap, n_queries, b.max_nJ, g, knn_idx_host, knn_dist_host, knn_cols, forward);
     if (rc != R3DM_OK) return rc;
     c->stats.ms_wall_match_post += now_ms() - t_post;
     float ms = 0.f;
@@ -448,7 +449,7 @@ static int run_kgraph_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float
         if (e == hipErrorInvalidValue) { c->err = "graph search: unsupported descriptor length / view size / parameters"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, e);
         return R3DM_OK;
-    }, knn_k ? knn_k : 2u);
+    }, knn_k ? knn_k : 2u, ForwardRatio{ratio_R, false});
     if (rc != R3DM_OK || jobs.empty()) return rc;
     c->stats.n_ann_rows16 += (rows16 && !rows8) ? 1 : 0;
     c->stats.n_ann_rows8 += rows8 ? 1 : 0;

@@ -830,6 +830,22 @@ extern "C" int r3dm_set_mutual_matching(r3dm_ctx* c, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_set_symmetric_ratio(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->symmetric_ratio = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_symmetric_ratio_report(const r3dm_ctx* c, uint64_t* checked, uint64_t* dropped_not_nearest, uint64_t* dropped_ratio)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    if (checked) *checked = c->symratio_counts[0];
+    if (dropped_not_nearest) *dropped_not_nearest = c->symratio_counts[1];
+    if (dropped_ratio) *dropped_ratio = c->symratio_counts[2];
+    return R3DM_OK;
+}
+
 // ------------------------------------------------------------------------------------------------
 // graph accessors, merge, files
 // ------------------------------------------------------------------------------------------------

@@ -192,7 +192,7 @@ static int run_hnsw_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float r
             c->stats.n_hnsw_retries += 1;
         }
         return R3DM_OK;
-    }, knn_k ? knn_k : 2u);
+    }, knn_k ? knn_k : 2u, ForwardRatio{ratio_R, false});
     if (rc == R3DM_OK && !jobs.empty()) c->stats.n_ann_rows8 += rows8 ? 1 : 0;
     return rc;
 }

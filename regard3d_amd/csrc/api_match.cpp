@@ -12,15 +12,19 @@
 // before the (i, j) ordering and both de-duplications.  Whatever arm nominated the matches, the check is the exhaustive one in the
 // reference's arithmetic: over J's f32 tiles where the length has a tensor kernel and no scalar tail, over the row-major rows
 // otherwise, over the word rows of binary views.  Adds the batch's two counters to the statistics.
-static int run_mutual_check(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride)
+// r3dm_set_symmetric_ratio: the same scan keeps the second minimum and repeats the batch's forward ratio test (`forward`) in reverse --
+// the mutual rule is part of that rule, so the check runs when either switch is on; the third counter goes to
+// r3dm_symmetric_ratio_report.
+static int run_mutual_check(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, ForwardRatio forward)
 {
     const uint32_t P = (uint32_t)jobs.size();
     const HostImage& first = *c->imgs[jobs[0].sI];
-    R3DM_HIP(c, c->d_mutual.ensure(16));
-    R3DM_HIP(c, hipMemsetAsync(c->d_mutual.p, 0, 16, c->stream));
+    R3DM_HIP(c, c->d_mutual.ensure(24));
+    R3DM_HIP(c, hipMemsetAsync(c->d_mutual.p, 0, 24, c->stream));
     MutualParams mp{};
     mp.imgs = c->d_imgs.as<ImgDev>(); mp.pairs = c->d_pairs.as<uint2>(); mp.n_pairs = P; mp.q_stride = q_stride;
     mp.nn_idx = c->d_nn.as<uint32_t>(); mp.counters = c->d_mutual.as<unsigned long long>();
+    mp.ratio_R = forward.R; mp.ratio_form = !c->symmetric_ratio ? 0u : (forward.on_roots ? 2u : 1u);
     // (a chunk of the MRPT arm may hold views of several lengths: the rows-based kernel reads each pair's own)
     const bool one_length = std::all_of(jobs.begin(), jobs.end(), [&](const PairJob& j) { return c->imgs[j.sI]->dim == first.dim; });
     if (first.dtype == R3DM_BIN) R3DM_HIP(c, launch_hamming_mutual(c->stream, mp, first.words));
@@ -34,22 +38,25 @@ static int run_mutual_check(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint3
         { const int rcl = ensure_layouts(c, slots, kLayRows); if (rcl != R3DM_OK) return rcl; }
         R3DM_HIP(c, launch_l2_mutual_items(c->stream, mp, (uint32_t)total_slots));
     }
-    unsigned long long counts[2] = {0, 0};
-    R3DM_HIP(c, hipMemcpyAsync(counts, mp.counters, 16, hipMemcpyDeviceToHost, c->stream));
+    unsigned long long counts[3] = {0, 0, 0};
+    R3DM_HIP(c, hipMemcpyAsync(counts, mp.counters, 24, hipMemcpyDeviceToHost, c->stream));
     R3DM_HIP(c, hipStreamSynchronize(c->stream));
     c->stats.n_mutual_checked += counts[0];
     c->stats.n_mutual_dropped += counts[1];
+    if (c->symmetric_ratio) for (int k = 0; k < 3; ++k) c->symratio_counts[k] += counts[k];
     return R3DM_OK;
 }
 
 // compaction + ordering + de-duplication of nn_idx[pair][*] (finalize_pairs_kernel), copy back, append the non-empty
 // pairs to `g` in job order.  Shared by the exhaustive and the graph-search drivers.  Calls that collect into a graph run the mutual
-// check first while its switch is on; the raw-list entries (g == nullptr: r3dm_knn2 and its relatives) never do.
+// check first while its switch or the symmetric ratio test's is on; the raw-list entries (g == nullptr: r3dm_knn2 and its relatives)
+// never do.
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
-                          uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols)
+                          uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols,
+                          ForwardRatio forward)
 {
     const uint32_t P = (uint32_t)jobs.size();
-    if (c->mutual_matching && g && P) { const int rcm = run_mutual_check(c, jobs, q_stride); if (rcm != R3DM_OK) return rcm; }
+    if ((c->mutual_matching || c->symmetric_ratio) && g && P) { const int rcm = run_mutual_check(c, jobs, q_stride, forward); if (rcm != R3DM_OK) return rcm; }
     // ---- finalisation: compact + order + de-duplicate, per pair
     R3DM_HIP(c, c->d_pair_off.ensure((size_t)P * 8));
     R3DM_HIP(c, c->d_pair_cnt.ensure((size_t)P * 4));
@@ -379,7 +386,7 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     }
 
     const double t_post = now_ms();            // (the stream is idle here only on the tensor path; good enough for a breakdown)
-    int rcf = finalize_batch(c, jobs, q_stride, sort_cap, n_queries, max_nJ, g, knn_idx_host, knn_dist_host);
+    int rcf = finalize_batch(c, jobs, q_stride, sort_cap, n_queries, max_nJ, g, knn_idx_host, knn_dist_host, 2, ForwardRatio{ratio_R, false});
     if (rcf != R3DM_OK) return rcf;
     c->stats.ms_wall_match_post += now_ms() - t_post;
     if (r3dm_dev_knob("R3DM_MATCH_TIMING", 0))
@@ -403,6 +410,7 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     *out = nullptr;
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
+    c->symratio_counts[0] = c->symratio_counts[1] = c->symratio_counts[2] = 0;
     c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;
     c->half_count = 0; c->level2_skip_count = 0;
     const double t_call = now_ms();

@@ -189,7 +189,7 @@ static int run_mrpt_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float r
         if (e == hipErrorInvalidValue) { c->err = "MRPT query: vote bytes + elected list of the largest index view of the batch exceed the 160 KB of LDS a wavefront can have"; return R3DM_ERR_UNSUPPORTED; }
         R3DM_HIP(c, e);
         return R3DM_OK;
-    }, knn_k ? knn_k : 2u);
+    }, knn_k ? knn_k : 2u, ForwardRatio{ratio, true});      // (the forward test above runs on square roots: so does its reverse)
 }
 
 static int r3dm_match_pairs_mrpt_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, float dist_ratio,

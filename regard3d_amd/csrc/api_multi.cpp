@@ -254,6 +254,13 @@ extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_symmetric_ratio(r3dm_multi* m, int enable)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) r3dm_set_symmetric_ratio(c, enable);
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_kgraph_hamming(r3dm_multi* m, int enable)
 {
     if (!m) return R3DM_ERR_INVALID;

@@ -164,6 +164,7 @@ struct Devices {
     void set_split_mfma(bool on) const { on_each(r3dm_set_split_mfma, on ? 1 : 0); }
     void set_hamming_mfma(bool on) const { on_each(r3dm_set_hamming_mfma, on ? 1 : 0); }
     void set_mutual(bool on) const { (void)call(r3dm_set_mutual_matching, r3dm_multi_set_mutual_matching, on ? 1 : 0); }
+    void set_symmetric_ratio(bool on) const { (void)call(r3dm_set_symmetric_ratio, r3dm_multi_set_symmetric_ratio, on ? 1 : 0); }
     int set_kgraph_hamming(bool on) const { return call(r3dm_set_kgraph_hamming, r3dm_multi_set_kgraph_hamming, on ? 1 : 0); }
     void set_guided(bool on, double rF, double rE, double rH) const { (void)call(r3dm_set_guided_matching, r3dm_multi_set_guided_matching, on ? 1 : 0, rF, rE, rH); }
     int set_preemptive(bool on, uint32_t head_rows, uint32_t min_matches) const
@@ -410,6 +411,7 @@ void R3DComputeMatches::setIntegerFastPath(bool on) { Devices{ctx_, multi_}.set_
 void R3DComputeMatches::setSplitFastPath(bool on) { Devices{ctx_, multi_}.set_split_mfma(on); }
 void R3DComputeMatches::setHammingFastPath(bool on) { Devices{ctx_, multi_}.set_hamming_mfma(on); }
 void R3DComputeMatches::setMutualMatching(bool on) { Devices{ctx_, multi_}.set_mutual(on); }
+void R3DComputeMatches::setSymmetricRatio(bool on) { Devices{ctx_, multi_}.set_symmetric_ratio(on); }
 
 // TracksBuilder::Build(map_Matches) + Filter(min_length) + ExportToSTL (and, with `kept`, the filter applied to the map itself): the
 // map becomes a graph (r3dm_graph_from_csr: map order is graph order), r3dm_build_tracks runs on the first device
@@ -775,6 +777,7 @@ static void apply_stage_flags(r3d_amd::R3DComputeMatches& stage, uint32_t flags,
     if (mask & R3DM_STAGE_F32_TILES) stage.setExactFastPaths(!has(R3DM_STAGE_F32_TILES));      // (R3DM_STAGE_SPLIT_MFMA / _INTEGER_MFMA: implied since round 3)
     if (mask & R3DM_STAGE_GUIDED_MATCHING) stage.setGuidedMatching(has(R3DM_STAGE_GUIDED_MATCHING));
     if (mask & R3DM_STAGE_MUTUAL_MATCHING) stage.setMutualMatching(has(R3DM_STAGE_MUTUAL_MATCHING));
+    if (mask & R3DM_STAGE_SYMMETRIC_RATIO) stage.setSymmetricRatio(has(R3DM_STAGE_SYMMETRIC_RATIO));
     if (mask & R3DM_STAGE_PREEMPTIVE_MATCHING) stage.setPreemptiveMatching(has(R3DM_STAGE_PREEMPTIVE_MATCHING));
     if (mask & R3DM_STAGE_PAIR_PROPOSAL) stage.setPairProposal(has(R3DM_STAGE_PAIR_PROPOSAL));
 }
@@ -873,7 +876,7 @@ extern "C" int r3dm_compute_matches_dir_flags(int device_id, const char* matches
     stage.addViews(vs);
     stage.setRegionsType(dtype, dim);
     stage.setSeed(seed);
-    apply_stage_flags(stage, flags, R3DM_STAGE_F32_TILES | R3DM_STAGE_MUTUAL_MATCHING | R3DM_STAGE_PREEMPTIVE_MATCHING | R3DM_STAGE_PAIR_PROPOSAL);
+    apply_stage_flags(stage, flags, R3DM_STAGE_F32_TILES | R3DM_STAGE_MUTUAL_MATCHING | R3DM_STAGE_SYMMETRIC_RATIO | R3DM_STAGE_PREEMPTIVE_MATCHING | R3DM_STAGE_PAIR_PROPOSAL);
     r3d_amd::R3DFParams params;
     params.distRatio_ = dist_ratio;
     params.computeFundalmentalMatrix_ = compute_F != 0;

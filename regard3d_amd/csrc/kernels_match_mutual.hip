@@ -14,17 +14,34 @@
 //                               l2_exact_batch_kernel streams I's (row reads are wave-uniform -> LDS broadcast)
 //   l2_mutual_items_kernel      any other length: one workgroup per accepted match over the row-major rows
 //   hamming_mutual_kernel<W>    binary rows of 8 / 16 words: the batch kernel's shape over the word rows, packed integer keys
+//
+// The symmetric ratio test (r3dm_set_symmetric_ratio; MutualParams::ratio_form != 0) is the same scan keeping TWO minima: a match stays
+// iff j is nearest AND f(d1) < R f(d2), d2 = the smallest distance from row i to a row of J other than j -- the forward 2-NN + ratio
+// rule with the views swapped.  It has kernels of its own (l2_symratio_batch_kernel<G>, l2_symratio_items_kernel,
+// hamming_symratio_kernel<W>) over the same frame, so the mutual-only kernels stay as they were.
 #include "kernels_match_common.hpp"
 
 namespace r3dm {
 
 // ------------------------------------------------------------------------------------------------
-// the frame of the two one-workgroup-per-pair kernels: gather the accepted (i, j) of the pair in query order into `cand`
+// the frame of the one-workgroup-per-pair kernels: gather the accepted (i, j) of the pair in query order into `cand`
 // (i << 32 | j), 256 per round; best_row(i, j, active) -> the row of J nearest to row i (it is called by ALL 256 threads and may
 // synchronise the workgroup); a candidate whose nearest row is not j loses its entry of nn_idx.
 // `cand` holds 512 keys: a round starts with fewer than 256 left over and gathers at most 256 more.
+// RATIO (the symmetric ratio test): best_row returns a Nearest2 -- the row, its distance d1 and the smallest distance d2 to any OTHER
+// row of J.  A candidate that is nearest stays only if reverse_ratio_passes, and never when J has fewer than two rows (no second
+// neighbour: the matcher with the views swapped returns nothing).  A third counter holds what the ratio alone removed.
 // ------------------------------------------------------------------------------------------------
-template <class BestRow>
+struct Nearest2 { uint32_t row; float d1, d2; };
+
+// the reverse ratio test, the forward test of the arm that accepted the match operation for operation: one f32 multiply, a strict <,
+// no FMA (-ffp-contract=off).  ratio_form 2 is the MRPT arm's, whose forward test runs on the square roots it returns.
+__device__ __forceinline__ bool reverse_ratio_passes(const MutualParams& P, float d1, float d2)
+{
+    return P.ratio_form == 2u ? sqrtf(d1) < P.ratio_R * sqrtf(d2) : d1 < P.ratio_R * d2;
+}
+
+template <bool RATIO, class BestRow>
 __device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32_t pair, uint32_t nJ, unsigned long long* cand,
                                                    uint32_t* wave_cnt, BestRow&& best_row)
 {
@@ -32,6 +49,7 @@ __device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32
     uint32_t* nn = P.nn_idx + (size_t)pair * P.q_stride;
     uint32_t held = 0, qpos = 0;                     // block-uniform: keys in cand, first query not gathered yet
     uint32_t checked = 0, dropped = 0;               // per wave, kept by its lane 0
+    uint32_t dropped_ratio = 0;                      // (RATIO) ... nearest, and removed by the reverse ratio test
     for (;;) {
         while (held < 256u && qpos < nJ) {
             const uint32_t q = qpos + threadIdx.x;
@@ -48,11 +66,16 @@ __device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32
         const bool active = threadIdx.x < cnt;
         const unsigned long long key = cand[active ? threadIdx.x : 0u];
         const uint32_t i = (uint32_t)(key >> 32), j = (uint32_t)key;
-        const uint32_t bj = best_row(i, j, active);
+        const auto best = best_row(i, j, active);
+        uint32_t bj;
+        if constexpr (RATIO) bj = best.row; else bj = best;
         const bool drop = active && bj != j;
-        if (drop) nn[j] = kNone;                     // (j < qpos: the gather never reads this entry again)
+        bool drop_ratio = false;
+        if constexpr (RATIO) drop_ratio = active && !drop && !(nJ >= 2u && reverse_ratio_passes(P, best.d1, best.d2));
+        if (drop || drop_ratio) nn[j] = kNone;       // (j < qpos: the gather never reads this entry again)
         const unsigned long long ba = __ballot(active), bd = __ballot(drop);
         checked += (uint32_t)__builtin_popcountll(ba); dropped += (uint32_t)__builtin_popcountll(bd);
+        if constexpr (RATIO) dropped_ratio += (uint32_t)__builtin_popcountll(__ballot(drop_ratio));
         // the keys beyond this round move to the front: read, barrier, write
         r3dm_syncthreads();
         const uint32_t rest = held - cnt;            // < 256
@@ -65,6 +88,7 @@ __device__ __forceinline__ void mutual_pair_rounds(const MutualParams& P, uint32
     if (lane == 0 && checked) {
         atomicAdd(P.counters, (unsigned long long)checked);
         if (dropped) atomicAdd(P.counters + 1, (unsigned long long)dropped);
+        if (dropped_ratio) atomicAdd(P.counters + 2, (unsigned long long)dropped_ratio);
     }
 }
 
@@ -82,7 +106,7 @@ void l2_mutual_batch_kernel(const MutualParams P)
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
     const uint32_t nJ = Jp->n, d4 = Ip->dim >> 2;    // dim % 4 == 0 guaranteed by the caller
     const gf4p itiles = (gf4p)Ip->tiled, jtiles = (gf4p)Jp->tiled;
-    mutual_pair_rounds(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> uint32_t {
+    mutual_pair_rounds<false>(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> uint32_t {
         f32x4 iv[D4];
         const gf4p irow = itiles + (size_t)(i >> 5) * (D4 * 32) + (i & 31u);
 #pragma unroll
@@ -105,13 +129,55 @@ void l2_mutual_batch_kernel(const MutualParams P)
     });
 }
 
+// the ratio form: the same stream of J's tiles, the serial scan keeps two minima.  Rows ascend, so an equal distance never replaces
+// the best (ties to the lower row) and becomes d2 -- a duplicate of row j gives d2 = d1.  When the best row is j, d2 is the minimum
+// over every other row; when it is not, the match is gone whatever d2 holds.
+template <int G>
+__global__ __launch_bounds__(256)
+void l2_symratio_batch_kernel(const MutualParams P)
+{
+    constexpr int D4 = G * 2;                        // float4 per (padded) row
+    __shared__ f32x4 tile[32 * D4];                  // 32 rows of J x Dpad floats, fragment order: [chunk k][row r]
+    __shared__ unsigned long long cand[512];
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t pair = blockIdx.x;
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const uint32_t nJ = Jp->n, d4 = Ip->dim >> 2;    // dim % 4 == 0 guaranteed by the caller
+    const gf4p itiles = (gf4p)Ip->tiled, jtiles = (gf4p)Jp->tiled;
+    mutual_pair_rounds<true>(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> Nearest2 {
+        f32x4 iv[D4];
+        const gf4p irow = itiles + (size_t)(i >> 5) * (D4 * 32) + (i & 31u);
+#pragma unroll
+        for (int k = 0; k < D4; ++k) iv[k] = (k < (int)d4) ? irow[k * 32] : f32x4{0.f, 0.f, 0.f, 0.f};
+        float bd = R3DM_INF, d2 = R3DM_INF; uint32_t bj = kNone;
+        for (uint32_t t0 = 0; t0 < nJ; t0 += 32) {
+            r3dm_syncthreads();                      // every wave has finished with the previous tile
+            {
+                const gf4p src = jtiles + (size_t)(t0 >> 5) * (D4 * 32);
+                for (uint32_t e = threadIdx.x; e < 32u * D4; e += 256) tile[e] = src[e];
+            }
+            r3dm_syncthreads();
+            const uint32_t rows_here = (nJ - t0 < 32u) ? nJ - t0 : 32u;
+            for (uint32_t r = 0; r < rows_here; ++r) {
+                const float result = stage_l2sq<D4>(iv, tile, r, d4);
+                if (result < bd) { d2 = bd; bd = result; bj = t0 + r; }
+                else if (result < d2) d2 = result;
+            }
+        }
+        return Nearest2{bj, bd, d2};
+    });
+}
+
 hipError_t launch_l2_mutual_batch(hipStream_t st, const MutualParams& P, uint32_t G)
 {
     if (P.n_pairs == 0) return hipSuccess;
     if (P.n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
     const dim3 grid(P.n_pairs);
     return dispatch_g(G, [&](auto g) {
-        hipLaunchKernelGGL((l2_mutual_batch_kernel<decltype(g)::value>), grid, dim3(256), 0, st, P);
+        if (P.ratio_form) hipLaunchKernelGGL((l2_symratio_batch_kernel<decltype(g)::value>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((l2_mutual_batch_kernel<decltype(g)::value>), grid, dim3(256), 0, st, P);
         return hipGetLastError();
     });
 }
@@ -163,11 +229,64 @@ void l2_mutual_items_kernel(const MutualParams P, uint32_t count)
     }
 }
 
+// the ratio form: every thread keeps a 2-list (best, its row, second distance) over its share of the rows, and the tree merges
+// 2-LISTS: the second minimum of a union is the loser's best or the winner's second -- it may be the second entry of one thread's
+// list, which a merge of bests alone would lose.  The winner is chosen under the (distance, row) order; the row of d2 does not matter.
+__global__ __launch_bounds__(256)
+void l2_symratio_items_kernel(const MutualParams P, uint32_t count)
+{
+    __shared__ float sd[256];
+    __shared__ float s2[256];
+    __shared__ uint32_t si[256];
+    uint32_t checked = 0, dropped = 0, dropped_ratio = 0;         // kept by thread 0
+    for (uint32_t it = blockIdx.x; it < count; it += gridDim.x) {
+        const uint32_t pair = it / P.q_stride, j = it % P.q_stride;
+        const uint2 pr = P.pairs[pair];
+        const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+        const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+        const uint32_t nJ = Jp->n;
+        if (j >= nJ) continue;                                    // block-uniform
+        const uint32_t i = P.nn_idx[it];                          // block-uniform: every thread reads it before the barriers below
+        if (i >= kFallback) continue;
+        const uint32_t dim = Ip->dim;
+        const float* iv = Ip->rows + (size_t)i * dim;
+        float bd = R3DM_INF, d2 = R3DM_INF; uint32_t bj = kNone;
+        for (uint32_t r = threadIdx.x; r < nJ; r += 256) {
+            const float d = exact_l2sq(iv, Jp->rows + (size_t)r * dim, dim);
+            if (d < bd) { d2 = bd; bd = d; bj = r; }
+            else if (d < d2) d2 = d;
+        }
+        sd[threadIdx.x] = bd; s2[threadIdx.x] = d2; si[threadIdx.x] = bj;
+        r3dm_syncthreads();
+        for (uint32_t s = 128; s > 0; s >>= 1) {
+            if (threadIdx.x < s) {
+                const float a0 = sd[threadIdx.x], a1 = s2[threadIdx.x]; const uint32_t x = si[threadIdx.x];
+                const float b0 = sd[threadIdx.x + s], b1 = s2[threadIdx.x + s]; const uint32_t y = si[threadIdx.x + s];
+                if (lex_less(b0, y, a0, x)) { sd[threadIdx.x] = b0; si[threadIdx.x] = y; s2[threadIdx.x] = a0 < b1 ? a0 : b1; }
+                else s2[threadIdx.x] = b0 < a1 ? b0 : a1;
+            }
+            r3dm_syncthreads();
+        }
+        if (threadIdx.x == 0) {
+            checked += 1;
+            if (si[0] != j) { P.nn_idx[it] = kNone; dropped += 1; }
+            else if (!(nJ >= 2u && reverse_ratio_passes(P, sd[0], s2[0]))) { P.nn_idx[it] = kNone; dropped_ratio += 1; }
+        }
+        r3dm_syncthreads();
+    }
+    if (threadIdx.x == 0 && checked) {
+        atomicAdd(P.counters, (unsigned long long)checked);
+        if (dropped) atomicAdd(P.counters + 1, (unsigned long long)dropped);
+        if (dropped_ratio) atomicAdd(P.counters + 2, (unsigned long long)dropped_ratio);
+    }
+}
+
 hipError_t launch_l2_mutual_items(hipStream_t st, const MutualParams& P, uint32_t count)
 {
     if (count == 0) return hipSuccess;
     const uint32_t grid = count < 16384u ? count : 16384u;
-    hipLaunchKernelGGL(l2_mutual_items_kernel, dim3(grid), dim3(256), 0, st, P, count);
+    if (P.ratio_form) hipLaunchKernelGGL(l2_symratio_items_kernel, dim3(grid), dim3(256), 0, st, P, count);
+    else hipLaunchKernelGGL(l2_mutual_items_kernel, dim3(grid), dim3(256), 0, st, P, count);
     return hipGetLastError();
 }
 
@@ -189,7 +308,7 @@ void hamming_mutual_kernel(const MutualParams P)
     const uint32_t nJ = Jp->n;
     const uint32_t* __restrict__ ibin = Ip->bin;
     const uint32_t* __restrict__ jbin = Jp->bin;
-    mutual_pair_rounds(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> uint32_t {
+    mutual_pair_rounds<false>(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> uint32_t {
         uint32_t a[W];
 #pragma unroll
         for (int w = 0; w < W; ++w) a[w] = ibin[(size_t)i * W + w];
@@ -212,13 +331,56 @@ void hamming_mutual_kernel(const MutualParams P)
     });
 }
 
+// the ratio form: the two smallest packed keys.  Keys of distinct rows are distinct, so when the smallest is row j's the second is the
+// minimum over every other row and its distance field is d2 (a duplicate of row j: the same distance, a higher row).  The distances
+// go into the test as floats, as the forward test takes them.
+template <int W>
+__global__ __launch_bounds__(256)
+void hamming_symratio_kernel(const MutualParams P)
+{
+    __shared__ uint32_t tile[32 * W];
+    __shared__ unsigned long long cand[512];
+    __shared__ uint32_t wave_cnt[4];
+    const uint32_t pair = blockIdx.x;
+    const uint2 pr = P.pairs[pair];
+    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
+    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
+    const uint32_t nJ = Jp->n;
+    const uint32_t* __restrict__ ibin = Ip->bin;
+    const uint32_t* __restrict__ jbin = Jp->bin;
+    mutual_pair_rounds<true>(P, pair, nJ, cand, wave_cnt, [&](uint32_t i, uint32_t, bool) -> Nearest2 {
+        uint32_t a[W];
+#pragma unroll
+        for (int w = 0; w < W; ++w) a[w] = ibin[(size_t)i * W + w];
+        uint32_t best = 0xFFFFFFFFu, second = 0xFFFFFFFFu;
+        for (uint32_t t0 = 0; t0 < nJ; t0 += 32) {
+            r3dm_syncthreads();
+            for (uint32_t e = threadIdx.x; e < 32u * W; e += 256)
+                tile[e] = (t0 + e / W < nJ) ? jbin[(size_t)t0 * W + e] : 0u;
+            r3dm_syncthreads();
+            const uint32_t rows_here = (nJ - t0 < 32u) ? nJ - t0 : 32u;
+            for (uint32_t r = 0; r < rows_here; ++r) {
+                uint32_t d = 0;
+#pragma unroll
+                for (int w = 0; w < W; ++w) d += (uint32_t)__builtin_popcount(a[w] ^ tile[r * W + w]);
+                const uint32_t key = ham_key(d, t0 + r);
+                const uint32_t loser = best < key ? key : best;
+                best = best < key ? best : key;
+                second = second < loser ? second : loser;
+            }
+        }
+        return Nearest2{best == 0xFFFFFFFFu ? kNone : ham_key_row(best), (float)ham_key_dist(best), (float)ham_key_dist(second)};
+    });
+}
+
 hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t words)
 {
     if (P.n_pairs == 0) return hipSuccess;
     if (P.n_pairs > kMaxBlocksOf256) return hipErrorInvalidValue;
     const dim3 grid(P.n_pairs);
     return dispatch_words(words, [&](auto w) {
-        hipLaunchKernelGGL((hamming_mutual_kernel<decltype(w)::value>), grid, dim3(256), 0, st, P);
+        if (P.ratio_form) hipLaunchKernelGGL((hamming_symratio_kernel<decltype(w)::value>), grid, dim3(256), 0, st, P);
+        else hipLaunchKernelGGL((hamming_mutual_kernel<decltype(w)::value>), grid, dim3(256), 0, st, P);
         return hipGetLastError();
     });
 }

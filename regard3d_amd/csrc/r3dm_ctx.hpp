@@ -580,7 +580,9 @@ struct r3dm_ctx {
     bool mutual_matching = false;                           // r3dm_set_mutual_matching: the mutual check runs before every finalisation into a graph
     bool kgraph_hamming = false;                            // r3dm_set_kgraph_hamming: the graph matcher serves binary views (Hamming index + search on the packed rows)
     r3dm_kgraph_hamming_stats kgraph_hamming_stats{};       // r3dm_kgraph_hamming_report: since r3dm_create (never reset)
-    DevBuf d_mutual;                                        // its two counters (allocated by the first batch that runs the check)
+    bool symmetric_ratio = false;                           // r3dm_set_symmetric_ratio: the check also applies the reverse ratio test (and runs with the mutual switch off)
+    uint64_t symratio_counts[3] = {0, 0, 0};                // r3dm_symmetric_ratio_report: checked / not nearest / removed by the reverse ratio in the last collecting call
+    DevBuf d_mutual;                                        // its three counters (allocated by the first batch that runs the check)
     // r3dm_set_preemptive_matching (api_preselect.cpp): the switch, its head size and threshold; the buffers of a gate call (row lists,
     // head table, pairs, counts), its events and its report -- all made by the first gate
     bool preemptive_on = false;
@@ -749,7 +751,8 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
                     int32_t* knn_idx_host, float* knn_dist_host);
 // knn_cols: entries per query in d_knn_idx / d_knn_dist (2: the 2-NN kernels; k: the k-list kernels of the approximate arms)
 int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_stride, uint32_t sort_cap,
-                   uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols = 2);
+                   uint64_t n_queries, uint32_t max_nJ, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host, uint32_t knn_cols = 2,
+                   ForwardRatio forward = ForwardRatio());   // forward: the batch's ratio test, which r3dm_set_symmetric_ratio repeats in reverse
 int run_exact_knn_pair(r3dm_ctx* c, uint32_t sI, uint32_t sJ, uint32_t k, int32_t* out_idx, float* out_dist);
 // an index search's two private slots: the index mounted into slot_index beside the freshly staged query view in slot_query
 int mount_index_beside_queries(r3dm_ctx* c, const r3dm_index* ix, const void* query, uint32_t n_query, uint32_t slot_index, uint32_t slot_query);
@@ -787,7 +790,7 @@ struct AnnBatch {
     uint32_t* nn_idx; int32_t* knn_idx; float* knn_dist; unsigned long long* n_comps;
 };
 int run_ann_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, r3dm_graph* g, int32_t* knn_idx_host, float* knn_dist_host,
-                  const std::function<int(const AnnBatch&)>& launch, uint32_t knn_cols = 2);
+                  const std::function<int(const AnnBatch&)>& launch, uint32_t knn_cols = 2, ForwardRatio forward = ForwardRatio());
 
 // ---- k-NN through an arm's structure on an r3dm_index (r3dm_index_kgraph_knn / _hnsw_knn / _mrpt_knn)
 // state(image of the index): R3DM_OK = the arm's structure is there and was built from these build parameters, 1 = not built yet,

@@ -274,8 +274,16 @@ struct MutualParams {
     uint32_t      n_pairs;
     uint32_t      q_stride;
     uint32_t*     nn_idx;         // [n_pairs][q_stride]
-    unsigned long long* counters; // [2]: matches checked, matches dropped (atomic; zeroed by the host)
+    unsigned long long* counters; // [3]: matches checked, dropped because not nearest, dropped by the reverse ratio (atomic; zeroed by the host)
+    // the symmetric ratio test (r3dm_set_symmetric_ratio): a match that is nearest must also pass f(d1) < ratio_R * f(d2), d2 = the
+    // smallest distance from its row of I to any other row of J.  ratio_form 0: mutual check only; 1: f = identity (ratio_R = the
+    // forward test's R: ratio^2 on squared distances, ratio on Hamming distances); 2: f = sqrtf, ratio_R = ratio (the MRPT arm)
+    float         ratio_R;
+    uint32_t      ratio_form;
 };
+// the forward ratio test of the batch a finalisation collects, for the reverse one: R as the arm's kernels got it, on_roots = the arm
+// compares square roots (MRPT's indexed pairs)
+struct ForwardRatio { float R = 0.0f; bool on_roots = false; };
 
 // the gate of preemptive matching (kernels_match_head.hip; r3dm_set_preemptive_matching, r3dm_preselect_pairs): a view's head is its
 // min(h, n) largest-scale rows in a row-major buffer of its own; the table of a gate call is indexed by slot
