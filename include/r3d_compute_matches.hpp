@@ -132,6 +132,14 @@ public:
     // is what setDirectRegistration(false) does.  128 / 4 are Wu's SIFT-era 100 / 4 rounded to a tile multiple, not tuned for LIOP.  Off by
     // default: the match files are the reference's only while it is off.
     void setPreemptiveMatching(bool on, uint32_t head_rows = 128, uint32_t min_matches = 4);
+    // no reference counterpart (the reference matches every row of every view): forwards r3dm_set_match_budget to every device context,
+    // so only the max_rows largest-scale features of a view take part in putative matching -- the other rows lose their matches; the
+    // putative files hold the views' own feature indices.  With setGuidedMatching on, the budgeted putatives decide which pairs and
+    // models survive and the guided step re-matches over all features.  The scale column of every view's .feat file is registered as
+    // its priority; the features sink carries no scales, so while this is on every view is registered from its files, exactly as under
+    // setPreemptiveMatching.  8,192 is VisualSFM's number, not tuned.  Off by default: the match files are the reference's only while
+    // it is off.
+    void setMatchBudget(bool on, uint32_t max_rows = 8192);
     // no reference counterpart (the reference matches exhaustivePairs): instead of all pairs, the stage matches the pairs that
     // r3dm_propose_pairs proposes (the contract is in r3dm.h).  After the views are registered it samples a vocabulary of n_words rows
     // from them in view-id order (r3dm_vocab_sample; lowered to half the collection's rows when it has fewer than 2 n_words), proposes
@@ -233,6 +241,7 @@ private:
     const size_t* sink_need_ = nullptr;    // views of the running features chunk
     bool direct_registration_ = true;
     bool preemptive_on_ = false;
+    bool budget_on_ = false;
     bool proposal_on_ = false;
     uint32_t proposal_words_ = 16384, proposal_top_k_ = 20;
     uint64_t last_pair_count_ = 0;
@@ -306,12 +315,13 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_DESCRIPTOR_MSURF 1024u /* setRegionsType(R3DM_F32, 64): the features stage writes M-SURF-64 rows (r3dm_set_descriptor_arm); together with R3DM_STAGE_DESCRIPTOR_MLDB: R3DM_ERR_INVALID */
 #define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
 #define R3DM_STAGE_PAIR_PROPOSAL 2048u /* the matcher gets the pairs r3dm_propose_pairs proposes, not all pairs (R3DComputeMatches::setPairProposal(true)): 16,384 words, lowered to half the collection's rows when it is smaller, top_k 20 -- untuned defaults */
+#define R3DM_STAGE_MATCH_BUDGET 8192u /* match budget with max_rows 8,192 (R3DComputeMatches::setMatchBudget(true), r3dm_set_match_budget): only each view's 8,192 largest-scale features are matched; default: every row is matched */
 #define R3DM_STAGE_SYMMETRIC_RATIO 4096u /* symmetric ratio test (R3DComputeMatches::setSymmetricRatio(true), r3dm_set_symmetric_ratio): a match must also pass the 2-NN + ratio rule with the views swapped; default off */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
-/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_SYMMETRIC_RATIO, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_F32_TILES */
+/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_SYMMETRIC_RATIO, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_MATCH_BUDGET, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_F32_TILES */
 int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                                    r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
                                    uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);

@@ -111,6 +111,7 @@ int r3dm_images_wait(r3dm_ctx* ctx);
 #define R3DM_LAYOUT_COUNTS 8u   /* count tiles + scale order (r3dm_set_split_mfma, votes x scale rows) */
 #define R3DM_LAYOUT_BIN8   16u  /* byte-per-bit tiles (r3dm_set_hamming_mfma) */
 #define R3DM_LAYOUT_HEAD   32u  /* the head rows of preemptive matching (r3dm_set_preemptive_matching, r3dm_preselect_pairs) */
+#define R3DM_LAYOUT_BUDGET 64u  /* the sub-view of the match budget (r3dm_set_match_budget) */
 int r3dm_view_info(r3dm_ctx* ctx, uint32_t view_id, uint32_t* layouts, uint64_t* bytes, uint64_t* ring_uploads, uint64_t* direct_uploads);
 /* device memory the context holds for its registered views (the slabs their layouts are cut from, live and recycled blocks alike),
  * for the upload ring (device slots + position-class tables), and the ring's page-locked host memory; any pointer may be NULL */
@@ -285,6 +286,65 @@ typedef struct {
     uint64_t n_views_without_priority; /* views of the call whose head is their first rows */
 } r3dm_preselect_stats;
 int r3dm_preselect_report(const r3dm_ctx* ctx, r3dm_preselect_stats* out);
+
+/* Opt-in match budget (default off; no reference counterpart -- the reference matches every row of every view, and parity with it
+ * depends on that default): only the N highest-priority rows of each view take part in putative matching (VisualSFM matches each
+ * image's 8,192 largest-scale features: Wu, 3DV 2013; COLMAP bounds the features per image).  ROWS OUTSIDE THE BUDGET LOSE THEIR
+ * MATCHES: the budget trades recall for time.  Nothing below carries a tolerance; every statement is bit for bit.
+ *
+ * Selected rows of a view of n rows for budget N (N >= 2).  S = the min(N, n) rows that come first under the order (priority
+ * descending, row index ascending) -- the priority and the order of r3dm_set_view_priority above: finite, >= 0, -0.0 stored as +0.0 --
+ * kept in ASCENDING ROW INDEX.  A view without priority takes its first min(N, n) rows.  A view with n <= N is WHOLE: nothing is copied,
+ * no kernel runs for it, and it is matched as registered.
+ *
+ * Graph.  For a pair (I, J) the collection entry runs exactly as it does with the switch off on the view I' = the rows S(I) of I in that
+ * order with their positions, and on J' likewise; every match (i', j') is returned as (S(I)[i'], S(J)[j']).  Put another way: the graph
+ * equals the graph of a fresh context in which the caller registered the sub-arrays under the same view ids, with every index mapped
+ * back through S -- on every arm and every tile format that collects matches into a graph (f32 tiles, r3dm_set_integer_mfma,
+ * r3dm_set_split_mfma with its count tiles, the popcount Hamming kernel, r3dm_set_hamming_mfma; r3dm_match_pairs_kgraph / _hnsw / _mrpt,
+ * whose indices are built on the sub-views and whose choice between index and scan looks at the sub-view), with the mutual and the
+ * symmetric-ratio check on top, the coordinate de-duplication, the order of pairs and of matches within a pair, and the device mirror
+ * under r3dm_set_device_graphs.  The ratio test sees the sub-view's second neighbour.  The budgeted graph is therefore NOT the full
+ * graph restricted to S: a query whose runner-up lies outside S may be accepted here and refused there.
+ *
+ * Honoured by r3dm_match_pairs, r3dm_match_pairs_kgraph / _hnsw / _mrpt and their r3dm_multi_* forms (each context budgets its own
+ * shard; the switch is r3dm_multi_set_match_budget; stage: R3DComputeMatches::setMatchBudget, R3DM_STAGE_MATCH_BUDGET).  IGNORED by the
+ * entries that return raw neighbour lists -- r3dm_knn2, r3dm_knn, the r3dm_index_* family, the *_knn2 / *_knn entries --, by the
+ * vocabulary entries, by r3dm_kgraph_index / r3dm_hnsw_index / r3dm_mrpt_index, which report on the whole view, and by guided matching
+ * and the filters, which read the registered positions through original indices: with guided matching on, the budgeted putatives
+ * decide which pairs and models survive and the guided step re-matches over ALL features.
+ *
+ * The preemptive gate is unchanged: it builds its heads from the whole views and runs before the budget.  With both switches on the
+ * graph is the budgeted graph restricted to the gate's kept pairs.
+ *
+ * r3dm_set_match_budget: the switch.  max_rows < 2 is R3DM_ERR_INVALID (also when enable is 0: the value is stored either way).  While
+ *   the switch is off and the primitive is not called nothing is allocated, uploaded or launched, and every entry returns what it
+ *   returns without it.
+ * r3dm_budget_rows: the primitive, whatever the switch says: S of the view from the device selection, ascending, in rows_out (room for
+ *   min(max_rows, n) entries); *n_out = min(max_rows, n); a whole view returns 0 .. n - 1.  An unregistered view or max_rows < 2 is
+ *   R3DM_ERR_INVALID.
+ * Cache.  A budgeted view holds its sub-view as one more on-demand layout, R3DM_LAYOUT_BUDGET in r3dm_view_info, whose bytes -- the
+ *   row list, the sub-view's layouts and the indices built on it -- are counted there and in r3dm_memory_info.  It is made by the first
+ *   collection call that needs it (selection: one workgroup per view, all views of the call in one launch; priorities reach the device
+ *   then; gather; staging as a registered view is staged) and remade when N, the priority or the registration changes;
+ *   r3dm_set_image(s) on the id and r3dm_clear_images release it; r3dm_drop_indices also drops the indices built on sub-views.
+ *   The selection walks a view R3DM_BUDGET_SELECT_CHUNK rows at a time -- it only matters to tests that straddle it.
+ * r3dm_budget_report: the last collection call or the last r3dm_budget_rows call; all zero after a collection call with the switch off. */
+#define R3DM_BUDGET_SELECT_CHUNK 256u
+int r3dm_set_match_budget(r3dm_ctx* ctx, int enable, uint32_t max_rows);
+int r3dm_budget_rows(r3dm_ctx* ctx, uint32_t view_id, uint32_t max_rows, uint32_t* rows_out, uint32_t* n_out);
+typedef struct {
+    double ms_select;                  /* HIP-event time of the selection kernel */
+    double ms_gather;                  /* ... of the gather kernels */
+    double ms_remap;                   /* ... of the remap kernels of the call's batches */
+    double ms_wall;                    /* host time of the budget's share: substitution (selection, gather, staging) and remaps */
+    uint64_t n_views_budgeted;         /* views of the call with more rows than the budget */
+    uint64_t n_views_whole;            /* views of the call matched as registered */
+    uint64_t n_subviews_built;         /* sub-views made by this call (the others were cached) */
+    uint64_t n_rows_selected;          /* rows of the budgeted views that take part: max_rows each */
+    uint64_t n_matches_remapped;       /* matches of pairs with a budgeted view, sent back through the row lists */
+} r3dm_budget_stats;
+int r3dm_budget_report(const r3dm_ctx* ctx, r3dm_budget_stats* out);
 
 /* Pair proposal from bag-of-words view signatures (no reference counterpart -- the reference matches exhaustivePairs, SURVEY.md section
  * 5, and parity with it depends on that: nothing proposes pairs unless a caller asks).  Instead of matching all n (n - 1) / 2 pairs of a
@@ -934,6 +994,7 @@ int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out);           /
 int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
+int r3dm_multi_set_match_budget(r3dm_multi* m, int enable, uint32_t max_rows);                                 /* on every context: each budgets its own shard */
 int r3dm_multi_match_pairs(r3dm_multi* m, const uint32_t* pairs_ij, uint64_t n_pairs,
                            float dist_ratio, int squared_metric, r3dm_graph** out);
 /* the same deal for the graph matcher (kgraph_match, config C5): a device builds the index of every image I whose row it owns */

@@ -46,6 +46,7 @@ EXPORTS = [
     "r3dm_set_kgraph_hamming", "r3dm_multi_set_kgraph_hamming", "r3dm_kgraph_hamming_report", "r3dm_kgraph_knn2_bits", "r3dm_kgraph_knn_bits",
     "r3dm_set_view_priority", "r3dm_preselect_pairs", "r3dm_set_preemptive_matching", "r3dm_preselect_report",
     "r3dm_multi_set_view_priority", "r3dm_multi_set_preemptive_matching",
+    "r3dm_set_match_budget", "r3dm_budget_rows", "r3dm_budget_report", "r3dm_multi_set_match_budget",
     "r3dm_build_tracks", "r3dm_tracks_count", "r3dm_tracks_offsets", "r3dm_tracks_observations", "r3dm_tracks_report", "r3dm_tracks_phase_ms", "r3dm_tracks_in_pair",
     "r3dm_tracks_free",
     "r3dm_detect_akaze_mldb_batch", "r3dm_set_descriptor_arm", "r3dm_multi_set_descriptor_arm",
@@ -68,6 +69,9 @@ STAGE_SYMMETRIC_RATIO = 4096                      # R3DM_STAGE_SYMMETRIC_RATIO: 
 STAGE_PAIR_PROPOSAL = 2048                        # R3DM_STAGE_PAIR_PROPOSAL: 16,384 words (half the collection's rows when that is less), top_k 20
 VOCAB_MAX_WORDS, VOCAB_HIST_LDS_WORDS, VOCAB_WORD_CHUNK = 65536, 8192, 32      # R3DM_VOCAB_* (include/r3dm.h)
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
+LAYOUT_BUDGET = 64                                # R3DM_LAYOUT_BUDGET
+BUDGET_SELECT_CHUNK = 256                         # R3DM_BUDGET_SELECT_CHUNK
+STAGE_MATCH_BUDGET = 8192                         # R3DM_STAGE_MATCH_BUDGET: r3dm_set_match_budget with max_rows 8,192 on every context of the stage
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
 # the descriptor arms, the rows of csrc/descriptor_arms.hpp (tests/test_descriptor_arms.py holds the two to each other): name, id
 # (R3DM_DESCRIPTOR_*; 2 is unassigned), stage flag, numpy dtype and length of a row
@@ -127,6 +131,16 @@ class PreselectStats(C.Structure):
     """r3dm_preselect_stats: the gate of the last match call (preemptive matching on) or preselect_pairs call"""
     _fields_ = [("ms_kernels", C.c_double), ("ms_wall", C.c_double), ("n_pairs", C.c_uint64), ("n_kept", C.c_uint64),
                 ("n_heads_built", C.c_uint64), ("n_views_without_priority", C.c_uint64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class BudgetStats(C.Structure):
+    """r3dm_budget_stats: the match budget's share of the last collection call (the switch on) or budget_rows call"""
+    _fields_ = [("ms_select", C.c_double), ("ms_gather", C.c_double), ("ms_remap", C.c_double), ("ms_wall", C.c_double),
+                ("n_views_budgeted", C.c_uint64), ("n_views_whole", C.c_uint64), ("n_subviews_built", C.c_uint64),
+                ("n_rows_selected", C.c_uint64), ("n_matches_remapped", C.c_uint64)]
 
     def as_dict(self):
         return {k: getattr(self, k) for k, _ in self._fields_}
@@ -259,12 +273,13 @@ class Stage:
             compute_E: bool = True, compute_H: bool = True, seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8,
             arms_as_requested: bool = False, split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
             guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False,
-            symmetric_ratio: bool = False) -> StageReport:
+            symmetric_ratio: bool = False, budget: bool = False) -> StageReport:
         """guided: bGuided_matching = true for the three filters (R3DM_STAGE_GUIDED_MATCHING); detector: "Fast-AKAZE" or "AKAZE"
         (R3DM_STAGE_DETECTOR_AKAZE, the GUI's keypointDetectorType 0); mutual: mutual nearest-neighbour matching (R3DM_STAGE_MUTUAL_MATCHING); preemptive: preemptive matching at 128 / 4
         (R3DM_STAGE_PREEMPTIVE_MATCHING); descriptor: "LIOP", "MLDB" (R3DM_STAGE_DESCRIPTOR_MLDB: binary regions, 61 bytes) or "MSURF"
         (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64, 64 floats); proposal: the matcher gets the pairs r3dm_propose_pairs proposes
-        (R3DM_STAGE_PAIR_PROPOSAL); symmetric_ratio: the symmetric ratio test (R3DM_STAGE_SYMMETRIC_RATIO)"""
+        (R3DM_STAGE_PAIR_PROPOSAL); symmetric_ratio: the symmetric ratio test (R3DM_STAGE_SYMMETRIC_RATIO); budget: the match budget at 8,192
+        rows per view (R3DM_STAGE_MATCH_BUDGET)"""
         dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
         keep = []
         arr = _stage_views(views, keep)
@@ -272,7 +287,7 @@ class Stage:
         rc = self._L.r3dm_stage_run(self._h, matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm, int(compute_F),
                                     int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                     (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | dflag, C.byref(rep), err, 1024)
+                                    | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | (STAGE_MATCH_BUDGET if budget else 0) | dflag, C.byref(rep), err, 1024)
         if rc != 0:
             raise R3dmError(f"r3dm_stage_run -> {rc}: {err.value.decode()}")
         return rep
@@ -294,7 +309,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
                           seed: int = 5489, batches_in_flight: int = 3, images_per_batch: int = 8, arms_as_requested: bool = False,
                           split_mfma: bool = False, integer_mfma: bool = False, f32_tiles: bool = False, background_nice: bool = False,
                           guided: bool = False, detector: str = "Fast-AKAZE", mutual: bool = False, preemptive: bool = False, descriptor: str = "LIOP", proposal: bool = False,
-            symmetric_ratio: bool = False) -> StageReport:
+            symmetric_ratio: bool = False, budget: bool = False) -> StageReport:
     """R3DComputeMatches::computeMatches from pixels (r3dm_compute_matches_stage): features stage for the views whose .feat/.desc
     are missing, matching, F / E / H filters, match files.  views: dicts with id, width, height, basename and optionally
     gray ([h, w] float32) or bgr ([h, w, 3] uint8) -- numpy or torch (host or device) -- and focal_px / ppx / ppy.
@@ -303,7 +318,8 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     the features stage writes MLDB-486 rows, the matcher runs its binary rules) or "MSURF" (R3DM_STAGE_DESCRIPTOR_MSURF: M-SURF-64
     rows of 64 floats, matched by the float rules as LIOP is); proposal: R3DM_STAGE_PAIR_PROPOSAL (the matcher gets the pairs
     r3dm_propose_pairs proposes from a vocabulary sampled from the stage's views: 16,384 words, half the collection's rows when that is
-    less, top_k 20); symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO (a match must also pass the 2-NN + ratio rule with the views swapped)."""
+    less, top_k 20); symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO (a match must also pass the 2-NN + ratio rule with the views swapped); budget:
+    R3DM_STAGE_MATCH_BUDGET (only each view's 8,192 largest-scale features are matched)."""
     dflag = _detector_flag(detector) | _descriptor_flag(descriptor)
     L = load_library()
     keep = []
@@ -314,7 +330,7 @@ def compute_matches_stage(device_ids, matches_dir: str, views, threshold: float 
     rc = L.r3dm_compute_matches_stage(ids, len(device_ids), matches_dir.encode(), arr, len(views), threshold, dist_ratio, matching_algorithm,
                                       int(compute_F), int(compute_E), int(compute_H), seed, batches_in_flight, images_per_batch,
                                       (1 if arms_as_requested else 0) | (2 if split_mfma else 0) | (4 if integer_mfma else 0) | (8 if f32_tiles else 0) | (16 if background_nice else 0)
-                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | dflag, C.byref(rep), err, 1024)
+                                      | (STAGE_GUIDED_MATCHING if guided else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0) | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | (STAGE_MATCH_BUDGET if budget else 0) | dflag, C.byref(rep), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_stage -> {rc}: {err.value.decode()}")
     return rep
@@ -327,11 +343,12 @@ class _DirView(C.Structure):
 
 def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0, dim: int = 144, dist_ratio: float = 0.6,
                         compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False, preemptive: bool = False,
-                        proposal: bool = False, symmetric_ratio: bool = False):
+                        proposal: bool = False, symmetric_ratio: bool = False, budget: bool = False):
     """R3DComputeMatches::computeMatches over a directory that holds every view's .feat / .desc (r3dm_compute_matches_dir_flags):
     exhaustive matching, the F filter when asked, matches.putative.txt / matches.f.txt.  views: dicts with id, width, height,
     basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive: R3DM_STAGE_PREEMPTIVE_MATCHING (the .feat scale column is
-    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL; symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO.  -> (putative pairs, geometric pairs)"""
+    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL; symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO; budget: R3DM_STAGE_MATCH_BUDGET (8,192 rows
+    per view, priority = the .feat scale column).  -> (putative pairs, geometric pairs)"""
     L = load_library()
     arr = (_DirView * len(views))(*[_DirView(int(v["id"]), int(v["width"]), int(v["height"]), str(v["basename"]).encode()) for v in views])
     npp, ngp = C.c_uint64(0), C.c_uint64(0)
@@ -340,7 +357,7 @@ def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0,
                                                  C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     rc = L.r3dm_compute_matches_dir_flags(device_id, matches_dir.encode(), arr, len(views), dtype, dim, dist_ratio, int(compute_F), seed,
                                           (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0)
-                                          | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0),
+                                          | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | (STAGE_MATCH_BUDGET if budget else 0),
                                           C.byref(npp), C.byref(ngp), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_dir_flags -> {rc}: {err.value.decode()}")
@@ -475,6 +492,10 @@ def load_library():
     L.r3dm_set_preemptive_matching.argtypes = [vp, C.c_int, u32, u32]
     L.r3dm_multi_set_preemptive_matching.argtypes = [vp, C.c_int, u32, u32]
     L.r3dm_preselect_report.argtypes = [vp, vp]
+    L.r3dm_set_match_budget.argtypes = [vp, C.c_int, u32]
+    L.r3dm_multi_set_match_budget.argtypes = [vp, C.c_int, u32]
+    L.r3dm_budget_rows.argtypes = [vp, u32, u32, vp, vp]
+    L.r3dm_budget_report.argtypes = [vp, vp]
     L.r3dm_vocab_sample.argtypes = [vp, vp, u32, u32, C.POINTER(vp)]
     L.r3dm_vocab_from_rows.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
     L.r3dm_vocab_info.argtypes = [vp, vp, vp, vp]
@@ -1558,6 +1579,27 @@ class Context:
         pair only if its preselect count reaches min_matches -- dropped pairs lose real matches; knn2 / knn / the index entries ignore it"""
         self._check(self._L.r3dm_set_preemptive_matching(self._h, int(bool(enable)), head_rows, min_matches), "r3dm_set_preemptive_matching")
 
+    def set_match_budget(self, enable: bool = True, max_rows: int = 8192):
+        """opt-in match budget (include/r3dm.h: r3dm_set_match_budget): match_pairs and the approximate matchers match only each view's
+        max_rows highest-priority rows (a view of at most max_rows rows is matched whole) and return the view's own row numbers -- rows
+        outside the budget lose their matches; knn2 / knn / the index entries, guided matching and the filters ignore it"""
+        self._check(self._L.r3dm_set_match_budget(self._h, int(bool(enable)), max_rows), "r3dm_set_match_budget")
+
+    def budget_rows(self, view_id: int, max_rows: int) -> np.ndarray:
+        """r3dm_budget_rows: the rows of the view the budget max_rows selects (device selection), ascending; works whatever
+        set_match_budget says"""
+        rows = np.zeros(max(min(int(max_rows), 1 << 22), 1), np.uint32)      # (a view holds fewer than 2^22 rows)
+        cnt = C.c_uint32(0)
+        self._check(self._L.r3dm_budget_rows(self._h, view_id, max_rows, _ptr(rows), C.byref(cnt)), "r3dm_budget_rows")
+        return rows[:cnt.value].copy()
+
+    def budget_report(self) -> dict:
+        """r3dm_budget_report: the budget's share of the last collection call (kernel times, wall time, views budgeted / whole, sub-views
+        built, rows selected, matches remapped)"""
+        s = BudgetStats()
+        self._check(self._L.r3dm_budget_report(self._h, C.byref(s)), "r3dm_budget_report")
+        return s.as_dict()
+
     def preselect_report(self) -> dict:
         """r3dm_preselect_report: the gate of the last call (times, pairs, pairs kept, heads built, views without priority)"""
         s = PreselectStats()
@@ -2161,6 +2203,16 @@ class MultiContext:
         """r3dm_preselect_report of context k: the gate of its shard of the last call"""
         s = PreselectStats()
         self._check(self._L.r3dm_preselect_report(self._L.r3dm_multi_ctx(self._h, k), C.byref(s)), "r3dm_preselect_report")
+        return s.as_dict()
+
+    def set_match_budget(self, enable: bool = True, max_rows: int = 8192):
+        """r3dm_multi_set_match_budget: Context.set_match_budget on every context; each budgets its own shard"""
+        self._check(self._L.r3dm_multi_set_match_budget(self._h, int(bool(enable)), max_rows), "r3dm_multi_set_match_budget")
+
+    def device_budget_report(self, k: int) -> dict:
+        """r3dm_budget_report of context k: the budget's share of its shard of the last call"""
+        s = BudgetStats()
+        self._check(self._L.r3dm_budget_report(self._L.r3dm_multi_ctx(self._h, k), C.byref(s)), "r3dm_budget_report")
         return s.as_dict()
 
     def set_preemptive_matching(self, enable: bool = True, head_rows: int = 128, min_matches: int = 4):

@@ -87,6 +87,9 @@ int match_collection_ann(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs
     if (rc != R3DM_OK) return rc;
     rc = preselect_gate(c, gate_ratio_R, indexed, scanned, arm.bin_ratio_R);      // r3dm_set_preemptive_matching
     if (rc != R3DM_OK) return rc;
+    BudgetCallGuard budget_guard{c};
+    rc = budget_substitute(c, indexed, scanned, arm.classify);                      // r3dm_set_match_budget
+    if (rc != R3DM_OK) return rc;
 
     r3dm_graph ga, gs;
     ga.offsets.push_back(0); gs.offsets.push_back(0);

@@ -56,6 +56,9 @@ extern "C" void r3dm_destroy(r3dm_ctx* c)
     if (c->pre_ev0) (void)hipEventDestroy(c->pre_ev0);
     if (c->pre_ev1) (void)hipEventDestroy(c->pre_ev1);
     c->pre_ev0 = c->pre_ev1 = nullptr;
+    for (DevBuf* b : {&c->bud_jobs, &c->bud_prio, &c->bud_raw, &c->bud_maps, &c->bud_sel}) b->release();
+    c->bud_pin.release();
+    for (hipEvent_t& e : c->bud_ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
     if (c->coop_ev) (void)hipEventDestroy(c->coop_ev);
     if (c->coop_stream) (void)hipStreamDestroy(c->coop_stream);
     c->coop_ev = nullptr; c->coop_stream = nullptr;
@@ -666,24 +669,30 @@ extern "C" int r3dm_view_info(r3dm_ctx* c, uint32_t view_id, uint32_t* layouts, 
     if (it == c->slot_of.end()) { c->err = "unregistered view"; return R3DM_ERR_INVALID; }
     const HostImage& h = *c->imgs[it->second];
     static_assert(kLayRows == R3DM_LAYOUT_ROWS && kLayBf16 == R3DM_LAYOUT_BF16 && kLaySplit == R3DM_LAYOUT_SPLIT && kLayCounts == R3DM_LAYOUT_COUNTS &&
-                  kLayBin8 == R3DM_LAYOUT_BIN8 && kLayHead == R3DM_LAYOUT_HEAD, "public layout bits");
+                  kLayBin8 == R3DM_LAYOUT_BIN8 && kLayHead == R3DM_LAYOUT_HEAD && kLayBudget == R3DM_LAYOUT_BUDGET, "public layout bits");
     if (layouts) *layouts = h.have;
     if (bytes) {
         // what the view's live layouts occupy (a recycled buffer may be larger than its present tenant; buffers of layouts the view
         // does not hold -- kept from an earlier tenant -- are not counted)
-        uint64_t b = 0;
-        if (h.dtype == R3DM_BIN) b += h.bin.cap; else b += h.tiled.cap + h.norms.cap;
-        if (h.has_xy) b += h.xy.cap + h.canon.cap;
-        if (h.have & kLayRows) b += h.rows.cap;
-        if (h.have & kLayBf16) b += h.tiled16.cap;
-        if (h.have & kLaySplit) b += h.tiledh.cap;
-        if (h.have & kLayCounts) b += h.tiledc.cap + h.tiledp.cap + h.cscale.cap + h.cquad.cap + h.cperm.cap;
-        if (h.have & kLayBin8) b += h.tiled8.cap + h.norms.cap;
-        if (h.have & kLayHead) b += h.head.cap;
-        if (h.ann_K) b += h.ann_adj.cap + h.ann_deg.cap;
-        if (h.compact_ready) b += h.ann_rows16.cap + h.ann_rows8.cap;
-        if (h.hnsw_M) b += h.hnsw_l0.cap + h.hnsw_up_off.cap + h.hnsw_up.cap;
-        if (h.mrpt_trees) b += h.mrpt_R.cap + h.mrpt_RT.cap + h.mrpt_splits.cap + h.mrpt_leaves.cap + h.mrpt_lf.cap;
+        auto held = [](const HostImage& v) {
+            uint64_t b = 0;
+            if (v.dtype == R3DM_BIN) b += v.bin.cap; else b += v.tiled.cap + v.norms.cap;
+            if (v.has_xy) b += v.xy.cap + v.canon.cap;
+            if (v.have & kLayRows) b += v.rows.cap;
+            if (v.have & kLayBf16) b += v.tiled16.cap;
+            if (v.have & kLaySplit) b += v.tiledh.cap;
+            if (v.have & kLayCounts) b += v.tiledc.cap + v.tiledp.cap + v.cscale.cap + v.cquad.cap + v.cperm.cap;
+            if (v.have & kLayBin8) b += v.tiled8.cap + v.norms.cap;
+            if (v.have & kLayHead) b += v.head.cap;
+            if (v.ann_K) b += v.ann_adj.cap + v.ann_deg.cap;
+            if (v.compact_ready) b += v.ann_rows16.cap + v.ann_rows8.cap;
+            if (v.hnsw_M) b += v.hnsw_l0.cap + v.hnsw_up_off.cap + v.hnsw_up.cap;
+            if (v.mrpt_trees) b += v.mrpt_R.cap + v.mrpt_RT.cap + v.mrpt_splits.cap + v.mrpt_leaves.cap + v.mrpt_lf.cap;
+            return b;
+        };
+        uint64_t b = held(h);
+        // the sub-view of the match budget: its row list and what its slot holds, layouts and indices made on it included
+        if ((h.have & kLayBudget) && h.bud_slot < c->imgs.size() && c->imgs[h.bud_slot]) b += h.bud_rows.cap + held(*c->imgs[h.bud_slot]);
         *bytes = b;
     }
     if (ring_uploads) *ring_uploads = c->n_ring_uploads;

@@ -92,6 +92,9 @@ int finalize_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, uint32_t q_str
         if (total <= out_cap) break;
         out_cap = total;                                   // overflow: nothing was lost, run it again with room
     }
+    // r3dm_set_match_budget: matches of sub-views go back into their views' own row numbers here, on the device, before the copy back
+    // and before the device mirror is made
+    if (g && total) { const int rcb = budget_remap(c, jobs, h_cnt.data(), c->d_pair_off.as<uint64_t>(), c->d_pair_cnt.as<uint32_t>(), c->d_out.as<r3dm_match>()); if (rcb != R3DM_OK) return rcb; }
     // the matches come back through the context's page-locked landing buffer on the context's stream (a synchronous hipMemcpy into a
     // fresh pageable vector runs on the null stream, pins the pages on the way and was seen to take 80 ms for 7.7 MB every few calls)
     const r3dm_match* h_m = nullptr;
@@ -419,6 +422,8 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     if (rcp != R3DM_OK) return rcp;
     const float R = squared_metric ? dist_ratio * dist_ratio : dist_ratio;
     { const int rcg = preselect_gate(c, R, none, jobs); if (rcg != R3DM_OK) return rcg; }      // r3dm_set_preemptive_matching
+    BudgetCallGuard budget_guard{c};
+    { const int rcb = budget_substitute(c, none, jobs); if (rcb != R3DM_OK) return rcb; }      // r3dm_set_match_budget
 
     auto g = std::unique_ptr<r3dm_graph>(new r3dm_graph());
     g->offsets.push_back(0);

@@ -282,6 +282,14 @@ extern "C" int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uin
     return rc;
 }
 
+extern "C" int r3dm_multi_set_match_budget(r3dm_multi* m, int enable, uint32_t max_rows)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    int rc = R3DM_OK;
+    for (r3dm_ctx* c : m->ctx) { const int r = r3dm_set_match_budget(c, enable, max_rows); if (r != R3DM_OK) { rc = r; m->err = c->err; } }
+    return rc;
+}
+
 extern "C" int r3dm_multi_set_guided_matching(r3dm_multi* m, int enable, double ratio_F, double ratio_E, double ratio_H)
 {
     if (!m) return R3DM_ERR_INVALID;

@@ -194,6 +194,7 @@ static int r3dm_set_view_priority_impl(r3dm_ctx* c, uint32_t view_id, const floa
         std::vector<float>().swap(v.priority);
     }
     v.have &= ~kLayHead; v.head_h = 0; v.head_n = 0;  // (the buffer stays: the next head of the view reuses it)
+    v.have &= ~kLayBudget; v.bud_N = 0;               // (the match budget's sub-view was selected by the old priority: its slot is refilled)
     return R3DM_OK;
 }
 

@@ -169,6 +169,7 @@ struct Devices {
     void set_guided(bool on, double rF, double rE, double rH) const { (void)call(r3dm_set_guided_matching, r3dm_multi_set_guided_matching, on ? 1 : 0, rF, rE, rH); }
     int set_preemptive(bool on, uint32_t head_rows, uint32_t min_matches) const
     { return call(r3dm_set_preemptive_matching, r3dm_multi_set_preemptive_matching, on ? 1 : 0, head_rows, min_matches); }
+    int set_budget(bool on, uint32_t max_rows) const { return call(r3dm_set_match_budget, r3dm_multi_set_match_budget, on ? 1 : 0, max_rows); }
 
     // the four matchers: `how` is the squared flag of the exhaustive one, the parameters of the others
     using Pairs = std::vector<uint32_t>;
@@ -355,8 +356,9 @@ bool R3DComputeMatches::runFeaturesStage(const R3DFParams& params, const std::st
     const int n_ctx = r3dm_multi_num_devices(feat_multi_);
     (void)r3dm_multi_set_keypoint_detector(feat_multi_, dl[0] == "AKAZE" ? R3DM_DETECTOR_AKAZE : R3DM_DETECTOR_FAST_AKAZE);
     (void)r3dm_multi_set_descriptor_arm(feat_multi_, arm->id);      // (MLDB / M-SURF with "AKAZE": refused by name by the features call below)
-    // the sink carries no scales: while preemptive matching is on, every view is registered from its files (setPreemptiveMatching)
-    const bool direct = direct_registration_ && !preemptive_on_;
+    // the sink carries no scales: while preemptive matching or the match budget is on, every view is registered from its files
+    // (setPreemptiveMatching, setMatchBudget)
+    const bool direct = direct_registration_ && !preemptive_on_ && !budget_on_;
     (void)r3dm_multi_set_features_sink(feat_multi_, direct ? &R3DComputeMatches::features_sink : nullptr, this);
     // the .feat / .desc of a batch are written behind the sink calls, beside the match phase (computeMatches waits for them before it
     // returns): only when the views are registered straight from the device, else Regions_Provider::load reads those files next
@@ -451,6 +453,12 @@ void R3DComputeMatches::setPreemptiveMatching(bool on, uint32_t head_rows, uint3
     preemptive_on_ = on && rc == R3DM_OK;
 }
 
+void R3DComputeMatches::setMatchBudget(bool on, uint32_t max_rows)
+{
+    const int rc = Devices{ctx_, multi_}.set_budget(on, max_rows);
+    budget_on_ = on && rc == R3DM_OK;
+}
+
 void R3DComputeMatches::setPairProposal(bool on, uint32_t n_words, uint32_t top_k)
 {
     proposal_on_ = on && n_words >= 2 && n_words <= R3DM_VOCAB_MAX_WORDS && top_k >= 1;
@@ -480,7 +488,7 @@ bool R3DComputeMatches::loadViews(const std::string& dir)
                 Loaded& L = chunk[(size_t)k];
                 if (registered_[vi + (size_t)k]) { L.ok = true; continue; }
                 // nothing may leave an OpenMP region by exception (std::terminate): a failed allocation is a failed load
-                try { L.ok = load_feat(dir + "/" + u.basename + ".feat", L.xy, preemptive_on_ ? &L.scale : nullptr) && load_desc(dir + "/" + u.basename + ".desc", row_bytes, L.desc, L.n); }
+                try { L.ok = load_feat(dir + "/" + u.basename + ".feat", L.xy, (preemptive_on_ || budget_on_) ? &L.scale : nullptr) && load_desc(dir + "/" + u.basename + ".desc", row_bytes, L.desc, L.n); }
                 catch (...) { L.ok = false; }
             }
             // one device: the chunk's views go to the matcher in ONE call -- up to the first view the per-view pass below will refuse, so
@@ -518,8 +526,8 @@ bool R3DComputeMatches::loadViews(const std::string& dir)
                 errorMessage_ = dev.last_error();
                 return false;
             }
-            // the scale column is the view's priority (r3dm_set_view_priority) while preemptive matching is on
-            if (preemptive_on_ && L.n && dev.set_priority(v.id_view, L.scale) != R3DM_OK) { errorMessage_ = "feature scales of " + v.basename + ": " + dev.last_error(); return false; }
+            // the scale column is the view's priority (r3dm_set_view_priority) while preemptive matching or the match budget is on
+            if ((preemptive_on_ || budget_on_) && L.n && dev.set_priority(v.id_view, L.scale) != R3DM_OK) { errorMessage_ = "feature scales of " + v.basename + ": " + dev.last_error(); return false; }
         }
         if (v.focal_px > 0.0) {
             const double K[9] = {v.focal_px, 0.0, v.ppx, 0.0, v.focal_px, v.ppy, 0.0, 0.0, 1.0};      // Pinhole_Intrinsic::K()
@@ -779,6 +787,7 @@ static void apply_stage_flags(r3d_amd::R3DComputeMatches& stage, uint32_t flags,
     if (mask & R3DM_STAGE_MUTUAL_MATCHING) stage.setMutualMatching(has(R3DM_STAGE_MUTUAL_MATCHING));
     if (mask & R3DM_STAGE_SYMMETRIC_RATIO) stage.setSymmetricRatio(has(R3DM_STAGE_SYMMETRIC_RATIO));
     if (mask & R3DM_STAGE_PREEMPTIVE_MATCHING) stage.setPreemptiveMatching(has(R3DM_STAGE_PREEMPTIVE_MATCHING));
+    if (mask & R3DM_STAGE_MATCH_BUDGET) stage.setMatchBudget(has(R3DM_STAGE_MATCH_BUDGET));
     if (mask & R3DM_STAGE_PAIR_PROPOSAL) stage.setPairProposal(has(R3DM_STAGE_PAIR_PROPOSAL));
 }
 
@@ -876,7 +885,7 @@ extern "C" int r3dm_compute_matches_dir_flags(int device_id, const char* matches
     stage.addViews(vs);
     stage.setRegionsType(dtype, dim);
     stage.setSeed(seed);
-    apply_stage_flags(stage, flags, R3DM_STAGE_F32_TILES | R3DM_STAGE_MUTUAL_MATCHING | R3DM_STAGE_SYMMETRIC_RATIO | R3DM_STAGE_PREEMPTIVE_MATCHING | R3DM_STAGE_PAIR_PROPOSAL);
+    apply_stage_flags(stage, flags, R3DM_STAGE_F32_TILES | R3DM_STAGE_MUTUAL_MATCHING | R3DM_STAGE_SYMMETRIC_RATIO | R3DM_STAGE_PREEMPTIVE_MATCHING | R3DM_STAGE_MATCH_BUDGET | R3DM_STAGE_PAIR_PROPOSAL);
     r3d_amd::R3DFParams params;
     params.distRatio_ = dist_ratio;
     params.computeFundalmentalMatrix_ = compute_F != 0;

@@ -4,6 +4,7 @@
 //                     every finalisation into a graph (finalize_batch), one certificate slack
 //                     (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
 //   api_preselect.cpp preemptive matching: view priorities, heads, the gate behind resolve_pairs, r3dm_preselect_pairs
+//   api_budget.cpp    the match budget: device selection of a view's rows, sub-view slots, the substitution behind the gate, the remap
 //   api_vocab.cpp     pair proposal: vocabularies, view signatures through the exhaustive matcher, scores, top-k selection
 //   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
@@ -228,6 +229,7 @@ enum : uint32_t {
     kLayCounts = 8u,     // count tiles + scale order (r3dm_set_split_mfma, rows = integer votes x a row scale); needs kLayRows
     kLayBin8   = 16u,    // one byte per bit in i8 fragment order (r3dm_set_hamming_mfma)
     kLayHead   = 32u,    // the head rows of preemptive matching, row-major (api_preselect.cpp: ensure_heads, not ensure_layouts)
+    kLayBudget = 64u,    // the sub-view of the match budget: row list + a slot of its own (api_budget.cpp: budget_substitute)
 };
 
 // the count tiles exist only for f32 views of at most 256 dimensions (anything else is never votes x scale: counts_ok stays false)
@@ -255,6 +257,7 @@ struct ViewState {
     uint32_t mrpt_trees = 0, mrpt_depth = 0; float mrpt_density = 0.0f; uint64_t mrpt_seed = 0;          // MRPT index, valid when mrpt_trees != 0
     std::vector<float> priority;      // r3dm_set_view_priority: one per row, or empty
     uint32_t head_h = 0, head_n = 0;  // kLayHead: the head size the head buffer was made for, and its rows (min(head_h, n))
+    uint32_t bud_N = 0;               // kLayBudget: the budget the sub-view was made for
     uint64_t serial = 0;              // this registration's number, unique in the process (new_tenant); 0: no tenant.  Keys what outlives
                                       // a registration outside the context: the signatures of an r3dm_vocab (api_vocab.cpp)
 };
@@ -266,12 +269,15 @@ inline std::atomic<uint64_t> g_view_serial{0};
 //   has_K, Kinv      the view's intrinsics (r3dm_set_intrinsics): survive a re-registration of the view, forgotten by clear()
 //   index buffers    ann_*, hnsw_*, mrpt_*: survive a new tenant (a rebuild reuses them), given back by clear() (rebuilt per collection:
 //                    a context that once held a 1000-view collection must not sit on their gigabytes)
+//   bud_slot         the slot of the view's sub-view (match budget): survives a new tenant (the sub-view is remade there), forgotten by
+//                    clear() -- the sub-view's slot is a slot of the table like any other and is cleared with it
 //   layout buffers   rows .. canon: survive both (a cleared view is a spare whose buffers serve the next collection), freed by release()
 //   borrowed, owner  a mounted r3dm_index (mount): the buffers are aliases of the index's, never freed here
 struct HostImage : ViewState {
     bool borrowed = false;
     struct r3dm_index* owner = nullptr;   // (layouts staged on first use are added to the index, under its lock)
-    DevBuf rows, tiled, tiled16, tiledh, tiledc, tiledp, cscale, cquad, cperm, tiled8, norms, bin, xy, canon, head;
+    DevBuf rows, tiled, tiled16, tiledh, tiledc, tiledp, cscale, cquad, cperm, tiled8, norms, bin, xy, canon, head, bud_rows;
+    uint32_t bud_slot = 0xFFFFFFFFu;      // match budget: the slot that holds this view's sub-view (bud_rows: its row list), or none
     DevBuf ann_adj, ann_deg, ann_rows16, ann_rows8;   // graph index; compact row copies only for bf16- / u8-exact views
     DevBuf hnsw_l0, hnsw_up_off, hnsw_up;             // hnswlib's arrays (kernels_hnsw.hip: HnswView)
     DevBuf mrpt_R, mrpt_RT, mrpt_splits, mrpt_leaves, mrpt_lf;      // kernels_mrpt.hip: MrptView
@@ -279,7 +285,7 @@ struct HostImage : ViewState {
     double Kinv[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     // the layout buffers of a view registered with a context are blocks of the context's arena (an r3dm_index owns plain allocations:
     // it outlives contexts)
-    std::array<DevBuf*, 15> layout_bufs() { return {&rows, &tiled, &tiled16, &tiledh, &tiledc, &tiledp, &cscale, &cquad, &cperm, &tiled8, &norms, &bin, &xy, &canon, &head}; }
+    std::array<DevBuf*, 16> layout_bufs() { return {&rows, &tiled, &tiled16, &tiledh, &tiledc, &tiledp, &cscale, &cquad, &cperm, &tiled8, &norms, &bin, &xy, &canon, &head, &bud_rows}; }
     void use_arena(DevArena* a) { for (DevBuf* x : layout_bufs()) x->arena = a; }
     void new_tenant(uint32_t id, uint32_t n_, uint32_t dim_, r3dm_dtype dtype_, uint32_t width_, uint32_t height_, bool xy)
     {
@@ -292,7 +298,7 @@ struct HostImage : ViewState {
         DevBuf* b[] = {&ann_adj, &ann_deg, &ann_rows16, &ann_rows8, &hnsw_l0, &hnsw_up_off, &hnsw_up, &mrpt_R, &mrpt_RT, &mrpt_splits, &mrpt_leaves, &mrpt_lf};
         for (DevBuf* x : b) x->release();
         static_cast<ViewState&>(*this) = ViewState();
-        has_K = false;
+        has_K = false; bud_slot = 0xFFFFFFFFu;
     }
     void release()
     {
@@ -591,6 +597,16 @@ struct r3dm_ctx {
     PinBuf pre_pin;
     hipEvent_t pre_ev0 = nullptr, pre_ev1 = nullptr;
     r3dm_preselect_stats preselect_stats{};
+    // r3dm_set_match_budget (api_budget.cpp): the switch and its N; the buffers of a substitution (priorities and selection jobs, the
+    // gathered rows on their way into a sub-view slot, the row-list table the remap reads), its events and its report -- all made by
+    // the first call that budgets a view
+    bool budget_on = false;
+    uint32_t budget_N = 8192;
+    DevBuf bud_jobs, bud_prio, bud_raw, bud_maps, bud_sel;
+    PinBuf bud_pin;
+    hipEvent_t bud_ev[2] = {nullptr, nullptr};
+    bool bud_maps_live = false;                              // bud_maps holds the table of the running collection call: its batches are remapped
+    r3dm_budget_stats budget_stats{};
     bool device_graphs = false;                             // r3dm_set_device_graphs: match / filter results keep a device mirror (GraphDev)
     DevBuf g_segs;                                          // segment table of the graph gather kernel (kernels_graph.hip)
     uint32_t liop_npix = 0;
@@ -770,6 +786,15 @@ int resolve_pairs(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t n_pairs, const
 // report; while the switch is on, both lists keep only the pairs whose head count reaches the threshold under ratio R
 // (bin_ratio_R >= 0: the R of pairs of binary views, where a call's list may mix them with float views under another rule)
 int preselect_gate(r3dm_ctx* c, float ratio_R, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned, float bin_ratio_R = -1.0f);
+// the match budget (api_budget.cpp), called by the four collection entries right after the gate: resets the report; while the switch is
+// on, every job's sI / sJ whose view has more rows than the budget becomes the slot of the view's sub-view (made here when missing or
+// stale; I / J stay), and with a classifier the jobs are dealt again between the two lists by their sub-views.  finalize_batch calls
+// budget_remap on the device's match array of every batch of such a call, before the copy back and the device mirror.
+int budget_substitute(r3dm_ctx* c, std::vector<PairJob>& indexed, std::vector<PairJob>& scanned, const PairClassifier& classify = nullptr);
+int budget_remap(r3dm_ctx* c, const std::vector<PairJob>& jobs, const uint32_t* pair_cnt_host, const uint64_t* pair_off_dev,
+                 const uint32_t* pair_cnt_dev, r3dm_match* matches_dev);       // (the pair table of the batch is in c->d_pairs)
+// ends the call's remapping on every exit of a collection entry
+struct BudgetCallGuard { r3dm_ctx* c; ~BudgetCallGuard() { c->bud_maps_live = false; } };
 // What a collection call of an arm is made of.  The chunk rules differ on purpose: KGraph and HNSW launch one descriptor length at a
 // time, MRPT's job records carry their own; HNSW and MRPT launch a grid row per pair (65,535 at most), KGraph does not.
 struct AnnArm {

@@ -300,8 +300,34 @@ struct HeadMatchParams {
     float           ratio_R;      // ratio^2 (squared metric) or ratio
 };
 
+// the match budget (kernels_match_budget.hip; r3dm_set_match_budget, r3dm_budget_rows): a view of more than N rows is matched through
+// a sub-view of its N highest-priority rows, staged in a slot of its own; matches come back through the sub-view's row list
+constexpr uint32_t kBudgetChunk = 256;              // rows per step of the selection's compaction; R3DM_BUDGET_SELECT_CHUNK
+struct BudgetSelectJob {
+    const float* priority;        // one per row, finite and >= 0 (-0.0 stored as +0.0); null: the first rows
+    uint32_t     n, N;            // rows of the view, the budget
+    uint32_t*    rows_out;        // [min(N, n)] ascending
+};
+struct BudgetGatherArgs {
+    const void*     src;          // fragment-order f32 tiles (F32 / U8 views) or word rows (BIN views)
+    const uint32_t* rows;         // the listed rows
+    uint32_t        n, hn, dim;   // rows of the view, rows listed, elements per row as registered (BIN: bytes)
+    uint32_t        per_row;      // float4 per padded row (2 G) / words per row
+    int             dtype;        // r3dm_dtype of the view: the element type of `out`
+    void*           out;          // [hn][dim] row-major
+    const float*    xy; float* xy_out;      // positions of the view (null: none) -> [hn][2]
+};
+struct BudgetMap { const uint32_t* rows; uint32_t n; };      // by slot: the row list of a sub-view slot, null for every other slot
+struct BudgetRemapParams {
+    const BudgetMap* maps;
+    const uint2*     pairs;       // slots of the batch's pairs (one workgroup each)
+    const uint64_t*  pair_off;    // FinalizeParams::pair_off / pair_cnt
+    const uint32_t*  pair_cnt;
+    r3dm_match*      matches;     // FinalizeParams::out
+};
+
 // pair proposal from bag-of-words view signatures (kernels_vocab.hip; r3dm_propose_pairs, r3dm_view_signatures)
-constexpr uint32_t kVocabHistLdsWords = 8192;       // largest vocabulary whose histogram a workgroup privatises in LDS (32 KiB); R3DM_VOCAB_HIST_LDS_WORDS
+constexpr uint32_t kVocabHistLdsWords = 8192;      // largest vocabulary whose histogram a workgroup privatises in LDS (32 KiB); R3DM_VOCAB_HIST_LDS_WORDS
 constexpr uint32_t kVocabTile = 64;                 // views per side of a score tile
 constexpr uint32_t kVocabChunk = 32;                // words of a score tile's LDS stage; R3DM_VOCAB_WORD_CHUNK
 struct VocabHistJob {
@@ -599,6 +625,11 @@ hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t
 // one workgroup per pair (G of 8 / 16 / 18 / 32, or 8 / 16 words)
 hipError_t launch_head_gather(hipStream_t st, const void* src, const uint32_t* rows, uint32_t hn, uint32_t per_row, bool binary, void* out);
 hipError_t launch_head_match(hipStream_t st, const HeadMatchParams& P, uint32_t n_pairs, bool binary, uint32_t G_or_words);
+// the match budget: one workgroup per job selects a view's rows; the listed rows and positions of one view -> row-major arrays; the
+// matches of a finalised batch back into the views' own row numbers (one workgroup per pair)
+hipError_t launch_budget_select(hipStream_t st, const BudgetSelectJob* jobs_dev, uint32_t n_jobs);
+hipError_t launch_budget_gather(hipStream_t st, const BudgetGatherArgs& A);
+hipError_t launch_budget_remap(hipStream_t st, const BudgetRemapParams& P, uint32_t n_pairs);
 hipError_t launch_vocab_hist(hipStream_t st, const VocabHistJob* jobs, uint32_t n_jobs, uint32_t max_n, uint32_t n_words);
 hipError_t launch_vocab_intersect(hipStream_t st, const VocabScoreParams& P, uint32_t n_slices);
 hipError_t launch_vocab_select(hipStream_t st, const VocabSelectParams& P);
