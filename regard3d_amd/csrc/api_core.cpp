@@ -772,14 +772,14 @@ extern "C" int r3dm_set_prefix_pruning(r3dm_ctx* c, int enable)
 extern "C" int r3dm_get_prefix_pruning_counts(r3dm_ctx* c, uint64_t out[2])
 {
     if (!c || !out) return R3DM_ERR_INVALID;
-    out[0] = c->prune_counts[0]; out[1] = c->prune_counts[1];
+    out[0] = c->prune_totals.tested; out[1] = c->prune_totals.pruned;
     return R3DM_OK;
 }
 
 extern "C" int r3dm_get_pair_filter_counts(r3dm_ctx* c, uint64_t* out)
 {
     if (!c || !out) return R3DM_ERR_INVALID;
-    *out = c->prune_counts[2];
+    *out = c->prune_totals.filtered;
     return R3DM_OK;
 }
 
@@ -793,14 +793,14 @@ extern "C" int r3dm_set_half_filter(r3dm_ctx* c, int enable)
 extern "C" int r3dm_get_half_filter_counts(r3dm_ctx* c, uint64_t* out)
 {
     if (!c || !out) return R3DM_ERR_INVALID;
-    *out = c->half_count;
+    *out = c->prune_totals.half;
     return R3DM_OK;
 }
 
 extern "C" int r3dm_get_level2_skip_counts(r3dm_ctx* c, uint64_t* out)
 {
     if (!c || !out) return R3DM_ERR_INVALID;
-    *out = c->level2_skip_count;
+    *out = c->prune_totals.skipped;
     return R3DM_OK;
 }
 

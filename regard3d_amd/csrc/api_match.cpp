@@ -193,8 +193,79 @@ static float cert_slack_factor(uint32_t G, bool split_or_count_tiles)
     return split_or_count_tiles ? (3.0f * dpad + 36.0f) * 2.3841858e-07f : 4.25f * dpad * 5.9604645e-08f;
 }
 
+// The pair-norm tiles the pruning kernel's filter reads (with `halves`, their f16 form for the level in front) and the tables of them
+// by slot, whose addresses go into `hdr` (device).  The tiles are scratch of the call, not a layout of a view: made here from the f32
+// tiles of the batch's views (one small kernel per view: 4 MB read, 2 MB written at 8192 rows) into one buffer of the context, which
+// the next batch overwrites.  A view therefore holds what it held (r3dm_view_info), and nothing has to follow the views' lifecycle.
+// tr: the host side of the asynchronous copies, the caller keeps it to the end of the call.
+static int stage_pairnorm_scratch(r3dm_ctx* c, const std::vector<uint32_t>& batch_slots, uint32_t G, bool halves, PruneHeader* hdr,
+                                  std::vector<uint64_t>& tr)
+{
+    constexpr size_t kPad = 4096;                          // the filter's window runs two groups (2 KiB) past a view's last tile
+    constexpr size_t kPadH = 8192;                         // the f16 level's window runs four blocks (4 KiB) past a view's last f16 tile
+    // per view: its f32 pair-norm tiles and, with the f16 level, its f16 tiles behind them (a quarter of the f32 tiles' bytes)
+    const size_t nslots = c->imgs.size();
+    size_t total = 0;
+    for (uint32_t s : batch_slots)
+        total += (size_t)c->imgs[s]->n_tiles * (G / 2) * 1024 + kPad + (halves ? (size_t)c->imgs[s]->n_tiles * (G / 4) * 1024 + kPadH : 0);
+    R3DM_HIP(c, c->d_pairnorm_tiles.ensure(total));
+    tr.assign(2 * nslots + 2, 0);                          // [slots: f32 tiles][slots: f16 tiles][the two tables' addresses]
+    size_t at = 0;
+    for (uint32_t s : batch_slots) {
+        const HostImage& h = *c->imgs[s];
+        float* dst = reinterpret_cast<float*>(c->d_pairnorm_tiles.as<unsigned char>() + at);
+        at += (size_t)h.n_tiles * (G / 2) * 1024 + kPad;
+        uint16_t* dsth = halves ? reinterpret_cast<uint16_t*>(c->d_pairnorm_tiles.as<unsigned char>() + at) : nullptr;
+        if (halves) at += (size_t)h.n_tiles * (G / 4) * 1024 + kPadH;
+        R3DM_HIP(c, launch_stage_pairnorm(c->stream, h.tiled.as<float>(), h.G, h.n_tiles, dst, dsth));
+        tr[s] = (uint64_t)(uintptr_t)dst;
+        tr[nslots + s] = (uint64_t)(uintptr_t)dsth;
+    }
+    // the tables of the tiles by slot, and their addresses in the header
+    R3DM_HIP(c, c->d_pairnorm.ensure(8 * 2 * nslots));
+    tr[2 * nslots] = (uint64_t)(uintptr_t)c->d_pairnorm.p;
+    tr[2 * nslots + 1] = (uint64_t)(uintptr_t)(c->d_pairnorm.as<uint64_t>() + nslots);
+    R3DM_HIP(c, hipMemcpyAsync(c->d_pairnorm.p, tr.data(), 8 * 2 * nslots, hipMemcpyHostToDevice, c->stream));
+    static_assert(sizeof hdr->pairnorm == 8 && sizeof hdr->halfnorm == 8, "a table's address is one 64-bit word of tr");
+    R3DM_HIP(c, hipMemcpyAsync(&hdr->pairnorm, &tr[2 * nslots], sizeof hdr->pairnorm, hipMemcpyHostToDevice, c->stream));
+    if (halves) R3DM_HIP(c, hipMemcpyAsync(&hdr->halfnorm, &tr[2 * nslots + 1], sizeof hdr->halfnorm, hipMemcpyHostToDevice, c->stream));
+    return R3DM_OK;
+}
+
+// The exact scan of the queries the nominator could not certify: per pair and slice of image I, and per query for the whole batch
+// where a pair's list overflowed (FbHeader::fb_total[1]) or the descriptor length has a scalar tail.
+static int rescan_uncertified(r3dm_ctx* c, MatchParams& mp, const std::vector<uint32_t>& batch_slots, const HostImage& first,
+                              uint32_t max_nI, uint64_t total_slots, bool overflowed)
+{
+    const uint32_t P = mp.n_pairs;
+    bool rescan = overflowed;                              // some pair overflowed its list
+    if ((first.dim & 3u) == 0) {
+        // a pair's uncertified queries are scanned by one workgroup per ~1024 rows of image I (at most 64): few pairs with
+        // long views (24 views of 28 k rows: 276 workgroups of 7.7 ms each) otherwise leave the chip idle behind one round,
+        // and a workgroup walks its rows tile by tile behind two barriers each (4096 rows per workgroup: 3.9 ms on those views)
+        uint32_t S = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (max_nI + 1023u) / 1024u));
+        while (S > 1 && (uint64_t)P * S > 65535ull * 4) --S;
+        mp.fb_slices = S; mp.fb_part = nullptr; mp.fb_done = nullptr;
+        if (S > 1) {
+            R3DM_HIP(c, c->d_fb2.ensure((size_t)P * kFbPerPair * S * 16 + (size_t)P * 4 + 64));
+            mp.fb_part = c->d_fb2.as<float4>();
+            mp.fb_done = reinterpret_cast<uint32_t*>(c->d_fb2.as<unsigned char>() + (size_t)P * kFbPerPair * S * 16);
+            R3DM_HIP(c, hipMemsetAsync(mp.fb_done, 0, (size_t)P * 4, c->stream));
+        }
+        R3DM_HIP(c, launch_l2_exact_batch(c->stream, mp, first.G));
+    }
+    else rescan = true;                                    // scalar-tail dims: generic exact kernel
+    if (rescan) {
+        if (total_slots > 0xFFFFFFFFull) { c->err = "batch too large for the exact rescan"; return R3DM_ERR_UNSUPPORTED; }
+        { const int rcl = ensure_layouts(c, batch_slots, kLayRows); if (rcl != R3DM_OK) return rcl; }      // the per-query scan reads row-major rows
+        R3DM_HIP(c, launch_l2_exact_items(c->stream, mp, (uint32_t)total_slots, 2));
+    }
+    return R3DM_OK;
+}
+
 // runs the 2-NN + ratio kernels over `jobs` (slot pairs, all of one dtype/dim) and appends the
 // non-empty results to `g` in job order.  knn_idx/knn_dist (host, optional) receive the raw 2-NN.
+// prepare -> plan -> stage -> launch -> rescan -> finalize.
 int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R, r3dm_graph* g,
                     int32_t* knn_idx_host, float* knn_dist_host)
 {
@@ -249,11 +320,9 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     R3DM_HIP(c, hipMemcpyAsync(c->d_pairs.p, hp.data(), sizeof(uint2) * P, hipMemcpyHostToDevice, c->stream));
     R3DM_HIP(c, c->d_nn.ensure((size_t)P * q_stride * 4));
     const uint64_t total_slots = (uint64_t)P * q_stride;
-    // per-pair lists of uncertified queries: [fb_total(2 words) | pad | the pruning kernels' words][fb_cnt: P][fb_q: P x kFbPerPair]
-    constexpr size_t kFbHeader = 24;                       // words: fb_total [0, 2), pad, MatchParams::prune_cnt's seven slots [4, 18), pad
-    const size_t fb_words = kFbHeader + (size_t)P + (size_t)P * kFbPerPair;
-    R3DM_HIP(c, c->d_fb.ensure(fb_words * 4));
-    R3DM_HIP(c, hipMemsetAsync(c->d_fb.p, 0, (kFbHeader + (size_t)P) * 4, c->stream));
+    // per-pair lists of uncertified queries: [FbHeader][fb_cnt: P][fb_q: P x kFbPerPair]; the header and the counts start at zero
+    R3DM_HIP(c, c->d_fb.ensure(sizeof(FbHeader) + ((size_t)P + (size_t)P * kFbPerPair) * 4));
+    R3DM_HIP(c, hipMemsetAsync(c->d_fb.p, 0, sizeof(FbHeader) + (size_t)P * 4, c->stream));
     R3DM_HIP(c, c->d_cnt.ensure(64));
     R3DM_HIP(c, hipMemsetAsync(c->d_cnt.p, 0, 64, c->stream));
     if (knn_idx_host) {
@@ -274,46 +343,16 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     mp.nn_idx = c->d_nn.as<uint32_t>();
     mp.knn_idx = knn_idx_host ? c->d_knn_idx.as<int32_t>() : nullptr;
     mp.knn_dist = knn_idx_host ? c->d_knn_dist.as<float>() : nullptr;
-    mp.fb_total = c->d_fb.as<uint32_t>();
-    mp.fb_cnt = c->d_fb.as<uint32_t>() + kFbHeader;
-    mp.fb_q = c->d_fb.as<uint32_t>() + kFbHeader + P;
-    // (words 4 .. 17 of the zeroed header: the 64-bit counters of the pruning kernels and their tables' addresses)
+    FbHeader* const fbh = c->d_fb.as<FbHeader>();
+    mp.fb_total = fbh->fb_total;
+    mp.fb_cnt = reinterpret_cast<uint32_t*>(fbh + 1);
+    mp.fb_q = mp.fb_cnt + P;
     const bool halves = prunes && c->half_filter;          // the f16 level in front of the filter (r3dm_set_half_filter)
     mp.prune = c->prefix_pruning ? (halves ? 3u : 1u) : 0u;
-    mp.prune_cnt = reinterpret_cast<unsigned long long*>(c->d_fb.as<uint32_t>() + 4);
-    // The pair-norm tiles are scratch of this call, not a layout of a view: made here from the f32 tiles of the batch's views (one
-    // small kernel per view: 4 MB read, 2 MB written at 8192 rows) into one buffer of the context, which the next batch overwrites.
-    // A view therefore holds what it held (r3dm_view_info), and nothing has to follow the views' lifecycle.
-    std::vector<uint64_t> tr;                              // (lives to the end of the call, like hp: the copies below are asynchronous)
-    if (prunes) {
-        constexpr size_t kPad = 4096;                      // the filter's window runs two groups (2 KiB) past a view's last tile
-        constexpr size_t kPadH = 8192;                     // the f16 level's window runs four blocks (4 KiB) past a view's last f16 tile
-        // per view: its f32 pair-norm tiles and, with the f16 level, its f16 tiles behind them (a quarter of the f32 tiles' bytes)
-        const size_t nslots = c->imgs.size();
-        size_t total = 0;
-        for (uint32_t s : batch_slots)
-            total += (size_t)c->imgs[s]->n_tiles * (first.G / 2) * 1024 + kPad + (halves ? (size_t)c->imgs[s]->n_tiles * (first.G / 4) * 1024 + kPadH : 0);
-        R3DM_HIP(c, c->d_pairnorm_tiles.ensure(total));
-        tr.assign(2 * nslots + 2, 0);                      // [slots: f32 tiles][slots: f16 tiles][the two tables' addresses]
-        size_t at = 0;
-        for (uint32_t s : batch_slots) {
-            const HostImage& h = *c->imgs[s];
-            float* dst = reinterpret_cast<float*>(c->d_pairnorm_tiles.as<unsigned char>() + at);
-            at += (size_t)h.n_tiles * (first.G / 2) * 1024 + kPad;
-            uint16_t* dsth = halves ? reinterpret_cast<uint16_t*>(c->d_pairnorm_tiles.as<unsigned char>() + at) : nullptr;
-            if (halves) at += (size_t)h.n_tiles * (first.G / 4) * 1024 + kPadH;
-            R3DM_HIP(c, launch_stage_pairnorm(c->stream, h.tiled.as<float>(), h.G, h.n_tiles, dst, dsth));
-            tr[s] = (uint64_t)(uintptr_t)dst;
-            tr[nslots + s] = (uint64_t)(uintptr_t)dsth;
-        }
-        // the tables of the tiles by slot, and their addresses behind the counters (MatchParams::prune_cnt [3] and [5])
-        R3DM_HIP(c, c->d_pairnorm.ensure(8 * 2 * nslots));
-        tr[2 * nslots] = (uint64_t)(uintptr_t)c->d_pairnorm.p;
-        tr[2 * nslots + 1] = (uint64_t)(uintptr_t)(c->d_pairnorm.as<uint64_t>() + nslots);
-        R3DM_HIP(c, hipMemcpyAsync(c->d_pairnorm.p, tr.data(), 8 * 2 * nslots, hipMemcpyHostToDevice, c->stream));
-        R3DM_HIP(c, hipMemcpyAsync(mp.prune_cnt + 3, &tr[2 * nslots], 8, hipMemcpyHostToDevice, c->stream));
-        if (halves) R3DM_HIP(c, hipMemcpyAsync(mp.prune_cnt + 5, &tr[2 * nslots + 1], 8, hipMemcpyHostToDevice, c->stream));
-    }
+    mp.prune_cnt = &fbh->prune;
+    // ---- stage: the pruning kernel's tables
+    std::vector<uint64_t> tr;                              // (lives to the end of the call, like hp: the copies from it are asynchronous)
+    if (prunes) { const int rcs = stage_pairnorm_scratch(c, batch_slots, first.G, halves, mp.prune_cnt, tr); if (rcs != R3DM_OK) return rcs; }
 
     const double t_dbg1 = now_ms();
     R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -347,38 +386,23 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
             if (plan.path == BatchPath::kIntegerTiles) c->stats.n_integer_mfma += 1;
         }
         R3DM_HIP(c, hipEventRecord(c->ev1, c->stream));
-        uint32_t fbt[2] = {0, 0};
-        R3DM_HIP(c, c->pin_small.ensure(72));
-        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, mp.fb_total, 72, hipMemcpyDeviceToHost, c->stream));
+        // the header comes back up to its last counter: the uncertified queries, and this batch's share of the call's pruning totals
+        constexpr size_t kRead = offsetof(FbHeader, prune) + sizeof(PruneHeader);
+        R3DM_HIP(c, c->pin_small.ensure(kRead));
+        R3DM_HIP(c, hipMemcpyAsync(c->pin_small.p, fbh, kRead, hipMemcpyDeviceToHost, c->stream));
         R3DM_HIP(c, hipStreamSynchronize(c->stream));
-        memcpy(fbt, c->pin_small.p, 8);
-        { uint64_t pc[3]; memcpy(pc, (const unsigned char*)c->pin_small.p + 16, 24); for (int k = 0; k < 3; ++k) c->prune_counts[k] += pc[k]; }
-        { uint64_t hc; memcpy(&hc, (const unsigned char*)c->pin_small.p + 48, 8); c->half_count += hc; }      // (prune_cnt[4]; [3] is the table's address)
-        { uint64_t sc; memcpy(&sc, (const unsigned char*)c->pin_small.p + 64, 8); c->level2_skip_count += sc; }      // (prune_cnt[6]; [5] is the f16 table's address)
-        n_fallback = fbt[0];
-        if (fbt[0] > 0) {
-            bool rescan = fbt[1] > 0;                      // some pair overflowed its list
-            if ((first.dim & 3u) == 0) {
-                // a pair's uncertified queries are scanned by one workgroup per ~1024 rows of image I (at most 64): few pairs with
-                // long views (24 views of 28 k rows: 276 workgroups of 7.7 ms each) otherwise leave the chip idle behind one round,
-                // and a workgroup walks its rows tile by tile behind two barriers each (4096 rows per workgroup: 3.9 ms on those views)
-                uint32_t S = std::min<uint32_t>(64u, std::max<uint32_t>(1u, (max_nI + 1023u) / 1024u));
-                while (S > 1 && (uint64_t)P * S > 65535ull * 4) --S;
-                mp.fb_slices = S; mp.fb_part = nullptr; mp.fb_done = nullptr;
-                if (S > 1) {
-                    R3DM_HIP(c, c->d_fb2.ensure((size_t)P * kFbPerPair * S * 16 + (size_t)P * 4 + 64));
-                    mp.fb_part = c->d_fb2.as<float4>();
-                    mp.fb_done = reinterpret_cast<uint32_t*>(c->d_fb2.as<unsigned char>() + (size_t)P * kFbPerPair * S * 16);
-                    R3DM_HIP(c, hipMemsetAsync(mp.fb_done, 0, (size_t)P * 4, c->stream));
-                }
-                R3DM_HIP(c, launch_l2_exact_batch(c->stream, mp, first.G));
-            }
-            else rescan = true;                            // scalar-tail dims: generic exact kernel
-            if (rescan) {
-                if (total_slots > 0xFFFFFFFFull) { c->err = "batch too large for the exact rescan"; return R3DM_ERR_UNSUPPORTED; }
-                { const int rcl = ensure_layouts(c, batch_slots, kLayRows); if (rcl != R3DM_OK) return rcl; }      // the per-query scan reads row-major rows
-                R3DM_HIP(c, launch_l2_exact_items(c->stream, mp, (uint32_t)total_slots, 2));
-            }
+        FbHeader hd{};
+        memcpy(&hd, c->pin_small.p, kRead);
+        c->prune_totals.tested += hd.prune.n_tested;
+        c->prune_totals.pruned += hd.prune.n_pruned;
+        c->prune_totals.filtered += hd.prune.n_filtered;
+        c->prune_totals.half += hd.prune.n_half;
+        c->prune_totals.skipped += hd.prune.n_skip;
+        n_fallback = hd.fb_total[0];
+        // ---- rescan
+        if (hd.fb_total[0] > 0) {
+            const int rcr = rescan_uncertified(c, mp, batch_slots, first, max_nI, total_slots, hd.fb_total[1] > 0);
+            if (rcr != R3DM_OK) return rcr;
         }
     } else {
         // descriptor length without a tensor kernel: exact scan of every query (slow, still on the GPU)
@@ -414,8 +438,7 @@ static int r3dm_match_pairs_impl(r3dm_ctx* c, const uint32_t* pairs_ij, uint64_t
     R3DM_HIP(c, hipSetDevice(c->device));
     c->stats = r3dm_stats{};
     c->symratio_counts[0] = c->symratio_counts[1] = c->symratio_counts[2] = 0;
-    c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;
-    c->half_count = 0; c->level2_skip_count = 0;
+    c->prune_totals = {};
     const double t_call = now_ms();
     std::vector<PairJob> jobs, none;
     const int rcp = resolve_pairs(c, pairs_ij, n_pairs, nullptr, none, jobs);
@@ -469,8 +492,7 @@ static int r3dm_knn2_impl(r3dm_ctx* c, const void* dataset, uint32_t n_dataset, 
     if (n_query < 1 || n_dataset < 2) return R3DM_ERR_INVALID;      // ArrayMatcherBruteForce: NN > nbRows / nbQuery < 1
     if (dtype == R3DM_BIN && !(((dim + 3) / 4) == 8 || ((dim + 3) / 4) == 16)) return R3DM_ERR_UNSUPPORTED;
     R3DM_HIP(c, hipSetDevice(c->device));
-    c->half_count = 0; c->level2_skip_count = 0;
-    c->prune_counts[0] = c->prune_counts[1] = c->prune_counts[2] = 0;            // (a raw 2-NN never prunes: the counters of this call read 0 / 0)
+    c->prune_totals = {};                                  // (a raw 2-NN never prunes: the counters of this call read 0 / 0)
     PrivateSlots s(c, 2);
     int rc = stage_into_slot(c, s[0], 0, 0, 0, dataset, n_dataset, dim, dtype, nullptr);
     if (rc == R3DM_OK) rc = stage_into_slot(c, s[1], 0, 0, 0, query, n_query, dim, dtype, nullptr);

@@ -212,7 +212,7 @@ extern "C" int r3dm_multi_get_prefix_pruning_counts(r3dm_multi* m, uint64_t out[
 {
     if (!m || !out) return R3DM_ERR_INVALID;
     out[0] = out[1] = 0;
-    for (r3dm_ctx* c : m->ctx) { out[0] += c->prune_counts[0]; out[1] += c->prune_counts[1]; }
+    for (r3dm_ctx* c : m->ctx) { out[0] += c->prune_totals.tested; out[1] += c->prune_totals.pruned; }
     return R3DM_OK;
 }
 
@@ -220,7 +220,7 @@ extern "C" int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out)
 {
     if (!m || !out) return R3DM_ERR_INVALID;
     *out = 0;
-    for (r3dm_ctx* c : m->ctx) *out += c->prune_counts[2];
+    for (r3dm_ctx* c : m->ctx) *out += c->prune_totals.filtered;
     return R3DM_OK;
 }
 
@@ -235,7 +235,7 @@ extern "C" int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out)
 {
     if (!m || !out) return R3DM_ERR_INVALID;
     *out = 0;
-    for (r3dm_ctx* c : m->ctx) *out += c->half_count;
+    for (r3dm_ctx* c : m->ctx) *out += c->prune_totals.half;
     return R3DM_OK;
 }
 
@@ -243,7 +243,7 @@ extern "C" int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out)
 {
     if (!m || !out) return R3DM_ERR_INVALID;
     *out = 0;
-    for (r3dm_ctx* c : m->ctx) *out += c->level2_skip_count;
+    for (r3dm_ctx* c : m->ctx) *out += c->prune_totals.skipped;
     return R3DM_OK;
 }
 

@@ -258,7 +258,7 @@ hipError_t launch_stage_bf16(hipStream_t st, const float* tiled, uint32_t G, uin
     return hipGetLastError();
 }
 
-// pair-norm tiles of the cascade's filter (l2_knn2_cascade_kernel): [tile][G / 2 groups][2][32][4] f32 in the fragment order of
+// pair-norm tiles of the cascade's filter (l2_knn2_half_kernel): [tile][G / 2 groups][2][32][4] f32 in the fragment order of
 // `tiled`, element k of a row = an upper bound of sqrt(x[2k]^2 + x[2k+1]^2).  Dimensions 2k and 2k+1 share a float4 of `tiled`.
 // The bound: x^2 and y^2 are exact in double (24-bit significands), their sum s and its root rd carry one rounding each, so
 // rd >= (1 - 2^-52) |(x, y)| (2^-50 if the root were off by a few ulps); f = (float)rd rounded to nearest is kept only if
@@ -328,21 +328,10 @@ void l2_knn2_mfma_kernel(const MatchParams P)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
-    // workgroup -> (pair, query block).  Workgroups are dealt round-robin to the 8 XCDs, each with its own L2; with
-    // xcd_map every workgroup of a pair runs on ONE XCD (pair p on XCD p % 8), so image I and the query tiles are pulled
-    // into one L2 instead of eight (pairs are sorted by I: an XCD's consecutive pairs mostly share their dataset image).
-    // (Written out in every 2-NN nominator, like the query load and the drain below: as shared functions they change the
-    // kernels' machine code, DESIGN.md 4.19.  The host side is pair_grid.)
+    // (the query load and the drain below stay written out in every 2-NN nominator: as shared functions they change the kernels'
+    //  machine code)
     uint32_t pair, qb;
-    if (P.xcd_map) {
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
+    if (!workgroup_pair(P, pair, qb)) return;
     const uint2 pr = P.pairs[pair];
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
@@ -462,17 +451,8 @@ void l2_knn2_prune_kernel(const MatchParams P)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
-    // workgroup -> (pair, query block): as in l2_knn2_mfma_kernel
     uint32_t pair, qb;
-    if (P.xcd_map) {
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
+    if (!workgroup_pair(P, pair, qb)) return;
     const uint2 pr = P.pairs[pair];
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
@@ -598,21 +578,10 @@ void l2_knn2_prune_kernel(const MatchParams P)
         pruned_lb[nj] = dead ? -R3DM_INF : x - __builtin_fabsf(x) * 2.384185791015625e-07f;
     }
     if (lane == 0 && n_tested) {
-        atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
-        if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
+        atomicAdd(&P.prune_cnt->n_tested, (unsigned long long)n_tested);
+        if (n_pruned) atomicAdd(&P.prune_cnt->n_pruned, (unsigned long long)n_pruned);
     }
     l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
-}
-
-template <int G, int GP, int NJ, int PF, int WPS>
-static hipError_t launch_l2_prune_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
-{
-    MatchParams P = Pin;
-    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_prune_kernel<G, GP, NJ, PF, WPS>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -643,176 +612,6 @@ static hipError_t launch_l2_prune_t(hipStream_t st, const MatchParams& Pin, uint
 // under, is the lower bound l2_finish_queries<PRUNE> asks for, whichever test pruned.
 // MODE (developer ablations): 0 the cascade | 1 filter only (step 2 never stops a tile).
 // ------------------------------------------------------------------------------------------------
-template <int G, int GP, int NJ, int PF, int WPS, int MODE>
-__global__ __launch_bounds__(256, WPS)
-void l2_knn2_cascade_kernel(const MatchParams P)
-{
-    constexpr int GR = G / 2;
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const uint32_t h = lane >> 5, c = lane & 31u;
-    // workgroup -> (pair, query block): as in l2_knn2_mfma_kernel
-    uint32_t pair, qb;
-    if (P.xcd_map) {
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
-    const uint2 pr = P.pairs[pair];
-    const ImgDev* __restrict__ Ip = P.imgs + pr.x;
-    const ImgDev* __restrict__ Jp = P.imgs + pr.y;
-    const float* const* pairnorm = reinterpret_cast<const float* const*>(P.prune_cnt[3]);      // (MatchParams::prune_cnt says why it lives there)
-    const float* __restrict__ redI = pairnorm[pr.x];
-    const float* __restrict__ redJ = pairnorm[pr.y];
-    const uint32_t nI = Ip->n, ntI = Ip->n_tiles, nJ = Jp->n, ntJ = Jp->n_tiles;
-    const uint32_t qt0 = (qb * 4u + wave) * NJ;
-    if (qt0 >= ntJ) return;                           // wave-uniform; no barriers in this kernel
-
-    // ---- reduced query fragments (B operand of the filter), scaled by -2; a tile that goes on reads the full ones (soffQ)
-    f32x4 bqr[NJ][GR];
-    uint32_t soffQ[NJ];
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj) {
-        uint32_t qt = qt0 + nj; if (qt >= ntJ) qt = ntJ - 1;          // clamp: results discarded below
-        soffQ[nj] = qt * (uint32_t)(G * 1024);
-        const gf4p src = (gf4p)redJ + (size_t)qt * (GR * 64) + lane;
-#pragma unroll
-        for (int g = 0; g < GR; ++g) bqr[nj][g] = src[g * 64] * -2.0f;
-    }
-    const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled);
-
-    Top2 st[NJ];
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
-
-    // ---- the lane's share of the thresholds (read again where a list has changed, as in the kernel above)
-    const bool exact_pair = l2_pair_is_exact(Ip, Jp, (float)(G * 8), false);
-    const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
-    const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
-    const float maxnormI = __uint_as_float(Ip->max_norm_bits);
-    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF) __attribute__((always_inline)) -> bool {
-        uint32_t q = (qt0 + (uint32_t)nj) * 32u + c;
-        asm volatile("" : "+v"(q));
-        const bool dead = !(q < nJ);                    // (covers a query tile beyond the last one too: its rows lie beyond nJ)
-        const uint32_t qo = dead ? 0u : q * 4u;
-        const float nb = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, 0, 0));
-        const float nbp = __uint_as_float((uint32_t)__builtin_amdgcn_raw_buffer_load_b32(rq, (int)qo, (int)(prefix_norm_offset(ntJ) * 4u), 0));
-        const float slkF = (P.err_scale + kPruneKeySlack) * (maxnormI + nb);
-        const float slk = exact_pair ? 0.0f : slkF;
-        nbs = nb + slk;
-        off = slk - nbp;
-        offF = slkF - nb;
-        return dead;
-    };
-    float thr[NJ], thrF[NJ], Tl[NJ], plT[NJ];
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned)
-    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0;      // wave-uniform
-    bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
-
-    if (nI >= 2) {
-        // ---- dataset stream of the filter (A operand): the pair-norm tiles, float4 index = (t*GR + g)*64 + lane, and the full norms
-        const gf4p abase = (gf4p)redI;
-        const gf4p nbase = (gf4p)Ip->norms;               // tile t, quad qd -> float4 index t*8 + 2*qd + h
-        f32x4 abuf[PF];
-#pragma unroll
-        for (int s = 0; s < PF; ++s) abuf[s] = abase[s * 64 + lane];
-        f32x4 nrm[4];
-#pragma unroll
-        for (int qd = 0; qd < 4; ++qd) nrm[qd] = nbase[2 * qd + h];
-
-        f32x16 accA[NJ], accB[NJ];
-        const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms), rr = wave_uniform_rsrc(redI);
-        const uint32_t voffA = lane * 16u, voffN = h * 16u;
-        const uint32_t tileB = (uint32_t)G * 1024u, tileRB = (uint32_t)GR * 1024u;      // bytes per tile, per reduced tile
-        const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
-        const uint32_t hb = 4u * h;
-        // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes)
-        auto refresh = [&]() __attribute__((always_inline)) {
-#pragma unroll
-            for (int nj = 0; nj < NJ; ++nj) {
-                if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
-                float nbs, off, offF;
-                const bool dead = lane_terms(nj, nbs, off, offF);
-                const float e0 = st[nj].d0 + nbs, e1 = st[nj].d1 + nbs;
-                const float re1 = R * e1;
-                float T = e0 < re1 ? __builtin_fmaxf(re1, e0 * invR) : re1;
-                T += __builtin_fabsf(T) * 4.76837158203125e-07f;        // 2^-21: the roundings of e1, R e1, 1 / R and e0 / R
-                Tl[nj] = T;
-                const float x = T + off, xF = T + offF;
-                thr[nj] = dead ? -R3DM_INF : x + __builtin_fabsf(x) * 2.384185791015625e-07f;      // 2^-22: the rounding of x
-                thrF[nj] = dead ? -R3DM_INF : xF + __builtin_fabsf(xF) * 2.384185791015625e-07f;
-            }
-        };
-        // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
-        auto tile = [&](uint32_t t, f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ], bool live) __attribute__((always_inline)) -> bool {
-            l2_pairnorm_tile_filter<GR, NJ, PF>(rr, rn, voffA, voffN, t * tileRB, (t + 1) * 128u, abuf, nrm, bqr, cur, prev, st,
-                                                (t - 1) * 32u + hb, live);
-            if (live) { refresh(); pruned_under_thr = false; }
-            n_tested += 1u;
-            // a lane objects when one of its filter keys is not above its threshold (written so that a NaN key objects)
-            bool obj = false;
-#pragma unroll
-            for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrF[nj]);
-            if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true; return false; }
-            const bool on = l2_prune_tile_restart<G, GP, NJ, MODE == 0>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
-            if (!on) { n_pruned += 1u; pruned_under_thr = true; }
-            return on;
-        };
-        bool live = false;
-        uint32_t t = 0;
-        for (; t + 1 < ntI; t += 2) {
-            live = tile(t, accA, accB, live);
-            live = tile(t + 1, accB, accA, live);
-        }
-        if (t < ntI) {
-            if (tile(t, accA, accB, live)) {
-#pragma unroll
-                for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-                    for (int r = 0; r < 16; ++r) top2_push(st[nj], accA[nj][r], t * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
-            }
-        } else if (live) {
-#pragma unroll
-            for (int nj = 0; nj < NJ; ++nj)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) top2_push(st[nj], accB[nj][r], (ntI - 1) * 32u + hb + (uint32_t)((r & 3) + 8 * (r >> 2)));
-        }
-    }
-
-    // plT -> the lower bound of the pruned rows' distances (a lane whose query does not exist holds none)
-    float pruned_lb[NJ];
-#pragma unroll
-    for (int nj = 0; nj < NJ; ++nj) {
-        if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
-        const bool dead = !((qt0 + (uint32_t)nj) * 32u + c < nJ);
-        pruned_lb[nj] = dead ? -R3DM_INF : plT[nj];
-    }
-    if (lane == 0 && n_tested) {
-        atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
-        if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
-        if (n_filtered) atomicAdd(P.prune_cnt + 2, (unsigned long long)n_filtered);
-    }
-    l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, h, c, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
-}
-
-template <int G, int GP, int NJ, int PF, int WPS, int MODE>
-static hipError_t launch_l2_cascade_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
-{
-    MatchParams P = Pin;
-    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_cascade_kernel<G, GP, NJ, PF, WPS, MODE>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
-}
-
 // ------------------------------------------------------------------------------------------------
 // The f16 level: a cheaper filter in front of the filter (r3dm_set_half_filter, default on).  The pair-norm filter is the one
 // contraction of the cascade whose result reaches no caller -- a lower bound, compared against a threshold -- and it stays a lower
@@ -872,50 +671,66 @@ constexpr float kHalfMarginAbs = 2.9103830456733704e-11f;                   // 2
 constexpr float kSkipLossFactor = 0.001953125f + 0.0001220703125f + 3.0517578125e-05f;      // 2^-9 + 2^-13 + 2^-15
 constexpr float kSkipLossAbs = 0.00390625f + 3.0517578125e-05f;                               // 2^-8 + 2^-15
 
+// ------------------------------------------------------------------------------------------------
+// Both forms are ONE kernel, and the template argument MODE also says how many levels run: MODE = 0 | 1 | 2 are the three levels with
+// the f16 level's MODE above, MODE = 20 | 21 the two levels (the cascade: pair-norm filter, then the restart) with the cascade's
+// MODE 0 | 1 above.  (The name and the argument list are the three-level kernel's, so that its symbol -- which
+// profiles/pmc_traffic.json and the tracked profiles name -- stays.)
+// They share the frame -- the workgroup's pair, lane_terms, the refresh with the T formula every proof above leans on, the tile
+// alternation, the drain of the last tile, pruned_lb, the counters, l2_finish_queries -- and differ in the table level 1 contracts,
+// in thrH / thrS, the skip and level 2, and in two counters; what only one form uses is declared in both and dies unused in the
+// other.  Each instantiation is, instruction for instruction, the kernel it was when the two were written out
+// (profiles/levels_frame_isa.txt).
+// ------------------------------------------------------------------------------------------------
+// a table's address out of the header, loaded as the 64-bit word it was before the header had a type: read through the pointer-typed
+// field, the load sits two instructions earlier in the two-level kernel
+template <class T>
+__device__ __forceinline__ const T* const* prune_table(const PruneHeader* hdr, size_t offset)
+{
+    return reinterpret_cast<const T* const*>(reinterpret_cast<const unsigned long long*>(hdr)[offset / 8]);
+}
+
 template <int G, int GP, int NJ, int PF, int WPS, int MODE>
 __global__ __launch_bounds__(256, WPS)
 void l2_knn2_half_kernel(const MatchParams P)
 {
-    constexpr int GR = G / 2, GH = G / 4;
+    static_assert((MODE >= 0 && MODE <= 2) || MODE == 20 || MODE == 21, "three levels: 0 | 1 | 2; two levels: 20 | 21");
+    constexpr bool H = MODE < 20;                     // the f16 level in front
+    constexpr int ABL = MODE % 20;                    // the form's own MODE (the header comments)
+    constexpr int GR = G / 2, GH = G / 4, G1 = H ? GH : GR;      // groups of a reduced tile, blocks of an f16 tile, what level 1 contracts
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
-    // workgroup -> (pair, query block): as in l2_knn2_mfma_kernel
     uint32_t pair, qb;
-    if (P.xcd_map) {
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
+    if (!workgroup_pair(P, pair, qb)) return;
     const uint2 pr = P.pairs[pair];
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
-    const float* const* pairnorm = reinterpret_cast<const float* const*>(P.prune_cnt[3]);      // (MatchParams::prune_cnt says why they live there)
-    const uint16_t* const* halfnorm = reinterpret_cast<const uint16_t* const*>(P.prune_cnt[5]);
+    const float* const* pairnorm = prune_table<float>(P.prune_cnt, offsetof(PruneHeader, pairnorm));
+    const uint16_t* const* halfnorm = H ? prune_table<uint16_t>(P.prune_cnt, offsetof(PruneHeader, halfnorm)) : nullptr;
     const float* __restrict__ redI = pairnorm[pr.x];
     const float* __restrict__ redJ = pairnorm[pr.y];
-    const uint16_t* __restrict__ hlfI = halfnorm[pr.x];
-    const uint16_t* __restrict__ hlfJ = halfnorm[pr.y];
+    const uint16_t* __restrict__ hlfI = H ? halfnorm[pr.x] : nullptr;
+    const uint16_t* __restrict__ hlfJ = H ? halfnorm[pr.y] : nullptr;
     const uint32_t nI = Ip->n, ntI = Ip->n_tiles, nJ = Jp->n, ntJ = Jp->n_tiles;
     const uint32_t qt0 = (qb * 4u + wave) * NJ;
     if (qt0 >= ntJ) return;                           // wave-uniform; no barriers in this kernel
 
-    // ---- f16 query fragments (B operand of level 1), scaled by -2 (exact, or -inf); a tile that goes on reads the f32 ones
-    // (soffQR: the reduced groups, soffQ: the full ones)
-    f32x4 bqh[NJ][GH];
+    // ---- query fragments of level 1 (B operand), scaled by -2: the reduced ones, or the f16 ones (exact, or -inf); a tile that goes
+    // on reads the f32 ones again (soffQR: the reduced groups, soffQ: the full ones)
+    f32x4 bq1[NJ][G1];
     uint32_t soffQ[NJ], soffQR[NJ];
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) {
         uint32_t qt = qt0 + nj; if (qt >= ntJ) qt = ntJ - 1;          // clamp: results discarded below
         soffQ[nj] = qt * (uint32_t)(G * 1024);
         soffQR[nj] = qt * (uint32_t)(GR * 1024);
-        const gf4p src = (gf4p)hlfJ + (size_t)qt * (GH * 64) + lane;
+        const gf4p src = (H ? (gf4p)hlfJ : (gf4p)redJ) + (size_t)qt * (G1 * 64) + lane;
 #pragma unroll
-        for (int g = 0; g < GH; ++g) bqh[nj][g] = __builtin_bit_cast(f32x4, __builtin_bit_cast(f16x8, src[g * 64]) * (_Float16)-2.0f);
+        for (int g = 0; g < G1; ++g) {
+            if constexpr (H) bq1[nj][g] = __builtin_bit_cast(f32x4, __builtin_bit_cast(f16x8, src[g * 64]) * (_Float16)-2.0f);
+            else bq1[nj][g] = src[g * 64] * -2.0f;
+        }
     }
     const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled), rqr = wave_uniform_rsrc(redJ);
 
@@ -923,7 +738,7 @@ void l2_knn2_half_kernel(const MatchParams P)
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) top2_init(st[nj]);
 
-    // ---- the lane's share of the thresholds (read again where a list has changed, as in the kernels above)
+    // ---- the lane's share of the thresholds (read again where a list has changed, as in the kernel above; mgn and loss: thrH, thrS)
     const bool exact_pair = l2_pair_is_exact(Ip, Jp, (float)(G * 8), false);
     const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
     const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
@@ -951,8 +766,9 @@ void l2_knn2_half_kernel(const MatchParams P)
     bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
 
     if (nI >= 2) {
-        // ---- dataset stream of level 1 (A operand): the f16 tiles, float4 index = (t*GH + g)*64 + lane, and the full norms
-        const gf4p abase = (gf4p)hlfI;
+        // ---- dataset stream of level 1 (A operand): the pair-norm tiles or the f16 tiles, float4 index = (t*G1 + g)*64 + lane, and
+        // the full norms
+        const gf4p abase = H ? (gf4p)hlfI : (gf4p)redI;
         const gf4p nbase = (gf4p)Ip->norms;               // tile t, quad qd -> float4 index t*8 + 2*qd + h
         f32x4 abuf[PF];
 #pragma unroll
@@ -969,7 +785,7 @@ void l2_knn2_half_kernel(const MatchParams P)
         const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
         uint32_t hb = 4u * h;
         // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes).  T, thr and thrF are the
-        // cascade's floats; thrH >= thrF + margin (the header comment)
+        // same floats with two levels and with three; thrH >= thrF + margin (the header comment)
         auto refresh = [&]() __attribute__((always_inline)) {
 #pragma unroll
             for (int nj = 0; nj < NJ; ++nj) {
@@ -992,26 +808,35 @@ void l2_knn2_half_kernel(const MatchParams P)
         };
         // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
         auto tile = [&](uint32_t t, f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ], bool live) __attribute__((always_inline)) -> bool {
-            l2_halfnorm_tile_filter<GH, NJ, PF>(rh, rn, voffA, voffN, t * tileHB, (t + 1) * 128u, abuf, nrm, bqh, cur, prev, st,
-                                                (t - 1) * 32u + hb, live);
+            if constexpr (H)
+                l2_halfnorm_tile_filter<GH, NJ, PF>(rh, rn, voffA, voffN, t * tileHB, (t + 1) * 128u, abuf, nrm, bq1, cur, prev, st,
+                                                    (t - 1) * 32u + hb, live);
+            else
+                l2_pairnorm_tile_filter<GR, NJ, PF>(rr, rn, voffA, voffN, t * tileRB, (t + 1) * 128u, abuf, nrm, bq1, cur, prev, st,
+                                                    (t - 1) * 32u + hb, live);
             if (live) { refresh(); pruned_under_thr = false; }
             n_tested += 1u;
-            // a lane objects when one of its keys is not above its threshold (written so that a NaN key objects)
+            // a lane objects when one of its level-1 keys is not above its threshold (written so that a NaN key objects)
             bool obj = false;
 #pragma unroll
             for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrH[nj]);
-            if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; n_half += 1u; pruned_under_thr = true; return false; }
+                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > (H ? thrH[nj] : thrF[nj]));
+            if (__builtin_amdgcn_ballot_w64(obj) == 0ull) {
+                n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true;
+                if constexpr (H) n_half += 1u;
+                return false;
+            }
+            // (two levels, MODE 21: the filter alone -- the restart never stops a tile)
             auto restart = [&]() __attribute__((always_inline)) -> bool {
-                const bool on = l2_prune_tile_restart<G, GP, NJ, true>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
+                const bool on = l2_prune_tile_restart<G, GP, NJ, H || ABL == 0>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
                 if (!on) { n_pruned += 1u; pruned_under_thr = true; }
                 return on;
             };
             // level 2 cannot prune a tile that holds a finite f16 key at or below thrS (the header comment): such a tile skips it.  Only
             // the tiles that object get here, so the second pass over the keys is off level 1's path.  The skip has a copy of the restart
             // to itself: with one copy entered from both sides the register allocator spills 70 registers, with two it spills none
-            if constexpr (MODE == 0) {
+            if constexpr (H && ABL == 0) {
                 bool far = false;
 #pragma unroll
                 for (int nj = 0; nj < NJ; ++nj)
@@ -1019,7 +844,7 @@ void l2_knn2_half_kernel(const MatchParams P)
                     for (int r = 0; r < 16; ++r) far |= (cur[nj][r] <= thrS[nj]) && (cur[nj][r] > -R3DM_INF);
                 if (__builtin_amdgcn_ballot_w64(far) != 0ull) { n_skip += 1u; return restart(); }
             }
-            if constexpr (MODE != 1) {
+            if constexpr (H && ABL != 1) {
                 l2_pairnorm_tile_stream<GR, NJ>(rr, rn, voffA, voffN, t * tileRB, t * 128u, rqr, soffQR, cur);
                 obj = false;
 #pragma unroll
@@ -1036,8 +861,9 @@ void l2_knn2_half_kernel(const MatchParams P)
             live = tile(t, accA, accB, live);
             live = tile(t + 1, accB, accA, live);
         }
-        // (the lane's half once more, from the lane counter: nothing of it has to live through the loop, whose registers are all taken)
-        hb = 4u * (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 5);
+        // (three levels: the lane's half once more, from the lane counter -- nothing of it has to live through the loop, whose registers
+        //  are all taken)
+        if constexpr (H) hb = 4u * (__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) >> 5);
         if (t < ntI) {
             if (tile(t, accA, accB, live)) {
 #pragma unroll
@@ -1054,7 +880,7 @@ void l2_knn2_half_kernel(const MatchParams P)
     }
 
     // plT -> the lower bound of the pruned rows' distances (a lane whose query does not exist holds none)
-    const uint32_t lane_e = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)), he = lane_e >> 5, ce = lane_e & 31u;      // (= lane, h, c: as above)
+    const uint32_t lane_e = H ? __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane, he = lane_e >> 5, ce = lane_e & 31u;      // (= lane, h, c: as above)
     float pruned_lb[NJ];
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) {
@@ -1063,24 +889,13 @@ void l2_knn2_half_kernel(const MatchParams P)
         pruned_lb[nj] = dead ? -R3DM_INF : plT[nj];
     }
     if (lane_e == 0 && n_tested) {
-        atomicAdd(P.prune_cnt, (unsigned long long)n_tested);
-        if (n_pruned) atomicAdd(P.prune_cnt + 1, (unsigned long long)n_pruned);
-        if (n_filtered) atomicAdd(P.prune_cnt + 2, (unsigned long long)n_filtered);
-        if (n_half) atomicAdd(P.prune_cnt + 4, (unsigned long long)n_half);
-        if (n_skip) atomicAdd(P.prune_cnt + 6, (unsigned long long)n_skip);
+        atomicAdd(&P.prune_cnt->n_tested, (unsigned long long)n_tested);
+        if (n_pruned) atomicAdd(&P.prune_cnt->n_pruned, (unsigned long long)n_pruned);
+        if (n_filtered) atomicAdd(&P.prune_cnt->n_filtered, (unsigned long long)n_filtered);
+        if (n_half) atomicAdd(&P.prune_cnt->n_half, (unsigned long long)n_half);         // (both stay 0 with two levels)
+        if (n_skip) atomicAdd(&P.prune_cnt->n_skip, (unsigned long long)n_skip);
     }
     l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, he, ce, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
-}
-
-template <int G, int GP, int NJ, int PF, int WPS, int MODE>
-static hipError_t launch_l2_half_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
-{
-    MatchParams P = Pin;
-    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_half_kernel<G, GP, NJ, PF, WPS, MODE>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
 }
 
 // The pruning kernel serves ratio tests that leave it room: near R = 1 a row matters up to the runner-up's distance, no prefix
@@ -1105,14 +920,19 @@ uint32_t l2_prefix_groups()
 }
 
 template <int G, int NJ, int PF, int PIPE, int WPS>
-static hipError_t launch_l2_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_t(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_mfma_kernel<G, NJ, PF, PIPE, WPS>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return launch_pair_kernel(l2_knn2_mfma_kernel<G, NJ, PF, PIPE, WPS>, NJ, true, st, P, max_nj_tiles);
+}
+template <int G, int GP, int NJ, int PF, int WPS>
+static hipError_t launch_l2_prune_t(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
+{
+    return launch_pair_kernel(l2_knn2_prune_kernel<G, GP, NJ, PF, WPS>, NJ, true, st, P, max_nj_tiles);
+}
+template <int G, int GP, int NJ, int PF, int WPS, int MODE>
+static hipError_t launch_l2_half_t(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
+{
+    return launch_pair_kernel(l2_knn2_half_kernel<G, GP, NJ, PF, WPS, MODE>, NJ, true, st, P, max_nj_tiles);
 }
 
 // The A/B variants below (tools/ab_l2.py) -- including two ablations whose results are meaningless (timing only) -- exist
@@ -1149,7 +969,7 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
             case 110: return launch_l2_prune_t<16, 10, 2, 2, 2>(st, P, max_nj_tiles);
             case 111: return launch_l2_prune_t<16, 11, 2, 1, 2>(st, P, max_nj_tiles);
             case 112: return launch_l2_prune_t<16, 12, 2, 2, 2>(st, P, max_nj_tiles);
-            case 120: return launch_l2_cascade_t<16, (int)kPrefixGroups, 2, 2, 2, 1>(st, P, max_nj_tiles);
+            case 120: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 21>(st, P, max_nj_tiles);
             default: break;
         }
         //   130: the f16 level, then straight to the restart (no f32 filter; timing only) | 131 / 132: the three levels with a
@@ -1171,7 +991,7 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
     // stops few tiles it adds 256 cycles to a tile of 4,096 and more (profiles/half_filter_model_c2.txt has R = 0.49).
     if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R)) {
         if ((P.prune & 2u) != 0) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
-        return launch_l2_cascade_t<16, (int)kPrefixGroups, 2, 2, 2, 0>(st, P, max_nj_tiles);
+        return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 20>(st, P, max_nj_tiles);
     }
     switch (G) {
         case 8:  return launch_l2_t<8, 2, 4, 3, 2>(st, P, max_nj_tiles);

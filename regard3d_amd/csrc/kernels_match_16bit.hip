@@ -26,8 +26,10 @@ void l2_knn2_int_kernel(const MatchParams P)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
+    // workgroup_pair (kernels_match_tiles.hpp), written out: called as a function it reorders l2_knn2_int_kernel<8, 3, 4, 2>, whose
+    // machine code profiles/pmc_traffic.json is keyed to (profiles/levels_frame_isa.txt)
     uint32_t pair, qb;
-    if (P.xcd_map) {                                       // pair p on XCD p % 8 (see l2_knn2_mfma_kernel)
+    if (P.xcd_map) {
         const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
         pair = (j / P.qb_per_pair) * 8u + xcd;
         qb = j % P.qb_per_pair;
@@ -103,14 +105,9 @@ void l2_knn2_int_kernel(const MatchParams P)
 }
 
 template <int GB, int NJ, int PF, int WPS, int ABL = 0>
-static hipError_t launch_l2_int(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_int(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, (uint32_t)xcd_map, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_int_kernel<GB, NJ, PF, WPS, ABL>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return launch_pair_kernel(l2_knn2_int_kernel<GB, NJ, PF, WPS, ABL>, NJ, true, st, P, max_nj_tiles);
 }
 
 // G = padded dim / 8; hipErrorNotSupported: no bf16 kernel for this G (the caller keeps the f32 tiles)
@@ -207,8 +204,10 @@ void l2_knn2_split_kernel(const MatchParams P)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
+    // workgroup_pair (kernels_match_tiles.hpp), written out: called as a function it costs l2_knn2_split_kernel<9, 2, 3> an instruction
+    // and other registers in its tile loop (profiles/levels_frame_isa.txt)
     uint32_t pair, qb;
-    if (P.xcd_map) {                                       // pair p on XCD p % 8 (see l2_knn2_mfma_kernel)
+    if (P.xcd_map) {
         const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
         pair = (j / P.qb_per_pair) * 8u + xcd;
         qb = j % P.qb_per_pair;
@@ -285,16 +284,12 @@ void l2_knn2_split_kernel(const MatchParams P)
 }
 
 template <int GB, int NJ, int PF>
-static hipError_t launch_l2_split_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_split_t(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
     const size_t lds = (size_t)4 * NJ * GB * 1024;
     hipError_t e = hipFuncSetAttribute((const void*)l2_knn2_split_kernel<GB, NJ, PF>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((l2_knn2_split_kernel<GB, NJ, PF>), dim3(grid), dim3(256), lds, st, P);
-    return hipGetLastError();
+    return launch_pair_kernel(l2_knn2_split_kernel<GB, NJ, PF>, NJ, false, st, P, max_nj_tiles, lds);
 }
 
 // G = padded dim / 8 of the views (8, 16, 18, 32); hipErrorInvalidValue -> no split kernel, caller keeps the f32 tiles
@@ -691,15 +686,7 @@ void l2_knn2_counts_kernel(const MatchParams P)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
     uint32_t pair, qb;
-    if (P.xcd_map) {                                       // pair p on XCD p % 8 (see l2_knn2_mfma_kernel)
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
+    if (!workgroup_pair(P, pair, qb)) return;
     const uint2 pr = P.pairs[pair];
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
@@ -947,6 +934,8 @@ void l2_knn2_counts2_kernel(const MatchParams P)
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
+    // workgroup_pair (kernels_match_tiles.hpp), written out: called as a function it reorders every instantiation, and
+    // profiles/pmc_traffic.json is keyed to the machine code of l2_knn2_counts2_kernel<9, 9> (profiles/levels_frame_isa.txt)
     uint32_t pair, qb;
     if (P.xcd_map) {
         const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
@@ -1053,23 +1042,15 @@ void l2_knn2_counts2_kernel(const MatchParams P)
 }
 
 template <int GB, int PF>
-static hipError_t launch_l2_counts2_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_counts2_t(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, 2u, 1u, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_counts2_kernel<GB, PF>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return launch_pair_kernel(l2_knn2_counts2_kernel<GB, PF>, 2u, false, st, P, max_nj_tiles);
 }
 
 template <int GB, int NJ, int PF>
-static hipError_t launch_l2_counts_t(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_counts_t(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
-    hipLaunchKernelGGL((l2_knn2_counts_kernel<GB, NJ, PF>), dim3(grid), dim3(256), 0, st, P);
-    return hipGetLastError();
+    return launch_pair_kernel(l2_knn2_counts_kernel<GB, NJ, PF>, NJ, false, st, P, max_nj_tiles);
 }
 
 // G = padded dim / 8 of the views (8, 16, 18, 32); hipErrorInvalidValue -> no count kernel, caller keeps the split tiles

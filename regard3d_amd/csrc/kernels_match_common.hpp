@@ -198,7 +198,7 @@ __device__ __forceinline__ bool l2_pair_is_exact(const ImgDev* __restrict__ Ip, 
 }
 
 // extra relative slack of the pruning kernel's keys over err_scale (l2_finish_queries<PRUNE>): 8 x 2^-24, for three roundings each
-// below 2^-24 x 2 (maxnorm + ||q||^2).  The pair-norm filter of l2_knn2_cascade_kernel carries (err_scale + kPruneKeySlack) (maxnorm + ||q||^2)
+// below 2^-24 x 2 (maxnorm + ||q||^2).  The pair-norm filter of l2_knn2_half_kernel carries (err_scale + kPruneKeySlack) (maxnorm + ||q||^2)
 // on EVERY pair: its keys are a 64-term f32 dot product of non-negative terms (products of rounded-up roots, never integers) started
 // from the stored ||a||^2, off by at most (128 + 65 + 64) u of ||a||^2 + ||q||^2 on the key side and 256 u on the reference's side,
 // 513 u <= err_scale = 544 u at D = 128; the 8 u here pay the roundings of the slack, of slack - ||q||^2 and of T (the derivation
@@ -213,7 +213,7 @@ constexpr float kPruneKeySlack = 4.76837158203125e-07f;
 //        the exact scan
 // lane_key_inv (count tiles, l2_knn2_counts_kernel): the keys of query tile nj are in units of lane_key_inv[nj]^-1, a value per QUERY
 //        (both lane halves of a column hold the same one)
-// PRUNE: the lists come from l2_knn2_cascade_kernel (or l2_knn2_prune_kernel), which left whole tiles out of them after their pair
+// PRUNE: the lists come from l2_knn2_half_kernel (or l2_knn2_prune_kernel), which left whole tiles out of them after their pair
 //        norms or a prefix of their dimensions;
 //        pruned_lb[nj] is this lane half's lower bound of the reference distance of every row it left out (+inf: none), and the
 //        keys carry up to three more roundings than l2_tile_step's (prefix norm, suffix norm, their sum)
@@ -301,7 +301,7 @@ __device__ __forceinline__ void l2_finish_queries(const MatchParams& P, uint32_t
         //     ia is the true best row; the true runner-up is eb or a pruned row, and ea is below fl(R .) of both.  Emit ia.
         //   * ea < fl(R eb) but not ea < fl(R PL): a pruned row may be the best row or spoil the ratio.  Exact scan.
         // An uncertified query keeps its shortcut with PL folded into the lower bound of everything un-nominated.
-        // The cascade (l2_knn2_cascade_kernel) prunes a tile on EITHER of two lower bounds of d, the prefix distance or the pair-norm
+        // The cascade (l2_knn2_half_kernel) prunes a tile on EITHER of two lower bounds of d, the prefix distance or the pair-norm
         // bound |a|^2 + |b|^2 - 2 sum_k sa_k sb_k less its slack (Cauchy-Schwarz per pair of dimensions: kernels_match.hip).  The
         // argument above uses of a pruned row only d > T for the T its lane half held at that moment, which holds for both, and of
         // pruned_lb only that it is at most every such T: the cascade hands over the smallest T itself.

@@ -98,15 +98,7 @@ void l2_knn2_int_lds_kernel(const MatchParams P)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
     uint32_t pair, qb;
-    if (P.xcd_map) {                                       // pair p on XCD p % 8 (see l2_knn2_mfma_kernel)
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;                     // whole workgroup
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
+    if (!workgroup_pair(P, pair, qb)) return;              // whole workgroup
     const uint2 pr = P.pairs[pair];
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
@@ -249,15 +241,7 @@ void l2_knn2_int_ring_kernel(const MatchParams P)
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t h = lane >> 5, c = lane & 31u;
     uint32_t pair, qb;
-    if (P.xcd_map) {                                       // pair p on XCD p % 8 (see l2_knn2_mfma_kernel)
-        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
-        pair = (j / P.qb_per_pair) * 8u + xcd;
-        qb = j % P.qb_per_pair;
-        if (pair >= P.n_pairs) return;                     // whole workgroup
-    } else {
-        pair = blockIdx.x / P.qb_per_pair;
-        qb = blockIdx.x % P.qb_per_pair;
-    }
+    if (!workgroup_pair(P, pair, qb)) return;              // whole workgroup
     const uint2 pr = P.pairs[pair];
     const ImgDev* __restrict__ Ip = P.imgs + pr.x;
     const ImgDev* __restrict__ Jp = P.imgs + pr.y;
@@ -401,29 +385,18 @@ void l2_knn2_int_ring_kernel(const MatchParams P)
 }
 
 template <int GB, int NJ, int PF, int WPS, int ABL = 0, int OPS = 0>
-static hipError_t launch_l2_int_ring(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_int_ring(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
     const size_t lds = kRingK * ((size_t)GB * 1024 + 256) + 2 * kRingK * 4;
-    {
-        const hipError_t e = hipFuncSetAttribute((const void*)l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>), dim3(grid), dim3(256), lds, st, P);
-    return hipGetLastError();
+    const hipError_t e = hipFuncSetAttribute((const void*)l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    return launch_pair_kernel(l2_knn2_int_ring_kernel<GB, NJ, PF, WPS, ABL, OPS>, NJ, false, st, P, max_nj_tiles, lds);
 }
 
 template <int GB, int NJ, int PF, int WPS, int ABL = 0, int OPS = 0>
-static hipError_t launch_l2_int_lds(hipStream_t st, const MatchParams& Pin, uint32_t max_nj_tiles)
+static hipError_t launch_l2_int_lds(hipStream_t st, const MatchParams& P, uint32_t max_nj_tiles)
 {
-    MatchParams P = Pin;
-    uint32_t grid; hipError_t status;
-    if (!pair_grid(P, max_nj_tiles, NJ, 1u, grid, status)) return status;
-    const size_t lds = 3 * (size_t)GB * 1024 + 3 * 1024;
-    hipLaunchKernelGGL((l2_knn2_int_lds_kernel<GB, NJ, PF, WPS, ABL, OPS>), dim3(grid), dim3(256), lds, st, P);
-    return hipGetLastError();
+    return launch_pair_kernel(l2_knn2_int_lds_kernel<GB, NJ, PF, WPS, ABL, OPS>, NJ, false, st, P, max_nj_tiles, 3 * (size_t)GB * 1024 + 3 * 1024);
 }
 
 // Opt-in exact MFMA Hamming (r3dm_set_hamming_mfma): binary rows of `words` u32 staged as 0 / 1 bytes (ImgDev::tiled8) with

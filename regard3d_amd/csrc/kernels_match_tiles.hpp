@@ -13,14 +13,15 @@
 //   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
 //   bf16x2_times_m2                    -2 x a packed pair of bf16 integers (the query fragments of the integer tiles)
-//   pair_grid                          host: qb_per_pair, xcd_map, the grid of a 2-NN launch and its bound
+//   workgroup_pair                     the workgroup -> (pair, query block) decode of every 2-NN nominator
+//   pair_grid, launch_pair_kernel      host: qb_per_pair, xcd_map, the grid of a 2-NN launch and its bound; the launch itself
 //   tiles_within_reach                 host: the 2^31-byte reach of the buffer offsets (dispatch_kl is in r3dm_internal.hpp)
 // Every step is templated on the list type and on NJ, the query tiles a wave holds; the K-list kernels that hold one tile keep arrays
 // of one.
-// What is NOT here, on purpose: the ping-pong loop around the steps (two steps, the odd tail, the drain of the last tile), the load of
-// a wave's query fragments and the workgroup -> (pair, query block) decode stay written out in every kernel.  Each of them was tried
-// as a function of this header and changed the machine code of the kernels that called it; a kernel's bytes decide.
-// What holds is what was a function before (the steps) and pure expressions on values (the descriptor, the bf16 repacking).
+// What is NOT here, on purpose: the ping-pong loop around the steps (two steps, the odd tail, the drain of the last tile) and the load
+// of a wave's query fragments stay written out in every kernel.  Each of them was tried as a function of this header and changed the
+// machine code of the kernels that called it; a kernel's bytes decide.  What holds is what was a function before (the
+// steps), pure expressions on values (the descriptor, the bf16 repacking) and the workgroup's decode in the very shape it had.
 //
 // Arithmetic contract as everywhere (kernels_match_common.hpp); every unit that includes this header is compiled with
 // -ffp-contract=off, fused operations are spelled fmaf() / MFMA.
@@ -260,7 +261,7 @@ __device__ __forceinline__ bool l2_prune_tile_finish(__amdgpu_buffer_rsrc_t ra, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// f32 tiles, match mode: the pair-norm filter in front of the prefix test (l2_knn2_cascade_kernel; Top2 lists only).
+// f32 tiles, match mode: the pair-norm filter in front of the prefix test (l2_knn2_half_kernel; Top2 lists only).
 // The same contraction over the REDUCED rows (the table behind MatchParams::prune_cnt: GR = G / 2 groups of 8 pair norms per tile,
 // tiles contiguous), accumulators started from the rows' FULL norms: after GR groups they hold kf = |a|^2 - 2 sum_k sa_k sb_k, and
 // kf + |b|^2 <= |a - b|^2 (Cauchy-Schwarz per pair; the proof and the slack: kernels_match.hip above the kernel).  The epilogue of
@@ -697,7 +698,28 @@ __device__ __forceinline__ uint32_t bf16x2_times_m2(uint32_t w)
 }
 
 // ------------------------------------------------------------------------------------------------
-// Grid of a 2-NN launch, the host mirror of the kernels' workgroup -> (pair, query block) decode (l2_knn2_mfma_kernel):
+// workgroup -> (pair, query block) of every 2-NN nominator; false: the workgroup has no pair (the whole workgroup returns).
+// Workgroups are dealt round-robin to the 8 XCDs, each with its own L2; with xcd_map every workgroup of a pair runs on ONE XCD
+// (pair p on XCD p % 8), so image I and the query tiles are pulled into one L2 instead of eight (pairs are sorted by I: an XCD's
+// consecutive pairs mostly share their dataset image).  The two branches keep the shape they had when every kernel wrote them out:
+// in this shape the kernels' machine code is what it was (profiles/levels_frame_isa.txt); a kernel's bytes decide.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool workgroup_pair(const MatchParams& P, uint32_t& pair, uint32_t& qb)
+{
+    if (P.xcd_map) {
+        const uint32_t xcd = blockIdx.x & 7u, j = blockIdx.x >> 3;
+        pair = (j / P.qb_per_pair) * 8u + xcd;
+        qb = j % P.qb_per_pair;
+        if (pair >= P.n_pairs) return false;
+    } else {
+        pair = blockIdx.x / P.qb_per_pair;
+        qb = blockIdx.x % P.qb_per_pair;
+    }
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------
+// Grid of a 2-NN launch, the host mirror of workgroup_pair:
 // 4 waves x nj query tiles x 32 queries per workgroup; with xcd_map the pair count is rounded up to the 8 XCDs.  Fills P.qb_per_pair
 // and P.xcd_map and returns true with the grid to launch; false with `status` = hipSuccess (an empty launch) or hipErrorInvalidValue
 // (a grid beyond 2^32 work-items).
@@ -712,6 +734,19 @@ inline bool pair_grid(MatchParams& P, uint32_t max_nj_tiles, uint32_t nj, uint32
     if (grid64 == 0 || grid64 > kMaxBlocksOf256) return false;
     grid = (uint32_t)grid64;
     return true;
+}
+
+// One 2-NN launch: `kernel` with nj query tiles per wave and `lds` bytes of dynamic LDS on a copy of the parameters that carries the
+// grid's mapping.  xcd_knob: the launch follows R3DM_XCD_MAP (developer build; the product's constant is 1); the others always map.
+inline hipError_t launch_pair_kernel(void (*kernel)(MatchParams), uint32_t nj, bool xcd_knob, hipStream_t st, const MatchParams& Pin,
+                                     uint32_t max_nj_tiles, size_t lds = 0)
+{
+    MatchParams P = Pin;
+    static const int xcd_map = r3dm_dev_knob("R3DM_XCD_MAP", 1);
+    uint32_t grid; hipError_t status;
+    if (!pair_grid(P, max_nj_tiles, nj, xcd_knob ? (uint32_t)xcd_map : 1u, grid, status)) return status;
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(256), lds, st, P);
+    return hipGetLastError();
 }
 
 // the nominators address a dataset through 32-bit buffer offsets: its tiles and both slacks must end below 2^31 - 1 bytes

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 #include <type_traits>
 
@@ -211,6 +212,29 @@ struct HnswBuildParams {
     const HnswBuildJob* jobs;
 };
 
+// What the pruning kernels keep behind MatchParams::prune_cnt (l2_knn2_prune_kernel: the first two counters; l2_knn2_half_kernel:
+// all of it): counters of wave tiles (32 rows x 64 queries; atomic, zeroed by the host) and the addresses of two tables by slot of
+// MatchParams::imgs, scratch of the call (run_match_batch), written by the host when the launch may prune.  Behind a pointer and in
+// no field of ImgDev or MatchParams: their sizes and offsets are what every other kernel's machine code and kernel arguments were
+// compiled with.  The order is the order the fields came in; the asserts below hold it.
+struct PruneHeader {
+    unsigned long long      n_tested;     // wave tiles tested
+    unsigned long long      n_pruned;     // ... pruned by any test
+    unsigned long long      n_filtered;   // ... pruned by the pair-norm filter, at either precision (part of n_pruned)
+    const float* const*     pairnorm;     // pair-norm tiles per slot: [n_tiles][G / 2][2][32][4] f32 in the fragment order of `tiled`, half its bytes
+    unsigned long long      n_half;       // ... pruned by the f16 level (part of n_filtered)
+    const uint16_t* const*  halfnorm;     // f16 pair-norm tiles per slot: [n_tiles][G / 4][2][32][8] f16; set when MatchParams::prune bit 1 is
+    unsigned long long      n_skip;       // tiles the f16 level sent straight to the restart, the filter unable to prune them (part of
+                                          // no count above: these tiles go on)
+};
+// the header of a batch's fallback lists (r3dm_ctx::d_fb): zeroed per batch, [fb_cnt: P][fb_q: P x kFbPerPair] behind it
+struct FbHeader {
+    uint32_t    fb_total[2];              // MatchParams::fb_total
+    uint32_t    pad0[2];
+    PruneHeader prune;                    // MatchParams::prune_cnt
+    uint32_t    pad1[6];
+};
+
 struct MatchParams {
     const ImgDev* imgs;
     const uint2*  pairs;          // slot indices (I, J)
@@ -236,16 +260,13 @@ struct MatchParams {
     // prefix pruning of the f32 2-NN tiles in match mode (r3dm_set_prefix_pruning; l2_knn2_prune_kernel).  Behind every older field:
     // their offsets are what the other kernels' machine code was compiled with.
     uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel; bit 1: with the f16 level in front (r3dm_set_half_filter)
-    // [0 .. 2]: wave tiles (32 rows x 64 queries) tested, pruned by any test, pruned by the pair-norm filter (atomic; zeroed by the
-    // host); [3]: the bits of a `const float* const*`, the pair-norm tiles of the cascade's filter (l2_knn2_cascade_kernel) per slot
-    // of `imgs`: [n_tiles][G / 2][2][32][4] f32 in the fragment order of `tiled`, half its bytes (scratch of the call: run_match_batch),
-    // written by the host when the launch may prune; [4]: wave tiles pruned by the f16 level (l2_knn2_half_kernel; part of [2]);
-    // [5]: the bits of a `const uint16_t* const*`, the f16 pair-norm tiles per slot: [n_tiles][G / 4][2][32][8] f16, written by the host
-    // when prune bit 1 is set; [6]: wave tiles the f16 level sent straight to the restart, the filter unable to prune them (part of
-    // neither count above: these tiles go on).  Behind this pointer and no field of ImgDev or of this struct: their sizes and
-    // offsets are what every other kernel's machine code and kernel arguments were compiled with.
-    unsigned long long* prune_cnt;
+    PruneHeader*  prune_cnt;      // the pruning kernels' counters and tables (FbHeader::prune)
 };
+static_assert(sizeof(MatchParams) == 120 && offsetof(MatchParams, prune_cnt) == 112, "kernel arguments: every 2-NN kernel was compiled with this layout");
+static_assert(offsetof(PruneHeader, n_tested) == 0 && offsetof(PruneHeader, n_pruned) == 8 && offsetof(PruneHeader, n_filtered) == 16 &&
+              offsetof(PruneHeader, pairnorm) == 24 && offsetof(PruneHeader, n_half) == 32 && offsetof(PruneHeader, halfnorm) == 40 &&
+              offsetof(PruneHeader, n_skip) == 48 && sizeof(PruneHeader) == 56, "the slots the pruning kernels were compiled with");
+static_assert(offsetof(FbHeader, fb_total) == 0 && offsetof(FbHeader, prune) == 16 && sizeof(FbHeader) == 96, "24 words, the counters 8-byte aligned");
 constexpr uint32_t kFbPerPair = 256;
 constexpr uint32_t kFallback = 0xFFFFFFFEu;
 

@@ -1,4 +1,4 @@
-"""Views for tests/test_gpu_pairnorm_filter.py (the pair-norm filter in front of the prefix test: l2_knn2_cascade_kernel) and for the CPU
+"""Views for tests/test_gpu_pairnorm_filter.py (the pair-norm filter in front of the prefix test: l2_knn2_half_kernel<…, MODE 20>) and for the CPU
 test that runs the numpy model of the cascade on them (tests/test_pairnorm_filter_model.py).  128 dimensions, integer-valued float32
 unless a case says otherwise.
 

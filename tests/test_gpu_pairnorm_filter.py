@@ -1,4 +1,4 @@
-"""The cascade of the pruning f32 2-NN kernel (l2_knn2_cascade_kernel: the pair-norm filter in front of the prefix test; match mode,
+"""The cascade of the pruning f32 2-NN kernel (l2_knn2_half_kernel<…, MODE 20>: the pair-norm filter in front of the prefix test; match mode,
 128-dimensional rows, R <= 0.5) on views built for the filter's edges.  Every case compares ctx.match_pairs with
 oracle.match_collection and with the same call after set_prefix_pruning(False), and reads both counters: the tiles pruned by any
 test (prefix_pruning_counts) and those pruned by the filter (pair_filter_counts).

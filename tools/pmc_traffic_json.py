@@ -27,7 +27,8 @@ out = {"_comment": "HBM-side traffic of ONE launch of the dominant kernel per be
        "16 B/lane streams -> read side doubled; WRITE_SIZE is uncalibrated on gfx950 and tiny here.  bench.py reports an entry only while "
        "code_sha16 equals the fingerprint of that kernel's machine code in the library it runs (regard3d_amd/codeobj.py)."}
 # bench.py's roofline names the headline kernel l2_knn2_mfma_kernel<G, NJ> whichever build of it ran: the pruning build
-# (l2_knn2_half_kernel, before it l2_knn2_cascade_kernel and l2_knn2_prune_kernel; match mode on 128-dimensional rows) is entered under that key, with its own name and fingerprint inside
+# (l2_knn2_half_kernel -- the three levels, or the cascade with MODE 20; in older passes l2_knn2_cascade_kernel and l2_knn2_prune_kernel; match
+# mode on 128-dimensional rows) is entered under that key, with its own name and fingerprint inside
 for pruning in ("l2_knn2_prune_kernel", "l2_knn2_cascade_kernel", "l2_knn2_half_kernel"):
     if pruning in vals:
         vals["l2_knn2_mfma_kernel"] = vals.pop(pruning)

@@ -13,7 +13,7 @@ above the kernel; l2_finish_queries<PRUNE> has the proof): per (query, half) wit
   not ea < R eb -> no match;  ea < R eb and ea < R PL -> the best seen row;  else the exact scan.
 Distances are exact here (integer-valued rows: float32 sums below 2^24), as the kernel's are for such pairs.
    python tools/prefix_prune_model.py --filter pairnorm [--gp 12] ...
-the cascade of l2_knn2_cascade_kernel: the pair-norm filter in front of the prefix test (model_pair_cascade).
+the cascade of l2_knn2_half_kernel<…, MODE 20>: the pair-norm filter in front of the prefix test (model_pair_cascade).
    python tools/prefix_prune_model.py --filter half [--gp 12] ...
 the three levels of l2_knn2_half_kernel: the same filter on pair norms rounded up to f16 in front of the cascade (model_pair_levels);
 it must prune no tile the cascade does not prune."""
@@ -140,7 +140,7 @@ def pairnorm_bound(a, b):
 
 
 def model_pair_cascade(a, b, gp, R, filter_only=False):
-    """the cascade of l2_knn2_cascade_kernel: per wave tile the pair-norm filter (8 groups), and behind it, for a tile some lane still
+    """the cascade of l2_knn2_half_kernel<…, MODE 20>: per wave tile the pair-norm filter (8 groups), and behind it, for a tile some lane still
     needs, the prefix test of model_pair on the tile run again from its group 0.  Distances in float64 (exact for the integer-valued
     views; the reference for any other, whose prefix test then carries the certificate's slack as the kernel's does).
     -> model_pair's dict + filtered (tiles the filter pruned), work (MFMA groups run, of 16 a tile)"""
