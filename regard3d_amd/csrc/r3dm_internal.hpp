@@ -287,8 +287,9 @@ struct FinalizeParams {
     uint32_t*     pair_cnt;       // [n_pairs]
 };
 
-// the mutual nearest-neighbour check (kernels_match_mutual.hip; r3dm_set_mutual_matching): runs on nn_idx between the matcher and the
-// finalisation; an accepted entry whose row of I has a nearer row of J (order: distance, row) becomes kNone
+// the mutual nearest-neighbour check (kernels_match_mutual.hip: l2_mutual_batch_kernel<RATIO, G>, l2_mutual_items_kernel<RATIO>,
+// hamming_mutual_kernel<RATIO, W>; r3dm_set_mutual_matching): runs on nn_idx between the matcher and the finalisation; an accepted
+// entry whose row of I has a nearer row of J (order: distance, row) becomes kNone.  RATIO is ratio_form != 0
 struct MutualParams {
     const ImgDev* imgs;
     const uint2*  pairs;          // slot indices (I, J)
@@ -637,8 +638,10 @@ hipError_t launch_l2_exact_items(hipStream_t st, const MatchParams& P, uint32_t 
 // exact scan of the per-pair fallback lists (one workgroup per pair); false return -> no kernel for this G
 hipError_t launch_l2_exact_batch(hipStream_t st, const MatchParams& P, uint32_t G);
 hipError_t launch_hamming_knn2(hipStream_t st, const MatchParams& P, uint32_t words, uint32_t max_n);
-// the mutual check: one workgroup per pair over J's f32 tiles (G with a tensor kernel, dim % 4 == 0) / over the word rows of binary
-// views (8 or 16 words); one workgroup per accepted match over the row-major rows for every other length (count = n_pairs x q_stride)
+// the mutual check, each with P.ratio_form != 0 as its kernel's RATIO: l2_mutual_batch_kernel<RATIO, G>, one workgroup per pair over
+// J's f32 tiles (G with a tensor kernel, dim % 4 == 0); hamming_mutual_kernel<RATIO, W> over the word rows of binary views (8 or 16
+// words); l2_mutual_items_kernel<RATIO>, one workgroup per accepted match over the row-major rows for every other length (count =
+// n_pairs x q_stride)
 hipError_t launch_l2_mutual_batch(hipStream_t st, const MutualParams& P, uint32_t G);
 hipError_t launch_l2_mutual_items(hipStream_t st, const MutualParams& P, uint32_t count);
 hipError_t launch_hamming_mutual(hipStream_t st, const MutualParams& P, uint32_t words);

@@ -177,7 +177,7 @@ def match_collection_mrpt(O, descs, xys, pairs, ratio, n_trees=26, depth=6, vote
 
 
 # ---------------------------------------------------------------------------------------------------- the brute-force loop
-ITEMS_THREADS = 256          # l2_symratio_items_kernel: thread t scans rows t, t + 256, ...
+ITEMS_THREADS = 256          # l2_mutual_items_kernel<true>: thread t scans rows t, t + 256, ...
 
 
 def brute_force_pair(dI, dJ, xyI, xyJ, ratio, squared=True, binary=False, mode="symmetric", bug=None):

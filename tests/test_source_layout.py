@@ -10,6 +10,7 @@ CSRC = os.path.join(ROOT, "regard3d_amd", "csrc")
 TOOLS = os.path.join(ROOT, "tools")
 RETIRED = ("R3DM_FILTER_ONLY_E", "R3DM_FILTER_DEVICE_ONLY", "R3DM_BISECT_")
 RETIRED_SEARCH = ("R3DM_ANN_KNN", "R3DM_HNSW_KNN", "R3DM_MRPT_KNN", "ann_search_body.inc", "hnsw_search_body.inc", "mrpt_query_body.inc")
+RETIRED_SYMRATIO = ("l2_symratio_", "hamming_symratio_")      # the ratio forms are the RATIO instantiations of the mutual kernels
 INCLUDES_HIP = re.compile(r'^[ \t]*#[ \t]*include[ \t]*["<][^">\n]*\.hip[">]', re.M)
 INCLUDES = re.compile(r'^[ \t]*#[ \t]*include[ \t]*["<]([^">\n]*)[">]', re.M)
 
@@ -51,6 +52,13 @@ def test_retired_search_bodies_stay_gone():
     assert len(files) > 10
     bad = [(os.path.relpath(f, ROOT), s) for f in files for s in RETIRED_SEARCH if s in _text(f)]
     assert not bad, f"the macro-cut search bodies are back: {bad}"
+
+
+def test_symmetric_ratio_has_no_kernels_of_its_own():
+    files = list(_files(CSRC))
+    assert any(f.endswith("kernels_match_mutual.hip") for f in files)
+    bad = [(os.path.relpath(f, ROOT), s) for f in files for s in RETIRED_SYMRATIO if s in _text(f)]
+    assert not bad, f"the copies of the mutual kernels are back: {bad}"
 
 
 def test_retired_filter_macros_stay_gone():

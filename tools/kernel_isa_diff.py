@@ -32,6 +32,8 @@ def kernels_of(path):
                 continue
             ins = [re.sub(r"\s*//.*", "", l).strip() for l in m.group(2).splitlines()]
             ins = [l for l in ins if l and not l.endswith(":") and not l.startswith(";")]
+            while ins and ins[-1] in ("s_nop 0", "..."):     # the padding up to the next kernel's alignment: not this kernel's code
+                ins.pop()
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True, text=True).stdout.strip()
             out[re.sub(r"\(.*", "", name).replace("void r3dm::", "").replace("r3dm::", "")] = (ins, res[m.group(1)])
     return out

@@ -1,9 +1,13 @@
 """Cost of the symmetric ratio test (r3dm_set_symmetric_ratio) at BASELINE config C2's size -- 200 views x 8,192
 SIFT-128 rows, 19,900 pairs, ratio 0.6 -- on the f32 tiles and on the integer tiles:
-    python tools/symmetric_ratio_perf.py [--package-root DIR] [--label NAME] [--images N] [--reps R]
+    python tools/symmetric_ratio_perf.py [--package-root DIR] [--label NAME] [--images N] [--reps R] [--kind sift|liop|akaze] [--dim D]
 One process, one context, the collection registered once.  Per tile format the legs the library offers ALTERNATE in one loop (off,
 mutual, symmetric, off, ...), so all see the same clocks; a line holds the median wall time of r3dm_match_pairs with its smallest and
 largest repetition, the matches returned and the three counters.  One JSON line per (tiles, leg).
+
+--kind / --dim go to synth.make_scene and choose the kernel of kernels_match_mutual.hip that the mutual and symmetric legs run: --dim 64 |
+128 | 144 | 256 the tile kernel of G = 8 | 16 | 18 | 32, a length without a tensor kernel (--dim 100) the rows-based kernel, --kind akaze
+(registered with binary=True: 61 bytes of bits in --dim >= 61 bytes, i.e. rows of 16 words) the Hamming kernel.
 
 --package-root: import regard3d_amd from DIR instead of this tree -- a build of the PARENT commit, which has the mutual switch only: its
 legs are "off" and "mutual".  profiles/symmetric_ratio_perf.txt was taken by running parent and tree alternately in one session (parent,
@@ -25,15 +29,17 @@ def main():
     ap.add_argument("--images", type=int, default=200)
     ap.add_argument("--feat", type=int, default=8192)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--kind", choices=("sift", "liop", "akaze"), default="sift")
+    ap.add_argument("--dim", type=int, default=None)
     a = ap.parse_args()
     sys.path.insert(0, a.package_root)
     from regard3d_amd import api, synth
 
-    sc = synth.make_scene(a.images, a.feat, "sift", seed=2002)
+    sc = synth.make_scene(a.images, a.feat, a.kind, seed=2002, dim=a.dim)
     pairs = sc.exhaustive_pairs()
     c = api.Context(0)
     for i in range(sc.n_images):
-        c.set_image(i, sc.descs[i], sc.xys[i], int(sc.widths[i]), int(sc.heights[i]))
+        c.set_image(i, sc.descs[i], sc.xys[i], int(sc.widths[i]), int(sc.heights[i]), binary=a.kind == "akaze")
     has_symmetric = hasattr(c, "set_symmetric_ratio")
     legs = ("off", "mutual", "symmetric") if has_symmetric else ("off", "mutual")
 
