@@ -163,6 +163,14 @@ int r3dm_get_half_filter_counts(r3dm_ctx* ctx, uint64_t* out);
  * is treated differently by it, only the filter's work on such a tile is saved.  r3dm_get_level2_skip_counts: the tiles of the last
  * r3dm_match_pairs call that went from the f16 level straight to the restart (0 with the f16 level off). */
 int r3dm_get_level2_skip_counts(r3dm_ctx* ctx, uint64_t* out);
+/* The tests that decide a tile at these levels ask whether ONE of a lane's 16 keys lies at or below a threshold.  Where no key can
+ * be a NaN or -inf, the minimum of the keys answers that (default on): a batch whose views all have max |row|^2 below 2^28 -- known on
+ * the host, no synchronisation -- runs the kernel with its tile tests in that form, every other batch the general form.  Every tile
+ * is decided as before, so the tiles skipped, all counters above and every result are the same with the switch on or off, on any
+ * data; only the time differs.  Off runs the kernel the library ran before.  r3dm_get_min_tile_test_counts: the pairs of the last
+ * r3dm_match_pairs call that the three-level kernel matched in the min form (out[0]) and in the general form (out[1]). */
+int r3dm_set_min_tile_test(r3dm_ctx* ctx, int enable);
+int r3dm_get_min_tile_test_counts(r3dm_ctx* ctx, uint64_t out[2]);
 
 /* Opt-in split-f16 nominator of the L2 matcher for REAL-valued descriptors (default off; no reference counterpart) -- LIOP-144,
  * normalised SIFT: what Regard3D actually matches (src/Regard3DFeatures.h:44-48).  Their matching is always "nominate on
@@ -992,6 +1000,8 @@ int r3dm_multi_get_pair_filter_counts(r3dm_multi* m, uint64_t* out);           /
 int r3dm_multi_set_half_filter(r3dm_multi* m, int enable);          /* r3dm_set_half_filter on every context */
 int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
+int r3dm_multi_set_min_tile_test(r3dm_multi* m, int enable);        /* r3dm_set_min_tile_test on every context */
+int r3dm_multi_get_min_tile_test_counts(r3dm_multi* m, uint64_t out[2]);       /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_set_match_budget(r3dm_multi* m, int enable, uint32_t max_rows);                                 /* on every context: each budgets its own shard */

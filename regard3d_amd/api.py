@@ -54,6 +54,7 @@ EXPORTS = [
     "r3dm_get_pair_filter_counts", "r3dm_multi_get_pair_filter_counts",
     "r3dm_set_half_filter", "r3dm_get_half_filter_counts", "r3dm_multi_set_half_filter", "r3dm_multi_get_half_filter_counts",
     "r3dm_get_level2_skip_counts", "r3dm_multi_get_level2_skip_counts",
+    "r3dm_set_min_tile_test", "r3dm_get_min_tile_test_counts", "r3dm_multi_set_min_tile_test", "r3dm_multi_get_min_tile_test_counts",
     "r3dm_detect_akaze_msurf", "r3dm_detect_akaze_msurf_batch",
     "r3dm_vocab_sample", "r3dm_vocab_from_rows", "r3dm_vocab_info", "r3dm_vocab_words", "r3dm_vocab_free", "r3dm_view_signatures", "r3dm_propose_pairs",
     "r3dm_vocab_report",
@@ -473,6 +474,10 @@ def load_library():
     L.r3dm_multi_get_half_filter_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_get_level2_skip_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_multi_get_level2_skip_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_set_min_tile_test.argtypes = [vp, C.c_int]
+    L.r3dm_get_min_tile_test_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_multi_set_min_tile_test.argtypes = [vp, C.c_int]
+    L.r3dm_multi_get_min_tile_test_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
@@ -1540,6 +1545,17 @@ class Context:
         self._check(self._L.r3dm_get_level2_skip_counts(self._h, C.byref(out)), "r3dm_get_level2_skip_counts")
         return int(out.value)
 
+    def set_min_tile_test(self, enable: bool = True):
+        """the min form of the three levels' tile tests, default on (include/r3dm.h: r3dm_set_min_tile_test); it decides every tile as
+        the general form does, so graphs and the other counters are the same either way"""
+        self._check(self._L.r3dm_set_min_tile_test(self._h, int(bool(enable))), "r3dm_set_min_tile_test")
+
+    def min_tile_test_counts(self):
+        """(pairs matched in the min form, pairs matched in the general form) by the three-level kernel in the last match_pairs call"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.r3dm_get_min_tile_test_counts(self._h, out), "r3dm_get_min_tile_test_counts")
+        return int(out[0]), int(out[1])
+
     def set_mutual_matching(self, enable: bool = True):
         """opt-in mutual nearest-neighbour matching (include/r3dm.h: r3dm_set_mutual_matching): a match (i, j) of match_pairs and the
         approximate matchers is kept iff j is the nearest row of J to row i under (distance, row index); Stats.n_mutual_checked /
@@ -2180,6 +2196,16 @@ class MultiContext:
         out = C.c_uint64(0)
         self._check(self._L.r3dm_multi_get_level2_skip_counts(self._h, C.byref(out)), "r3dm_multi_get_level2_skip_counts")
         return int(out.value)
+
+    def set_min_tile_test(self, enable: bool = True):
+        """r3dm_multi_set_min_tile_test: Context.set_min_tile_test on every context"""
+        self._check(self._L.r3dm_multi_set_min_tile_test(self._h, int(bool(enable))), "r3dm_multi_set_min_tile_test")
+
+    def min_tile_test_counts(self):
+        """(min form, general form) pairs, summed over the contexts' last match calls"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.r3dm_multi_get_min_tile_test_counts(self._h, out), "r3dm_multi_get_min_tile_test_counts")
+        return int(out[0]), int(out[1])
 
     def set_mutual_matching(self, enable: bool = True):
         """r3dm_multi_set_mutual_matching: Context.set_mutual_matching on every context"""

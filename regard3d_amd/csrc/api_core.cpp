@@ -804,6 +804,20 @@ extern "C" int r3dm_get_level2_skip_counts(r3dm_ctx* c, uint64_t* out)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_set_min_tile_test(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->min_tile_test = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_get_min_tile_test_counts(r3dm_ctx* c, uint64_t out[2])
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    out[0] = c->prune_totals.min_pairs; out[1] = c->prune_totals.general_pairs;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_set_split_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;

@@ -348,7 +348,16 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
     mp.fb_cnt = reinterpret_cast<uint32_t*>(fbh + 1);
     mp.fb_q = mp.fb_cnt + P;
     const bool halves = prunes && c->half_filter;          // the f16 level in front of the filter (r3dm_set_half_filter)
-    mp.prune = c->prefix_pruning ? (halves ? 3u : 1u) : 0u;
+    // the three levels' tile tests take their min form (MatchParams::prune bit 2) where no level-1 key can be a NaN or -inf: every view
+    // of the batch has max |row|^2 below kMinTileTestNormBits (kernels_match.hip above the kernel has the derivation).  The
+    // statistics are on the host since sync_view_stats above; a view without them keeps the batch on the general form.
+    bool min_form = halves && c->min_tile_test;
+    for (size_t i = 0; min_form && i < batch_slots.size(); ++i) {
+        const HostImage& v = *c->imgs[batch_slots[i]];
+        min_form = v.stats_valid && v.stat_bits[0] < kMinTileTestNormBits;
+    }
+    if (halves) (min_form ? c->prune_totals.min_pairs : c->prune_totals.general_pairs) += P;
+    mp.prune = c->prefix_pruning ? (halves ? (min_form ? 7u : 3u) : 1u) : 0u;
     mp.prune_cnt = &fbh->prune;
     // ---- stage: the pruning kernel's tables
     std::vector<uint64_t> tr;                              // (lives to the end of the call, like hp: the copies from it are asynchronous)

@@ -247,6 +247,21 @@ extern "C" int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out)
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_min_tile_test(r3dm_multi* m, int enable)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) r3dm_set_min_tile_test(c, enable);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_multi_get_min_tile_test_counts(r3dm_multi* m, uint64_t out[2])
+{
+    if (!m || !out) return R3DM_ERR_INVALID;
+    out[0] = out[1] = 0;
+    for (r3dm_ctx* c : m->ctx) { out[0] += c->prune_totals.min_pairs; out[1] += c->prune_totals.general_pairs; }
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
 {
     if (!m) return R3DM_ERR_INVALID;

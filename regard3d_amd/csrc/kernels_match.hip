@@ -663,8 +663,35 @@ void l2_knn2_prune_kernel(const MatchParams P)
 // A key that is -inf or NaN comes from an f16 pair norm of +inf (or a NaN), whose loss no L bounds: only a key above -inf counts (a NaN
 // fails both compares).  thrS is -inf for a dead lane and while thrF = +inf; a NaN thrS (M = +inf) skips nothing.  A tile may still run
 // level 2 when it need not; the skip never fires where level 2 would prune.
-// MODE (developer ablations): 0 the three levels, level 2 skipped where it cannot prune | 1 level 1, then straight to the restart
-// (timing only: other tiles are pruned) | 2 the three levels without the skip.
+// MODE: 0 the three levels, level 2 skipped where it cannot prune | 3 the same with the tile tests in their min form (below);
+// developer ablations: 1 level 1, then straight to the restart (timing only: other tiles are pruned) | 2 the three levels without the
+// skip | 4 level 1 alone: no tile behind tile 0 goes on | 5 level 1 alone without its decision (4 and 5: timing only).
+// THE MIN FORM OF THE TILE TESTS (MODE 3; r3dm_set_min_tile_test, default on).  The tests above ask of a lane's 16 keys of a query tile
+// "is ONE key not above thr?" (the objections of level 1, of level 2, of the restart's prefix test) and "is ONE key above -inf at or below
+// thrS?" (the skip): 16 v_cmp that alternate with 16 s_or on every tile, twice on a tile that objects.  Both are questions about the
+// MINIMUM of the keys -- unless a key is a NaN (the general form lets it object; v_min3_f32 returns the operand that is no NaN and
+// loses it) or -inf (the general form keeps it from the skip; a minimum cannot tell it from a finite key beside it).  Where no key is
+// either, with m = min k (tile_key_min: 8 v_min3_f32 / v_min_f32 per query tile, no scalar unit),
+//     any(!(k > thr))  ==  !(m > thr)          any(k <= thrS and k > -inf)  ==  m <= thrS       for ANY thr, thrS (NaN, +-inf included),
+// so every tile is decided as in MODE 0 -- the same tiles pruned, the same skips, lists, T, plT and counters -- and the skip reads
+// the minimum the objection made.  A dead lane (thrH = thrS = -inf) neither objects nor skips, the first tile (thrH = +inf) objects.
+// THE RULE: both views of every pair of the batch have ImgDev::max_norm_bits < the bits of 2^28, as unsigned integers (run_match_batch
+// decides per batch from the host's copy, kMinTileTestNormBits; any other batch runs MODE 0).  A NaN or +inf norm has larger bits
+// than every finite one, so the data is finite, and every STORED norm N (the fma chain of staging, >= (1 - 128 u) |row|^2, u = 2^-24)
+// is below 2^28: |row|^2 < 2^28 (1 + 2^-16), every member and every pair |(x, y)| <= |row| < 2^14 (1 + 2^-17).  Then
+//   the f32 pair norms   s <= (1 + 2^-22) |(x, y)| < 16,384.2 (stage_pairnorm_kernel's root and nudge)
+//   the f16 pair norms   h <= (1 + 2^-10) s + 2^-14 < 16,401 (pairnorm_to_half: the round-up, the floor), far below 32,752, so the
+//                        query fragment -2 h is a finite f16 (exact: a power of two) and no h is +inf
+//   level 1   a product ha (-2 hb) is below 5.4e8 in magnitude and exact in f32; 64 of them, in any order and with any roundings,
+//             stay below 3.5e10 beside an accumulator that starts at N < 2^28, or at +inf on a padding row -- whose pair norms are 0,
+//             times finite factors: no 0 x inf.  Every key kh_c is finite, or +inf on a padding row: never a NaN, never -inf
+//   level 2   the same with s for h: products sa (-2 sb) below 5.4e8, each rounded once, 64 of them: kf_c finite or +inf
+//   the restart's prefix test   starts at the prefix norm (at most N, or +inf on a padding row, whose members are 0) and adds 96
+//             products a_i (-2 b_i) below 5.4e8 each: finite or +inf.
+// c2's rows have |row|^2 = 2^18.  tests/test_min_tile_test_rule.py has the worst cases in numpy (all of a row in one pair at 2^28 - 16).
+// WHAT ELSE MODE 3 DOES: the first MFMA of a tile takes the norm registers as its C operand for BOTH query tiles (l2_halfnorm_tile_filter
+// <CSTART>: one 16-register tuple the four norm loads fill; MODE 0 copies it for the second query tile, 8 v_mov_b64).  Per tile the
+// decision is 17 VALU + 2 v_cmp + 1 s_or (MODE 0: 32 v_cmp + 32 s_or), the skip test 2 v_cmp + 1 s_or (64 v_cmp + 32 s_and + 32 s_or).
 // ------------------------------------------------------------------------------------------------
 constexpr float kHalfMarginFactor = 400.0f * 5.9604644775390625e-08f;       // 400 x 2^-24
 constexpr float kHalfMarginAbs = 2.9103830456733704e-11f;                   // 2^-35
@@ -672,7 +699,7 @@ constexpr float kSkipLossFactor = 0.001953125f + 0.0001220703125f + 3.0517578125
 constexpr float kSkipLossAbs = 0.00390625f + 3.0517578125e-05f;                               // 2^-8 + 2^-15
 
 // ------------------------------------------------------------------------------------------------
-// Both forms are ONE kernel, and the template argument MODE also says how many levels run: MODE = 0 | 1 | 2 are the three levels with
+// Both forms are ONE kernel, and the template argument MODE also says how many levels run: MODE = 0 .. 5 are the three levels with
 // the f16 level's MODE above, MODE = 20 | 21 the two levels (the cascade: pair-norm filter, then the restart) with the cascade's
 // MODE 0 | 1 above.  (The name and the argument list are the three-level kernel's, so that its symbol -- which
 // profiles/pmc_traffic.json and the tracked profiles name -- stays.)
@@ -694,9 +721,10 @@ template <int G, int GP, int NJ, int PF, int WPS, int MODE>
 __global__ __launch_bounds__(256, WPS)
 void l2_knn2_half_kernel(const MatchParams P)
 {
-    static_assert((MODE >= 0 && MODE <= 2) || MODE == 20 || MODE == 21, "three levels: 0 | 1 | 2; two levels: 20 | 21");
+    static_assert((MODE >= 0 && MODE <= 5) || MODE == 20 || MODE == 21, "three levels: 0 .. 5; two levels: 20 | 21");
     constexpr bool H = MODE < 20;                     // the f16 level in front
-    constexpr int ABL = MODE % 20;                    // the form's own MODE (the header comments)
+    constexpr bool MIN = MODE == 3;                   // the min form of the three levels' tile tests
+    constexpr int ABL = MIN ? 0 : MODE % 20;          // the form's own MODE (the header comments)
     constexpr int GR = G / 2, GH = G / 4, G1 = H ? GH : GR;      // groups of a reduced tile, blocks of an f16 tile, what level 1 contracts
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -763,6 +791,7 @@ void l2_knn2_half_kernel(const MatchParams P)
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; thrH[nj] = R3DM_INF; thrS[nj] = -R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned, and never skips level 2)
     uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0, n_half = 0, n_skip = 0;      // wave-uniform
+    float sink = 0.0f;                                // (MODE 5: what consumes the keys)
     bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
 
     if (nI >= 2) {
@@ -809,7 +838,7 @@ void l2_knn2_half_kernel(const MatchParams P)
         // one tile: `live` says whether `prev` holds keys to fold, and afterwards whether `cur` does
         auto tile = [&](uint32_t t, f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ], bool live) __attribute__((always_inline)) -> bool {
             if constexpr (H)
-                l2_halfnorm_tile_filter<GH, NJ, PF>(rh, rn, voffA, voffN, t * tileHB, (t + 1) * 128u, abuf, nrm, bq1, cur, prev, st,
+                l2_halfnorm_tile_filter<GH, NJ, PF, MIN>(rh, rn, voffA, voffN, t * tileHB, (t + 1) * 128u, abuf, nrm, bq1, cur, prev, st,
                                                     (t - 1) * 32u + hb, live);
             else
                 l2_pairnorm_tile_filter<GR, NJ, PF>(rr, rn, voffA, voffN, t * tileRB, (t + 1) * 128u, abuf, nrm, bq1, cur, prev, st,
@@ -817,19 +846,36 @@ void l2_knn2_half_kernel(const MatchParams P)
             if (live) { refresh(); pruned_under_thr = false; }
             n_tested += 1u;
             // a lane objects when one of its level-1 keys is not above its threshold (written so that a NaN key objects)
+            // (MODE 4 and 5 leave tile 0 to the three levels, so that the lists hold rows and no query goes to the exact scan)
+            if constexpr (MODE == 5) {                  // (timing only: level 1 without its decision -- one add per query tile keeps the MFMAs)
+                if (t != 0) {
+#pragma unroll
+                    for (int nj = 0; nj < NJ; ++nj) sink += cur[nj][0];
+                    n_pruned += 1u;
+                    return false;
+                }
+            }
             bool obj = false;
+            float m[NJ];                                // (the min form: the smallest of the lane's keys, per query tile)
+            if constexpr (MIN) {
+                tile_key_min<NJ>(cur, m);
 #pragma unroll
-            for (int nj = 0; nj < NJ; ++nj)
+                for (int nj = 0; nj < NJ; ++nj) obj |= !(m[nj] > thrH[nj]);
+            } else {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > (H ? thrH[nj] : thrF[nj]));
+                for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > (H ? thrH[nj] : thrF[nj]));
+            }
             if (__builtin_amdgcn_ballot_w64(obj) == 0ull) {
                 n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true;
                 if constexpr (H) n_half += 1u;
                 return false;
             }
+            if constexpr (MODE == 4) { if (t != 0) { n_pruned += 1u; return false; } }      // (timing only: level 1 alone -- no tile behind tile 0 goes on)
             // (two levels, MODE 21: the filter alone -- the restart never stops a tile)
             auto restart = [&]() __attribute__((always_inline)) -> bool {
-                const bool on = l2_prune_tile_restart<G, GP, NJ, H || ABL == 0>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
+                const bool on = l2_prune_tile_restart<G, GP, NJ, H || ABL == 0, MIN>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
                 if (!on) { n_pruned += 1u; pruned_under_thr = true; }
                 return on;
             };
@@ -838,19 +884,30 @@ void l2_knn2_half_kernel(const MatchParams P)
             // to itself: with one copy entered from both sides the register allocator spills 70 registers, with two it spills none
             if constexpr (H && ABL == 0) {
                 bool far = false;
+                if constexpr (MIN) {                    // (no key is -inf: the same minimum answers)
 #pragma unroll
-                for (int nj = 0; nj < NJ; ++nj)
+                    for (int nj = 0; nj < NJ; ++nj) far |= m[nj] <= thrS[nj];
+                } else {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) far |= (cur[nj][r] <= thrS[nj]) && (cur[nj][r] > -R3DM_INF);
+                    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) far |= (cur[nj][r] <= thrS[nj]) && (cur[nj][r] > -R3DM_INF);
+                }
                 if (__builtin_amdgcn_ballot_w64(far) != 0ull) { n_skip += 1u; return restart(); }
             }
             if constexpr (H && ABL != 1) {
                 l2_pairnorm_tile_stream<GR, NJ>(rr, rn, voffA, voffN, t * tileRB, t * 128u, rqr, soffQR, cur);
                 obj = false;
+                if constexpr (MIN) {
+                    tile_key_min<NJ>(cur, m);
 #pragma unroll
-                for (int nj = 0; nj < NJ; ++nj)
+                    for (int nj = 0; nj < NJ; ++nj) obj |= !(m[nj] > thrF[nj]);
+                } else {
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrF[nj]);
+                    for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thrF[nj]);
+                }
                 if (__builtin_amdgcn_ballot_w64(obj) == 0ull) { n_pruned += 1u; n_filtered += 1u; pruned_under_thr = true; return false; }
             }
             return restart();
@@ -894,6 +951,7 @@ void l2_knn2_half_kernel(const MatchParams P)
         if (n_filtered) atomicAdd(&P.prune_cnt->n_filtered, (unsigned long long)n_filtered);
         if (n_half) atomicAdd(&P.prune_cnt->n_half, (unsigned long long)n_half);         // (both stay 0 with two levels)
         if (n_skip) atomicAdd(&P.prune_cnt->n_skip, (unsigned long long)n_skip);
+        if constexpr (MODE == 5) { if (sink == 12345.0f) atomicAdd(&P.prune_cnt->n_skip, 1ull); }
     }
     l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, he, ce, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
 }
@@ -980,6 +1038,11 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
                 case 131: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 1, 2, 0>(st, P, max_nj_tiles);
                 case 132: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 0>(st, P, max_nj_tiles);
                 case 133: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 2>(st, P, max_nj_tiles);
+                //   134: level 1 alone, no tile ever goes on | 135: level 1 alone without its decision (both timing only) | 136: the
+                //   general form of the tile tests where the min form would run (results and counters unchanged)
+                case 134: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 4>(st, P, max_nj_tiles);
+                case 135: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 5>(st, P, max_nj_tiles);
+                case 136: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
                 default: break;
             }
         }
@@ -990,6 +1053,8 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
     // as the cascade does (kPruneMaxR): it prunes what the filter prunes, at a sixteenth of the matrix cycles, and where the filter
     // stops few tiles it adds 256 cycles to a tile of 4,096 and more (profiles/half_filter_model_c2.txt has R = 0.49).
     if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R)) {
+        // ... and with the tile tests in their min form where the batch's norms allow it (run_match_batch: MatchParams::prune bit 2)
+        if ((P.prune & 6u) == 6u) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 3>(st, P, max_nj_tiles);
         if ((P.prune & 2u) != 0) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
         return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 20>(st, P, max_nj_tiles);
     }

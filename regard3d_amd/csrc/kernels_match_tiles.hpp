@@ -9,6 +9,7 @@
 //   l2_prune_tile_prefix / _finish     ... stopped after a prefix of its dimensions when no lane needs the rest (match mode)
 //   l2_pairnorm_tile_filter / l2_prune_tile_restart   ... ruled out on its pair norms first; a tile that is not starts over
 //   l2_halfnorm_tile_filter / l2_pairnorm_tile_stream ... ruled out on its pair norms in f16 before that (v_mfma_f32_32x32x16_f16)
+//   tile_key_min                       the minimum of a lane's 16 keys per query tile, a v_min3_f32 tree (the min form of those tile tests)
 //   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
 //   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
 //   split_tile_step                    ... on the split-f16 planes                (3 x v_mfma_f32_32x32x16_f16)
@@ -261,6 +262,39 @@ __device__ __forceinline__ bool l2_prune_tile_finish(__amdgpu_buffer_rsrc_t ra, 
 }
 
 // ------------------------------------------------------------------------------------------------
+// The minimum of a lane's 16 keys, per query tile, as a tree of v_min3_f32: five over 15 keys, two over their results and the 16th
+// key, one v_min_f32 -- 8 VALU instructions three deep, no scalar unit, where 16 compares alternate with 16 s_or.  For the tile tests
+// of the min form of l2_knn2_half_kernel, whose keys are never NaN (kernels_match.hip above the kernel: v_min3_f32 returns the
+// operand that is no NaN, so a NaN key would be lost).
+// Written as inline assembly: fminf() on an MFMA result gets a canonicalising v_max_f32 x, x in front of every input (the compiler
+// cannot know the result to be quiet), which doubles the count.  The hazard recogniser does not look into inline assembly, and a
+// VALU read of an MFMA result needs wait states; so one key of the LAST query tile passes through an instruction the compiler sees
+// (v_max_f32 x, x, the value itself), every first-level instruction names its result as an input, and the matrix pipe retires in
+// order: the wait the compiler puts in front of that one instruction covers every read below (int_tile_step does the same with its
+// block 0).
+// ------------------------------------------------------------------------------------------------
+// v_min3_f32 (vmin3, kernels_match_common.hpp) that the compiler may not move in front of `after`
+__device__ __forceinline__ float vmin3_after(float a, float b, float c, float after)
+{
+    float m;
+    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(m) : "v"(a), "v"(b), "v"(c), "v"(after));
+    return m;
+}
+template <int NJ>
+__device__ __forceinline__ void tile_key_min(const f32x16 (&k)[NJ], float (&m)[NJ])
+{
+    const float first = __builtin_canonicalizef(k[NJ - 1][0]);      // v_max_f32 x, x: the key itself (no key is a NaN)
+#pragma unroll
+    for (int nj = 0; nj < NJ; ++nj) {
+        const f32x16& x = k[nj];
+        const float t0 = vmin3_after(nj == NJ - 1 ? first : x[0], x[1], x[15], first);
+        const float t1 = vmin3_after(x[2], x[3], x[4], first), t2 = vmin3_after(x[5], x[6], x[7], first);
+        const float t3 = vmin3_after(x[8], x[9], x[10], first), t4 = vmin3_after(x[11], x[12], x[13], first);
+        m[nj] = vmin2(vmin3(t0, t1, t2), vmin3(t3, t4, x[14]));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // f32 tiles, match mode: the pair-norm filter in front of the prefix test (l2_knn2_half_kernel; Top2 lists only).
 // The same contraction over the REDUCED rows (the table behind MatchParams::prune_cnt: GR = G / 2 groups of 8 pair norms per tile,
 // tiles contiguous), accumulators started from the rows' FULL norms: after GR groups they hold kf = |a|^2 - 2 sum_k sa_k sb_k, and
@@ -321,7 +355,10 @@ __device__ __forceinline__ void l2_pairnorm_tile_filter(__amdgpu_buffer_rsrc_t r
 // blocks; the A window runs on from tile to tile.  The caller decides on `cur`.
 //   v_mfma_f32_32x32x16_f16: A lane l = A[i = l&31][k = 8 (l>>5) .. + 7], B lane l = B[k = 8 (l>>5) .. + 7][j = l&31], D as the f32 form.
 // ------------------------------------------------------------------------------------------------
-template <int GH, int NJ, int PF>
+// CSTART (the min form of the kernel): every query tile's first MFMA takes the norms as its C operand -- one 16-register tuple, filled
+// by the four norm loads -- and the next tile's norms are fetched behind those MFMAs, so no accumulator is started by a copy.  The keys
+// are the same floats: C enters the contraction exactly as a started accumulator does.
+template <int GH, int NJ, int PF, bool CSTART = false>
 __device__ __forceinline__ void l2_halfnorm_tile_filter(__amdgpu_buffer_rsrc_t rh, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
                                                         uint32_t soffH, uint32_t soffN, f32x4 (&abuf)[PF], f32x4 (&nrm)[4],
                                                         const f32x4 (&bqh)[NJ][GH], f32x16 (&cur)[NJ], const f32x16 (&prev)[NJ],
@@ -329,21 +366,36 @@ __device__ __forceinline__ void l2_halfnorm_tile_filter(__amdgpu_buffer_rsrc_t r
 {
     static_assert(GH % PF == 0, "the window keeps block g in slot g % PF from tile to tile");
     // soffH: byte offset of this tile's f16 block 0; soffN: of the NEXT tile's norms
+    if constexpr (!CSTART) {
 #pragma unroll
-    for (int nj = 0; nj < NJ; ++nj)
+        for (int nj = 0; nj < NJ; ++nj)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) cur[nj][r] = nrm[r >> 2][r & 3];
+            for (int r = 0; r < 16; ++r) cur[nj][r] = nrm[r >> 2][r & 3];
+    }
 #pragma unroll
     for (int g = 0; g < GH; ++g) {
         const f16x8 a = __builtin_bit_cast(f16x8, abuf[g % PF]);
         abuf[g % PF] = bload16(rh, voffA, soffH + (uint32_t)(g + PF) * 1024u);
+        if (CSTART && g == 0) {
+            const f32x16 n16 = __builtin_shufflevector(__builtin_shufflevector(nrm[0], nrm[1], 0, 1, 2, 3, 4, 5, 6, 7),
+                                                       __builtin_shufflevector(nrm[2], nrm[3], 0, 1, 2, 3, 4, 5, 6, 7),
+                                                       0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(f16x8, bqh[nj][g]), n16, 0, 0, 0);
+            // (the tuple stays live behind the last MFMA, or that one is tied to it and gets a copy; and no norm load moves in front)
+            asm volatile("" : : "v"(n16));
+            __builtin_amdgcn_sched_barrier(0);
+        }
         if (g == 0) {   // next tile's norms: as early as the accumulators' start allows
 #pragma unroll
             for (int qd = 0; qd < 4; ++qd) nrm[qd] = bload16(rn, voffN, soffN + (uint32_t)qd * 32u);
         }
+        if (!(CSTART && g == 0)) {
 #pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
-            cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
+            for (int nj = 0; nj < NJ; ++nj)
+                cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, __builtin_bit_cast(f16x8, bqh[nj][g]), cur[nj], 0, 0, 0);
+        }
         if (prev_live) {
             // this block's share of the previous tile's keys: test-and-skip as in l2_tile_step<PIPE 3>
             bool any = false;
@@ -417,7 +469,8 @@ __device__ __forceinline__ void l2_pairnorm_tile_stream(__amdgpu_buffer_rsrc_t r
 // view's tiles; the first W groups' latency is exposed once per such tile -- the other wave of the SIMD has the matrix pipe meanwhile.
 // The filter's window (next reduced tile) and norms stay untouched.  Returns whether `cur` holds the keys of a finished tile
 // (wave-uniform).  TEST_PREFIX = false (developer ablation): the tile always finishes.
-template <int G, int GP, int NJ, bool TEST_PREFIX>
+// MIN (the min form of the kernel): the prefix test on tile_key_min's minimum -- the same verdict where no key is a NaN.
+template <int G, int GP, int NJ, bool TEST_PREFIX, bool MIN = false>
 __device__ __forceinline__ bool l2_prune_tile_restart(__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
                                                       uint32_t soffA, uint32_t soffN, uint32_t soffP, __amdgpu_buffer_rsrc_t rq,
                                                       const uint32_t (&soffQ)[NJ], f32x16 (&cur)[NJ], const float (&thr)[NJ])
@@ -461,10 +514,17 @@ __device__ __forceinline__ bool l2_prune_tile_restart(__amdgpu_buffer_rsrc_t ra,
     if constexpr (TEST_PREFIX) {
         // a lane objects when one of its prefix keys is not above its threshold (written so that a NaN key objects)
         bool obj = false;
+        if constexpr (MIN) {
+            float m[NJ];
+            tile_key_min<NJ>(cur, m);
 #pragma unroll
-        for (int nj = 0; nj < NJ; ++nj)
+            for (int nj = 0; nj < NJ; ++nj) obj |= !(m[nj] > thr[nj]);
+        } else {
 #pragma unroll
-            for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thr[nj]);
+            for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) obj |= !(cur[nj][r] > thr[nj]);
+        }
         if (__builtin_amdgcn_ballot_w64(obj) == 0ull) return false;
     }
 #pragma unroll

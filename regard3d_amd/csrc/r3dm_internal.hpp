@@ -29,6 +29,9 @@ constexpr uint32_t kTileRows = 32;            // rows per MFMA tile (32x32x2 f32
 constexpr uint32_t kSlackBytes = 32768;
 // l2_knn2_prune_kernel tests a tile after GP = kPrefixGroups of its 16 groups of 8 dimensions (DESIGN.md, f32 kernel section)
 constexpr uint32_t kPrefixGroups = 12;
+// the min form of l2_knn2_half_kernel's tile tests serves views whose ImgDev::max_norm_bits lies below the bits of 2^28 (compared as
+// unsigned integers, so a NaN norm lies above): then no key of any level is a NaN or -inf (kernels_match.hip above the kernel)
+constexpr uint32_t kMinTileTestNormBits = 0x4D800000u;
 __host__ __device__ inline uint32_t prefix_norm_offset(uint32_t n_tiles) { return n_tiles * 32u + kSlackBytes / 4u; }      // in floats
 __host__ __device__ inline size_t norms_bytes(uint32_t n_tiles) { return 2 * ((size_t)n_tiles * 128 + kSlackBytes); }
 // the prefix groups of the build that runs: the product's constant; the developer build's R3DM_L2_VARIANT 109 .. 112 pick 9 .. 12
@@ -259,7 +262,8 @@ struct MatchParams {
     uint32_t      fb_slices;      // 1: one workgroup per pair, results emitted directly
     // prefix pruning of the f32 2-NN tiles in match mode (r3dm_set_prefix_pruning; l2_knn2_prune_kernel).  Behind every older field:
     // their offsets are what the other kernels' machine code was compiled with.
-    uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel; bit 1: with the f16 level in front (r3dm_set_half_filter)
+    uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel; bit 1: with the f16 level in front (r3dm_set_half_filter);
+                                  // bit 2: ... and its tile tests in the min form (r3dm_set_min_tile_test; every norm below kMinTileTestNormBits)
     PruneHeader*  prune_cnt;      // the pruning kernels' counters and tables (FbHeader::prune)
 };
 static_assert(sizeof(MatchParams) == 120 && offsetof(MatchParams, prune_cnt) == 112, "kernel arguments: every 2-NN kernel was compiled with this layout");
