@@ -171,6 +171,16 @@ int r3dm_get_level2_skip_counts(r3dm_ctx* ctx, uint64_t* out);
  * r3dm_match_pairs call that the three-level kernel matched in the min form (out[0]) and in the general form (out[1]). */
 int r3dm_set_min_tile_test(r3dm_ctx* ctx, int enable);
 int r3dm_get_min_tile_test_counts(r3dm_ctx* ctx, uint64_t out[2]);
+/* A tile none of these levels rules out starts over on its f32 rows, and that restart first tests a 96-dimension prefix distance --
+ * which prunes most of the tiles that get there.  In front of it (default on, where the f16 level serves): the same prefix test on
+ * the rows rounded to f16, on the f16 matrix instructions -- a sixteenth of its matrix cycles, half its bytes.  Its threshold carries
+ * a margin for the rounding of the rows and the arithmetic of both, so it prunes a tile only if the restart's prefix test would: the
+ * tiles pruned, all counters above and every result are the same with the switch on or off, on any data (elements beyond 32,752 in
+ * magnitude get nothing from it); only the time differs.  Off runs the kernel the library ran before.  The f16 rows are scratch of
+ * the call too (192 bytes more per row).  r3dm_get_half_prefix_counts: the tiles of the last
+ * r3dm_match_pairs call that reached this test (out[0]) and that it pruned (out[1], part of the pruned tiles above). */
+int r3dm_set_half_prefix(r3dm_ctx* ctx, int enable);
+int r3dm_get_half_prefix_counts(r3dm_ctx* ctx, uint64_t out[2]);
 
 /* Opt-in split-f16 nominator of the L2 matcher for REAL-valued descriptors (default off; no reference counterpart) -- LIOP-144,
  * normalised SIFT: what Regard3D actually matches (src/Regard3DFeatures.h:44-48).  Their matching is always "nominate on
@@ -1002,6 +1012,8 @@ int r3dm_multi_get_half_filter_counts(r3dm_multi* m, uint64_t* out);           /
 int r3dm_multi_get_level2_skip_counts(r3dm_multi* m, uint64_t* out);           /* summed over the contexts' last calls */
 int r3dm_multi_set_min_tile_test(r3dm_multi* m, int enable);        /* r3dm_set_min_tile_test on every context */
 int r3dm_multi_get_min_tile_test_counts(r3dm_multi* m, uint64_t out[2]);       /* summed over the contexts' last calls */
+int r3dm_multi_set_half_prefix(r3dm_multi* m, int enable);          /* r3dm_set_half_prefix on every context */
+int r3dm_multi_get_half_prefix_counts(r3dm_multi* m, uint64_t out[2]);         /* summed over the contexts' last calls */
 int r3dm_multi_set_view_priority(r3dm_multi* m, uint32_t view_id, const float* priority, uint32_t n);      /* on every context, as r3dm_multi_set_image replicates the view */
 int r3dm_multi_set_preemptive_matching(r3dm_multi* m, int enable, uint32_t head_rows, uint32_t min_matches);   /* on every context: each gates its own shard */
 int r3dm_multi_set_match_budget(r3dm_multi* m, int enable, uint32_t max_rows);                                 /* on every context: each budgets its own shard */

@@ -55,6 +55,7 @@ EXPORTS = [
     "r3dm_set_half_filter", "r3dm_get_half_filter_counts", "r3dm_multi_set_half_filter", "r3dm_multi_get_half_filter_counts",
     "r3dm_get_level2_skip_counts", "r3dm_multi_get_level2_skip_counts",
     "r3dm_set_min_tile_test", "r3dm_get_min_tile_test_counts", "r3dm_multi_set_min_tile_test", "r3dm_multi_get_min_tile_test_counts",
+    "r3dm_set_half_prefix", "r3dm_get_half_prefix_counts", "r3dm_multi_set_half_prefix", "r3dm_multi_get_half_prefix_counts",
     "r3dm_detect_akaze_msurf", "r3dm_detect_akaze_msurf_batch",
     "r3dm_vocab_sample", "r3dm_vocab_from_rows", "r3dm_vocab_info", "r3dm_vocab_words", "r3dm_vocab_free", "r3dm_view_signatures", "r3dm_propose_pairs",
     "r3dm_vocab_report",
@@ -478,6 +479,10 @@ def load_library():
     L.r3dm_get_min_tile_test_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_multi_set_min_tile_test.argtypes = [vp, C.c_int]
     L.r3dm_multi_get_min_tile_test_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_set_half_prefix.argtypes = [vp, C.c_int]
+    L.r3dm_get_half_prefix_counts.argtypes = [vp, C.POINTER(u64)]
+    L.r3dm_multi_set_half_prefix.argtypes = [vp, C.c_int]
+    L.r3dm_multi_get_half_prefix_counts.argtypes = [vp, C.POINTER(u64)]
     L.r3dm_set_hamming_mfma.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_narrow_tiles.argtypes = [vp, C.c_int]
     L.r3dm_set_knn_hamming_tiles.argtypes = [vp, C.c_int]
@@ -1556,6 +1561,17 @@ class Context:
         self._check(self._L.r3dm_get_min_tile_test_counts(self._h, out), "r3dm_get_min_tile_test_counts")
         return int(out[0]), int(out[1])
 
+    def set_half_prefix(self, enable: bool = True):
+        """the restart's prefix test on f16 rows in front of the restart, default on (include/r3dm.h: r3dm_set_half_prefix); it prunes
+        only tiles the restart's own prefix test would, so graphs and the other counters are the same either way"""
+        self._check(self._L.r3dm_set_half_prefix(self._h, int(bool(enable))), "r3dm_set_half_prefix")
+
+    def half_prefix_counts(self):
+        """(tiles that reached the f16 prefix test, tiles it pruned) in the last match_pairs call"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.r3dm_get_half_prefix_counts(self._h, out), "r3dm_get_half_prefix_counts")
+        return int(out[0]), int(out[1])
+
     def set_mutual_matching(self, enable: bool = True):
         """opt-in mutual nearest-neighbour matching (include/r3dm.h: r3dm_set_mutual_matching): a match (i, j) of match_pairs and the
         approximate matchers is kept iff j is the nearest row of J to row i under (distance, row index); Stats.n_mutual_checked /
@@ -2205,6 +2221,16 @@ class MultiContext:
         """(min form, general form) pairs, summed over the contexts' last match calls"""
         out = (C.c_uint64 * 2)()
         self._check(self._L.r3dm_multi_get_min_tile_test_counts(self._h, out), "r3dm_multi_get_min_tile_test_counts")
+        return int(out[0]), int(out[1])
+
+    def set_half_prefix(self, enable: bool = True):
+        """r3dm_multi_set_half_prefix: Context.set_half_prefix on every context"""
+        self._check(self._L.r3dm_multi_set_half_prefix(self._h, int(bool(enable))), "r3dm_multi_set_half_prefix")
+
+    def half_prefix_counts(self):
+        """(reached the f16 prefix test, pruned by it) tiles, summed over the contexts' last match calls"""
+        out = (C.c_uint64 * 2)()
+        self._check(self._L.r3dm_multi_get_half_prefix_counts(self._h, out), "r3dm_multi_get_half_prefix_counts")
         return int(out[0]), int(out[1])
 
     def set_mutual_matching(self, enable: bool = True):

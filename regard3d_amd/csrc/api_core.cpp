@@ -818,6 +818,20 @@ extern "C" int r3dm_get_min_tile_test_counts(r3dm_ctx* c, uint64_t out[2])
     return R3DM_OK;
 }
 
+extern "C" int r3dm_set_half_prefix(r3dm_ctx* c, int enable)
+{
+    if (!c) return R3DM_ERR_INVALID;
+    c->half_prefix = (enable != 0);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_get_half_prefix_counts(r3dm_ctx* c, uint64_t out[2])
+{
+    if (!c || !out) return R3DM_ERR_INVALID;
+    out[0] = c->prune_totals.prefix16_tested; out[1] = c->prune_totals.prefix16_pruned;
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_set_split_mfma(r3dm_ctx* c, int enable)
 {
     if (!c) return R3DM_ERR_INVALID;

@@ -198,8 +198,10 @@ static float cert_slack_factor(uint32_t G, bool split_or_count_tiles)
 // tiles of the batch's views (one small kernel per view: 4 MB read, 2 MB written at 8192 rows) into one buffer of the context, which
 // the next batch overwrites.  A view therefore holds what it held (r3dm_view_info), and nothing has to follow the views' lifecycle.
 // tr: the host side of the asynchronous copies, the caller keeps it to the end of the call.
-static int stage_pairnorm_scratch(r3dm_ctx* c, const std::vector<uint32_t>& batch_slots, uint32_t G, bool halves, PruneHeader* hdr,
-                                  std::vector<uint64_t>& tr)
+// prefix16: with them the rows' 96-dimension prefixes as f16 too, the f16 prefix test's table (r3dm_set_half_prefix): 6 KiB per tile and
+// no padding, its reads end with a view's last tile (l2_prefix16_tile_stream).
+static int stage_pairnorm_scratch(r3dm_ctx* c, const std::vector<uint32_t>& batch_slots, uint32_t G, bool halves, bool prefix16,
+                                  PruneHeader* hdr, std::vector<uint64_t>& tr)
 {
     constexpr size_t kPad = 4096;                          // the filter's window runs two groups (2 KiB) past a view's last tile
     constexpr size_t kPadH = 8192;                         // the f16 level's window runs four blocks (4 KiB) past a view's last f16 tile
@@ -207,9 +209,10 @@ static int stage_pairnorm_scratch(r3dm_ctx* c, const std::vector<uint32_t>& batc
     const size_t nslots = c->imgs.size();
     size_t total = 0;
     for (uint32_t s : batch_slots)
-        total += (size_t)c->imgs[s]->n_tiles * (G / 2) * 1024 + kPad + (halves ? (size_t)c->imgs[s]->n_tiles * (G / 4) * 1024 + kPadH : 0);
+        total += (size_t)c->imgs[s]->n_tiles * (G / 2) * 1024 + kPad + (halves ? (size_t)c->imgs[s]->n_tiles * (G / 4) * 1024 + kPadH : 0) +
+                 (prefix16 ? (size_t)c->imgs[s]->n_tiles * (kPrefixGroups / 2) * 1024 : 0);
     R3DM_HIP(c, c->d_pairnorm_tiles.ensure(total));
-    tr.assign(2 * nslots + 2, 0);                          // [slots: f32 tiles][slots: f16 tiles][the two tables' addresses]
+    tr.assign(3 * nslots + 3, 0);                          // [slots: f32 tiles][slots: f16 tiles][slots: f16 prefix rows][the three tables' addresses]
     size_t at = 0;
     for (uint32_t s : batch_slots) {
         const HostImage& h = *c->imgs[s];
@@ -217,18 +220,23 @@ static int stage_pairnorm_scratch(r3dm_ctx* c, const std::vector<uint32_t>& batc
         at += (size_t)h.n_tiles * (G / 2) * 1024 + kPad;
         uint16_t* dsth = halves ? reinterpret_cast<uint16_t*>(c->d_pairnorm_tiles.as<unsigned char>() + at) : nullptr;
         if (halves) at += (size_t)h.n_tiles * (G / 4) * 1024 + kPadH;
-        R3DM_HIP(c, launch_stage_pairnorm(c->stream, h.tiled.as<float>(), h.G, h.n_tiles, dst, dsth));
+        uint16_t* dstp = prefix16 ? reinterpret_cast<uint16_t*>(c->d_pairnorm_tiles.as<unsigned char>() + at) : nullptr;
+        if (prefix16) at += (size_t)h.n_tiles * (kPrefixGroups / 2) * 1024;
+        R3DM_HIP(c, launch_stage_pairnorm(c->stream, h.tiled.as<float>(), h.G, h.n_tiles, dst, dsth, dstp));
         tr[s] = (uint64_t)(uintptr_t)dst;
         tr[nslots + s] = (uint64_t)(uintptr_t)dsth;
+        tr[2 * nslots + s] = (uint64_t)(uintptr_t)dstp;
     }
     // the tables of the tiles by slot, and their addresses in the header
-    R3DM_HIP(c, c->d_pairnorm.ensure(8 * 2 * nslots));
-    tr[2 * nslots] = (uint64_t)(uintptr_t)c->d_pairnorm.p;
-    tr[2 * nslots + 1] = (uint64_t)(uintptr_t)(c->d_pairnorm.as<uint64_t>() + nslots);
-    R3DM_HIP(c, hipMemcpyAsync(c->d_pairnorm.p, tr.data(), 8 * 2 * nslots, hipMemcpyHostToDevice, c->stream));
-    static_assert(sizeof hdr->pairnorm == 8 && sizeof hdr->halfnorm == 8, "a table's address is one 64-bit word of tr");
-    R3DM_HIP(c, hipMemcpyAsync(&hdr->pairnorm, &tr[2 * nslots], sizeof hdr->pairnorm, hipMemcpyHostToDevice, c->stream));
-    if (halves) R3DM_HIP(c, hipMemcpyAsync(&hdr->halfnorm, &tr[2 * nslots + 1], sizeof hdr->halfnorm, hipMemcpyHostToDevice, c->stream));
+    R3DM_HIP(c, c->d_pairnorm.ensure(8 * 3 * nslots));
+    tr[3 * nslots] = (uint64_t)(uintptr_t)c->d_pairnorm.p;
+    tr[3 * nslots + 1] = (uint64_t)(uintptr_t)(c->d_pairnorm.as<uint64_t>() + nslots);
+    tr[3 * nslots + 2] = (uint64_t)(uintptr_t)(c->d_pairnorm.as<uint64_t>() + 2 * nslots);
+    R3DM_HIP(c, hipMemcpyAsync(c->d_pairnorm.p, tr.data(), 8 * 3 * nslots, hipMemcpyHostToDevice, c->stream));
+    static_assert(sizeof hdr->pairnorm == 8 && sizeof hdr->halfnorm == 8 && sizeof hdr->prefix16 == 8, "a table's address is one 64-bit word of tr");
+    R3DM_HIP(c, hipMemcpyAsync(&hdr->pairnorm, &tr[3 * nslots], sizeof hdr->pairnorm, hipMemcpyHostToDevice, c->stream));
+    if (halves) R3DM_HIP(c, hipMemcpyAsync(&hdr->halfnorm, &tr[3 * nslots + 1], sizeof hdr->halfnorm, hipMemcpyHostToDevice, c->stream));
+    if (prefix16) R3DM_HIP(c, hipMemcpyAsync(&hdr->prefix16, &tr[3 * nslots + 2], sizeof hdr->prefix16, hipMemcpyHostToDevice, c->stream));
     return R3DM_OK;
 }
 
@@ -357,11 +365,13 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
         min_form = v.stats_valid && v.stat_bits[0] < kMinTileTestNormBits;
     }
     if (halves) (min_form ? c->prune_totals.min_pairs : c->prune_totals.general_pairs) += P;
-    mp.prune = c->prefix_pruning ? (halves ? (min_form ? 7u : 3u) : 1u) : 0u;
+    // the f16 prefix test in front of the restart (r3dm_set_half_prefix: MatchParams::prune bit 3) serves where the three levels serve
+    const bool prefix16 = halves && c->half_prefix;
+    mp.prune = c->prefix_pruning ? (halves ? (min_form ? 7u : 3u) | (prefix16 ? 8u : 0u) : 1u) : 0u;
     mp.prune_cnt = &fbh->prune;
     // ---- stage: the pruning kernel's tables
     std::vector<uint64_t> tr;                              // (lives to the end of the call, like hp: the copies from it are asynchronous)
-    if (prunes) { const int rcs = stage_pairnorm_scratch(c, batch_slots, first.G, halves, mp.prune_cnt, tr); if (rcs != R3DM_OK) return rcs; }
+    if (prunes) { const int rcs = stage_pairnorm_scratch(c, batch_slots, first.G, halves, prefix16, mp.prune_cnt, tr); if (rcs != R3DM_OK) return rcs; }
 
     const double t_dbg1 = now_ms();
     R3DM_HIP(c, hipEventRecord(c->ev0, c->stream));
@@ -407,6 +417,9 @@ int run_match_batch(r3dm_ctx* c, const std::vector<PairJob>& jobs, float ratio_R
         c->prune_totals.filtered += hd.prune.n_filtered;
         c->prune_totals.half += hd.prune.n_half;
         c->prune_totals.skipped += hd.prune.n_skip;
+        // (the f16 prefix test sees every tile the filter leaves: the skipped ones and those level 2 lets through)
+        if (prefix16) c->prune_totals.prefix16_tested += hd.prune.n_tested - hd.prune.n_filtered;
+        c->prune_totals.prefix16_pruned += hd.prune.n_prefix16;
         n_fallback = hd.fb_total[0];
         // ---- rescan
         if (hd.fb_total[0] > 0) {

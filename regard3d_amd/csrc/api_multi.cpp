@@ -262,6 +262,21 @@ extern "C" int r3dm_multi_get_min_tile_test_counts(r3dm_multi* m, uint64_t out[2
     return R3DM_OK;
 }
 
+extern "C" int r3dm_multi_set_half_prefix(r3dm_multi* m, int enable)
+{
+    if (!m) return R3DM_ERR_INVALID;
+    for (r3dm_ctx* c : m->ctx) r3dm_set_half_prefix(c, enable);
+    return R3DM_OK;
+}
+
+extern "C" int r3dm_multi_get_half_prefix_counts(r3dm_multi* m, uint64_t out[2])
+{
+    if (!m || !out) return R3DM_ERR_INVALID;
+    out[0] = out[1] = 0;
+    for (r3dm_ctx* c : m->ctx) { out[0] += c->prune_totals.prefix16_tested; out[1] += c->prune_totals.prefix16_pruned; }
+    return R3DM_OK;
+}
+
 extern "C" int r3dm_multi_set_mutual_matching(r3dm_multi* m, int enable)
 {
     if (!m) return R3DM_ERR_INVALID;

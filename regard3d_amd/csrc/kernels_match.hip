@@ -278,8 +278,28 @@ __device__ __forceinline__ uint16_t pairnorm_to_half(float f)
     return (uint16_t)((__float_as_uint(f) - (112u << 23) + 0x1FFFu) >> 13);
 }
 
+// tiledp16 (may be null): the first 8 kPrefixGroups = 96 dimensions of every row themselves as f16, for the f16 prefix test of
+// l2_knn2_half_kernel: [tile][kPrefixGroups / 2 blocks of 16 dimensions][lane half][32 rows][8 f16], the fragment order of
+// v_mfma_f32_32x32x16_f16, 6 KiB per tile.  The rounding (row_to_half; tests/half_prefix_cases.py restates it in numpy bit for bit):
+//   a NaN stays a NaN;  |x| < 2^-14 becomes +0 (no subnormal is emitted);  |x| > 32,752 becomes a NaN;  any other value is rounded to the
+//   nearest f16, ties to even (32,752 is an f16, so nothing rounds past it): |h - x| <= 2^-11 |x|, or h = 0 and |x| < 2^-14.
+// Why the cut is at 32,752 and gives a NaN, where the pair norms go to +inf above 65,504: the kernel scales the query fragment by -2 IN
+// f16, which is finite for every stored finite value only up to 32,752 (65,504 / 2); and rows have signs, so an infinite factor gives
+// keys of -inf OR +inf (the factors' signs differ) -- and a key of +inf objects to nothing.  A NaN factor makes every key it enters a
+// NaN, which objects whatever the signs are.
+__device__ __forceinline__ uint16_t row_to_half(float f)
+{
+    const uint32_t u = __float_as_uint(f), mag = u & 0x7FFFFFFFu;
+    if (mag > 0x7F800000u) return 0x7E00u;                           // NaN stays NaN: its keys object
+    if (mag > 0x46FFE000u) return 0x7E00u;                           // |x| > 32,752 (+-inf too): NaN as well
+    if (mag < 0x38800000u) return 0u;                                // |x| < 2^-14: +0
+    const uint32_t v = mag - (112u << 23);                           // a normal f16: drop 13 significand bits, to nearest, ties to even
+    return (uint16_t)(((u >> 16) & 0x8000u) | ((v + 0xFFFu + ((v >> 13) & 1u)) >> 13));
+}
+
 __global__ __launch_bounds__(256)
-void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* __restrict__ tiledr, uint16_t* __restrict__ tiledrh)
+void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* __restrict__ tiledr, uint16_t* __restrict__ tiledrh,
+                           uint16_t* __restrict__ tiledp16)
 {
     const uint32_t t = blockIdx.x, GR = G / 2u;
     const float* src = tiled + (size_t)t * G * 256u;
@@ -299,11 +319,21 @@ void stage_pairnorm_kernel(const float* __restrict__ tiled, uint32_t G, float* _
             dsth[(k >> 4) * 512u + ((k >> 3) & 1u) * 256u + r * 8u + (k & 7u)] = pairnorm_to_half(f);
         }
     }
+    if (tiledp16) {
+        constexpr uint32_t GB = kPrefixGroups / 2u;                   // blocks of 16 dimensions
+        uint16_t* dstp = tiledp16 + (size_t)t * GB * 512u;
+        for (uint32_t e = threadIdx.x; e < GB * 512u; e += 256u) {
+            const uint32_t k = e & 7u, r = (e >> 3) & 31u, hh = (e >> 8) & 1u, b = e >> 9;
+            const uint32_t d = 16u * b + 8u * hh + k;                // the dimension; in the f32 tiles: g = d / 8, half (d / 4) & 1
+            dstp[e] = row_to_half(src[(d >> 3) * 256u + ((d >> 2) & 1u) * 128u + r * 4u + (d & 3u)]);
+        }
+    }
 }
-hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr, uint16_t* tiledrh)
+hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr, uint16_t* tiledrh,
+                                 uint16_t* tiledp16)
 {
     if (n_tiles == 0) return hipSuccess;
-    hipLaunchKernelGGL(stage_pairnorm_kernel, dim3(n_tiles), dim3(256), 0, st, tiled, G, tiledr, tiledrh);
+    hipLaunchKernelGGL(stage_pairnorm_kernel, dim3(n_tiles), dim3(256), 0, st, tiled, G, tiledr, tiledrh, tiledp16);
     return hipGetLastError();
 }
 
@@ -665,7 +695,8 @@ void l2_knn2_prune_kernel(const MatchParams P)
 // level 2 when it need not; the skip never fires where level 2 would prune.
 // MODE: 0 the three levels, level 2 skipped where it cannot prune | 3 the same with the tile tests in their min form (below);
 // developer ablations: 1 level 1, then straight to the restart (timing only: other tiles are pruned) | 2 the three levels without the
-// skip | 4 level 1 alone: no tile behind tile 0 goes on | 5 level 1 alone without its decision (4 and 5: timing only).
+// skip | 4 level 1 alone: no tile behind tile 0 goes on | 5 level 1 alone without its decision (4 and 5: timing only) | 8, 9: 4 and 5 in
+// the min form | 6, 7: MODE 0 and 3 with the f16 prefix test in front of the restart (below).
 // THE MIN FORM OF THE TILE TESTS (MODE 3; r3dm_set_min_tile_test, default on).  The tests above ask of a lane's 16 keys of a query tile
 // "is ONE key not above thr?" (the objections of level 1, of level 2, of the restart's prefix test) and "is ONE key above -inf at or below
 // thrS?" (the skip): 16 v_cmp that alternate with 16 s_or on every tile, twice on a tile that objects.  Both are questions about the
@@ -692,14 +723,54 @@ void l2_knn2_prune_kernel(const MatchParams P)
 // WHAT ELSE MODE 3 DOES: the first MFMA of a tile takes the norm registers as its C operand for BOTH query tiles (l2_halfnorm_tile_filter
 // <CSTART>: one 16-register tuple the four norm loads fill; MODE 0 copies it for the second query tile, 8 v_mov_b64).  Per tile the
 // decision is 17 VALU + 2 v_cmp + 1 s_or (MODE 0: 32 v_cmp + 32 s_or), the skip test 2 v_cmp + 1 s_or (64 v_cmp + 32 s_and + 32 s_or).
+// THE F16 PREFIX TEST (MODE 6 | 7 = MODE 0 | 3 with it; r3dm_set_half_prefix, default on).  A tile that gets to the restart first runs
+// the restart's prefix test -- 48 v_mfma_f32_32x32x2_f32 per query tile, 36 KiB -- and three times in four that test prunes it: once
+// more a threshold test whose result reaches no caller.  In front of it: the same test on the rows ROUNDED to f16 (stage_pairnorm_kernel's
+// third table, row_to_half), 6 v_mfma_f32_32x32x16_f16 per query tile and 18 KiB (l2_prefix16_tile_stream), from the same stored prefix
+// norm nP.  No lane has a key kq_c that is not above its thrQ -> the tile is pruned (n_prefix16, part of n_pruned); else the restart as
+// ever, its own prefix test included.  THE INVARIANT: this test prunes a tile only if the restart's prefix test would; then the pruned
+// tiles, the lists, T, plT, the five older counters and every result are those of MODE 0 | 3 on any data.  It holds when
+//     thrQ >= thr + D + eP + eQ:    kp_c >= kp - eP,  kq_c <= kq + eQ,  kq <= kp + D   =>   kq_c > thrQ  implies  kp_c > thr,
+// kp = nP - 2 sum_i a_i q_i the restart's prefix key and kq = nP - 2 sum_i A_i Q_i this test's, both exact on the STORED operands (the f32
+// rows a, q of the tiles; A, Q their f16 values), i over the 96 prefix dimensions.  S = |a_P|^2 + |q_P|^2 <= (1 + 2^-16) M, M = max|a|^2 +
+// |q|^2 on the stored norms as above (a stored norm is at least (1 - 128 u) of its row's), eps = 2^-11, dlt = 2^-14, all operands finite:
+//   D, the operand rounding, D = 2 sum_i |a_i q_i - A_i Q_i|.  row_to_half gives |A - a| <= eps |a| for a value it keeps and A = 0 for
+//           |a| < dlt.  Per dimension: both kept: |a q - A Q| <= ((1 + eps)^2 - 1) |a| |q|;  a flushed: A Q = 0 and |a q| <= dlt |q|;  q
+//           flushed: <= dlt |a| -- ONE term dlt x per dimension, x a member of a or q.  Over the 96 dimensions, twice:
+//             (2 eps + eps^2) 2 sum |a_i| |q_i|  <=  (2^-10 + 2^-22) S
+//             2 dlt sum x  <=  2^-15 S + 96 x 2^-13:   2 d x <= e x^2 + d^2 / e per value (the step of kSkipLoss) with d = dlt, e = 2^-15
+//   eP, the f32 prefix key's evaluation, the matrix unit assumed to TRUNCATE (2 u of the value per product rounding and per addition):
+//             2   the 96 products -2 a_i q_i (-2 q is exact): 2 u x 2 sum |a_i| |q_i| <= 2 u S
+//           384   96 additions into accumulators within nP + 2 sum |a_i| |q_i| <= 2 (1 + 2^-16) M
+//   eQ, the f16 contraction's: the products A (-2 Q) are exact in f32 (11-bit x 11-bit significands; |A|, |Q| <= 32,752 and 0 or >= 2^-14:
+//           -2 Q is a finite f16, no product overflows or underflows);
+//           385   96 additions (16 per MFMA, six MFMAs, in any order) of partial sums and accumulators within nP + (1 + eps)^2 S <= 2.002 M
+//   = (2^-10 + 2^-15 + 2^-22 + 771 u) (1 + 2^-16) M + 3 x 2^-8  <  (2^-10 + 1,288 u) M + 2^-6.4.
+// The kernel takes marginQ = (2^-10 + 2^-14 + 2^-15) M + 2^-6 (kPrefixMarginFactor = 2^-10 + 1,536 u, kPrefixMarginAbs): 248 u M and
+// 0.0039 pay the two roundings of marginQ itself (2 u of it), and thrQ = (thr + marginQ) rounded up by 2^-22 of it, which pays that
+// sum's rounding.  thrQ is lane-constant between two refreshes; the kernel makes it where the test runs, from lane_terms -- on 4 % of
+// the tiles -- because one more register per query tile through the tile loop does not fit (256 VGPRs with it, and a spill).
+// Operands that are not finite, or beyond f16: row_to_half turns a NaN, +-inf and every |x| > 32,752 into a NaN, and a NaN factor makes
+// every key it enters a NaN, which objects (the general form's compare; the min form never sees one, below): such a tile only ever
+// goes on to the restart.  (+-inf would not do: rows have signs, so A (-2 Q) with one infinite factor is -inf OR +inf, and a key of
+// +inf objects to nothing.  The cut is 32,752 = 65,504 / 2 because the kernel scales Q by -2 in f16.)  thr = +inf gives thrQ = +inf, a
+// NaN thr or M = +inf gives a NaN or +inf thrQ: the test objects; a dead lane has thr = -inf and, M finite, thrQ = -inf -- or a NaN,
+// which only objects.  A padding row has nP = +inf and members 0: its key is +inf (or a NaN beside a NaN factor), as the restart's.
+// THE MIN FORM'S RULE reaches the new keys: max |row|^2 < 2^28 (1 + 2^-16) gives |x| < 2^14 (1 + 2^-17), so |A| <= 2^14 (1 + 2^-10)
+// < 32,752: no NaN, -2 Q finite; a product is below 5.4e8 and exact, 96 of them stay below 5.2e10 beside nP < 2^28, or +inf on a
+// padding row, whose members are 0 times finite factors.  Every key kq_c is finite, or +inf on a padding row: never a NaN, never -inf.
+// tools/prefix_prune_model.py --filter half --skip lane --prefix16 restates the test in numpy (profiles/half_prefix_model_c2.txt);
+// tests/test_half_prefix_rule.py has the bound's worst cases.
 // ------------------------------------------------------------------------------------------------
 constexpr float kHalfMarginFactor = 400.0f * 5.9604644775390625e-08f;       // 400 x 2^-24
 constexpr float kHalfMarginAbs = 2.9103830456733704e-11f;                   // 2^-35
 constexpr float kSkipLossFactor = 0.001953125f + 0.0001220703125f + 3.0517578125e-05f;      // 2^-9 + 2^-13 + 2^-15
 constexpr float kSkipLossAbs = 0.00390625f + 3.0517578125e-05f;                               // 2^-8 + 2^-15
+constexpr float kPrefixMarginFactor = 0.0009765625f + 6.103515625e-05f + 3.0517578125e-05f;  // 2^-10 + 2^-14 + 2^-15
+constexpr float kPrefixMarginAbs = 0.015625f;                                                 // 2^-6
 
 // ------------------------------------------------------------------------------------------------
-// Both forms are ONE kernel, and the template argument MODE also says how many levels run: MODE = 0 .. 5 are the three levels with
+// Both forms are ONE kernel, and the template argument MODE also says how many levels run: MODE = 0 .. 9 are the three levels with
 // the f16 level's MODE above, MODE = 20 | 21 the two levels (the cascade: pair-norm filter, then the restart) with the cascade's
 // MODE 0 | 1 above.  (The name and the argument list are the three-level kernel's, so that its symbol -- which
 // profiles/pmc_traffic.json and the tracked profiles name -- stays.)
@@ -721,10 +792,12 @@ template <int G, int GP, int NJ, int PF, int WPS, int MODE>
 __global__ __launch_bounds__(256, WPS)
 void l2_knn2_half_kernel(const MatchParams P)
 {
-    static_assert((MODE >= 0 && MODE <= 5) || MODE == 20 || MODE == 21, "three levels: 0 .. 5; two levels: 20 | 21");
+    static_assert((MODE >= 0 && MODE <= 9) || MODE == 20 || MODE == 21, "three levels: 0 .. 9; two levels: 20 | 21");
     constexpr bool H = MODE < 20;                     // the f16 level in front
-    constexpr bool MIN = MODE == 3;                   // the min form of the three levels' tile tests
-    constexpr int ABL = MIN ? 0 : MODE % 20;          // the form's own MODE (the header comments)
+    constexpr bool MIN = MODE == 3 || (MODE >= 7 && MODE <= 9);   // the min form of the three levels' tile tests
+    constexpr bool Q16 = MODE == 6 || MODE == 7;      // the f16 prefix test in front of the restart
+    constexpr bool L1_ALONE = MODE == 4 || MODE == 8, L1_UNDECIDED = MODE == 5 || MODE == 9;      // (timing only)
+    constexpr int ABL = (MIN || Q16) ? 0 : MODE % 20; // the form's own MODE (the header comments)
     constexpr int GR = G / 2, GH = G / 4, G1 = H ? GH : GR;      // groups of a reduced tile, blocks of an f16 tile, what level 1 contracts
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -740,6 +813,9 @@ void l2_knn2_half_kernel(const MatchParams P)
     const float* __restrict__ redJ = pairnorm[pr.y];
     const uint16_t* __restrict__ hlfI = H ? halfnorm[pr.x] : nullptr;
     const uint16_t* __restrict__ hlfJ = H ? halfnorm[pr.y] : nullptr;
+    const uint16_t* const* prefix16 = Q16 ? prune_table<uint16_t>(P.prune_cnt, offsetof(PruneHeader, prefix16)) : nullptr;
+    const uint16_t* __restrict__ p16I = Q16 ? prefix16[pr.x] : nullptr;
+    const uint16_t* __restrict__ p16J = Q16 ? prefix16[pr.y] : nullptr;
     const uint32_t nI = Ip->n, ntI = Ip->n_tiles, nJ = Jp->n, ntJ = Jp->n_tiles;
     const uint32_t qt0 = (qb * 4u + wave) * NJ;
     if (qt0 >= ntJ) return;                           // wave-uniform; no barriers in this kernel
@@ -747,12 +823,13 @@ void l2_knn2_half_kernel(const MatchParams P)
     // ---- query fragments of level 1 (B operand), scaled by -2: the reduced ones, or the f16 ones (exact, or -inf); a tile that goes
     // on reads the f32 ones again (soffQR: the reduced groups, soffQ: the full ones)
     f32x4 bq1[NJ][G1];
-    uint32_t soffQ[NJ], soffQR[NJ];
+    uint32_t soffQ[NJ], soffQR[NJ], soffQB[NJ];
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) {
         uint32_t qt = qt0 + nj; if (qt >= ntJ) qt = ntJ - 1;          // clamp: results discarded below
         soffQ[nj] = qt * (uint32_t)(G * 1024);
         soffQR[nj] = qt * (uint32_t)(GR * 1024);
+        soffQB[nj] = qt * (uint32_t)(GP / 2 * 1024);
         const gf4p src = (H ? (gf4p)hlfJ : (gf4p)redJ) + (size_t)qt * (G1 * 64) + lane;
 #pragma unroll
         for (int g = 0; g < G1; ++g) {
@@ -760,7 +837,7 @@ void l2_knn2_half_kernel(const MatchParams P)
             else bq1[nj][g] = src[g * 64] * -2.0f;
         }
     }
-    const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled), rqr = wave_uniform_rsrc(redJ);
+    const __amdgpu_buffer_rsrc_t rqt = wave_uniform_rsrc(Jp->tiled), rqr = wave_uniform_rsrc(redJ), rqp = wave_uniform_rsrc(p16J);
 
     Top2 st[NJ];
 #pragma unroll
@@ -771,7 +848,7 @@ void l2_knn2_half_kernel(const MatchParams P)
     const float R = P.ratio_R, invR = 1.0f / P.ratio_R;
     const __amdgpu_buffer_rsrc_t rq = wave_uniform_rsrc(Jp->norms);
     const float maxnormI = __uint_as_float(Ip->max_norm_bits);
-    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF, float& mgn, float& loss) __attribute__((always_inline)) -> bool {
+    auto lane_terms = [&](int nj, float& nbs, float& off, float& offF, float& mgn, float& loss, float& mgnQ) __attribute__((always_inline)) -> bool {
         uint32_t q = (qt0 + (uint32_t)nj) * 32u + c;
         asm volatile("" : "+v"(q));
         const bool dead = !(q < nJ);                    // (covers a query tile beyond the last one too: its rows lie beyond nJ)
@@ -785,12 +862,13 @@ void l2_knn2_half_kernel(const MatchParams P)
         offF = slkF - nb;
         mgn = kHalfMarginFactor * (maxnormI + nb) + kHalfMarginAbs;
         loss = kSkipLossFactor * (maxnormI + nb) + kSkipLossAbs;
+        mgnQ = kPrefixMarginFactor * (maxnormI + nb) + kPrefixMarginAbs;
         return dead;
     };
     float thr[NJ], thrF[NJ], thrH[NJ], thrS[NJ], Tl[NJ], plT[NJ];
 #pragma unroll
     for (int nj = 0; nj < NJ; ++nj) { thr[nj] = R3DM_INF; thrF[nj] = R3DM_INF; thrH[nj] = R3DM_INF; thrS[nj] = -R3DM_INF; Tl[nj] = R3DM_INF; plT[nj] = R3DM_INF; }      // (nothing is above +inf: tile 0 is never pruned, and never skips level 2)
-    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0, n_half = 0, n_skip = 0;      // wave-uniform
+    uint32_t n_tested = 0, n_pruned = 0, n_filtered = 0, n_half = 0, n_skip = 0, n_prefix16 = 0;      // wave-uniform
     float sink = 0.0f;                                // (MODE 5: what consumes the keys)
     bool pruned_under_thr = false;                    // ... as is this: a tile was pruned since the thresholds were last refreshed (plT does not hold it yet)
 
@@ -808,9 +886,10 @@ void l2_knn2_half_kernel(const MatchParams P)
 
         f32x16 accA[NJ], accB[NJ];
         const __amdgpu_buffer_rsrc_t ra = wave_uniform_rsrc(Ip->tiled), rn = wave_uniform_rsrc(Ip->norms), rr = wave_uniform_rsrc(redI),
-                                     rh = wave_uniform_rsrc(hlfI);
+                                     rh = wave_uniform_rsrc(hlfI), rp = wave_uniform_rsrc(p16I);
         const uint32_t voffA = lane * 16u, voffN = h * 16u;
         const uint32_t tileB = (uint32_t)G * 1024u, tileRB = (uint32_t)GR * 1024u, tileHB = (uint32_t)GH * 1024u;      // bytes per tile, reduced tile, f16 tile
+        const uint32_t tileQB = (uint32_t)(GP / 2) * 1024u;           // ... and per tile of the f16 prefix rows
         const uint32_t poff = prefix_norm_offset(ntI) * 4u;        // bytes from the norms to the prefix norms
         uint32_t hb = 4u * h;
         // the thresholds follow the lists: refreshed behind every epilogue (the only place a list changes).  T, thr and thrF are the
@@ -819,8 +898,8 @@ void l2_knn2_half_kernel(const MatchParams P)
 #pragma unroll
             for (int nj = 0; nj < NJ; ++nj) {
                 if (pruned_under_thr) plT[nj] = __builtin_fminf(plT[nj], Tl[nj]);
-                float nbs, off, offF, mgn, loss;
-                const bool dead = lane_terms(nj, nbs, off, offF, mgn, loss);
+                float nbs, off, offF, mgn, loss, mgnQ;
+                const bool dead = lane_terms(nj, nbs, off, offF, mgn, loss, mgnQ);
                 const float e0 = st[nj].d0 + nbs, e1 = st[nj].d1 + nbs;
                 const float re1 = R * e1;
                 float T = e0 < re1 ? __builtin_fmaxf(re1, e0 * invR) : re1;
@@ -847,7 +926,7 @@ void l2_knn2_half_kernel(const MatchParams P)
             n_tested += 1u;
             // a lane objects when one of its level-1 keys is not above its threshold (written so that a NaN key objects)
             // (MODE 4 and 5 leave tile 0 to the three levels, so that the lists hold rows and no query goes to the exact scan)
-            if constexpr (MODE == 5) {                  // (timing only: level 1 without its decision -- one add per query tile keeps the MFMAs)
+            if constexpr (L1_UNDECIDED) {               // (timing only: level 1 without its decision -- one add per query tile keeps the MFMAs)
                 if (t != 0) {
 #pragma unroll
                     for (int nj = 0; nj < NJ; ++nj) sink += cur[nj][0];
@@ -872,9 +951,37 @@ void l2_knn2_half_kernel(const MatchParams P)
                 if constexpr (H) n_half += 1u;
                 return false;
             }
-            if constexpr (MODE == 4) { if (t != 0) { n_pruned += 1u; return false; } }      // (timing only: level 1 alone -- no tile behind tile 0 goes on)
+            if constexpr (L1_ALONE) { if (t != 0) { n_pruned += 1u; return false; } }      // (timing only: level 1 alone -- no tile behind tile 0 goes on)
             // (two levels, MODE 21: the filter alone -- the restart never stops a tile)
+            // (with the f16 prefix test: the restart's prefix test on the rows rounded to f16 first -- no lane has a key that is not above
+            //  its thrQ -> the restart would prune the tile, so it is pruned here; else the restart as ever, its verdict its own)
             auto restart = [&]() __attribute__((always_inline)) -> bool {
+                if constexpr (Q16) {
+                    l2_prefix16_tile_stream<GP / 2, NJ>(rp, rn, voffA, voffN, t * tileQB, poff + t * 128u, rqp, soffQB, cur);
+                    // thrQ = thr + marginQ, rounded up: made here from the lane's terms, where 4 % of the tiles come by -- a register per
+                    // query tile that lived through the loop would not fit (-inf for a dead lane, +inf while thr is +inf)
+                    float thrQ[NJ];
+#pragma unroll
+                    for (int nj = 0; nj < NJ; ++nj) {
+                        float nbs, off, offF, mgn, loss, mgnQ;
+                        const bool dead = lane_terms(nj, nbs, off, offF, mgn, loss, mgnQ);
+                        const float xQ = thr[nj] + mgnQ;
+                        thrQ[nj] = dead ? -R3DM_INF : xQ + __builtin_fabsf(xQ) * 2.384185791015625e-07f;   // 2^-22: the rounding of xQ
+                    }
+                    bool objq = false;
+                    if constexpr (MIN) {
+                        float mq[NJ];
+                        tile_key_min<NJ>(cur, mq);
+#pragma unroll
+                        for (int nj = 0; nj < NJ; ++nj) objq |= !(mq[nj] > thrQ[nj]);
+                    } else {
+#pragma unroll
+                        for (int nj = 0; nj < NJ; ++nj)
+#pragma unroll
+                            for (int r = 0; r < 16; ++r) objq |= !(cur[nj][r] > thrQ[nj]);
+                    }
+                    if (__builtin_amdgcn_ballot_w64(objq) == 0ull) { n_pruned += 1u; n_prefix16 += 1u; pruned_under_thr = true; return false; }
+                }
                 const bool on = l2_prune_tile_restart<G, GP, NJ, H || ABL == 0, MIN>(ra, rn, voffA, voffN, t * tileB, t * 128u, poff + t * 128u, rqt, soffQ, cur, thr);
                 if (!on) { n_pruned += 1u; pruned_under_thr = true; }
                 return on;
@@ -951,7 +1058,8 @@ void l2_knn2_half_kernel(const MatchParams P)
         if (n_filtered) atomicAdd(&P.prune_cnt->n_filtered, (unsigned long long)n_filtered);
         if (n_half) atomicAdd(&P.prune_cnt->n_half, (unsigned long long)n_half);         // (both stay 0 with two levels)
         if (n_skip) atomicAdd(&P.prune_cnt->n_skip, (unsigned long long)n_skip);
-        if constexpr (MODE == 5) { if (sink == 12345.0f) atomicAdd(&P.prune_cnt->n_skip, 1ull); }
+        if (n_prefix16) atomicAdd(&P.prune_cnt->n_prefix16, (unsigned long long)n_prefix16);
+        if constexpr (L1_UNDECIDED) { if (sink == 12345.0f) atomicAdd(&P.prune_cnt->n_skip, 1ull); }
     }
     l2_finish_queries<NJ, false, false, true>(P, pair, Ip, Jp, st, qt0, he, ce, (float)(G * 8), false, 1.0f, 0.0f, nullptr, pruned_lb);
 }
@@ -1042,7 +1150,14 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
                 //   general form of the tile tests where the min form would run (results and counters unchanged)
                 case 134: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 4>(st, P, max_nj_tiles);
                 case 135: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 5>(st, P, max_nj_tiles);
-                case 136: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
+                case 136: return (P.prune & 8u) ? launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 6>(st, P, max_nj_tiles)
+                                                : launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
+                //   137 / 138: 134 / 135 in the min form | 139: the three levels without the f16 prefix test where it would run
+                //   (results and older counters unchanged)
+                case 137: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 8>(st, P, max_nj_tiles);
+                case 138: return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 9>(st, P, max_nj_tiles);
+                case 139: return (P.prune & 4u) ? launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 3>(st, P, max_nj_tiles)
+                                                : launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
                 default: break;
             }
         }
@@ -1054,6 +1169,9 @@ hipError_t launch_l2_knn2(hipStream_t st, const MatchParams& P, uint32_t G, uint
     // stops few tiles it adds 256 cycles to a tile of 4,096 and more (profiles/half_filter_model_c2.txt has R = 0.49).
     if (l2_prune_serves(G, P.prune != 0, P.knn_idx != nullptr, P.ratio_R)) {
         // ... and with the tile tests in their min form where the batch's norms allow it (run_match_batch: MatchParams::prune bit 2)
+        // ... and with the f16 prefix test in front of the restart (r3dm_set_half_prefix: MatchParams::prune bit 3), in either form
+        if ((P.prune & 14u) == 14u) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 7>(st, P, max_nj_tiles);
+        if ((P.prune & 10u) == 10u) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 6>(st, P, max_nj_tiles);
         if ((P.prune & 6u) == 6u) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 3>(st, P, max_nj_tiles);
         if ((P.prune & 2u) != 0) return launch_l2_half_t<16, (int)kPrefixGroups, 2, 4, 2, 0>(st, P, max_nj_tiles);
         return launch_l2_half_t<16, (int)kPrefixGroups, 2, 2, 2, 20>(st, P, max_nj_tiles);

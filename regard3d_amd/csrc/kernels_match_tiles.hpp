@@ -9,6 +9,7 @@
 //   l2_prune_tile_prefix / _finish     ... stopped after a prefix of its dimensions when no lane needs the rest (match mode)
 //   l2_pairnorm_tile_filter / l2_prune_tile_restart   ... ruled out on its pair norms first; a tile that is not starts over
 //   l2_halfnorm_tile_filter / l2_pairnorm_tile_stream ... ruled out on its pair norms in f16 before that (v_mfma_f32_32x32x16_f16)
+//   l2_prefix16_tile_stream            ... the restart's prefix test on the rows rounded to f16, in front of the restart
 //   tile_key_min                       the minimum of a lane's 16 keys per query tile, a v_min3_f32 tree (the min form of those tile tests)
 //   int_tile_step                      ... on the bf16 tiles of integer rows      (v_mfma_f32_32x32x16_bf16)
 //   int_tile_step_lds                  ... on bf16 / i8 tiles shared through LDS  (v_mfma_f32_32x32x16_bf16 / v_mfma_i32_32x32x32_i8)
@@ -458,6 +459,57 @@ __device__ __forceinline__ void l2_pairnorm_tile_stream(__amdgpu_buffer_rsrc_t r
 #pragma unroll
             for (int nj = 0; nj < NJ; ++nj)
                 cur[nj] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[cc], b[nj][cc], cur[nj], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+}
+
+// The restart's prefix test on a tile that is about to enter the restart, on the rows rounded to f16 (the third table behind
+// MatchParams::prune_cnt, stage_pairnorm_kernel: [tile][GB = GP / 2 blocks of 16 dimensions][lane half][32 rows][8 f16], 6 KiB per tile,
+// tiles contiguous): GB v_mfma_f32_32x32x16_f16 per query tile instead of 4 GP v_mfma_f32_32x32x2_f32, the accumulators started from the
+// same stored prefix norms -- through the C operand of each query tile's first MFMA, one 16-register tuple the four norm loads fill, as
+// in l2_halfnorm_tile_filter<CSTART>.  Built like l2_pairnorm_tile_stream: nothing of it is in registers when it starts, the dataset
+// view's blocks and the query view's blocks (x -2 in f16: exact for every stored finite value, row_to_half) stream through a W-deep
+// window.  Level 1's window and norms stay untouched.  The caller decides on `cur`.
+template <int GB, int NJ>
+__device__ __forceinline__ void l2_prefix16_tile_stream(__amdgpu_buffer_rsrc_t rp, __amdgpu_buffer_rsrc_t rn, uint32_t voffA, uint32_t voffN,
+                                                        uint32_t soffB, uint32_t soffP, __amdgpu_buffer_rsrc_t rqp,
+                                                        const uint32_t (&soffQB)[NJ], f32x16 (&cur)[NJ])
+{
+    constexpr int W = 2;
+    static_assert(GB % W == 0, "window slots");
+    // soffB: byte offset of this tile's f16 block 0; soffP: of THIS tile's prefix norms
+    f32x4 wa[W], wb[NJ][W];
+#pragma unroll
+    for (int s = 0; s < W; ++s) {
+        wa[s] = bload16(rp, voffA, soffB + (uint32_t)s * 1024u);
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) wb[nj][s] = bload16(rqp, voffA, soffQB[nj] + (uint32_t)s * 1024u);
+    }
+    f32x4 np[4];
+#pragma unroll
+    for (int qd = 0; qd < 4; ++qd) np[qd] = bload16(rn, voffN, soffP + (uint32_t)qd * 32u);
+#pragma unroll
+    for (int g = 0; g < GB; ++g) {
+        const f16x8 a = __builtin_bit_cast(f16x8, wa[g % W]);
+        f16x8 b[NJ];
+#pragma unroll
+        for (int nj = 0; nj < NJ; ++nj) b[nj] = __builtin_bit_cast(f16x8, wb[nj][g % W]) * (_Float16)-2.0f;
+        if (g + W < GB) {
+            wa[g % W] = bload16(rp, voffA, soffB + (uint32_t)(g + W) * 1024u);
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) wb[nj][g % W] = bload16(rqp, voffA, soffQB[nj] + (uint32_t)(g + W) * 1024u);
+        }
+        if (g == 0) {
+            const f32x16 n16 = __builtin_shufflevector(__builtin_shufflevector(np[0], np[1], 0, 1, 2, 3, 4, 5, 6, 7),
+                                                       __builtin_shufflevector(np[2], np[3], 0, 1, 2, 3, 4, 5, 6, 7),
+                                                       0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15);
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b[nj], n16, 0, 0, 0);
+            asm volatile("" : : "v"(n16));                // (the tuple stays live behind the last MFMA: none is tied to it)
+        } else {
+#pragma unroll
+            for (int nj = 0; nj < NJ; ++nj) cur[nj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a, b[nj], cur[nj], 0, 0, 0);
+        }
         __builtin_amdgcn_sched_barrier(0);
     }
 }

@@ -576,6 +576,7 @@ struct r3dm_ctx {
     bool integer_mfma = false;                              // r3dm_set_integer_mfma
     bool prefix_pruning = true;                             // r3dm_set_prefix_pruning: match mode on 128-dimensional rows stops tiles early
     bool half_filter = true;                                // r3dm_set_half_filter: the f16 level in front of the pair-norm filter
+    bool half_prefix = true;                                // r3dm_set_half_prefix: the restart's prefix test on f16 rows in front of the restart
     bool min_tile_test = true;                              // r3dm_set_min_tile_test: the three levels' tile tests in their min form where the norms allow it
     // wave tiles of the last match call, summed over its batches from PruneHeader's counters
     struct PruneTotals {
@@ -583,6 +584,7 @@ struct r3dm_ctx {
         uint64_t filtered = 0;                              // r3dm_get_pair_filter_counts: pruned by the filter (part of pruned)
         uint64_t half = 0;                                  // r3dm_get_half_filter_counts: pruned by the f16 level (part of filtered)
         uint64_t skipped = 0;                               // r3dm_get_level2_skip_counts: sent by the f16 level straight to the restart (no f32 filter)
+        uint64_t prefix16_tested = 0, prefix16_pruned = 0;  // r3dm_get_half_prefix_counts: tiles the f16 prefix test saw / pruned (part of pruned)
         uint64_t min_pairs = 0, general_pairs = 0;          // r3dm_get_min_tile_test_counts: pairs the three levels matched in the min form / the general form
     } prune_totals;
     bool split_mfma = false;                                // r3dm_set_split_mfma

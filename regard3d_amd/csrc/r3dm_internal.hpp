@@ -229,13 +229,15 @@ struct PruneHeader {
     const uint16_t* const*  halfnorm;     // f16 pair-norm tiles per slot: [n_tiles][G / 4][2][32][8] f16; set when MatchParams::prune bit 1 is
     unsigned long long      n_skip;       // tiles the f16 level sent straight to the restart, the filter unable to prune them (part of
                                           // no count above: these tiles go on)
+    const uint16_t* const*  prefix16;     // the rows' first 8 GP dimensions as f16, per slot: [n_tiles][GP / 2][2][32][8] f16; set when MatchParams::prune bit 3 is
+    unsigned long long      n_prefix16;   // tiles the f16 prefix test pruned in front of the restart (part of n_pruned)
 };
 // the header of a batch's fallback lists (r3dm_ctx::d_fb): zeroed per batch, [fb_cnt: P][fb_q: P x kFbPerPair] behind it
 struct FbHeader {
     uint32_t    fb_total[2];              // MatchParams::fb_total
     uint32_t    pad0[2];
     PruneHeader prune;                    // MatchParams::prune_cnt
-    uint32_t    pad1[6];
+    uint32_t    pad1[2];
 };
 
 struct MatchParams {
@@ -263,13 +265,15 @@ struct MatchParams {
     // prefix pruning of the f32 2-NN tiles in match mode (r3dm_set_prefix_pruning; l2_knn2_prune_kernel).  Behind every older field:
     // their offsets are what the other kernels' machine code was compiled with.
     uint32_t      prune;          // != 0: launch_l2_knn2 may pick the pruning kernel; bit 1: with the f16 level in front (r3dm_set_half_filter);
-                                  // bit 2: ... and its tile tests in the min form (r3dm_set_min_tile_test; every norm below kMinTileTestNormBits)
+                                  // bit 2: ... and its tile tests in the min form (r3dm_set_min_tile_test; every norm below kMinTileTestNormBits);
+                                  // bit 3: ... and the f16 prefix test in front of the restart (r3dm_set_half_prefix)
     PruneHeader*  prune_cnt;      // the pruning kernels' counters and tables (FbHeader::prune)
 };
 static_assert(sizeof(MatchParams) == 120 && offsetof(MatchParams, prune_cnt) == 112, "kernel arguments: every 2-NN kernel was compiled with this layout");
 static_assert(offsetof(PruneHeader, n_tested) == 0 && offsetof(PruneHeader, n_pruned) == 8 && offsetof(PruneHeader, n_filtered) == 16 &&
               offsetof(PruneHeader, pairnorm) == 24 && offsetof(PruneHeader, n_half) == 32 && offsetof(PruneHeader, halfnorm) == 40 &&
-              offsetof(PruneHeader, n_skip) == 48 && sizeof(PruneHeader) == 56, "the slots the pruning kernels were compiled with");
+              offsetof(PruneHeader, n_skip) == 48 && offsetof(PruneHeader, prefix16) == 56 && offsetof(PruneHeader, n_prefix16) == 64 &&
+              sizeof(PruneHeader) == 72, "the slots the pruning kernels were compiled with");
 static_assert(offsetof(FbHeader, fb_total) == 0 && offsetof(FbHeader, prune) == 16 && sizeof(FbHeader) == 96, "24 words, the counters 8-byte aligned");
 constexpr uint32_t kFbPerPair = 256;
 constexpr uint32_t kFallback = 0xFFFFFFFEu;
@@ -616,7 +620,8 @@ hipError_t launch_stage_positions(hipStream_t st, const StageViewArgs& A);      
 hipError_t launch_untile_rows(hipStream_t st, const float* tiled, uint32_t n, uint32_t dim, uint32_t G, uint32_t n_tiles, float* rows);
 hipError_t launch_stage_bf16(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, uint16_t* tiled16);
 // tiledrh: null, or the f16 tiles of the same pair norms (the f16 level of l2_knn2_half_kernel), n_tiles x G x 256 bytes
-hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr, uint16_t* tiledrh);
+hipError_t launch_stage_pairnorm(hipStream_t st, const float* tiled, uint32_t G, uint32_t n_tiles, float* tiledr, uint16_t* tiledrh,
+                                 uint16_t* tiledp16 = nullptr);
 // whether launch_l2_knn2 takes the pruning kernel for such a launch (which reads the pair-norm tiles behind MatchParams::prune_cnt: the caller makes them, run_match_batch)
 bool l2_prune_serves(uint32_t G, bool prune, bool raw_knn, float ratio_R);
 hipError_t launch_stage_bin(hipStream_t st, const uint8_t* raw, uint32_t n, uint32_t nbytes,

@@ -21,6 +21,8 @@ if len(sys.argv) > 3 and sys.argv[3] == "nohalf":
     c.set_half_filter(False)             # the cascade without the f16 level in front (R3DM_L2_VARIANT 130: the f16 level, then straight to the restart; 131 / 132: its window 1 / 2 blocks deep; 133: the three levels without the skip of level 2; default: the three levels, level 2 skipped where it cannot prune)
 if len(sys.argv) > 3 and sys.argv[3] == "nomin":
     c.set_min_tile_test(False)           # the three levels with the general form of their tile tests (R3DM_L2_VARIANT 136 forces it too; 134: level 1 alone, no tile ever goes on; 135: level 1 alone without its decision -- both timing only; default: the min form where the norms allow it)
+if len(sys.argv) > 3 and sys.argv[3] == "noprefix16":
+    c.set_half_prefix(False)             # the three levels without the f16 prefix test in front of the restart (R3DM_L2_VARIANT 139 forces that too; 137 / 138: 134 / 135 in the min form, timing only; default: the test runs where the three levels do)
 for i in range(n_img): c.set_image(i, descs[i], xys[i], 4000, 3000)
 ii, jj = np.triu_indices(n_img, k=1); pairs = np.stack([ii, jj], 1).astype(np.uint32)
 res = []
@@ -31,4 +33,4 @@ tested, pruned = c.prefix_pruning_counts()
 print(json.dumps({"variant": os.environ.get("R3DM_L2_VARIANT", "default"), "tiles_pruned_share": round(pruned / tested, 4) if tested else None,
                   "tiles_filtered_share": round(c.pair_filter_counts() / tested, 4) if tested else None,
                   "tiles_half_share": round(c.half_filter_counts() / tested, 4) if tested else None,
-                  "tiles_level2_skipped_share": round(c.level2_skip_counts() / tested, 4) if tested else None, "pairs_min_form_general_form": c.min_tile_test_counts(), "kernel_ms": round(s.ms_match_kernels, 2), "pairs": len(pairs), "tflops": [round(x, 2) for x in res], "kind": kind, "matches": g.num_matches, "queries": s.n_queries, "fallback": s.n_exact_fallback}))
+                  "tiles_level2_skipped_share": round(c.level2_skip_counts() / tested, 4) if tested else None, "pairs_min_form_general_form": c.min_tile_test_counts(), "tiles_f16_prefix_reached_pruned": c.half_prefix_counts(), "kernel_ms": round(s.ms_match_kernels, 2), "pairs": len(pairs), "tflops": [round(x, 2) for x in res], "kind": kind, "matches": g.num_matches, "queries": s.n_queries, "fallback": s.n_exact_fallback}))

@@ -16,7 +16,9 @@ Distances are exact here (integer-valued rows: float32 sums below 2^24), as the 
 the cascade of l2_knn2_half_kernel<…, MODE 20>: the pair-norm filter in front of the prefix test (model_pair_cascade).
    python tools/prefix_prune_model.py --filter half [--gp 12] ...
 the three levels of l2_knn2_half_kernel: the same filter on pair norms rounded up to f16 in front of the cascade (model_pair_levels);
-it must prune no tile the cascade does not prune."""
+it must prune no tile the cascade does not prune.
+   python tools/prefix_prune_model.py --filter half --skip lane --prefix16 [--gp 12] ...
+with the f16 prefix test in front of the restart (rows_to_half, prefix16_bound): it must prune no tile the restart's f32 prefix test keeps."""
 import argparse
 import os
 import sys
@@ -264,7 +266,37 @@ def skip_loss(a, b, LBH, form="lane"):
         return (2.0 ** -9 + 2.0 ** -20) * dot2 + (2.0 ** -13 + 2.0 ** -15) * M + SKIP_LOSS_ABS
 
 
-def model_pair_levels(a, b, gp, R, half=True, skip=None):
+PREFIX_MARGIN = 2.0 ** -10 + 2.0 ** -14 + 2.0 ** -15  # kPrefixMarginFactor (kernels_match.hip, above l2_knn2_half_kernel)
+PREFIX_MARGIN_ABS = 2.0 ** -6                         # kPrefixMarginAbs
+CYC_PREFIX16 = 12 * 32                                # the f16 prefix test: 6 v_mfma_f32_32x32x16_f16 per query tile
+
+
+def rows_to_half(x):
+    """[...] float32 -> float64 holding f16 values: row_to_half (kernels_match.hip) bit for bit on the float's bits -- a NaN stays a NaN,
+    |x| < 2^-14 becomes +0, |x| > 32,752 becomes a NaN, any other value loses 13 significand bits to nearest, ties to even"""
+    u = np.ascontiguousarray(x, np.float32).view(np.uint32)
+    mag = u & np.uint32(0x7FFFFFFF)
+    v = (mag.astype(np.int64) - (112 << 23)) & 0xFFFFFFFF
+    h = (((u >> np.uint32(16)) & np.uint32(0x8000)).astype(np.int64) | ((v + 0xFFF + ((v >> 13) & 1)) >> 13)) & 0xFFFF
+    h = np.where(mag < np.uint32(0x38800000), 0, h)
+    h = np.where(mag > np.uint32(0x46FFE000), 0x7E00, h)
+    return h.astype(np.uint16).view(np.float16).astype(np.float64)
+
+
+def prefix16_bound(a, b, gp):
+    """-> (DPQ [nI, nJ], marginQ [nJ]) in float64: DPQ = |a_P|^2 + |b_P|^2 - 2 sum_i A_i B_i over the first 8 gp dimensions, A and B
+    the rows rounded to f16 (rows_to_half; a NaN factor poisons its sum), and the margin thrQ carries above thr,
+    (2^-10 + 2^-14 + 2^-15) (max|a|^2 + |b|^2) + 2^-6"""
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    na, nb = (a64 * a64).sum(1), (b64 * b64).sum(1)
+    ap, bp = a64[:, :8 * gp], b64[:, :8 * gp]
+    A, B = rows_to_half(a[:, :8 * gp]), rows_to_half(b[:, :8 * gp])
+    with np.errstate(invalid="ignore", over="ignore"):
+        dot = (A[:, None, :] * B[None, :, :]).sum(2) if a.shape[0] * b.shape[0] <= 1 << 16 else A @ B.T
+        return (ap * ap).sum(1)[:, None] + (bp * bp).sum(1)[None, :] - 2.0 * dot, PREFIX_MARGIN * (na.max(initial=0.0) + nb) + PREFIX_MARGIN_ABS
+
+
+def model_pair_levels(a, b, gp, R, half=True, skip=None, prefix16=False):
     """the three levels of l2_knn2_half_kernel: per wave tile the f16 level (thrH = thrF + margin), behind it the pair-norm filter,
     behind that the tile run again with the prefix test -- model_pair_cascade with one more level in front (half=False: without it,
     the cascade itself), and with the outcome PER TILE.
@@ -274,7 +306,12 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
     key at or below thrS = thrF - L goes straight to the restart.  No older output depends on it but `cycles`; it adds skipped (such
     tiles), unsound (those of them the pair-norm filter would have pruned: must be 0), tile_skip [n_tiles, n_waves] and gap: the
     smallest distance of any finite key of level 1 or 2 from the threshold it is compared with (thrH, thrF, thrS) -- where that is well
-    above the float32 roundings, the kernel decides every tile as this model does."""
+    above the float32 roundings, the kernel decides every tile as this model does.
+    prefix16 = True: the f16 prefix test in front of the restart (thrQ = thr + marginQ) on every tile that gets there.  No older output
+    depends on it; it adds reach (tiles that reach the restart), prefix_pruned (those the restart's f32 prefix test prunes), prefix16
+    (those the f16 test prunes), unsound16 (those of them the f32 prefix test keeps: must be 0), between (tiles the f32 test prunes and the
+    f16 test lets through: they lie between thr and thrQ), cycles16 (matrix cycles with the level), tile_prefix16 [n_tiles, n_waves]
+    and gap16, gap's like for the f16 prefix keys against thrQ."""
     R64 = float(np.float32(R))
     nI, nJ = a.shape[0], b.shape[0]
     a64, b64 = a.astype(np.float64), b.astype(np.float64)
@@ -286,6 +323,7 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
         LB, slackF = pairnorm_bound(a, b)
         LBH, margin = halfnorm_bound(a, b)
         loss = skip_loss(a, b, LBH, skip) if (skip and half) else None
+        DPQ, marginQ = prefix16_bound(a, b, gp) if prefix16 else (None, None)
     slackP = np.zeros(nJ) if _exact_pair(a, b) else slackF
     n_tiles = (nI + 31) // 32
     n_waves = (nJ + 63) // 64
@@ -296,6 +334,8 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
     wave_of_q = np.arange(nJ) // 64
     tiles = pruned = filtered = halved = work = cycles = skipped = unsound = 0
     tile_skip = np.zeros((n_tiles, n_waves), bool); gap = np.inf
+    reach = prefix_pruned = n_prefix16 = unsound16 = between = cycles16 = 0
+    tile_prefix16 = np.zeros((n_tiles, n_waves), bool); gap16 = np.inf
     tile_half = np.zeros((n_tiles, n_waves), bool); tile_filtered = np.zeros((n_tiles, n_waves), bool); tile_pruned = np.zeros((n_tiles, n_waves), bool)
     for t in range(n_tiles):
         lo, hi = t * 32, min(nI, t * 32 + 32)
@@ -306,6 +346,7 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
             T = np.where(e0 < re1, np.maximum(re1, e0 / R64), re1)
             T = T + np.abs(T) * 2.0 ** -21
         objH = np.zeros((2, nJ), bool); objF = np.zeros((2, nJ), bool); objP = np.zeros((2, nJ), bool); far = np.zeros((2, nJ), bool)
+        objQ = np.zeros((2, nJ), bool)
         with np.errstate(invalid="ignore"):
             for h in (0, 1):
                 m = half_of_row[: hi - lo] == h
@@ -314,6 +355,11 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
                     objH[h] = ~(LBH[rows[m]] - (slackF + margin)[None, :] > T[h][None, :]).all(0)
                     objF[h] = ~(LB[rows[m]] - slackF[None, :] > T[h][None, :]).all(0)
                     objP[h] = ~(DP[rows[m]] - slackP[None, :] > T[h][None, :]).all(0)
+                    if prefix16:
+                        keysQ = DPQ[rows[m]] - (slackP + marginQ)[None, :]
+                        objQ[h] = ~(keysQ > T[h][None, :]).all(0)
+                        g = np.abs(keysQ - T[h][None, :])
+                        gap16 = min(gap16, float(g[np.isfinite(g)].min(initial=np.inf)))
                     if loss is not None:
                         # kh_c <= thrS and kh_c > -inf (false for a NaN key); thrS = -inf while the threshold is +inf
                         Lm = loss[rows[m]] if loss.shape[0] > 1 else loss
@@ -340,6 +386,16 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
         n2, n3p, n3 = int(wH.sum()), int((wH & wF & ~wP).sum()), int(wave_on.sum())
         work += 8 * n2 + gp * n3p + 16 * n3
         cycles += (CYC_HALF * n_waves if half else 0) + CYC_GROUP * (8 * (n2 - int(wS.sum())) + gp * n3p + 16 * n3)
+        if prefix16:
+            wQ = np.zeros(n_waves, bool)
+            np.logical_or.at(wQ, wave_of_q, objQ[0] | objQ[1])
+            at_restart = wH & wF
+            tile_prefix16[t] = at_restart & ~wQ
+            reach += int(at_restart.sum()); prefix_pruned += n3p
+            n_prefix16 += int((at_restart & ~wQ).sum()); unsound16 += int((at_restart & ~wQ & wP).sum())
+            between += int((at_restart & wQ & ~wP).sum())
+            cycles16 += (CYC_HALF * n_waves if half else 0) + CYC_GROUP * 8 * (n2 - int(wS.sum())) + CYC_PREFIX16 * int(at_restart.sum()) + \
+                CYC_GROUP * (gp * int((at_restart & wQ & ~wP).sum()) + 16 * int((at_restart & wQ & wP).sum()))
         go = wave_on[wave_of_q]
         pl[:, ~go] = np.minimum(pl[:, ~go], T[:, ~go])
         if go.any():
@@ -365,18 +421,29 @@ def model_pair_levels(a, b, gp, R, half=True, skip=None):
         t1 = np.take_along_axis(Dt, o[:1], 0)[0]; t2 = np.take_along_axis(Dt, o[1:2], 0)[0]
         truth = np.where(t1 < R64 * t2, o[0], -1)
     decided = verdict != -2
-    return {"tiles": tiles, "pruned": pruned, "filtered": filtered, "half": halved, "work": work, "cycles": cycles,
+    extra = {"reach": reach, "prefix_pruned": prefix_pruned, "prefix16": n_prefix16, "unsound16": unsound16, "between": between,
+             "cycles16": cycles16, "tile_prefix16": tile_prefix16, "gap16": gap16} if prefix16 else {}
+    return {**extra, "tiles": tiles, "pruned": pruned, "filtered": filtered, "half": halved, "work": work, "cycles": cycles,
             "fallback": int((~decided).sum()), "wrong": int((decided & (verdict != truth)).sum()), "matches": int((truth >= 0).sum()),
             "queries": nJ, "skipped": skipped, "unsound": unsound, "tile_skip": tile_skip, "gap": gap, "tile_half": tile_half, "tile_filtered": tile_filtered, "tile_pruned": tile_pruned, "verdict": verdict}
 
 
-def run_levels(views, pairs, gp, ratio, squared=True, out=print, skip=None):
+def run_levels(views, pairs, gp, ratio, squared=True, out=print, skip=None, prefix16=False):
     """model_pair_levels with and without the f16 level on every pair: the shares per level, the matrix cycles of both, and whether
-    any tile or verdict differs between them (it must not).  skip = "lane" / "key": with the skip of level 2 in that form of L (a
+    any tile or verdict differs between them (it must not).  prefix16 (with skip): the f16 prefix test in front of
+    the restart -- a third line per pair: tiles that reach the restart, tiles its f32 prefix test prunes, tiles the f16 test prunes, tiles
+    the f16 test prunes and the f32 test keeps (must be 0), the matrix cycles a tile with and without it.  skip = "lane" / "key": with the skip of level 2 in that form of L (a
     second line per pair: the share of level 1's objecting tiles that skip, the cycles with it, the unsound skips -- must be 0)"""
     R = ratio * ratio if squared else ratio
     keys = ("tiles", "pruned", "filtered", "half", "cycles", "fallback", "wrong", "matches", "queries", "skipped", "unsound")
     acc = dict.fromkeys(keys, 0); acc["cycles_cascade"] = 0; acc["differs"] = 0; acc["cycles_skip"] = 0
+    keys16 = ("reach", "prefix_pruned", "prefix16", "unsound16", "between", "cycles16")
+    if prefix16:
+        acc.update(dict.fromkeys(keys16, 0))
+    qline = lambda r: (f"reach the restart {r['reach']}  pruned there by the f32 prefix test {r['prefix_pruned']}  pruned by the f16 prefix test "
+                       f"{r['prefix16']} ({r['prefix16'] / max(r['prefix_pruned'], 1):.4f} of those)  let through between thr and thrQ {r['between']}  "
+                       f"pruned by the f16 test and kept by the f32 test {r['unsound16']}  "
+                       f"matrix cycles a tile {r['cycles16'] / r['tiles']:.0f} (without it {r['cycles_skip'] / r['tiles']:.0f})")
     sline = lambda r: (f"level 2 skipped on {r['skipped']} of {r['tiles'] - r['half']} objecting tiles ({r['skipped'] / max(r['tiles'] - r['half'], 1):.4f}; "
                        f"level 2 still runs on {(r['tiles'] - r['half'] - r['skipped']) / r['tiles']:.4f} of all, prunes {(r['filtered'] - r['half']) / r['tiles']:.4f})  "
                        f"matrix cycles a tile {r['cycles_skip'] / r['tiles']:.0f} (without the skip {r['cycles'] / r['tiles']:.0f})  "
@@ -389,7 +456,9 @@ def run_levels(views, pairs, gp, ratio, squared=True, out=print, skip=None):
         r0 = model_pair_levels(views[i], views[j], gp, R, half=False)
         r["cycles_cascade"] = r0["cycles"]; r["cycles_skip"] = r["cycles"]
         if skip:
-            rs = model_pair_levels(views[i], views[j], gp, R, skip=skip)
+            rs = model_pair_levels(views[i], views[j], gp, R, skip=skip, prefix16=prefix16)
+            if prefix16:
+                r.update({k: rs[k] for k in keys16})
             assert all(np.array_equal(rs[k], r[k]) for k in ("pruned", "filtered", "half", "tile_half", "tile_filtered", "tile_pruned", "verdict"))
             r["cycles_skip"] = rs["cycles"]; r["skipped"] = rs["skipped"]; r["unsound"] = rs["unsound"]
         r["differs"] = int((r["tile_filtered"] != r0["tile_filtered"]).sum() + (r["tile_pruned"] != r0["tile_pruned"]).sum() + (r["verdict"] != r0["verdict"]).sum())
@@ -399,8 +468,12 @@ def run_levels(views, pairs, gp, ratio, squared=True, out=print, skip=None):
             f"wrong verdicts {r['wrong']}  tiles or verdicts unlike the cascade's {r['differs']}")
         if skip:
             out(f"skip of level 2 ({skip})  pair ({i},{j})  {sline(r)}")
+        if prefix16:
+            out(f"f16 prefix test  pair ({i},{j})  {qline(r)}")
     if skip:
         out(f"skip of level 2 ({skip})  ALL {len(pairs)} pairs, R = {R:.4f}: {sline(acc)}")
+    if prefix16:
+        out(f"f16 prefix test  ALL {len(pairs)} pairs, R = {R:.4f}: {qline(acc)}")
     out(f"half + pairnorm + GP {gp:2d}  ALL {len(pairs)} pairs, {acc['queries']} queries, R = {R:.4f}: {line(acc)}  "
         f"exact scan {acc['fallback']} ({acc['fallback'] / max(acc['queries'], 1):.2e})  wrong verdicts {acc['wrong']}  "
         f"tiles or verdicts unlike the cascade's {acc['differs']}")
@@ -454,6 +527,8 @@ def main():
                     help="pairnorm: the cascade, the pair-norm filter in front of GP = --gp[-1]; half: the f16 level in front of the cascade")
     ap.add_argument("--skip", choices=["none", "lane", "key"], default="none",
                     help="with --filter half: the skip of level 2 with L lane-constant (the kernel's) or key-dependent")
+    ap.add_argument("--prefix16", action="store_true",
+                    help="with --filter half --skip lane: the f16 prefix test in front of the restart (r3dm_set_half_prefix)")
     ap.add_argument("--summary", action="store_true", help="with --filter pairnorm: only the ALL line")
     a = ap.parse_args()
     from regard3d_amd import synth
@@ -464,8 +539,8 @@ def main():
     for ratio in a.ratio:
         if a.filter == "half":
             acc = run_levels(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print,
-                             skip=None if a.skip == "none" else a.skip)
-            bad += acc["wrong"] + acc["differs"] + acc["unsound"]
+                             skip=None if a.skip == "none" else a.skip, prefix16=a.prefix16 and a.skip != "none")
+            bad += acc["wrong"] + acc["differs"] + acc["unsound"] + acc.get("unsound16", 0)
             continue
         if a.filter == "pairnorm":
             bad += run_cascade(views, pairs, a.gp[-1], ratio, out=(lambda s: print(s) if " ALL " in s else None) if a.summary else print)["wrong"]
