@@ -8,7 +8,7 @@ set -e
 cd "$(dirname "$0")"
 HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 WHAT=${1:-all}
-SRC="kernels_match.hip kernels_match_16bit.hip kernels_match_hamming.hip kernels_match_exact.hip kernels_match_mutual.hip kernels_match_head.hip kernels_match_budget.hip kernels_match_knn.hip kernels_match_knn16.hip kernels_match_knn8.hip kernels_filter.hip kernels_filter_e.hip kernels_filter_coop.hip kernels_liop.hip kernels_ann.hip kernels_hnsw.hip kernels_mrpt.hip kernels_akaze.hip kernels_akaze_classic.hip kernels_graph.hip kernels_guided.hip kernels_tracks.hip kernels_vocab.hip api_core.cpp api_match.cpp api_preselect.cpp api_budget.cpp api_vocab.cpp api_ann.cpp api_hnsw.cpp api_mrpt.cpp api_filter.cpp api_guided.cpp api_tracks.cpp api_akaze.cpp api_akaze_classic.cpp api_liop.cpp api_features.cpp api_multi.cpp api_comm.cpp compute_matches.cpp"
+SRC="kernels_match.hip kernels_match_16bit.hip kernels_match_hamming.hip kernels_match_exact.hip kernels_match_mutual.hip kernels_match_head.hip kernels_match_budget.hip kernels_match_knn.hip kernels_match_knn16.hip kernels_match_knn8.hip kernels_filter.hip kernels_filter_e.hip kernels_filter_coop.hip kernels_liop.hip kernels_ann.hip kernels_hnsw.hip kernels_mrpt.hip kernels_akaze.hip kernels_akaze_classic.hip kernels_graph.hip kernels_guided.hip kernels_tracks.hip kernels_vocab.hip kernels_vocab_train.hip api_core.cpp api_match.cpp api_preselect.cpp api_budget.cpp api_vocab.cpp api_ann.cpp api_hnsw.cpp api_mrpt.cpp api_filter.cpp api_guided.cpp api_tracks.cpp api_akaze.cpp api_akaze_classic.cpp api_liop.cpp api_features.cpp api_multi.cpp api_comm.cpp compute_matches.cpp"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fPIC -fopenmp -Wall -Wno-unused-result -Iinclude"
 # filter_device.hpp (wg_fence) orders global-memory exchanges INSIDE a workgroup with a workgroup-scope fence: valid only while the
 # waves of a workgroup share a CU and its L1, i.e. never in threadgroup-split mode

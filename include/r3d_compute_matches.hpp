@@ -149,6 +149,11 @@ public:
     // the gate sees the proposed pairs.  A collection with fewer than 4 rows or 2 views keeps all pairs.  16,384 / 20 are untuned defaults.
     // Off by default: the match files are the reference's only while it is off.
     void setPairProposal(bool on, uint32_t n_words = 16384, uint32_t top_k = 20);
+    // refinements of setPairProposal, without effect while it is off: max_iterations > 0 trains the sampled vocabulary on the views it
+    // was sampled from before it is used (r3dm_vocab_train: at most that many Lloyd updates), idf weights the scores
+    // (r3dm_vocab_set_weighting(R3DM_VOCAB_WEIGHT_IDF)).  The match files are again the switch-off files restricted to the proposed
+    // pairs.  0 / false, the default, is setPairProposal as it was.
+    void setPairProposalTraining(uint32_t max_iterations, bool idf);
     // pairs the last computeMatches call handed to its matcher (all pairs, or the proposed ones)
     uint64_t lastPairCount() const { return last_pair_count_; }
     // How the approximate arms of the dispatch (0 FLANN, 1-3 KGraph, 5 MRPT, 6-8 HNSW) are served.  kArmsFastest (default): by the
@@ -244,6 +249,8 @@ private:
     bool budget_on_ = false;
     bool proposal_on_ = false;
     uint32_t proposal_words_ = 16384, proposal_top_k_ = 20;
+    uint32_t proposal_train_iterations_ = 0;
+    bool proposal_idf_ = false;
     uint64_t last_pair_count_ = 0;
     int background_nice_ = 0;
     static int features_sink(void* self, uint32_t image_index, uint32_t n_features, const float* desc_device, const float* xy_as_written);
@@ -315,13 +322,14 @@ int  r3dm_stage_run(r3dm_stage* s, const char* matches_dir, const r3dm_view_imag
 #define R3DM_STAGE_DESCRIPTOR_MSURF 1024u /* setRegionsType(R3DM_F32, 64): the features stage writes M-SURF-64 rows (r3dm_set_descriptor_arm); together with R3DM_STAGE_DESCRIPTOR_MLDB: R3DM_ERR_INVALID */
 #define R3DM_STAGE_PREEMPTIVE_MATCHING 256u /* preemptive matching with head_rows 128, min_matches 4 (R3DComputeMatches::setPreemptiveMatching(true), r3dm_set_preemptive_matching); default: every pair is matched */
 #define R3DM_STAGE_PAIR_PROPOSAL 2048u /* the matcher gets the pairs r3dm_propose_pairs proposes, not all pairs (R3DComputeMatches::setPairProposal(true)): 16,384 words, lowered to half the collection's rows when it is smaller, top_k 20 -- untuned defaults */
+#define R3DM_STAGE_PROPOSAL_TRAINED 16384u /* with R3DM_STAGE_PAIR_PROPOSAL (no effect without it): the sampled vocabulary is trained for at most 10 Lloyd updates and the scores are idf-weighted (R3DComputeMatches::setPairProposalTraining(10, true)) -- untuned defaults */
 #define R3DM_STAGE_MATCH_BUDGET 8192u /* match budget with max_rows 8,192 (R3DComputeMatches::setMatchBudget(true), r3dm_set_match_budget): only each view's 8,192 largest-scale features are matched; default: every row is matched */
 #define R3DM_STAGE_SYMMETRIC_RATIO 4096u /* symmetric ratio test (R3DComputeMatches::setSymmetricRatio(true), r3dm_set_symmetric_ratio): a match must also pass the 2-NN + ratio rule with the views swapped; default off */
 typedef struct { uint32_t id, width, height; const char* basename; } r3dm_view;
 int r3dm_compute_matches_dir(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                              r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed,
                              uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);
-/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_SYMMETRIC_RATIO, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_MATCH_BUDGET, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_F32_TILES */
+/* the same with the flags of the stage that apply to a directory of feature files: R3DM_STAGE_MUTUAL_MATCHING, R3DM_STAGE_SYMMETRIC_RATIO, R3DM_STAGE_PREEMPTIVE_MATCHING, R3DM_STAGE_MATCH_BUDGET, R3DM_STAGE_PAIR_PROPOSAL, R3DM_STAGE_PROPOSAL_TRAINED, R3DM_STAGE_F32_TILES */
 int r3dm_compute_matches_dir_flags(int device_id, const char* matches_dir, const r3dm_view* views, uint32_t n_views,
                                    r3dm_dtype dtype, uint32_t dim, float dist_ratio, int compute_F, uint64_t seed, uint32_t flags,
                                    uint64_t* n_putative_pairs, uint64_t* n_geometric_pairs, char* err, size_t err_cap);

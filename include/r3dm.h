@@ -433,6 +433,60 @@ typedef struct {
 } r3dm_vocab_stats;
 int  r3dm_vocab_report(const r3dm_vocab* vocab, r3dm_vocab_stats* out);
 
+/* Trained vocabularies: Lloyd's k-means iterations on the device (opt-in like everything above: with neither
+ * r3dm_vocab_train nor r3dm_vocab_set_weighting called, nothing new is allocated or launched and every result is what it was).
+ *
+ * r3dm_vocab_train: `init` is any vocabulary of the context's device and is not modified; *out is a new vocabulary of the same type,
+ *   length and word count, without signatures.  The training set is every row of the listed views; global row g is the row's position in
+ *   the concatenation of the views in list order (as in r3dm_vocab_sample; empty views are allowed), T their number.  Refusals: those of
+ *   r3dm_vocab_sample (unregistered id, id listed twice, views of mixed type or length), a view unlike the vocabulary, another device's
+ *   vocabulary, max_iterations == 0, T == 0 (R3DM_ERR_INVALID), T >= 2^32 (R3DM_ERR_UNSUPPORTED).  A failed call leaves *out NULL and
+ *   nothing behind.  r3dm_stats is left as the call found it.
+ *
+ * Assignment.  a[g] = the word of row g under "Word of a row" above (first neighbour under the reference's distance, ties to the lowest
+ *   word), against the current words; it does not depend on how the rows are batched or on the tile path the context's switches select.
+ * Stop.  Iteration t = 0, 1, ... assigns and counts moved_t = #{g : a_t[g] != a_(t-1)[g]}, moved_0 = T.  If t > 0 and moved_t = 0 the
+ *   call stops there: converged, no update.  Otherwise the words are updated; after max_iterations updates the call stops.
+ * Members of word w.  The rows g with a[g] = w in ascending g; count = their number.
+ * Update, F32.  Per dimension the members are summed in double on a fixed tree: blocks of R3DM_VOCAB_TRAIN_BLOCK consecutive members are
+ *   each summed sequentially in member order starting from 0.0, then the block sums are added sequentially in block order starting from
+ *   0.0.  New element = (float)(sum / (double)count): an IEEE double division, rounded to nearest-even into f32.  There is no product, so
+ *   no FMA can enter.  (A restatement must add in this order: numpy's sum is pairwise, cumsum is sequential.)
+ * Update, U8.  Exact integer sums; byte = floor((2 sum + count) / (2 count)): a half rounds up.
+ * Update, BIN.  Per bit, ones = the members with the bit set; the bit is 1 iff 2 ones > count (a tie gives 0).
+ * Empty words.  A word without members keeps its row.
+ *
+ * r3dm_vocab_train_report: of the r3dm_vocab_train call that made this vocabulary (all zero for any other vocabulary). */
+#define R3DM_VOCAB_TRAIN_BLOCK 256u
+typedef struct {
+    uint32_t n_updates;                /* updates run: <= max_iterations */
+    uint32_t converged;                /* 1: an assignment moved no row; 0: stopped by max_iterations */
+    uint64_t n_moved;                  /* moved_t of the last assignment */
+    uint64_t n_empty;                  /* words without members under the last assignment */
+    uint64_t max_members;              /* the largest member count under the last assignment */
+    uint64_t n_rows_assigned;          /* rows sent through the matcher, all assignments together */
+    double   ms_assign, ms_sort, ms_update;          /* HIP-event times of the three phases, summed over the iterations */
+} r3dm_vocab_train_stats;
+int  r3dm_vocab_train(r3dm_ctx* ctx, const r3dm_vocab* init, const uint32_t* view_ids, uint32_t n_views, uint32_t max_iterations, r3dm_vocab** out);
+int  r3dm_vocab_train_report(const r3dm_vocab* vocab, r3dm_vocab_train_stats* out);
+
+/* idf-weighted scores.  r3dm_vocab_set_weighting(vocab, R3DM_VOCAB_WEIGHT_IDF) changes how r3dm_propose_pairs on that vocabulary scores
+ * and ranks (r3dm_view_signatures is unaffected); R3DM_VOCAB_WEIGHT_COUNTS, the default, is the rule above.  Under IDF every call computes,
+ * from its own list of views:
+ *   N = the listed views with rows;  df[w] = those of them with h[w] > 0;  q[w] = 0 if df[w] = 0, else log2_q8(N, df[w])
+ *   log2_q8(N, df), an integer procedure for 256 log2(N / df), N >= df >= 1:
+ *     e = the largest integer with df 2^e <= N;  x = floor(N 2^(62 - e) / df) (Q1.62 in [2^62, 2^63), 128-bit numerator);  q = e;
+ *     eight times: x = (x x) >> 62 on the 128-bit product;  q = 2 q;  if x >= 2^63 then x >>= 1 and q += 1.
+ *     (q(N, N) = 0, q(8, 1) = 768, q(3, 2) = 149; a word present in every listed view weighs nothing.)
+ *   s(i, j) = sum_w q[w] min(h_i[w], h_j[w]);  W_i = sum_w q[w] h_i[w];  key(i, j) = floor(s 2^32 / min(W_i, W_j)) in u64
+ *   candidates: the listed views with W > 0; a view with W_i = 0 proposes nothing and is proposed by nobody.  Rank, union and scores_out
+ *   (u32) as above.  If any W_i >= 2^32 the call returns R3DM_ERR_UNSUPPORTED (this keeps s in u32 and s 2^32 in u64).
+ * r3dm_vocab_weights: q of the last r3dm_propose_pairs call on the vocabulary, n_words u32; all 1 under COUNTS or before any call. */
+#define R3DM_VOCAB_WEIGHT_COUNTS 0
+#define R3DM_VOCAB_WEIGHT_IDF    1
+int  r3dm_vocab_set_weighting(r3dm_vocab* vocab, int mode);
+int  r3dm_vocab_weights(const r3dm_vocab* vocab, uint32_t* q_out /* host, n_words */);
+
 /* ---- putative matching ----
  * pairs_ij: n_pairs x 2 view ids (I, J); J's rows are the queries, I's rows the dataset.
  * Descriptor lengths and speed: the tensor kernels serve float / byte rows of up to 64, 128, 144 and 256 elements (rows are padded

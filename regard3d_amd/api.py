@@ -58,7 +58,7 @@ EXPORTS = [
     "r3dm_set_half_prefix", "r3dm_get_half_prefix_counts", "r3dm_multi_set_half_prefix", "r3dm_multi_get_half_prefix_counts",
     "r3dm_detect_akaze_msurf", "r3dm_detect_akaze_msurf_batch",
     "r3dm_vocab_sample", "r3dm_vocab_from_rows", "r3dm_vocab_info", "r3dm_vocab_words", "r3dm_vocab_free", "r3dm_view_signatures", "r3dm_propose_pairs",
-    "r3dm_vocab_report",
+    "r3dm_vocab_report", "r3dm_vocab_train", "r3dm_vocab_train_report", "r3dm_vocab_set_weighting", "r3dm_vocab_weights",
 ]
 GUIDED_KIND = {"F": 0, "E": 1, "H": 2}
 STAGE_GUIDED_MATCHING = 32
@@ -73,6 +73,7 @@ VOCAB_MAX_WORDS, VOCAB_HIST_LDS_WORDS, VOCAB_WORD_CHUNK = 65536, 8192, 32      #
 LAYOUT_HEAD = 32                                  # R3DM_LAYOUT_HEAD
 LAYOUT_BUDGET = 64                                # R3DM_LAYOUT_BUDGET
 BUDGET_SELECT_CHUNK = 256                         # R3DM_BUDGET_SELECT_CHUNK
+STAGE_PROPOSAL_TRAINED = 16384                    # R3DM_STAGE_PROPOSAL_TRAINED: with STAGE_PAIR_PROPOSAL, 10 Lloyd updates of the sampled vocabulary + idf weights
 STAGE_MATCH_BUDGET = 8192                         # R3DM_STAGE_MATCH_BUDGET: r3dm_set_match_budget with max_rows 8,192 on every context of the stage
 DETECTORS = {"Fast-AKAZE": 0, "AKAZE": 1}       # R3DM_DETECTOR_FAST_AKAZE / R3DM_DETECTOR_AKAZE
 # the descriptor arms, the rows of csrc/descriptor_arms.hpp (tests/test_descriptor_arms.py holds the two to each other): name, id
@@ -157,6 +158,18 @@ class VocabStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class VocabTrainStats(C.Structure):
+    """r3dm_vocab_train_stats: the r3dm_vocab_train call that made a vocabulary"""
+    _fields_ = [("n_updates", C.c_uint32), ("converged", C.c_uint32), ("n_moved", C.c_uint64), ("n_empty", C.c_uint64), ("max_members", C.c_uint64),
+                ("n_rows_assigned", C.c_uint64), ("ms_assign", C.c_double), ("ms_sort", C.c_double), ("ms_update", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+VOCAB_WEIGHT_COUNTS, VOCAB_WEIGHT_IDF = 0, 1
+
+
 class Vocab:
     """r3dm_vocab (include/r3dm.h, "Pair proposal"): n_words rows of one type and length, and the signatures of the views counted
     against them.  Made by Context.vocab_sample / vocab_from_rows; close() releases it."""
@@ -173,6 +186,20 @@ class Vocab:
         rc = self._L.r3dm_vocab_words(self._h, out.ctypes.data)
         if rc != 0:
             raise R3dmError(f"r3dm_vocab_words -> {rc}")
+        return out
+
+    def set_weighting(self, mode: int):
+        """r3dm_vocab_set_weighting: VOCAB_WEIGHT_COUNTS (default) or VOCAB_WEIGHT_IDF for the propose_pairs calls on this vocabulary"""
+        rc = self._L.r3dm_vocab_set_weighting(self._h, int(mode))
+        if rc != 0:
+            raise R3dmError(f"r3dm_vocab_set_weighting -> {rc}")
+
+    def weights(self) -> np.ndarray:
+        """r3dm_vocab_weights: q[w] of the last propose_pairs call, [n_words] uint32 (all 1 under COUNTS)"""
+        out = np.zeros(self.n_words, np.uint32)
+        rc = self._L.r3dm_vocab_weights(self._h, out.ctypes.data)
+        if rc != 0:
+            raise R3dmError(f"r3dm_vocab_weights -> {rc}")
         return out
 
     def close(self):
@@ -345,11 +372,12 @@ class _DirView(C.Structure):
 
 def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0, dim: int = 144, dist_ratio: float = 0.6,
                         compute_F: bool = True, seed: int = 5489, f32_tiles: bool = False, mutual: bool = False, preemptive: bool = False,
-                        proposal: bool = False, symmetric_ratio: bool = False, budget: bool = False):
+                        proposal: bool = False, symmetric_ratio: bool = False, budget: bool = False, proposal_trained: bool = False):
     """R3DComputeMatches::computeMatches over a directory that holds every view's .feat / .desc (r3dm_compute_matches_dir_flags):
     exhaustive matching, the F filter when asked, matches.putative.txt / matches.f.txt.  views: dicts with id, width, height,
     basename; dtype: F32 / U8 / BIN; mutual: R3DM_STAGE_MUTUAL_MATCHING; preemptive: R3DM_STAGE_PREEMPTIVE_MATCHING (the .feat scale column is
-    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL; symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO; budget: R3DM_STAGE_MATCH_BUDGET (8,192 rows
+    every view's priority); proposal: R3DM_STAGE_PAIR_PROPOSAL; proposal_trained: R3DM_STAGE_PROPOSAL_TRAINED (with proposal: the
+    vocabulary is trained for at most 10 updates and the scores are idf-weighted); symmetric_ratio: R3DM_STAGE_SYMMETRIC_RATIO; budget: R3DM_STAGE_MATCH_BUDGET (8,192 rows
     per view, priority = the .feat scale column).  -> (putative pairs, geometric pairs)"""
     L = load_library()
     arr = (_DirView * len(views))(*[_DirView(int(v["id"]), int(v["width"]), int(v["height"]), str(v["basename"]).encode()) for v in views])
@@ -359,8 +387,8 @@ def compute_matches_dir(device_id: int, matches_dir: str, views, dtype: int = 0,
                                                  C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.c_char_p, C.c_size_t]
     rc = L.r3dm_compute_matches_dir_flags(device_id, matches_dir.encode(), arr, len(views), dtype, dim, dist_ratio, int(compute_F), seed,
                                           (8 if f32_tiles else 0) | (STAGE_MUTUAL_MATCHING if mutual else 0) | (STAGE_PREEMPTIVE_MATCHING if preemptive else 0)
-                                          | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | (STAGE_MATCH_BUDGET if budget else 0),
-                                          C.byref(npp), C.byref(ngp), err, 1024)
+                                          | (STAGE_PAIR_PROPOSAL if proposal else 0) | (STAGE_SYMMETRIC_RATIO if symmetric_ratio else 0) | (STAGE_MATCH_BUDGET if budget else 0)
+                                          | (STAGE_PROPOSAL_TRAINED if proposal_trained else 0), C.byref(npp), C.byref(ngp), err, 1024)
     if rc != 0:
         raise R3dmError(f"r3dm_compute_matches_dir_flags -> {rc}: {err.value.decode()}")
     return int(npp.value), int(ngp.value)
@@ -514,6 +542,10 @@ def load_library():
     L.r3dm_view_signatures.argtypes = [vp, vp, vp, u32, vp]
     L.r3dm_propose_pairs.argtypes = [vp, vp, vp, u32, u32, vp, C.c_uint64, C.POINTER(C.c_uint64), vp]
     L.r3dm_vocab_report.argtypes = [vp, vp]
+    L.r3dm_vocab_train.argtypes = [vp, vp, vp, u32, u32, C.POINTER(vp)]
+    L.r3dm_vocab_train_report.argtypes = [vp, vp]
+    L.r3dm_vocab_set_weighting.argtypes = [vp, C.c_int]
+    L.r3dm_vocab_weights.argtypes = [vp, vp]
     L.r3dm_index_create.argtypes = [vp, vp, u32, u32, C.c_int, C.POINTER(vp)]
     L.r3dm_index_knn2.argtypes = [vp, vp, vp, u32, vp, vp]
     L.r3dm_index_destroy.argtypes = [vp]; L.r3dm_index_destroy.restype = None
@@ -1683,6 +1715,23 @@ class Context:
         rc = self._L.r3dm_vocab_report(vocab._h, C.byref(s))
         if rc != 0:
             raise R3dmError(f"r3dm_vocab_report -> {rc}")
+        return s.as_dict()
+
+    def vocab_train(self, init: Vocab, view_ids, max_iterations: int) -> Vocab:
+        """r3dm_vocab_train: Lloyd's iterations on the device over every row of the listed views, starting from `init` (left as it is);
+        the new vocabulary has init's type, length and word count and no signatures.  The rule is in include/r3dm.h"""
+        ids = np.ascontiguousarray(view_ids, np.uint32).reshape(-1)
+        h = C.c_void_p()
+        self._check(self._L.r3dm_vocab_train(self._h, init._h, _ptr(ids) if ids.size else None, ids.size, max_iterations, C.byref(h)), "r3dm_vocab_train")
+        return Vocab(self._L, h.value)
+
+    def vocab_train_report(self, vocab: Vocab) -> dict:
+        """r3dm_vocab_train_report: updates run, converged, moved / empty / largest member count of the last assignment, rows assigned
+        and the HIP-event times of assignment, sort and update of the r3dm_vocab_train call that made `vocab`"""
+        s = VocabTrainStats()
+        rc = self._L.r3dm_vocab_train_report(vocab._h, C.byref(s))
+        if rc != 0:
+            raise R3dmError(f"r3dm_vocab_train_report -> {rc}")
         return s.as_dict()
 
     def set_split_mfma(self, enable: bool = True):

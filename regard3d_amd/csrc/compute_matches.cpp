@@ -465,6 +465,11 @@ void R3DComputeMatches::setPairProposal(bool on, uint32_t n_words, uint32_t top_
     proposal_words_ = n_words; proposal_top_k_ = top_k;
 }
 
+void R3DComputeMatches::setPairProposalTraining(uint32_t max_iterations, bool idf)
+{
+    proposal_train_iterations_ = max_iterations; proposal_idf_ = idf;
+}
+
 void R3DComputeMatches::setGuidedMatching(bool on, double ratio_F, double ratio_E, double ratio_H) { Devices{ctx_, multi_}.set_guided(on, ratio_F, ratio_E, ratio_H); }
 
 void R3DComputeMatches::setRegionsType(r3dm_dtype dtype, uint32_t dim) { dtype_ = dtype; dim_ = dim; }
@@ -556,6 +561,13 @@ bool R3DComputeMatches::listPairs(std::vector<uint32_t>& pairs)
             r3dm_ctx* pc = Devices{ctx_, multi_}.first_ctx();
             r3dm_vocab* vocab = nullptr;
             int rcp = r3dm_vocab_sample(pc, ids.data(), (uint32_t)ids.size(), n_words, &vocab);
+            if (rcp == R3DM_OK && proposal_train_iterations_) {
+                // trained on the views it was sampled from; the sample is the start and is given back
+                r3dm_vocab* trained = nullptr;
+                rcp = r3dm_vocab_train(pc, vocab, ids.data(), (uint32_t)ids.size(), proposal_train_iterations_, &trained);
+                if (rcp == R3DM_OK) { r3dm_vocab_free(vocab); vocab = trained; }
+            }
+            if (rcp == R3DM_OK && proposal_idf_) rcp = r3dm_vocab_set_weighting(vocab, R3DM_VOCAB_WEIGHT_IDF);
             std::vector<uint32_t> proposed(2 * ids.size() * (size_t)proposal_top_k_);
             uint64_t n_proposed = 0;
             if (rcp == R3DM_OK) rcp = r3dm_propose_pairs(pc, vocab, ids.data(), (uint32_t)ids.size(), proposal_top_k_, proposed.data(), proposed.size() / 2, &n_proposed, nullptr);
@@ -789,6 +801,7 @@ static void apply_stage_flags(r3d_amd::R3DComputeMatches& stage, uint32_t flags,
     if (mask & R3DM_STAGE_PREEMPTIVE_MATCHING) stage.setPreemptiveMatching(has(R3DM_STAGE_PREEMPTIVE_MATCHING));
     if (mask & R3DM_STAGE_MATCH_BUDGET) stage.setMatchBudget(has(R3DM_STAGE_MATCH_BUDGET));
     if (mask & R3DM_STAGE_PAIR_PROPOSAL) stage.setPairProposal(has(R3DM_STAGE_PAIR_PROPOSAL));
+    if (mask & R3DM_STAGE_PROPOSAL_TRAINED) stage.setPairProposalTraining(has(R3DM_STAGE_PROPOSAL_TRAINED) ? 10 : 0, has(R3DM_STAGE_PROPOSAL_TRAINED));
 }
 
 extern "C" int r3dm_stage_run(r3dm_stage* sp, const char* matches_dir, const r3dm_view_image* views, uint32_t n_views,
@@ -885,7 +898,7 @@ extern "C" int r3dm_compute_matches_dir_flags(int device_id, const char* matches
     stage.addViews(vs);
     stage.setRegionsType(dtype, dim);
     stage.setSeed(seed);
-    apply_stage_flags(stage, flags, R3DM_STAGE_F32_TILES | R3DM_STAGE_MUTUAL_MATCHING | R3DM_STAGE_SYMMETRIC_RATIO | R3DM_STAGE_PREEMPTIVE_MATCHING | R3DM_STAGE_MATCH_BUDGET | R3DM_STAGE_PAIR_PROPOSAL);
+    apply_stage_flags(stage, flags, R3DM_STAGE_F32_TILES | R3DM_STAGE_MUTUAL_MATCHING | R3DM_STAGE_SYMMETRIC_RATIO | R3DM_STAGE_PREEMPTIVE_MATCHING | R3DM_STAGE_MATCH_BUDGET | R3DM_STAGE_PAIR_PROPOSAL | R3DM_STAGE_PROPOSAL_TRAINED);
     r3d_amd::R3DFParams params;
     params.distRatio_ = dist_ratio;
     params.computeFundalmentalMatrix_ = compute_F != 0;

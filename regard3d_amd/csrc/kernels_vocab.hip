@@ -10,9 +10,13 @@
 //   vocab_intersect_kernel      s(i, j) = sum_w min(h_i[w], h_j[w]) for all pairs of the listed views: a workgroup owns a 64 x 64 tile
 //                               of (view, view) and a slice of the word axis, streams the slice through LDS 32 words at a time, a lane
 //                               holds a 4 x 4 block of the tile in registers (8 x ds_read_b128 per 64 min-adds), and adds its u32 sums
-//                               to the score matrix with integer atomics.  Only tiles on or above the diagonal run: s is symmetric
+//                               to the score matrix with integer atomics.  Only tiles on or above the diagonal run: s is symmetric.
+//                               <IDF>: every min is multiplied by the word's weight q[w] (r3dm_vocab_set_weighting), staged beside the tile
+//   vocab_df_kernel             df[w] = the number of listed views with h[w] > 0: what the host turns into the weights
+//   vocab_weight_sum_kernel     W_i = sum_w q[w] h_i[w] in u64: the normaliser vocab_select_kernel is handed under IDF, where it is
+//                               handed the row counts otherwise
 //   vocab_select_kernel         one workgroup per view: top_k times the smallest composite ((2^32 - key) << 31) | rank not yet taken,
-//                               key = floor(s 2^32 / min(n_i, n_j)) in u64, rank = the candidate's place in view-id order
+//                               key = floor(s 2^32 / min(n_i, n_j)) in u64 (n = row counts, or the W under IDF), rank = the candidate's place in view-id order
 #include "kernels_match_common.hpp"
 
 namespace r3dm {
@@ -54,6 +58,7 @@ hipError_t launch_vocab_hist(hipStream_t st, const VocabHistJob* jobs, uint32_t 
     return hipGetLastError();
 }
 
+template <bool IDF>
 __global__ __launch_bounds__(256)
 void vocab_intersect_kernel(const VocabScoreParams P)
 {
@@ -62,6 +67,7 @@ void vocab_intersect_kernel(const VocabScoreParams P)
     // ds_read_b128 lane group reads lie on disjoint banks
     constexpr uint32_t S = kVocabChunk + 4;
     __shared__ u32x4 a4[kVocabTile * S / 4], b4[kVocabTile * S / 4];
+    __shared__ u32x4 q4[IDF ? kVocabChunk / 4 : 1];            // IDF: the weights of the stage's words
     uint32_t* a = reinterpret_cast<uint32_t*>(a4);
     uint32_t* b = reinterpret_cast<uint32_t*>(b4);
     const uint32_t V = P.n_views;
@@ -90,6 +96,8 @@ void vocab_intersect_kernel(const VocabScoreParams P)
             const u32x4 v = (in && src[k]) ? *reinterpret_cast<const u32x4*>(src[k] + w0 + lc) : u32x4{0u, 0u, 0u, 0u};
             *reinterpret_cast<u32x4*>((k < 2 ? a : b) + (lr + 32u * (uint32_t)(k & 1)) * S + lc) = v;
         }
+        if (IDF && threadIdx.x < kVocabChunk / 4)
+            q4[threadIdx.x] = w0 + threadIdx.x * 4u < w_end ? *reinterpret_cast<const u32x4*>(P.q + w0 + threadIdx.x * 4u) : u32x4{0u, 0u, 0u, 0u};
         r3dm_syncthreads();
 #pragma unroll
         for (uint32_t k = 0; k < kVocabChunk; k += 4) {
@@ -103,7 +111,10 @@ void vocab_intersect_kernel(const VocabScoreParams P)
 #pragma unroll
                 for (int c = 0; c < 4; ++c)
 #pragma unroll
-                    for (int e = 0; e < 4; ++e) acc[r][c] += av[r][e] < bv[c][e] ? av[r][e] : bv[c][e];
+                    for (int e = 0; e < 4; ++e) {
+                        const uint32_t m = av[r][e] < bv[c][e] ? av[r][e] : bv[c][e];
+                        if (IDF) acc[r][c] += q4[k / 4][e] * m; else acc[r][c] += m;
+                    }
         }
     }
 #pragma unroll
@@ -122,7 +133,51 @@ hipError_t launch_vocab_intersect(hipStream_t st, const VocabScoreParams& P, uin
     if (P.n_views == 0) return hipSuccess;
     const uint32_t nt = (P.n_views + kVocabTile - 1) / kVocabTile;
     if (nt > 65535u || n_slices == 0 || n_slices > 65535u || (P.stride & 3u) || (P.words_per_z % kVocabChunk)) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(vocab_intersect_kernel, dim3(nt, nt, n_slices), dim3(256), 0, st, P);
+    if (P.q) hipLaunchKernelGGL(vocab_intersect_kernel<true>, dim3(nt, nt, n_slices), dim3(256), 0, st, P);
+    else hipLaunchKernelGGL(vocab_intersect_kernel<false>, dim3(nt, nt, n_slices), dim3(256), 0, st, P);
+    return hipGetLastError();
+}
+
+// one thread per word: df[w] = the number of listed views whose signature holds word w
+__global__ __launch_bounds__(256)
+void vocab_df_kernel(const uint32_t* __restrict__ sig, const uint32_t* __restrict__ sig_row, uint32_t stride, uint32_t n_views, uint32_t n_words,
+                     uint32_t* __restrict__ df)
+{
+    const uint32_t w = blockIdx.x * 256u + threadIdx.x;
+    if (w >= n_words) return;
+    uint32_t n = 0;
+    for (uint32_t v = 0; v < n_views; ++v) n += sig[(size_t)sig_row[v] * stride + w] != 0u;
+    df[w] = n;
+}
+
+// one workgroup per view: W[v] = sum_w q[w] h_v[w] in u64 (integer adds: the order of the reduction does not matter)
+__global__ __launch_bounds__(256)
+void vocab_weight_sum_kernel(const uint32_t* __restrict__ sig, const uint32_t* __restrict__ sig_row, uint32_t stride, uint32_t n_words,
+                             const uint32_t* __restrict__ q, unsigned long long* __restrict__ W)
+{
+    __shared__ unsigned long long wave_sum[4];
+    const uint32_t* h = sig + (size_t)sig_row[blockIdx.x] * stride;
+    unsigned long long s = 0;
+    for (uint32_t w = threadIdx.x; w < n_words; w += 256) s += (unsigned long long)q[w] * h[w];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    if ((threadIdx.x & 63u) == 0) wave_sum[threadIdx.x >> 6] = s;
+    r3dm_syncthreads();
+    if (threadIdx.x == 0) W[blockIdx.x] = wave_sum[0] + wave_sum[1] + wave_sum[2] + wave_sum[3];
+}
+
+hipError_t launch_vocab_df(hipStream_t st, const uint32_t* sig, const uint32_t* sig_row, uint32_t stride, uint32_t n_views, uint32_t n_words, uint32_t* df)
+{
+    if (n_words == 0) return hipSuccess;
+    hipLaunchKernelGGL(vocab_df_kernel, dim3((n_words + 255u) / 256u), dim3(256), 0, st, sig, sig_row, stride, n_views, n_words, df);
+    return hipGetLastError();
+}
+
+hipError_t launch_vocab_weight_sums(hipStream_t st, const uint32_t* sig, const uint32_t* sig_row, uint32_t stride, uint32_t n_views, uint32_t n_words,
+                                    const uint32_t* q, unsigned long long* W)
+{
+    if (n_views == 0) return hipSuccess;
+    hipLaunchKernelGGL(vocab_weight_sum_kernel, dim3(n_views), dim3(256), 0, st, sig, sig_row, stride, n_words, q, W);
     return hipGetLastError();
 }
 

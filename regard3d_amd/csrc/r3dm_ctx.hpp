@@ -5,7 +5,7 @@
 //                     (cert_slack_factor), one index mount (mount_index_beside_queries), one k <= 2 detour (knn_by_knn2)
 //   api_preselect.cpp preemptive matching: view priorities, heads, the gate behind resolve_pairs, r3dm_preselect_pairs
 //   api_budget.cpp    the match budget: device selection of a view's rows, sub-view slots, the substitution behind the gate, the remap
-//   api_vocab.cpp     pair proposal: vocabularies, view signatures through the exhaustive matcher, scores, top-k selection
+//   api_vocab.cpp     pair proposal: vocabularies and their training, view signatures through the exhaustive matcher, scores, top-k selection
 //   api_ann.cpp       what the approximate matchers share -- pair resolution (resolve_pairs, also the exhaustive matcher's), the collection
 //                     call (match_collection_ann), the search batch (run_ann_batch) -- and the graph matcher (KGraph arms 0-4)
 //   api_hnsw.cpp, api_mrpt.cpp   the HNSW arms 6-8 and the MRPT arm 5 on those frames: index build, search launch, their rules

@@ -371,10 +371,31 @@ struct VocabScoreParams {
     uint32_t        stride, n_views;
     uint32_t        words_per_z;  // words of a workgroup's slice of the word axis (a multiple of kVocabChunk)
     uint32_t*       scores;       // [n_views][n_views], zeroed by the host; the diagonal stays 0
+    const uint32_t* q;            // [stride] word weights (R3DM_VOCAB_WEIGHT_IDF; zero past n_words), or nullptr: plain counts
+};
+// vocabulary training (kernels_vocab_train.hip; r3dm_vocab_train)
+constexpr uint32_t kVocabTrainBlock = 256;          // members of a word summed sequentially before the block sums are; R3DM_VOCAB_TRAIN_BLOCK
+struct VocabAssignJob {
+    const int32_t* idx;           // a view's 2-lists as the matcher leaves them: [n][2], entry 0 = the row's word
+    uint32_t       n;             // rows of the view
+    uint32_t       g0;            // global row of the view's first row
+};
+struct VocabTrainParams {
+    const void* const* views;     // [n_views]: fragment-order f32 tiles (float / byte views) or word rows (binary views)
+    const uint2*    loc;          // [T]: (view, local row) of the members in sorted order
+    const uint2*    blocks;       // [n_blocks]: (first member, members <= kVocabTrainBlock) of a block
+    const uint32_t* first_block;  // [n_words + 1]: the first block of every word
+    const uint32_t* counts;       // [n_words]: members of every word
+    uint32_t        n_blocks, n_words, dim;
+    uint32_t        row_units;    // float4 per padded row of the tiles (2 G), or u32 words per binary row
+    uint32_t        pieces;       // of them, those that hold elements: ceil(dim / 4) float4, or all words
+    double*         block_sums;   // [n_blocks][pieces * 4]
+    uint32_t*       block_bits;   // [n_blocks][pieces * 32] (binary)
+    void*           words;        // [n_words][dim] of the vocabulary's type
 };
 struct VocabSelectParams {
     const uint32_t* scores;       // [n_views][n_views]
-    const uint32_t* n_rows;       // [n_views]: rows of every listed view
+    const uint32_t* n_rows;       // [n_views]: rows of every listed view (R3DM_VOCAB_WEIGHT_IDF: its W = sum_w q[w] h[w])
     const uint32_t* rank;         // [n_views]: place of every listed view in view-id order
     uint32_t        n_views, top_k;
     uint32_t*       sel;          // [n_views][top_k]: ranks of the picks in order, kNone behind the last candidate
@@ -666,6 +687,14 @@ hipError_t launch_budget_remap(hipStream_t st, const BudgetRemapParams& P, uint3
 hipError_t launch_vocab_hist(hipStream_t st, const VocabHistJob* jobs, uint32_t n_jobs, uint32_t max_n, uint32_t n_words);
 hipError_t launch_vocab_intersect(hipStream_t st, const VocabScoreParams& P, uint32_t n_slices);
 hipError_t launch_vocab_select(hipStream_t st, const VocabSelectParams& P);
+hipError_t launch_vocab_df(hipStream_t st, const uint32_t* sig, const uint32_t* sig_row, uint32_t stride, uint32_t n_views, uint32_t n_words, uint32_t* df);
+hipError_t launch_vocab_weight_sums(hipStream_t st, const uint32_t* sig, const uint32_t* sig_row, uint32_t stride, uint32_t n_views, uint32_t n_words,
+                                    const uint32_t* q, unsigned long long* W);
+hipError_t launch_vocab_assign(hipStream_t st, const VocabAssignJob* jobs, uint32_t n_jobs, uint32_t max_n, uint32_t* assign, unsigned int* moved);
+hipError_t launch_vocab_sort_keys(hipStream_t st, const uint32_t* assign, uint32_t T, uint32_t* keys, uint32_t* vals);
+hipError_t launch_vocab_locate(hipStream_t st, const uint32_t* order, uint32_t T, const uint32_t* base, uint32_t n_views, uint2* loc);
+hipError_t launch_vocab_block_sums(hipStream_t st, const VocabTrainParams& P, r3dm_dtype dtype);
+hipError_t launch_vocab_update(hipStream_t st, const VocabTrainParams& P, r3dm_dtype dtype);
 hipError_t launch_finalize(hipStream_t st, const FinalizeParams& P);
 hipError_t launch_filter_F(hipStream_t st, const FilterParams& P);
 hipError_t launch_filter_E(hipStream_t st, const FilterParams& P, size_t lds);   // the E kernels of launch_filter_F (kernels_filter_e.hip)

@@ -1,9 +1,12 @@
 """Measurement of pair proposal on one MI355X (profiles/vocab_perf.txt):
-    python tools/vocab_perf.py <n_views> <exhaustive 0|1> [<output file>]
+    python tools/vocab_perf.py <n_views> <exhaustive 0|1> [<output file> [train]]
 bench.py's synthetic SIFT-128 views (8,192 rows each): HIP-event times of the phases of r3dm_propose_pairs at 4,096 and 16,384 words,
 top_k 20; the fraction of pairs proposed; recall of the pairs with F-inliers in an exhaustive run (exhaustive = 1) or of the pairs of
 views that share features in the scene (0: sizes at which a pass over all pairs is too long); r3dm_match_pairs on all pairs and on
-the proposed ones; the preemptive gate on the same views."""
+the proposed ones; the preemptive gate on the same views.
+With `train` (profiles/vocab_train_perf.txt) instead: r3dm_vocab_train from the sampled vocabulary, 10
+iterations, at both word counts -- HIP-event ms per iteration of assignment, sort and update, the update's bytes per second -- and the
+recall of the same target at top_k 2, 4, 8 and 20 for the sampled, the trained and the trained + idf-weighted vocabulary."""
 import os
 import sys
 import time
@@ -59,6 +62,40 @@ if exhaustive:
     say(f"exhaustive run: {g.num_pairs} putative pairs, {len(inlier_pairs)} pairs with F inliers ({100.0 * len(inlier_pairs) / len(allp):.2f} % of all pairs)")
 target = inlier_pairs if inlier_pairs is not None else truth
 target_name = "pairs with F inliers in the exhaustive run" if inlier_pairs is not None else "pairs of views that share features (scene truth; no exhaustive run at this size)"
+
+HBM_BYTES_PER_S = 8.0e12                                            # MI355X HBM3E peak
+
+for n_words in (4096, 16384) if len(sys.argv) > 4 and sys.argv[4] == "train" else ():
+    init = ctx.vocab_sample(ids, n_words)
+    reps = []
+    for it in range(4):                                             # the first is the warm-up
+        v = ctx.vocab_train(init, ids, 10)
+        r = ctx.vocab_train_report(v)
+        if it:
+            reps.append(r)
+        if it < 3:
+            v.close()
+    n_assign = reps[0]["n_rows_assigned"] // (n_views * 8192)
+    n_upd = reps[0]["n_updates"]
+    a, s_, u = (med([r[k] for r in reps]) for k in ("ms_assign", "ms_sort", "ms_update"))
+    row_bytes = n_views * 8192 * 128 * 4
+    say(f"n_words {n_words} train 10: {n_upd} updates, {n_assign} assignments, converged {reps[0]['converged']}, moved at the last {reps[0]['n_moved']}, "
+        f"empty {reps[0]['n_empty']}, largest word {reps[0]['max_members']}")
+    say(f"  per iteration: assignment {a / n_assign:.2f} ms, sort {s_ / n_upd:.3f} ms, update {u / n_upd:.3f} ms (HIP events, medians of 3 after a warm-up); "
+        f"sort + update {'<' if (s_ + u) / n_upd < a / n_assign else '>='} assignment")
+    say(f"  update reads {row_bytes / 1e9:.3f} GB of rows: {row_bytes / (u / n_upd * 1e-3) / 1e12:.3f} TB/s, {100.0 * row_bytes / (u / n_upd * 1e-3) / HBM_BYTES_PER_S:.1f} % of {HBM_BYTES_PER_S / 1e12:.0f} TB/s")
+    for name, vv, idf in (("sampled", init, False), ("trained", v, False), ("trained + idf", v, True)):
+        vv.set_weighting(api.VOCAB_WEIGHT_IDF if idf else api.VOCAB_WEIGHT_COUNTS)
+        cells = []
+        for top_k in (2, 4, 8, 20):
+            ps = {(int(x), int(y)) for x, y in ctx.propose_pairs(vv, ids, top_k)}
+            cells.append(f"top_k {top_k}: {len(ps & target) / max(len(target), 1):.4f} ({len(ps)} pairs)")
+        say(f"  recall of the {target_name}, {name}: " + ", ".join(cells))
+    v.close(); init.close()
+if len(sys.argv) > 4 and sys.argv[4] == "train":
+    ctx.close()
+    out.close()
+    sys.exit(0)
 
 for n_words in (4096, 16384):
     reps = []
