@@ -210,10 +210,14 @@ def _l2sq(rows, q):
     return acc
 
 
-def mrpt_model(ex, d0, q, n_trees, depth, votes, k):
+def mrpt_model(ex, d0, q, n_trees, depth, votes, k, route_strict=False, rerank_high=False):
     """Mrpt::query(q, k, votes) on the arrays of orc_mrpt_export, then ArrayMatcher_mrpt::SearchNeighbours' retry and drop rules with
     NN = k (matcher_mrpt.h:207-243).  -> rows [nq, k], sqrtf distances [nq, k], n_elected of the attempt that answered [nq],
-    class [nq]: 0 = k rows elected at the first attempt, 1 = only by the retry, 2 = dropped"""
+    class [nq]: 0 = k rows elected at the first attempt, 1 = only by the retry, 2 = dropped, n_elected of the FIRST attempt [nq] (the
+    rows measured for a query are those of the first attempt plus, where a retry ran -- fewer than k of them and votes > 1 -- the third
+    value).
+    route_strict / rerank_high: two WRONG variants (`<` for `<=` at a split; equal distances to the higher row) for the tests that show
+    a case table would notice them (tests/test_mrpt_cases.py)"""
     R, splits, leaves, leaf_first = ex["R"], ex["splits"], ex["leaves"], ex["leaf_first"]
     n, dim = d0.shape
     nq = len(q)
@@ -223,17 +227,19 @@ def mrpt_model(ex, d0, q, n_trees, depth, votes, k):
         pq = pq + R[None, :, c] * q[:, c, None]
     n_inner = (1 << depth) - 1
     idx = np.full((nq, k), -1, np.int32); dist = np.full((nq, k), -1.0, np.float32)
-    ne_out = np.zeros(nq, np.uint32); cls = np.zeros(nq, np.int32)
+    ne_out = np.zeros(nq, np.uint32); cls = np.zeros(nq, np.int32); ne_first = np.zeros(nq, np.uint32)
     for r in range(nq):
         tally = np.zeros(n, np.int32)
         for t in range(n_trees):
             node = 0
             for d in range(depth):                                       # mrpt.c:176-180
-                node = 2 * node + 1 if pq[r, t * depth + d] <= splits[t, node] else 2 * node + 2
+                left = pq[r, t * depth + d] < splits[t, node] if route_strict else pq[r, t * depth + d] <= splits[t, node]
+                node = 2 * node + 1 if left else 2 * node + 2
             leaf = node - n_inner
             tally[leaves[t, leaf_first[leaf]:leaf_first[leaf + 1]]] += 1
         need = votes
         elected = np.where(tally >= need)[0]
+        ne_first[r] = len(elected)
         if len(elected) < k and need > 1:                                # "Try again" with votes - 1
             cls[r] = 1
             need -= 1
@@ -243,9 +249,9 @@ def mrpt_model(ex, d0, q, n_trees, depth, votes, k):
             cls[r] = 2
             continue
         d2 = _l2sq(d0[elected], q[r])
-        o = np.lexsort((elected, d2))[:k]
+        o = np.lexsort((-elected if rerank_high else elected, d2))[:k]
         idx[r] = elected[o]; dist[r] = np.sqrt(d2[o])
-    return idx, dist, ne_out, cls
+    return idx, dist, ne_out, cls, ne_first
 
 
 MRPT_VOTES = (4, 1)      # 4: the three classes below; 1: a hundred and more elected rows, several per lane of the re-rank
@@ -286,14 +292,14 @@ def _mrpt_case(oracle_mod, votes, k):
 @pytest.mark.parametrize("votes", MRPT_VOTES)
 def test_mrpt_model_is_the_restatement_at_k2(oracle, votes):
     """CPU: the numpy model against orc_mrpt_knn2 -- rows, distance bits, n_elected"""
-    mi, md, mne, _ = _mrpt_case(oracle, votes, 2)
+    mi, md, mne, _, _ = _mrpt_case(oracle, votes, 2)
     ei, ed, ene = _mrpt_index(oracle).knn2(_mrpt_views()[1], votes)
     assert np.array_equal(mi, ei) and np.array_equal(_bits(md), _bits(ed)) and np.array_equal(mne, ene)
 
 
 def test_mrpt_scene_holds_the_three_classes(oracle):
     """CPU: at k = 8 and votes 4 some queries elect 8 rows at once, some only with votes - 1, some are dropped"""
-    _, _, ne, cls = _mrpt_case(oracle, 4, 8)
+    _, _, ne, cls, _ = _mrpt_case(oracle, 4, 8)
     assert all((cls == c).sum() >= 20 for c in (0, 1, 2)), np.bincount(cls, minlength=3)
     assert _mrpt_case(oracle, 1, 8)[2].min() > 64              # votes 1: lanes of the re-rank hold several rows each
 
@@ -303,7 +309,7 @@ def test_mrpt_scene_holds_the_three_classes(oracle):
 @pytest.mark.parametrize("votes", MRPT_VOTES)
 def test_mrpt_equals_the_model(ctx, oracle, votes, k):
     d0, d1 = _mrpt_views()
-    mi, md, _, cls = _mrpt_case(oracle, votes, k)
+    mi, md, _, cls, _ = _mrpt_case(oracle, votes, k)
     gi, gd = ctx.mrpt_knn(d0, d1, _mrpt_params(votes), k)
     assert np.array_equal(gi, mi)
     assert np.array_equal(_bits(gd), _bits(md))
@@ -354,7 +360,7 @@ def _mrpt_big_case(oracle_mod, k):
 
 def test_mrpt_model_is_the_restatement_at_k2_above_64k_lds(oracle):
     """CPU: the numpy model against orc_mrpt_knn2 on the 12,288-row scene -- rows, distance bits, n_elected"""
-    mi, md, mne, cls = _mrpt_big_case(oracle, 2)
+    mi, md, mne, cls, _ = _mrpt_big_case(oracle, 2)
     ei, ed, ene = _mrpt_big_index(oracle).knn2(_mrpt_big_views()[1], MRPT_BIG_VOTES)
     assert np.array_equal(mi, ei) and np.array_equal(_bits(md), _bits(ed)) and np.array_equal(mne, ene)
     assert (cls != 2).sum() >= MRPT_BIG_QUERIES // 2, "most queries are answered: the comparison is about rows, not about -1"
@@ -365,7 +371,7 @@ def test_mrpt_model_is_the_restatement_at_k2_above_64k_lds(oracle):
 def test_mrpt_above_64k_lds_equals_the_model(ctx, oracle, k):
     """k = 2 is the 2-NN call (mrpt_knn2: the kernel's 2-NN tail), k = 3 the k-list tail; each raises its own kernel's LDS limit"""
     d0, d1 = _mrpt_big_views()
-    mi, md, _, _ = _mrpt_big_case(oracle, k)
+    mi, md, _, _, _ = _mrpt_big_case(oracle, k)
     gi, gd = ctx.mrpt_knn2(d0, d1, _mrpt_params(MRPT_BIG_VOTES)) if k == 2 else ctx.mrpt_knn(d0, d1, _mrpt_params(MRPT_BIG_VOTES), k)
     assert np.array_equal(gi, mi)
     assert np.array_equal(_bits(gd), _bits(md))
